@@ -8,7 +8,7 @@ configs[1]: random A*B=C gates, BLS12-381), one process per GPU.
 A step = one complete create_proof_with_assignment (prover.rs:66-237) FROM HOST INPUTS, as benches/bench.rs:79 times
 it and SURVEY.md §8d defines the metric: scalar H2D (x, w from pinned host memory), witness map, NTTs, the three merged
 MSMs, both Fiat-Shamir hashes; the proving key (bases + matrices + window tables) is resident in HBM before the timed
-region.  `ms_per_step_hbm_resident` / `value_hbm_resident` in the same line are the variant with the assignment already in
+region.  `ms_per_step_hbm_resident` / `value_hbm_resident` (with --full) are the variant with the assignment already in
 HBM (pm_prove_phase1_device).  With N > 1 ONE proof is spread over the N GPUs (layout "vector": witness map, four-step
 NTT with one all-to-all per transform, scans and MSM pairs sharded; the ranks joined by a pm_comm = RCCL inside the
 library), so scaling is "strong".
@@ -18,11 +18,21 @@ GPU, a failing or stalled rank ends the attempt (fail-fast collectives in the li
 layer falls back RCCL -> host-staged torch.distributed until one configuration completes; the JSON line says which ran
 (`config.exchange`, `n_ranks_seen`).
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: the MSM bucket accumulation,
-HIP-event timed on the library's stream), `cpu_baseline` (the CPU restatement oracle/cpp proving the SAME
-2^20-100-gate circuit on this box's host cores, once; "CPU restatement -- not arkworks") and
-`msm_micro` (the metric's second half: standalone resident G1 MSM pairs/s at 2^20 ... 2^26 pairs), `ntt_micro` (standalone
-resident transforms at 2^21, 2^22, 2^24) and `stages` (per stage ms, algorithmic GB/s / 8 TB/s, lane-mads/s / peak).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, `proof_bytes` of the last timed step); nothing else runs.
+
+  --dump-outputs DIR   after the timed steps, writes the proof the last timed step returned (Proof::serialize_compressed
+                       bytes) as DIR/proof.npy (one float32 per byte) and DIR/proof_bits.npy (one float32 0 / 1 per bit, LSB
+                       first); the inputs are seeded, so two builds can be compared output for output
+  --full               everything else the line used to carry: the HBM-resident and phase-by-phase variants, `roofline`
+                       (dominant kernel: the MSM bucket accumulation, HIP-event timed on the library's stream, traffic from
+                       rocprofv3 --pmc child passes), `valu`, `stages` (per stage ms, algorithmic GB/s / 8 TB/s,
+                       lane-mads/s / peak), `proof_verified`, `throughput_in_flight`, `cpu_baseline` (the CPU restatement
+                       oracle/cpp proving the SAME 2^20-100-gate circuit on this box's host cores, once; "CPU restatement -- not
+                       arkworks"), `ntt_micro` (standalone resident transforms at 2^21, 2^22, 2^24), `msm_micro`
+                       (the metric's second half: standalone resident G1 MSM pairs/s at 2^20 ... 2^26 pairs) and `other_configs`
+                       (BN254 @ 2^20, BLS12-381 @ 2^22 and @ 2^24); the --no-* / --*-micro / --other-configs / --inflight
+                       options trim those legs.
 """
 import argparse
 import json
@@ -152,7 +162,7 @@ def live_traffic(args, timeout_s=None):
     for ctr in ("FETCH_SIZE", "WRITE_SIZE", "GRBM_GUI_ACTIVE"):
         d = tempfile.mkdtemp(prefix="pm_pmc_", dir="/tmp")
         cmd = [exe, "--kernel-trace", "--pmc", ctr, "--output-format", "csv", "-d", d, "-o", "run", "--", sys.executable,
-               os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--msm-micro", "", "--ntt-micro", "", "--no-live-traffic", "--inflight", "0", "--other-configs", "",
+               os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--msm-micro", "", "--ntt-micro", "", "--no-live-traffic", "--inflight", "0", "--other-configs", "",
                "--log-constraints", str(args.log_constraints), "--curve", args.curve, "--transcript", args.transcript, "--opt", "msm_overlap=0"]
         env = dict(os.environ, TMPDIR="/tmp")
         try:
@@ -358,6 +368,19 @@ def other_config(ctx, curve, log_nr, transcript, proofs=3):
     return out
 
 
+def dump_outputs(out_dir, curve, proof):
+    """--dump-outputs: what the timed path hands its caller -- the proof of the last timed step, Proof::serialize_compressed
+    bytes ([a]_1, [c]_1, a(x1), [d]_1; data_structures.rs:10-19) -- as float32 arrays: proof.npy one value 0 ... 255 per
+    byte, proof_bits.npy one value 0 / 1 per bit (LSB first), on which no tolerance short of 1 passes a differing proof."""
+    import numpy as np
+    g1 = 48 if curve == "bls12_381" else 32
+    b = np.frombuffer(proof, dtype=np.uint8)
+    assert b.size == 3 * g1 + 32, (curve, b.size)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "proof.npy"), b.astype(np.float32))
+    np.save(os.path.join(out_dir, "proof_bits.npy"), np.unpackbits(b, bitorder="little").astype(np.float32))
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -366,16 +389,21 @@ def parse_args():
     ap.add_argument("--log-constraints", type=int, default=20)
     ap.add_argument("--curve", default="bls12_381")
     ap.add_argument("--transcript", default="merlin")
-    ap.add_argument("--cpu-baseline-log", type=int, default=0, help="0 = the headline workload itself when this box has >= 32 host threads, else 2^16")
+    ap.add_argument("--cpu-baseline-log", type=int, default=0, help="--full: 0 = the headline workload itself when this box has >= 32 host threads, else 2^16")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--msm-micro", default="20,22,24,26", help="log2 lengths of the standalone resident MSM legs ('' = none)")
-    ap.add_argument("--ntt-micro", default="21,22,24", help="log2 sizes of the standalone resident NTT legs ('' = none)")
+    ap.add_argument("--msm-micro", default="20,22,24,26", help="--full: log2 lengths of the standalone resident MSM legs ('' = none)")
+    ap.add_argument("--ntt-micro", default="21,22,24", help="--full: log2 sizes of the standalone resident NTT legs ('' = none)")
     ap.add_argument("--other-configs", default="bn254:20,bls12_381:22,bls12_381:24",
-                    help="curve:log2(constraints) legs run after the headline on the same GPU (BASELINE.json configs[4], configs[2], configs[3] on one GPU; '' = none)")
-    ap.add_argument("--inflight", type=int, default=2, help="proofs in flight of the serving-throughput leg beside `value` (0 = skip; single GPU only)")
-    ap.add_argument("--no-live-traffic", action="store_true", help="do not spawn the two rocprofv3 --pmc child passes that measure `roofline.traffic`")
+                    help="--full: curve:log2(constraints) legs run after the headline on the same GPU (BASELINE.json configs[4], configs[2], configs[3] on one GPU; '' = none)")
+    ap.add_argument("--inflight", type=int, default=2, help="--full: proofs in flight of the serving-throughput leg beside `value` (0 = skip; single GPU only)")
+    ap.add_argument("--no-live-traffic", action="store_true", help="--full: do not spawn the rocprofv3 --pmc child passes that measure `roofline.traffic`")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="pm_ctx_set_option on the proving context before the key is generated, e.g. --opt msm_overlap=0 --opt tables=wide")
+    ap.add_argument("--full", action="store_true",
+                    help="run the extra legs after the timed steps (resident / phase-by-phase / msm_overlap = 0 proofs, roofline, stages, "
+                         "verifier, live traffic, in-flight throughput, CPU baseline, NTT / MSM micro legs, other configurations)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's proof to DIR/proof.npy and DIR/proof_bits.npy (float32)")
     return ap.parse_args()
 
 
@@ -542,11 +570,14 @@ def worker(args):
             threading.Timer(float(die_after), lambda: os._exit(17)).start()
     acc_all_ms, sort_all_ms, red_all_ms, ntt_all_ms, poly_all_ms = [], [], [], [], []
     acc_ms, msm_ms, sort_ms, red_ms, phase_ms, acc1_ms = [], [], [], [], [], []
-    pm.collect_timings = not native                 # phase-by-phase path: keep the stage slots of every phase
+    # the stage timers are read for --full's reports only: a plain run's steps are the proofs and nothing else
+    pm.collect_timings = args.full and not native   # phase-by-phase path: keep the stage slots of every phase
     barrier()
     t0 = time.perf_counter()
     for step_i in range(args.steps):
         proof_b = prove_once()
+        if not args.full:
+            continue
         if native:                                  # slots accumulated over the three phases of the proof
             # pm_host_prove leaves its stage timers unread (pm_last_timings reads ~50 event pairs, ~0.1 ms of host time): the LAST timed
             # proof is the sample -- a prover does not query its timers between proofs
@@ -568,74 +599,56 @@ def worker(args):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     ms_per_step = dt / args.steps * 1e3
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, curve, proof_b)
     pm.collect_timings = False
-    # the same proofs with the assignment already resident in HBM (pm_prove_phase1_device): reported beside `value`
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        proof_res_b = prove_once(resident=True)
-    barrier()
-    dt_res = time.perf_counter() - t1
-    if world > 1:
-        tt = torch.tensor([dt_res], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dt_res = float(tt.item())
-    ms_resident = dt_res / args.steps * 1e3
-    assert proof_res_b == proof_b
-    # one phase-by-phase proof outside the timed region: per-phase stage breakdown, and the two host paths agree
-    pm.collect_timings = True
-    t1 = time.perf_counter()
-    proof_py = pm.prove_limbs(pk, inst, x_l, w_l, r_a, py_combine, dev_ptrs).to_bytes()
-    ms_python_glue = (time.perf_counter() - t1) * 1e3
-    pm.collect_timings = False
-    assert proof_py == proof_b
-    tm3, tm1 = pm.phase_timings[2], pm.phase_timings[0]
-    if native:
-        acc_ms, msm_ms, sort_ms, red_ms, phase_ms = [tm3["msm_accumulate"]], [tm3["msm_total"]], [tm3["msm_sort"]], [tm3["msm_reduce"]], [tm3["phase"]]
-        acc1_ms = [tm1["msm_accumulate"]]
-    # Roofline sample, outside the timed region: ONE proof with PM_OPT_MSM_OVERLAP = 0, so that each k_accumulate launch runs
-    # alone on the chip (in the timed proofs the [a] launch shares it with the transforms and the [c] MSM, which
-    # inflates its HIP-event duration); these are the durations rocprofv3 --stats of the same configuration prints.
-    overlap_was = pm.ctx.get_option("msm_overlap")
-    pm.ctx.set_option("msm_overlap", 0)
-    pm.collect_timings = True
-    proof_serial = pm.prove_limbs(pk, inst, x_l, w_l, r_a, py_combine, dev_ptrs).to_bytes()
-    pm.collect_timings = False
-    pm.ctx.set_option("msm_overlap", overlap_was)
-    assert proof_serial == proof_b
-    acc_serial_ms = pm.phase_timings[0]["msm_accumulate"] + pm.phase_timings[2]["msm_accumulate"]
-    tm1_serial, tm3_serial = dict(pm.phase_timings[0]), dict(pm.phase_timings[2])
-    if os.environ.get("BENCH_PHASES"):             # dev hook: stage timings of all three phases (stderr)
-        log(rank, "phase-by-phase proof %.2f ms; phases:" % ms_python_glue)
-        for i, tm in enumerate(pm.phase_timings):
-            log(rank, " phase %d:" % (i + 1), {k: round(v, 2) for k, v in tm.items() if v})
+    if args.full:
+        # the same proofs with the assignment already resident in HBM (pm_prove_phase1_device): reported beside `value`
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            proof_res_b = prove_once(resident=True)
+        barrier()
+        dt_res = time.perf_counter() - t1
+        if world > 1:
+            tt = torch.tensor([dt_res], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            dt_res = float(tt.item())
+        ms_resident = dt_res / args.steps * 1e3
+        assert proof_res_b == proof_b
+        # one phase-by-phase proof outside the timed region: per-phase stage breakdown, and the two host paths agree
+        pm.collect_timings = True
+        t1 = time.perf_counter()
+        proof_py = pm.prove_limbs(pk, inst, x_l, w_l, r_a, py_combine, dev_ptrs).to_bytes()
+        ms_python_glue = (time.perf_counter() - t1) * 1e3
+        pm.collect_timings = False
+        assert proof_py == proof_b
+        tm3, tm1 = pm.phase_timings[2], pm.phase_timings[0]
+        if native:
+            acc_ms, msm_ms, sort_ms, red_ms, phase_ms = [tm3["msm_accumulate"]], [tm3["msm_total"]], [tm3["msm_sort"]], [tm3["msm_reduce"]], [tm3["phase"]]
+            acc1_ms = [tm1["msm_accumulate"]]
+        # Roofline sample, outside the timed region: ONE proof with PM_OPT_MSM_OVERLAP = 0, so that each k_accumulate launch runs
+        # alone on the chip (in the timed proofs the [a] launch shares it with the transforms and the [c] MSM, which
+        # inflates its HIP-event duration); these are the durations rocprofv3 --stats of the same configuration prints.
+        overlap_was = pm.ctx.get_option("msm_overlap")
+        pm.ctx.set_option("msm_overlap", 0)
+        pm.collect_timings = True
+        proof_serial = pm.prove_limbs(pk, inst, x_l, w_l, r_a, py_combine, dev_ptrs).to_bytes()
+        pm.collect_timings = False
+        pm.ctx.set_option("msm_overlap", overlap_was)
+        assert proof_serial == proof_b
+        acc_serial_ms = pm.phase_timings[0]["msm_accumulate"] + pm.phase_timings[2]["msm_accumulate"]
+        tm1_serial, tm3_serial = dict(pm.phase_timings[0]), dict(pm.phase_timings[2])
+        if os.environ.get("BENCH_PHASES"):             # dev hook: stage timings of all three phases (stderr)
+            log(rank, "phase-by-phase proof %.2f ms; phases:" % ms_python_glue)
+            for i, tm in enumerate(pm.phase_timings):
+                log(rank, " phase %d:" % (i + 1), {k: round(v, 2) for k, v in tm.items() if v})
     n = pk.n
     d_pairs_total = 10 * n + 22                     # quotient MSM M8 (prover.rs:229)
     d_pairs_rank = pk.msm_plan(2)[0]
     pairs_per_proof = (n + 3) + (2 * r1cs.m0 + r1cs.mw + nr + (n - 1) + (n + 1) + 5) + d_pairs_total
     avg = lambda v: sum(v) / max(len(v), 1)
     if rank == 0:
-        bpp = MSM_BYTES_PER_PAIR[curve]
-        # Dominant kernel: k_accumulate, launched once per merged MSM = 3 launches per proof ([a], [c], [d]).  Roofline
-        # over ALL of them: algorithmic bytes per launch = 128 B x (this rank's pairs of the three MSMs) / 3, average
-        # launch duration = (HIP-event time of the three launches) / 3 -- the same average rocprofv3 --stats prints.
-        plans = [pk.msm_plan(k) for k in range(3)]              # (resident pairs, windows, bits, tables)
-        launches = 3
-        acc_s = acc_serial_ms * 1e-3                             # per proof, all three launches, each running alone
-        acc_overlapped_s = (avg(acc_all_ms) if native else avg(acc_ms) + avg(acc1_ms)) * 1e-3   # as in the timed proofs
-        pairs_rank = sum(p[0] for p in plans)
-        achieved = (bpp * pairs_rank / acc_s / 1e9) if acc_s > 0 else 0.0
-        mads_rank = float(MADS_PER_MIXED_ADD[curve]) * sum(p[0] * p[1] for p in plans)
-        msm_windows = plans[2][1]
-        traffic, traffic_source = None, None
-        tfile = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tfile):
-            try:
-                tj = json.load(open(tfile))
-                key = "k_accumulate/%s/2^%d/%dgpu/avg_launch" % (curve, args.log_constraints, shard_count)
-                traffic = tj.get(key)
-            except Exception:
-                traffic = None
         out = {
             "metric": "prove_constraints_per_sec", "value": nr / (dt / args.steps), "unit": "constraints/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
@@ -649,40 +662,64 @@ def worker(args):
             "msm_pairs_per_sec": pairs_per_proof / (dt / args.steps),
             "timed_entry_point": "pm_host_prove%s from pinned HOST buffers (x, w: %.1f MB H2D inside every step; SURVEY.md §8d, benches/bench.rs:79)"
                                  % ("_sharded" if world > 1 else "", (x_l.nbytes + w_l.nbytes) / 1e6),
-            "ms_per_step_hbm_resident": ms_resident, "value_hbm_resident": nr / (dt_res / args.steps),
             "n_ranks_seen": comm_meta["ranks_seen"] if comm_meta else world,
             "exchange": comm_meta if comm_meta else {"kind": "none (single GPU)" if not multi else "torch.distributed point all-gather (pairs layout)", "ranks_seen": world},
             "launch": {"supervised": supervised, "attempt": int(os.environ.get("BENCH_ATTEMPT", "0")), "torch_distributed_backend": backend if multi else None},
             "host_glue": "native (pm_host_prove%s: C++ transcript + challenge arithmetic inside the library)" % ("_sharded" if world > 1 else "")
                          if native else "python (phases driven from bench.py)",
-            "ms_per_step_python_glue": ms_python_glue,
             "arithmetic": "integer, 28/32-bit limbs in u32 registers (255-bit Fr, 381-bit Fq Montgomery)",
-            "msm_d_pairs_per_sec_kernel_time": d_pairs_rank / (avg(msm_ms) * 1e-3) if avg(msm_ms) > 0 else None,
-            "stage_ms_phase3": {"msm_sort": avg(sort_ms), "msm_accumulate": avg(acc_ms), "msm_reduce": avg(red_ms),
-                                "msm_total": avg(msm_ms), "phase3_total": avg(phase_ms)},
-            "roofline": {"bound": "hbm", "kernel": "k_accumulate (MSM bucket accumulation; %d launches per proof: [a], [c], [d])" % launches,
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": "profiles/pmc_traffic.json (committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command)",
-                         "launches_per_step": launches, "avg_launch_ms": acc_s * 1e3 / launches,
-                         "timing": "HIP events on the library's stream around each launch of one msm_overlap = 0 proof outside the timed region "
-                                   "(launches run alone); in the timed proofs [a] overlaps other kernels: %.3f ms per proof there" % (acc_overlapped_s * 1e3),
-                         "algorithmic_bytes_per_launch": bpp * pairs_rank / launches,
-                         "largest_launch": {"pairs": d_pairs_rank, "ms": avg(acc_ms),
-                                            "achieved": (bpp * d_pairs_rank / (avg(acc_ms) * 1e-3) / 1e9) if avg(acc_ms) > 0 else None},
-                         "note": "algorithmic bytes = %d B/pair x %d pairs over %d launches; the kernel is integer-ALU-bound "
-                                 "(%d mixed adds x %d v_mad_u64_u32 per pair: see `valu` and DESIGN.md §4.2)" %
-                                 (bpp, pairs_rank, launches, msm_windows, MADS_PER_MIXED_ADD[curve])},
-            "valu": {"kernel": "k_accumulate", "unit": "lane-mads/s (v_mad_u64_u32)", "mads_per_mixed_add": MADS_PER_MIXED_ADD[curve],
-                     "mixed_adds_per_pair": [p[1] for p in plans], "achieved": mads_rank / acc_s if acc_s > 0 else None, "peak": VALU_MAD_PEAK,
-                     "frac": (mads_rank / acc_s / VALU_MAD_PEAK) if acc_s > 0 else None,
-                     "note": "the real bound of this kernel: mads are 79 % of its instruction stream (3 542 of 4 468 per mixed add, point load included); "
-                             "SQ counters (profiles/r04_pmc_sort_summary.txt): 0.94 of the VALU issue slots at the 2.0-2.1 GHz the package power limit leaves (profiles/r04_power_probe.txt)"},
-            "stages": stage_report(curve, r1cs, pk, tm1_serial, tm3_serial, plans),
             "proof_bytes": proof_b.hex(),
-            # Polymath::verify (verifier.rs:19-62) on the timed proof, by the library's own CPU verifier (pm_host_verify)
-            "proof_verified": bool(pm.verify(pm.make_vk(pk, x_trap, z_trap), inst[1:], proof_b)),
         }
-        if world == 1 and shard_count == 1 and not multi:
+        if args.full:
+            bpp = MSM_BYTES_PER_PAIR[curve]
+            # Dominant kernel: k_accumulate, launched once per merged MSM = 3 launches per proof ([a], [c], [d]).  Roofline
+            # over ALL of them: algorithmic bytes per launch = 128 B x (this rank's pairs of the three MSMs) / 3, average
+            # launch duration = (HIP-event time of the three launches) / 3 -- the same average rocprofv3 --stats prints.
+            plans = [pk.msm_plan(k) for k in range(3)]              # (resident pairs, windows, bits, tables)
+            launches = 3
+            acc_s = acc_serial_ms * 1e-3                             # per proof, all three launches, each running alone
+            acc_overlapped_s = (avg(acc_all_ms) if native else avg(acc_ms) + avg(acc1_ms)) * 1e-3   # as in the timed proofs
+            pairs_rank = sum(p[0] for p in plans)
+            achieved = (bpp * pairs_rank / acc_s / 1e9) if acc_s > 0 else 0.0
+            mads_rank = float(MADS_PER_MIXED_ADD[curve]) * sum(p[0] * p[1] for p in plans)
+            msm_windows = plans[2][1]
+            traffic, traffic_source = None, None
+            tfile = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(tfile):
+                try:
+                    tj = json.load(open(tfile))
+                    key = "k_accumulate/%s/2^%d/%dgpu/avg_launch" % (curve, args.log_constraints, shard_count)
+                    traffic = tj.get(key)
+                except Exception:
+                    traffic = None
+            out.update({
+                "ms_per_step_hbm_resident": ms_resident, "value_hbm_resident": nr / (dt_res / args.steps),
+                "ms_per_step_python_glue": ms_python_glue,
+                "msm_d_pairs_per_sec_kernel_time": d_pairs_rank / (avg(msm_ms) * 1e-3) if avg(msm_ms) > 0 else None,
+                "stage_ms_phase3": {"msm_sort": avg(sort_ms), "msm_accumulate": avg(acc_ms), "msm_reduce": avg(red_ms),
+                                    "msm_total": avg(msm_ms), "phase3_total": avg(phase_ms)},
+                "roofline": {"bound": "hbm", "kernel": "k_accumulate (MSM bucket accumulation; %d launches per proof: [a], [c], [d])" % launches,
+                             "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                             "traffic": traffic, "traffic_source": "profiles/pmc_traffic.json (committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command)",
+                             "launches_per_step": launches, "avg_launch_ms": acc_s * 1e3 / launches,
+                             "timing": "HIP events on the library's stream around each launch of one msm_overlap = 0 proof outside the timed region "
+                                       "(launches run alone); in the timed proofs [a] overlaps other kernels: %.3f ms per proof there" % (acc_overlapped_s * 1e3),
+                             "algorithmic_bytes_per_launch": bpp * pairs_rank / launches,
+                             "largest_launch": {"pairs": d_pairs_rank, "ms": avg(acc_ms),
+                                                "achieved": (bpp * d_pairs_rank / (avg(acc_ms) * 1e-3) / 1e9) if avg(acc_ms) > 0 else None},
+                             "note": "algorithmic bytes = %d B/pair x %d pairs over %d launches; the kernel is integer-ALU-bound "
+                                     "(%d mixed adds x %d v_mad_u64_u32 per pair: see `valu` and DESIGN.md §4.2)" %
+                                     (bpp, pairs_rank, launches, msm_windows, MADS_PER_MIXED_ADD[curve])},
+                "valu": {"kernel": "k_accumulate", "unit": "lane-mads/s (v_mad_u64_u32)", "mads_per_mixed_add": MADS_PER_MIXED_ADD[curve],
+                         "mixed_adds_per_pair": [p[1] for p in plans], "achieved": mads_rank / acc_s if acc_s > 0 else None, "peak": VALU_MAD_PEAK,
+                         "frac": (mads_rank / acc_s / VALU_MAD_PEAK) if acc_s > 0 else None,
+                         "note": "the real bound of this kernel: mads are 79 % of its instruction stream (3 542 of 4 468 per mixed add, point load included); "
+                                 "SQ counters (profiles/r04_pmc_sort_summary.txt): 0.94 of the VALU issue slots at the 2.0-2.1 GHz the package power limit leaves (profiles/r04_power_probe.txt)"},
+                "stages": stage_report(curve, r1cs, pk, tm1_serial, tm3_serial, plans),
+                # Polymath::verify (verifier.rs:19-62) on the timed proof, by the library's own CPU verifier (pm_host_verify)
+                "proof_verified": bool(pm.verify(pm.make_vk(pk, x_trap, z_trap), inst[1:], proof_b)),
+            })
+        if args.full and world == 1 and shard_count == 1 and not multi:
             if not args.no_live_traffic:
                 pk_bytes_note = "(the parent's key stays resident: the children build their own)"
                 log(rank, "measuring k_accumulate's HBM traffic and clock: three rocprofv3 --pmc child passes %s ..." % pk_bytes_note)

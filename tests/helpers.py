@@ -59,3 +59,21 @@ def pm_csrs(curve, r1cs):
 
 
 TABLES_OPT = {"1": "auto", "0": "off", "wide": "wide"}     # the parametrisations' historical names (PM_TABLES values)
+
+
+def patch_preimages(patch_text):
+    """A unified diff -> {path: [(start, count, lines), ...]}: per hunk, the line range of the ORIGINAL file its header names
+    and the lines it expects there (context and removed lines, in order).  A file the patch creates has one hunk (0, 0, [])."""
+    out, path, hunk = {}, None, None
+    for line in patch_text.split("\n"):
+        if line.startswith("diff --git "):
+            path, hunk = line.split(" b/", 1)[1], None
+            out[path] = []
+        elif line.startswith("@@ "):
+            start, _, count = line.split()[1][1:].partition(",")
+            hunk = (int(start), int(count or 1), [])
+            out[path].append(hunk)
+        elif hunk is not None and line[:1] in (" ", "-", ""):
+            if len(hunk[2]) < hunk[1]:
+                hunk[2].append(line[1:])
+    return out

@@ -140,9 +140,6 @@ def test_rust_wrapper_and_reference_patch_are_consistent():
         assert "pub fn " + fn in wrapper and fn in added
 
 
-REFERENCE = "/root/reference"
-
-
 def _patch_files(patch):
     return re.findall(r"^diff --git a/(\S+) b/", patch, flags=re.M)
 
@@ -182,18 +179,27 @@ def test_every_snark_method_of_the_reference_has_a_route_in_the_patch():
     assert "in_flight.prove_phase2" in added and "in_flight.prove_phase3" in added
 
 
-def test_reference_patch_applies_to_the_reference(tmp_path):
-    """With the reference checkout present (this container; never on the GPU box): `patch -p1 --dry-run` of the committed
-    patch against an untouched copy succeeds with no fuzz and no rejects."""
-    import shutil
-    import subprocess
-    if not os.path.isdir(REFERENCE) or not shutil.which("patch"):
-        pytest.skip("no reference checkout / no patch(1) here")
-    work = tmp_path / "ref"
-    shutil.copytree(REFERENCE, work, ignore=shutil.ignore_patterns(".git", "target"))
-    run = subprocess.run(["patch", "-p1", "--dry-run", "-i", os.path.join(ROOT, "rust", "reference-patch", "sigma0-polymath-hip.patch")],
-                         cwd=work, capture_output=True, text=True)
-    assert run.returncode == 0 and "fuzz" not in run.stdout and "FAILED" not in run.stdout, run.stdout + run.stderr
+def test_reference_patch_applies_to_the_reference():
+    """The committed patch applies to an untouched reference checkout with no offset, no fuzz and no rejects: every hunk's
+    pre-image (its context and removed lines) is the reference's text in the range the hunk header names, and a file the
+    patch creates is not there.  The reference's side is held as per-hunk sha256s (tests/golden/reference_patch_preimage.json,
+    written by tools/gen_patch_preimage.py from a checkout), so no checkout is needed here."""
+    import hashlib
+    from helpers import load_golden, patch_preimages
+    fx = load_golden("reference_patch_preimage.json")
+    patch = open(os.path.join(ROOT, "rust", "reference-patch", "sigma0-polymath-hip.patch")).read()
+    assert fx["patch"] == "rust/reference-patch/sigma0-polymath-hip.patch"
+    pre = patch_preimages(patch)
+    assert pre and sorted(pre) == sorted(fx["files"]) == sorted(_patch_files(patch))
+    for path, hunks in pre.items():
+        ref = fx["files"][path]
+        if ref.get("absent"):
+            assert [(s, c, l) for s, c, l in hunks] == [(0, 0, [])], path          # a new file: "--- /dev/null", "@@ -0,0 ..."
+            continue
+        assert [(s, c) for s, c, _ in hunks] == [(h["start"], h["count"]) for h in ref["hunks"]], path
+        for (start, count, lines), h in zip(hunks, ref["hunks"]):
+            assert len(lines) == count and 1 <= start and start - 1 + count <= ref["lines"], (path, start)
+            assert hashlib.sha256("\n".join(lines).encode()).hexdigest() == h["sha256"], (path, start)
 
 
 def test_integration_md_quotes_the_rust_sources():

@@ -529,7 +529,7 @@ def test_bench_two_ranks_one_gpu_same_proof():
     proof bytes as the single-rank run."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--steps", "1", "--warmup", "0", "--log-constraints", "12", "--no-cpu-baseline", "--msm-micro", "", "--no-live-traffic", "--other-configs", ""]
+    common = ["--full", "--steps", "1", "--warmup", "0", "--log-constraints", "12", "--no-cpu-baseline", "--msm-micro", "", "--no-live-traffic", "--other-configs", ""]
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + common, capture_output=True, text=True, timeout=900)
     assert one.returncode == 0, one.stderr[-3000:]
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo", BENCH_FORCE_DEVICE="0")
@@ -558,7 +558,7 @@ def test_bench_gpus_2_starts_its_own_ranks():
      and the HBM-resident variant is reported beside it."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--steps", "2", "--warmup", "1", "--log-constraints", "12", "--no-cpu-baseline", "--msm-micro", "", "--no-live-traffic", "--other-configs", ""]
+    common = ["--full", "--steps", "2", "--warmup", "1", "--log-constraints", "12", "--no-cpu-baseline", "--msm-micro", "", "--no-live-traffic", "--other-configs", ""]
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + common, capture_output=True, text=True, timeout=900)
     assert one.returncode == 0, one.stderr[-3000:]
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo", BENCH_FORCE_DEVICE="0")
@@ -584,7 +584,7 @@ def test_bench_fallback_chain_when_rccl_cannot_serve_the_job():
     fabric that will not come up, seen end to end: one JSON line, from a later attempt, with the single-GPU proof."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--steps", "2", "--warmup", "1", "--log-constraints", "12", "--no-cpu-baseline", "--msm-micro", "", "--no-live-traffic", "--other-configs", ""]
+    common = ["--full", "--steps", "2", "--warmup", "1", "--log-constraints", "12", "--no-cpu-baseline", "--msm-micro", "", "--no-live-traffic", "--other-configs", ""]
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + common, capture_output=True, text=True, timeout=900)
     assert one.returncode == 0, one.stderr[-3000:]
     env = dict(os.environ, BENCH_FORCE_DEVICE="0", BENCH_ATTEMPT_DEADLINE_S="300")
@@ -627,6 +627,36 @@ def test_bench_dead_rank_ends_the_job_non_zero():
     assert not [l for l in run.stdout.splitlines() if l.startswith("{")]
     assert "exited with code 17" in run.stderr or "failed" in run.stderr, run.stderr[-2000:]
     assert time.time() - t0 < 400
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_proof(tmp_path):
+    """A plain `bench.py` run (no --full): the headline keys with `steps` = --steps and `value` from `ms_per_step`, none of
+    --full's legs; --dump-outputs writes the last timed step's proof (proof.npy one float32 per byte, proof_bits.npy one per
+    bit, LSB first), and a second run with the same arguments writes the same arrays."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-constraints", "12",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert run.returncode == 0, run.stderr[-3000:]
+        lines = [l for l in run.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        assert j["metric"] == "prove_constraints_per_sec" and j["unit"] == "constraints/s" and j["higher_is_better"] is True and j["dtype"] == "u32"
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0
+        assert abs(j["value"] - ((1 << 12) - 100) / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+        for extra in ("ms_per_step_hbm_resident", "roofline", "valu", "stages", "proof_verified", "throughput_in_flight", "cpu_baseline",
+                      "ntt_micro", "msm_micro", "other_configs"):
+            assert extra not in j, extra
+        proof, bits = np.load(d / "proof.npy"), np.load(d / "proof_bits.npy")
+        assert proof.dtype == np.float32 and bits.dtype == np.float32
+        raw = bytes.fromhex(j["proof_bytes"])
+        assert len(raw) == 3 * 48 + 32 and proof.astype(np.uint8).tobytes() == raw
+        assert np.array_equal(bits, np.unpackbits(np.frombuffer(raw, dtype=np.uint8), bitorder="little").astype(np.float32))
+        dumps.append((proof, bits))
+    assert all(np.array_equal(a, b) for a, b in zip(*dumps))
 
 
 def test_full_size_2p20_proof_passes_pairing_verifier(oracle):

@@ -10,7 +10,7 @@ d=json.loads(sys.stdin.read()); print('$v rep $rep best_ms %.3f' % d['best_ms'],
 done; done
 for v in ${VARIANTS:-base new}; do
   export POLYMATH_HIP_LIB=$GRAFT_REPO_ROOT/ab/libpolymath_hip_$v.so      # loaded through api.LIB_PATH: the in-tree library is never overwritten
-  timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --msm-micro "" --ntt-micro "" --no-live-traffic 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --msm-micro "" --ntt-micro "" --no-live-traffic 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split('\n')[-1]); print('$v ms_per_step %.3f resident %s' % (d['ms_per_step'], d.get('ms_per_step_hbm_resident')), {k:round(v.get('ms'),3) for k,v in d.get('stages',{}).items() if isinstance(v,dict)})"
 done

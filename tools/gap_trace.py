@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU idle gaps inside ONE proof and the HIP calls the host made during each: from
-  rocprofv3 --hip-runtime-trace --kernel-trace --output-format csv -d OUT -o t -- python3 bench.py --steps 2 --warmup 1 ...
+  rocprofv3 --hip-runtime-trace --kernel-trace --output-format csv -d OUT -o t -- python3 bench.py --full --steps 2 --warmup 1 ...
   python tools/gap_trace.py OUT/t_kernel_trace.csv OUT/t_hip_api_trace.csv [min_gap_us] [proof]
 proof = -1: the last one in the trace (bench.py: the msm_overlap = 0 proof of the stage report), -2 (default): the last TIMED proof."""
 import csv, sys, collections
