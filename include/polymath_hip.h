@@ -124,7 +124,10 @@ typedef enum pm_option {
                                    * workspaces are left out of the HBM granted to window tables.  Default 1 (PM_INFLIGHT_CONTEXTS). */
     PM_OPT_MSM_TASK_LEN = 6,      /* entries of one bucket-accumulation task; 0 = twice the mean bucket load.  Default 0 (PM_MSM_SEG). */
     PM_OPT_TABLE_WINDOW_BITS = 7, /* (key) widest window of the table sets; 0 = the cost model of tables_plan.  Default 0 (PM_TABLE_C). */
-    PM_NUM_OPTIONS = 8
+    PM_OPT_WIRE_CHUNK_LOG = 8,    /* compressed points per staging chunk of pm_pk_load_bytes / pm_g1_decode /
+                                   * pm_pk_export_bases_compressed: 2^v, 4 <= v <= 24.  Default 20 (PM_WIRE_CHUNK_LOG); lower values put
+                                   * chunk boundaries inside small vectors (tests). */
+    PM_NUM_OPTIONS = 9
 } pm_option;
 typedef enum pm_tables_mode {
     PM_TABLES_OFF = 0,      /* no window tables, no wide mode: every MSM on the per-window pipeline */
@@ -201,6 +204,41 @@ int pm_pk_msm_plan(const pm_pk *pk, int which, uint64_t *pairs, unsigned *window
 /* Copy (a range of) one base vector back to the host, x||y Montgomery, 16*fq_limbs bytes apart. */
 int pm_pk_export_bases(pm_ctx *ctx, const pm_pk *pk, int which, size_t offset, size_t len, uint64_t *out_xy);
 void pm_pk_free(pm_pk *pk);
+
+/* ---- proving keys as bytes: ProvingKey::serialize_compressed (data_structures.rs:56-73), decoded on the device ---------
+ * Compressed G1 = ark-serialize's compressed form: BLS12-381 48 bytes, the zcash encoding (big-endian x, flags 0x80 compressed /
+ * 0x40 infinity / 0x20 y > -y in the FIRST byte); BN254 32 bytes, ark's short-Weierstrass flags (little-endian x, 0x80 y > -y /
+ * 0x40 infinity in the LAST byte, both at once is an error).  Infinity must be canonical (every other bit zero).  validate != 0 is
+ * ark's Validate::Yes (deserialize_compressed: on the curve AND, on BLS12-381, in the prime-order subgroup, checked as [r]P == O);
+ * validate == 0 is deserialize_compressed_unchecked (the curve equation is still enforced by decompression).  BN254's G1 has
+ * cofactor 1.  The host mirror polymath_amd/host/wire.hpp (deser_g1 / ser_g1) is the specification, bit for bit. */
+typedef enum pm_g1_status {       /* one verdict per point; the text is deser_g1's WireError for the same case */
+    PM_G1_OK = 0,
+    PM_G1_BAD_FLAGS = 1,          /* "G1: not a compressed point" (BLS12-381) / "G1: both flag bits set" (BN254) */
+    PM_G1_COORD_GE_P = 2,         /* "G1: coordinate >= p" */
+    PM_G1_NOT_ON_CURVE = 3,       /* "G1: not on the curve" (x^3 + b has no square root) */
+    PM_G1_NOT_IN_SUBGROUP = 4,    /* "G1: not in the prime-order subgroup" (validate != 0, BLS12-381 only) */
+    PM_G1_NONCANONICAL_INF = 5,   /* "G1: non-canonical encoding of the point at infinity" */
+    PM_G1_INF_SIGN = 6            /* "G1: sign bit on the point at infinity" (BLS12-381; on BN254 that is PM_G1_BAD_FLAGS) */
+} pm_g1_status;
+/* Batch decode, host to host: `count` packed records of 48 (BLS12-381) / 32 (BN254) bytes -> out_xy (x||y Montgomery, 2*fq_limbs
+ * u64 per point; infinity and every refused point x = y = 0) and one pm_g1_status byte per point.  PM_OK even when points are bad:
+ * the verdicts are in `status`. */
+int pm_g1_decode(pm_ctx *ctx, int curve, const uint8_t *in, size_t count, int validate, uint64_t *out_xy, uint8_t *status);
+/* The whole ProvingKey::serialize_compressed byte string -> a resident key, as pm_pk_load_sharded would make it (shard_rank /
+ * shard_count / layout alike; window tables and the wide mode follow the same way).  The host parses the vk, the SAP header and
+ * matrices (canonical Fr) and the six length prefixes; the points go to the device compressed, through pinned staging in chunks
+ * of 2^PM_OPT_WIRE_CHUNK_LOG, and are decoded straight into the resident base array: no decoded point crosses the bus.  On a
+ * sharded key only this rank's resident ranges are copied and checked.  `bytes` may be an mmap of the key file; it is only read.
+ * The VerifyingKey is the byte prefix (data_structures.rs:56-58: vk is the first field): 392 bytes on BLS12-381, 280 on BN254 --
+ * its points are always validated (host).  PM_ERR_INVALID_ARG, no handle, nothing allocated: truncated or trailing bytes, a vector
+ * length that does not fit the key's shape, vk.m0 / n / sigma / omega disagreeing with the SAP matrices, or a refused point --
+ * pm_last_error then names the first one in wire order, e.g. "x_powers_g1[17]: G1: not in the prime-order subgroup". */
+int pm_pk_load_bytes(pm_ctx *ctx, int curve, const uint8_t *bytes, size_t len, int validate, int shard_rank, int shard_count,
+                     int layout, pm_pk **out);
+/* pm_pk_export_bases, compressed: `len` records of 48 / 32 bytes (ser_g1, the encoding pm_pk_load_bytes reads) into out.
+ * Same ranges and restrictions as pm_pk_export_bases. */
+int pm_pk_export_bases_compressed(pm_ctx *ctx, const pm_pk *pk, int which, size_t offset, size_t len, uint8_t *out);
 
 /* ---- prove: create_proof_with_assignment split at its two transcript calls ---------------- */
 /* Fiat-Shamir choices of the reference (src/transcript/{merlin,keccak256,blake3}.rs) for pm_host_prove. */

@@ -23,6 +23,9 @@ STATUS = {0: "PM_OK", 1: "PM_ERR_INVALID_ARG", 2: "PM_ERR_LEN_MISMATCH", 3: "PM_
           8: "PM_ERR_STATE", 9: "PM_ERR_COMM"}
 (X_POWERS, X_POWERS_Y_ALPHA, X_POWERS_Y_GAMMA, X_POWERS_Y_GAMMA_Z, X_POWERS_ZH_BY_Y_ALPHA,
  UJ_WJ_LCS_BY_Y_ALPHA) = range(6)
+# pm_g1_status (include/polymath_hip.h): the verdict of one compressed G1 encoding
+G1_OK, G1_BAD_FLAGS, G1_COORD_GE_P, G1_NOT_ON_CURVE, G1_NOT_IN_SUBGROUP, G1_NONCANONICAL_INF, G1_INF_SIGN = range(7)
+G1_BYTES = {PM_BLS12_381: 48, PM_BN254: 32}                # compressed record of one point
 TIMING_SLOTS = ["witness_map", "ntt", "poly", "msm_sort", "msm_accumulate", "msm_reduce", "msm_total", "phase"]
 
 u64p = ct.POINTER(ct.c_uint64)
@@ -58,10 +61,11 @@ EXPORTS = [
     "pm_comm_rccl_unique_id", "pm_comm_rccl_create", "pm_comm_local_create", "pm_comm_from_callbacks", "pm_comm_destroy", "pm_comm_rank",
     "pm_comm_world", "pm_comm_last_error", "pm_comm_kind", "pm_comm_set_timeout_ms", "pm_comm_abort", "pm_comm_failed", "pm_comm_busy_ms", "pm_host_make_vk", "pm_host_verify", "pm_comm_all_gather", "pm_comm_all_to_all", "pm_comm_all_gather_device", "pm_comm_combine_points", "pm_ctx_set_comm",
     "pm_ctx_set_option", "pm_ctx_get_option", "pm_comm_local_set_serialize",
+    "pm_g1_decode", "pm_pk_load_bytes", "pm_pk_export_bases_compressed",
 ]
 # pm_option / pm_tables_mode (include/polymath_hip.h)
 OPTIONS = {"msm_overlap": 0, "ntt_overlap": 1, "tables": 2, "msm_max_piece_log": 3, "max_seg_log": 4, "inflight_contexts": 5,
-           "msm_task_len": 6, "table_window_bits": 7}
+           "msm_task_len": 6, "table_window_bits": 7, "wire_chunk_log": 8}
 TABLES_MODES = {"off": 0, "auto": 1, "wide": 2, "no_wide": 3}
 SHARD_PAIRS, SHARD_VECTOR = 0, 1
 LAYOUTS = {"pairs": SHARD_PAIRS, "vector": SHARD_VECTOR, 0: 0, 1: 1}
@@ -153,6 +157,9 @@ def load_library():
     L.pm_ctx_set_option.argtypes = [vp, i, ct.c_longlong]
     L.pm_ctx_get_option.argtypes = [vp, i, ct.POINTER(ct.c_longlong)]
     L.pm_comm_local_set_serialize.argtypes = [vp, i]
+    L.pm_g1_decode.argtypes = [vp, i, vp, sz, i, u64p, vp]
+    L.pm_pk_load_bytes.argtypes = [vp, i, vp, sz, i, i, i, i, ct.POINTER(vp)]
+    L.pm_pk_export_bases_compressed.argtypes = [vp, vp, i, sz, sz, vp]
     _lib = L
     return L
 
@@ -219,6 +226,32 @@ def synth_r1cs(curve, nr, seed):
         raise PolymathError(st, "pm_synth_r1cs")
     rowptr = np.arange(nr + 1, dtype=np.uint64)
     return [CsrArrays(rowptr, cols[k], vals[k]) for k in range(3)], inst, wit
+
+
+def _byte_view(data):
+    """(buffer keeping the memory alive, address, length) of bytes / bytearray / memoryview / np.memmap, without a copy where the
+    object exposes a C-contiguous buffer (bytes objects do: ctypes reads them in place)."""
+    if isinstance(data, bytes):
+        return data, ct.cast(ct.c_char_p(data), ct.c_void_p).value, len(data)
+    arr = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.reshape(-1).view(np.uint8)
+    if not arr.flags.c_contiguous:
+        arr = np.ascontiguousarray(arr)
+    return arr, arr.ctypes.data, arr.nbytes
+
+
+def g1_decode(ctx, curve, data, validate=True):
+    """pm_g1_decode: packed compressed G1 records (48 B BLS12-381 / 32 B BN254) -> (xy np.uint64 [count, 2 fq_limbs] Montgomery,
+    infinity and refused points all-zero; status np.uint8 [count] of G1_* codes)."""
+    cid = CURVE_IDS[curve]
+    keep, addr, nbytes = _byte_view(data)
+    if nbytes % G1_BYTES[cid]:
+        raise ValueError("not a whole number of %d-byte records" % G1_BYTES[cid])
+    count = nbytes // G1_BYTES[cid]
+    xy = np.zeros((count, 2 * FQ_LIMBS64[cid]), dtype=np.uint64)
+    status = np.zeros(count, dtype=np.uint8)
+    ctx.check(ctx.L.pm_g1_decode(ctx.h, cid, ct.c_void_p(addr), count, int(bool(validate)), _p(xy), status.ctypes.data_as(ct.c_void_p)))
+    del keep
+    return xy, status
 
 
 def layout_indices(n, shard_count, shard_rank, coefficients=True):
@@ -517,6 +550,19 @@ class ProvingKey:
         pk.shard_rank, pk.shard_count, pk.layout = shard_rank, shard_count, LAYOUTS[layout]
         return pk
 
+    @classmethod
+    def load_bytes(cls, ctx, curve, data, validate=True, shard_rank=0, shard_count=1, layout="pairs"):
+        """pm_pk_load_bytes: ProvingKey::serialize_compressed bytes -> resident key; the points are decoded (and with `validate`
+        checked as ark's Validate::Yes does) on the device.  data: bytes, memoryview or np.memmap of a key file, not copied."""
+        keep, addr, nbytes = _byte_view(data)
+        h = ct.c_void_p()
+        ctx.check(ctx.L.pm_pk_load_bytes(ctx.h, CURVE_IDS[curve], ct.c_void_p(addr), nbytes, int(bool(validate)), shard_rank, shard_count,
+                                         LAYOUTS[layout], ct.byref(h)))
+        del keep
+        pk = cls(ctx, curve, h, None)
+        pk.shard_rank, pk.shard_count, pk.layout = shard_rank, shard_count, LAYOUTS[layout]
+        return pk
+
     def view(self, ctx):
         """The same resident key used from another context (a pm_pk is immutable and shareable; each context runs
         one proof at a time).  The view does not own the handle: free the original."""
@@ -548,6 +594,14 @@ class ProvingKey:
         out = np.zeros((length, 2 * self.nq), dtype=np.uint64)
         self.ctx.check(self.ctx.L.pm_pk_export_bases(self.ctx.h, self.h, which, offset, length, _p(out)))
         return out
+
+    def export_bases_compressed(self, which, offset=0, length=None):
+        """pm_pk_export_bases_compressed: (a range of) base vector `which` as its serialize_compressed point records -> bytes."""
+        if length is None:
+            length = self.base_lens[which] - offset
+        out = ct.create_string_buffer(max(1, length * G1_BYTES[self.cid]))
+        self.ctx.check(self.ctx.L.pm_pk_export_bases_compressed(self.ctx.h, self.h, which, offset, length, out))
+        return out.raw[:length * G1_BYTES[self.cid]]
 
     # --- the three prover phases: (status, outputs...) tuples, status codes of pm_status
     def phase1(self, x, w, r_a):

@@ -85,6 +85,7 @@ static const OptionSpec OPTION_SPECS[PM_NUM_OPTIONS] = {
     /* PM_OPT_INFLIGHT_CONTEXTS */ {"PM_INFLIGHT_CONTEXTS", 1, 1, 64},
     /* PM_OPT_MSM_TASK_LEN      */ {"PM_MSM_SEG", 0, 0, 1 << 20},
     /* PM_OPT_TABLE_WINDOW_BITS */ {"PM_TABLE_C", 0, 0, 24},
+    /* PM_OPT_WIRE_CHUNK_LOG    */ {"PM_WIRE_CHUNK_LOG", 20, 4, 24},
 };
 static void options_defaults(pm_options *o) {
     for (int k = 0; k < PM_NUM_OPTIONS; ++k) {
@@ -603,10 +604,14 @@ static int for_cat_range(const pm_pk *pk, uint64_t lo, uint64_t hi, Affine<C> *d
     return PM_OK;
 }
 
-// Allocates the resident base array and fills it through `fill`; then, when they fit (sized for 288 GB of
-// HBM), builds one set of window tables per merged MSM on the device.
+// Allocates the resident base array and fills it through `fill` (pk_fill_resident); then, when they fit (sized for 288 GB of
+// HBM), builds one set of window tables per merged MSM on the device (pk_build_tables).
+template <class C>
+static int pk_build_tables(pm_ctx *ctx, pm_pk *pk);
 template <class C, class F>
-static int pk_fill_bases(pm_ctx *ctx, pm_pk *pk, F fill) {
+static int pk_fill_bases(pm_ctx *ctx, pm_pk *pk, F fill);
+template <class C, class F>
+static int pk_fill_resident(pm_ctx *ctx, pm_pk *pk, F fill) {
     const uint64_t resident = pk_resident_points(pk);
     PM_HIP(ctx, hipMalloc(&pk->d_bases, (resident ? resident : 1) * sizeof(Affine<C>)));
     Affine<C> *d = (Affine<C> *)pk->d_bases;
@@ -622,6 +627,18 @@ static int pk_fill_bases(pm_ctx *ctx, pm_pk *pk, F fill) {
         }
     }
     PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PM_OK;
+}
+
+template <class C, class F>
+static int pk_fill_bases(pm_ctx *ctx, pm_pk *pk, F fill) {
+    PM_TRY(pk_fill_resident<C>(ctx, pk, fill));
+    return pk_build_tables<C>(ctx, pk);
+}
+
+template <class C>
+static int pk_build_tables(pm_ctx *ctx, pm_pk *pk) {
+    Affine<C> *d = (Affine<C> *)pk->d_bases;
     const long long tmode = ctx->opt.v[PM_OPT_TABLES];
     pk->max_piece = (uint64_t)msm_max_piece(ctx);
     if (tmode == PM_TABLES_OFF) return PM_OK;
@@ -722,6 +739,141 @@ extern "C" int pm_pk_load(pm_ctx *ctx, int curve, uint64_t n, uint64_t m0, uint6
                           const pm_csr *a, const pm_csr *b, const pm_csr *c, const pm_base_array bases[PM_NUM_BASE_VECS],
                           int shard_rank, int shard_count, pm_pk **out) {
     return pm_pk_load_sharded(ctx, curve, n, m0, mw, nr, sigma, a, b, c, bases, shard_rank, shard_count, PM_SHARD_PAIRS, out);
+}
+
+// ---- keys as bytes (ProvingKey::serialize_compressed; g1_codec.hip decodes the points)
+static const char *const BASE_VEC_NAMES[PM_NUM_BASE_VECS] = {"x_powers_g1", "x_powers_y_alpha_g1", "x_powers_y_gamma_g1",
+                                                             "x_powers_y_gamma_z_g1", "x_powers_zh_by_y_alpha_g1",
+                                                             "uj_wj_lcs_by_y_alpha_g1"};
+static const int WIRE_VECTOR_ORDER[PM_NUM_BASE_VECS] = {PM_X_POWERS, PM_X_POWERS_Y_ALPHA, PM_X_POWERS_ZH_BY_Y_ALPHA, PM_X_POWERS_Y_GAMMA,
+                                                        PM_X_POWERS_Y_GAMMA_Z, PM_UJ_WJ_LCS_BY_Y_ALPHA};   // data_structures.rs:60-72
+
+static size_t wire_chunk(const pm_ctx *ctx) { return (size_t)1 << ctx->opt.v[PM_OPT_WIRE_CHUNK_LOG]; }
+
+struct PinnedPair {   // two pinned staging buffers, freed with the call
+    void *p[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~PinnedPair() {
+        for (int k = 0; k < 2; ++k) {
+            if (ev[k]) (void)hipEventDestroy(ev[k]);
+            if (p[k]) (void)hipHostFree(p[k]);
+        }
+    }
+};
+
+template <class C>
+static int pk_load_bytes_impl(pm_ctx *ctx, const uint8_t *bytes, size_t len, int validate, int shard_rank, int shard_count, int layout,
+                              pm_pk **out) {
+    const size_t NB = 4 * C::FqP::N;
+    WireLayout w;
+    PM_TRY(pk_wire_parse<C>(bytes, len, w, ctx->err));
+    pm_pk *pk = new pm_pk();
+    auto fail = [&](int st, const std::string &why) { pk_release(pk); if (!why.empty()) ctx->err = "pm_pk_load_bytes: " + why; return st; };
+    int st = pk_init_layout<C>(ctx, pk, w.m0, w.mw, w.nr, shard_rank, shard_count, layout);
+    if (st) return fail(st, st == PM_ERR_HIP ? "" : "the key's shape or the shard arguments are not supported");
+    // the checks of pmhost::pk_load: the prover hashes the vk's n / m0 / omega while the device derives its own from the SAP header
+    if (w.vk_m0 != w.m0) return fail(PM_ERR_INVALID_ARG, "vk.m0 disagrees with the SAP matrices' m0");
+    if (w.n != pk->n || w.sigma != pk->sigma) return fail(PM_ERR_INVALID_ARG, "vk.n / vk.sigma disagree with the domain of the SAP matrices");
+    if (memcmp(w.omega, pk->omega, 32) != 0) return fail(PM_ERR_INVALID_ARG, "vk.omega is not the generator of the size-n domain");
+    for (int v = 0; v < PM_NUM_BASE_VECS; ++v)
+        if (w.vec_len[v] != pk->base_len[v])
+            return fail(PM_ERR_INVALID_ARG, std::string(BASE_VEC_NAMES[v]) + ": length " + std::to_string(w.vec_len[v]) +
+                                                " does not match the key's shape (" + std::to_string(pk->base_len[v]) + ")");
+    pm_csr m[3];
+    for (int k = 0; k < 3; ++k) {
+        if (w.col[k].empty()) { w.col[k].push_back(0); w.val[k].assign(4, 0); }   // non-null pointers for an empty matrix
+        m[k] = pm_csr{w.nr, w.rowptr[k].data(), w.col[k].data(), w.val[k].data()};
+        if (w.rowptr[k].size() != w.nr + 1) return fail(PM_ERR_INVALID_ARG, "a matrix does not have num_constraints rows");
+    }
+    st = pk_upload_matrices<C>(ctx, pk, &m[0], &m[1], &m[2]);
+    if (st) return fail(st, st == PM_ERR_HIP ? "" : "a matrix column is out of range");
+    // The compressed points of each requested range go through two staging slots, each a pinned host buffer and a device buffer:
+    // the host copies chunk k + 1 out of the caller's bytes (an mmap, say) while the device decodes chunk k.  A slot is refilled
+    // only after the decode that read it has finished (its event is recorded behind the kernel), whatever way the runtime moves
+    // the copy.  Refused points lower a per-vector slot; nothing is read back until the whole resident set is decoded.
+    const size_t CH = wire_chunk(ctx);
+    DevBuf d_in[2], d_bad;
+    struct Release { DevBuf *a; DevBuf &b; ~Release() { a[0].release(); a[1].release(); b.release(); } } release{d_in, d_bad};
+    PinnedPair pin;
+    if (d_in[0].reserve(CH * NB) != hipSuccess || d_in[1].reserve(CH * NB) != hipSuccess || d_bad.reserve(PM_NUM_BASE_VECS * 8) != hipSuccess)
+        return fail(PM_ERR_HIP, "out of device memory for the staging buffers");
+    for (int k = 0; k < 2; ++k)
+        if (hipHostMalloc(&pin.p[k], CH * NB, hipHostMallocDefault) != hipSuccess ||
+            hipEventCreateWithFlags(&pin.ev[k], hipEventDisableTiming) != hipSuccess)
+            return fail(PM_ERR_HIP, "out of pinned host memory for the staging buffers");
+    if (hipMemsetAsync(d_bad.p, 0xFF, PM_NUM_BASE_VECS * 8, ctx->stream) != hipSuccess) return fail(PM_ERR_HIP, "hipMemsetAsync failed");
+    unsigned long long *bad = d_bad.as<unsigned long long>();
+    int slot = 0;
+    bool used[2] = {false, false};
+    st = pk_fill_resident<C>(ctx, pk, [&](int v, uint64_t start, uint64_t count, Affine<C> *dst) -> int {
+        for (uint64_t s = 0; s < count; s += CH) {
+            const uint64_t cnt = std::min<uint64_t>(CH, count - s);
+            if (used[slot]) PM_HIP(ctx, hipEventSynchronize(pin.ev[slot]));
+            memcpy(pin.p[slot], bytes + w.vec_off[v] + (start + s) * NB, cnt * NB);
+            PM_HIP(ctx, hipMemcpyAsync(d_in[slot].p, pin.p[slot], cnt * NB, hipMemcpyHostToDevice, ctx->stream));
+            PM_TRY(g1_decode_device<C>(ctx, d_in[slot].as<uint8_t>(), cnt, validate != 0, dst + s, nullptr, bad + v, start + s));
+            PM_HIP(ctx, hipEventRecord(pin.ev[slot], ctx->stream));
+            used[slot] = true;
+            slot ^= 1;
+            PM_TRY(bases_convert<C>(ctx, dst + s, cnt, true));
+        }
+        return PM_OK;
+    });
+    if (st) return fail(st, "");
+    unsigned long long h_bad[PM_NUM_BASE_VECS];
+    if (hipMemcpy(h_bad, d_bad.p, sizeof(h_bad), hipMemcpyDeviceToHost) != hipSuccess) return fail(PM_ERR_HIP, "reading the verdicts failed");
+    for (int v : WIRE_VECTOR_ORDER)
+        if (h_bad[v] != ~0ull)
+            return fail(PM_ERR_INVALID_ARG, std::string(BASE_VEC_NAMES[v]) + "[" + std::to_string(h_bad[v] >> 8) + "]: " +
+                                                g1_status_text(C::ID, (int)(h_bad[v] & 0xFF)));
+    d_in[0].release();
+    d_in[1].release();
+    st = pk_build_tables<C>(ctx, pk);
+    if (st) return fail(st, "");
+    *out = pk;
+    return PM_OK;
+}
+
+extern "C" int pm_pk_load_bytes(pm_ctx *ctx, int curve, const uint8_t *bytes, size_t len, int validate, int shard_rank, int shard_count,
+                                int layout, pm_pk **out) {
+    if (!ctx || !bytes || !out) return PM_ERR_INVALID_ARG;
+    *out = nullptr;
+    PM_TRY(set_device(ctx));
+    try {
+        return PM_DISPATCH(curve, pk_load_bytes_impl<BlsCurve>(ctx, bytes, len, validate, shard_rank, shard_count, layout, out),
+                           pk_load_bytes_impl<BnCurve>(ctx, bytes, len, validate, shard_rank, shard_count, layout, out));
+    } catch (const std::exception &e) {       // host allocation failure while parsing the matrices: a status, never an abort
+        ctx->err = e.what();
+        return PM_ERR_STATE;
+    }
+}
+
+template <class C>
+static int g1_decode_impl(pm_ctx *ctx, const uint8_t *in, size_t count, int validate, uint64_t *out_xy, uint8_t *status) {
+    const size_t NB = 4 * C::FqP::N, CH = wire_chunk(ctx);
+    DevBuf d_in, d_out, d_st;
+    struct Release { DevBuf &a, &b, &c; ~Release() { a.release(); b.release(); c.release(); } } release{d_in, d_out, d_st};
+    const size_t first = std::min(count, CH);
+    PM_HIP(ctx, d_in.reserve(first * NB));
+    PM_HIP(ctx, d_out.reserve(first * sizeof(Affine<C>)));
+    PM_HIP(ctx, d_st.reserve(first));
+    for (size_t s = 0; s < count; s += CH) {
+        const size_t cnt = std::min(CH, count - s);
+        PM_HIP(ctx, hipMemcpyAsync(d_in.p, in + s * NB, cnt * NB, hipMemcpyHostToDevice, ctx->stream));
+        PM_TRY(g1_decode_device<C>(ctx, d_in.as<uint8_t>(), cnt, validate != 0, d_out.as<Affine<C>>(), d_st.as<uint8_t>(), nullptr, 0));
+        PM_HIP(ctx, hipMemcpyAsync((uint8_t *)out_xy + s * sizeof(Affine<C>), d_out.p, cnt * sizeof(Affine<C>), hipMemcpyDeviceToHost, ctx->stream));
+        PM_HIP(ctx, hipMemcpyAsync(status + s, d_st.p, cnt, hipMemcpyDeviceToHost, ctx->stream));
+        PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return PM_OK;
+}
+
+extern "C" int pm_g1_decode(pm_ctx *ctx, int curve, const uint8_t *in, size_t count, int validate, uint64_t *out_xy, uint8_t *status) {
+    if (!ctx || (count && (!in || !out_xy || !status))) return PM_ERR_INVALID_ARG;
+    if (!count) return PM_OK;
+    PM_TRY(set_device(ctx));
+    return PM_DISPATCH(curve, g1_decode_impl<BlsCurve>(ctx, in, count, validate, out_xy, status),
+                       g1_decode_impl<BnCurve>(ctx, in, count, validate, out_xy, status));
 }
 
 // generate_proving_key (generator.rs:24-167) with the trapdoors supplied.  The dense uj_wj_lcs loop
@@ -870,29 +1022,61 @@ extern "C" int pm_pk_msm_plan(const pm_pk *pk, int which, uint64_t *pairs, unsig
     return PM_OK;
 }
 
+// Device element offset of [offset, offset + len) of base vector `which`; false if that range is not resident on this shard.
+static bool pk_dev_range(const pm_pk *pk, int which, size_t offset, size_t len, uint64_t *dev_off) {
+    uint64_t lo = pk->seg_off[which] + offset, hi = lo + len;
+    if (pk->shard_count == 1 && pk->layout == PM_SHARD_PAIRS) {
+        *dev_off = lo;
+        return true;
+    }
+    for (int k = 0; k < 3; ++k) {
+        uint64_t at = pk->res_dev_off[k];
+        for (const auto &pc : pk->pieces[k]) {
+            if (lo >= pc.cat_lo && hi <= pc.cat_lo + pc.count) { *dev_off = at + (lo - pc.cat_lo); return true; }
+            at += pc.count;
+        }
+    }
+    return false;
+}
+
 extern "C" int pm_pk_export_bases(pm_ctx *ctx, const pm_pk *pk, int which, size_t offset, size_t len, uint64_t *out_xy) {
     if (!ctx || !pk || !out_xy || which < 0 || which >= PM_NUM_BASE_VECS) return PM_ERR_INVALID_ARG;
     if (offset + len > pk->base_len[which]) return PM_ERR_INVALID_ARG;
     PM_TRY(set_device(ctx));
     size_t pt = pk->curve == PM_BLS12_381 ? sizeof(Affine<BlsCurve>) : sizeof(Affine<BnCurve>);
-    uint64_t lo = pk->seg_off[which] + offset, hi = lo + len;
     uint64_t dev_off = 0;
-    bool found = false;
-    if (pk->shard_count == 1 && pk->layout == PM_SHARD_PAIRS) {
-        dev_off = lo;
-        found = true;
-    } else {
-        for (int k = 0; k < 3 && !found; ++k) {
-            uint64_t at = pk->res_dev_off[k];
-            for (const auto &pc : pk->pieces[k]) {
-                if (lo >= pc.cat_lo && hi <= pc.cat_lo + pc.count) { dev_off = at + (lo - pc.cat_lo); found = true; break; }
-                at += pc.count;
-            }
-        }
-    }
-    if (!found) return PM_ERR_INVALID_ARG;  // not resident on this shard
+    if (!pk_dev_range(pk, which, offset, len, &dev_off)) return PM_ERR_INVALID_ARG;  // not resident on this shard
     const void *src = (const uint8_t *)pk->d_bases + dev_off * pt;
     return PM_DISPATCH(pk->curve, download_points<BlsCurve>(ctx, src, len, out_xy), download_points<BnCurve>(ctx, src, len, out_xy));
+}
+
+// resident (internal-form) points -> standard form -> compressed records, in chunks through the context's scratch
+template <class C>
+static int export_compressed_impl(pm_ctx *ctx, const Affine<C> *d_src, size_t len, uint8_t *out) {
+    const size_t NB = 4 * C::FqP::N, CH = wire_chunk(ctx), first = std::min(len, CH);
+    PM_HIP(ctx, ctx->scratch.reserve(first * (sizeof(Affine<C>) + NB)));
+    Affine<C> *d_pts = ctx->scratch.as<Affine<C>>();
+    uint8_t *d_rec = (uint8_t *)(d_pts + first);   // sizeof(Affine<C>) = 96 / 64 bytes: 16-byte aligned
+    for (size_t s = 0; s < len; s += CH) {
+        const size_t cnt = std::min(CH, len - s);
+        PM_HIP(ctx, hipMemcpyAsync(d_pts, d_src + s, cnt * sizeof(Affine<C>), hipMemcpyDeviceToDevice, ctx->stream));
+        PM_TRY(bases_convert<C>(ctx, d_pts, cnt, false));
+        PM_TRY(g1_encode_device<C>(ctx, d_pts, cnt, d_rec));
+        PM_HIP(ctx, hipMemcpyAsync(out + s * NB, d_rec, cnt * NB, hipMemcpyDeviceToHost, ctx->stream));
+        PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return PM_OK;
+}
+
+extern "C" int pm_pk_export_bases_compressed(pm_ctx *ctx, const pm_pk *pk, int which, size_t offset, size_t len, uint8_t *out) {
+    if (!ctx || !pk || !out || which < 0 || which >= PM_NUM_BASE_VECS) return PM_ERR_INVALID_ARG;
+    if (offset + len > pk->base_len[which]) return PM_ERR_INVALID_ARG;
+    PM_TRY(set_device(ctx));
+    uint64_t dev_off = 0;
+    if (!pk_dev_range(pk, which, offset, len, &dev_off)) return PM_ERR_INVALID_ARG;  // not resident on this shard
+    if (!len) return PM_OK;
+    return PM_DISPATCH(pk->curve, export_compressed_impl<BlsCurve>(ctx, (const Affine<BlsCurve> *)pk->d_bases + dev_off, len, out),
+                       export_compressed_impl<BnCurve>(ctx, (const Affine<BnCurve> *)pk->d_bases + dev_off, len, out));
 }
 
 // -------------------------------------------------------------------------------- prove

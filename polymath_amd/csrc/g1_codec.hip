@@ -1,0 +1,237 @@
+// Compressed G1 points on the device: ProvingKey::serialize_compressed (data_structures.rs:56-73) holds every base as
+// ark-serialize's compressed encoding, and a key from somebody else's setup arrives as exactly that.  Decoding costs one
+// square root in Fq per point (and, under Validate::Yes, a subgroup check on BLS12-381): ~4 400 Fq products a point, 26 M
+// points at 2^20 gates -- hours on one host thread, about a second here.  The host mirror polymath_amd/host/wire.hpp
+// (deser_g1, ser_g1, g1_in_subgroup) is the bit-exact specification of both kernels.
+//
+// One lane per point.  Flags, infinity and malformed input are MASKED, not branched on: a lane whose encoding has already
+// failed (or is the point at infinity) runs the same square-root chain and subgroup loop on a dummy value and drops the
+// result, so the exponent chain and the scalar loop stay wave-uniform.
+#include <algorithm>
+#include <cstring>
+
+#include "internal.h"
+#include "../host/wire.hpp"
+
+namespace pm {
+
+// canonical a > (p - 1) / 2, i.e. a > -a in the integer order deser_g1 compares in (fq_cmp(y, -y) > 0)
+template <class P>
+__host__ __device__ __forceinline__ bool fq_canon_gt_half(const Fp<P> &a) {
+    bool gt = false, decided = false;
+#pragma unroll
+    for (int i = P::N - 1; i >= 0; --i) {
+        const uint32_t h = (P::MOD[i] >> 1) | (i + 1 < P::N ? P::MOD[i + 1] << 31 : 0u);
+        if (!decided && a.l[i] != h) { gt = a.l[i] > h; decided = true; }
+    }
+    return gt;
+}
+
+// canonical a < p
+template <class P>
+__device__ __forceinline__ bool fq_canon_lt_p(const Fp<P> &a) {
+    bool lt = false, decided = false;
+#pragma unroll
+    for (int i = P::N - 1; i >= 0; --i)
+        if (!decided && a.l[i] != P::MOD[i]) { lt = a.l[i] < P::MOD[i]; decided = true; }
+    return lt;
+}
+
+// a^((p+1)/4): the square root when one exists (p = 3 mod 4 on both curves; p + 1 does not carry out of limb 0).  The exponent
+// is a constant: its bits are the same on every lane, so the branch below is a scalar one.
+template <class P>
+__device__ Fp<P> fq_pow_p1_4(const Fp<P> &a) {
+    Fp<P> acc = Fp<P>::one();
+#pragma unroll 1
+    for (int i = P::N - 1; i >= 0; --i) {
+        const uint32_t lo = P::MOD[i] + (i == 0 ? 1u : 0u), hi = i + 1 < P::N ? P::MOD[i + 1] : 0u;
+        const uint32_t e = (lo >> 2) | (hi << 30);
+#pragma unroll 1
+        for (int b = 31; b >= 0; --b) {
+            acc = sqr<P>(acc);
+            if ((e >> b) & 1u) acc = mul<P>(acc, a);
+        }
+    }
+    return acc;
+}
+
+// [r] P == O (g1_in_subgroup of wire.hpp, the same double-and-add over the bits of r): P affine, Montgomery, not infinity
+template <class C>
+__device__ bool g1_r_torsion(const Affine<C> &p) {
+    typedef typename C::FrP R;
+    XYZZ<C> acc = XYZZ<C>::identity();
+#pragma unroll 1
+    for (int i = R::N - 1; i >= 0; --i) {
+        const uint32_t e = R::MOD[i];
+#pragma unroll 1
+        for (int b = 31; b >= 0; --b) {
+            acc = xyzz_dbl<C>(acc);
+            if ((e >> b) & 1u) xyzz_madd<C>(acc, p, false);
+        }
+    }
+    return acc.is_identity();
+}
+
+template <class C>
+__global__ __launch_bounds__(256, 2) void k_g1_decode(const uint8_t *in, size_t count, int validate, Affine<C> *out, uint8_t *status,
+                                                   unsigned long long *first_bad, uint64_t base_index) {
+    typedef typename C::FqP P;
+    typedef Fp<P> Fq;
+    constexpr int NW = P::N, NB = 4 * NW;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    uint32_t w[NW];
+    const uint4 *src = (const uint4 *)(in + i * NB);   // NB = 48 / 32 and a 16-byte aligned base: whole 16-byte loads
+#pragma unroll
+    for (int k = 0; k < NB / 16; ++k) {
+        const uint4 v = src[k];
+        w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w;
+    }
+    Fq x;
+    bool inf, larger;
+    int st = PM_G1_OK;
+    if (C::ID == 0) {   // zcash: big-endian, flags in the first byte
+        const uint32_t flags = w[0] & 0xFFu;
+#pragma unroll
+        for (int k = 0; k < NW; ++k) x.l[k] = __builtin_bswap32(w[NW - 1 - k]);
+        x.l[NW - 1] &= 0x1FFFFFFFu;
+        inf = (flags & 0x40u) != 0;
+        larger = (flags & 0x20u) != 0;
+        if (!(flags & 0x80u)) st = PM_G1_BAD_FLAGS;
+        else if (inf && larger) st = PM_G1_INF_SIGN;
+    } else {            // ark short Weierstrass: little-endian, flags in the last byte
+        const uint32_t flags = w[NW - 1] >> 24;
+#pragma unroll
+        for (int k = 0; k < NW; ++k) x.l[k] = w[k];
+        x.l[NW - 1] &= 0x3FFFFFFFu;
+        inf = (flags & 0x40u) != 0;
+        larger = (flags & 0x80u) != 0;
+        if (inf && larger) st = PM_G1_BAD_FLAGS;
+    }
+    if (st == PM_G1_OK && inf && !x.is_zero()) st = PM_G1_NONCANONICAL_INF;
+    if (st == PM_G1_OK && !inf && !fq_canon_lt_p<P>(x)) st = PM_G1_COORD_GE_P;
+    const bool live = st == PM_G1_OK && !inf;          // lanes that decode a real point; the others compute on x = 0
+    Fq b;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) b.l[k] = C::B_MONT[k];
+    const Fq xm = live ? to_mont<P>(x) : Fq::zero();
+    const Fq rhs = add<P>(mul<P>(sqr<P>(xm), xm), b);
+    Fq y = fq_pow_p1_4<P>(rhs);
+    if (live && !sqr<P>(y).eq(rhs)) st = PM_G1_NOT_ON_CURVE;
+    if (fq_canon_gt_half<P>(from_mont<P>(y)) != larger) y = neg<P>(y);
+    Affine<C> pt{xm, y};
+    if (C::ID == 0 && validate) {                      // BN254's G1 has cofactor 1: nothing to check there
+        Affine<C> probe = pt;
+        if (!(live && st == PM_G1_OK)) {               // masked lane: the generator stands in
+#pragma unroll
+            for (int k = 0; k < NW; ++k) { probe.x.l[k] = C::GX_MONT[k]; probe.y.l[k] = C::GY_MONT[k]; }
+        }
+        const bool in_g1 = g1_r_torsion<C>(probe);
+        if (live && st == PM_G1_OK && !in_g1) st = PM_G1_NOT_IN_SUBGROUP;
+    }
+    if (st != PM_G1_OK || inf) pt = Affine<C>::infinity();   // the ABI's infinity: x = y = 0
+    out[i] = pt;
+    if (status) status[i] = (uint8_t)st;
+    if (st != PM_G1_OK && first_bad) atomicMin(first_bad, (unsigned long long)(((base_index + i) << 8) | (uint64_t)st));
+}
+
+template <class C>
+__global__ __launch_bounds__(256) void k_g1_encode(const Affine<C> *pts, size_t count, uint8_t *out) {
+    typedef typename C::FqP P;
+    typedef Fp<P> Fq;
+    constexpr int NW = P::N, NB = 4 * NW;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const Affine<C> a = pts[i];
+    const bool inf = a.is_inf();
+    const Fq x = from_mont<P>(a.x);
+    const bool larger = !inf && fq_canon_gt_half<P>(from_mont<P>(a.y));
+    uint32_t w[NW];
+    if (C::ID == 0) {
+#pragma unroll
+        for (int k = 0; k < NW; ++k) w[k] = __builtin_bswap32(x.l[NW - 1 - k]);
+        w[0] |= 0x80u | (inf ? 0x40u : 0u) | (larger ? 0x20u : 0u);
+    } else {
+#pragma unroll
+        for (int k = 0; k < NW; ++k) w[k] = x.l[k];
+        w[NW - 1] |= ((inf ? 0x40u : 0u) | (larger ? 0x80u : 0u)) << 24;
+    }
+    uint4 *dst = (uint4 *)(out + i * NB);
+#pragma unroll
+    for (int k = 0; k < NB / 16; ++k) dst[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+}
+
+template <class C>
+int g1_decode_device(pm_ctx *ctx, const uint8_t *d_in, size_t count, bool validate, Affine<C> *d_out, uint8_t *d_status,
+                     unsigned long long *d_first_bad, uint64_t base_index) {
+    if (!count) return PM_OK;
+    if (((uintptr_t)d_in & 15) != 0) { ctx->err = "g1_decode: staging not 16-byte aligned"; return PM_ERR_STATE; }
+    hipLaunchKernelGGL(k_g1_decode<C>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, d_in, count, validate ? 1 : 0,
+                       d_out, d_status, d_first_bad, base_index);
+    PM_HIP(ctx, hipGetLastError());
+    return PM_OK;
+}
+
+template <class C>
+int g1_encode_device(pm_ctx *ctx, const Affine<C> *d_pts, size_t count, uint8_t *d_out) {
+    if (!count) return PM_OK;
+    if (((uintptr_t)d_out & 15) != 0) { ctx->err = "g1_encode: staging not 16-byte aligned"; return PM_ERR_STATE; }
+    hipLaunchKernelGGL(k_g1_encode<C>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, d_pts, count, d_out);
+    PM_HIP(ctx, hipGetLastError());
+    return PM_OK;
+}
+
+const char *g1_status_text(int curve, int status) {
+    switch (status) {
+    case PM_G1_OK: return "ok";
+    case PM_G1_BAD_FLAGS: return curve == PM_BLS12_381 ? "G1: not a compressed point" : "G1: both flag bits set";
+    case PM_G1_COORD_GE_P: return "G1: coordinate >= p";
+    case PM_G1_NOT_ON_CURVE: return "G1: not on the curve";
+    case PM_G1_NOT_IN_SUBGROUP: return "G1: not in the prime-order subgroup";
+    case PM_G1_NONCANONICAL_INF: return "G1: non-canonical encoding of the point at infinity";
+    case PM_G1_INF_SIGN: return "G1: sign bit on the point at infinity";
+    default: return "G1: unknown status";
+    }
+}
+
+// The key's byte string parsed as far as the host needs it: vk (points validated: four of them), the SAP header and matrices,
+// and where each base vector's compressed points start.  The points themselves are left to k_g1_decode.
+template <class C>
+int pk_wire_parse(const uint8_t *data, size_t len, WireLayout &out, std::string &err) {
+    const size_t NB = 4 * C::FqP::N;
+    try {
+        pmhost::Reader rd(data, len);
+        const pmhost::VerifyingKeyT<C> vk = pmhost::read_vk_c<C>(rd);
+        out.vk_len = rd.off;
+        out.n = vk.n; out.vk_m0 = vk.m0; out.sigma = vk.sigma;
+        memcpy(out.omega, vk.omega.l, 32);
+        out.m0 = rd.u64(); out.mw = rd.u64(); out.nr = rd.u64();
+        for (int k = 0; k < 3; ++k) {
+            pmhost::CsrHost m = pmhost::WireKey<C>::get_matrix(rd);
+            out.rowptr[k] = std::move(m.rowptr);
+            out.col[k] = std::move(m.col);
+            out.val[k] = std::move(m.val);
+        }
+        for (int which : pmhost::PK_WIRE_VECTORS) {
+            const uint64_t cnt = rd.u64();
+            if (cnt > (len - rd.off) / NB) throw pmhost::WireError("truncated key");
+            out.vec_len[which] = cnt;
+            out.vec_off[which] = rd.off;
+            rd.off += cnt * NB;
+        }
+        if (rd.off != len) throw pmhost::WireError("trailing bytes after the key");
+    } catch (const std::exception &e) {
+        err = std::string("pm_pk_load_bytes: ") + e.what();
+        return PM_ERR_INVALID_ARG;
+    }
+    return PM_OK;
+}
+
+#define PM_INST(C)                                                                                                              \
+    template int g1_decode_device<C>(pm_ctx *, const uint8_t *, size_t, bool, Affine<C> *, uint8_t *, unsigned long long *, uint64_t); \
+    template int g1_encode_device<C>(pm_ctx *, const Affine<C> *, size_t, uint8_t *);                                          \
+    template int pk_wire_parse<C>(const uint8_t *, size_t, WireLayout &, std::string &);
+PM_INST(BlsCurve)
+PM_INST(BnCurve)
+
+}  // namespace pm

@@ -380,6 +380,28 @@ int fixed_base_batch(pm_ctx *ctx, const Fp<typename C::FrP> *d_scalars, size_t l
 template <class C>
 int bases_convert(pm_ctx *ctx, Affine<C> *d_points, size_t len, bool to_internal);
 
+// g1_codec.hip: compressed G1 (include/polymath_hip.h, pm_g1_status).  Decode: `count` records of 4 fq words each at d_in (16-byte
+// aligned) -> standard-Montgomery affine points (refused and infinity: x = y = 0); d_status (optional) one pm_g1_status per point;
+// d_first_bad (optional) atomically lowered to ((base_index + i) << 8 | status) for every refused point i.  Encode: the inverse,
+// standard-Montgomery points -> records (d_out 16-byte aligned).
+template <class C>
+int g1_decode_device(pm_ctx *ctx, const uint8_t *d_in, size_t count, bool validate, Affine<C> *d_out, uint8_t *d_status,
+                     unsigned long long *d_first_bad, uint64_t base_index);
+template <class C>
+int g1_encode_device(pm_ctx *ctx, const Affine<C> *d_pts, size_t count, uint8_t *d_out);
+const char *g1_status_text(int curve, int status);
+// ProvingKey::serialize_compressed parsed on the host without touching its base points (pk_wire_parse)
+struct WireLayout {
+    size_t vk_len = 0;
+    uint64_t n = 0, vk_m0 = 0, sigma = 0, omega[4] = {0, 0, 0, 0};   // the vk's header fields
+    uint64_t m0 = 0, mw = 0, nr = 0;                                  // the SAP matrices' header
+    std::vector<uint64_t> rowptr[3], val[3];                          // a, b, c as serialised (duplicates kept), val Montgomery
+    std::vector<uint32_t> col[3];
+    uint64_t vec_off[PM_NUM_BASE_VECS] = {0}, vec_len[PM_NUM_BASE_VECS] = {0};   // by pm_base_vec: byte offset of point 0, points
+};
+template <class C>
+int pk_wire_parse(const uint8_t *data, size_t len, WireLayout &out, std::string &err);
+
 // setup.hip: the uj_wj_lcs scalars of generator.rs:112-136 on the device (Lagrange coefficients at x + the sparse pass over the
 // key's CSR matrices); `lagrange` and `work` are scratch the caller releases
 template <class C>

@@ -250,6 +250,13 @@ def deser_g2(field, b):
     return ((x0, x1), neg if _fq2_gt(y, neg) != bool(b[0] & 0x20) else y)
 
 
+def _csr_rows(field, csr, nr):
+    """api.CsrArrays (Montgomery values) -> rows of (canonical value, column)"""
+    vals = [_from_limbs(v) * field.Rr_inv % field.r for v in csr.val.tolist()]
+    cols, rp = csr.col.tolist(), csr.rowptr.tolist()
+    return [[(vals[k], cols[k]) for k in range(rp[i], rp[i + 1])] for i in range(nr)]
+
+
 def ser_matrix(field, rows):
     out = [_u64(len(rows))]
     for row in rows:
@@ -487,6 +494,33 @@ class Polymath:
         pk = api.ProvingKey.load(self.ctx, self.curve, vk.n, m0, mw, nr, vk.sigma, A, B, C, arrays, shard_rank, shard_count)
         pk.omega = vk.omega
         return pk, vk, r1cs
+
+    # ---- the same wire format with the points on the device (pm_pk_load_bytes / pm_pk_export_bases_compressed): both curves
+    VK_BYTES = {"bls12_381": 392, "bn254": 280}             # VerifyingKey::serialize_compressed: the key's first field
+
+    def pk_load_bytes(self, data, validate=True, shard_rank=0, shard_count=1, layout="pairs"):
+        """ProvingKey::serialize_compressed bytes (bytes, memoryview or an np.memmap of the file) -> (device-resident ProvingKey,
+        vk bytes).  The points are decoded on the GPU; validate = ark's Validate::Yes (subgroup check on BLS12-381), False =
+        deserialize_compressed_unchecked.  The vk is returned as its bytes (the key's prefix) on both curves: verify takes bytes."""
+        pk = api.ProvingKey.load_bytes(self.ctx, self.curve, data, validate, shard_rank, shard_count, layout)
+        pk.omega = self.field.fr_int(pk.omega_limbs)
+        return pk, bytes(memoryview(data)[:self.VK_BYTES[self.curve]])
+
+    def pk_serialize(self, pk, r1cs, vk_bytes):
+        """ProvingKey::serialize_compressed of a resident key, the six vectors encoded on the GPU (equals pk_to_bytes on
+        BLS12-381).  vk_bytes: VerifyingKey::serialize_compressed (VerifyingKey.to_bytes, or api.make_vk on either curve)."""
+        f = self.field
+        if len(vk_bytes) != self.VK_BYTES[self.curve]:
+            raise ValueError("vk_bytes: %d bytes, expected %d" % (len(vk_bytes), self.VK_BYTES[self.curve]))
+        if isinstance(r1cs, LimbCircuit):     # matrices as limb arrays (synthetic_r1cs_native): rows read back from the CSR
+            mats = [_csr_rows(f, m, r1cs.nr) for m in r1cs.csrs]
+        else:
+            mats = [r1cs.a, r1cs.b, r1cs.c]
+        out = [bytes(vk_bytes), _u64(r1cs.m0), _u64(r1cs.mw), _u64(r1cs.nr)] + [ser_matrix(f, m) for m in mats]
+        for which in PK_WIRE_VECTORS:
+            out.append(_u64(pk.base_lens[which]))
+            out.append(pk.export_bases_compressed(which))
+        return b"".join(out)
 
     # ---- common.rs:21-71
     def compute_x1(self, t, public_inputs, commitments):

@@ -53,13 +53,23 @@ pub const PM_OPT_MAX_SEG_LOG: i32 = 4;
 pub const PM_OPT_INFLIGHT_CONTEXTS: i32 = 5;
 pub const PM_OPT_MSM_TASK_LEN: i32 = 6;
 pub const PM_OPT_TABLE_WINDOW_BITS: i32 = 7;
-pub const PM_NUM_OPTIONS: i32 = 8;
+pub const PM_OPT_WIRE_CHUNK_LOG: i32 = 8;
+pub const PM_NUM_OPTIONS: i32 = 9;
 
 // pm_tables_mode
 pub const PM_TABLES_OFF: c_longlong = 0;
 pub const PM_TABLES_AUTO: c_longlong = 1;
 pub const PM_TABLES_WIDE: c_longlong = 2;
 pub const PM_TABLES_NO_WIDE: c_longlong = 3;
+
+// pm_g1_status: the verdict of one compressed G1 encoding (pm_g1_decode)
+pub const PM_G1_OK: u8 = 0;
+pub const PM_G1_BAD_FLAGS: u8 = 1;
+pub const PM_G1_COORD_GE_P: u8 = 2;
+pub const PM_G1_NOT_ON_CURVE: u8 = 3;
+pub const PM_G1_NOT_IN_SUBGROUP: u8 = 4;
+pub const PM_G1_NONCANONICAL_INF: u8 = 5;
+pub const PM_G1_INF_SIGN: u8 = 6;
 
 // pm_transcript
 pub const PM_TRANSCRIPT_MERLIN: i32 = 0;
@@ -143,6 +153,10 @@ extern "C" {
     pub fn pm_pk_msm_plan(pk: *const pm_pk, which: i32, pairs: *mut u64, windows: *mut u32, window_bits: *mut u32, tables: *mut i32) -> i32;
     pub fn pm_pk_export_bases(ctx: *mut pm_ctx, pk: *const pm_pk, which: i32, offset: usize, len: usize, out_xy: *mut u64) -> i32;
     pub fn pm_pk_free(pk: *mut pm_pk);
+    // ---- proving keys as bytes: ProvingKey::serialize_compressed, points decoded / encoded on the device
+    pub fn pm_g1_decode(ctx: *mut pm_ctx, curve: i32, input: *const u8, count: usize, validate: i32, out_xy: *mut u64, status: *mut u8) -> i32;
+    pub fn pm_pk_load_bytes(ctx: *mut pm_ctx, curve: i32, bytes: *const u8, len: usize, validate: i32, shard_rank: i32, shard_count: i32, layout: i32, out: *mut *mut pm_pk) -> i32;
+    pub fn pm_pk_export_bases_compressed(ctx: *mut pm_ctx, pk: *const pm_pk, which: i32, offset: usize, len: usize, out: *mut u8) -> i32;
     // ---- prove: create_proof_with_assignment (prover.rs:66-237) split at its two transcript calls
     pub fn pm_prove_phase1(ctx: *mut pm_ctx, pk: *const pm_pk, x: *const u64, w: *const u64, r_a: *const u64, a_g1_xy: *mut u64, a_inf: *mut i32, c_g1_xy: *mut u64, c_inf: *mut i32) -> i32;
     pub fn pm_prove_phase1_device(ctx: *mut pm_ctx, pk: *const pm_pk, d_x: *const u64, d_w: *const u64, r_a: *const u64, a_g1_xy: *mut u64, a_inf: *mut i32, c_g1_xy: *mut u64, c_inf: *mut i32) -> i32;

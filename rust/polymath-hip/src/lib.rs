@@ -562,6 +562,23 @@ impl GpuKey {
         Ok(GpuKey { raw, curve, m0: k.m0, mw: k.mw })
     }
 
+    /// `pm_pk_load_bytes`: a key file's bytes (`ProvingKey::serialize_compressed`, e.g. an mmap) straight to the device; the
+    /// points are decoded there, with `validate` as ark's `Validate::Yes`.  A refused key names its first bad point in the error.
+    pub fn load_bytes<E: Pairing>(ctx: &mut Context, bytes: &[u8], validate: bool) -> Result<GpuKey, HipError> {
+        let curve = curve_checked::<E>()?;
+        let vk_len = if curve.id() == sys::PM_BLS12_381 { 392 } else { 280 };
+        let header = |k: usize| bytes.get(vk_len + 8 * k..vk_len + 8 * k + 8).map(|b| u64::from_le_bytes(b.try_into().unwrap()));
+        let (m0, mw) = match (header(0), header(1)) {
+            (Some(m0), Some(mw)) => (m0, mw),
+            _ => return Err(err(Status::InvalidArg, "truncated key")),
+        };
+        let mut raw = core::ptr::null_mut();
+        // SAFETY: `bytes` outlives the call and is only read; the library keeps no pointer to it.
+        let rc = unsafe { sys::pm_pk_load_bytes(ctx.raw, curve.id(), bytes.as_ptr(), bytes.len(), validate as i32, 0, 1, sys::PM_SHARD_PAIRS, &mut raw) };
+        ctx.check(rc)?;
+        Ok(GpuKey { raw, curve, m0, mw })
+    }
+
     /// `pm_pk_load_sharded`: this rank's share of a key for ONE proof over `shard_count` GPUs (one process per GPU).  `layout`:
     /// [`ShardLayout::Vector`] shards witness map, transforms, scans and MSM pairs (the context must have been joined to its
     /// rank's [`Comm`] first); [`ShardLayout::Pairs`] shards the MSM pair ranges only and the phases return PARTIAL points

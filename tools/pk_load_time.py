@@ -1,0 +1,115 @@
+"""Time pm_pk_load_bytes: a ProvingKey::serialize_compressed byte string -> resident key, points decoded on the GPU.
+
+    python tools/pk_load_time.py [--log-gates 20] [--out FILE]
+
+BLS12-381, 2^k - 100 synthetic gates (k = 20: 27.3 M points).  The key is generated on the device and serialised with
+Polymath.pk_serialize; after one warm-up, pm_pk_load_bytes is timed three times each with validate 1 and 0 (each run ends
+with a stream synchronisation on the loading context), once more with the window tables off (tables = load - that), and
+pm_pk_load from already-decoded arrays is timed as today's path without its decoding cost.  The host baseline is
+tools/host_deser_time.cpp (the host mirror's deser_g1, one thread) on 10 000 of the key's records, scaled to the key.
+The decode kernel's own time comes from a separate `rocprofv3 --kernel-trace --stats` run of this script (--profile-only)."""
+import argparse
+import os
+import struct
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--log-gates", type=int, default=20)
+ap.add_argument("--out", default=None)
+ap.add_argument("--chunk-logs", default="", help="comma list of wire_chunk_log values to time once each (validate 1)")
+ap.add_argument("--profile-only", action="store_true", help="one validated load and nothing else (under rocprofv3)")
+args = ap.parse_args()
+
+from polymath_amd import api, circuits as PC            # noqa: E402
+from polymath_amd.polymath import Polymath              # noqa: E402
+
+lines = []
+
+
+def say(s):
+    print(s, flush=True)
+    lines.append(s)
+
+
+curve = "bls12_381"
+nr = (1 << args.log_gates) - 100
+pm = Polymath(curve, "merlin", device=0)
+c_r = pm.field.r
+lc = PC.synthetic_r1cs_native(curve, nr)
+g = PC.SplitMix64(0x10AD)
+x, z = g.fr(c_r), g.fr(c_r)
+t = time.perf_counter()
+pk = pm.setup(lc, x, z)
+say("key: %d gates, n = %d, %d points; generated in %.2f s" % (nr, pk.n, sum(pk.base_lens), time.perf_counter() - t))
+t = time.perf_counter()
+data = pm.pk_serialize(pk, lc, pm.make_vk(pk, x, z))
+say("pk_serialize: %d bytes in %.2f s (matrices serialised in Python)" % (len(data), time.perf_counter() - t))
+decoded = None if args.profile_only else [pk.export_bases(v) for v in range(6)]
+pk.free()
+
+
+def sync(k):
+    k.export_bases(1, 0, 1)          # a stream synchronisation on the loading context
+
+
+def load(validate):
+    t0 = time.perf_counter()
+    k = api.ProvingKey.load_bytes(pm.ctx, curve, data, validate)
+    sync(k)
+    dt = time.perf_counter() - t0
+    k.free()
+    return dt
+
+
+if args.profile_only:
+    say("validated load: %.3f s" % load(True))
+    sys.exit(0)
+
+load(True)                            # warm-up
+for validate in (1, 0):
+    ts = [load(bool(validate)) for _ in range(3)]
+    say("pm_pk_load_bytes validate=%d: %s s (best %.3f)" % (validate, " ".join("%.3f" % v for v in ts), min(ts)))
+tables = pm.ctx.get_option("tables")
+pm.ctx.set_option("tables", "off")
+for validate in (1, 0):
+    ts = [load(bool(validate)) for _ in range(2)]
+    say("pm_pk_load_bytes validate=%d, tables off: %s s" % (validate, " ".join("%.3f" % v for v in ts)))
+pm.ctx.set_option("tables", tables)
+for cl in [int(v) for v in args.chunk_logs.split(",") if v]:
+    old = pm.ctx.get_option("wire_chunk_log")
+    pm.ctx.set_option("wire_chunk_log", cl)
+    say("pm_pk_load_bytes validate=1, wire_chunk_log=%d: %.3f s" % (cl, load(True)))
+    pm.ctx.set_option("wire_chunk_log", old)
+A, B, C = lc.csrs
+for _ in range(2):
+    t0 = time.perf_counter()
+    k = api.ProvingKey.load(pm.ctx, curve, pk.n, lc.m0, lc.mw, lc.nr, pk.sigma, A, B, C, decoded)
+    sync(k)
+    say("pm_pk_load from decoded arrays (no decoding): %.3f s" % (time.perf_counter() - t0))
+    k.free()
+# host baseline: deser_g1 of the host mirror on 10 000 of the key's x_powers records
+exe = os.path.join(ROOT, "tools", "host_deser_time")
+subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tools", "host_deser_time.cpp")])
+off = 392 + 24
+for _ in range(3):
+    rows = struct.unpack_from("<Q", data, off)[0]
+    off += 8
+    for _ in range(rows):
+        off += 8 + 40 * struct.unpack_from("<Q", data, off)[0]
+with tempfile.NamedTemporaryFile(suffix=".bin") as f:
+    f.write(data[off + 8:off + 8 + 48 * 10000])
+    f.flush()
+    out = subprocess.run([exe, f.name], capture_output=True, text=True, check=True).stdout
+total = sum(len(d) for d in decoded)
+for line in out.strip().splitlines():
+    us = float(line.split(",")[1].split()[0])
+    say("%s -> x %d points = %.0f s on one thread" % (line, total, us * 1e-6 * total))
+if args.out:
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
