@@ -158,7 +158,7 @@ extern "C" void pm_ctx_destroy(pm_ctx *ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     timing_flush(ctx);
     MsmWorkspace &m = ctx->msm;
-    for (DevBuf *b : {&m.set.sorted, &m.set.counts, &m.set.bucket_off, &m.set.task_off, &m.set.order, &m.set.partials, &m.set.task_cnt}) b->release();
+    for (DevBuf *b : {&m.set.sorted, &m.set.counts, &m.set.bucket_off, &m.set.task_off, &m.set.tasks, &m.set.partials, &m.set.task_cnt}) b->release();
     for (DevBuf *b : {&m.digits, &m.cursor, &m.wsum,
                       &m.region, &m.sub, &m.digits2, &m.len_bins, &m.block_cnt, &m.hot, &ctx->scratch, &ctx->flags, &ctx->xw, &ctx->ue, &ctx->we, &ctx->u, &ctx->w,
                       &ctx->wit_u, &ctx->u2, &ctx->sc_a, &ctx->sc_c, &ctx->quotient, &ctx->ztail, &ctx->ra, &ctx->sh_a, &ctx->sh_b, &ctx->sh_c, &ctx->halo,

@@ -84,7 +84,7 @@ enum TimingSlot {
 
 // What one bucket pipeline hands from its sort to its accumulation and from there to the reduction.
 struct MsmSet {
-    DevBuf sorted, counts, bucket_off, task_off, order, partials, task_cnt;
+    DevBuf sorted, counts, bucket_off, task_off, tasks, partials, task_cnt;   // tasks: uint4 descriptors in accumulate order (msm.hip: k_task_bins)
 };
 struct MsmWorkspace {
     MsmSet set;

@@ -17,8 +17,9 @@
 //                 longer than SEG entries into SEG-sized tasks (skewed scalars -> hot buckets).
 //   k_scatter     same LDS staging: claim a range per (workgroup, bucket) with one global atomic,
 //                 then place entries with LDS atomics -> base indices grouped by bucket.
-//   k_task_bins   tasks ordered by descending length, so the lanes of a wave carry equal loads.
-//   k_accumulate  one lane per task: XYZZ mixed adds (8M+2S each) over its <= SEG entries;
+//   k_task_bins   task descriptors ordered by descending length, so the lanes of a wave carry equal loads.
+//   k_accumulate  persistent waves draw 64 descriptors at a time from a ticket counter; one lane per task: XYZZ
+//                 mixed adds (8M+2S each) over its <= SEG entries;
 //                 bases are gathered from HBM by index (96 B affine points, or 128 B TablePoint records).
 //   k_task_fold   buckets that own many tasks (skewed scalars) have their partials summed in parallel.
 //   k_bucket_reduce  per window sum_b (b+1) * B_b by per-lane running sums over K buckets, a
@@ -255,22 +256,25 @@ constexpr unsigned TASK_MAX_BINS = 8192;
 // One lane per BUCKET g (its tasks are task_off[g] .. task_off[g + 1] - 1: all but the last are full, L = seg, bin 0; the last
 // one has the remainder), so a lane issues at most two LDS atomics and no search.  (Round 2 ran one lane per TASK and found
 // the task's bucket by a 21-step binary search over task_off: 0.19 ms for the two launches at 2^21 buckets.)
+// The scatter pass writes each task's DESCRIPTOR at its place in the order: {partial slot t, first entry, end entry, 0}, so
+// k_accumulate reads one 16-byte record per task and nothing else of the bucket metadata.
 template <bool SCATTER>
-__global__ __launch_bounds__(1024) void k_task_bins(const uint32_t *counts, const uint32_t *task_off, size_t G, unsigned seg,
-                                                    unsigned lshift, unsigned nbins, uint32_t *len_cnt, const uint32_t *len_off,
-                                                    uint32_t *len_cursor, uint32_t *order) {
+__global__ __launch_bounds__(1024) void k_task_bins(const uint32_t *counts, const uint32_t *bucket_off, const uint32_t *task_off, size_t G,
+                                                    unsigned seg, unsigned lshift, unsigned nbins, uint32_t *len_cnt, const uint32_t *len_off,
+                                                    uint32_t *len_cursor, uint4 *tasks) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     uint32_t *h = (uint32_t *)smem_raw;
     for (unsigned b = threadIdx.x; b < nbins; b += blockDim.x) h[b] = 0;
     __syncthreads();
     const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t t0 = 0, n = 0, rank_full = 0, rank_last = 0;
+    uint32_t t0 = 0, n = 0, rank_full = 0, rank_last = 0, cnt = 0;
     unsigned bin = 0;
     if (g < G) {
         t0 = task_off[g];
         n = task_off[g + 1] - t0;
         if (n) {
-            const uint32_t L = counts[g] - (n - 1) * seg;           // 1 .. seg
+            cnt = counts[g];
+            const uint32_t L = cnt - (n - 1) * seg;                 // 1 .. seg
             bin = (seg - L) >> lshift;
             if (n > 1) rank_full = atomicAdd(&h[0], n - 1);
             rank_last = atomicAdd(&h[bin], 1u);
@@ -289,39 +293,22 @@ __global__ __launch_bounds__(1024) void k_task_bins(const uint32_t *counts, cons
         }
         __syncthreads();
         if (n) {
-            const uint32_t at = h[0] + rank_full;
-            for (uint32_t k = 0; k + 1 < n; ++k) order[at + k] = t0 + k;       // (a hot bucket: thousands; the rest: none or one)
-            order[h[bin] + rank_last] = t0 + n - 1;
+            const uint32_t at = h[0] + rank_full, first = bucket_off[g];
+            for (uint32_t k = 0; k + 1 < n; ++k)                           // (a hot bucket: thousands; the rest: none or one)
+                tasks[at + k] = make_uint4(t0 + k, first + k * seg, first + (k + 1) * seg, 0u);
+            tasks[h[bin] + rank_last] = make_uint4(t0 + n - 1, first + (n - 1) * seg, first + cnt, 0u);
         }
     }
 }
 
 // ---------------------------------------------------------------------------- accumulate
-// One lane per task (taken in order[]); TABLE selects the point record (TablePoint of a window table, or the
-// dense affine array of the per-window pipeline).  The accumulator lives in reduced-radix registers (fq28.cuh): 10 carry-free
-// Montgomery products and 7 lazy add/sub per mixed add.  `bases` are in INTERNAL Montgomery form.
+// One lane per task; TABLE selects the point record (TablePoint of a window table, or the dense affine array of the per-window
+// pipeline).  The accumulator lives in reduced-radix registers (fq28.cuh): 10 carry-free Montgomery products and 7 lazy add/sub
+// per mixed add.  `bases` are in INTERNAL Montgomery form.
 // The exceptional case acc == +-point (doubling / cancellation) is resolved on the dense path.
 template <class C, bool TABLE>
-__global__ __launch_bounds__(128) void k_accumulate(const uint32_t *sorted, const uint32_t *counts,
-                                                    const uint32_t *bucket_off, const uint32_t *task_off,
-                                                    const uint32_t *order, const void *points, XYZZ<C> *partials, size_t G,
-                                                    unsigned seg) {
+__device__ __forceinline__ void accumulate_task(const uint32_t *sorted, const uint4 d, const void *points, XYZZ<C> *partials) {
     typedef typename C::FqRR RR;
-    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t total = task_off[G];
-    if (t >= total) return;
-    t = order[t];   // tasks by descending length: equal loads inside a wave
-    // bucket of task t: largest g with task_off[g] <= t  (empty buckets have zero tasks)
-    size_t lo = 0, hi = G;
-    while (hi - lo > 1) {
-        size_t mid = (lo + hi) >> 1;
-        if (task_off[mid] <= t) lo = mid; else hi = mid;
-    }
-    const size_t g = lo;
-    const uint32_t k = (uint32_t)t - task_off[g];
-    const uint32_t start = bucket_off[g] + k * seg;
-    uint32_t end = bucket_off[g] + counts[g];
-    if (start + seg < end) end = start + seg;
     XYZZ28<C> acc;
     acc.X = acc.Y = acc.ZZ = acc.ZZZ = f28_zero<RR>();
 #ifndef PM_ACC_IDX_VEC
@@ -334,7 +321,7 @@ __global__ __launch_bounds__(128) void k_accumulate(const uint32_t *sorted, cons
     uint4 quad = make_uint4(0u, 0u, 0u, 0u);
     uint32_t quad_at = 0xffffffffu;
 #endif
-    for (uint32_t e = start; e < end; ++e) {
+    for (uint32_t e = d.y; e < d.z; ++e) {
 #if PM_ACC_IDX_VEC == 4
         if ((e & ~3u) != quad_at) {
             quad_at = e & ~3u;
@@ -357,7 +344,28 @@ __global__ __launch_bounds__(128) void k_accumulate(const uint32_t *sorted, cons
             if (!xyzz28_madd<C>(acc, p, neg)) acc = xyzz28_madd_exceptional<C>(acc, p, neg);
         }
     }
-    partials[t] = xyzz28_store<C>(acc);   // INTERNAL form: the bucket reduction stays on reduced-radix arithmetic
+    partials[d.x] = xyzz28_store<C>(acc);   // INTERNAL form: the bucket reduction stays on reduced-radix arithmetic
+}
+
+// Persistent lanes: the grid holds only as many workgroups as can be resident (accumulate() below), and a wave takes the next 64
+// descriptors of tasks[] (descending length: equal loads inside the wave) with one global atomic on the context's ticket
+// counter, until the tasks run out.  Waves never wait on each other, so the kernel can share the chip with another context's
+// launch.  (It replaced one lane per task over a grid of max_tasks lanes -- ~16 rounds of short-lived workgroups, ~1 M lanes
+// that only read task_off[G], a 21-probe search over task_off[] before each task's first gather: -1.3 ms per proof, DESIGN.md
+// §4.2.  Drawing the next ticket one batch early measured slower.)
+template <class C, bool TABLE>
+__global__ __launch_bounds__(128) void k_accumulate(const uint32_t *sorted, const uint32_t *task_off, const uint4 *tasks,
+                                                    const void *points, XYZZ<C> *partials, size_t G, uint32_t *ticket) {
+    const uint32_t total = task_off[G];
+    const unsigned lane = threadIdx.x & 63u;
+    for (;;) {
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(ticket, 64u);
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (base >= total) break;
+        const uint32_t i = base + lane;
+        if (i < total) accumulate_task<C, TABLE>(sorted, tasks[i], points, partials);
+    }
 }
 
 // ------------------------------------------------------------------------- bucket reduce
@@ -1064,24 +1072,42 @@ static int fold_hot_buckets(pm_ctx *ctx, MsmSet &S, size_t G, size_t max_tasks) 
     return PM_OK;
 }
 
-// order[] for k_accumulate (see k_task_bins); enqueued on the context's stream after the bucket scan.
+// tasks[] for k_accumulate (see k_task_bins); enqueued on the context's stream after the bucket scan.  Also zeroes the context's
+// accumulate ticket (the word in front of the length bins: one memset for both).
 static int task_order(pm_ctx *ctx, MsmSet &S, const uint32_t *counts, size_t G, size_t seg, size_t max_tasks) {
     MsmWorkspace &ws = ctx->msm;
     unsigned lshift = 0;
     while (((seg - 1) >> lshift) + 1 > TASK_MAX_BINS) ++lshift;
     const unsigned nbins = (unsigned)(((seg - 1) >> lshift) + 1);
-    PM_HIP(ctx, S.order.reserve(max_tasks * 4));
-    PM_HIP(ctx, ws.len_bins.reserve((3 * (size_t)nbins + 4) * 4));
-    uint32_t *len_cnt = ws.len_bins.as<uint32_t>(), *len_off = len_cnt + nbins, *len_cursor = len_off + nbins + 1;
-    PM_HIP(ctx, hipMemsetAsync(len_cnt, 0, (size_t)nbins * 4, ctx->stream));
+    PM_HIP(ctx, S.tasks.reserve(max_tasks * sizeof(uint4)));
+    PM_HIP(ctx, ws.len_bins.reserve((3 * (size_t)nbins + 5) * 4));
+    uint32_t *ticket = ws.len_bins.as<uint32_t>(), *len_cnt = ticket + 1, *len_off = len_cnt + nbins, *len_cursor = len_off + nbins + 1;
+    PM_HIP(ctx, hipMemsetAsync(ticket, 0, ((size_t)nbins + 1) * 4, ctx->stream));
     const unsigned blocks = (unsigned)((G + 1023) / 1024);      // one lane per bucket
-    hipLaunchKernelGGL(k_task_bins<false>, dim3(blocks), dim3(1024), nbins * 4, ctx->stream, counts, S.task_off.as<uint32_t>(), G,
-                       (unsigned)seg, lshift, nbins, len_cnt, (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_task_bins<false>, dim3(blocks), dim3(1024), nbins * 4, ctx->stream, counts, S.bucket_off.as<uint32_t>(),
+                       S.task_off.as<uint32_t>(), G, (unsigned)seg, lshift, nbins, len_cnt, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                       (uint4 *)nullptr);
     PM_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, ctx->stream, len_cnt, len_off, len_cursor, nbins);
     PM_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_task_bins<true>, dim3(blocks), dim3(1024), nbins * 4, ctx->stream, counts, S.task_off.as<uint32_t>(), G,
-                       (unsigned)seg, lshift, nbins, (uint32_t *)nullptr, len_off, len_cursor, S.order.as<uint32_t>());
+    hipLaunchKernelGGL(k_task_bins<true>, dim3(blocks), dim3(1024), nbins * 4, ctx->stream, counts, S.bucket_off.as<uint32_t>(),
+                       S.task_off.as<uint32_t>(), G, (unsigned)seg, lshift, nbins, (uint32_t *)nullptr, len_off, len_cursor,
+                       S.tasks.as<uint4>());
+    PM_HIP(ctx, hipGetLastError());
+    return PM_OK;
+}
+
+// k_accumulate over the tasks[] that task_order enqueued: a grid of as many 128-lane workgroups as the device holds at once (no
+// more than max_tasks lanes); the waves draw the tasks from the ticket that task_order zeroed.
+template <class C, bool TABLE>
+static int accumulate(pm_ctx *ctx, MsmSet &S, const void *points, size_t G, size_t max_tasks) {
+    int per_cu = 0, cus = 0;
+    PM_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_accumulate<C, TABLE>, 128, 0));
+    PM_HIP(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    size_t blocks = (size_t)(per_cu > 0 ? per_cu : 1) * (size_t)(cus > 0 ? cus : 1);
+    if (blocks > (max_tasks + 127) / 128) blocks = (max_tasks + 127) / 128;
+    hipLaunchKernelGGL((k_accumulate<C, TABLE>), dim3((unsigned)blocks), dim3(128), 0, ctx->stream, S.sorted.as<uint32_t>(),
+                       S.task_off.as<uint32_t>(), S.tasks.as<uint4>(), points, S.partials.as<XYZZ<C>>(), G, ctx->msm.len_bins.as<uint32_t>());
     PM_HIP(ctx, hipGetLastError());
     return PM_OK;
 }
@@ -1142,11 +1168,7 @@ static int msm_piece(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C:
     }
     {
         StageTimer t(ctx, T_MSM_ACCUMULATE);
-        size_t blocks = (p.max_tasks + 127) / 128;
-        hipLaunchKernelGGL((k_accumulate<C, false>), dim3((unsigned)blocks), dim3(128), 0, ctx->stream, S.sorted.as<uint32_t>(),
-                           counts, S.bucket_off.as<uint32_t>(), S.task_off.as<uint32_t>(), S.order.as<uint32_t>(), (const void *)d_bases,
-                           S.partials.as<XYZZ<C>>(), G, p.seg);
-        PM_HIP(ctx, hipGetLastError());
+        PM_TRY((accumulate<C, false>(ctx, S, (const void *)d_bases, G, p.max_tasks)));
     }
     std::vector<XYZZ<C>> hS(p.nwin);
     {
@@ -1353,16 +1375,8 @@ static int msm_piece_tables(pm_ctx *ctx, const MsmTables &tb, const Fp<typename 
     PM_TRY(sort_all());
     {
         StageTimer t(ctx, T_MSM_ACCUMULATE);
-        const size_t blocks = (max_tasks + 127) / 128;
-        if (wide)
-            hipLaunchKernelGGL((k_accumulate<C, false>), dim3((unsigned)blocks), dim3(128), 0, ctx->stream, S.sorted.as<uint32_t>(), S.counts.as<uint32_t>(),
-                               S.bucket_off.as<uint32_t>(), S.task_off.as<uint32_t>(), S.order.as<uint32_t>(), (const void *)plain,
-                               S.partials.as<XYZZ<C>>(), NB, (unsigned)seg);
-        else
-            hipLaunchKernelGGL((k_accumulate<C, true>), dim3((unsigned)blocks), dim3(128), 0, ctx->stream, S.sorted.as<uint32_t>(), S.counts.as<uint32_t>(),
-                               S.bucket_off.as<uint32_t>(), S.task_off.as<uint32_t>(), S.order.as<uint32_t>(), tb.table,
-                               S.partials.as<XYZZ<C>>(), NB, (unsigned)seg);
-        PM_HIP(ctx, hipGetLastError());
+        if (wide) PM_TRY((accumulate<C, false>(ctx, S, (const void *)plain, NB, max_tasks)));
+        else PM_TRY((accumulate<C, true>(ctx, S, tb.table, NB, max_tasks)));
     }
     if (wide) {
         // all windows' bucket sets reduced by ONE set of launches; then sum_w 2^(off_w) S_w by Horner from the top window: a chain
