@@ -335,16 +335,27 @@ int msm_resident_end(pm_ctx *ctx, uint64_t *out_xy, int *out_inf);
 template <class C>
 int reduce_two_level(pm_ctx *ctx, size_t NB, XYZZ<C> **out, unsigned nsets = 1, size_t bucket0 = 0);   // bucket0: first bucket of the first set
 
-// Wide mode: buckets of the set of a window that is one bit narrower than the plan's widest (c bits; the 256 % nwin wider windows
-// come first): half of 2^(c-1) where that is still whole 2^15-bucket sort regions.  Planner (setup.hip: wide_plan), driver and
-// kernels (msm.hip: win_base) agree through this.
-inline size_t wide_narrow_buckets(unsigned nwin, unsigned c) {
-    const size_t nb1 = (size_t)1 << (c - 1);
-    return (256 % nwin != 0 && (nb1 >> 1) >= ((size_t)1 << 15)) ? nb1 >> 1 : nb1;
-}
-inline size_t wide_total_buckets(unsigned nwin, unsigned c) {
-    const size_t nb1 = (size_t)1 << (c - 1), nbn = wide_narrow_buckets(nwin, c);
-    return nbn == nb1 ? nb1 * nwin : nb1 * (256 % nwin) + nbn * (nwin - 256 % nwin);
+// The sort's first level (msm.hip: k_tbl_count / k_tbl_partition) splits the buckets into regions of 2^15, one region per scan lane
+// of a workgroup of at most 1024 lanes.
+constexpr unsigned SORT_REGION_BITS = 15, SORT_MAX_REGIONS = 1024;
+
+// Wide mode: the bucket sets of a plan of nwin windows whose widest has c bits.  The 256 % nwin windows of c bits come first and own
+// `wide_b` = 2^(c-1) buckets each; the windows that are one bit narrower own `narrow_b`: half of that where it is still whole sort
+// regions (then n_narrow > 0), otherwise all nwin sets count as wide.  Planner (setup.hip: wide_plan), driver (msm.hip: bucket_plan)
+// and kernels (msm.hip: win_base) agree through this.
+struct WideSets {
+    size_t wide_b, narrow_b;
+    unsigned n_wide, n_narrow;
+    size_t total() const { return n_wide * wide_b + n_narrow * narrow_b; }
+};
+inline WideSets wide_sets(unsigned nwin, unsigned c) {
+    WideSets s;
+    s.wide_b = (size_t)1 << (c - 1);
+    const bool halve = 256 % nwin != 0 && (s.wide_b >> 1) >= ((size_t)1 << SORT_REGION_BITS);
+    s.narrow_b = halve ? s.wide_b >> 1 : s.wide_b;
+    s.n_wide = halve ? 256 % nwin : nwin;
+    s.n_narrow = nwin - s.n_wide;
+    return s;
 }
 
 // One bucket pipeline covers at most this many pairs (sorted-entry positions are u32: windows x pairs < 2^32); longer
@@ -447,6 +458,13 @@ inline pm_ctx *ctx_aux(pm_ctx *ctx) {
 // PINNED_STAGE_BYTES for small device-to-host records that must land without stalling the host (prove_sharded.hip: phase 1's
 // flags and halo coefficients -- a pageable destination makes hipMemcpyAsync wait for the stream).  nullptr on failure.
 constexpr size_t PINNED_SLOTS_BYTES = 4096, PINNED_STAGE_BYTES = 32768;
+constexpr size_t PINNED_MSM_SUM = 0,           // msm_begin -> msm_end: the reduced point of an enqueued MSM, internal form (XYZZ<C>)
+                 PINNED_MSM_POINT = 1024,      // msm_begin -> msm_end: the affine result of an MSM that ran synchronously ...
+                 PINNED_MSM_INF = 2048,        // ... and its infinity flag (int)
+                 PINNED_REMAINDER = 3072,      // prove_sharded.hip, phase 3: the quotient's remainder H_0 (one Fr)
+                 PINNED_FLAGS = PINNED_SLOTS_BYTES;   // the provers' status flags (4 bytes), first word of the staging area
+template <class T>
+inline T *pinned_slot(pm_ctx *ctx, size_t offset) { return (T *)((uint8_t *)ctx->h_pinned + offset); }
 inline void *ctx_pinned(pm_ctx *ctx) {
     if (!ctx->h_pinned && hipHostMalloc(&ctx->h_pinned, PINNED_SLOTS_BYTES + PINNED_STAGE_BYTES, hipHostMallocDefault) != hipSuccess) ctx->h_pinned = nullptr;
     return ctx->h_pinned;

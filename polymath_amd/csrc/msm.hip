@@ -24,8 +24,8 @@
 //   k_task_fold   buckets that own many tasks (skewed scalars) have their partials summed in parallel.
 //   k_bucket_reduce  per window sum_b (b+1) * B_b by per-lane running sums over K buckets, a
 //                 small scalar multiple, and an LDS tree reduction per workgroup.
-//   host_finish   Horner over the W window sums (c doublings each) and one inversion to affine, on the
-//                 host: an O(W) dependent chain (see host_finish).
+//   host_horner   Horner over the W window sums (c doublings each), then host_finish: one inversion to affine, on
+//                 the host: an O(W) dependent chain (see host_horner).
 #include <cstdlib>
 #include <cstring>
 
@@ -311,27 +311,19 @@ __device__ __forceinline__ void accumulate_task(const uint32_t *sorted, const ui
     typedef typename C::FqRR RR;
     XYZZ28<C> acc;
     acc.X = acc.Y = acc.ZZ = acc.ZZZ = f28_zero<RR>();
-#ifndef PM_ACC_IDX_VEC
-#define PM_ACC_IDX_VEC 4
-#endif
-#if PM_ACC_IDX_VEC == 4
     // The task's indices are read four at a time (one aligned 16-byte load per four additions): a lane's 4-byte load used to pull a
     // whole line of sorted[] through L2 for one entry, and by the lane's next addition (~4 500 instructions and 3 MB of gathered
-    // points per XCD later) the line was gone again.  sorted[] carries 16 bytes of padding for the last quad.
+    // points per XCD later) the line was gone again: 37 % fewer L2 reads, time neutral (profiles/r06_k_accumulate_l2_accounting.txt).
+    // sorted[] carries 16 bytes of padding for the last quad.
     uint4 quad = make_uint4(0u, 0u, 0u, 0u);
     uint32_t quad_at = 0xffffffffu;
-#endif
     for (uint32_t e = d.y; e < d.z; ++e) {
-#if PM_ACC_IDX_VEC == 4
         if ((e & ~3u) != quad_at) {
             quad_at = e & ~3u;
             quad = *(const uint4 *)(sorted + quad_at);
         }
         const unsigned q = e & 3u;
         const uint32_t v = q == 0 ? quad.x : q == 1 ? quad.y : q == 2 ? quad.z : quad.w;
-#else
-        const uint32_t v = sorted[e];
-#endif
         const bool neg = (v & 1u) != 0;
         if (TABLE) {   // window tables: one aligned 128-byte record, already on 28-bit limbs
             const TablePoint<C> tp = ((const TablePoint<C> *)points)[v >> 1];
@@ -506,7 +498,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 // scan + k_region_pass_staged<FINAL>; every scatter is staged through LDS and written out coalesced.
 // Reduction: k_reduce_level0 / k_reduce_level1 / k_sum_final (chains of dependent point additions).
 // =====================================================================================================
-constexpr unsigned LO_BITS = 15;
+constexpr unsigned LO_BITS = SORT_REGION_BITS;   // internal.h: 2^15 buckets per first-level region
 
 // Inclusive scan of one value per lane across the workgroup (blockDim <= 1024): wave shuffles + one LDS hop
 // (2 barriers; the LDS Hillis-Steele it replaces needed 2 log2(n)).  wt: 64 words of LDS scratch.
@@ -584,7 +576,7 @@ __device__ __forceinline__ bool digit_at(const Fp<P> &k, unsigned lo, unsigned c
 template <class P, unsigned NWIN>
 __global__ __launch_bounds__(1024) void k_tbl_count(const Fp<P> *scalars, const unsigned char *inf, size_t len, unsigned regions,
                                                    uint32_t *block_cnt, uint32_t win_buckets, uint32_t narrow_buckets) {
-    __shared__ uint32_t cnt[1024];
+    __shared__ uint32_t cnt[SORT_MAX_REGIONS];
     for (unsigned r = threadIdx.x; r < regions; r += blockDim.x) cnt[r] = 0;
     __syncthreads();
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -698,13 +690,13 @@ __global__ __launch_bounds__(1024) void k_region_offsets(const uint32_t *region_
 // entry (i, w) -> region of its bucket: key = low LO_BITS of the bucket, val = table index << 1 | negate.
 // One scalar per lane.  The workgroup's entries are staged through LDS in region order so that the global
 // stores are coalesced (consecutive lanes -> consecutive addresses of a region's run).
-//   LDS: cnt[1024] | delta[1024] | staged vals (u32 x blockDim nwin) | staged region<<16|key (u32 x same)
+//   LDS: cnt[SORT_MAX_REGIONS] | delta[SORT_MAX_REGIONS] | staged vals (u32 x blockDim nwin) | staged region<<16|key (u32 x same)
 template <class P, unsigned NWIN>
 __global__ __launch_bounds__(1024) void k_tbl_partition(const Fp<P> *scalars, const unsigned char *inf, size_t len,
                                                        unsigned regions, const uint32_t *region_off, const uint32_t *block_off, size_t tbl_stride, size_t base_index, uint16_t *keys,
                                                        uint32_t *vals, uint32_t win_buckets, uint32_t narrow_buckets) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    uint32_t *cnt = (uint32_t *)smem_raw, *delta = cnt + 1024;
+    uint32_t *cnt = (uint32_t *)smem_raw, *delta = cnt + SORT_MAX_REGIONS;
     uint32_t *st_val = delta + 1024, *st_key = st_val + (size_t)blockDim.x * NWIN;
     __shared__ uint32_t tot, wt[64];
     const unsigned t = threadIdx.x, BD = blockDim.x;
@@ -723,23 +715,13 @@ __global__ __launch_bounds__(1024) void k_tbl_partition(const Fp<P> *scalars, co
             if (digit_at<P>(k, win_off(NWIN, w), win_width(NWIN, w), carry, b, neg)) rank[w] = atomicAdd(&cnt[(b + win_base(NWIN, w, win_buckets, narrow_buckets)) >> LO_BITS], 1u);
     }
     __syncthreads();
-    {   // exclusive scan over the regions: lane t owns regions [t rpl, (t + 1) rpl), rpl = 1 or 2 (regions <= 2 blockDim, checked by
-        // the host: the 768 regions of a 12-window wide plan on 512 lanes)
-        const unsigned rpl = (regions + BD - 1) / BD;
-        uint32_t c[2] = {0u, 0u};
-        for (unsigned j = 0; j < rpl; ++j) {
-            const unsigned r = t * rpl + j;
-            c[j] = r < regions ? cnt[r] : 0u;
-        }
-        const uint32_t incl = block_inclusive_scan(c[0] + c[1], wt);
-        uint32_t ex = incl - (c[0] + c[1]);
-        for (unsigned j = 0; j < rpl; ++j) {
-            const unsigned r = t * rpl + j;
-            if (r < regions) {
-                cnt[r] = ex;                                                                  // first staged slot of the region
-                delta[r] = region_off[r] + block_off[(size_t)blockIdx.x * regions + r] - ex;  // global = delta[region] + slot
-                ex += c[j];
-            }
+    {   // exclusive scan over the regions: lane t owns region t (regions <= blockDim, checked by the host: bucket_plan)
+        const uint32_t c = t < regions ? cnt[t] : 0u;
+        const uint32_t incl = block_inclusive_scan(c, wt);
+        if (t < regions) {
+            const uint32_t ex = incl - c;
+            cnt[t] = ex;                                                                  // first staged slot of the region
+            delta[t] = region_off[t] + block_off[(size_t)blockIdx.x * regions + t] - ex;  // global = delta[region] + slot
         }
         if (t == BD - 1) tot = incl;
     }
@@ -769,6 +751,7 @@ __global__ __launch_bounds__(1024) void k_tbl_partition(const Fp<P> *scalars, co
 // (nbins per segment, global bin id = segment * nbins + bin).
 //   RS_HIST : counts[global bin] += occurrences
 //   RS_MID  : entries move to (keys_out, vals_out) at out_off[global bin] + rank, key keeps its low bin_shift bits
+//             (k_region_pass_staged only; k_region_pass keeps the two output arguments of its launch, unused)
 //   RS_FINAL: sorted[out_off[global bin] + rank] = val
 // With 64 regions -> 128 sub-regions -> 256 buckets every pass writes runs of ~100+ entries per bin instead
 // of single scattered words (the two-level version spent most of its time on 4-byte scattered stores).
@@ -780,7 +763,8 @@ template <int MODE>
 __global__ __launch_bounds__(1024) void k_region_pass(const uint16_t *keys, const uint32_t *vals, const uint32_t *seg_off,
                                                       unsigned nseg, unsigned bin_shift, unsigned nbins, unsigned chunk,
                                                       uint32_t *counts, const uint32_t *out_off, uint32_t *cursor,
-                                                      uint32_t *sorted, uint16_t *keys_out, uint32_t *vals_out) {
+                                                      uint32_t *sorted, uint16_t * /*keys_out*/, uint32_t * /*vals_out*/) {
+    static_assert(MODE == RS_HIST || MODE == RS_FINAL, "the middle level runs staged (k_region_pass_staged<RS_MID>)");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     uint32_t *h = (uint32_t *)smem_raw;
     const uint32_t total = seg_off[nseg];
@@ -793,7 +777,6 @@ __global__ __launch_bounds__(1024) void k_region_pass(const uint16_t *keys, cons
         unsigned mid = (ra + rb) >> 1;
         if (seg_off[mid] <= lo) ra = mid; else rb = mid;
     }
-    const uint16_t low_mask = (uint16_t)((1u << bin_shift) - 1);
     for (unsigned r = ra; r < nseg; ++r) {
         const uint32_t s0 = seg_off[r] > lo ? seg_off[r] : lo;
         const uint32_t s1 = seg_off[r + 1] < hi ? seg_off[r + 1] : hi;
@@ -831,15 +814,7 @@ __global__ __launch_bounds__(1024) void k_region_pass(const uint16_t *keys, cons
 #pragma unroll
             for (unsigned q = 0; q < RS_PER_LANE; ++q) {
                 const uint32_t e = s0 + q * blockDim.x + threadIdx.x;
-                if (e < s1) {
-                    const uint32_t pos = h[key[q] >> bin_shift] + rank[q];
-                    if (MODE == RS_FINAL) {
-                        sorted[pos] = vals[e];
-                    } else {
-                        keys_out[pos] = key[q] & low_mask;
-                        vals_out[pos] = vals[e];
-                    }
-                }
+                if (e < s1) sorted[h[key[q] >> bin_shift] + rank[q]] = vals[e];
             }
         }
         __syncthreads();
@@ -902,13 +877,8 @@ __global__ __launch_bounds__(1024) void k_hist_small(const uint16_t *keys, const
 // the global stores are coalesced: consecutive lanes write consecutive addresses of a bin's run
 // (the direct version above issues 64 scattered 4-byte stores per wave-instruction).
 //   LDS: h[nbins] | start[nbins] | delta[nbins] | staged vals (u32 x ST_CHUNK) | staged keys (u16 x ST_CHUNK)
-#ifndef PM_ST_THREADS
-#define PM_ST_THREADS 1024
-#endif
-#ifndef PM_ST_PER_LANE
-#define PM_ST_PER_LANE 8
-#endif
-constexpr unsigned ST_THREADS = PM_ST_THREADS, ST_PER_LANE = PM_ST_PER_LANE, ST_CHUNK = ST_PER_LANE * ST_THREADS, ST_MAX_BINS = 256;
+// 1024 lanes x 8 entries: the workgroup shapes swept after the 16-byte loads went in, profiles/r05_sort_chunk_shapes_after_wide_loads.txt
+constexpr unsigned ST_THREADS = 1024, ST_PER_LANE = 8, ST_CHUNK = ST_PER_LANE * ST_THREADS, ST_MAX_BINS = 256;
 
 template <int MODE>
 __global__ __launch_bounds__(ST_THREADS) void k_region_pass_staged(const uint16_t *keys, const uint32_t *vals, const uint32_t *seg_off,
@@ -1036,27 +1006,127 @@ __global__ __launch_bounds__(1024) void k_scan_small(const uint32_t *cnt, uint32
     if (t == 0) off[n] = carry;
 }
 
-// Final combine on the host: S = sum_w 2^(c w) S_w by Horner (c doublings per window) and one inversion
-// to affine -- an O(W c) dependent chain on W points (9 ms on one GPU lane, ~0.3 ms here).
-template <class C>
-static void host_finish(const XYZZ<C> *S /*[nwin], internal form*/, unsigned nwin, unsigned c, Affine<C> *out, int *inf) {
-    XYZZ<C> acc = XYZZ<C>::identity();
-    for (int w = (int)nwin - 1; w >= 0; --w) {
-        for (unsigned k = 0; k < c; ++k) acc = xyzz_dbl<C>(acc);
-        acc = xyzz_add<C>(acc, xyzz_internal_to_std<C>(S[w]));
+// ------------------------------------------------------------------------------- the plan
+// Everything one bucket pipeline derives from its inputs before the first launch; the stages below read it and recompute nothing.
+// Three shapes: per-window (pipeline A: nwin sets of 2^(c-1) buckets, LDS-histogram sort), tables (one shared set, radix sort over
+// the window tables' indices) and wide (tables == wide == true: one set per window, radix sort, points from the plain base array).
+struct BucketPlan {
+    bool tables, wide;
+    unsigned nwin, c;                        // windows; bits of the widest
+    size_t len, E;                           // pairs; E = nwin * len, the most entries the sort can see
+    // the bucket sets, in bucket order: n_wide_sets of NB1 = 2^(c-1) buckets, then n_narrow_sets of NBn (wide mode, internal.h:
+    // wide_sets); NB = all of them.  Per-window: nwin sets of NB1; tables: one.
+    size_t NB1, NBn, NB;
+    unsigned n_wide_sets, n_narrow_sets;
+    uint32_t win_buckets, narrow_buckets;    // win_base()'s arguments: NB1 and NBn in wide mode, 0 for the shared set
+    size_t seg, max_tasks;                   // entries per accumulate task; bound on the number of tasks
+    unsigned chunk, nchunks;                 // per-window: scalars per histogram / scatter workgroup
+    // table-mode sort: regions of lo_buckets (2^15, or the whole of a smaller set); first-level workgroup and its dynamic LDS
+    unsigned lo_buckets, regions, pbd;
+    size_t plds, keys_bytes;
+    bool two_level;                          // msm_reduce.hip: reduce_two_level per group of sets; otherwise reduce_single_level
+    unsigned red_lanes, red_block, bpw;      // single-level reduction: lanes and workgroups per set
+    unsigned nsums;                          // window sums the pipeline hands to host_horner ...
+    unsigned char width[64];                 // ... and the doublings in front of each
+};
+
+// scalars per first-level workgroup of the table-mode sort: 512 up to 16 windows, 256 beyond (the staged entries take lanes x
+// windows x 8 bytes of LDS).  From 512 regions up (the 12-window wide plan of a 2^24-gate key: 4 x 2^21 + 8 x 2^20 buckets): 1024, so that a
+// workgroup's run inside a region is 24 entries (96 B of values), not 12 -- what the first level pays for is the length of that
+// run, not the number of regions: same-box A/B at 2^24 gates in profiles/r06_wide_ragged_sets_ab.txt (512 regions on 512 lanes:
+// sort + 5 ... 8 ms against 768 on 1024) and r06_wide_12_windows_ab.txt; 256 against 512 lanes below that: flat
+// (profiles/r05_sort_chunk_shapes_after_wide_loads.txt, (3))
+constexpr unsigned PARTITION_LANES = 512, PARTITION_WIDE_LANES = 1024, PARTITION_WIDE_FROM = 512;
+
+// tb: the window tables or the wide plan of the MSM; nullptr (or c == 0): the per-window pipeline on `len` pairs of scalar_bits-bit scalars
+static int bucket_plan(const MsmTables *tb, size_t len, unsigned scalar_bits, long long task_len, BucketPlan &p) {
+    p = BucketPlan();
+    p.len = len;
+    p.tables = tb && tb->c;
+    if (!p.tables) {
+        const MsmPlan w = make_plan(len, scalar_bits, task_len > 0 ? (unsigned)task_len : 0u);
+        p.nwin = w.nwin; p.c = w.c; p.seg = w.seg; p.max_tasks = w.max_tasks; p.chunk = w.chunk; p.nchunks = w.nchunks;
+        p.NB1 = w.nbuckets;
+        p.n_wide_sets = w.nwin;
+        for (unsigned i = 0; i < w.nwin; ++i) p.width[i] = (unsigned char)w.c;
+    } else {
+        p.wide = tb->wide;
+        p.nwin = tb->nwin; p.c = tb->c;
+        if (p.nwin < 10 || p.nwin > 32) return PM_ERR_INVALID_ARG;      // the first level's instantiations (sort_first_level)
+        for (unsigned w = 0; w < p.nwin; ++w)                            // the kernels derive the layout from nwin alone
+            if (tb->off[w] != win_off(p.nwin, w) || tb->width[w] != win_width(p.nwin, w)) return PM_ERR_INVALID_ARG;
+        p.NB1 = (size_t)1 << (p.c - 1);
+        p.n_wide_sets = 1;
+        if (p.wide) {
+            const WideSets s = wide_sets(p.nwin, p.c);
+            p.NBn = s.narrow_b; p.n_wide_sets = s.n_wide; p.n_narrow_sets = s.n_narrow;
+            p.win_buckets = (uint32_t)p.NB1; p.narrow_buckets = (uint32_t)p.NBn;
+            for (unsigned w = 0; w < p.nwin; ++w) p.width[w] = tb->width[w];
+        }
     }
-    *inf = acc.is_identity() ? 1 : 0;
-    *out = xyzz_to_affine<C>(acc);
+    p.NB = p.n_wide_sets * p.NB1 + p.n_narrow_sets * p.NBn;
+    p.E = (size_t)p.nwin * len;
+    p.nsums = p.n_wide_sets + p.n_narrow_sets;
+    p.red_lanes = (unsigned)((p.NB1 + RED_K - 1) / RED_K);
+    p.red_block = 64;
+    while (p.red_block < p.red_lanes && p.red_block < 256) p.red_block <<= 1;
+    p.bpw = (p.red_lanes + p.red_block - 1) / p.red_block;
+    if (!p.tables) return PM_OK;
+
+    p.lo_buckets = (unsigned)(p.NB < ((size_t)1 << LO_BITS) ? p.NB : ((size_t)1 << LO_BITS));
+    p.regions = (unsigned)(p.NB / p.lo_buckets);
+    if ((size_t)p.regions * p.lo_buckets != p.NB) return PM_ERR_INVALID_ARG;   // whole regions only
+    p.pbd = p.regions >= PARTITION_WIDE_FROM ? PARTITION_WIDE_LANES : p.nwin <= 16 ? PARTITION_LANES : 256;
+    if (p.regions > p.pbd || p.regions > SORT_MAX_REGIONS) return PM_ERR_INVALID_ARG;   // one region per scan lane; cnt[] / delta[] of k_tbl_partition
+    p.plds = 2 * SORT_MAX_REGIONS * 4 + (size_t)p.pbd * p.nwin * 8;
+    p.two_level = p.NB1 >= 4096;                                           // msm_reduce.hip: k_reduce_level0 / level1 / final
+    if (p.wide && !p.two_level) return PM_ERR_INVALID_ARG;                 // wide plans have c >= 16 (setup.hip: wide_plan)
+    p.seg = 2 * (p.E / p.NB + 1);
+    if (p.seg < 64) p.seg = 64;
+    if (task_len > 0) p.seg = (size_t)task_len;                            // PM_OPT_MSM_TASK_LEN (tuning sweeps)
+    p.max_tasks = p.NB + p.E / p.seg + 1;
+    p.keys_bytes = (p.E * 2 + 15) & ~(size_t)15;
+    return PM_OK;
+}
+
+// ------------------------------------------------------------------------------- shared stages
+// Each takes the context, the bucket set and the plan, and enqueues on ctx->stream.
+
+// the set's buffers, the scan's tile totals
+template <class C>
+static int reserve_set(pm_ctx *ctx, MsmSet &S, const BucketPlan &p) {
+    PM_HIP(ctx, S.sorted.reserve(p.E * 4 + 16));      // + 16: k_accumulate reads aligned quads of indices
+    PM_HIP(ctx, S.counts.reserve(2 * p.NB * 4));      // counts | cursor, one memset
+    PM_HIP(ctx, S.bucket_off.reserve((p.NB + 1) * 4));
+    PM_HIP(ctx, S.task_off.reserve((p.NB + 1) * 4));
+    PM_HIP(ctx, S.partials.reserve(p.max_tasks * sizeof(XYZZ<C>)));
+    PM_HIP(ctx, S.task_cnt.reserve(p.NB * 4));
+    PM_HIP(ctx, ctx->msm.cursor.reserve(((p.NB + SCAN_TILE - 1) / SCAN_TILE + 1) * 8));
+    return PM_OK;
+}
+
+// bucket_off / task_off from the set's counts (k_scan_tiles)
+static int bucket_scan(pm_ctx *ctx, MsmSet &S, const BucketPlan &p) {
+    uint32_t *tile_tot = ctx->msm.cursor.as<uint32_t>(), *bucket_off = S.bucket_off.as<uint32_t>(), *task_off = S.task_off.as<uint32_t>();
+    const unsigned ntiles = (unsigned)((p.NB + SCAN_TILE - 1) / SCAN_TILE);
+    hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(256), 0, ctx->stream, S.counts.as<uint32_t>(), bucket_off, task_off, tile_tot, p.NB,
+                       (unsigned)p.seg);
+    PM_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, ctx->stream, tile_tot, ntiles, bucket_off, task_off, p.NB);
+    PM_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_scan_add, dim3(ntiles), dim3(256), 0, ctx->stream, bucket_off, task_off, tile_tot, p.NB);
+    PM_HIP(ctx, hipGetLastError());
+    return PM_OK;
 }
 
 // effective task counts for the reduction + parallel fold of hot buckets (k_task_counts / k_task_fold);
 // enqueued after k_accumulate, before the bucket reduction
 template <class C>
-static int fold_hot_buckets(pm_ctx *ctx, MsmSet &S, size_t G, size_t max_tasks) {
+static int fold_hot_buckets(pm_ctx *ctx, MsmSet &S, const BucketPlan &p) {
     MsmWorkspace &ws = ctx->msm;
-    size_t cap = max_tasks > G ? max_tasks - G + 1 : 1;          // a listed bucket has > FOLD_MIN tasks
+    const size_t G = p.NB;
+    size_t cap = p.max_tasks > G ? p.max_tasks - G + 1 : 1;          // a listed bucket has > FOLD_MIN tasks
     cap = cap / FOLD_MIN + 1;
-    PM_HIP(ctx, S.task_cnt.reserve(G * 4));
     PM_HIP(ctx, ws.hot.reserve((2 * cap + 2) * 4));
     uint32_t *hot_counts = ws.hot.as<uint32_t>(), *hot_a = hot_counts + 2, *hot_b = hot_a + cap;
     PM_HIP(ctx, hipMemsetAsync(hot_counts, 0, 8, ctx->stream));
@@ -1074,12 +1144,14 @@ static int fold_hot_buckets(pm_ctx *ctx, MsmSet &S, size_t G, size_t max_tasks) 
 
 // tasks[] for k_accumulate (see k_task_bins); enqueued on the context's stream after the bucket scan.  Also zeroes the context's
 // accumulate ticket (the word in front of the length bins: one memset for both).
-static int task_order(pm_ctx *ctx, MsmSet &S, const uint32_t *counts, size_t G, size_t seg, size_t max_tasks) {
+static int task_order(pm_ctx *ctx, MsmSet &S, const BucketPlan &p) {
     MsmWorkspace &ws = ctx->msm;
+    const size_t G = p.NB, seg = p.seg;
+    const uint32_t *counts = S.counts.as<uint32_t>();
     unsigned lshift = 0;
     while (((seg - 1) >> lshift) + 1 > TASK_MAX_BINS) ++lshift;
     const unsigned nbins = (unsigned)(((seg - 1) >> lshift) + 1);
-    PM_HIP(ctx, S.tasks.reserve(max_tasks * sizeof(uint4)));
+    PM_HIP(ctx, S.tasks.reserve(p.max_tasks * sizeof(uint4)));
     PM_HIP(ctx, ws.len_bins.reserve((3 * (size_t)nbins + 5) * 4));
     uint32_t *ticket = ws.len_bins.as<uint32_t>(), *len_cnt = ticket + 1, *len_off = len_cnt + nbins, *len_cursor = len_off + nbins + 1;
     PM_HIP(ctx, hipMemsetAsync(ticket, 0, ((size_t)nbins + 1) * 4, ctx->stream));
@@ -1100,98 +1172,185 @@ static int task_order(pm_ctx *ctx, MsmSet &S, const uint32_t *counts, size_t G, 
 // k_accumulate over the tasks[] that task_order enqueued: a grid of as many 128-lane workgroups as the device holds at once (no
 // more than max_tasks lanes); the waves draw the tasks from the ticket that task_order zeroed.
 template <class C, bool TABLE>
-static int accumulate(pm_ctx *ctx, MsmSet &S, const void *points, size_t G, size_t max_tasks) {
+static int accumulate(pm_ctx *ctx, MsmSet &S, const BucketPlan &p, const void *points) {
     int per_cu = 0, cus = 0;
     PM_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_accumulate<C, TABLE>, 128, 0));
     PM_HIP(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
     size_t blocks = (size_t)(per_cu > 0 ? per_cu : 1) * (size_t)(cus > 0 ? cus : 1);
-    if (blocks > (max_tasks + 127) / 128) blocks = (max_tasks + 127) / 128;
+    if (blocks > (p.max_tasks + 127) / 128) blocks = (p.max_tasks + 127) / 128;
     hipLaunchKernelGGL((k_accumulate<C, TABLE>), dim3((unsigned)blocks), dim3(128), 0, ctx->stream, S.sorted.as<uint32_t>(),
-                       S.task_off.as<uint32_t>(), S.tasks.as<uint4>(), points, S.partials.as<XYZZ<C>>(), G, ctx->msm.len_bins.as<uint32_t>());
+                       S.task_off.as<uint32_t>(), S.tasks.as<uint4>(), points, S.partials.as<XYZZ<C>>(), p.NB, ctx->msm.len_bins.as<uint32_t>());
     PM_HIP(ctx, hipGetLastError());
     return PM_OK;
 }
 
-// ------------------------------------------------------------------------------- driver
-// One bucket pipeline over at most msm_max_piece() pairs (internal.h; sorted-entry positions are u32: W * len < 2^32).
-
+// Single-level reduction (k_bucket_reduce + k_sum_parts) of n_wide_sets sets of NB1 buckets: the windows of the per-window pipeline,
+// or a shared set too small for msm_reduce.hip.  *out = the sets' sums, internal form, inside the workspace.
 template <class C>
-static int msm_piece(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_scalars, size_t len, Affine<C> *h_out,
-                     int *h_inf) {
-    typedef typename C::FrP FrP;
-    StageTimer t_total(ctx, T_MSM_TOTAL);
-    MsmPlan p = make_plan(len, (unsigned)FrP::BITS, (unsigned)ctx->opt.v[PM_OPT_MSM_TASK_LEN]);
-    MsmWorkspace &ws = ctx->msm;
-    MsmSet &S = ws.set;
-    const size_t G = (size_t)p.nwin * p.nbuckets;
-    PM_HIP(ctx, ws.digits.reserve((size_t)p.nwin * len * 4));
-    PM_HIP(ctx, S.sorted.reserve((size_t)p.nwin * len * 4 + 16));   // + 16: k_accumulate reads aligned quads of indices
-    PM_HIP(ctx, S.counts.reserve(2 * G * 4));  // counts | cursor, one memset
-    PM_HIP(ctx, S.bucket_off.reserve((G + 1) * 4));
-    PM_HIP(ctx, S.task_off.reserve((G + 1) * 4));
-    PM_HIP(ctx, ws.cursor.reserve(((G + SCAN_TILE - 1) / SCAN_TILE + 1) * 8));  // scan tile totals
-    PM_HIP(ctx, S.partials.reserve(p.max_tasks * sizeof(XYZZ<C>)));
-    const unsigned red_lanes = (p.nbuckets + RED_K - 1) / RED_K;      // lanes per window
-    unsigned red_block = 64;
-    while (red_block < red_lanes && red_block < 256) red_block <<= 1;
-    const unsigned bpw = (red_lanes + red_block - 1) / red_block;
-    PM_HIP(ctx, ws.wsum.reserve(((size_t)p.nwin * bpw + p.nwin) * sizeof(XYZZ<C>)));
-    uint32_t *counts = S.counts.as<uint32_t>(), *cursor = counts + G;
-    {
-        StageTimer t(ctx, T_MSM_SORT);
-        PM_HIP(ctx, hipMemsetAsync(counts, 0, 2 * G * 4, ctx->stream));
-        hipLaunchKernelGGL(k_digits<C>, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, ctx->stream, d_scalars, d_bases,
-                           ws.digits.as<uint32_t>(), len, p.c, p.nwin);
-        PM_HIP(ctx, hipGetLastError());
-        size_t lds = (size_t)p.nbuckets * 4;
-        if (lds > 48 * 1024) {  // CDNA4: up to 160 KiB of LDS per workgroup, opt in above the default cap
-            PM_HIP(ctx, hipFuncSetAttribute((const void *)k_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            PM_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        }
-        hipLaunchKernelGGL(k_hist, dim3(p.nchunks, p.nwin), dim3(1024), lds, ctx->stream, ws.digits.as<uint32_t>(), counts,
-                           len, p.chunk, p.nbuckets);
-        PM_HIP(ctx, hipGetLastError());
-        const unsigned ntiles = (unsigned)((G + SCAN_TILE - 1) / SCAN_TILE);
-        hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(256), 0, ctx->stream, counts, S.bucket_off.as<uint32_t>(),
-                           S.task_off.as<uint32_t>(), ws.cursor.as<uint32_t>(), G, p.seg);
-        PM_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, ctx->stream, ws.cursor.as<uint32_t>(), ntiles,
-                           S.bucket_off.as<uint32_t>(), S.task_off.as<uint32_t>(), G);
-        PM_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_scan_add, dim3(ntiles), dim3(256), 0, ctx->stream, S.bucket_off.as<uint32_t>(),
-                           S.task_off.as<uint32_t>(), ws.cursor.as<uint32_t>(), G);
-        PM_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_scatter, dim3(p.nchunks, p.nwin), dim3(1024), lds, ctx->stream, ws.digits.as<uint32_t>(),
-                           S.bucket_off.as<uint32_t>(), cursor, S.sorted.as<uint32_t>(), len, p.chunk, p.nbuckets);
-        PM_HIP(ctx, hipGetLastError());
-        PM_TRY(task_order(ctx, S, counts, G, p.seg, p.max_tasks));
-    }
-    {
-        StageTimer t(ctx, T_MSM_ACCUMULATE);
-        PM_TRY((accumulate<C, false>(ctx, S, (const void *)d_bases, G, p.max_tasks)));
-    }
-    std::vector<XYZZ<C>> hS(p.nwin);
-    {
-        StageTimer t(ctx, T_MSM_REDUCE);
-        PM_TRY(fold_hot_buckets<C>(ctx, S, G, p.max_tasks));
-        XYZZ<C> *parts = ws.wsum.as<XYZZ<C>>(), *dS = parts + (size_t)p.nwin * bpw;
-        hipLaunchKernelGGL(k_bucket_reduce<C>, dim3(p.nwin * bpw), dim3(red_block), red_block * sizeof(XYZZ28<C>), ctx->stream,
-                           S.partials.as<XYZZ<C>>(), S.task_off.as<uint32_t>(), S.task_cnt.as<uint32_t>(), p.nbuckets, red_lanes, bpw, parts);
-        PM_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_sum_parts<C>, dim3(p.nwin), dim3(64), 0, ctx->stream, parts, bpw, dS);
-        PM_HIP(ctx, hipGetLastError());
-        PM_HIP(ctx, hipMemcpyAsync(hS.data(), dS, hS.size() * sizeof(XYZZ<C>), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    host_finish<C>(hS.data(), p.nwin, p.c, h_out, h_inf);
+static int reduce_single_level(pm_ctx *ctx, MsmSet &S, const BucketPlan &p, XYZZ<C> **out) {
+    const unsigned sets = p.n_wide_sets;
+    PM_HIP(ctx, ctx->msm.wsum.reserve(((size_t)sets * p.bpw + sets) * sizeof(XYZZ<C>)));
+    XYZZ<C> *parts = ctx->msm.wsum.as<XYZZ<C>>(), *sums = parts + (size_t)sets * p.bpw;
+    hipLaunchKernelGGL(k_bucket_reduce<C>, dim3(sets * p.bpw), dim3(p.red_block), p.red_block * sizeof(XYZZ28<C>), ctx->stream,
+                       S.partials.as<XYZZ<C>>(), S.task_off.as<uint32_t>(), S.task_cnt.as<uint32_t>(), (unsigned)p.NB1, p.red_lanes, p.bpw, parts);
+    PM_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_sum_parts<C>, dim3(sets), dim3(64), 0, ctx->stream, parts, p.bpw, sums);
+    PM_HIP(ctx, hipGetLastError());
+    *out = sums;
     return PM_OK;
 }
 
-// ------------------------------------------------------------------------- table-mode driver
-// tb.wide: `plain` = the MSM's first base (internal form); the piece's pairs are plain[tb.base_index ...], every window has its own
-// bucket set and the window sums are combined on the host.  Otherwise the window tables of tb.
-// async_res != nullptr (table mode only): everything is ENQUEUED on ctx->stream, the reduced point (internal form) is copied to
-// *async_res -- pinned host memory -- and the call returns without waiting; the caller synchronises and finishes (msm_end).
+// Final combine on the host, two steps.  host_horner: sum_w 2^(off_w) S_w from the top window down -- width[w] doublings in front
+// of S_w -- an O(256) dependent chain on nsums points (9 ms on one GPU lane, ~0.3 ms here); a single sum is the case of one window
+// of width 0.  host_finish: the infinity flag and one inversion to affine.
+template <class C>
+static XYZZ<C> host_horner(const XYZZ<C> *sums /*[nsums], internal form*/, unsigned nsums, const unsigned char *width) {
+    XYZZ<C> acc = XYZZ<C>::identity();
+    for (int w = (int)nsums - 1; w >= 0; --w) {
+        for (unsigned k = 0; k < width[w]; ++k) acc = xyzz_dbl<C>(acc);
+        acc = xyzz_add<C>(acc, xyzz_internal_to_std<C>(sums[w]));
+    }
+    return acc;
+}
+template <class C>
+static void host_finish(const XYZZ<C> &acc, Affine<C> *out, int *inf) {
+    *inf = acc.is_identity() ? 1 : 0;
+    *out = xyzz_to_affine<C>(acc);
+}
+
+// ------------------------------------------------------------------------------- the sorts
+// Pipeline (A): digits, LDS histogram per (chunk, window), bucket scan, LDS-staged scatter.
+template <class C>
+static int sort_windows(pm_ctx *ctx, MsmSet &S, const BucketPlan &p, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_scalars) {
+    MsmWorkspace &ws = ctx->msm;
+    PM_HIP(ctx, ws.digits.reserve(p.E * 4));
+    uint32_t *counts = S.counts.as<uint32_t>(), *cursor = counts + p.NB, *digits = ws.digits.as<uint32_t>();
+    const unsigned nbuckets = (unsigned)p.NB1;
+    PM_HIP(ctx, hipMemsetAsync(counts, 0, 2 * p.NB * 4, ctx->stream));
+    hipLaunchKernelGGL(k_digits<C>, dim3((unsigned)((p.len + 255) / 256)), dim3(256), 0, ctx->stream, d_scalars, d_bases, digits, p.len, p.c, p.nwin);
+    PM_HIP(ctx, hipGetLastError());
+    const size_t lds = (size_t)nbuckets * 4;
+    if (lds > 48 * 1024) {  // CDNA4: up to 160 KiB of LDS per workgroup, opt in above the default cap
+        PM_HIP(ctx, hipFuncSetAttribute((const void *)k_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        PM_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    hipLaunchKernelGGL(k_hist, dim3(p.nchunks, p.nwin), dim3(1024), lds, ctx->stream, digits, counts, p.len, p.chunk, nbuckets);
+    PM_HIP(ctx, hipGetLastError());
+    PM_TRY(bucket_scan(ctx, S, p));
+    hipLaunchKernelGGL(k_scatter, dim3(p.nchunks, p.nwin), dim3(1024), lds, ctx->stream, digits, S.bucket_off.as<uint32_t>(), cursor,
+                       S.sorted.as<uint32_t>(), p.len, p.chunk, nbuckets);
+    PM_HIP(ctx, hipGetLastError());
+    return PM_OK;
+}
+
+// What the levels of the table-mode sort share: (u16 key, u32 value) entries in ws.digits, the regions' counters in ws.region.
+struct SortBuffers {
+    uint16_t *keys;
+    uint32_t *vals, *region_count, *region_off, *region_cursor;
+};
+
+// First level: every (scalar, window) entry into the region of its bucket -- per-workgroup region counts, their column scan, the
+// regions' offsets, the partition.  The kernels are instantiated per window count (win_off): the chain below finds nwin's.
+template <class P, unsigned NWIN = 10>
+static int sort_first_level(pm_ctx *ctx, const BucketPlan &p, const MsmTables &tb, const Fp<P> *d_scalars, const SortBuffers &b) {
+    if (p.nwin != NWIN) {
+        if constexpr (NWIN < 32) return sort_first_level<P, NWIN + 1>(ctx, p, tb, d_scalars, b);
+        return PM_ERR_INVALID_ARG;
+    }
+    hipStream_t st = ctx->stream;
+    const unsigned char *inf = tb.inf + tb.base_index;
+    const unsigned pblocks = (unsigned)((p.len + p.pbd - 1) / p.pbd);
+    const BlockScanShape bsh = block_scan_shape(pblocks, p.regions);
+    PM_HIP(ctx, ctx->msm.block_cnt.reserve(((size_t)pblocks + bsh.G) * p.regions * 4));
+    uint32_t *block_cnt = ctx->msm.block_cnt.as<uint32_t>(), *block_partial = block_cnt + (size_t)pblocks * p.regions;
+    PM_HIP(ctx, hipMemsetAsync(b.region_count, 0, (size_t)p.regions * 4, st));
+    hipLaunchKernelGGL((k_tbl_count<P, NWIN>), dim3(pblocks), dim3(p.pbd), 0, st, d_scalars, inf, p.len, p.regions, block_cnt, p.win_buckets,
+                       p.narrow_buckets);
+    hipLaunchKernelGGL(k_block_sums, dim3(bsh.G), dim3(1024), 0, st, block_cnt, pblocks, p.regions, bsh, block_partial);
+    hipLaunchKernelGGL(k_block_offsets, dim3(bsh.G), dim3(1024), 0, st, block_cnt, pblocks, p.regions, bsh, block_partial, b.region_count);
+    hipLaunchKernelGGL(k_region_offsets, dim3(1), dim3(1024), 0, st, b.region_count, b.region_off, b.region_cursor, p.regions);
+    PM_HIP(ctx, hipFuncSetAttribute((const void *)k_tbl_partition<P, NWIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.plds));
+    hipLaunchKernelGGL((k_tbl_partition<P, NWIN>), dim3(pblocks), dim3(p.pbd), p.plds, st, d_scalars, inf, p.len, p.regions, b.region_off, block_cnt,
+                       p.wide ? (size_t)0 : tb.stride, tb.base_index, b.keys, b.vals, p.win_buckets, p.narrow_buckets);
+    PM_HIP(ctx, hipGetLastError());
+    return PM_OK;
+}
+
+constexpr unsigned SUB_BINS = 128, FIN_BINS = 256, FIN_BITS = 8;
+
+// Regions of 2^15 buckets -> 128 sub-regions of 256 buckets -> buckets
+static int sort_three_levels(pm_ctx *ctx, MsmSet &S, const BucketPlan &p, const SortBuffers &b) {
+    MsmWorkspace &ws = ctx->msm;
+    hipStream_t st = ctx->stream;
+    const unsigned nsub = p.regions * SUB_BINS, chunk = 1u << RS_CHUNK_LOG;
+    PM_HIP(ctx, ws.sub.reserve((3 * (size_t)nsub + 4) * 4));
+    PM_HIP(ctx, ws.digits2.reserve(p.keys_bytes + p.E * 4 + 128));
+    uint32_t *counts = S.counts.as<uint32_t>(), *cursor = counts + p.NB;
+    uint32_t *sub_count = ws.sub.as<uint32_t>(), *sub_off = sub_count + nsub, *sub_cursor = sub_off + nsub + 1;
+    uint16_t *keys2 = (uint16_t *)ws.digits2.p;
+    uint32_t *vals2 = (uint32_t *)((uint8_t *)ws.digits2.p + p.keys_bytes);
+    const unsigned sblocks = (unsigned)((p.E + chunk - 1) / chunk), stblocks = (unsigned)((p.E + ST_CHUNK - 1) / ST_CHUNK);
+    PM_HIP(ctx, hipMemsetAsync(sub_count, 0, (size_t)nsub * 4, st));
+    hipLaunchKernelGGL(k_hist_small, dim3(sblocks), dim3(1024), 0, st, b.keys, b.region_off, p.regions, FIN_BITS, SUB_BINS, chunk, sub_count);
+    PM_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, st, sub_count, sub_off, sub_cursor, nsub);
+    PM_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_region_pass_staged<RS_MID>, dim3(stblocks), dim3(ST_THREADS), 0, st, b.keys, b.vals, b.region_off, p.regions,
+                       FIN_BITS, SUB_BINS, sub_off, sub_cursor, (uint32_t *)nullptr, keys2, vals2);
+    PM_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_hist_small, dim3(sblocks), dim3(1024), 0, st, keys2, sub_off, nsub, 0u, FIN_BINS, chunk, counts);
+    PM_HIP(ctx, hipGetLastError());
+    PM_TRY(bucket_scan(ctx, S, p));
+    // (round 5 measured the last level WITHOUT LDS staging -- lanes storing their 4-byte indices straight into the sub-region's
+    // 120 KB output window, which stays in L2: the sort of a 2^24-pair MSM 2.66 -> 3.70 ms, a proof +2.2 ms; 64 partial-line
+    // stores per wave instruction cost more than the staging saves: profiles/r05_sort_final_direct_negative.txt)
+    hipLaunchKernelGGL(k_region_pass_staged<RS_FINAL>, dim3(stblocks), dim3(ST_THREADS), 0, st, keys2, vals2, sub_off, nsub, 0u,
+                       FIN_BINS, S.bucket_off.as<uint32_t>(), cursor, S.sorted.as<uint32_t>(), (uint16_t *)nullptr, (uint32_t *)nullptr);
+    PM_HIP(ctx, hipGetLastError());
+    return PM_OK;
+}
+
+// Small bucket sets (< 2^15): one region, sorted directly with an NB-entry LDS table
+static int sort_one_region(pm_ctx *ctx, MsmSet &S, const BucketPlan &p, const SortBuffers &b) {
+    hipStream_t st = ctx->stream;
+    const unsigned chunk = 1u << RS_CHUNK_LOG, sblocks = (unsigned)((p.E + chunk - 1) / chunk);
+    const size_t lds = (size_t)p.lo_buckets * 4;
+    uint32_t *counts = S.counts.as<uint32_t>(), *cursor = counts + p.NB;
+    hipLaunchKernelGGL(k_region_pass<RS_HIST>, dim3(sblocks), dim3(1024), lds, st, b.keys, b.vals, b.region_off, p.regions, 0u,
+                       p.lo_buckets, chunk, counts, (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
+                       (uint16_t *)nullptr, (uint32_t *)nullptr);
+    PM_HIP(ctx, hipGetLastError());
+    PM_TRY(bucket_scan(ctx, S, p));
+    hipLaunchKernelGGL(k_region_pass<RS_FINAL>, dim3(sblocks), dim3(1024), lds, st, b.keys, b.vals, b.region_off, p.regions, 0u,
+                       p.lo_buckets, chunk, (uint32_t *)nullptr, S.bucket_off.as<uint32_t>(), cursor, S.sorted.as<uint32_t>(),
+                       (uint16_t *)nullptr, (uint32_t *)nullptr);
+    PM_HIP(ctx, hipGetLastError());
+    return PM_OK;
+}
+
+// Pipeline (B), tables and wide: (scalar, window) entries -> table (or base) indices grouped by bucket
+template <class C>
+static int sort_tables(pm_ctx *ctx, MsmSet &S, const BucketPlan &p, const MsmTables &tb, const Fp<typename C::FrP> *d_scalars) {
+    MsmWorkspace &ws = ctx->msm;
+    PM_HIP(ctx, ws.digits.reserve(p.keys_bytes + p.E * 4 + 128));     // + 128: the staged passes read whole groups of ST_PER_LANE entries
+    PM_HIP(ctx, ws.region.reserve((3 * (size_t)p.regions + 4) * 4));
+    SortBuffers b;
+    b.keys = (uint16_t *)ws.digits.p;
+    b.vals = (uint32_t *)((uint8_t *)ws.digits.p + p.keys_bytes);
+    b.region_count = ws.region.as<uint32_t>();
+    b.region_off = b.region_count + p.regions;
+    b.region_cursor = b.region_off + p.regions + 1;
+    PM_HIP(ctx, hipMemsetAsync(S.counts.as<uint32_t>(), 0, 2 * p.NB * 4, ctx->stream));
+    PM_TRY((sort_first_level<typename C::FrP>(ctx, p, tb, d_scalars, b)));
+    return p.lo_buckets == (1u << LO_BITS) ? sort_three_levels(ctx, S, p, b) : sort_one_region(ctx, S, p, b);
+}
+
+// ------------------------------------------------------------------------------- driver
+// One bucket pipeline over at most msm_max_piece() pairs (internal.h; sorted-entry positions are u32: W * len < 2^32), ENQUEUED on
+// ctx->stream: sort, task order, accumulation, reduction, and the copy of the plan's nsums window sums (internal form) to h_sums.
+// Nothing here waits; the caller synchronises the stream and hands h_sums to host_horner.
+// d_bases: the piece's bases (per-window); in wide mode the MSM's first base (internal form), the piece's pairs being
+// d_bases[tb->base_index ...]; unused with tables.
 //
 // (Round 4 measured the sort in CHUNKS of pairs -- chunk k + 1 sorted on a second stream under chunk k's accumulation, one bucket
 // set, the next chunk's tasks continuing from the previous partials -- and lost: k_accumulate holds 2 x 248 of a SIMD's 512 registers,
@@ -1199,272 +1358,67 @@ static int msm_piece(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C:
 // time-slice instead of overlapping.  +1.8 ms per proof at two chunks, +5 at three: profiles/r04_chunked_sort_overlap_negative.txt;
 // the implementation is commit 5de5c70.)
 template <class C>
-static int msm_piece_tables(pm_ctx *ctx, const MsmTables &tb, const Fp<typename C::FrP> *d_scalars,
-                            size_t len, Affine<C> *h_out, int *h_inf, const Affine<C> *plain = nullptr, XYZZ<C> *async_res = nullptr) {
-    typedef typename C::FrP FrP;
-    StageTimer t_total(ctx, T_MSM_TOTAL);
-    MsmWorkspace &ws = ctx->msm;
-    const unsigned c = tb.c, nwin = tb.nwin;
-    const bool wide = tb.wide;
-    if ((wide && !plain) || (wide && async_res)) return PM_ERR_INVALID_ARG;
-    const size_t NB1 = (size_t)1 << (c - 1);               // buckets of one window
-    // buckets of the pipeline: one shared set, or one set per window -- 2^(c-1) for the 256 % nwin windows of c bits, half of that for
-    // the narrower ones (round 6; wide_narrow_buckets)
-    const size_t NBn = wide ? wide_narrow_buckets(nwin, c) : 0;
-    const unsigned n_wide_sets = !wide ? 1u : (NBn == NB1 ? nwin : 256 % nwin), n_narrow_sets = wide ? nwin - n_wide_sets : 0u;
-    const size_t NB = (size_t)n_wide_sets * NB1 + (size_t)n_narrow_sets * NBn;
-    const uint32_t win_buckets = wide ? (uint32_t)NB1 : 0u, narrow_buckets = (uint32_t)NBn;
-    const unsigned lo_buckets = (unsigned)(NB < ((size_t)1 << LO_BITS) ? NB : ((size_t)1 << LO_BITS));
-    const unsigned regions = (unsigned)(NB / lo_buckets);
-    if (regions > 1024 || (size_t)regions * lo_buckets != NB) return PM_ERR_INVALID_ARG;   // whole regions only (wide mode: nwin 2^(c-1) buckets)
-    for (unsigned w = 0; w < nwin; ++w)   // the kernels derive the layout from nwin alone
-        if (tb.off[w] != win_off(nwin, w) || tb.width[w] != win_width(nwin, w)) return PM_ERR_INVALID_ARG;
-    const bool two_level = NB1 >= 4096;                // msm_reduce.hip: k_reduce_level0 / level1 / final
-    if (wide && !two_level) return PM_ERR_INVALID_ARG;  // wide plans have c >= 16 (setup.hip: wide_plan)
-    const size_t Emax = (size_t)nwin * len;
-    size_t seg = 2 * (Emax / NB + 1);
-    if (seg < 64) seg = 64;
-    if (ctx->opt.v[PM_OPT_MSM_TASK_LEN] > 0) seg = (size_t)ctx->opt.v[PM_OPT_MSM_TASK_LEN];
-    const size_t max_tasks = NB + Emax / seg + 1;
-    const unsigned chunk = 1u << RS_CHUNK_LOG;
-    const size_t keys_bytes = (Emax * 2 + 15) & ~(size_t)15;
-    PM_HIP(ctx, ws.digits.reserve(keys_bytes + Emax * 4 + 128));     // + 128: the staged passes read whole groups of ST_PER_LANE entries
-    PM_HIP(ctx, ws.region.reserve((3 * (size_t)regions + 4) * 4));
-    PM_HIP(ctx, ws.cursor.reserve(((NB + SCAN_TILE - 1) / SCAN_TILE + 1) * 8));
-    MsmSet &S = ws.set;
+static int msm_enqueue(pm_ctx *ctx, const BucketPlan &p, const MsmTables *tb, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_scalars,
+                       XYZZ<C> *h_sums) {
+    MsmSet &S = ctx->msm.set;
+    if (p.wide && !d_bases) return PM_ERR_INVALID_ARG;
+    PM_TRY(reserve_set<C>(ctx, S, p));
     {
-        PM_HIP(ctx, S.sorted.reserve(Emax * 4 + 16));      // + 16: k_accumulate reads aligned quads of indices
-        PM_HIP(ctx, S.counts.reserve(2 * NB * 4));
-        PM_HIP(ctx, S.bucket_off.reserve((NB + 1) * 4));
-        PM_HIP(ctx, S.task_off.reserve((NB + 1) * 4));
-        PM_HIP(ctx, S.partials.reserve(max_tasks * sizeof(XYZZ<C>)));
-        PM_HIP(ctx, S.task_cnt.reserve(NB * 4));
-    }
-    const unsigned red_lanes = (unsigned)((NB + RED_K - 1) / RED_K);              // single-level path (small NB)
-    unsigned red_block = 64;
-    while (red_block < red_lanes && red_block < 256) red_block <<= 1;
-    const unsigned bpw = (red_lanes + red_block - 1) / red_block;
-    if (!two_level) PM_HIP(ctx, ws.wsum.reserve(((size_t)bpw + 4) * sizeof(XYZZ<C>)));
-    uint16_t *keys = (uint16_t *)ws.digits.p;
-    uint32_t *vals = (uint32_t *)((uint8_t *)ws.digits.p + keys_bytes);
-    uint32_t *region_count = ws.region.as<uint32_t>(), *region_off = region_count + regions, *region_cursor = region_off + regions + 1;
-#ifndef PM_PARTITION_LANES
-#define PM_PARTITION_LANES 512
-#endif
-#ifndef PM_PARTITION_WIDE_LANES
-#define PM_PARTITION_WIDE_LANES 1024
-#endif
-    // scalars per partition workgroup.  From 512 regions up (the 12-window wide plan of a 2^24-gate key: 4 x 2^21 + 8 x 2^20 buckets):
-    // 1024, so that a workgroup's run inside a region is 24 entries (96 B of values), not 12 -- what the first level pays for is
-    // the length of that run, not the number of regions: same-box A/B at 2^24 gates in profiles/r06_wide_ragged_sets_ab.txt (512
-    // regions on 512 lanes: sort + 5 ... 8 ms against 768 regions on 1024) and r06_wide_12_windows_ab.txt
-#ifndef PM_PARTITION_WIDE_FROM
-#define PM_PARTITION_WIDE_FROM 512
-#endif
-    const unsigned pbd = regions >= PM_PARTITION_WIDE_FROM ? PM_PARTITION_WIDE_LANES : nwin <= 16 ? PM_PARTITION_LANES : 256;
-    if (regions > 2 * pbd) return PM_ERR_INVALID_ARG;                  // at most two regions per scan lane (k_tbl_partition)
-    const size_t plds = 2 * 1024 * 4 + (size_t)pbd * nwin * 8;
-    {
-        const unsigned pblocks_max = (unsigned)((len + pbd - 1) / pbd);
-        const BlockScanShape bsh_max = block_scan_shape(pblocks_max, regions);
-        PM_HIP(ctx, ws.block_cnt.reserve(((size_t)pblocks_max + bsh_max.G) * regions * 4));
-    }
-    const unsigned SUB_BINS = 128, FIN_BINS = 256, FIN_BITS = 8;
-    const unsigned nsub = regions * SUB_BINS;
-    if (lo_buckets == (1u << LO_BITS)) {
-        PM_HIP(ctx, ws.sub.reserve((3 * (size_t)nsub + 4) * 4));
-        PM_HIP(ctx, ws.digits2.reserve(keys_bytes + Emax * 4 + 128));
-    }
-
-    // ---- the sort: (scalar, window) entries -> table indices grouped by bucket, task order
-    auto sort_all = [&]() -> int {
         StageTimer t(ctx, T_MSM_SORT);
-        hipStream_t st = ctx->stream;
-        const size_t lo = 0, cnt = len;
-        const size_t E = (size_t)nwin * cnt;
-        const unsigned char *inf = tb.inf + tb.base_index + lo;
-        const Fp<FrP> *sc = d_scalars + lo;
-        uint32_t *counts = S.counts.as<uint32_t>(), *cursor = counts + NB;
-        PM_HIP(ctx, hipMemsetAsync(counts, 0, 2 * NB * 4, st));
-        PM_HIP(ctx, hipMemsetAsync(region_count, 0, (size_t)regions * 4, st));
-        const unsigned pblocks = (unsigned)((cnt + pbd - 1) / pbd);
-        const BlockScanShape bsh = block_scan_shape(pblocks, regions);
-        uint32_t *block_cnt = ws.block_cnt.as<uint32_t>(), *block_partial = block_cnt + (size_t)pblocks * regions;
-        int launched = 0;
-#define PM_TBL_CASE(NW)                                                                                                     \
-        case NW:                                                                                                                \
-            hipLaunchKernelGGL((k_tbl_count<FrP, NW>), dim3(pblocks), dim3(pbd), 0, st, sc, inf, cnt, regions,                  \
-                               block_cnt, win_buckets, narrow_buckets);                                                         \
-            hipLaunchKernelGGL(k_block_sums, dim3(bsh.G), dim3(1024), 0, st, block_cnt, pblocks, regions, bsh, block_partial);  \
-            hipLaunchKernelGGL(k_block_offsets, dim3(bsh.G), dim3(1024), 0, st, block_cnt, pblocks, regions, bsh, block_partial, \
-                               region_count);                                                                                  \
-            hipLaunchKernelGGL(k_region_offsets, dim3(1), dim3(1024), 0, st, region_count, region_off, region_cursor,           \
-                               regions);                                                                                        \
-            if (hipFuncSetAttribute((const void *)k_tbl_partition<FrP, NW>, hipFuncAttributeMaxDynamicSharedMemorySize,         \
-                                    (int)plds) != hipSuccess) break;                                                            \
-            hipLaunchKernelGGL((k_tbl_partition<FrP, NW>), dim3(pblocks), dim3(pbd), plds, st, sc, inf, cnt,                    \
-                               regions, region_off, block_cnt, wide ? (size_t)0 : tb.stride, tb.base_index + lo, keys, vals,    \
-                               win_buckets, narrow_buckets);                                                                    \
-            launched = 1;                                                                                                       \
-            break;
-        switch (nwin) {
-            PM_TBL_CASE(10) PM_TBL_CASE(11) PM_TBL_CASE(12) PM_TBL_CASE(13) PM_TBL_CASE(14) PM_TBL_CASE(15) PM_TBL_CASE(16)
-            PM_TBL_CASE(17) PM_TBL_CASE(18) PM_TBL_CASE(19) PM_TBL_CASE(20) PM_TBL_CASE(21) PM_TBL_CASE(22) PM_TBL_CASE(23)
-            PM_TBL_CASE(24) PM_TBL_CASE(25) PM_TBL_CASE(26) PM_TBL_CASE(27) PM_TBL_CASE(28) PM_TBL_CASE(29) PM_TBL_CASE(30)
-            PM_TBL_CASE(31) PM_TBL_CASE(32)
-            default: break;
-        }
-#undef PM_TBL_CASE
-        if (!launched) return PM_ERR_INVALID_ARG;
-        PM_HIP(ctx, hipGetLastError());
-        const unsigned sblocks = (unsigned)((E + chunk - 1) / chunk);
-        const unsigned ntiles = (unsigned)((NB + SCAN_TILE - 1) / SCAN_TILE);
-        auto bucket_scan = [&]() -> int {
-            hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(256), 0, st, counts, S.bucket_off.as<uint32_t>(),
-                               S.task_off.as<uint32_t>(), ws.cursor.as<uint32_t>(), NB, (unsigned)seg);
-            PM_HIP(ctx, hipGetLastError());
-            hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, st, ws.cursor.as<uint32_t>(), ntiles,
-                               S.bucket_off.as<uint32_t>(), S.task_off.as<uint32_t>(), NB);
-            PM_HIP(ctx, hipGetLastError());
-            hipLaunchKernelGGL(k_scan_add, dim3(ntiles), dim3(256), 0, st, S.bucket_off.as<uint32_t>(),
-                               S.task_off.as<uint32_t>(), ws.cursor.as<uint32_t>(), NB);
-            PM_HIP(ctx, hipGetLastError());
-            return PM_OK;
-        };
-        if (lo_buckets == (1u << LO_BITS)) {
-            // three levels: regions (2^15 buckets) -> 128 sub-regions of 256 buckets -> buckets
-            uint32_t *sub_count = ws.sub.as<uint32_t>(), *sub_off = sub_count + nsub, *sub_cursor = sub_off + nsub + 1;
-            uint16_t *keys2 = (uint16_t *)ws.digits2.p;
-            uint32_t *vals2 = (uint32_t *)((uint8_t *)ws.digits2.p + keys_bytes);
-            PM_HIP(ctx, hipMemsetAsync(sub_count, 0, (size_t)nsub * 4, st));
-            hipLaunchKernelGGL(k_hist_small, dim3(sblocks), dim3(1024), 0, st, keys, region_off, regions, FIN_BITS, SUB_BINS, chunk,
-                               sub_count);
-            PM_HIP(ctx, hipGetLastError());
-            hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, st, sub_count, sub_off, sub_cursor, nsub);
-            PM_HIP(ctx, hipGetLastError());
-            const unsigned stblocks = (unsigned)((E + ST_CHUNK - 1) / ST_CHUNK);
-            hipLaunchKernelGGL(k_region_pass_staged<RS_MID>, dim3(stblocks), dim3(ST_THREADS), 0, st, keys, vals, region_off, regions,
-                               FIN_BITS, SUB_BINS, sub_off, sub_cursor, (uint32_t *)nullptr, keys2, vals2);
-            PM_HIP(ctx, hipGetLastError());
-            hipLaunchKernelGGL(k_hist_small, dim3(sblocks), dim3(1024), 0, st, keys2, sub_off, nsub, 0u, FIN_BINS, chunk, counts);
-            PM_HIP(ctx, hipGetLastError());
-            PM_TRY(bucket_scan());
-            // (round 5 measured the last level WITHOUT LDS staging -- lanes storing their 4-byte indices straight into the sub-region's
-            // 120 KB output window, which stays in L2: the sort of a 2^24-pair MSM 2.66 -> 3.70 ms, a proof +2.2 ms; 64 partial-line
-            // stores per wave instruction cost more than the staging saves: profiles/r05_sort_final_direct_negative.txt)
-            hipLaunchKernelGGL(k_region_pass_staged<RS_FINAL>, dim3(stblocks), dim3(ST_THREADS), 0, st, keys2, vals2, sub_off, nsub, 0u,
-                               FIN_BINS, S.bucket_off.as<uint32_t>(), cursor, S.sorted.as<uint32_t>(), (uint16_t *)nullptr,
-                               (uint32_t *)nullptr);
-            PM_HIP(ctx, hipGetLastError());
-        } else {
-            // small bucket sets (< 2^15): one region, sorted directly with an nbuckets-entry LDS table
-            const size_t lds = (size_t)lo_buckets * 4;
-            hipLaunchKernelGGL(k_region_pass<RS_HIST>, dim3(sblocks), dim3(1024), lds, st, keys, vals, region_off, regions, 0u,
-                               lo_buckets, chunk, counts, (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                               (uint16_t *)nullptr, (uint32_t *)nullptr);
-            PM_HIP(ctx, hipGetLastError());
-            PM_TRY(bucket_scan());
-            hipLaunchKernelGGL(k_region_pass<RS_FINAL>, dim3(sblocks), dim3(1024), lds, st, keys, vals, region_off, regions, 0u,
-                               lo_buckets, chunk, (uint32_t *)nullptr, S.bucket_off.as<uint32_t>(), cursor, S.sorted.as<uint32_t>(),
-                               (uint16_t *)nullptr, (uint32_t *)nullptr);
-            PM_HIP(ctx, hipGetLastError());
-        }
-        PM_TRY(task_order(ctx, S, counts, NB, seg, max_tasks));
-        return PM_OK;
-    };
-    PM_TRY(sort_all());
+        PM_TRY(p.tables ? sort_tables<C>(ctx, S, p, *tb, d_scalars) : sort_windows<C>(ctx, S, p, d_bases, d_scalars));
+        PM_TRY(task_order(ctx, S, p));
+    }
     {
         StageTimer t(ctx, T_MSM_ACCUMULATE);
-        if (wide) PM_TRY((accumulate<C, false>(ctx, S, (const void *)plain, NB, max_tasks)));
-        else PM_TRY((accumulate<C, true>(ctx, S, tb.table, NB, max_tasks)));
+        if (p.tables && !p.wide) PM_TRY((accumulate<C, true>(ctx, S, p, tb->table)));
+        else PM_TRY((accumulate<C, false>(ctx, S, p, (const void *)d_bases)));
     }
-    if (wide) {
-        // all windows' bucket sets reduced by ONE set of launches; then sum_w 2^(off_w) S_w by Horner from the top window: a chain
-        // of 256 dependent doublings -- a few hundred microseconds on the host, milliseconds on one GPU lane
-        std::vector<XYZZ<C>> hS(nwin);
-        {
-            StageTimer t(ctx, T_MSM_REDUCE);
-            PM_TRY(fold_hot_buckets<C>(ctx, S, NB, max_tasks));
-            XYZZ<C> *dres = nullptr;
-            PM_TRY(reduce_two_level<C>(ctx, NB1, &dres, n_wide_sets));                       // the sets of the c-bit windows ...
-            PM_HIP(ctx, hipMemcpyAsync(hS.data(), dres, n_wide_sets * sizeof(XYZZ<C>), hipMemcpyDeviceToHost, ctx->stream));
-            if (n_narrow_sets) {                                                             // ... then those of the (c - 1)-bit ones (stream order:
-                PM_TRY(reduce_two_level<C>(ctx, NBn, &dres, n_narrow_sets, (size_t)n_wide_sets * NB1));   // the workspace is free again)
-                PM_HIP(ctx, hipMemcpyAsync(hS.data() + n_wide_sets, dres, n_narrow_sets * sizeof(XYZZ<C>), hipMemcpyDeviceToHost, ctx->stream));
-            }
-        }
-        PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        XYZZ<C> acc = XYZZ<C>::identity();
-        for (int w = (int)nwin - 1; w >= 0; --w) {
-            for (unsigned b = 0; b < tb.width[w]; ++b) acc = xyzz_dbl<C>(acc);
-            acc = xyzz_add<C>(acc, xyzz_internal_to_std<C>(hS[w]));
-        }
-        *h_inf = acc.is_identity() ? 1 : 0;
-        *h_out = xyzz_to_affine<C>(acc);
-        return PM_OK;
+    StageTimer t(ctx, T_MSM_REDUCE);
+    PM_TRY(fold_hot_buckets<C>(ctx, S, p));
+    XYZZ<C> *d_sums = nullptr;
+    if (!p.two_level) {
+        PM_TRY(reduce_single_level<C>(ctx, S, p, &d_sums));
+    } else {   // all sets of one size by ONE set of launches: those of the c-bit windows (or the shared set) ...
+        PM_TRY(reduce_two_level<C>(ctx, p.NB1, &d_sums, p.n_wide_sets));
     }
-    XYZZ<C> hres;
-    {
-        StageTimer t(ctx, T_MSM_REDUCE);
-        PM_TRY(fold_hot_buckets<C>(ctx, S, NB, max_tasks));
-        XYZZ<C> *dres = nullptr;
-        if (two_level) {
-            PM_TRY(reduce_two_level<C>(ctx, NB, &dres));
-        } else {
-            XYZZ<C> *parts = ws.wsum.as<XYZZ<C>>();
-            dres = parts + bpw;
-            hipLaunchKernelGGL(k_bucket_reduce<C>, dim3(bpw), dim3(red_block), red_block * sizeof(XYZZ28<C>), ctx->stream,
-                               S.partials.as<XYZZ<C>>(), S.task_off.as<uint32_t>(), S.task_cnt.as<uint32_t>(), (unsigned)NB, red_lanes, bpw, parts);
-            PM_HIP(ctx, hipGetLastError());
-            hipLaunchKernelGGL(k_sum_parts<C>, dim3(1), dim3(64), 0, ctx->stream, parts, bpw, dres);
-            PM_HIP(ctx, hipGetLastError());
-        }
-        PM_HIP(ctx, hipMemcpyAsync(async_res ? async_res : &hres, dres, sizeof(hres), hipMemcpyDeviceToHost, ctx->stream));
+    PM_HIP(ctx, hipMemcpyAsync(h_sums, d_sums, p.n_wide_sets * sizeof(XYZZ<C>), hipMemcpyDeviceToHost, ctx->stream));
+    if (p.n_narrow_sets) {   // ... then those of the (c - 1)-bit ones (stream order: the workspace is free again)
+        PM_TRY(reduce_two_level<C>(ctx, p.NBn, &d_sums, p.n_narrow_sets, (size_t)p.n_wide_sets * p.NB1));
+        PM_HIP(ctx, hipMemcpyAsync(h_sums + p.n_wide_sets, d_sums, p.n_narrow_sets * sizeof(XYZZ<C>), hipMemcpyDeviceToHost, ctx->stream));
     }
-    if (async_res) return PM_OK;                       // msm_end: stream sync, then the two lines below
-    PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    XYZZ<C> acc = xyzz_internal_to_std<C>(hres);
-    *h_inf = acc.is_identity() ? 1 : 0;
-    *h_out = xyzz_to_affine<C>(acc);
     return PM_OK;
 }
 
+// plan, enqueue, synchronise, finish -- per piece of at most msm_max_piece() pairs; very long MSMs (the 10n-pair quotient commitment
+// at n >= 2^24 on one GPU) run several, summed on the host
 template <class C>
 int msm_run(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_scalars, size_t len, Affine<C> *h_out,
             int *h_inf, const MsmTables *tables) {
-    if (len == 0) {
-        *h_out = Affine<C>::infinity();
-        *h_inf = 1;
-        return PM_OK;
-    }
     const bool tbl = tables && tables->c;
-    const size_t MSM_MAX_PIECE = msm_max_piece(ctx);
-    const bool wide = tbl && tables->wide;
-    if (len <= MSM_MAX_PIECE)
-        return tbl ? msm_piece_tables<C>(ctx, *tables, d_scalars, len, h_out, h_inf, wide ? d_bases : nullptr)
-                   : msm_piece<C>(ctx, d_bases, d_scalars, len, h_out, h_inf);
-    // very long MSMs (the 10n-pair quotient commitment at n >= 2^24 on one GPU): pieces, summed on the host
+    const size_t max_piece = msm_max_piece(ctx);
     XYZZ<C> acc = XYZZ<C>::identity();
-    for (size_t off = 0; off < len; off += MSM_MAX_PIECE) {
-        size_t cnt = len - off < MSM_MAX_PIECE ? len - off : MSM_MAX_PIECE;
-        Affine<C> part;
-        int inf = 1;
+    std::vector<XYZZ<C>> sums;
+    for (size_t off = 0; off < len; off += max_piece) {
+        StageTimer t_total(ctx, T_MSM_TOTAL);
+        const size_t cnt = len - off < max_piece ? len - off : max_piece;
+        MsmTables tb;
         if (tbl) {
-            MsmTables tb = *tables;
+            tb = *tables;
             tb.base_index += off;
-            PM_TRY(msm_piece_tables<C>(ctx, tb, d_scalars + off, cnt, &part, &inf, wide ? d_bases : nullptr));
-        } else {
-            PM_TRY(msm_piece<C>(ctx, d_bases + off, d_scalars + off, cnt, &part, &inf));
         }
-        if (!inf) xyzz_madd<C>(acc, part, false);
+        BucketPlan p;
+        PM_TRY(bucket_plan(tbl ? &tb : nullptr, cnt, (unsigned)C::FrP::BITS, ctx->opt.v[PM_OPT_MSM_TASK_LEN], p));
+        sums.resize(p.nsums);
+        PM_TRY(msm_enqueue<C>(ctx, p, tbl ? &tb : nullptr, tbl ? d_bases : d_bases + off, d_scalars + off, sums.data()));
+        PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        acc = xyzz_add<C>(acc, host_horner<C>(sums.data(), p.nsums, p.width));
     }
-    *h_inf = acc.is_identity() ? 1 : 0;
-    *h_out = xyzz_to_affine<C>(acc);
+    host_finish<C>(acc, h_out, h_inf);
     return PM_OK;
 }
 
 // Asynchronous pair for a single-piece table-mode MSM: msm_begin enqueues the whole pipeline on ctx->stream and returns at once
-// (the result travels to the context's pinned slot), msm_end waits for the stream and converts the point.  Two contexts (ctx and
+// (the reduced point travels to the context's pinned slot), msm_end waits for the stream and finishes it.  Two contexts (ctx and
 // its helper ctx->aux: own streams, own workspaces) can so run two MSMs concurrently from ONE host thread -- the latency-bound
 // sort front end and bucket reduction of one hide under the accumulation of the other.  MSMs that need the host in the middle
 // (several pieces, wide mode, no tables) run synchronously inside msm_begin; msm_end then just hands the result over.
@@ -1473,14 +1427,15 @@ int msm_begin(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *
     ctx->msm_async = 0;
     const bool tbl = tables && tables->c && !tables->wide;
     if (!ctx_pinned(ctx)) { ctx->err = "pinned result slot allocation failed"; return PM_ERR_HIP; }
-    Affine<C> *slot_pt = (Affine<C> *)((uint8_t *)ctx->h_pinned + 1024);
-    int *slot_inf = (int *)((uint8_t *)ctx->h_pinned + 2048);
     if (len == 0 || !tbl || len > msm_max_piece(ctx)) {           // synchronous: result parked in the slot
-        PM_TRY(msm_run<C>(ctx, d_bases, d_scalars, len, slot_pt, slot_inf, tables));
+        PM_TRY(msm_run<C>(ctx, d_bases, d_scalars, len, pinned_slot<Affine<C>>(ctx, PINNED_MSM_POINT), pinned_slot<int>(ctx, PINNED_MSM_INF), tables));
         ctx->msm_async = 2;
         return PM_OK;
     }
-    PM_TRY(msm_piece_tables<C>(ctx, *tables, d_scalars, len, (Affine<C> *)nullptr, (int *)nullptr, (const Affine<C> *)nullptr, (XYZZ<C> *)ctx->h_pinned));
+    StageTimer t_total(ctx, T_MSM_TOTAL);
+    BucketPlan p;
+    PM_TRY(bucket_plan(tables, len, (unsigned)C::FrP::BITS, ctx->opt.v[PM_OPT_MSM_TASK_LEN], p));   // one shared set: one sum
+    PM_TRY(msm_enqueue<C>(ctx, p, tables, d_bases, d_scalars, pinned_slot<XYZZ<C>>(ctx, PINNED_MSM_SUM)));
     ctx->msm_async = 1;
     return PM_OK;
 }
@@ -1488,13 +1443,12 @@ int msm_begin(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *
 template <class C>
 int msm_end(pm_ctx *ctx, Affine<C> *h_out, int *h_inf) {
     if (ctx->msm_async == 2) {
-        *h_out = *(const Affine<C> *)((const uint8_t *)ctx->h_pinned + 1024);
-        *h_inf = *(const int *)((const uint8_t *)ctx->h_pinned + 2048);
+        *h_out = *pinned_slot<const Affine<C>>(ctx, PINNED_MSM_POINT);
+        *h_inf = *pinned_slot<const int>(ctx, PINNED_MSM_INF);
     } else if (ctx->msm_async == 1) {
         PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const XYZZ<C> acc = xyzz_internal_to_std<C>(*(const XYZZ<C> *)ctx->h_pinned);
-        *h_inf = acc.is_identity() ? 1 : 0;
-        *h_out = xyzz_to_affine<C>(acc);
+        const unsigned char width0 = 0;
+        host_finish<C>(host_horner<C>(pinned_slot<const XYZZ<C>>(ctx, PINNED_MSM_SUM), 1, &width0), h_out, h_inf);
     } else {
         return PM_ERR_STATE;
     }

@@ -599,7 +599,7 @@ int prove_phase1_impl(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const uin
     // synchronisation, so the host does not wait here and the sort's fifteen launches are enqueued while the transforms still run.
     // An unsatisfied witness (prover.rs:107-108) is reported after the MSMs it no longer stops -- the rare path pays, not the proof.
     if (!ctx_pinned(ctx)) { ctx->err = "pinned staging allocation failed"; return PM_ERR_HIP; }
-    volatile unsigned *hflags_p = (volatile unsigned *)((uint8_t *)ctx->h_pinned + PINNED_SLOTS_BYTES);
+    volatile unsigned *hflags_p = pinned_slot<volatile unsigned>(ctx, PINNED_FLAGS);
     *hflags_p = 0;
     PM_HIP(ctx, hipMemcpyAsync((void *)hflags_p, flags, 4, hipMemcpyDeviceToHost, st));
     if (a_early) {
@@ -732,7 +732,7 @@ int prove_phase3_impl(pm_ctx *ctx, const uint64_t *x1_in, const uint64_t *x2_in,
     }
     // rem == 0 (prover.rs:221) is read after the MSM's final synchronisation: no host wait between the division and the sort
     if (!ctx_pinned(ctx)) { ctx->err = "pinned staging allocation failed"; return PM_ERR_HIP; }
-    volatile unsigned *hflags_p = (volatile unsigned *)((uint8_t *)ctx->h_pinned + PINNED_SLOTS_BYTES);
+    volatile unsigned *hflags_p = pinned_slot<volatile unsigned>(ctx, PINNED_FLAGS);
     *hflags_p = 0;
     PM_HIP(ctx, hipMemcpyAsync((void *)hflags_p, flags, 4, hipMemcpyDeviceToHost, st));
     const int st_d = msm_shard<C>(ctx, pk, 2, q, d_xy, d_inf);   // [d]_1 = M8, prover.rs:229

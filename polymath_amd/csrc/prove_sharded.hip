@@ -830,7 +830,7 @@ int prove_phase1_sharded(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const 
     // before the MSM pipelines below could even be enqueued) and into the record after the MSMs' final synchronisation
     uint8_t *stage = nullptr;
     const size_t halo_bytes = (size_t)N * sizeof(Fr);
-    if (ctx_pinned(ctx) && 16 + halo_bytes <= PINNED_STAGE_BYTES) stage = (uint8_t *)ctx->h_pinned + PINNED_SLOTS_BYTES;
+    if (ctx_pinned(ctx) && 16 + halo_bytes <= PINNED_STAGE_BYTES) stage = pinned_slot<uint8_t>(ctx, PINNED_FLAGS);
     struct DrainOnExit {      // without pinned staging the copies target `mine`: no return path may free it while they are pending
         hipStream_t st;
         bool armed;
@@ -1005,7 +1005,7 @@ int prove_phase3_sharded(pm_ctx *ctx, const uint64_t *x1_in, const uint64_t *x2_
         ctx->err = "pinned result slot allocation failed";
         return PM_ERR_HIP;
     }
-    Fr *h_rem = (Fr *)((uint8_t *)ctx->h_pinned + 3072);     // pinned: the copy below must not block the host (msm.hip uses [0, 2052))
+    Fr *h_rem = pinned_slot<Fr>(ctx, PINNED_REMAINDER);      // pinned: the copy below must not block the host
     *h_rem = Fr::one();
     {
         StageTimer t(ctx, T_POLY);

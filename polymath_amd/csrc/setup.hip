@@ -337,25 +337,24 @@ MsmTables tables_plan(size_t total_pairs, unsigned n_msm, size_t resident_points
 }
 
 // Plan of the WIDE mode (no tables: MsmTables::wide): every window has its own bucket set -- 2^(c-1) buckets for the 256 % nwin
-// windows of c bits, half as many for the others (round 6: internal.h: wide_narrow_buckets; until then 2^(c-1) for all: 12 windows
+// windows of c bits, half as many for the others (round 6: internal.h: wide_sets; until then 2^(c-1) for all: 12 windows
 // of 22 / 21 bits reduced 25.2 M buckets instead of 16.8 M and sorted into 768 regions instead of 512).  piece = the pairs one
 // bucket pipeline covers (<= msm_max_piece()).  Cost in the units of tables_plan: accumulation of nwin x piece entries + the
-// reduction of all sets, within the sort front end's limit of 1024 regions of 2^15 buckets (k_tbl_partition: up to two regions
-// per scan lane) and >= 4096 buckets per window (the two-level reduction).  Long MSMs land on 12 windows of 22 / 21 bits: 12
-// additions per pair where the LDS-histogram pipeline of the one-shot MSM stops at c = 16 (16 additions).  force_c
-// (PM_OPT_TABLE_WINDOW_BITS, tuning / tests): the widest window, whatever the cost model says.
+// reduction of all sets, within the sort front end's limit of SORT_MAX_REGIONS regions of 2^15 buckets (k_tbl_partition: one region
+// per scan lane; msm.hip: bucket_plan holds the plan to the workgroup's lanes) and >= 4096 buckets per window (the two-level
+// reduction).  12 windows are the fewest whose widest window (22 bits) passes the c <= 23 test, and where long MSMs land: 12
+// additions per pair where the LDS-histogram pipeline of the one-shot MSM stops at c = 16 (16 additions), in 512 regions (same-box
+// A/B against round 5's 512-region plan of 13 windows: profiles/r06_wide_12_windows_ab.txt).  force_c (PM_OPT_TABLE_WINDOW_BITS,
+// tuning / tests): the widest window, whatever the cost model says.
 MsmTables wide_plan(size_t piece, unsigned force_c) {
     MsmTables best_t;
     double best = 1e300;
-    for (unsigned nwin = 11; nwin <= 16; ++nwin) {
+    for (unsigned nwin = 12; nwin <= 16; ++nwin) {
         MsmTables t;
         tables_layout(t, nwin);
         if (t.c < 16 || t.c > 23) continue;                                   // whole 2^15-bucket regions per window (the sort's first level)
-#ifndef PM_WIDE_MAX_REGIONS
-#define PM_WIDE_MAX_REGIONS 1024          // same-box A/B against round 5's front end: PM_BUILD_FLAGS=-DPM_WIDE_MAX_REGIONS=512
-#endif
-        const double NBT = (double)wide_total_buckets(nwin, t.c);              // all sets: the narrower windows own half as many (round 6)
-        if (NBT / 32768.0 > (double)PM_WIDE_MAX_REGIONS) continue;
+        const double NBT = (double)wide_sets(nwin, t.c).total();               // all sets: the narrower windows own half as many (round 6)
+        if (NBT / 32768.0 > (double)SORT_MAX_REGIONS) continue;
         if ((double)nwin * (double)piece >= 4294967296.0) continue;          // u32 positions of the sorted entries
         if (force_c >= 16 && force_c <= 23) {
             if (t.c == force_c) { best_t = t; break; }
