@@ -28,6 +28,132 @@ static Fp<P> rand_fp() {
     return r;
 }
 
+// Degenerate additions -- a + (-a), a + a, O + a, a + O, O + O, dbl(O), "cancel, then add b" -- through every entry the kernels
+// use: xyzz28_madd + xyzz28_madd_exceptional, xyzz28_add_full, xyzz28_add_into_full, xyzz28_dbl.  The operands are LOOSE: both
+// sides come out of addition chains (a and -a out of different chains, so with different projective coordinates), as a task's
+// accumulator or a running sum does, not out of a fresh load.  The fast paths know the identity by ZZ being zero in EVERY limb, so
+// a cancellation has to return exactly that, and it has to survive xyzz28_store -> xyzz28_load.
+template <class C>
+static int degenerate(const char *name, const std::vector<Affine<C>> &pts) {
+    typedef typename C::FqRR RR;
+    int fails = 0, checks = 0;
+    auto zero28 = []() { XYZZ28<C> z; z.X = z.Y = z.ZZ = z.ZZZ = f28_zero<RR>(); return z; };
+    auto internal = [](const Affine<C> &p) { return Affine<C>{fq_std_to_int<C>(p.x), fq_std_to_int<C>(p.y)}; };
+    auto madd_full = [&](XYZZ28<C> &a, int i, bool negate) {       // what accumulate_task does; -> the fast path's verdict
+        const bool fast = xyzz28_madd<C>(a, internal(pts[i]), negate);
+        if (!fast) a = xyzz28_madd_exceptional<C>(a, internal(pts[i]), negate);
+        return fast;
+    };
+    auto chain28 = [&](std::initializer_list<int> idx, bool negate) {
+        XYZZ28<C> a = zero28();
+        for (int i : idx) madd_full(a, i, negate);
+        return a;
+    };
+    auto same = [&](const XYZZ28<C> &got, const XYZZ<C> &want, const char *what) {
+        ++checks;
+        const XYZZ<C> g = xyzz_internal_to_std<C>(xyzz28_store<C>(got));
+        bool ok = g.is_identity() == want.is_identity();
+        if (ok && !want.is_identity()) {
+            const Affine<C> a1 = xyzz_to_affine<C>(g), a2 = xyzz_to_affine<C>(want);
+            ok = a1.x.eq(a2.x) && a1.y.eq(a2.y);
+        }
+        if (!ok) { ++fails; printf("%s degenerate: %s differs from the dense result\n", name, what); }
+    };
+    auto literal_O = [&](const XYZZ28<C> &a, const char *what) {
+        ++checks;
+        const XYZZ<C> rec = xyzz28_store<C>(a);
+        const bool ok = f28_all_zero<RR>(a.ZZ) && rec.X.is_zero() && rec.Y.is_zero() && rec.ZZ.is_zero() && rec.ZZZ.is_zero() &&
+                        f28_all_zero<RR>(xyzz28_load<C>(rec).ZZ);
+        if (!ok) { ++fails; printf("%s degenerate: %s is not the all-zero identity\n", name, what); }
+    };
+    auto expect = [&](bool cond, const char *what) {
+        ++checks;
+        if (!cond) { ++fails; printf("%s degenerate: %s\n", name, what); }
+    };
+    // a = 3G + 5G + 12G = 20G = pts[19], a2 = the same point from another chain, na = -20G from a third
+    const XYZZ28<C> a = chain28({2, 4, 11}, false), a2 = chain28({11, 2, 4}, false), na = chain28({4, 11, 2}, true), b = chain28({6, 30}, false);
+    XYZZ<C> A = XYZZ<C>::identity(), B = XYZZ<C>::identity();
+    for (int i : {2, 4, 11}) xyzz_madd<C>(A, pts[i], false);
+    for (int i : {6, 30}) xyzz_madd<C>(B, pts[i], false);
+    const XYZZ<C> O = XYZZ<C>::identity(), A2 = xyzz_dbl<C>(A);
+    same(a, XYZZ<C>::from_affine(pts[19]), "the chain 3G + 5G + 12G");
+    same(na, [&] { XYZZ<C> t = O; xyzz_madd<C>(t, pts[19], true); return t; }(), "the chain -(5G + 12G + 3G)");
+    // ---- xyzz28_madd + xyzz28_madd_exceptional
+    {
+        XYZZ28<C> x = a;
+        expect(!madd_full(x, 19, true), "xyzz28_madd did not hand a + (-a) to the cold path");
+        literal_O(x, "madd: a + (-a)");
+        same(x, O, "madd: a + (-a)");
+        expect(madd_full(x, 6, false) && madd_full(x, 30, false), "madd after a cancellation left the fast path");
+        same(x, B, "madd: cancel, then add b");
+        x = a;
+        expect(!madd_full(x, 19, false), "xyzz28_madd did not hand a + a to the cold path");
+        same(x, A2, "madd: a + a");
+        expect(!madd_full(x, 39, true), "xyzz28_madd did not hand 2a + (-2a) to the cold path");
+        literal_O(x, "madd: double, then cancel");
+        x = zero28();
+        madd_full(x, 19, true);
+        same(x, [&] { XYZZ<C> t = O; xyzz_madd<C>(t, pts[19], true); return t; }(), "madd: O + (-a)");
+    }
+    // ---- xyzz28_add_full (registers) and xyzz28_add_into_full (streamed accumulator): the same script for both
+    for (int into = 0; into < 2; ++into) {
+        auto add = [&](XYZZ28<C> &x, const XYZZ28<C> &y) { if (into) xyzz28_add_into_full<C>(&x, y); else xyzz28_add_full<C>(x, y); };
+        const char *tag = into ? "add_into_full" : "add_full";
+        char what[96];
+        auto say = [&](const char *s) { snprintf(what, sizeof what, "%s: %s", tag, s); return (const char *)what; };
+        XYZZ28<C> x = a, probe = a;
+        expect(into ? !xyzz28_add_into<C>(&probe, na) : !xyzz28_add<C>(probe, na), say("a + (-a) stayed on the fast path"));
+        add(x, na);
+        literal_O(x, say("a + (-a)"));
+        same(x, xyzz_add<C>(A, [&] { XYZZ<C> t = O; xyzz_madd<C>(t, pts[19], true); return t; }()), say("a + (-a)"));
+        add(x, b);
+        same(x, B, say("cancel, then add b"));
+        add(x, a);
+        same(x, xyzz_add<C>(B, A), say("cancel, add b, add a"));
+        x = na;                                                     // the other order, through the memory record a partial travels in
+        add(x, xyzz28_load<C>(xyzz28_store<C>(a2)));
+        literal_O(x, say("(-a) + load(store(a))"));
+        x = a;
+        probe = a;
+        expect(into ? !xyzz28_add_into<C>(&probe, a2) : !xyzz28_add<C>(probe, a2), say("a + a stayed on the fast path"));
+        add(x, a2);
+        same(x, A2, say("a + a"));
+        add(x, xyzz28_load<C>(xyzz28_store<C>(x)));
+        same(x, xyzz_dbl<C>(A2), say("2a + load(store(2a))"));
+        x = zero28();
+        add(x, a);
+        same(x, A, say("O + a"));
+        add(x, zero28());
+        same(x, A, say("a + O"));
+        x = zero28();
+        add(x, zero28());
+        literal_O(x, say("O + O"));
+        add(x, na);
+        add(x, a2);
+        literal_O(x, say("O + (-a) + a"));
+    }
+    // ---- xyzz28_dbl
+    {
+        XYZZ28<C> x = zero28();
+        xyzz28_dbl<C>(x);
+        literal_O(x, "dbl: 2 O");
+        x = a;
+        xyzz28_add_full<C>(x, na);
+        xyzz28_dbl<C>(x);
+        literal_O(x, "dbl: 2 (a + (-a))");
+        x = a;
+        xyzz28_dbl<C>(x);
+        same(x, A2, "dbl: 2a against xyzz_dbl");
+        XYZZ28<C> y = a2;
+        xyzz28_add_full<C>(y, a);
+        same(y, xyzz_internal_to_std<C>(xyzz28_store<C>(x)), "dbl: 2a against a + a");
+        xyzz28_add_full<C>(x, chain28({39}, true));                 // 2a + (-40G)
+        literal_O(x, "dbl: 2a + (-2a)");
+    }
+    printf("%s degenerate additions: %d failures of %d checks\n", name, fails, checks);
+    return fails;
+}
+
 template <class C>
 static int run(const char *name, int iters) {
     typedef typename C::FqP Q;
@@ -130,6 +256,8 @@ static int run(const char *name, int iters) {
     Affine<C> pi{fq_std_to_int<C>(pts[7].x), fq_std_to_int<C>(pts[7].y)};
     bool ok1 = xyzz28_madd<C>(e, pi, false), ok2 = xyzz28_madd<C>(e, pi, true), ok3 = xyzz28_madd<C>(e, pi, false);
     if (!ok1 || ok2 || ok3) { fails++; printf("%s exceptional-case detection wrong %d %d %d\n", name, ok1, ok2, ok3); }
+    // 4. what the cold paths RETURN for cancellations, doublings and the identity, on every entry
+    fails += degenerate<C>(name, pts);
     printf("%s: %d failures (%d exceptional cases resolved)\n", name, fails, exceptional);
     return fails;
 }

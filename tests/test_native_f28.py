@@ -14,3 +14,8 @@ def test_f28_host_selftest(tmp_path):
     out = subprocess.run([exe, "1500"], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "bls12_381: 0 failures" in out.stdout and "bn254: 0 failures" in out.stdout
+    # a + (-a), a + a, O + a, a + O, O + O, dbl(O) through madd / add_full / add_into_full / dbl on chain-produced operands:
+    # the dense result, and for every cancellation the all-zero identity that survives store -> load
+    for curve in ("bls12_381", "bn254"):
+        line = [l for l in out.stdout.splitlines() if l.startswith(curve + " degenerate additions:")]
+        assert len(line) == 1 and " 0 failures of " in line[0] and int(line[0].split(" of ")[1].split()[0]) == 43, out.stdout
