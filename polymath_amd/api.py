@@ -26,6 +26,11 @@ STATUS = {0: "PM_OK", 1: "PM_ERR_INVALID_ARG", 2: "PM_ERR_LEN_MISMATCH", 3: "PM_
 # pm_g1_status (include/polymath_hip.h): the verdict of one compressed G1 encoding
 G1_OK, G1_BAD_FLAGS, G1_COORD_GE_P, G1_NOT_ON_CURVE, G1_NOT_IN_SUBGROUP, G1_NONCANONICAL_INF, G1_INF_SIGN = range(7)
 G1_BYTES = {PM_BLS12_381: 48, PM_BN254: 32}                # compressed record of one point
+PROOF_BYTES = {PM_BLS12_381: 176, PM_BN254: 128}            # Proof::serialize_compressed
+# pm_verify_verdict (include/polymath_hip.h): one per proof of pm_verify_batch
+VERIFY_REJECTED, VERIFY_ACCEPTED, VERIFY_MALFORMED = range(3)
+# what pm_last_timings' slots hold after pm_verify_batch (ms: GPU time of the kernels, wall time of the two host parts)
+VERIFY_TIMING_SLOTS = {"decode": 0, "terms": 1, "tree": 2, "host_glue": 3, "host_pairing": 4, "device_total": 7}
 TIMING_SLOTS = ["witness_map", "ntt", "poly", "msm_sort", "msm_accumulate", "msm_reduce", "msm_total", "phase"]
 
 u64p = ct.POINTER(ct.c_uint64)
@@ -61,7 +66,7 @@ EXPORTS = [
     "pm_comm_rccl_unique_id", "pm_comm_rccl_create", "pm_comm_local_create", "pm_comm_from_callbacks", "pm_comm_destroy", "pm_comm_rank",
     "pm_comm_world", "pm_comm_last_error", "pm_comm_kind", "pm_comm_set_timeout_ms", "pm_comm_abort", "pm_comm_failed", "pm_comm_busy_ms", "pm_host_make_vk", "pm_host_verify", "pm_comm_all_gather", "pm_comm_all_to_all", "pm_comm_all_gather_device", "pm_comm_combine_points", "pm_ctx_set_comm",
     "pm_ctx_set_option", "pm_ctx_get_option", "pm_comm_local_set_serialize",
-    "pm_g1_decode", "pm_pk_load_bytes", "pm_pk_export_bases_compressed",
+    "pm_g1_decode", "pm_pk_load_bytes", "pm_pk_export_bases_compressed", "pm_verify_batch",
 ]
 # pm_option / pm_tables_mode (include/polymath_hip.h)
 OPTIONS = {"msm_overlap": 0, "ntt_overlap": 1, "tables": 2, "msm_max_piece_log": 3, "max_seg_log": 4, "inflight_contexts": 5,
@@ -160,6 +165,7 @@ def load_library():
     L.pm_g1_decode.argtypes = [vp, i, vp, sz, i, u64p, vp]
     L.pm_pk_load_bytes.argtypes = [vp, i, vp, sz, i, i, i, i, ct.POINTER(vp)]
     L.pm_pk_export_bases_compressed.argtypes = [vp, vp, i, sz, sz, vp]
+    L.pm_verify_batch.argtypes = [vp, i, i, ct.c_char_p, sz, u64p, sz, vp, sz, sz, ct.c_char_p, vp, intp, ct.POINTER(sz)]
     _lib = L
     return L
 
@@ -252,6 +258,41 @@ def g1_decode(ctx, curve, data, validate=True):
     ctx.check(ctx.L.pm_g1_decode(ctx.h, cid, ct.c_void_p(addr), count, int(bool(validate)), _p(xy), status.ctypes.data_as(ct.c_void_p)))
     del keep
     return xy, status
+
+
+def verify_batch(ctx, curve, transcript, vk_bytes, public_inputs, proofs, seed=None, verdicts=True):
+    """pm_verify_batch: many proofs against one verifying key; the per-proof curve work on the GPU, a handful of pairing checks on
+    the host.  public_inputs: Montgomery limbs [count, n_inputs, 4], WITHOUT the leading one; proofs: a list of
+    Proof::serialize_compressed byte strings or one packed buffer; seed: None or 32 bytes mixed into the weights' key.
+    -> (np.uint8[count] of VERIFY_* codes, or None with verdicts=False; all_accepted: bool; n_checks: int)."""
+    cid = CURVE_IDS[curve]
+    plen = PROOF_BYTES[cid]
+    if isinstance(proofs, (list, tuple)):
+        if any(len(p) != plen for p in proofs):
+            raise PolymathError(1, "pm_verify_batch: a proof is not %d bytes" % plen)
+        proofs = b"".join(bytes(p) for p in proofs)
+    keep, addr, nbytes = _byte_view(proofs)
+    if nbytes % plen:
+        raise PolymathError(1, "pm_verify_batch: not a whole number of %d-byte proofs" % plen)
+    count = nbytes // plen
+    pub = _c(public_inputs).reshape(count, -1, 4) if count and np.size(public_inputs) else np.zeros((count, 0, 4), dtype=np.uint64)
+    n_inputs = pub.shape[1]
+    if seed is not None and len(seed) != 32:
+        raise ValueError("seed: 32 bytes")
+    out = np.zeros(count, dtype=np.uint8) if verdicts else None
+    acc, checks = ct.c_int(0), ct.c_size_t(0)
+    ctx.check(ctx.L.pm_verify_batch(ctx.h, cid, TRANSCRIPT_IDS[transcript], bytes(vk_bytes), len(vk_bytes), _p(pub) if pub.size else None, n_inputs,
+                                    ct.c_void_p(addr), plen, count, bytes(seed) if seed is not None else None,
+                                    out.ctypes.data_as(ct.c_void_p) if verdicts else None, ct.byref(acc), ct.byref(checks)))
+    del keep
+    return out, bool(acc.value), int(checks.value)
+
+
+def verify_batch_timings(ctx):
+    """pm_last_timings after verify_batch, under the names of VERIFY_TIMING_SLOTS (ms)."""
+    arr = (ct.c_double * len(TIMING_SLOTS))()
+    ctx.L.pm_last_timings(ctx.h, arr, len(TIMING_SLOTS))
+    return {k: float(arr[v]) for k, v in VERIFY_TIMING_SLOTS.items()}
 
 
 def layout_indices(n, shard_count, shard_rank, coefficients=True):

@@ -20,6 +20,11 @@ using namespace pm;
 extern "C" void pm_host_keccak_f1600(uint64_t state[25]) { pmhost::keccak_f1600(state); }
 
 // ------------------------------------------------------------------------------ helpers
+int pm::host_threads_env() {
+    static const int env_threads = [] { const char *e = getenv("PM_HOST_THREADS"); return e ? std::max(1, atoi(e)) : 0; }();   // read once
+    return env_threads;
+}
+
 // body(lo, hi, thread) over [0, count) in contiguous chunks on up to 32 host threads (one below 2^16 items).  An exception in a
 // worker (bad_alloc) is caught there and re-thrown on the calling thread after the join -- never a std::terminate.
 template <class F>
@@ -27,7 +32,7 @@ static void parallel_chunks(uint64_t count, F body) {
     unsigned T = std::thread::hardware_concurrency();
     if (T > 32) T = 32;
     if (T < 1 || count < ((uint64_t)1 << 16)) T = 1;
-    static const int env_threads = [] { const char *e = getenv("PM_HOST_THREADS"); return e ? std::max(1, atoi(e)) : 0; }();   // read once
+    const int env_threads = host_threads_env();
     if (env_threads) T = (unsigned)env_threads;
     if (T == 1) { body((uint64_t)0, count, 0u); return; }
     std::vector<std::thread> th;

@@ -307,6 +307,9 @@ struct HostProfile {
     }
 };
 
+// PM_HOST_THREADS of the environment (read once, api.hip): the host glue's thread count; 0 = not set, the caller chooses
+int host_threads_env();
+
 // ---- per-curve entry points implemented in the .hip translation units -----------------------
 template <class C>
 int ntt_run(pm_ctx *ctx, Fp<typename C::FrP> *d_data, unsigned log_n, bool inverse);

@@ -7,7 +7,8 @@
 //   BN254    : w^12 = 18 w^6 - 82 (i = w^6 - 9), D-type twist (x w^2, y w^3), optimal ate: loop over 6x + 2, then the
 //              two Frobenius line steps with pi(Q) and -pi^2(Q).
 // Any non-degenerate bilinear map gives the same accept/reject answer for a product-equals-one check;
-// bilinearity is unit-tested (tests/native/host_selftest.cpp).  ~0.3 s per check.
+// bilinearity is unit-tested (tests/native/host_selftest.cpp).  Measured (profiles/verify_batch.txt): a check of three pairs
+// 118 ms on BLS12-381, 57 ms on BN254; a whole verification (two pairs and the G1 glue) 142.5 ms / 59.1 ms.
 #pragma once
 #include <array>
 #include <vector>

@@ -370,21 +370,36 @@ public:
         return vk;
     }
 
-    // verify (lib.rs:80-90) -> verify_proof (verifier.rs:19-62).  `public_inputs` WITHOUT the leading one (:26).
-    static bool verify(const VerifyingKeyT<C> &vk, const std::vector<Fr> &public_inputs, const Proof<C> &proof) {
-        typedef pm::XYZZ<C> J;
+    // The transcript and scalar part of verify_proof (verifier.rs:24-42), shared by verify and the batch verifier
+    // (csrc/verify_batch.hip).  a_bytes / c_bytes: the COMPRESSED records of [a]_1 and [c]_1 -- an accepted encoding is canonical
+    // (wire.hpp: deser_g1), so the bytes a proof arrived in are the bytes ser_g1 would hash.
+    struct Challenges { Fr x1, x2, c_at_x1; };
+    static Challenges verifier_challenges(const VerifyingKeyT<C> &vk, const std::vector<Fr> &public_inputs, const uint8_t *a_bytes,
+                                          const uint8_t *c_bytes, const Fr &a_at_x1) {
         T t("polymath");                                                                   // :24
         std::vector<Fr> pub{Fr::one()};
         pub.insert(pub.end(), public_inputs.begin(), public_inputs.end());                 // :26
-        Fr x1 = compute_x1(t, pub, proof.a_g1, proof.c_g1);                                // :29
-        Fr y1 = F::pow(x1, vk.sigma), y1_inv = F::inv(y1);                                 // :32
+        Challenges ch;
+        ch.x1 = compute_x1_bytes(t, pub, a_bytes, c_bytes);                                // :29
+        Fr y1 = F::pow(ch.x1, vk.sigma), y1_inv = F::inv(y1);                              // :32
         Fr y1_gamma = F::pow(y1_inv, MINUS_GAMMA);                                         // :34
         ProvingKey<C> view;                                                                // n / omega carrier for compute_pi_at_x1
         view.n = vk.n; view.omega = vk.omega;
-        Fr pi_at_x1 = compute_pi_at_x1(view, pub, x1, y1_gamma);                           // :35
+        Fr pi_at_x1 = compute_pi_at_x1(view, pub, ch.x1, y1_gamma);                        // :35
         Fr y1_alpha = F::pow(y1_inv, MINUS_ALPHA);                                         // :37
-        Fr c_at_x1 = F::mul(F::sub(F::mul(F::add(proof.a_at_x1, y1_gamma), proof.a_at_x1), pi_at_x1), F::inv(y1_alpha));   // :40
-        Fr x2 = compute_x2(t, x1, proof.a_at_x1, c_at_x1);                                 // :42
+        ch.c_at_x1 = F::mul(F::sub(F::mul(F::add(a_at_x1, y1_gamma), a_at_x1), pi_at_x1), F::inv(y1_alpha));   // :40
+        ch.x2 = compute_x2(t, ch.x1, a_at_x1, ch.c_at_x1);                                 // :42
+        return ch;
+    }
+
+    // verify (lib.rs:80-90) -> verify_proof (verifier.rs:19-62).  `public_inputs` WITHOUT the leading one (:26).
+    static bool verify(const VerifyingKeyT<C> &vk, const std::vector<Fr> &public_inputs, const Proof<C> &proof) {
+        typedef pm::XYZZ<C> J;
+        Bytes a_bytes, c_bytes;
+        ser_g1<C>(proof.a_g1, a_bytes);
+        ser_g1<C>(proof.c_g1, c_bytes);
+        const Challenges ch = verifier_challenges(vk, public_inputs, a_bytes.data(), c_bytes.data(), proof.a_at_x1);   // :24-42
+        const Fr &x1 = ch.x1, &x2 = ch.x2, &c_at_x1 = ch.c_at_x1;
         // commitments_minus_evals_in_g1 = a + x2 c - (a_at_x1 + x2 c_at_x1) [1]_1         :44-47
         auto smul = [](const G1Point<C> &g, const Fr &k_mont) {
             J acc = J::identity();
@@ -411,14 +426,22 @@ public:
 
     // common.rs:21-30
     static Fr compute_x1(T &t, const std::vector<Fr> &public_inputs, const G1Point<C> &a, const G1Point<C> &c) {
+        Bytes ab, cb;
+        ser_g1<C>(a, ab);
+        ser_g1<C>(c, cb);
+        return compute_x1_bytes(t, public_inputs, ab.data(), cb.data());
+    }
+    // the same on the two points' compressed records (4 * C::FqP::N bytes each)
+    static Fr compute_x1_bytes(T &t, const std::vector<Fr> &public_inputs, const uint8_t *a_bytes, const uint8_t *c_bytes) {
+        const size_t NB = 4 * C::FqP::N;
         Bytes m;
         ser_u64(public_inputs.size(), m);
         for (const Fr &v : public_inputs) ser_fr<C>(v, m);
         t.append_message("public_inputs", m);
         Bytes g;
         ser_u64(2, g);
-        ser_g1<C>(a, g);
-        ser_g1<C>(c, g);
+        g.insert(g.end(), a_bytes, a_bytes + NB);
+        g.insert(g.end(), c_bytes, c_bytes + NB);
         t.append_message("commitments", g);
         return t.challenge("x1");
     }

@@ -71,6 +71,11 @@ pub const PM_G1_NOT_IN_SUBGROUP: u8 = 4;
 pub const PM_G1_NONCANONICAL_INF: u8 = 5;
 pub const PM_G1_INF_SIGN: u8 = 6;
 
+// pm_verify_verdict
+pub const PM_VERIFY_REJECTED: u8 = 0;
+pub const PM_VERIFY_ACCEPTED: u8 = 1;
+pub const PM_VERIFY_MALFORMED: u8 = 2;
+
 // pm_transcript
 pub const PM_TRANSCRIPT_MERLIN: i32 = 0;
 pub const PM_TRANSCRIPT_KECCAK256: i32 = 1;
@@ -166,6 +171,7 @@ extern "C" {
     pub fn pm_host_prove_sharded(ctx: *mut pm_ctx, pk: *const pm_pk, transcript: i32, instance_host: *const u64, x: *const u64, w: *const u64, assignment_on_device: i32, r_a: *const u64, combine: pm_combine_fn, user: *mut c_void, proof_bytes: *mut u8, capacity: usize, proof_len: *mut usize) -> i32;
     pub fn pm_host_make_vk(curve: i32, n: u64, m0: u64, sigma: u64, omega: *const u64, x_trapdoor: *const u64, z_trapdoor: *const u64, vk_bytes: *mut u8, capacity: usize, vk_len: *mut usize) -> i32;
     pub fn pm_host_verify(curve: i32, transcript: i32, vk_bytes: *const u8, vk_len: usize, public_inputs: *const u64, n_inputs: usize, proof_bytes: *const u8, proof_len: usize, accepted: *mut i32) -> i32;
+    pub fn pm_verify_batch(ctx: *mut pm_ctx, curve: i32, transcript: i32, vk_bytes: *const u8, vk_len: usize, public_inputs: *const u64, n_inputs: usize, proofs: *const u8, proof_len: usize, count: usize, seed32: *const u8, verdicts: *mut u8, all_accepted: *mut i32, n_checks: *mut usize) -> i32;
     pub fn pm_host_keccak_f1600(state: *mut u64);
     // ---- multi-GPU exchange layer (no reference counterpart: the reference is single-process CPU code)
     pub fn pm_comm_rccl_unique_id(out_128_bytes: *mut c_void) -> i32;

@@ -268,6 +268,25 @@ pub struct Context {
     device: i32,
 }
 
+/// `pm_verify_verdict`: what [`Context::verify_batch`] says about one proof.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Verdict {
+    Rejected,
+    Accepted,
+    /// the bytes `pm_host_verify` refuses: a point that does not decode into the group, `a_at_x1 >= r`
+    Malformed,
+}
+
+impl Verdict {
+    fn from_raw(v: u8) -> Verdict {
+        match v {
+            sys::PM_VERIFY_ACCEPTED => Verdict::Accepted,
+            sys::PM_VERIFY_MALFORMED => Verdict::Malformed,
+            _ => Verdict::Rejected,
+        }
+    }
+}
+
 // SAFETY: a pm_ctx may be driven from any ONE thread at a time (the header's threading rule); `&mut self` on every call
 // that touches it enforces that.
 unsafe impl Send for Context {}
@@ -308,6 +327,32 @@ impl Context {
         } else {
             Err(HipError { status: Status::from_raw(rc), message: self.last_error() })
         }
+    }
+
+    /// Many proofs against one verifying key (`pm_verify_batch`): the per-proof curve work on the GPU, a handful of pairing
+    /// checks on the host.  `public_inputs`: `proofs.len() / proof_len` x `n_inputs` `Fr` as Montgomery limbs, WITHOUT the leading
+    /// one; `proofs`: packed `Proof::serialize_compressed` records; `transcript`: a `sys::PM_TRANSCRIPT_*` id; `seed`: mixed
+    /// into the weights' key (the weights are bound to the batch either way).  Returns one verdict per proof and the number of
+    /// pairing checks made.
+    pub fn verify_batch(&mut self, curve: Curve, transcript: i32, vk_bytes: &[u8], public_inputs: &[u64], n_inputs: usize, proofs: &[u8],
+                        seed: Option<&[u8; 32]>) -> Result<(Vec<Verdict>, usize), HipError> {
+        let proof_len = match curve {
+            Curve::Bls12_381 => 176,
+            Curve::Bn254 => 128,
+        };
+        if proofs.len() % proof_len != 0 || public_inputs.len() != proofs.len() / proof_len * n_inputs * sys::PM_FR_LIMBS {
+            return Err(err(Status::InvalidArg, "verify_batch: proofs / public_inputs do not have the batch's shape"));
+        }
+        let count = proofs.len() / proof_len;
+        let mut raw = vec![0u8; count];
+        let (mut all, mut checks) = (0i32, 0usize);
+        // SAFETY: live context; every pointer covers the length passed with it, `raw` holds `count` bytes, the seed is 32 bytes or null.
+        let rc = unsafe {
+            sys::pm_verify_batch(self.raw, curve.id(), transcript, vk_bytes.as_ptr(), vk_bytes.len(), public_inputs.as_ptr(), n_inputs, proofs.as_ptr(),
+                                 proof_len, count, seed.map_or(core::ptr::null(), |s| s.as_ptr()), raw.as_mut_ptr(), &mut all, &mut checks)
+        };
+        self.check(rc)?;
+        Ok((raw.into_iter().map(Verdict::from_raw).collect(), checks))
     }
 
     /// Run `f` on this thread's context (created on first use on `device`).

@@ -1,0 +1,74 @@
+"""Batch verification against single verification (DESIGN.md "Batch verification"; profiles/verify_batch.txt).
+
+    python tools/verify_bench.py --count 1024 [--bad 8] [--curve bls12_381] [--distinct 64]
+
+Makes proofs of circuits.MiMCDemo (16 rounds) on one key -- `--distinct` of them with their own witness and r_a, tiled up to
+`--count` -- and times (a) verify_batch, (b) the same with verdicts=False, (c) pm_host_verify on 4 of the proofs (mean) and,
+with --bad F, (d) the batch with F proofs tampered (a_at_x1 + 1, spread evenly): the bisection.  Prints ONE JSON line; the
+kernel times are pm_last_timings' (HIP events inside the call)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--count", type=int, required=True)
+    ap.add_argument("--bad", type=int, default=0)
+    ap.add_argument("--curve", default="bls12_381")
+    ap.add_argument("--distinct", type=int, default=64)
+    a = ap.parse_args()
+    from polymath_amd import api, circuits as PC, rng as R
+    from polymath_amd.polymath import Polymath
+    pm = Polymath(a.curve, "merlin", device=0)
+    f, r = pm.field, pm.field.r
+    rng = R.StdRng.seed_from_u64(7)
+    consts = [R.fr_rand(rng, r) for _ in range(16)]
+    shape = PC.MiMCDemo(R.fr_rand(rng, r), R.fr_rand(rng, r), consts)
+    pk = pm.setup(shape, rng)
+    vk = pm.make_vk(pk, *pm.last_trapdoors)
+    made = []
+    for _ in range(min(a.distinct, a.count)):
+        circuit = PC.MiMCDemo(R.fr_rand(rng, r), R.fr_rand(rng, r), consts)
+        made.append((f.fr_limbs(pm._synthesize(circuit)[1][1:]), pm.prove(pk, circuit, rng).to_bytes()))
+    items = [made[i % len(made)] for i in range(a.count)]
+    pub = np.stack([x for x, _ in items])
+    proofs = [p for _, p in items]
+
+    def timed(proofs, **kw):
+        t0 = time.perf_counter()
+        v, ok, checks = api.verify_batch(pm.ctx, a.curve, "merlin", vk, pub, b"".join(proofs), **kw)
+        wall = (time.perf_counter() - t0) * 1e3
+        return dict(wall_ms=round(wall, 3), all_accepted=ok, n_checks=checks, rejected=int((v == 0).sum()) if v is not None else None,
+                    **{k + "_ms": round(x, 3) for k, x in api.verify_batch_timings(pm.ctx).items()})
+
+    timed(proofs[:2])                                  # first launch: code objects
+    out = dict(curve=a.curve, count=a.count, distinct=len(made), gates=pk.n)
+    out["batch"] = timed(proofs)
+    out["batch_no_verdicts"] = timed(proofs, verdicts=False)
+    t0 = time.perf_counter()
+    for x, p in items[:4]:
+        assert api.verify(a.curve, "merlin", vk, x, p)
+    out["host_verify_ms"] = round((time.perf_counter() - t0) * 1e3 / min(4, len(items)), 3)
+    out["proofs_per_s"] = round(a.count / out["batch"]["wall_ms"] * 1e3, 1)
+    out["ratio_to_count_singles"] = round(out["batch"]["wall_ms"] / (a.count * out["host_verify_ms"]), 6)
+    if a.bad:
+        g1 = api.G1_BYTES[api.CURVE_IDS[a.curve]]
+        tampered = list(proofs)
+        for k in range(a.bad):
+            i = (2 * k + 1) * a.count // (2 * a.bad)
+            p = tampered[i]
+            v = (int.from_bytes(p[2 * g1:2 * g1 + 32], "little") + 1) % r
+            tampered[i] = p[:2 * g1] + v.to_bytes(32, "little") + p[2 * g1 + 32:]
+        out["descent"] = dict(bad=a.bad, **timed(tampered))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
