@@ -328,7 +328,7 @@ int pm_host_verify(int curve, int transcript, const uint8_t *vk_bytes, size_t vk
  *   *all_accepted : 1 iff every proof is PM_VERIFY_ACCEPTED (count == 0: 1, with *n_checks = 0)
  * PM_ERR_INVALID_ARG, nothing computed: a malformed vk, another proof_len, an unknown curve or transcript, count > 2^20.
  * Device and host memory are taken per call and returned.  pm_last_timings afterwards: slot 0 the decode kernel, 1 the terms kernel,
- * 2 the tree kernels, 7 the device part as a whole (GPU ms); 3 the host's per-proof glue, 4 the host's pairing checks (wall ms). */
+ * 2 the tree kernels, 7 the device part as a whole up to the tree (GPU ms); 3 the host's per-proof glue, 4 the pairing checks (wall ms). */
 typedef enum pm_verify_verdict {
     PM_VERIFY_REJECTED = 0,
     PM_VERIFY_ACCEPTED = 1,
@@ -337,6 +337,32 @@ typedef enum pm_verify_verdict {
 int pm_verify_batch(pm_ctx *ctx, int curve, int transcript, const uint8_t *vk_bytes, size_t vk_len, const uint64_t *public_inputs, size_t n_inputs,
                     const uint8_t *proofs, size_t proof_len, size_t count, const uint8_t *seed32, uint8_t *verdicts, int *all_accepted,
                     size_t *n_checks);
+
+/* The same call with the place of the pairing checks chosen.  (An argument, not a pm_option: the option table is part of the ABI that
+ * existing hosts compile against.)  pm_verify_batch is pm_verify_batch2 with PM_VERIFY_PAIRING_HOST, bit for bit.
+ *   PM_VERIFY_PAIRING_DEVICE: the root is checked by pm_pairing_check_batch's kernel in a launch of ONE lane (the same sums, -g_S G
+ *     included: the lane forms it): a valid batch still costs one check.  After a failing root, with verdicts != NULL, ONE launch checks
+ *     every live leaf of the sum tree -- U_i - g_i G against [z]_2, -V_i against [x]_2, W_i against [1]_2, the lane forming g_i G, -V_i
+ *     and the affine points -- and a leaf's check is exact (above), so there is no bisection:
+ *         *n_checks = 1 + the number of proofs that are not PM_VERIFY_MALFORMED;   with verdicts == NULL:  *n_checks <= 1
+ *     (host mode: *n_checks <= 1 + 2 f ceil(log2 count)).  Malformed proofs keep PM_VERIFY_MALFORMED and are not checked.
+ * Verdicts, *all_accepted, the weights, the meaning of seed32 and every PM_ERR_INVALID_ARG case are the same in both modes; another
+ * `pairing` value is PM_ERR_INVALID_ARG.  pm_last_timings: slot 4 is the pairing checks' wall ms wherever they ran (device mode: line
+ * tables, launches and copies), slot 5 the GPU ms of the pairing launches (device mode only). */
+typedef enum pm_verify_pairing { PM_VERIFY_PAIRING_HOST = 0, PM_VERIFY_PAIRING_DEVICE = 1 } pm_verify_pairing;
+int pm_verify_batch2(pm_ctx *ctx, int curve, int transcript, const uint8_t *vk_bytes, size_t vk_len, const uint64_t *public_inputs, size_t n_inputs,
+                     const uint8_t *proofs, size_t proof_len, size_t count, const uint8_t *seed32, int pairing, uint8_t *verdicts,
+                     int *all_accepted, size_t *n_checks);
+
+/* count independent checks  prod_{j<k} e(P[i][j], Q[j]) == 1  against k <= 4 FIXED G2 points, one lane of ONE launch per check.
+ * g2: k affine points, x.c0 || x.c1 || y.c0 || y.c1, Montgomery, 4 * fq_limbs u64 each (on the twist, else PM_ERR_INVALID_ARG;
+ *     the subgroup is the caller's business, as with msm_unchecked).  g1: count * k points, the G1 affine-in convention
+ *     (stride, infinity byte / all-zero), check after check; a pair whose G1 point is infinity contributes 1.  is_one: count bytes, 0 / 1.
+ * The pairing is the optimal ate pairing of both engines, with the final exponentiation's hard part by an x-chain (on BLS12-381 it
+ * yields the cube of the usual value: 3 does not divide r, so "== 1" is unchanged).  count == 0 returns PM_OK; count <= 2^22.
+ * Device and host memory are taken per call and returned.  pm_last_timings slot 7: the GPU ms of the launch. */
+int pm_pairing_check_batch(pm_ctx *ctx, int curve, const uint64_t *g2, size_t k, const void *g1, size_t g1_stride,
+                           size_t count, uint8_t *is_one);
 
 /* Host helper: Keccak-f[1600] on 25 little-endian lanes, shared by the host mirrors' Merlin / Keccak256
  * transcripts (the reference's transcripts are host code too: src/transcript/ *.rs). */

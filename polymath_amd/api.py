@@ -29,8 +29,11 @@ G1_BYTES = {PM_BLS12_381: 48, PM_BN254: 32}                # compressed record o
 PROOF_BYTES = {PM_BLS12_381: 176, PM_BN254: 128}            # Proof::serialize_compressed
 # pm_verify_verdict (include/polymath_hip.h): one per proof of pm_verify_batch
 VERIFY_REJECTED, VERIFY_ACCEPTED, VERIFY_MALFORMED = range(3)
-# what pm_last_timings' slots hold after pm_verify_batch (ms: GPU time of the kernels, wall time of the two host parts)
-VERIFY_TIMING_SLOTS = {"decode": 0, "terms": 1, "tree": 2, "host_glue": 3, "host_pairing": 4, "device_total": 7}
+# what pm_last_timings' slots hold after pm_verify_batch (ms: GPU time of the kernels, wall time of the two host parts).  host_pairing is
+# the pairing checks' wall time wherever they ran; pairing_kernels the GPU time of the device mode's launches (0 in host mode)
+VERIFY_TIMING_SLOTS = {"decode": 0, "terms": 1, "tree": 2, "host_glue": 3, "host_pairing": 4, "pairing_kernels": 5, "device_total": 7}
+# pm_verify_pairing (include/polymath_hip.h): where pm_verify_batch2 runs its pairing checks
+VERIFY_PAIRING = {"host": 0, "device": 1}
 TIMING_SLOTS = ["witness_map", "ntt", "poly", "msm_sort", "msm_accumulate", "msm_reduce", "msm_total", "phase"]
 
 u64p = ct.POINTER(ct.c_uint64)
@@ -67,6 +70,7 @@ EXPORTS = [
     "pm_comm_world", "pm_comm_last_error", "pm_comm_kind", "pm_comm_set_timeout_ms", "pm_comm_abort", "pm_comm_failed", "pm_comm_busy_ms", "pm_host_make_vk", "pm_host_verify", "pm_comm_all_gather", "pm_comm_all_to_all", "pm_comm_all_gather_device", "pm_comm_combine_points", "pm_ctx_set_comm",
     "pm_ctx_set_option", "pm_ctx_get_option", "pm_comm_local_set_serialize",
     "pm_g1_decode", "pm_pk_load_bytes", "pm_pk_export_bases_compressed", "pm_verify_batch",
+    "pm_verify_batch2", "pm_pairing_check_batch",
 ]
 # pm_option / pm_tables_mode (include/polymath_hip.h)
 OPTIONS = {"msm_overlap": 0, "ntt_overlap": 1, "tables": 2, "msm_max_piece_log": 3, "max_seg_log": 4, "inflight_contexts": 5,
@@ -166,6 +170,8 @@ def load_library():
     L.pm_pk_load_bytes.argtypes = [vp, i, vp, sz, i, i, i, i, ct.POINTER(vp)]
     L.pm_pk_export_bases_compressed.argtypes = [vp, vp, i, sz, sz, vp]
     L.pm_verify_batch.argtypes = [vp, i, i, ct.c_char_p, sz, u64p, sz, vp, sz, sz, ct.c_char_p, vp, intp, ct.POINTER(sz)]
+    L.pm_verify_batch2.argtypes = [vp, i, i, ct.c_char_p, sz, u64p, sz, vp, sz, sz, ct.c_char_p, i, vp, intp, ct.POINTER(sz)]
+    L.pm_pairing_check_batch.argtypes = [vp, i, u64p, sz, vp, sz, sz, vp]
     _lib = L
     return L
 
@@ -260,9 +266,24 @@ def g1_decode(ctx, curve, data, validate=True):
     return xy, status
 
 
-def verify_batch(ctx, curve, transcript, vk_bytes, public_inputs, proofs, seed=None, verdicts=True):
-    """pm_verify_batch: many proofs against one verifying key; the per-proof curve work on the GPU, a handful of pairing checks on
-    the host.  public_inputs: Montgomery limbs [count, n_inputs, 4], WITHOUT the leading one; proofs: a list of
+def pairing_check_batch(ctx, curve, g2, g1):
+    """pm_pairing_check_batch: count checks prod_j e(g1[i][j], g2[j]) == 1 on the GPU, one lane each.  g2: Montgomery limbs
+    [k, 4 fq_limbs] (x.c0 || x.c1 || y.c0 || y.c1), k <= 4; g1: [count, k, 2 fq_limbs] (x || y; all-zero = infinity).
+    -> np.uint8[count] of 0 / 1."""
+    cid = CURVE_IDS[curve]
+    g2 = _c(g2).reshape(-1, 4 * FQ_LIMBS64[cid])
+    k = g2.shape[0]
+    g1 = _c(g1).reshape(-1, k, 2 * FQ_LIMBS64[cid]) if np.size(g1) else np.zeros((0, k, 2 * FQ_LIMBS64[cid]), dtype=np.uint64)
+    out = np.zeros(g1.shape[0], dtype=np.uint8)
+    ctx.check(ctx.L.pm_pairing_check_batch(ctx.h, cid, _p(g2), k, g1.ctypes.data_as(ct.c_void_p), 16 * FQ_LIMBS64[cid], g1.shape[0],
+                                           out.ctypes.data_as(ct.c_void_p)))
+    return out
+
+
+def verify_batch(ctx, curve, transcript, vk_bytes, public_inputs, proofs, seed=None, verdicts=True, pairing="host"):
+    """pm_verify_batch2: many proofs against one verifying key; the per-proof curve work on the GPU, the pairing checks on the host
+    (pairing="host": a handful per valid batch, a bisection otherwise; what pm_verify_batch does) or on the GPU (pairing="device":
+    the root in a launch of one lane, every live leaf in one more launch if it fails).  public_inputs: Montgomery limbs [count, n_inputs, 4], WITHOUT the leading one; proofs: a list of
     Proof::serialize_compressed byte strings or one packed buffer; seed: None or 32 bytes mixed into the weights' key.
     -> (np.uint8[count] of VERIFY_* codes, or None with verdicts=False; all_accepted: bool; n_checks: int)."""
     cid = CURVE_IDS[curve]
@@ -281,9 +302,9 @@ def verify_batch(ctx, curve, transcript, vk_bytes, public_inputs, proofs, seed=N
         raise ValueError("seed: 32 bytes")
     out = np.zeros(count, dtype=np.uint8) if verdicts else None
     acc, checks = ct.c_int(0), ct.c_size_t(0)
-    ctx.check(ctx.L.pm_verify_batch(ctx.h, cid, TRANSCRIPT_IDS[transcript], bytes(vk_bytes), len(vk_bytes), _p(pub) if pub.size else None, n_inputs,
-                                    ct.c_void_p(addr), plen, count, bytes(seed) if seed is not None else None,
-                                    out.ctypes.data_as(ct.c_void_p) if verdicts else None, ct.byref(acc), ct.byref(checks)))
+    ctx.check(ctx.L.pm_verify_batch2(ctx.h, cid, TRANSCRIPT_IDS[transcript], bytes(vk_bytes), len(vk_bytes), _p(pub) if pub.size else None, n_inputs,
+                                     ct.c_void_p(addr), plen, count, bytes(seed) if seed is not None else None, VERIFY_PAIRING[pairing],
+                                     out.ctypes.data_as(ct.c_void_p) if verdicts else None, ct.byref(acc), ct.byref(checks)))
     del keep
     return out, bool(acc.value), int(checks.value)
 

@@ -404,6 +404,26 @@ int g1_decode_device(pm_ctx *ctx, const uint8_t *d_in, size_t count, bool valida
 template <class C>
 int g1_encode_device(pm_ctx *ctx, const Affine<C> *d_pts, size_t count, uint8_t *d_out);
 const char *g1_status_text(int curve, int status);
+
+// pairing_batch.hip: checks  prod_j e(P[i][j], Q_j) == 1  against k <= 4 fixed G2 points, one lane per check.  pairing_prepare walks the
+// Miller loop of each Q_j on the host (g2: k x 4 Fq, x.c0 || x.c1 || y.c0 || y.c1; bit j of `pairs` clear: Q_j = O, the pair is left out
+// and its words are not read; a point off the twist is PM_ERR_INVALID_ARG) and uploads the line tables; the caller releases buf.
+// pairing_check_launch enqueues ONE launch of `count` lanes on the context's stream: lane i takes its k points from d_pts[i k ..], or,
+// with d_terms (k == 3), from node i of the batch verifier's sum tree as U_i + neg_g_i G, -V_i, W_i (d_neg_g: 8 canonical words a
+// lane; d_live: optional, a zero byte leaves the lane out).  d_is_one: one byte 0 / 1 per lane.  GPU ms go to timing_slot.
+struct PairingPrepared {
+    DevBuf buf;
+    size_t consts_offset = 0;
+    int k = 0;
+    unsigned pairs = 0;
+};
+template <class C>
+struct VerifyTerm;
+template <class C>
+int pairing_prepare(pm_ctx *ctx, const uint32_t *g2, int k, unsigned pairs, PairingPrepared *out);
+template <class C>
+int pairing_check_launch(pm_ctx *ctx, const PairingPrepared &prep, const Affine<C> *d_pts, const VerifyTerm<C> *d_terms, const uint32_t *d_neg_g,
+                         const uint8_t *d_live, const Affine<C> &G, size_t count, uint8_t *d_is_one, int timing_slot);
 // ProvingKey::serialize_compressed parsed on the host without touching its base points (pk_wire_parse)
 struct WireLayout {
     size_t vk_len = 0;

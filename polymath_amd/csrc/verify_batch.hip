@@ -1,12 +1,14 @@
 // pm_verify_batch: many Polymath proofs against one verifying key, one verdict each (include/polymath_hip.h; DESIGN.md "Batch
 // verification").  A single verification is O(1) and stays host code (pm_host_verify); a batch is dominated by per-proof G1 work --
-// three decompressions with a subgroup check and four scalar multiplications -- which runs here on the device, while the pairings,
-// a handful per batch, stay on the host (host/pairing.hpp).
+// three decompressions with a subgroup check and four scalar multiplications -- which runs here on the device.  The pairing checks,
+// a handful per valid batch, run on the host (host/pairing.hpp; pm_verify_batch, PM_VERIFY_PAIRING_HOST) or on the device
+// (pairing_batch.hip; pm_verify_batch2 with PM_VERIFY_PAIRING_DEVICE: the root in a launch of one lane, then every live leaf in ONE launch).
 //
 //   host   : repack the 3 point records of every proof, upload                       |  device: k_g1_decode (validate = 1)
 //   host   : per proof x1, x2, c(x1) as Polymath::verify computes them (threads)      |
 //   host   : weights rho_i from the batch's hash; scalars rho, rho x2, rho x1; g_i    |  device: k_verify_terms, k_verify_tree per level
 //   host   : root check (3 Miller loops, one final exponentiation); on failure bisect over the device's sum tree
+//   device mode instead: line tables of [z]_2, [x]_2, [1]_2 (host, once) | k_pairing_check on the root; on failure on all leaves
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -47,8 +49,12 @@ void glue_threads(size_t count, F body) {
 }
 
 struct DevBufs {   // the call's device memory: released on every way out
-    DevBuf in, pts, status, scalars, tree;
-    ~DevBufs() { in.release(); pts.release(); status.release(); scalars.release(); tree.release(); }
+    DevBuf in, pts, status, scalars, tree, neg_g, live, is_one;
+    PairingPrepared prep;
+    ~DevBufs() {
+        in.release(); pts.release(); status.release(); scalars.release(); tree.release();
+        neg_g.release(); live.release(); is_one.release(); prep.buf.release();
+    }
 };
 
 double ms_since(std::chrono::steady_clock::time_point t0) {
@@ -57,7 +63,7 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 
 template <class C, class T>
 int verify_batch_impl(pm_ctx *ctx, int transcript, const uint8_t *vk_bytes, size_t vk_len, const uint64_t *inputs, size_t n_inputs, const uint8_t *proofs,
-                      size_t count, const uint8_t *seed32, uint8_t *verdicts, int *all_accepted, size_t *n_checks) {
+                      size_t count, const uint8_t *seed32, int pairing, uint8_t *verdicts, int *all_accepted, size_t *n_checks) {
     typedef pmhost::FrOps<C> F;
     typedef typename F::Fr Fr;
     typedef typename C::FrP R;
@@ -213,6 +219,55 @@ int verify_batch_impl(pm_ctx *ctx, int transcript, const uint8_t *vk_bytes, size
     std::vector<uint8_t> verdict(count);
     for (size_t i = 0; i < count; ++i) verdict[i] = bad[i] ? PM_VERIFY_MALFORMED : PM_VERIFY_ACCEPTED;
     const bool any_bad = live_pre[count] != count;
+    if (pairing == PM_VERIFY_PAIRING_DEVICE) {
+        // The same equation, one lane per node: the root alone, then -- a leaf's check being the reference's own equation raised to
+        // a non-zero weight, hence exact -- every live leaf at once.  The lanes form -g G, -V and the affine points themselves.
+        const auto t0 = std::chrono::steady_clock::now();
+        bool root_ok = true;
+        if (live_pre[count]) {
+            constexpr int N = C::FqP::N;
+            const typename Pairing::G2 *q[3] = {&vk.z_g2, &vk.x_g2, &vk.one_g2};
+            uint32_t g2[3][4 * N] = {};
+            unsigned pairs = 0;
+            for (int j = 0; j < 3; ++j) {
+                if (q[j]->inf) continue;
+                pairs |= 1u << j;
+                memcpy(&g2[j][0], q[j]->x.c0.l, 4 * N); memcpy(&g2[j][N], q[j]->x.c1.l, 4 * N);
+                memcpy(&g2[j][2 * N], q[j]->y.c0.l, 4 * N); memcpy(&g2[j][3 * N], q[j]->y.c1.l, 4 * N);
+            }
+            PM_TRY(pairing_prepare<C>(ctx, &g2[0][0], 3, pairs, &d.prep));
+            const Affine<C> G = vk.one_g1.inf ? Affine<C>::infinity() : vk.one_g1.p;
+            std::vector<Fr> neg_g(count + 1);                    // canonical; the root's behind the leaves'
+            std::vector<uint8_t> live(count), is_one(count + 1, 0);
+            for (size_t i = 0; i < count; ++i) { neg_g[i] = from_mont<R>(F::neg(g[i])); live[i] = bad[i] ? 0 : 1; }
+            neg_g[count] = from_mont<R>(F::neg(g_pre[count]));
+            PM_HIP(ctx, d.neg_g.reserve((count + 1) * sizeof(Fr)));
+            PM_HIP(ctx, d.live.reserve(count));
+            PM_HIP(ctx, d.is_one.reserve(count + 1));
+            PM_HIP(ctx, hipMemcpyAsync(d.neg_g.p, neg_g.data(), (count + 1) * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+            PM_HIP(ctx, hipMemcpyAsync(d.live.p, live.data(), count, hipMemcpyHostToDevice, ctx->stream));
+            PM_TRY(pairing_check_launch<C>(ctx, d.prep, nullptr, tree + verify_level_offset(padded, depth), d.neg_g.as<uint32_t>() + 8 * count, nullptr, G, 1,
+                                           d.is_one.as<uint8_t>() + count, T_MSM_REDUCE));
+            PM_HIP(ctx, hipMemcpyAsync(&is_one[count], d.is_one.as<uint8_t>() + count, 1, hipMemcpyDeviceToHost, ctx->stream));
+            PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            checks = 1;
+            root_ok = is_one[count] != 0;
+            if (!root_ok && verdicts) {
+                PM_TRY(pairing_check_launch<C>(ctx, d.prep, nullptr, tree, d.neg_g.as<uint32_t>(), d.live.as<uint8_t>(), G, count, d.is_one.as<uint8_t>(),
+                                               T_MSM_REDUCE));
+                PM_HIP(ctx, hipMemcpyAsync(is_one.data(), d.is_one.p, count, hipMemcpyDeviceToHost, ctx->stream));
+                PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                for (size_t i = 0; i < count; ++i)
+                    if (!bad[i] && !is_one[i]) verdict[i] = PM_VERIFY_REJECTED;
+                checks += live_pre[count];
+            }
+        }
+        ctx->timing_ms[T_MSM_ACCUMULATE] = ms_since(t0);
+        if (verdicts) memcpy(verdicts, verdict.data(), count);
+        *all_accepted = root_ok && !any_bad ? 1 : 0;
+        if (n_checks) *n_checks = checks;
+        return PM_OK;
+    }
     const bool root_ok = live_pre[count] == 0 || check(depth, 0);
     if (!root_ok && verdicts && hip_status == PM_OK) {
         // A failing node has a failing child.  The Miller product of a node is the product of its children's, so when the left child
@@ -241,20 +296,21 @@ int verify_batch_impl(pm_ctx *ctx, int transcript, const uint8_t *vk_bytes, size
 
 template <class C>
 int verify_batch_curve(pm_ctx *ctx, int transcript, const uint8_t *vk, size_t vk_len, const uint64_t *in, size_t n_in, const uint8_t *proofs, size_t count,
-                       const uint8_t *seed, uint8_t *verdicts, int *all, size_t *nc) {
+                       const uint8_t *seed, int pairing, uint8_t *verdicts, int *all, size_t *nc) {
     switch (transcript) {
-        case PM_TRANSCRIPT_MERLIN: return verify_batch_impl<C, pmhost::MerlinFieldTranscript<C>>(ctx, transcript, vk, vk_len, in, n_in, proofs, count, seed, verdicts, all, nc);
-        case PM_TRANSCRIPT_KECCAK256: return verify_batch_impl<C, pmhost::Keccak256Transcript<C>>(ctx, transcript, vk, vk_len, in, n_in, proofs, count, seed, verdicts, all, nc);
-        case PM_TRANSCRIPT_BLAKE3: return verify_batch_impl<C, pmhost::Blake3Transcript<C>>(ctx, transcript, vk, vk_len, in, n_in, proofs, count, seed, verdicts, all, nc);
+        case PM_TRANSCRIPT_MERLIN: return verify_batch_impl<C, pmhost::MerlinFieldTranscript<C>>(ctx, transcript, vk, vk_len, in, n_in, proofs, count, seed, pairing, verdicts, all, nc);
+        case PM_TRANSCRIPT_KECCAK256: return verify_batch_impl<C, pmhost::Keccak256Transcript<C>>(ctx, transcript, vk, vk_len, in, n_in, proofs, count, seed, pairing, verdicts, all, nc);
+        case PM_TRANSCRIPT_BLAKE3: return verify_batch_impl<C, pmhost::Blake3Transcript<C>>(ctx, transcript, vk, vk_len, in, n_in, proofs, count, seed, pairing, verdicts, all, nc);
         default: return PM_ERR_INVALID_ARG;
     }
 }
 
 }  // namespace
 
-extern "C" int pm_verify_batch(pm_ctx *ctx, int curve, int transcript, const uint8_t *vk_bytes, size_t vk_len, const uint64_t *public_inputs, size_t n_inputs,
-                               const uint8_t *proofs, size_t proof_len, size_t count, const uint8_t *seed32, uint8_t *verdicts, int *all_accepted,
-                               size_t *n_checks) {
+extern "C" int pm_verify_batch2(pm_ctx *ctx, int curve, int transcript, const uint8_t *vk_bytes, size_t vk_len, const uint64_t *public_inputs, size_t n_inputs,
+                                const uint8_t *proofs, size_t proof_len, size_t count, const uint8_t *seed32, int pairing, uint8_t *verdicts,
+                                int *all_accepted, size_t *n_checks) {
+    if (pairing != PM_VERIFY_PAIRING_HOST && pairing != PM_VERIFY_PAIRING_DEVICE) return PM_ERR_INVALID_ARG;
     if (!ctx || !vk_bytes || !all_accepted || (count && (!proofs || (n_inputs && !public_inputs)))) return PM_ERR_INVALID_ARG;
     if (curve != PM_BLS12_381 && curve != PM_BN254) return PM_ERR_INVALID_ARG;
     if (transcript < PM_TRANSCRIPT_MERLIN || transcript > PM_TRANSCRIPT_BLAKE3) return PM_ERR_INVALID_ARG;
@@ -272,8 +328,8 @@ extern "C" int pm_verify_batch(pm_ctx *ctx, int curve, int transcript, const uin
         }
         if (hipSetDevice(ctx->device) != hipSuccess) return PM_ERR_HIP;
         return curve == PM_BLS12_381
-                   ? verify_batch_curve<BlsCurve>(ctx, transcript, vk_bytes, vk_len, public_inputs, n_inputs, proofs, count, seed32, verdicts, all_accepted, n_checks)
-                   : verify_batch_curve<BnCurve>(ctx, transcript, vk_bytes, vk_len, public_inputs, n_inputs, proofs, count, seed32, verdicts, all_accepted, n_checks);
+                   ? verify_batch_curve<BlsCurve>(ctx, transcript, vk_bytes, vk_len, public_inputs, n_inputs, proofs, count, seed32, pairing, verdicts, all_accepted, n_checks)
+                   : verify_batch_curve<BnCurve>(ctx, transcript, vk_bytes, vk_len, public_inputs, n_inputs, proofs, count, seed32, pairing, verdicts, all_accepted, n_checks);
     } catch (const pmhost::WireError &) {               // malformed vk bytes
         return PM_ERR_INVALID_ARG;
     } catch (const std::bad_alloc &) {
@@ -283,4 +339,11 @@ extern "C" int pm_verify_batch(pm_ctx *ctx, int curve, int transcript, const uin
         ctx->err = e.what();
         return PM_ERR_INVALID_ARG;
     }
+}
+
+extern "C" int pm_verify_batch(pm_ctx *ctx, int curve, int transcript, const uint8_t *vk_bytes, size_t vk_len, const uint64_t *public_inputs, size_t n_inputs,
+                               const uint8_t *proofs, size_t proof_len, size_t count, const uint8_t *seed32, uint8_t *verdicts, int *all_accepted,
+                               size_t *n_checks) {
+    return pm_verify_batch2(ctx, curve, transcript, vk_bytes, vk_len, public_inputs, n_inputs, proofs, proof_len, count, seed32, PM_VERIFY_PAIRING_HOST,
+                            verdicts, all_accepted, n_checks);
 }

@@ -76,6 +76,10 @@ pub const PM_VERIFY_REJECTED: u8 = 0;
 pub const PM_VERIFY_ACCEPTED: u8 = 1;
 pub const PM_VERIFY_MALFORMED: u8 = 2;
 
+// pm_verify_pairing: where pm_verify_batch2 runs its pairing checks
+pub const PM_VERIFY_PAIRING_HOST: i32 = 0;
+pub const PM_VERIFY_PAIRING_DEVICE: i32 = 1;
+
 // pm_transcript
 pub const PM_TRANSCRIPT_MERLIN: i32 = 0;
 pub const PM_TRANSCRIPT_KECCAK256: i32 = 1;
@@ -172,6 +176,8 @@ extern "C" {
     pub fn pm_host_make_vk(curve: i32, n: u64, m0: u64, sigma: u64, omega: *const u64, x_trapdoor: *const u64, z_trapdoor: *const u64, vk_bytes: *mut u8, capacity: usize, vk_len: *mut usize) -> i32;
     pub fn pm_host_verify(curve: i32, transcript: i32, vk_bytes: *const u8, vk_len: usize, public_inputs: *const u64, n_inputs: usize, proof_bytes: *const u8, proof_len: usize, accepted: *mut i32) -> i32;
     pub fn pm_verify_batch(ctx: *mut pm_ctx, curve: i32, transcript: i32, vk_bytes: *const u8, vk_len: usize, public_inputs: *const u64, n_inputs: usize, proofs: *const u8, proof_len: usize, count: usize, seed32: *const u8, verdicts: *mut u8, all_accepted: *mut i32, n_checks: *mut usize) -> i32;
+    pub fn pm_verify_batch2(ctx: *mut pm_ctx, curve: i32, transcript: i32, vk_bytes: *const u8, vk_len: usize, public_inputs: *const u64, n_inputs: usize, proofs: *const u8, proof_len: usize, count: usize, seed32: *const u8, pairing: i32, verdicts: *mut u8, all_accepted: *mut i32, n_checks: *mut usize) -> i32;
+    pub fn pm_pairing_check_batch(ctx: *mut pm_ctx, curve: i32, g2: *const u64, k: usize, g1: *const c_void, g1_stride: usize, count: usize, is_one: *mut u8) -> i32;
     pub fn pm_host_keccak_f1600(state: *mut u64);
     // ---- multi-GPU exchange layer (no reference counterpart: the reference is single-process CPU code)
     pub fn pm_comm_rccl_unique_id(out_128_bytes: *mut c_void) -> i32;

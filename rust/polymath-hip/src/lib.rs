@@ -355,6 +355,50 @@ impl Context {
         Ok((raw.into_iter().map(Verdict::from_raw).collect(), checks))
     }
 
+    /// [`Context::verify_batch`] with the pairing checks on the GPU (`pm_verify_batch2`, `PM_VERIFY_PAIRING_DEVICE`): the root in a launch
+    /// of one lane and, if it fails, every well-formed proof's own check in ONE more launch -- no bisection.  Same verdicts; the
+    /// number of checks is then 1 + the number of proofs that are not [`Verdict::Malformed`].
+    pub fn verify_batch_device_pairing(&mut self, curve: Curve, transcript: i32, vk_bytes: &[u8], public_inputs: &[u64], n_inputs: usize,
+                                       proofs: &[u8], seed: Option<&[u8; 32]>) -> Result<(Vec<Verdict>, usize), HipError> {
+        let proof_len = match curve {
+            Curve::Bls12_381 => 176,
+            Curve::Bn254 => 128,
+        };
+        if proofs.len() % proof_len != 0 || public_inputs.len() != proofs.len() / proof_len * n_inputs * sys::PM_FR_LIMBS {
+            return Err(err(Status::InvalidArg, "verify_batch: proofs / public_inputs do not have the batch's shape"));
+        }
+        let count = proofs.len() / proof_len;
+        let mut raw = vec![0u8; count];
+        let (mut all, mut checks) = (0i32, 0usize);
+        // SAFETY: live context; every pointer covers the length passed with it, `raw` holds `count` bytes, the seed is 32 bytes or null.
+        let rc = unsafe {
+            sys::pm_verify_batch2(self.raw, curve.id(), transcript, vk_bytes.as_ptr(), vk_bytes.len(), public_inputs.as_ptr(), n_inputs, proofs.as_ptr(),
+                                  proof_len, count, seed.map_or(core::ptr::null(), |s| s.as_ptr()), sys::PM_VERIFY_PAIRING_DEVICE, raw.as_mut_ptr(),
+                                  &mut all, &mut checks)
+        };
+        self.check(rc)?;
+        Ok((raw.into_iter().map(Verdict::from_raw).collect(), checks))
+    }
+
+    /// `pm_pairing_check_batch`: `g1.len() / (k * 2 * fq_limbs)` checks `prod_j e(g1[i][j], g2[j]) == 1` against `k <= 4` fixed G2
+    /// points, one GPU lane each.  `g2`: `k` x (`x.c0 || x.c1 || y.c0 || y.c1`), `g1`: checks x `k` x (`x || y`), Montgomery limbs;
+    /// an all-zero G1 point is the point at infinity and contributes 1.
+    pub fn pairing_check_batch(&mut self, curve: Curve, g2: &[u64], g1: &[u64]) -> Result<Vec<bool>, HipError> {
+        let fq = curve.fq_limbs();
+        let k = g2.len() / (4 * fq);
+        if k == 0 || g2.len() != k * 4 * fq || g1.len() % (k * 2 * fq) != 0 {
+            return Err(err(Status::InvalidArg, "pairing_check_batch: g2 / g1 do not have the checks' shape"));
+        }
+        let count = g1.len() / (k * 2 * fq);
+        let mut raw = vec![0u8; count];
+        // SAFETY: live context; `g2` holds k points, `g1` count * k points 16 * fq bytes apart, `raw` count bytes.
+        let rc = unsafe {
+            sys::pm_pairing_check_batch(self.raw, curve.id(), g2.as_ptr(), k, g1.as_ptr() as *const c_void, 16 * fq, count, raw.as_mut_ptr())
+        };
+        self.check(rc)?;
+        Ok(raw.into_iter().map(|b| b != 0).collect())
+    }
+
     /// Run `f` on this thread's context (created on first use on `device`).
     pub fn with_thread_local<T>(device: i32, f: impl FnOnce(&mut Context) -> Result<T, HipError>) -> Result<T, HipError> {
         use std::cell::RefCell;

@@ -1,11 +1,11 @@
 """Batch verification against single verification (DESIGN.md "Batch verification"; profiles/verify_batch.txt).
 
-    python tools/verify_bench.py --count 1024 [--bad 8] [--curve bls12_381] [--distinct 64]
+    python tools/verify_bench.py --count 1024 [--bad 8] [--curve bls12_381] [--distinct 64] [--pairing host|device]
 
 Makes proofs of circuits.MiMCDemo (16 rounds) on one key -- `--distinct` of them with their own witness and r_a, tiled up to
 `--count` -- and times (a) verify_batch, (b) the same with verdicts=False, (c) pm_host_verify on 4 of the proofs (mean) and,
-with --bad F, (d) the batch with F proofs tampered (a_at_x1 + 1, spread evenly): the bisection.  Prints ONE JSON line; the
-kernel times are pm_last_timings' (HIP events inside the call)."""
+with --bad F, (d) the batch with F proofs tampered (a_at_x1 + 1, spread evenly): the bisection (--pairing host) or the one launch
+over all leaves (--pairing device).  Prints ONE JSON line; the kernel times are pm_last_timings' (HIP events inside the call)."""
 import argparse
 import json
 import os
@@ -23,6 +23,7 @@ def main():
     ap.add_argument("--bad", type=int, default=0)
     ap.add_argument("--curve", default="bls12_381")
     ap.add_argument("--distinct", type=int, default=64)
+    ap.add_argument("--pairing", choices=("host", "device"), default="host")
     a = ap.parse_args()
     from polymath_amd import api, circuits as PC, rng as R
     from polymath_amd.polymath import Polymath
@@ -43,13 +44,13 @@ def main():
 
     def timed(proofs, **kw):
         t0 = time.perf_counter()
-        v, ok, checks = api.verify_batch(pm.ctx, a.curve, "merlin", vk, pub, b"".join(proofs), **kw)
+        v, ok, checks = api.verify_batch(pm.ctx, a.curve, "merlin", vk, pub, b"".join(proofs), pairing=a.pairing, **kw)
         wall = (time.perf_counter() - t0) * 1e3
         return dict(wall_ms=round(wall, 3), all_accepted=ok, n_checks=checks, rejected=int((v == 0).sum()) if v is not None else None,
                     **{k + "_ms": round(x, 3) for k, x in api.verify_batch_timings(pm.ctx).items()})
 
     timed(proofs[:2])                                  # first launch: code objects
-    out = dict(curve=a.curve, count=a.count, distinct=len(made), gates=pk.n)
+    out = dict(curve=a.curve, pairing=a.pairing, count=a.count, distinct=len(made), gates=pk.n)
     out["batch"] = timed(proofs)
     out["batch_no_verdicts"] = timed(proofs, verdicts=False)
     t0 = time.perf_counter()
