@@ -164,6 +164,13 @@ size_t pm_bases_len(const pm_bases *b);
 void pm_bases_free(pm_bases *b);
 int pm_msm_g1_resident(pm_ctx *ctx, const pm_bases *bases, size_t base_offset, const uint64_t *scalars,
                        int scalars_on_device, size_t len, uint64_t *out_xy, int *out_inf);
+/* `batch` MSMs of `len` pairs each against the SAME base range [base_offset, base_offset + len) in one call: row b is
+ * scalars[b * len .. (b + 1) * len) (Montgomery Fr, 4 limbs each), its result out_xy[b] (2 fq limb vectors) and out_inf[b], in the
+ * form pm_msm_g1_resident gives.  Same argument checks and status codes; batch == 0 writes nothing, len == 0 gives every row the
+ * identity, batch == 1 is pm_msm_g1_resident itself.  Runs the per-window pipeline over the plain resident points: window tables
+ * (pm_bases_precompute) and wide plans are not used by batches; the results are the same on a precomputed pm_bases. */
+int pm_msm_g1_resident_batch(pm_ctx *ctx, const pm_bases *bases, size_t base_offset, const uint64_t *scalars,
+                             int scalars_on_device, size_t len, size_t batch, uint64_t *out_xy, int *out_inf);
 
 /* Host-side G1 helpers used to combine per-GPU partial MSM results (RCCL has no
  * elliptic-curve reduction op, so partial points are all-gathered and summed locally). */

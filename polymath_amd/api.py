@@ -62,7 +62,7 @@ class PolymathError(RuntimeError):
 EXPORTS = [
     "pm_device_count", "pm_ctx_create", "pm_ctx_destroy", "pm_last_error", "pm_last_timings", "pm_ntt",
     "pm_ntt_device", "pm_msm_g1", "pm_bases_upload", "pm_bases_generate_multiples", "pm_bases_download",
-    "pm_bases_precompute", "pm_bases_len", "pm_bases_free", "pm_msm_g1_resident", "pm_g1_sum", "pm_pk_load", "pm_pk_generate",
+    "pm_bases_precompute", "pm_bases_len", "pm_bases_free", "pm_msm_g1_resident", "pm_msm_g1_resident_batch", "pm_g1_sum", "pm_pk_load", "pm_pk_generate",
     "pm_pk_info", "pm_pk_msm_plan", "pm_pk_export_bases", "pm_pk_free", "pm_prove_phase1", "pm_prove_phase1_device", "pm_prove_phase2", "pm_prove_phase3", "pm_host_prove", "pm_host_prove_sharded",
     "pm_prove_tap", "pm_host_keccak_f1600", "pm_synth_r1cs", "pm_selftest_field",
     "pm_pk_load_sharded", "pm_pk_generate_sharded", "pm_layout_indices", "pm_pk_msm_pieces",
@@ -111,6 +111,7 @@ def load_library():
     L.pm_bases_free.argtypes = [vp]
     L.pm_bases_free.restype = None
     L.pm_msm_g1_resident.argtypes = [vp, vp, sz, vp, i, sz, u64p, intp]
+    L.pm_msm_g1_resident_batch.argtypes = [vp, vp, sz, vp, i, sz, sz, u64p, intp]
     L.pm_g1_sum.argtypes = [i, u64p, intp, sz, u64p, intp]
     L.pm_pk_load.argtypes = [vp, i, u64, u64, u64, u64, u64, ct.POINTER(PmCsr), ct.POINTER(PmCsr), ct.POINTER(PmCsr),
                              ct.POINTER(PmBaseArray), i, i, ct.POINTER(vp)]
@@ -550,6 +551,23 @@ class Bases:
                                                _p(out), ct.byref(inf))
         self.ctx.check(st)
         return out, inf.value
+
+    def msm_batch(self, scalars, offset=0, length=None, device_ptr=None, batch=None):
+        """pm_msm_g1_resident_batch: `batch` MSMs of `length` pairs against bases [offset, offset + length).  scalars: host np.uint64
+        [batch, len, 4], or device_ptr (int) + length + batch for rows already in HBM, row after row.
+        -> (np.uint64 [batch, 2 nq], np.int32 [batch])."""
+        if device_ptr is not None:
+            ptr, on_device = ct.c_void_p(device_ptr), 1
+        else:
+            scalars = _c(scalars)
+            batch = scalars.shape[0] if batch is None else batch
+            length = (scalars.shape[1] if scalars.ndim == 3 else 0) if length is None else length
+            ptr, on_device = scalars.ctypes.data_as(ct.c_void_p), 0
+        out = np.zeros((batch, 2 * FQ_LIMBS64[self.cid]), dtype=np.uint64)
+        inf = np.zeros(batch, dtype=np.int32)
+        self.ctx.check(self.ctx.L.pm_msm_g1_resident_batch(self.ctx.h, self.h, offset, ptr, on_device, length, batch, _p(out),
+                                                           inf.ctypes.data_as(intp)))
+        return out, inf
 
     def free(self):
         if self.h:

@@ -165,7 +165,7 @@ extern "C" void pm_ctx_destroy(pm_ctx *ctx) {
     MsmWorkspace &m = ctx->msm;
     for (DevBuf *b : {&m.set.sorted, &m.set.counts, &m.set.bucket_off, &m.set.task_off, &m.set.tasks, &m.set.partials, &m.set.task_cnt}) b->release();
     for (DevBuf *b : {&m.digits, &m.cursor, &m.wsum,
-                      &m.region, &m.sub, &m.digits2, &m.len_bins, &m.block_cnt, &m.hot, &ctx->scratch, &ctx->flags, &ctx->xw, &ctx->ue, &ctx->we, &ctx->u, &ctx->w,
+                      &m.region, &m.sub, &m.digits2, &m.len_bins, &m.block_cnt, &m.hot, &m.batch, &ctx->scratch, &ctx->flags, &ctx->xw, &ctx->ue, &ctx->we, &ctx->u, &ctx->w,
                       &ctx->wit_u, &ctx->u2, &ctx->sc_a, &ctx->sc_c, &ctx->quotient, &ctx->ztail, &ctx->ra, &ctx->sh_a, &ctx->sh_b, &ctx->sh_c, &ctx->halo,
                       &ctx->shard_roots, &ctx->ntt_tmp})
         b->release();
@@ -373,6 +373,42 @@ extern "C" int pm_msm_g1_resident(pm_ctx *ctx, const pm_bases *bases, size_t bas
     return PM_DISPATCH(bases->curve,
                        msm_resident_impl<BlsCurve>(ctx, bases, base_offset, scalars, scalars_on_device, len, out_xy, out_inf),
                        msm_resident_impl<BnCurve>(ctx, bases, base_offset, scalars, scalars_on_device, len, out_xy, out_inf));
+}
+
+template <class C>
+static int msm_resident_batch_impl(pm_ctx *ctx, const pm_bases *bases, size_t off, const uint64_t *scalars, int on_device, size_t len,
+                                   size_t batch, uint64_t *out_xy, int *out_inf) {
+    typedef Fp<typename C::FrP> Fr;
+    const Fr *d_sc = (const Fr *)scalars;
+    if (!on_device && len) {
+        PM_HIP(ctx, ctx->scratch.reserve(batch * len * sizeof(Fr)));
+        PM_HIP(ctx, hipMemcpyAsync(ctx->scratch.p, scalars, batch * len * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+        d_sc = ctx->scratch.as<Fr>();
+    }
+    std::vector<Affine<C>> r(batch);
+    std::vector<int> inf(batch, 1);
+    timing_reset(ctx);
+    // the plain resident points, with or without window tables beside them (pm_bases_precompute keeps d_points)
+    PM_TRY(msm_run_batch<C>(ctx, (const Affine<C> *)bases->d_points + off, d_sc, len, batch, r.data(), inf.data()));
+    timing_flush(ctx);
+    for (size_t b = 0; b < batch; ++b) {
+        if (inf[b]) memset((uint8_t *)out_xy + b * sizeof(Affine<C>), 0, sizeof(Affine<C>));
+        else memcpy((uint8_t *)out_xy + b * sizeof(Affine<C>), &r[b], sizeof(Affine<C>));
+        out_inf[b] = inf[b];
+    }
+    return PM_OK;
+}
+
+extern "C" int pm_msm_g1_resident_batch(pm_ctx *ctx, const pm_bases *bases, size_t base_offset, const uint64_t *scalars,
+                                        int scalars_on_device, size_t len, size_t batch, uint64_t *out_xy, int *out_inf) {
+    if (batch == 1) return pm_msm_g1_resident(ctx, bases, base_offset, scalars, scalars_on_device, len, out_xy, out_inf);
+    if (!ctx || !bases || (batch && (!out_xy || !out_inf || (len && !scalars)))) return PM_ERR_INVALID_ARG;
+    if (base_offset + len > bases->len) return PM_ERR_LEN_MISMATCH;
+    if (batch == 0) return PM_OK;
+    PM_TRY(set_device(ctx));
+    return PM_DISPATCH(bases->curve,
+                       msm_resident_batch_impl<BlsCurve>(ctx, bases, base_offset, scalars, scalars_on_device, len, batch, out_xy, out_inf),
+                       msm_resident_batch_impl<BnCurve>(ctx, bases, base_offset, scalars, scalars_on_device, len, batch, out_xy, out_inf));
 }
 
 extern "C" int pm_msm_g1(pm_ctx *ctx, int curve, const void *bases, size_t base_stride, const uint64_t *scalars,

@@ -89,6 +89,7 @@ struct MsmSet {
 struct MsmWorkspace {
     MsmSet set;
     DevBuf digits, cursor, wsum, region, sub, digits2, len_bins, block_cnt, hot;
+    DevBuf batch;   // msm_run_batch: the base range's infinity flags, then one (point, flag) record per row of a group
 };
 
 // Window tables of a resident base vector (setup.hip: tables_build): point (w, i) = 2^(c w) P_i lives at
@@ -322,6 +323,12 @@ int twiddles_get(pm_ctx *ctx, unsigned log_n, bool inv_dir, const Fp<typename C:
 template <class C>
 int msm_run(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_scalars, size_t len,
             Affine<C> *h_out, int *h_inf, const MsmTables *tables = nullptr);
+
+// `batch` MSMs of `len` pairs against the same bases: row b = d_scalars[b * len ..), results in h_out[b], h_inf[b].  Per-window pipeline
+// over the plain base array only (no tables, no wide plan); see msm.hip.
+template <class C>
+int msm_run_batch(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_scalars, size_t len, size_t batch,
+                  Affine<C> *h_out, int *h_inf);
 
 // the same in two halves (msm.hip): enqueue on ctx->stream without waiting / wait and convert
 template <class C>

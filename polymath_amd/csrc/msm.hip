@@ -7,6 +7,8 @@
 // Two pipelines share the task / accumulate / reduce kernels: (A) below, per-window Pippenger
 // over a plain base array (one-shot pm_msm_g1, keys whose tables do not fit); (B) "Table mode" further down,
 // the path every resident key takes.
+// A batch of scalar rows against one base range (pm_msm_g1_resident_batch) is pipeline (A) over rows x windows bucket sets with its
+// own digits kernel and a device-side final combine: msm_run_batch, at the end of this file.
 // Pipeline (A), all on one HIP stream, no host round trip until the final point:
 //   k_digits      scalar (Montgomery) -> canonical -> W signed c-bit digits, one u32 per
 //                 (window, scalar): (bucket << 1 | negate), NONE for zero digits / infinity bases.
@@ -567,6 +569,28 @@ __device__ __forceinline__ bool digit_at(const Fp<P> &k, unsigned lo, unsigned c
     neg = carry;
     bucket = m - 1;
     return m != 0;
+}
+
+// k_digits over a batch of scalar rows against ONE base range (msm_run_batch): lane i recodes scalar i of row blockIdx.y into set
+// s = row * nwin + w, whose digits are digits[s * len ..): stores coalesced along i.  inf[i] = 1 for a base at infinity
+// (setup.hip: infinity_flags, once per call, not once per row).
+template <class C>
+__global__ __launch_bounds__(256) void k_digits_batch(const Fp<typename C::FrP> *scalars, const unsigned char *inf, uint32_t *digits, size_t len,
+                                                      unsigned c, unsigned nwin) {
+    typedef typename C::FrP P;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    const size_t row = blockIdx.y;
+    const Fp<P> k = from_mont<P>(scalars[row * len + i]);
+    const bool skip = inf[i] != 0;
+    uint32_t carry = 0;
+    uint32_t *d = digits + row * nwin * len + i;
+#pragma unroll 1
+    for (unsigned w = 0; w < nwin; ++w) {
+        uint32_t bucket, neg;
+        const bool some = digit_at<P>(k, w * c, c, carry, bucket, neg);
+        d[(size_t)w * len] = some && !skip ? (bucket << 1) | neg : DIGIT_NONE;
+    }
 }
 
 // Region populations PER WORKGROUP: block_cnt[workgroup][region], with the same workgroup -> scalar mapping
@@ -1218,29 +1242,63 @@ static void host_finish(const XYZZ<C> &acc, Affine<C> *out, int *inf) {
     *out = xyzz_to_affine<C>(acc);
 }
 
+// The same combine on the device, one lane per row of a batch (msm_run_batch): sums[row * nwin + w] = S_w of that row, internal form;
+// out[row] = sum_w 2^(c w) S_w as a standard-Montgomery affine point (all-zero for the identity) and its infinity flag.  The chain is
+// host_horner's: c doublings, then one addition per window, on the reduced-radix registers of the bucket reduction.  The window sums of
+// structured inputs (bases G, 2G, 3G ..., equal or opposite rows) coincide, cancel or are O: every addition is xyzz28_add_full, which
+// hands P = +-Q to the complete dense formulas; xyzz28_dbl is complete (no point of order 2); O is ZZ == 0 in every limb throughout.
+template <class C>
+struct BatchPoint {
+    Affine<C> p;
+    uint32_t inf;
+};
+
+template <class C>
+__global__ __launch_bounds__(64) void k_window_combine(const XYZZ<C> *sums, unsigned nwin, unsigned c, unsigned rows, BatchPoint<C> *out) {
+    typedef typename C::FqRR RR;
+    const unsigned row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= rows) return;
+    const XYZZ<C> *s = sums + (size_t)row * nwin;
+    XYZZ28<C> acc;
+    acc.X = acc.Y = acc.ZZ = acc.ZZZ = f28_zero<RR>();
+#pragma unroll 1
+    for (int w = (int)nwin - 1; w >= 0; --w) {
+#pragma unroll 1
+        for (unsigned k = 0; k < c; ++k) xyzz28_dbl<C>(acc);
+        xyzz28_add_full<C>(acc, xyzz28_load<C>(s[w]));
+    }
+    const XYZZ<C> r = xyzz28_to_std<C>(acc);
+    out[row].inf = r.is_identity() ? 1u : 0u;
+    out[row].p = xyzz_to_affine<C>(r);          // one inversion; the identity comes out as x = y = 0
+}
+
 // ------------------------------------------------------------------------------- the sorts
+// histogram, bucket scan and scatter of the plan's n_wide_sets digit arrays of p.len entries each (set s: digits[s * len ..))
+static int sort_sets(pm_ctx *ctx, MsmSet &S, const BucketPlan &p, const uint32_t *digits, uint32_t *counts, uint32_t *cursor, unsigned nbuckets) {
+    const size_t lds = (size_t)nbuckets * 4;
+    if (lds > 48 * 1024) {  // CDNA4: up to 160 KiB of LDS per workgroup, opt in above the default cap
+        PM_HIP(ctx, hipFuncSetAttribute((const void *)k_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        PM_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    hipLaunchKernelGGL(k_hist, dim3(p.nchunks, p.n_wide_sets), dim3(1024), lds, ctx->stream, digits, counts, p.len, p.chunk, nbuckets);
+    PM_HIP(ctx, hipGetLastError());
+    PM_TRY(bucket_scan(ctx, S, p));
+    hipLaunchKernelGGL(k_scatter, dim3(p.nchunks, p.n_wide_sets), dim3(1024), lds, ctx->stream, digits, S.bucket_off.as<uint32_t>(), cursor,
+                       S.sorted.as<uint32_t>(), p.len, p.chunk, nbuckets);
+    PM_HIP(ctx, hipGetLastError());
+    return PM_OK;
+}
+
 // Pipeline (A): digits, LDS histogram per (chunk, window), bucket scan, LDS-staged scatter.
 template <class C>
 static int sort_windows(pm_ctx *ctx, MsmSet &S, const BucketPlan &p, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_scalars) {
     MsmWorkspace &ws = ctx->msm;
     PM_HIP(ctx, ws.digits.reserve(p.E * 4));
     uint32_t *counts = S.counts.as<uint32_t>(), *cursor = counts + p.NB, *digits = ws.digits.as<uint32_t>();
-    const unsigned nbuckets = (unsigned)p.NB1;
     PM_HIP(ctx, hipMemsetAsync(counts, 0, 2 * p.NB * 4, ctx->stream));
     hipLaunchKernelGGL(k_digits<C>, dim3((unsigned)((p.len + 255) / 256)), dim3(256), 0, ctx->stream, d_scalars, d_bases, digits, p.len, p.c, p.nwin);
     PM_HIP(ctx, hipGetLastError());
-    const size_t lds = (size_t)nbuckets * 4;
-    if (lds > 48 * 1024) {  // CDNA4: up to 160 KiB of LDS per workgroup, opt in above the default cap
-        PM_HIP(ctx, hipFuncSetAttribute((const void *)k_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        PM_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
-    hipLaunchKernelGGL(k_hist, dim3(p.nchunks, p.nwin), dim3(1024), lds, ctx->stream, digits, counts, p.len, p.chunk, nbuckets);
-    PM_HIP(ctx, hipGetLastError());
-    PM_TRY(bucket_scan(ctx, S, p));
-    hipLaunchKernelGGL(k_scatter, dim3(p.nchunks, p.nwin), dim3(1024), lds, ctx->stream, digits, S.bucket_off.as<uint32_t>(), cursor,
-                       S.sorted.as<uint32_t>(), p.len, p.chunk, nbuckets);
-    PM_HIP(ctx, hipGetLastError());
-    return PM_OK;
+    return sort_sets(ctx, S, p, digits, counts, cursor, (unsigned)p.NB1);
 }
 
 // What the levels of the table-mode sort share: (u16 key, u32 value) entries in ws.digits, the regions' counters in ws.region.
@@ -1417,6 +1475,88 @@ int msm_run(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_
     return PM_OK;
 }
 
+// `batch` MSMs of `len` pairs each against ONE base range: row b = d_scalars[b * len ..) times d_bases[0 .. len).  The per-window
+// pipeline handles nwin independent bucket sets, every stage indexed by set, and sorted[] holds plain base indices: a group of `rows`
+// rows is the same pipeline over rows * nwin sets -- set s = b * nwin + w owns digits [s * len, (s + 1) * len) -- planned once for
+// `len` and scaled.  New are the digits over (row, i) (k_digits_batch) and the final combine on the device (k_window_combine): one
+// copy of rows x (point, flag) ends a group; the host neither doubles nor inverts.
+// A group is as many whole rows as keep rows * len <= msm_max_piece(), rows * nwin <= 65 535 (grid y of k_hist / k_scatter) and
+// E, NB < 2^32 (u32 positions); further groups reuse the workspace in stream order.  A row longer than one piece runs row by row
+// through msm_run.  Window tables and wide plans are NOT used here: the points are the plain resident array (pm_bases keeps it
+// beside its tables), so a precomputed pm_bases gives the same points, at the per-window pipeline's 16+ additions per pair.
+// NOT yet measured against a loop of msm_run (tools/msm_bench.py --batch does it): DESIGN.md §4.2 "Batched MSM", profiles/msm_batch.txt.
+template <class C>
+int msm_run_batch(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_scalars, size_t len, size_t batch, Affine<C> *h_out,
+                  int *h_inf) {
+    if (len == 0) {
+        for (size_t b = 0; b < batch; ++b) { h_out[b] = Affine<C>::infinity(); h_inf[b] = 1; }
+        return PM_OK;
+    }
+    const size_t max_piece = msm_max_piece(ctx);
+    if (len > max_piece) {
+        for (size_t b = 0; b < batch; ++b) PM_TRY(msm_run<C>(ctx, d_bases, d_scalars + b * len, len, h_out + b, h_inf + b));
+        return PM_OK;
+    }
+    BucketPlan row;
+    PM_TRY(bucket_plan(nullptr, len, (unsigned)C::FrP::BITS, ctx->opt.v[PM_OPT_MSM_TASK_LEN], row));
+    const size_t u32_max = 0xFFFFFFFFull;
+    size_t group = max_piece / len;
+    if (group > 65535 / row.nwin) group = 65535 / row.nwin;
+    if (group > u32_max / row.E) group = u32_max / row.E;
+    if (group > u32_max / row.NB) group = u32_max / row.NB;
+    if (group > batch) group = batch;
+    if (group < 1) return PM_ERR_INVALID_ARG;
+
+    MsmWorkspace &ws = ctx->msm;
+    const size_t flag_bytes = (len + 15) & ~(size_t)15;
+    PM_HIP(ctx, ws.batch.reserve(flag_bytes + group * sizeof(BatchPoint<C>)));
+    unsigned char *d_inf = ws.batch.as<unsigned char>();
+    BatchPoint<C> *d_res = (BatchPoint<C> *)(d_inf + flag_bytes);
+    PM_TRY(infinity_flags<C>(ctx, d_bases, len, d_inf));
+    std::vector<BatchPoint<C>> res(group);
+    for (size_t b0 = 0; b0 < batch; b0 += group) {
+        StageTimer t_total(ctx, T_MSM_TOTAL);
+        const size_t rows = batch - b0 < group ? batch - b0 : group;
+        BucketPlan p = row;
+        p.n_wide_sets = (unsigned)(rows * row.nwin);
+        p.nsums = p.n_wide_sets;
+        p.NB = rows * row.NB;
+        p.E = rows * row.E;
+        p.max_tasks = p.NB + p.E / p.seg + 1;
+        MsmSet &S = ws.set;
+        PM_TRY(reserve_set<C>(ctx, S, p));
+        {
+            StageTimer t(ctx, T_MSM_SORT);
+            PM_HIP(ctx, ws.digits.reserve(p.E * 4));
+            uint32_t *counts = S.counts.as<uint32_t>(), *cursor = counts + p.NB, *digits = ws.digits.as<uint32_t>();
+            const unsigned nbuckets = (unsigned)p.NB1;
+            PM_HIP(ctx, hipMemsetAsync(counts, 0, 2 * p.NB * 4, ctx->stream));
+            hipLaunchKernelGGL(k_digits_batch<C>, dim3((unsigned)((len + 255) / 256), (unsigned)rows), dim3(256), 0, ctx->stream,
+                               d_scalars + b0 * len, d_inf, digits, len, p.c, p.nwin);
+            PM_HIP(ctx, hipGetLastError());
+            PM_TRY(sort_sets(ctx, S, p, digits, counts, cursor, nbuckets));
+            PM_TRY(task_order(ctx, S, p));
+        }
+        {
+            StageTimer t(ctx, T_MSM_ACCUMULATE);
+            PM_TRY((accumulate<C, false>(ctx, S, p, (const void *)d_bases)));
+        }
+        {
+            StageTimer t(ctx, T_MSM_REDUCE);
+            PM_TRY(fold_hot_buckets<C>(ctx, S, p));
+            XYZZ<C> *d_sums = nullptr;
+            PM_TRY(reduce_single_level<C>(ctx, S, p, &d_sums));
+            hipLaunchKernelGGL(k_window_combine<C>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, ctx->stream, d_sums, p.nwin, p.c,
+                               (unsigned)rows, d_res);
+            PM_HIP(ctx, hipGetLastError());
+        }
+        PM_HIP(ctx, hipMemcpyAsync(res.data(), d_res, rows * sizeof(BatchPoint<C>), hipMemcpyDeviceToHost, ctx->stream));
+        PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (size_t r = 0; r < rows; ++r) { h_out[b0 + r] = res[r].p; h_inf[b0 + r] = (int)res[r].inf; }
+    }
+    return PM_OK;
+}
+
 // Asynchronous pair for a single-piece table-mode MSM: msm_begin enqueues the whole pipeline on ctx->stream and returns at once
 // (the reduced point travels to the context's pinned slot), msm_end waits for the stream and finishes it.  Two contexts (ctx and
 // its helper ctx->aux: own streams, own workspaces) can so run two MSMs concurrently from ONE host thread -- the latency-bound
@@ -1462,5 +1602,7 @@ template int msm_end<BlsCurve>(pm_ctx *, Affine<BlsCurve> *, int *);
 template int msm_end<BnCurve>(pm_ctx *, Affine<BnCurve> *, int *);
 template int msm_run<BlsCurve>(pm_ctx *, const Affine<BlsCurve> *, const Fp<BlsFrP> *, size_t, Affine<BlsCurve> *, int *, const MsmTables *);
 template int msm_run<BnCurve>(pm_ctx *, const Affine<BnCurve> *, const Fp<BnFrP> *, size_t, Affine<BnCurve> *, int *, const MsmTables *);
+template int msm_run_batch<BlsCurve>(pm_ctx *, const Affine<BlsCurve> *, const Fp<BlsFrP> *, size_t, size_t, Affine<BlsCurve> *, int *);
+template int msm_run_batch<BnCurve>(pm_ctx *, const Affine<BnCurve> *, const Fp<BnFrP> *, size_t, size_t, Affine<BnCurve> *, int *);
 
 }  // namespace pm

@@ -150,6 +150,7 @@ extern "C" {
     pub fn pm_bases_len(b: *const pm_bases) -> usize;
     pub fn pm_bases_free(b: *mut pm_bases);
     pub fn pm_msm_g1_resident(ctx: *mut pm_ctx, bases: *const pm_bases, base_offset: usize, scalars: *const u64, scalars_on_device: i32, len: usize, out_xy: *mut u64, out_inf: *mut i32) -> i32;
+    pub fn pm_msm_g1_resident_batch(ctx: *mut pm_ctx, bases: *const pm_bases, base_offset: usize, scalars: *const u64, scalars_on_device: i32, len: usize, batch: usize, out_xy: *mut u64, out_inf: *mut i32) -> i32;
     pub fn pm_g1_sum(curve: i32, points_xy: *const u64, infs: *const i32, count: usize, out_xy: *mut u64, out_inf: *mut i32) -> i32;
     // ---- proving key (data_structures.rs:56-73; generator.rs:24-167)
     pub fn pm_pk_load(ctx: *mut pm_ctx, curve: i32, n: u64, m0: u64, mw: u64, nr: u64, sigma: u64, a: *const pm_csr, b: *const pm_csr, c: *const pm_csr, bases: *const pm_base_array, shard_rank: i32, shard_count: i32, out: *mut *mut pm_pk) -> i32;

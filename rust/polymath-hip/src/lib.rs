@@ -921,6 +921,70 @@ impl Context {
     }
 }
 
+// ------------------------------------------------------------------------------------------ resident bases
+/// One `pm_bases`: a G1 base vector resident in HBM (an SRS that many polynomials are committed against).
+pub struct ResidentBases {
+    raw: *mut sys::pm_bases,
+    curve: Curve,
+    len: usize,
+}
+
+// SAFETY: the device allocation is immutable after upload; calls take the context by `&mut`.
+unsafe impl Send for ResidentBases {}
+
+impl ResidentBases {
+    pub fn upload<E: Pairing>(ctx: &mut Context, bases: &[E::G1Affine]) -> Result<ResidentBases, HipError> {
+        let curve = curve_checked::<E>()?;
+        let mut raw = core::ptr::null_mut();
+        // SAFETY: `bases.len()` points of size_of::<G1Affine>() bytes each (layout checked).
+        let rc = unsafe { sys::pm_bases_upload(ctx.raw, curve.id(), bases.as_ptr() as *const c_void, core::mem::size_of::<E::G1Affine>(), bases.len(), &mut raw) };
+        ctx.check(rc)?;
+        Ok(ResidentBases { raw, curve, len: bases.len() })
+    }
+
+    pub fn len(&self) -> usize {
+        self.len
+    }
+
+    pub fn is_empty(&self) -> bool {
+        self.len == 0
+    }
+
+    /// `pm_msm_g1_resident_batch`: one MSM per row of `rows` (all of one length `len <= self.len() - offset`) against bases
+    /// `[offset, offset + len)`, in one call.  Rows are copied into one contiguous host buffer first.
+    pub fn msm_batch<E: Pairing>(&self, ctx: &mut Context, offset: usize, rows: &[&[E::ScalarField]]) -> Result<Vec<E::G1Affine>, HipError> {
+        let curve = curve_checked::<E>()?;
+        if curve != self.curve {
+            return Err(err(Status::InvalidArg, "bases were uploaded for another curve"));
+        }
+        let len = rows.first().map_or(0, |r| r.len());
+        if rows.iter().any(|r| r.len() != len) {
+            return Err(err(Status::InvalidArg, "rows of a batch must have one length"));
+        }
+        let flat: Vec<E::ScalarField> = rows.iter().flat_map(|r| r.iter().copied()).collect();
+        let mut xy = vec![0u64; rows.len() * 12];
+        let mut inf = vec![0i32; rows.len()];
+        let nq = 2 * curve.fq_limbs();
+        // SAFETY: rows.len() * len scalars in (layout checked); rows.len() points of nq <= 12 words and as many flags out.
+        let rc = unsafe { sys::pm_msm_g1_resident_batch(ctx.raw, self.raw, offset, fr_ptr(&flat), 0, len, rows.len(), xy.as_mut_ptr(), inf.as_mut_ptr()) };
+        ctx.check(rc)?;
+        Ok((0..rows.len())
+            .map(|b| {
+                let mut p = [0u64; 12];
+                p[..nq].copy_from_slice(&xy[b * nq..(b + 1) * nq]);
+                g1_from_raw::<E>(curve, &p, inf[b])
+            })
+            .collect())
+    }
+}
+
+impl Drop for ResidentBases {
+    fn drop(&mut self) {
+        // SAFETY: created by pm_bases_upload, freed once.
+        unsafe { sys::pm_bases_free(self.raw) }
+    }
+}
+
 /// The device this process proves on: `POLYMATH_HIP_DEVICE`, else `LOCAL_RANK` (one process per GPU), else 0.
 pub fn default_device() -> i32 {
     for var in ["POLYMATH_HIP_DEVICE", "LOCAL_RANK"] {
