@@ -289,6 +289,29 @@ int pm_host_prove(pm_ctx *ctx, const pm_pk *pk, int transcript, const uint64_t *
                   const uint64_t *w, int assignment_on_device, const uint64_t *r_a, uint8_t *proof_bytes, size_t capacity,
                   size_t *proof_len);
 
+/* `count` runs of create_proof_with_assignment (prover.rs:66-237) against ONE unsharded key, transcript included.
+ *   instance_host : count x m0 Fr, host, Montgomery, leading one included (hashed), proof after proof
+ *   x, w          : count x m0 / count x mw Fr, host pointers or (assignment_on_device != 0) device pointers, row after row
+ *   r_a           : count x 2 Fr, host
+ *   proofs        : count x proof_len bytes (176 BLS12-381 / 128 BN254), Proof::serialize_compressed of proof i at i * proof_len
+ *   status        : count ints, pm_status of proof i
+ * The proofs run in GROUPS: every vector of the prover is a [group][len] array on the device, every kernel has the proof as a grid
+ * dimension, and the three MSMs of a proof are three batched MSMs per group over the key's plain points (the key's window tables are
+ * neither used nor needed).  A group is as many proofs as keep group * (10 n + 22) inside one MSM piece and the group's vectors inside
+ * half of the free device memory; the workspace is owned by the context, reused by later calls and KEPT at the size of the largest group
+ * seen until pm_ctx_destroy -- after one large batch, device memory that a later pm_pk_generate or key load on the same device could
+ * use for window tables stays with this context (use a context of its own for large batches and destroy it to hand the memory
+ * back).  A key whose single proof exceeds an MSM piece runs
+ * as a loop of pm_host_prove.  For every i with status[i] == PM_OK, proof i is bit for bit what pm_host_prove returns for row i.
+ * PM_OK: the batch ran, the per-proof outcomes are in status[] -- a row with an unsatisfied assignment gets the status pm_host_prove
+ * returns for it (PM_ERR_REMAINDER_NONZERO / PM_ERR_DEGREE_BOUND) and zeroed bytes, and does not disturb its neighbours.
+ * PM_ERR_INVALID_ARG, nothing computed: a sharded key, a key on another device, an unknown transcript, a wrong proof_len, a NULL
+ * pointer where one is required.  count == 0 is PM_OK; count == 1 is pm_host_prove.  The context stays usable as before (a proof in
+ * flight between pm_prove_phase1 and phase 3 is not disturbed); pm_last_timings reports every slot summed over the batch. */
+int pm_host_prove_batch(pm_ctx *ctx, const pm_pk *pk, int transcript, size_t count, const uint64_t *instance_host,
+                        const uint64_t *x, const uint64_t *w, int assignment_on_device, const uint64_t *r_a,
+                        uint8_t *proofs, size_t proof_len, int *status);
+
 /* The same on a SHARDED key (one rank of a multi-GPU proof): `combine` is called between the phases with this
  * rank's partial points -- count = 2 ([a]_1, [c]_1) after phase 1, count = 1 ([d]_1) after phase 3 -- and must
  * replace them, in place, by the sums over all ranks (all-gather over RCCL + pm_g1_sum: SURVEY.md §8e; RCCL has

@@ -63,7 +63,7 @@ EXPORTS = [
     "pm_device_count", "pm_ctx_create", "pm_ctx_destroy", "pm_last_error", "pm_last_timings", "pm_ntt",
     "pm_ntt_device", "pm_msm_g1", "pm_bases_upload", "pm_bases_generate_multiples", "pm_bases_download",
     "pm_bases_precompute", "pm_bases_len", "pm_bases_free", "pm_msm_g1_resident", "pm_msm_g1_resident_batch", "pm_g1_sum", "pm_pk_load", "pm_pk_generate",
-    "pm_pk_info", "pm_pk_msm_plan", "pm_pk_export_bases", "pm_pk_free", "pm_prove_phase1", "pm_prove_phase1_device", "pm_prove_phase2", "pm_prove_phase3", "pm_host_prove", "pm_host_prove_sharded",
+    "pm_pk_info", "pm_pk_msm_plan", "pm_pk_export_bases", "pm_pk_free", "pm_prove_phase1", "pm_prove_phase1_device", "pm_prove_phase2", "pm_prove_phase3", "pm_host_prove", "pm_host_prove_batch", "pm_host_prove_sharded",
     "pm_prove_tap", "pm_host_keccak_f1600", "pm_synth_r1cs", "pm_selftest_field",
     "pm_pk_load_sharded", "pm_pk_generate_sharded", "pm_layout_indices", "pm_pk_msm_pieces",
     "pm_comm_rccl_unique_id", "pm_comm_rccl_create", "pm_comm_local_create", "pm_comm_from_callbacks", "pm_comm_destroy", "pm_comm_rank",
@@ -119,6 +119,7 @@ def load_library():
                                  u64p, i, i, ct.POINTER(vp)]
     L.pm_pk_info.argtypes = [vp, u64p, u64p, u64p, u64p, u64p]
     L.pm_host_prove.argtypes = [vp, vp, ct.c_int, u64p, ct.c_void_p, ct.c_void_p, ct.c_int, u64p, ct.c_char_p, ct.c_size_t, ct.POINTER(ct.c_size_t)]
+    L.pm_host_prove_batch.argtypes = [vp, vp, ct.c_int, sz, u64p, ct.c_void_p, ct.c_void_p, ct.c_int, u64p, ct.c_char_p, sz, intp]
     L.pm_host_prove_sharded.argtypes = [vp, vp, ct.c_int, u64p, ct.c_void_p, ct.c_void_p, ct.c_int, u64p, COMBINE_FN, ct.c_void_p, ct.c_char_p,
                                         ct.c_size_t, ct.POINTER(ct.c_size_t)]
     L.pm_pk_msm_plan.argtypes = [vp, ct.c_int, u64p, ct.POINTER(ct.c_uint), ct.POINTER(ct.c_uint), intp]
@@ -736,6 +737,26 @@ class ProvingKey:
         if failure:
             raise failure[0]
         return rc, buf.raw[:n.value]
+
+    def host_prove_batch(self, transcript, instance_limbs, x, w, r_a, on_device=False):
+        """pm_host_prove_batch: `count` proofs against this (unsharded) key in one native call.  instance_limbs: (count, m0, 4) host
+        limbs (hashed); x, w: (count, m0, 4) / (count, mw, 4) host limbs, or device pointers (ints) to the same rows with
+        on_device=True; r_a: (count, 2, 4).  -> (status of the call, bytes of count * proof_len, np.int32[count] per-proof statuses)."""
+        inst = _c(instance_limbs)
+        count = int(inst.shape[0]) if inst.ndim == 3 else 0
+        proof_len = 3 * 8 * self.nq + 32
+        buf = ct.create_string_buffer(max(1, count * proof_len))
+        status = np.zeros(max(1, count), dtype=np.int32)
+        r_a = _c(r_a)
+        if on_device:
+            px, pw = ct.c_void_p(x), ct.c_void_p(w)
+        else:
+            x = _c(x)
+            w = _c(w) if np.size(w) else np.zeros((max(1, count), 1, 4), dtype=np.uint64)
+            px, pw = x.ctypes.data_as(ct.c_void_p), w.ctypes.data_as(ct.c_void_p)
+        rc = self.ctx.L.pm_host_prove_batch(self.ctx.h, self.h, self.TRANSCRIPT_IDS[transcript], count, _p(inst), px, pw, int(on_device), _p(r_a),
+                                            buf, proof_len, status.ctypes.data_as(ct.POINTER(ct.c_int)))
+        return rc, buf.raw[:count * proof_len], status[:count]
 
     def phase2(self, x1):
         out = np.zeros(4, dtype=np.uint64)

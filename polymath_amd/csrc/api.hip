@@ -170,6 +170,7 @@ extern "C" void pm_ctx_destroy(pm_ctx *ctx) {
                       &ctx->shard_roots, &ctx->ntt_tmp})
         b->release();
     for (auto &b : ctx->lvl) b.release();
+    ctx->pb.release();
     for (auto &b : ctx->fb_table) b.release();
     for (auto &t : ctx->tw) { t.fwd.release(); t.inv.release(); t.fwd_int.release(); t.inv_int.release(); }
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);

@@ -95,6 +95,141 @@ extern "C" int pm_host_prove(pm_ctx *ctx, const pm_pk *pk, int transcript, const
                                  proof_len);
 }
 
+// ---- pm_host_prove_batch: `count` proofs against one unsharded key, in groups whose vectors are [rows][len] arrays (prove_batch.hip) ----
+namespace {
+
+template <class C, class T>
+int host_prove_batch_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *instance_host, const uint64_t *x, const uint64_t *w,
+                          int on_device, const uint64_t *r_a, uint8_t *proofs, size_t proof_len, int *status) {
+    typedef pmhost::Polymath<C, T> PMH;
+    typedef typename PMH::Fr Fr;
+    typedef typename PMH::Glue Glue;
+    const size_t m0 = pk->m0, mw = pk->mw;
+    size_t group = 0;
+    PM_TRY(pm::prove_batch_group<C>(ctx, pk, count, &group));
+    if (group == 0) {
+        // one proof's [d]_1 row exceeds an MSM piece (or not even one proof fits the memory share): the per-proof path, which splits
+        // its MSMs into pieces; the stage times are summed over the proofs
+        double sum[pm::T_NUM_SLOTS] = {0};
+        for (size_t i = 0; i < count; ++i) {
+            size_t len = 0;
+            uint8_t *out = proofs + i * proof_len;
+            status[i] = host_prove_impl<C, T>(ctx, pk, instance_host + 4 * m0 * i, x + 4 * m0 * i, w ? w + 4 * mw * i : nullptr, on_device,
+                                              r_a + 8 * i, nullptr, nullptr, out, proof_len, &len);
+            if (status[i] == PM_OK && len != proof_len) status[i] = PM_ERR_STATE;
+            if (status[i] != PM_OK) memset(out, 0, proof_len);
+            if (status[i] == PM_ERR_HIP) {      // a device error is the call's, not the row's: stop, the rows not reached carry it too
+                for (size_t j = i + 1; j < count; ++j) { status[j] = PM_ERR_HIP; memset(proofs + j * proof_len, 0, proof_len); }
+                return PM_ERR_HIP;
+            }
+            pm::timing_flush_now(ctx);
+            for (int s = 0; s < pm::T_NUM_SLOTS; ++s) sum[s] += ctx->timing_ms[s];
+        }
+        pm::timing_reset(ctx);
+        for (int s = 0; s < pm::T_NUM_SLOTS; ++s) ctx->timing_ms[s] = sum[s];
+        return PM_OK;
+    }
+    pmhost::ProvingKey<C> key;          // n / m0 / sigma / omega carrier of the host glue: no device handle
+    key.n = pk->n; key.m0 = pk->m0; key.sigma = pk->sigma;
+    memcpy(key.omega.l, pk->omega, 32);
+    pm::timing_reset(ctx);             // the phases below add to the slots and never reset them: the sums over the batch
+    int rc = PM_OK;
+    size_t done = 0;                   // proofs of finished groups
+    try {
+        std::vector<pm::Affine<C>> pa(group), pc(group), pd(group);
+        std::vector<int> ia(group), ic(group), id(group);
+        std::vector<unsigned> flags(group);
+        std::vector<Fr> x1(group), x2(group), a_at(group), c_at(group), u_at(group);
+        std::vector<std::vector<Fr>> inst(group, std::vector<Fr>(m0));
+        std::vector<pmhost::Proof<C>> proof(group);
+        for (size_t g0 = 0; g0 < count && rc == PM_OK; g0 += group) {
+            const size_t rows = count - g0 < group ? count - g0 : group;
+            const uint64_t *ra = r_a + 8 * g0;
+            int *stat = status + g0;
+            rc = pm::prove_batch_phase1<C>(ctx, pk, rows, x + 4 * m0 * g0, w ? w + 4 * mw * g0 : nullptr, on_device != 0, ra, pa.data(), ia.data(),
+                                           pc.data(), ic.data(), flags.data());
+            if (rc != PM_OK) break;
+            std::vector<Glue> glue(rows);
+            for (size_t b = 0; b < rows; ++b) {
+                const unsigned hf = flags[b];
+                stat[b] = (hf & 1u) ? PM_ERR_REMAINDER_NONZERO                      // prover.rs:108
+                          : ((hf & 2u) || !(hf & 4u)) ? PM_ERR_DEGREE_BOUND         // prover.rs:107
+                                                      : PM_OK;
+                x1[b] = x2[b] = a_at[b] = c_at[b] = Fr::zero();     // a refused proof rides along on zeros; its results are dropped
+                if (stat[b] != PM_OK) continue;
+                memcpy((void *)inst[b].data(), instance_host + 4 * m0 * (g0 + b), m0 * sizeof(Fr));
+                proof[b].a_g1.p = pa[b]; proof[b].a_g1.inf = ia[b] != 0;
+                proof[b].c_g1.p = pc[b]; proof[b].c_g1.inf = ic[b] != 0;
+                PMH::glue_x1(glue[b], key, inst[b], proof[b]);
+                x1[b] = glue[b].x1;
+            }
+            rc = pm::prove_batch_phase2<C>(ctx, pk, rows, (const uint64_t *)x1.data(), (uint64_t *)u_at.data());
+            if (rc != PM_OK) break;
+            for (size_t b = 0; b < rows; ++b) {
+                if (stat[b] != PM_OK) continue;
+                PMH::glue_x2(glue[b], key, inst[b], (const Fr *)(ra + 8 * b), u_at[b], proof[b]);
+                x2[b] = glue[b].x2; a_at[b] = proof[b].a_at_x1; c_at[b] = glue[b].c_at_x1;
+            }
+            rc = pm::prove_batch_phase3<C>(ctx, pk, rows, ra, (const uint64_t *)x1.data(), (const uint64_t *)x2.data(), (const uint64_t *)a_at.data(),
+                                           (const uint64_t *)c_at.data(), pd.data(), id.data(), flags.data());
+            if (rc != PM_OK) break;
+            for (size_t b = 0; b < rows; ++b) {
+                uint8_t *out = proofs + (g0 + b) * proof_len;
+                if (stat[b] == PM_OK && (flags[b] & 8u)) stat[b] = PM_ERR_REMAINDER_NONZERO;   // prover.rs:221
+                if (stat[b] == PM_OK) {
+                    proof[b].d_g1.p = pd[b]; proof[b].d_g1.inf = id[b] != 0;
+                    const pmhost::Bytes bytes = proof[b].to_bytes();
+                    if (bytes.size() == proof_len) memcpy(out, bytes.data(), proof_len);
+                    else stat[b] = PM_ERR_STATE;
+                }
+                if (stat[b] != PM_OK) memset(out, 0, proof_len);
+            }
+            done = g0 + rows;
+        }
+    } catch (const std::exception &e) {
+        ctx->err = e.what();
+        rc = PM_ERR_STATE;
+    }
+    // the call failed inside a group: that group's rows and the ones not reached carry the call's status and zeroed bytes
+    for (size_t i = done; rc != PM_OK && i < count; ++i) { status[i] = rc; memset(proofs + i * proof_len, 0, proof_len); }
+    return rc;
+}
+
+template <class C>
+int host_prove_batch_curve(pm_ctx *ctx, const pm_pk *pk, int transcript, size_t count, const uint64_t *ih, const uint64_t *x, const uint64_t *w,
+                           int dev, const uint64_t *r_a, uint8_t *proofs, size_t proof_len, int *status) {
+    switch (transcript) {
+        case PM_TRANSCRIPT_MERLIN: return host_prove_batch_impl<C, pmhost::MerlinFieldTranscript<C>>(ctx, pk, count, ih, x, w, dev, r_a, proofs, proof_len, status);
+        case PM_TRANSCRIPT_KECCAK256: return host_prove_batch_impl<C, pmhost::Keccak256Transcript<C>>(ctx, pk, count, ih, x, w, dev, r_a, proofs, proof_len, status);
+        case PM_TRANSCRIPT_BLAKE3: return host_prove_batch_impl<C, pmhost::Blake3Transcript<C>>(ctx, pk, count, ih, x, w, dev, r_a, proofs, proof_len, status);
+        default: return PM_ERR_INVALID_ARG;
+    }
+}
+
+}  // namespace
+
+extern "C" int pm_host_prove_batch(pm_ctx *ctx, const pm_pk *pk, int transcript, size_t count, const uint64_t *instance_host, const uint64_t *x,
+                                   const uint64_t *w, int assignment_on_device, const uint64_t *r_a, uint8_t *proofs, size_t proof_len,
+                                   int *status) {
+    if (!ctx || !pk) return PM_ERR_INVALID_ARG;
+    if (transcript != PM_TRANSCRIPT_MERLIN && transcript != PM_TRANSCRIPT_KECCAK256 && transcript != PM_TRANSCRIPT_BLAKE3) return PM_ERR_INVALID_ARG;
+    if (pk->shard_count != 1 || pk->layout != PM_SHARD_PAIRS || pk->device != ctx->device) return PM_ERR_INVALID_ARG;
+    const size_t fq_bytes = pk->curve == PM_BLS12_381 ? sizeof(pm::Fp<pm::BlsFqP>) : sizeof(pm::Fp<pm::BnFqP>);
+    if (proof_len != 3 * fq_bytes + 32) return PM_ERR_INVALID_ARG;     // Proof::serialize_compressed: three G1 points and one Fr
+    if (count == 0) return PM_OK;
+    if (!instance_host || !x || !r_a || !proofs || !status || (pk->mw && !w)) return PM_ERR_INVALID_ARG;
+    if (count == 1) {   // one proof: forwarded to the per-proof chain (permitted by the contract; the two routes have not been measured at B = 1)
+        size_t len = 0;
+        status[0] = pm_host_prove(ctx, pk, transcript, instance_host, x, w, assignment_on_device, r_a, proofs, proof_len, &len);
+        if (status[0] != PM_OK) memset(proofs, 0, proof_len);
+        return status[0] == PM_ERR_HIP ? (int)PM_ERR_HIP : (int)PM_OK;
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return PM_ERR_HIP;
+    return pk->curve == PM_BLS12_381
+               ? host_prove_batch_curve<pm::BlsCurve>(ctx, pk, transcript, count, instance_host, x, w, assignment_on_device, r_a, proofs, proof_len, status)
+               : host_prove_batch_curve<pm::BnCurve>(ctx, pk, transcript, count, instance_host, x, w, assignment_on_device, r_a, proofs, proof_len, status);
+}
+
 // ---- verify (lib.rs:80-90 -> verifier.rs:19-62) and the verifying key (generator.rs:139-157): host code, no GPU --------------
 namespace {
 

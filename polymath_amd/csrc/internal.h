@@ -112,6 +112,16 @@ struct MsmTables {
     bool wide = false;
 };
 
+// pm_host_prove_batch (prove_batch.hip): the vectors of one GROUP of proofs as [rows][len] arrays, reserved for the largest group seen
+// and reused by later groups and calls.
+struct ProveBatchWs {
+    DevBuf xw, ue, we, u, w, wit_u, u2, tmp, sc_a, sc_c, quotient, lvl[6], part, rows, flags;   // rows: one parameter record per proof
+    void release() {
+        for (DevBuf *b : {&xw, &ue, &we, &u, &w, &wit_u, &u2, &tmp, &sc_a, &sc_c, &quotient, &part, &rows, &flags}) b->release();
+        for (DevBuf &b : lvl) b.release();
+    }
+};
+
 struct TwiddleCache {
     int curve = -1;
     unsigned log_n = 0;
@@ -270,6 +280,7 @@ struct pm_ctx {
     pm::DevBuf xw, ue, we, u, w, wit_u, u2, sc_a, sc_c, quotient, ztail, lvl[6], ra;
     // PM_SHARD_VECTOR prover (prove_sharded.hip): transform temporaries, halo coefficients, roots of the cross-rank butterfly
     pm::DevBuf sh_a, sh_b, sh_c, halo, shard_roots;
+    pm::ProveBatchWs pb;
     uint64_t shard_roots_n;
     uint32_t shard_roots_N;
     int shard_roots_curve;
@@ -314,6 +325,9 @@ int host_threads_env();
 // ---- per-curve entry points implemented in the .hip translation units -----------------------
 template <class C>
 int ntt_run(pm_ctx *ctx, Fp<typename C::FrP> *d_data, unsigned log_n, bool inverse);
+// `rows` transforms, row b at d_data + b * row_stride, the row as grid y of ntt_run's passes (rows == 1: exactly ntt_run)
+template <class C>
+int ntt_run_batch(pm_ctx *ctx, Fp<typename C::FrP> *d_data, unsigned log_n, bool inverse, size_t rows, size_t row_stride);
 // device table of omega_{2^log_n}^j (or its inverse), j < 2^(log_n - 1); cached per context
 template <class C>
 int twiddles_get(pm_ctx *ctx, unsigned log_n, bool inv_dir, const Fp<typename C::FrP> **out);
@@ -466,6 +480,21 @@ int prove_phase2_impl(pm_ctx *ctx, const uint64_t *x1, uint64_t *u_at_x1);
 template <class C>
 int prove_phase3_impl(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const uint64_t *a_at_x1,
                       const uint64_t *c_at_x1, uint64_t *d_xy, int *d_inf);
+
+// prove_batch.hip: the three phases over a group of `rows` proofs against one unsharded key (blockIdx.y = proof).  x / w / r_a / x1 / ...
+// are `rows` records back to back; flags_out[b] = the flag word of proof b (prove.hip: k_check_sap) as the phase left it.
+// prove_batch_group: the largest group the context's msm_max_piece and the HBM budget allow for `count` proofs; 0 = one proof's [d]_1
+// row exceeds a piece (the caller loops over the per-proof path).
+template <class C>
+int prove_batch_group(pm_ctx *ctx, const pm_pk *pk, size_t count, size_t *group);
+template <class C>
+int prove_batch_phase1(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *x, const uint64_t *w, bool assignment_on_device,
+                       const uint64_t *r_a, Affine<C> *a, int *a_inf, Affine<C> *c, int *c_inf, unsigned *flags_out);
+template <class C>
+int prove_batch_phase2(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *x1, uint64_t *u_at_x1);
+template <class C>
+int prove_batch_phase3(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *r_a, const uint64_t *x1, const uint64_t *x2,
+                       const uint64_t *a_at_x1, const uint64_t *c_at_x1, Affine<C> *d, int *d_inf, unsigned *flags_out);
 
 template <class C>
 int prove_phase1_sharded(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const uint64_t *w, const uint64_t *r_a, uint64_t *a_xy, int *a_inf,

@@ -55,7 +55,8 @@ __global__ void k_twiddles(Fp<P> *out, Fp<P> *out_int, Tw28<RR> *out28, size_t c
 }
 
 template <class P>
-__global__ void k_bitrev(Fp<P> *a, unsigned log_n) {
+__global__ void k_bitrev(Fp<P> *a, unsigned log_n, size_t row_stride) {
+    a += (size_t)blockIdx.y * row_stride;      // ntt_run_batch: grid y = row of a [rows][row_stride] array (one row: y = 0)
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     size_t n = (size_t)1 << log_n;
     if (i >= n) return;
@@ -80,9 +81,11 @@ constexpr int LOG_TILE = 8;
 // outputs by `scale` on the way out (the n^-1 of an inverse transform, folded into its last pass).
 template <class P, class RR>
 __global__ __launch_bounds__(256) void k_ntt_pass(const Fp<P> *a, Fp<P> *dst, const Fp<P> *tw, unsigned log_n, unsigned s0, unsigned ns,
-                                                   unsigned log_cols, Fp<P> scale, int do_scale) {
+                                                   unsigned log_cols, Fp<P> scale, int do_scale, size_t a_stride, size_t dst_stride) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     Fp<P> *tile = (Fp<P> *)smem_raw;  // [2^ns][cols]
+    a += (size_t)blockIdx.y * a_stride;        // grid y = row (ntt_run_batch)
+    dst += (size_t)blockIdx.y * dst_stride;
     const unsigned cols = 1u << log_cols, rows = 1u << ns;
     const size_t lo_groups = ((size_t)1 << s0) >> log_cols;  // groups of `cols` consecutive lo values
     const size_t g = blockIdx.x;
@@ -346,9 +349,12 @@ __device__ __forceinline__ void l28_emit(const F28<RR> &v, Fp<P> *dst, const F28
 // general pass: stages [s0, s0 + ns), tile of 2^ns rows x 2^log_cols contiguous columns, src -> dst at the same positions
 template <class P, class RR, unsigned TH>
 __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_ntt_pass28(const Fp<P> *a, Fp<P> *dst, const Tw28<RR> *tw, unsigned log_n, unsigned s0, unsigned ns,
-                                                             unsigned log_cols, Fp<P> scale_int, int do_scale, int pair_stages) {
+                                                             unsigned log_cols, Fp<P> scale_int, int do_scale, int pair_stages, size_t a_stride,
+                                                             size_t dst_stride) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     uint32_t *t = (uint32_t *)smem_raw;
+    a += (size_t)blockIdx.y * a_stride;        // grid y = row (ntt_run_batch)
+    dst += (size_t)blockIdx.y * dst_stride;
     constexpr unsigned tile = L28_EPL * TH;      // == rows * cols: full tiles only (ntt_run)
     const unsigned cols = 1u << log_cols;
     const size_t lo_groups = ((size_t)1 << s0) >> log_cols, g = blockIdx.x;
@@ -385,9 +391,11 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 // (src -> dst.)  The tile is swizzled (column (c + r) & (cols - 1)) so that the column-major store phase is bank-conflict free.
 template <class P, class RR, unsigned TH>
 __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_ntt_first_pass28(const Fp<P> *src, Fp<P> *dst, const Tw28<RR> *tw, unsigned log_n, unsigned ns,
-                                                                   unsigned log_cols, int pair_stages) {
+                                                                   unsigned log_cols, int pair_stages, size_t src_stride, size_t dst_stride) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     uint32_t *t = (uint32_t *)smem_raw;
+    src += (size_t)blockIdx.y * src_stride;    // grid y = row (ntt_run_batch)
+    dst += (size_t)blockIdx.y * dst_stride;
     constexpr unsigned tile = L28_EPL * TH;      // == rows * cols: full tiles only (ntt_run)
     const unsigned cols = 1u << log_cols, rows = 1u << ns, H = log_n - ns, cm = cols - 1;
     const size_t g = blockIdx.x;
@@ -415,7 +423,8 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 }
 
 template <class P>
-__global__ void k_scale(Fp<P> *a, size_t n, Fp<P> s) {
+__global__ void k_scale(Fp<P> *a, size_t n, Fp<P> s, size_t row_stride) {
+    a += (size_t)blockIdx.y * row_stride;
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) a[i] = mul<P>(a[i], s);
 }
@@ -488,12 +497,16 @@ int twiddles_get(pm_ctx *ctx, unsigned log_n, bool inv_dir, const Fp<typename C:
     return PM_OK;
 }
 
+// `rows` transforms of 2^log_n points each, row b at d + b * row_stride: the pass structure below with the row as grid y (the
+// out-of-place passes' temporary holds [rows][n]).  rows == 1 is ntt_run: the same kernels on the same grids.
 template <class C>
-int ntt_run(pm_ctx *ctx, Fp<typename C::FrP> *d, unsigned log_n, bool inv_dir) {
+int ntt_run_batch(pm_ctx *ctx, Fp<typename C::FrP> *d, unsigned log_n, bool inv_dir, size_t rows, size_t row_stride) {
     typedef typename C::FrP P;
     typedef Fp<P> Fr;
     if (log_n > (unsigned)C::TWO_ADICITY) return PM_ERR_DOMAIN_TOO_LARGE;  // D::new(..) None, prover.rs:83,317
-    if (log_n == 0) return PM_OK;
+    if (log_n == 0 || rows == 0) return PM_OK;
+    if (rows > 65535 || row_stride < ((size_t)1 << log_n)) return PM_ERR_INVALID_ARG;
+    const unsigned gy = (unsigned)rows;
     StageTimer timer(ctx, T_NTT);
     const size_t n = (size_t)1 << log_n;
     TwiddleCache *slot = nullptr;
@@ -506,7 +519,7 @@ int ntt_run(pm_ctx *ctx, Fp<typename C::FrP> *d, unsigned log_n, bool inv_dir) {
     const Fr ninv = inv_dir ? inverse<P>(from_u64<P>((uint64_t)n)) : Fr::one();
     if (ntt_l28_domain(log_n)) {
         // the same pass structure on the reduced-radix tiles (k_ntt_pass28, 9 limbs of 29 bits): 2^11 elements x 36 B = 72 KiB of LDS per workgroup
-        PM_HIP(ctx, ctx->ntt_tmp.reserve(n * sizeof(Fr)));
+        PM_HIP(ctx, ctx->ntt_tmp.reserve(rows * n * sizeof(Fr)));
         Fr *tmp = ctx->ntt_tmp.as<Fr>();
         typedef typename C::FrNttRR RR;
         const Tw28<RR> *tw28 = twb.as<Tw28<RR>>();
@@ -543,29 +556,29 @@ int ntt_run(pm_ctx *ctx, Fp<typename C::FrP> *d, unsigned log_n, bool inv_dir) {
             if (k && s0 < log_cols) return PM_ERR_STATE;          // never for log_n >= 11: the kernels' limb-plane stride is the FULL tile
             const bool last = s0 + ns == log_n;
             if (k == 0) {
-                const dim3 grid((unsigned)(n >> (ns + log_cols)));
+                const dim3 grid((unsigned)(n >> (ns + log_cols)), gy);
                 const size_t lds = ((size_t)1 << (ns + log_cols)) * RR::N * 4;
                 if (small)
-                    hipLaunchKernelGGL((k_ntt_first_pass28<P, RR, 256>), grid, dim3(256), lds, ctx->stream, (const Fr *)d, tmp, tw28, log_n, ns, log_cols, pair_stages);
+                    hipLaunchKernelGGL((k_ntt_first_pass28<P, RR, 256>), grid, dim3(256), lds, ctx->stream, (const Fr *)d, tmp, tw28, log_n, ns, log_cols, pair_stages, row_stride, n);
                 else
-                    hipLaunchKernelGGL((k_ntt_first_pass28<P, RR, 512>), grid, dim3(512), lds, ctx->stream, (const Fr *)d, tmp, tw28, log_n, ns, log_cols, pair_stages);
+                    hipLaunchKernelGGL((k_ntt_first_pass28<P, RR, 512>), grid, dim3(512), lds, ctx->stream, (const Fr *)d, tmp, tw28, log_n, ns, log_cols, pair_stages, row_stride, n);
             } else {
                 if (s0 < log_cols) log_cols = s0;
-                const dim3 grid((unsigned)(n >> (ns + log_cols)));
+                const dim3 grid((unsigned)(n >> (ns + log_cols)), gy);
                 const size_t lds = ((size_t)1 << (ns + log_cols)) * RR::N * 4;
                 if (small)
                     hipLaunchKernelGGL((k_ntt_pass28<P, RR, 256>), grid, dim3(256), lds, ctx->stream, (const Fr *)tmp, last ? d : tmp, tw28, log_n, s0, ns,
-                                       log_cols, scale_int, last && inv_dir ? 1 : 0, pair_stages);
+                                       log_cols, scale_int, last && inv_dir ? 1 : 0, pair_stages, n, last ? row_stride : n);
                 else
                     hipLaunchKernelGGL((k_ntt_pass28<P, RR, 512>), grid, dim3(512), lds, ctx->stream, (const Fr *)tmp, last ? d : tmp, tw28, log_n, s0, ns,
-                                       log_cols, scale_int, last && inv_dir ? 1 : 0, pair_stages);
+                                       log_cols, scale_int, last && inv_dir ? 1 : 0, pair_stages, n, last ? row_stride : n);
             }
             PM_HIP(ctx, hipGetLastError());
             s0 += ns;
         }
         return PM_OK;
     }
-    hipLaunchKernelGGL(k_bitrev<P>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d, log_n);
+    hipLaunchKernelGGL(k_bitrev<P>, dim3((unsigned)((n + 255) / 256), gy), dim3(256), 0, ctx->stream, d, log_n, row_stride);
     PM_HIP(ctx, hipGetLastError());
     unsigned s0 = 0;
     while (s0 < log_n) {
@@ -575,21 +588,28 @@ int ntt_run(pm_ctx *ctx, Fp<typename C::FrP> *d, unsigned log_n, bool inv_dir) {
         if (s0 < log_cols) log_cols = s0;
         size_t tiles = n >> (ns + log_cols);
         size_t lds = ((size_t)1 << (ns + log_cols)) * sizeof(Fr);
-        hipLaunchKernelGGL((k_ntt_pass<P, typename C::FrRR>), dim3((unsigned)tiles), dim3(256), lds, ctx->stream, (const Fr *)d, d, tw, log_n, s0, ns,
-                           log_cols, ninv, 0);
+        hipLaunchKernelGGL((k_ntt_pass<P, typename C::FrRR>), dim3((unsigned)tiles, gy), dim3(256), lds, ctx->stream, (const Fr *)d, d, tw, log_n, s0, ns,
+                           log_cols, ninv, 0, row_stride, row_stride);
         PM_HIP(ctx, hipGetLastError());
         s0 += ns;
     }
     if (inv_dir) {
-        hipLaunchKernelGGL(k_scale<P>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d, n, ninv);
+        hipLaunchKernelGGL(k_scale<P>, dim3((unsigned)((n + 255) / 256), gy), dim3(256), 0, ctx->stream, d, n, ninv, row_stride);
         PM_HIP(ctx, hipGetLastError());
     }
     return PM_OK;
+}
+
+template <class C>
+int ntt_run(pm_ctx *ctx, Fp<typename C::FrP> *d, unsigned log_n, bool inv_dir) {
+    return ntt_run_batch<C>(ctx, d, log_n, inv_dir, 1, (size_t)1 << (log_n > 63 ? 0 : log_n));
 }
 
 template int twiddles_get<BlsCurve>(pm_ctx *, unsigned, bool, const Fp<BlsFrP> **);
 template int twiddles_get<BnCurve>(pm_ctx *, unsigned, bool, const Fp<BnFrP> **);
 template int ntt_run<BlsCurve>(pm_ctx *, Fp<BlsFrP> *, unsigned, bool);
 template int ntt_run<BnCurve>(pm_ctx *, Fp<BnFrP> *, unsigned, bool);
+template int ntt_run_batch<BlsCurve>(pm_ctx *, Fp<BlsFrP> *, unsigned, bool, size_t, size_t);
+template int ntt_run_batch<BnCurve>(pm_ctx *, Fp<BnFrP> *, unsigned, bool, size_t, size_t);
 
 }  // namespace pm

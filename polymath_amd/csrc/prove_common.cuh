@@ -3,6 +3,7 @@
 #include <cstring>
 
 #include "internal.h"
+#include "fq28.cuh"
 
 namespace pm {
 
@@ -68,6 +69,107 @@ static inline NumConsts<P> make_num_consts(const Fp<P> &x2, const Fp<P> rah[2], 
     nc.two_x2_r1 = dbl<P>(nc.x2r1);
     nc.minus_const = neg<P>(add<P>(a_at, mul<P>(x2, c_at)));
     return nc;
+}
+
+// ------------------------------------------------------------- numerator + division (phase 3)
+// Numerator of prover.rs:211-216, multiplied through by Y^-gamma = X^(5 sigma), as a function of
+// the coefficient index k (never materialised):
+//   [0,2)            x2 r_a
+//   2s + [0,3)       r_a + x2 r_a^2
+//   3s + [0,n)       x2 * witness_u                          (prover.rs:168-171)
+//   5s + [0,n+1)     u + x2 * 2 r_a u  - (a + x2 c) at +0    (prover.rs:145-152,366-368,196-197)
+//   8s + [0,2n-1)    x2 * u^2     (witness_w + (u^2 - w) = u^2: N6 == N2)
+template <class P>
+__device__ __forceinline__ Fp<P> numerator_at(uint64_t k, const NumParams &np, const NumConsts<P> &nc, const Fp<P> *u,
+                                              const Fp<P> *wit_u, const Fp<P> *u2) {
+    const uint64_t s = np.sigma, n = np.n;
+    if (k >= 8 * s) {
+        uint64_t i = k - 8 * s;
+        return i < 2 * n - 1 ? mul<P>(nc.x2, u2[i]) : Fp<P>::zero();
+    }
+    if (k >= 5 * s) {
+        uint64_t i = k - 5 * s;
+        if (i > n) return Fp<P>::zero();
+        Fp<P> t = Fp<P>::zero();
+        if (i < n) t = add<P>(u[i], mul<P>(nc.two_x2_r0, u[i]));
+        if (i > 0) t = add<P>(t, mul<P>(nc.two_x2_r1, u[i - 1]));
+        if (i == 0) t = add<P>(t, nc.minus_const);
+        return t;
+    }
+    if (k >= 3 * s) {
+        uint64_t i = k - 3 * s;
+        return i < n ? mul<P>(nc.x2, wit_u[i]) : Fp<P>::zero();
+    }
+    if (k >= 2 * s) {
+        uint64_t i = k - 2 * s;
+        return i < 3 ? nc.b2[i] : Fp<P>::zero();
+    }
+    if (k == 0) return nc.x2r0;
+    if (k == 1) return nc.x2r1;
+    return Fp<P>::zero();
+}
+
+// Round 5: the two kernels that walk the numerator -- k_div_level0 and k_div_expand0, 0.77 of the scan's 0.89 ms -- run their Horner
+// chains in REDUCED RADIX (fq28.cuh: 9 limbs of 29 bits), as the transform tiles do: the multipliers x1, x2, 2 x2 r_a are handed over
+// in the internal Montgomery form (value 2^261 mod p), so that f28_mul(standard-form value, multiplier) is again a standard-form
+// value, sums are limb-wise, and a dense canonical element is only rebuilt where one is STORED.  The dense product mul<P> unpacks both
+// operands and shifts / reduces / packs its result every time: ~370 instructions for 162 multiplier operations against ~200.
+// Values are the same residues, the stored elements the same canonical words.
+template <class RR>
+struct NumMul28 {
+    F28<RR> x1, x2, two_x2_r0, two_x2_r1;      // internal form, canonical, tight limbs
+};
+template <class P>
+static inline NumMul28<typename Radix28<P>::RR> make_num_mul28(const Fp<P> &x1, const NumConsts<P> &nc) {
+    typedef typename Radix28<P>::RR RR;
+    Fp<P> k;
+    for (int i = 0; i < P::N; ++i) k.l[i] = RR::STD2INT[i];
+    NumMul28<RR> m;
+    m.x1 = f28_unpack<RR>(mul<P>(x1, k).l);
+    m.x2 = f28_unpack<RR>(mul<P>(nc.x2, k).l);
+    m.two_x2_r0 = f28_unpack<RR>(mul<P>(nc.two_x2_r0, k).l);
+    m.two_x2_r1 = f28_unpack<RR>(mul<P>(nc.two_x2_r1, k).l);
+    return m;
+}
+// numerator_at on reduced-radix limbs: a LAZY standard-form value, limbs < 4 * 2^29, value < 7p (u + two products + a constant)
+template <class P, class RR>
+__device__ __forceinline__ F28<RR> numerator28_at(uint64_t k, const NumParams &np, const NumConsts<P> &nc, const NumMul28<RR> &m, const Fp<P> *u,
+                                                  const Fp<P> *wit_u, const Fp<P> *u2) {
+    const uint64_t s = np.sigma, n = np.n;
+    if (k >= 8 * s) {
+        const uint64_t i = k - 8 * s;
+        return i < 2 * n - 1 ? f28_mul<RR>(f28_unpack<RR>(u2[i].l), m.x2) : f28_zero<RR>();
+    }
+    if (k >= 5 * s) {
+        const uint64_t i = k - 5 * s;
+        if (i > n) return f28_zero<RR>();
+        F28<RR> t = f28_zero<RR>();
+        if (i < n) {
+            const F28<RR> ui = f28_unpack<RR>(u[i].l);
+            t = f28_add<RR>(ui, f28_mul<RR>(ui, m.two_x2_r0));
+        }
+        if (i > 0) t = f28_add<RR>(t, f28_mul<RR>(f28_unpack<RR>(u[i - 1].l), m.two_x2_r1));
+        if (i == 0) t = f28_add<RR>(t, f28_unpack<RR>(nc.minus_const.l));
+        return t;
+    }
+    if (k >= 3 * s) {
+        const uint64_t i = k - 3 * s;
+        return i < n ? f28_mul<RR>(f28_unpack<RR>(wit_u[i].l), m.x2) : f28_zero<RR>();
+    }
+    if (k >= 2 * s) {
+        const uint64_t i = k - 2 * s;
+        return i < 3 ? f28_unpack<RR>(nc.b2[i].l) : f28_zero<RR>();
+    }
+    if (k == 0) return f28_unpack<RR>(nc.x2r0.l);
+    if (k == 1) return f28_unpack<RR>(nc.x2r1.l);
+    return f28_zero<RR>();
+}
+// one Horner step: acc (tight limbs, value < 9p) -> acc x1 + N_k: the product is < 2p, the sum < 9p; carries propagated so that the
+// next product's columns stay inside 64 bits (9 * 2^29 * 2^29 * 2 < 2^63)
+template <class P, class RR>
+__device__ __forceinline__ F28<RR> horner28_step(const F28<RR> &acc, uint64_t k, const NumParams &np, const NumConsts<P> &nc, const NumMul28<RR> &m,
+                                                 const Fp<P> *u, const Fp<P> *wit_u, const Fp<P> *u2) {
+    return f28_weak_norm<RR>(f28_add<RR>(f28_mul<RR>(acc, m.x1), numerator28_at<P, RR>(k, np, nc, m, u, wit_u, u2)));
 }
 
 }  // namespace pm

@@ -319,6 +319,29 @@ public:
     // all-gather + pm_g1_sum of SURVEY.md §8e; null for an unsharded key.  Non-zero return aborts the proof.
     typedef std::function<int(G1Point<C> *points, int count)> Combine;
 
+    // The host part of create_proof_with_assignment between the GPU phases, shared by prove_raw and the batch prover
+    // (csrc/host_prove.hip: pm_host_prove_batch), one Glue per proof.
+    struct Glue {
+        T t;
+        Fr x1, y1_alpha, y1_gamma, c_at_x1, x2;
+        Glue() : t("polymath") {}                                                           // prover.rs:125, B_POLYMATH
+    };
+    // after phase 1 ([a]_1, [c]_1 of `proof` known): x1 and the powers of y1
+    static void glue_x1(Glue &g, const ProvingKey<C> &pk, const std::vector<Fr> &instance, const Proof<C> &proof) {
+        g.x1 = compute_x1(g.t, instance, proof.a_g1, proof.c_g1);                           // :126
+        Fr y1 = F::pow(g.x1, pk.sigma), y1_inv = F::inv(y1);                                // :128
+        g.y1_alpha = F::pow(y1_inv, MINUS_ALPHA);                                           // :130
+        g.y1_gamma = F::pow(y1_inv, MINUS_GAMMA);                                           // :134
+    }
+    // after phase 2 (u(x1) known): a(x1) into the proof, c(x1) and x2
+    static void glue_x2(Glue &g, const ProvingKey<C> &pk, const std::vector<Fr> &instance, const Fr r_a[2], const Fr &u_at_x1, Proof<C> &proof) {
+        Fr ra_at = F::add(r_a[0], F::mul(r_a[1], g.x1));
+        proof.a_at_x1 = F::add(u_at_x1, F::mul(ra_at, g.y1_alpha));                         // :132
+        Fr pi_at_x1 = compute_pi_at_x1(pk, instance, g.x1, g.y1_gamma);                     // :135
+        g.c_at_x1 = F::mul(F::sub(F::mul(F::add(proof.a_at_x1, g.y1_gamma), proof.a_at_x1), pi_at_x1), F::inv(g.y1_alpha));   // :138, common.rs:73-75
+        g.x2 = compute_x2(g.t, g.x1, proof.a_at_x1, g.c_at_x1);                             // :189
+    }
+
     Proof<C> prove_raw(const ProvingKey<C> &pk, const std::vector<Fr> &instance, const uint64_t *x, const uint64_t *w, bool on_device,
                        const Fr r_a[2], const Combine &combine = nullptr) {
         Proof<C> proof;
@@ -334,19 +357,13 @@ public:
             proof.a_g1 = ac[0];
             proof.c_g1 = ac[1];
         }
-        T t("polymath");                                                                    // prover.rs:125, B_POLYMATH
-        Fr x1 = compute_x1(t, instance, proof.a_g1, proof.c_g1);                            // :126
-        Fr y1 = F::pow(x1, pk.sigma), y1_inv = F::inv(y1);                                  // :128
-        Fr y1_alpha = F::pow(y1_inv, MINUS_ALPHA);                                          // :130
+        Glue g;
+        glue_x1(g, pk, instance, proof);
         Fr u_at_x1;
-        st = pm_prove_phase2(ctx_.h, (const uint64_t *)x1.l, (uint64_t *)u_at_x1.l);
+        st = pm_prove_phase2(ctx_.h, (const uint64_t *)g.x1.l, (uint64_t *)u_at_x1.l);
         if (st) throw PolymathError(2, st, "prove phase 2 failed");
-        Fr ra_at = F::add(r_a[0], F::mul(r_a[1], x1));
-        proof.a_at_x1 = F::add(u_at_x1, F::mul(ra_at, y1_alpha));                           // :132
-        Fr y1_gamma = F::pow(y1_inv, MINUS_GAMMA);                                          // :134
-        Fr pi_at_x1 = compute_pi_at_x1(pk, instance, x1, y1_gamma);                         // :135
-        Fr c_at_x1 = F::mul(F::sub(F::mul(F::add(proof.a_at_x1, y1_gamma), proof.a_at_x1), pi_at_x1), F::inv(y1_alpha));   // :138, common.rs:73-75
-        Fr x2 = compute_x2(t, x1, proof.a_at_x1, c_at_x1);                                  // :189
+        glue_x2(g, pk, instance, r_a, u_at_x1, proof);
+        const Fr &x1 = g.x1, &x2 = g.x2, &c_at_x1 = g.c_at_x1;
         st = pm_prove_phase3(ctx_.h, (const uint64_t *)x1.l, (const uint64_t *)x2.l, (const uint64_t *)proof.a_at_x1.l,
                              (const uint64_t *)c_at_x1.l, (uint64_t *)&proof.d_g1.p, &di);
         if (st) throw PolymathError(3, st, "prove phase 3 failed: status " + std::to_string(st));   // prover.rs:221,222

@@ -392,6 +392,42 @@ class Polymath:
             raise PolymathProverError(0, rc)
         return data
 
+    def prove_batch(self, pk, circuits_or_limbs, r_as, device_ptrs=None):
+        """Many assignments of one circuit against one unsharded key in ONE native call (pm_host_prove_batch: every stage of the
+        prover with the proof as a grid dimension, three batched MSMs per group of proofs).  circuits_or_limbs[i]: a circuit, a
+        LimbCircuit or an (x_limbs, w_limbs) pair; r_as[i] = [r0, r1].  device_ptrs = (d_x, d_w): the assignments are already in HBM
+        as count x m0 / count x mw rows (the x limbs of circuits_or_limbs are still hashed on the host).
+        -> (proofs, statuses): proofs[i] = Proof::serialize_compressed bytes, or None where statuses[i] != 0 (an unsatisfied
+        assignment gets the status prove_native raises for it and leaves its neighbours alone)."""
+        if self.transcript_name is None:
+            raise ValueError("prove_batch needs one of the reference's transcripts: " + ", ".join(TRANSCRIPTS))
+        if len(circuits_or_limbs) != len(r_as):
+            raise ValueError("one r_a per assignment")
+        f = self.field
+        xs, ws = [], []
+        for c in circuits_or_limbs:
+            if isinstance(c, LimbCircuit):
+                x, w = c.inst_limbs, c.wit_limbs
+            elif isinstance(c, tuple) and len(c) == 2:
+                x, w = c
+            else:
+                _, instance, witness = self._synthesize(c)
+                x, w = f.fr_limbs(instance), f.fr_limbs(witness)
+            xs.append(np.asarray(x, dtype=np.uint64).reshape(-1, 4))
+            ws.append(np.asarray(w, dtype=np.uint64).reshape(-1, 4))
+        count = len(xs)
+        x_all = np.stack(xs) if count else np.zeros((0, 0, 4), dtype=np.uint64)
+        w_all = np.stack(ws) if count else np.zeros((0, 0, 4), dtype=np.uint64)
+        ra_all = np.stack([f.fr_limbs(list(r)) for r in r_as]) if count else np.zeros((0, 2, 4), dtype=np.uint64)
+        if device_ptrs is not None:
+            rc, data, status = pk.host_prove_batch(self.transcript_name, x_all, device_ptrs[0], device_ptrs[1], ra_all, on_device=True)
+        else:
+            rc, data, status = pk.host_prove_batch(self.transcript_name, x_all, x_all, w_all, ra_all)
+        if rc:
+            raise PolymathProverError(0, rc)
+        plen = len(data) // count if count else 0
+        return [data[i * plen:(i + 1) * plen] if status[i] == 0 else None for i in range(count)], [int(s) for s in status]
+
     def prove_limbs(self, pk, instance, x_limbs, w_limbs, r_a, combine=None, device_ptrs=None):
         """device_ptrs = (d_x, d_w): the assignment is already resident in HBM (pm_prove_phase1_device)."""
         f, r = self.field, self.field.r

@@ -715,6 +715,47 @@ impl GpuKey {
         Ok(GpuKey { raw, curve, m0: r1cs.m0, mw: r1cs.mw })
     }
 
+    /// `pm_host_prove_batch`: `rows.len()` runs of `create_proof_with_assignment` against this (unsharded) key in one call, the
+    /// library's own transcript (`transcript`: `sys::PM_TRANSCRIPT_*`) included.  Row i = (instance with the leading one, witness,
+    /// r_a).  Returns, per row, `Ok(Proof::serialize_compressed bytes)` or the status `pm_host_prove` gives that row (an unsatisfied
+    /// assignment: `RemainderNonzero` / `DegreeBound`); a failing row leaves its neighbours alone.  The outer error is the call's.
+    pub fn prove_batch<E: Pairing>(
+        &self,
+        ctx: &mut Context,
+        transcript: i32,
+        rows: &[(&[E::ScalarField], &[E::ScalarField], [E::ScalarField; 2])],
+    ) -> Result<Vec<Result<Vec<u8>, Status>>, HipError> {
+        let curve = curve_checked::<E>()?;
+        if curve != self.curve {
+            return Err(err(Status::InvalidArg, "key of another curve"));
+        }
+        let (mut x, mut w, mut ra) = (Vec::new(), Vec::new(), Vec::new());
+        for (xi, wi, ri) in rows {
+            if xi.len() as u64 != self.m0 || wi.len() as u64 != self.mw {
+                return Err(err(Status::LenMismatch, "a row's instance / witness length is not the key's"));
+            }
+            x.extend_from_slice(xi);
+            w.extend_from_slice(wi);
+            ra.extend_from_slice(ri);
+        }
+        let proof_len = 3 * 8 * curve.fq_limbs() + 32;
+        let mut bytes = vec![0u8; proof_len * rows.len()];
+        let mut status = vec![0i32; rows.len()];
+        let w_ptr = if w.is_empty() { core::ptr::null() } else { fr_ptr(&w) };
+        // SAFETY: live key and context; x / w / ra hold rows.len() records of m0 / mw / 2 elements (layout checked), `bytes` and
+        // `status` have room for rows.len() records.
+        let rc = unsafe {
+            sys::pm_host_prove_batch(ctx.raw, self.raw, transcript, rows.len(), fr_ptr(&x), fr_ptr(&x), w_ptr, 0, fr_ptr(&ra), bytes.as_mut_ptr(), proof_len,
+                                     status.as_mut_ptr())
+        };
+        ctx.check(rc)?;
+        Ok(status
+            .iter()
+            .zip(bytes.chunks_exact(proof_len))
+            .map(|(&s, b)| if s == sys::PM_OK { Ok(b.to_vec()) } else { Err(Status::from_raw(s)) })
+            .collect())
+    }
+
     /// `pm_pk_info`: n, m0, sigma, omega and the six base-vector lengths of this key.
     pub fn info<E: Pairing>(&self) -> Result<KeyInfo<E>, HipError> {
         let curve = curve_checked::<E>()?;

@@ -1,0 +1,87 @@
+#!/usr/bin/env python3
+"""Batch prover against a loop of single proofs: one key, B device-resident assignments of one circuit, alternating in this process
+  (a) one pm_host_prove_batch call of B proofs            (b) a loop of B pm_host_prove calls (device pointers)
+and printing proofs/s for both plus the stage split of pm_last_timings (summed over the batch for (a); one proof for (b)).
+  python tools/prove_bench.py --circuit mimc322 --batch 256 --reps 5
+  python tools/prove_bench.py --circuit bench:32000 --batch 16 --reps 3        BenchCircuit with 32000 constraints: n = 2^16
+The B rows cycle through min(B, 32) distinct seeded assignments with distinct r_a (a proof's cost does not depend on its values)."""
+import argparse, json, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+from polymath_amd import circuits as PC
+from polymath_amd.polymath import Polymath
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants) or bench:NC (BenchCircuit, NC constraints)")
+ap.add_argument("--batch", type=int, default=16)
+ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--curve", default="bls12_381")
+ap.add_argument("--transcript", default="merlin")
+ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="pm_ctx_set_option before the key is made, e.g. --opt tables=0")
+a = ap.parse_args()
+pm = Polymath(a.curve, a.transcript, device=0)
+for kv in a.opt:
+    pm.ctx.set_option(kv.split("=", 1)[0], int(kv.split("=", 1)[1]))
+r = pm.field.r
+g = PC.SplitMix64(20260117)
+if a.circuit.startswith("mimc"):
+    consts = [g.fr(r) for _ in range(int(a.circuit[4:]))]
+    make = lambda: PC.MiMCDemo(g.fr(r), g.fr(r), consts)
+else:
+    nc = int(a.circuit.split(":", 1)[1])
+    make = lambda: PC.BenchCircuit(g.fr(r), g.fr(r), 10, nc)
+B, distinct = a.batch, min(a.batch, 32)
+circuits = [make() for _ in range(distinct)]
+t0 = time.time()
+pk = pm.setup(circuits[0], g.fr(r), g.fr(r))
+setup_s = time.time() - t0
+rows = []
+for c in circuits:
+    _, inst, wit = pm._synthesize(c)
+    rows.append((pm.field.fr_limbs(inst), pm.field.fr_limbs(wit), [g.fr(r), g.fr(r)]))
+pick = [i % distinct for i in range(B)]
+xs = np.ascontiguousarray(np.stack([rows[i][0] for i in pick]))
+ws = np.ascontiguousarray(np.stack([rows[i][1] for i in pick]))
+ras = np.ascontiguousarray(np.stack([pm.field.fr_limbs(rows[i][2]) for i in pick]))
+dx = torch.from_numpy(xs.view(np.int64)).cuda()
+dw = torch.from_numpy(ws.view(np.int64)).cuda()
+torch.cuda.synchronize()
+m0, mw = xs.shape[1], ws.shape[1]
+
+
+def run_batch():
+    t0 = time.perf_counter()
+    rc, data, status = pk.host_prove_batch(a.transcript, xs, dx.data_ptr(), dw.data_ptr(), ras, on_device=True)
+    dt = time.perf_counter() - t0
+    assert rc == 0 and not status.any(), (rc, status)
+    return dt, data, pm.ctx.timings()
+
+
+def run_loop():
+    out = []
+    t0 = time.perf_counter()
+    for i in range(B):
+        rc, proof = pk.host_prove(a.transcript, xs[i], dx.data_ptr() + 32 * m0 * i, dw.data_ptr() + 32 * mw * i, ras[i], on_device=True)
+        assert rc == 0
+        out.append(proof)
+    dt = time.perf_counter() - t0
+    return dt, b"".join(out), pm.ctx.timings()
+
+
+_, db, _ = run_batch()                  # warm-up of both routes (allocations, twiddles, first launches) and the equality check
+_, dl, _ = run_loop()
+ta, tb = [], []
+for _ in range(a.reps):
+    dt, _, tm_batch = run_batch()
+    ta.append(dt)
+    dt, _, tm_one = run_loop()
+    tb.append(dt)
+med = lambda v: sorted(v)[len(v) // 2]
+print(json.dumps({"curve": a.curve, "circuit": a.circuit, "n": pk.n, "batch": B, "bytes_equal": db == dl, "setup_s": round(setup_s, 3),
+                  "batch_ms": [round(t * 1e3, 3) for t in ta], "loop_ms": [round(t * 1e3, 3) for t in tb],
+                  "batch_proofs_per_s": round(B / med(ta), 1), "loop_proofs_per_s": round(B / med(tb), 1),
+                  "batch_over_loop": round(med(tb) / med(ta), 3),
+                  "batch_stage_ms_sum_over_batch": {k: round(v, 3) for k, v in tm_batch.items()},
+                  "loop_stage_ms_last_proof": {k: round(v, 3) for k, v in tm_one.items()}}))
