@@ -144,8 +144,14 @@ int pm_ctx_get_option(const pm_ctx *ctx, int option, long long *value);
 /* Radix-2 NTT over Fr, natural order in and out, like ark-poly Radix2EvaluationDomain::fft /
  * ifft (prover.rs:241,319,325); inverse scales by 1/n.  `data` is a HOST buffer of 2^log_n Fr. */
 int pm_ntt(pm_ctx *ctx, int curve, uint64_t *data, unsigned log_n, int inverse);
-/* Same on a DEVICE buffer (hipMalloc'd by the caller, e.g. a torch tensor's data_ptr). */
+/* Same on a DEVICE buffer (hipMalloc'd by the caller, e.g. a torch tensor's data_ptr).  The transform runs on the context's own
+ * non-blocking stream and has finished when the call returns; work of the caller's streams that writes the buffer must be
+ * complete before the call. */
 int pm_ntt_device(pm_ctx *ctx, int curve, uint64_t *d_data, unsigned log_n, int inverse);
+/* `rows` transforms of 2^log_n points each on a DEVICE buffer, row b at d_data + b * row_stride Fr elements; the elements
+ * between the end of a row and the start of the next (row_stride > 2^log_n) are neither read nor written.  rows == 0 is
+ * PM_OK and touches nothing; PM_ERR_INVALID_ARG for rows > 65535 or row_stride < 2^log_n. */
+int pm_ntt_batch_device(pm_ctx *ctx, int curve, uint64_t *d_data, unsigned log_n, int inverse, size_t rows, size_t row_stride);
 
 /* Variable-base MSM == E::G1::msm_unchecked(bases, scalars) (prover.rs:380-384), host buffers. */
 int pm_msm_g1(pm_ctx *ctx, int curve, const void *bases, size_t base_stride, const uint64_t *scalars,

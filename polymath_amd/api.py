@@ -61,7 +61,7 @@ class PolymathError(RuntimeError):
 
 EXPORTS = [
     "pm_device_count", "pm_ctx_create", "pm_ctx_destroy", "pm_last_error", "pm_last_timings", "pm_ntt",
-    "pm_ntt_device", "pm_msm_g1", "pm_bases_upload", "pm_bases_generate_multiples", "pm_bases_download",
+    "pm_ntt_device", "pm_ntt_batch_device", "pm_msm_g1", "pm_bases_upload", "pm_bases_generate_multiples", "pm_bases_download",
     "pm_bases_precompute", "pm_bases_len", "pm_bases_free", "pm_msm_g1_resident", "pm_msm_g1_resident_batch", "pm_g1_sum", "pm_pk_load", "pm_pk_generate",
     "pm_pk_info", "pm_pk_msm_plan", "pm_pk_export_bases", "pm_pk_free", "pm_prove_phase1", "pm_prove_phase1_device", "pm_prove_phase2", "pm_prove_phase3", "pm_host_prove", "pm_host_prove_batch", "pm_host_prove_sharded",
     "pm_prove_tap", "pm_host_keccak_f1600", "pm_synth_r1cs", "pm_selftest_field",
@@ -101,6 +101,7 @@ def load_library():
     L.pm_last_timings.argtypes = [vp, ct.POINTER(ct.c_double), i]
     L.pm_ntt.argtypes = [vp, i, u64p, ct.c_uint, i]
     L.pm_ntt_device.argtypes = [vp, i, vp, ct.c_uint, i]
+    L.pm_ntt_batch_device.argtypes = [vp, i, vp, ct.c_uint, i, sz, sz]
     L.pm_msm_g1.argtypes = [vp, i, vp, sz, u64p, sz, u64p, intp]
     L.pm_bases_upload.argtypes = [vp, i, vp, sz, sz, ct.POINTER(vp)]
     L.pm_bases_generate_multiples.argtypes = [vp, i, sz, ct.POINTER(vp)]
@@ -490,6 +491,10 @@ class Context:
 
     def ntt_device(self, curve, dptr, log_n, inverse=False):
         self.check(self.L.pm_ntt_device(self.h, CURVE_IDS[curve], ct.c_void_p(dptr), log_n, int(inverse)))
+
+    def ntt_batch_device(self, curve, dptr, log_n, inverse, rows, row_stride):
+        """pm_ntt_batch_device: `rows` transforms in place on a device buffer, row b at dptr + b * row_stride Fr elements."""
+        self.check(self.L.pm_ntt_batch_device(self.h, CURVE_IDS[curve], ct.c_void_p(dptr), log_n, int(inverse), rows, row_stride))
 
     def msm(self, curve, bases, scalars):
         cid = CURVE_IDS[curve]

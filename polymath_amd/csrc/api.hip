@@ -230,6 +230,22 @@ extern "C" int pm_ntt_device(pm_ctx *ctx, int curve, uint64_t *d_data, unsigned 
     return PM_DISPATCH(curve, ntt_dev<BlsCurve>(ctx, d_data, log_n, inverse), ntt_dev<BnCurve>(ctx, d_data, log_n, inverse));
 }
 
+template <class C>
+static int ntt_batch_dev(pm_ctx *ctx, uint64_t *d, unsigned log_n, int inverse, size_t rows, size_t row_stride) {
+    timing_reset(ctx);
+    PM_TRY(ntt_run_batch<C>(ctx, (Fp<typename C::FrP> *)d, log_n, inverse != 0, rows, row_stride));
+    PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    timing_flush(ctx);
+    return PM_OK;
+}
+
+extern "C" int pm_ntt_batch_device(pm_ctx *ctx, int curve, uint64_t *d_data, unsigned log_n, int inverse, size_t rows, size_t row_stride) {
+    if (!ctx || !d_data) return PM_ERR_INVALID_ARG;
+    PM_TRY(set_device(ctx));
+    return PM_DISPATCH(curve, ntt_batch_dev<BlsCurve>(ctx, d_data, log_n, inverse, rows, row_stride),
+                       ntt_batch_dev<BnCurve>(ctx, d_data, log_n, inverse, rows, row_stride));
+}
+
 // ---------------------------------------------------------------------------------- MSM
 struct BasesDeleter {   // frees the device allocations with the handle: error paths cannot leak HBM
     void operator()(pm_bases *b) const {

@@ -142,6 +142,7 @@ extern "C" {
     // ---- standalone kernels: Radix2EvaluationDomain::fft / ifft (prover.rs:241,319,325), msm_unchecked (prover.rs:380-384)
     pub fn pm_ntt(ctx: *mut pm_ctx, curve: i32, data: *mut u64, log_n: u32, inverse: i32) -> i32;
     pub fn pm_ntt_device(ctx: *mut pm_ctx, curve: i32, d_data: *mut u64, log_n: u32, inverse: i32) -> i32;
+    pub fn pm_ntt_batch_device(ctx: *mut pm_ctx, curve: i32, d_data: *mut u64, log_n: u32, inverse: i32, rows: usize, row_stride: usize) -> i32;
     pub fn pm_msm_g1(ctx: *mut pm_ctx, curve: i32, bases: *const c_void, base_stride: usize, scalars: *const u64, len: usize, out_xy: *mut u64, out_inf: *mut i32) -> i32;
     pub fn pm_bases_upload(ctx: *mut pm_ctx, curve: i32, bases: *const c_void, base_stride: usize, len: usize, out: *mut *mut pm_bases) -> i32;
     pub fn pm_bases_generate_multiples(ctx: *mut pm_ctx, curve: i32, len: usize, out: *mut *mut pm_bases) -> i32;

@@ -794,24 +794,30 @@ def test_device_field_products_match_host_cios(gpu_ctx):
 
 
 @pytest.mark.parametrize("curve", CURVE_LIST)
-@pytest.mark.parametrize("log_n", [11, 13, 18, 19])
+@pytest.mark.parametrize("log_n", [11, 13, 14, 15, 16, 17, 18, 19, 20])
 def test_ntt_extreme_inputs_vs_oracle(gpu_ctx, oracle, curve, log_n):
     """The reduced-radix tile kernels carry lazily (ntt.hip: values up to 37p, limbs up to 2^29 + 2^30 between carry
     propagations): inputs that push every butterfly to the top of its range -- all p - 1, p - 1 / 0 / 1 patterns, one spike --
     must still come out canonical and equal to the oracle's transform (prover.rs:241,319,325 call sites), both directions.
-    11 = one 6- and one 5-stage pass, 13 = 7 + 6, 18 = two 9-stage passes, 19 = 7 + 6 + 6."""
+    11 = one 6- and one 5-stage pass, 13 = 7 + 6, 18 = two 9-stage passes, 19 = 7 + 6 + 6; 14 = 7 + 7 (a 7-stage pass in
+    k_ntt_pass28, not only in the first-pass kernel), 15 = 8 + 7 and 16 = 8 + 8 (8-stage passes: values below 33p on the small
+    tile, the `ns <= 7` argument of l28_emit false), 17 = 9 + 8, 20 = 7 + 7 + 6.
+    What this does NOT tell apart is `ns <= 7` from `ns <= 8` in that argument: in the default build (PM_NTT_CANONICAL_QUOT = 1)
+    both settings of short_pass reach f28_canonical_quot, whose code does not depend on JMAX, so the two branches are the same
+    instructions.  They differ only in a PM_NTT_CANONICAL_QUOT = 0 build (conditional subtractions from 16p or from 32p)."""
     r = CURVES[curve].r
     n = 1 << log_n
     rng = np.random.default_rng(log_n)
-    pats = [
-        [r - 1] * n,
-        [(r - 1) if (i & 1) else 0 for i in range(n)],
-        [(r - 1) if (i % 3 == 0) else 1 for i in range(n)],
-        [r - 1 - int(v) for v in rng.integers(0, 4, size=n)],
-        [0] * (n - 1) + [r - 1],
+    i = np.arange(n)
+    pats = [                                   # (the distinct values, which of them every element takes)
+        ([r - 1], np.zeros(n, dtype=np.int64)),
+        ([0, r - 1], i & 1),
+        ([1, r - 1], (i % 3 == 0).astype(np.int64)),
+        ([r - 1, r - 2, r - 3, r - 4], rng.integers(0, 4, size=n)),
+        ([0, r - 1], (i == n - 1).astype(np.int64)),
     ]
-    for vals in pats:
-        a = oracle.fr_to_mont_limbs(curve, vals)
+    for table, which in pats:
+        a = oracle.fr_to_mont_limbs(curve, table)[which]
         for inverse in (False, True):
             assert np.array_equal(gpu_ctx.ntt(curve, a, log_n, inverse), oracle.ntt(curve, a, log_n, inverse, 8)), (log_n, inverse)
 
