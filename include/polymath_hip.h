@@ -318,6 +318,32 @@ int pm_host_prove_batch(pm_ctx *ctx, const pm_pk *pk, int transcript, size_t cou
                         const uint64_t *x, const uint64_t *w, int assignment_on_device, const uint64_t *r_a,
                         uint8_t *proofs, size_t proof_len, int *status);
 
+/* WHICH constraints an assignment violates: what a caller runs after PM_ERR_REMAINDER_NONZERO (the prover itself only learns that
+ * some row fails).  The answer ark-relations' ConstraintSystem::which_is_unsatisfied gives on the host, for `count` assignments
+ * against ONE unsharded key, from the key's resident matrices.
+ *   x, w      : count x m0 (leading one included) / count x mw Fr, Montgomery, host pointers or (assignment_on_device != 0) device
+ *               pointers, row after row, exactly as pm_host_prove_batch takes them; device arrays are read in place
+ *   n_bad[i]  : count u64, host: the number of constraint rows r < nr with (A z)_r (B z)_r != (C z)_r for assignment i, under the
+ *               first-entry rule the prover applies to a column named twice in a row (common.rs:100-105)
+ *   rows      : count x max_rows u64, host: rows[i * max_rows + j], j < min(n_bad[i], max_rows), are the SMALLEST failing row
+ *               indices of assignment i in ascending order; the slots after them hold UINT64_MAX.  A row index is the
+ *               constraint's position in the matrices the key was made from.  May be NULL only if max_rows == 0 (count only).
+ *   abc       : count x max_rows x 12 u64, host, or NULL (then not computed): (A z)_r, (B z)_r, (C z)_r of the row in the same
+ *               slot of `rows`, 4 Montgomery limbs each; zero for an unused slot
+ * n_bad[i] == 0 exactly when the prover's witness check passes for assignment i: (Az + Bz)^2 = 4 Cz + (Az - Bz)^2 <=> Az Bz = Cz
+ * in odd characteristic, and the public-input rows of the square system hold identically.  The outputs are the same words on
+ * every run (no atomics), whatever the grouping: assignments run in groups of as many as keep group * (m0 + mw) <=
+ * 2^PM_OPT_MSM_MAX_PIECE_LOG (at least one, at most 65 535).
+ * count == 0 is PM_OK and writes nothing.  PM_ERR_INVALID_ARG, nothing computed or written: a sharded key, a key on another
+ * device, a NULL n_bad, a NULL rows with max_rows > 0, a NULL x, a NULL w with mw > 0.  Device memory is taken per call and
+ * returned; the context stays usable and a proof in flight between pm_prove_phase1 and pm_prove_phase3 is not disturbed.
+ * pm_last_timings afterwards: slot 0 the GPU ms of the call's kernels, the other slots zero.
+ * pm_r1cs_check is pm_r1cs_check_batch with count == 1. */
+int pm_r1cs_check(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const uint64_t *w, int assignment_on_device,
+                  size_t max_rows, uint64_t *n_bad, uint64_t *rows, uint64_t *abc);
+int pm_r1cs_check_batch(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *x, const uint64_t *w,
+                        int assignment_on_device, size_t max_rows, uint64_t *n_bad, uint64_t *rows, uint64_t *abc);
+
 /* The same on a SHARDED key (one rank of a multi-GPU proof): `combine` is called between the phases with this
  * rank's partial points -- count = 2 ([a]_1, [c]_1) after phase 1, count = 1 ([d]_1) after phase 3 -- and must
  * replace them, in place, by the sums over all ranks (all-gather over RCCL + pm_g1_sum: SURVEY.md §8e; RCCL has

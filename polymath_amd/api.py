@@ -71,6 +71,7 @@ EXPORTS = [
     "pm_ctx_set_option", "pm_ctx_get_option", "pm_comm_local_set_serialize",
     "pm_g1_decode", "pm_pk_load_bytes", "pm_pk_export_bases_compressed", "pm_verify_batch",
     "pm_verify_batch2", "pm_pairing_check_batch",
+    "pm_r1cs_check", "pm_r1cs_check_batch",
 ]
 # pm_option / pm_tables_mode (include/polymath_hip.h)
 OPTIONS = {"msm_overlap": 0, "ntt_overlap": 1, "tables": 2, "msm_max_piece_log": 3, "max_seg_log": 4, "inflight_contexts": 5,
@@ -121,6 +122,8 @@ def load_library():
     L.pm_pk_info.argtypes = [vp, u64p, u64p, u64p, u64p, u64p]
     L.pm_host_prove.argtypes = [vp, vp, ct.c_int, u64p, ct.c_void_p, ct.c_void_p, ct.c_int, u64p, ct.c_char_p, ct.c_size_t, ct.POINTER(ct.c_size_t)]
     L.pm_host_prove_batch.argtypes = [vp, vp, ct.c_int, sz, u64p, ct.c_void_p, ct.c_void_p, ct.c_int, u64p, ct.c_char_p, sz, intp]
+    L.pm_r1cs_check.argtypes = [vp, vp, ct.c_void_p, ct.c_void_p, ct.c_int, sz, u64p, u64p, u64p]
+    L.pm_r1cs_check_batch.argtypes = [vp, vp, sz, ct.c_void_p, ct.c_void_p, ct.c_int, sz, u64p, u64p, u64p]
     L.pm_host_prove_sharded.argtypes = [vp, vp, ct.c_int, u64p, ct.c_void_p, ct.c_void_p, ct.c_int, u64p, COMBINE_FN, ct.c_void_p, ct.c_char_p,
                                         ct.c_size_t, ct.POINTER(ct.c_size_t)]
     L.pm_pk_msm_plan.argtypes = [vp, ct.c_int, u64p, ct.POINTER(ct.c_uint), ct.POINTER(ct.c_uint), intp]
@@ -762,6 +765,42 @@ class ProvingKey:
         rc = self.ctx.L.pm_host_prove_batch(self.ctx.h, self.h, self.TRANSCRIPT_IDS[transcript], count, _p(inst), px, pw, int(on_device), _p(r_a),
                                             buf, proof_len, status.ctypes.data_as(ct.POINTER(ct.c_int)))
         return rc, buf.raw[:count * proof_len], status[:count]
+
+    def r1cs_check_batch(self, x, w, max_rows=16, residuals=False, on_device=False, count=None):
+        """pm_r1cs_check_batch: which constraint rows each of `count` assignments violates.  x, w: (count, m0, 4) / (count, mw, 4) host
+        limbs, or device pointers (ints) to the same rows with on_device=True and `count` given.  -> (status of the call,
+        np.uint64[count] n_bad, np.uint64[count, max_rows] smallest failing rows ascending (padding 2^64 - 1),
+        np.uint64[count, max_rows, 3, 4] (Az, Bz, Cz) of the listed rows or None)."""
+        if on_device:
+            px, pw = ct.c_void_p(x), ct.c_void_p(w)
+        else:
+            x = _c(x)
+            count = int(x.shape[0]) if x.ndim == 3 else 0
+            w = _c(w) if np.size(w) else np.zeros((max(1, count), 1, 4), dtype=np.uint64)
+            px, pw = x.ctypes.data_as(ct.c_void_p), w.ctypes.data_as(ct.c_void_p)
+        count, max_rows = int(count), int(max_rows)
+        n_bad = np.zeros(count, dtype=np.uint64)
+        rows = np.full((count, max_rows), np.iinfo(np.uint64).max, dtype=np.uint64)
+        abc = np.zeros((count, max_rows, 3, 4), dtype=np.uint64) if residuals else None
+        rc = self.ctx.L.pm_r1cs_check_batch(self.ctx.h, self.h, count, px, pw, int(on_device), max_rows, _p(n_bad) if count else None,
+                                            _p(rows) if rows.size else None, _p(abc) if residuals and abc.size else None)
+        return rc, n_bad, rows, abc
+
+    def r1cs_check(self, x, w, max_rows=16, residuals=False, on_device=False):
+        """pm_r1cs_check: one assignment, x (m0, 4) / w (mw, 4) host limbs or device pointers.  -> (status, n_bad, rows[max_rows], abc or None)."""
+        if on_device:
+            px, pw = ct.c_void_p(x), ct.c_void_p(w)
+        else:
+            x = _c(x)
+            w = _c(w) if np.size(w) else np.zeros((1, 4), dtype=np.uint64)
+            px, pw = x.ctypes.data_as(ct.c_void_p), w.ctypes.data_as(ct.c_void_p)
+        max_rows = int(max_rows)
+        n_bad = np.zeros(1, dtype=np.uint64)
+        rows = np.full(max_rows, np.iinfo(np.uint64).max, dtype=np.uint64)
+        abc = np.zeros((max_rows, 3, 4), dtype=np.uint64) if residuals else None
+        rc = self.ctx.L.pm_r1cs_check(self.ctx.h, self.h, px, pw, int(on_device), max_rows, _p(n_bad), _p(rows) if rows.size else None,
+                                      _p(abc) if residuals and abc.size else None)
+        return rc, int(n_bad[0]), rows, abc
 
     def phase2(self, x1):
         out = np.zeros(4, dtype=np.uint64)

@@ -21,6 +21,19 @@ __device__ __forceinline__ Fp<P> csr_row_dot(const uint64_t *rowptr, const uint3
     return acc;
 }
 
+// the same dot product with z = x || w read from the caller's two arrays in place (r1cs_check.hip): column j < m0 is x[j]
+template <class P>
+__device__ __forceinline__ Fp<P> csr_row_dot(const uint64_t *rowptr, const uint32_t *col, const uint64_t *val,
+                                             const Fp<P> *x, const Fp<P> *w, uint64_t m0, uint64_t r) {
+    Fp<P> acc = Fp<P>::zero();
+    for (uint64_t k = rowptr[r]; k < rowptr[r + 1]; ++k) {
+        Fp<P> v = *(const Fp<P> *)(val + 4 * k);
+        const uint64_t j = col[k];
+        acc = add<P>(acc, mul<P>(v, j < m0 ? x[j] : w[j - m0]));
+    }
+    return acc;
+}
+
 struct CsrDev {
     const uint64_t *rowptr;
     const uint32_t *col;

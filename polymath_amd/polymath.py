@@ -428,6 +428,54 @@ class Polymath:
         plen = len(data) // count if count else 0
         return [data[i * plen:(i + 1) * plen] if status[i] == 0 else None for i in range(count)], [int(s) for s in status]
 
+    # ---- which constraints fail (ark-relations: ConstraintSystem::which_is_unsatisfied): what to call after a status 4
+    def _assignment_limbs(self, c):
+        if isinstance(c, LimbCircuit):
+            x, w = c.inst_limbs, c.wit_limbs
+        elif isinstance(c, tuple) and len(c) == 2:
+            x, w = c
+        else:
+            _, instance, witness = self._synthesize(c)
+            x, w = self.field.fr_limbs(instance), self.field.fr_limbs(witness)
+        return np.asarray(x, dtype=np.uint64).reshape(-1, 4), np.asarray(w, dtype=np.uint64).reshape(-1, 4)
+
+    def _check_result(self, n_bad, rows, abc):
+        listed = [int(r) for r in rows[:min(int(n_bad), len(rows))]]
+        if abc is None:
+            return int(n_bad), listed
+        f = self.field
+        return int(n_bad), listed, [tuple(f.fr_int(abc[j, k]) for k in range(3)) for j in range(len(listed))]
+
+    def check_assignment(self, pk, circuit_or_limbs, max_rows=16, residuals=False, device_ptrs=None):
+        """Which R1CS rows an assignment violates (pm_r1cs_check, on the key's resident matrices).  circuit_or_limbs: a circuit, a
+        LimbCircuit or an (x_limbs, w_limbs) pair; device_ptrs = (d_x, d_w): the assignment is already in HBM (circuit_or_limbs may
+        then be None).  -> (n_bad, rows) or, with residuals, (n_bad, rows, abc): n_bad = the number of rows r with
+        (Az)_r (Bz)_r != (Cz)_r, rows = the min(n_bad, max_rows) smallest of them in ascending order, abc[j] = ((Az)_r, (Bz)_r, (Cz)_r)
+        of rows[j] as canonical ints.  n_bad == 0 exactly when prove / prove_native accept the assignment's witness check."""
+        if device_ptrs is not None:
+            rc, n_bad, rows, abc = pk.r1cs_check(device_ptrs[0], device_ptrs[1], max_rows, residuals, on_device=True)
+        else:
+            x, w = self._assignment_limbs(circuit_or_limbs)
+            rc, n_bad, rows, abc = pk.r1cs_check(x, w, max_rows, residuals)
+        self.ctx.check(rc)
+        return self._check_result(n_bad, rows, abc)
+
+    def check_batch(self, pk, circuits_or_limbs, max_rows=16, residuals=False, device_ptrs=None):
+        """check_assignment for many assignments of one circuit in ONE native call (pm_r1cs_check_batch).  device_ptrs = (d_x, d_w):
+        count x m0 / count x mw rows in HBM, with circuits_or_limbs the count (an int) or a sequence of that length.
+        -> list of check_assignment results."""
+        if device_ptrs is not None:
+            count = circuits_or_limbs if isinstance(circuits_or_limbs, int) else len(circuits_or_limbs)
+            rc, n_bad, rows, abc = pk.r1cs_check_batch(device_ptrs[0], device_ptrs[1], max_rows, residuals, on_device=True, count=count)
+        else:
+            pairs = [self._assignment_limbs(c) for c in circuits_or_limbs]
+            count = len(pairs)
+            x_all = np.stack([p[0] for p in pairs]) if count else np.zeros((0, 0, 4), dtype=np.uint64)
+            w_all = np.stack([p[1] for p in pairs]) if count else np.zeros((0, 0, 4), dtype=np.uint64)
+            rc, n_bad, rows, abc = pk.r1cs_check_batch(x_all, w_all, max_rows, residuals)
+        self.ctx.check(rc)
+        return [self._check_result(n_bad[i], rows[i], None if abc is None else abc[i]) for i in range(count)]
+
     def prove_limbs(self, pk, instance, x_limbs, w_limbs, r_a, combine=None, device_ptrs=None):
         """device_ptrs = (d_x, d_w): the assignment is already resident in HBM (pm_prove_phase1_device)."""
         f, r = self.field, self.field.r

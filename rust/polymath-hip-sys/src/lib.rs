@@ -175,6 +175,8 @@ extern "C" {
     pub fn pm_prove_phase3(ctx: *mut pm_ctx, x1: *const u64, x2: *const u64, a_at_x1: *const u64, c_at_x1: *const u64, d_g1_xy: *mut u64, d_inf: *mut i32) -> i32;
     pub fn pm_host_prove(ctx: *mut pm_ctx, pk: *const pm_pk, transcript: i32, instance_host: *const u64, x: *const u64, w: *const u64, assignment_on_device: i32, r_a: *const u64, proof_bytes: *mut u8, capacity: usize, proof_len: *mut usize) -> i32;
     pub fn pm_host_prove_batch(ctx: *mut pm_ctx, pk: *const pm_pk, transcript: i32, count: usize, instance_host: *const u64, x: *const u64, w: *const u64, assignment_on_device: i32, r_a: *const u64, proofs: *mut u8, proof_len: usize, status: *mut i32) -> i32;
+    pub fn pm_r1cs_check(ctx: *mut pm_ctx, pk: *const pm_pk, x: *const u64, w: *const u64, assignment_on_device: i32, max_rows: usize, n_bad: *mut u64, rows: *mut u64, abc: *mut u64) -> i32;
+    pub fn pm_r1cs_check_batch(ctx: *mut pm_ctx, pk: *const pm_pk, count: usize, x: *const u64, w: *const u64, assignment_on_device: i32, max_rows: usize, n_bad: *mut u64, rows: *mut u64, abc: *mut u64) -> i32;
     pub fn pm_host_prove_sharded(ctx: *mut pm_ctx, pk: *const pm_pk, transcript: i32, instance_host: *const u64, x: *const u64, w: *const u64, assignment_on_device: i32, r_a: *const u64, combine: pm_combine_fn, user: *mut c_void, proof_bytes: *mut u8, capacity: usize, proof_len: *mut usize) -> i32;
     pub fn pm_host_make_vk(curve: i32, n: u64, m0: u64, sigma: u64, omega: *const u64, x_trapdoor: *const u64, z_trapdoor: *const u64, vk_bytes: *mut u8, capacity: usize, vk_len: *mut usize) -> i32;
     pub fn pm_host_verify(curve: i32, transcript: i32, vk_bytes: *const u8, vk_len: usize, public_inputs: *const u64, n_inputs: usize, proof_bytes: *const u8, proof_len: usize, accepted: *mut i32) -> i32;

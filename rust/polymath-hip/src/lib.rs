@@ -756,6 +756,37 @@ impl GpuKey {
             .collect())
     }
 
+    /// `pm_r1cs_check`: which constraints the assignment violates -- what `ConstraintSystem::which_is_unsatisfied` answers on the
+    /// host, from the key's resident matrices; the call to make after a `RemainderNonzero`.  `instance` carries the leading one.
+    /// Returns the number of rows r with (Az)_r (Bz)_r != (Cz)_r and the `min(n_bad, max_rows)` smallest of them in ascending
+    /// order (a row index is the constraint's position in the matrices the key was made from).  The count is zero exactly when
+    /// the prover's witness check passes.  A proof in flight on `ctx` is not disturbed.
+    pub fn check_assignment<E: Pairing>(
+        &self,
+        ctx: &mut Context,
+        instance: &[E::ScalarField],
+        witness: &[E::ScalarField],
+        max_rows: usize,
+    ) -> Result<(u64, Vec<u64>), HipError> {
+        let curve = curve_checked::<E>()?;
+        if curve != self.curve {
+            return Err(err(Status::InvalidArg, "key of another curve"));
+        }
+        if instance.len() as u64 != self.m0 || witness.len() as u64 != self.mw {
+            return Err(err(Status::LenMismatch, "the instance / witness length is not the key's"));
+        }
+        let mut n_bad = 0u64;
+        let mut rows = vec![u64::MAX; max_rows];
+        let w_ptr = if witness.is_empty() { core::ptr::null() } else { fr_ptr(witness) };
+        let rows_ptr = if max_rows == 0 { core::ptr::null_mut() } else { rows.as_mut_ptr() };
+        // SAFETY: live key and context; instance / witness hold m0 / mw elements (layout checked), `rows` has max_rows slots,
+        // the residuals are not asked for.
+        let rc = unsafe { sys::pm_r1cs_check(ctx.raw, self.raw, fr_ptr(instance), w_ptr, 0, max_rows, &mut n_bad, rows_ptr, core::ptr::null_mut()) };
+        ctx.check(rc)?;
+        rows.truncate((n_bad as usize).min(max_rows));
+        Ok((n_bad, rows))
+    }
+
     /// `pm_pk_info`: n, m0, sigma, omega and the six base-vector lengths of this key.
     pub fn info<E: Pairing>(&self) -> Result<KeyInfo<E>, HipError> {
         let curve = curve_checked::<E>()?;
