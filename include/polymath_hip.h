@@ -410,8 +410,20 @@ int pm_verify_batch(pm_ctx *ctx, int curve, int transcript, const uint8_t *vk_by
  *     (host mode: *n_checks <= 1 + 2 f ceil(log2 count)).  Malformed proofs keep PM_VERIFY_MALFORMED and are not checked.
  * Verdicts, *all_accepted, the weights, the meaning of seed32 and every PM_ERR_INVALID_ARG case are the same in both modes; another
  * `pairing` value is PM_ERR_INVALID_ARG.  pm_last_timings: slot 4 is the pairing checks' wall ms wherever they ran (device mode: line
- * tables, launches and copies), slot 5 the GPU ms of the pairing launches (device mode only). */
+ * tables, launches and copies), slot 5 the GPU ms of the pairing launches (device mode only).
+ * `pairing` may be OR-ed with a pm_verify_challenges value, the place of the per-proof challenges (a flag of this argument: the set of
+ * entry points is pinned like the option table).  PM_VERIFY_CHALLENGES_HOST (0) changes nothing, bit for bit.
+ *   PM_VERIFY_CHALLENGES_DEVICE: x1_i, x2_i, c_i(x1_i) (verifier.rs:24-42 with common.rs:21-98: the Fiat-Shamir transcript of
+ *     src/transcript/{merlin,keccak256,blake3}.rs, pi(x1) and c(x1)) come from one lane per proof of ONE launch behind the decode, and
+ *     the lane goes on to rho_i x2_i, rho_i x1_i and g_i: the proofs and inputs go up once; one byte, g_i and the challenges
+ *     (pm_prove_tap, which = 8) come back per proof, and
+ *     the host keeps the weights' key and draws, the merge of malformed points, the prefix sums of g_i and the checks.
+ * The challenges are the same bits in both modes, hence so are verdicts, *all_accepted, the weights and *n_checks for one seed, under
+ * either pairing mode; any other bit in `pairing` is PM_ERR_INVALID_ARG.  pm_last_timings: slot 6 is the GPU ms of the challenge launch
+ * (0 with host challenges); slot 3 stays the host's glue (wall ms), which with device challenges is the weights' key, the draws and
+ * the uploads. */
 typedef enum pm_verify_pairing { PM_VERIFY_PAIRING_HOST = 0, PM_VERIFY_PAIRING_DEVICE = 1 } pm_verify_pairing;
+typedef enum pm_verify_challenges { PM_VERIFY_CHALLENGES_HOST = 0, PM_VERIFY_CHALLENGES_DEVICE = 256 } pm_verify_challenges;
 int pm_verify_batch2(pm_ctx *ctx, int curve, int transcript, const uint8_t *vk_bytes, size_t vk_len, const uint64_t *public_inputs, size_t n_inputs,
                      const uint8_t *proofs, size_t proof_len, size_t count, const uint8_t *seed32, int pairing, uint8_t *verdicts,
                      int *all_accepted, size_t *n_checks);
@@ -504,7 +516,10 @@ int pm_selftest_field(pm_ctx *ctx, size_t products_per_field, uint64_t seed, uin
 
 /* Debug / parity taps: copy an intermediate vector of the proof in flight back to the host.
  * which: 0 u_evals(n) 1 w_evals(n) 2 u coeffs(n) 3 w coeffs(n) 4 h coeffs(n) 5 witness-u coeffs(n)
- *        6 z_tail(M-m0) 7 quotient (10n+23) */
+ *        6 z_tail(M-m0) 7 quotient (10n+23)
+ *        8 (no proof in flight needed) what the last pm_verify_batch2 with PM_VERIFY_CHALLENGES_DEVICE on this context derived, four
+ *          elements a proof: x1, x2, c(x1) (Montgomery) and one whose first word is 1 iff a_at_x1 < r (else the other three are
+ *          zero); the point records were hashed as given, whether or not they decode.  PM_ERR_STATE when there is none. */
 int pm_prove_tap(pm_ctx *ctx, int which, uint64_t *out, size_t max_elems, size_t *n_elems);
 
 #ifdef __cplusplus

@@ -30,10 +30,13 @@ PROOF_BYTES = {PM_BLS12_381: 176, PM_BN254: 128}            # Proof::serialize_c
 # pm_verify_verdict (include/polymath_hip.h): one per proof of pm_verify_batch
 VERIFY_REJECTED, VERIFY_ACCEPTED, VERIFY_MALFORMED = range(3)
 # what pm_last_timings' slots hold after pm_verify_batch (ms: GPU time of the kernels, wall time of the two host parts).  host_pairing is
-# the pairing checks' wall time wherever they ran; pairing_kernels the GPU time of the device mode's launches (0 in host mode)
-VERIFY_TIMING_SLOTS = {"decode": 0, "terms": 1, "tree": 2, "host_glue": 3, "host_pairing": 4, "pairing_kernels": 5, "device_total": 7}
+# the pairing checks' wall time wherever they ran; pairing_kernels the GPU time of the device mode's launches (0 in host mode);
+# challenge_kernel the GPU time of the challenge launch (device challenges; else 0)
+VERIFY_TIMING_SLOTS = {"decode": 0, "terms": 1, "tree": 2, "host_glue": 3, "host_pairing": 4, "pairing_kernels": 5, "challenge_kernel": 6, "device_total": 7}
 # pm_verify_pairing (include/polymath_hip.h): where pm_verify_batch2 runs its pairing checks
 VERIFY_PAIRING = {"host": 0, "device": 1}
+# pm_verify_challenges (include/polymath_hip.h): where the per-proof Fiat-Shamir challenges run; OR-ed into pm_verify_batch2's `pairing`
+VERIFY_CHALLENGES = {"host": 0, "device": 256}
 TIMING_SLOTS = ["witness_map", "ntt", "poly", "msm_sort", "msm_accumulate", "msm_reduce", "msm_total", "phase"]
 
 u64p = ct.POINTER(ct.c_uint64)
@@ -286,11 +289,13 @@ def pairing_check_batch(ctx, curve, g2, g1):
     return out
 
 
-def verify_batch(ctx, curve, transcript, vk_bytes, public_inputs, proofs, seed=None, verdicts=True, pairing="host"):
+def verify_batch(ctx, curve, transcript, vk_bytes, public_inputs, proofs, seed=None, verdicts=True, pairing="host", challenges="host"):
     """pm_verify_batch2: many proofs against one verifying key; the per-proof curve work on the GPU, the pairing checks on the host
     (pairing="host": a handful per valid batch, a bisection otherwise; what pm_verify_batch does) or on the GPU (pairing="device":
     the root in a launch of one lane, every live leaf in one more launch if it fails).  public_inputs: Montgomery limbs [count, n_inputs, 4], WITHOUT the leading one; proofs: a list of
     Proof::serialize_compressed byte strings or one packed buffer; seed: None or 32 bytes mixed into the weights' key.
+    challenges="device": the per-proof Fiat-Shamir challenges and scalar glue on the GPU too (one lane per proof; the same bits, so
+    nothing in the result changes; PM_VERIFY_CHALLENGES_DEVICE OR-ed into the call's `pairing` argument).
     -> (np.uint8[count] of VERIFY_* codes, or None with verdicts=False; all_accepted: bool; n_checks: int)."""
     cid = CURVE_IDS[curve]
     plen = PROOF_BYTES[cid]
@@ -309,10 +314,27 @@ def verify_batch(ctx, curve, transcript, vk_bytes, public_inputs, proofs, seed=N
     out = np.zeros(count, dtype=np.uint8) if verdicts else None
     acc, checks = ct.c_int(0), ct.c_size_t(0)
     ctx.check(ctx.L.pm_verify_batch2(ctx.h, cid, TRANSCRIPT_IDS[transcript], bytes(vk_bytes), len(vk_bytes), _p(pub) if pub.size else None, n_inputs,
-                                     ct.c_void_p(addr), plen, count, bytes(seed) if seed is not None else None, VERIFY_PAIRING[pairing],
+                                     ct.c_void_p(addr), plen, count, bytes(seed) if seed is not None else None,
+                                     VERIFY_PAIRING[pairing] | VERIFY_CHALLENGES[challenges],
                                      out.ctypes.data_as(ct.c_void_p) if verdicts else None, ct.byref(acc), ct.byref(checks)))
     del keep
     return out, bool(acc.value), int(checks.value)
+
+
+def verifier_challenges_batch(ctx, curve, transcript, vk_bytes, public_inputs, proofs):
+    """x1, x2 and c(x1) of every proof as verify_proof derives them (verifier.rs:24-42), computed on the GPU, one lane per proof: a
+    verify_batch call with challenges="device", then pm_prove_tap(8), which holds what that call's lanes derived.  Arguments as
+    verify_batch; the point records are hashed as given, whether or not they decode.  A diagnostic: the batch is verified as well.
+    -> (x1, x2, c_at_x1: np.uint64 [count, 4] Montgomery limbs; ok: np.uint8 [count], 0 where a_at_x1 >= r, that row's outputs zero)."""
+    _, _, _ = verify_batch(ctx, curve, transcript, vk_bytes, public_inputs, proofs, verdicts=False, challenges="device")
+    count = (len(proofs) if isinstance(proofs, (list, tuple)) else _byte_view(proofs)[2] // PROOF_BYTES[CURVE_IDS[curve]])
+    rows = np.zeros((count, 4, 4), dtype=np.uint64)
+    if count:
+        n = ct.c_size_t(0)
+        ctx.check(ctx.L.pm_prove_tap(ctx.h, 8, _p(rows), 4 * count, ct.byref(n)))
+        if n.value != 4 * count:
+            raise PolymathError(8, "pm_prove_tap(8): %d elements for %d proofs" % (n.value, count))
+    return rows[:, 0].copy(), rows[:, 1].copy(), rows[:, 2].copy(), rows[:, 3, 0].astype(np.uint8)
 
 
 def verify_batch_timings(ctx):

@@ -1220,6 +1220,12 @@ extern "C" int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *
 
 extern "C" int pm_prove_tap(pm_ctx *ctx, int which, uint64_t *out, size_t max_elems, size_t *n_elems) {
     if (!ctx || !out || !n_elems) return PM_ERR_INVALID_ARG;
+    if (which == 8) {   // the batch verifier's tap (verify_batch.hip): host memory, no proof in flight needed
+        if (ctx->verify_tap.empty()) return PM_ERR_STATE;
+        *n_elems = ctx->verify_tap.size() / 4;
+        memcpy(out, ctx->verify_tap.data(), std::min(*n_elems, max_elems) * 32);
+        return PM_OK;
+    }
     if (!ctx->pk || ctx->phase < 1) return PM_ERR_STATE;
     PM_TRY(set_device(ctx));
     const pm_pk *pk = ctx->pk;

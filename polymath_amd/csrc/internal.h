@@ -281,6 +281,7 @@ struct pm_ctx {
     // PM_SHARD_VECTOR prover (prove_sharded.hip): transform temporaries, halo coefficients, roots of the cross-rank butterfly
     pm::DevBuf sh_a, sh_b, sh_c, halo, shard_roots;
     pm::ProveBatchWs pb;
+    std::vector<uint64_t> verify_tap;   // pm_prove_tap(8): x1, x2, c(x1), ok of the last batch verified with device challenges, 16 words a proof
     uint64_t shard_roots_n;
     uint32_t shard_roots_N;
     int shard_roots_curve;
@@ -445,6 +446,26 @@ int pairing_prepare(pm_ctx *ctx, const uint32_t *g2, int k, unsigned pairs, Pair
 template <class C>
 int pairing_check_launch(pm_ctx *ctx, const PairingPrepared &prep, const Affine<C> *d_pts, const VerifyTerm<C> *d_terms, const uint32_t *d_neg_g,
                          const uint8_t *d_live, const Affine<C> &G, size_t count, uint8_t *d_is_one, int timing_slot);
+// challenges.hip: the verifier's Fiat-Shamir challenges (transcript.cuh: fs_verifier_challenges), one proof per lane, ONE launch on
+// the context's stream.  Proof i reads its [a]_1 / [c]_1 records at d_a + i a_stride / d_c + i c_stride, the 32 bytes of a(x1) at
+// d_a_at + i a_at_stride and n_inputs Montgomery public inputs at d_inputs + i n_inputs (all strides multiples of 8, the bases
+// 8-byte aligned).  Outputs, each optional (null: not written): x1, x2, c(x1) (Montgomery); ok (0: a(x1) >= r, the row's outputs
+// are zero); and, with d_scalars -- whose rho words the caller has filled -- the batch verifier's record (rho x2, rho x1 canonical)
+// and d_g[i] = rho_i (a(x1) + x2 c(x1)) (Montgomery); a row that is not ok, or one of whose three points the decoder refused
+// (d_point_status: optional, 3 bytes a row), gets an all-zero record and g = 0: no weight, it never enters a sum.
+// GPU ms go to timing_slot.
+struct VerifyScalars;
+struct ChallengeRows {
+    const uint8_t *d_a, *d_c, *d_a_at;
+    size_t a_stride, c_stride, a_at_stride;
+    const uint64_t *d_inputs;
+    size_t n_inputs, count;
+    const uint8_t *d_point_status;
+};
+template <class C>
+int verifier_challenges_launch(pm_ctx *ctx, int transcript, uint64_t n, uint64_t sigma, const Fp<typename C::FrP> &omega, const ChallengeRows &rows,
+                               Fp<typename C::FrP> *d_x1, Fp<typename C::FrP> *d_x2, Fp<typename C::FrP> *d_c_at_x1, uint8_t *d_ok,
+                               VerifyScalars *d_scalars, Fp<typename C::FrP> *d_g, int timing_slot);
 // ProvingKey::serialize_compressed parsed on the host without touching its base points (pk_wire_parse)
 struct WireLayout {
     size_t vk_len = 0;

@@ -49,11 +49,12 @@ void glue_threads(size_t count, F body) {
 }
 
 struct DevBufs {   // the call's device memory: released on every way out
-    DevBuf in, pts, status, scalars, tree, neg_g, live, is_one;
+    DevBuf in, pts, status, scalars, tree, neg_g, live, is_one, a_at, inputs, g, ok, tap;
     PairingPrepared prep;
     ~DevBufs() {
         in.release(); pts.release(); status.release(); scalars.release(); tree.release();
         neg_g.release(); live.release(); is_one.release(); prep.buf.release();
+        a_at.release(); inputs.release(); g.release(); ok.release(); tap.release();
     }
 };
 
@@ -63,7 +64,7 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 
 template <class C, class T>
 int verify_batch_impl(pm_ctx *ctx, int transcript, const uint8_t *vk_bytes, size_t vk_len, const uint64_t *inputs, size_t n_inputs, const uint8_t *proofs,
-                      size_t count, const uint8_t *seed32, int pairing, uint8_t *verdicts, int *all_accepted, size_t *n_checks) {
+                      size_t count, const uint8_t *seed32, int pairing, int challenges, uint8_t *verdicts, int *all_accepted, size_t *n_checks) {
     typedef pmhost::FrOps<C> F;
     typedef typename F::Fr Fr;
     typedef typename C::FrP R;
@@ -124,37 +125,81 @@ int verify_batch_impl(pm_ctx *ctx, int transcript, const uint8_t *vk_bytes, size
         if (!(lo | hi)) lo = 1;
         sc[i].rho[0] = (uint32_t)lo; sc[i].rho[1] = (uint32_t)(lo >> 32); sc[i].rho[2] = (uint32_t)hi; sc[i].rho[3] = (uint32_t)(hi >> 32);
     }
-    glue_threads(count, [&](size_t i) {
-        const uint8_t *p = proofs + i * PL;
-        Fr a_at_x1;
-        try {
-            a_at_x1 = F::from_le_bytes_canonical(p + 2 * NB);
-        } catch (const std::runtime_error &) {
-            bad[i] = 1;
-            return;
-        }
-        std::vector<Fr> pub(n_inputs);
-        if (n_inputs) memcpy((void *)pub.data(), inputs + i * n_inputs * PM_FR_LIMBS, n_inputs * sizeof(Fr));
-        const typename PMath::Challenges ch = PMath::verifier_challenges(vk, pub, p, p + NB, a_at_x1);
-        Fr rho = Fr::zero();
-        memcpy(rho.l, sc[i].rho, 16);
-        rho = to_mont<R>(rho);
-        const Fr rx2 = from_mont<R>(F::mul(rho, ch.x2)), rx1 = from_mont<R>(F::mul(rho, ch.x1));
-        memcpy(sc[i].rx2, rx2.l, 32);
-        memcpy(sc[i].rx1, rx1.l, 32);
-        g[i] = F::mul(rho, F::add(a_at_x1, F::mul(ch.x2, ch.c_at_x1)));
-    });
-    ctx->timing_ms[T_MSM_SORT] = ms_since(t_glue);
+    const bool device_challenges = challenges == PM_VERIFY_CHALLENGES_DEVICE;
     std::vector<uint8_t> st(3 * count);
-    PM_HIP(ctx, hipMemcpyAsync(st.data(), d.status.p, st.size(), hipMemcpyDeviceToHost, ctx->stream));
-    PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (size_t i = 0; i < count; ++i) {
-        if (st[3 * i] | st[3 * i + 1] | st[3 * i + 2]) bad[i] = 1;
-        if (bad[i]) { memset(&sc[i], 0, sizeof(VerifyScalars)); g[i] = Fr::zero(); }   // no weight: never enters a sum
+    if (device_challenges) {
+        // The per-proof transcript and scalar glue as ONE launch behind the decode (challenges.hip): the lanes read [a]_1 and [c]_1
+        // from the packed records the decoder reads, a(x1) and the public inputs from two more uploads -- no byte goes up twice --
+        // and write the scalars where k_verify_terms takes them.  Back come one byte and g_i per proof,
+        // and the three challenges for pm_prove_tap(8).
+        std::vector<uint8_t> a_at(32 * count), ok(count);
+        for (size_t i = 0; i < count; ++i) memcpy(&a_at[32 * i], proofs + i * PL + 2 * NB, 32);
+        const size_t in_bytes = count * n_inputs * sizeof(Fr);
+        PM_HIP(ctx, d.a_at.reserve(a_at.size()));
+        if (in_bytes) PM_HIP(ctx, d.inputs.reserve(in_bytes));
+        PM_HIP(ctx, d.g.reserve(count * sizeof(Fr)));
+        PM_HIP(ctx, d.ok.reserve(count));
+        PM_HIP(ctx, hipMemcpyAsync(d.a_at.p, a_at.data(), a_at.size(), hipMemcpyHostToDevice, ctx->stream));
+        if (in_bytes) PM_HIP(ctx, hipMemcpyAsync(d.inputs.p, inputs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+        PM_HIP(ctx, hipMemcpyAsync(d.scalars.p, sc.data(), count * sizeof(VerifyScalars), hipMemcpyHostToDevice, ctx->stream));   // the weights
+        const uint8_t *in = d.in.as<uint8_t>();
+        const ChallengeRows rows{in, in + NB, d.a_at.as<uint8_t>(), 3 * NB, 3 * NB, 32, d.inputs.as<uint64_t>(), n_inputs, count, d.status.as<uint8_t>()};
+        PM_HIP(ctx, d.tap.reserve(3 * count * sizeof(Fr)));
+        Fr *tap = d.tap.as<Fr>();
+        PM_TRY(verifier_challenges_launch<C>(ctx, transcript, vk.n, vk.sigma, vk.omega, rows, tap, tap + count, tap + 2 * count, d.ok.as<uint8_t>(),
+                                             d.scalars.as<VerifyScalars>(), d.g.as<Fr>(), T_MSM_TOTAL));
+        ctx->timing_ms[T_MSM_SORT] = ms_since(t_glue);
+        std::vector<Fr> tap_host(3 * count);
+        PM_HIP(ctx, hipMemcpyAsync(ok.data(), d.ok.p, count, hipMemcpyDeviceToHost, ctx->stream));
+        PM_HIP(ctx, hipMemcpyAsync((void *)g.data(), d.g.p, count * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+        PM_HIP(ctx, hipMemcpyAsync(st.data(), d.status.p, st.size(), hipMemcpyDeviceToHost, ctx->stream));
+        PM_HIP(ctx, hipMemcpyAsync((void *)tap_host.data(), d.tap.p, 3 * count * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+        PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        // what the lanes derived, kept for pm_prove_tap(8): per proof x1, x2, c(x1) (Montgomery) and a word that is 1 iff a(x1) < r
+        ctx->verify_tap.assign(16 * count, 0);
+        for (size_t i = 0; i < count; ++i) {
+            for (int k = 0; k < 3; ++k) memcpy(&ctx->verify_tap[16 * i + 4 * k], tap_host[k * count + i].l, sizeof(Fr));
+            ctx->verify_tap[16 * i + 12] = ok[i];
+        }
+        // `sc` holds the weights only from here on: the records are the device's (d.scalars), rows without weight zeroed by the lane
+        // the malformed-point merge on the host's side: `bad` and g_i
+        for (size_t i = 0; i < count; ++i) {
+            bad[i] = !ok[i] || (st[3 * i] | st[3 * i + 1] | st[3 * i + 2]);
+            if (bad[i]) g[i] = Fr::zero();
+        }
+    } else {
+        ctx->verify_tap.clear();
+        glue_threads(count, [&](size_t i) {
+            const uint8_t *p = proofs + i * PL;
+            Fr a_at_x1;
+            try {
+                a_at_x1 = F::from_le_bytes_canonical(p + 2 * NB);
+            } catch (const std::runtime_error &) {
+                bad[i] = 1;
+                return;
+            }
+            std::vector<Fr> pub(n_inputs);
+            if (n_inputs) memcpy((void *)pub.data(), inputs + i * n_inputs * PM_FR_LIMBS, n_inputs * sizeof(Fr));
+            const typename PMath::Challenges ch = PMath::verifier_challenges(vk, pub, p, p + NB, a_at_x1);
+            Fr rho = Fr::zero();
+            memcpy(rho.l, sc[i].rho, 16);
+            rho = to_mont<R>(rho);
+            const Fr rx2 = from_mont<R>(F::mul(rho, ch.x2)), rx1 = from_mont<R>(F::mul(rho, ch.x1));
+            memcpy(sc[i].rx2, rx2.l, 32);
+            memcpy(sc[i].rx1, rx1.l, 32);
+            g[i] = F::mul(rho, F::add(a_at_x1, F::mul(ch.x2, ch.c_at_x1)));
+        });
+        ctx->timing_ms[T_MSM_SORT] = ms_since(t_glue);
+        PM_HIP(ctx, hipMemcpyAsync(st.data(), d.status.p, st.size(), hipMemcpyDeviceToHost, ctx->stream));
+        PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (size_t i = 0; i < count; ++i) {
+            if (st[3 * i] | st[3 * i + 1] | st[3 * i + 2]) bad[i] = 1;
+            if (bad[i]) { memset(&sc[i], 0, sizeof(VerifyScalars)); g[i] = Fr::zero(); }   // no weight: never enters a sum
+        }
     }
 
     // ---- device: the terms and their sum tree
-    PM_HIP(ctx, hipMemcpyAsync(d.scalars.p, sc.data(), count * sizeof(VerifyScalars), hipMemcpyHostToDevice, ctx->stream));
+    if (!device_challenges) PM_HIP(ctx, hipMemcpyAsync(d.scalars.p, sc.data(), count * sizeof(VerifyScalars), hipMemcpyHostToDevice, ctx->stream));
     VerifyTerm<C> *tree = d.tree.as<VerifyTerm<C>>();
     {
         StageTimer t(ctx, T_NTT);
@@ -296,11 +341,11 @@ int verify_batch_impl(pm_ctx *ctx, int transcript, const uint8_t *vk_bytes, size
 
 template <class C>
 int verify_batch_curve(pm_ctx *ctx, int transcript, const uint8_t *vk, size_t vk_len, const uint64_t *in, size_t n_in, const uint8_t *proofs, size_t count,
-                       const uint8_t *seed, int pairing, uint8_t *verdicts, int *all, size_t *nc) {
+                       const uint8_t *seed, int pairing, int challenges, uint8_t *verdicts, int *all, size_t *nc) {
     switch (transcript) {
-        case PM_TRANSCRIPT_MERLIN: return verify_batch_impl<C, pmhost::MerlinFieldTranscript<C>>(ctx, transcript, vk, vk_len, in, n_in, proofs, count, seed, pairing, verdicts, all, nc);
-        case PM_TRANSCRIPT_KECCAK256: return verify_batch_impl<C, pmhost::Keccak256Transcript<C>>(ctx, transcript, vk, vk_len, in, n_in, proofs, count, seed, pairing, verdicts, all, nc);
-        case PM_TRANSCRIPT_BLAKE3: return verify_batch_impl<C, pmhost::Blake3Transcript<C>>(ctx, transcript, vk, vk_len, in, n_in, proofs, count, seed, pairing, verdicts, all, nc);
+        case PM_TRANSCRIPT_MERLIN: return verify_batch_impl<C, pmhost::MerlinFieldTranscript<C>>(ctx, transcript, vk, vk_len, in, n_in, proofs, count, seed, pairing, challenges, verdicts, all, nc);
+        case PM_TRANSCRIPT_KECCAK256: return verify_batch_impl<C, pmhost::Keccak256Transcript<C>>(ctx, transcript, vk, vk_len, in, n_in, proofs, count, seed, pairing, challenges, verdicts, all, nc);
+        case PM_TRANSCRIPT_BLAKE3: return verify_batch_impl<C, pmhost::Blake3Transcript<C>>(ctx, transcript, vk, vk_len, in, n_in, proofs, count, seed, pairing, challenges, verdicts, all, nc);
         default: return PM_ERR_INVALID_ARG;
     }
 }
@@ -310,6 +355,9 @@ int verify_batch_curve(pm_ctx *ctx, int transcript, const uint8_t *vk, size_t vk
 extern "C" int pm_verify_batch2(pm_ctx *ctx, int curve, int transcript, const uint8_t *vk_bytes, size_t vk_len, const uint64_t *public_inputs, size_t n_inputs,
                                 const uint8_t *proofs, size_t proof_len, size_t count, const uint8_t *seed32, int pairing, uint8_t *verdicts,
                                 int *all_accepted, size_t *n_checks) {
+    // `pairing` is a pm_verify_pairing value, optionally OR-ed with PM_VERIFY_CHALLENGES_DEVICE
+    const int challenges = pairing & PM_VERIFY_CHALLENGES_DEVICE;
+    pairing &= ~PM_VERIFY_CHALLENGES_DEVICE;
     if (pairing != PM_VERIFY_PAIRING_HOST && pairing != PM_VERIFY_PAIRING_DEVICE) return PM_ERR_INVALID_ARG;
     if (!ctx || !vk_bytes || !all_accepted || (count && (!proofs || (n_inputs && !public_inputs)))) return PM_ERR_INVALID_ARG;
     if (curve != PM_BLS12_381 && curve != PM_BN254) return PM_ERR_INVALID_ARG;
@@ -328,8 +376,8 @@ extern "C" int pm_verify_batch2(pm_ctx *ctx, int curve, int transcript, const ui
         }
         if (hipSetDevice(ctx->device) != hipSuccess) return PM_ERR_HIP;
         return curve == PM_BLS12_381
-                   ? verify_batch_curve<BlsCurve>(ctx, transcript, vk_bytes, vk_len, public_inputs, n_inputs, proofs, count, seed32, pairing, verdicts, all_accepted, n_checks)
-                   : verify_batch_curve<BnCurve>(ctx, transcript, vk_bytes, vk_len, public_inputs, n_inputs, proofs, count, seed32, pairing, verdicts, all_accepted, n_checks);
+                   ? verify_batch_curve<BlsCurve>(ctx, transcript, vk_bytes, vk_len, public_inputs, n_inputs, proofs, count, seed32, pairing, challenges, verdicts, all_accepted, n_checks)
+                   : verify_batch_curve<BnCurve>(ctx, transcript, vk_bytes, vk_len, public_inputs, n_inputs, proofs, count, seed32, pairing, challenges, verdicts, all_accepted, n_checks);
     } catch (const pmhost::WireError &) {               // malformed vk bytes
         return PM_ERR_INVALID_ARG;
     } catch (const std::bad_alloc &) {

@@ -533,9 +533,10 @@ class Polymath:
         pb = proof.to_bytes() if isinstance(proof, Proof) else bytes(proof)
         return api.verify(self.curve, self.transcript_name, vk_bytes, self.field.fr_limbs(list(public_inputs)), pb)
 
-    def verify_batch(self, vk_bytes, list_of_inputs, list_of_proofs, seed=None, pairing="host"):
+    def verify_batch(self, vk_bytes, list_of_inputs, list_of_proofs, seed=None, pairing="host", challenges="host"):
         """Many proofs against one key (pm_verify_batch2: the per-proof curve work on the GPU, the pairing checks on the host or,
-        pairing="device", one lane per check on the GPU: all verdicts of a failing batch from one launch).
+        pairing="device", one lane per check on the GPU: all verdicts of a failing batch from one launch; challenges="device": the
+        per-proof Fiat-Shamir challenges and scalar glue on the GPU as well, one lane per proof, same bits).
         list_of_inputs[i]: proof i's public inputs WITHOUT the leading one; list_of_proofs[i]: a Proof or its bytes.
         -> (verdicts np.uint8[count] of api.VERIFY_* codes, all_accepted, n_checks)."""
         if self.transcript_name is None:
@@ -544,7 +545,7 @@ class Polymath:
             raise ValueError("one list of public inputs per proof")
         pbs = [p.to_bytes() if isinstance(p, Proof) else bytes(p) for p in list_of_proofs]
         pub = np.stack([self.field.fr_limbs(list(x)) for x in list_of_inputs]) if pbs else np.zeros((0, 0, 4), dtype=np.uint64)
-        return api.verify_batch(self.ctx, self.curve, self.transcript_name, vk_bytes, pub, pbs, seed=seed, pairing=pairing)
+        return api.verify_batch(self.ctx, self.curve, self.transcript_name, vk_bytes, pub, pbs, seed=seed, pairing=pairing, challenges=challenges)
 
     # ---- ProvingKey wire format (§8 f-4)
     def pk_to_bytes(self, pk, r1cs, vk):

@@ -360,6 +360,16 @@ impl Context {
     /// number of checks is then 1 + the number of proofs that are not [`Verdict::Malformed`].
     pub fn verify_batch_device_pairing(&mut self, curve: Curve, transcript: i32, vk_bytes: &[u8], public_inputs: &[u64], n_inputs: usize,
                                        proofs: &[u8], seed: Option<&[u8; 32]>) -> Result<(Vec<Verdict>, usize), HipError> {
+        self.verify_batch_with(curve, transcript, vk_bytes, public_inputs, n_inputs, proofs, seed, sys::PM_VERIFY_PAIRING_DEVICE,
+                               sys::PM_VERIFY_CHALLENGES_HOST)
+    }
+
+    /// [`Context::verify_batch`] with both modes chosen (`pm_verify_batch2`): `pairing` a `sys::PM_VERIFY_PAIRING_*`, `challenges` a
+    /// `sys::PM_VERIFY_CHALLENGES_*` value, OR-ed into the call's `pairing` argument.  With `PM_VERIFY_CHALLENGES_DEVICE` the per-proof Fiat-Shamir challenges and scalar glue
+    /// run on the GPU too, one lane per proof; the challenges are the same bits, so verdicts and the number of checks do not change.
+    #[allow(clippy::too_many_arguments)]
+    pub fn verify_batch_with(&mut self, curve: Curve, transcript: i32, vk_bytes: &[u8], public_inputs: &[u64], n_inputs: usize, proofs: &[u8],
+                             seed: Option<&[u8; 32]>, pairing: i32, challenges: i32) -> Result<(Vec<Verdict>, usize), HipError> {
         let proof_len = match curve {
             Curve::Bls12_381 => 176,
             Curve::Bn254 => 128,
@@ -373,11 +383,27 @@ impl Context {
         // SAFETY: live context; every pointer covers the length passed with it, `raw` holds `count` bytes, the seed is 32 bytes or null.
         let rc = unsafe {
             sys::pm_verify_batch2(self.raw, curve.id(), transcript, vk_bytes.as_ptr(), vk_bytes.len(), public_inputs.as_ptr(), n_inputs, proofs.as_ptr(),
-                                  proof_len, count, seed.map_or(core::ptr::null(), |s| s.as_ptr()), sys::PM_VERIFY_PAIRING_DEVICE, raw.as_mut_ptr(),
-                                  &mut all, &mut checks)
+                                  proof_len, count, seed.map_or(core::ptr::null(), |s| s.as_ptr()), pairing | challenges, raw.as_mut_ptr(), &mut all,
+                                  &mut checks)
         };
         self.check(rc)?;
         Ok((raw.into_iter().map(Verdict::from_raw).collect(), checks))
+    }
+
+    /// What the lanes of the last [`Context::verify_batch_with`] call with `PM_VERIFY_CHALLENGES_DEVICE` derived (`pm_prove_tap(8)`):
+    /// per proof `x1`, `x2`, `c(x1)` as Montgomery limbs and whether `a_at_x1` was canonical (if not, the three are zero).
+    #[allow(clippy::type_complexity)]
+    pub fn last_verifier_challenges(&mut self, count: usize) -> Result<Vec<([u64; 4], [u64; 4], [u64; 4], bool)>, HipError> {
+        let mut raw = vec![0u64; 16 * count];
+        let mut n = 0usize;
+        // SAFETY: live context; `raw` holds 4 * count elements of 4 limbs.
+        let rc = unsafe { sys::pm_prove_tap(self.raw, 8, raw.as_mut_ptr(), 4 * count, &mut n) };
+        self.check(rc)?;
+        if n != 4 * count {
+            return Err(err(Status::InvalidArg, "last_verifier_challenges: the last batch had another count"));
+        }
+        let limbs = |i: usize| [raw[i], raw[i + 1], raw[i + 2], raw[i + 3]];
+        Ok((0..count).map(|r| (limbs(16 * r), limbs(16 * r + 4), limbs(16 * r + 8), raw[16 * r + 12] != 0)).collect())
     }
 
     /// `pm_pairing_check_batch`: `g1.len() / (k * 2 * fq_limbs)` checks `prod_j e(g1[i][j], g2[j]) == 1` against `k <= 4` fixed G2

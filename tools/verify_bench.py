@@ -1,11 +1,14 @@
 """Batch verification against single verification (DESIGN.md "Batch verification"; profiles/verify_batch.txt).
 
     python tools/verify_bench.py --count 1024 [--bad 8] [--curve bls12_381] [--distinct 64] [--pairing host|device]
+                                 [--challenges host|device] [--alternate ROUNDS]
 
 Makes proofs of circuits.MiMCDemo (16 rounds) on one key -- `--distinct` of them with their own witness and r_a, tiled up to
 `--count` -- and times (a) verify_batch, (b) the same with verdicts=False, (c) pm_host_verify on 4 of the proofs (mean) and,
 with --bad F, (d) the batch with F proofs tampered (a_at_x1 + 1, spread evenly): the bisection (--pairing host) or the one launch
-over all leaves (--pairing device).  Prints ONE JSON line; the kernel times are pm_last_timings' (HIP events inside the call)."""
+over all leaves (--pairing device).  --challenges picks where the per-proof Fiat-Shamir challenges run (PM_VERIFY_CHALLENGES_DEVICE); with
+--alternate N the valid batch is also verified N more times in each mode, host and device taking turns in this one process, and
+"alternate" lists per call the wall time, slot 3 (host glue, wall ms) and slot 6 (challenge kernel, GPU ms).  Prints ONE JSON line; the kernel times are pm_last_timings' (HIP events inside the call)."""
 import argparse
 import json
 import os
@@ -24,6 +27,8 @@ def main():
     ap.add_argument("--curve", default="bls12_381")
     ap.add_argument("--distinct", type=int, default=64)
     ap.add_argument("--pairing", choices=("host", "device"), default="host")
+    ap.add_argument("--challenges", choices=("host", "device"), default="host")
+    ap.add_argument("--alternate", type=int, default=0)
     a = ap.parse_args()
     from polymath_amd import api, circuits as PC, rng as R
     from polymath_amd.polymath import Polymath
@@ -42,15 +47,17 @@ def main():
     pub = np.stack([x for x, _ in items])
     proofs = [p for _, p in items]
 
-    def timed(proofs, **kw):
+    def timed(proofs, challenges=a.challenges, **kw):
         t0 = time.perf_counter()
-        v, ok, checks = api.verify_batch(pm.ctx, a.curve, "merlin", vk, pub, b"".join(proofs), pairing=a.pairing, **kw)
+        v, ok, checks = api.verify_batch(pm.ctx, a.curve, "merlin", vk, pub, b"".join(proofs), pairing=a.pairing, challenges=challenges, **kw)
         wall = (time.perf_counter() - t0) * 1e3
         return dict(wall_ms=round(wall, 3), all_accepted=ok, n_checks=checks, rejected=int((v == 0).sum()) if v is not None else None,
                     **{k + "_ms": round(x, 3) for k, x in api.verify_batch_timings(pm.ctx).items()})
 
     timed(proofs[:2])                                  # first launch: code objects
-    out = dict(curve=a.curve, pairing=a.pairing, count=a.count, distinct=len(made), gates=pk.n)
+    if a.alternate and a.challenges != "device":
+        timed(proofs[:2], challenges="device")       # the other mode's code object, only when that mode is timed
+    out = dict(curve=a.curve, pairing=a.pairing, challenges=a.challenges, count=a.count, distinct=len(made), gates=pk.n)
     out["batch"] = timed(proofs)
     out["batch_no_verdicts"] = timed(proofs, verdicts=False)
     t0 = time.perf_counter()
@@ -68,6 +75,14 @@ def main():
             v = (int.from_bytes(p[2 * g1:2 * g1 + 32], "little") + 1) % r
             tampered[i] = p[:2 * g1] + v.to_bytes(32, "little") + p[2 * g1 + 32:]
         out["descent"] = dict(bad=a.bad, **timed(tampered))
+    if a.alternate:
+        out["alternate"] = []
+        for _ in range(a.alternate):
+            for mode in ("host", "device"):
+                t = timed(proofs, challenges=mode)
+                assert t["all_accepted"] and t["n_checks"] == 1
+                out["alternate"].append(dict(challenges=mode, wall_ms=t["wall_ms"], slot3_host_glue_ms=t["host_glue_ms"],
+                                             slot6_challenge_kernel_ms=t["challenge_kernel_ms"]))
     print(json.dumps(out))
 
 
