@@ -283,6 +283,41 @@ int pm_prove_phase2(pm_ctx *ctx, const uint64_t *x1, uint64_t *u_at_x1);
 int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const uint64_t *a_at_x1,
                     const uint64_t *c_at_x1, uint64_t *d_g1_xy, int *d_inf);
 
+/* ---- partial assignments: flags of the `assignment_on_device` argument -----------------------------------------------------
+ * pm_host_prove, pm_host_prove_batch, pm_r1cs_check and pm_r1cs_check_batch read `assignment_on_device` as a flag word (flags of an
+ * existing argument: the set of entry points and the option table are pinned).  0 and 1 mean what they always meant; a bit outside
+ * the two below is PM_ERR_INVALID_ARG.  The other entry points with such an argument (pm_host_prove_sharded, the phases) do not solve.
+ *   PM_ASSIGNMENT_SOLVE: the caller supplies only the values it chooses; every Fr of x or w whose four words are UINT64_MAX (>= r on
+ *     both curves, so never a field element) is UNKNOWN and is computed on the device first, by forward propagation through the key's
+ *     resident constraint rows (first-entry rule applied, as the prover and pm_r1cs_check read them; a stored entry with a zero
+ *     coefficient names no variable).  The call then runs on the completed assignment and its results are, bit for bit, those of the
+ *     same call without the flag on that assignment.  instance_host of the prove calls uses the same marker: unknown public inputs are
+ *     replaced by the solved values before they are hashed.  Without the flag nothing looks for markers.  The caller's arrays are
+ *     never written, on host or device: the completed assignment lives in memory of the context.
+ *   The rule.  Rows are visited once, in matrix order.  At row r, among the non-zero entries of A_r, B_r, C_r:
+ *     no unknown column                       -- a check row, skipped
+ *     one unknown u, in exactly one of them   -- z_u = (Az Bz - C_rest) / coef   (u in C)
+ *                                                z_u = (Cz / Bz - A_rest) / coef (u in A; u in B alike with Az), and u is known from here on
+ *     anything else                           -- two or more unknowns, or one unknown in two of the three (b (1 - b) = 0): unsolvable
+ *   PM_ERR_INVALID_ARG, pm_last_error naming the row or column, nothing computed and no output written: an unsolvable row, a marked
+ *   column that no row determines, a marker at column 0, a sharded key, and -- in a batch -- an assignment that does not mark the
+ *   columns assignment 0 marks (the first differing (assignment, column) is named; a kernel compares them).
+ *   At run time a step that would divide by zero (Bz = 0 with u in A) leaves that assignment STUCK, even where Cz = 0 too (the value
+ *   is then undetermined): its other solved values are undefined, its neighbours are not affected, and its smallest stuck row is
+ *   reported (a 64-bit atomic minimum: the same word on every run, since everything downstream of a stuck row has a larger index):
+ *     pm_r1cs_check[_batch]   n_bad[i] = UINT64_MAX, rows[i][0] = the stuck row (max_rows > 0), the other slots UINT64_MAX, abc zero
+ *     pm_host_prove_batch     status[i] = PM_ERR_INVALID_ARG, zeroed bytes
+ *     pm_host_prove           returns PM_ERR_INVALID_ARG
+ *   Assignments are solved in the groups the call runs in anyway; the results are the same words under every grouping.  The solving
+ *   plan (steps, dependency levels, launch schedule, inverses of the coefficients) is kept by the context for ONE (key, pattern) and
+ *   rebuilt when either differs; it is freed with the context.  pm_prove_tap 9 and 10 read the results back.
+ *   pm_last_timings: after a check call slot 1 holds the GPU ms of the solve kernels (slot 0: the check kernels, as without the flag);
+ *   in the prove calls they are added to slot 0, which carries the witness map. */
+typedef enum pm_assignment_flags {
+    PM_ASSIGNMENT_DEVICE = 1,   /* x, w are device pointers (what "non-zero" has meant) */
+    PM_ASSIGNMENT_SOLVE = 2     /* entries equal to the unknown marker are solved first */
+} pm_assignment_flags;
+
 /* Whole create_proof_with_assignment (prover.rs:66-237) for an UNSHARDED key, transcript included: the three
  * phases above plus the host glue between them (compute_x1 / compute_x2, common.rs:21-71; pi and c at x1,
  * :73-98; transcript = pm_transcript), run by the library's own C++ mirror of that glue.  For hosts without a
@@ -519,7 +554,15 @@ int pm_selftest_field(pm_ctx *ctx, size_t products_per_field, uint64_t seed, uin
  *        6 z_tail(M-m0) 7 quotient (10n+23)
  *        8 (no proof in flight needed) what the last pm_verify_batch2 with PM_VERIFY_CHALLENGES_DEVICE on this context derived, four
  *          elements a proof: x1, x2, c(x1) (Montgomery) and one whose first word is 1 iff a_at_x1 < r (else the other three are
- *          zero); the point records were hashed as given, whether or not they decode.  PM_ERR_STATE when there is none. */
+ *          zero); the point records were hashed as given, whether or not they decode.  PM_ERR_STATE when there is none.
+ *        9 (no proof in flight needed) the last call with PM_ASSIGNMENT_SOLVE on this context, 1 + m0 elements per assignment, for all
+ *          `count` of them: one whose first word is the assignment's stuck row, UINT64_MAX if it completed, then the m0 completed
+ *          instance values (Montgomery; zeros if stuck).  Host memory.  PM_ERR_STATE when there was no such call.
+ *       10 (no proof in flight needed) the last pm_r1cs_check[_batch] with PM_ASSIGNMENT_SOLVE: count x (m0 + mw) elements, the completed
+ *          x || w rows, assignment after assignment (a stuck one's row is undefined).  PM_ERR_STATE if the last call with the flag was a
+ *          prove call (its groups reuse the prover's workspace) or there was none.  The rows stay in a device buffer of the context,
+ *          count * (m0 + mw) * 32 bytes, KEPT until the next call with the flag reuses it or pm_ctx_destroy frees it: after one large
+ *          batch that memory stays with the context (use a context of its own for large batches and destroy it). */
 int pm_prove_tap(pm_ctx *ctx, int which, uint64_t *out, size_t max_elems, size_t *n_elems);
 
 #ifdef __cplusplus

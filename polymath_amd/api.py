@@ -37,6 +37,10 @@ VERIFY_TIMING_SLOTS = {"decode": 0, "terms": 1, "tree": 2, "host_glue": 3, "host
 VERIFY_PAIRING = {"host": 0, "device": 1}
 # pm_verify_challenges (include/polymath_hip.h): where the per-proof Fiat-Shamir challenges run; OR-ed into pm_verify_batch2's `pairing`
 VERIFY_CHALLENGES = {"host": 0, "device": 256}
+# pm_assignment_flags (include/polymath_hip.h): the `assignment_on_device` argument of the check and host-prove calls is a flag word
+ASSIGNMENT_DEVICE, ASSIGNMENT_SOLVE = 1, 2
+UNKNOWN_LIMBS = (0xFFFFFFFFFFFFFFFF,) * 4     # an Fr of x / w / instance_host with these words is unknown under ASSIGNMENT_SOLVE
+NOT_STUCK = 0xFFFFFFFFFFFFFFFF                # first word of a tap-9 record of an assignment that completed
 TIMING_SLOTS = ["witness_map", "ntt", "poly", "msm_sort", "msm_accumulate", "msm_reduce", "msm_total", "phase"]
 
 u64p = ct.POINTER(ct.c_uint64)
@@ -475,9 +479,13 @@ class Context:
         except Exception:
             pass
 
+    def last_error(self):
+        """pm_last_error: the message of the context's last failing call (the row or column a solving call refused, ...)."""
+        return self.L.pm_last_error(self.h).decode()
+
     def check(self, st):
         if st:
-            raise PolymathError(st, self.L.pm_last_error(self.h).decode())
+            raise PolymathError(st, self.last_error())
 
     def set_comm(self, comm):
         """Join this context to its rank's communicator (needed by PM_SHARD_VECTOR keys)."""
@@ -734,13 +742,27 @@ class ProvingKey:
 
     TRANSCRIPT_IDS = {"merlin": 0, "keccak256": 1, "blake3": 2}
 
-    def host_prove(self, transcript, instance_limbs, x, w, r_a, on_device=False, combine_many=None):
+    def host_prove(self, transcript, instance_limbs, x, w, r_a, on_device=False, combine_many=None, solve=False):
         """pm_host_prove / pm_host_prove_sharded: all three phases and the Fiat-Shamir glue in one native call.
         x, w: numpy limb arrays, or device pointers (ints) with on_device=True.  combine_many (sharded keys):
         [(xy, inf), ...] -> the same list summed over all ranks (polymath_amd.distributed.PointCombiner.many).
+        solve (unsharded keys, pm_host_prove with PM_ASSIGNMENT_SOLVE): entries equal to UNKNOWN_LIMBS are computed on the device first;
+        solve_results() then returns the completed public inputs.
         -> (status, proof bytes)."""
         buf = ct.create_string_buffer(256)
         n = ct.c_size_t(0)
+        if solve:
+            if combine_many is not None:
+                raise ValueError("solve needs an unsharded key")
+            if on_device:
+                px, pw = ct.c_void_p(x), ct.c_void_p(w)
+            else:
+                x = _c(x)
+                w = _c(w) if len(w) else np.zeros((1, 4), dtype=np.uint64)
+                px, pw = x.ctypes.data_as(ct.c_void_p), w.ctypes.data_as(ct.c_void_p)
+            rc = self.ctx.L.pm_host_prove(self.ctx.h, self.h, self.TRANSCRIPT_IDS[transcript], _p(_c(instance_limbs)), px, pw,
+                                          int(bool(on_device)) | ASSIGNMENT_SOLVE, _p(_c(r_a)), buf, len(buf), ct.byref(n))
+            return rc, buf.raw[:n.value]
         words = 2 * self.nq
         failure = []
 
@@ -768,10 +790,12 @@ class ProvingKey:
             raise failure[0]
         return rc, buf.raw[:n.value]
 
-    def host_prove_batch(self, transcript, instance_limbs, x, w, r_a, on_device=False):
+    def host_prove_batch(self, transcript, instance_limbs, x, w, r_a, on_device=False, solve=False):
         """pm_host_prove_batch: `count` proofs against this (unsharded) key in one native call.  instance_limbs: (count, m0, 4) host
         limbs (hashed); x, w: (count, m0, 4) / (count, mw, 4) host limbs, or device pointers (ints) to the same rows with
-        on_device=True; r_a: (count, 2, 4).  -> (status of the call, bytes of count * proof_len, np.int32[count] per-proof statuses)."""
+        on_device=True; r_a: (count, 2, 4).  solve: PM_ASSIGNMENT_SOLVE, entries equal to UNKNOWN_LIMBS (instance_limbs included) are computed
+        on the device first; solve_results() then returns the completed public inputs.
+        -> (status of the call, bytes of count * proof_len, np.int32[count] per-proof statuses)."""
         inst = _c(instance_limbs)
         count = int(inst.shape[0]) if inst.ndim == 3 else 0
         proof_len = 3 * 8 * self.nq + 32
@@ -784,15 +808,17 @@ class ProvingKey:
             x = _c(x)
             w = _c(w) if np.size(w) else np.zeros((max(1, count), 1, 4), dtype=np.uint64)
             px, pw = x.ctypes.data_as(ct.c_void_p), w.ctypes.data_as(ct.c_void_p)
-        rc = self.ctx.L.pm_host_prove_batch(self.ctx.h, self.h, self.TRANSCRIPT_IDS[transcript], count, _p(inst), px, pw, int(on_device), _p(r_a),
+        rc = self.ctx.L.pm_host_prove_batch(self.ctx.h, self.h, self.TRANSCRIPT_IDS[transcript], count, _p(inst), px, pw, int(bool(on_device)) | (ASSIGNMENT_SOLVE if solve else 0), _p(r_a),
                                             buf, proof_len, status.ctypes.data_as(ct.POINTER(ct.c_int)))
         return rc, buf.raw[:count * proof_len], status[:count]
 
-    def r1cs_check_batch(self, x, w, max_rows=16, residuals=False, on_device=False, count=None):
+    def r1cs_check_batch(self, x, w, max_rows=16, residuals=False, on_device=False, count=None, solve=False):
         """pm_r1cs_check_batch: which constraint rows each of `count` assignments violates.  x, w: (count, m0, 4) / (count, mw, 4) host
         limbs, or device pointers (ints) to the same rows with on_device=True and `count` given.  -> (status of the call,
         np.uint64[count] n_bad, np.uint64[count, max_rows] smallest failing rows ascending (padding 2^64 - 1),
-        np.uint64[count, max_rows, 3, 4] (Az, Bz, Cz) of the listed rows or None)."""
+        np.uint64[count, max_rows, 3, 4] (Az, Bz, Cz) of the listed rows or None).  solve: PM_ASSIGNMENT_SOLVE, entries equal to
+        UNKNOWN_LIMBS are computed on the device first (a stuck assignment: n_bad = 2^64 - 1, rows[0] = its stuck row);
+        solve_results() / solved_assignments() read the completed values back."""
         if on_device:
             px, pw = ct.c_void_p(x), ct.c_void_p(w)
         else:
@@ -804,12 +830,13 @@ class ProvingKey:
         n_bad = np.zeros(count, dtype=np.uint64)
         rows = np.full((count, max_rows), np.iinfo(np.uint64).max, dtype=np.uint64)
         abc = np.zeros((count, max_rows, 3, 4), dtype=np.uint64) if residuals else None
-        rc = self.ctx.L.pm_r1cs_check_batch(self.ctx.h, self.h, count, px, pw, int(on_device), max_rows, _p(n_bad) if count else None,
+        rc = self.ctx.L.pm_r1cs_check_batch(self.ctx.h, self.h, count, px, pw, int(bool(on_device)) | (ASSIGNMENT_SOLVE if solve else 0), max_rows, _p(n_bad) if count else None,
                                             _p(rows) if rows.size else None, _p(abc) if residuals and abc.size else None)
         return rc, n_bad, rows, abc
 
-    def r1cs_check(self, x, w, max_rows=16, residuals=False, on_device=False):
-        """pm_r1cs_check: one assignment, x (m0, 4) / w (mw, 4) host limbs or device pointers.  -> (status, n_bad, rows[max_rows], abc or None)."""
+    def r1cs_check(self, x, w, max_rows=16, residuals=False, on_device=False, solve=False):
+        """pm_r1cs_check: one assignment, x (m0, 4) / w (mw, 4) host limbs or device pointers; solve as in r1cs_check_batch.
+        -> (status, n_bad, rows[max_rows], abc or None)."""
         if on_device:
             px, pw = ct.c_void_p(x), ct.c_void_p(w)
         else:
@@ -820,7 +847,7 @@ class ProvingKey:
         n_bad = np.zeros(1, dtype=np.uint64)
         rows = np.full(max_rows, np.iinfo(np.uint64).max, dtype=np.uint64)
         abc = np.zeros((max_rows, 3, 4), dtype=np.uint64) if residuals else None
-        rc = self.ctx.L.pm_r1cs_check(self.ctx.h, self.h, px, pw, int(on_device), max_rows, _p(n_bad), _p(rows) if rows.size else None,
+        rc = self.ctx.L.pm_r1cs_check(self.ctx.h, self.h, px, pw, int(bool(on_device)) | (ASSIGNMENT_SOLVE if solve else 0), max_rows, _p(n_bad), _p(rows) if rows.size else None,
                                       _p(abc) if residuals and abc.size else None)
         return rc, int(n_bad[0]), rows, abc
 
@@ -840,6 +867,17 @@ class ProvingKey:
         n = ct.c_size_t(0)
         self.ctx.check(self.ctx.L.pm_prove_tap(self.ctx.h, which, _p(out), max_elems, ct.byref(n)))
         return out[:min(n.value, max_elems)]
+
+    def solve_results(self, count):
+        """pm_prove_tap(9) after a call with solve=True over `count` assignments on this key's context
+        -> (np.uint64[count] stuck row or NOT_STUCK, np.uint64[count, m0, 4] completed public inputs, Montgomery limbs, zeros where stuck)."""
+        rec = self.tap(9, count * (1 + self.m0)).reshape(count, 1 + self.m0, 4)
+        return rec[:, 0, 0].copy(), rec[:, 1:, :].copy()
+
+    def solved_assignments(self, count, mw):
+        """pm_prove_tap(10) after r1cs_check[_batch](solve=True) over `count` assignments -> np.uint64[count, m0 + mw, 4], the completed
+        x || w rows (a stuck assignment's row is undefined)."""
+        return self.tap(10, count * (self.m0 + mw)).reshape(count, self.m0 + mw, 4)
 
     def free(self):
         if self.h and not getattr(self, "_view", False):

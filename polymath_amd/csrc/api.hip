@@ -121,6 +121,13 @@ extern "C" int pm_ctx_get_option(const pm_ctx *ctx, int option, long long *value
     return PM_OK;
 }
 
+namespace pm {
+uint64_t pk_serial_next() {
+    static std::atomic<uint64_t> next{0};
+    return ++next;
+}
+}  // namespace pm
+
 extern "C" int pm_ctx_create(int device, pm_ctx **out) {
     if (!out) return PM_ERR_INVALID_ARG;
     *out = nullptr;
@@ -171,6 +178,7 @@ extern "C" void pm_ctx_destroy(pm_ctx *ctx) {
         b->release();
     for (auto &b : ctx->lvl) b.release();
     ctx->pb.release();
+    ctx->sv.release();
     for (auto &b : ctx->fb_table) b.release();
     for (auto &t : ctx->tw) { t.fwd.release(); t.inv.release(); t.fwd_int.release(); t.inv_int.release(); }
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
@@ -1224,6 +1232,20 @@ extern "C" int pm_prove_tap(pm_ctx *ctx, int which, uint64_t *out, size_t max_el
         if (ctx->verify_tap.empty()) return PM_ERR_STATE;
         *n_elems = ctx->verify_tap.size() / 4;
         memcpy(out, ctx->verify_tap.data(), std::min(*n_elems, max_elems) * 32);
+        return PM_OK;
+    }
+    if (which == 9) {   // the witness solver's small results (solve.hip): host memory
+        if (ctx->sv.tap9.empty()) return PM_ERR_STATE;
+        *n_elems = ctx->sv.tap9.size() / 4;
+        memcpy(out, ctx->sv.tap9.data(), std::min(*n_elems, max_elems) * 32);
+        return PM_OK;
+    }
+    if (which == 10) {  // ... and the completed rows of the last solving check call, in the context's device buffer
+        if (!ctx->sv.tap10_rows) return PM_ERR_STATE;
+        PM_TRY(set_device(ctx));
+        *n_elems = ctx->sv.tap10_rows * ctx->sv.tap10_cols;
+        const size_t k10 = std::min(*n_elems, max_elems);
+        if (k10) PM_HIP(ctx, hipMemcpy(out, ctx->sv.xw.p, k10 * 32, hipMemcpyDeviceToHost));
         return PM_OK;
     }
     if (!ctx->pk || ctx->phase < 1) return PM_ERR_STATE;

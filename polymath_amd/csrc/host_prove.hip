@@ -87,10 +87,76 @@ extern "C" int pm_host_prove_sharded(pm_ctx *ctx, const pm_pk *pk, int transcrip
                : host_prove_curve<pm::BnCurve>(ctx, pk, transcript, instance_host, x, w, assignment_on_device, r_a, combine, user, proof_bytes, capacity, proof_len);
 }
 
+// ---- PM_ASSIGNMENT_SOLVE (solve.hip): the unknown entries of the assignment are computed on the device first ----
+namespace {
+
+constexpr uint64_t NOT_STUCK = ~(uint64_t)0;
+
+inline bool is_marker(const uint64_t *fr) { return (fr[0] & fr[1] & fr[2] & fr[3]) == ~(uint64_t)0; }
+
+// instance_host with its unknown entries replaced by the solved values of assignment i (tap 9): what gets hashed
+void solved_instance(const pm_ctx *ctx, const pm_pk *pk, size_t i, const uint64_t *instance_host, uint64_t *out) {
+    const uint64_t *solved = pm::solve_tap9_row(ctx, pk, i) + 4;
+    for (size_t j = 0; j < pk->m0; ++j) memcpy(out + 4 * j, is_marker(instance_host + 4 * j) ? solved + 4 * j : instance_host + 4 * j, 32);
+}
+
+// One proof from a partial assignment: solved into the context's own row, proved from there as a device assignment.
+// *stage: 0 the solver refused the structure (nothing computed), 1 the assignment is stuck, 2 the prover ran (the status is its own).
+template <class C>
+int host_prove_solve(pm_ctx *ctx, const pm_pk *pk, int transcript, const uint64_t *instance_host, const uint64_t *x, const uint64_t *w,
+                     bool on_device, const uint64_t *r_a, uint8_t *proof_bytes, size_t cap, size_t *proof_len, int *stage) {
+    *stage = 0;
+    pm::timing_reset(ctx);
+    {
+        pm::TimingGuard timing_guard{ctx};
+        PM_TRY(pm::solve_all<C>(ctx, pk, 1, x, w, on_device, 1, pm::T_WITNESS_MAP));
+    }
+    ctx->sv.tap10_rows = 0;     // a prove call: tap 10 belongs to the check calls
+    const uint64_t stuck = pm::solve_tap9_row(ctx, pk, 0)[0];
+    if (stuck != NOT_STUCK) {
+        *stage = 1;
+        ctx->err = "pm_host_prove: the assignment is stuck at row " + std::to_string(stuck) + " (division by zero)";
+        return PM_ERR_INVALID_ARG;
+    }
+    *stage = 2;
+    std::vector<uint64_t> inst(4 * pk->m0);
+    solved_instance(ctx, pk, 0, instance_host, inst.data());
+    const double solve_ms = ctx->timing_ms[pm::T_WITNESS_MAP];
+    const uint64_t *xw = (const uint64_t *)ctx->sv.xw.p;
+    const int rc = host_prove_curve<C>(ctx, pk, transcript, inst.data(), xw, xw + 4 * pk->m0, 1, r_a, nullptr, nullptr, proof_bytes, cap, proof_len);
+    ctx->timing_ms[pm::T_WITNESS_MAP] += solve_ms;   // the proof's slots start from zero; its pending timers are added when they are read
+    return rc;
+}
+
+int host_prove_solve_any(pm_ctx *ctx, const pm_pk *pk, int transcript, const uint64_t *instance_host, const uint64_t *x, const uint64_t *w,
+                         bool on_device, const uint64_t *r_a, uint8_t *proof_bytes, size_t cap, size_t *proof_len, int *stage) {
+    *stage = 0;
+    if (!ctx || !pk || !instance_host || !x || !r_a || !proof_bytes || (pk->mw && !w)) return PM_ERR_INVALID_ARG;
+    if (transcript != PM_TRANSCRIPT_MERLIN && transcript != PM_TRANSCRIPT_KECCAK256 && transcript != PM_TRANSCRIPT_BLAKE3) return PM_ERR_INVALID_ARG;
+    if (pk->shard_count != 1 || pk->layout != PM_SHARD_PAIRS || pk->device != ctx->device) return PM_ERR_INVALID_ARG;
+    if (hipSetDevice(ctx->device) != hipSuccess) return PM_ERR_HIP;
+    try {
+        return pk->curve == PM_BLS12_381
+                   ? host_prove_solve<pm::BlsCurve>(ctx, pk, transcript, instance_host, x, w, on_device, r_a, proof_bytes, cap, proof_len, stage)
+                   : host_prove_solve<pm::BnCurve>(ctx, pk, transcript, instance_host, x, w, on_device, r_a, proof_bytes, cap, proof_len, stage);
+    } catch (const std::bad_alloc &) {
+        ctx->err = "pm_host_prove: out of host memory";
+        return PM_ERR_STATE;
+    }
+}
+
+}  // namespace
+
 extern "C" int pm_host_prove(pm_ctx *ctx, const pm_pk *pk, int transcript, const uint64_t *instance_host, const uint64_t *x,
                              const uint64_t *w, int assignment_on_device, const uint64_t *r_a, uint8_t *proof_bytes, size_t capacity,
                              size_t *proof_len) {
+    if (!pm::assignment_flags_ok(assignment_on_device)) return PM_ERR_INVALID_ARG;
     if (pk && pk->shard_count != 1) return PM_ERR_INVALID_ARG;
+    if (assignment_on_device & PM_ASSIGNMENT_SOLVE) {
+        int stage = 0;
+        return host_prove_solve_any(ctx, pk, transcript, instance_host, x, w, (assignment_on_device & PM_ASSIGNMENT_DEVICE) != 0, r_a, proof_bytes,
+                                    capacity, proof_len, &stage);
+    }
     return pm_host_prove_sharded(ctx, pk, transcript, instance_host, x, w, assignment_on_device, r_a, nullptr, nullptr, proof_bytes, capacity,
                                  proof_len);
 }
@@ -100,7 +166,7 @@ namespace {
 
 template <class C, class T>
 int host_prove_batch_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *instance_host, const uint64_t *x, const uint64_t *w,
-                          int on_device, const uint64_t *r_a, uint8_t *proofs, size_t proof_len, int *status) {
+                          int on_device, bool solve, const uint64_t *r_a, uint8_t *proofs, size_t proof_len, int *status) {
     typedef pmhost::Polymath<C, T> PMH;
     typedef typename PMH::Fr Fr;
     typedef typename PMH::Glue Glue;
@@ -111,10 +177,37 @@ int host_prove_batch_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint
         // one proof's [d]_1 row exceeds an MSM piece (or not even one proof fits the memory share): the per-proof path, which splits
         // its MSMs into pieces; the stage times are summed over the proofs
         double sum[pm::T_NUM_SLOTS] = {0};
+        size_t xs = m0, ws = mw;        // elements between consecutive x rows / w rows
+        std::vector<uint64_t> solved_inst(solve ? 4 * m0 : 0);
+        if (solve) {
+            // the whole batch is completed first, in the check's groups, into the context's [count][m0 + mw] rows; the proofs read them there
+            size_t sg = pm::msm_max_piece(ctx) / (m0 + mw);
+            pm::timing_reset(ctx);
+            {
+                pm::TimingGuard timing_guard{ctx};
+                PM_TRY(pm::solve_all<C>(ctx, pk, count, x, w, on_device != 0, sg < count ? sg : count, pm::T_WITNESS_MAP));
+            }
+            ctx->sv.tap10_rows = 0;
+            sum[pm::T_WITNESS_MAP] = ctx->timing_ms[pm::T_WITNESS_MAP];
+            x = (const uint64_t *)ctx->sv.xw.p;
+            w = x + 4 * m0;
+            xs = ws = m0 + mw;
+            on_device = 1;
+        }
         for (size_t i = 0; i < count; ++i) {
             size_t len = 0;
             uint8_t *out = proofs + i * proof_len;
-            status[i] = host_prove_impl<C, T>(ctx, pk, instance_host + 4 * m0 * i, x + 4 * m0 * i, w ? w + 4 * mw * i : nullptr, on_device,
+            const uint64_t *inst = instance_host + 4 * m0 * i;
+            if (solve && pm::solve_tap9_row(ctx, pk, i)[0] != NOT_STUCK) {
+                status[i] = PM_ERR_INVALID_ARG;
+                memset(out, 0, proof_len);
+                continue;
+            }
+            if (solve) {
+                solved_instance(ctx, pk, i, inst, solved_inst.data());
+                inst = solved_inst.data();
+            }
+            status[i] = host_prove_impl<C, T>(ctx, pk, inst, x + 4 * xs * i, w ? w + 4 * ws * i : nullptr, on_device,
                                               r_a + 8 * i, nullptr, nullptr, out, proof_len, &len);
             if (status[i] == PM_OK && len != proof_len) status[i] = PM_ERR_STATE;
             if (status[i] != PM_OK) memset(out, 0, proof_len);
@@ -133,6 +226,17 @@ int host_prove_batch_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint
     key.n = pk->n; key.m0 = pk->m0; key.sigma = pk->sigma;
     memcpy(key.omega.l, pk->omega, 32);
     pm::timing_reset(ctx);             // the phases below add to the slots and never reset them: the sums over the batch
+    typename PMH::Fr *gxw = nullptr;   // solve: the group's x || w rows in the prover's workspace
+    const size_t n_groups = (count + group - 1) / group;
+    if (solve) {
+        // every assignment must mark the columns assignment 0 marks, and the structure must be solvable, before anything is computed:
+        // one pass of the pattern kernel over all groups (with one group, its rows then stay where the prover reads them)
+        PM_TRY(pm::solve_begin<C>(ctx, pk, count));
+        PM_TRY(pm::prove_batch_xw<C>(ctx, pk, group, &gxw));
+        for (size_t g0 = 0; g0 < count; g0 += group)
+            PM_TRY(pm::solve_load<C>(ctx, pk, gxw, count - g0 < group ? count - g0 : group, g0, x, w, on_device != 0));
+        PM_TRY(pm::solve_plan<C>(ctx, pk));
+    }
     int rc = PM_OK;
     size_t done = 0;                   // proofs of finished groups
     try {
@@ -146,8 +250,13 @@ int host_prove_batch_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint
             const size_t rows = count - g0 < group ? count - g0 : group;
             const uint64_t *ra = r_a + 8 * g0;
             int *stat = status + g0;
+            if (solve) {
+                if (n_groups > 1) rc = pm::solve_load<C>(ctx, pk, gxw, rows, g0, x, w, on_device != 0);   // (compares the rows once more: harmless)
+                if (rc == PM_OK) rc = pm::solve_group<C>(ctx, pk, gxw, rows, g0, pm::T_WITNESS_MAP);
+                if (rc != PM_OK) break;
+            }
             rc = pm::prove_batch_phase1<C>(ctx, pk, rows, x + 4 * m0 * g0, w ? w + 4 * mw * g0 : nullptr, on_device != 0, ra, pa.data(), ia.data(),
-                                           pc.data(), ic.data(), flags.data());
+                                           pc.data(), ic.data(), flags.data(), solve);
             if (rc != PM_OK) break;
             std::vector<Glue> glue(rows);
             for (size_t b = 0; b < rows; ++b) {
@@ -156,8 +265,10 @@ int host_prove_batch_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint
                           : ((hf & 2u) || !(hf & 4u)) ? PM_ERR_DEGREE_BOUND         // prover.rs:107
                                                       : PM_OK;
                 x1[b] = x2[b] = a_at[b] = c_at[b] = Fr::zero();     // a refused proof rides along on zeros; its results are dropped
+                if (solve && pm::solve_tap9_row(ctx, pk, g0 + b)[0] != NOT_STUCK) stat[b] = PM_ERR_INVALID_ARG;   // stuck: its row holds no assignment
                 if (stat[b] != PM_OK) continue;
-                memcpy((void *)inst[b].data(), instance_host + 4 * m0 * (g0 + b), m0 * sizeof(Fr));
+                if (solve) solved_instance(ctx, pk, g0 + b, instance_host + 4 * m0 * (g0 + b), (uint64_t *)inst[b].data());
+                else memcpy((void *)inst[b].data(), instance_host + 4 * m0 * (g0 + b), m0 * sizeof(Fr));
                 proof[b].a_g1.p = pa[b]; proof[b].a_g1.inf = ia[b] != 0;
                 proof[b].c_g1.p = pc[b]; proof[b].c_g1.inf = ic[b] != 0;
                 PMH::glue_x1(glue[b], key, inst[b], proof[b]);
@@ -197,11 +308,11 @@ int host_prove_batch_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint
 
 template <class C>
 int host_prove_batch_curve(pm_ctx *ctx, const pm_pk *pk, int transcript, size_t count, const uint64_t *ih, const uint64_t *x, const uint64_t *w,
-                           int dev, const uint64_t *r_a, uint8_t *proofs, size_t proof_len, int *status) {
+                           int dev, bool solve, const uint64_t *r_a, uint8_t *proofs, size_t proof_len, int *status) {
     switch (transcript) {
-        case PM_TRANSCRIPT_MERLIN: return host_prove_batch_impl<C, pmhost::MerlinFieldTranscript<C>>(ctx, pk, count, ih, x, w, dev, r_a, proofs, proof_len, status);
-        case PM_TRANSCRIPT_KECCAK256: return host_prove_batch_impl<C, pmhost::Keccak256Transcript<C>>(ctx, pk, count, ih, x, w, dev, r_a, proofs, proof_len, status);
-        case PM_TRANSCRIPT_BLAKE3: return host_prove_batch_impl<C, pmhost::Blake3Transcript<C>>(ctx, pk, count, ih, x, w, dev, r_a, proofs, proof_len, status);
+        case PM_TRANSCRIPT_MERLIN: return host_prove_batch_impl<C, pmhost::MerlinFieldTranscript<C>>(ctx, pk, count, ih, x, w, dev, solve, r_a, proofs, proof_len, status);
+        case PM_TRANSCRIPT_KECCAK256: return host_prove_batch_impl<C, pmhost::Keccak256Transcript<C>>(ctx, pk, count, ih, x, w, dev, solve, r_a, proofs, proof_len, status);
+        case PM_TRANSCRIPT_BLAKE3: return host_prove_batch_impl<C, pmhost::Blake3Transcript<C>>(ctx, pk, count, ih, x, w, dev, solve, r_a, proofs, proof_len, status);
         default: return PM_ERR_INVALID_ARG;
     }
 }
@@ -211,13 +322,24 @@ int host_prove_batch_curve(pm_ctx *ctx, const pm_pk *pk, int transcript, size_t 
 extern "C" int pm_host_prove_batch(pm_ctx *ctx, const pm_pk *pk, int transcript, size_t count, const uint64_t *instance_host, const uint64_t *x,
                                    const uint64_t *w, int assignment_on_device, const uint64_t *r_a, uint8_t *proofs, size_t proof_len,
                                    int *status) {
-    if (!ctx || !pk) return PM_ERR_INVALID_ARG;
+    if (!pm::assignment_flags_ok(assignment_on_device) || !ctx || !pk) return PM_ERR_INVALID_ARG;
+    const bool solve = (assignment_on_device & PM_ASSIGNMENT_SOLVE) != 0;
+    const int on_device = assignment_on_device & PM_ASSIGNMENT_DEVICE;
     if (transcript != PM_TRANSCRIPT_MERLIN && transcript != PM_TRANSCRIPT_KECCAK256 && transcript != PM_TRANSCRIPT_BLAKE3) return PM_ERR_INVALID_ARG;
     if (pk->shard_count != 1 || pk->layout != PM_SHARD_PAIRS || pk->device != ctx->device) return PM_ERR_INVALID_ARG;
     const size_t fq_bytes = pk->curve == PM_BLS12_381 ? sizeof(pm::Fp<pm::BlsFqP>) : sizeof(pm::Fp<pm::BnFqP>);
     if (proof_len != 3 * fq_bytes + 32) return PM_ERR_INVALID_ARG;     // Proof::serialize_compressed: three G1 points and one Fr
     if (count == 0) return PM_OK;
     if (!instance_host || !x || !r_a || !proofs || !status || (pk->mw && !w)) return PM_ERR_INVALID_ARG;
+    if (count == 1 && solve) {   // as below; what the solver refuses is the CALL's status and leaves the outputs alone
+        size_t len = 0;
+        int stage = 0;
+        const int rc = host_prove_solve_any(ctx, pk, transcript, instance_host, x, w, on_device != 0, r_a, proofs, proof_len, &len, &stage);
+        if (stage == 0) return rc;
+        status[0] = rc;
+        if (rc != PM_OK) memset(proofs, 0, proof_len);
+        return rc == PM_ERR_HIP ? (int)PM_ERR_HIP : (int)PM_OK;
+    }
     if (count == 1) {   // one proof: forwarded to the per-proof chain (permitted by the contract; the two routes have not been measured at B = 1)
         size_t len = 0;
         status[0] = pm_host_prove(ctx, pk, transcript, instance_host, x, w, assignment_on_device, r_a, proofs, proof_len, &len);
@@ -226,8 +348,8 @@ extern "C" int pm_host_prove_batch(pm_ctx *ctx, const pm_pk *pk, int transcript,
     }
     if (hipSetDevice(ctx->device) != hipSuccess) return PM_ERR_HIP;
     return pk->curve == PM_BLS12_381
-               ? host_prove_batch_curve<pm::BlsCurve>(ctx, pk, transcript, count, instance_host, x, w, assignment_on_device, r_a, proofs, proof_len, status)
-               : host_prove_batch_curve<pm::BnCurve>(ctx, pk, transcript, count, instance_host, x, w, assignment_on_device, r_a, proofs, proof_len, status);
+               ? host_prove_batch_curve<pm::BlsCurve>(ctx, pk, transcript, count, instance_host, x, w, on_device, solve, r_a, proofs, proof_len, status)
+               : host_prove_batch_curve<pm::BnCurve>(ctx, pk, transcript, count, instance_host, x, w, on_device, solve, r_a, proofs, proof_len, status);
 }
 
 // ---- verify (lib.rs:80-90 -> verifier.rs:19-62) and the verifying key (generator.rs:139-157): host code, no GPU --------------

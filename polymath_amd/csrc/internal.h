@@ -15,6 +15,7 @@
 
 #include "../../include/polymath_hip.h"
 #include "../host/layout.hpp"
+#include "../host/solve_plan.hpp"
 #include "ec.cuh"
 
 namespace pm {
@@ -122,6 +123,22 @@ struct ProveBatchWs {
     }
 };
 
+// Witness solving (solve.hip): the context's plan cache -- one plan, keyed by (key, unknown pattern) -- and the buffers of the last
+// call with PM_ASSIGNMENT_SOLVE.  xw: the completed x || w rows of a check call (pm_prove_tap(10)); the prover completes its groups in
+// its own workspace (ProveBatchWs::xw) and keeps only tap9.
+struct SolveWs {
+    DevBuf xw, pattern, mismatch, stuck, steps;
+    pmsolve::Plan plan;
+    uint64_t plan_key = 0;               // pm_pk::serial of the plan's key; 0 = no plan
+    std::vector<uint8_t> plan_pattern;   // one byte per column
+    std::vector<uint64_t> tap9;          // pm_prove_tap(9): per assignment 4 * (1 + m0) words; empty = no call with the flag yet
+    size_t tap10_rows = 0;               // pm_prove_tap(10): rows of xw that hold a check call's completed assignments; 0 = none
+    size_t tap10_cols = 0;
+    void release() {
+        for (DevBuf *b : {&xw, &pattern, &mismatch, &stuck, &steps}) b->release();
+    }
+};
+
 struct TwiddleCache {
     int curve = -1;
     unsigned log_n = 0;
@@ -143,7 +160,12 @@ struct pm_bases {
     pm::MsmTables tables;
 };
 
+namespace pm {
+uint64_t pk_serial_next();   // api.hip: 1, 2, 3, ... -- a key's identity for caches that outlive it (an address can come back)
+}
+
 struct pm_pk {
+    uint64_t serial = pm::pk_serial_next();
     int curve, device;
     uint64_t n, m0, mw, nr, sigma;
     unsigned log_n;
@@ -281,6 +303,7 @@ struct pm_ctx {
     // PM_SHARD_VECTOR prover (prove_sharded.hip): transform temporaries, halo coefficients, roots of the cross-rank butterfly
     pm::DevBuf sh_a, sh_b, sh_c, halo, shard_roots;
     pm::ProveBatchWs pb;
+    pm::SolveWs sv;
     std::vector<uint64_t> verify_tap;   // pm_prove_tap(8): x1, x2, c(x1), ok of the last batch verified with device challenges, 16 words a proof
     uint64_t shard_roots_n;
     uint32_t shard_roots_N;
@@ -510,12 +533,39 @@ template <class C>
 int prove_batch_group(pm_ctx *ctx, const pm_pk *pk, size_t count, size_t *group);
 template <class C>
 int prove_batch_phase1(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *x, const uint64_t *w, bool assignment_on_device,
-                       const uint64_t *r_a, Affine<C> *a, int *a_inf, Affine<C> *c, int *c_inf, unsigned *flags_out);
+                       const uint64_t *r_a, Affine<C> *a, int *a_inf, Affine<C> *c, int *c_inf, unsigned *flags_out, bool xw_resident = false);
 template <class C>
 int prove_batch_phase2(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *x1, uint64_t *u_at_x1);
 template <class C>
 int prove_batch_phase3(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *r_a, const uint64_t *x1, const uint64_t *x2,
                        const uint64_t *a_at_x1, const uint64_t *c_at_x1, Affine<C> *d, int *d_inf, unsigned *flags_out);
+
+// the group's [rows][m0 + mw] assignment buffer (pm_ctx::pb), reserved: what prove_batch_phase1 reads with xw_resident
+template <class C>
+int prove_batch_xw(pm_ctx *ctx, const pm_pk *pk, size_t rows, Fp<typename C::FrP> **xw);
+
+// solve.hip: PM_ASSIGNMENT_SOLVE.  A call with the flag runs, in this order:
+//   solve_begin    forgets the last call's taps and sizes tap 9 for `count` assignments
+//   solve_load     per group: the caller's x / w rows (host or device) -> rows of d_xw ([g][m0 + mw]), and the pattern kernel over them;
+//                  g0 = index of the group's first assignment in the batch (assignment 0 sets the pattern)
+//   solve_plan     after the last group: pattern and mismatch slot come down; PM_ERR_INVALID_ARG with pm_last_error set for a marker at
+//                  column 0, a mismatching assignment or an unsolvable structure; otherwise the plan is taken from the cache or built
+//   solve_group    per group: the launch schedule over d_xw, then the stuck rows and completed instances of the group into tap 9;
+//                  GPU ms go to timing_slot.  The stream is idle on return.
+// solve_all is the four over a whole batch in groups of the check's size into pm_ctx::sv.xw ([count][m0 + mw], pm_prove_tap(10)).
+template <class C>
+int solve_begin(pm_ctx *ctx, const pm_pk *pk, size_t count);
+template <class C>
+int solve_load(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t g, size_t g0, const uint64_t *x, const uint64_t *w, bool on_device);
+template <class C>
+int solve_plan(pm_ctx *ctx, const pm_pk *pk);
+template <class C>
+int solve_group(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t g, size_t g0, int timing_slot);
+template <class C>
+int solve_all(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *x, const uint64_t *w, bool on_device, size_t group, int timing_slot);
+// the flag word of an `assignment_on_device` argument: false = a bit outside PM_ASSIGNMENT_DEVICE | PM_ASSIGNMENT_SOLVE
+inline bool assignment_flags_ok(int f) { return (f & ~(PM_ASSIGNMENT_DEVICE | PM_ASSIGNMENT_SOLVE)) == 0; }
+inline const uint64_t *solve_tap9_row(const pm_ctx *ctx, const pm_pk *pk, size_t i) { return ctx->sv.tap9.data() + i * 4 * (1 + pk->m0); }
 
 template <class C>
 int prove_phase1_sharded(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const uint64_t *w, const uint64_t *r_a, uint64_t *a_xy, int *a_inf,

@@ -402,8 +402,17 @@ static int upload_rows(pm_ctx *ctx, const std::vector<BatchRow<typename C::FrP>>
 }
 
 template <class C>
+int prove_batch_xw(pm_ctx *ctx, const pm_pk *pk, size_t rows, Fp<typename C::FrP> **xw) {
+    PM_HIP(ctx, ctx->pb.xw.reserve(rows * (pk->m0 + pk->mw) * sizeof(Fp<typename C::FrP>)));
+    *xw = ctx->pb.xw.as<Fp<typename C::FrP>>();
+    return PM_OK;
+}
+
+// xw_resident: the group's x || w rows are already in the workspace (prove_batch_xw: the witness solver completed them there);
+// x and w are then not read
+template <class C>
 int prove_batch_phase1(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *x, const uint64_t *w, bool assignment_on_device,
-                       const uint64_t *r_a, Affine<C> *a, int *a_inf, Affine<C> *c, int *c_inf, unsigned *flags_out) {
+                       const uint64_t *r_a, Affine<C> *a, int *a_inf, Affine<C> *c, int *c_inf, unsigned *flags_out, bool xw_resident) {
     typedef typename C::FrP P;
     typedef Fp<P> Fr;
     const BatchDims d = batch_dims(pk);
@@ -427,8 +436,10 @@ int prove_batch_phase1(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t
     PM_HIP(ctx, hipMemsetAsync(flags, 0, rows * sizeof(unsigned), st));
     const hipMemcpyKind kind = assignment_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     // rows of x (m0) and of w (mw) interleave into rows of x || w
-    PM_HIP(ctx, hipMemcpy2DAsync(xw, (m0 + mw) * sizeof(Fr), x, m0 * sizeof(Fr), m0 * sizeof(Fr), rows, kind, st));
-    if (mw) PM_HIP(ctx, hipMemcpy2DAsync(xw + m0, (m0 + mw) * sizeof(Fr), w, mw * sizeof(Fr), mw * sizeof(Fr), rows, kind, st));
+    if (!xw_resident) {
+        PM_HIP(ctx, hipMemcpy2DAsync(xw, (m0 + mw) * sizeof(Fr), x, m0 * sizeof(Fr), m0 * sizeof(Fr), rows, kind, st));
+        if (mw) PM_HIP(ctx, hipMemcpy2DAsync(xw + m0, (m0 + mw) * sizeof(Fr), w, mw * sizeof(Fr), mw * sizeof(Fr), rows, kind, st));
+    }
     std::vector<BatchRow<P>> par(rows);
     memset((void *)par.data(), 0, rows * sizeof(BatchRow<P>));
     for (size_t b = 0; b < rows; ++b) memcpy((void *)par[b].ra, r_a + 8 * b, 2 * sizeof(Fr));
@@ -594,8 +605,9 @@ int prove_batch_phase3(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t
 
 #define PM_INST(C)                                                                                                                          \
     template int prove_batch_group<C>(pm_ctx *, const pm_pk *, size_t, size_t *);                                                           \
+    template int prove_batch_xw<C>(pm_ctx *, const pm_pk *, size_t, Fp<typename C::FrP> **);                                                \
     template int prove_batch_phase1<C>(pm_ctx *, const pm_pk *, size_t, const uint64_t *, const uint64_t *, bool, const uint64_t *,         \
-                                       Affine<C> *, int *, Affine<C> *, int *, unsigned *);                                                \
+                                       Affine<C> *, int *, Affine<C> *, int *, unsigned *, bool);                                          \
     template int prove_batch_phase2<C>(pm_ctx *, const pm_pk *, size_t, const uint64_t *, uint64_t *);                                      \
     template int prove_batch_phase3<C>(pm_ctx *, const pm_pk *, size_t, const uint64_t *, const uint64_t *, const uint64_t *,              \
                                        const uint64_t *, const uint64_t *, Affine<C> *, int *, unsigned *);

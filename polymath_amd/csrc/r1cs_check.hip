@@ -22,13 +22,14 @@ constexpr unsigned R1CS_SCAN_ROWS = R1CS_SCAN_LANES * 64;      // rows covered b
 static_assert(R1CS_SCAN_LANES % 64 == 0 && R1CS_SCAN_ROWS <= (1u << 16), "the scan's waves are whole and an iteration's counts stay small");
 constexpr uint64_t R1CS_NO_ROW = ~(uint64_t)0;                 // an unused slot of `rows`
 
-// mask[b][r / 64] bit r % 64 = row r of assignment b fails.  blockDim.x is a multiple of 64, so a wave holds 64 consecutive rows
+// mask[b][r / 64] bit r % 64 = row r of assignment b fails.  xs, ws: elements between the x rows / the w rows of consecutive assignments
+// (m0 and mw for the caller's two arrays; m0 + mw for both where the rows are x || w, as the solver leaves them).  blockDim.x is a multiple of 64, so a wave holds 64 consecutive rows
 // starting at a multiple of 64; every lane reaches the ballot (lanes past nr vote 0), lane 0 of the wave stores the word.
 template <class P>
-__global__ __launch_bounds__(256) void k_r1cs_mask(CsrDev A, CsrDev B, CsrDev Cm, const Fp<P> *x, const Fp<P> *w, uint64_t m0, uint64_t mw,
+__global__ __launch_bounds__(256) void k_r1cs_mask(CsrDev A, CsrDev B, CsrDev Cm, const Fp<P> *x, const Fp<P> *w, uint64_t m0, uint64_t xs, uint64_t ws,
                                                    uint64_t nr, uint64_t words, unsigned long long *mask) {
     const uint64_t b = blockIdx.y;
-    x += b * m0; w += b * mw; mask += b * words;
+    x += b * xs; w += b * ws; mask += b * words;
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool bad = false;
     if (r < nr) {
@@ -84,12 +85,12 @@ __global__ __launch_bounds__(R1CS_SCAN_LANES) void k_r1cs_scan(const unsigned lo
 
 // abc: [assignment][max_rows][3] = (Az)_r, (Bz)_r, (Cz)_r of the row in the slot, zero for an unused slot
 template <class P>
-__global__ __launch_bounds__(256) void k_r1cs_residuals(CsrDev A, CsrDev B, CsrDev Cm, const Fp<P> *x, const Fp<P> *w, uint64_t m0, uint64_t mw,
+__global__ __launch_bounds__(256) void k_r1cs_residuals(CsrDev A, CsrDev B, CsrDev Cm, const Fp<P> *x, const Fp<P> *w, uint64_t m0, uint64_t xs, uint64_t ws,
                                                         const uint64_t *rows, uint64_t max_rows, Fp<P> *abc) {
     const uint64_t b = blockIdx.y;
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= max_rows) return;
-    x += b * m0; w += b * mw;
+    x += b * xs; w += b * ws;
     const uint64_t r = rows[b * max_rows + j];
     Fp<P> *out = abc + (b * max_rows + j) * 3;
     if (r == R1CS_NO_ROW) {
@@ -110,11 +111,12 @@ struct CheckBufs {   // the call's device memory: released on every way out
     }
 };
 
+// With `solve` (PM_ASSIGNMENT_SOLVE) the unknown entries are computed first (solve.hip) and the check reads the completed rows.
 // Assignments run in GROUPS of as many as keep group * (m0 + mw) inside one MSM piece (the knob pm_host_prove_batch sizes its groups
 // by), at least one, at most 65 535 (grid y).  Host assignments are uploaded group by group; device assignments are read where they
 // are.  The device lists min(max_rows, nr) rows per assignment -- no more can fail -- and the host pads the caller's slots beyond.
 template <class C>
-int r1cs_check_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *x, const uint64_t *w, bool on_device, size_t max_rows,
+int r1cs_check_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *x, const uint64_t *w, bool on_device, bool solve, size_t max_rows,
                     uint64_t *n_bad, uint64_t *rows, uint64_t *abc) {
     typedef typename C::FrP P;
     typedef Fp<P> Fr;
@@ -129,6 +131,16 @@ int r1cs_check_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *
     CheckBufs d;
     TimingGuard timing_guard{ctx};
     timing_reset(ctx);
+    uint64_t xs = m0, ws = mw;
+    if (solve) {
+        // the assignments are completed first, in the same groups, into the context's [count][m0 + mw] buffer (pm_prove_tap(10)); the
+        // check then reads those rows.  A structural error returns here: nothing has been written.
+        PM_TRY(solve_all<C>(ctx, pk, count, x, w, on_device, group, T_NTT));
+        x = (const uint64_t *)ctx->sv.xw.p;
+        w = x + 4 * m0;
+        xs = ws = m0 + mw;
+        on_device = true;
+    }
     if (!on_device) {
         PM_HIP(ctx, d.x.reserve(group * m0 * sizeof(Fr)));
         if (mw) PM_HIP(ctx, d.w.reserve(group * mw * sizeof(Fr)));
@@ -142,7 +154,7 @@ int r1cs_check_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *
         Cm{pk->d_rowptr[2], pk->d_col[2], pk->d_val[2]};
     for (size_t g0 = 0; g0 < count; g0 += group) {
         const size_t g = count - g0 < group ? count - g0 : group;
-        const Fr *gx = (const Fr *)x + g0 * m0, *gw = mw ? (const Fr *)w + g0 * mw : nullptr;
+        const Fr *gx = (const Fr *)x + g0 * xs, *gw = mw ? (const Fr *)w + g0 * ws : nullptr;
         if (!on_device) {
             PM_HIP(ctx, hipMemcpyAsync(d.x.p, gx, g * m0 * sizeof(Fr), hipMemcpyHostToDevice, st));
             if (mw) PM_HIP(ctx, hipMemcpyAsync(d.w.p, gw, g * mw * sizeof(Fr), hipMemcpyHostToDevice, st));
@@ -152,7 +164,7 @@ int r1cs_check_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *
         {
             StageTimer t(ctx, T_WITNESS_MAP);
             if (words) {
-                hipLaunchKernelGGL(k_r1cs_mask<P>, dim3(nblk(nr), (unsigned)g), dim3(256), 0, st, A, B, Cm, gx, gw, m0, mw, nr, words,
+                hipLaunchKernelGGL(k_r1cs_mask<P>, dim3(nblk(nr), (unsigned)g), dim3(256), 0, st, A, B, Cm, gx, gw, m0, xs, ws, nr, words,
                                    d.mask.as<unsigned long long>());
                 PM_HIP(ctx, hipGetLastError());
             }
@@ -160,7 +172,7 @@ int r1cs_check_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *
                                d.n_bad.as<uint64_t>(), d.rows.as<uint64_t>());
             PM_HIP(ctx, hipGetLastError());
             if (listed && abc) {
-                hipLaunchKernelGGL(k_r1cs_residuals<P>, dim3(nblk(listed), (unsigned)g), dim3(256), 0, st, A, B, Cm, gx, gw, m0, mw,
+                hipLaunchKernelGGL(k_r1cs_residuals<P>, dim3(nblk(listed), (unsigned)g), dim3(256), 0, st, A, B, Cm, gx, gw, m0, xs, ws,
                                    d.rows.as<uint64_t>(), listed, d.abc.as<Fr>());
                 PM_HIP(ctx, hipGetLastError());
             }
@@ -178,6 +190,13 @@ int r1cs_check_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *
             memcpy(res, h_abc.data() + b * listed * 12, listed * 12 * sizeof(uint64_t));
             memset(res + listed * 12, 0, (max_rows - listed) * 12 * sizeof(uint64_t));
         }
+        for (size_t b = 0; b < g && solve; ++b) {   // a stuck assignment has nothing to check: its stuck row instead
+            const uint64_t stuck = solve_tap9_row(ctx, pk, g0 + b)[0];
+            if (stuck == R1CS_NO_ROW) continue;
+            n_bad[g0 + b] = R1CS_NO_ROW;
+            for (size_t j = 0; j < max_rows; ++j) rows[(g0 + b) * max_rows + j] = j ? R1CS_NO_ROW : stuck;
+            if (abc && max_rows) memset(abc + (g0 + b) * max_rows * 12, 0, max_rows * 12 * sizeof(uint64_t));
+        }
     }
     return PM_OK;
 }
@@ -187,15 +206,16 @@ int r1cs_check_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *
 
 extern "C" int pm_r1cs_check_batch(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *x, const uint64_t *w, int assignment_on_device,
                                    size_t max_rows, uint64_t *n_bad, uint64_t *rows, uint64_t *abc) {
-    if (!ctx || !pk) return PM_ERR_INVALID_ARG;
+    if (!pm::assignment_flags_ok(assignment_on_device) || !ctx || !pk) return PM_ERR_INVALID_ARG;
+    const bool on_device = (assignment_on_device & PM_ASSIGNMENT_DEVICE) != 0, solve = (assignment_on_device & PM_ASSIGNMENT_SOLVE) != 0;
     if (pk->shard_count != 1 || pk->layout != PM_SHARD_PAIRS || pk->device != ctx->device) return PM_ERR_INVALID_ARG;
     if (count == 0) return PM_OK;
     if (!n_bad || !x || (pk->mw && !w) || (max_rows && !rows)) return PM_ERR_INVALID_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return PM_ERR_HIP;
     try {
         return pk->curve == PM_BLS12_381
-                   ? pm::r1cs_check_impl<pm::BlsCurve>(ctx, pk, count, x, w, assignment_on_device != 0, max_rows, n_bad, rows, abc)
-                   : pm::r1cs_check_impl<pm::BnCurve>(ctx, pk, count, x, w, assignment_on_device != 0, max_rows, n_bad, rows, abc);
+                   ? pm::r1cs_check_impl<pm::BlsCurve>(ctx, pk, count, x, w, on_device, solve, max_rows, n_bad, rows, abc)
+                   : pm::r1cs_check_impl<pm::BnCurve>(ctx, pk, count, x, w, on_device, solve, max_rows, n_bad, rows, abc);
     } catch (const std::bad_alloc &) {
         ctx->err = "pm_r1cs_check: out of host memory";
         return PM_ERR_STATE;

@@ -1,0 +1,300 @@
+// PM_ASSIGNMENT_SOLVE: complete partial assignments on the device by forward propagation through the key's resident constraint rows
+// (include/polymath_hip.h), so that a caller supplies only the values it chooses and the library computes the rest
+// before it checks or proves.  The PLAN -- which row determines which column, in which order -- is host work, done once per (key,
+// pattern) by host/solve_plan.hpp; the arithmetic is the kernels below, assignment = grid y (or the lane, in the chain kernel):
+//   k_solve_pattern   one lane per (column, assignment): the unknown pattern of assignment 0; every other assignment is compared
+//                     with it and the first differing (assignment, column) lowers one word
+//   k_solve_inv       one lane per step, once per plan: 1 / coefficient of the step's unknown
+//   k_solve_level     a WIDE dependency level: one lane per (step, assignment); a level is its own launch, so stream order is
+//                     the dependency order
+//   k_solve_chain     a run of consecutive NARROW levels: one lane per assignment walks the run's steps in plan order.  A lane
+//                     reads back only its own stores: no barriers, no fences.  The MiMC shape (depth 644, width 1) is one such run
+//                     and the batch is its parallel dimension.
+// The two solving kernels exist twice: DIV = false for ranges of kind-C steps only, DIV = true for ranges with kind-A / kind-B steps,
+// which call inverse<P> (a Fermat chain) -- the plan sorts a level by kind, so kind-C ranges do not carry its registers.
+// A step that would divide by zero stores zero and lowers the assignment's stuck word to its row (64-bit atomic minimum: the same
+// word on every run).  Every other store has one writer.  Plain C++ and vector stores only.
+#include <cstring>
+#include <vector>
+
+#include "internal.h"
+#include "prove_common.cuh"
+
+namespace pm {
+
+constexpr uint64_t SOLVE_NONE = ~(uint64_t)0;   // no stuck row / no mismatch / no entry to skip
+
+template <class P>
+struct SolveStepDev {
+    uint64_t pos;                    // the unknown's entry in its matrix
+    uint32_t row, col, kind, pad;
+    Fp<P> inv;                       // 1 / coefficient (k_solve_inv)
+};
+
+template <class P>
+__device__ __forceinline__ bool is_marker(const Fp<P> &v) {
+    uint32_t a = ~0u;
+#pragma unroll
+    for (int i = 0; i < P::N; ++i) a &= v.l[i];
+    return a == ~0u;
+}
+
+// xw: [g][ncols], the group's rows; g0 = the batch index of row 0.  pattern: one byte per column, written from assignment 0 of the
+// batch (a lane per byte) and read by the groups after the first (an earlier launch wrote it); the rows that share assignment 0's
+// launch compare with its values directly.
+template <class P>
+__global__ __launch_bounds__(256) void k_solve_pattern(const Fp<P> *xw, uint64_t ncols, uint64_t g0, uint8_t *pattern, unsigned long long *mismatch) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (j >= ncols) return;
+    const bool unknown = is_marker<P>(xw[b * ncols + j]);
+    if (g0 + b == 0) {
+        pattern[j] = unknown ? 1 : 0;
+        return;
+    }
+    const bool expected = g0 == 0 ? is_marker<P>(xw[j]) : pattern[j] != 0;
+    if (unknown != expected) atomicMin(mismatch, (unsigned long long)(((g0 + b) << 32) | j));
+}
+
+__device__ __forceinline__ const CsrDev &matrix_of(uint32_t kind, const CsrDev &A, const CsrDev &B, const CsrDev &Cm) {
+    return kind == pmsolve::KIND_A ? A : kind == pmsolve::KIND_B ? B : Cm;
+}
+
+template <class P>
+__global__ __launch_bounds__(256) void k_solve_inv(CsrDev A, CsrDev B, CsrDev Cm, SolveStepDev<P> *steps, uint64_t count) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const Fp<P> coef = *(const Fp<P> *)(matrix_of(steps[t].kind, A, B, Cm).val + 4 * steps[t].pos);
+    steps[t].inv = coef.eq(Fp<P>::one()) ? coef : inverse<P>(coef);
+}
+
+// (M z)_r without entry `skip` (SOLVE_NONE: the whole row)
+template <class P>
+__device__ __forceinline__ Fp<P> row_dot_skip(const CsrDev &M, const Fp<P> *z, uint64_t r, uint64_t skip) {
+    Fp<P> acc = Fp<P>::zero();
+    for (uint64_t k = M.rowptr[r]; k < M.rowptr[r + 1]; ++k) {
+        if (k == skip) continue;
+        acc = add<P>(acc, mul<P>(*(const Fp<P> *)(M.val + 4 * k), z[M.col[k]]));
+    }
+    return acc;
+}
+
+// one step on one assignment (z = its x || w row): the partial dot products of the row, the unknown's entry left out, then
+//   kind C: z_u = (Az Bz - C_rest) / coef      kind A: z_u = (Cz / Bz - A_rest) / coef      kind B: z_u = (Cz / Az - B_rest) / coef
+template <class P, bool DIV>
+__device__ __forceinline__ void solve_step(const CsrDev &A, const CsrDev &B, const CsrDev &Cm, const SolveStepDev<P> &s, Fp<P> *z,
+                                           unsigned long long *stuck) {
+    const uint64_t r = s.row;
+    const uint32_t kind = s.kind;
+    const Fp<P> az = row_dot_skip<P>(A, z, r, kind == pmsolve::KIND_A ? s.pos : SOLVE_NONE);
+    const Fp<P> bz = row_dot_skip<P>(B, z, r, kind == pmsolve::KIND_B ? s.pos : SOLVE_NONE);
+    const Fp<P> cz = row_dot_skip<P>(Cm, z, r, kind == pmsolve::KIND_C ? s.pos : SOLVE_NONE);
+    Fp<P> v;
+    if (!DIV || kind == pmsolve::KIND_C) {
+        v = sub<P>(mul<P>(az, bz), cz);
+    } else {
+        const Fp<P> den = kind == pmsolve::KIND_A ? bz : az, rest = kind == pmsolve::KIND_A ? az : bz;
+        if (den.is_zero()) {        // 0 / 0 included: the value is then undetermined
+            atomicMin(stuck, (unsigned long long)r);
+            z[s.col] = Fp<P>::zero();
+            return;
+        }
+        v = sub<P>(mul<P>(cz, inverse<P>(den)), rest);
+    }
+    z[s.col] = mul<P>(v, s.inv);
+}
+
+template <class P, bool DIV>
+__global__ __launch_bounds__(256) void k_solve_level(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, uint32_t lo, uint32_t hi,
+                                                     Fp<P> *xw, uint64_t ncols, unsigned long long *stuck) {
+    const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (t >= hi) return;
+    solve_step<P, DIV>(A, B, Cm, steps[t], xw + b * ncols, stuck + b);
+}
+
+// the step index is the same in every lane: the step record and the row's CSR metadata are uniform loads
+template <class P, bool DIV>
+__global__ __launch_bounds__(64) void k_solve_chain(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, uint32_t lo, uint32_t hi,
+                                                    Fp<P> *xw, uint64_t ncols, unsigned long long *stuck, uint64_t rows) {
+    const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= rows) return;
+    Fp<P> *z = xw + b * ncols;
+    for (uint32_t t = lo; t < hi; ++t) solve_step<P, DIV>(A, B, Cm, steps[t], z, stuck + b);
+}
+
+namespace {
+
+inline CsrDev csr_dev(const pm_pk *pk, int i) { return CsrDev{pk->d_rowptr[i], pk->d_col[i], pk->d_val[i]}; }
+
+}  // namespace
+
+template <class C>
+int solve_begin(pm_ctx *ctx, const pm_pk *pk, size_t count) {
+    SolveWs &sv = ctx->sv;
+    const uint64_t ncols = pk->m0 + pk->mw;
+    sv.tap9.clear();
+    sv.tap10_rows = sv.tap10_cols = 0;
+    if (count == 0 || count > 0xffffffffull || pk->nr > 0xffffffffull || ncols > 0xffffffffull) {
+        ctx->err = "pm solve: more than 2^32 - 1 assignments, rows or columns";
+        return PM_ERR_INVALID_ARG;
+    }
+    PM_HIP(ctx, sv.pattern.reserve(ncols));
+    PM_HIP(ctx, sv.mismatch.reserve(sizeof(unsigned long long)));
+    PM_HIP(ctx, hipMemsetAsync(sv.mismatch.p, 0xff, sizeof(unsigned long long), ctx->stream));
+    sv.tap9.assign(count * 4 * (1 + pk->m0), 0);
+    return PM_OK;
+}
+
+template <class C>
+int solve_load(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t g, size_t g0, const uint64_t *x, const uint64_t *w, bool on_device) {
+    typedef typename C::FrP P;
+    typedef Fp<P> Fr;
+    const uint64_t m0 = pk->m0, mw = pk->mw, ncols = m0 + mw;
+    if (g == 0 || g > 65535) return PM_ERR_INVALID_ARG;
+    hipStream_t st = ctx->stream;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    // rows of x (m0) and of w (mw) interleave into rows of x || w; the caller's arrays are only read
+    PM_HIP(ctx, hipMemcpy2DAsync(d_xw, ncols * sizeof(Fr), x + 4 * m0 * g0, m0 * sizeof(Fr), m0 * sizeof(Fr), g, kind, st));
+    if (mw) PM_HIP(ctx, hipMemcpy2DAsync(d_xw + m0, ncols * sizeof(Fr), w + 4 * mw * g0, mw * sizeof(Fr), mw * sizeof(Fr), g, kind, st));
+    hipLaunchKernelGGL(k_solve_pattern<P>, dim3(nblk(ncols), (unsigned)g), dim3(256), 0, st, d_xw, ncols, (uint64_t)g0, ctx->sv.pattern.as<uint8_t>(),
+                       ctx->sv.mismatch.as<unsigned long long>());
+    PM_HIP(ctx, hipGetLastError());
+    return PM_OK;
+}
+
+template <class C>
+int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
+    typedef typename C::FrP P;
+    SolveWs &sv = ctx->sv;
+    const uint64_t ncols = pk->m0 + pk->mw, nr = pk->nr;
+    hipStream_t st = ctx->stream;
+    std::vector<uint8_t> pattern(ncols);
+    unsigned long long mismatch = SOLVE_NONE;
+    PM_HIP(ctx, hipMemcpyAsync(pattern.data(), sv.pattern.p, ncols, hipMemcpyDeviceToHost, st));
+    PM_HIP(ctx, hipMemcpyAsync(&mismatch, sv.mismatch.p, sizeof mismatch, hipMemcpyDeviceToHost, st));
+    PM_HIP(ctx, hipStreamSynchronize(st));
+    if (pattern[0]) {
+        ctx->err = "pm solve: column 0 (the constant one) is marked unknown";
+        return PM_ERR_INVALID_ARG;
+    }
+    if (mismatch != SOLVE_NONE) {
+        ctx->err = "pm solve: assignment " + std::to_string(mismatch >> 32) + " differs from assignment 0 at column " + std::to_string(mismatch & 0xffffffffull) +
+                   ": every assignment of a batch must mark the same columns";
+        return PM_ERR_INVALID_ARG;
+    }
+    if (sv.plan_key == pk->serial && sv.plan_pattern == pattern) return PM_OK;
+    sv.plan_key = 0;
+    // the key's matrices come down once per plan: the key keeps no host copy
+    std::vector<uint64_t> rowptr[3], val[3];
+    std::vector<uint32_t> col[3];
+    pmsolve::Csr m[3];
+    for (int i = 0; i < 3; ++i) {
+        const uint64_t nnz = pk->nnz[i];
+        rowptr[i].resize(nr + 1);
+        col[i].resize(nnz ? nnz : 1);
+        val[i].resize(nnz ? 4 * nnz : 4);
+        PM_HIP(ctx, hipMemcpyAsync(rowptr[i].data(), pk->d_rowptr[i], (nr + 1) * 8, hipMemcpyDeviceToHost, st));
+        if (nnz) {
+            PM_HIP(ctx, hipMemcpyAsync(col[i].data(), pk->d_col[i], nnz * 4, hipMemcpyDeviceToHost, st));
+            PM_HIP(ctx, hipMemcpyAsync(val[i].data(), pk->d_val[i], nnz * 32, hipMemcpyDeviceToHost, st));
+        }
+        m[i] = pmsolve::Csr{rowptr[i].data(), col[i].data(), val[i].data()};
+    }
+    PM_HIP(ctx, hipStreamSynchronize(st));
+    sv.plan = pmsolve::build_plan(m, nr, pk->m0, pk->mw, pattern.data());
+    if (sv.plan.error != pmsolve::OK) {
+        ctx->err = "pm solve: " + sv.plan.message;
+        return PM_ERR_INVALID_ARG;
+    }
+    const size_t n_steps = sv.plan.steps.size();
+    if (n_steps) {
+        std::vector<SolveStepDev<P>> host(n_steps);
+        memset((void *)host.data(), 0, n_steps * sizeof(SolveStepDev<P>));
+        for (size_t t = 0; t < n_steps; ++t) {
+            const pmsolve::Step &s = sv.plan.steps[t];
+            host[t].pos = s.pos; host[t].row = s.row; host[t].col = s.col; host[t].kind = s.kind;
+        }
+        PM_HIP(ctx, sv.steps.reserve(n_steps * sizeof(SolveStepDev<P>)));
+        PM_HIP(ctx, hipMemcpyAsync(sv.steps.p, host.data(), n_steps * sizeof(SolveStepDev<P>), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_solve_inv<P>, dim3(nblk(n_steps)), dim3(256), 0, st, csr_dev(pk, 0), csr_dev(pk, 1), csr_dev(pk, 2), sv.steps.as<SolveStepDev<P>>(),
+                           (uint64_t)n_steps);
+        PM_HIP(ctx, hipGetLastError());
+        PM_HIP(ctx, hipStreamSynchronize(st));   // `host` goes out of scope
+    }
+    sv.plan_pattern.swap(pattern);
+    sv.plan_key = pk->serial;
+    return PM_OK;
+}
+
+template <class C>
+int solve_group(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t g, size_t g0, int timing_slot) {
+    typedef typename C::FrP P;
+    typedef Fp<P> Fr;
+    SolveWs &sv = ctx->sv;
+    const uint64_t m0 = pk->m0, ncols = m0 + pk->mw;
+    if (g == 0 || g > 65535 || sv.plan_key != pk->serial || (g0 + g) * 4 * (1 + m0) > sv.tap9.size()) return PM_ERR_STATE;
+    hipStream_t st = ctx->stream;
+    TimingGuard timing_guard{ctx};
+    PM_HIP(ctx, sv.stuck.reserve(g * sizeof(unsigned long long)));
+    unsigned long long *stuck = sv.stuck.as<unsigned long long>();
+    PM_HIP(ctx, hipMemsetAsync(stuck, 0xff, g * sizeof(unsigned long long), st));
+    const CsrDev A = csr_dev(pk, 0), B = csr_dev(pk, 1), Cm = csr_dev(pk, 2);
+    const SolveStepDev<P> *steps = sv.steps.as<SolveStepDev<P>>();
+    {
+        StageTimer t(ctx, timing_slot);
+        for (const pmsolve::Launch &l : sv.plan.launches) {
+            if (l.chain) {
+                const dim3 grid(nblk(g, 64)), block(64);
+                if (l.divides) hipLaunchKernelGGL((k_solve_chain<P, true>), grid, block, 0, st, A, B, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
+                else hipLaunchKernelGGL((k_solve_chain<P, false>), grid, block, 0, st, A, B, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
+            } else {
+                const dim3 grid(nblk(l.hi - l.lo), (unsigned)g), block(256);
+                if (l.divides) hipLaunchKernelGGL((k_solve_level<P, true>), grid, block, 0, st, A, B, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck);
+                else hipLaunchKernelGGL((k_solve_level<P, false>), grid, block, 0, st, A, B, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck);
+            }
+            PM_HIP(ctx, hipGetLastError());
+        }
+    }
+    // the small results: per assignment the stuck word and the completed instance -> tap 9
+    std::vector<unsigned long long> h_stuck(g);
+    uint64_t *tap = sv.tap9.data() + g0 * 4 * (1 + m0);
+    PM_HIP(ctx, hipMemcpyAsync(h_stuck.data(), stuck, g * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    PM_HIP(ctx, hipMemcpy2DAsync(tap + 4, (1 + m0) * sizeof(Fr), d_xw, ncols * sizeof(Fr), m0 * sizeof(Fr), g, hipMemcpyDeviceToHost, st));
+    PM_HIP(ctx, hipStreamSynchronize(st));
+    for (size_t b = 0; b < g; ++b) {
+        uint64_t *row = tap + b * 4 * (1 + m0);
+        row[0] = h_stuck[b];
+        row[1] = row[2] = row[3] = 0;
+        if (h_stuck[b] != SOLVE_NONE) memset(row + 4, 0, m0 * sizeof(Fr));
+    }
+    return PM_OK;
+}
+
+template <class C>
+int solve_all(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *x, const uint64_t *w, bool on_device, size_t group, int timing_slot) {
+    typedef Fp<typename C::FrP> Fr;
+    const uint64_t ncols = pk->m0 + pk->mw;
+    if (group < 1) group = 1;
+    if (group > 65535) group = 65535;
+    PM_TRY(solve_begin<C>(ctx, pk, count));
+    PM_HIP(ctx, ctx->sv.xw.reserve(count * ncols * sizeof(Fr)));
+    Fr *xw = ctx->sv.xw.as<Fr>();
+    for (size_t g0 = 0; g0 < count; g0 += group)
+        PM_TRY(solve_load<C>(ctx, pk, xw + g0 * ncols, count - g0 < group ? count - g0 : group, g0, x, w, on_device));
+    PM_TRY(solve_plan<C>(ctx, pk));
+    for (size_t g0 = 0; g0 < count; g0 += group)
+        PM_TRY(solve_group<C>(ctx, pk, xw + g0 * ncols, count - g0 < group ? count - g0 : group, g0, timing_slot));
+    ctx->sv.tap10_rows = count;
+    ctx->sv.tap10_cols = ncols;
+    return PM_OK;
+}
+
+#define PM_INST(C)                                                                                                             \
+    template int solve_begin<C>(pm_ctx *, const pm_pk *, size_t);                                                              \
+    template int solve_load<C>(pm_ctx *, const pm_pk *, Fp<typename C::FrP> *, size_t, size_t, const uint64_t *, const uint64_t *, bool); \
+    template int solve_plan<C>(pm_ctx *, const pm_pk *);                                                                       \
+    template int solve_group<C>(pm_ctx *, const pm_pk *, Fp<typename C::FrP> *, size_t, size_t, int);                         \
+    template int solve_all<C>(pm_ctx *, const pm_pk *, size_t, const uint64_t *, const uint64_t *, bool, size_t, int);
+PM_INST(BlsCurve)
+PM_INST(BnCurve)
+
+}  // namespace pm

@@ -19,6 +19,7 @@ from .transcript import TRANSCRIPTS
 
 MINUS_ALPHA, MINUS_GAMMA = 3, 5        # common.rs:11,14
 B_POLYMATH = b"polymath"               # common.rs:8
+UNKNOWN = api.UNKNOWN_LIMBS             # the marker limbs of a value the device is to solve (PM_ASSIGNMENT_SOLVE); >= r on both curves
 
 FIELDS = {
     "bls12_381": dict(r=0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001,
@@ -392,13 +393,16 @@ class Polymath:
             raise PolymathProverError(0, rc)
         return data
 
-    def prove_batch(self, pk, circuits_or_limbs, r_as, device_ptrs=None):
+    def prove_batch(self, pk, circuits_or_limbs, r_as, device_ptrs=None, solve=False):
         """Many assignments of one circuit against one unsharded key in ONE native call (pm_host_prove_batch: every stage of the
         prover with the proof as a grid dimension, three batched MSMs per group of proofs).  circuits_or_limbs[i]: a circuit, a
         LimbCircuit or an (x_limbs, w_limbs) pair; r_as[i] = [r0, r1].  device_ptrs = (d_x, d_w): the assignments are already in HBM
         as count x m0 / count x mw rows (the x limbs of circuits_or_limbs are still hashed on the host).
         -> (proofs, statuses): proofs[i] = Proof::serialize_compressed bytes, or None where statuses[i] != 0 (an unsatisfied
-        assignment gets the status prove_native raises for it and leaves its neighbours alone)."""
+        assignment gets the status prove_native raises for it and leaves its neighbours alone).
+        solve=True: circuits_or_limbs[i] is an (x_limbs, w_limbs) pair -- or partial_limbs(...) -- whose UNKNOWN entries the device
+        computes first (PM_ASSIGNMENT_SOLVE); a stuck assignment gets status 1.  -> (proofs, statuses, instances) in that mode only:
+        instances[i] = the completed public inputs as ints, leading one included, or None where the assignment is stuck."""
         if self.transcript_name is None:
             raise ValueError("prove_batch needs one of the reference's transcripts: " + ", ".join(TRANSCRIPTS))
         if len(circuits_or_limbs) != len(r_as):
@@ -420,13 +424,55 @@ class Polymath:
         w_all = np.stack(ws) if count else np.zeros((0, 0, 4), dtype=np.uint64)
         ra_all = np.stack([f.fr_limbs(list(r)) for r in r_as]) if count else np.zeros((0, 2, 4), dtype=np.uint64)
         if device_ptrs is not None:
-            rc, data, status = pk.host_prove_batch(self.transcript_name, x_all, device_ptrs[0], device_ptrs[1], ra_all, on_device=True)
+            rc, data, status = pk.host_prove_batch(self.transcript_name, x_all, device_ptrs[0], device_ptrs[1], ra_all, on_device=True, solve=solve)
         else:
-            rc, data, status = pk.host_prove_batch(self.transcript_name, x_all, x_all, w_all, ra_all)
+            rc, data, status = pk.host_prove_batch(self.transcript_name, x_all, x_all, w_all, ra_all, solve=solve)
         if rc:
             raise PolymathProverError(0, rc)
         plen = len(data) // count if count else 0
-        return [data[i * plen:(i + 1) * plen] if status[i] == 0 else None for i in range(count)], [int(s) for s in status]
+        proofs = [data[i * plen:(i + 1) * plen] if status[i] == 0 else None for i in range(count)]
+        if not solve:
+            return proofs, [int(s) for s in status]
+        stuck, inst = pk.solve_results(count) if count else ([], [])
+        return proofs, [int(s) for s in status], [None if int(stuck[i]) != api.NOT_STUCK else [f.fr_int(v) for v in inst[i]] for i in range(count)]
+
+    # ---- partial assignments: the caller gives the values it chooses, the device computes the rest (PM_ASSIGNMENT_SOLVE)
+    def partial_limbs(self, instance, witness):
+        """(x_limbs, w_limbs) of an assignment given as ints, with UNKNOWN (or None) where the value is to be solved."""
+        f = self.field
+        x = f.fr_limbs([0 if v is None or v is UNKNOWN else v for v in instance]).reshape(-1, 4).copy()
+        w = f.fr_limbs([0 if v is None or v is UNKNOWN else v for v in witness]).reshape(-1, 4).copy() if len(witness) else np.zeros((0, 4), dtype=np.uint64)
+        for arr, vals in ((x, instance), (w, witness)):
+            for j, v in enumerate(vals):
+                if v is None or v is UNKNOWN:
+                    arr[j] = api.UNKNOWN_LIMBS
+        return x, w
+
+    def solve_batch(self, pk, partials, device_ptrs=None):
+        """Complete partial assignments on the device: a check call with max_rows = 0 plus pm_prove_tap(10).  partials[i]: an (x_limbs,
+        w_limbs) pair (partial_limbs); device_ptrs = (d_x, d_w, mw): the rows are already in HBM and `partials` is their count.
+        -> [(stuck_row or None, instance_ints, witness_ints)]; a stuck assignment's values are None."""
+        f = self.field
+        if device_ptrs is not None:
+            count, mw = int(partials), int(device_ptrs[2])
+            rc, n_bad, _, _ = pk.r1cs_check_batch(device_ptrs[0], device_ptrs[1], 0, False, on_device=True, count=count, solve=True)
+        else:
+            pairs = [self._assignment_limbs(c) for c in partials]
+            count = len(pairs)
+            if count == 0:
+                return []
+            mw = pairs[0][1].shape[0]
+            rc, n_bad, _, _ = pk.r1cs_check_batch(np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs]), 0, False, solve=True)
+        self.ctx.check(rc)
+        stuck, _ = pk.solve_results(count)
+        rows = pk.solved_assignments(count, mw)
+        out = []
+        for i in range(count):
+            if int(stuck[i]) != api.NOT_STUCK:
+                out.append((int(stuck[i]), None, None))
+            else:
+                out.append((None, [f.fr_int(v) for v in rows[i, :pk.m0]], [f.fr_int(v) for v in rows[i, pk.m0:]]))
+        return out
 
     # ---- which constraints fail (ark-relations: ConstraintSystem::which_is_unsatisfied): what to call after a status 4
     def _assignment_limbs(self, c):
@@ -460,19 +506,21 @@ class Polymath:
         self.ctx.check(rc)
         return self._check_result(n_bad, rows, abc)
 
-    def check_batch(self, pk, circuits_or_limbs, max_rows=16, residuals=False, device_ptrs=None):
+    def check_batch(self, pk, circuits_or_limbs, max_rows=16, residuals=False, device_ptrs=None, solve=False):
         """check_assignment for many assignments of one circuit in ONE native call (pm_r1cs_check_batch).  device_ptrs = (d_x, d_w):
         count x m0 / count x mw rows in HBM, with circuits_or_limbs the count (an int) or a sequence of that length.
+        solve=True: the assignments are partial (partial_limbs) and are completed on the device first; a stuck assignment reports
+        n_bad = 2^64 - 1 and its stuck row as the only listed row.
         -> list of check_assignment results."""
         if device_ptrs is not None:
             count = circuits_or_limbs if isinstance(circuits_or_limbs, int) else len(circuits_or_limbs)
-            rc, n_bad, rows, abc = pk.r1cs_check_batch(device_ptrs[0], device_ptrs[1], max_rows, residuals, on_device=True, count=count)
+            rc, n_bad, rows, abc = pk.r1cs_check_batch(device_ptrs[0], device_ptrs[1], max_rows, residuals, on_device=True, count=count, solve=solve)
         else:
             pairs = [self._assignment_limbs(c) for c in circuits_or_limbs]
             count = len(pairs)
             x_all = np.stack([p[0] for p in pairs]) if count else np.zeros((0, 0, 4), dtype=np.uint64)
             w_all = np.stack([p[1] for p in pairs]) if count else np.zeros((0, 0, 4), dtype=np.uint64)
-            rc, n_bad, rows, abc = pk.r1cs_check_batch(x_all, w_all, max_rows, residuals)
+            rc, n_bad, rows, abc = pk.r1cs_check_batch(x_all, w_all, max_rows, residuals, solve=solve)
         self.ctx.check(rc)
         return [self._check_result(n_bad[i], rows[i], None if abc is None else abc[i]) for i in range(count)]
 

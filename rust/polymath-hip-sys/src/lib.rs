@@ -83,6 +83,10 @@ pub const PM_VERIFY_PAIRING_DEVICE: i32 = 1;
 pub const PM_VERIFY_CHALLENGES_HOST: i32 = 0;
 pub const PM_VERIFY_CHALLENGES_DEVICE: i32 = 256;
 
+// pm_assignment_flags: the `assignment_on_device` argument of pm_host_prove[_batch] and pm_r1cs_check[_batch] is a flag word
+pub const PM_ASSIGNMENT_DEVICE: i32 = 1;
+pub const PM_ASSIGNMENT_SOLVE: i32 = 2;
+
 // pm_transcript
 pub const PM_TRANSCRIPT_MERLIN: i32 = 0;
 pub const PM_TRANSCRIPT_KECCAK256: i32 = 1;

@@ -201,6 +201,18 @@ fn fr_ptr<F>(s: &[F]) -> *const u64 {
     s.as_ptr() as *const u64
 }
 
+/// Montgomery limbs of a partial assignment appended to `out`: a value's own four words, or the unknown marker (four times
+/// `u64::MAX`: not a field element on either curve) for `None`.
+fn partial_limbs<F>(vals: &[Option<F>], out: &mut Vec<u64>) {
+    for v in vals {
+        match v {
+            // SAFETY: a scalar is four u64 limbs (`curve_checked` has verified the layout before any caller gets here).
+            Some(f) => out.extend_from_slice(unsafe { core::slice::from_raw_parts(fr_ptr(core::slice::from_ref(f)), 4) }),
+            None => out.extend_from_slice(&[u64::MAX; 4]),
+        }
+    }
+}
+
 fn fr_from_raw<E: Pairing>(curve: Curve, limbs: [u64; 4]) -> E::ScalarField {
     match curve {
         Curve::Bls12_381 => same_type(ark_bls12_381::Fr::new_unchecked(BigInt::new(limbs))),
@@ -779,6 +791,109 @@ impl GpuKey {
             .iter()
             .zip(bytes.chunks_exact(proof_len))
             .map(|(&s, b)| if s == sys::PM_OK { Ok(b.to_vec()) } else { Err(Status::from_raw(s)) })
+            .collect())
+    }
+
+    /// `pm_host_prove_batch` with `PM_ASSIGNMENT_SOLVE`: the rows are PARTIAL assignments -- `None` where the library is to compute
+    /// the value on the GPU, by forward propagation through the key's constraint rows -- and every row must leave the same
+    /// entries open.  Row i = (instance with the leading one, witness, r_a).  Returns, per row, the proof bytes together with the
+    /// completed instance (what the verifier needs; `pm_prove_tap(9)`), or the row's status: `InvalidArg` for an assignment that
+    /// got stuck on a division by zero, otherwise what [`GpuKey::prove_batch`] gives it.  The outer error is the call's: an
+    /// unsolvable structure is `InvalidArg` with the row or column in the message, and nothing has been computed.
+    #[allow(clippy::type_complexity)]
+    pub fn prove_batch_from_partial<E: Pairing>(
+        &self,
+        ctx: &mut Context,
+        transcript: i32,
+        rows: &[(&[Option<E::ScalarField>], &[Option<E::ScalarField>], [E::ScalarField; 2])],
+    ) -> Result<Vec<Result<(Vec<u8>, Vec<E::ScalarField>), Status>>, HipError> {
+        let curve = curve_checked::<E>()?;
+        if curve != self.curve {
+            return Err(err(Status::InvalidArg, "key of another curve"));
+        }
+        let (mut x, mut w, mut ra) = (Vec::new(), Vec::new(), Vec::new());
+        for (xi, wi, ri) in rows {
+            if xi.len() as u64 != self.m0 || wi.len() as u64 != self.mw {
+                return Err(err(Status::LenMismatch, "a row's instance / witness length is not the key's"));
+            }
+            partial_limbs(xi, &mut x);
+            partial_limbs(wi, &mut w);
+            ra.extend_from_slice(ri);
+        }
+        let proof_len = 3 * 8 * curve.fq_limbs() + 32;
+        let mut bytes = vec![0u8; proof_len * rows.len()];
+        let mut status = vec![0i32; rows.len()];
+        let w_ptr = if w.is_empty() { core::ptr::null() } else { w.as_ptr() };
+        // SAFETY: live key and context; x / w hold rows.len() records of m0 / mw elements of 4 limbs, ra rows.len() records of 2
+        // elements (layout checked), `bytes` and `status` have room for rows.len() records.  The arrays are only read.
+        let rc = unsafe {
+            sys::pm_host_prove_batch(ctx.raw, self.raw, transcript, rows.len(), x.as_ptr(), x.as_ptr(), w_ptr, sys::PM_ASSIGNMENT_SOLVE, fr_ptr(&ra),
+                                     bytes.as_mut_ptr(), proof_len, status.as_mut_ptr())
+        };
+        ctx.check(rc)?;
+        let solved = if rows.is_empty() { Vec::new() } else { self.solve_results::<E>(ctx, rows.len())? };
+        Ok(status
+            .iter()
+            .zip(bytes.chunks_exact(proof_len))
+            .zip(solved)
+            .map(|((&s, b), (_, inst))| if s == sys::PM_OK { Ok((b.to_vec(), inst)) } else { Err(Status::from_raw(s)) })
+            .collect())
+    }
+
+    /// `pm_r1cs_check_batch` with `PM_ASSIGNMENT_SOLVE` and no rows asked for: complete partial assignments (`None` = to be computed)
+    /// without proving.  Returns, per assignment, its stuck row (`Some(row)`: a division by zero there, the instance is then all
+    /// zero) and the completed instance, leading one included.
+    #[allow(clippy::type_complexity)]
+    pub fn solve<E: Pairing>(
+        &self,
+        ctx: &mut Context,
+        rows: &[(&[Option<E::ScalarField>], &[Option<E::ScalarField>])],
+    ) -> Result<Vec<(Option<u64>, Vec<E::ScalarField>)>, HipError> {
+        let curve = curve_checked::<E>()?;
+        if curve != self.curve {
+            return Err(err(Status::InvalidArg, "key of another curve"));
+        }
+        if rows.is_empty() {
+            return Ok(Vec::new());
+        }
+        let (mut x, mut w) = (Vec::new(), Vec::new());
+        for (xi, wi) in rows {
+            if xi.len() as u64 != self.m0 || wi.len() as u64 != self.mw {
+                return Err(err(Status::LenMismatch, "a row's instance / witness length is not the key's"));
+            }
+            partial_limbs(xi, &mut x);
+            partial_limbs(wi, &mut w);
+        }
+        let mut n_bad = vec![0u64; rows.len()];
+        let w_ptr = if w.is_empty() { core::ptr::null() } else { w.as_ptr() };
+        // SAFETY: live key and context; x / w hold rows.len() records of m0 / mw elements of 4 limbs; no rows, no residuals.
+        let rc = unsafe {
+            sys::pm_r1cs_check_batch(ctx.raw, self.raw, rows.len(), x.as_ptr(), w_ptr, sys::PM_ASSIGNMENT_SOLVE, 0, n_bad.as_mut_ptr(), core::ptr::null_mut(),
+                                     core::ptr::null_mut())
+        };
+        ctx.check(rc)?;
+        self.solve_results::<E>(ctx, rows.len())
+    }
+
+    /// `pm_prove_tap(9)`: stuck row and completed instance of each of the `count` assignments of the last solving call on `ctx`.
+    #[allow(clippy::type_complexity)]
+    fn solve_results<E: Pairing>(&self, ctx: &mut Context, count: usize) -> Result<Vec<(Option<u64>, Vec<E::ScalarField>)>, HipError> {
+        let per = 1 + self.m0 as usize;
+        let mut raw = vec![0u64; 4 * per * count];
+        let mut n = 0usize;
+        // SAFETY: live context; `raw` holds per * count elements of 4 limbs.
+        let rc = unsafe { sys::pm_prove_tap(ctx.raw, 9, raw.as_mut_ptr(), per * count, &mut n) };
+        ctx.check(rc)?;
+        if n != per * count {
+            return Err(err(Status::InvalidArg, "solve_results: the last solving call had another count"));
+        }
+        let limbs = |i: usize| [raw[i], raw[i + 1], raw[i + 2], raw[i + 3]];
+        Ok((0..count)
+            .map(|r| {
+                let at = 4 * per * r;
+                let stuck = if raw[at] == u64::MAX { None } else { Some(raw[at]) };
+                (stuck, (1..per).map(|j| fr_from_raw::<E>(self.curve, limbs(at + 4 * j))).collect())
+            })
             .collect())
     }
 

@@ -4,7 +4,12 @@
 and printing proofs/s for both plus the stage split of pm_last_timings (summed over the batch for (a); one proof for (b)).
   python tools/prove_bench.py --circuit mimc322 --batch 256 --reps 5
   python tools/prove_bench.py --circuit bench:32000 --batch 16 --reps 3        BenchCircuit with 32000 constraints: n = 2^16
-The B rows cycle through min(B, 32) distinct seeded assignments with distinct r_a (a proof's cost does not depend on its values)."""
+The B rows cycle through min(B, 32) distinct seeded assignments with distinct r_a (a proof's cost does not depend on its values).
+  python tools/prove_bench.py --circuit mimc322 --batch 256 --reps 5 --solve
+compares inputs -> proofs instead (mimcK only), host limbs in both routes, alternating in this process:
+  (a) the B assignments synthesised on the host (MiMCDemo.generate_constraints, Python integers), then one pm_host_prove_batch call
+  (b) B partial assignments (xl, xr given, everything else the unknown marker), one pm_host_prove_batch call with PM_ASSIGNMENT_SOLVE
+Every rep of (a) synthesises all B assignments again: that is the step (b) moves to the GPU."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -20,7 +25,10 @@ ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--curve", default="bls12_381")
 ap.add_argument("--transcript", default="merlin")
 ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="pm_ctx_set_option before the key is made, e.g. --opt tables=0")
+ap.add_argument("--solve", action="store_true", help="host-synthesised assignments against partial assignments solved on the GPU")
 a = ap.parse_args()
+if a.solve and not a.circuit.startswith("mimc"):
+    ap.error("--solve needs a mimcK circuit")
 pm = Polymath(a.curve, a.transcript, device=0)
 for kv in a.opt:
     pm.ctx.set_option(kv.split("=", 1)[0], int(kv.split("=", 1)[1]))
@@ -51,6 +59,53 @@ torch.cuda.synchronize()
 m0, mw = xs.shape[1], ws.shape[1]
 
 
+def solve_comparison():
+    inputs = [(circuits[i].xl, circuits[i].xr) for i in pick]
+    ra_all = [rows[i][2] for i in pick]
+    partial = [pm.partial_limbs([1, None], [xl, xr] + [None] * (mw - 2)) for xl, xr in inputs]
+
+    def run_host():
+        t0 = time.perf_counter()
+        t_syn = 0.0
+        full = []
+        for xl, xr in inputs:
+            _, inst, wit = pm._synthesize(PC.MiMCDemo(xl, xr, consts))
+            full.append((pm.field.fr_limbs(inst), pm.field.fr_limbs(wit)))
+        t_syn = time.perf_counter() - t0
+        proofs, status = pm.prove_batch(pk, full, ra_all)
+        assert not any(status)
+        return time.perf_counter() - t0, t_syn, proofs, pm.ctx.timings()
+
+    def run_solve():
+        t0 = time.perf_counter()
+        proofs, status, _ = pm.prove_batch(pk, partial, ra_all, solve=True)
+        assert not any(status)
+        return time.perf_counter() - t0, proofs, pm.ctx.timings()
+
+    _, _, ph, _ = run_host()
+    _, ps, _ = run_solve()
+    th, tsyn, tsv = [], [], []
+    for _ in range(a.reps):
+        dt, syn, _, tm_host = run_host()
+        th.append(dt)
+        tsyn.append(syn)
+        dt, _, tm_solve = run_solve()
+        tsv.append(dt)
+    print(json.dumps({"curve": a.curve, "circuit": a.circuit, "n": pk.n, "batch": B, "bytes_equal": ph == ps, "setup_s": round(setup_s, 3),
+                      "host_synthesis_ms": [round(t * 1e3, 3) for t in th], "of_which_synthesis_ms": [round(t * 1e3, 3) for t in tsyn],
+                      "solve_ms": [round(t * 1e3, 3) for t in tsv],
+                      "host_proofs_per_s": round(B / med(th), 1), "solve_proofs_per_s": round(B / med(tsv), 1),
+                      "solve_over_host": round(med(th) / med(tsv), 3),
+                      "host_stage_ms_sum_over_batch": {k: round(v, 3) for k, v in tm_host.items()},
+                      "solve_stage_ms_sum_over_batch": {k: round(v, 3) for k, v in tm_solve.items()}}))
+
+
+med = lambda v: sorted(v)[len(v) // 2]
+if a.solve:
+    solve_comparison()
+    sys.exit(0)
+
+
 def run_batch():
     t0 = time.perf_counter()
     rc, data, status = pk.host_prove_batch(a.transcript, xs, dx.data_ptr(), dw.data_ptr(), ras, on_device=True)
@@ -78,7 +133,6 @@ for _ in range(a.reps):
     ta.append(dt)
     dt, _, tm_one = run_loop()
     tb.append(dt)
-med = lambda v: sorted(v)[len(v) // 2]
 print(json.dumps({"curve": a.curve, "circuit": a.circuit, "n": pk.n, "batch": B, "bytes_equal": db == dl, "setup_s": round(setup_s, 3),
                   "batch_ms": [round(t * 1e3, 3) for t in ta], "loop_ms": [round(t * 1e3, 3) for t in tb],
                   "batch_proofs_per_s": round(B / med(ta), 1), "loop_proofs_per_s": round(B / med(tb), 1),
