@@ -13,6 +13,7 @@
 #include "internal.h"
 #include "comm.h"
 #include "fq28.cuh"
+#include "prove_common.cuh"
 #include "../host/hashes.hpp"
 
 using namespace pm;
@@ -963,7 +964,7 @@ static int pk_generate_impl(pm_ctx *ctx, uint64_t m0, uint64_t mw, uint64_t nr, 
     st = pk_upload_matrices<C>(ctx, pk, a, b, c);
     if (st) return guard(st);
     hp.mark("matrices: first-entry pass + upload");
-    const uint64_t n = pk->n, sigma = pk->sigma, Lz = 2 * m0 + mw + nr;
+    const uint64_t n = pk->n, sigma = pk->sigma, Lz = proof_shape(pk).Lz;
     Fr x, z, omega;
     memcpy(x.l, x_trap, 32);
     memcpy(z.l, z_trap, 32);
@@ -1251,7 +1252,8 @@ extern "C" int pm_prove_tap(pm_ctx *ctx, int which, uint64_t *out, size_t max_el
     if (!ctx->pk || ctx->phase < 1) return PM_ERR_STATE;
     PM_TRY(set_device(ctx));
     const pm_pk *pk = ctx->pk;
-    const uint64_t n = pk->n, Lz = 2 * pk->m0 + pk->mw + pk->nr;
+    const pm::ProofShape shape = pm::proof_shape(pk);
+    const uint64_t n = shape.n, Lz = shape.Lz;
     const void *src = nullptr;
     size_t cnt = 0;
     if (pk->layout == PM_SHARD_VECTOR) {
@@ -1285,7 +1287,7 @@ extern "C" int pm_prove_tap(pm_ctx *ctx, int which, uint64_t *out, size_t max_el
         case 6: src = ctx->sc_c.p; cnt = Lz; break;
         case 7:
             if (ctx->phase < 3) return PM_ERR_STATE;
-            src = ctx->quotient.p; cnt = 8 * pk->sigma + 2 * n - 2; break;
+            src = ctx->quotient.p; cnt = shape.len_d; break;
         default: return PM_ERR_INVALID_ARG;
     }
     *n_elems = cnt;

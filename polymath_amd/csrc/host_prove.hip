@@ -3,6 +3,7 @@
 // transcripts of src/transcript/*.rs, challenge arithmetic of common.rs:21-98, ark wire format) driven on the
 // caller's context.  The three phases stay the boundary; this is their caller, compiled once.
 #include "internal.h"
+#include "prove_common.cuh"
 #include "../host/polymath.hpp"
 #include "../host/wire.hpp"
 
@@ -260,10 +261,7 @@ int host_prove_batch_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint
             if (rc != PM_OK) break;
             std::vector<Glue> glue(rows);
             for (size_t b = 0; b < rows; ++b) {
-                const unsigned hf = flags[b];
-                stat[b] = (hf & 1u) ? PM_ERR_REMAINDER_NONZERO                      // prover.rs:108
-                          : ((hf & 2u) || !(hf & 4u)) ? PM_ERR_DEGREE_BOUND         // prover.rs:107
-                                                      : PM_OK;
+                stat[b] = pm::phase1_flag_status(flags[b]);
                 x1[b] = x2[b] = a_at[b] = c_at[b] = Fr::zero();     // a refused proof rides along on zeros; its results are dropped
                 if (solve && pm::solve_tap9_row(ctx, pk, g0 + b)[0] != NOT_STUCK) stat[b] = PM_ERR_INVALID_ARG;   // stuck: its row holds no assignment
                 if (stat[b] != PM_OK) continue;
@@ -286,7 +284,7 @@ int host_prove_batch_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint
             if (rc != PM_OK) break;
             for (size_t b = 0; b < rows; ++b) {
                 uint8_t *out = proofs + (g0 + b) * proof_len;
-                if (stat[b] == PM_OK && (flags[b] & 8u)) stat[b] = PM_ERR_REMAINDER_NONZERO;   // prover.rs:221
+                if (stat[b] == PM_OK) stat[b] = pm::phase3_flag_status(flags[b]);
                 if (stat[b] == PM_OK) {
                     proof[b].d_g1.p = pd[b]; proof[b].d_g1.inf = id[b] != 0;
                     const pmhost::Bytes bytes = proof[b].to_bytes();

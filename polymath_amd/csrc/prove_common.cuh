@@ -49,6 +49,45 @@ struct NumConsts {
     Fp<P> x2, r0, r1, x2r0, x2r1, b2[3], two_x2_r0, two_x2_r1, minus_const;
 };
 
+// The lengths of one proof's vectors on an unsharded key, and the level plan of the division scan (prove_kernels.cuh): level l holds
+// cnt[l] values, DIV_L of them per lane, until the top level is <= 64 values for one lane (16^6 covers every domain of both curves).
+constexpr unsigned DIV_L = 16;      // 16 puts 20 K waves on the chip at 2^20 (32: 10 K, half of its wave slots idle): 0.98 -> 0.90 ms
+constexpr unsigned HORNER_L = 16;   // coefficients per lane of the phase-2 Horner sum
+struct ProofShape {
+    uint64_t n, m0, mw, nr, sigma;
+    uint64_t Lz;        // |z_tail| = M - m0
+    uint64_t len_a;     // [a]_1 scalars: u (n) | 0 | r_a (2)
+    uint64_t len_c;     // [c]_1 scalars: z_tail | h (n-1) | 2 r_a u (n+1) | r_a^2 (3) | r_a (2)
+    uint64_t num_len;   // coefficients of the numerator (numerator_at's table)
+    uint64_t len_d;     // [d]_1 scalars: the quotient
+    uint64_t cnt[8];
+    int levels;
+};
+static inline ProofShape proof_shape(uint64_t n, uint64_t m0, uint64_t mw, uint64_t nr, uint64_t sigma) {
+    ProofShape s{};
+    s.n = n; s.m0 = m0; s.mw = mw; s.nr = nr; s.sigma = sigma;
+    s.Lz = 2 * m0 + mw + nr;
+    s.len_a = n + 3;
+    s.len_c = s.Lz + (n - 1) + (n + 1) + 3 + 2;
+    s.num_len = 8 * sigma + 2 * n - 1;
+    s.len_d = s.num_len - 1;
+    s.cnt[0] = s.num_len;
+    while (s.cnt[s.levels] > 64 && s.levels < 6) {
+        s.cnt[s.levels + 1] = (s.cnt[s.levels] + DIV_L - 1) / DIV_L;
+        ++s.levels;
+    }
+    return s;
+}
+static inline ProofShape proof_shape(const pm_pk *pk) { return proof_shape(pk->n, pk->m0, pk->mw, pk->nr, pk->sigma); }
+
+// The flag word of a proof (k_check_sap) as a status.  Phase 1 reads bits 0-2, phase 3 bit 3.
+static inline int phase1_flag_status(unsigned flags) {
+    if (flags & 1u) return PM_ERR_REMAINDER_NONZERO;                  // prover.rs:108
+    if ((flags & 2u) || !(flags & 4u)) return PM_ERR_DEGREE_BOUND;    // prover.rs:107
+    return PM_OK;
+}
+static inline int phase3_flag_status(unsigned flags) { return (flags & 8u) ? PM_ERR_REMAINDER_NONZERO : PM_OK; }   // prover.rs:221
+
 // ------------------------------------------------------------------------------- helpers
 template <class P>
 static inline Fp<P> load_fr(const uint64_t *p) {
