@@ -64,9 +64,6 @@ static void repack_bases(const void *src, size_t stride, size_t len, Affine<C> *
     }
 }
 
-#define PM_DISPATCH(curve, CALL_BLS, CALL_BN) \
-    ((curve) == PM_BLS12_381 ? (CALL_BLS) : (curve) == PM_BN254 ? (CALL_BN) : (int)PM_ERR_INVALID_ARG)
-
 static int set_device(pm_ctx *ctx) {
     PM_HIP(ctx, hipSetDevice(ctx->device));
     return PM_OK;
@@ -173,11 +170,10 @@ extern "C" void pm_ctx_destroy(pm_ctx *ctx) {
     MsmWorkspace &m = ctx->msm;
     for (DevBuf *b : {&m.set.sorted, &m.set.counts, &m.set.bucket_off, &m.set.task_off, &m.set.tasks, &m.set.partials, &m.set.task_cnt}) b->release();
     for (DevBuf *b : {&m.digits, &m.cursor, &m.wsum,
-                      &m.region, &m.sub, &m.digits2, &m.len_bins, &m.block_cnt, &m.hot, &m.batch, &ctx->scratch, &ctx->flags, &ctx->xw, &ctx->ue, &ctx->we, &ctx->u, &ctx->w,
-                      &ctx->wit_u, &ctx->u2, &ctx->sc_a, &ctx->sc_c, &ctx->quotient, &ctx->ztail, &ctx->ra, &ctx->sh_a, &ctx->sh_b, &ctx->sh_c, &ctx->halo,
+                      &m.region, &m.sub, &m.digits2, &m.len_bins, &m.block_cnt, &m.hot, &m.batch, &ctx->scratch, &ctx->sh_a, &ctx->sh_b, &ctx->sh_c, &ctx->halo,
                       &ctx->shard_roots, &ctx->ntt_tmp})
         b->release();
-    for (auto &b : ctx->lvl) b.release();
+    ctx->pw.release();
     ctx->pb.release();
     ctx->sv.release();
     for (auto &b : ctx->fb_table) b.release();
@@ -221,7 +217,7 @@ static int ntt_host(pm_ctx *ctx, uint64_t *data, unsigned log_n, int inverse) {
 extern "C" int pm_ntt(pm_ctx *ctx, int curve, uint64_t *data, unsigned log_n, int inverse) {
     if (!ctx || !data) return PM_ERR_INVALID_ARG;
     PM_TRY(set_device(ctx));
-    return PM_DISPATCH(curve, ntt_host<BlsCurve>(ctx, data, log_n, inverse), ntt_host<BnCurve>(ctx, data, log_n, inverse));
+    return with_curve(curve, [&](auto cv) { return ntt_host<type_of<decltype(cv)>>(ctx, data, log_n, inverse); });
 }
 
 template <class C>
@@ -236,7 +232,7 @@ static int ntt_dev(pm_ctx *ctx, uint64_t *d, unsigned log_n, int inverse) {
 extern "C" int pm_ntt_device(pm_ctx *ctx, int curve, uint64_t *d_data, unsigned log_n, int inverse) {
     if (!ctx || !d_data) return PM_ERR_INVALID_ARG;
     PM_TRY(set_device(ctx));
-    return PM_DISPATCH(curve, ntt_dev<BlsCurve>(ctx, d_data, log_n, inverse), ntt_dev<BnCurve>(ctx, d_data, log_n, inverse));
+    return with_curve(curve, [&](auto cv) { return ntt_dev<type_of<decltype(cv)>>(ctx, d_data, log_n, inverse); });
 }
 
 template <class C>
@@ -251,8 +247,7 @@ static int ntt_batch_dev(pm_ctx *ctx, uint64_t *d, unsigned log_n, int inverse, 
 extern "C" int pm_ntt_batch_device(pm_ctx *ctx, int curve, uint64_t *d_data, unsigned log_n, int inverse, size_t rows, size_t row_stride) {
     if (!ctx || !d_data) return PM_ERR_INVALID_ARG;
     PM_TRY(set_device(ctx));
-    return PM_DISPATCH(curve, ntt_batch_dev<BlsCurve>(ctx, d_data, log_n, inverse, rows, row_stride),
-                       ntt_batch_dev<BnCurve>(ctx, d_data, log_n, inverse, rows, row_stride));
+    return with_curve(curve, [&](auto cv) { return ntt_batch_dev<type_of<decltype(cv)>>(ctx, d_data, log_n, inverse, rows, row_stride); });
 }
 
 // ---------------------------------------------------------------------------------- MSM
@@ -287,8 +282,7 @@ static int bases_upload_impl(pm_ctx *ctx, const void *bases, size_t stride, size
 extern "C" int pm_bases_upload(pm_ctx *ctx, int curve, const void *bases, size_t base_stride, size_t len, pm_bases **out) {
     if (!ctx || !out || (len && !bases)) return PM_ERR_INVALID_ARG;
     PM_TRY(set_device(ctx));
-    return PM_DISPATCH(curve, bases_upload_impl<BlsCurve>(ctx, bases, base_stride, len, out),
-                       bases_upload_impl<BnCurve>(ctx, bases, base_stride, len, out));
+    return with_curve(curve, [&](auto cv) { return bases_upload_impl<type_of<decltype(cv)>>(ctx, bases, base_stride, len, out); });
 }
 
 template <class C>
@@ -305,7 +299,7 @@ static int bases_multiples_impl(pm_ctx *ctx, size_t len, pm_bases **out) {
 extern "C" int pm_bases_generate_multiples(pm_ctx *ctx, int curve, size_t len, pm_bases **out) {
     if (!ctx || !out) return PM_ERR_INVALID_ARG;
     PM_TRY(set_device(ctx));
-    return PM_DISPATCH(curve, bases_multiples_impl<BlsCurve>(ctx, len, out), bases_multiples_impl<BnCurve>(ctx, len, out));
+    return with_curve(curve, [&](auto cv) { return bases_multiples_impl<type_of<decltype(cv)>>(ctx, len, out); });
 }
 
 // device -> host copy of resident (internal-form) points, converted back to standard Montgomery form
@@ -325,7 +319,7 @@ extern "C" int pm_bases_download(pm_ctx *ctx, const pm_bases *b, size_t offset, 
     PM_TRY(set_device(ctx));
     size_t pt = b->curve == PM_BLS12_381 ? sizeof(Affine<BlsCurve>) : sizeof(Affine<BnCurve>);
     const void *src = (const uint8_t *)b->d_points + offset * pt;
-    return PM_DISPATCH(b->curve, download_points<BlsCurve>(ctx, src, len, out_xy), download_points<BnCurve>(ctx, src, len, out_xy));
+    return with_curve(b->curve, [&](auto cv) { return download_points<type_of<decltype(cv)>>(ctx, src, len, out_xy); });
 }
 
 template <class C>
@@ -357,7 +351,7 @@ static int bases_precompute_impl(pm_ctx *ctx, pm_bases *b) {
 extern "C" int pm_bases_precompute(pm_ctx *ctx, pm_bases *b) {
     if (!ctx || !b) return PM_ERR_INVALID_ARG;
     PM_TRY(set_device(ctx));
-    return PM_DISPATCH(b->curve, bases_precompute_impl<BlsCurve>(ctx, b), bases_precompute_impl<BnCurve>(ctx, b));
+    return with_curve(b->curve, [&](auto cv) { return bases_precompute_impl<type_of<decltype(cv)>>(ctx, b); });
 }
 
 extern "C" size_t pm_bases_len(const pm_bases *b) { return b ? b->len : 0; }
@@ -396,9 +390,9 @@ extern "C" int pm_msm_g1_resident(pm_ctx *ctx, const pm_bases *bases, size_t bas
     if (!ctx || !bases || !out_xy || !out_inf || (len && !scalars)) return PM_ERR_INVALID_ARG;
     if (base_offset + len > bases->len) return PM_ERR_LEN_MISMATCH;  // prover.rs:381
     PM_TRY(set_device(ctx));
-    return PM_DISPATCH(bases->curve,
-                       msm_resident_impl<BlsCurve>(ctx, bases, base_offset, scalars, scalars_on_device, len, out_xy, out_inf),
-                       msm_resident_impl<BnCurve>(ctx, bases, base_offset, scalars, scalars_on_device, len, out_xy, out_inf));
+    return with_curve(bases->curve, [&](auto cv) {
+        return msm_resident_impl<type_of<decltype(cv)>>(ctx, bases, base_offset, scalars, scalars_on_device, len, out_xy, out_inf);
+    });
 }
 
 template <class C>
@@ -432,9 +426,9 @@ extern "C" int pm_msm_g1_resident_batch(pm_ctx *ctx, const pm_bases *bases, size
     if (base_offset + len > bases->len) return PM_ERR_LEN_MISMATCH;
     if (batch == 0) return PM_OK;
     PM_TRY(set_device(ctx));
-    return PM_DISPATCH(bases->curve,
-                       msm_resident_batch_impl<BlsCurve>(ctx, bases, base_offset, scalars, scalars_on_device, len, batch, out_xy, out_inf),
-                       msm_resident_batch_impl<BnCurve>(ctx, bases, base_offset, scalars, scalars_on_device, len, batch, out_xy, out_inf));
+    return with_curve(bases->curve, [&](auto cv) {
+        return msm_resident_batch_impl<type_of<decltype(cv)>>(ctx, bases, base_offset, scalars, scalars_on_device, len, batch, out_xy, out_inf);
+    });
 }
 
 extern "C" int pm_msm_g1(pm_ctx *ctx, int curve, const void *bases, size_t base_stride, const uint64_t *scalars,
@@ -466,8 +460,7 @@ static int g1_sum_impl(const uint64_t *pts, const int *infs, size_t count, uint6
 
 extern "C" int pm_g1_sum(int curve, const uint64_t *points_xy, const int *infs, size_t count, uint64_t *out_xy, int *out_inf) {
     if (!out_xy || !out_inf || (count && !points_xy)) return PM_ERR_INVALID_ARG;
-    return PM_DISPATCH(curve, g1_sum_impl<BlsCurve>(points_xy, infs, count, out_xy, out_inf),
-                       g1_sum_impl<BnCurve>(points_xy, infs, count, out_xy, out_inf));
+    return with_curve(curve, [&](auto cv) { return g1_sum_impl<type_of<decltype(cv)>>(points_xy, infs, count, out_xy, out_inf); });
 }
 
 // ------------------------------------------------------------------------- proving key
@@ -798,8 +791,9 @@ extern "C" int pm_pk_load_sharded(pm_ctx *ctx, int curve, uint64_t n, uint64_t m
                                   int shard_rank, int shard_count, int layout, pm_pk **out) {
     if (!ctx || !a || !b || !c || !bases || !out) return PM_ERR_INVALID_ARG;
     PM_TRY(set_device(ctx));
-    return PM_DISPATCH(curve, pk_load_impl<BlsCurve>(ctx, n, m0, mw, nr, sigma, a, b, c, bases, shard_rank, shard_count, layout, out),
-                       pk_load_impl<BnCurve>(ctx, n, m0, mw, nr, sigma, a, b, c, bases, shard_rank, shard_count, layout, out));
+    return with_curve(curve, [&](auto cv) {
+        return pk_load_impl<type_of<decltype(cv)>>(ctx, n, m0, mw, nr, sigma, a, b, c, bases, shard_rank, shard_count, layout, out);
+    });
 }
 
 extern "C" int pm_pk_load(pm_ctx *ctx, int curve, uint64_t n, uint64_t m0, uint64_t mw, uint64_t nr, uint64_t sigma,
@@ -907,8 +901,9 @@ extern "C" int pm_pk_load_bytes(pm_ctx *ctx, int curve, const uint8_t *bytes, si
     *out = nullptr;
     PM_TRY(set_device(ctx));
     try {
-        return PM_DISPATCH(curve, pk_load_bytes_impl<BlsCurve>(ctx, bytes, len, validate, shard_rank, shard_count, layout, out),
-                           pk_load_bytes_impl<BnCurve>(ctx, bytes, len, validate, shard_rank, shard_count, layout, out));
+        return with_curve(curve, [&](auto cv) {
+            return pk_load_bytes_impl<type_of<decltype(cv)>>(ctx, bytes, len, validate, shard_rank, shard_count, layout, out);
+        });
     } catch (const std::exception &e) {       // host allocation failure while parsing the matrices: a status, never an abort
         ctx->err = e.what();
         return PM_ERR_STATE;
@@ -939,8 +934,7 @@ extern "C" int pm_g1_decode(pm_ctx *ctx, int curve, const uint8_t *in, size_t co
     if (!ctx || (count && (!in || !out_xy || !status))) return PM_ERR_INVALID_ARG;
     if (!count) return PM_OK;
     PM_TRY(set_device(ctx));
-    return PM_DISPATCH(curve, g1_decode_impl<BlsCurve>(ctx, in, count, validate, out_xy, status),
-                       g1_decode_impl<BnCurve>(ctx, in, count, validate, out_xy, status));
+    return with_curve(curve, [&](auto cv) { return g1_decode_impl<type_of<decltype(cv)>>(ctx, in, count, validate, out_xy, status); });
 }
 
 // generate_proving_key (generator.rs:24-167) with the trapdoors supplied.  The dense uj_wj_lcs loop
@@ -1028,8 +1022,9 @@ extern "C" int pm_pk_generate_sharded(pm_ctx *ctx, int curve, uint64_t m0, uint6
     if (!ctx || !a || !b || !c || !x_trapdoor || !z_trapdoor || !out) return PM_ERR_INVALID_ARG;
     PM_TRY(set_device(ctx));
     try {
-        return PM_DISPATCH(curve, pk_generate_impl<BlsCurve>(ctx, m0, mw, nr, a, b, c, x_trapdoor, z_trapdoor, shard_rank, shard_count, layout, out),
-                           pk_generate_impl<BnCurve>(ctx, m0, mw, nr, a, b, c, x_trapdoor, z_trapdoor, shard_rank, shard_count, layout, out));
+        return with_curve(curve, [&](auto cv) {
+            return pk_generate_impl<type_of<decltype(cv)>>(ctx, m0, mw, nr, a, b, c, x_trapdoor, z_trapdoor, shard_rank, shard_count, layout, out);
+        });
     } catch (const std::exception &e) {       // host allocation failure in the O(n) setup vectors: a status, never an abort
         ctx->err = e.what();
         return PM_ERR_STATE;
@@ -1114,7 +1109,7 @@ extern "C" int pm_pk_export_bases(pm_ctx *ctx, const pm_pk *pk, int which, size_
     uint64_t dev_off = 0;
     if (!pk_dev_range(pk, which, offset, len, &dev_off)) return PM_ERR_INVALID_ARG;  // not resident on this shard
     const void *src = (const uint8_t *)pk->d_bases + dev_off * pt;
-    return PM_DISPATCH(pk->curve, download_points<BlsCurve>(ctx, src, len, out_xy), download_points<BnCurve>(ctx, src, len, out_xy));
+    return with_curve(pk->curve, [&](auto cv) { return download_points<type_of<decltype(cv)>>(ctx, src, len, out_xy); });
 }
 
 // resident (internal-form) points -> standard form -> compressed records, in chunks through the context's scratch
@@ -1142,8 +1137,9 @@ extern "C" int pm_pk_export_bases_compressed(pm_ctx *ctx, const pm_pk *pk, int w
     uint64_t dev_off = 0;
     if (!pk_dev_range(pk, which, offset, len, &dev_off)) return PM_ERR_INVALID_ARG;  // not resident on this shard
     if (!len) return PM_OK;
-    return PM_DISPATCH(pk->curve, export_compressed_impl<BlsCurve>(ctx, (const Affine<BlsCurve> *)pk->d_bases + dev_off, len, out),
-                       export_compressed_impl<BnCurve>(ctx, (const Affine<BnCurve> *)pk->d_bases + dev_off, len, out));
+    return with_curve(pk->curve, [&](auto cv) {
+        return export_compressed_impl<type_of<decltype(cv)>>(ctx, (const Affine<type_of<decltype(cv)>> *)pk->d_bases + dev_off, len, out);
+    });
 }
 
 // -------------------------------------------------------------------------------- prove
@@ -1180,11 +1176,11 @@ extern "C" int pm_prove_phase1(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, 
     if (pk->device != ctx->device) return PM_ERR_INVALID_ARG;
     PM_TRY(set_device(ctx));
     return guarded(ctx, [&] {
-        if (pk->layout == PM_SHARD_VECTOR)
-            return PM_DISPATCH(pk->curve, prove_phase1_sharded<BlsCurve>(ctx, pk, x, w, r_a, a_g1_xy, a_inf, c_g1_xy, c_inf, false),
-                               prove_phase1_sharded<BnCurve>(ctx, pk, x, w, r_a, a_g1_xy, a_inf, c_g1_xy, c_inf, false));
-        return PM_DISPATCH(pk->curve, prove_phase1_impl<BlsCurve>(ctx, pk, x, w, r_a, a_g1_xy, a_inf, c_g1_xy, c_inf, false),
-                           prove_phase1_impl<BnCurve>(ctx, pk, x, w, r_a, a_g1_xy, a_inf, c_g1_xy, c_inf, false));
+        return with_curve(pk->curve, [&](auto cv) {
+            typedef type_of<decltype(cv)> C;
+            return pk->layout == PM_SHARD_VECTOR ? prove_phase1_sharded<C>(ctx, pk, x, w, r_a, a_g1_xy, a_inf, c_g1_xy, c_inf, false)
+                                                 : prove_phase1_impl<C>(ctx, pk, x, w, r_a, a_g1_xy, a_inf, c_g1_xy, c_inf, false);
+        });
     });
 }
 
@@ -1194,11 +1190,11 @@ extern "C" int pm_prove_phase1_device(pm_ctx *ctx, const pm_pk *pk, const uint64
     if (pk->device != ctx->device) return PM_ERR_INVALID_ARG;
     PM_TRY(set_device(ctx));
     return guarded(ctx, [&] {
-        if (pk->layout == PM_SHARD_VECTOR)
-            return PM_DISPATCH(pk->curve, prove_phase1_sharded<BlsCurve>(ctx, pk, d_x, d_w, r_a, a_g1_xy, a_inf, c_g1_xy, c_inf, true),
-                               prove_phase1_sharded<BnCurve>(ctx, pk, d_x, d_w, r_a, a_g1_xy, a_inf, c_g1_xy, c_inf, true));
-        return PM_DISPATCH(pk->curve, prove_phase1_impl<BlsCurve>(ctx, pk, d_x, d_w, r_a, a_g1_xy, a_inf, c_g1_xy, c_inf, true),
-                           prove_phase1_impl<BnCurve>(ctx, pk, d_x, d_w, r_a, a_g1_xy, a_inf, c_g1_xy, c_inf, true));
+        return with_curve(pk->curve, [&](auto cv) {
+            typedef type_of<decltype(cv)> C;
+            return pk->layout == PM_SHARD_VECTOR ? prove_phase1_sharded<C>(ctx, pk, d_x, d_w, r_a, a_g1_xy, a_inf, c_g1_xy, c_inf, true)
+                                                 : prove_phase1_impl<C>(ctx, pk, d_x, d_w, r_a, a_g1_xy, a_inf, c_g1_xy, c_inf, true);
+        });
     });
 }
 
@@ -1207,9 +1203,10 @@ extern "C" int pm_prove_phase2(pm_ctx *ctx, const uint64_t *x1, uint64_t *u_at_x
     if (!ctx->pk) return PM_ERR_STATE;
     PM_TRY(set_device(ctx));
     return guarded(ctx, [&] {
-        if (ctx->pk->layout == PM_SHARD_VECTOR)
-            return PM_DISPATCH(ctx->pk->curve, prove_phase2_sharded<BlsCurve>(ctx, x1, u_at_x1), prove_phase2_sharded<BnCurve>(ctx, x1, u_at_x1));
-        return PM_DISPATCH(ctx->pk->curve, prove_phase2_impl<BlsCurve>(ctx, x1, u_at_x1), prove_phase2_impl<BnCurve>(ctx, x1, u_at_x1));
+        return with_curve(ctx->pk->curve, [&](auto cv) {
+            typedef type_of<decltype(cv)> C;
+            return ctx->pk->layout == PM_SHARD_VECTOR ? prove_phase2_sharded<C>(ctx, x1, u_at_x1) : prove_phase2_impl<C>(ctx, x1, u_at_x1);
+        });
     });
 }
 
@@ -1219,11 +1216,11 @@ extern "C" int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *
     if (!ctx->pk) return PM_ERR_STATE;
     PM_TRY(set_device(ctx));
     return guarded(ctx, [&] {
-        if (ctx->pk->layout == PM_SHARD_VECTOR)
-            return PM_DISPATCH(ctx->pk->curve, prove_phase3_sharded<BlsCurve>(ctx, x1, x2, a_at_x1, c_at_x1, d_g1_xy, d_inf),
-                               prove_phase3_sharded<BnCurve>(ctx, x1, x2, a_at_x1, c_at_x1, d_g1_xy, d_inf));
-        return PM_DISPATCH(ctx->pk->curve, prove_phase3_impl<BlsCurve>(ctx, x1, x2, a_at_x1, c_at_x1, d_g1_xy, d_inf),
-                           prove_phase3_impl<BnCurve>(ctx, x1, x2, a_at_x1, c_at_x1, d_g1_xy, d_inf));
+        return with_curve(ctx->pk->curve, [&](auto cv) {
+            typedef type_of<decltype(cv)> C;
+            return ctx->pk->layout == PM_SHARD_VECTOR ? prove_phase3_sharded<C>(ctx, x1, x2, a_at_x1, c_at_x1, d_g1_xy, d_inf)
+                                                      : prove_phase3_impl<C>(ctx, x1, x2, a_at_x1, c_at_x1, d_g1_xy, d_inf);
+        });
     });
 }
 
@@ -1262,14 +1259,14 @@ extern "C" int pm_prove_tap(pm_ctx *ctx, int which, uint64_t *out, size_t max_el
         const uint64_t N = (uint64_t)pk->shard_count, q = (uint64_t)pk->shard_rank, m = n / N;
         const uint64_t zcnt = pmlayout::ztail_lo(Lz, (uint32_t)N, (uint32_t)q + 1) - pmlayout::ztail_lo(Lz, (uint32_t)N, (uint32_t)q);
         switch (which) {
-            case 2: src = ctx->u.p; cnt = m; break;
-            case 3: src = ctx->w.p; cnt = m; break;
-            case 4: src = (const uint8_t *)ctx->sc_c.p + zcnt * 32; cnt = m - (q == N - 1 ? 1 : 0); break;
-            case 5: src = ctx->wit_u.p; cnt = m; break;
-            case 6: src = ctx->sc_c.p; cnt = zcnt; break;
+            case 2: src = ctx->pw.u.p; cnt = m; break;
+            case 3: src = ctx->pw.w.p; cnt = m; break;
+            case 4: src = (const uint8_t *)ctx->pw.sc_c.p + zcnt * 32; cnt = m - (q == N - 1 ? 1 : 0); break;
+            case 5: src = ctx->pw.wit_u.p; cnt = m; break;
+            case 6: src = ctx->pw.sc_c.p; cnt = zcnt; break;
             case 7:
                 if (ctx->phase < 3) return PM_ERR_STATE;
-                src = ctx->quotient.p; cnt = pk->res_cnt[2]; break;
+                src = ctx->pw.quotient.p; cnt = pk->res_cnt[2]; break;
             default: return PM_ERR_INVALID_ARG;
         }
         *n_elems = cnt;
@@ -1278,16 +1275,16 @@ extern "C" int pm_prove_tap(pm_ctx *ctx, int which, uint64_t *out, size_t max_el
         return PM_OK;
     }
     switch (which) {
-        case 0: src = ctx->ue.p; cnt = n; break;
-        case 1: src = ctx->we.p; cnt = n; break;
-        case 2: src = ctx->u.p; cnt = n; break;
-        case 3: src = ctx->w.p; cnt = n; break;
-        case 4: src = (const uint8_t *)ctx->sc_c.p + Lz * 32; cnt = n - 1; break;
-        case 5: src = ctx->wit_u.p; cnt = n; break;
-        case 6: src = ctx->sc_c.p; cnt = Lz; break;
+        case 0: src = ctx->pw.ue.p; cnt = n; break;
+        case 1: src = ctx->pw.we.p; cnt = n; break;
+        case 2: src = ctx->pw.u.p; cnt = n; break;
+        case 3: src = ctx->pw.w.p; cnt = n; break;
+        case 4: src = (const uint8_t *)ctx->pw.sc_c.p + Lz * 32; cnt = n - 1; break;
+        case 5: src = ctx->pw.wit_u.p; cnt = n; break;
+        case 6: src = ctx->pw.sc_c.p; cnt = Lz; break;
         case 7:
             if (ctx->phase < 3) return PM_ERR_STATE;
-            src = ctx->quotient.p; cnt = shape.len_d; break;
+            src = ctx->pw.quotient.p; cnt = shape.len_d; break;
         default: return PM_ERR_INVALID_ARG;
     }
     *n_elems = cnt;

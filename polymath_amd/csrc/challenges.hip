@@ -65,9 +65,8 @@ __global__ __launch_bounds__(CHALLENGE_BLOCK) void k_verifier_challenges(fs::FsV
 template <class C, int KIND>
 int launch_kind(pm_ctx *ctx, const fs::FsVk<C> &vk, const ChallengeRows &rows, const ChallengeOut<C> &out, int timing_slot) {
     StageTimer t(ctx, timing_slot);
-    hipLaunchKernelGGL((k_verifier_challenges<C, KIND>), dim3((unsigned)((rows.count + CHALLENGE_BLOCK - 1) / CHALLENGE_BLOCK)), dim3(CHALLENGE_BLOCK), 0,
-                       ctx->stream, vk, rows, out);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, (k_verifier_challenges<C, KIND>), dim3((unsigned)((rows.count + CHALLENGE_BLOCK - 1) / CHALLENGE_BLOCK)), dim3(CHALLENGE_BLOCK), 0,
+                   ctx->stream, vk, rows, out);
     return PM_OK;
 }
 

@@ -166,9 +166,8 @@ int g1_decode_device(pm_ctx *ctx, const uint8_t *d_in, size_t count, bool valida
                      unsigned long long *d_first_bad, uint64_t base_index) {
     if (!count) return PM_OK;
     if (((uintptr_t)d_in & 15) != 0) { ctx->err = "g1_decode: staging not 16-byte aligned"; return PM_ERR_STATE; }
-    hipLaunchKernelGGL(k_g1_decode<C>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, d_in, count, validate ? 1 : 0,
-                       d_out, d_status, d_first_bad, base_index);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_g1_decode<C>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, d_in, count, validate ? 1 : 0,
+                   d_out, d_status, d_first_bad, base_index);
     return PM_OK;
 }
 
@@ -176,8 +175,7 @@ template <class C>
 int g1_encode_device(pm_ctx *ctx, const Affine<C> *d_pts, size_t count, uint8_t *d_out) {
     if (!count) return PM_OK;
     if (((uintptr_t)d_out & 15) != 0) { ctx->err = "g1_encode: staging not 16-byte aligned"; return PM_ERR_STATE; }
-    hipLaunchKernelGGL(k_g1_encode<C>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, d_pts, count, d_out);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_g1_encode<C>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, d_pts, count, d_out);
     return PM_OK;
 }
 

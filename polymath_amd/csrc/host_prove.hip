@@ -63,17 +63,6 @@ int host_prove_impl(pm_ctx *ctx, const pm_pk *pk, const uint64_t *instance_host,
     return status;
 }
 
-template <class C>
-int host_prove_curve(pm_ctx *ctx, const pm_pk *pk, int transcript, const uint64_t *ih, const uint64_t *x, const uint64_t *w, int dev,
-                     const uint64_t *r_a, pm_combine_fn cf, void *user, uint8_t *out, size_t cap, size_t *len) {
-    switch (transcript) {
-        case PM_TRANSCRIPT_MERLIN: return host_prove_impl<C, pmhost::MerlinFieldTranscript<C>>(ctx, pk, ih, x, w, dev, r_a, cf, user, out, cap, len);
-        case PM_TRANSCRIPT_KECCAK256: return host_prove_impl<C, pmhost::Keccak256Transcript<C>>(ctx, pk, ih, x, w, dev, r_a, cf, user, out, cap, len);
-        case PM_TRANSCRIPT_BLAKE3: return host_prove_impl<C, pmhost::Blake3Transcript<C>>(ctx, pk, ih, x, w, dev, r_a, cf, user, out, cap, len);
-        default: return PM_ERR_INVALID_ARG;
-    }
-}
-
 }  // namespace
 
 extern "C" int pm_host_prove_sharded(pm_ctx *ctx, const pm_pk *pk, int transcript, const uint64_t *instance_host, const uint64_t *x,
@@ -83,9 +72,13 @@ extern "C" int pm_host_prove_sharded(pm_ctx *ctx, const pm_pk *pk, int transcrip
     if (pk->device != ctx->device) return PM_ERR_INVALID_ARG;
     if (pk->shard_count != 1 && !combine && !ctx->comm) return PM_ERR_INVALID_ARG;   // a shard's points are partial sums: somebody has to add them
     if (hipSetDevice(ctx->device) != hipSuccess) return PM_ERR_HIP;
-    return pk->curve == PM_BLS12_381
-               ? host_prove_curve<pm::BlsCurve>(ctx, pk, transcript, instance_host, x, w, assignment_on_device, r_a, combine, user, proof_bytes, capacity, proof_len)
-               : host_prove_curve<pm::BnCurve>(ctx, pk, transcript, instance_host, x, w, assignment_on_device, r_a, combine, user, proof_bytes, capacity, proof_len);
+    return pm::with_curve(pk->curve, [&](auto cv) {
+        typedef pm::type_of<decltype(cv)> C;
+        return pmhost::with_transcript<C>(transcript, [&](auto t) {
+            return host_prove_impl<C, pm::type_of<decltype(t)>>(ctx, pk, instance_host, x, w, assignment_on_device, r_a, combine, user, proof_bytes,
+                                                                capacity, proof_len);
+        });
+    });
 }
 
 // ---- PM_ASSIGNMENT_SOLVE (solve.hip): the unknown entries of the assignment are computed on the device first ----
@@ -124,7 +117,9 @@ int host_prove_solve(pm_ctx *ctx, const pm_pk *pk, int transcript, const uint64_
     solved_instance(ctx, pk, 0, instance_host, inst.data());
     const double solve_ms = ctx->timing_ms[pm::T_WITNESS_MAP];
     const uint64_t *xw = (const uint64_t *)ctx->sv.xw.p;
-    const int rc = host_prove_curve<C>(ctx, pk, transcript, inst.data(), xw, xw + 4 * pk->m0, 1, r_a, nullptr, nullptr, proof_bytes, cap, proof_len);
+    const int rc = pmhost::with_transcript<C>(transcript, [&](auto t) {
+        return host_prove_impl<C, pm::type_of<decltype(t)>>(ctx, pk, inst.data(), xw, xw + 4 * pk->m0, 1, r_a, nullptr, nullptr, proof_bytes, cap, proof_len);
+    });
     ctx->timing_ms[pm::T_WITNESS_MAP] += solve_ms;   // the proof's slots start from zero; its pending timers are added when they are read
     return rc;
 }
@@ -133,13 +128,13 @@ int host_prove_solve_any(pm_ctx *ctx, const pm_pk *pk, int transcript, const uin
                          bool on_device, const uint64_t *r_a, uint8_t *proof_bytes, size_t cap, size_t *proof_len, int *stage) {
     *stage = 0;
     if (!ctx || !pk || !instance_host || !x || !r_a || !proof_bytes || (pk->mw && !w)) return PM_ERR_INVALID_ARG;
-    if (transcript != PM_TRANSCRIPT_MERLIN && transcript != PM_TRANSCRIPT_KECCAK256 && transcript != PM_TRANSCRIPT_BLAKE3) return PM_ERR_INVALID_ARG;
+    if (!pmhost::transcript_ok(transcript)) return PM_ERR_INVALID_ARG;
     if (pk->shard_count != 1 || pk->layout != PM_SHARD_PAIRS || pk->device != ctx->device) return PM_ERR_INVALID_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return PM_ERR_HIP;
     try {
-        return pk->curve == PM_BLS12_381
-                   ? host_prove_solve<pm::BlsCurve>(ctx, pk, transcript, instance_host, x, w, on_device, r_a, proof_bytes, cap, proof_len, stage)
-                   : host_prove_solve<pm::BnCurve>(ctx, pk, transcript, instance_host, x, w, on_device, r_a, proof_bytes, cap, proof_len, stage);
+        return pm::with_curve(pk->curve, [&](auto cv) {
+            return host_prove_solve<pm::type_of<decltype(cv)>>(ctx, pk, transcript, instance_host, x, w, on_device, r_a, proof_bytes, cap, proof_len, stage);
+        });
     } catch (const std::bad_alloc &) {
         ctx->err = "pm_host_prove: out of host memory";
         return PM_ERR_STATE;
@@ -304,17 +299,6 @@ int host_prove_batch_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint
     return rc;
 }
 
-template <class C>
-int host_prove_batch_curve(pm_ctx *ctx, const pm_pk *pk, int transcript, size_t count, const uint64_t *ih, const uint64_t *x, const uint64_t *w,
-                           int dev, bool solve, const uint64_t *r_a, uint8_t *proofs, size_t proof_len, int *status) {
-    switch (transcript) {
-        case PM_TRANSCRIPT_MERLIN: return host_prove_batch_impl<C, pmhost::MerlinFieldTranscript<C>>(ctx, pk, count, ih, x, w, dev, solve, r_a, proofs, proof_len, status);
-        case PM_TRANSCRIPT_KECCAK256: return host_prove_batch_impl<C, pmhost::Keccak256Transcript<C>>(ctx, pk, count, ih, x, w, dev, solve, r_a, proofs, proof_len, status);
-        case PM_TRANSCRIPT_BLAKE3: return host_prove_batch_impl<C, pmhost::Blake3Transcript<C>>(ctx, pk, count, ih, x, w, dev, solve, r_a, proofs, proof_len, status);
-        default: return PM_ERR_INVALID_ARG;
-    }
-}
-
 }  // namespace
 
 extern "C" int pm_host_prove_batch(pm_ctx *ctx, const pm_pk *pk, int transcript, size_t count, const uint64_t *instance_host, const uint64_t *x,
@@ -323,7 +307,7 @@ extern "C" int pm_host_prove_batch(pm_ctx *ctx, const pm_pk *pk, int transcript,
     if (!pm::assignment_flags_ok(assignment_on_device) || !ctx || !pk) return PM_ERR_INVALID_ARG;
     const bool solve = (assignment_on_device & PM_ASSIGNMENT_SOLVE) != 0;
     const int on_device = assignment_on_device & PM_ASSIGNMENT_DEVICE;
-    if (transcript != PM_TRANSCRIPT_MERLIN && transcript != PM_TRANSCRIPT_KECCAK256 && transcript != PM_TRANSCRIPT_BLAKE3) return PM_ERR_INVALID_ARG;
+    if (!pmhost::transcript_ok(transcript)) return PM_ERR_INVALID_ARG;
     if (pk->shard_count != 1 || pk->layout != PM_SHARD_PAIRS || pk->device != ctx->device) return PM_ERR_INVALID_ARG;
     const size_t fq_bytes = pk->curve == PM_BLS12_381 ? sizeof(pm::Fp<pm::BlsFqP>) : sizeof(pm::Fp<pm::BnFqP>);
     if (proof_len != 3 * fq_bytes + 32) return PM_ERR_INVALID_ARG;     // Proof::serialize_compressed: three G1 points and one Fr
@@ -345,9 +329,12 @@ extern "C" int pm_host_prove_batch(pm_ctx *ctx, const pm_pk *pk, int transcript,
         return status[0] == PM_ERR_HIP ? (int)PM_ERR_HIP : (int)PM_OK;
     }
     if (hipSetDevice(ctx->device) != hipSuccess) return PM_ERR_HIP;
-    return pk->curve == PM_BLS12_381
-               ? host_prove_batch_curve<pm::BlsCurve>(ctx, pk, transcript, count, instance_host, x, w, on_device, solve, r_a, proofs, proof_len, status)
-               : host_prove_batch_curve<pm::BnCurve>(ctx, pk, transcript, count, instance_host, x, w, on_device, solve, r_a, proofs, proof_len, status);
+    return pm::with_curve(pk->curve, [&](auto cv) {
+        typedef pm::type_of<decltype(cv)> C;
+        return pmhost::with_transcript<C>(transcript, [&](auto t) {
+            return host_prove_batch_impl<C, pm::type_of<decltype(t)>>(ctx, pk, count, instance_host, x, w, on_device, solve, r_a, proofs, proof_len, status);
+        });
+    });
 }
 
 // ---- verify (lib.rs:80-90 -> verifier.rs:19-62) and the verifying key (generator.rs:139-157): host code, no GPU --------------
@@ -386,28 +373,18 @@ int verify_impl(const uint8_t *vk_bytes, size_t vk_len, const uint64_t *inputs, 
     return PM_OK;
 }
 
-template <class C>
-int verify_curve(int transcript, const uint8_t *vk, size_t vk_len, const uint64_t *in, size_t n_in, const uint8_t *pr, size_t pr_len, int *acc) {
-    switch (transcript) {
-        case PM_TRANSCRIPT_MERLIN: return verify_impl<C, pmhost::MerlinFieldTranscript<C>>(vk, vk_len, in, n_in, pr, pr_len, acc);
-        case PM_TRANSCRIPT_KECCAK256: return verify_impl<C, pmhost::Keccak256Transcript<C>>(vk, vk_len, in, n_in, pr, pr_len, acc);
-        case PM_TRANSCRIPT_BLAKE3: return verify_impl<C, pmhost::Blake3Transcript<C>>(vk, vk_len, in, n_in, pr, pr_len, acc);
-        default: return PM_ERR_INVALID_ARG;
-    }
-}
-
 }  // namespace
 
 extern "C" int pm_host_make_vk(int curve, uint64_t n, uint64_t m0, uint64_t sigma, const uint64_t *omega, const uint64_t *x_trapdoor,
                                const uint64_t *z_trapdoor, uint8_t *vk_bytes, size_t capacity, size_t *vk_len) {
     if (!omega || !x_trapdoor || !z_trapdoor || !vk_bytes) return PM_ERR_INVALID_ARG;
     try {
-        if (curve == PM_BLS12_381) return make_vk_impl<pm::BlsCurve>(n, m0, sigma, omega, x_trapdoor, z_trapdoor, vk_bytes, capacity, vk_len);
-        if (curve == PM_BN254) return make_vk_impl<pm::BnCurve>(n, m0, sigma, omega, x_trapdoor, z_trapdoor, vk_bytes, capacity, vk_len);
+        return pm::with_curve(curve, [&](auto cv) {
+            return make_vk_impl<pm::type_of<decltype(cv)>>(n, m0, sigma, omega, x_trapdoor, z_trapdoor, vk_bytes, capacity, vk_len);
+        });
     } catch (const std::exception &) {
         return PM_ERR_STATE;
     }
-    return PM_ERR_INVALID_ARG;
 }
 
 extern "C" int pm_host_verify(int curve, int transcript, const uint8_t *vk_bytes, size_t vk_len, const uint64_t *public_inputs, size_t n_inputs,
@@ -415,10 +392,13 @@ extern "C" int pm_host_verify(int curve, int transcript, const uint8_t *vk_bytes
     if (!vk_bytes || !proof_bytes || !accepted || (n_inputs && !public_inputs)) return PM_ERR_INVALID_ARG;
     *accepted = 0;
     try {
-        if (curve == PM_BLS12_381) return verify_curve<pm::BlsCurve>(transcript, vk_bytes, vk_len, public_inputs, n_inputs, proof_bytes, proof_len, accepted);
-        if (curve == PM_BN254) return verify_curve<pm::BnCurve>(transcript, vk_bytes, vk_len, public_inputs, n_inputs, proof_bytes, proof_len, accepted);
+        return pm::with_curve(curve, [&](auto cv) {
+            typedef pm::type_of<decltype(cv)> C;
+            return pmhost::with_transcript<C>(transcript, [&](auto t) {
+                return verify_impl<C, pm::type_of<decltype(t)>>(vk_bytes, vk_len, public_inputs, n_inputs, proof_bytes, proof_len, accepted);
+            });
+        });
     } catch (const std::exception &) {      // malformed vk / proof bytes (off-curve points, non-canonical scalars, truncation)
         return PM_ERR_INVALID_ARG;
     }
-    return PM_ERR_INVALID_ARG;
 }

@@ -41,6 +41,27 @@ struct pm_error_sink {
         if (_s != PM_OK) return _s;   \
     } while (0)
 
+// a kernel launch and its launch-error check
+#define PM_LAUNCH(ctx, kernel, grid, block, lds, stream, ...)                  \
+    do {                                                                       \
+        hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);     \
+        PM_HIP(ctx, hipGetLastError());                                        \
+    } while (0)
+
+// A runtime pm_curve id as a type: with_curve(curve, [&](auto cv) { return f<type_of<decltype(cv)>>(...); }) calls the lambda with a tag
+// whose ::type is BlsCurve or BnCurve; any other id is PM_ERR_INVALID_ARG.  (host/polymath.hpp: with_transcript does the same for the
+// three host transcripts.)
+template <class C>
+struct CurveTag { typedef C type; };
+template <class Tag>
+using type_of = typename Tag::type;
+template <class F>
+inline int with_curve(int curve, F f) {
+    if (curve == PM_BLS12_381) return f(CurveTag<BlsCurve>{});
+    if (curve == PM_BN254) return f(CurveTag<BnCurve>{});
+    return PM_ERR_INVALID_ARG;
+}
+
 // Growable device buffer owned by a context (never shrinks: the prover reuses its workspaces).
 struct DevBuf {
     void *p = nullptr;
@@ -113,19 +134,29 @@ struct MsmTables {
     bool wide = false;
 };
 
-// pm_host_prove_batch (prove_batch.hip): the vectors of one GROUP of proofs as [rows][len] arrays, reserved for the largest group seen
-// and reused by later groups and calls.
-struct ProveBatchWs {
-    DevBuf xw, ue, we, u, w, wit_u, u2, tmp, sc_a, sc_c, quotient, lvl[6], part, rows, flags;   // rows: one parameter record per proof
-    void release() {
-        for (DevBuf *b : {&xw, &ue, &we, &u, &w, &wit_u, &u2, &tmp, &sc_a, &sc_c, &quotient, &part, &rows, &flags}) b->release();
-        for (DevBuf &b : lvl) b.release();
+// The vectors of `rows` proofs against one unsharded key as [rows][len] arrays (prove.hip / prove_batch.hip), reserved for the largest
+// shape seen and reused.  A context holds two: pm_ctx::pw, the proof in flight of the three-phase API (rows = 1; the sharded prover keeps
+// its local vectors there too), and pm_ctx::pb, the groups of pm_host_prove_batch -- a batch call leaves the proof in flight alone.
+struct ProveWs {
+    // tmp: the transforms' out-of-place temporary; part: phase 2's partial sums; rows: the per-proof values of the phase being run
+    // (phase 1: r_a as [rows][2], phases 2 and 3 of a group: one BatchRow record per proof); flags: one status word per proof
+    DevBuf xw, ue, we, u, w, wit_u, u2, tmp, sc_a, sc_c, quotient, lvl[6], part, rows, flags;
+    template <class F>
+    void for_each(F f) {
+        for (DevBuf *b : {&xw, &ue, &we, &u, &w, &wit_u, &u2, &tmp, &sc_a, &sc_c, &quotient, &part, &rows, &flags}) f(*b);
+        for (DevBuf &b : lvl) f(b);
+    }
+    void release() { for_each([](DevBuf &b) { b.release(); }); }
+    size_t bytes_held() {
+        size_t held = 0;
+        for_each([&](DevBuf &b) { held += b.bytes; });
+        return held;
     }
 };
 
 // Witness solving (solve.hip): the context's plan cache -- one plan, keyed by (key, unknown pattern) -- and the buffers of the last
 // call with PM_ASSIGNMENT_SOLVE.  xw: the completed x || w rows of a check call (pm_prove_tap(10)); the prover completes its groups in
-// its own workspace (ProveBatchWs::xw) and keeps only tap9.
+// its own workspace (ProveWs::xw) and keeps only tap9.
 struct SolveWs {
     DevBuf xw, pattern, mismatch, stuck, steps;
     pmsolve::Plan plan;
@@ -283,7 +314,7 @@ struct pm_ctx {
     pm::MsmWorkspace msm;
     pm::TwiddleCache tw[8];   // the sharded prover works with log m, log n and log 2n tables of both directions
     unsigned long long tw_clock;
-    pm::DevBuf scratch, flags, ntt_tmp;   // ntt_tmp: the out-of-place first / last passes of ntt_run
+    pm::DevBuf scratch, ntt_tmp;   // ntt_tmp: the out-of-place first / last passes of ntt_run
     void *h_pinned;           // 4 KiB of pinned host memory: the asynchronous MSM's result slot (msm.hip: msm_begin / msm_end)
     int msm_async;            // 0 none pending, 1 enqueued (msm_end synchronises), 2 ran synchronously (result parked in the slot)
     bool ntt_lds_attr[2];     // ntt.hip: the tile kernels' dynamic-LDS limit has been raised on this context's device (per curve id)
@@ -299,10 +330,10 @@ struct pm_ctx {
     uint64_t ra_host[8];      // r_a of the proof in flight (phase 3's numerator constants need it on the host)
     bool keep_timings;   // pm_host_prove: the stage slots accumulate over the three phases of one proof
     bool lazy_timings;   // ... and are read by pm_last_timings instead of at the end of every phase (timing_flush)
-    pm::DevBuf xw, ue, we, u, w, wit_u, u2, sc_a, sc_c, quotient, ztail, lvl[6], ra;
+    pm::ProveWs pw;      // its vectors (prove.hip; prove_sharded.hip: this rank's local ones)
     // PM_SHARD_VECTOR prover (prove_sharded.hip): transform temporaries, halo coefficients, roots of the cross-rank butterfly
     pm::DevBuf sh_a, sh_b, sh_c, halo, shard_roots;
-    pm::ProveBatchWs pb;
+    pm::ProveWs pb;      // pm_host_prove_batch: the vectors of a group of proofs
     pm::SolveWs sv;
     std::vector<uint64_t> verify_tap;   // pm_prove_tap(8): x1, x2, c(x1), ok of the last batch verified with device challenges, 16 words a proof
     uint64_t shard_roots_n;
@@ -516,6 +547,13 @@ int powers_fill(pm_ctx *ctx, Fp<typename C::FrP> *d_out, size_t count, const Fp<
 template <class C>
 int msm_resident(pm_ctx *ctx, const pm_pk *pk, int which, const Fp<typename C::FrP> *d_scalars, uint64_t *out_xy, int *out_inf);
 
+// prove.hip: phase 1's enqueue list between the uploads and the MSMs, for the `rows` proofs of a ProveWs (both provers run it)
+struct ProofShape;
+template <class C>
+int phase1_enqueue_u(pm_ctx *ctx, const pm_pk *pk, const ProofShape &shape, ProveWs &ws, size_t rows, bool sc_a_now);
+template <class C>
+int phase1_enqueue_rest(pm_ctx *ctx, const pm_pk *pk, const ProofShape &shape, ProveWs &ws, size_t rows, Fp<typename C::FrP> *sc_a_or_null);
+
 template <class C>
 int prove_phase1_impl(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const uint64_t *w, const uint64_t *r_a,
                       uint64_t *a_xy, int *a_inf, uint64_t *c_xy, int *c_inf, bool assignment_on_device);
@@ -540,7 +578,7 @@ template <class C>
 int prove_batch_phase3(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *r_a, const uint64_t *x1, const uint64_t *x2,
                        const uint64_t *a_at_x1, const uint64_t *c_at_x1, Affine<C> *d, int *d_inf, unsigned *flags_out);
 
-// the group's [rows][m0 + mw] assignment buffer (pm_ctx::pb), reserved: what prove_batch_phase1 reads with xw_resident
+// the group's [rows][m0 + mw] assignment buffer (pm_ctx::pb.xw), reserved: what prove_batch_phase1 reads with xw_resident
 template <class C>
 int prove_batch_xw(pm_ctx *ctx, const pm_pk *pk, size_t rows, Fp<typename C::FrP> **xw);
 

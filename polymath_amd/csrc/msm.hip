@@ -1133,13 +1133,10 @@ static int reserve_set(pm_ctx *ctx, MsmSet &S, const BucketPlan &p) {
 static int bucket_scan(pm_ctx *ctx, MsmSet &S, const BucketPlan &p) {
     uint32_t *tile_tot = ctx->msm.cursor.as<uint32_t>(), *bucket_off = S.bucket_off.as<uint32_t>(), *task_off = S.task_off.as<uint32_t>();
     const unsigned ntiles = (unsigned)((p.NB + SCAN_TILE - 1) / SCAN_TILE);
-    hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(256), 0, ctx->stream, S.counts.as<uint32_t>(), bucket_off, task_off, tile_tot, p.NB,
-                       (unsigned)p.seg);
-    PM_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, ctx->stream, tile_tot, ntiles, bucket_off, task_off, p.NB);
-    PM_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_scan_add, dim3(ntiles), dim3(256), 0, ctx->stream, bucket_off, task_off, tile_tot, p.NB);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_scan_tiles, dim3(ntiles), dim3(256), 0, ctx->stream, S.counts.as<uint32_t>(), bucket_off, task_off, tile_tot, p.NB,
+                   (unsigned)p.seg);
+    PM_LAUNCH(ctx, k_scan_totals, dim3(1), dim3(1024), 0, ctx->stream, tile_tot, ntiles, bucket_off, task_off, p.NB);
+    PM_LAUNCH(ctx, k_scan_add, dim3(ntiles), dim3(256), 0, ctx->stream, bucket_off, task_off, tile_tot, p.NB);
     return PM_OK;
 }
 
@@ -1154,15 +1151,12 @@ static int fold_hot_buckets(pm_ctx *ctx, MsmSet &S, const BucketPlan &p) {
     PM_HIP(ctx, ws.hot.reserve((2 * cap + 2) * 4));
     uint32_t *hot_counts = ws.hot.as<uint32_t>(), *hot_a = hot_counts + 2, *hot_b = hot_a + cap;
     PM_HIP(ctx, hipMemsetAsync(hot_counts, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(k_task_counts, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, ctx->stream, S.task_off.as<uint32_t>(), G,
-                       S.task_cnt.as<uint32_t>(), hot_a, hot_b, hot_counts, (uint32_t)cap);
-    PM_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL((k_task_fold<C, 256>), dim3(256), dim3(256), 256 * sizeof(XYZZ28<C>), ctx->stream, S.partials.as<XYZZ<C>>(),
-                       S.task_off.as<uint32_t>(), S.task_cnt.as<uint32_t>(), hot_a, hot_counts, (uint32_t)cap);
-    PM_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL((k_task_fold<C, 64>), dim3(1024), dim3(256), 256 * sizeof(XYZZ28<C>), ctx->stream, S.partials.as<XYZZ<C>>(),
-                       S.task_off.as<uint32_t>(), S.task_cnt.as<uint32_t>(), hot_b, hot_counts + 1, (uint32_t)cap);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_task_counts, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, ctx->stream, S.task_off.as<uint32_t>(), G,
+                   S.task_cnt.as<uint32_t>(), hot_a, hot_b, hot_counts, (uint32_t)cap);
+    PM_LAUNCH(ctx, (k_task_fold<C, 256>), dim3(256), dim3(256), 256 * sizeof(XYZZ28<C>), ctx->stream, S.partials.as<XYZZ<C>>(),
+                   S.task_off.as<uint32_t>(), S.task_cnt.as<uint32_t>(), hot_a, hot_counts, (uint32_t)cap);
+    PM_LAUNCH(ctx, (k_task_fold<C, 64>), dim3(1024), dim3(256), 256 * sizeof(XYZZ28<C>), ctx->stream, S.partials.as<XYZZ<C>>(),
+                   S.task_off.as<uint32_t>(), S.task_cnt.as<uint32_t>(), hot_b, hot_counts + 1, (uint32_t)cap);
     return PM_OK;
 }
 
@@ -1180,16 +1174,13 @@ static int task_order(pm_ctx *ctx, MsmSet &S, const BucketPlan &p) {
     uint32_t *ticket = ws.len_bins.as<uint32_t>(), *len_cnt = ticket + 1, *len_off = len_cnt + nbins, *len_cursor = len_off + nbins + 1;
     PM_HIP(ctx, hipMemsetAsync(ticket, 0, ((size_t)nbins + 1) * 4, ctx->stream));
     const unsigned blocks = (unsigned)((G + 1023) / 1024);      // one lane per bucket
-    hipLaunchKernelGGL(k_task_bins<false>, dim3(blocks), dim3(1024), nbins * 4, ctx->stream, counts, S.bucket_off.as<uint32_t>(),
-                       S.task_off.as<uint32_t>(), G, (unsigned)seg, lshift, nbins, len_cnt, (const uint32_t *)nullptr, (uint32_t *)nullptr,
-                       (uint4 *)nullptr);
-    PM_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, ctx->stream, len_cnt, len_off, len_cursor, nbins);
-    PM_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_task_bins<true>, dim3(blocks), dim3(1024), nbins * 4, ctx->stream, counts, S.bucket_off.as<uint32_t>(),
-                       S.task_off.as<uint32_t>(), G, (unsigned)seg, lshift, nbins, (uint32_t *)nullptr, len_off, len_cursor,
-                       S.tasks.as<uint4>());
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_task_bins<false>, dim3(blocks), dim3(1024), nbins * 4, ctx->stream, counts, S.bucket_off.as<uint32_t>(),
+                   S.task_off.as<uint32_t>(), G, (unsigned)seg, lshift, nbins, len_cnt, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                   (uint4 *)nullptr);
+    PM_LAUNCH(ctx, k_scan_small, dim3(1), dim3(1024), 0, ctx->stream, len_cnt, len_off, len_cursor, nbins);
+    PM_LAUNCH(ctx, k_task_bins<true>, dim3(blocks), dim3(1024), nbins * 4, ctx->stream, counts, S.bucket_off.as<uint32_t>(),
+                   S.task_off.as<uint32_t>(), G, (unsigned)seg, lshift, nbins, (uint32_t *)nullptr, len_off, len_cursor,
+                   S.tasks.as<uint4>());
     return PM_OK;
 }
 
@@ -1202,9 +1193,8 @@ static int accumulate(pm_ctx *ctx, MsmSet &S, const BucketPlan &p, const void *p
     PM_HIP(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
     size_t blocks = (size_t)(per_cu > 0 ? per_cu : 1) * (size_t)(cus > 0 ? cus : 1);
     if (blocks > (p.max_tasks + 127) / 128) blocks = (p.max_tasks + 127) / 128;
-    hipLaunchKernelGGL((k_accumulate<C, TABLE>), dim3((unsigned)blocks), dim3(128), 0, ctx->stream, S.sorted.as<uint32_t>(),
-                       S.task_off.as<uint32_t>(), S.tasks.as<uint4>(), points, S.partials.as<XYZZ<C>>(), p.NB, ctx->msm.len_bins.as<uint32_t>());
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, (k_accumulate<C, TABLE>), dim3((unsigned)blocks), dim3(128), 0, ctx->stream, S.sorted.as<uint32_t>(),
+                   S.task_off.as<uint32_t>(), S.tasks.as<uint4>(), points, S.partials.as<XYZZ<C>>(), p.NB, ctx->msm.len_bins.as<uint32_t>());
     return PM_OK;
 }
 
@@ -1215,11 +1205,9 @@ static int reduce_single_level(pm_ctx *ctx, MsmSet &S, const BucketPlan &p, XYZZ
     const unsigned sets = p.n_wide_sets;
     PM_HIP(ctx, ctx->msm.wsum.reserve(((size_t)sets * p.bpw + sets) * sizeof(XYZZ<C>)));
     XYZZ<C> *parts = ctx->msm.wsum.as<XYZZ<C>>(), *sums = parts + (size_t)sets * p.bpw;
-    hipLaunchKernelGGL(k_bucket_reduce<C>, dim3(sets * p.bpw), dim3(p.red_block), p.red_block * sizeof(XYZZ28<C>), ctx->stream,
-                       S.partials.as<XYZZ<C>>(), S.task_off.as<uint32_t>(), S.task_cnt.as<uint32_t>(), (unsigned)p.NB1, p.red_lanes, p.bpw, parts);
-    PM_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_sum_parts<C>, dim3(sets), dim3(64), 0, ctx->stream, parts, p.bpw, sums);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_bucket_reduce<C>, dim3(sets * p.bpw), dim3(p.red_block), p.red_block * sizeof(XYZZ28<C>), ctx->stream,
+                   S.partials.as<XYZZ<C>>(), S.task_off.as<uint32_t>(), S.task_cnt.as<uint32_t>(), (unsigned)p.NB1, p.red_lanes, p.bpw, parts);
+    PM_LAUNCH(ctx, k_sum_parts<C>, dim3(sets), dim3(64), 0, ctx->stream, parts, p.bpw, sums);
     *out = sums;
     return PM_OK;
 }
@@ -1280,12 +1268,10 @@ static int sort_sets(pm_ctx *ctx, MsmSet &S, const BucketPlan &p, const uint32_t
         PM_HIP(ctx, hipFuncSetAttribute((const void *)k_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         PM_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
-    hipLaunchKernelGGL(k_hist, dim3(p.nchunks, p.n_wide_sets), dim3(1024), lds, ctx->stream, digits, counts, p.len, p.chunk, nbuckets);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_hist, dim3(p.nchunks, p.n_wide_sets), dim3(1024), lds, ctx->stream, digits, counts, p.len, p.chunk, nbuckets);
     PM_TRY(bucket_scan(ctx, S, p));
-    hipLaunchKernelGGL(k_scatter, dim3(p.nchunks, p.n_wide_sets), dim3(1024), lds, ctx->stream, digits, S.bucket_off.as<uint32_t>(), cursor,
-                       S.sorted.as<uint32_t>(), p.len, p.chunk, nbuckets);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_scatter, dim3(p.nchunks, p.n_wide_sets), dim3(1024), lds, ctx->stream, digits, S.bucket_off.as<uint32_t>(), cursor,
+                   S.sorted.as<uint32_t>(), p.len, p.chunk, nbuckets);
     return PM_OK;
 }
 
@@ -1296,8 +1282,7 @@ static int sort_windows(pm_ctx *ctx, MsmSet &S, const BucketPlan &p, const Affin
     PM_HIP(ctx, ws.digits.reserve(p.E * 4));
     uint32_t *counts = S.counts.as<uint32_t>(), *cursor = counts + p.NB, *digits = ws.digits.as<uint32_t>();
     PM_HIP(ctx, hipMemsetAsync(counts, 0, 2 * p.NB * 4, ctx->stream));
-    hipLaunchKernelGGL(k_digits<C>, dim3((unsigned)((p.len + 255) / 256)), dim3(256), 0, ctx->stream, d_scalars, d_bases, digits, p.len, p.c, p.nwin);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_digits<C>, dim3((unsigned)((p.len + 255) / 256)), dim3(256), 0, ctx->stream, d_scalars, d_bases, digits, p.len, p.c, p.nwin);
     return sort_sets(ctx, S, p, digits, counts, cursor, (unsigned)p.NB1);
 }
 
@@ -1328,9 +1313,8 @@ static int sort_first_level(pm_ctx *ctx, const BucketPlan &p, const MsmTables &t
     hipLaunchKernelGGL(k_block_offsets, dim3(bsh.G), dim3(1024), 0, st, block_cnt, pblocks, p.regions, bsh, block_partial, b.region_count);
     hipLaunchKernelGGL(k_region_offsets, dim3(1), dim3(1024), 0, st, b.region_count, b.region_off, b.region_cursor, p.regions);
     PM_HIP(ctx, hipFuncSetAttribute((const void *)k_tbl_partition<P, NWIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.plds));
-    hipLaunchKernelGGL((k_tbl_partition<P, NWIN>), dim3(pblocks), dim3(p.pbd), p.plds, st, d_scalars, inf, p.len, p.regions, b.region_off, block_cnt,
-                       p.wide ? (size_t)0 : tb.stride, tb.base_index, b.keys, b.vals, p.win_buckets, p.narrow_buckets);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, (k_tbl_partition<P, NWIN>), dim3(pblocks), dim3(p.pbd), p.plds, st, d_scalars, inf, p.len, p.regions, b.region_off, block_cnt,
+                   p.wide ? (size_t)0 : tb.stride, tb.base_index, b.keys, b.vals, p.win_buckets, p.narrow_buckets);
     return PM_OK;
 }
 
@@ -1349,22 +1333,17 @@ static int sort_three_levels(pm_ctx *ctx, MsmSet &S, const BucketPlan &p, const 
     uint32_t *vals2 = (uint32_t *)((uint8_t *)ws.digits2.p + p.keys_bytes);
     const unsigned sblocks = (unsigned)((p.E + chunk - 1) / chunk), stblocks = (unsigned)((p.E + ST_CHUNK - 1) / ST_CHUNK);
     PM_HIP(ctx, hipMemsetAsync(sub_count, 0, (size_t)nsub * 4, st));
-    hipLaunchKernelGGL(k_hist_small, dim3(sblocks), dim3(1024), 0, st, b.keys, b.region_off, p.regions, FIN_BITS, SUB_BINS, chunk, sub_count);
-    PM_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, st, sub_count, sub_off, sub_cursor, nsub);
-    PM_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_region_pass_staged<RS_MID>, dim3(stblocks), dim3(ST_THREADS), 0, st, b.keys, b.vals, b.region_off, p.regions,
-                       FIN_BITS, SUB_BINS, sub_off, sub_cursor, (uint32_t *)nullptr, keys2, vals2);
-    PM_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_hist_small, dim3(sblocks), dim3(1024), 0, st, keys2, sub_off, nsub, 0u, FIN_BINS, chunk, counts);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_hist_small, dim3(sblocks), dim3(1024), 0, st, b.keys, b.region_off, p.regions, FIN_BITS, SUB_BINS, chunk, sub_count);
+    PM_LAUNCH(ctx, k_scan_small, dim3(1), dim3(1024), 0, st, sub_count, sub_off, sub_cursor, nsub);
+    PM_LAUNCH(ctx, k_region_pass_staged<RS_MID>, dim3(stblocks), dim3(ST_THREADS), 0, st, b.keys, b.vals, b.region_off, p.regions,
+                   FIN_BITS, SUB_BINS, sub_off, sub_cursor, (uint32_t *)nullptr, keys2, vals2);
+    PM_LAUNCH(ctx, k_hist_small, dim3(sblocks), dim3(1024), 0, st, keys2, sub_off, nsub, 0u, FIN_BINS, chunk, counts);
     PM_TRY(bucket_scan(ctx, S, p));
     // (round 5 measured the last level WITHOUT LDS staging -- lanes storing their 4-byte indices straight into the sub-region's
     // 120 KB output window, which stays in L2: the sort of a 2^24-pair MSM 2.66 -> 3.70 ms, a proof +2.2 ms; 64 partial-line
     // stores per wave instruction cost more than the staging saves: profiles/r05_sort_final_direct_negative.txt)
-    hipLaunchKernelGGL(k_region_pass_staged<RS_FINAL>, dim3(stblocks), dim3(ST_THREADS), 0, st, keys2, vals2, sub_off, nsub, 0u,
-                       FIN_BINS, S.bucket_off.as<uint32_t>(), cursor, S.sorted.as<uint32_t>(), (uint16_t *)nullptr, (uint32_t *)nullptr);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_region_pass_staged<RS_FINAL>, dim3(stblocks), dim3(ST_THREADS), 0, st, keys2, vals2, sub_off, nsub, 0u,
+                   FIN_BINS, S.bucket_off.as<uint32_t>(), cursor, S.sorted.as<uint32_t>(), (uint16_t *)nullptr, (uint32_t *)nullptr);
     return PM_OK;
 }
 
@@ -1374,15 +1353,13 @@ static int sort_one_region(pm_ctx *ctx, MsmSet &S, const BucketPlan &p, const So
     const unsigned chunk = 1u << RS_CHUNK_LOG, sblocks = (unsigned)((p.E + chunk - 1) / chunk);
     const size_t lds = (size_t)p.lo_buckets * 4;
     uint32_t *counts = S.counts.as<uint32_t>(), *cursor = counts + p.NB;
-    hipLaunchKernelGGL(k_region_pass<RS_HIST>, dim3(sblocks), dim3(1024), lds, st, b.keys, b.vals, b.region_off, p.regions, 0u,
-                       p.lo_buckets, chunk, counts, (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                       (uint16_t *)nullptr, (uint32_t *)nullptr);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_region_pass<RS_HIST>, dim3(sblocks), dim3(1024), lds, st, b.keys, b.vals, b.region_off, p.regions, 0u,
+                   p.lo_buckets, chunk, counts, (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
+                   (uint16_t *)nullptr, (uint32_t *)nullptr);
     PM_TRY(bucket_scan(ctx, S, p));
-    hipLaunchKernelGGL(k_region_pass<RS_FINAL>, dim3(sblocks), dim3(1024), lds, st, b.keys, b.vals, b.region_off, p.regions, 0u,
-                       p.lo_buckets, chunk, (uint32_t *)nullptr, S.bucket_off.as<uint32_t>(), cursor, S.sorted.as<uint32_t>(),
-                       (uint16_t *)nullptr, (uint32_t *)nullptr);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_region_pass<RS_FINAL>, dim3(sblocks), dim3(1024), lds, st, b.keys, b.vals, b.region_off, p.regions, 0u,
+                   p.lo_buckets, chunk, (uint32_t *)nullptr, S.bucket_off.as<uint32_t>(), cursor, S.sorted.as<uint32_t>(),
+                   (uint16_t *)nullptr, (uint32_t *)nullptr);
     return PM_OK;
 }
 
@@ -1531,9 +1508,8 @@ int msm_run_batch(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::Fr
             uint32_t *counts = S.counts.as<uint32_t>(), *cursor = counts + p.NB, *digits = ws.digits.as<uint32_t>();
             const unsigned nbuckets = (unsigned)p.NB1;
             PM_HIP(ctx, hipMemsetAsync(counts, 0, 2 * p.NB * 4, ctx->stream));
-            hipLaunchKernelGGL(k_digits_batch<C>, dim3((unsigned)((len + 255) / 256), (unsigned)rows), dim3(256), 0, ctx->stream,
-                               d_scalars + b0 * len, d_inf, digits, len, p.c, p.nwin);
-            PM_HIP(ctx, hipGetLastError());
+            PM_LAUNCH(ctx, k_digits_batch<C>, dim3((unsigned)((len + 255) / 256), (unsigned)rows), dim3(256), 0, ctx->stream,
+                           d_scalars + b0 * len, d_inf, digits, len, p.c, p.nwin);
             PM_TRY(sort_sets(ctx, S, p, digits, counts, cursor, nbuckets));
             PM_TRY(task_order(ctx, S, p));
         }
@@ -1546,9 +1522,8 @@ int msm_run_batch(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::Fr
             PM_TRY(fold_hot_buckets<C>(ctx, S, p));
             XYZZ<C> *d_sums = nullptr;
             PM_TRY(reduce_single_level<C>(ctx, S, p, &d_sums));
-            hipLaunchKernelGGL(k_window_combine<C>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, ctx->stream, d_sums, p.nwin, p.c,
-                               (unsigned)rows, d_res);
-            PM_HIP(ctx, hipGetLastError());
+            PM_LAUNCH(ctx, k_window_combine<C>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, ctx->stream, d_sums, p.nwin, p.c,
+                           (unsigned)rows, d_res);
         }
         PM_HIP(ctx, hipMemcpyAsync(res.data(), d_res, rows * sizeof(BatchPoint<C>), hipMemcpyDeviceToHost, ctx->stream));
         PM_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -248,15 +248,12 @@ int reduce_two_level(pm_ctx *ctx, size_t NB, XYZZ<C> **out, unsigned nsets, size
                  blocks1 = (lanes1 + per_block1 - 1) / per_block1;
     PM_HIP(ctx, ws.wsum.reserve((2 * lanes0 + (blocks0 > blocks1 ? blocks0 : blocks1) + 4 + nsets) * sizeof(XYZZ<C>)));
     XYZZ<C> *A = ws.wsum.as<XYZZ<C>>(), *Acc = A + lanes0, *parts = Acc + lanes0, *dres = parts + (blocks0 > blocks1 ? blocks0 : blocks1);
-    hipLaunchKernelGGL(k_reduce_level0<C>, dim3((unsigned)blocks0), dim3(256), 256 * sizeof(XYZZ28<C>), ctx->stream,
-                       S->partials.as<XYZZ<C>>(), S->task_off.as<uint32_t>() + bucket0, S->task_cnt.as<uint32_t>() + bucket0, total, lanes0, K0, A, Acc);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_reduce_level0<C>, dim3((unsigned)blocks0), dim3(256), 256 * sizeof(XYZZ28<C>), ctx->stream,
+                   S->partials.as<XYZZ<C>>(), S->task_off.as<uint32_t>() + bucket0, S->task_cnt.as<uint32_t>() + bucket0, total, lanes0, K0, A, Acc);
     const unsigned per_set = (unsigned)(blocks1 / nsets);     // level-1 workgroups (= partials) per set; exact when nsets > 1
-    hipLaunchKernelGGL((k_reduce_level1_coop<C, 4>), dim3((unsigned)blocks1), dim3(256), 64 * sizeof(XYZZ28<C>), ctx->stream, A, Acc,
-                       lanes0, K0, R1, parts, set_lanes);
-    PM_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL((k_sum_final_coop<C, 4>), dim3(nsets), dim3(256), 64 * sizeof(XYZZ28<C>), ctx->stream, parts, per_set, dres);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, (k_reduce_level1_coop<C, 4>), dim3((unsigned)blocks1), dim3(256), 64 * sizeof(XYZZ28<C>), ctx->stream, A, Acc,
+                   lanes0, K0, R1, parts, set_lanes);
+    PM_LAUNCH(ctx, (k_sum_final_coop<C, 4>), dim3(nsets), dim3(256), 64 * sizeof(XYZZ28<C>), ctx->stream, parts, per_set, dres);
     *out = dres;
     return PM_OK;
 }

@@ -578,8 +578,7 @@ int ntt_run_batch(pm_ctx *ctx, Fp<typename C::FrP> *d, unsigned log_n, bool inv_
         }
         return PM_OK;
     }
-    hipLaunchKernelGGL(k_bitrev<P>, dim3((unsigned)((n + 255) / 256), gy), dim3(256), 0, ctx->stream, d, log_n, row_stride);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_bitrev<P>, dim3((unsigned)((n + 255) / 256), gy), dim3(256), 0, ctx->stream, d, log_n, row_stride);
     unsigned s0 = 0;
     while (s0 < log_n) {
         unsigned ns = log_n - s0 < tile_log ? log_n - s0 : tile_log;
@@ -588,14 +587,12 @@ int ntt_run_batch(pm_ctx *ctx, Fp<typename C::FrP> *d, unsigned log_n, bool inv_
         if (s0 < log_cols) log_cols = s0;
         size_t tiles = n >> (ns + log_cols);
         size_t lds = ((size_t)1 << (ns + log_cols)) * sizeof(Fr);
-        hipLaunchKernelGGL((k_ntt_pass<P, typename C::FrRR>), dim3((unsigned)tiles, gy), dim3(256), lds, ctx->stream, (const Fr *)d, d, tw, log_n, s0, ns,
-                           log_cols, ninv, 0, row_stride, row_stride);
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, (k_ntt_pass<P, typename C::FrRR>), dim3((unsigned)tiles, gy), dim3(256), lds, ctx->stream, (const Fr *)d, d, tw, log_n, s0, ns,
+                       log_cols, ninv, 0, row_stride, row_stride);
         s0 += ns;
     }
     if (inv_dir) {
-        hipLaunchKernelGGL(k_scale<P>, dim3((unsigned)((n + 255) / 256), gy), dim3(256), 0, ctx->stream, d, n, ninv, row_stride);
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, k_scale<P>, dim3((unsigned)((n + 255) / 256), gy), dim3(256), 0, ctx->stream, d, n, ninv, row_stride);
     }
     return PM_OK;
 }

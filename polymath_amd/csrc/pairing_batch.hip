@@ -87,10 +87,9 @@ int pairing_check_launch(pm_ctx *ctx, const PairingPrepared &prep, const Affine<
     if (!count) return PM_OK;
     if (d_terms && prep.k != 3) return PM_ERR_INVALID_ARG;
     StageTimer t(ctx, timing_slot);
-    hipLaunchKernelGGL(k_pairing_check<C>, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, ctx->stream, (const typename T::Line *)prep.buf.p,
-                       (const typename T::Consts *)((const uint8_t *)prep.buf.p + prep.consts_offset), prep.k, prep.pairs, d_pts, d_terms, d_neg_g, d_live,
-                       G, count, d_is_one);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_pairing_check<C>, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, ctx->stream, (const typename T::Line *)prep.buf.p,
+                   (const typename T::Consts *)((const uint8_t *)prep.buf.p + prep.consts_offset), prep.k, prep.pairs, d_pts, d_terms, d_neg_g, d_live,
+                   G, count, d_is_one);
     return PM_OK;
 }
 
@@ -148,8 +147,7 @@ extern "C" int pm_pairing_check_batch(pm_ctx *ctx, int curve, const uint64_t *g2
     if (!count) return PM_OK;
     if (!g1 || !is_one) return PM_ERR_INVALID_ARG;
     try {
-        return curve == PM_BLS12_381 ? pairing_check_batch_impl<BlsCurve>(ctx, g2, k, g1, g1_stride, count, is_one)
-                                     : pairing_check_batch_impl<BnCurve>(ctx, g2, k, g1, g1_stride, count, is_one);
+        return with_curve(curve, [&](auto cv) { return pairing_check_batch_impl<type_of<decltype(cv)>>(ctx, g2, k, g1, g1_stride, count, is_one); });
     } catch (const std::bad_alloc &) {
         ctx->err = "pm_pairing_check_batch: out of host memory";
         return PM_ERR_STATE;

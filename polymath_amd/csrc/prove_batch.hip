@@ -1,9 +1,10 @@
 // pm_host_prove_batch, device side: the three phases of prove.hip over a GROUP of proofs against one unsharded key.  Every vector of
-// prove.hip is a [rows][len] array here (pm_ctx::pb), every kernel has the proof as grid y, and the three MSMs of a proof become three
-// msm_run_batch calls per group: row b of the [a] / [c] / [d] scalar matrices is proof b's scalar vector, laid out at the stride
-// msm_run_batch reads (the MSM's pair count).
+// prove.hip is a [rows][len] array here -- the same ProveWs type, the context's second instance `pb`, so that a proof in flight in `pw`
+// is left alone -- every kernel has the proof as grid y, and the three MSMs of a proof become three msm_run_batch calls per group: row b
+// of the [a] / [c] / [d] scalar matrices is proof b's scalar vector, laid out at the stride msm_run_batch reads (the MSM's pair count).
 //
-// The kernels are prove_kernels.cuh's, the ones prove.hip launches for one proof.  r_a goes up as a [rows][2] array; what else differs
+// The kernels are prove_kernels.cuh's, the ones prove.hip launches for one proof, and phase 1 between the uploads and the MSMs is
+// prove.hip's phase1_enqueue_u / phase1_enqueue_rest with rows = the group.  r_a goes up as a [rows][2] array; what else differs
 // from proof to proof (x1, the numerator's constants and reduced-radix multipliers, the division's level multipliers) is one BatchRow
 // record per proof in device memory, uploaded once per phase and indexed by blockIdx.y.  Each proof has its own flag word.
 // A proof whose witness fails a check keeps running (every operation is defined on any field values); the host drops its result.
@@ -50,11 +51,7 @@ int prove_batch_group(pm_ctx *ctx, const pm_pk *pk, size_t count, size_t *group)
     if (g > 65535) g = 65535;                       // grid y
     size_t free_b = 0, total_b = 0;
     PM_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-    size_t held = 0;
-    ProveBatchWs &ws = ctx->pb;
-    for (const DevBuf *b : {&ws.xw, &ws.ue, &ws.we, &ws.u, &ws.w, &ws.wit_u, &ws.u2, &ws.tmp, &ws.sc_a, &ws.sc_c, &ws.quotient, &ws.part, &ws.rows, &ws.flags})
-        held += b->bytes;
-    for (const DevBuf &b : ws.lvl) held += b.bytes;
+    const size_t held = ctx->pb.bytes_held();
     unsigned nwin = 0, c = 0;
     msm_plan_query((size_t)d.len_d, (unsigned)C::FrP::BITS, &nwin, &c);
     const size_t per_row = row_elems(d) * sizeof(Fr) + (size_t)nwin * d.len_d * 16 +
@@ -90,20 +87,18 @@ int prove_batch_phase1(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t
     const ProofShape d = proof_shape(pk);
     if (!layout_ok(pk, d) || rows == 0 || rows > 65535) return PM_ERR_INVALID_ARG;
     if (pk->log_n + 1 > (unsigned)C::TWO_ADICITY) return PM_ERR_DOMAIN_TOO_LARGE;  // prover.rs:317
-    const uint64_t n = d.n, m0 = d.m0, mw = d.mw, nr = d.nr, Lz = d.Lz, len_a = d.len_a, len_c = d.len_c;
-    const unsigned gy = (unsigned)rows;
+    const uint64_t n = d.n, m0 = d.m0, mw = d.mw, len_a = d.len_a, len_c = d.len_c;
     hipStream_t st = ctx->stream;
     TimingGuard timing_guard{ctx};
     StageTimer t_phase(ctx, T_PHASE);
-    ProveBatchWs &ws = ctx->pb;
+    ProveWs &ws = ctx->pb;
     PM_HIP(ctx, ws.xw.reserve(rows * (m0 + mw) * sizeof(Fr)));
     for (DevBuf *b : {&ws.ue, &ws.we, &ws.u, &ws.w, &ws.wit_u, &ws.tmp}) PM_HIP(ctx, b->reserve(rows * n * sizeof(Fr)));
     PM_HIP(ctx, ws.u2.reserve(rows * 2 * n * sizeof(Fr)));
     PM_HIP(ctx, ws.sc_c.reserve(rows * len_c * sizeof(Fr)));
     PM_HIP(ctx, ws.sc_a.reserve(rows * len_a * sizeof(Fr)));
     PM_HIP(ctx, ws.flags.reserve(rows * sizeof(unsigned)));
-    Fr *xw = ws.xw.as<Fr>(), *ue = ws.ue.as<Fr>(), *we = ws.we.as<Fr>(), *u = ws.u.as<Fr>(), *wv = ws.w.as<Fr>();
-    Fr *wit_u = ws.wit_u.as<Fr>(), *u2 = ws.u2.as<Fr>(), *tmp = ws.tmp.as<Fr>(), *sc_c = ws.sc_c.as<Fr>(), *sc_a = ws.sc_a.as<Fr>();
+    Fr *xw = ws.xw.as<Fr>(), *sc_c = ws.sc_c.as<Fr>(), *sc_a = ws.sc_a.as<Fr>();
     unsigned *flags = ws.flags.as<unsigned>();
     PM_HIP(ctx, hipMemsetAsync(flags, 0, rows * sizeof(unsigned), st));
     const hipMemcpyKind kind = assignment_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -113,60 +108,9 @@ int prove_batch_phase1(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t
         if (mw) PM_HIP(ctx, hipMemcpy2DAsync(xw + m0, (m0 + mw) * sizeof(Fr), w, mw * sizeof(Fr), mw * sizeof(Fr), rows, kind, st));
     }
     PM_HIP(ctx, ws.rows.reserve(rows * 2 * sizeof(Fr)));      // this phase's per-proof values are r_a alone: [rows][2]
-    Fr *ra = ws.rows.as<Fr>();
-    PM_HIP(ctx, hipMemcpyAsync(ra, r_a, rows * 2 * sizeof(Fr), hipMemcpyHostToDevice, st));
-    {
-        StageTimer t(ctx, T_WITNESS_MAP);
-        CsrDev A{pk->d_rowptr[0], pk->d_col[0], pk->d_val[0]}, B{pk->d_rowptr[1], pk->d_col[1], pk->d_val[1]},
-            Cm{pk->d_rowptr[2], pk->d_col[2], pk->d_val[2]};
-        const uint64_t head = n > m0 + mw ? n : m0 + mw;
-        hipLaunchKernelGGL(k_witness_head<P>, dim3(nblk(head), gy), dim3(256), 0, st, xw, m0 + mw, ue, we, sc_c, len_c, m0, mw, nr, n);
-        PM_HIP(ctx, hipGetLastError());
-        if (nr) {
-            hipLaunchKernelGGL(k_witness_rows<P>, dim3(nblk(nr), gy), dim3(256), 0, st, A, B, Cm, xw, m0 + mw, ue, we, n, sc_c + m0 + mw, len_c,
-                               m0, nr);
-            PM_HIP(ctx, hipGetLastError());
-        }
-        hipLaunchKernelGGL(k_check_sap<P>, dim3(nblk(n), gy), dim3(256), 0, st, ue, we, n, flags);
-        PM_HIP(ctx, hipGetLastError());
-    }
-    PM_HIP(ctx, hipMemcpyAsync(u, ue, rows * n * sizeof(Fr), hipMemcpyDeviceToDevice, st));
-    PM_HIP(ctx, hipMemcpyAsync(wv, we, rows * n * sizeof(Fr), hipMemcpyDeviceToDevice, st));
-    PM_TRY(ntt_run_batch<C>(ctx, u, pk->log_n, true, rows, n));
-    hipLaunchKernelGGL(k_sc_a<P>, dim3(nblk(n), gy), dim3(256), 0, st, u, ra, (uint64_t)2, sc_a, len_a, n);
-    PM_HIP(ctx, hipGetLastError());
-    PM_TRY(ntt_run_batch<C>(ctx, wv, pk->log_n, true, rows, n));
-    if (2 * m0 <= 16 && pk->log_n >= 1) {   // few public inputs: the sparse sum beats a fifth transform
-        const Fr *winv = nullptr;
-        PM_TRY(twiddles_get<C>(ctx, pk->log_n, true, &winv));
-        StageTimer t(ctx, T_NTT);
-        hipLaunchKernelGGL(k_wit_u_sparse<P>, dim3(nblk(n), gy), dim3(256), 0, st, u, ue, winv, inverse<P>(from_u64<P>(n)), n, (unsigned)(2 * m0),
-                           wit_u);
-        PM_HIP(ctx, hipGetLastError());
-    } else {
-        hipLaunchKernelGGL(k_copy_zero_head<P>, dim3(nblk(n), gy), dim3(256), 0, st, ue, wit_u, n, 2 * m0);
-        PM_HIP(ctx, hipGetLastError());
-        PM_TRY(ntt_run_batch<C>(ctx, wit_u, pk->log_n, true, rows, n));
-    }
-    {
-        const Fr *psi = nullptr, *psi_inv = nullptr;
-        PM_TRY(twiddles_get<C>(ctx, pk->log_n + 1, false, &psi));
-        PM_TRY(twiddles_get<C>(ctx, pk->log_n + 1, true, &psi_inv));
-        hipLaunchKernelGGL(k_twist<P>, dim3(nblk(n), gy), dim3(256), 0, st, u, psi, tmp, n);
-        PM_HIP(ctx, hipGetLastError());
-        PM_TRY(ntt_run_batch<C>(ctx, tmp, pk->log_n, false, rows, n));
-        hipLaunchKernelGGL(k_square<P>, dim3(nblk(n), gy), dim3(256), 0, st, tmp, n);
-        PM_HIP(ctx, hipGetLastError());
-        PM_TRY(ntt_run_batch<C>(ctx, tmp, pk->log_n, true, rows, n));
-        hipLaunchKernelGGL(k_untwist_combine<P>, dim3(nblk(n), gy), dim3(256), 0, st, tmp, psi_inv, wv, u2, n, inverse<P>(from_u64<P>(2)));
-        PM_HIP(ctx, hipGetLastError());
-    }
-    {
-        StageTimer t(ctx, T_POLY);
-        hipLaunchKernelGGL(k_phase1_scalars<P>, dim3(nblk(n + 1), gy), dim3(256), 0, st, u, u2, ra, (uint64_t)2, sc_c + Lz, len_c, (Fr *)nullptr,
-                           len_a, n, flags);
-        PM_HIP(ctx, hipGetLastError());
-    }
+    PM_HIP(ctx, hipMemcpyAsync(ws.rows.p, r_a, rows * 2 * sizeof(Fr), hipMemcpyHostToDevice, st));
+    PM_TRY(phase1_enqueue_u<C>(ctx, pk, d, ws, rows, true));
+    PM_TRY(phase1_enqueue_rest<C>(ctx, pk, d, ws, rows, (Fr *)nullptr));
     // [a]_1 and [c]_1 of every proof of the group: two batches over the key's PLAIN points (no tables, no wide plan)
     const Affine<C> *bases = (const Affine<C> *)pk->d_bases;
     PM_TRY(msm_run_batch<C>(ctx, bases + pk->res_dev_off[0], sc_a, (size_t)len_a, rows, a, a_inf));
@@ -183,7 +127,7 @@ int prove_batch_phase2(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t
     const ProofShape d = proof_shape(pk);
     if (rows == 0 || rows > 65535) return PM_ERR_INVALID_ARG;
     hipStream_t st = ctx->stream;
-    ProveBatchWs &ws = ctx->pb;
+    ProveWs &ws = ctx->pb;
     std::vector<BatchRow<P>> par(rows);
     memset((void *)par.data(), 0, rows * sizeof(BatchRow<P>));
     for (size_t b = 0; b < rows; ++b) par[b].x1 = load_fr<P>(x1 + 4 * b);
@@ -192,10 +136,8 @@ int prove_batch_phase2(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t
     const unsigned blocks = nblk(lanes);
     PM_HIP(ctx, ws.part.reserve(rows * ((size_t)blocks + 1) * sizeof(Fr)));
     Fr *part = ws.part.as<Fr>(), *sums = part + rows * blocks;
-    hipLaunchKernelGGL(k_horner_partial_rows<P>, dim3(blocks, (unsigned)rows), dim3(256), 0, st, ws.u.as<Fr>(), d.n, ws.rows.as<BatchRow<P>>(), HORNER_L, part);
-    PM_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_sum_small<P>, dim3((unsigned)rows), dim3(256), 0, st, part, blocks, sums);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_horner_partial_rows<P>, dim3(blocks, (unsigned)rows), dim3(256), 0, st, ws.u.as<Fr>(), d.n, ws.rows.as<BatchRow<P>>(), HORNER_L, part);
+    PM_LAUNCH(ctx, k_sum_small<P>, dim3((unsigned)rows), dim3(256), 0, st, part, blocks, sums);
     PM_HIP(ctx, hipMemcpyAsync(u_at_x1, sums, rows * sizeof(Fr), hipMemcpyDeviceToHost, st));
     PM_HIP(ctx, hipStreamSynchronize(st));
     return PM_OK;
@@ -213,7 +155,7 @@ int prove_batch_phase3(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t
     hipStream_t st = ctx->stream;
     TimingGuard timing_guard{ctx};
     StageTimer t_phase(ctx, T_PHASE);
-    ProveBatchWs &ws = ctx->pb;
+    ProveWs &ws = ctx->pb;
     NumParams np{d.n, d.sigma, d.num_len};
     std::vector<BatchRow<P>> par(rows);
     memset((void *)par.data(), 0, rows * sizeof(BatchRow<P>));
@@ -228,15 +170,10 @@ int prove_batch_phase3(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t
     }
     PM_TRY(upload_rows<C>(ctx, par));
     const BatchRow<P> *drows = ws.rows.as<BatchRow<P>>();
-    // V[l] | H[l] of level l >= 1, per row: cnt[l] values, then cnt[l] + 1 suffix values
-    Fr *V[8] = {nullptr}, *H[8] = {nullptr};
-    uint64_t vs[8] = {0};
-    for (int l = 1; l <= levels; ++l) {
-        vs[l] = 2 * d.cnt[l] + 2;
-        PM_HIP(ctx, ws.lvl[l - 1].reserve(rows * vs[l] * sizeof(Fr)));
-        V[l] = ws.lvl[l - 1].as<Fr>();
-        H[l] = V[l] + d.cnt[l];
-    }
+    DivLevels<Fr> lv;
+    PM_HIP(ctx, div_levels_reserve(ws, d, rows, lv));
+    Fr *const *V = lv.V, *const *H = lv.H;
+    const uint64_t *vs = lv.vs;
     PM_HIP(ctx, ws.quotient.reserve((rows * d.len_d + 2) * sizeof(Fr)));
     Fr *q = ws.quotient.as<Fr>();
     unsigned *flags = ws.flags.as<unsigned>();
@@ -244,28 +181,22 @@ int prove_batch_phase3(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t
     {
         StageTimer t(ctx, T_POLY);
         if (levels == 0) {   // small: one lane per proof does the whole division
-            hipLaunchKernelGGL(k_div_expand0_rows<P>, dim3(1, gy), dim3(64), 0, st, np, drows, u, wit_u, u2, (unsigned)np.len, (uint64_t)1,
-                               (const Fr *)nullptr, (uint64_t)0, q, d.len_d, flags);
-            PM_HIP(ctx, hipGetLastError());
+            PM_LAUNCH(ctx, k_div_expand0_rows<P>, dim3(1, gy), dim3(64), 0, st, np, drows, u, wit_u, u2, (unsigned)np.len, (uint64_t)1,
+                           (const Fr *)nullptr, (uint64_t)0, q, d.len_d, flags);
         } else {
-            hipLaunchKernelGGL(k_div_level0_rows<P>, dim3(nblk(d.cnt[1]), gy), dim3(256), 0, st, np, drows, u, wit_u, u2, L, d.cnt[1], V[1], vs[1]);
-            PM_HIP(ctx, hipGetLastError());
+            PM_LAUNCH(ctx, k_div_level0_rows<P>, dim3(nblk(d.cnt[1]), gy), dim3(256), 0, st, np, drows, u, wit_u, u2, L, d.cnt[1], V[1], vs[1]);
             for (int l = 1; l < levels; ++l) {
-                hipLaunchKernelGGL(k_div_levelN_rows<P>, dim3(nblk(d.cnt[l + 1]), gy), dim3(256), 0, st, V[l], vs[l], d.cnt[l], drows, l, L, d.cnt[l + 1],
-                                   V[l + 1], vs[l + 1]);
-                PM_HIP(ctx, hipGetLastError());
+                PM_LAUNCH(ctx, k_div_levelN_rows<P>, dim3(nblk(d.cnt[l + 1]), gy), dim3(256), 0, st, V[l], vs[l], d.cnt[l], drows, l, L, d.cnt[l + 1],
+                               V[l + 1], vs[l + 1]);
             }
-            hipLaunchKernelGGL(k_div_top_rows<P>, dim3(nblk(rows, 64)), dim3(64), 0, st, V[levels], vs[levels], d.cnt[levels], drows, levels, gy,
-                               H[levels]);
-            PM_HIP(ctx, hipGetLastError());
+            PM_LAUNCH(ctx, k_div_top_rows<P>, dim3(nblk(rows, 64)), dim3(64), 0, st, V[levels], vs[levels], d.cnt[levels], drows, levels, gy,
+                           H[levels]);
             for (int l = levels - 1; l >= 1; --l) {
-                hipLaunchKernelGGL(k_div_expandN_rows<P>, dim3(nblk(d.cnt[l + 1]), gy), dim3(256), 0, st, V[l], vs[l], d.cnt[l], drows, l, L, d.cnt[l + 1],
-                                   H[l + 1], vs[l + 1], H[l]);
-                PM_HIP(ctx, hipGetLastError());
+                PM_LAUNCH(ctx, k_div_expandN_rows<P>, dim3(nblk(d.cnt[l + 1]), gy), dim3(256), 0, st, V[l], vs[l], d.cnt[l], drows, l, L, d.cnt[l + 1],
+                               H[l + 1], vs[l + 1], H[l]);
             }
-            hipLaunchKernelGGL(k_div_expand0_rows<P>, dim3(nblk(d.cnt[1]), gy), dim3(256), 0, st, np, drows, u, wit_u, u2, L, d.cnt[1], H[1], vs[1], q,
-                               d.len_d, flags);
-            PM_HIP(ctx, hipGetLastError());
+            PM_LAUNCH(ctx, k_div_expand0_rows<P>, dim3(nblk(d.cnt[1]), gy), dim3(256), 0, st, np, drows, u, wit_u, u2, L, d.cnt[1], H[1], vs[1], q,
+                           d.len_d, flags);
         }
     }
     PM_TRY(msm_run_batch<C>(ctx, (const Affine<C> *)pk->d_bases + pk->res_dev_off[2], q, (size_t)d.len_d, rows, dpt, d_inf));   // [d]_1 = M8

@@ -80,6 +80,25 @@ static inline ProofShape proof_shape(uint64_t n, uint64_t m0, uint64_t mw, uint6
 }
 static inline ProofShape proof_shape(const pm_pk *pk) { return proof_shape(pk->n, pk->m0, pk->mw, pk->nr, pk->sigma); }
 
+// Phase 3: the division's level buffers of `rows` proofs in ws.lvl, reserved.  Level l >= 1 of a proof is V[l] (cnt[l] values) followed
+// by H[l] (cnt[l] + 1 suffix values); proof b's are vs[l] elements further on than proof b - 1's.
+template <class Fr>
+struct DivLevels {
+    Fr *V[8] = {nullptr}, *H[8] = {nullptr};
+    uint64_t vs[8] = {0};
+};
+template <class Fr>
+static inline hipError_t div_levels_reserve(ProveWs &ws, const ProofShape &d, size_t rows, DivLevels<Fr> &lv) {
+    for (int l = 1; l <= d.levels; ++l) {
+        lv.vs[l] = 2 * d.cnt[l] + 2;
+        const hipError_t e = ws.lvl[l - 1].reserve(rows * lv.vs[l] * sizeof(Fr));
+        if (e != hipSuccess) return e;
+        lv.V[l] = ws.lvl[l - 1].template as<Fr>();
+        lv.H[l] = lv.V[l] + d.cnt[l];
+    }
+    return hipSuccess;
+}
+
 // The flag word of a proof (k_check_sap) as a status.  Phase 1 reads bits 0-2, phase 3 bit 3.
 static inline int phase1_flag_status(unsigned flags) {
     if (flags & 1u) return PM_ERR_REMAINDER_NONZERO;                  // prover.rs:108

@@ -705,23 +705,23 @@ int prove_phase1_sharded(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const 
     if (len_c != pk->res_cnt[1] || m + (q == 0 ? 2 : 0) != pk->res_cnt[0]) return PM_ERR_STATE;   // key and prover disagree on the layout
     // assignment: [x (m0) | w padded to N slices of wblk | staging of this rank's slice]
     const uint64_t wblk = (mw + N - 1) / N;
-    PM_HIP(ctx, ctx->xw.reserve((m0 + ((uint64_t)N + 1) * wblk) * sizeof(Fr)));
-    PM_HIP(ctx, ctx->ue.reserve(m * sizeof(Fr)));
-    PM_HIP(ctx, ctx->we.reserve(m * sizeof(Fr)));
-    PM_HIP(ctx, ctx->u.reserve((m + 2) * sizeof(Fr)));
-    PM_HIP(ctx, ctx->w.reserve(m * sizeof(Fr)));
-    PM_HIP(ctx, ctx->wit_u.reserve(m * sizeof(Fr)));
-    PM_HIP(ctx, ctx->u2.reserve(2 * m * sizeof(Fr)));
-    PM_HIP(ctx, ctx->sc_c.reserve((len_c + 1) * sizeof(Fr)));
-    PM_HIP(ctx, ctx->ra.reserve(2 * sizeof(Fr)));
-    PM_HIP(ctx, ctx->flags.reserve(64));
+    PM_HIP(ctx, ctx->pw.xw.reserve((m0 + ((uint64_t)N + 1) * wblk) * sizeof(Fr)));
+    PM_HIP(ctx, ctx->pw.ue.reserve(m * sizeof(Fr)));
+    PM_HIP(ctx, ctx->pw.we.reserve(m * sizeof(Fr)));
+    PM_HIP(ctx, ctx->pw.u.reserve((m + 2) * sizeof(Fr)));
+    PM_HIP(ctx, ctx->pw.w.reserve(m * sizeof(Fr)));
+    PM_HIP(ctx, ctx->pw.wit_u.reserve(m * sizeof(Fr)));
+    PM_HIP(ctx, ctx->pw.u2.reserve(2 * m * sizeof(Fr)));
+    PM_HIP(ctx, ctx->pw.sc_c.reserve((len_c + 1) * sizeof(Fr)));
+    PM_HIP(ctx, ctx->pw.rows.reserve(2 * sizeof(Fr)));
+    PM_HIP(ctx, ctx->pw.flags.reserve(64));
     PM_HIP(ctx, ctx->sh_a.reserve(m * sizeof(Fr)));
     PM_HIP(ctx, ctx->sh_b.reserve(m * sizeof(Fr)));
     PM_HIP(ctx, ctx->sh_c.reserve((m > 2 * m0 ? m : 2 * m0) * sizeof(Fr)));
-    Fr *xw = ctx->xw.as<Fr>(), *ue = ctx->ue.as<Fr>(), *we = ctx->we.as<Fr>(), *u = ctx->u.as<Fr>(), *wv = ctx->w.as<Fr>();
-    Fr *wit_u = ctx->wit_u.as<Fr>(), *u2lo = ctx->u2.as<Fr>(), *u2hi = u2lo + m, *sc_c = ctx->sc_c.as<Fr>(), *ra = ctx->ra.as<Fr>();
+    Fr *xw = ctx->pw.xw.as<Fr>(), *ue = ctx->pw.ue.as<Fr>(), *we = ctx->pw.we.as<Fr>(), *u = ctx->pw.u.as<Fr>(), *wv = ctx->pw.w.as<Fr>();
+    Fr *wit_u = ctx->pw.wit_u.as<Fr>(), *u2lo = ctx->pw.u2.as<Fr>(), *u2hi = u2lo + m, *sc_c = ctx->pw.sc_c.as<Fr>(), *ra = ctx->pw.rows.as<Fr>();
     Fr *ta = ctx->sh_a.as<Fr>(), *tb = ctx->sh_b.as<Fr>(), *tc = ctx->sh_c.as<Fr>();
-    unsigned *flags = ctx->flags.as<unsigned>();
+    unsigned *flags = ctx->pw.flags.as<unsigned>();
     PM_HIP(ctx, hipMemsetAsync(flags, 0, 64, st));
     // Every rank needs the whole assignment (the rows it owns read arbitrary columns: prover.rs:279-302).  From HOST buffers
     // each rank uploads only its 1/N slice of w over its own PCIe link and the fabric delivers the rest (all-gather of
@@ -746,21 +746,17 @@ int prove_phase1_sharded(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const 
     const bool sparse_head = 2 * m0 <= 16;
     {
         StageTimer t(ctx, T_WITNESS_MAP);
-        hipLaunchKernelGGL(k_witness_cyclic<P>, dim3(nblk(m)), dim3(256), 0, st, A, Bm, Cm, xw, ue, we, m0, nr, L);
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, k_witness_cyclic<P>, dim3(nblk(m)), dim3(256), 0, st, A, Bm, Cm, xw, ue, we, m0, nr, L);
         if (zcnt) {
-            hipLaunchKernelGGL(k_ztail_slice<P>, dim3(nblk(zcnt)), dim3(256), 0, st, A, Bm, xw, sc_c, m0, mw, zl, zh);
-            PM_HIP(ctx, hipGetLastError());
+            PM_LAUNCH(ctx, k_ztail_slice<P>, dim3(nblk(zcnt)), dim3(256), 0, st, A, Bm, xw, sc_c, m0, mw, zl, zh);
         }
-        hipLaunchKernelGGL(k_check_sap_L<P>, dim3(nblk(m)), dim3(256), 0, st, ue, we, m, flags);   // rem == 0 of prover.rs:108
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, k_check_sap_L<P>, dim3(nblk(m)), dim3(256), 0, st, ue, we, m, flags);   // rem == 0 of prover.rs:108
     }
     hp.mark("upload+witness");
     // N1, N2 (prover.rs:94,96): the transforms consume their input, so the witness-only U part (N5) is prepared first
     if (!sparse_head) {
         PM_HIP(ctx, hipMemcpyAsync(tc, ue, m * sizeof(Fr), hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_zero_head_cyclic<P>, dim3(nblk(m)), dim3(256), 0, st, tc, 2 * m0, L);
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, k_zero_head_cyclic<P>, dim3(nblk(m)), dim3(256), 0, st, tc, 2 * m0, L);
         PM_TRY(dist_intt<C>(ctx, pk, L, tc, ta, wit_u));
     }
     // PM_OPT_NTT_OVERLAP: w's transform (N2) runs on the helper context's stream beside u's chain
@@ -785,30 +781,24 @@ int prove_phase1_sharded(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const 
         const Fr *winv = nullptr;
         PM_TRY(twiddles_get<C>(ctx, pk->log_n, true, &winv));
         StageTimer t(ctx, T_NTT);
-        hipLaunchKernelGGL(k_ue_head<P>, dim3(1), dim3(64), 0, st, A, Bm, Cm, xw, tc, m0, nr, (unsigned)(2 * m0));
-        PM_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_wit_u_sparse_L<P>, dim3(nblk(m)), dim3(256), 0, st, u, tc, winv, inverse<P>(from_u64<P>(n)), (unsigned)(2 * m0), wit_u, L);
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, k_ue_head<P>, dim3(1), dim3(64), 0, st, A, Bm, Cm, xw, tc, m0, nr, (unsigned)(2 * m0));
+        PM_LAUNCH(ctx, k_wit_u_sparse_L<P>, dim3(nblk(m)), dim3(256), 0, st, u, tc, winv, inverse<P>(from_u64<P>(n)), (unsigned)(2 * m0), wit_u, L);
     }
     {   // square_polynomial (prover.rs:315-328) through the negacyclic half (prove.hip: k_twist): u^2 = lo + X^n hi
         const Fr *psi = nullptr, *psi_inv = nullptr;
         PM_TRY(twiddles_get<C>(ctx, pk->log_n + 1, false, &psi));
         PM_TRY(twiddles_get<C>(ctx, pk->log_n + 1, true, &psi_inv));
-        hipLaunchKernelGGL(k_twist_L<P>, dim3(nblk(m)), dim3(256), 0, st, u, psi, ta, L);
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, k_twist_L<P>, dim3(nblk(m)), dim3(256), 0, st, u, psi, ta, L);
         PM_TRY(dist_ntt<C>(ctx, pk, L, ta, tb, tc));
-        hipLaunchKernelGGL(k_square_L<P>, dim3(nblk(m)), dim3(256), 0, st, tc, m);
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, k_square_L<P>, dim3(nblk(m)), dim3(256), 0, st, tc, m);
         PM_TRY(dist_intt<C>(ctx, pk, L, tc, tb, ta));
         if (wctx != ctx) PM_HIP(ctx, hipStreamWaitEvent(st, wctx->ev_sc_a, 0));   // w's coefficients
-        hipLaunchKernelGGL(k_untwist_combine_L<P>, dim3(nblk(m)), dim3(256), 0, st, ta, psi_inv, wv, u2lo, u2hi, L, inverse<P>(from_u64<P>(2)));
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, k_untwist_combine_L<P>, dim3(nblk(m)), dim3(256), 0, st, ta, psi_inv, wv, u2lo, u2hi, L, inverse<P>(from_u64<P>(2)));
     }
     {
         StageTimer t(ctx, T_POLY);
-        hipLaunchKernelGGL(k_phase1_scalars_L<P>, dim3(nblk(m)), dim3(256), 0, st, u, u2hi, ra, sc_c + zcnt, sc_c + zcnt + hcnt,
-                           tail ? sc_c + zcnt + hcnt + rucnt : (Fr *)nullptr, L, flags);
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, k_phase1_scalars_L<P>, dim3(nblk(m)), dim3(256), 0, st, u, u2hi, ra, sc_c + zcnt, sc_c + zcnt + hcnt,
+                       tail ? sc_c + zcnt + hcnt + rucnt : (Fr *)nullptr, L, flags);
     }
     hp.mark("transforms");
     // ONE exchange for the whole phase, after the MSMs: the status flags, the two partial points and the halo coefficients
@@ -824,8 +814,7 @@ int prove_phase1_sharded(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const 
     Fr *my_halo = (Fr *)(mine.data() + sizeof(Rec1));
     PM_HIP(ctx, ctx->halo.reserve(2 * (size_t)N * sizeof(Fr)));            // [halo of my blocks (phase 3) | my blocks' last coefficients]
     Fr *d_last = ctx->halo.as<Fr>() + N;
-    hipLaunchKernelGGL(k_halo_pack<P>, dim3((N + 63) / 64), dim3(64), 0, st, (const Fr *)u, L, d_last);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_halo_pack<P>, dim3((N + 63) / 64), dim3(64), 0, st, (const Fr *)u, L, d_last);
     // flags and halo go to PINNED staging (a pageable destination would make these two copies wait for the stream -- all transforms --
     // before the MSM pipelines below could even be enqueued) and into the record after the MSMs' final synchronisation
     uint8_t *stage = nullptr;
@@ -929,23 +918,20 @@ int prove_phase2_sharded(pm_ctx *ctx, const uint64_t *x1_in, uint64_t *u_at_x1) 
     const size_t S = pk->segs.size(), SS = pk->seg_slots;   // SS = the longest segment list of any rank (the exchanged record size)
     const size_t rec = 1 + 2 * SS;                          // [ u(x1) partial | P_s (SS) | Q_s (SS) ]
     PM_HIP(ctx, ctx->scratch.reserve(((size_t)blocks + rec) * sizeof(Fr)));
-    PM_HIP(ctx, ctx->lvl[0].reserve(2 * S * SEG_THREADS_MAX * sizeof(Fr)));    // lane values of the division scan: laneP | laneQ
+    PM_HIP(ctx, ctx->pw.lvl[0].reserve(2 * S * SEG_THREADS_MAX * sizeof(Fr)));    // lane values of the division scan: laneP | laneQ
     Fr *part = ctx->scratch.as<Fr>(), *out = part + blocks;
-    Fr *laneP = ctx->lvl[0].as<Fr>(), *laneQ = laneP + S * SEG_THREADS_MAX;
-    hipLaunchKernelGGL(k_horner_partial_L<P>, dim3(blocks), dim3(256), 0, st, ctx->u.as<Fr>(), L, x1, Lh, part);
-    PM_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_phase2_pack<P>, dim3(1), dim3(256), 0, st, (const Fr *)part, blocks, out);
-    PM_HIP(ctx, hipGetLastError());
+    Fr *laneP = ctx->pw.lvl[0].as<Fr>(), *laneQ = laneP + S * SEG_THREADS_MAX;
+    PM_LAUNCH(ctx, k_horner_partial_L<P>, dim3(blocks), dim3(256), 0, st, ctx->pw.u.as<Fr>(), L, x1, Lh, part);
+    PM_LAUNCH(ctx, k_phase2_pack<P>, dim3(1), dim3(256), 0, st, (const Fr *)part, blocks, out);
     {   // the x1-dependent half of phase 3's division scan (k_seg_base): its segment sums ride on this phase's exchange
         StageTimer t(ctx, T_POLY);
         const SegData sd{pk->n, pk->sigma};
         const uint64_t m = pk->n / (uint64_t)pk->shard_count;
-        const Fr *u = ctx->u.as<Fr>(), *wit_u = ctx->wit_u.as<Fr>(), *u2lo = ctx->u2.as<Fr>(), *u2hi = u2lo + m, *halo = ctx->halo.as<Fr>();
+        const Fr *u = ctx->pw.u.as<Fr>(), *wit_u = ctx->pw.wit_u.as<Fr>(), *u2lo = ctx->pw.u2.as<Fr>(), *u2hi = u2lo + m, *halo = ctx->halo.as<Fr>();
         const Segment *d_segs = (const Segment *)pk->d_segs;
         PM_HIP(ctx, hipMemsetAsync(out + 1, 0, 2 * SS * sizeof(Fr), st));
-        hipLaunchKernelGGL((k_seg_base<P, SEG_LANES>), dim3((unsigned)S), dim3(SEG_LANES), 0, st, d_segs, sd, u, wit_u, u2lo, u2hi, halo, x1, laneP, laneQ,
-                           out + 1, out + 1 + SS);
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, (k_seg_base<P, SEG_LANES>), dim3((unsigned)S), dim3(SEG_LANES), 0, st, d_segs, sd, u, wit_u, u2lo, u2hi, halo, x1, laneP, laneQ,
+                       out + 1, out + 1 + SS);
     }
     std::vector<Fr> mine(rec);
     ctx->seg_all.resize(rec * L.N * sizeof(Fr));
@@ -991,16 +977,16 @@ int prove_phase3_sharded(pm_ctx *ctx, const uint64_t *x1_in, const uint64_t *x2_
         ctx->err = "phase 3 needs the x1 of phase 2 (its data sums of the division scan were taken at that point)";
         return phase_end.ok(PM_ERR_INVALID_ARG);   // the same call on every rank: a verdict they share, the communicator stays usable
     }
-    PM_HIP(ctx, ctx->quotient.reserve((pk->res_cnt[2] + 1) * sizeof(Fr)));
-    PM_HIP(ctx, ctx->lvl[1].reserve((S + 1) * sizeof(Fr)));            // carries
-    Fr *qv = ctx->quotient.as<Fr>(), *laneP = ctx->lvl[0].as<Fr>(), *laneQ = laneP + S * SEG_THREADS_MAX, *carry = ctx->lvl[1].as<Fr>();
-    const Fr *u = ctx->u.as<Fr>(), *wit_u = ctx->wit_u.as<Fr>(), *u2lo = ctx->u2.as<Fr>(), *u2hi = u2lo + m, *halo = ctx->halo.as<Fr>();
+    PM_HIP(ctx, ctx->pw.quotient.reserve((pk->res_cnt[2] + 1) * sizeof(Fr)));
+    PM_HIP(ctx, ctx->pw.lvl[1].reserve((S + 1) * sizeof(Fr)));            // carries
+    Fr *qv = ctx->pw.quotient.as<Fr>(), *laneP = ctx->pw.lvl[0].as<Fr>(), *laneQ = laneP + S * SEG_THREADS_MAX, *carry = ctx->pw.lvl[1].as<Fr>();
+    const Fr *u = ctx->pw.u.as<Fr>(), *wit_u = ctx->pw.wit_u.as<Fr>(), *u2lo = ctx->pw.u2.as<Fr>(), *u2hi = u2lo + m, *halo = ctx->halo.as<Fr>();
     const Segment *d_segs = (const Segment *)pk->d_segs;
     // The carry chain over ALL segments (k_seg_chain, one workgroup), then the expansion of this rank's segments; phase 2's
     // exchanged data sums go up once (N x (1 + 2 SS) Fr, ~80 KB at N = 8), the remainder H_0 comes back with the MSM's result.
     const size_t T = pk->all_segs.size();
-    PM_HIP(ctx, ctx->lvl[2].reserve(rec * N * sizeof(Fr)));
-    Fr *d_hall = ctx->lvl[2].as<Fr>(), *d_rem = carry + S;
+    PM_HIP(ctx, ctx->pw.lvl[2].reserve(rec * N * sizeof(Fr)));
+    Fr *d_hall = ctx->pw.lvl[2].as<Fr>(), *d_rem = carry + S;
     if (!ctx_pinned(ctx)) {
         ctx->err = "pinned result slot allocation failed";
         return PM_ERR_HIP;
@@ -1010,12 +996,10 @@ int prove_phase3_sharded(pm_ctx *ctx, const uint64_t *x1_in, const uint64_t *x2_
     {
         StageTimer t(ctx, T_POLY);
         PM_HIP(ctx, hipMemcpyAsync(d_hall, ctx->seg_all.data(), rec * N * sizeof(Fr), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_seg_chain<P>, dim3(1), dim3(CHAIN_THREADS), 0, st, (const SegRefDev *)pk->d_all_segs, (unsigned)T, (const Fr *)d_hall, rec, SS,
-                           nc, x1, pow_u64<P>(x1, pk->max_seg), pk->max_seg, n, sigma, q, carry, d_rem);
-        PM_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL((k_seg_expand<P, SEG_LANES>), dim3((unsigned)S), dim3(SEG_LANES), 0, st, d_segs, sd, nc, u, wit_u, u2lo, u2hi, halo, x1,
-                           (const Fr *)laneP, (const Fr *)laneQ, (const Fr *)carry, qv);
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, k_seg_chain<P>, dim3(1), dim3(CHAIN_THREADS), 0, st, (const SegRefDev *)pk->d_all_segs, (unsigned)T, (const Fr *)d_hall, rec, SS,
+                       nc, x1, pow_u64<P>(x1, pk->max_seg), pk->max_seg, n, sigma, q, carry, d_rem);
+        PM_LAUNCH(ctx, (k_seg_expand<P, SEG_LANES>), dim3((unsigned)S), dim3(SEG_LANES), 0, st, d_segs, sd, nc, u, wit_u, u2lo, u2hi, halo, x1,
+                       (const Fr *)laneP, (const Fr *)laneQ, (const Fr *)carry, qv);
         PM_HIP(ctx, hipMemcpyAsync(h_rem, d_rem, sizeof(Fr), hipMemcpyDeviceToHost, st));      // lands before the MSM's final synchronisation
     }
     hp.mark("chain+expand enqueue");

@@ -164,17 +164,14 @@ int r1cs_check_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *
         {
             StageTimer t(ctx, T_WITNESS_MAP);
             if (words) {
-                hipLaunchKernelGGL(k_r1cs_mask<P>, dim3(nblk(nr), (unsigned)g), dim3(256), 0, st, A, B, Cm, gx, gw, m0, xs, ws, nr, words,
-                                   d.mask.as<unsigned long long>());
-                PM_HIP(ctx, hipGetLastError());
+                PM_LAUNCH(ctx, k_r1cs_mask<P>, dim3(nblk(nr), (unsigned)g), dim3(256), 0, st, A, B, Cm, gx, gw, m0, xs, ws, nr, words,
+                               d.mask.as<unsigned long long>());
             }
-            hipLaunchKernelGGL(k_r1cs_scan, dim3((unsigned)g), dim3(R1CS_SCAN_LANES), 0, st, d.mask.as<unsigned long long>(), words, listed,
-                               d.n_bad.as<uint64_t>(), d.rows.as<uint64_t>());
-            PM_HIP(ctx, hipGetLastError());
+            PM_LAUNCH(ctx, k_r1cs_scan, dim3((unsigned)g), dim3(R1CS_SCAN_LANES), 0, st, d.mask.as<unsigned long long>(), words, listed,
+                           d.n_bad.as<uint64_t>(), d.rows.as<uint64_t>());
             if (listed && abc) {
-                hipLaunchKernelGGL(k_r1cs_residuals<P>, dim3(nblk(listed), (unsigned)g), dim3(256), 0, st, A, B, Cm, gx, gw, m0, xs, ws,
-                                   d.rows.as<uint64_t>(), listed, d.abc.as<Fr>());
-                PM_HIP(ctx, hipGetLastError());
+                PM_LAUNCH(ctx, k_r1cs_residuals<P>, dim3(nblk(listed), (unsigned)g), dim3(256), 0, st, A, B, Cm, gx, gw, m0, xs, ws,
+                               d.rows.as<uint64_t>(), listed, d.abc.as<Fr>());
             }
         }
         PM_HIP(ctx, hipMemcpyAsync(n_bad + g0, d.n_bad.p, g * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -213,9 +210,9 @@ extern "C" int pm_r1cs_check_batch(pm_ctx *ctx, const pm_pk *pk, size_t count, c
     if (!n_bad || !x || (pk->mw && !w) || (max_rows && !rows)) return PM_ERR_INVALID_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return PM_ERR_HIP;
     try {
-        return pk->curve == PM_BLS12_381
-                   ? pm::r1cs_check_impl<pm::BlsCurve>(ctx, pk, count, x, w, on_device, solve, max_rows, n_bad, rows, abc)
-                   : pm::r1cs_check_impl<pm::BnCurve>(ctx, pk, count, x, w, on_device, solve, max_rows, n_bad, rows, abc);
+        return pm::with_curve(pk->curve, [&](auto cv) {
+            return pm::r1cs_check_impl<pm::type_of<decltype(cv)>>(ctx, pk, count, x, w, on_device, solve, max_rows, n_bad, rows, abc);
+        });
     } catch (const std::bad_alloc &) {
         ctx->err = "pm_r1cs_check: out of host memory";
         return PM_ERR_STATE;

@@ -34,8 +34,7 @@ int powers_fill(pm_ctx *ctx, Fp<typename C::FrP> *d_out, size_t count, const Fp<
     if (!count) return PM_OK;
     const unsigned L = 64;
     size_t lanes = (count + L - 1) / L;
-    hipLaunchKernelGGL(k_powers<P>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, ctx->stream, d_out, count, scale, x, L);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_powers<P>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, ctx->stream, d_out, count, scale, x, L);
     return PM_OK;
 }
 
@@ -137,9 +136,8 @@ int fixed_base_batch(pm_ctx *ctx, const Fp<typename C::FrP> *d_scalars, size_t l
     const Affine<C> *table = nullptr;
     PM_TRY(fixed_base_table<C>(ctx, &table));
     size_t lanes = (len + FB_BATCH - 1) / FB_BATCH;
-    hipLaunchKernelGGL(k_fixed_base<C>, dim3((unsigned)((lanes + 127) / 128)), dim3(128), 0, ctx->stream, d_scalars, len,
-                       table, d_out);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_fixed_base<C>, dim3((unsigned)((lanes + 127) / 128)), dim3(128), 0, ctx->stream, d_scalars, len,
+                   table, d_out);
     return PM_OK;
 }
 
@@ -163,9 +161,8 @@ int bases_generate_multiples(pm_ctx *ctx, size_t len, Affine<C> *d_out) {
     PM_HIP(ctx, ctx->scratch.reserve((len < CH ? len : CH) * sizeof(Fr)));
     for (size_t s = 0; s < len; s += CH) {
         size_t cnt = len - s < CH ? len - s : CH;
-        hipLaunchKernelGGL(k_iota_mont<P>, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream,
-                           ctx->scratch.as<Fr>(), cnt, (uint64_t)(s + 1));
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, k_iota_mont<P>, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream,
+                       ctx->scratch.as<Fr>(), cnt, (uint64_t)(s + 1));
         PM_TRY(fixed_base_batch<C>(ctx, ctx->scratch.as<Fr>(), cnt, d_out + s));
         PM_TRY(bases_convert<C>(ctx, d_out + s, cnt, true));
     }
@@ -191,9 +188,8 @@ __global__ void k_bases_convert(Affine<C> *pts, size_t len, int to_internal) {
 template <class C>
 int bases_convert(pm_ctx *ctx, Affine<C> *d_points, size_t len, bool to_internal) {
     if (!len) return PM_OK;
-    hipLaunchKernelGGL(k_bases_convert<C>, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, ctx->stream, d_points, len,
-                       to_internal ? 1 : 0);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_bases_convert<C>, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, ctx->stream, d_points, len,
+                   to_internal ? 1 : 0);
     return PM_OK;
 }
 
@@ -263,13 +259,11 @@ __global__ __launch_bounds__(128) void k_table_next(const TablePoint<C> *prev, T
 template <class C>
 int tables_build(pm_ctx *ctx, const Affine<C> *d_points, TablePoint<C> *d_table, size_t count, const MsmTables &t) {
     if (!t.c || !count) return PM_OK;
-    hipLaunchKernelGGL(k_table_window0<C>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, d_points, d_table, count);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_table_window0<C>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, d_points, d_table, count);
     size_t lanes = (count + TB_BATCH - 1) / TB_BATCH;
     for (unsigned w = 1; w < t.nwin; ++w) {   // T_w = 2^(width of window w-1) * T_{w-1}
-        hipLaunchKernelGGL(k_table_next<C>, dim3((unsigned)((lanes + 127) / 128)), dim3(128), 0, ctx->stream,
-                           d_table + (size_t)(w - 1) * t.stride, d_table + (size_t)w * t.stride, count, (unsigned)t.width[w - 1]);
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, k_table_next<C>, dim3((unsigned)((lanes + 127) / 128)), dim3(128), 0, ctx->stream,
+                       d_table + (size_t)(w - 1) * t.stride, d_table + (size_t)w * t.stride, count, (unsigned)t.width[w - 1]);
     }
     PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PM_OK;
@@ -289,8 +283,7 @@ __global__ void k_inf_flags(const Affine<C> *pts, size_t count, unsigned char *f
 template <class C>
 int infinity_flags(pm_ctx *ctx, const Affine<C> *d_points, size_t count, unsigned char *d_flags) {
     if (!count) return PM_OK;
-    hipLaunchKernelGGL(k_inf_flags<C>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, d_points, count, d_flags);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_inf_flags<C>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, d_points, count, d_flags);
     return PM_OK;
 }
 
@@ -482,19 +475,16 @@ int lcs_scalars(pm_ctx *ctx, const pm_pk *pk, const Fp<typename C::FrP> &x, cons
     PM_HIP(ctx, work.reserve(std::max((size_t)n * sizeof(Fr), 2 * acc_bytes)));
     Fr *L = lagrange.as<Fr>();
     const unsigned CH = 64;
-    hipLaunchKernelGGL(k_lagrange<P>, dim3(nblk((n + CH - 1) / CH)), dim3(256), 0, ctx->stream, L, work.as<Fr>(), (size_t)n, x, omega, kscale, CH);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_lagrange<P>, dim3(nblk((n + CH - 1) / CH)), dim3(256), 0, ctx->stream, L, work.as<Fr>(), (size_t)n, x, omega, kscale, CH);
     unsigned long long *uacc = work.as<unsigned long long>(), *wacc = uacc + (size_t)mcols * 8;
     PM_HIP(ctx, hipMemsetAsync(uacc, 0, 2 * acc_bytes, ctx->stream));       // `pre` is dead: the stream orders the two uses
     if (nr) {
         const CsrDev A{pk->d_rowptr[0], pk->d_col[0], pk->d_val[0]}, B{pk->d_rowptr[1], pk->d_col[1], pk->d_val[1]},
             Cm{pk->d_rowptr[2], pk->d_col[2], pk->d_val[2]};
-        hipLaunchKernelGGL(k_lcs_rows<P>, dim3(nblk(nr)), dim3(256), 0, ctx->stream, A, B, Cm, (const Fr *)L, m0, nr, uacc, wacc);
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, k_lcs_rows<P>, dim3(nblk(nr)), dim3(256), 0, ctx->stream, A, B, Cm, (const Fr *)L, m0, nr, uacc, wacc);
     }
-    hipLaunchKernelGGL(k_lcs_finish<P>, dim3(nblk(Lz)), dim3(256), 0, ctx->stream, (const unsigned long long *)uacc, (const unsigned long long *)wacc,
-                       (const Fr *)L, m0, mw, nr, y_gamma, y_to_minus_alpha, d_lcs);
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_lcs_finish<P>, dim3(nblk(Lz)), dim3(256), 0, ctx->stream, (const unsigned long long *)uacc, (const unsigned long long *)wacc,
+                   (const Fr *)L, m0, mw, nr, y_gamma, y_to_minus_alpha, d_lcs);
     return PM_OK;
 }
 

@@ -155,9 +155,8 @@ int solve_load(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t g
     // rows of x (m0) and of w (mw) interleave into rows of x || w; the caller's arrays are only read
     PM_HIP(ctx, hipMemcpy2DAsync(d_xw, ncols * sizeof(Fr), x + 4 * m0 * g0, m0 * sizeof(Fr), m0 * sizeof(Fr), g, kind, st));
     if (mw) PM_HIP(ctx, hipMemcpy2DAsync(d_xw + m0, ncols * sizeof(Fr), w + 4 * mw * g0, mw * sizeof(Fr), mw * sizeof(Fr), g, kind, st));
-    hipLaunchKernelGGL(k_solve_pattern<P>, dim3(nblk(ncols), (unsigned)g), dim3(256), 0, st, d_xw, ncols, (uint64_t)g0, ctx->sv.pattern.as<uint8_t>(),
-                       ctx->sv.mismatch.as<unsigned long long>());
-    PM_HIP(ctx, hipGetLastError());
+    PM_LAUNCH(ctx, k_solve_pattern<P>, dim3(nblk(ncols), (unsigned)g), dim3(256), 0, st, d_xw, ncols, (uint64_t)g0, ctx->sv.pattern.as<uint8_t>(),
+                   ctx->sv.mismatch.as<unsigned long long>());
     return PM_OK;
 }
 
@@ -215,9 +214,8 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
         }
         PM_HIP(ctx, sv.steps.reserve(n_steps * sizeof(SolveStepDev<P>)));
         PM_HIP(ctx, hipMemcpyAsync(sv.steps.p, host.data(), n_steps * sizeof(SolveStepDev<P>), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_solve_inv<P>, dim3(nblk(n_steps)), dim3(256), 0, st, csr_dev(pk, 0), csr_dev(pk, 1), csr_dev(pk, 2), sv.steps.as<SolveStepDev<P>>(),
-                           (uint64_t)n_steps);
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, k_solve_inv<P>, dim3(nblk(n_steps)), dim3(256), 0, st, csr_dev(pk, 0), csr_dev(pk, 1), csr_dev(pk, 2), sv.steps.as<SolveStepDev<P>>(),
+                       (uint64_t)n_steps);
         PM_HIP(ctx, hipStreamSynchronize(st));   // `host` goes out of scope
     }
     sv.plan_pattern.swap(pattern);

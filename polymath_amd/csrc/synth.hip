@@ -89,7 +89,7 @@ static int synth_impl(uint64_t nr, uint64_t seed, uint64_t *a_val, uint32_t *a_c
 extern "C" int pm_synth_r1cs(int curve, uint64_t nr, uint64_t seed, uint64_t *a_val, uint32_t *a_col, uint64_t *b_val, uint32_t *b_col,
                              uint64_t *c_val, uint32_t *c_col, uint64_t *instance, uint64_t *witness) {
     if (!a_val || !a_col || !b_val || !b_col || !c_val || !c_col || !instance || !witness) return PM_ERR_INVALID_ARG;
-    if (curve == PM_BLS12_381) return synth_impl<pm::BlsFrP>(nr, seed, a_val, a_col, b_val, b_col, c_val, c_col, instance, witness);
-    if (curve == PM_BN254) return synth_impl<pm::BnFrP>(nr, seed, a_val, a_col, b_val, b_col, c_val, c_col, instance, witness);
-    return PM_ERR_INVALID_ARG;
+    return pm::with_curve(curve, [&](auto cv) {
+        return synth_impl<typename pm::type_of<decltype(cv)>::FrP>(nr, seed, a_val, a_col, b_val, b_col, c_val, c_col, instance, witness);
+    });
 }

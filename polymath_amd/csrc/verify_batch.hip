@@ -203,17 +203,15 @@ int verify_batch_impl(pm_ctx *ctx, int transcript, const uint8_t *vk_bytes, size
     VerifyTerm<C> *tree = d.tree.as<VerifyTerm<C>>();
     {
         StageTimer t(ctx, T_NTT);
-        hipLaunchKernelGGL(k_verify_terms<C>, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, ctx->stream, d.pts.as<Affine<C>>(),
-                           d.status.as<uint8_t>(), d.scalars.as<VerifyScalars>(), count, padded, tree);
-        PM_HIP(ctx, hipGetLastError());
+        PM_LAUNCH(ctx, k_verify_terms<C>, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, ctx->stream, d.pts.as<Affine<C>>(),
+                       d.status.as<uint8_t>(), d.scalars.as<VerifyScalars>(), count, padded, tree);
     }
     {
         StageTimer t(ctx, T_POLY);
         for (unsigned l = 1; l <= depth; ++l) {
             const size_t nodes = padded >> l;
-            hipLaunchKernelGGL(k_verify_tree<C>, dim3((unsigned)((3 * nodes + 255) / 256)), dim3(256), 0, ctx->stream,
-                               tree + verify_level_offset(padded, l - 1), tree + verify_level_offset(padded, l), nodes);
-            PM_HIP(ctx, hipGetLastError());
+            PM_LAUNCH(ctx, k_verify_tree<C>, dim3((unsigned)((3 * nodes + 255) / 256)), dim3(256), 0, ctx->stream,
+                           tree + verify_level_offset(padded, l - 1), tree + verify_level_offset(padded, l), nodes);
         }
     }
     t_all.stop();
@@ -339,17 +337,6 @@ int verify_batch_impl(pm_ctx *ctx, int transcript, const uint8_t *vk_bytes, size
     return PM_OK;
 }
 
-template <class C>
-int verify_batch_curve(pm_ctx *ctx, int transcript, const uint8_t *vk, size_t vk_len, const uint64_t *in, size_t n_in, const uint8_t *proofs, size_t count,
-                       const uint8_t *seed, int pairing, int challenges, uint8_t *verdicts, int *all, size_t *nc) {
-    switch (transcript) {
-        case PM_TRANSCRIPT_MERLIN: return verify_batch_impl<C, pmhost::MerlinFieldTranscript<C>>(ctx, transcript, vk, vk_len, in, n_in, proofs, count, seed, pairing, challenges, verdicts, all, nc);
-        case PM_TRANSCRIPT_KECCAK256: return verify_batch_impl<C, pmhost::Keccak256Transcript<C>>(ctx, transcript, vk, vk_len, in, n_in, proofs, count, seed, pairing, challenges, verdicts, all, nc);
-        case PM_TRANSCRIPT_BLAKE3: return verify_batch_impl<C, pmhost::Blake3Transcript<C>>(ctx, transcript, vk, vk_len, in, n_in, proofs, count, seed, pairing, challenges, verdicts, all, nc);
-        default: return PM_ERR_INVALID_ARG;
-    }
-}
-
 }  // namespace
 
 extern "C" int pm_verify_batch2(pm_ctx *ctx, int curve, int transcript, const uint8_t *vk_bytes, size_t vk_len, const uint64_t *public_inputs, size_t n_inputs,
@@ -361,7 +348,7 @@ extern "C" int pm_verify_batch2(pm_ctx *ctx, int curve, int transcript, const ui
     if (pairing != PM_VERIFY_PAIRING_HOST && pairing != PM_VERIFY_PAIRING_DEVICE) return PM_ERR_INVALID_ARG;
     if (!ctx || !vk_bytes || !all_accepted || (count && (!proofs || (n_inputs && !public_inputs)))) return PM_ERR_INVALID_ARG;
     if (curve != PM_BLS12_381 && curve != PM_BN254) return PM_ERR_INVALID_ARG;
-    if (transcript < PM_TRANSCRIPT_MERLIN || transcript > PM_TRANSCRIPT_BLAKE3) return PM_ERR_INVALID_ARG;
+    if (!pmhost::transcript_ok(transcript)) return PM_ERR_INVALID_ARG;
     if (proof_len != (curve == PM_BLS12_381 ? 176u : 128u) || count > VERIFY_MAX_COUNT) return PM_ERR_INVALID_ARG;
     *all_accepted = 0;
     if (n_checks) *n_checks = 0;
@@ -375,9 +362,13 @@ extern "C" int pm_verify_batch2(pm_ctx *ctx, int curve, int transcript, const ui
             return PM_OK;
         }
         if (hipSetDevice(ctx->device) != hipSuccess) return PM_ERR_HIP;
-        return curve == PM_BLS12_381
-                   ? verify_batch_curve<BlsCurve>(ctx, transcript, vk_bytes, vk_len, public_inputs, n_inputs, proofs, count, seed32, pairing, challenges, verdicts, all_accepted, n_checks)
-                   : verify_batch_curve<BnCurve>(ctx, transcript, vk_bytes, vk_len, public_inputs, n_inputs, proofs, count, seed32, pairing, challenges, verdicts, all_accepted, n_checks);
+        return with_curve(curve, [&](auto cv) {
+            typedef type_of<decltype(cv)> C;
+            return pmhost::with_transcript<C>(transcript, [&](auto t) {
+                return verify_batch_impl<C, type_of<decltype(t)>>(ctx, transcript, vk_bytes, vk_len, public_inputs, n_inputs, proofs, count, seed32, pairing,
+                                                                  challenges, verdicts, all_accepted, n_checks);
+            });
+        });
     } catch (const pmhost::WireError &) {               // malformed vk bytes
         return PM_ERR_INVALID_ARG;
     } catch (const std::bad_alloc &) {

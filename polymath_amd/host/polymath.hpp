@@ -121,6 +121,21 @@ struct HashTranscript {          // transcript/keccak256.rs:12-43, blake3.rs:12-
 template <class C> using Keccak256Transcript = HashTranscript<C, keccak256>;
 template <class C> using Blake3Transcript = HashTranscript<C, blake3>;
 
+// A runtime pm_transcript id as one of the three types: f(tag) with `typename decltype(tag)::type` the transcript over curve C
+// (csrc/internal.h: pm::type_of); any other id is PM_ERR_INVALID_ARG.
+template <class T>
+struct TypeTag { typedef T type; };
+inline bool transcript_ok(int t) { return t == PM_TRANSCRIPT_MERLIN || t == PM_TRANSCRIPT_KECCAK256 || t == PM_TRANSCRIPT_BLAKE3; }
+template <class C, class F>
+inline int with_transcript(int transcript, F f) {
+    switch (transcript) {
+        case PM_TRANSCRIPT_MERLIN: return f(TypeTag<MerlinFieldTranscript<C>>{});
+        case PM_TRANSCRIPT_KECCAK256: return f(TypeTag<Keccak256Transcript<C>>{});
+        case PM_TRANSCRIPT_BLAKE3: return f(TypeTag<Blake3Transcript<C>>{});
+        default: return PM_ERR_INVALID_ARG;
+    }
+}
+
 // ------------------------------------------------------------------------ constraint system
 struct Variable { int kind; size_t index; };   // kind 0 = One, 1 = instance, 2 = witness
 static const Variable ONE{0, 0};

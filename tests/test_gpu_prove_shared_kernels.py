@@ -9,7 +9,11 @@ with the CPU oracle:
 The rows of a batch share the circuit and the assignment (CI.random_r1cs gives one per circuit) and differ in r_a, so every
 per-proof value -- r_a, x1, x2, the numerator's constants, the level multipliers -- differs from row to row.  A batch of one forwards
 to the single prover.  One batch at n = 8 has a violated constraint in its middle row: that row alone is refused, with the single
-prover's status."""
+prover's status.
+
+Phase 1 between the uploads and the MSMs is one enqueue list for both provers (csrc/prove.hip: phase1_enqueue_u / phase1_enqueue_rest).
+With msm_overlap = 0 the single prover takes the list's other branch -- no k_sc_a launch, k_phase1_scalars writes the [a]_1 scalars --
+which no test above reaches; the batch prover's stays as it is.  Both must still give the oracle's bytes."""
 import pytest
 
 from oracle import driver as DR
@@ -40,6 +44,16 @@ def _key(gpu_ctx, oracle, curve, m0, nr, n):
     return _KEYS[k]
 
 
+def _oracle_bytes(s, oracle, curve):
+    """the oracle's three proofs of a key (one per r_a), computed once"""
+    if "want" not in s:
+        opk, c = s["opk"], s["c"]
+        omega = oracle.fr_from_mont_limbs(curve, opk.omega_limbs)[0]
+        s["want"] = [SE.ser_proof(c, DR.prove(opk, opk.n, opk.sigma, omega, s["inst"], s["wit"], r_a, T.make_transcripts(c)["merlin"]))
+                     for r_a in s["r_a"]]
+    return s["want"]
+
+
 @pytest.mark.parametrize("curve,m0,nr,n", [
     ("bls12_381", 1, 1, 4), ("bn254", 1, 1, 4),
     ("bls12_381", 1, 3, 8), ("bn254", 1, 3, 8),
@@ -47,12 +61,10 @@ def _key(gpu_ctx, oracle, curve, m0, nr, n):
 ])
 def test_small_shapes_bytes_equal_single_prover_and_oracle(gpu_ctx, oracle, curve, m0, nr, n):
     s = _key(gpu_ctx, oracle, curve, m0, nr, n)
-    pm, pk, opk, c = s["pm"], s["pk"], s["opk"], s["c"]
+    pm, pk = s["pm"], s["pk"]
     assert 8 * (n + 3) + 2 * n - 1 == {4: 63, 8: 103, 32: 343}[n]          # the numerator's length: <= 64 only at n = 4
-    omega = oracle.fr_from_mont_limbs(curve, opk.omega_limbs)[0]
     single = [pm.prove_native(pk, s["xl"], s["wl"], r_a) for r_a in s["r_a"]]
-    want = [SE.ser_proof(c, DR.prove(opk, opk.n, opk.sigma, omega, s["inst"], s["wit"], r_a, T.make_transcripts(c)["merlin"]))
-            for r_a in s["r_a"]]
+    want = _oracle_bytes(s, oracle, curve)
     assert len(set(single)) == 3
     for count in (1, 3):
         proofs, status = pm.prove_batch(pk, [(s["xl"], s["wl"])] * count, s["r_a"][:count])
@@ -60,6 +72,25 @@ def test_small_shapes_bytes_equal_single_prover_and_oracle(gpu_ctx, oracle, curv
         for i in range(count):
             assert proofs[i] == single[i], (count, i, "single prover")
             assert proofs[i] == want[i], (count, i, "oracle")
+
+
+@pytest.mark.parametrize("curve,m0,nr,n", [("bls12_381", 1, 1, 4), ("bn254", 1, 1, 4), ("bls12_381", 9, 7, 32)])
+def test_msm_overlap_off_bytes_equal_oracle(gpu_ctx, oracle, curve, m0, nr, n):
+    s = _key(gpu_ctx, oracle, curve, m0, nr, n)
+    pm, pk = s["pm"], s["pk"]
+    want = _oracle_bytes(s, oracle, curve)
+    assert pm.ctx is gpu_ctx
+    overlap_was = gpu_ctx.get_option("msm_overlap")
+    gpu_ctx.set_option("msm_overlap", 0)
+    try:
+        single = [pm.prove_native(pk, s["xl"], s["wl"], r_a) for r_a in s["r_a"]]
+        proofs, status = pm.prove_batch(pk, [(s["xl"], s["wl"])] * 3, s["r_a"])
+    finally:
+        gpu_ctx.set_option("msm_overlap", overlap_was)
+    assert status == [PM_OK] * 3, status
+    for i in range(3):
+        assert single[i] == want[i], (i, "single prover")
+        assert proofs[i] == want[i], (i, "batch prover")
 
 
 def test_violated_row_in_the_middle_of_a_batch(gpu_ctx, oracle):
