@@ -146,11 +146,7 @@ int prove_phase1_impl(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const uin
     const uint64_t n = d.n, m0 = d.m0, mw = d.mw;
     if (pk->log_n + 1 > (unsigned)C::TWO_ADICITY) return PM_ERR_DOMAIN_TOO_LARGE;  // prover.rs:317
     hipStream_t st = ctx->stream;
-    if (!ctx->keep_timings) timing_reset(ctx);
-    ctx->pk = pk;
-    ctx->phase = 0;
-    TimingGuard timing_guard{ctx};
-    StageTimer t_phase(ctx, T_PHASE);
+    PhaseTimers timers(ctx, pk);
     ProveWs &ws = ctx->pw;
     PM_HIP(ctx, ws.xw.reserve((m0 + mw) * sizeof(Fr)));
     for (DevBuf *b : {&ws.ue, &ws.we, &ws.u, &ws.w, &ws.wit_u, &ws.tmp}) PM_HIP(ctx, b->reserve(n * sizeof(Fr)));
@@ -210,10 +206,8 @@ int prove_phase1_impl(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const uin
     // The status flags ride behind the MSMs (round 4): they land in pinned staging and are read after the MSM's own final
     // synchronisation, so the host does not wait here and the sort's fifteen launches are enqueued while the transforms still run.
     // An unsatisfied witness (prover.rs:107-108) is reported after the MSMs it no longer stops -- the rare path pays, not the proof.
-    if (!ctx_pinned(ctx)) { ctx->err = "pinned staging allocation failed"; return PM_ERR_HIP; }
-    volatile unsigned *hflags_p = pinned_slot<volatile unsigned>(ctx, PINNED_FLAGS);
-    *hflags_p = 0;
-    PM_HIP(ctx, hipMemcpyAsync((void *)hflags_p, flags, 4, hipMemcpyDeviceToHost, st));
+    volatile unsigned *hflags_p = nullptr;
+    PM_TRY(stage_flags(ctx, flags, &hflags_p));
     if (a_early) {
         const int st_c = msm_shard<C>(ctx, pk, 1, sc_c, c_xy, c_inf);
         helper.join();
@@ -235,8 +229,7 @@ int prove_phase1_impl(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const uin
         if (const int s_flags = phase1_flag_status(*hflags_p)) return s_flags;
         PM_TRY(s_c);
     }
-    t_phase.stop();
-    timing_flush(ctx);
+    timers.done();
     ctx->phase = 1;
     return PM_OK;
 }
@@ -272,9 +265,7 @@ int prove_phase3_impl(pm_ctx *ctx, const uint64_t *x1_in, const uint64_t *x2_in,
     if (ctx->phase < 1 || !ctx->pk) return PM_ERR_STATE;
     const pm_pk *pk = ctx->pk;
     hipStream_t st = ctx->stream;
-    if (!ctx->keep_timings) timing_reset(ctx);
-    TimingGuard timing_guard{ctx};
-    StageTimer t_phase(ctx, T_PHASE);
+    PhaseTimers timers(ctx);
     const ProofShape d = proof_shape(pk);
     const uint64_t *cnt = d.cnt;
     const int levels = d.levels;
@@ -320,16 +311,13 @@ int prove_phase3_impl(pm_ctx *ctx, const uint64_t *x1_in, const uint64_t *x2_in,
         }
     }
     // rem == 0 (prover.rs:221) is read after the MSM's final synchronisation: no host wait between the division and the sort
-    if (!ctx_pinned(ctx)) { ctx->err = "pinned staging allocation failed"; return PM_ERR_HIP; }
-    volatile unsigned *hflags_p = pinned_slot<volatile unsigned>(ctx, PINNED_FLAGS);
-    *hflags_p = 0;
-    PM_HIP(ctx, hipMemcpyAsync((void *)hflags_p, flags, 4, hipMemcpyDeviceToHost, st));
+    volatile unsigned *hflags_p = nullptr;
+    PM_TRY(stage_flags(ctx, flags, &hflags_p));
     const int st_d = msm_shard<C>(ctx, pk, 2, q, d_xy, d_inf);   // [d]_1 = M8, prover.rs:229
     PM_HIP(ctx, hipStreamSynchronize(st));
     if (const int s_flags = phase3_flag_status(*hflags_p)) return s_flags;
     PM_TRY(st_d);
-    t_phase.stop();
-    timing_flush(ctx);
+    timers.done();
     ctx->phase = 3;
     return PM_OK;
 }

@@ -123,6 +123,53 @@ static inline void store_affine_host(const Affine<C> &a, int inf, uint64_t *xy, 
 
 static inline unsigned nblk(uint64_t n, unsigned b = 256) { return (unsigned)((n + b - 1) / b); }
 
+// omega^e from the half-size table tw[j] = omega^j, j < n/2 (omega^(n/2) = -1)
+template <class P>
+__device__ __forceinline__ Fp<P> tw_pow(const Fp<P> *tw, uint64_t n, uint64_t e) {
+    e &= n - 1;
+    const uint64_t half = n >> 1;
+    return e < half ? tw[e] : neg<P>(tw[e - half]);
+}
+
+// The sum of one value per lane over a workgroup of THREADS lanes, by a tree in `sh` (THREADS elements of LDS): lane 0 gets the sum, the
+// other lanes zero.  The tree's last barrier is the trailing one -- only lane 0 reads sh[0] after it and only lane 0 writes it next, so
+// `sh` can take the next sum at once.
+template <class P, unsigned THREADS>
+__device__ __forceinline__ Fp<P> block_sum(Fp<P> *sh, const Fp<P> &v) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (unsigned off = THREADS / 2; off > 0; off >>= 1) {
+        if (threadIdx.x < off) sh[threadIdx.x] = add<P>(sh[threadIdx.x], sh[threadIdx.x + off]);
+        __syncthreads();
+    }
+    return threadIdx.x == 0 ? sh[0] : Fp<P>::zero();
+}
+
+// The opening of a prover phase: the context's stage times start afresh (unless the caller keeps them) and T_PHASE brackets the phase;
+// `start` = the key of a proof that begins here (phase 1).  Every return path stops the phase timer and then reads the timers.
+struct PhaseTimers {
+    TimingGuard guard;
+    StageTimer t_phase;
+    static pm_ctx *open(pm_ctx *ctx, const pm_pk *start) {
+        if (!ctx->keep_timings) timing_reset(ctx);
+        if (start) { ctx->pk = start; ctx->phase = 0; }
+        return ctx;
+    }
+    explicit PhaseTimers(pm_ctx *ctx, const pm_pk *start = nullptr) : guard{open(ctx, start)}, t_phase(ctx, T_PHASE) {}
+    void done() { t_phase.stop(); timing_flush(guard.ctx); }   // on success: the times are read before the phase returns
+};
+
+// The flag word of a proof rides behind the phase's MSMs: its copy to the host is enqueued here and read after the MSM's own final
+// synchronisation, so the host does not wait between the kernels and the sort.  It lands in the pinned slot PINNED_FLAGS (a pageable
+// destination would make the copy wait for the stream) unless the caller names another destination; zeroed first.
+static inline int stage_flags(pm_ctx *ctx, const unsigned *d_flags, volatile unsigned **h_flags, unsigned *dst = nullptr) {
+    if (!dst && !ctx_pinned(ctx)) { ctx->err = "pinned staging allocation failed"; return PM_ERR_HIP; }
+    *h_flags = dst ? dst : pinned_slot<volatile unsigned>(ctx, PINNED_FLAGS);
+    **h_flags = 0;
+    PM_HIP(ctx, hipMemcpyAsync((void *)*h_flags, d_flags, 4, hipMemcpyDeviceToHost, ctx->stream));
+    return PM_OK;
+}
+
 
 // the constants of the numerator (prover.rs:145-197) from the challenges and r_a
 template <class P>

@@ -216,13 +216,8 @@ __device__ __forceinline__ void horner_partial(const Fp<P> *u, uint64_t n, const
         for (uint64_t k = hi; k-- > lo;) acc = add<P>(mul<P>(acc, x1), u[k]);
         acc = mul<P>(acc, pow_u64<P>(x1, lo));
     }
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (unsigned off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) sh[threadIdx.x] = add<P>(sh[threadIdx.x], sh[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partials[blockIdx.x] = sh[0];
+    const Fp<P> sum = block_sum<P, 256>(sh, acc);
+    if (threadIdx.x == 0) partials[blockIdx.x] = sum;
 }
 template <class P>
 __global__ __launch_bounds__(256) void k_horner_partial(const Fp<P> *u, uint64_t n, Fp<P> x1, unsigned L, Fp<P> *partials) {
@@ -241,13 +236,8 @@ __global__ __launch_bounds__(256) void k_sum_small(const Fp<P> *in, unsigned cou
     in += (uint64_t)blockIdx.x * count;
     Fp<P> acc = Fp<P>::zero();
     for (unsigned i = threadIdx.x; i < count; i += 256) acc = add<P>(acc, in[i]);
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (unsigned off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) sh[threadIdx.x] = add<P>(sh[threadIdx.x], sh[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
+    const Fp<P> sum = block_sum<P, 256>(sh, acc);
+    if (threadIdx.x == 0) out[blockIdx.x] = sum;
 }
 
 // ------------------------------------------------------------- division (phase 3)

@@ -8,11 +8,10 @@
 //   MSMs              the pairs follow the coefficients: no scalar moves between GPUs (prover.rs:118-123, 229)     row 1
 // Same three phases, same outputs (partial points) as prove.hip; every rank returns the same status because the
 // check flags are exchanged before any rank decides.
-#include <thread>
-
 #include "comm.h"
 #include "internal.h"
 #include "prove_common.cuh"
+#include "prove_kernels.cuh"
 
 namespace pm {
 
@@ -29,25 +28,6 @@ static int comm_alive(pm_ctx *ctx) {
     if (!ctx->comm->failed) return PM_OK;
     ctx->err = "communicator failed: " + ctx->comm->error();
     return PM_ERR_COMM;
-}
-
-// omega^e from the half-size table tw[j] = omega^j, j < n/2 (omega^(n/2) = -1)
-template <class P>
-__device__ __forceinline__ Fp<P> tw_pow(const Fp<P> *tw, uint64_t n, uint64_t e) {
-    e &= n - 1;
-    const uint64_t half = n >> 1;
-    return e < half ? tw[e] : neg<P>(tw[e - half]);
-}
-
-template <class P>
-__global__ void k_check_sap_L(const Fp<P> *ue, const Fp<P> *we, uint64_t count, unsigned *flags) {   // (Uz)^2 == Wz, prover.rs:108
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count && !sqr<P>(ue[i]).eq(we[i])) atomicOr(flags, 1u);
-}
-template <class P>
-__global__ void k_square_L(Fp<P> *a, uint64_t count) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) a[i] = sqr<P>(a[i]);
 }
 
 // ------------------------------------------------------------------------------------------------ witness map
@@ -257,8 +237,7 @@ template <class C>
 static int dist_intt(pm_ctx *ctx, pm_ctx *e, const pm_pk *pk, const Layout &L, Fp<typename C::FrP> *x, Fp<typename C::FrP> *tmp, Fp<typename C::FrP> *y) {
     typedef typename C::FrP P;
     typedef Fp<P> Fr;
-    unsigned log_m = 0;
-    while (((uint64_t)1 << log_m) < L.m) ++log_m;
+    const unsigned log_m = (unsigned)__builtin_ctzll(L.m);                      // m = n / N: a power of two
     auto on_e = [&](int st) { if (st != PM_OK && e != ctx) ctx->err = e->err; return st; };
     PM_TRY(on_e(ntt_run<C>(e, x, log_m, true)));                                // N local transforms (this rank's), scaled by 1/m
     StageTimer t(e, T_NTT);
@@ -271,18 +250,13 @@ static int dist_intt(pm_ctx *ctx, pm_ctx *e, const pm_pk *pk, const Layout &L, F
     PM_HIP(ctx, hipGetLastError());
     return PM_OK;
 }
-template <class C>
-static int dist_intt(pm_ctx *ctx, const pm_pk *pk, const Layout &L, Fp<typename C::FrP> *x, Fp<typename C::FrP> *tmp, Fp<typename C::FrP> *y) {
-    return dist_intt<C>(ctx, ctx, pk, L, x, tmp, y);
-}
 
 // coefficients (blocked, `y`, kept) -> evaluations (cyclic, `x`); `tmp`: m elements of scratch
 template <class C>
 static int dist_ntt(pm_ctx *ctx, const pm_pk *pk, const Layout &L, const Fp<typename C::FrP> *y, Fp<typename C::FrP> *tmp, Fp<typename C::FrP> *x) {
     typedef typename C::FrP P;
     typedef Fp<P> Fr;
-    unsigned log_m = 0;
-    while (((uint64_t)1 << log_m) < L.m) ++log_m;
+    const unsigned log_m = (unsigned)__builtin_ctzll(L.m);
     {
         StageTimer t(ctx, T_NTT);
         const Fr *rf = nullptr, *ri = nullptr, *tw = nullptr;
@@ -369,13 +343,8 @@ __global__ __launch_bounds__(256) void k_horner_partial_L(const Fp<P> *u, Layout
         for (uint64_t k = lo + Lh; k-- > lo;) acc = add<P>(mul<P>(acc, x1), u[k]);
         acc = mul<P>(acc, pow_u64<P>(x1, pmlayout::coeff_global(L, lo)));
     }
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (unsigned off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) sh[threadIdx.x] = add<P>(sh[threadIdx.x], sh[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partials[blockIdx.x] = sh[0];
+    const Fp<P> sum = block_sum<P, 256>(sh, acc);
+    if (threadIdx.x == 0) partials[blockIdx.x] = sum;
 }
 // out[k1] = the last coefficient of this rank's block k1: the halo the next block's owner needs in the division (phase 3)
 template <class P>
@@ -383,71 +352,21 @@ __global__ void k_halo_pack(const Fp<P> *u, Layout L, Fp<P> *out) {
     const unsigned k1 = blockIdx.x * blockDim.x + threadIdx.x;
     if (k1 < L.N) out[k1] = u[(uint64_t)k1 * L.B + L.B - 1];
 }
-// out[0] = sum of `count` partials
-template <class P>
-__global__ __launch_bounds__(256) void k_phase2_pack(const Fp<P> *partials, unsigned count, Fp<P> *out) {
-    __shared__ Fp<P> sh[256];
-    Fp<P> acc = Fp<P>::zero();
-    for (unsigned i = threadIdx.x; i < count; i += 256) acc = add<P>(acc, partials[i]);
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (unsigned off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) sh[threadIdx.x] = add<P>(sh[threadIdx.x], sh[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = sh[0];
-}
 
 // ----------------------------------------------------------------------------------- division scan (phase 3)
-struct SegData {   // what numerator_seg reads
-    uint64_t n, sigma;
-};
-
-// numerator coefficient at index a + j of segment g (numerator_at of prove.hip on this rank's local arrays)
-template <class P>
-__device__ __forceinline__ Fp<P> numerator_seg(const Segment &g, uint64_t j, const SegData &sd, const NumConsts<P> &nc, const Fp<P> *u,
-                                               const Fp<P> *wit_u, const Fp<P> *u2lo, const Fp<P> *u2hi, const Fp<P> *halo) {
-    switch (g.kind) {
-        case pmlayout::SEG_WITU: return mul<P>(nc.x2, wit_u[g.loc0 + j]);
-        case pmlayout::SEG_U2LO: return mul<P>(nc.x2, u2lo[g.loc0 + j]);
-        case pmlayout::SEG_U2HI: return mul<P>(nc.x2, u2hi[g.loc0 + j]);
-        case pmlayout::SEG_U: {
-            const uint64_t i = g.a + j - 5 * sd.sigma;
-            Fp<P> t = Fp<P>::zero();
-            if (i < sd.n) {
-                const Fp<P> ui = u[g.loc0 + j];
-                t = add<P>(ui, mul<P>(nc.two_x2_r0, ui));
-            }
-            if (i > 0) {
-                const Fp<P> prev = (j == 0 && g.halo) ? halo[g.halo - 1] : u[g.loc0 + j - 1];
-                t = add<P>(t, mul<P>(nc.two_x2_r1, prev));
-            } else {
-                t = add<P>(t, nc.minus_const);
-            }
-            return t;
-        }
-        default: {
-            const uint64_t k = g.a + j;
-            if (k == 0) return nc.x2r0;
-            if (k == 1) return nc.x2r1;
-            if (k >= 2 * sd.sigma && k < 2 * sd.sigma + 3) return nc.b2[k - 2 * sd.sigma];
-            return Fp<P>::zero();
-        }
-    }
-}
-
 constexpr unsigned SEG_THREADS_MAX = 1024;   // lane values are stored with this stride whatever the workgroup size
 
 // The division scan in two halves that straddle the second challenge.  The numerator's coefficients depend on x2 (and on a, c at
 // x1, which come after it) only through a handful of constants: on a data segment N_k = c1 D1_k + c2 D2_k (+ one constant at the
 // first index of the u region), with D1, D2 this rank's coefficient arrays -- wit_u, (u^2)_lo, (u^2)_hi, or (u_i, u_{i-1}).  So
 // the Horner sums of the DATA at x1 can be taken as soon as x1 is known (phase 2) and travel with the u(x1) partials; phase 3 then
-// needs no exchange before its MSM: every rank derives all segment values V_s = c1 P_s + c2 Q_s + constants on the host.
+// needs no exchange before its MSM: every rank derives all segment values V_s = c1 P_s + c2 Q_s + constants on the device.
 //
-// k_seg_base (phase 2): one workgroup per segment; lane t owns the `span` consecutive indices from a + t span:
-//   laneP[t] = sum_j D1_{lo + j} x1^j,  laneQ[t] likewise for D2 (u region only);  P_s = sum_t laneP[t] x1^(t span), Q_s likewise.
+// The numerator (numerator_at's table, prove_common.cuh) is stated for the scan by three functions, and nowhere else in this file:
+// seg_data (D1, D2 at one index of a segment), seg_combine (c1 D1 + c2 D2 for the segment's kind -- linear, so it serves one index,
+// a lane's Horner sums and a segment's alike) and seg_consts (the constants inside an index range, as a polynomial in x1).
 template <class P>
-__device__ __forceinline__ void seg_data(const Segment &g, uint64_t j, const SegData &sd, const Fp<P> *u, const Fp<P> *wit_u, const Fp<P> *u2lo,
+__device__ __forceinline__ void seg_data(const Segment &g, uint64_t j, const NumParams &np, const Fp<P> *u, const Fp<P> *wit_u, const Fp<P> *u2lo,
                                          const Fp<P> *u2hi, const Fp<P> *halo, Fp<P> &d1, Fp<P> &d2) {
     d1 = Fp<P>::zero();
     d2 = Fp<P>::zero();
@@ -456,17 +375,51 @@ __device__ __forceinline__ void seg_data(const Segment &g, uint64_t j, const Seg
         case pmlayout::SEG_U2LO: d1 = u2lo[g.loc0 + j]; break;
         case pmlayout::SEG_U2HI: d1 = u2hi[g.loc0 + j]; break;
         case pmlayout::SEG_U: {
-            const uint64_t i = g.a + j - 5 * sd.sigma;
-            if (i < sd.n) d1 = u[g.loc0 + j];
+            const uint64_t i = g.a + j - 5 * np.sigma;
+            if (i < np.n) d1 = u[g.loc0 + j];
             if (i > 0) d2 = (j == 0 && g.halo) ? halo[g.halo - 1] : u[g.loc0 + j - 1];
             break;
         }
         default: break;
     }
 }
+template <class P>
+__device__ __forceinline__ Fp<P> seg_combine(uint32_t kind, const Fp<P> &d1, const Fp<P> &d2, const NumConsts<P> &nc) {
+    switch (kind) {
+        case pmlayout::SEG_WITU: case pmlayout::SEG_U2LO: case pmlayout::SEG_U2HI: return mul<P>(nc.x2, d1);
+        case pmlayout::SEG_U: return add<P>(add<P>(d1, mul<P>(nc.two_x2_r0, d1)), mul<P>(nc.two_x2_r1, d2));
+        default: return Fp<P>::zero();       // fillers hold constants only
+    }
+}
+// sum of const_i x1^(pos_i - a) over the constants with pos_i in [a, b): all but a handful of ranges in the whole proof have none
+template <class P>
+__device__ __forceinline__ Fp<P> seg_consts(uint64_t a, uint64_t b, const Fp<P> &x1, const NumConsts<P> &nc, uint64_t sigma) {
+    const uint64_t s2 = 2 * sigma, s5 = 5 * sigma;
+    Fp<P> v = Fp<P>::zero();
+    if (!(a < 2 || (a < s2 + 3 && b > s2) || (a <= s5 && b > s5))) return v;
+#pragma unroll 1   // one copy of the product; i is uniform, so the selects below are scalar
+    for (int i = 0; i < 6; ++i) {
+        const uint64_t pos = i < 2 ? (uint64_t)i : i < 5 ? s2 + (i - 2) : s5;
+        if (pos < a || pos >= b) continue;
+        const Fp<P> c = i == 0 ? nc.x2r0 : i == 1 ? nc.x2r1 : i == 2 ? nc.b2[0] : i == 3 ? nc.b2[1] : i == 4 ? nc.b2[2] : nc.minus_const;
+        v = add<P>(v, mul<P>(c, pow_u64<P>(x1, pos - a)));
+    }
+    return v;
+}
 
+// numerator coefficient at index a + j of segment g (numerator_at of prove_common.cuh on this rank's local arrays)
+template <class P>
+__device__ __forceinline__ Fp<P> numerator_seg(const Segment &g, uint64_t j, const NumParams &np, const NumConsts<P> &nc, const Fp<P> &x1,
+                                               const Fp<P> *u, const Fp<P> *wit_u, const Fp<P> *u2lo, const Fp<P> *u2hi, const Fp<P> *halo) {
+    Fp<P> d1, d2;
+    seg_data<P>(g, j, np, u, wit_u, u2lo, u2hi, halo, d1, d2);
+    return add<P>(seg_combine<P>(g.kind, d1, d2, nc), seg_consts<P>(g.a + j, g.a + j + 1, x1, nc, np.sigma));
+}
+
+// k_seg_base (phase 2): one workgroup per segment; lane t owns the `span` consecutive indices from a + t span:
+//   laneP[t] = sum_j D1_{lo + j} x1^j,  laneQ[t] likewise for D2 (u region only);  P_s = sum_t laneP[t] x1^(t span), Q_s likewise.
 template <class P, unsigned SEG_THREADS>
-__global__ __launch_bounds__(SEG_THREADS) void k_seg_base(const Segment *segs, SegData sd, const Fp<P> *u, const Fp<P> *wit_u, const Fp<P> *u2lo,
+__global__ __launch_bounds__(SEG_THREADS) void k_seg_base(const Segment *segs, NumParams np, const Fp<P> *u, const Fp<P> *wit_u, const Fp<P> *u2lo,
                                                           const Fp<P> *u2hi, const Fp<P> *halo, Fp<P> x1, Fp<P> *laneP, Fp<P> *laneQ, Fp<P> *Pseg,
                                                           Fp<P> *Qseg) {
     __shared__ Fp<P> sh[SEG_THREADS];
@@ -481,13 +434,12 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg_base(const Segment *segs, S
     const bool two = g.kind == pmlayout::SEG_U;
     const uint64_t len = g.b - g.a, span = (len + SEG_THREADS - 1) / SEG_THREADS;
     const uint64_t lo = (uint64_t)threadIdx.x * span;
-    uint64_t hi = lo + span;
-    if (hi > len) hi = len;
+    const uint64_t hi = lo + span < len ? lo + span : len;
     Fp<P> accP = Fp<P>::zero(), accQ = Fp<P>::zero();
     if (lo < len) {
         for (uint64_t j = hi; j-- > lo;) {
             Fp<P> d1, d2;
-            seg_data<P>(g, j, sd, u, wit_u, u2lo, u2hi, halo, d1, d2);
+            seg_data<P>(g, j, np, u, wit_u, u2lo, u2hi, halo, d1, d2);
             accP = add<P>(mul<P>(accP, x1), d1);
             if (two) accQ = add<P>(mul<P>(accQ, x1), d2);
         }
@@ -495,32 +447,14 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg_base(const Segment *segs, S
     laneP[at] = accP;
     laneQ[at] = accQ;
     const Fp<P> xl = lo < len ? pow_u64<P>(x1, lo) : Fp<P>::zero();
-    sh[threadIdx.x] = lo < len ? mul<P>(accP, xl) : accP;
-    __syncthreads();
-    for (unsigned off = SEG_THREADS / 2; off > 0; off >>= 1) {
-        if (threadIdx.x < off) sh[threadIdx.x] = add<P>(sh[threadIdx.x], sh[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) Pseg[blockIdx.x] = sh[0];
-    __syncthreads();
-    sh[threadIdx.x] = two && lo < len ? mul<P>(accQ, xl) : Fp<P>::zero();
-    __syncthreads();
-    for (unsigned off = SEG_THREADS / 2; off > 0; off >>= 1) {
-        if (threadIdx.x < off) sh[threadIdx.x] = add<P>(sh[threadIdx.x], sh[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) Qseg[blockIdx.x] = sh[0];
+    const Fp<P> Ps = block_sum<P, SEG_THREADS>(sh, lo < len ? mul<P>(accP, xl) : accP);
+    const Fp<P> Qs = block_sum<P, SEG_THREADS>(sh, two && lo < len ? mul<P>(accQ, xl) : Fp<P>::zero());
+    if (threadIdx.x == 0) { Pseg[blockIdx.x] = Ps; Qseg[blockIdx.x] = Qs; }
 }
 
 // 512 lanes per segment: with ~256-400 segments per rank every CU holds one or two workgroups at 2-4 waves per SIMD (1024 lanes and
 // half as many segments left a third of the chip idle and four waves queueing on each busy SIMD: profiles/r03_k_*)
 constexpr unsigned SEG_LANES = 512;
-
-// does [a, b) contain one of the numerator's constants (indices 0, 1, 2 sigma .. 2 sigma + 2)?
-__host__ __device__ inline bool filler_has_const(uint64_t a, uint64_t b, uint64_t sigma) {
-    const uint64_t s2 = 2 * sigma;
-    return a < 2 || (a < s2 + 3 && b > s2);
-}
 
 // k_seg_chain (phase 3): the carry chain over ALL ranks' segments, on the device (round 2 and the first half of round 3 folded it on
 // the host: ~2 600 segments x a few Fr products = 0.16 ms of host time per proof at N = 8).  One workgroup.  In increasing index
@@ -530,42 +464,37 @@ __host__ __device__ inline bool filler_has_const(uint64_t a, uint64_t b, uint64_
 struct SegRefDev { uint64_t a, b; uint32_t rank, idx; };   // == pm_pk::SegRef
 constexpr unsigned CHAIN_THREADS = 512;
 
+// the kind of the segment that starts at index a (quotient_segments of layout.hpp: a segment never straddles two regions)
+__device__ __forceinline__ uint32_t seg_kind_at(uint64_t a, uint64_t n, uint64_t sigma) {
+    if (a >= 8 * sigma) return a < 8 * sigma + n ? pmlayout::SEG_U2LO : pmlayout::SEG_U2HI;
+    if (a >= 5 * sigma) return a <= 5 * sigma + n ? pmlayout::SEG_U : pmlayout::SEG_FILLER;
+    return a >= 3 * sigma && a < 3 * sigma + n ? pmlayout::SEG_WITU : pmlayout::SEG_FILLER;
+}
+// V of segment e from its rank's exchanged record [ u(x1) partial | P_s (SS) | Q_s (SS) ]
 template <class P>
-__device__ __forceinline__ Fp<P> seg_value(const SegRefDev &e, const Fp<P> *hall, size_t rec, size_t SS, const NumConsts<P> &nc, const Fp<P> &c1u,
-                                           const Fp<P> &x1, uint64_t n, uint64_t sigma) {
-    const uint64_t s2 = 2 * sigma, s3 = 3 * sigma, s5 = 5 * sigma, s8 = 8 * sigma, a = e.a, b = e.b;
-    const Fp<P> Ps = hall[(size_t)e.rank * rec + 1 + e.idx];
-    if ((a >= s3 && a < s3 + n) || a >= s8) return mul<P>(nc.x2, Ps);                           // witness_u, (u^2)_lo, (u^2)_hi
-    if (a >= s5 && a <= s5 + n) {                                                                  // the u region (n + 1 entries)
-        Fp<P> v = add<P>(mul<P>(c1u, Ps), mul<P>(nc.two_x2_r1, hall[(size_t)e.rank * rec + 1 + SS + e.idx]));
-        if (a == s5) v = add<P>(v, nc.minus_const);                                                // its first index, offset 0
-        return v;
-    }
-    Fp<P> v = Fp<P>::zero();                                                                       // fillers: the constants
-    if (filler_has_const(a, b, sigma)) {
-        const uint64_t pos[5] = {0, 1, s2, s2 + 1, s2 + 2};
-        const Fp<P> val[5] = {nc.x2r0, nc.x2r1, nc.b2[0], nc.b2[1], nc.b2[2]};
-        for (int i = 0; i < 5; ++i)
-            if (pos[i] >= a && pos[i] < b) v = add<P>(v, mul<P>(val[i], pow_u64<P>(x1, pos[i] - a)));
-    }
-    return v;
+__device__ __forceinline__ Fp<P> seg_value(const SegRefDev &e, const Fp<P> *hall, size_t rec, size_t SS, const NumParams &np, const NumConsts<P> &nc,
+                                           const Fp<P> &x1) {
+    const uint32_t kind = seg_kind_at(e.a, np.n, np.sigma);
+    const Fp<P> *sums = hall + (size_t)e.rank * rec + 1 + e.idx;
+    const Fp<P> Ps = kind != pmlayout::SEG_FILLER ? sums[0] : Fp<P>::zero();
+    const Fp<P> Qs = kind == pmlayout::SEG_U ? sums[SS] : Fp<P>::zero();
+    return add<P>(seg_combine<P>(kind, Ps, Qs, nc), seg_consts<P>(e.a, e.b, x1, nc, np.sigma));
 }
 
 template <class P>
-__global__ __launch_bounds__(CHAIN_THREADS) void k_seg_chain(const SegRefDev *segs, unsigned T, const Fp<P> *hall, size_t rec, size_t SS, NumConsts<P> nc,
-                                                             Fp<P> x1, Fp<P> x1_pow_common, uint64_t common_len, uint64_t n, uint64_t sigma, uint32_t my_rank,
+__global__ __launch_bounds__(CHAIN_THREADS) void k_seg_chain(const SegRefDev *segs, unsigned T, const Fp<P> *hall, size_t rec, size_t SS, NumParams np,
+                                                             NumConsts<P> nc, Fp<P> x1, Fp<P> x1_pow_common, uint64_t common_len, uint32_t my_rank,
                                                              Fp<P> *carry, Fp<P> *rem) {
     __shared__ Fp<P> shA[CHAIN_THREADS], shB[CHAIN_THREADS];
     const unsigned t = threadIdx.x, per = (T + CHAIN_THREADS - 1) / CHAIN_THREADS;
     const unsigned lo = t * per < T ? t * per : T, hi = lo + per < T ? lo + per : T;
-    const Fp<P> c1u = add<P>(Fp<P>::one(), nc.two_x2_r0);
     auto mult = [&](const SegRefDev &e) { const uint64_t len = e.b - e.a; return len == common_len ? x1_pow_common : pow_u64<P>(x1, len); };
     // this lane's run as ONE affine map h -> A + B h (h = H at the run's upper end)
     Fp<P> A = Fp<P>::zero(), B = Fp<P>::one();
     for (unsigned i = hi; i-- > lo;) {
         const SegRefDev e = segs[i];
         const Fp<P> M = mult(e);
-        A = add<P>(seg_value<P>(e, hall, rec, SS, nc, c1u, x1, n, sigma), mul<P>(M, A));
+        A = add<P>(seg_value<P>(e, hall, rec, SS, np, nc, x1), mul<P>(M, A));
         B = mul<P>(M, B);
     }
     shA[t] = A;
@@ -588,7 +517,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_seg_chain(const SegRefDev *se
     for (unsigned i = hi; i-- > lo;) {
         const SegRefDev e = segs[i];
         if (e.rank == my_rank) carry[e.idx] = h;
-        h = add<P>(seg_value<P>(e, hall, rec, SS, nc, c1u, x1, n, sigma), mul<P>(mult(e), h));
+        h = add<P>(seg_value<P>(e, hall, rec, SS, np, nc, x1), mul<P>(mult(e), h));
     }
     if (t == 0) rem[0] = h;                            // H_0: the remainder of the division (prover.rs:221)
 }
@@ -597,7 +526,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_seg_chain(const SegRefDev *se
 // constant multiplier X = x1^span (every lane but the last active one owns a full span; the carry-in is folded into the
 // last lane's value), then every lane re-walks its span and writes q_{k-1} = H_k.
 template <class P, unsigned SEG_THREADS>
-__global__ __launch_bounds__(SEG_THREADS) void k_seg_expand(const Segment *segs, SegData sd, NumConsts<P> nc, const Fp<P> *u, const Fp<P> *wit_u,
+__global__ __launch_bounds__(SEG_THREADS) void k_seg_expand(const Segment *segs, NumParams np, NumConsts<P> nc, const Fp<P> *u, const Fp<P> *wit_u,
                                                             const Fp<P> *u2lo, const Fp<P> *u2hi, const Fp<P> *halo, Fp<P> x1,
                                                             const Fp<P> *laneP, const Fp<P> *laneQ, const Fp<P> *carry, Fp<P> *q) {
     __shared__ Fp<P> sh[SEG_THREADS];
@@ -605,29 +534,15 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg_expand(const Segment *segs,
     const uint64_t len = g.b - g.a, span = (len + SEG_THREADS - 1) / SEG_THREADS;
     const unsigned t = threadIdx.x, active = (unsigned)((len + span - 1) / span);
     const uint64_t lo = (uint64_t)t * span;
-    uint64_t hi = lo + span;
-    if (hi > len) hi = len;
+    const uint64_t hi = lo + span < len ? lo + span : len;
     const Fp<P> cin = carry[blockIdx.x];
     Fp<P> w = Fp<P>::zero();
     if (t < active) {
         // this lane's Horner value of the numerator (carry-in 0) from phase 2's data sums and the constants phase 3 brought
         const size_t at = (size_t)blockIdx.x * SEG_THREADS_MAX + t;
-        switch (g.kind) {
-            case pmlayout::SEG_WITU:
-            case pmlayout::SEG_U2LO:
-            case pmlayout::SEG_U2HI: w = mul<P>(nc.x2, laneP[at]); break;
-            case pmlayout::SEG_U: {
-                const Fp<P> p = laneP[at];
-                w = add<P>(add<P>(p, mul<P>(nc.two_x2_r0, p)), mul<P>(nc.two_x2_r1, laneQ[at]));
-                const uint64_t k0 = 5 * sd.sigma;                        // the constant term sits at the region's first index
-                if (g.a + lo <= k0 && k0 < g.a + hi) w = add<P>(w, mul<P>(nc.minus_const, pow_u64<P>(x1, k0 - g.a - lo)));
-                break;
-            }
-            default:
-                if (filler_has_const(g.a + lo, g.a + hi, sd.sigma))      // a handful of lanes in the whole proof
-                    for (uint64_t j = hi; j-- > lo;) w = add<P>(mul<P>(w, x1), numerator_seg<P>(g, j, sd, nc, u, wit_u, u2lo, u2hi, halo));
-                break;
-        }
+        const Fp<P> Pl = g.kind != pmlayout::SEG_FILLER ? laneP[at] : Fp<P>::zero();
+        const Fp<P> Ql = g.kind == pmlayout::SEG_U ? laneQ[at] : Fp<P>::zero();
+        w = add<P>(seg_combine<P>(g.kind, Pl, Ql, nc), seg_consts<P>(g.a + lo, g.a + hi, x1, nc, np.sigma));
         if (t == active - 1) w = add<P>(w, mul<P>(cin, pow_u64<P>(x1, hi - lo)));
     }
     sh[t] = w;
@@ -646,7 +561,7 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg_expand(const Segment *segs,
     Fp<P> acc = t + 1 < active ? sh[t + 1] : cin;          // H at this lane's upper end
     const uint64_t skip = g.a == 0 ? 1 : 0;                // index 0 is the remainder, not a quotient coefficient
     for (uint64_t j = hi; j-- > lo;) {
-        acc = add<P>(mul<P>(acc, x1), numerator_seg<P>(g, j, sd, nc, u, wit_u, u2lo, u2hi, halo));
+        acc = add<P>(mul<P>(acc, x1), numerator_seg<P>(g, j, np, nc, x1, u, wit_u, u2lo, u2hi, halo));
         if (g.a + j > 0) q[g.qoff + j - skip] = acc;
     }
 }
@@ -678,6 +593,32 @@ struct PhaseEnd {
     }
 };
 
+// One rank's partial point as it travels; `flags` carries the rank's status word where a phase sends one along (phase 1), else 0.
+template <class C>
+struct RankPoint { uint64_t xy[sizeof(Affine<C>) / 8]; uint32_t inf, flags; };
+
+// [.]_1 = the sum over the ranks of their partial points (RCCL has no elliptic-curve reduction: all-gather + local adds, SURVEY.md §8e
+// row 1), in two steps so that a phase can judge what came with the points before it adds them.  gather_ranks: ONE all-gather of this
+// rank's record `mine` -- RankPoints first, then whatever else the phase sends along -- into `all`; the ranks' flag words are OR-ed into *flags.
+template <class C>
+static int gather_ranks(pm_ctx *ctx, const void *mine, size_t rec_bytes, std::vector<uint8_t> &all, unsigned *flags = nullptr) {
+    all.resize(rec_bytes * ctx->comm->world);
+    PM_TRY(comm_status(ctx, ctx->comm->all_gather(mine, all.data(), rec_bytes, ctx->stream), "all_gather"));
+    for (size_t at = 0; flags && at < all.size(); at += rec_bytes) *flags |= ((const RankPoint<C> *)(all.data() + at))->flags;
+    return PM_OK;
+}
+// sum_over_ranks: pm_g1_sum of RankPoint number `column` of the gathered records
+template <class C>
+static int sum_over_ranks(const std::vector<uint8_t> &all, size_t rec_bytes, unsigned column, uint64_t *xy, int *inf) {
+    std::vector<uint64_t> pts;
+    std::vector<int> infs;
+    for (size_t at = 0; at < all.size(); at += rec_bytes) {
+        const RankPoint<C> *p = (const RankPoint<C> *)(all.data() + at) + column;
+        pts.insert(pts.end(), p->xy, p->xy + sizeof(Affine<C>) / 8);
+        infs.push_back((int)p->inf);
+    }
+    return pm_g1_sum(C::ID, pts.data(), infs.data(), infs.size(), xy, inf);
+}
 
 // ------------------------------------------------------------------------------------------------- phase 1
 template <class C>
@@ -694,34 +635,26 @@ int prove_phase1_sharded(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const 
     const uint64_t m = L.m, B = L.B;
     const uint32_t N = L.N, q = L.q;
     hipStream_t st = ctx->stream;
-    if (!ctx->keep_timings) timing_reset(ctx);
-    ctx->pk = pk;
-    ctx->phase = 0;
-    TimingGuard timing_guard{ctx};
-    StageTimer t_phase(ctx, T_PHASE);
+    PhaseTimers timers(ctx, pk);
     const uint64_t zl = pmlayout::ztail_lo(Lz, N, q), zh = pmlayout::ztail_lo(Lz, N, q + 1), zcnt = zh - zl;
     const uint64_t hcnt = m - (q == N - 1 ? 1 : 0), rucnt = (uint64_t)N * (B + 1), tail = q == 0 ? 5 : 0;
     const uint64_t len_c = zcnt + hcnt + rucnt + tail;
     if (len_c != pk->res_cnt[1] || m + (q == 0 ? 2 : 0) != pk->res_cnt[0]) return PM_ERR_STATE;   // key and prover disagree on the layout
     // assignment: [x (m0) | w padded to N slices of wblk | staging of this rank's slice]
     const uint64_t wblk = (mw + N - 1) / N;
-    PM_HIP(ctx, ctx->pw.xw.reserve((m0 + ((uint64_t)N + 1) * wblk) * sizeof(Fr)));
-    PM_HIP(ctx, ctx->pw.ue.reserve(m * sizeof(Fr)));
-    PM_HIP(ctx, ctx->pw.we.reserve(m * sizeof(Fr)));
-    PM_HIP(ctx, ctx->pw.u.reserve((m + 2) * sizeof(Fr)));
-    PM_HIP(ctx, ctx->pw.w.reserve(m * sizeof(Fr)));
-    PM_HIP(ctx, ctx->pw.wit_u.reserve(m * sizeof(Fr)));
-    PM_HIP(ctx, ctx->pw.u2.reserve(2 * m * sizeof(Fr)));
-    PM_HIP(ctx, ctx->pw.sc_c.reserve((len_c + 1) * sizeof(Fr)));
-    PM_HIP(ctx, ctx->pw.rows.reserve(2 * sizeof(Fr)));
-    PM_HIP(ctx, ctx->pw.flags.reserve(64));
-    PM_HIP(ctx, ctx->sh_a.reserve(m * sizeof(Fr)));
-    PM_HIP(ctx, ctx->sh_b.reserve(m * sizeof(Fr)));
+    ProveWs &ws = ctx->pw;
+    PM_HIP(ctx, ws.xw.reserve((m0 + ((uint64_t)N + 1) * wblk) * sizeof(Fr)));
+    for (DevBuf *b : {&ws.ue, &ws.we, &ws.w, &ws.wit_u, &ctx->sh_a, &ctx->sh_b}) PM_HIP(ctx, b->reserve(m * sizeof(Fr)));
+    PM_HIP(ctx, ws.u.reserve((m + 2) * sizeof(Fr)));
+    PM_HIP(ctx, ws.u2.reserve(2 * m * sizeof(Fr)));
+    PM_HIP(ctx, ws.sc_c.reserve((len_c + 1) * sizeof(Fr)));
+    PM_HIP(ctx, ws.rows.reserve(2 * sizeof(Fr)));
+    PM_HIP(ctx, ws.flags.reserve(64));
     PM_HIP(ctx, ctx->sh_c.reserve((m > 2 * m0 ? m : 2 * m0) * sizeof(Fr)));
-    Fr *xw = ctx->pw.xw.as<Fr>(), *ue = ctx->pw.ue.as<Fr>(), *we = ctx->pw.we.as<Fr>(), *u = ctx->pw.u.as<Fr>(), *wv = ctx->pw.w.as<Fr>();
-    Fr *wit_u = ctx->pw.wit_u.as<Fr>(), *u2lo = ctx->pw.u2.as<Fr>(), *u2hi = u2lo + m, *sc_c = ctx->pw.sc_c.as<Fr>(), *ra = ctx->pw.rows.as<Fr>();
+    Fr *xw = ws.xw.as<Fr>(), *ue = ws.ue.as<Fr>(), *we = ws.we.as<Fr>(), *u = ws.u.as<Fr>(), *wv = ws.w.as<Fr>();
+    Fr *wit_u = ws.wit_u.as<Fr>(), *u2lo = ws.u2.as<Fr>(), *u2hi = u2lo + m, *sc_c = ws.sc_c.as<Fr>(), *ra = ws.rows.as<Fr>();
     Fr *ta = ctx->sh_a.as<Fr>(), *tb = ctx->sh_b.as<Fr>(), *tc = ctx->sh_c.as<Fr>();
-    unsigned *flags = ctx->pw.flags.as<unsigned>();
+    unsigned *flags = ws.flags.as<unsigned>();
     PM_HIP(ctx, hipMemsetAsync(flags, 0, 64, st));
     // Every rank needs the whole assignment (the rows it owns read arbitrary columns: prover.rs:279-302).  From HOST buffers
     // each rank uploads only its 1/N slice of w over its own PCIe link and the fabric delivers the rest (all-gather of
@@ -747,33 +680,28 @@ int prove_phase1_sharded(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const 
     {
         StageTimer t(ctx, T_WITNESS_MAP);
         PM_LAUNCH(ctx, k_witness_cyclic<P>, dim3(nblk(m)), dim3(256), 0, st, A, Bm, Cm, xw, ue, we, m0, nr, L);
-        if (zcnt) {
-            PM_LAUNCH(ctx, k_ztail_slice<P>, dim3(nblk(zcnt)), dim3(256), 0, st, A, Bm, xw, sc_c, m0, mw, zl, zh);
-        }
-        PM_LAUNCH(ctx, k_check_sap_L<P>, dim3(nblk(m)), dim3(256), 0, st, ue, we, m, flags);   // rem == 0 of prover.rs:108
+        if (zcnt) PM_LAUNCH(ctx, k_ztail_slice<P>, dim3(nblk(zcnt)), dim3(256), 0, st, A, Bm, xw, sc_c, m0, mw, zl, zh);
+        PM_LAUNCH(ctx, k_check_sap<P>, dim3(nblk(m), 1), dim3(256), 0, st, ue, we, m, flags);   // rem == 0 of prover.rs:108
     }
     hp.mark("upload+witness");
     // N1, N2 (prover.rs:94,96): the transforms consume their input, so the witness-only U part (N5) is prepared first
     if (!sparse_head) {
         PM_HIP(ctx, hipMemcpyAsync(tc, ue, m * sizeof(Fr), hipMemcpyDeviceToDevice, st));
         PM_LAUNCH(ctx, k_zero_head_cyclic<P>, dim3(nblk(m)), dim3(256), 0, st, tc, 2 * m0, L);
-        PM_TRY(dist_intt<C>(ctx, pk, L, tc, ta, wit_u));
+        PM_TRY(dist_intt<C>(ctx, ctx, pk, L, tc, ta, wit_u));
     }
     // PM_OPT_NTT_OVERLAP: w's transform (N2) runs on the helper context's stream beside u's chain
     // (N1, then the three transforms of the square) and joins before k_untwist_combine_L, so that on a fabric its all-to-all
     // travels under u's kernels and u's under w's local passes.  Every rank issues the exchanges in the same order
     // (u, w, square forward, square inverse); they are on two streams of ONE communicator.
-    const bool ntt_beside = ctx->opt.v[PM_OPT_NTT_OVERLAP] != 0;
     pm_ctx *wctx = ctx;
-    if (ntt_beside) {
-        pm_ctx *aux = ctx_aux(ctx);
-        if (aux && aux->sh_a.reserve(m * sizeof(Fr)) == hipSuccess) wctx = aux;
-    }
-    if (wctx != ctx) {   // `we` is complete (and k_check_sap_L has read it) at this point of the stream
+    if (pm_ctx *aux = ctx->opt.v[PM_OPT_NTT_OVERLAP] != 0 ? ctx_aux(ctx) : nullptr)
+        if (aux->sh_a.reserve(m * sizeof(Fr)) == hipSuccess) wctx = aux;
+    if (wctx != ctx) {   // `we` is complete (and k_check_sap has read it) at this point of the stream
         PM_HIP(ctx, hipEventRecord(ctx->ev_sc_a, st));
         PM_HIP(ctx, hipStreamWaitEvent(wctx->stream, ctx->ev_sc_a, 0));
     }
-    PM_TRY(dist_intt<C>(ctx, pk, L, ue, ta, u));
+    PM_TRY(dist_intt<C>(ctx, ctx, pk, L, ue, ta, u));
     if (q == 0) PM_HIP(ctx, hipMemcpyAsync(u + m, ra, 2 * sizeof(Fr), hipMemcpyDeviceToDevice, st));   // sc_a = u || r_a on rank 0
     PM_TRY(dist_intt<C>(ctx, wctx, pk, L, we, wctx != ctx ? wctx->sh_a.as<Fr>() : ta, wv));
     if (wctx != ctx) PM_HIP(ctx, hipEventRecord(wctx->ev_sc_a, wctx->stream));
@@ -784,14 +712,14 @@ int prove_phase1_sharded(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const 
         PM_LAUNCH(ctx, k_ue_head<P>, dim3(1), dim3(64), 0, st, A, Bm, Cm, xw, tc, m0, nr, (unsigned)(2 * m0));
         PM_LAUNCH(ctx, k_wit_u_sparse_L<P>, dim3(nblk(m)), dim3(256), 0, st, u, tc, winv, inverse<P>(from_u64<P>(n)), (unsigned)(2 * m0), wit_u, L);
     }
-    {   // square_polynomial (prover.rs:315-328) through the negacyclic half (prove.hip: k_twist): u^2 = lo + X^n hi
+    {   // square_polynomial (prover.rs:315-328) through the negacyclic half (prove_kernels.cuh: k_twist): u^2 = lo + X^n hi
         const Fr *psi = nullptr, *psi_inv = nullptr;
         PM_TRY(twiddles_get<C>(ctx, pk->log_n + 1, false, &psi));
         PM_TRY(twiddles_get<C>(ctx, pk->log_n + 1, true, &psi_inv));
         PM_LAUNCH(ctx, k_twist_L<P>, dim3(nblk(m)), dim3(256), 0, st, u, psi, ta, L);
         PM_TRY(dist_ntt<C>(ctx, pk, L, ta, tb, tc));
-        PM_LAUNCH(ctx, k_square_L<P>, dim3(nblk(m)), dim3(256), 0, st, tc, m);
-        PM_TRY(dist_intt<C>(ctx, pk, L, tc, tb, ta));
+        PM_LAUNCH(ctx, k_square<P>, dim3(nblk(m), 1), dim3(256), 0, st, tc, m);
+        PM_TRY(dist_intt<C>(ctx, ctx, pk, L, tc, tb, ta));
         if (wctx != ctx) PM_HIP(ctx, hipStreamWaitEvent(st, wctx->ev_sc_a, 0));   // w's coefficients
         PM_LAUNCH(ctx, k_untwist_combine_L<P>, dim3(nblk(m)), dim3(256), 0, st, ta, psi_inv, wv, u2lo, u2hi, L, inverse<P>(from_u64<P>(2)));
     }
@@ -801,97 +729,73 @@ int prove_phase1_sharded(pm_ctx *ctx, const pm_pk *pk, const uint64_t *x, const 
                        tail ? sc_c + zcnt + hcnt + rucnt : (Fr *)nullptr, L, flags);
     }
     hp.mark("transforms");
-    // ONE exchange for the whole phase, after the MSMs: the status flags, the two partial points and the halo coefficients
-    // phase 3 needs (the last coefficient of each of this rank's blocks).  The flags travel with the points instead of
-    // ahead of them: an unsatisfied witness costs the MSMs before every rank reports it -- the rare path pays, not the proof.
-    struct Rec1 {
-        uint32_t flags, a_inf, c_inf, pad;
-        uint64_t a_xy[sizeof(Affine<C>) / 8], c_xy[sizeof(Affine<C>) / 8];
-    };
-    const size_t rec_bytes = sizeof(Rec1) + (size_t)N * sizeof(Fr);
-    std::vector<uint8_t> mine(rec_bytes), all(rec_bytes * N);
-    Rec1 *r1 = (Rec1 *)mine.data();
-    Fr *my_halo = (Fr *)(mine.data() + sizeof(Rec1));
+    // ONE exchange for the whole phase, after the MSMs: the two partial points, the status flags (in the first point's flag word) and
+    // the halo coefficients phase 3 needs (the last coefficient of each of this rank's blocks).  The flags travel with the points instead
+    // of ahead of them: an unsatisfied witness costs the MSMs before every rank reports it -- the rare path pays, not the proof.
+    const size_t halo_bytes = (size_t)N * sizeof(Fr), rec_bytes = 2 * sizeof(RankPoint<C>) + halo_bytes;
+    std::vector<uint8_t> mine(rec_bytes), all;
+    RankPoint<C> *pt = (RankPoint<C> *)mine.data();                        // [a]_1, [c]_1
+    Fr *my_halo = (Fr *)(pt + 2);
     PM_HIP(ctx, ctx->halo.reserve(2 * (size_t)N * sizeof(Fr)));            // [halo of my blocks (phase 3) | my blocks' last coefficients]
     Fr *d_last = ctx->halo.as<Fr>() + N;
     PM_LAUNCH(ctx, k_halo_pack<P>, dim3((N + 63) / 64), dim3(64), 0, st, (const Fr *)u, L, d_last);
     // flags and halo go to PINNED staging (a pageable destination would make these two copies wait for the stream -- all transforms --
     // before the MSM pipelines below could even be enqueued) and into the record after the MSMs' final synchronisation
-    uint8_t *stage = nullptr;
-    const size_t halo_bytes = (size_t)N * sizeof(Fr);
-    if (ctx_pinned(ctx) && 16 + halo_bytes <= PINNED_STAGE_BYTES) stage = pinned_slot<uint8_t>(ctx, PINNED_FLAGS);
+    uint8_t *stage = ctx_pinned(ctx) && 16 + halo_bytes <= PINNED_STAGE_BYTES ? pinned_slot<uint8_t>(ctx, PINNED_FLAGS) : nullptr;
     struct DrainOnExit {      // without pinned staging the copies target `mine`: no return path may free it while they are pending
         hipStream_t st;
         bool armed;
         ~DrainOnExit() { if (armed) (void)hipStreamSynchronize(st); }
     } drain{st, stage == nullptr};
-    PM_HIP(ctx, hipMemcpyAsync(stage ? (void *)stage : (void *)&r1->flags, flags, 4, hipMemcpyDeviceToHost, st));
+    volatile unsigned *h_flags = nullptr;
+    PM_TRY(stage_flags(ctx, flags, &h_flags, stage ? nullptr : &pt[0].flags));
     PM_HIP(ctx, hipMemcpyAsync(stage ? (void *)(stage + 16) : (void *)my_halo, d_last, halo_bytes, hipMemcpyDeviceToHost, st));   // both land before the MSM's final sync
     // [a]_1 and [c]_1 are independent MSMs: both pipelines are ENQUEUED before either is waited for -- [a]_1 on the helper
     // context's stream and workspace, behind an event on this stream; [c]_1 here -- so the smaller one's latency-bound sort
     // front end and bucket reduction run under the larger one's accumulation.  One host thread, no collective in between
     // (the single-GPU prover starts [a]_1 earlier, from a second thread: prove.hip).  PM_OPT_MSM_OVERLAP = 0: one after the other.
     int a_inf_l = 1, c_inf_l = 1;
-    const bool overlap = ctx->opt.v[PM_OPT_MSM_OVERLAP] != 0;
-    if (pm_ctx *aux = overlap ? ctx_aux(ctx) : nullptr) {
+    if (pm_ctx *aux = ctx->opt.v[PM_OPT_MSM_OVERLAP] != 0 ? ctx_aux(ctx) : nullptr) {
         timing_reset_aux(ctx, aux);
         PM_HIP(ctx, hipEventRecord(ctx->ev_sc_a, st));
         PM_HIP(ctx, hipStreamWaitEvent(aux->stream, ctx->ev_sc_a, 0));
         int st_a = msm_resident_begin<C>(aux, pk, 0, u);
         const int st_c = st_a == PM_OK ? msm_resident_begin<C>(ctx, pk, 1, sc_c) : (int)PM_OK;
-        const int en_c = st_a == PM_OK && st_c == PM_OK ? msm_resident_end<C>(ctx, r1->c_xy, &c_inf_l) : (int)PM_OK;
-        if (st_a == PM_OK) st_a = msm_resident_end<C>(aux, r1->a_xy, &a_inf_l);      // always drained: its scalars live in this context
+        const int en_c = st_a == PM_OK && st_c == PM_OK ? msm_resident_end<C>(ctx, pt[1].xy, &c_inf_l) : (int)PM_OK;
+        if (st_a == PM_OK) st_a = msm_resident_end<C>(aux, pt[0].xy, &a_inf_l);      // always drained: its scalars live in this context
         timing_flush(aux);
         timing_absorb_aux(ctx, aux);
         if (st_a != PM_OK) { ctx->err = aux->err; return st_a; }
         PM_TRY(st_c);
         PM_TRY(en_c);
     } else {
-        PM_TRY(msm_resident<C>(ctx, pk, 0, u, r1->a_xy, &a_inf_l));
-        PM_TRY(msm_resident<C>(ctx, pk, 1, sc_c, r1->c_xy, &c_inf_l));
+        PM_TRY(msm_resident<C>(ctx, pk, 0, u, pt[0].xy, &a_inf_l));
+        PM_TRY(msm_resident<C>(ctx, pk, 1, sc_c, pt[1].xy, &c_inf_l));
     }
     hp.mark("msm_a+c");
-    if (stage) {              // the MSMs' final synchronisation is behind us: the staged words have landed
-        memcpy(&r1->flags, stage, 4);
-        memcpy(my_halo, stage + 16, halo_bytes);
-    }
+    pt[0].flags = *h_flags;   // the MSMs' final synchronisation is behind us: the staged words have landed
+    if (stage) memcpy(my_halo, stage + 16, halo_bytes);
     drain.armed = false;
-    r1->a_inf = (uint32_t)a_inf_l;
-    r1->c_inf = (uint32_t)c_inf_l;
-    r1->pad = 0;
-    PM_TRY(comm_status(ctx, ctx->comm->all_gather(mine.data(), all.data(), rec_bytes, st), "all_gather"));
-    hp.mark("exchange");
+    pt[0].inf = (uint32_t)a_inf_l;
+    pt[1].inf = (uint32_t)c_inf_l;
     unsigned hflags = 0;
-    std::vector<uint64_t> pa((size_t)N * (sizeof(Affine<C>) / 8)), pc(pa.size());
-    std::vector<int> ia(N), ic(N);
-    for (uint32_t r = 0; r < N; ++r) {
-        const Rec1 *rr = (const Rec1 *)(all.data() + (size_t)r * rec_bytes);
-        hflags |= rr->flags;
-        memcpy(&pa[r * (sizeof(Affine<C>) / 8)], rr->a_xy, sizeof(Affine<C>));
-        memcpy(&pc[r * (sizeof(Affine<C>) / 8)], rr->c_xy, sizeof(Affine<C>));
-        ia[r] = (int)rr->a_inf;
-        ic[r] = (int)rr->c_inf;
-    }
-    if (hflags & 1u) return phase_end.ok(PM_ERR_REMAINDER_NONZERO);                 // prover.rs:108 -- the same flags on every rank
-    if ((hflags & 2u) || !(hflags & 4u)) return phase_end.ok(PM_ERR_DEGREE_BOUND);   // prover.rs:107
-    // [a]_1, [c]_1 = the sums over the ranks (RCCL has no elliptic-curve reduction: all-gather + local adds)
-    PM_TRY(pm_g1_sum(C::ID, pa.data(), ia.data(), N, a_xy, a_inf));
-    PM_TRY(pm_g1_sum(C::ID, pc.data(), ic.data(), N, c_xy, c_inf));
+    PM_TRY(gather_ranks<C>(ctx, mine.data(), rec_bytes, all, &hflags));
+    hp.mark("exchange");
+    if (const int s = phase1_flag_status(hflags)) return phase_end.ok(s);           // prover.rs:107-108 -- the same flags on every rank
+    PM_TRY(sum_over_ranks<C>(all, rec_bytes, 0, a_xy, a_inf));
+    PM_TRY(sum_over_ranks<C>(all, rec_bytes, 1, c_xy, c_inf));
     // halo of my block k1 = the coefficient just below its first one: the last of rank q-1's block k1, or (q = 0) of
     // rank N-1's block k1-1; block (0, 0) starts at coefficient 0 and has none
-    {
-        std::vector<Fr> halo(N, Fr::zero());
-        auto last_of = [&](uint32_t r, uint32_t k1) { return ((const Fr *)(all.data() + (size_t)r * rec_bytes + sizeof(Rec1)))[k1]; };
-        for (uint32_t k1 = 0; k1 < N; ++k1) {
-            if (q > 0) halo[k1] = last_of(q - 1, k1);
-            else if (k1 > 0) halo[k1] = last_of(N - 1, k1 - 1);
-        }
-        PM_HIP(ctx, hipMemcpyAsync(ctx->halo.p, halo.data(), (size_t)N * sizeof(Fr), hipMemcpyHostToDevice, st));
-        PM_HIP(ctx, hipStreamSynchronize(st));     // `halo` is a stack vector
+    std::vector<Fr> halo(N, Fr::zero());
+    auto last_of = [&](uint32_t r, uint32_t k1) { return ((const Fr *)(all.data() + (size_t)r * rec_bytes + 2 * sizeof(RankPoint<C>)))[k1]; };
+    for (uint32_t k1 = 0; k1 < N; ++k1) {
+        if (q > 0) halo[k1] = last_of(q - 1, k1);
+        else if (k1 > 0) halo[k1] = last_of(N - 1, k1 - 1);
     }
+    PM_HIP(ctx, hipMemcpyAsync(ctx->halo.p, halo.data(), halo_bytes, hipMemcpyHostToDevice, st));
+    PM_HIP(ctx, hipStreamSynchronize(st));     // `halo` is a stack vector
     hp.mark("sums+halo");
-    t_phase.stop();
-    timing_flush(ctx);
+    timers.done();
     hp.mark("timers");
     PM_TRY(comm_alive(ctx));
     ctx->phase = 1;
@@ -913,8 +817,7 @@ int prove_phase2_sharded(pm_ctx *ctx, const uint64_t *x1_in, uint64_t *u_at_x1) 
     const Fr x1 = load_fr<P>(x1_in);
     unsigned Lh = 16;
     while (Lh > L.B) Lh >>= 1;
-    const uint64_t lanes = L.m / Lh;
-    const unsigned blocks = nblk(lanes);
+    const unsigned blocks = nblk(L.m / Lh);          // lanes of Lh coefficients
     const size_t S = pk->segs.size(), SS = pk->seg_slots;   // SS = the longest segment list of any rank (the exchanged record size)
     const size_t rec = 1 + 2 * SS;                          // [ u(x1) partial | P_s (SS) | Q_s (SS) ]
     PM_HIP(ctx, ctx->scratch.reserve(((size_t)blocks + rec) * sizeof(Fr)));
@@ -922,15 +825,14 @@ int prove_phase2_sharded(pm_ctx *ctx, const uint64_t *x1_in, uint64_t *u_at_x1) 
     Fr *part = ctx->scratch.as<Fr>(), *out = part + blocks;
     Fr *laneP = ctx->pw.lvl[0].as<Fr>(), *laneQ = laneP + S * SEG_THREADS_MAX;
     PM_LAUNCH(ctx, k_horner_partial_L<P>, dim3(blocks), dim3(256), 0, st, ctx->pw.u.as<Fr>(), L, x1, Lh, part);
-    PM_LAUNCH(ctx, k_phase2_pack<P>, dim3(1), dim3(256), 0, st, (const Fr *)part, blocks, out);
+    PM_LAUNCH(ctx, k_sum_small<P>, dim3(1), dim3(256), 0, st, (const Fr *)part, blocks, out);
     {   // the x1-dependent half of phase 3's division scan (k_seg_base): its segment sums ride on this phase's exchange
         StageTimer t(ctx, T_POLY);
-        const SegData sd{pk->n, pk->sigma};
-        const uint64_t m = pk->n / (uint64_t)pk->shard_count;
-        const Fr *u = ctx->pw.u.as<Fr>(), *wit_u = ctx->pw.wit_u.as<Fr>(), *u2lo = ctx->pw.u2.as<Fr>(), *u2hi = u2lo + m, *halo = ctx->halo.as<Fr>();
+        const NumParams np{pk->n, pk->sigma, 0};
+        const Fr *u = ctx->pw.u.as<Fr>(), *wit_u = ctx->pw.wit_u.as<Fr>(), *u2lo = ctx->pw.u2.as<Fr>(), *u2hi = u2lo + L.m, *halo = ctx->halo.as<Fr>();
         const Segment *d_segs = (const Segment *)pk->d_segs;
         PM_HIP(ctx, hipMemsetAsync(out + 1, 0, 2 * SS * sizeof(Fr), st));
-        PM_LAUNCH(ctx, (k_seg_base<P, SEG_LANES>), dim3((unsigned)S), dim3(SEG_LANES), 0, st, d_segs, sd, u, wit_u, u2lo, u2hi, halo, x1, laneP, laneQ,
+        PM_LAUNCH(ctx, (k_seg_base<P, SEG_LANES>), dim3((unsigned)S), dim3(SEG_LANES), 0, st, d_segs, np, u, wit_u, u2lo, u2hi, halo, x1, laneP, laneQ,
                        out + 1, out + 1 + SS);
     }
     std::vector<Fr> mine(rec);
@@ -962,16 +864,14 @@ int prove_phase3_sharded(pm_ctx *ctx, const uint64_t *x1_in, const uint64_t *x2_
     PhaseEnd phase_end(ctx, "phase 3");
     HostProfile hp("phase 3", pk->shard_rank);
     hipStream_t st = ctx->stream;
-    if (!ctx->keep_timings) timing_reset(ctx);
-    TimingGuard timing_guard{ctx};
-    StageTimer t_phase(ctx, T_PHASE);
-    const uint64_t n = pk->n, sigma = pk->sigma, m = n / (uint64_t)pk->shard_count;
+    PhaseTimers timers(ctx);
+    const uint64_t m = pk->n / (uint64_t)pk->shard_count;
     const uint32_t N = (uint32_t)pk->shard_count, q = (uint32_t)pk->shard_rank;
     const Fr x1 = load_fr<P>(x1_in), x2 = load_fr<P>(x2_in), a_at = load_fr<P>(a_in), c_at = load_fr<P>(c_in);
     Fr rah[2];
     memcpy(rah, ctx->ra_host, sizeof(rah));          // phase 1 kept the host copy of r_a: no device read-back, no synchronisation here
     const NumConsts<P> nc = make_num_consts<P>(x2, rah, a_at, c_at);
-    const SegData sd{n, sigma};
+    const NumParams np{pk->n, pk->sigma, 0};
     const size_t S = pk->segs.size(), SS = pk->seg_slots, rec = 1 + 2 * SS;
     if (memcmp(ctx->x1_host, x1_in, sizeof(Fr)) != 0 || ctx->seg_all.size() != rec * N * sizeof(Fr)) {
         ctx->err = "phase 3 needs the x1 of phase 2 (its data sums of the division scan were taken at that point)";
@@ -984,52 +884,36 @@ int prove_phase3_sharded(pm_ctx *ctx, const uint64_t *x1_in, const uint64_t *x2_
     const Segment *d_segs = (const Segment *)pk->d_segs;
     // The carry chain over ALL segments (k_seg_chain, one workgroup), then the expansion of this rank's segments; phase 2's
     // exchanged data sums go up once (N x (1 + 2 SS) Fr, ~80 KB at N = 8), the remainder H_0 comes back with the MSM's result.
-    const size_t T = pk->all_segs.size();
     PM_HIP(ctx, ctx->pw.lvl[2].reserve(rec * N * sizeof(Fr)));
     Fr *d_hall = ctx->pw.lvl[2].as<Fr>(), *d_rem = carry + S;
-    if (!ctx_pinned(ctx)) {
-        ctx->err = "pinned result slot allocation failed";
-        return PM_ERR_HIP;
-    }
+    if (!ctx_pinned(ctx)) { ctx->err = "pinned result slot allocation failed"; return PM_ERR_HIP; }
     Fr *h_rem = pinned_slot<Fr>(ctx, PINNED_REMAINDER);      // pinned: the copy below must not block the host
     *h_rem = Fr::one();
     {
         StageTimer t(ctx, T_POLY);
         PM_HIP(ctx, hipMemcpyAsync(d_hall, ctx->seg_all.data(), rec * N * sizeof(Fr), hipMemcpyHostToDevice, st));
-        PM_LAUNCH(ctx, k_seg_chain<P>, dim3(1), dim3(CHAIN_THREADS), 0, st, (const SegRefDev *)pk->d_all_segs, (unsigned)T, (const Fr *)d_hall, rec, SS,
-                       nc, x1, pow_u64<P>(x1, pk->max_seg), pk->max_seg, n, sigma, q, carry, d_rem);
-        PM_LAUNCH(ctx, (k_seg_expand<P, SEG_LANES>), dim3((unsigned)S), dim3(SEG_LANES), 0, st, d_segs, sd, nc, u, wit_u, u2lo, u2hi, halo, x1,
+        PM_LAUNCH(ctx, k_seg_chain<P>, dim3(1), dim3(CHAIN_THREADS), 0, st, (const SegRefDev *)pk->d_all_segs, (unsigned)pk->all_segs.size(), (const Fr *)d_hall, rec, SS,
+                       np, nc, x1, pow_u64<P>(x1, pk->max_seg), pk->max_seg, q, carry, d_rem);
+        PM_LAUNCH(ctx, (k_seg_expand<P, SEG_LANES>), dim3((unsigned)S), dim3(SEG_LANES), 0, st, d_segs, np, nc, u, wit_u, u2lo, u2hi, halo, x1,
                        (const Fr *)laneP, (const Fr *)laneQ, (const Fr *)carry, qv);
         PM_HIP(ctx, hipMemcpyAsync(h_rem, d_rem, sizeof(Fr), hipMemcpyDeviceToHost, st));      // lands before the MSM's final synchronisation
     }
     hp.mark("chain+expand enqueue");
-    // [d]_1 = M8, prover.rs:229: this rank's partial sum, then the sum over the ranks (all-gather + local adds, like phase 1)
-    {
-        struct Rec3 {
-            uint64_t xy[sizeof(Affine<C>) / 8];
-            uint64_t inf;
-        } mine3;
-        int inf_l = 1;
-        // (Two half-length pipelines with a bucket set each lost 0.6 ms per rank at N = 8: profiles/r03_n_*; chunks of pairs sorted
-        // under the accumulation into ONE bucket set lost on one GPU: profiles/r04_chunked_sort_overlap_negative.txt.)
-        PM_TRY(msm_resident<C>(ctx, pk, 2, qv, mine3.xy, &inf_l));
-        hp.mark("expand+msm_d");
-        if (!h_rem->is_zero()) return phase_end.ok(PM_ERR_REMAINDER_NONZERO);   // prover.rs:221 -- H_0 is the same value on every rank
-        mine3.inf = (uint64_t)inf_l;
-        std::vector<Rec3> all3(N);
-        PM_TRY(comm_status(ctx, ctx->comm->all_gather(&mine3, all3.data(), sizeof(Rec3), st), "all_gather"));
-        std::vector<uint64_t> pts((size_t)N * (sizeof(Affine<C>) / 8));
-        std::vector<int> infs(N);
-        for (uint32_t r = 0; r < N; ++r) {
-            memcpy(&pts[r * (sizeof(Affine<C>) / 8)], all3[r].xy, sizeof(Affine<C>));
-            infs[r] = (int)all3[r].inf;
-        }
-        hp.mark("exchange_d");
-        PM_TRY(pm_g1_sum(C::ID, pts.data(), infs.data(), N, d_xy, d_inf));
-        hp.mark("sum");
-    }
-    t_phase.stop();
-    timing_flush(ctx);
+    // [d]_1 = M8, prover.rs:229: this rank's partial sum, then the sum over the ranks
+    // (Two half-length pipelines with a bucket set each lost 0.6 ms per rank at N = 8: profiles/r03_n_*; chunks of pairs sorted
+    // under the accumulation into ONE bucket set lost on one GPU: profiles/r04_chunked_sort_overlap_negative.txt.)
+    RankPoint<C> mine{};
+    std::vector<uint8_t> all;
+    int inf_l = 1;
+    PM_TRY(msm_resident<C>(ctx, pk, 2, qv, mine.xy, &inf_l));
+    hp.mark("expand+msm_d");
+    if (!h_rem->is_zero()) return phase_end.ok(PM_ERR_REMAINDER_NONZERO);   // prover.rs:221 -- H_0 is the same value on every rank
+    mine.inf = (uint32_t)inf_l;
+    PM_TRY(gather_ranks<C>(ctx, &mine, sizeof(mine), all));
+    hp.mark("exchange_d");
+    PM_TRY(sum_over_ranks<C>(all, sizeof(mine), 0, d_xy, d_inf));
+    hp.mark("sum");
+    timers.done();
     PM_TRY(comm_alive(ctx));
     ctx->phase = 3;
     return phase_end.ok(PM_OK);

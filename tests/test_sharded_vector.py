@@ -834,6 +834,80 @@ def test_vector_sharded_tiny_domains_and_ragged_shapes(curve):
         ref_pk.free()
 
 
+def _segment_starts(n, N, max_seg):
+    """The first index of every sub-segment of every rank: quotient_segments of polymath_amd/host/layout.hpp, cut points only.
+    A mirror, not a binding: a change to the segment rules of layout.hpp must be repeated here."""
+    s, m, B = n + 3, n // N, n // N // N
+    starts = set()
+
+    def filler(lo, hi):
+        for q in range(N):
+            starts.update(range(lo + (hi - lo) * q // N, lo + (hi - lo) * (q + 1) // N, max_seg))
+
+    def blocks(base, limit, extend_last):
+        for k in range(0, n, B):                                      # block (k1, q) starts at k1 m + q B: every multiple of B
+            cnt = min(B + (1 if extend_last and k + B == n else 0), limit - k)
+            starts.update(range(base + k, base + k + cnt, max_seg))
+    filler(0, 3 * s)
+    blocks(3 * s, n, False)
+    filler(3 * s + n, 5 * s)
+    blocks(5 * s, n + 1, True)
+    filler(5 * s + n + 1, 8 * s)
+    blocks(8 * s, n, False)
+    blocks(8 * s + n, n - 1, False)
+    return starts
+
+
+@pytest.mark.gpu
+def test_vector_sharded_numerator_constants_at_segment_and_lane_edges():
+    """The numerator's constants (indices 0, 1, 2 sigma .. 2 sigma + 2 and 5 sigma) as the first or last index of a sub-segment and of
+    a lane's span: sub-segments of 2, 4, 8, 16 indices (PM_OPT_MAX_SEG_LOG = 1 .. 4) on n = 32 (9 gates) and n = 8 (the dummy circuit),
+    2 ranks, bn254.  With 512 lanes per segment every lane owns ONE index, so every constant is the first and the last index of a
+    lane; the cut points of the sub-segments are checked below on the layout itself.  Every rank's proof equals the unsharded proof
+    of the same library, and one flipped witness limb is PM_ERR_REMAINDER_NONZERO on every rank with the communicators intact."""
+    from polymath_amd import circuits as PC
+    from polymath_amd.polymath import Field, LimbCircuit, Polymath, PolymathProverError, _csr
+    curve, N = "bn254", 2
+    c = CURVES[curve]
+    f = Field(curve)
+    g = PC.SplitMix64(0xC0457)
+    pm0 = Polymath(curve, "merlin", device=0)
+
+    def limb_circuit(r1cs, inst, wit):
+        return LimbCircuit(f, r1cs.m0, r1cs.mw, r1cs.nr, (_csr(f, r1cs.a), _csr(f, r1cs.b), _csr(f, r1cs.c)), f.fr_limbs(inst), f.fr_limbs(wit))
+    # (circuit, n, the witness whose flip breaks a gate: the output of gate 0 / the factor a)
+    cases = [(limb_circuit(*PC.synthetic_r1cs(c.r, 9)), 32, 2), (limb_circuit(*pm0._synthesize(PC.DummyCircuit(g.fr(c.r), g.fr(c.r)))), 8, 0)]
+    for lc, n, flip in cases:
+        x, z, r_a = g.fr(c.r), g.fr(c.r), [g.fr(c.r), g.fr(c.r)]
+        ref_pk = pm0.setup(lc, x, z)
+        assert ref_pk.n == n
+        ref = pm0.prove_native(ref_pk, lc.inst_limbs, lc.wit_limbs, r_a)
+        ref_pk.free()
+        bad = lc.wit_limbs.copy()
+        bad[flip, 0] ^= np.uint64(1)
+        sigma = n + 3
+        cuts = {k: _segment_starts(n, N, 1 << k) for k in (1, 2, 3, 4)}
+        # over the sweep as a whole (not for every k): some sub-segment size cuts the triple 2 sigma .. 2 sigma + 2 in two, some size
+        # leaves it whole in the interior of one sub-segment; every size cuts at 5 sigma and at 0
+        assert any(cuts[k] & {2 * sigma + 1, 2 * sigma + 2} for k in cuts), (n, "no cut inside the triple")
+        assert any(not cuts[k] & {2 * sigma, 2 * sigma + 1, 2 * sigma + 2, 2 * sigma + 3} for k in cuts), (n, "the triple is never interior")
+        assert all(5 * sigma in cuts[k] and 0 in cuts[k] for k in cuts)
+        for k in cuts:
+            pms, pks, comms, proofs = _sharded_proofs(curve, lc, x, z, r_a, N, options={"max_seg_log": k})
+            assert all(p == ref for p in proofs), (n, k)
+
+            def prove_bad(r):
+                try:
+                    pms[r].prove_native(pks[r], lc.inst_limbs, bad, r_a)
+                except PolymathProverError as e:
+                    return e.status
+                return 0
+            assert _run_ranks(N, prove_bad, comms) == [4] * N, (n, k)             # PM_ERR_REMAINDER_NONZERO
+            assert not any(cm.failed for cm in comms)
+            for pk in pks:
+                pk.free()
+
+
 @pytest.mark.gpu
 def test_vector_sharded_keys_loaded_from_an_existing_key():
     """pm_pk_load_sharded(layout = PM_SHARD_VECTOR): every rank uploads only ITS pieces of an existing ProvingKey given in
