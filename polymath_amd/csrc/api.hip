@@ -853,8 +853,7 @@ static int pk_load_bytes_impl(pm_ctx *ctx, const uint8_t *bytes, size_t len, int
     // only after the decode that read it has finished (its event is recorded behind the kernel), whatever way the runtime moves
     // the copy.  Refused points lower a per-vector slot; nothing is read back until the whole resident set is decoded.
     const size_t CH = wire_chunk(ctx);
-    DevBuf d_in[2], d_bad;
-    struct Release { DevBuf *a; DevBuf &b; ~Release() { a[0].release(); a[1].release(); b.release(); } } release{d_in, d_bad};
+    ScopedDevBuf d_in[2], d_bad;
     PinnedPair pin;
     if (d_in[0].reserve(CH * NB) != hipSuccess || d_in[1].reserve(CH * NB) != hipSuccess || d_bad.reserve(PM_NUM_BASE_VECS * 8) != hipSuccess)
         return fail(PM_ERR_HIP, "out of device memory for the staging buffers");
@@ -887,8 +886,7 @@ static int pk_load_bytes_impl(pm_ctx *ctx, const uint8_t *bytes, size_t len, int
         if (h_bad[v] != ~0ull)
             return fail(PM_ERR_INVALID_ARG, std::string(BASE_VEC_NAMES[v]) + "[" + std::to_string(h_bad[v] >> 8) + "]: " +
                                                 g1_status_text(C::ID, (int)(h_bad[v] & 0xFF)));
-    d_in[0].release();
-    d_in[1].release();
+    for (ScopedDevBuf &b : d_in) b.release();   // before the tables: they want the memory
     st = pk_build_tables<C>(ctx, pk);
     if (st) return fail(st, "");
     *out = pk;
@@ -913,8 +911,7 @@ extern "C" int pm_pk_load_bytes(pm_ctx *ctx, int curve, const uint8_t *bytes, si
 template <class C>
 static int g1_decode_impl(pm_ctx *ctx, const uint8_t *in, size_t count, int validate, uint64_t *out_xy, uint8_t *status) {
     const size_t NB = 4 * C::FqP::N, CH = wire_chunk(ctx);
-    DevBuf d_in, d_out, d_st;
-    struct Release { DevBuf &a, &b, &c; ~Release() { a.release(); b.release(); c.release(); } } release{d_in, d_out, d_st};
+    ScopedDevBuf d_in, d_out, d_st;
     const size_t first = std::min(count, CH);
     PM_HIP(ctx, d_in.reserve(first * NB));
     PM_HIP(ctx, d_out.reserve(first * sizeof(Affine<C>)));
@@ -970,8 +967,7 @@ static int pk_generate_impl(pm_ctx *ctx, uint64_t m0, uint64_t mw, uint64_t nr, 
     Fr zh = sub<P>(xn, one);                                                       // :106
     // uj_wj_lcs scalars (generator.rs:112-136) on the device: Lagrange coefficients at x by chunked batch inversion, the sparse pass
     // over the CSR matrices already uploaded above (setup.hip: lcs_scalars).  Rounds 1-3 ran both on <= 32 host threads.
-    DevBuf d_lagrange, d_work, d_lcs_buf;
-    struct Release { DevBuf &a, &b, &c; ~Release() { a.release(); b.release(); c.release(); } } release_lcs{d_lagrange, d_work, d_lcs_buf};
+    ScopedDevBuf d_lagrange, d_work, d_lcs_buf;
     {
         if (hipMalloc(&d_lcs_buf.p, (Lz ? Lz : 1) * sizeof(Fr)) != hipSuccess) { ctx->err = "out of device memory for the lcs scalars"; return guard(PM_ERR_HIP); }
         d_lcs_buf.bytes = (Lz ? Lz : 1) * sizeof(Fr);

@@ -39,26 +39,12 @@ __global__ __launch_bounds__(CHALLENGE_BLOCK) void k_verifier_challenges(fs::FsV
     if (out.x2) out.x2[i] = ch.x2;
     if (out.c_at_x1) out.c_at_x1[i] = ch.c_at_x1;
     if (out.scalars) {
-        // verify_batch.hip's host glue: rho x2, rho x1 canonical, g = rho (a(x1) + x2 c(x1)); a row that is not ok takes no part
+        // the glue the host mode runs too (verify_batch.cuh: verify_weigh); a row that is not ok, or with a refused point, takes no part
         VerifyScalars sc = out.scalars[i];
-        Fr rho = Fr::zero();
-#pragma unroll
-        for (int k = 0; k < 4; ++k) rho.l[k] = sc.rho[k];
-        rho = to_mont<P>(rho);
-        const Fr rx2 = from_mont<P>(mul<P>(rho, ch.x2)), rx1 = from_mont<P>(mul<P>(rho, ch.x1));
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { sc.rx2[k] = rx2.l[k]; sc.rx1[k] = rx1.l[k]; }
-        Fr g = mul<P>(rho, add<P>(a_at, mul<P>(ch.x2, ch.c_at_x1)));
         const uint8_t *st = rows.d_point_status;
-        if (!ok || (st && (st[3 * i] | st[3 * i + 1] | st[3 * i + 2]))) {   // no weight: the row never enters a sum
-#pragma unroll
-            for (int k = 0; k < 4; ++k) sc.rho[k] = 0;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) sc.rx2[k] = sc.rx1[k] = 0;
-            g = Fr::zero();
-        }
+        const bool live = ok && !(st && (st[3 * i] | st[3 * i + 1] | st[3 * i + 2]));
+        out.g[i] = verify_weigh<C>(sc, ch.x1, ch.x2, ch.c_at_x1, a_at, live);
         out.scalars[i] = sc;
-        out.g[i] = g;
     }
 }
 

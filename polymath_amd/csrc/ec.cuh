@@ -116,6 +116,24 @@ PM_HD_COLD XYZZ<C> xyzz_add(const XYZZ<C> &a, const XYZZ<C> &b) {
     return r;
 }
 
+// [k] P by binary double-and-add, top bit first.  k: nwords canonical little-endian 32-bit words.  P = O and k = 0 both give the
+// identity.  THE scalar multiplication of the verifiers and of their tests; msm.hip: host_horner is a different loop.
+template <class C>
+PM_HD XYZZ<C> xyzz_mul_words(const Affine<C> &P, const uint32_t *k, int nwords) {
+    XYZZ<C> acc = XYZZ<C>::identity();
+    if (P.is_inf()) return acc;
+#pragma unroll 1
+    for (int i = nwords - 1; i >= 0; --i) {
+        const uint32_t word = k[i];
+#pragma unroll 1
+        for (int b = 31; b >= 0; --b) {
+            acc = xyzz_dbl<C>(acc);
+            if ((word >> b) & 1u) xyzz_madd<C>(acc, P, false);
+        }
+    }
+    return acc;
+}
+
 // XYZZ -> affine (one Fermat inversion: x = X/ZZ, y = Y/ZZZ; 1/ZZ = (ZZ/ZZZ)^2 ... computed as
 // i = 1/ZZZ, 1/ZZ = (i * ZZ)^2 since ZZ^3 = ZZZ^2  =>  (ZZ/ZZZ)^2 = ZZ^2/ZZ^3 = 1/ZZ).
 template <class C>

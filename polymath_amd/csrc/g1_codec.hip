@@ -58,18 +58,7 @@ __device__ Fp<P> fq_pow_p1_4(const Fp<P> &a) {
 // [r] P == O (g1_in_subgroup of wire.hpp, the same double-and-add over the bits of r): P affine, Montgomery, not infinity
 template <class C>
 __device__ bool g1_r_torsion(const Affine<C> &p) {
-    typedef typename C::FrP R;
-    XYZZ<C> acc = XYZZ<C>::identity();
-#pragma unroll 1
-    for (int i = R::N - 1; i >= 0; --i) {
-        const uint32_t e = R::MOD[i];
-#pragma unroll 1
-        for (int b = 31; b >= 0; --b) {
-            acc = xyzz_dbl<C>(acc);
-            if ((e >> b) & 1u) xyzz_madd<C>(acc, p, false);
-        }
-    }
-    return acc.is_identity();
+    return xyzz_mul_words<C>(p, C::FrP::MOD, C::FrP::N).is_identity();
 }
 
 template <class C>

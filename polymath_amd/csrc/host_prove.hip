@@ -363,9 +363,7 @@ template <class C, class T>
 int verify_impl(const uint8_t *vk_bytes, size_t vk_len, const uint64_t *inputs, size_t n_inputs, const uint8_t *proof_bytes, size_t proof_len,
                 int *accepted) {
     typedef typename pmhost::FrOps<C>::Fr Fr;
-    pmhost::Reader rd(vk_bytes, vk_len);
-    const pmhost::VerifyingKeyT<C> vk = pmhost::read_vk_c<C>(rd);
-    if (rd.off != vk_len) return PM_ERR_INVALID_ARG;
+    const pmhost::VerifyingKeyT<C> vk = pmhost::read_vk_exact<C>(vk_bytes, vk_len);
     const pmhost::Proof<C> proof = pmhost::read_proof<C>(proof_bytes, proof_len);
     std::vector<Fr> pub(n_inputs);
     if (n_inputs) memcpy((void *)pub.data(), inputs, n_inputs * sizeof(Fr));

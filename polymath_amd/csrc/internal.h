@@ -92,6 +92,15 @@ struct DevBuf {
     T *as() const { return (T *)p; }
 };
 
+// A DevBuf that lives for one call: released on every way out of its scope.  DevBuf itself has no destructor because the context's
+// workspaces (pm_ctx, pm_pk, pm_bases) release explicitly; every call-scoped buffer is one of these.
+struct ScopedDevBuf : DevBuf {
+    ScopedDevBuf() = default;
+    ScopedDevBuf(const ScopedDevBuf &) = delete;
+    void operator=(const ScopedDevBuf &) = delete;
+    ~ScopedDevBuf() { release(); }
+};
+
 enum TimingSlot {
     T_WITNESS_MAP = 0,
     T_NTT = 1,
@@ -101,7 +110,16 @@ enum TimingSlot {
     T_MSM_REDUCE = 5,
     T_MSM_TOTAL = 6,
     T_PHASE = 7,
-    T_NUM_SLOTS = 8
+    T_NUM_SLOTS = 8,
+    // the batch verifier's names for the same slots (api.py: VERIFY_TIMING_SLOTS)
+    TV_DECODE = T_WITNESS_MAP,
+    TV_TERMS = T_NTT,
+    TV_TREE = T_POLY,
+    TV_HOST_GLUE = T_MSM_SORT,             // wall ms of the host's part of the challenges stage
+    TV_PAIRING_HOST = T_MSM_ACCUMULATE,    // wall ms of the pairing stage
+    TV_PAIRING_KERNELS = T_MSM_REDUCE,
+    TV_CHALLENGE_KERNEL = T_MSM_TOTAL,
+    TV_DEVICE_TOTAL = T_PHASE
 };
 
 // What one bucket pipeline hands from its sort to its accumulation and from there to the reduction.
@@ -483,12 +501,12 @@ const char *g1_status_text(int curve, int status);
 
 // pairing_batch.hip: checks  prod_j e(P[i][j], Q_j) == 1  against k <= 4 fixed G2 points, one lane per check.  pairing_prepare walks the
 // Miller loop of each Q_j on the host (g2: k x 4 Fq, x.c0 || x.c1 || y.c0 || y.c1; bit j of `pairs` clear: Q_j = O, the pair is left out
-// and its words are not read; a point off the twist is PM_ERR_INVALID_ARG) and uploads the line tables; the caller releases buf.
+// and its words are not read; a point off the twist is PM_ERR_INVALID_ARG) and uploads the line tables, which live as long as `out`.
 // pairing_check_launch enqueues ONE launch of `count` lanes on the context's stream: lane i takes its k points from d_pts[i k ..], or,
 // with d_terms (k == 3), from node i of the batch verifier's sum tree as U_i + neg_g_i G, -V_i, W_i (d_neg_g: 8 canonical words a
 // lane; d_live: optional, a zero byte leaves the lane out).  d_is_one: one byte 0 / 1 per lane.  GPU ms go to timing_slot.
 struct PairingPrepared {
-    DevBuf buf;
+    ScopedDevBuf buf;
     size_t consts_offset = 0;
     int k = 0;
     unsigned pairs = 0;
@@ -533,7 +551,7 @@ template <class C>
 int pk_wire_parse(const uint8_t *data, size_t len, WireLayout &out, std::string &err);
 
 // setup.hip: the uj_wj_lcs scalars of generator.rs:112-136 on the device (Lagrange coefficients at x + the sparse pass over the
-// key's CSR matrices); `lagrange` and `work` are scratch the caller releases
+// key's CSR matrices); `lagrange` and `work` are the caller's scratch
 template <class C>
 int lcs_scalars(pm_ctx *ctx, const pm_pk *pk, const Fp<typename C::FrP> &x, const Fp<typename C::FrP> &omega, const Fp<typename C::FrP> &kscale,
                 const Fp<typename C::FrP> &y_gamma, const Fp<typename C::FrP> &y_to_minus_alpha, DevBuf &lagrange, DevBuf &work,

@@ -21,30 +21,12 @@ template <class C>
 __global__ __launch_bounds__(64) void k_pairing_check(const typename Tower<C>::Line *tab, const typename Tower<C>::Consts *consts, int k, unsigned pairs,
                                                       const Affine<C> *pts, const VerifyTerm<C> *terms, const uint32_t *neg_g, const uint8_t *live,
                                                       Affine<C> G, size_t count, uint8_t *is_one) {
-    typedef typename C::FqP Q;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     Affine<C> P[PAIRING_MAX_PAIRS];
     if (terms) {                                                // k == 3: e(U - g G, [z]_2) e(-V, [x]_2) e(W, [1]_2)
         if (live && !live[i]) { is_one[i] = 0; return; }
-        XYZZ<C> lhs = terms[i].U;
-        if (!G.is_inf()) {
-            XYZZ<C> acc = XYZZ<C>::identity();
-#pragma unroll 1
-            for (int w = 7; w >= 0; --w) {
-                const uint32_t word = neg_g[8 * i + w];
-#pragma unroll 1
-                for (int b = 31; b >= 0; --b) {
-                    acc = xyzz_dbl<C>(acc);
-                    if ((word >> b) & 1u) xyzz_madd<C>(acc, G, false);
-                }
-            }
-            lhs = xyzz_add<C>(lhs, acc);
-        }
-        P[0] = xyzz_to_affine<C>(lhs);
-        P[1] = xyzz_to_affine<C>(terms[i].V);
-        P[1].y = neg<Q>(P[1].y);
-        P[2] = xyzz_to_affine<C>(terms[i].W);
+        verify_node_points<C>(terms[i], neg_g + 8 * i, G, P);
         P[3] = Affine<C>::infinity();
     } else {
 #pragma unroll 1
@@ -108,32 +90,27 @@ using namespace pm;
 
 constexpr size_t PAIRING_MAX_COUNT = (size_t)1 << 22;
 
-struct CheckBufs {   // the call's device memory: released on every way out
-    PairingPrepared prep;
-    DevBuf pts, out;
-    ~CheckBufs() { prep.buf.release(); pts.release(); out.release(); }
-};
-
 template <class C>
 int pairing_check_batch_impl(pm_ctx *ctx, const uint64_t *g2, size_t k, const void *g1, size_t stride, size_t count, uint8_t *is_one) {
     const size_t PT = sizeof(Affine<C>);
     if (stride < PT) return PM_ERR_INVALID_ARG;
     PM_HIP(ctx, hipSetDevice(ctx->device));
-    CheckBufs d;
+    PairingPrepared prep;
+    ScopedDevBuf d_pts, d_out;
     TimingGuard flush{ctx};
     timing_reset(ctx);
-    PM_TRY(pairing_prepare<C>(ctx, (const uint32_t *)g2, (int)k, (1u << k) - 1u, &d.prep));
+    PM_TRY(pairing_prepare<C>(ctx, (const uint32_t *)g2, (int)k, (1u << k) - 1u, &prep));
     std::vector<Affine<C>> pts(count * k);
     const uint8_t *s = (const uint8_t *)g1;
     for (size_t i = 0; i < count * k; ++i) {
         memcpy((void *)&pts[i], s + i * stride, PT);
         if (stride > PT && s[i * stride + PT] != 0) pts[i] = Affine<C>::infinity();   // arkworks' `infinity: bool`
     }
-    PM_HIP(ctx, d.pts.reserve(pts.size() * PT));
-    PM_HIP(ctx, d.out.reserve(count));
-    PM_HIP(ctx, hipMemcpyAsync(d.pts.p, pts.data(), pts.size() * PT, hipMemcpyHostToDevice, ctx->stream));
-    PM_TRY(pairing_check_launch<C>(ctx, d.prep, d.pts.as<Affine<C>>(), nullptr, nullptr, nullptr, Affine<C>::infinity(), count, d.out.as<uint8_t>(), T_PHASE));
-    PM_HIP(ctx, hipMemcpyAsync(is_one, d.out.p, count, hipMemcpyDeviceToHost, ctx->stream));
+    PM_HIP(ctx, d_pts.reserve(pts.size() * PT));
+    PM_HIP(ctx, d_out.reserve(count));
+    PM_HIP(ctx, hipMemcpyAsync(d_pts.p, pts.data(), pts.size() * PT, hipMemcpyHostToDevice, ctx->stream));
+    PM_TRY(pairing_check_launch<C>(ctx, prep, d_pts.as<Affine<C>>(), nullptr, nullptr, nullptr, Affine<C>::infinity(), count, d_out.as<uint8_t>(), T_PHASE));
+    PM_HIP(ctx, hipMemcpyAsync(is_one, d_out.p, count, hipMemcpyDeviceToHost, ctx->stream));
     PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PM_OK;
 }

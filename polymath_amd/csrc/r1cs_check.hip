@@ -104,13 +104,6 @@ __global__ __launch_bounds__(256) void k_r1cs_residuals(CsrDev A, CsrDev B, CsrD
 
 namespace {
 
-struct CheckBufs {   // the call's device memory: released on every way out
-    DevBuf x, w, mask, n_bad, rows, abc;
-    ~CheckBufs() {
-        x.release(); w.release(); mask.release(); n_bad.release(); rows.release(); abc.release();
-    }
-};
-
 // With `solve` (PM_ASSIGNMENT_SOLVE) the unknown entries are computed first (solve.hip) and the check reads the completed rows.
 // Assignments run in GROUPS of as many as keep group * (m0 + mw) inside one MSM piece (the knob pm_host_prove_batch sizes its groups
 // by), at least one, at most 65 535 (grid y).  Host assignments are uploaded group by group; device assignments are read where they
@@ -128,7 +121,7 @@ int r1cs_check_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *
     if (group > 65535) group = 65535;
     if (group > count) group = count;
     hipStream_t st = ctx->stream;
-    CheckBufs d;
+    ScopedDevBuf d_x, d_w, d_mask, d_n_bad, d_rows, d_abc;   // the call's device memory
     TimingGuard timing_guard{ctx};
     timing_reset(ctx);
     uint64_t xs = m0, ws = mw;
@@ -142,13 +135,13 @@ int r1cs_check_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *
         on_device = true;
     }
     if (!on_device) {
-        PM_HIP(ctx, d.x.reserve(group * m0 * sizeof(Fr)));
-        if (mw) PM_HIP(ctx, d.w.reserve(group * mw * sizeof(Fr)));
+        PM_HIP(ctx, d_x.reserve(group * m0 * sizeof(Fr)));
+        if (mw) PM_HIP(ctx, d_w.reserve(group * mw * sizeof(Fr)));
     }
-    if (words) PM_HIP(ctx, d.mask.reserve(group * words * sizeof(unsigned long long)));
-    PM_HIP(ctx, d.n_bad.reserve(group * sizeof(uint64_t)));
-    if (listed) PM_HIP(ctx, d.rows.reserve(group * listed * sizeof(uint64_t)));
-    if (listed && abc) PM_HIP(ctx, d.abc.reserve(group * listed * 3 * sizeof(Fr)));
+    if (words) PM_HIP(ctx, d_mask.reserve(group * words * sizeof(unsigned long long)));
+    PM_HIP(ctx, d_n_bad.reserve(group * sizeof(uint64_t)));
+    if (listed) PM_HIP(ctx, d_rows.reserve(group * listed * sizeof(uint64_t)));
+    if (listed && abc) PM_HIP(ctx, d_abc.reserve(group * listed * 3 * sizeof(Fr)));
     std::vector<uint64_t> h_rows(group * listed), h_abc(abc ? group * listed * 12 : 0);
     const CsrDev A{pk->d_rowptr[0], pk->d_col[0], pk->d_val[0]}, B{pk->d_rowptr[1], pk->d_col[1], pk->d_val[1]},
         Cm{pk->d_rowptr[2], pk->d_col[2], pk->d_val[2]};
@@ -156,27 +149,27 @@ int r1cs_check_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *
         const size_t g = count - g0 < group ? count - g0 : group;
         const Fr *gx = (const Fr *)x + g0 * xs, *gw = mw ? (const Fr *)w + g0 * ws : nullptr;
         if (!on_device) {
-            PM_HIP(ctx, hipMemcpyAsync(d.x.p, gx, g * m0 * sizeof(Fr), hipMemcpyHostToDevice, st));
-            if (mw) PM_HIP(ctx, hipMemcpyAsync(d.w.p, gw, g * mw * sizeof(Fr), hipMemcpyHostToDevice, st));
-            gx = d.x.as<Fr>();
-            gw = d.w.as<Fr>();
+            PM_HIP(ctx, hipMemcpyAsync(d_x.p, gx, g * m0 * sizeof(Fr), hipMemcpyHostToDevice, st));
+            if (mw) PM_HIP(ctx, hipMemcpyAsync(d_w.p, gw, g * mw * sizeof(Fr), hipMemcpyHostToDevice, st));
+            gx = d_x.as<Fr>();
+            gw = d_w.as<Fr>();
         }
         {
             StageTimer t(ctx, T_WITNESS_MAP);
             if (words) {
                 PM_LAUNCH(ctx, k_r1cs_mask<P>, dim3(nblk(nr), (unsigned)g), dim3(256), 0, st, A, B, Cm, gx, gw, m0, xs, ws, nr, words,
-                               d.mask.as<unsigned long long>());
+                               d_mask.as<unsigned long long>());
             }
-            PM_LAUNCH(ctx, k_r1cs_scan, dim3((unsigned)g), dim3(R1CS_SCAN_LANES), 0, st, d.mask.as<unsigned long long>(), words, listed,
-                           d.n_bad.as<uint64_t>(), d.rows.as<uint64_t>());
+            PM_LAUNCH(ctx, k_r1cs_scan, dim3((unsigned)g), dim3(R1CS_SCAN_LANES), 0, st, d_mask.as<unsigned long long>(), words, listed,
+                           d_n_bad.as<uint64_t>(), d_rows.as<uint64_t>());
             if (listed && abc) {
                 PM_LAUNCH(ctx, k_r1cs_residuals<P>, dim3(nblk(listed), (unsigned)g), dim3(256), 0, st, A, B, Cm, gx, gw, m0, xs, ws,
-                               d.rows.as<uint64_t>(), listed, d.abc.as<Fr>());
+                               d_rows.as<uint64_t>(), listed, d_abc.as<Fr>());
             }
         }
-        PM_HIP(ctx, hipMemcpyAsync(n_bad + g0, d.n_bad.p, g * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        if (listed) PM_HIP(ctx, hipMemcpyAsync(h_rows.data(), d.rows.p, g * listed * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        if (listed && abc) PM_HIP(ctx, hipMemcpyAsync(h_abc.data(), d.abc.p, g * listed * 3 * sizeof(Fr), hipMemcpyDeviceToHost, st));
+        PM_HIP(ctx, hipMemcpyAsync(n_bad + g0, d_n_bad.p, g * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        if (listed) PM_HIP(ctx, hipMemcpyAsync(h_rows.data(), d_rows.p, g * listed * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        if (listed && abc) PM_HIP(ctx, hipMemcpyAsync(h_abc.data(), d_abc.p, g * listed * 3 * sizeof(Fr), hipMemcpyDeviceToHost, st));
         PM_HIP(ctx, hipStreamSynchronize(st));
         for (size_t b = 0; b < g && max_rows; ++b) {
             uint64_t *out = rows + (g0 + b) * max_rows;

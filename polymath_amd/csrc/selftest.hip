@@ -60,7 +60,7 @@ static int selftest_field(pm_ctx *ctx, size_t n, uint64_t seed, uint64_t *bad) {
         a[2] = F::one();
         a[3] = pm1; b[3] = F::one();
     }
-    DevBuf da, db, dr;
+    ScopedDevBuf da, db, dr;
     PM_HIP(ctx, da.reserve(n * sizeof(F)));
     PM_HIP(ctx, db.reserve(n * sizeof(F)));
     PM_HIP(ctx, dr.reserve(6 * n * sizeof(F)));
@@ -74,9 +74,6 @@ static int selftest_field(pm_ctx *ctx, size_t n, uint64_t seed, uint64_t *bad) {
             hipMemcpyAsync(r.data(), dr.p, 6 * n * sizeof(F), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
             hipStreamSynchronize(ctx->stream) != hipSuccess) { st = PM_ERR_HIP; break; }
     } while (false);
-    da.release();
-    db.release();
-    dr.release();
     if (st) { ctx->err = "pm_selftest_field: HIP call failed"; return st; }
     uint64_t m = 0;
     for (size_t it = 0; it < n; ++it) {

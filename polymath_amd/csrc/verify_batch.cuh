@@ -92,6 +92,37 @@ PM_HD XYZZ<C> verify_tree_add(const XYZZ<C> &a_std, const XYZZ<C> &b_std) {
     return xyzz28_to_std<C>(a);
 }
 
+// The scalar glue of one proof, for the challenge lanes (challenges.hip) and for the host's threads alike.  sc.rho holds the weight
+// on entry; sc.rx2 = rho x2 and sc.rx1 = rho x1 (canonical) are filled in, and g = rho (a(x1) + x2 c(x1)) (Montgomery) comes back.
+// A row that is not live -- a(x1) not canonical, a refused point -- has no weight: an all-zero record and g = 0, it never enters a sum.
+template <class C>
+PM_HD Fp<typename C::FrP> verify_weigh(VerifyScalars &sc, const Fp<typename C::FrP> &x1, const Fp<typename C::FrP> &x2,
+                                       const Fp<typename C::FrP> &c_at_x1, const Fp<typename C::FrP> &a_at_x1, bool live) {
+    typedef typename C::FrP P;
+    typedef Fp<P> Fr;
+    Fr rho = Fr::zero();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) rho.l[k] = sc.rho[k];
+    rho = to_mont<P>(rho);
+    const Fr rx2 = from_mont<P>(mul<P>(rho, x2)), rx1 = from_mont<P>(mul<P>(rho, x1));
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { sc.rx2[k] = rx2.l[k]; sc.rx1[k] = rx1.l[k]; }
+    Fr g = mul<P>(rho, add<P>(a_at_x1, mul<P>(x2, c_at_x1)));
+    if (!live) { sc = VerifyScalars{}; g = Fr::zero(); }
+    return g;
+}
+
+// The G1 side of a tree node's equation  e(U - g G, [z]_2) e(-V, [x]_2) e(W, [1]_2) == 1:  P = {U + neg_g G, -V, W}, affine, the
+// identity as infinity.  neg_g: -g mod r in 8 canonical words.  One lane of k_pairing_check (pairing_batch.hip) or one host check.
+template <class C>
+PM_HD void verify_node_points(const VerifyTerm<C> &node, const uint32_t *neg_g, const Affine<C> &G, Affine<C> P[3]) {
+    const XYZZ<C> lhs = xyzz_add<C>(node.U, xyzz_mul_words<C>(G, neg_g, 8));   // G = O: U itself
+    P[0] = xyzz_to_affine<C>(lhs);
+    P[1] = xyzz_to_affine<C>(node.V);
+    P[1].y = neg<typename C::FqP>(P[1].y);
+    P[2] = xyzz_to_affine<C>(node.W);
+}
+
 // The tree over `padded` = 2^depth leaves lives in one array of 2 padded - 1 nodes: level l (0 = leaves) holds padded >> l nodes
 // from verify_level_offset(padded, l) on; the root is the last node.
 PM_HD size_t verify_level_offset(size_t padded, unsigned level) { return 2 * padded - (2 * padded >> level); }

@@ -434,15 +434,9 @@ public:
         const Fr &x1 = ch.x1, &x2 = ch.x2, &c_at_x1 = ch.c_at_x1;
         // commitments_minus_evals_in_g1 = a + x2 c - (a_at_x1 + x2 c_at_x1) [1]_1         :44-47
         auto smul = [](const G1Point<C> &g, const Fr &k_mont) {
-            J acc = J::identity();
-            if (g.inf) return acc;
-            Fr k = pm::from_mont<typename C::FrP>(k_mont);
-            for (int i = 7; i >= 0; --i)
-                for (int b = 31; b >= 0; --b) {
-                    acc = pm::xyzz_dbl<C>(acc);
-                    if ((k.l[i] >> b) & 1) pm::xyzz_madd<C>(acc, g.p, false);
-                }
-            return acc;
+            if (g.inf) return J::identity();
+            const Fr k = pm::from_mont<typename C::FrP>(k_mont);
+            return pm::xyzz_mul_words<C>(g.p, k.l, 8);
         };
         J lhs = J::identity();
         if (!proof.a_g1.inf) pm::xyzz_madd<C>(lhs, proof.a_g1.p, false);

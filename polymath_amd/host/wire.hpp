@@ -201,13 +201,7 @@ inline Bls12Pairing::G2 deser_g2(Reader &rd) { return deser_g2_c<pm::BlsCurve>(r
 template <class C>
 inline bool g1_in_subgroup(const G1Point<C> &g) {
     if (C::ID != 0 || g.inf) return true;
-    pm::XYZZ<C> acc = pm::XYZZ<C>::identity();
-    for (int i = C::FrP::N - 1; i >= 0; --i)
-        for (int b = 31; b >= 0; --b) {
-            acc = pm::xyzz_dbl<C>(acc);
-            if ((C::FrP::MOD[i] >> b) & 1) pm::xyzz_madd<C>(acc, g.p, false);
-        }
-    return acc.is_identity();
+    return pm::xyzz_mul_words<C>(g.p, C::FrP::MOD, C::FrP::N).is_identity();
 }
 
 // validate = ark-serialize's Validate::Yes (deserialize_compressed: on the curve AND in the prime-order subgroup); false =
@@ -281,6 +275,14 @@ inline VerifyingKeyT<C> read_vk_c(Reader &rd) {
     vk.m0 = rd.u64();
     vk.sigma = rd.u64();
     vk.omega = FrOps<C>::from_le_bytes_canonical(rd.take(32));
+    return vk;
+}
+// a byte string that is one vk and nothing else: trailing bytes are refused like any other malformed key
+template <class C>
+inline VerifyingKeyT<C> read_vk_exact(const uint8_t *bytes, size_t len) {
+    Reader rd(bytes, len);
+    const VerifyingKeyT<C> vk = read_vk_c<C>(rd);
+    if (rd.off != len) throw WireError("trailing bytes after the verifying key");
     return vk;
 }
 inline void ser_vk(const VerifyingKey &vk, Bytes &out) { ser_vk_c<pm::BlsCurve>(vk, out); }

@@ -27,9 +27,7 @@ int main() {
         pm::Affine<pm::BlsCurve> g1;
         for (int i = 0; i < 12; ++i) { g1.x.l[i] = pm::BlsCurve::GX_MONT[i]; g1.y.l[i] = pm::BlsCurve::GY_MONT[i]; }
         auto g1mul = [&](uint32_t k) {
-            pm::XYZZ<pm::BlsCurve> acc = pm::XYZZ<pm::BlsCurve>::identity();
-            for (int b = 31; b >= 0; --b) { acc = pm::xyzz_dbl<pm::BlsCurve>(acc); if ((k >> b) & 1) pm::xyzz_madd<pm::BlsCurve>(acc, g1, false); }
-            return pm::xyzz_to_affine<pm::BlsCurve>(acc);
+            return pm::xyzz_to_affine<pm::BlsCurve>(pm::xyzz_mul_words<pm::BlsCurve>(g1, &k, 1));
         };
         uint32_t a = 0x1234567u, b = 0x89abcdu, ab_lo, ab_hi;
         uint64_t ab = (uint64_t)a * b;
@@ -59,9 +57,7 @@ int main() {
         pm::Affine<CC> g1;
         for (int i = 0; i < 8; ++i) { g1.x.l[i] = CC::GX_MONT[i]; g1.y.l[i] = CC::GY_MONT[i]; }
         auto g1mul = [&](uint32_t k) {
-            pm::XYZZ<CC> acc = pm::XYZZ<CC>::identity();
-            for (int b = 31; b >= 0; --b) { acc = pm::xyzz_dbl<CC>(acc); if ((k >> b) & 1) pm::xyzz_madd<CC>(acc, g1, false); }
-            return pm::xyzz_to_affine<CC>(acc);
+            return pm::xyzz_to_affine<CC>(pm::xyzz_mul_words<CC>(g1, &k, 1));
         };
         uint32_t a = 0x1234567u, b = 0x89abcdu;
         uint64_t ab = (uint64_t)a * b;

@@ -50,13 +50,7 @@ struct Suite {
     }
     static Affine<C> g1_mul(const Affine<C> &p, const Fr &k_mont) {
         const Fr k = from_mont<R>(k_mont);
-        XYZZ<C> acc = XYZZ<C>::identity();
-        for (int i = R::N - 1; i >= 0; --i)
-            for (int b = 31; b >= 0; --b) {
-                acc = xyzz_dbl<C>(acc);
-                if ((k.l[i] >> b) & 1) xyzz_madd<C>(acc, p, false);
-            }
-        return xyzz_to_affine<C>(acc);
+        return xyzz_to_affine<C>(xyzz_mul_words<C>(p, k.l, R::N));
     }
     static typename Host::G2 g2_mul(const typename Host::G2 &p, const Fr &k_mont) {
         const Fr k = from_mont<R>(k_mont);

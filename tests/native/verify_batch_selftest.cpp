@@ -1,5 +1,7 @@
 // Host build of the batch verifier's device functions (csrc/verify_batch.cuh: verify_term, verify_tree_add -- PM_HD, plain C++
-// here) against the dense double-and-add of Polymath::verify (ec.cuh: xyzz_dbl / xyzz_madd).  Built and run by
+// here) against the dense double-and-add of Polymath::verify (ec.cuh: xyzz_mul_words); that double-and-add against repeated
+// addition; and the two pieces the host and the lanes share, verify_weigh and verify_node_points, against scalar arithmetic mod r
+// done by shift-and-add on canonical words (no Montgomery form).  Built and run by
 // tests/test_native_verify_batch.py (CPU, no GPU).  Prints "<curve>: <failures> failures of <checks>".
 #include <cstdio>
 #include <cstdlib>
@@ -52,16 +54,30 @@ struct Suite {
         return g;
     }
     // the dense path: smul of Polymath::verify
-    static XYZZ<C> smul(const Affine<C> &p, const Scalar &k) {
-        XYZZ<C> acc = XYZZ<C>::identity();
-        if (p.is_inf()) return acc;
+    static XYZZ<C> smul(const Affine<C> &p, const Scalar &k) { return xyzz_mul_words<C>(p, k.w, 8); }
+    // a + b mod r and a b mod r on canonical words, by carry and by shift-and-add: independent of the Montgomery code under test
+    static Scalar add_mod(const Scalar &a, const Scalar &b) {
+        uint32_t t[9], d[9];
+        uint64_t c = 0;
+        for (int i = 0; i < 8; ++i) { c += (uint64_t)a.w[i] + b.w[i]; t[i] = (uint32_t)c; c >>= 32; }
+        t[8] = (uint32_t)c;
+        int64_t br = 0;
+        for (int i = 0; i < 9; ++i) { br += (int64_t)t[i] - (i < 8 ? R::MOD[i] : 0u); d[i] = (uint32_t)br; br >>= 32; }
+        Scalar s;
+        for (int i = 0; i < 8; ++i) s.w[i] = br < 0 ? t[i] : d[i];
+        return s;
+    }
+    static Scalar mul_plain(const Scalar &a, const Scalar &b) {
+        Scalar acc = small(0);
         for (int i = 7; i >= 0; --i)
-            for (int b = 31; b >= 0; --b) {
-                acc = xyzz_dbl<C>(acc);
-                if ((k.w[i] >> b) & 1) xyzz_madd<C>(acc, p, false);
+            for (int bit = 31; bit >= 0; --bit) {
+                acc = add_mod(acc, acc);
+                if ((b.w[i] >> bit) & 1) acc = add_mod(acc, a);
             }
         return acc;
     }
+    static Scalar negated_mod(const Scalar &a) { return mul_plain(a, r_minus_1()); }
+    static Fr mont(const Scalar &a) { Fr x; memcpy(x.l, a.w, 32); return to_mont<R>(x); }
     static Affine<C> rand_point() { return xyzz_to_affine<C>(smul(generator(), rand_scalar())); }
     static Affine<C> negated(Affine<C> p) { p.y = neg<Q>(p.y); return p; }
 
@@ -136,7 +152,64 @@ struct Suite {
         same(root.W, sum.W, what, "W");
     }
 
+    void expect(bool ok, const char *what) {
+        ++checks;
+        if (!ok) { ++fails; printf("%s: %s\n", name, what); }
+    }
+
+    // xyzz_mul_words against repeated addition: k = 0 .. 9, r - 1 (one more addition closes the group), P = O
+    void mul_words_cases() {
+        const Affine<C> P = rand_point(), O = Affine<C>::infinity();
+        XYZZ<C> sum = XYZZ<C>::identity();
+        for (uint32_t k = 0; k < 10; ++k) {
+            same(smul(P, small(k)), sum, "xyzz_mul_words: k P against k additions", "point");
+            sum = xyzz_add<C>(sum, XYZZ<C>::from_affine(P));
+        }
+        const XYZZ<C> m = smul(P, r_minus_1());
+        same(m, XYZZ<C>::from_affine(negated(P)), "xyzz_mul_words: (r - 1) P", "-P");
+        expect(xyzz_add<C>(m, XYZZ<C>::from_affine(P)).is_identity(), "xyzz_mul_words: (r - 1) P + P is not O");
+        expect(smul(O, rand_scalar()).is_identity() && smul(O, small(0)).is_identity(), "xyzz_mul_words: k O is not O");
+        const uint32_t one_word = 0x80000001u;
+        Scalar wide = small(one_word);
+        same(xyzz_mul_words<C>(P, &one_word, 1), smul(P, wide), "xyzz_mul_words: one word against eight", "point");
+    }
+
+    // verify_weigh: rho x2, rho x1 canonical and g = rho (a + x2 c) as Polymath::verifier_challenges' caller needs them
+    void weigh_case(const char *what, const Scalar &rho, const Scalar &x1, const Scalar &x2, const Scalar &c_at, const Scalar &a_at, bool live) {
+        VerifyScalars sc;
+        memset(&sc, 0xA5, sizeof sc);
+        memcpy(sc.rho, rho.w, 16);
+        const Fr g = from_mont<R>(verify_weigh<C>(sc, mont(x1), mont(x2), mont(c_at), mont(a_at), live));
+        const Scalar zero = small(0);
+        const Scalar rx2 = live ? mul_plain(rho, x2) : zero, rx1 = live ? mul_plain(rho, x1) : zero;
+        const Scalar want_g = live ? mul_plain(rho, add_mod(a_at, mul_plain(x2, c_at))) : zero;
+        expect(!memcmp(sc.rho, live ? rho.w : zero.w, 16) && !memcmp(sc.rx2, rx2.w, 32) && !memcmp(sc.rx1, rx1.w, 32) && !memcmp(g.l, want_g.w, 32), what);
+    }
+
+    // verify_node_points on a node of known multiples of G: {(u + neg_g) G, -v G, w G}
+    void node_case(const char *what, const Scalar &u, const Scalar &v, const Scalar &w, const Scalar &neg_g, bool with_g) {
+        const Affine<C> G = generator(), none = Affine<C>::infinity();
+        const VerifyTerm<C> nd{smul(G, u), smul(G, v), smul(G, w)};
+        Affine<C> P[3];
+        verify_node_points<C>(nd, neg_g.w, with_g ? G : none, P);
+        const Scalar k[3] = {with_g ? add_mod(u, neg_g) : u, negated_mod(v), w};
+        for (int j = 0; j < 3; ++j) {
+            const Affine<C> want = xyzz_to_affine<C>(smul(G, k[j]));
+            expect(P[j].x.eq(want.x) && P[j].y.eq(want.y) && affine_on_curve<C>(P[j]), what);
+        }
+    }
+
     void run() {
+        mul_words_cases();
+        for (int k = 0; k < 4; ++k)
+            weigh_case("verify_weigh: a drawn row", rho128(next_u64(), next_u64()), rand_scalar(), rand_scalar(), rand_scalar(), rand_scalar(), true);
+        weigh_case("verify_weigh: x1 = 0, x2 = r - 1", rho128(~0ull, ~0ull), small(0), r_minus_1(), r_minus_1(), r_minus_1(), true);
+        weigh_case("verify_weigh: a dead row", rho128(next_u64(), next_u64()), rand_scalar(), rand_scalar(), rand_scalar(), rand_scalar(), false);
+        for (int k = 0; k < 2; ++k) node_case("verify_node_points: a drawn node", rand_scalar(), rand_scalar(), rand_scalar(), rand_scalar(), true);
+        const Scalar u = rand_scalar();
+        node_case("verify_node_points: g G = U (the first point is O)", u, rand_scalar(), rand_scalar(), negated_mod(u), true);
+        node_case("verify_node_points: V = W = O", u, small(0), small(0), rand_scalar(), true);
+        node_case("verify_node_points: G = O", u, rand_scalar(), rand_scalar(), rand_scalar(), false);
         const Affine<C> O = Affine<C>::infinity();
         const Scalar one = small(1), zero = small(0), rm1 = r_minus_1();
         for (int k = 0; k < 6; ++k)

@@ -6,11 +6,10 @@ pm_pairing_check_batch: cases with known answers from oracle/pyref G1 / G2 arith
 a + 1 (!= 1), a pool of them tiled to count = 1, 2, 65, 300 (lane 64 and five waves); k = 1 with P = O; k = 3 with and without an
 infinite point; a G2 point off the twist.
 
-pm_verify_batch2, device mode: the proofs of test_gpu_verify_batch.py (its helpers are copied here), the host verifier
+pm_verify_batch2, device mode: the proofs of test_gpu_verify_batch.py (tests/verify_helpers.py), the host verifier
 api.verify (pm_host_verify) the reference for every verdict, n_checks == 1 for a valid batch and == 1 + live after a failing root;
 then the same context in host mode.  One timed comparison in one process (32 BLS12-381 proofs, 3 tampered, spread apart): device
 mode must be faster than host mode, no ratio asserted (the ratio is printed under -s; profiles/verify_batch_device_pairing.txt)."""
-import math
 import os
 import random
 import time
@@ -18,11 +17,11 @@ import time
 import numpy as np
 import pytest
 
+import verify_helpers as VH
+from verify_helpers import CURVES2, G1N, _bound, _ctx, _host_verdict, _key, _moved_point, _plus_one, _proofs
+
 pytestmark = pytest.mark.gpu
 
-CURVES2 = ("bls12_381", "bn254")
-G1N = {"bls12_381": 48, "bn254": 32}
-_STATE = {}
 
 
 # ------------------------------------------------------------------------------------------------ pm_pairing_check_batch
@@ -42,10 +41,6 @@ def _g2_row(c, Q):
     n = c.fq_limbs64
     (x0, x1), (y0, y1) = Q
     return sum((_limbs(c.fq_to_mont(v), n) for v in (x0, x1, y0, y1)), [])
-
-
-def _ctx(curve):
-    return _key(curve)["pm"]["merlin"].ctx
 
 
 @pytest.mark.parametrize("curve", CURVES2)
@@ -117,73 +112,8 @@ def test_pairing_check_batch_one_and_three_pairs(curve):
 
 
 # ------------------------------------------------------------------------------- pm_verify_batch2, PM_VERIFY_PAIRING_DEVICE
-def _bound(count, f):
-    return 1 + 2 * f * (math.ceil(math.log2(count)) if count > 1 else 0)
-
-
-def _key(curve):
-    """one context, key and vk per curve, and a growing list of (public inputs as ints, proof bytes) per transcript"""
-    if curve not in _STATE:
-        from polymath_amd import api, circuits as PC, rng as R
-        from polymath_amd.polymath import Polymath
-        rng = R.StdRng.seed_from_u64(0xB47C + len(curve))
-        pm = Polymath(curve, "merlin", device=0)
-        r = pm.field.r
-        consts = [R.fr_rand(rng, r) for _ in range(16)]
-        circuit = PC.MiMCDemo(R.fr_rand(rng, r), R.fr_rand(rng, r), consts)
-        pk = pm.setup(circuit, rng)
-        _STATE[curve] = dict(api=api, pm={"merlin": pm}, pk=pk, vk=pm.make_vk(pk, *pm.last_trapdoors), rng=rng, consts=consts, proofs={})
-    return _STATE[curve]
-
-
-def _proofs(curve, transcript, count):
-    from polymath_amd import circuits as PC, rng as R
-    from polymath_amd.polymath import Polymath
-    s = _key(curve)
-    if transcript not in s["pm"]:
-        s["pm"][transcript] = Polymath(curve, transcript, ctx=s["pm"]["merlin"].ctx)
-    pm, have = s["pm"][transcript], s["proofs"].setdefault(transcript, [])
-    while len(have) < count:
-        circuit = PC.MiMCDemo(R.fr_rand(s["rng"], pm.field.r), R.fr_rand(s["rng"], pm.field.r), s["consts"])
-        proof = pm.prove(s["pk"], circuit, s["rng"])
-        have.append((pm._synthesize(circuit)[1][1:], proof.to_bytes()))
-    return have[:count]
-
-
 def _run(curve, transcript, items, pairing="device", **kw):
-    s = _key(curve)
-    pm = s["pm"]["merlin"]
-    pub = np.stack([pm.field.fr_limbs(list(x)) for x, _ in items]) if items else np.zeros((0, 0, 4), dtype=np.uint64)
-    return s["api"].verify_batch(pm.ctx, curve, transcript, s["vk"], pub, [p for _, p in items], pairing=pairing, **kw)
-
-
-def _host_verdict(curve, transcript, item):
-    s = _key(curve)
-    api = s["api"]
-    try:
-        return api.VERIFY_ACCEPTED if api.verify(curve, transcript, s["vk"], s["pm"]["merlin"].field.fr_limbs(list(item[0])), item[1]) else api.VERIFY_REJECTED
-    except api.PolymathError:
-        return api.VERIFY_MALFORMED
-
-
-def _moved_point(curve, item):
-    """a_g1's x walked until the encoding no longer decodes into the group (off the curve, or on it and outside G1)"""
-    for tweak in range(1, 40):
-        bad = bytearray(item[1])
-        k = G1N[curve] - 1 if curve == "bls12_381" else 0           # the low byte of x
-        bad[k] = (bad[k] + tweak) & 0xFF
-        cand = (item[0], bytes(bad))
-        if _host_verdict(curve, "merlin", cand) == 2:
-            return cand
-    raise AssertionError("no tweak of x left the group")
-
-
-def _plus_one(curve, item, r):
-    """a_at_x1 + 1"""
-    g1 = G1N[curve]
-    x, p = item
-    a_at = int.from_bytes(p[2 * g1:2 * g1 + 32], "little")
-    return (x, p[:2 * g1] + ((a_at + 1) % r).to_bytes(32, "little") + p[2 * g1 + 32:])
+    return VH._run(curve, transcript, items, pairing=pairing, **kw)
 
 
 @pytest.mark.parametrize("curve", CURVES2)

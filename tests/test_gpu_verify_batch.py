@@ -7,67 +7,13 @@ Cost: the file's time is the host's pairing checks.  Measured on the GPU box's h
 test_throughput_gate under -s): one product_is_one of three pairs 118 ms on BLS12-381 / 57 ms on BN254, one pm_host_verify
 142.5 ms / 59.1 ms.  With the counts below the file ran in 24 s there (budget: 60 s), so no count was shrunk.  The tampered proofs of the mixed batch sit next to each other (18, 19, 20 of 21)
 so that the bisection shares its path: 10 checks a call instead of ~17 when they are spread."""
-import math
-
 import numpy as np
 import pytest
 
 from helpers import I, load_golden
+from verify_helpers import CURVES2, G1N, _bound, _host_verdict, _key, _moved_point, _proofs, _run
 
 pytestmark = pytest.mark.gpu
-
-CURVES2 = ("bls12_381", "bn254")
-G1N = {"bls12_381": 48, "bn254": 32}
-_STATE = {}
-
-
-def _bound(count, f):
-    return 1 + 2 * f * (math.ceil(math.log2(count)) if count > 1 else 0)
-
-
-def _key(curve):
-    """one context, key and vk per curve, and a growing list of (public inputs as ints, proof bytes) per transcript"""
-    if curve not in _STATE:
-        from polymath_amd import api, circuits as PC, rng as R
-        from polymath_amd.polymath import Polymath
-        rng = R.StdRng.seed_from_u64(0xB47C + len(curve))
-        pm = Polymath(curve, "merlin", device=0)
-        r = pm.field.r
-        consts = [R.fr_rand(rng, r) for _ in range(16)]
-        circuit = PC.MiMCDemo(R.fr_rand(rng, r), R.fr_rand(rng, r), consts)
-        pk = pm.setup(circuit, rng)
-        _STATE[curve] = dict(api=api, pm={"merlin": pm}, pk=pk, vk=pm.make_vk(pk, *pm.last_trapdoors), rng=rng, consts=consts, proofs={})
-    return _STATE[curve]
-
-
-def _proofs(curve, transcript, count):
-    from polymath_amd import circuits as PC, rng as R
-    from polymath_amd.polymath import Polymath
-    s = _key(curve)
-    if transcript not in s["pm"]:
-        s["pm"][transcript] = Polymath(curve, transcript, ctx=s["pm"]["merlin"].ctx)
-    pm, have = s["pm"][transcript], s["proofs"].setdefault(transcript, [])
-    while len(have) < count:
-        circuit = PC.MiMCDemo(R.fr_rand(s["rng"], pm.field.r), R.fr_rand(s["rng"], pm.field.r), s["consts"])
-        proof = pm.prove(s["pk"], circuit, s["rng"])
-        have.append((pm._synthesize(circuit)[1][1:], proof.to_bytes()))
-    return have[:count]
-
-
-def _run(curve, transcript, items, **kw):
-    s = _key(curve)
-    pm = s["pm"]["merlin"]
-    pub = np.stack([pm.field.fr_limbs(list(x)) for x, _ in items]) if items else np.zeros((0, 0, 4), dtype=np.uint64)
-    return s["api"].verify_batch(pm.ctx, curve, transcript, s["vk"], pub, [p for _, p in items], **kw)
-
-
-def _host_verdict(curve, transcript, item):
-    s = _key(curve)
-    api = s["api"]
-    try:
-        return api.VERIFY_ACCEPTED if api.verify(curve, transcript, s["vk"], s["pm"]["merlin"].field.fr_limbs(list(item[0])), item[1]) else api.VERIFY_REJECTED
-    except api.PolymathError:
-        return api.VERIFY_MALFORMED
 
 
 @pytest.mark.parametrize("curve", CURVES2)
@@ -86,18 +32,6 @@ def test_valid_batches(curve):
     items = _proofs(curve, "merlin", 3)
     v, ok, checks = pm.verify_batch(_key(curve)["vk"], [x for x, _ in items], [p for _, p in items])     # the facade beside Polymath.verify
     assert v.tolist() == [1, 1, 1] and ok and checks == 1
-
-
-def _moved_point(curve, item):
-    """a_g1's x walked until the encoding no longer decodes into the group (off the curve, or on it and outside G1)"""
-    for tweak in range(1, 40):
-        bad = bytearray(item[1])
-        k = G1N[curve] - 1 if curve == "bls12_381" else 0           # the low byte of x
-        bad[k] = (bad[k] + tweak) & 0xFF
-        cand = (item[0], bytes(bad))
-        if _host_verdict(curve, "merlin", cand) == 2:
-            return cand
-    raise AssertionError("no tweak of x left the group")
 
 
 @pytest.mark.parametrize("curve", CURVES2)
