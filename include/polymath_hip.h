@@ -123,7 +123,10 @@ typedef enum pm_option {
     PM_OPT_INFLIGHT_CONTEXTS = 5, /* (key) how many contexts will prove on the key at once: their per-proof vectors and MSM
                                    * workspaces are left out of the HBM granted to window tables.  Default 1 (PM_INFLIGHT_CONTEXTS). */
     PM_OPT_MSM_TASK_LEN = 6,      /* entries of one bucket-accumulation task; 0 = twice the mean bucket load.  Default 0 (PM_MSM_SEG). */
-    PM_OPT_TABLE_WINDOW_BITS = 7, /* (key) widest window of the table sets; 0 = the cost model of tables_plan.  Default 0 (PM_TABLE_C). */
+    PM_OPT_TABLE_WINDOW_BITS = 7, /* (key) widest window of the table sets; 0 = the cost model of tables_plan.  Default 0 (PM_TABLE_C).
+                                   * Developer values 100 m + w force the window radix m 2^a (m = 1: the power-of-two layout, m = 5)
+                                   * on w windows, 10 <= w <= 32 (m = 5: w <= 16), or on the cost model's count for that m with
+                                   * w = 0: 100 restores the power-of-two plans, 511 is 11 windows of radix 5 2^21. */
     PM_OPT_WIRE_CHUNK_LOG = 8,    /* compressed points per staging chunk of pm_pk_load_bytes / pm_g1_decode /
                                    * pm_pk_export_bases_compressed: 2^v, 4 <= v <= 24.  Default 20 (PM_WIRE_CHUNK_LOG); lower values put
                                    * chunk boundaries inside small vectors (tests). */

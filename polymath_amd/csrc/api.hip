@@ -87,7 +87,7 @@ static const OptionSpec OPTION_SPECS[PM_NUM_OPTIONS] = {
     /* PM_OPT_MAX_SEG_LOG       */ {"PM_MAX_SEG_LOG", 0, 0, 40},
     /* PM_OPT_INFLIGHT_CONTEXTS */ {"PM_INFLIGHT_CONTEXTS", 1, 1, 64},
     /* PM_OPT_MSM_TASK_LEN      */ {"PM_MSM_SEG", 0, 0, 1 << 20},
-    /* PM_OPT_TABLE_WINDOW_BITS */ {"PM_TABLE_C", 0, 0, 24},
+    /* PM_OPT_TABLE_WINDOW_BITS */ {"PM_TABLE_C", 0, 0, 532},     // 4 ... 24: window bits; 100 m + windows: the radix (setup.hip: tables_plan)
     /* PM_OPT_WIRE_CHUNK_LOG    */ {"PM_WIRE_CHUNK_LOG", 20, 4, 24},
 };
 static void options_defaults(pm_options *o) {

@@ -141,6 +141,10 @@ struct MsmTables {
     unsigned c = 0, nwin = 0;        // c = widest window; buckets = 2^(c-1)
     unsigned off[33] = {0};          // bit offset of window w (off[nwin] = 256)
     unsigned char width[32] = {0};   // bits of window w
+    // Radix m 2^a, the same for every window of the set (radix.cuh).  m = 1: the balanced power-of-two layout above (a unused).
+    // m = 5: point (w, i) = R^w P_i with R = 5 2^a, one shared set of R / 2 = 5 2^(a-1) buckets; c = a + 3 = ceil(log2 R), off[] and
+    // width[] stay zero.  Tables only, never wide.
+    unsigned m = 1, a = 0;
     size_t stride = 0;               // points per window
     size_t base_index = 0;           // first point of this MSM inside window 0
     const unsigned char *inf = nullptr;   // device: one flag byte per point of window 0 (1 = point at infinity)
@@ -435,6 +439,7 @@ int reduce_two_level(pm_ctx *ctx, size_t NB, XYZZ<C> **out, unsigned nsets = 1, 
 // The sort's first level (msm.hip: k_tbl_count / k_tbl_partition) splits the buckets into regions of 2^15, one region per scan lane
 // of a workgroup of at most 1024 lanes.
 constexpr unsigned SORT_REGION_BITS = 15, SORT_MAX_REGIONS = 1024;
+constexpr unsigned RADIX5_MAX_WINDOWS = 16;   // radix 5 2^a (radix.cuh): the first sort level is instantiated for 10 ... 16 windows
 
 // Wide mode: the bucket sets of a plan of nwin windows whose widest has c bits.  The 256 % nwin windows of c bits come first and own
 // `wide_b` = 2^(c-1) buckets each; the windows that are one bit narrower own `narrow_b`: half of that where it is still whole sort
@@ -465,6 +470,8 @@ inline size_t msm_max_piece(const pm_ctx *ctx) {
 
 // choose c and the number of windows for a key whose longest MSM has `max_len` pairs
 void msm_plan_query(size_t len, unsigned scalar_bits, unsigned *nwin, unsigned *c);
+// force_c (PM_OPT_TABLE_WINDOW_BITS): 0; 4 ... 24, the widest window of the power-of-two layout; or 100 m + windows, the radix
+// m 2^a (m = 1 | 5, radix.cuh) on that many windows (0: as many as the cost model likes for that m)
 MsmTables tables_plan(size_t total_pairs, unsigned n_msm, size_t resident_points, unsigned scalar_bits, unsigned force_c = 0);
 // the plan of an MSM that gets no tables (MsmTables::wide); c == 0 if none applies (short MSMs: the per-window pipeline)
 MsmTables wide_plan(size_t piece, unsigned force_c = 0);

@@ -33,6 +33,7 @@
 
 #include "internal.h"
 #include "fq28.cuh"
+#include "radix.cuh"
 
 namespace pm {
 
@@ -597,7 +598,9 @@ __global__ __launch_bounds__(256) void k_digits_batch(const Fp<typename C::FrP> 
 // as k_tbl_partition (one scalar per lane).  A column-wise scan (k_block_sums, k_block_offsets) turns them into each
 // workgroup's offset inside each region, so neither kernel touches a global atomic: 41 K workgroups x 64
 // regions hammering 64 addresses serialised in L2 and cost more than the rest of the kernel.
-template <class P, unsigned NWIN>
+// M: the radix's multiplier (internal.h: MsmTables::m).  M = 5: the digits of radix 5 2^a (radix.cuh), a = the shift of (field, NWIN),
+// one shared bucket set -- dg[w] = bucket << 1 | negate, so the region of a digit is dg >> (LO_BITS + 1).
+template <class P, unsigned NWIN, unsigned M>
 __global__ __launch_bounds__(1024) void k_tbl_count(const Fp<P> *scalars, const unsigned char *inf, size_t len, unsigned regions,
                                                    uint32_t *block_cnt, uint32_t win_buckets, uint32_t narrow_buckets) {
     __shared__ uint32_t cnt[SORT_MAX_REGIONS];
@@ -606,10 +609,18 @@ __global__ __launch_bounds__(1024) void k_tbl_count(const Fp<P> *scalars, const 
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < len) {
         const Fp<P> k = canon_scalar<P>(scalars, inf, i);
-        uint32_t carry = 0, b, neg;
+        if constexpr (M == 5) {
+            uint32_t dg[NWIN];
+            radix5_recode<NWIN, radix_min_shift<P>(5, NWIN)>(k.l, dg);
 #pragma unroll
-        for (unsigned w = 0; w < NWIN; ++w)
-            if (digit_at<P>(k, win_off(NWIN, w), win_width(NWIN, w), carry, b, neg)) atomicAdd(&cnt[(b + win_base(NWIN, w, win_buckets, narrow_buckets)) >> LO_BITS], 1u);
+            for (unsigned w = 0; w < NWIN; ++w)
+                if (dg[w] != RADIX_NO_DIGIT) atomicAdd(&cnt[dg[w] >> (LO_BITS + 1)], 1u);
+        } else {
+            uint32_t carry = 0, b, neg;
+#pragma unroll
+            for (unsigned w = 0; w < NWIN; ++w)
+                if (digit_at<P>(k, win_off(NWIN, w), win_width(NWIN, w), carry, b, neg)) atomicAdd(&cnt[(b + win_base(NWIN, w, win_buckets, narrow_buckets)) >> LO_BITS], 1u);
+        }
     }
     __syncthreads();
     for (unsigned r = threadIdx.x; r < regions; r += blockDim.x) block_cnt[(size_t)blockIdx.x * regions + r] = cnt[r];
@@ -715,7 +726,7 @@ __global__ __launch_bounds__(1024) void k_region_offsets(const uint32_t *region_
 // One scalar per lane.  The workgroup's entries are staged through LDS in region order so that the global
 // stores are coalesced (consecutive lanes -> consecutive addresses of a region's run).
 //   LDS: cnt[SORT_MAX_REGIONS] | delta[SORT_MAX_REGIONS] | staged vals (u32 x blockDim nwin) | staged region<<16|key (u32 x same)
-template <class P, unsigned NWIN>
+template <class P, unsigned NWIN, unsigned M>
 __global__ __launch_bounds__(1024) void k_tbl_partition(const Fp<P> *scalars, const unsigned char *inf, size_t len,
                                                        unsigned regions, const uint32_t *region_off, const uint32_t *block_off, size_t tbl_stride, size_t base_index, uint16_t *keys,
                                                        uint32_t *vals, uint32_t win_buckets, uint32_t narrow_buckets) {
@@ -730,13 +741,21 @@ __global__ __launch_bounds__(1024) void k_tbl_partition(const Fp<P> *scalars, co
     // registers (NWIN per lane) so that pass 2 needs no second LDS atomic
     const size_t i = (size_t)blockIdx.x * BD + t;
     uint32_t rank[NWIN];
+    uint32_t dg[M == 5 ? NWIN : 1];     // M = 5: the digits are recoded once and kept (bucket << 1 | negate, radix.cuh)
     Fp<P> k = Fp<P>::zero();
     if (i < len) {
         k = canon_scalar<P>(scalars, inf, i);
-        uint32_t carry = 0, b, neg;
+        if constexpr (M == 5) {
+            radix5_recode<NWIN, radix_min_shift<P>(5, NWIN)>(k.l, dg);
 #pragma unroll
-        for (unsigned w = 0; w < NWIN; ++w)
-            if (digit_at<P>(k, win_off(NWIN, w), win_width(NWIN, w), carry, b, neg)) rank[w] = atomicAdd(&cnt[(b + win_base(NWIN, w, win_buckets, narrow_buckets)) >> LO_BITS], 1u);
+            for (unsigned w = 0; w < NWIN; ++w)
+                if (dg[w] != RADIX_NO_DIGIT) rank[w] = atomicAdd(&cnt[dg[w] >> (LO_BITS + 1)], 1u);
+        } else {
+            uint32_t carry = 0, b, neg;
+#pragma unroll
+            for (unsigned w = 0; w < NWIN; ++w)
+                if (digit_at<P>(k, win_off(NWIN, w), win_width(NWIN, w), carry, b, neg)) rank[w] = atomicAdd(&cnt[(b + win_base(NWIN, w, win_buckets, narrow_buckets)) >> LO_BITS], 1u);
+        }
     }
     __syncthreads();
     {   // exclusive scan over the regions: lane t owns region t (regions <= blockDim, checked by the host: bucket_plan)
@@ -751,15 +770,25 @@ __global__ __launch_bounds__(1024) void k_tbl_partition(const Fp<P> *scalars, co
     }
     __syncthreads();
     if (i < len) {
-        uint32_t carry = 0, b, neg;
+        if constexpr (M == 5) {
 #pragma unroll
-        for (unsigned w = 0; w < NWIN; ++w)
-            if (digit_at<P>(k, win_off(NWIN, w), win_width(NWIN, w), carry, b, neg)) {
-                b += win_base(NWIN, w, win_buckets, narrow_buckets);
-                const uint32_t rg = b >> LO_BITS, slot = cnt[rg] + rank[w];
-                st_key[slot] = (rg << 16) | (b & ((1u << LO_BITS) - 1));
-                st_val[slot] = (uint32_t)(((size_t)w * tbl_stride + base_index + i) << 1) | neg;
-            }
+            for (unsigned w = 0; w < NWIN; ++w)
+                if (dg[w] != RADIX_NO_DIGIT) {
+                    const uint32_t b = dg[w] >> 1, rg = b >> LO_BITS, slot = cnt[rg] + rank[w];
+                    st_key[slot] = (rg << 16) | (b & ((1u << LO_BITS) - 1));
+                    st_val[slot] = (uint32_t)(((size_t)w * tbl_stride + base_index + i) << 1) | (dg[w] & 1u);
+                }
+        } else {
+            uint32_t carry = 0, b, neg;
+#pragma unroll
+            for (unsigned w = 0; w < NWIN; ++w)
+                if (digit_at<P>(k, win_off(NWIN, w), win_width(NWIN, w), carry, b, neg)) {
+                    b += win_base(NWIN, w, win_buckets, narrow_buckets);
+                    const uint32_t rg = b >> LO_BITS, slot = cnt[rg] + rank[w];
+                    st_key[slot] = (rg << 16) | (b & ((1u << LO_BITS) - 1));
+                    st_val[slot] = (uint32_t)(((size_t)w * tbl_stride + base_index + i) << 1) | neg;
+                }
+        }
     }
     __syncthreads();
     const uint32_t total = tot;
@@ -1039,7 +1068,7 @@ struct BucketPlan {
     unsigned nwin, c;                        // windows; bits of the widest
     size_t len, E;                           // pairs; E = nwin * len, the most entries the sort can see
     // the bucket sets, in bucket order: n_wide_sets of NB1 = 2^(c-1) buckets, then n_narrow_sets of NBn (wide mode, internal.h:
-    // wide_sets); NB = all of them.  Per-window: nwin sets of NB1; tables: one.
+    // wide_sets); NB = all of them.  Per-window: nwin sets of NB1; tables: one (radix 5 2^a: of 5 2^(a-1) buckets, in whole regions).
     size_t NB1, NBn, NB;
     unsigned n_wide_sets, n_narrow_sets;
     uint32_t win_buckets, narrow_buckets;    // win_base()'s arguments: NB1 and NBn in wide mode, 0 for the shared set
@@ -1059,7 +1088,9 @@ struct BucketPlan {
 // workgroup's run inside a region is 24 entries (96 B of values), not 12 -- what the first level pays for is the length of that
 // run, not the number of regions: same-box A/B at 2^24 gates in profiles/r06_wide_ragged_sets_ab.txt (512 regions on 512 lanes:
 // sort + 5 ... 8 ms against 768 on 1024) and r06_wide_12_windows_ab.txt; 256 against 512 lanes below that: flat
-// (profiles/r05_sort_chunk_shapes_after_wide_loads.txt, (3))
+// (profiles/r05_sort_chunk_shapes_after_wide_loads.txt, (3)).  The radix-5 plans stay below that threshold and on 512 lanes: 11 windows
+// in 160 regions (runs of 35 entries) measured 3.56 ms of sort on 512 lanes against 3.68 on 1024 for the 21 M-pair [d]_1, 56.61 ...
+// 56.74 against 56.79 ... 56.96 ms per proof on one box (profiles/msm_radix5_ab.txt); 12 windows in 40 regions write runs of 150.
 constexpr unsigned PARTITION_LANES = 512, PARTITION_WIDE_LANES = 1024, PARTITION_WIDE_FROM = 512;
 
 // tb: the window tables or the wide plan of the MSM; nullptr (or c == 0): the per-window pipeline on `len` pairs of scalar_bits-bit scalars
@@ -1077,9 +1108,20 @@ static int bucket_plan(const MsmTables *tb, size_t len, unsigned scalar_bits, lo
         p.wide = tb->wide;
         p.nwin = tb->nwin; p.c = tb->c;
         if (p.nwin < 10 || p.nwin > 32) return PM_ERR_INVALID_ARG;      // the first level's instantiations (sort_first_level)
-        for (unsigned w = 0; w < p.nwin; ++w)                            // the kernels derive the layout from nwin alone
-            if (tb->off[w] != win_off(p.nwin, w) || tb->width[w] != win_width(p.nwin, w)) return PM_ERR_INVALID_ARG;
-        p.NB1 = (size_t)1 << (p.c - 1);
+        if (tb->m == 5) {
+            // radix 5 2^a: R / 2 = 5 2^(a-1) buckets -- 40 or 160 whole regions for the plans tables_plan chooses by itself; a
+            // forced small radix (tests) that is more than one region and not whole ones is padded with empty buckets, which
+            // the scan, the task order and the reduction pass over
+            if (p.wide || p.nwin > RADIX5_MAX_WINDOWS || tb->a < 11 || tb->a > 28) return PM_ERR_INVALID_ARG;
+            const size_t region = (size_t)1 << LO_BITS;
+            p.NB1 = (size_t)5 << (tb->a - 1);
+            if (p.NB1 > region) p.NB1 = (p.NB1 + region - 1) / region * region;
+        } else {
+            if (tb->m != 1) return PM_ERR_INVALID_ARG;
+            for (unsigned w = 0; w < p.nwin; ++w)                        // the kernels derive the layout from nwin alone
+                if (tb->off[w] != win_off(p.nwin, w) || tb->width[w] != win_width(p.nwin, w)) return PM_ERR_INVALID_ARG;
+            p.NB1 = (size_t)1 << (p.c - 1);
+        }
         p.n_wide_sets = 1;
         if (p.wide) {
             const WideSets s = wide_sets(p.nwin, p.c);
@@ -1294,12 +1336,25 @@ struct SortBuffers {
 
 // First level: every (scalar, window) entry into the region of its bucket -- per-workgroup region counts, their column scan, the
 // regions' offsets, the partition.  The kernels are instantiated per window count (win_off): the chain below finds nwin's.
+template <class P, unsigned NWIN, unsigned M>
+static int sort_first_level_launch(pm_ctx *ctx, const BucketPlan &p, const MsmTables &tb, const Fp<P> *d_scalars, const SortBuffers &b);
 template <class P, unsigned NWIN = 10>
 static int sort_first_level(pm_ctx *ctx, const BucketPlan &p, const MsmTables &tb, const Fp<P> *d_scalars, const SortBuffers &b) {
     if (p.nwin != NWIN) {
         if constexpr (NWIN < 32) return sort_first_level<P, NWIN + 1>(ctx, p, tb, d_scalars, b);
         return PM_ERR_INVALID_ARG;
     }
+    if (tb.m == 5) {
+        if constexpr (NWIN <= RADIX5_MAX_WINDOWS) {
+            if (tb.a != radix_min_shift<P>(5, NWIN)) return PM_ERR_INVALID_ARG;     // the kernels' shift is that of (field, windows)
+            return sort_first_level_launch<P, NWIN, 5>(ctx, p, tb, d_scalars, b);
+        }
+        return PM_ERR_INVALID_ARG;
+    }
+    return sort_first_level_launch<P, NWIN, 1>(ctx, p, tb, d_scalars, b);
+}
+template <class P, unsigned NWIN, unsigned M>
+static int sort_first_level_launch(pm_ctx *ctx, const BucketPlan &p, const MsmTables &tb, const Fp<P> *d_scalars, const SortBuffers &b) {
     hipStream_t st = ctx->stream;
     const unsigned char *inf = tb.inf + tb.base_index;
     const unsigned pblocks = (unsigned)((p.len + p.pbd - 1) / p.pbd);
@@ -1307,13 +1362,13 @@ static int sort_first_level(pm_ctx *ctx, const BucketPlan &p, const MsmTables &t
     PM_HIP(ctx, ctx->msm.block_cnt.reserve(((size_t)pblocks + bsh.G) * p.regions * 4));
     uint32_t *block_cnt = ctx->msm.block_cnt.as<uint32_t>(), *block_partial = block_cnt + (size_t)pblocks * p.regions;
     PM_HIP(ctx, hipMemsetAsync(b.region_count, 0, (size_t)p.regions * 4, st));
-    hipLaunchKernelGGL((k_tbl_count<P, NWIN>), dim3(pblocks), dim3(p.pbd), 0, st, d_scalars, inf, p.len, p.regions, block_cnt, p.win_buckets,
+    hipLaunchKernelGGL((k_tbl_count<P, NWIN, M>), dim3(pblocks), dim3(p.pbd), 0, st, d_scalars, inf, p.len, p.regions, block_cnt, p.win_buckets,
                        p.narrow_buckets);
     hipLaunchKernelGGL(k_block_sums, dim3(bsh.G), dim3(1024), 0, st, block_cnt, pblocks, p.regions, bsh, block_partial);
     hipLaunchKernelGGL(k_block_offsets, dim3(bsh.G), dim3(1024), 0, st, block_cnt, pblocks, p.regions, bsh, block_partial, b.region_count);
     hipLaunchKernelGGL(k_region_offsets, dim3(1), dim3(1024), 0, st, b.region_count, b.region_off, b.region_cursor, p.regions);
-    PM_HIP(ctx, hipFuncSetAttribute((const void *)k_tbl_partition<P, NWIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.plds));
-    PM_LAUNCH(ctx, (k_tbl_partition<P, NWIN>), dim3(pblocks), dim3(p.pbd), p.plds, st, d_scalars, inf, p.len, p.regions, b.region_off, block_cnt,
+    PM_HIP(ctx, hipFuncSetAttribute((const void *)k_tbl_partition<P, NWIN, M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.plds));
+    PM_LAUNCH(ctx, (k_tbl_partition<P, NWIN, M>), dim3(pblocks), dim3(p.pbd), p.plds, st, d_scalars, inf, p.len, p.regions, b.region_off, block_cnt,
                    p.wide ? (size_t)0 : tb.stride, tb.base_index, b.keys, b.vals, p.win_buckets, p.narrow_buckets);
     return PM_OK;
 }

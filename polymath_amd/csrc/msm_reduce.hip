@@ -10,7 +10,8 @@ namespace pm {
 // not work:
 //   level 0  lane t owns buckets [t K0, t K0 + K0):  A_t = sum B_b,  acc_t = sum (b - t K0 + 1) B_b
 //            (2 K0 adds; K0 is chosen so that NB / K0 ~ 2^17 lanes = one full round of the chip);
-//   level 1  lane j owns R level-0 outputs: running sums, (jR) * sum A by double-and-add, + acc_t; LDS tree
+//            NB need be no power of two (radix 5 2^a: 5 2^(a-1) buckets), nor K0: the last lane's range is cut at NB;
+//   level 1  lane j owns R level-0 outputs: running sums, (jR) * sum A by double-and-add, times K0, + acc_t; LDS tree
 //            per workgroup (2^15 lanes: a short chain on a quarter-full chip beats a full chip of scalar muls);
 //   final    one workgroup sums the level-1 partials.
 //   S = sum_t acc_t + sum_t (t K0) A_t.
@@ -197,7 +198,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
             xyzz28_add_coop<C, LP>(acc, m, role);
         }
-        for (unsigned k = 1; k < K0; k <<= 1) xyzz28_dbl_coop<C, LP>(acc, role);   // K0 is a power of two
+        if (K0 & (K0 - 1)) {                                               // acc *= K0, any K0 (the same for every lane): double-and-add
+            const XYZZ28<C> base = acc;
+            for (int b = 30 - __clz((int)K0); b >= 0; --b) {
+                xyzz28_dbl_coop<C, LP>(acc, role);
+                if ((K0 >> b) & 1) xyzz28_add_coop<C, LP>(acc, base, role);
+            }
+        } else {
+            for (unsigned k = 1; k < K0; k <<= 1) xyzz28_dbl_coop<C, LP>(acc, role);   // a power of two: doublings only
+        }
         for (unsigned i = 0; i < R; ++i)
             if (t0 + i < lanes0) xyzz28_add_coop<C, LP>(acc, xyzz28_load<C>(Acc[t0 + i]), role);
     }
@@ -229,10 +238,17 @@ template <class C>
 int reduce_two_level(pm_ctx *ctx, size_t NB, XYZZ<C> **out, unsigned nsets, size_t bucket0) {
     MsmWorkspace &ws = ctx->msm;
     const MsmSet *S = &ws.set;
-    if (nsets == 0 || (NB & (NB - 1)) != 0) return PM_ERR_INVALID_ARG;
+    if (nsets == 0 || NB == 0 || (nsets > 1 && (NB & (NB - 1)) != 0)) return PM_ERR_INVALID_ARG;   // several sets: powers of two (wide mode)
     const size_t total = NB * nsets;
     unsigned K0 = 4;                                   // level-0 fan-in: <= 2^17 lanes = 2 waves per SIMD, one round of the chip
-    while (total / K0 > ((size_t)1 << 17) && K0 < 64) K0 <<= 1;   // (swept in profiles/r02_levers.jsonl: K0 = 2 doubles level 1's work and loses)
+    if (nsets > 1 || (NB & (NB - 1)) == 0) {
+        while (total / K0 > ((size_t)1 << 17) && K0 < 64) K0 <<= 1;   // (swept in profiles/r02_levers.jsonl: K0 = 2 doubles level 1's work and loses)
+    } else {
+        // one set of any size (radix 5 2^a: 5 2^(a-1) buckets): K0 = ceil(NB / 2^17) as a plain integer -- 40 for 5.24 M buckets, 10 for
+        // 1.31 M.  The next power of two would leave the chip 62 % full on a chain 1.6 times as long (64 against 40).
+        const size_t k = (NB + ((size_t)1 << 17) - 1) >> 17;
+        if (k > K0) K0 = (unsigned)k;
+    }
     // levels 1 and final on lane GROUPS (4 lanes per point, a share of the products each): 256 / LP points per workgroup, and
     // R = 2 LP keeps level 1 at 2^16 lanes = one wave per SIMD (its register budget); K0 and R swept on MI355X in round 2
     // (profiles/r02_levers.jsonl, r02_m_reduce_pair_sweep.txt)
