@@ -123,10 +123,19 @@ typedef enum pm_option {
     PM_OPT_INFLIGHT_CONTEXTS = 5, /* (key) how many contexts will prove on the key at once: their per-proof vectors and MSM
                                    * workspaces are left out of the HBM granted to window tables.  Default 1 (PM_INFLIGHT_CONTEXTS). */
     PM_OPT_MSM_TASK_LEN = 6,      /* entries of one bucket-accumulation task; 0 = twice the mean bucket load.  Default 0 (PM_MSM_SEG). */
-    PM_OPT_TABLE_WINDOW_BITS = 7, /* (key) widest window of the table sets; 0 = the cost model of tables_plan.  Default 0 (PM_TABLE_C).
-                                   * Developer values 100 m + w force the window radix m 2^a (m = 1: the power-of-two layout, m = 5)
-                                   * on w windows, 10 <= w <= 32 (m = 5: w <= 16), or on the cost model's count for that m with
-                                   * w = 0: 100 restores the power-of-two plans, 511 is 11 windows of radix 5 2^21. */
+    PM_OPT_TABLE_WINDOW_BITS = 7, /* (key) developer knob (tuning sweeps, tests) over the MSM window plans; default 0 (PM_TABLE_C).
+                                   * Decoded in one place, csrc/msm_plan.h: decode_window_option.  Accepted, 0 ... 532:
+                                   *   0          the cost models choose (tables_plan for window tables, wide_plan without them);
+                                   *   4 ... 24   the widest window of the power-of-two layout: ceil(256 / v) windows of v bits or one
+                                   *              fewer, taken as it is (the MSM is refused if the kernels cannot run it: more than 32
+                                   *              windows, i.e. v < 8).  A key's MSMs without tables (wide mode) are held to v as well
+                                   *              when 16 <= v <= 23: 16, 18, 19, 20, 22 name 16, 15, 14, 13, 12 windows; 17, 21 and 23
+                                   *              name none, and such an MSM then runs the per-window pipeline;
+                                   *   100 m + w  the window radix m 2^a on w windows: m = 1 the power-of-two layout, 10 <= w <= 32; m = 5
+                                   *              radix 5 2^a, 10 <= w <= 16 (a = the smallest shift that covers the scalar field);
+                                   *              w = 0: the cost model's count for that m.  100 restores the power-of-two plans, 511 is
+                                   *              11 windows of radix 5 2^21.  Wide mode plans as for 0.  Any other m or w: no tables;
+                                   *   1 ... 3, 25 ... 99   name nothing: as 0. */
     PM_OPT_WIRE_CHUNK_LOG = 8,    /* compressed points per staging chunk of pm_pk_load_bytes / pm_g1_decode /
                                    * pm_pk_export_bases_compressed: 2^v, 4 <= v <= 24.  Default 20 (PM_WIRE_CHUNK_LOG); lower values put
                                    * chunk boundaries inside small vectors (tests). */

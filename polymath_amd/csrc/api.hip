@@ -87,7 +87,7 @@ static const OptionSpec OPTION_SPECS[PM_NUM_OPTIONS] = {
     /* PM_OPT_MAX_SEG_LOG       */ {"PM_MAX_SEG_LOG", 0, 0, 40},
     /* PM_OPT_INFLIGHT_CONTEXTS */ {"PM_INFLIGHT_CONTEXTS", 1, 1, 64},
     /* PM_OPT_MSM_TASK_LEN      */ {"PM_MSM_SEG", 0, 0, 1 << 20},
-    /* PM_OPT_TABLE_WINDOW_BITS */ {"PM_TABLE_C", 0, 0, 532},     // 4 ... 24: window bits; 100 m + windows: the radix (setup.hip: tables_plan)
+    /* PM_OPT_TABLE_WINDOW_BITS */ {"PM_TABLE_C", 0, 0, 532},     // accepted values: include/polymath_hip.h
     /* PM_OPT_WIRE_CHUNK_LOG    */ {"PM_WIRE_CHUNK_LOG", 20, 4, 24},
 };
 static void options_defaults(pm_options *o) {
@@ -324,9 +324,9 @@ extern "C" int pm_bases_download(pm_ctx *ctx, const pm_bases *b, size_t offset, 
 
 template <class C>
 static int bases_precompute_impl(pm_ctx *ctx, pm_bases *b) {
-    if (b->tables.c || !b->len) return PM_OK;
-    MsmTables tb = tables_plan(b->len, 1, b->len, (unsigned)C::FrP::BITS, (unsigned)ctx->opt.v[PM_OPT_TABLE_WINDOW_BITS]);
-    if (!tb.c) return PM_OK;
+    if (b->tables.planned() || !b->len) return PM_OK;
+    MsmTables tb(tables_plan(b->len, 1, b->len, (unsigned)C::FrP::BITS, decode_window_option((unsigned)ctx->opt.v[PM_OPT_TABLE_WINDOW_BITS])), b->len);
+    if (!tb.planned()) return PM_OK;
     void *d_table = nullptr, *d_flags = nullptr;
     int st = PM_OK;
     if (hipMalloc(&d_table, b->len * tb.nwin * sizeof(TablePoint<C>)) != hipSuccess || hipMalloc(&d_flags, b->len) != hipSuccess) {
@@ -371,7 +371,7 @@ static int msm_resident_impl(pm_ctx *ctx, const pm_bases *bases, size_t off, con
     Affine<C> r;
     int inf = 1;
     timing_reset(ctx);
-    if (bases->tables.c) {
+    if (bases->tables.planned()) {
         MsmTables tb = bases->tables;
         tb.base_index = off;
         PM_TRY(msm_run<C>(ctx, (const Affine<C> *)nullptr, d_sc, len, &r, &inf, &tb));
@@ -720,24 +720,25 @@ static int pk_build_tables(pm_ctx *ctx, pm_pk *pk) {
         budget -= (double)inflight * 256.0 * (double)(len_d < pk->max_piece ? len_d : pk->max_piece);
         budget -= (double)inflight * 256.0 * (double)len_a;
     }
+    const WindowOption forced = decode_window_option((unsigned)ctx->opt.v[PM_OPT_TABLE_WINDOW_BITS]);
     int order[3] = {0, 1, 2};
     std::sort(order, order + 3, [&](int x, int y) { return pk->res_cnt[x] < pk->res_cnt[y]; });
     for (int q = 0; q < 3; ++q) {
         const int k = order[q];
         const uint64_t len = pk->res_cnt[k];
         if (!len) continue;
-        MsmTables tb = tables_plan((size_t)len, 1, (size_t)len, (unsigned)C::FrP::BITS, (unsigned)ctx->opt.v[PM_OPT_TABLE_WINDOW_BITS]);
+        MsmTables tb(tables_plan((size_t)len, 1, (size_t)len, (unsigned)C::FrP::BITS, forced), (size_t)len);
         // no table plan at all (nwin x points would overflow the u32 table indices: the 335 M-pair [d]_1 of a 2^24-gate key) counts
         // as "does not fit"
-        const double need = tb.c ? (double)len * tb.nwin * sizeof(TablePoint<C>) + (double)len : 1e300;
+        const double need = tb.planned() ? (double)len * tb.nwin * sizeof(TablePoint<C>) + (double)len : 1e300;
         const bool force_wide = tmode == PM_TABLES_WIDE;      // test / tuning knob -- no tables for any MSM, wide mode at any size
         if (need > budget || force_wide) {
             // No room for this MSM's tables (the 10n-pair [d]_1 of a 2^24-gate key on one GPU: 515 GB): WIDE mode -- the same
             // sort / accumulate / reduce kernels on the plain base array, one bucket set per window, 13 additions per pair
             // instead of the 16 of the one-shot pipeline.  Costs one infinity-flag byte per point.  PM_TABLES_NO_WIDE disables.
             const size_t piece = (size_t)(len < pk->max_piece ? len : pk->max_piece);
-            MsmTables wt = tmode == PM_TABLES_NO_WIDE ? MsmTables() : wide_plan(piece, (unsigned)ctx->opt.v[PM_OPT_TABLE_WINDOW_BITS]);
-            if (wt.c && (piece >= ((size_t)1 << 18) || force_wide) && (double)len < budget) {
+            MsmTables wt(tmode == PM_TABLES_NO_WIDE ? WindowLayout() : wide_plan(piece, forced), 0);
+            if (wt.planned() && (piece >= ((size_t)1 << 18) || force_wide) && (double)len < budget) {
                 budget -= (double)len;
                 PM_HIP(ctx, hipMalloc(&pk->d_tab_inf[k], len));
                 PM_TRY(infinity_flags<C>(ctx, d + pk->res_dev_off[k], (size_t)len, (unsigned char *)pk->d_tab_inf[k]));
@@ -1066,9 +1067,9 @@ extern "C" int pm_pk_msm_plan(const pm_pk *pk, int which, uint64_t *pairs, unsig
     if (!pk || which < 0 || which > 2) return PM_ERR_INVALID_ARG;
     const uint64_t len = pk->res_cnt[which];
     unsigned nwin = 0, c = 0;
-    if (pk->tables[which].c) {
+    if (pk->tables[which].planned()) {
         nwin = pk->tables[which].nwin;
-        c = pk->tables[which].c;
+        c = pk->tables[which].widest();
     } else {
         const uint64_t piece = len < pk->max_piece ? len : pk->max_piece;
         pm::msm_plan_query((size_t)piece, pk->curve == PM_BLS12_381 ? (unsigned)BlsFrP::BITS : (unsigned)BnFrP::BITS, &nwin, &c);
@@ -1076,7 +1077,7 @@ extern "C" int pm_pk_msm_plan(const pm_pk *pk, int which, uint64_t *pairs, unsig
     if (pairs) *pairs = len;
     if (windows) *windows = nwin;
     if (window_bits) *window_bits = c;
-    if (tables) *tables = pk->tables[which].c && !pk->tables[which].wide ? 1 : 0;
+    if (tables) *tables = pk->tables[which].planned() && !pk->tables[which].wide ? 1 : 0;
     return PM_OK;
 }
 

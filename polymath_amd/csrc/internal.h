@@ -17,6 +17,7 @@
 #include "../host/layout.hpp"
 #include "../host/solve_plan.hpp"
 #include "ec.cuh"
+#include "msm_plan.h"
 
 namespace pm {
 
@@ -132,28 +133,16 @@ struct MsmWorkspace {
     DevBuf batch;   // msm_run_batch: the base range's infinity flags, then one (point, flag) record per row of a group
 };
 
-// Window tables of a resident base vector (setup.hip: tables_build): point (w, i) = 2^(c w) P_i lives at
-// index w * stride + i of the table array.  c == 0: no tables (per-window Pippenger).
-// Windows are BALANCED: the 256 scalar bits (255 + signed-digit carry) are split into nwin windows of
-// width c or c - 1 (wider ones first), so no window is narrow -- with one shared bucket set a short top
-// window would pile all of its digits into a few hot buckets.
-struct MsmTables {
-    unsigned c = 0, nwin = 0;        // c = widest window; buckets = 2^(c-1)
-    unsigned off[33] = {0};          // bit offset of window w (off[nwin] = 256)
-    unsigned char width[32] = {0};   // bits of window w
-    // Radix m 2^a, the same for every window of the set (radix.cuh).  m = 1: the balanced power-of-two layout above (a unused).
-    // m = 5: point (w, i) = R^w P_i with R = 5 2^a, one shared set of R / 2 = 5 2^(a-1) buckets; c = a + 3 = ceil(log2 R), off[] and
-    // width[] stay zero.  Tables only, never wide.
-    unsigned m = 1, a = 0;
-    size_t stride = 0;               // points per window
+// Window tables of a resident base vector (setup.hip: tables_build) or, with wide, the plan of an MSM that runs without tables: the
+// layout (msm_plan.h: WindowLayout -- planned(), widest(), the bucket sets) plus where the points are.  Point (w, i) lives at index
+// w * stride + i of the table array.  Not planned: no tables (per-window Pippenger).
+struct MsmTables : WindowLayout {
+    size_t stride = 0;               // points per window (0 in wide mode)
     size_t base_index = 0;           // first point of this MSM inside window 0
     const unsigned char *inf = nullptr;   // device: one flag byte per point of window 0 (1 = point at infinity)
-    const void *table = nullptr;          // device: TablePoint<C>[nwin][stride]
-    // WIDE mode (table == nullptr, wide == true): no tables in HBM -- every window keeps its OWN set of 2^(c-1) buckets (key =
-    // w 2^(c-1) + bucket), the points are gathered from the plain base array, the nwin window sums are combined by a Horner
-    // chain of doublings on the host.  Same sort / accumulate / reduce kernels as the table mode, so c can be 19-20 (13-14
-    // additions per pair) where the LDS-histogram pipeline of one-shot MSMs is limited to c = 16.
-    bool wide = false;
+    const void *table = nullptr;          // device: TablePoint<C>[nwin][stride]; nullptr in wide mode
+    MsmTables() = default;
+    MsmTables(const WindowLayout &layout, size_t points_per_window) : WindowLayout(layout), stride(points_per_window) {}
 };
 
 // The vectors of `rows` proofs against one unsharded key as [rows][len] arrays (prove.hip / prove_batch.hip), reserved for the largest
@@ -409,7 +398,7 @@ int ntt_run_batch(pm_ctx *ctx, Fp<typename C::FrP> *d_data, unsigned log_n, bool
 template <class C>
 int twiddles_get(pm_ctx *ctx, unsigned log_n, bool inv_dir, const Fp<typename C::FrP> **out);
 
-// tables == nullptr (or c == 0): d_bases points at the MSM's first base.  Otherwise d_bases is unused, the
+// tables == nullptr (or not planned): d_bases points at the MSM's first base.  Otherwise d_bases is unused, the
 // points come from tables->table and tables->base_index locates the MSM's first base inside window 0.
 template <class C>
 int msm_run(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_scalars, size_t len,
@@ -431,34 +420,11 @@ int msm_resident_begin(pm_ctx *ctx, const pm_pk *pk, int which, const Fp<typenam
 template <class C>
 int msm_resident_end(pm_ctx *ctx, uint64_t *out_xy, int *out_inf);
 
-// msm_reduce.hip: the bucket reduction of the table-mode MSM (one set of NB >= 4096 buckets whose task partials sit in ctx->msm),
-// three launches on ctx->stream; *out = the sum sum_b (b + 1) B_b, internal form, inside the workspace.
+// msm_reduce.hip: the bucket reduction of the table-mode MSM over the sets of one ReduceShape (msm_plan.h; bucket_plan made and checked
+// it) whose task partials sit in ctx->msm, three launches on ctx->stream; *out = the sums sum_b (b + 1) B_b of the sets, internal
+// form, inside the workspace.  bucket0: first bucket of the first set.
 template <class C>
-int reduce_two_level(pm_ctx *ctx, size_t NB, XYZZ<C> **out, unsigned nsets = 1, size_t bucket0 = 0);   // bucket0: first bucket of the first set
-
-// The sort's first level (msm.hip: k_tbl_count / k_tbl_partition) splits the buckets into regions of 2^15, one region per scan lane
-// of a workgroup of at most 1024 lanes.
-constexpr unsigned SORT_REGION_BITS = 15, SORT_MAX_REGIONS = 1024;
-constexpr unsigned RADIX5_MAX_WINDOWS = 16;   // radix 5 2^a (radix.cuh): the first sort level is instantiated for 10 ... 16 windows
-
-// Wide mode: the bucket sets of a plan of nwin windows whose widest has c bits.  The 256 % nwin windows of c bits come first and own
-// `wide_b` = 2^(c-1) buckets each; the windows that are one bit narrower own `narrow_b`: half of that where it is still whole sort
-// regions (then n_narrow > 0), otherwise all nwin sets count as wide.  Planner (setup.hip: wide_plan), driver (msm.hip: bucket_plan)
-// and kernels (msm.hip: win_base) agree through this.
-struct WideSets {
-    size_t wide_b, narrow_b;
-    unsigned n_wide, n_narrow;
-    size_t total() const { return n_wide * wide_b + n_narrow * narrow_b; }
-};
-inline WideSets wide_sets(unsigned nwin, unsigned c) {
-    WideSets s;
-    s.wide_b = (size_t)1 << (c - 1);
-    const bool halve = 256 % nwin != 0 && (s.wide_b >> 1) >= ((size_t)1 << SORT_REGION_BITS);
-    s.narrow_b = halve ? s.wide_b >> 1 : s.wide_b;
-    s.n_wide = halve ? 256 % nwin : nwin;
-    s.n_narrow = nwin - s.n_wide;
-    return s;
-}
+int reduce_two_level(pm_ctx *ctx, const ReduceShape &shape, XYZZ<C> **out, size_t bucket0 = 0);
 
 // One bucket pipeline covers at most this many pairs (sorted-entry positions are u32: windows x pairs < 2^32); longer
 // MSMs run in pieces summed on the host.  2^27 in production; PM_OPT_MSM_MAX_PIECE_LOG (developer / test knob) lowers it
@@ -468,13 +434,6 @@ inline size_t msm_max_piece(const pm_ctx *ctx) {
     return (size_t)1 << (lg < 4 ? 4 : lg > 27 ? 27 : lg);
 }
 
-// choose c and the number of windows for a key whose longest MSM has `max_len` pairs
-void msm_plan_query(size_t len, unsigned scalar_bits, unsigned *nwin, unsigned *c);
-// force_c (PM_OPT_TABLE_WINDOW_BITS): 0; 4 ... 24, the widest window of the power-of-two layout; or 100 m + windows, the radix
-// m 2^a (m = 1 | 5, radix.cuh) on that many windows (0: as many as the cost model likes for that m)
-MsmTables tables_plan(size_t total_pairs, unsigned n_msm, size_t resident_points, unsigned scalar_bits, unsigned force_c = 0);
-// the plan of an MSM that gets no tables (MsmTables::wide); c == 0 if none applies (short MSMs: the per-window pipeline)
-MsmTables wide_plan(size_t piece, unsigned force_c = 0);
 // window 0 of d_table <- the `count` internal-form affine points at d_points; then windows 1..nwin-1
 template <class C>
 struct TablePoint;   // fq28.cuh: 128-byte, 28-bit-limb record

@@ -33,52 +33,10 @@
 
 #include "internal.h"
 #include "fq28.cuh"
-#include "radix.cuh"
 
 namespace pm {
 
 constexpr uint32_t DIGIT_NONE = 0xFFFFFFFFu;
-
-struct MsmPlan {
-    unsigned c, nwin, nbuckets;  // nbuckets = 2^(c-1) per window
-    unsigned seg;                // max entries per accumulate task
-    size_t len;
-    unsigned chunk, nchunks;     // scalars per histogram workgroup
-    size_t max_tasks;
-};
-
-static MsmPlan make_plan(size_t len, unsigned scalar_bits, unsigned task_len = 0) {
-    MsmPlan p;
-    p.len = len;
-    // choose c minimising  W(c) * (len + 6 * 2^(c-1))   (6 ~ cost of the reduce per bucket in madds)
-    double best = 1e300;
-    unsigned bc = 4;
-    for (unsigned c = 4; c <= 16; ++c) {
-        unsigned w = (scalar_bits + 1 + c - 1) / c;
-        double cost = (double)w * ((double)len + 6.0 * (double)(1u << (c - 1)));
-        if (cost < best) { best = cost; bc = c; }
-    }
-    p.c = bc;
-    p.nwin = (scalar_bits + 1 + bc - 1) / bc;
-    p.nbuckets = 1u << (bc - 1);
-    size_t avg = len / p.nbuckets + 1;
-    size_t seg = 2 * avg;
-    if (seg < 64) seg = 64;
-    p.seg = (unsigned)seg;
-    p.chunk = 1u << 15;   // scalars per (chunk, window) histogram / scatter workgroup (tools/msm_bench.py sweep)
-    if (len < p.chunk) p.chunk = (unsigned)(len ? len : 1);
-    p.nchunks = (unsigned)((len + p.chunk - 1) / p.chunk);
-    if (task_len) p.seg = task_len;   // PM_OPT_MSM_TASK_LEN (tuning sweeps)
-    p.max_tasks = (size_t)p.nwin * p.nbuckets + ((size_t)p.nwin * len) / p.seg + 1;
-    return p;
-}
-
-// windows (= bucket additions per pair) and window width the per-window pipeline picks for `len` pairs
-void msm_plan_query(size_t len, unsigned scalar_bits, unsigned *nwin, unsigned *c) {
-    MsmPlan p = make_plan(len ? len : 1, scalar_bits);
-    *nwin = p.nwin;
-    *c = p.c;
-}
 
 // ------------------------------------------------------------------------------ digits
 template <class C>
@@ -367,9 +325,7 @@ __global__ __launch_bounds__(128) void k_accumulate(const uint32_t *sorted, cons
 // Window sum S_w = sum_b (b+1) * B_b, B_b = sum of the bucket's task partials.  Lane j of the window
 // owns RED_K consecutive buckets [jK, jK+K):  sum (b+1) B_b = jK * A + sum_i (i+1) B_{jK+i}  with
 // A = running sum (descending), second term = sum of the running sums; jK * A by double-and-add
-// (jK < 2^c).  Everything on F28 registers; workgroup LDS tree, then k_sum_parts per window.
-// RED_K = 4 keeps the dependent chain short (8 adds + <= 15 doublings) and puts 8192 lanes on a window.
-constexpr unsigned RED_K = 4;
+// (jK < 2^c).  Everything on F28 registers; workgroup LDS tree, then k_sum_parts per window.  RED_K: msm_plan.h.
 
 // sh[threadIdx.x] holds each lane's value on entry; on exit sh[0] holds the workgroup sum
 template <class C>
@@ -501,7 +457,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 // scan + k_region_pass_staged<FINAL>; every scatter is staged through LDS and written out coalesced.
 // Reduction: k_reduce_level0 / k_reduce_level1 / k_sum_final (chains of dependent point additions).
 // =====================================================================================================
-constexpr unsigned LO_BITS = SORT_REGION_BITS;   // internal.h: 2^15 buckets per first-level region
+constexpr unsigned LO_BITS = SORT_REGION_BITS;   // msm_plan.h: 2^15 buckets per first-level region
 
 // Inclusive scan of one value per lane across the workgroup (blockDim <= 1024): wave shuffles + one LDS hop
 // (2 barriers; the LDS Hillis-Steele it replaces needed 2 log2(n)).  wt: 64 words of LDS scratch.
@@ -537,20 +493,8 @@ __device__ __forceinline__ Fp<P> canon_scalar(const Fp<P> *scalars, const unsign
     return k;
 }
 
-// signed digit w of canonical scalar k: returns false for a zero digit; bucket = |d| - 1
-// Balanced window layout as a function of the window count (the same formula as setup.hip: tables_layout).
-// The kernels are instantiated per NWIN so that every bit offset, shift and limb index is an immediate:
-// with a run-time layout the compiler parks the scalar in LDS and fetches offsets with vector loads.
-__host__ __device__ constexpr unsigned win_width(unsigned nwin, unsigned w) { return 256 / nwin + (w < 256 % nwin ? 1u : 0u); }
-__host__ __device__ constexpr unsigned win_off(unsigned nwin, unsigned w) { return w * (256 / nwin) + (w < 256 % nwin ? w : 256 % nwin); }
-// Wide mode (every window has its own bucket set): first bucket of window w's set.  The 256 % nwin windows that are one bit wider come
-// first (win_width) and own `wide_b` buckets each, the others `narrow_b` (round 6: half as many, where that is still whole sort
-// regions; until then every set had wide_b buckets: 12 windows of 22 / 21 bits held 12 x 2^21 = 25.2 M buckets instead of 16.8 M).
-// Table mode passes 0 for both: one shared set.
-__host__ __device__ constexpr uint32_t win_base(unsigned nwin, unsigned w, uint32_t wide_b, uint32_t narrow_b) {
-    return w <= 256 % nwin ? w * wide_b : (256 % nwin) * wide_b + (w - 256 % nwin) * narrow_b;
-}
-
+// signed digit of canonical scalar k in the window of c bits at bit lo (msm_plan.h: win_off / win_width / win_base, called with the
+// kernels' NWIN): returns false for a zero digit; bucket = |d| - 1
 template <class P>
 __device__ __forceinline__ bool digit_at(const Fp<P> &k, unsigned lo, unsigned c, uint32_t &carry, uint32_t &bucket, uint32_t &neg) {
     const uint32_t half = 1u << (c - 1), full = 1u << c, mask = full - 1;
@@ -1059,102 +1003,7 @@ __global__ __launch_bounds__(1024) void k_scan_small(const uint32_t *cnt, uint32
     if (t == 0) off[n] = carry;
 }
 
-// ------------------------------------------------------------------------------- the plan
-// Everything one bucket pipeline derives from its inputs before the first launch; the stages below read it and recompute nothing.
-// Three shapes: per-window (pipeline A: nwin sets of 2^(c-1) buckets, LDS-histogram sort), tables (one shared set, radix sort over
-// the window tables' indices) and wide (tables == wide == true: one set per window, radix sort, points from the plain base array).
-struct BucketPlan {
-    bool tables, wide;
-    unsigned nwin, c;                        // windows; bits of the widest
-    size_t len, E;                           // pairs; E = nwin * len, the most entries the sort can see
-    // the bucket sets, in bucket order: n_wide_sets of NB1 = 2^(c-1) buckets, then n_narrow_sets of NBn (wide mode, internal.h:
-    // wide_sets); NB = all of them.  Per-window: nwin sets of NB1; tables: one (radix 5 2^a: of 5 2^(a-1) buckets, in whole regions).
-    size_t NB1, NBn, NB;
-    unsigned n_wide_sets, n_narrow_sets;
-    uint32_t win_buckets, narrow_buckets;    // win_base()'s arguments: NB1 and NBn in wide mode, 0 for the shared set
-    size_t seg, max_tasks;                   // entries per accumulate task; bound on the number of tasks
-    unsigned chunk, nchunks;                 // per-window: scalars per histogram / scatter workgroup
-    // table-mode sort: regions of lo_buckets (2^15, or the whole of a smaller set); first-level workgroup and its dynamic LDS
-    unsigned lo_buckets, regions, pbd;
-    size_t plds, keys_bytes;
-    bool two_level;                          // msm_reduce.hip: reduce_two_level per group of sets; otherwise reduce_single_level
-    unsigned red_lanes, red_block, bpw;      // single-level reduction: lanes and workgroups per set
-    unsigned nsums;                          // window sums the pipeline hands to host_horner ...
-    unsigned char width[64];                 // ... and the doublings in front of each
-};
-
-// scalars per first-level workgroup of the table-mode sort: 512 up to 16 windows, 256 beyond (the staged entries take lanes x
-// windows x 8 bytes of LDS).  From 512 regions up (the 12-window wide plan of a 2^24-gate key: 4 x 2^21 + 8 x 2^20 buckets): 1024, so that a
-// workgroup's run inside a region is 24 entries (96 B of values), not 12 -- what the first level pays for is the length of that
-// run, not the number of regions: same-box A/B at 2^24 gates in profiles/r06_wide_ragged_sets_ab.txt (512 regions on 512 lanes:
-// sort + 5 ... 8 ms against 768 on 1024) and r06_wide_12_windows_ab.txt; 256 against 512 lanes below that: flat
-// (profiles/r05_sort_chunk_shapes_after_wide_loads.txt, (3)).  The radix-5 plans stay below that threshold and on 512 lanes: 11 windows
-// in 160 regions (runs of 35 entries) measured 3.56 ms of sort on 512 lanes against 3.68 on 1024 for the 21 M-pair [d]_1, 56.61 ...
-// 56.74 against 56.79 ... 56.96 ms per proof on one box (profiles/msm_radix5_ab.txt); 12 windows in 40 regions write runs of 150.
-constexpr unsigned PARTITION_LANES = 512, PARTITION_WIDE_LANES = 1024, PARTITION_WIDE_FROM = 512;
-
-// tb: the window tables or the wide plan of the MSM; nullptr (or c == 0): the per-window pipeline on `len` pairs of scalar_bits-bit scalars
-static int bucket_plan(const MsmTables *tb, size_t len, unsigned scalar_bits, long long task_len, BucketPlan &p) {
-    p = BucketPlan();
-    p.len = len;
-    p.tables = tb && tb->c;
-    if (!p.tables) {
-        const MsmPlan w = make_plan(len, scalar_bits, task_len > 0 ? (unsigned)task_len : 0u);
-        p.nwin = w.nwin; p.c = w.c; p.seg = w.seg; p.max_tasks = w.max_tasks; p.chunk = w.chunk; p.nchunks = w.nchunks;
-        p.NB1 = w.nbuckets;
-        p.n_wide_sets = w.nwin;
-        for (unsigned i = 0; i < w.nwin; ++i) p.width[i] = (unsigned char)w.c;
-    } else {
-        p.wide = tb->wide;
-        p.nwin = tb->nwin; p.c = tb->c;
-        if (p.nwin < 10 || p.nwin > 32) return PM_ERR_INVALID_ARG;      // the first level's instantiations (sort_first_level)
-        if (tb->m == 5) {
-            // radix 5 2^a: R / 2 = 5 2^(a-1) buckets -- 40 or 160 whole regions for the plans tables_plan chooses by itself; a
-            // forced small radix (tests) that is more than one region and not whole ones is padded with empty buckets, which
-            // the scan, the task order and the reduction pass over
-            if (p.wide || p.nwin > RADIX5_MAX_WINDOWS || tb->a < 11 || tb->a > 28) return PM_ERR_INVALID_ARG;
-            const size_t region = (size_t)1 << LO_BITS;
-            p.NB1 = (size_t)5 << (tb->a - 1);
-            if (p.NB1 > region) p.NB1 = (p.NB1 + region - 1) / region * region;
-        } else {
-            if (tb->m != 1) return PM_ERR_INVALID_ARG;
-            for (unsigned w = 0; w < p.nwin; ++w)                        // the kernels derive the layout from nwin alone
-                if (tb->off[w] != win_off(p.nwin, w) || tb->width[w] != win_width(p.nwin, w)) return PM_ERR_INVALID_ARG;
-            p.NB1 = (size_t)1 << (p.c - 1);
-        }
-        p.n_wide_sets = 1;
-        if (p.wide) {
-            const WideSets s = wide_sets(p.nwin, p.c);
-            p.NBn = s.narrow_b; p.n_wide_sets = s.n_wide; p.n_narrow_sets = s.n_narrow;
-            p.win_buckets = (uint32_t)p.NB1; p.narrow_buckets = (uint32_t)p.NBn;
-            for (unsigned w = 0; w < p.nwin; ++w) p.width[w] = tb->width[w];
-        }
-    }
-    p.NB = p.n_wide_sets * p.NB1 + p.n_narrow_sets * p.NBn;
-    p.E = (size_t)p.nwin * len;
-    p.nsums = p.n_wide_sets + p.n_narrow_sets;
-    p.red_lanes = (unsigned)((p.NB1 + RED_K - 1) / RED_K);
-    p.red_block = 64;
-    while (p.red_block < p.red_lanes && p.red_block < 256) p.red_block <<= 1;
-    p.bpw = (p.red_lanes + p.red_block - 1) / p.red_block;
-    if (!p.tables) return PM_OK;
-
-    p.lo_buckets = (unsigned)(p.NB < ((size_t)1 << LO_BITS) ? p.NB : ((size_t)1 << LO_BITS));
-    p.regions = (unsigned)(p.NB / p.lo_buckets);
-    if ((size_t)p.regions * p.lo_buckets != p.NB) return PM_ERR_INVALID_ARG;   // whole regions only
-    p.pbd = p.regions >= PARTITION_WIDE_FROM ? PARTITION_WIDE_LANES : p.nwin <= 16 ? PARTITION_LANES : 256;
-    if (p.regions > p.pbd || p.regions > SORT_MAX_REGIONS) return PM_ERR_INVALID_ARG;   // one region per scan lane; cnt[] / delta[] of k_tbl_partition
-    p.plds = 2 * SORT_MAX_REGIONS * 4 + (size_t)p.pbd * p.nwin * 8;
-    p.two_level = p.NB1 >= 4096;                                           // msm_reduce.hip: k_reduce_level0 / level1 / final
-    if (p.wide && !p.two_level) return PM_ERR_INVALID_ARG;                 // wide plans have c >= 16 (setup.hip: wide_plan)
-    p.seg = 2 * (p.E / p.NB + 1);
-    if (p.seg < 64) p.seg = 64;
-    if (task_len > 0) p.seg = (size_t)task_len;                            // PM_OPT_MSM_TASK_LEN (tuning sweeps)
-    p.max_tasks = p.NB + p.E / p.seg + 1;
-    p.keys_bytes = (p.E * 2 + 15) & ~(size_t)15;
-    return PM_OK;
-}
-
+// The plan every stage below reads -- BucketPlan, made by bucket_plan from the MSM's layout before the first launch -- is msm_plan.h's.
 // ------------------------------------------------------------------------------- shared stages
 // Each takes the context, the bucket set and the plan, and enqueues on ctx->stream.
 
@@ -1469,11 +1318,11 @@ static int msm_enqueue(pm_ctx *ctx, const BucketPlan &p, const MsmTables *tb, co
     if (!p.two_level) {
         PM_TRY(reduce_single_level<C>(ctx, S, p, &d_sums));
     } else {   // all sets of one size by ONE set of launches: those of the c-bit windows (or the shared set) ...
-        PM_TRY(reduce_two_level<C>(ctx, p.NB1, &d_sums, p.n_wide_sets));
+        PM_TRY(reduce_two_level<C>(ctx, p.reduce_wide, &d_sums));
     }
     PM_HIP(ctx, hipMemcpyAsync(h_sums, d_sums, p.n_wide_sets * sizeof(XYZZ<C>), hipMemcpyDeviceToHost, ctx->stream));
     if (p.n_narrow_sets) {   // ... then those of the (c - 1)-bit ones (stream order: the workspace is free again)
-        PM_TRY(reduce_two_level<C>(ctx, p.NBn, &d_sums, p.n_narrow_sets, (size_t)p.n_wide_sets * p.NB1));
+        PM_TRY(reduce_two_level<C>(ctx, p.reduce_narrow, &d_sums, (size_t)p.n_wide_sets * p.NB1));
         PM_HIP(ctx, hipMemcpyAsync(h_sums + p.n_wide_sets, d_sums, p.n_narrow_sets * sizeof(XYZZ<C>), hipMemcpyDeviceToHost, ctx->stream));
     }
     return PM_OK;
@@ -1484,7 +1333,7 @@ static int msm_enqueue(pm_ctx *ctx, const BucketPlan &p, const MsmTables *tb, co
 template <class C>
 int msm_run(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_scalars, size_t len, Affine<C> *h_out,
             int *h_inf, const MsmTables *tables) {
-    const bool tbl = tables && tables->c;
+    const bool tbl = tables && tables->planned();
     const size_t max_piece = msm_max_piece(ctx);
     XYZZ<C> acc = XYZZ<C>::identity();
     std::vector<XYZZ<C>> sums;
@@ -1497,7 +1346,7 @@ int msm_run(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_
             tb.base_index += off;
         }
         BucketPlan p;
-        PM_TRY(bucket_plan(tbl ? &tb : nullptr, cnt, (unsigned)C::FrP::BITS, ctx->opt.v[PM_OPT_MSM_TASK_LEN], p));
+        if (!bucket_plan(tb, cnt, (unsigned)C::FrP::BITS, ctx->opt.v[PM_OPT_MSM_TASK_LEN], p)) return PM_ERR_INVALID_ARG;   // tb not planned: per-window
         sums.resize(p.nsums);
         PM_TRY(msm_enqueue<C>(ctx, p, tbl ? &tb : nullptr, tbl ? d_bases : d_bases + off, d_scalars + off, sums.data()));
         PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1530,7 +1379,7 @@ int msm_run_batch(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::Fr
         return PM_OK;
     }
     BucketPlan row;
-    PM_TRY(bucket_plan(nullptr, len, (unsigned)C::FrP::BITS, ctx->opt.v[PM_OPT_MSM_TASK_LEN], row));
+    if (!bucket_plan(WindowLayout(), len, (unsigned)C::FrP::BITS, ctx->opt.v[PM_OPT_MSM_TASK_LEN], row)) return PM_ERR_INVALID_ARG;
     const size_t u32_max = 0xFFFFFFFFull;
     size_t group = max_piece / len;
     if (group > 65535 / row.nwin) group = 65535 / row.nwin;
@@ -1549,12 +1398,7 @@ int msm_run_batch(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::Fr
     for (size_t b0 = 0; b0 < batch; b0 += group) {
         StageTimer t_total(ctx, T_MSM_TOTAL);
         const size_t rows = batch - b0 < group ? batch - b0 : group;
-        BucketPlan p = row;
-        p.n_wide_sets = (unsigned)(rows * row.nwin);
-        p.nsums = p.n_wide_sets;
-        p.NB = rows * row.NB;
-        p.E = rows * row.E;
-        p.max_tasks = p.NB + p.E / p.seg + 1;
+        const BucketPlan p = bucket_plan_rows(row, rows);
         MsmSet &S = ws.set;
         PM_TRY(reserve_set<C>(ctx, S, p));
         {
@@ -1595,7 +1439,7 @@ int msm_run_batch(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::Fr
 template <class C>
 int msm_begin(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_scalars, size_t len, const MsmTables *tables) {
     ctx->msm_async = 0;
-    const bool tbl = tables && tables->c && !tables->wide;
+    const bool tbl = tables && tables->planned() && !tables->wide;
     if (!ctx_pinned(ctx)) { ctx->err = "pinned result slot allocation failed"; return PM_ERR_HIP; }
     if (len == 0 || !tbl || len > msm_max_piece(ctx)) {           // synchronous: result parked in the slot
         PM_TRY(msm_run<C>(ctx, d_bases, d_scalars, len, pinned_slot<Affine<C>>(ctx, PINNED_MSM_POINT), pinned_slot<int>(ctx, PINNED_MSM_INF), tables));
@@ -1604,7 +1448,7 @@ int msm_begin(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *
     }
     StageTimer t_total(ctx, T_MSM_TOTAL);
     BucketPlan p;
-    PM_TRY(bucket_plan(tables, len, (unsigned)C::FrP::BITS, ctx->opt.v[PM_OPT_MSM_TASK_LEN], p));   // one shared set: one sum
+    if (!bucket_plan(*tables, len, (unsigned)C::FrP::BITS, ctx->opt.v[PM_OPT_MSM_TASK_LEN], p)) return PM_ERR_INVALID_ARG;   // one shared set: one sum
     PM_TRY(msm_enqueue<C>(ctx, p, tables, d_bases, d_scalars, pinned_slot<XYZZ<C>>(ctx, PINNED_MSM_SUM)));
     ctx->msm_async = 1;
     return PM_OK;

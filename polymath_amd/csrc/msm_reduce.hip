@@ -231,50 +231,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     if (threadIdx.x == 0) out[blockIdx.x] = xyzz28_store<C>(sh[0]);
 }
 
-// sum_b (b + 1) B_b over each of `nsets` sets of NB buckets (set s = buckets [s NB, (s + 1) NB)) whose (folded) task partials sit in
-// ctx->msm: three launches on ctx->stream, the nsets results (internal form) at (*out)[0 .. nsets) in the workspace.  nsets = 1:
-// the shared bucket set of the window-table MSM; nsets = windows: the wide-window MSM without tables.
+// sum_b (b + 1) B_b over each of the shape's nsets sets of `buckets` buckets (set s = buckets [s NB, (s + 1) NB) from bucket0 on) whose
+// (folded) task partials sit in ctx->msm: three launches on ctx->stream, the nsets results (internal form) at (*out)[0 .. nsets) in
+// the workspace.  nsets = 1: the shared bucket set of the window-table MSM; several: one size of sets of the wide-window MSM without
+// tables.  K0, R1 and the lane counts: msm_plan.h: reduce_shape; bucket_plan has refused what the kernels cannot run.
 template <class C>
-int reduce_two_level(pm_ctx *ctx, size_t NB, XYZZ<C> **out, unsigned nsets, size_t bucket0) {
+int reduce_two_level(pm_ctx *ctx, const ReduceShape &sh, XYZZ<C> **out, size_t bucket0) {
     MsmWorkspace &ws = ctx->msm;
     const MsmSet *S = &ws.set;
-    if (nsets == 0 || NB == 0 || (nsets > 1 && (NB & (NB - 1)) != 0)) return PM_ERR_INVALID_ARG;   // several sets: powers of two (wide mode)
-    const size_t total = NB * nsets;
-    unsigned K0 = 4;                                   // level-0 fan-in: <= 2^17 lanes = 2 waves per SIMD, one round of the chip
-    if (nsets > 1 || (NB & (NB - 1)) == 0) {
-        while (total / K0 > ((size_t)1 << 17) && K0 < 64) K0 <<= 1;   // (swept in profiles/r02_levers.jsonl: K0 = 2 doubles level 1's work and loses)
-    } else {
-        // one set of any size (radix 5 2^a: 5 2^(a-1) buckets): K0 = ceil(NB / 2^17) as a plain integer -- 40 for 5.24 M buckets, 10 for
-        // 1.31 M.  The next power of two would leave the chip 62 % full on a chain 1.6 times as long (64 against 40).
-        const size_t k = (NB + ((size_t)1 << 17) - 1) >> 17;
-        if (k > K0) K0 = (unsigned)k;
-    }
-    // levels 1 and final on lane GROUPS (4 lanes per point, a share of the products each): 256 / LP points per workgroup, and
-    // R = 2 LP keeps level 1 at 2^16 lanes = one wave per SIMD (its register budget); K0 and R swept on MI355X in round 2
-    // (profiles/r02_levers.jsonl, r02_m_reduce_pair_sweep.txt)
-    constexpr unsigned coop = 4;
-    unsigned R1 = 2 * coop;
-    const unsigned per_block1 = 256 / coop;                   // points per level-1 workgroup
-    const size_t set_lanes = (NB + K0 - 1) / K0;              // level-0 outputs per bucket set
-    if (nsets > 1) {   // no level-1 workgroup may straddle two sets
-        while (set_lanes % ((size_t)R1 * per_block1) != 0 && R1 > 1) R1 >>= 1;
-        if (NB % K0 != 0 || set_lanes % ((size_t)R1 * per_block1) != 0) return PM_ERR_INVALID_ARG;
-    }
-    const size_t lanes0 = set_lanes * nsets, lanes1 = (lanes0 + R1 - 1) / R1, blocks0 = (lanes0 + 255) / 256,
-                 blocks1 = (lanes1 + per_block1 - 1) / per_block1;
-    PM_HIP(ctx, ws.wsum.reserve((2 * lanes0 + (blocks0 > blocks1 ? blocks0 : blocks1) + 4 + nsets) * sizeof(XYZZ<C>)));
-    XYZZ<C> *A = ws.wsum.as<XYZZ<C>>(), *Acc = A + lanes0, *parts = Acc + lanes0, *dres = parts + (blocks0 > blocks1 ? blocks0 : blocks1);
-    PM_LAUNCH(ctx, k_reduce_level0<C>, dim3((unsigned)blocks0), dim3(256), 256 * sizeof(XYZZ28<C>), ctx->stream,
-                   S->partials.as<XYZZ<C>>(), S->task_off.as<uint32_t>() + bucket0, S->task_cnt.as<uint32_t>() + bucket0, total, lanes0, K0, A, Acc);
-    const unsigned per_set = (unsigned)(blocks1 / nsets);     // level-1 workgroups (= partials) per set; exact when nsets > 1
-    PM_LAUNCH(ctx, (k_reduce_level1_coop<C, 4>), dim3((unsigned)blocks1), dim3(256), 64 * sizeof(XYZZ28<C>), ctx->stream, A, Acc,
-                   lanes0, K0, R1, parts, set_lanes);
-    PM_LAUNCH(ctx, (k_sum_final_coop<C, 4>), dim3(nsets), dim3(256), 64 * sizeof(XYZZ28<C>), ctx->stream, parts, per_set, dres);
+    const size_t most_blocks = sh.blocks0 > sh.blocks1 ? sh.blocks0 : sh.blocks1;
+    PM_HIP(ctx, ws.wsum.reserve((2 * sh.lanes0 + most_blocks + 4 + sh.nsets) * sizeof(XYZZ<C>)));
+    XYZZ<C> *A = ws.wsum.as<XYZZ<C>>(), *Acc = A + sh.lanes0, *parts = Acc + sh.lanes0, *dres = parts + most_blocks;
+    PM_LAUNCH(ctx, k_reduce_level0<C>, dim3((unsigned)sh.blocks0), dim3(256), 256 * sizeof(XYZZ28<C>), ctx->stream,
+                   S->partials.as<XYZZ<C>>(), S->task_off.as<uint32_t>() + bucket0, S->task_cnt.as<uint32_t>() + bucket0, sh.buckets * sh.nsets, sh.lanes0,
+                   sh.K0, A, Acc);
+    const unsigned per_set = (unsigned)(sh.blocks1 / sh.nsets);     // level-1 workgroups (= partials) per set; exact when nsets > 1
+    PM_LAUNCH(ctx, (k_reduce_level1_coop<C, REDUCE_COOP>), dim3((unsigned)sh.blocks1), dim3(256), 256 / REDUCE_COOP * sizeof(XYZZ28<C>), ctx->stream,
+                   A, Acc, sh.lanes0, sh.K0, sh.R1, parts, sh.set_lanes);
+    PM_LAUNCH(ctx, (k_sum_final_coop<C, REDUCE_COOP>), dim3(sh.nsets), dim3(256), 256 / REDUCE_COOP * sizeof(XYZZ28<C>), ctx->stream, parts, per_set, dres);
     *out = dres;
     return PM_OK;
 }
 
-template int reduce_two_level<BlsCurve>(pm_ctx *, size_t, XYZZ<BlsCurve> **, unsigned, size_t);
-template int reduce_two_level<BnCurve>(pm_ctx *, size_t, XYZZ<BnCurve> **, unsigned, size_t);
+template int reduce_two_level<BlsCurve>(pm_ctx *, const ReduceShape &, XYZZ<BlsCurve> **, size_t);
+template int reduce_two_level<BnCurve>(pm_ctx *, const ReduceShape &, XYZZ<BnCurve> **, size_t);
 
 }  // namespace pm

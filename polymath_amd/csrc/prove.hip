@@ -23,7 +23,7 @@ int msm_resident(pm_ctx *ctx, const pm_pk *pk, int which, const Fp<typename C::F
     const Affine<C> *bases = (const Affine<C> *)pk->d_bases + pk->res_dev_off[which];
     Affine<C> r;
     int inf = 1;
-    if (pk->tables[which].c) {   // this MSM's own window tables (window 0 = its resident pairs), or the wide mode on the plain array
+    if (pk->tables[which].planned()) {   // this MSM's own window tables (window 0 = its resident pairs), or the wide mode on the plain array
         MsmTables tb = pk->tables[which];
         tb.base_index = 0;
         PM_TRY(msm_run<C>(ctx, tb.wide ? bases : (const Affine<C> *)nullptr, d_scalars, (size_t)pk->res_cnt[which], &r, &inf, &tb));
@@ -40,7 +40,7 @@ int msm_resident_begin(pm_ctx *ctx, const pm_pk *pk, int which, const Fp<typenam
     const Affine<C> *bases = (const Affine<C> *)pk->d_bases + pk->res_dev_off[which];
     if (count == 0) { lo = 0; count = pk->res_cnt[which]; }
     if (lo + count > pk->res_cnt[which]) return PM_ERR_INVALID_ARG;
-    if (pk->tables[which].c) {
+    if (pk->tables[which].planned()) {
         MsmTables tb = pk->tables[which];
         tb.base_index = (size_t)lo;
         return msm_begin<C>(ctx, tb.wide ? bases : (const Affine<C> *)nullptr, d_scalars + lo, (size_t)count, &tb);

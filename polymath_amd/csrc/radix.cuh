@@ -1,4 +1,4 @@
-// Window radix R = m 2^a of the table-mode MSM (m = 5; m = 1 is the ragged power-of-two layout of msm.hip: win_off / win_width).
+// Window radix R = m 2^a of the table-mode MSM (m = 5; m = 1 is the ragged power-of-two layout of msm_plan.h: win_off / win_width).
 //
 // A power-of-two radix quantises the window count: 12 windows need 22-bit digits (2^21 buckets, two thirds of the windows fill only
 // the lower half), 11 need 2^23 buckets.  R = 5 2^a sits between: 12 windows on 5 2^19 (1.31 M buckets), 11 on 5 2^21 (5.24 M).
@@ -6,7 +6,7 @@
 // long division from the top limb, a 3-bit remainder and a multiply-high by the reciprocal of 5 -- no hardware division), then
 // msm.hip's signed-digit rule with full = R, half = R / 2.
 //
-// Plain C++: the kernels of msm.hip, the planner of setup.hip and the CPU self-test (tests/native/radix_selftest.cpp) share it.
+// Plain C++: the kernels of msm.hip, the planners of msm_plan.h and the CPU self-tests (tests/native/radix_selftest.cpp, msm_plan_selftest.cpp) share it.
 // Every shift, limb count and limb index below is a compile-time constant of (windows, a): the recursion over the window index is
 // what makes them so (a loop over a run-time layout makes the compiler park the scalar in LDS, see msm.hip: digit_at).
 #pragma once

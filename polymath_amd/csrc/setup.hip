@@ -11,7 +11,6 @@
 #include <algorithm>
 #include "fq28.cuh"
 #include "prove_common.cuh"
-#include "radix.cuh"
 
 namespace pm {
 
@@ -267,15 +266,15 @@ __global__ __launch_bounds__(128) void k_table_next(const TablePoint<C> *prev, T
 
 template <class C>
 int tables_build(pm_ctx *ctx, const Affine<C> *d_points, TablePoint<C> *d_table, size_t count, const MsmTables &t) {
-    if (!t.c || !count) return PM_OK;
+    if (!t.planned() || !count) return PM_OK;
     PM_LAUNCH(ctx, k_table_window0<C>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, d_points, d_table, count);
     size_t lanes = (count + TB_BATCH - 1) / TB_BATCH;
     if (t.m != 1 && t.m != 5) return PM_ERR_INVALID_ARG;
-    for (unsigned w = 1; w < t.nwin; ++w) {   // T_w = 2^(width of window w-1) * T_{w-1}; radix 5 2^a: T_w = 5 2^a T_{w-1}
+    for (unsigned w = 1; w < t.nwin; ++w) {   // T_w = 2^(win_width of window w-1) * T_{w-1}; radix 5 2^a: T_w = 5 2^a T_{w-1}
         const TablePoint<C> *prev = d_table + (size_t)(w - 1) * t.stride;
         TablePoint<C> *next = d_table + (size_t)w * t.stride;
         if (t.m == 5) PM_LAUNCH(ctx, (k_table_next<C, 5>), dim3((unsigned)((lanes + 127) / 128)), dim3(128), 0, ctx->stream, prev, next, count, t.a);
-        else PM_LAUNCH(ctx, (k_table_next<C, 1>), dim3((unsigned)((lanes + 127) / 128)), dim3(128), 0, ctx->stream, prev, next, count, (unsigned)t.width[w - 1]);
+        else PM_LAUNCH(ctx, (k_table_next<C, 1>), dim3((unsigned)((lanes + 127) / 128)), dim3(128), 0, ctx->stream, prev, next, count, win_width(t.nwin, w - 1));
     }
     PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PM_OK;
@@ -297,123 +296,6 @@ int infinity_flags(pm_ctx *ctx, const Affine<C> *d_points, size_t count, unsigne
     if (!count) return PM_OK;
     PM_LAUNCH(ctx, k_inf_flags<C>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, d_points, count, d_flags);
     return PM_OK;
-}
-
-// Layout of one table set.  Cost model in units of one mixed add at full throughput (0.148 ns measured,
-// 6.75 G adds/s):  E = W * pairs bucket entries;
-//   accumulate = max(E, (E / buckets) * 135e3)   one lane per bucket: a lane's chain of mixed adds costs ~20 us
-//                                                each, so few, long buckets leave the machine latency-bound;
-//   reduce     = 8.1e6 + 2.7 * buckets           measured 1.41 ms at 2^19 and 2.04 ms at 2^21 buckets: a
-//                                                fixed dependent-add chain plus 2 full adds per bucket;
-// subject to W * resident < 2^31 (u32 table indices).
-static void tables_layout(MsmTables &t, unsigned nwin) {
-    const unsigned total = 256, base = total / nwin, rem = total % nwin;
-    t.nwin = nwin;
-    unsigned off = 0;
-    for (unsigned w = 0; w < nwin; ++w) {
-        t.off[w] = off;
-        t.width[w] = (unsigned char)(base + (w < rem ? 1 : 0));
-        off += t.width[w];
-    }
-    t.off[nwin] = off;
-    t.c = base + (rem ? 1 : 0);
-}
-
-// Radix 5 2^a on nwin windows (radix.cuh): a = the smallest shift for which the top digit of the curve's scalars never carries
-// out -- (r - 1) div R^(nwin-1) + 1 <= R / 2 in exact integer arithmetic; a plan that fails it is rejected (t.c stays 0).
-// 10 ... 16 windows: the instantiations of the first sort level (msm.hip: sort_first_level).
-static void tables_layout_radix5(MsmTables &t, unsigned nwin, unsigned scalar_bits) {
-    t = MsmTables();
-    if (nwin < 10 || nwin > RADIX5_MAX_WINDOWS) return;
-    const unsigned a = scalar_bits == (unsigned)BlsFrP::BITS ? radix_min_shift<BlsFrP>(5, nwin) : radix_min_shift<BnFrP>(5, nwin);
-    if (!a || !(scalar_bits == (unsigned)BlsFrP::BITS ? radix_top_fits<BlsFrP>(5, nwin, a) : radix_top_fits<BnFrP>(5, nwin, a))) return;
-    t.nwin = nwin;
-    t.m = 5;
-    t.a = a;
-    t.c = a + 3;                  // ceil(log2 R): what pm_pk_msm_plan reports
-}
-
-// Radix 5 2^a joins the enumeration for long MSMs only: below 2^22 pairs the model's two candidates differ by less than its error,
-// and the [a]_1 MSM, the shards of a sharded key and short resident vectors keep the power-of-two plans they were measured with.
-constexpr size_t RADIX5_MIN_PAIRS = (size_t)1 << 22;
-
-MsmTables tables_plan(size_t total_pairs, unsigned n_msm, size_t resident_points, unsigned scalar_bits, unsigned force_c) {
-    // PM_OPT_TABLE_WINDOW_BITS = 100 m + windows (developer knob: tests, same-box A/Bs): the radix's multiplier and the window count
-    const unsigned force_m = force_c >= 100 ? force_c / 100 : 0, force_w = force_c >= 100 ? force_c % 100 : 0;
-    if (force_c >= 100 && ((force_m != 1 && force_m != 5) || (force_w && (force_w < 10 || force_w > 32)))) return MsmTables();
-    MsmTables best_t;
-    double best = 1e300;
-    for (unsigned nwin = 10; nwin <= 32; ++nwin)
-        for (unsigned m = 1; m <= 5; m += 4) {
-            if (force_m ? m != force_m : m == 5 && total_pairs < RADIX5_MIN_PAIRS) continue;
-            if (force_w && nwin != force_w) continue;
-            MsmTables t;
-            double NB;
-            if (m == 1) {
-                tables_layout(t, nwin);
-                if (t.c < 4 || t.c > 23) continue;
-                NB = (double)((size_t)1 << (t.c - 1));
-            } else {
-                tables_layout_radix5(t, nwin, scalar_bits);
-                if (!t.c) continue;
-                if (!force_w && t.a < SORT_REGION_BITS + 1) continue;       // whole 2^15-bucket regions (msm.hip: bucket_plan pads the others)
-                NB = 5.0 * (double)((size_t)1 << (t.a - 1));
-            }
-            if ((double)nwin * (double)resident_points >= 2147483648.0) continue;
-            const double E = (double)nwin * (double)total_pairs;
-            const double acc = std::max(E, E / NB * 135e3);
-            // bucket reduction + the sort's fixed part, in units of one accumulated entry (0.142 ns): the four-lane reduction measures
-            // 0.66 ms at 2^19 buckets and 1.39 ms at 2^21 (profiles/r02_m_reduce_pair_sweep.txt) = 2.9e6 + 3.3 NB, plus ~0.4e6 of sort launches.
-            // Refit on the 21 M-pair [d]_1 of a 2^20-gate proof (profiles/msm_radix5_ab.txt): 0.131 ns per accumulated entry at 11 and at
-            // 12 windows; reduction 0.95 / 1.39 / 2.68 ms at 1.31 M / 2.10 M / 5.24 M buckets = 0.375 ms + 0.44 ns (3.3 entries) per bucket:
-            // both constants stand, and with them every power-of-two plan.  Radix 5 2^a pays two more terms: its recoding in the two
-            // kernels of the first sort level, 0.41 ms for 21 M scalars = 0.15 entries per pair, and the bucket-side passes of the sort
-            // (memset, scan, task bins), 0.19 ms for 3.1 M more buckets = 0.45 entries per bucket -- which the power-of-two plans pay as
-            // well, but their fit never held it.
-            double cost = acc + (double)n_msm * (3.3e6 + 3.3 * NB);
-            if (m == 5) cost += 0.15 * (double)total_pairs + (double)n_msm * 0.45 * NB;
-            if (cost < best) { best = cost; best_t = t; }
-        }
-    // PM_OPT_TABLE_WINDOW_BITS (developer knob for tuning sweeps): widest window; 24 = the 11-window experiment (profiles/r02_levers_*.jsonl)
-    if (force_c >= 4 && force_c <= 24) {
-        best_t = MsmTables();
-        tables_layout(best_t, (256 + force_c - 1) / force_c);
-    }
-    best_t.stride = resident_points;
-    return best_t;
-}
-
-// Plan of the WIDE mode (no tables: MsmTables::wide): every window has its own bucket set -- 2^(c-1) buckets for the 256 % nwin
-// windows of c bits, half as many for the others (round 6: internal.h: wide_sets; until then 2^(c-1) for all: 12 windows
-// of 22 / 21 bits reduced 25.2 M buckets instead of 16.8 M and sorted into 768 regions instead of 512).  piece = the pairs one
-// bucket pipeline covers (<= msm_max_piece()).  Cost in the units of tables_plan: accumulation of nwin x piece entries + the
-// reduction of all sets, within the sort front end's limit of SORT_MAX_REGIONS regions of 2^15 buckets (k_tbl_partition: one region
-// per scan lane; msm.hip: bucket_plan holds the plan to the workgroup's lanes) and >= 4096 buckets per window (the two-level
-// reduction).  12 windows are the fewest whose widest window (22 bits) passes the c <= 23 test, and where long MSMs land: 12
-// additions per pair where the LDS-histogram pipeline of the one-shot MSM stops at c = 16 (16 additions), in 512 regions (same-box
-// A/B against round 5's 512-region plan of 13 windows: profiles/r06_wide_12_windows_ab.txt).  force_c (PM_OPT_TABLE_WINDOW_BITS,
-// tuning / tests): the widest window, whatever the cost model says.
-MsmTables wide_plan(size_t piece, unsigned force_c) {
-    MsmTables best_t;
-    double best = 1e300;
-    for (unsigned nwin = 12; nwin <= 16; ++nwin) {
-        MsmTables t;
-        tables_layout(t, nwin);
-        if (t.c < 16 || t.c > 23) continue;                                   // whole 2^15-bucket regions per window (the sort's first level)
-        const double NBT = (double)wide_sets(nwin, t.c).total();               // all sets: the narrower windows own half as many (round 6)
-        if (NBT / 32768.0 > (double)SORT_MAX_REGIONS) continue;
-        if ((double)nwin * (double)piece >= 4294967296.0) continue;          // u32 positions of the sorted entries
-        if (force_c >= 16 && force_c <= 23) {
-            if (t.c == force_c) { best_t = t; break; }
-            continue;
-        }
-        const double E = (double)nwin * (double)piece;
-        const double cost = std::max(E, E / NBT * 135e3) + 3.3e6 + 3.3 * NBT;   // the sets are reduced in one or two batched launches
-        if (cost < best) { best = cost; best_t = t; }
-    }
-    best_t.wide = best_t.c != 0;
-    best_t.stride = 0;
-    return best_t;
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -155,7 +155,7 @@ def msm_two_references(curve, hb, ks, scalars, key=None, nthreads=16):
 
 
 def per_window_bits(n, scalar_bits):
-    """Window width of the per-window pipeline for n pairs (mirror of msm.hip: make_plan -- used only to AIM the probes)."""
+    """Window width of the per-window pipeline for n pairs (mirror of msm_plan.h: per_window_bits -- used only to AIM the probes)."""
     best, bc = None, 4
     for c in range(4, 17):
         cost = ((scalar_bits + c) // c) * (n + 6 * (1 << (c - 1)))
