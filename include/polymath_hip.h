@@ -310,12 +310,29 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  *     no unknown column                       -- a check row, skipped
  *     one unknown u, in exactly one of them   -- z_u = (Az Bz - C_rest) / coef   (u in C)
  *                                                z_u = (Cz / Bz - A_rest) / coef (u in A; u in B alike with Az), and u is known from here on
- *     anything else                           -- two or more unknowns, or one unknown in two of the three (b (1 - b) = 0): unsolvable
+ *     a booleanity row                        -- the only unknown is u, C_r has no non-zero entry and {A_r, B_r} = {k z_u, k' (1 - z_u)} in
+ *                                                either order, k, k' != 0: one side is the single entry (k, u), the other exactly the two
+ *                                                entries (k', column 0) and (-k', u).  It marks u BOOLEAN-PENDING and is otherwise a check row
+ *     a decomposition row                     -- k >= 2 unknowns, all boolean-pending, all in the same one of A, B, C and in neither of the
+ *                                                others, with coefficients c 2^0 ... c 2^(k-1), each exactly once in any stored order, c != 0,
+ *                                                k <= bitlength(r) - 1 (254 on BLS12-381's Fr, 253 on BN254's: the solution is then unique).
+ *                                                ONE step for all k columns: t = the ordinary formula of that matrix with the k entries left
+ *                                                out and coef = c; z_{u_i} = bit i of the canonical integer of t, as field 0 or field 1
+ *     anything else                           -- two or more unknowns that are no decomposition, or one unknown in two of the three in any
+ *                                                other shape (u u = ..., a constant other than minus the coefficient, a non-empty C, further
+ *                                                entries): unsolvable
+ *   A boolean-pending column that is the single unknown of a later ordinary row is solved by that row; its booleanity row is then a
+ *   constraint like any other, which the check reports if the value is not 0 or 1.  One that is still pending when the rows end is
+ *   unsolvable: its booleanity row (the smallest such row) and column are named.  Booleanity rows that come AFTER the decomposition row
+ *   are not looked for: that decomposition row is refused.  XOR, AND, rotations and recompositions are ordinary one-unknown rows, so
+ *   range checks, comparisons, modular additions and ARX hashes complete.  Not solved: the is-zero / inverse-or-zero gadget (its value
+ *   is not unique), bits spread over two matrices, signed or non-binary digits.
  *   PM_ERR_INVALID_ARG, pm_last_error naming the row or column, nothing computed and no output written: an unsolvable row, a marked
  *   column that no row determines, a marker at column 0, a sharded key, and -- in a batch -- an assignment that does not mark the
  *   columns assignment 0 marks (the first differing (assignment, column) is named; a kernel compares them).
  *   At run time a step that would divide by zero (Bz = 0 with u in A) leaves that assignment STUCK, even where Cz = 0 too (the value
- *   is then undetermined): its other solved values are undefined, its neighbours are not affected, and its smallest stuck row is
+ *   is then undetermined), and so does a decomposition whose t is 2^k or more (no boolean solution; its k values are stored as
+ *   zero): its other solved values are undefined, its neighbours are not affected, and its smallest stuck row is
  *   reported (a 64-bit atomic minimum: the same word on every run, since everything downstream of a stuck row has a larger index):
  *     pm_r1cs_check[_batch]   n_bad[i] = UINT64_MAX, rows[i][0] = the stuck row (max_rows > 0), the other slots UINT64_MAX, abc zero
  *     pm_host_prove_batch     status[i] = PM_ERR_INVALID_ARG, zeroed bytes

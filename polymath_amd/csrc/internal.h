@@ -169,7 +169,7 @@ struct ProveWs {
 // call with PM_ASSIGNMENT_SOLVE.  xw: the completed x || w rows of a check call (pm_prove_tap(10)); the prover completes its groups in
 // its own workspace (ProveWs::xw) and keeps only tap9.
 struct SolveWs {
-    DevBuf xw, pattern, mismatch, stuck, steps;
+    DevBuf xw, pattern, mismatch, stuck, steps, bit_cols;
     pmsolve::Plan plan;
     uint64_t plan_key = 0;               // pm_pk::serial of the plan's key; 0 = no plan
     std::vector<uint8_t> plan_pattern;   // one byte per column
@@ -177,7 +177,7 @@ struct SolveWs {
     size_t tap10_rows = 0;               // pm_prove_tap(10): rows of xw that hold a check call's completed assignments; 0 = none
     size_t tap10_cols = 0;
     void release() {
-        for (DevBuf *b : {&xw, &pattern, &mismatch, &stuck, &steps}) b->release();
+        for (DevBuf *b : {&xw, &pattern, &mismatch, &stuck, &steps, &bit_cols}) b->release();
     }
 };
 

@@ -7,13 +7,16 @@
 //   k_solve_inv       one lane per step, once per plan: 1 / coefficient of the step's unknown
 //   k_solve_level     a WIDE dependency level: one lane per (step, assignment); a level is its own launch, so stream order is
 //                     the dependency order
+//   k_solve_bits      the bit decompositions of a wide level, one lane per (step, assignment) as well: a launch of their own, so
+//                     that lanes doing one store do not sit beside lanes doing k
 //   k_solve_chain     a run of consecutive NARROW levels: one lane per assignment walks the run's steps in plan order.  A lane
 //                     reads back only its own stores: no barriers, no fences.  The MiMC shape (depth 644, width 1) is one such run
 //                     and the batch is its parallel dimension.
-// The two solving kernels exist twice: DIV = false for ranges of kind-C steps only, DIV = true for ranges with kind-A / kind-B steps,
+// The solving kernels exist twice: DIV = false for ranges of kind-C steps only, DIV = true for ranges with kind-A / kind-B steps,
 // which call inverse<P> (a Fermat chain) -- the plan sorts a level by kind, so kind-C ranges do not carry its registers.
 // A step that would divide by zero stores zero and lowers the assignment's stuck word to its row (64-bit atomic minimum: the same
-// word on every run).  Every other store has one writer.  Plain C++ and vector stores only.
+// word on every run); so does a decomposition whose value has no k-bit form, in all its k columns.  Every other store has one
+// writer.  Plain C++ and vector stores only.
 #include <cstring>
 #include <vector>
 
@@ -26,8 +29,8 @@ constexpr uint64_t SOLVE_NONE = ~(uint64_t)0;   // no stuck row / no mismatch / 
 
 template <class P>
 struct SolveStepDev {
-    uint64_t pos;                    // the unknown's entry in its matrix
-    uint32_t row, col, kind, pad;
+    uint64_t pos;                    // the unknown's entry in its matrix; a decomposition: the entry that holds c
+    uint32_t row, col, kind, bits;   // bits != 0: a decomposition into the columns bit_cols[col .. col + bits), exponent order
     Fp<P> inv;                       // 1 / coefficient (k_solve_inv)
 };
 
@@ -59,11 +62,14 @@ __device__ __forceinline__ const CsrDev &matrix_of(uint32_t kind, const CsrDev &
     return kind == pmsolve::KIND_A ? A : kind == pmsolve::KIND_B ? B : Cm;
 }
 
+// KIND_BITS_x -> KIND_x
+__device__ __forceinline__ uint32_t matrix_kind(uint32_t kind) { return kind >= pmsolve::KIND_BITS_C ? kind - pmsolve::KIND_BITS_C : kind; }
+
 template <class P>
 __global__ __launch_bounds__(256) void k_solve_inv(CsrDev A, CsrDev B, CsrDev Cm, SolveStepDev<P> *steps, uint64_t count) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count) return;
-    const Fp<P> coef = *(const Fp<P> *)(matrix_of(steps[t].kind, A, B, Cm).val + 4 * steps[t].pos);
+    const Fp<P> coef = *(const Fp<P> *)(matrix_of(matrix_kind(steps[t].kind), A, B, Cm).val + 4 * steps[t].pos);
     steps[t].inv = coef.eq(Fp<P>::one()) ? coef : inverse<P>(coef);
 }
 
@@ -74,6 +80,20 @@ __device__ __forceinline__ Fp<P> row_dot_skip(const CsrDev &M, const Fp<P> *z, u
     for (uint64_t k = M.rowptr[r]; k < M.rowptr[r + 1]; ++k) {
         if (k == skip) continue;
         acc = add<P>(acc, mul<P>(*(const Fp<P> *)(M.val + 4 * k), z[M.col[k]]));
+    }
+    return acc;
+}
+
+// (M z)_r without the entries whose value is still the marker.  In a decomposition row those are exactly its k unknowns: every other
+// column the row names was given (never a marker) or was stored by an earlier level or an earlier step of this lane (a field
+// element, zero where that step was stuck).
+template <class P>
+__device__ __forceinline__ Fp<P> row_dot_unmarked(const CsrDev &M, const Fp<P> *z, uint64_t r) {
+    Fp<P> acc = Fp<P>::zero();
+    for (uint64_t k = M.rowptr[r]; k < M.rowptr[r + 1]; ++k) {
+        const Fp<P> v = z[M.col[k]];
+        if (is_marker<P>(v)) continue;
+        acc = add<P>(acc, mul<P>(*(const Fp<P> *)(M.val + 4 * k), v));
     }
     return acc;
 }
@@ -103,6 +123,53 @@ __device__ __forceinline__ void solve_step(const CsrDev &A, const CsrDev &B, con
     z[s.col] = mul<P>(v, s.inv);
 }
 
+// one decomposition on one assignment: t = (the unknown part of the row) / c with the k unknown entries left out of the dot
+// product -- their columns still hold the marker, and row_dot_unmarked passes over markers -- then z_{cols[i]} = bit i of the
+// canonical integer of t, as field 0 or field 1.  t >= 2^k has no such form: stuck, like a zero divisor, with zero in all k columns.
+template <class P, bool DIV>
+__device__ __forceinline__ void solve_bits(const CsrDev &A, const CsrDev &B, const CsrDev &Cm, const SolveStepDev<P> &s, const uint32_t *__restrict__ bit_cols,
+                                           Fp<P> *z, unsigned long long *stuck) {
+    const uint64_t r = s.row;
+    const uint32_t kind = matrix_kind(s.kind), k = s.bits;
+    const uint32_t *cols = bit_cols + s.col;
+    const Fp<P> az = kind == pmsolve::KIND_A ? row_dot_unmarked<P>(A, z, r) : row_dot_skip<P>(A, z, r, SOLVE_NONE);
+    const Fp<P> bz = kind == pmsolve::KIND_B ? row_dot_unmarked<P>(B, z, r) : row_dot_skip<P>(B, z, r, SOLVE_NONE);
+    const Fp<P> cz = kind == pmsolve::KIND_C ? row_dot_unmarked<P>(Cm, z, r) : row_dot_skip<P>(Cm, z, r, SOLVE_NONE);
+    Fp<P> v = Fp<P>::zero();
+    bool ok = true;
+    if (!DIV || kind == pmsolve::KIND_C) {
+        v = sub<P>(mul<P>(az, bz), cz);
+    } else {
+        const Fp<P> den = kind == pmsolve::KIND_A ? bz : az, rest = kind == pmsolve::KIND_A ? az : bz;
+        ok = !den.is_zero();
+        if (ok) v = sub<P>(mul<P>(cz, inverse<P>(den)), rest);
+    }
+    Fp<P> t = Fp<P>::zero();
+    if (ok) {
+        t = from_mont<P>(mul<P>(v, s.inv));
+        uint32_t high = 0;           // the bits of t from k upwards; k <= bitlength(r) - 1 < 32 N
+#pragma unroll
+        for (int i = 0; i < P::N; ++i) high |= 32u * i >= k ? t.l[i] : 32u * (i + 1) > k ? t.l[i] >> (k - 32u * i) : 0u;
+        ok = high == 0;
+    }
+    if (!ok) {
+        atomicMin(stuck, (unsigned long long)r);
+        t = Fp<P>::zero();
+    }
+    for (uint32_t i = 0; i < k; i += 32) {
+        uint32_t word = 0;
+#pragma unroll
+        for (int w = 0; w < P::N; ++w) word = i == 32u * w ? t.l[w] : word;   // t.l[i / 32] without indexing registers
+        for (uint32_t j = i; j < k && j < i + 32; ++j) {
+            const uint32_t mask = 0u - ((word >> (j - i)) & 1u);              // one & mask: field 1 or field 0, no table to select from
+            Fp<P> bit;
+#pragma unroll
+            for (int w = 0; w < P::N; ++w) bit.l[w] = P::ONE[w] & mask;
+            z[cols[j]] = bit;
+        }
+    }
+}
+
 template <class P, bool DIV>
 __global__ __launch_bounds__(256) void k_solve_level(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, uint32_t lo, uint32_t hi,
                                                      Fp<P> *xw, uint64_t ncols, unsigned long long *stuck) {
@@ -111,14 +178,25 @@ __global__ __launch_bounds__(256) void k_solve_level(CsrDev A, CsrDev B, CsrDev 
     solve_step<P, DIV>(A, B, Cm, steps[t], xw + b * ncols, stuck + b);
 }
 
-// the step index is the same in every lane: the step record and the row's CSR metadata are uniform loads
 template <class P, bool DIV>
-__global__ __launch_bounds__(64) void k_solve_chain(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, uint32_t lo, uint32_t hi,
-                                                    Fp<P> *xw, uint64_t ncols, unsigned long long *stuck, uint64_t rows) {
+__global__ __launch_bounds__(256) void k_solve_bits(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, const uint32_t *__restrict__ bit_cols,
+                                                    uint32_t lo, uint32_t hi, Fp<P> *xw, uint64_t ncols, unsigned long long *stuck) {
+    const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (t >= hi) return;
+    solve_bits<P, DIV>(A, B, Cm, steps[t], bit_cols, xw + b * ncols, stuck + b);
+}
+
+// the step index is the same in every lane: the step record, the row's CSR metadata and a decomposition's column list are uniform loads
+template <class P, bool DIV>
+__global__ __launch_bounds__(64) void k_solve_chain(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, const uint32_t *__restrict__ bit_cols,
+                                                    uint32_t lo, uint32_t hi, Fp<P> *xw, uint64_t ncols, unsigned long long *stuck, uint64_t rows) {
     const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= rows) return;
     Fp<P> *z = xw + b * ncols;
-    for (uint32_t t = lo; t < hi; ++t) solve_step<P, DIV>(A, B, Cm, steps[t], z, stuck + b);
+    for (uint32_t t = lo; t < hi; ++t) {
+        if (steps[t].bits) solve_bits<P, DIV>(A, B, Cm, steps[t], bit_cols, z, stuck + b);
+        else solve_step<P, DIV>(A, B, Cm, steps[t], z, stuck + b);
+    }
 }
 
 namespace {
@@ -199,7 +277,9 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
         m[i] = pmsolve::Csr{rowptr[i].data(), col[i].data(), val[i].data()};
     }
     PM_HIP(ctx, hipStreamSynchronize(st));
-    sv.plan = pmsolve::build_plan(m, nr, pk->m0, pk->mw, pattern.data());
+    uint64_t modulus[4];
+    for (int i = 0; i < 4; ++i) modulus[i] = (uint64_t)P::MOD[2 * i] | (uint64_t)P::MOD[2 * i + 1] << 32;
+    sv.plan = pmsolve::build_plan(m, nr, pk->m0, pk->mw, pattern.data(), pmsolve::WIDE_STEPS, modulus);
     if (sv.plan.error != pmsolve::OK) {
         ctx->err = "pm solve: " + sv.plan.message;
         return PM_ERR_INVALID_ARG;
@@ -210,7 +290,12 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
         memset((void *)host.data(), 0, n_steps * sizeof(SolveStepDev<P>));
         for (size_t t = 0; t < n_steps; ++t) {
             const pmsolve::Step &s = sv.plan.steps[t];
-            host[t].pos = s.pos; host[t].row = s.row; host[t].col = s.col; host[t].kind = s.kind;
+            host[t].pos = s.pos; host[t].row = s.row; host[t].col = s.bits ? s.cols_off : s.col; host[t].kind = s.kind; host[t].bits = s.bits;
+        }
+        const std::vector<uint32_t> &bit_cols = sv.plan.bit_cols;
+        if (!bit_cols.empty()) {
+            PM_HIP(ctx, sv.bit_cols.reserve(bit_cols.size() * sizeof(uint32_t)));
+            PM_HIP(ctx, hipMemcpyAsync(sv.bit_cols.p, bit_cols.data(), bit_cols.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         }
         PM_HIP(ctx, sv.steps.reserve(n_steps * sizeof(SolveStepDev<P>)));
         PM_HIP(ctx, hipMemcpyAsync(sv.steps.p, host.data(), n_steps * sizeof(SolveStepDev<P>), hipMemcpyHostToDevice, st));
@@ -237,16 +322,19 @@ int solve_group(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t 
     PM_HIP(ctx, hipMemsetAsync(stuck, 0xff, g * sizeof(unsigned long long), st));
     const CsrDev A = csr_dev(pk, 0), B = csr_dev(pk, 1), Cm = csr_dev(pk, 2);
     const SolveStepDev<P> *steps = sv.steps.as<SolveStepDev<P>>();
+    const uint32_t *bit_cols = sv.plan.bit_cols.empty() ? nullptr : sv.bit_cols.as<uint32_t>();
     {
         StageTimer t(ctx, timing_slot);
         for (const pmsolve::Launch &l : sv.plan.launches) {
             if (l.chain) {
                 const dim3 grid(nblk(g, 64)), block(64);
-                if (l.divides) hipLaunchKernelGGL((k_solve_chain<P, true>), grid, block, 0, st, A, B, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
-                else hipLaunchKernelGGL((k_solve_chain<P, false>), grid, block, 0, st, A, B, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
+                if (l.divides) hipLaunchKernelGGL((k_solve_chain<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
+                else hipLaunchKernelGGL((k_solve_chain<P, false>), grid, block, 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
             } else {
                 const dim3 grid(nblk(l.hi - l.lo), (unsigned)g), block(256);
-                if (l.divides) hipLaunchKernelGGL((k_solve_level<P, true>), grid, block, 0, st, A, B, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck);
+                if (l.bits && l.divides) hipLaunchKernelGGL((k_solve_bits<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck);
+                else if (l.bits) hipLaunchKernelGGL((k_solve_bits<P, false>), grid, block, 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck);
+                else if (l.divides) hipLaunchKernelGGL((k_solve_level<P, true>), grid, block, 0, st, A, B, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck);
                 else hipLaunchKernelGGL((k_solve_level<P, false>), grid, block, 0, st, A, B, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck);
             }
             PM_HIP(ctx, hipGetLastError());

@@ -1,6 +1,6 @@
 // Witness solving, host side: the PLAN that completes a partial assignment by forward propagation through the rows of an R1CS
-// (DESIGN.md §4.10).  Header-only, no HIP: the library's driver (csrc/solve.hip) and a CPU program (tests/native/
-// solve_plan_selftest.cpp) include the same file.
+// (DESIGN.md §4.10).  Header-only, no HIP: the library's driver (csrc/solve.hip) and two CPU programs (tests/native/
+// solve_plan_selftest.cpp, solve_bits_selftest.cpp) include the same file.
 //
 // Input: the three matrices in CSR form with the first-entry rule already applied (a column occurs at most once per row and
 // matrix: the key's resident matrices are like that), m0 + mw columns and one byte per column, non-zero = unknown.  A stored entry
@@ -9,17 +9,39 @@
 //   one unknown u, in exactly one of A, B, C  a solve step (kind = the matrix that holds u); u is known from here on
 //   anything else                             the structure is unsolvable: the error names the row
 // and a marked column that no row determines is an error that names the column.
-// level(step) = 1 + max level of the columns the row reads (given columns: level 0).  The steps come out sorted by level, inside
-// a level by kind (C first: the kinds that divide share a launch), stable by row -- one counting sort.  O(nnz + columns).
+//
+// With the field's modulus (four 64-bit words; the coefficients are canonical Montgomery words) two more rows are understood, so
+// that bit decompositions -- and with them boolean circuits -- complete:
+//   booleanity    the only unknown is u, C_r has no non-zero entry, and {A_r, B_r} = {k z_u, k' (1 - z_u)}: one side is the single
+//                 entry (k, u), the other exactly the two entries (k', column 0) and (-k', u), k and k' non-zero.  The row marks u
+//                 BOOLEAN-PENDING, remembers r and is otherwise a check row.  One unknown in two matrices in any other shape is
+//                 ERR_TWO_MATRICES at once.
+//   decomposition k >= 2 unknowns, all boolean-pending, all in the same one of A, B, C and in no other, with coefficients
+//                 c 2^0 ... c 2^(k-1), each exactly once in any stored order, c non-zero, k <= bitlength(r) - 1 (the solution is then
+//                 unique).  ONE step (kind BITS_C / BITS_A / BITS_B) that determines all k columns: t as for the ordinary kinds with
+//                 the k entries left out and coef = c; z_{u_i} = bit i of the canonical integer of t.  t >= 2^k is stuck at run time.
+//                 Step::pos / col name the entry that holds c, Plan::bit_cols[cols_off .. cols_off + bits) the columns in exponent
+//                 order.  Any other row with two or more unknowns is ERR_MANY_UNKNOWNS; the message says which condition failed.
+//                 Booleanity rows that come AFTER the decomposition row are not looked for: that decomposition row is refused.
+// A boolean-pending column that is the single unknown of a later ordinary row is solved by it.  One still pending at the end of the
+// pass is ERR_TWO_MATRICES naming its booleanity row (the smallest such row), before ERR_UNDETERMINED is looked for.
+// Without the modulus (nullptr) both additions are off.
+//
+// level(step) = 1 + max level of the columns the row reads (given columns: level 0); a decomposition gives all its columns that
+// level.  The steps come out sorted by level, inside a level by kind (C first: the kinds that divide share a launch; then the
+// decompositions in the same order), stable by row -- one counting sort.  O(nnz + columns), plus k log k per decomposition.
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
 namespace pmsolve {
 
-enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2 };   // z_u = (Az Bz - C_rest) / coef;  (Cz / Bz - A_rest) / coef;  (Cz / Az - B_rest) / coef
+// z_u = (Az Bz - C_rest) / coef;  (Cz / Bz - A_rest) / coef;  (Cz / Az - B_rest) / coef;  KIND_BITS_x = KIND_BITS_C + x: a decomposition
+enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5 };
+constexpr uint32_t NUM_KINDS = 6;
 
 constexpr uint32_t WIDE_STEPS = 32;   // a level of at least this many steps gets launches of its own; narrower ones are walked by one lane per assignment
 
@@ -30,14 +52,16 @@ struct Csr {
 };
 
 struct Step {
-    uint64_t pos;     // index of the unknown's entry in its matrix (col / val arrays)
+    uint64_t pos;     // index of the unknown's entry in its matrix (col / val arrays); a decomposition: of the entry that holds c
     uint32_t row, col, kind, level;
+    uint32_t bits = 0, cols_off = 0;   // a decomposition: Plan::bit_cols[cols_off .. cols_off + bits), exponent order; bits = 0 otherwise
 };
 
 struct Launch {
     uint32_t lo, hi;  // steps [lo, hi) of the sorted list
     uint8_t chain;    // 1: one lane per assignment walks the steps in order; 0: one lane per (step, assignment), all of one level
-    uint8_t divides;  // 1: some step of the range is KIND_A / KIND_B
+    uint8_t divides;  // 1: some step of the range is KIND_A / KIND_B / KIND_BITS_A / KIND_BITS_B
+    uint8_t bits = 0; // chain == 0 only.  1: every step of the range is a decomposition; 0: none is
 };
 
 enum Error : int { OK = 0, ERR_MANY_UNKNOWNS = 1, ERR_TWO_MATRICES = 2, ERR_UNDETERMINED = 3, ERR_COLUMN_ZERO = 4 };
@@ -46,6 +70,7 @@ struct Plan {
     std::vector<Step> steps;          // sorted by (level, kind, row)
     std::vector<uint32_t> level_ptr;  // level l (1-based) = steps [level_ptr[l - 1], level_ptr[l])
     std::vector<Launch> launches;
+    std::vector<uint32_t> bit_cols;   // the decompositions' columns
     int error = OK;
     uint64_t error_row = 0, error_col = 0;
     std::string message;              // empty when error == OK
@@ -54,10 +79,100 @@ struct Plan {
 
 inline bool coef_is_zero(const uint64_t *v) { return (v[0] | v[1] | v[2] | v[3]) == 0; }
 
-inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, const uint8_t *unknown, uint32_t wide_steps = WIDE_STEPS) {
+// 256-bit helpers on canonical residues (4 x u64, little-endian)
+inline bool words_less(const uint64_t *a, const uint64_t *b) {
+    for (int i = 3; i >= 0; --i)
+        if (a[i] != b[i]) return a[i] < b[i];
+    return false;
+}
+inline bool words_equal(const uint64_t *a, const uint64_t *b) { return a[0] == b[0] && a[1] == b[1] && a[2] == b[2] && a[3] == b[3]; }
+// out = a + b mod `modulus`, for a, b < modulus
+inline void add_mod(const uint64_t *a, const uint64_t *b, const uint64_t *modulus, uint64_t *out) {
+    uint64_t s[4], d[4], carry = 0, borrow = 0;
+    for (int i = 0; i < 4; ++i) {
+        const uint64_t t = a[i] + carry;
+        const uint64_t c1 = t < carry;
+        s[i] = t + b[i];
+        carry = c1 | (uint64_t)(s[i] < t);
+    }
+    for (int i = 0; i < 4; ++i) {
+        const uint64_t t = s[i] - borrow;
+        const uint64_t b1 = s[i] < borrow;
+        d[i] = t - modulus[i];
+        borrow = b1 | (uint64_t)(t < modulus[i]);
+    }
+    const bool ge = carry || !borrow;
+    for (int i = 0; i < 4; ++i) out[i] = ge ? d[i] : s[i];
+}
+inline uint32_t bit_length(const uint64_t *a) {
+    for (int i = 3; i >= 0; --i)
+        if (a[i]) return 64 * (uint32_t)i + 64 - (uint32_t)__builtin_clzll(a[i]);
+    return 0;
+}
+
+struct Unknown {   // an unknown's entry in the row under the cursor
+    uint32_t matrix, col;
+    uint64_t pos;
+};
+
+// the booleanity shape, for a row whose unknown entries are `occ` (all of one column) with nz[k] non-zero entries in matrix k
+inline bool is_booleanity(const Csr m[3], uint64_t r, const std::vector<Unknown> &occ, const uint32_t nz[3], const uint64_t *modulus) {
+    if (occ.size() != 2 || occ[0].matrix != 0 || occ[1].matrix != 1 || nz[2] != 0) return false;
+    if (!((nz[0] == 1 && nz[1] == 2) || (nz[0] == 2 && nz[1] == 1))) return false;
+    const int two = nz[0] == 2 ? 0 : 1;   // the side k' (1 - z_u)
+    for (uint64_t e = m[two].rowptr[r]; e < m[two].rowptr[r + 1]; ++e) {
+        if (e == occ[two].pos || coef_is_zero(m[two].val + 4 * e)) continue;
+        uint64_t sum[4];
+        add_mod(m[two].val + 4 * e, m[two].val + 4 * occ[two].pos, modulus, sum);
+        return m[two].col[e] == 0 && coef_is_zero(sum);
+    }
+    return false;
+}
+
+// the decomposition shape, for a row whose unknown entries are `occ` (two or more columns): nullptr and `order` = the indices of
+// occ in exponent order, or the condition that failed
+inline const char *decomposition_order(const Csr m[3], const std::vector<Unknown> &occ, const std::vector<uint32_t> &bool_row, const uint64_t *modulus,
+                                       std::vector<uint32_t> &order) {
+    constexpr uint32_t NONE = ~(uint32_t)0;
+    const size_t k = occ.size();
+    for (const Unknown &o : occ) {
+        if (o.matrix != occ[0].matrix) return "the unknowns lie in more than one matrix";
+        if (bool_row[o.col] == NONE) return "an unknown that no earlier row constrains boolean";
+    }
+    if (k > bit_length(modulus) - 1) return "more bits than bitlength(r) - 1";
+    const uint64_t *val = m[occ[0].matrix].val;
+    std::vector<uint32_t> sorted(k), next(k, NONE);
+    for (size_t i = 0; i < k; ++i) sorted[i] = (uint32_t)i;
+    const auto less = [&](uint32_t a, uint32_t b) { return words_less(val + 4 * occ[a].pos, val + 4 * occ[b].pos); };
+    std::sort(sorted.begin(), sorted.end(), less);
+    for (size_t i = 1; i < k; ++i)
+        if (words_equal(val + 4 * occ[sorted[i - 1]].pos, val + 4 * occ[sorted[i]].pos)) return "a coefficient occurs twice";
+    std::vector<uint8_t> has_pred(k, 0);
+    for (size_t i = 0; i < k; ++i) {
+        uint64_t twice[4];
+        add_mod(val + 4 * occ[i].pos, val + 4 * occ[i].pos, modulus, twice);
+        const auto it = std::lower_bound(sorted.begin(), sorted.end(), twice, [&](uint32_t a, const uint64_t *w) { return words_less(val + 4 * occ[a].pos, w); });
+        if (it != sorted.end() && words_equal(val + 4 * occ[*it].pos, twice)) {
+            next[i] = *it;
+            has_pred[*it] = 1;
+        }
+    }
+    uint32_t first = NONE;
+    for (size_t i = 0; i < k; ++i)
+        if (!has_pred[i]) {
+            if (first != NONE) return "the coefficients are not c 2^0 ... c 2^(k-1)";
+            first = (uint32_t)i;
+        }
+    order.clear();
+    for (uint32_t i = first; i != NONE && order.size() < k; i = next[i]) order.push_back(i);
+    return order.size() == k ? nullptr : "the coefficients are not c 2^0 ... c 2^(k-1)";
+}
+
+inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, const uint8_t *unknown, uint32_t wide_steps = WIDE_STEPS,
+                       const uint64_t *modulus = nullptr) {
     Plan p;
     const uint64_t ncols = m0 + mw;
-    constexpr uint32_t UNSOLVED = ~(uint32_t)0;
+    constexpr uint32_t UNSOLVED = ~(uint32_t)0, NONE = ~(uint32_t)0;
     if (ncols && unknown[0]) {
         p.error = ERR_COLUMN_ZERO;
         p.message = "column 0 (the constant one) is marked unknown";
@@ -65,43 +180,92 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
     }
     std::vector<uint32_t> level(ncols);
     for (uint64_t j = 0; j < ncols; ++j) level[j] = unknown[j] ? UNSOLVED : 0;
+    std::vector<uint32_t> bool_row(modulus ? ncols : 0, NONE);   // boolean-pending: the column is UNSOLVED and this is its booleanity row
     static const char *const NAME[3] = {"A", "B", "C"};
     static const uint32_t KIND_OF[3] = {KIND_A, KIND_B, KIND_C};
     uint32_t max_level = 0;
+    std::vector<Unknown> occ;
+    std::vector<uint32_t> order;
     for (uint64_t r = 0; r < nr; ++r) {
-        uint32_t u = 0, found = 0, reads = 0, in_matrix = 0;
-        uint64_t pos = 0;
-        for (int k = 0; k < 3 && p.error == OK; ++k) {
-            for (uint64_t e = m[k].rowptr[r]; e < m[k].rowptr[r + 1]; ++e) {
+        uint32_t reads = 0, nz[3] = {0, 0, 0};
+        occ.clear();
+        // without the modulus the second unknown entry decides the error, as it always did; with it the whole row is read
+        for (int k = 0; k < 3 && (modulus || occ.size() < 2); ++k) {
+            for (uint64_t e = m[k].rowptr[r]; e < m[k].rowptr[r + 1] && (modulus || occ.size() < 2); ++e) {
                 if (coef_is_zero(m[k].val + 4 * e)) continue;
+                ++nz[k];
                 const uint32_t j = m[k].col[e];
                 if (level[j] != UNSOLVED) {
                     if (level[j] > reads) reads = level[j];
                     continue;
                 }
-                if (found && j != u) {
-                    p.error = ERR_MANY_UNKNOWNS;
-                    p.error_row = r;
-                    p.error_col = j;
-                    p.message = "row " + std::to_string(r) + ": two or more unknowns (columns " + std::to_string(u) + " and " + std::to_string(j) + ")";
-                    break;
-                }
-                if (found) {   // the same unknown again: in another matrix, or a second time in this one
-                    p.error = ERR_TWO_MATRICES;
-                    p.error_row = r;
-                    p.error_col = j;
-                    p.message = "row " + std::to_string(r) + ": unknown column " + std::to_string(j) + " occurs in " + NAME[in_matrix] + " and in " + NAME[k];
-                    break;
-                }
-                found = 1; u = j; pos = e; in_matrix = (uint32_t)k;
+                occ.push_back(Unknown{(uint32_t)k, j, e});
             }
         }
-        if (p.error != OK) return p;
-        if (!found) continue;
+        if (occ.empty()) continue;
         const uint32_t lv = reads + 1;
-        level[u] = lv;
-        if (lv > max_level) max_level = lv;
-        p.steps.push_back(Step{pos, (uint32_t)r, u, KIND_OF[in_matrix], lv});
+        if (occ.size() == 1) {
+            const uint32_t u = occ[0].col;
+            level[u] = lv;
+            if (lv > max_level) max_level = lv;
+            p.steps.push_back(Step{occ[0].pos, (uint32_t)r, u, KIND_OF[occ[0].matrix], lv});
+            continue;
+        }
+        const uint32_t u = occ[0].col;
+        uint32_t j = occ[1].col;
+        const char *why = nullptr;
+        if (modulus) {
+            bool one_column = true;
+            for (const Unknown &o : occ)
+                if (one_column && o.col != u) {   // two or more unknowns: the error names the first other one, wherever u occurs again
+                    one_column = false;
+                    j = o.col;
+                }
+            if (one_column) {
+                if (is_booleanity(m, r, occ, nz, modulus)) {
+                    if (bool_row[u] == NONE) bool_row[u] = (uint32_t)r;
+                    continue;
+                }
+            } else if (!(why = decomposition_order(m, occ, bool_row, modulus, order))) {
+                const Unknown &c = occ[order[0]];
+                Step s{c.pos, (uint32_t)r, c.col, KIND_BITS_C + KIND_OF[c.matrix], lv};
+                s.bits = (uint32_t)order.size();
+                s.cols_off = (uint32_t)p.bit_cols.size();
+                for (uint32_t i : order) {
+                    p.bit_cols.push_back(occ[i].col);
+                    level[occ[i].col] = lv;
+                }
+                if (lv > max_level) max_level = lv;
+                p.steps.push_back(s);
+                continue;
+            }
+        }
+        p.error_row = r;
+        p.error_col = j;
+        if (j != u) {
+            p.error = ERR_MANY_UNKNOWNS;
+            p.message = "row " + std::to_string(r) + ": two or more unknowns (columns " + std::to_string(u) + " and " + std::to_string(j) + ")";
+            if (why) p.message += std::string(", and no bit decomposition: ") + why;
+        } else {   // the same unknown again: in another matrix, or a second time in this one
+            p.error = ERR_TWO_MATRICES;
+            p.message = "row " + std::to_string(r) + ": unknown column " + std::to_string(j) + " occurs in " + NAME[occ[0].matrix] + " and in " + NAME[occ[1].matrix];
+        }
+        return p;
+    }
+    if (modulus) {
+        uint64_t pending = ncols;
+        for (uint64_t j = 0; j < ncols; ++j)
+            if (level[j] == UNSOLVED && bool_row[j] != NONE && (pending == ncols || bool_row[j] < bool_row[pending])) pending = j;
+        if (pending != ncols) {
+            p.error = ERR_TWO_MATRICES;
+            p.error_row = bool_row[pending];
+            p.error_col = pending;
+            p.message = "row " + std::to_string(p.error_row) + ": unknown column " + std::to_string(pending) +
+                        " occurs in A and in B (a booleanity row, and no later row determines the column)";
+            p.steps.clear();
+            p.bit_cols.clear();
+            return p;
+        }
     }
     for (uint64_t j = 0; j < ncols; ++j)
         if (level[j] == UNSOLVED) {
@@ -109,31 +273,38 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
             p.error_col = j;
             p.message = "column " + std::to_string(j) + " is marked unknown and no row determines it";
             p.steps.clear();
+            p.bit_cols.clear();
             return p;
         }
     // counting sort by (level, kind); the row order inside a key is the order of discovery
-    std::vector<uint32_t> start((size_t)max_level * 3 + 1, 0);
-    for (const Step &s : p.steps) ++start[(size_t)(s.level - 1) * 3 + s.kind + 1];
+    constexpr size_t K = NUM_KINDS;
+    std::vector<uint32_t> start((size_t)max_level * K + 1, 0);
+    for (const Step &s : p.steps) ++start[(size_t)(s.level - 1) * K + s.kind + 1];
     for (size_t i = 1; i < start.size(); ++i) start[i] += start[i - 1];
     p.level_ptr.resize((size_t)max_level + 1);
-    for (uint32_t l = 0; l <= max_level; ++l) p.level_ptr[l] = start[(size_t)l * 3];
+    for (uint32_t l = 0; l <= max_level; ++l) p.level_ptr[l] = start[(size_t)l * K];
     {
         std::vector<Step> sorted(p.steps.size());
         std::vector<uint32_t> cursor(start.begin(), start.end() - 1);
-        for (const Step &s : p.steps) sorted[cursor[(size_t)(s.level - 1) * 3 + s.kind]++] = s;
+        for (const Step &s : p.steps) sorted[cursor[(size_t)(s.level - 1) * K + s.kind]++] = s;
         p.steps.swap(sorted);
     }
-    // launch schedule: a wide level is its own launch, split where the dividing kinds begin; consecutive narrow levels are one chain
+    // launch schedule: a wide level is its own launch, split where the dividing kinds begin and again where the decompositions and
+    // their dividing kinds begin; consecutive narrow levels are one chain
     for (uint32_t l = 0; l < max_level; ++l) {
-        const uint32_t lo = p.level_ptr[l], hi = p.level_ptr[l + 1], mid = start[(size_t)l * 3 + 1];   // [lo, mid) KIND_C, [mid, hi) A and B
+        const uint32_t *at = start.data() + (size_t)l * K;
+        const uint32_t lo = at[KIND_C], ab = at[KIND_A], bits = at[KIND_BITS_C], bits_ab = at[KIND_BITS_A], hi = at[K];
+        const uint8_t divides = (uint8_t)(bits > ab || hi > bits_ab);
         if (hi - lo >= wide_steps) {
-            if (mid > lo) p.launches.push_back(Launch{lo, mid, 0, 0});
-            if (hi > mid) p.launches.push_back(Launch{mid, hi, 0, 1});
+            if (ab > lo) p.launches.push_back(Launch{lo, ab, 0, 0});
+            if (bits > ab) p.launches.push_back(Launch{ab, bits, 0, 1});
+            if (bits_ab > bits) p.launches.push_back(Launch{bits, bits_ab, 0, 0, 1});
+            if (hi > bits_ab) p.launches.push_back(Launch{bits_ab, hi, 0, 1, 1});
         } else if (!p.launches.empty() && p.launches.back().chain) {
             p.launches.back().hi = hi;
-            p.launches.back().divides |= (uint8_t)(hi > mid);
+            p.launches.back().divides |= divides;
         } else {
-            p.launches.push_back(Launch{lo, hi, 1, (uint8_t)(hi > mid)});
+            p.launches.push_back(Launch{lo, hi, 1, divides});
         }
     }
     return p;

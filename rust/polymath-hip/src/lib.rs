@@ -795,10 +795,11 @@ impl GpuKey {
     }
 
     /// `pm_host_prove_batch` with `PM_ASSIGNMENT_SOLVE`: the rows are PARTIAL assignments -- `None` where the library is to compute
-    /// the value on the GPU, by forward propagation through the key's constraint rows -- and every row must leave the same
+    /// the value on the GPU, by forward propagation through the key's constraint rows (bit decompositions included: the bits of
+    /// `Boolean::new_witness` variables that one row sums to a known value are computed from it) -- and every row must leave the same
     /// entries open.  Row i = (instance with the leading one, witness, r_a).  Returns, per row, the proof bytes together with the
     /// completed instance (what the verifier needs; `pm_prove_tap(9)`), or the row's status: `InvalidArg` for an assignment that
-    /// got stuck on a division by zero, otherwise what [`GpuKey::prove_batch`] gives it.  The outer error is the call's: an
+    /// got stuck on a division by zero or on a value that does not fit its bits, otherwise what [`GpuKey::prove_batch`] gives it.  The outer error is the call's: an
     /// unsolvable structure is `InvalidArg` with the row or column in the message, and nothing has been computed.
     #[allow(clippy::type_complexity)]
     pub fn prove_batch_from_partial<E: Pairing>(
@@ -841,8 +842,8 @@ impl GpuKey {
     }
 
     /// `pm_r1cs_check_batch` with `PM_ASSIGNMENT_SOLVE` and no rows asked for: complete partial assignments (`None` = to be computed)
-    /// without proving.  Returns, per assignment, its stuck row (`Some(row)`: a division by zero there, the instance is then all
-    /// zero) and the completed instance, leading one included.
+    /// without proving.  Returns, per assignment, its stuck row (`Some(row)`: a division by zero there, or a bit decomposition of a
+    /// value of 2^k or more; the instance is then all zero) and the completed instance, leading one included.
     #[allow(clippy::type_complexity)]
     pub fn solve<E: Pairing>(
         &self,

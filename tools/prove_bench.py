@@ -6,10 +6,12 @@ and printing proofs/s for both plus the stage split of pm_last_timings (summed o
   python tools/prove_bench.py --circuit bench:32000 --batch 16 --reps 3        BenchCircuit with 32000 constraints: n = 2^16
 The B rows cycle through min(B, 32) distinct seeded assignments with distinct r_a (a proof's cost does not depend on its values).
   python tools/prove_bench.py --circuit mimc322 --batch 256 --reps 5 --solve
-compares inputs -> proofs instead (mimcK only), host limbs in both routes, alternating in this process:
-  (a) the B assignments synthesised on the host (MiMCDemo.generate_constraints, Python integers), then one pm_host_prove_batch call
-  (b) B partial assignments (xl, xr given, everything else the unknown marker), one pm_host_prove_batch call with PM_ASSIGNMENT_SOLVE
-Every rep of (a) synthesises all B assignments again: that is the step (b) moves to the GPU."""
+compares inputs -> proofs instead (mimcK and arx only), host limbs in both routes, alternating in this process:
+  (a) the B assignments synthesised on the host (generate_constraints, Python integers), then one pm_host_prove_batch call
+  (b) B partial assignments (the inputs given, everything else the unknown marker), one pm_host_prove_batch call with PM_ASSIGNMENT_SOLVE
+Every rep of (a) synthesises all B assignments again: that is the step (b) moves to the GPU.
+  python tools/prove_bench.py --circuit arx --batch 256 --reps 5 --solve        ArxDemo, 32-bit words, 8 rounds; arx:W:R for others
+is the same comparison on a boolean circuit (bit decompositions, XOR rows)."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -19,7 +21,7 @@ from polymath_amd import circuits as PC
 from polymath_amd.polymath import Polymath
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants) or bench:NC (BenchCircuit, NC constraints)")
+ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants), bench:NC (BenchCircuit, NC constraints) or arx[:WIDTH:ROUNDS] (ArxDemo)")
 ap.add_argument("--batch", type=int, default=16)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--curve", default="bls12_381")
@@ -27,8 +29,8 @@ ap.add_argument("--transcript", default="merlin")
 ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="pm_ctx_set_option before the key is made, e.g. --opt tables=0")
 ap.add_argument("--solve", action="store_true", help="host-synthesised assignments against partial assignments solved on the GPU")
 a = ap.parse_args()
-if a.solve and not a.circuit.startswith("mimc"):
-    ap.error("--solve needs a mimcK circuit")
+if a.solve and not a.circuit.startswith(("mimc", "arx")):
+    ap.error("--solve needs a mimcK or an arx circuit")
 pm = Polymath(a.curve, a.transcript, device=0)
 for kv in a.opt:
     pm.ctx.set_option(kv.split("=", 1)[0], int(kv.split("=", 1)[1]))
@@ -37,6 +39,13 @@ g = PC.SplitMix64(20260117)
 if a.circuit.startswith("mimc"):
     consts = [g.fr(r) for _ in range(int(a.circuit[4:]))]
     make = lambda: PC.MiMCDemo(g.fr(r), g.fr(r), consts)
+    again = lambda c: PC.MiMCDemo(c.xl, c.xr, consts)
+    partial_of = lambda c: ([1, None], [c.xl, c.xr] + [None] * (mw - 2))
+elif a.circuit.startswith("arx"):
+    width, rounds = (int(v) for v in a.circuit.split(":")[1:3]) if ":" in a.circuit else (32, 8)
+    make = lambda: PC.ArxDemo(g.next_u64() % (1 << width), g.next_u64() % (1 << width), width, rounds, 7 % width or 1)
+    again = lambda c: PC.ArxDemo(c.a, c.b, c.width, c.rounds, c.rot)
+    partial_of = lambda c: c.partial(r)
 else:
     nc = int(a.circuit.split(":", 1)[1])
     make = lambda: PC.BenchCircuit(g.fr(r), g.fr(r), 10, nc)
@@ -60,16 +69,16 @@ m0, mw = xs.shape[1], ws.shape[1]
 
 
 def solve_comparison():
-    inputs = [(circuits[i].xl, circuits[i].xr) for i in pick]
+    inputs = [circuits[i] for i in pick]
     ra_all = [rows[i][2] for i in pick]
-    partial = [pm.partial_limbs([1, None], [xl, xr] + [None] * (mw - 2)) for xl, xr in inputs]
+    partial = [pm.partial_limbs(*partial_of(c)) for c in inputs]
 
     def run_host():
         t0 = time.perf_counter()
         t_syn = 0.0
         full = []
-        for xl, xr in inputs:
-            _, inst, wit = pm._synthesize(PC.MiMCDemo(xl, xr, consts))
+        for c in inputs:
+            _, inst, wit = pm._synthesize(again(c))
             full.append((pm.field.fr_limbs(inst), pm.field.fr_limbs(wit)))
         t_syn = time.perf_counter() - t0
         proofs, status = pm.prove_batch(pk, full, ra_all)
