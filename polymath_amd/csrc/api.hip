@@ -470,136 +470,22 @@ struct HostCsr {
     std::vector<uint64_t> val;
 };
 
-// m_at (common.rs:100-105) only ever sees the FIRST entry of a row with a given column.
-static int dedupe_csr(const pm_csr *m, uint64_t nr, uint64_t ncols, HostCsr &out) {
-    if (!m || m->nrows != nr || !m->rowptr) return PM_ERR_INVALID_ARG;
+// m_at (common.rs:100-105) only ever sees the FIRST entry of a row with a given column: the matrix without the later ones, its row
+// pointers starting at 0.  The caller has checked rows and columns (pk_upload_matrices).
+static void dedupe_csr(const pm_csr *m, uint64_t nr, HostCsr &out) {
     out.rowptr.assign(1, 0);
     for (uint64_t r = 0; r < nr; ++r) {
-        size_t start = out.col.size();
+        const size_t start = out.col.size();
         for (uint64_t k = m->rowptr[r]; k < m->rowptr[r + 1]; ++k) {
-            if (m->col[k] >= ncols) return PM_ERR_INVALID_ARG;
-            bool dup = false;
-            for (size_t q = start; q < out.col.size(); ++q)
-                if (out.col[q] == m->col[k]) { dup = true; break; }
-            if (dup) continue;
+            if (std::find(out.col.begin() + start, out.col.end(), m->col[k]) != out.col.end()) continue;
             out.col.push_back(m->col[k]);
-            for (int i = 0; i < 4; ++i) out.val.push_back(m->val[4 * k + i]);
+            out.val.insert(out.val.end(), m->val + 4 * k, m->val + 4 * k + 4);
         }
         out.rowptr.push_back(out.col.size());
     }
-    return PM_OK;
 }
 
-static void pk_release(pm_pk *pk) {
-    if (!pk) return;
-    (void)hipSetDevice(pk->device);
-    for (int i = 0; i < 3; ++i) {
-        if (pk->d_rowptr[i]) (void)hipFree(pk->d_rowptr[i]);
-        if (pk->d_col[i]) (void)hipFree(pk->d_col[i]);
-        if (pk->d_val[i]) (void)hipFree(pk->d_val[i]);
-    }
-    if (pk->d_bases) (void)hipFree(pk->d_bases);
-    if (pk->d_segs) (void)hipFree(pk->d_segs);
-    if (pk->d_all_segs) (void)hipFree(pk->d_all_segs);
-    for (int k = 0; k < 3; ++k) {
-        if (pk->d_tab[k]) (void)hipFree(pk->d_tab[k]);
-        if (pk->d_tab_inf[k]) (void)hipFree(pk->d_tab_inf[k]);
-    }
-    delete pk;
-}
-
-extern "C" void pm_pk_free(pm_pk *pk) { pk_release(pk); }
-
-// Shapes, domain, the logical base concatenation and this shard's resident ranges.
-template <class C>
-static int pk_init_layout(pm_ctx *ctx, pm_pk *pk, uint64_t m0, uint64_t mw, uint64_t nr, int shard_rank, int shard_count, int layout = PM_SHARD_PAIRS) {
-    typedef typename C::FrP P;
-    if (m0 < 1 || shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return PM_ERR_INVALID_ARG;
-    if (layout != PM_SHARD_PAIRS && layout != PM_SHARD_VECTOR) return PM_ERR_INVALID_ARG;
-    pk->layout = layout;
-    pk->curve = C::ID;
-    pk->device = ctx->device;
-    pk->m0 = m0; pk->mw = mw; pk->nr = nr;
-    uint64_t rows = 2 * (m0 + nr);                     // common.rs:131-135
-    uint64_t n = 1;
-    unsigned log_n = 0;
-    while (n < rows) { n <<= 1; ++log_n; }             // Radix2EvaluationDomain::new, generator.rs:60
-    if (log_n > (unsigned)C::TWO_ADICITY) return PM_ERR_DOMAIN_TOO_LARGE;
-    pk->n = n; pk->log_n = log_n; pk->sigma = n + 3;   // generator.rs:66-70
-    Fp<P> w;
-    for (int i = 0; i < P::N; ++i) w.l[i] = C::ROOT_MONT[i];
-    for (unsigned i = log_n; i < (unsigned)C::TWO_ADICITY; ++i) w = sqr<P>(w);
-    memcpy(pk->omega, w.l, 32);
-    pk->shard_rank = shard_rank; pk->shard_count = shard_count;
-    const uint64_t Lz = 2 * m0 + mw + nr;
-    pk->base_len[PM_X_POWERS] = n + 1;
-    pk->base_len[PM_X_POWERS_Y_ALPHA] = 3;
-    pk->base_len[PM_X_POWERS_Y_GAMMA] = 2;
-    pk->base_len[PM_X_POWERS_Y_GAMMA_Z] = 2 * (n - 1) + 8 * pk->sigma + 1;
-    pk->base_len[PM_X_POWERS_ZH_BY_Y_ALPHA] = n - 1;
-    pk->base_len[PM_UJ_WJ_LCS_BY_Y_ALPHA] = Lz;
-    const int order[6] = {PM_UJ_WJ_LCS_BY_Y_ALPHA, PM_X_POWERS_ZH_BY_Y_ALPHA, PM_X_POWERS, PM_X_POWERS_Y_ALPHA,
-                          PM_X_POWERS_Y_GAMMA, PM_X_POWERS_Y_GAMMA_Z};
-    uint64_t off = 0;
-    for (int k = 0; k < 6; ++k) { pk->seg_off[order[k]] = off; off += pk->base_len[order[k]]; }
-    pk->total_points = off;
-    pk->msm_lo[0] = pk->seg_off[PM_X_POWERS];            pk->msm_len[0] = n + 3;
-    pk->msm_lo[1] = 0;                                   pk->msm_len[1] = pk->seg_off[PM_X_POWERS_Y_GAMMA_Z];
-    pk->msm_lo[2] = pk->seg_off[PM_X_POWERS_Y_GAMMA_Z];  pk->msm_len[2] = pk->base_len[PM_X_POWERS_Y_GAMMA_Z] - 1;
-    for (int k = 0; k < 3; ++k) {
-        pk->res_lo[k] = pk->msm_len[k] * (uint64_t)shard_rank / (uint64_t)shard_count;
-        pk->res_hi[k] = pk->msm_len[k] * (uint64_t)(shard_rank + 1) / (uint64_t)shard_count;
-    }
-    if (layout == PM_SHARD_VECTOR) {
-        if (!pmlayout::layout_ok(n, (uint32_t)shard_count)) return PM_ERR_INVALID_ARG;   // N a power of two, N^2 | n
-        const pmlayout::Layout L = pmlayout::make_layout(n, (uint32_t)shard_count, (uint32_t)shard_rank);
-        const pmlayout::KeyShape ks = pmlayout::key_shape(n, m0, mw, nr);
-        pk->max_seg = pmlayout::pick_max_seg(n, (uint32_t)shard_count);
-        if (ctx->opt.v[PM_OPT_MAX_SEG_LOG] > 0) pk->max_seg = (uint64_t)1 << ctx->opt.v[PM_OPT_MAX_SEG_LOG];   // test knob: many tiny sub-segments
-        pk->segs = pmlayout::quotient_segments(n, (uint32_t)shard_count, (uint32_t)shard_rank, pk->max_seg);
-        pk->seg_slots = 0;
-        for (uint32_t r = 0; r < (uint32_t)shard_count; ++r) {
-            const std::vector<pmlayout::Segment> sr = (int)r == shard_rank ? pk->segs : pmlayout::quotient_segments(n, (uint32_t)shard_count, r, pk->max_seg);
-            pk->seg_slots = std::max(pk->seg_slots, sr.size());
-            for (size_t i = 0; i < sr.size(); ++i) pk->all_segs.push_back(pm_pk::SegRef{sr[i].a, sr[i].b, r, (uint32_t)i});
-        }
-        std::sort(pk->all_segs.begin(), pk->all_segs.end(), [](const pm_pk::SegRef &x, const pm_pk::SegRef &y) { return x.a < y.a; });
-        uint64_t at = 0;                                    // the ranks' segments must tile [0, len) exactly
-        for (const auto &e : pk->all_segs) {
-            if (e.a != at || e.b <= e.a) return PM_ERR_STATE;
-            at = e.b;
-        }
-        if (at != pmlayout::numerator_len(n)) return PM_ERR_STATE;
-        PM_HIP(ctx, hipMalloc(&pk->d_segs, pk->segs.size() * sizeof(pmlayout::Segment)));
-        PM_HIP(ctx, hipMemcpy(pk->d_segs, pk->segs.data(), pk->segs.size() * sizeof(pmlayout::Segment), hipMemcpyHostToDevice));
-        // the carry chain of the division scan runs on the device too (prove_sharded.hip: k_seg_chain): all ranks' segments, in index order
-        PM_HIP(ctx, hipMalloc(&pk->d_all_segs, pk->all_segs.size() * sizeof(pm_pk::SegRef)));
-        PM_HIP(ctx, hipMemcpy(pk->d_all_segs, pk->all_segs.data(), pk->all_segs.size() * sizeof(pm_pk::SegRef), hipMemcpyHostToDevice));
-        pk->pieces[0] = pmlayout::pieces_a(ks, L);
-        pk->pieces[1] = pmlayout::pieces_c(ks, L);
-        pk->pieces[2] = pmlayout::pieces_d(ks, pk->segs);
-        for (int k = 0; k < 3; ++k) { pk->res_lo[k] = 0; pk->res_hi[k] = 0; }   // not contiguous: unused in this layout
-    } else {
-        for (int k = 0; k < 3; ++k) pk->pieces[k] = {pmlayout::Piece{pk->msm_lo[k] + pk->res_lo[k], pk->res_hi[k] - pk->res_lo[k]}};
-    }
-    for (int k = 0; k < 3; ++k) {
-        pk->res_cnt[k] = 0;
-        for (const auto &pc : pk->pieces[k]) pk->res_cnt[k] += pc.count;
-    }
-    if (shard_count == 1 && layout == PM_SHARD_PAIRS) {   // the whole logical concatenation is resident
-        for (int k = 0; k < 3; ++k) pk->res_dev_off[k] = pk->msm_lo[k];
-    } else {  // device layout [c pairs | a pairs | d pairs]
-        pk->res_dev_off[1] = 0;
-        pk->res_dev_off[0] = pk->res_cnt[1];
-        pk->res_dev_off[2] = pk->res_dev_off[0] + pk->res_cnt[0];
-    }
-    return PM_OK;
-}
-
-static uint64_t pk_resident_points(const pm_pk *pk) {
-    if (pk->shard_count == 1 && pk->layout == PM_SHARD_PAIRS) return pk->total_points;
-    return pk->res_cnt[0] + pk->res_cnt[1] + pk->res_cnt[2];
-}
+extern "C" void pm_pk_free(pm_pk *pk) { delete pk; }   // the key owns its device memory (internal.h)
 
 template <class C>
 static int pk_upload_matrices(pm_ctx *ctx, pm_pk *pk, const pm_csr *a, const pm_csr *b, const pm_csr *c) {
@@ -607,10 +493,10 @@ static int pk_upload_matrices(pm_ctx *ctx, pm_pk *pk, const pm_csr *a, const pm_
     const uint64_t nr = pk->nr, ncols = pk->m0 + pk->mw;
     for (int i = 0; i < 3; ++i) {
         if (!m[i] || m[i]->nrows != nr || !m[i]->rowptr) return PM_ERR_INVALID_ARG;
-        // One parallel pass over the rows: column range, and whether ANY row repeats a column (m_at, common.rs:100-105, only ever
-        // sees the first entry).  Without repeats -- every circuit ark-relations' `to_matrices` produces after its own
-        // linear-combination merging, and the synthetic ones -- the caller's arrays go to the device as they are: no host copy
-        // (round 4: the copying first-entry pass was 1.05 s of host time at 2^24 gates).
+        // The one check of a matrix, one parallel pass over its rows: row pointers, column range, and whether ANY row repeats a
+        // column (m_at, common.rs:100-105, only ever sees the first entry).  Without repeats -- every circuit ark-relations'
+        // `to_matrices` produces after its own linear-combination merging, and the synthetic ones -- the caller's arrays go to the
+        // device as they are: no host copy (round 4: the copying first-entry pass was 1.05 s of host time at 2^24 gates).
         std::atomic<int> bad{0}, repeats{0};
         const pm_csr *mi = m[i];
         parallel_chunks(nr, [&](uint64_t lo, uint64_t hi, unsigned) {
@@ -630,17 +516,17 @@ static int pk_upload_matrices(pm_ctx *ctx, pm_pk *pk, const pm_csr *a, const pm_
         const uint32_t *col = mi->col;
         uint64_t nnz = nr ? mi->rowptr[nr] - mi->rowptr[0] : 0;
         if (repeats || (nr && mi->rowptr[0] != 0)) {
-            PM_TRY(dedupe_csr(mi, nr, ncols, h));
+            dedupe_csr(mi, nr, h);
             rowptr = h.rowptr.data(); col = h.col.data(); val = h.val.data();
             nnz = h.col.size();
         }
         const uint64_t zero_row = 0;
         pk->nnz[i] = nnz;
-        PM_HIP(ctx, hipMalloc((void **)&pk->d_rowptr[i], (nr + 1) * 8));
+        PM_HIP(ctx, pk->alloc(&pk->d_rowptr[i], (nr + 1) * 8));
         PM_HIP(ctx, hipMemcpy(pk->d_rowptr[i], nr ? rowptr : &zero_row, (nr + 1) * 8, hipMemcpyHostToDevice));
         const size_t nz = nnz ? nnz : 1;
-        PM_HIP(ctx, hipMalloc((void **)&pk->d_col[i], nz * 4));
-        PM_HIP(ctx, hipMalloc((void **)&pk->d_val[i], nz * 32));
+        PM_HIP(ctx, pk->alloc(&pk->d_col[i], nz * 4));
+        PM_HIP(ctx, pk->alloc(&pk->d_val[i], nz * 32));
         if (nnz) {
             PM_HIP(ctx, hipMemcpy(pk->d_col[i], col, nnz * 4, hipMemcpyHostToDevice));
             PM_HIP(ctx, hipMemcpy(pk->d_val[i], val, nnz * 32, hipMemcpyHostToDevice));
@@ -652,10 +538,7 @@ static int pk_upload_matrices(pm_ctx *ctx, pm_pk *pk, const pm_csr *a, const pm_
 // Apply `fill(vec, start, count, dst)` to every piece of the logical concatenation range [lo, hi).
 template <class C, class F>
 static int for_cat_range(const pm_pk *pk, uint64_t lo, uint64_t hi, Affine<C> *dst, F fill) {
-    const int order[6] = {PM_UJ_WJ_LCS_BY_Y_ALPHA, PM_X_POWERS_ZH_BY_Y_ALPHA, PM_X_POWERS, PM_X_POWERS_Y_ALPHA,
-                          PM_X_POWERS_Y_GAMMA, PM_X_POWERS_Y_GAMMA_Z};
-    for (int k = 0; k < 6; ++k) {
-        int v = order[k];
+    for (int v : pmlayout::CAT_ORDER) {
         uint64_t s = pk->seg_off[v], e = s + pk->base_len[v];
         uint64_t a = std::max(lo, s), b = std::min(hi, e);
         if (a >= b) continue;
@@ -664,94 +547,26 @@ static int for_cat_range(const pm_pk *pk, uint64_t lo, uint64_t hi, Affine<C> *d
     return PM_OK;
 }
 
-// Allocates the resident base array and fills it through `fill` (pk_fill_resident); then, when they fit (sized for 288 GB of
-// HBM), builds one set of window tables per merged MSM on the device (pk_build_tables).
-template <class C>
-static int pk_build_tables(pm_ctx *ctx, pm_pk *pk);
-template <class C, class F>
-static int pk_fill_bases(pm_ctx *ctx, pm_pk *pk, F fill);
-template <class C, class F>
-static int pk_fill_resident(pm_ctx *ctx, pm_pk *pk, F fill) {
-    const uint64_t resident = pk_resident_points(pk);
-    PM_HIP(ctx, hipMalloc(&pk->d_bases, (resident ? resident : 1) * sizeof(Affine<C>)));
-    Affine<C> *d = (Affine<C> *)pk->d_bases;
-    if (pk->shard_count == 1 && pk->layout == PM_SHARD_PAIRS) {
-        PM_TRY(for_cat_range<C>(pk, 0, pk->total_points, d, fill));
-    } else {
-        for (int k = 0; k < 3; ++k) {
-            uint64_t at = pk->res_dev_off[k];
-            for (const auto &pc : pk->pieces[k]) {
-                if (pc.count) PM_TRY(for_cat_range<C>(pk, pc.cat_lo, pc.cat_lo + pc.count, d + at, fill));
-                at += pc.count;
-            }
-        }
-    }
-    PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PM_OK;
-}
-
-template <class C, class F>
-static int pk_fill_bases(pm_ctx *ctx, pm_pk *pk, F fill) {
-    PM_TRY(pk_fill_resident<C>(ctx, pk, fill));
-    return pk_build_tables<C>(ctx, pk);
-}
-
+// Sized for 288 GB of HBM: window tables for the merged MSMs that table_grants (key_plan.hpp) gives them to, the infinity flags of the
+// wide mode for those it gives that.
 template <class C>
 static int pk_build_tables(pm_ctx *ctx, pm_pk *pk) {
-    Affine<C> *d = (Affine<C> *)pk->d_bases;
-    const long long tmode = ctx->opt.v[PM_OPT_TABLES];
     pk->max_piece = (uint64_t)msm_max_piece(ctx);
-    if (tmode == PM_TABLES_OFF) return PM_OK;
-    // Budget: free HBM minus the per-proof vectors (~40 Fr per domain point; 26 are in use) and the MSM workspaces: 16 B
-    // per (pair, window) entry of the sort's two ping-pong arrays and the sorted indices, 13-16 windows, plus the
-    // bucket-side arrays -> 256 B per pair of one <= 2^27-pair piece, for the main context's largest MSM and for the
-    // helper context's [a]_1 MSM.  Tables are granted per MSM, smallest first, while they fit; an MSM without tables
-    // runs the per-window pipeline on the plain array.
     size_t free_b = 0, total_b = 0;
     PM_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-    // PM_INFLIGHT_CONTEXTS: how many contexts will prove on this resident key at once (each owns the per-proof vectors
-    // and an MSM workspace; default 1).  The helper context of the overlapped [a]_1 MSM (prove.hip) has a workspace of
-    // its own as well.
-    const int inflight = (int)ctx->opt.v[PM_OPT_INFLIGHT_CONTEXTS];
     const uint64_t vec_n = pk->layout == PM_SHARD_VECTOR ? pk->n / (uint64_t)pk->shard_count : pk->n;   // length of a rank's vectors
-    double budget = 0.9 * (double)free_b - (double)inflight * 64.0 * 40.0 * (double)vec_n;
-    {
-        const uint64_t len_d = pk->res_cnt[2], len_a = pk->res_cnt[0];
-        budget -= (double)inflight * 256.0 * (double)(len_d < pk->max_piece ? len_d : pk->max_piece);
-        budget -= (double)inflight * 256.0 * (double)len_a;
-    }
-    const WindowOption forced = decode_window_option((unsigned)ctx->opt.v[PM_OPT_TABLE_WINDOW_BITS]);
-    int order[3] = {0, 1, 2};
-    std::sort(order, order + 3, [&](int x, int y) { return pk->res_cnt[x] < pk->res_cnt[y]; });
-    for (int q = 0; q < 3; ++q) {
-        const int k = order[q];
-        const uint64_t len = pk->res_cnt[k];
-        if (!len) continue;
-        MsmTables tb(tables_plan((size_t)len, 1, (size_t)len, (unsigned)C::FrP::BITS, forced), (size_t)len);
-        // no table plan at all (nwin x points would overflow the u32 table indices: the 335 M-pair [d]_1 of a 2^24-gate key) counts
-        // as "does not fit"
-        const double need = tb.planned() ? (double)len * tb.nwin * sizeof(TablePoint<C>) + (double)len : 1e300;
-        const bool force_wide = tmode == PM_TABLES_WIDE;      // test / tuning knob -- no tables for any MSM, wide mode at any size
-        if (need > budget || force_wide) {
-            // No room for this MSM's tables (the 10n-pair [d]_1 of a 2^24-gate key on one GPU: 515 GB): WIDE mode -- the same
-            // sort / accumulate / reduce kernels on the plain base array, one bucket set per window, 13 additions per pair
-            // instead of the 16 of the one-shot pipeline.  Costs one infinity-flag byte per point.  PM_TABLES_NO_WIDE disables.
-            const size_t piece = (size_t)(len < pk->max_piece ? len : pk->max_piece);
-            MsmTables wt(tmode == PM_TABLES_NO_WIDE ? WindowLayout() : wide_plan(piece, forced), 0);
-            if (wt.planned() && (piece >= ((size_t)1 << 18) || force_wide) && (double)len < budget) {
-                budget -= (double)len;
-                PM_HIP(ctx, hipMalloc(&pk->d_tab_inf[k], len));
-                PM_TRY(infinity_flags<C>(ctx, d + pk->res_dev_off[k], (size_t)len, (unsigned char *)pk->d_tab_inf[k]));
-                wt.inf = (const unsigned char *)pk->d_tab_inf[k];
-                pk->tables[k] = wt;
-            }
-            continue;
-        }
-        budget -= need;
-        PM_HIP(ctx, hipMalloc(&pk->d_tab[k], len * tb.nwin * sizeof(TablePoint<C>)));
-        PM_HIP(ctx, hipMalloc(&pk->d_tab_inf[k], len));
-        PM_TRY(infinity_flags<C>(ctx, d + pk->res_dev_off[k], (size_t)len, (unsigned char *)pk->d_tab_inf[k]));
-        PM_TRY(tables_build<C>(ctx, d + pk->res_dev_off[k], (TablePoint<C> *)pk->d_tab[k], (size_t)len, tb));
+    const auto grants = table_grants(free_b, (int)ctx->opt.v[PM_OPT_INFLIGHT_CONTEXTS], vec_n, pk->res_cnt, pk->max_piece, ctx->opt.v[PM_OPT_TABLES],
+                                     (unsigned)ctx->opt.v[PM_OPT_TABLE_WINDOW_BITS], (unsigned)C::FrP::BITS, sizeof(TablePoint<C>));
+    for (int k = 0; k < 3; ++k) {
+        if (grants[k].kind == Grant::NONE) continue;
+        const bool wide = grants[k].kind == Grant::WIDE;
+        const size_t len = (size_t)pk->res_cnt[k];
+        const Affine<C> *points = (const Affine<C> *)pk->d_bases + pk->res_dev_off[k];
+        MsmTables tb(grants[k].layout, wide ? 0 : len);
+        if (!wide) PM_HIP(ctx, pk->alloc(&pk->d_tab[k], len * tb.nwin * sizeof(TablePoint<C>)));
+        PM_HIP(ctx, pk->alloc(&pk->d_tab_inf[k], len));
+        PM_TRY(infinity_flags<C>(ctx, points, len, (unsigned char *)pk->d_tab_inf[k]));
+        if (!wide) PM_TRY(tables_build<C>(ctx, points, (TablePoint<C> *)pk->d_tab[k], len, tb));
         tb.inf = (const unsigned char *)pk->d_tab_inf[k];
         tb.table = pk->d_tab[k];
         pk->tables[k] = tb;
@@ -759,40 +574,90 @@ static int pk_build_tables(pm_ctx *ctx, pm_pk *pk) {
     return PM_OK;
 }
 
+// The one skeleton of the three ways a key comes to be (pm_pk_load*, pm_pk_load_bytes, pm_pk_generate*): plan, segment lists, matrices,
+// resident points, window tables.  *out is written on success only; on every other way out the key goes, and its device memory with it.
+//   planned(st, pk)   after key_plan, with its status: the caller's own checks of the shape; returns the status to go on with
+//   uploaded(st, pk)  after pk_upload_matrices, likewise: what the caller prepares once the matrices are resident
+//   fill(vec, start, count, dst)   points [start, start + count) of base vector `vec` to the device at dst, in the internal form
+//   filled()          between the fill and the tables: the byte loader reads its verdicts and frees its staging -- the tables want the memory
+template <class C, class Planned, class Uploaded, class Fill, class Filled>
+static int pk_build(pm_ctx *ctx, uint64_t m0, uint64_t mw, uint64_t nr, int shard_rank, int shard_count, int layout, const pm_csr *a, const pm_csr *b,
+                    const pm_csr *c, Planned planned, Uploaded uploaded, Fill fill, Filled filled, pm_pk **out) {
+    typedef typename C::FrP P;
+    std::unique_ptr<pm_pk> pk(new pm_pk());
+    pk->curve = C::ID;
+    pk->device = ctx->device;
+    const long long seg_log = ctx->opt.v[PM_OPT_MAX_SEG_LOG];   // test knob: many tiny sub-segments
+    const int st = key_plan(C::TWO_ADICITY, m0, mw, nr, shard_rank, shard_count, layout, seg_log > 0 ? (uint64_t)1 << seg_log : 0, *pk);
+    Fp<P> w;   // omega: the generator of the size-n domain
+    for (int i = 0; i < P::N; ++i) w.l[i] = C::ROOT_MONT[i];
+    for (unsigned i = pk->log_n; i < (unsigned)C::TWO_ADICITY; ++i) w = sqr<P>(w);
+    memcpy(pk->omega, w.l, 32);
+    PM_TRY(planned(st, *pk));
+    if (pk->layout == PM_SHARD_VECTOR) {   // the division scan reads both lists on the device (prove_sharded.hip: k_seg_base, k_seg_chain)
+        PM_HIP(ctx, pk->alloc(&pk->d_segs, pk->segs.size() * sizeof(pmlayout::Segment)));
+        PM_HIP(ctx, hipMemcpy(pk->d_segs, pk->segs.data(), pk->segs.size() * sizeof(pmlayout::Segment), hipMemcpyHostToDevice));
+        PM_HIP(ctx, pk->alloc(&pk->d_all_segs, pk->all_segs.size() * sizeof(pm_pk::SegRef)));
+        PM_HIP(ctx, hipMemcpy(pk->d_all_segs, pk->all_segs.data(), pk->all_segs.size() * sizeof(pm_pk::SegRef), hipMemcpyHostToDevice));
+    }
+    PM_TRY(uploaded(pk_upload_matrices<C>(ctx, pk.get(), a, b, c), *pk));
+    PM_HIP(ctx, pk->alloc(&pk->d_bases, std::max<uint64_t>(pk->resident_points(), 1) * sizeof(Affine<C>)));
+    PM_TRY(pk->for_resident([&](uint64_t lo, uint64_t count, uint64_t at) {
+        return count ? for_cat_range<C>(pk.get(), lo, lo + count, (Affine<C> *)pk->d_bases + at, fill) : (int)PM_OK;
+    }));
+    PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PM_TRY(filled());
+    PM_TRY(pk_build_tables<C>(ctx, pk.get()));
+    *out = pk.release();
+    return PM_OK;
+}
+static int pk_pass(int st, const pm_pk &) { return st; }   // a caller of pk_build with nothing to do at a step
+static int pk_nothing() { return PM_OK; }
+
+// The way in of all three: the device, the curve, and a host exception while the key is read or built (bad_alloc in the parse of the
+// bytes, in a matrix copy, in the plan's vectors) as a status with the message in pm_last_error, never an abort.
+template <class F>
+static int pk_entry(pm_ctx *ctx, int curve, F body) {
+    PM_TRY(set_device(ctx));
+    try {
+        return with_curve(curve, body);
+    } catch (const std::exception &e) {
+        ctx->err = e.what();
+        return PM_ERR_STATE;
+    }
+}
+
 template <class C>
 static int pk_load_impl(pm_ctx *ctx, uint64_t n, uint64_t m0, uint64_t mw, uint64_t nr, uint64_t sigma, const pm_csr *a,
                         const pm_csr *b, const pm_csr *c, const pm_base_array *bases, int shard_rank, int shard_count, int layout,
                         pm_pk **out) {
-    pm_pk *pk = new pm_pk();
-    auto guard = [&](int st) { if (st != PM_OK) pk_release(pk); return st; };
-    int st = pk_init_layout<C>(ctx, pk, m0, mw, nr, shard_rank, shard_count, layout);
-    if (st) return guard(st);
-    if (pk->n != n || pk->sigma != sigma) return guard(PM_ERR_INVALID_ARG);
-    for (int v = 0; v < PM_NUM_BASE_VECS; ++v)
-        if (bases[v].len < pk->base_len[v] || bases[v].stride < sizeof(Affine<C>) || !bases[v].points)
-            return guard(PM_ERR_LEN_MISMATCH);
-    st = pk_upload_matrices<C>(ctx, pk, a, b, c);
-    if (st) return guard(st);
     std::vector<Affine<C>> tmp;
-    st = pk_fill_bases<C>(ctx, pk, [&](int v, uint64_t start, uint64_t count, Affine<C> *dst) -> int {
-        tmp.resize(count);
-        repack_bases<C>((const uint8_t *)bases[v].points + start * bases[v].stride, bases[v].stride, count, tmp.data());
-        PM_HIP(ctx, hipMemcpy(dst, tmp.data(), count * sizeof(Affine<C>), hipMemcpyHostToDevice));
-        PM_TRY(bases_convert<C>(ctx, dst, count, true));
-        PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return PM_OK;
-    });
-    if (st) return guard(st);
-    *out = pk;
-    return PM_OK;
+    return pk_build<C>(
+        ctx, m0, mw, nr, shard_rank, shard_count, layout, a, b, c,
+        [&](int st, const pm_pk &pk) -> int {
+            if (st) return st;
+            if (pk.n != n || pk.sigma != sigma) return PM_ERR_INVALID_ARG;
+            for (int v = 0; v < PM_NUM_BASE_VECS; ++v)
+                if (bases[v].len < pk.base_len[v] || bases[v].stride < sizeof(Affine<C>) || !bases[v].points) return PM_ERR_LEN_MISMATCH;
+            return PM_OK;
+        },
+        pk_pass,
+        [&](int v, uint64_t start, uint64_t count, Affine<C> *dst) -> int {
+            tmp.resize(count);
+            repack_bases<C>((const uint8_t *)bases[v].points + start * bases[v].stride, bases[v].stride, count, tmp.data());
+            PM_HIP(ctx, hipMemcpy(dst, tmp.data(), count * sizeof(Affine<C>), hipMemcpyHostToDevice));
+            PM_TRY(bases_convert<C>(ctx, dst, count, true));
+            PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            return PM_OK;
+        },
+        pk_nothing, out);
 }
 
 extern "C" int pm_pk_load_sharded(pm_ctx *ctx, int curve, uint64_t n, uint64_t m0, uint64_t mw, uint64_t nr, uint64_t sigma,
                                   const pm_csr *a, const pm_csr *b, const pm_csr *c, const pm_base_array bases[PM_NUM_BASE_VECS],
                                   int shard_rank, int shard_count, int layout, pm_pk **out) {
     if (!ctx || !a || !b || !c || !bases || !out) return PM_ERR_INVALID_ARG;
-    PM_TRY(set_device(ctx));
-    return with_curve(curve, [&](auto cv) {
+    return pk_entry(ctx, curve, [&](auto cv) {
         return pk_load_impl<type_of<decltype(cv)>>(ctx, n, m0, mw, nr, sigma, a, b, c, bases, shard_rank, shard_count, layout, out);
     });
 }
@@ -829,26 +694,12 @@ static int pk_load_bytes_impl(pm_ctx *ctx, const uint8_t *bytes, size_t len, int
     const size_t NB = 4 * C::FqP::N;
     WireLayout w;
     PM_TRY(pk_wire_parse<C>(bytes, len, w, ctx->err));
-    pm_pk *pk = new pm_pk();
-    auto fail = [&](int st, const std::string &why) { pk_release(pk); if (!why.empty()) ctx->err = "pm_pk_load_bytes: " + why; return st; };
-    int st = pk_init_layout<C>(ctx, pk, w.m0, w.mw, w.nr, shard_rank, shard_count, layout);
-    if (st) return fail(st, st == PM_ERR_HIP ? "" : "the key's shape or the shard arguments are not supported");
-    // the checks of pmhost::pk_load: the prover hashes the vk's n / m0 / omega while the device derives its own from the SAP header
-    if (w.vk_m0 != w.m0) return fail(PM_ERR_INVALID_ARG, "vk.m0 disagrees with the SAP matrices' m0");
-    if (w.n != pk->n || w.sigma != pk->sigma) return fail(PM_ERR_INVALID_ARG, "vk.n / vk.sigma disagree with the domain of the SAP matrices");
-    if (memcmp(w.omega, pk->omega, 32) != 0) return fail(PM_ERR_INVALID_ARG, "vk.omega is not the generator of the size-n domain");
-    for (int v = 0; v < PM_NUM_BASE_VECS; ++v)
-        if (w.vec_len[v] != pk->base_len[v])
-            return fail(PM_ERR_INVALID_ARG, std::string(BASE_VEC_NAMES[v]) + ": length " + std::to_string(w.vec_len[v]) +
-                                                " does not match the key's shape (" + std::to_string(pk->base_len[v]) + ")");
+    auto fail = [&](int st, const std::string &why) { if (!why.empty()) ctx->err = "pm_pk_load_bytes: " + why; return st; };
     pm_csr m[3];
     for (int k = 0; k < 3; ++k) {
         if (w.col[k].empty()) { w.col[k].push_back(0); w.val[k].assign(4, 0); }   // non-null pointers for an empty matrix
         m[k] = pm_csr{w.nr, w.rowptr[k].data(), w.col[k].data(), w.val[k].data()};
-        if (w.rowptr[k].size() != w.nr + 1) return fail(PM_ERR_INVALID_ARG, "a matrix does not have num_constraints rows");
     }
-    st = pk_upload_matrices<C>(ctx, pk, &m[0], &m[1], &m[2]);
-    if (st) return fail(st, st == PM_ERR_HIP ? "" : "a matrix column is out of range");
     // The compressed points of each requested range go through two staging slots, each a pinned host buffer and a device buffer:
     // the host copies chunk k + 1 out of the caller's bytes (an mmap, say) while the device decodes chunk k.  A slot is refilled
     // only after the decode that read it has finished (its event is recorded behind the kernel), whatever way the runtime moves
@@ -856,57 +707,69 @@ static int pk_load_bytes_impl(pm_ctx *ctx, const uint8_t *bytes, size_t len, int
     const size_t CH = wire_chunk(ctx);
     ScopedDevBuf d_in[2], d_bad;
     PinnedPair pin;
-    if (d_in[0].reserve(CH * NB) != hipSuccess || d_in[1].reserve(CH * NB) != hipSuccess || d_bad.reserve(PM_NUM_BASE_VECS * 8) != hipSuccess)
-        return fail(PM_ERR_HIP, "out of device memory for the staging buffers");
-    for (int k = 0; k < 2; ++k)
-        if (hipHostMalloc(&pin.p[k], CH * NB, hipHostMallocDefault) != hipSuccess ||
-            hipEventCreateWithFlags(&pin.ev[k], hipEventDisableTiming) != hipSuccess)
-            return fail(PM_ERR_HIP, "out of pinned host memory for the staging buffers");
-    if (hipMemsetAsync(d_bad.p, 0xFF, PM_NUM_BASE_VECS * 8, ctx->stream) != hipSuccess) return fail(PM_ERR_HIP, "hipMemsetAsync failed");
-    unsigned long long *bad = d_bad.as<unsigned long long>();
     int slot = 0;
     bool used[2] = {false, false};
-    st = pk_fill_resident<C>(ctx, pk, [&](int v, uint64_t start, uint64_t count, Affine<C> *dst) -> int {
-        for (uint64_t s = 0; s < count; s += CH) {
-            const uint64_t cnt = std::min<uint64_t>(CH, count - s);
-            if (used[slot]) PM_HIP(ctx, hipEventSynchronize(pin.ev[slot]));
-            memcpy(pin.p[slot], bytes + w.vec_off[v] + (start + s) * NB, cnt * NB);
-            PM_HIP(ctx, hipMemcpyAsync(d_in[slot].p, pin.p[slot], cnt * NB, hipMemcpyHostToDevice, ctx->stream));
-            PM_TRY(g1_decode_device<C>(ctx, d_in[slot].as<uint8_t>(), cnt, validate != 0, dst + s, nullptr, bad + v, start + s));
-            PM_HIP(ctx, hipEventRecord(pin.ev[slot], ctx->stream));
-            used[slot] = true;
-            slot ^= 1;
-            PM_TRY(bases_convert<C>(ctx, dst + s, cnt, true));
-        }
-        return PM_OK;
-    });
-    if (st) return fail(st, "");
-    unsigned long long h_bad[PM_NUM_BASE_VECS];
-    if (hipMemcpy(h_bad, d_bad.p, sizeof(h_bad), hipMemcpyDeviceToHost) != hipSuccess) return fail(PM_ERR_HIP, "reading the verdicts failed");
-    for (int v : WIRE_VECTOR_ORDER)
-        if (h_bad[v] != ~0ull)
-            return fail(PM_ERR_INVALID_ARG, std::string(BASE_VEC_NAMES[v]) + "[" + std::to_string(h_bad[v] >> 8) + "]: " +
-                                                g1_status_text(C::ID, (int)(h_bad[v] & 0xFF)));
-    for (ScopedDevBuf &b : d_in) b.release();   // before the tables: they want the memory
-    st = pk_build_tables<C>(ctx, pk);
-    if (st) return fail(st, "");
-    *out = pk;
-    return PM_OK;
+    return pk_build<C>(
+        ctx, w.m0, w.mw, w.nr, shard_rank, shard_count, layout, &m[0], &m[1], &m[2],
+        [&](int st, const pm_pk &pk) -> int {
+            if (st) return fail(st, "the key's shape or the shard arguments are not supported");
+            // the checks of pmhost::pk_load: the prover hashes the vk's n / m0 / omega while the device derives its own from the SAP header
+            if (w.vk_m0 != w.m0) return fail(PM_ERR_INVALID_ARG, "vk.m0 disagrees with the SAP matrices' m0");
+            if (w.n != pk.n || w.sigma != pk.sigma) return fail(PM_ERR_INVALID_ARG, "vk.n / vk.sigma disagree with the domain of the SAP matrices");
+            if (memcmp(w.omega, pk.omega, 32) != 0) return fail(PM_ERR_INVALID_ARG, "vk.omega is not the generator of the size-n domain");
+            for (int v = 0; v < PM_NUM_BASE_VECS; ++v)
+                if (w.vec_len[v] != pk.base_len[v])
+                    return fail(PM_ERR_INVALID_ARG, std::string(BASE_VEC_NAMES[v]) + ": length " + std::to_string(w.vec_len[v]) +
+                                                        " does not match the key's shape (" + std::to_string(pk.base_len[v]) + ")");
+            for (int k = 0; k < 3; ++k)
+                if (w.rowptr[k].size() != w.nr + 1) return fail(PM_ERR_INVALID_ARG, "a matrix does not have num_constraints rows");
+            return PM_OK;
+        },
+        [&](int st, const pm_pk &) -> int {
+            if (st) return fail(st, st == PM_ERR_HIP ? "" : "a matrix column is out of range");
+            if (d_in[0].reserve(CH * NB) != hipSuccess || d_in[1].reserve(CH * NB) != hipSuccess || d_bad.reserve(PM_NUM_BASE_VECS * 8) != hipSuccess)
+                return fail(PM_ERR_HIP, "out of device memory for the staging buffers");
+            for (int k = 0; k < 2; ++k)
+                if (hipHostMalloc(&pin.p[k], CH * NB, hipHostMallocDefault) != hipSuccess ||
+                    hipEventCreateWithFlags(&pin.ev[k], hipEventDisableTiming) != hipSuccess)
+                    return fail(PM_ERR_HIP, "out of pinned host memory for the staging buffers");
+            if (hipMemsetAsync(d_bad.p, 0xFF, PM_NUM_BASE_VECS * 8, ctx->stream) != hipSuccess) return fail(PM_ERR_HIP, "hipMemsetAsync failed");
+            return PM_OK;
+        },
+        [&](int v, uint64_t start, uint64_t count, Affine<C> *dst) -> int {
+            for (uint64_t s = 0; s < count; s += CH) {
+                const uint64_t cnt = std::min<uint64_t>(CH, count - s);
+                if (used[slot]) PM_HIP(ctx, hipEventSynchronize(pin.ev[slot]));
+                memcpy(pin.p[slot], bytes + w.vec_off[v] + (start + s) * NB, cnt * NB);
+                PM_HIP(ctx, hipMemcpyAsync(d_in[slot].p, pin.p[slot], cnt * NB, hipMemcpyHostToDevice, ctx->stream));
+                PM_TRY(g1_decode_device<C>(ctx, d_in[slot].as<uint8_t>(), cnt, validate != 0, dst + s, nullptr, d_bad.as<unsigned long long>() + v, start + s));
+                PM_HIP(ctx, hipEventRecord(pin.ev[slot], ctx->stream));
+                used[slot] = true;
+                slot ^= 1;
+                PM_TRY(bases_convert<C>(ctx, dst + s, cnt, true));
+            }
+            return PM_OK;
+        },
+        [&]() -> int {
+            unsigned long long h_bad[PM_NUM_BASE_VECS];
+            if (hipMemcpy(h_bad, d_bad.p, sizeof(h_bad), hipMemcpyDeviceToHost) != hipSuccess) return fail(PM_ERR_HIP, "reading the verdicts failed");
+            for (int v : WIRE_VECTOR_ORDER)
+                if (h_bad[v] != ~0ull)
+                    return fail(PM_ERR_INVALID_ARG, std::string(BASE_VEC_NAMES[v]) + "[" + std::to_string(h_bad[v] >> 8) + "]: " +
+                                                        g1_status_text(C::ID, (int)(h_bad[v] & 0xFF)));
+            for (ScopedDevBuf &b : d_in) b.release();   // before the tables: they want the memory
+            return PM_OK;
+        },
+        out);
 }
 
 extern "C" int pm_pk_load_bytes(pm_ctx *ctx, int curve, const uint8_t *bytes, size_t len, int validate, int shard_rank, int shard_count,
                                 int layout, pm_pk **out) {
     if (!ctx || !bytes || !out) return PM_ERR_INVALID_ARG;
     *out = nullptr;
-    PM_TRY(set_device(ctx));
-    try {
-        return with_curve(curve, [&](auto cv) {
-            return pk_load_bytes_impl<type_of<decltype(cv)>>(ctx, bytes, len, validate, shard_rank, shard_count, layout, out);
-        });
-    } catch (const std::exception &e) {       // host allocation failure while parsing the matrices: a status, never an abort
-        ctx->err = e.what();
-        return PM_ERR_STATE;
-    }
+    return pk_entry(ctx, curve, [&](auto cv) {
+        return pk_load_bytes_impl<type_of<decltype(cv)>>(ctx, bytes, len, validate, shard_rank, shard_count, layout, out);
+    });
 }
 
 template <class C>
@@ -947,85 +810,73 @@ static int pk_generate_impl(pm_ctx *ctx, uint64_t m0, uint64_t mw, uint64_t nr, 
                             int shard_count, int layout, pm_pk **out) {
     typedef typename C::FrP P;
     typedef Fp<P> Fr;
-    pm_pk *pk = new pm_pk();
-    auto guard = [&](int st) { if (st != PM_OK) pk_release(pk); return st; };
     HostProfile hp("setup", shard_rank);            // PM_PROFILE_HOST=1: where the host thread's time goes (stderr)
-    int st = pk_init_layout<C>(ctx, pk, m0, mw, nr, shard_rank, shard_count, layout);
-    if (st) return guard(st);
-    hp.mark("layout");
-    st = pk_upload_matrices<C>(ctx, pk, a, b, c);
-    if (st) return guard(st);
-    hp.mark("matrices: first-entry pass + upload");
-    const uint64_t n = pk->n, sigma = pk->sigma, Lz = proof_shape(pk).Lz;
-    Fr x, z, omega;
+    Fr x, z;
     memcpy(x.l, x_trap, 32);
     memcpy(z.l, z_trap, 32);
-    memcpy(omega.l, pk->omega, 32);
-    Fr xn = pow_u64<P>(x, n), one = Fr::one();
-    if (xn.eq(one) || pow_u64<P>(z, n).eq(one)) return guard(PM_ERR_INVALID_ARG);  // sample_element_outside_domain
-    Fr y = pow_u64<P>(x, sigma), yinv = inverse<P>(y);                            // generator.rs:73
-    Fr y_alpha = pow_u64<P>(yinv, 3), y_to_minus_alpha = pow_u64<P>(y, 3), y_gamma = pow_u64<P>(yinv, 5);
-    Fr zh = sub<P>(xn, one);                                                       // :106
-    // uj_wj_lcs scalars (generator.rs:112-136) on the device: Lagrange coefficients at x by chunked batch inversion, the sparse pass
-    // over the CSR matrices already uploaded above (setup.hip: lcs_scalars).  Rounds 1-3 ran both on <= 32 host threads.
-    ScopedDevBuf d_lagrange, d_work, d_lcs_buf;
-    {
-        if (hipMalloc(&d_lcs_buf.p, (Lz ? Lz : 1) * sizeof(Fr)) != hipSuccess) { ctx->err = "out of device memory for the lcs scalars"; return guard(PM_ERR_HIP); }
-        d_lcs_buf.bytes = (Lz ? Lz : 1) * sizeof(Fr);
-        const Fr kscale = mul<P>(zh, inverse<P>(from_u64<P>(n)));
-        st = lcs_scalars<C>(ctx, pk, x, omega, kscale, y_gamma, y_to_minus_alpha, d_lagrange, d_work, d_lcs_buf.as<Fr>());
-        if (st) return guard(st);
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "lcs scalars: stream failed"; return guard(PM_ERR_HIP); }
-        d_lagrange.release();
-        d_work.release();
-    }
-    hp.mark("lcs scalars (device, synchronised)");
-    const Fr *d_lcs = d_lcs_buf.as<Fr>();
-    // per-vector scale of the x-power vectors (generator.rs:82-109)
-    Fr scale[PM_NUM_BASE_VECS];
-    scale[PM_X_POWERS] = one;
-    scale[PM_X_POWERS_Y_ALPHA] = y_alpha;
-    scale[PM_X_POWERS_Y_GAMMA] = y_gamma;
-    scale[PM_X_POWERS_Y_GAMMA_Z] = mul<P>(y_gamma, z);
-    scale[PM_X_POWERS_ZH_BY_Y_ALPHA] = mul<P>(zh, y_to_minus_alpha);
+    Fr scale[PM_NUM_BASE_VECS];                     // per-vector scale of the x-power vectors (generator.rs:82-109)
+    ScopedDevBuf d_lcs_buf;
     const uint64_t CH = (uint64_t)1 << 22;
-    st = pk_fill_bases<C>(ctx, pk, [&](int v, uint64_t start, uint64_t count, Affine<C> *dst) -> int {
-        PM_HIP(ctx, ctx->scratch.reserve(std::min(count, CH) * sizeof(Fr)));
-        Fr *d_sc = ctx->scratch.as<Fr>();
-        for (uint64_t s = 0; s < count; s += CH) {
-            uint64_t cnt = std::min(CH, count - s);
-            const Fr *src = d_sc;
-            if (v == PM_UJ_WJ_LCS_BY_Y_ALPHA) {
-                src = d_lcs + start + s;
-            } else {
-                Fr first = mul<P>(scale[v], pow_u64<P>(x, start + s));
-                PM_TRY(powers_fill<C>(ctx, d_sc, cnt, first, x));
+    const int st = pk_build<C>(
+        ctx, m0, mw, nr, shard_rank, shard_count, layout, a, b, c,
+        [&](int st, const pm_pk &) { hp.mark("layout"); return st; },
+        [&](int st, const pm_pk &pk) -> int {
+            if (st) return st;
+            hp.mark("matrices: first-entry pass + upload");
+            const uint64_t n = pk.n, Lz = pk.base_len[PM_UJ_WJ_LCS_BY_Y_ALPHA];
+            Fr omega;
+            memcpy(omega.l, pk.omega, 32);
+            Fr xn = pow_u64<P>(x, n), one = Fr::one();
+            if (xn.eq(one) || pow_u64<P>(z, n).eq(one)) return PM_ERR_INVALID_ARG;          // sample_element_outside_domain
+            Fr y = pow_u64<P>(x, pk.sigma), yinv = inverse<P>(y);                           // generator.rs:73
+            Fr y_alpha = pow_u64<P>(yinv, 3), y_to_minus_alpha = pow_u64<P>(y, 3), y_gamma = pow_u64<P>(yinv, 5);
+            Fr zh = sub<P>(xn, one);                                                        // :106
+            // uj_wj_lcs scalars (generator.rs:112-136) on the device: Lagrange coefficients at x by chunked batch inversion, the sparse
+            // pass over the CSR matrices uploaded just now (setup.hip: lcs_scalars).  Rounds 1-3 ran both on <= 32 host threads.
+            ScopedDevBuf d_lagrange, d_work;
+            if (hipMalloc(&d_lcs_buf.p, (Lz ? Lz : 1) * sizeof(Fr)) != hipSuccess) { ctx->err = "out of device memory for the lcs scalars"; return PM_ERR_HIP; }
+            d_lcs_buf.bytes = (Lz ? Lz : 1) * sizeof(Fr);
+            const Fr kscale = mul<P>(zh, inverse<P>(from_u64<P>(n)));
+            PM_TRY(lcs_scalars<C>(ctx, &pk, x, omega, kscale, y_gamma, y_to_minus_alpha, d_lagrange, d_work, d_lcs_buf.as<Fr>()));
+            if (hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "lcs scalars: stream failed"; return PM_ERR_HIP; }
+            hp.mark("lcs scalars (device, synchronised)");
+            scale[PM_X_POWERS] = one;
+            scale[PM_X_POWERS_Y_ALPHA] = y_alpha;
+            scale[PM_X_POWERS_Y_GAMMA] = y_gamma;
+            scale[PM_X_POWERS_Y_GAMMA_Z] = mul<P>(y_gamma, z);
+            scale[PM_X_POWERS_ZH_BY_Y_ALPHA] = mul<P>(zh, y_to_minus_alpha);
+            return PM_OK;
+        },
+        [&](int v, uint64_t start, uint64_t count, Affine<C> *dst) -> int {
+            PM_HIP(ctx, ctx->scratch.reserve(std::min(count, CH) * sizeof(Fr)));
+            Fr *d_sc = ctx->scratch.as<Fr>();
+            for (uint64_t s = 0; s < count; s += CH) {
+                uint64_t cnt = std::min(CH, count - s);
+                const Fr *src = d_sc;
+                if (v == PM_UJ_WJ_LCS_BY_Y_ALPHA) {
+                    src = d_lcs_buf.as<Fr>() + start + s;
+                } else {
+                    Fr first = mul<P>(scale[v], pow_u64<P>(x, start + s));
+                    PM_TRY(powers_fill<C>(ctx, d_sc, cnt, first, x));
+                }
+                PM_TRY(fixed_base_batch<C>(ctx, src, cnt, dst + s));
+                PM_TRY(bases_convert<C>(ctx, dst + s, cnt, true));
+                PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
             }
-            PM_TRY(fixed_base_batch<C>(ctx, src, cnt, dst + s));
-            PM_TRY(bases_convert<C>(ctx, dst + s, cnt, true));
-            PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        return PM_OK;
-    });
-    if (st) return guard(st);
-    hp.mark("bases + tables (device, synchronised)");
-    *out = pk;
-    return PM_OK;
+            return PM_OK;
+        },
+        pk_nothing, out);
+    if (st == PM_OK) hp.mark("bases + tables (device, synchronised)");
+    return st;
 }
 
 extern "C" int pm_pk_generate_sharded(pm_ctx *ctx, int curve, uint64_t m0, uint64_t mw, uint64_t nr, const pm_csr *a,
                                       const pm_csr *b, const pm_csr *c, const uint64_t *x_trapdoor, const uint64_t *z_trapdoor,
                                       int shard_rank, int shard_count, int layout, pm_pk **out) {
     if (!ctx || !a || !b || !c || !x_trapdoor || !z_trapdoor || !out) return PM_ERR_INVALID_ARG;
-    PM_TRY(set_device(ctx));
-    try {
-        return with_curve(curve, [&](auto cv) {
-            return pk_generate_impl<type_of<decltype(cv)>>(ctx, m0, mw, nr, a, b, c, x_trapdoor, z_trapdoor, shard_rank, shard_count, layout, out);
-        });
-    } catch (const std::exception &e) {       // host allocation failure in the O(n) setup vectors: a status, never an abort
-        ctx->err = e.what();
-        return PM_ERR_STATE;
-    }
+    return pk_entry(ctx, curve, [&](auto cv) {
+        return pk_generate_impl<type_of<decltype(cv)>>(ctx, m0, mw, nr, a, b, c, x_trapdoor, z_trapdoor, shard_rank, shard_count, layout, out);
+    });
 }
 
 extern "C" int pm_pk_generate(pm_ctx *ctx, int curve, uint64_t m0, uint64_t mw, uint64_t nr, const pm_csr *a,
@@ -1083,19 +934,12 @@ extern "C" int pm_pk_msm_plan(const pm_pk *pk, int which, uint64_t *pairs, unsig
 
 // Device element offset of [offset, offset + len) of base vector `which`; false if that range is not resident on this shard.
 static bool pk_dev_range(const pm_pk *pk, int which, size_t offset, size_t len, uint64_t *dev_off) {
-    uint64_t lo = pk->seg_off[which] + offset, hi = lo + len;
-    if (pk->shard_count == 1 && pk->layout == PM_SHARD_PAIRS) {
-        *dev_off = lo;
-        return true;
-    }
-    for (int k = 0; k < 3; ++k) {
-        uint64_t at = pk->res_dev_off[k];
-        for (const auto &pc : pk->pieces[k]) {
-            if (lo >= pc.cat_lo && hi <= pc.cat_lo + pc.count) { *dev_off = at + (lo - pc.cat_lo); return true; }
-            at += pc.count;
-        }
-    }
-    return false;
+    const uint64_t lo = pk->seg_off[which] + offset, hi = lo + len;
+    return pk->for_resident([&](uint64_t piece_lo, uint64_t count, uint64_t at) {
+        if (lo < piece_lo || hi > piece_lo + count) return 0;
+        *dev_off = at + (lo - piece_lo);
+        return 1;
+    }) != 0;
 }
 
 extern "C" int pm_pk_export_bases(pm_ctx *ctx, const pm_pk *pk, int which, size_t offset, size_t len, uint64_t *out_xy) {

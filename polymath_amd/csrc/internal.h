@@ -14,10 +14,9 @@
 #include <vector>
 
 #include "../../include/polymath_hip.h"
-#include "../host/layout.hpp"
+#include "../host/key_plan.hpp"
 #include "../host/solve_plan.hpp"
 #include "ec.cuh"
-#include "msm_plan.h"
 
 namespace pm {
 
@@ -94,7 +93,7 @@ struct DevBuf {
 };
 
 // A DevBuf that lives for one call: released on every way out of its scope.  DevBuf itself has no destructor because the context's
-// workspaces (pm_ctx, pm_pk, pm_bases) release explicitly; every call-scoped buffer is one of these.
+// workspaces (pm_ctx, pm_bases) release explicitly; every call-scoped buffer is one of these.
 struct ScopedDevBuf : DevBuf {
     ScopedDevBuf() = default;
     ScopedDevBuf(const ScopedDevBuf &) = delete;
@@ -206,49 +205,43 @@ namespace pm {
 uint64_t pk_serial_next();   // api.hip: 1, 2, 3, ... -- a key's identity for caches that outlive it (an address can come back)
 }
 
-struct pm_pk {
+// A resident proving key: the plan of host/key_plan.hpp (shapes, the logical base concatenation, this rank's pieces and segments --
+// the provers read its fields as the key's) and the device memory that holds what it describes.
+struct pm_pk : pm::KeyPlan {
     uint64_t serial = pm::pk_serial_next();
-    int curve, device;
-    uint64_t n, m0, mw, nr, sigma;
-    unsigned log_n;
-    uint64_t omega[4];
-    int shard_rank, shard_count;
+    int curve = 0, device = 0;
+    uint64_t omega[4] = {0, 0, 0, 0};
+    // Every device allocation of the key is made by alloc() and freed by the destructor; the typed pointers below are views of them.
+    std::vector<void *> owned;
+    template <class T>
+    hipError_t alloc(T **p, size_t bytes) {
+        owned.reserve(owned.size() + 1);
+        const hipError_t e = hipMalloc((void **)p, bytes);
+        if (e == hipSuccess) owned.push_back((void *)*p);
+        return e;
+    }
+    pm_pk() = default;
+    pm_pk(const pm_pk &) = delete;
+    void operator=(const pm_pk &) = delete;
+    ~pm_pk() {
+        (void)hipSetDevice(device);
+        for (void *p : owned) (void)hipFree(p);
+    }
     // R1CS matrices on the device (CSR; duplicates of a column inside a row removed, see api)
-    uint64_t *d_rowptr[3];
-    uint32_t *d_col[3];
-    uint64_t *d_val[3];
-    uint64_t nnz[3];
-    // all base vectors in one device allocation, ordered
-    //   [uj_wj_lcs | x_powers_zh | x_powers | y_alpha | y_gamma | y_gamma_z]
-    // so that the pair ranges of the merged MSMs are contiguous (DESIGN.md "MSM merging").
-    void *d_bases;
-    uint64_t base_len[PM_NUM_BASE_VECS];  // logical lengths (whole key)
-    uint64_t seg_off[PM_NUM_BASE_VECS];   // element offset of each vector inside the LOGICAL concatenation
-    uint64_t total_points;                // logical
-    // shard: this device holds logical points [res_lo[k], res_hi[k]) of MSM k (0 = a, 1 = c, 2 = d)
-    // stored at d_bases + res_dev_off[k]
-    uint64_t res_lo[3], res_hi[3], res_dev_off[3];
-    uint64_t msm_lo[3], msm_len[3];  // logical pair range of each merged MSM inside the concatenation
-    // Generalisation of [res_lo, res_hi): MSM k's resident pairs are `pieces[k]` (ranges of the logical concatenation),
-    // stored back to back at d_bases + res_dev_off[k]; res_cnt[k] = their total.  layout 0 (PM_SHARD_PAIRS): one
-    // contiguous piece per MSM, the prover's scalar vectors are whole and this rank reads them at res_lo[k].
-    // layout 1 (PM_SHARD_VECTOR, host/layout.hpp): the pieces follow the blocked coefficient layout, the prover builds
-    // only this rank's scalars (in piece order) and `segs` is this rank's part of the quotient index space.
-    int layout;
-    std::vector<pmlayout::Piece> pieces[3];
-    uint64_t res_cnt[3];
-    std::vector<pmlayout::Segment> segs;
-    uint64_t max_seg;
+    uint64_t *d_rowptr[3] = {nullptr, nullptr, nullptr};
+    uint32_t *d_col[3] = {nullptr, nullptr, nullptr};
+    uint64_t *d_val[3] = {nullptr, nullptr, nullptr};
+    uint64_t nnz[3] = {0, 0, 0};
+    // the resident points of all base vectors in one allocation: the pieces of merged MSM k back to back from element res_dev_off[k]
+    // (the whole concatenation in its own order when whole_resident()), so that every merged MSM reads one contiguous range
+    void *d_bases = nullptr;
     uint64_t max_piece = (uint64_t)1 << 27;   // msm_max_piece of the creating context (pm_pk_msm_plan reports plans without a context)
-    struct SegRef { uint64_t a, b; uint32_t rank, idx; };
-    std::vector<SegRef> all_segs;    // the segments of ALL ranks in increasing index order (the carry chain of the division scan)
-    size_t seg_slots;                // max over ranks of the segment count
-    void *d_segs;                    // device copy of `segs`
-    void *d_all_segs = nullptr;      // device copy of `all_segs`
+    void *d_segs = nullptr;                   // device copy of `segs`
+    void *d_all_segs = nullptr;               // device copy of `all_segs`
     // Window tables, ONE SET PER MERGED MSM (its own window width: the optimum depends on the pair count):
-    // d_tab[k] holds [nwin_k][res_hi[k] - res_lo[k]] points, window 0 being a copy of the MSM's resident slice.
+    // d_tab[k] holds [nwin_k][res_cnt[k]] points, window 0 being a copy of the MSM's resident pairs.
     pm::MsmTables tables[3];
-    void *d_tab[3], *d_tab_inf[3];   // tables and their infinity flags (tables[k].inf)
+    void *d_tab[3] = {nullptr, nullptr, nullptr}, *d_tab_inf[3] = {nullptr, nullptr, nullptr};   // tables and their infinity flags (tables[k].inf)
 };
 
 // One persistent host thread per context that runs a helper job (the overlapped [a]_1 MSM of prove.hip): created on first

@@ -56,11 +56,11 @@ int msm_resident_end(pm_ctx *ctx, uint64_t *out_xy, int *out_inf) {
     return PM_OK;
 }
 
-// PM_SHARD_PAIRS: the scalar vector is the whole logical one; this rank's pairs are the contiguous range at res_lo
+// PM_SHARD_PAIRS: the scalar vector is the whole logical one; this rank's pairs are its one piece of the MSM's range
 template <class C>
 static int msm_shard(pm_ctx *ctx, const pm_pk *pk, int which, const Fp<typename C::FrP> *d_scalars, uint64_t *out_xy,
                      int *out_inf) {
-    return msm_resident<C>(ctx, pk, which, d_scalars + pk->res_lo[which], out_xy, out_inf);
+    return msm_resident<C>(ctx, pk, which, d_scalars + (pk->pieces[which][0].cat_lo - pk->msm_lo[which]), out_xy, out_inf);
 }
 
 // ------------------------------------------------------------------------------- phase 1

@@ -22,8 +22,10 @@ namespace {
 
 // the key's MSM ranges are the scalar rows this file writes
 bool layout_ok(const pm_pk *pk, const ProofShape &d) {
-    return pk->shard_count == 1 && pk->layout == PM_SHARD_PAIRS && pk->res_cnt[0] == d.len_a && pk->res_cnt[1] == d.len_c &&
-           pk->res_cnt[2] == d.len_d && pk->res_lo[0] == 0 && pk->res_lo[1] == 0 && pk->res_lo[2] == 0;
+    const uint64_t len[3] = {d.len_a, d.len_c, d.len_d};
+    for (int k = 0; k < 3; ++k)   // one piece per MSM: all of its range
+        if (pk->pieces[k].size() != 1 || pk->pieces[k][0].cat_lo != pk->msm_lo[k] || pk->pieces[k][0].count != len[k]) return false;
+    return pk->whole_resident();
 }
 
 // Fr elements of the group's vectors per proof (pm_ctx::pb and the transforms' out-of-place temporary)

@@ -69,7 +69,7 @@ static inline ProofShape proof_shape(uint64_t n, uint64_t m0, uint64_t mw, uint6
     s.Lz = 2 * m0 + mw + nr;
     s.len_a = n + 3;
     s.len_c = s.Lz + (n - 1) + (n + 1) + 3 + 2;
-    s.num_len = 8 * sigma + 2 * n - 1;
+    s.num_len = pmlayout::numerator_len(n);   // sigma = n + 3 on every key (key_shape)
     s.len_d = s.num_len - 1;
     s.cnt[0] = s.num_len;
     while (s.cnt[s.levels] > 64 && s.levels < 6) {

@@ -16,6 +16,8 @@
 
 #include <vector>
 
+#include "../../include/polymath_hip.h"
+
 #ifndef PM_LAYOUT_HD
 #ifdef __HIPCC__
 #define PM_LAYOUT_HD __host__ __device__ inline
@@ -50,28 +52,39 @@ PM_LAYOUT_HD uint64_t eval_local(const Layout &L, uint64_t i) { return i / L.N; 
 PM_LAYOUT_HD uint64_t eval_global(const Layout &L, uint64_t j) { return j * L.N + L.q; }
 
 // ---------------------------------------------------------------------------------------------- MSM pair lists
-// A rank's share of a merged MSM is a list of pieces of the key's LOGICAL base concatenation
-//   [uj_wj_lcs (Lz) | x_powers_zh (n-1) | x_powers (n+1) | y_alpha (3) | y_gamma (2) | y_gamma_z (10n+23)]
-// stored back to back in HBM in list order; the scalar vector the prover builds has the same order.
+// The key's LOGICAL base concatenation, as pm_base_vec ids: the ONE statement of its order.  The three merged MSMs read contiguous
+// stretches of it ([c]_1: everything before y_gamma_z, [a]_1: x_powers and two of y_alpha, [d]_1: y_gamma_z), and a rank's share of a
+// merged MSM is a list of pieces of it, stored back to back in HBM in list order; the scalar vector the prover builds has the same order.
+inline constexpr int CAT_ORDER[PM_NUM_BASE_VECS] = {PM_UJ_WJ_LCS_BY_Y_ALPHA, PM_X_POWERS_ZH_BY_Y_ALPHA, PM_X_POWERS,
+                                                    PM_X_POWERS_Y_ALPHA, PM_X_POWERS_Y_GAMMA, PM_X_POWERS_Y_GAMMA_Z};
 struct Piece {
     uint64_t cat_lo, count;
 };
 
+// coefficients of the numerator of the quotient (prover.rs:211-225; the index space is drawn below): 8 sigma + 2n - 1, sigma = n + 3
+inline uint64_t numerator_len(uint64_t n) { return 8 * (n + 3) + 2 * n - 1; }
+
 struct KeyShape {
     uint64_t n, m0, mw, nr, sigma, Lz;
-    uint64_t off_lcs, off_zh, off_xp, off_ya, off_yg, off_ygz;   // segment offsets inside the concatenation
+    // by pm_base_vec: logical length (whole key) and element offset inside the LOGICAL concatenation; all of its points
+    uint64_t base_len[PM_NUM_BASE_VECS], seg_off[PM_NUM_BASE_VECS], total_points;
+    uint64_t off_lcs, off_zh, off_xp, off_ya, off_yg, off_ygz;      // the offsets by name
 };
 
 inline KeyShape key_shape(uint64_t n, uint64_t m0, uint64_t mw, uint64_t nr) {
     KeyShape s;
-    s.n = n; s.m0 = m0; s.mw = mw; s.nr = nr; s.sigma = n + 3;
+    s.n = n; s.m0 = m0; s.mw = mw; s.nr = nr; s.sigma = n + 3;   // generator.rs:66-70
     s.Lz = 2 * m0 + mw + nr;
-    s.off_lcs = 0;
-    s.off_zh = s.Lz;
-    s.off_xp = s.off_zh + (n - 1);
-    s.off_ya = s.off_xp + (n + 1);
-    s.off_yg = s.off_ya + 3;
-    s.off_ygz = s.off_yg + 2;
+    s.base_len[PM_UJ_WJ_LCS_BY_Y_ALPHA] = s.Lz;
+    s.base_len[PM_X_POWERS_ZH_BY_Y_ALPHA] = n - 1;
+    s.base_len[PM_X_POWERS] = n + 1;
+    s.base_len[PM_X_POWERS_Y_ALPHA] = 3;
+    s.base_len[PM_X_POWERS_Y_GAMMA] = 2;
+    s.base_len[PM_X_POWERS_Y_GAMMA_Z] = numerator_len(n);
+    s.total_points = 0;
+    for (int v : CAT_ORDER) { s.seg_off[v] = s.total_points; s.total_points += s.base_len[v]; }
+    s.off_lcs = s.seg_off[PM_UJ_WJ_LCS_BY_Y_ALPHA]; s.off_zh = s.seg_off[PM_X_POWERS_ZH_BY_Y_ALPHA]; s.off_xp = s.seg_off[PM_X_POWERS];
+    s.off_ya = s.seg_off[PM_X_POWERS_Y_ALPHA]; s.off_yg = s.seg_off[PM_X_POWERS_Y_GAMMA]; s.off_ygz = s.seg_off[PM_X_POWERS_Y_GAMMA_Z];
     return s;
 }
 
@@ -108,7 +121,7 @@ inline std::vector<Piece> pieces_c(const KeyShape &s, const Layout &L) {
 }
 
 // ------------------------------------------------------------------------------------- quotient segments
-// Numerator index space [0, len), len = 8 sigma + 2n - 1 (prover.rs:211-225, multiplied through by X^(5 sigma)):
+// Numerator index space [0, len), len = numerator_len(n) (prover.rs:211-225, multiplied through by X^(5 sigma)):
 //   [0, 3s)            constants at 0,1 and 2s..2s+2, zeros elsewhere          "filler 0"
 //   3s + [0, n)        x2 * witness_u                                          region R2
 //   [3s + n, 5s)       zeros                                                   "filler 1"
@@ -130,12 +143,10 @@ struct Segment {
     uint32_t halo;       // SEG_U: 1 + index k1 of the block whose predecessor value u[start - 1] is needed at `a`, 0 = none
 };
 
-inline uint64_t numerator_len(uint64_t n) { return 8 * (n + 3) + 2 * n - 1; }
-
 // all segments of rank `q` in increasing index order
 inline std::vector<Segment> quotient_segments(uint64_t n, uint32_t N, uint32_t q, uint64_t max_seg) {
     const Layout L = make_layout(n, N, q);
-    const uint64_t s = n + 3, len = numerator_len(n);
+    const uint64_t s = n + 3;
     std::vector<Segment> out;
     auto push_split = [&](uint64_t a, uint64_t b, uint32_t kind, uint64_t loc0, uint32_t halo) {
         for (uint64_t x = a; x < b; x += max_seg) {
@@ -165,7 +176,6 @@ inline std::vector<Segment> quotient_segments(uint64_t n, uint32_t N, uint32_t q
     filler(5 * s + n + 1, 8 * s);
     blocks(8 * s, SEG_U2LO, n, false);
     blocks(8 * s + n, SEG_U2HI, n - 1, false);
-    (void)len;
     uint64_t off = 0;
     for (auto &g : out) {
         g.qoff = off;

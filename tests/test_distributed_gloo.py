@@ -23,7 +23,7 @@ for curve, nq in (("bls12_381", 6), ("bn254", 4)):
     n = 257
     bases, sc = CO.g1_multiples(curve, n), rand_fr_limbs(curve, n, 5)
     whole, winf = CO.msm(curve, bases, sc, 1)
-    lo, hi = n * rank // world, n * (rank + 1) // world          # the shard rule of pm_pk_* (res_lo / res_hi)
+    lo, hi = n * rank // world, n * (rank + 1) // world          # the shard rule of pm_pk_* (key_plan.hpp: PM_SHARD_PAIRS)
     part, pinf = CO.msm(curve, bases[lo:hi], sc[lo:hi], 1)
     comb = PointCombiner(None, curve, nq, rank, world, backend_gloo=True)
     got, ginf = comb(part, pinf)
