@@ -318,15 +318,35 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  *                                                k <= bitlength(r) - 1 (254 on BLS12-381's Fr, 253 on BN254's: the solution is then unique).
  *                                                ONE step for all k columns: t = the ordinary formula of that matrix with the k entries left
  *                                                out and coef = c; z_{u_i} = bit i of the canonical integer of t, as field 0 or field 1
- *     anything else                           -- two or more unknowns that are no decomposition, or one unknown in two of the three in any
+ *     an is-zero pair                         -- the two rows every equality test compiles to, with two fresh unknowns m (the multiplier)
+ *                                                and b (the flag):  arkworks  (a - b) mult = neq ; (a - b) (1 - neq) = 0
+ *                                                                   circom    (-in) inv = out - 1 ; in out = 0
+ *                                                The opener r1 has exactly these two unknowns, each once: one of A_r1, B_r1 is the known side
+ *                                                K1 (no unknown, not zero), the other has (cm, m) as its only non-zero entry, C_r1 names b with
+ *                                                coefficient cb beside any known rest.  The closer r2 is the FIRST later row that names m or b:
+ *                                                it names b and not m, b is its only unknown, in exactly one of A_r2, B_r2 (coefficient kb
+ *                                                beside any known rest) and not in C_r2, and the other of A_r2, B_r2 is K2 = K1 or -K1: the
+ *                                                same non-zero (column, coefficient) entries in any stored order, or every one negated.  Any
+ *                                                number of openers may be open at once.  ONE step for both columns, with d = K1 z:
+ *                                                  d != 0:  b = ((C_r2 z) / (K2 z) - rest_r2) / kb,  m = ((C_r1 z, with b) / d) / cm
+ *                                                  d == 0:  b = -C_r1_rest / cb,  m = 0
+ *                                                Where d == 0 every m satisfies both rows; the library fixes m = 0 (circom's convention, and
+ *                                                what d^(r-2) gives).  A caller that wants another value (arkworks' witness generation
+ *                                                writes 1) supplies m itself: only b is unknown then and r1 is an ordinary row.  The step
+ *                                                never leaves an assignment stuck; if d == 0 and C_r2 z != 0 the closer is a failing row like
+ *                                                any other (the check reports it, the prover returns PM_ERR_REMAINDER_NONZERO)
+ *     anything else                           -- two or more unknowns that are no decomposition and no opener, an opener whose closer is
+ *                                                missing or has another shape (the opener's row is named), or one unknown in two of the three in any
  *                                                other shape (u u = ..., a constant other than minus the coefficient, a non-empty C, further
  *                                                entries): unsolvable
  *   A boolean-pending column that is the single unknown of a later ordinary row is solved by that row; its booleanity row is then a
  *   constraint like any other, which the check reports if the value is not 0 or 1.  One that is still pending when the rows end is
  *   unsolvable: its booleanity row (the smallest such row) and column are named.  Booleanity rows that come AFTER the decomposition row
  *   are not looked for: that decomposition row is refused.  XOR, AND, rotations and recompositions are ordinary one-unknown rows, so
- *   range checks, comparisons, modular additions and ARX hashes complete.  Not solved: the is-zero / inverse-or-zero gadget (its value
- *   is not unique), bits spread over two matrices, signed or non-binary digits.
+ *   range checks, comparisons, modular additions and ARX hashes complete, and with the is-zero pair so do equality tests, selection on
+ *   equality, table membership and data-dependent branches.  Not solved: a closer before its opener or separated from it by rows that
+ *   name the pair, K2 = lambda K1 for other lambda, a known rest beside m in the opener, bits spread over two matrices, signed or
+ *   non-binary digits.
  *   PM_ERR_INVALID_ARG, pm_last_error naming the row or column, nothing computed and no output written: an unsolvable row, a marked
  *   column that no row determines, a marker at column 0, a sharded key, and -- in a batch -- an assignment that does not mark the
  *   columns assignment 0 marks (the first differing (assignment, column) is named; a kernel compares them).

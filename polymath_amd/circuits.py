@@ -1,7 +1,8 @@
 """Workload generators: the reference's harness circuits as ConstraintSynthesizer-shaped classes
 (tests/dummy.rs:20-35, tests/mimc.rs:74-143, benches/bench.rs:38-61) and the synthetic
 "random A*B=C gates" R1CS BASELINE.json quotes the headline metric on, and two boolean circuits of this project's
-own (RangeCheck, ArxDemo) whose witnesses the device completes from the inputs (PM_ASSIGNMENT_SOLVE)."""
+own (RangeCheck, ArxDemo) and two that branch on equality (MatchCount, EqChain: is-zero pairs in arkworks' and in circom's form) whose
+witnesses the device completes from the inputs (PM_ASSIGNMENT_SOLVE)."""
 from .polymath import ConstraintSystem, Field, LimbCircuit, R1CS
 
 SPLITMIX_SEED = 0x706F6C796D617468  # "polymath"
@@ -198,6 +199,130 @@ def arx_native(a, b, width, rounds, rot):
         s = a + b
         a, b = (s & mask) ^ _rotr(b, rot, width), s & mask
     return a
+
+
+def _lc_value(cs, lc):
+    value = {"one": lambda i: 1, "inst": lambda i: cs.instance[i], "wit": lambda i: cs.witness[i]}
+    return sum(coef * value[kind](idx) for coef, (kind, idx) in lc) % cs.r
+
+
+def _merged(lc):
+    """the linear combination with one entry per variable (the matrices keep the FIRST entry of a column that a row names twice)"""
+    total = {}
+    for coef, var in lc:
+        total[var] = total.get(var, 0) + coef
+    return [(coef, var) for var, coef in total.items()]
+
+
+def _new_is_zero(cs, lc, form, free=0):
+    """The is-zero / inverse-or-zero pair on the linear combination `lc` (value d): two fresh witnesses, the flag first and then the
+    multiplier m, and two rows, the opener and the closer of DESIGN.md §4.10.
+        "ark"     (is_neq of arkworks' FpVar): the flag is neq = [d != 0], a Boolean::new_witness with its booleanity row first;
+                  lc * m = neq ;  lc * (1 - neq) = 0
+        "circom"  (circomlib's IsZero): the flag is out = [d == 0];
+                  (-lc) * m = out - 1 ;  lc * out = 0
+    m = 1 / d where d != 0; where d == 0 every m satisfies both rows and `free` is written: 0 is what the device computes (circom's
+    convention, and what 0^(r-2) gives), 1 is what arkworks' witness generation writes.
+    -> (eq, flag, m): eq = the linear combination that is [d == 0], the two variables."""
+    one, r = ConstraintSystem.ONE, cs.r
+    d = _lc_value(cs, lc)
+    m_v = pow(d, r - 2, r) if d else free
+    if form == "ark":
+        flag = _new_boolean(cs, int(d != 0))
+        m = cs.new_witness_variable(m_v)
+        cs.enforce_constraint(lc, [(1, m)], [(1, flag)])
+        cs.enforce_constraint(lc, [(1, one), (-1, flag)], [])
+        return [(1, one), (-1, flag)], flag, m
+    if form == "circom":
+        flag = cs.new_witness_variable(int(d == 0))
+        m = cs.new_witness_variable(m_v)
+        cs.enforce_constraint([(-coef, v) for coef, v in lc], [(1, m)], [(1, flag), (-1, one)])
+        cs.enforce_constraint(lc, [(1, flag)], [])
+        return [(1, flag)], flag, m
+    raise ValueError("form is 'ark' or 'circom'")
+
+
+class _PartialPairs(_Partial):
+    """_Partial for circuits with is-zero pairs: partial(r, multipliers=True) gives the multipliers as well (the value generate_constraints
+    wrote: 1 / d, or `free` where d == 0), so that only the flags are unknown and every opener is an ordinary kind-C step -- the way
+    to get a free multiplier other than the device's 0."""
+
+    def _pair(self, cs, lc):
+        eq, _, m = _new_is_zero(cs, lc, self.form, self.free)
+        self._multipliers.append(m[1])
+        return eq
+
+    def partial(self, r, multipliers=False):
+        instance, witness = super().partial(r)
+        if multipliers:
+            cs = ConstraintSystem(r)
+            self.generate_constraints(cs)
+            for j in self._multipliers:
+                witness[j] = cs.witness[j]
+        return instance, witness
+
+    def native(self, r):
+        """-> (instance, witness) as the rows define them, on Python integers"""
+        cs = ConstraintSystem(r)
+        self.generate_constraints(cs)
+        return list(cs.instance), list(cs.witness)
+
+
+class MatchCount(_PartialPairs):
+    """How many of `values` equal `key`: per value one is-zero pair on v_i - key, then  (sum e_i) * 1 = count  with e_i = [v_i == key]
+    and count the public input.  ONE dependency level of len(values) pairs, then one ordinary step.  Witness layout: key, then per
+    value v_i, its flag, its multiplier.  The caller chooses key and the values."""
+
+    def __init__(self, values, key, form, free=0):
+        self.values, self.key, self.form, self.free = list(values), key, form, free
+
+    def generate_constraints(self, cs):
+        self._chosen, self._multipliers = [], []
+        one = ConstraintSystem.ONE
+        key = self._given(cs, self.key)
+        total = []
+        for value in self.values:
+            v = self._given(cs, value)
+            total += self._pair(cs, [(1, v), (-1, key)])
+        count = cs.new_input_variable(sum(int((v - self.key) % cs.r == 0) for v in self.values))
+        cs.enforce_constraint(_merged(total), [(1, one)], [(1, count)])
+
+
+class EqChain(_PartialPairs):
+    """A recurrence that branches on equality:  e_i = [s_i == t_i],  s_{i+1} = s_i + 1 + e_i t_i,  s_0 = x.  Per step the witness
+    t_i, one is-zero pair on s_i - t_i and the row  e_i * t_i = s_{i+1} - s_i - 1 ; step i's tested value depends on step i - 1's
+    flag, so the dependency structure is len(targets) pairs deep and one wide.  With bits > 0 every new state is also range-checked:
+    `bits` boolean witnesses and  s_{i+1} * 1 = sum 2^j b_j  (the states must stay below 2^bits).  The last state is the public input.
+    The caller chooses x and the targets; eq_chain_targets makes targets that hit and miss where wanted."""
+
+    def __init__(self, x, targets, form, free=0, bits=0):
+        self.x, self.targets, self.form, self.free, self.bits = x, list(targets), form, free, bits
+
+    def generate_constraints(self, cs):
+        self._chosen, self._multipliers = [], []
+        one, r = ConstraintSystem.ONE, cs.r
+        s_v = self.x % r
+        s = self._given(cs, s_v)
+        for i, t_v in enumerate(self.targets):
+            t = self._given(cs, t_v)
+            eq = self._pair(cs, [(1, s), (-1, t)])
+            next_v = (s_v + 1 + (t_v if (s_v - t_v) % r == 0 else 0)) % r
+            nxt = cs.new_input_variable(next_v) if i == len(self.targets) - 1 else cs.new_witness_variable(next_v)
+            cs.enforce_constraint(eq, [(1, t)], [(1, nxt), (-1, s), (-1, one)])
+            if self.bits:
+                assert next_v < 1 << self.bits
+                cs.enforce_constraint([(1, nxt)], [(1, one)], _weighted(_new_bits(cs, next_v, self.bits)))
+            s, s_v = nxt, next_v
+
+
+def eq_chain_targets(x, hits, r, miss=5):
+    """targets for EqChain(x, ...) such that step i finds equality exactly where hits[i]: the state itself, or the state + miss"""
+    targets, s = [], x % r
+    for hit in hits:
+        t = s if hit else (s + miss) % r
+        targets.append(t)
+        s = (s + 1 + (t if hit else 0)) % r
+    return targets
 
 
 def synthetic_r1cs(r, nr, seed=SPLITMIX_SEED):

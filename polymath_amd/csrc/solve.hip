@@ -4,19 +4,23 @@
 // pattern) by host/solve_plan.hpp; the arithmetic is the kernels below, assignment = grid y (or the lane, in the chain kernel):
 //   k_solve_pattern   one lane per (column, assignment): the unknown pattern of assignment 0; every other assignment is compared
 //                     with it and the first differing (assignment, column) lowers one word
-//   k_solve_inv       one lane per step, once per plan: 1 / coefficient of the step's unknown
+//   k_solve_inv       one lane per step, once per plan: 1 / coefficient of the step's unknown; two more lanes per is-zero pair:
+//                     1 / cm and 1 / cb of its opener
 //   k_solve_level     a WIDE dependency level: one lane per (step, assignment); a level is its own launch, so stream order is
 //                     the dependency order
 //   k_solve_bits      the bit decompositions of a wide level, one lane per (step, assignment) as well: a launch of their own, so
 //                     that lanes doing one store do not sit beside lanes doing k
+//   k_solve_iszero    the is-zero pairs of a wide level, one lane per (step, assignment) as well: two stores and one inversion each
 //   k_solve_chain     a run of consecutive NARROW levels: one lane per assignment walks the run's steps in plan order.  A lane
 //                     reads back only its own stores: no barriers, no fences.  The MiMC shape (depth 644, width 1) is one such run
 //                     and the batch is its parallel dimension.
 // The solving kernels exist twice: DIV = false for ranges of kind-C steps only, DIV = true for ranges with kind-A / kind-B steps,
-// which call inverse<P> (a Fermat chain) -- the plan sorts a level by kind, so kind-C ranges do not carry its registers.
+// or is-zero pairs, which call inverse<P> (a Fermat chain) -- the plan sorts a level by kind, so kind-C ranges do not carry its
+// registers, and the is-zero step exists in the DIV = true chain only.
 // A step that would divide by zero stores zero and lowers the assignment's stuck word to its row (64-bit atomic minimum: the same
 // word on every run); so does a decomposition whose value has no k-bit form, in all its k columns.  Every other store has one
-// writer.  Plain C++ and vector stores only.
+// writer.  An is-zero pair never sticks: where the tested value is zero its multiplier is free and is stored as zero.  Plain C++ and
+// vector stores only.
 #include <cstring>
 #include <vector>
 
@@ -30,8 +34,19 @@ constexpr uint64_t SOLVE_NONE = ~(uint64_t)0;   // no stuck row / no mismatch / 
 template <class P>
 struct SolveStepDev {
     uint64_t pos;                    // the unknown's entry in its matrix; a decomposition: the entry that holds c
-    uint32_t row, col, kind, bits;   // bits != 0: a decomposition into the columns bit_cols[col .. col + bits), exponent order
+    uint32_t row, col, kind, bits;   // bits != 0: a decomposition into the columns bit_cols[col .. col + bits), exponent order;
+                                     // kind == KIND_ISZERO: row = the closer, pos / col = the flag's entry in it, bits = its SolvePairDev
     Fp<P> inv;                       // 1 / coefficient (k_solve_inv)
+};
+
+// what an is-zero step needs beside its SolveStepDev: the opener row r1
+template <class P>
+struct SolvePairDev {
+    uint64_t pos_m, pos_c;           // (cm, m) in A_r1 or B_r1; (cb, b) in C_r1
+    uint32_t row1, col_m;
+    uint32_t m_in_b, b_in_b;         // K1 = A_r1 (the multiplier lies in B_r1) / K2 = A_r2 (the flag lies in B_r2); 0: the B sides
+    uint32_t negated, pad;           // K2 = -K1
+    Fp<P> inv_cm, inv_cb;            // k_solve_inv
 };
 
 template <class P>
@@ -66,11 +81,24 @@ __device__ __forceinline__ const CsrDev &matrix_of(uint32_t kind, const CsrDev &
 __device__ __forceinline__ uint32_t matrix_kind(uint32_t kind) { return kind >= pmsolve::KIND_BITS_C ? kind - pmsolve::KIND_BITS_C : kind; }
 
 template <class P>
-__global__ __launch_bounds__(256) void k_solve_inv(CsrDev A, CsrDev B, CsrDev Cm, SolveStepDev<P> *steps, uint64_t count) {
+__global__ __launch_bounds__(256) void k_solve_inv(CsrDev A, CsrDev B, CsrDev Cm, SolveStepDev<P> *steps, uint64_t count, SolvePairDev<P> *pairs, uint64_t n_pairs) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    const Fp<P> coef = *(const Fp<P> *)(matrix_of(matrix_kind(steps[t].kind), A, B, Cm).val + 4 * steps[t].pos);
-    steps[t].inv = coef.eq(Fp<P>::one()) ? coef : inverse<P>(coef);
+    if (t >= count + 2 * n_pairs) return;
+    const Fp<P> *at;
+    Fp<P> *out;
+    if (t < count) {                 // an is-zero step's own entry is the flag's, in the closer's A or B
+        const uint32_t kind = steps[t].kind;
+        const CsrDev &M = kind == pmsolve::KIND_ISZERO ? (pairs[steps[t].bits].b_in_b ? B : A) : matrix_of(matrix_kind(kind), A, B, Cm);
+        at = (const Fp<P> *)(M.val + 4 * steps[t].pos);
+        out = &steps[t].inv;
+    } else {
+        SolvePairDev<P> &pr = pairs[(t - count) >> 1];
+        const bool multiplier = ((t - count) & 1) == 0;
+        at = (const Fp<P> *)(multiplier ? (pr.m_in_b ? B : A).val + 4 * pr.pos_m : Cm.val + 4 * pr.pos_c);
+        out = multiplier ? &pr.inv_cm : &pr.inv_cb;
+    }
+    const Fp<P> coef = *at;
+    *out = coef.eq(Fp<P>::one()) ? coef : inverse<P>(coef);
 }
 
 // (M z)_r without entry `skip` (SOLVE_NONE: the whole row)
@@ -170,6 +198,29 @@ __device__ __forceinline__ void solve_bits(const CsrDev &A, const CsrDev &B, con
     }
 }
 
+// one is-zero pair on one assignment.  d1 = K1 z is the tested value up to sign, d2 = K2 z = +-d1 by the plan, so ONE inversion
+// serves both rows; inverse<P>(0) is 0 (a power of zero), which is the convention for the free multiplier, so m needs no branch and
+// only b is a select:
+//   d1 != 0:  b = ((C_r2 z) / d2 - rest_r2) / kb,   m = ((C_r1 z, with b) / d1) / cm
+//   d1 == 0:  b = -C_r1_rest / cb,                  m = 0
+// Both columns still hold the marker; the dot products leave their entries out by position.
+template <class P>
+__device__ __forceinline__ void solve_iszero(const CsrDev &A, const CsrDev &B, const CsrDev &Cm, const SolveStepDev<P> &s, const SolvePairDev<P> &pr, Fp<P> *z) {
+    const uint64_t r1 = pr.row1, r2 = s.row;
+    const Fp<P> d1 = row_dot_skip<P>(pr.m_in_b ? A : B, z, r1, SOLVE_NONE);
+    const Fp<P> c1_rest = row_dot_skip<P>(Cm, z, r1, pr.pos_c);
+    const Fp<P> rest2 = row_dot_skip<P>(pr.b_in_b ? B : A, z, r2, s.pos);
+    const Fp<P> c2 = row_dot_skip<P>(Cm, z, r2, SOLVE_NONE);
+    const Fp<P> inv1 = inverse<P>(d1);
+    const Fp<P> inv2 = pr.negated ? neg<P>(inv1) : inv1;
+    const Fp<P> b_unequal = mul<P>(sub<P>(mul<P>(c2, inv2), rest2), s.inv);
+    const Fp<P> b_equal = mul<P>(neg<P>(c1_rest), pr.inv_cb);
+    const Fp<P> b = d1.is_zero() ? b_equal : b_unequal;
+    const Fp<P> c1 = add<P>(c1_rest, mul<P>(*(const Fp<P> *)(Cm.val + 4 * pr.pos_c), b));
+    z[s.col] = b;
+    z[pr.col_m] = mul<P>(mul<P>(c1, inv1), pr.inv_cm);
+}
+
 template <class P, bool DIV>
 __global__ __launch_bounds__(256) void k_solve_level(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, uint32_t lo, uint32_t hi,
                                                      Fp<P> *xw, uint64_t ncols, unsigned long long *stuck) {
@@ -186,15 +237,28 @@ __global__ __launch_bounds__(256) void k_solve_bits(CsrDev A, CsrDev B, CsrDev C
     solve_bits<P, DIV>(A, B, Cm, steps[t], bit_cols, xw + b * ncols, stuck + b);
 }
 
-// the step index is the same in every lane: the step record, the row's CSR metadata and a decomposition's column list are uniform loads
+template <class P>
+__global__ __launch_bounds__(256) void k_solve_iszero(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, const SolvePairDev<P> *__restrict__ pairs,
+                                                      uint32_t lo, uint32_t hi, Fp<P> *xw, uint64_t ncols) {
+    const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (t >= hi) return;
+    solve_iszero<P>(A, B, Cm, steps[t], pairs[steps[t].bits], xw + b * ncols);
+}
+
+// the step index is the same in every lane: the step record, the pair record, the row's CSR metadata and a decomposition's column
+// list are uniform loads.  A range with an is-zero pair is a dividing one (the plan says so): the DIV = false body has no such branch.
 template <class P, bool DIV>
 __global__ __launch_bounds__(64) void k_solve_chain(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, const uint32_t *__restrict__ bit_cols,
-                                                    uint32_t lo, uint32_t hi, Fp<P> *xw, uint64_t ncols, unsigned long long *stuck, uint64_t rows) {
+                                                    const SolvePairDev<P> *__restrict__ pairs, uint32_t lo, uint32_t hi, Fp<P> *xw, uint64_t ncols,
+                                                    unsigned long long *stuck, uint64_t rows) {
     const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= rows) return;
     Fp<P> *z = xw + b * ncols;
     for (uint32_t t = lo; t < hi; ++t) {
-        if (steps[t].bits) solve_bits<P, DIV>(A, B, Cm, steps[t], bit_cols, z, stuck + b);
+        if (steps[t].kind == pmsolve::KIND_ISZERO) {
+            // DIV = false would pass over the pair and leave both markers in place: solve_plan refuses a plan that asks for that
+            if constexpr (DIV) solve_iszero<P>(A, B, Cm, steps[t], pairs[steps[t].bits], z);
+        } else if (steps[t].bits) solve_bits<P, DIV>(A, B, Cm, steps[t], bit_cols, z, stuck + b);
         else solve_step<P, DIV>(A, B, Cm, steps[t], z, stuck + b);
     }
 }
@@ -284,13 +348,35 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
         ctx->err = "pm solve: " + sv.plan.message;
         return PM_ERR_INVALID_ARG;
     }
+    // the DIV = false kernels have no is-zero step in them: a range with a pair must be a dividing one
+    for (const pmsolve::Launch &l : sv.plan.launches)
+        for (uint32_t t = l.lo; t < l.hi && !l.divides; ++t)
+            if (sv.plan.steps[t].kind == pmsolve::KIND_ISZERO) {
+                ctx->err = "pm solve: the plan puts the is-zero pair of row " + std::to_string(sv.plan.steps[t].row) + " into a launch that does not divide";
+                return PM_ERR_STATE;
+            }
     const size_t n_steps = sv.plan.steps.size();
+    sv.n_pairs = 0;
     if (n_steps) {
         std::vector<SolveStepDev<P>> host(n_steps);
+        std::vector<SolvePairDev<P>> host_pairs;
         memset((void *)host.data(), 0, n_steps * sizeof(SolveStepDev<P>));
         for (size_t t = 0; t < n_steps; ++t) {
             const pmsolve::Step &s = sv.plan.steps[t];
             host[t].pos = s.pos; host[t].row = s.row; host[t].col = s.bits ? s.cols_off : s.col; host[t].kind = s.kind; host[t].bits = s.bits;
+            if (s.kind != pmsolve::KIND_ISZERO) continue;
+            host[t].bits = (uint32_t)host_pairs.size();
+            SolvePairDev<P> pr;
+            memset((void *)&pr, 0, sizeof pr);
+            const pmsolve::PairRows &rows = sv.plan.pairs[s.cols_off];
+            pr.pos_m = rows.pos_m; pr.pos_c = rows.pos_c; pr.row1 = rows.row1; pr.col_m = rows.col_m; pr.m_in_b = rows.m_in_b; pr.b_in_b = rows.b_in_b;
+            pr.negated = rows.negated;
+            host_pairs.push_back(pr);
+        }
+        sv.n_pairs = host_pairs.size();
+        if (sv.n_pairs) {
+            PM_HIP(ctx, sv.pairs.reserve(sv.n_pairs * sizeof(SolvePairDev<P>)));
+            PM_HIP(ctx, hipMemcpyAsync(sv.pairs.p, host_pairs.data(), sv.n_pairs * sizeof(SolvePairDev<P>), hipMemcpyHostToDevice, st));
         }
         const std::vector<uint32_t> &bit_cols = sv.plan.bit_cols;
         if (!bit_cols.empty()) {
@@ -299,9 +385,9 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
         }
         PM_HIP(ctx, sv.steps.reserve(n_steps * sizeof(SolveStepDev<P>)));
         PM_HIP(ctx, hipMemcpyAsync(sv.steps.p, host.data(), n_steps * sizeof(SolveStepDev<P>), hipMemcpyHostToDevice, st));
-        PM_LAUNCH(ctx, k_solve_inv<P>, dim3(nblk(n_steps)), dim3(256), 0, st, csr_dev(pk, 0), csr_dev(pk, 1), csr_dev(pk, 2), sv.steps.as<SolveStepDev<P>>(),
-                       (uint64_t)n_steps);
-        PM_HIP(ctx, hipStreamSynchronize(st));   // `host` goes out of scope
+        PM_LAUNCH(ctx, k_solve_inv<P>, dim3(nblk(n_steps + 2 * sv.n_pairs)), dim3(256), 0, st, csr_dev(pk, 0), csr_dev(pk, 1), csr_dev(pk, 2),
+                       sv.steps.as<SolveStepDev<P>>(), (uint64_t)n_steps, sv.n_pairs ? sv.pairs.as<SolvePairDev<P>>() : nullptr, (uint64_t)sv.n_pairs);
+        PM_HIP(ctx, hipStreamSynchronize(st));   // `host` and `host_pairs` go out of scope
     }
     sv.plan_pattern.swap(pattern);
     sv.plan_key = pk->serial;
@@ -323,16 +409,18 @@ int solve_group(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t 
     const CsrDev A = csr_dev(pk, 0), B = csr_dev(pk, 1), Cm = csr_dev(pk, 2);
     const SolveStepDev<P> *steps = sv.steps.as<SolveStepDev<P>>();
     const uint32_t *bit_cols = sv.plan.bit_cols.empty() ? nullptr : sv.bit_cols.as<uint32_t>();
+    const SolvePairDev<P> *pairs = sv.n_pairs ? sv.pairs.as<SolvePairDev<P>>() : nullptr;
     {
         StageTimer t(ctx, timing_slot);
         for (const pmsolve::Launch &l : sv.plan.launches) {
             if (l.chain) {
                 const dim3 grid(nblk(g, 64)), block(64);
-                if (l.divides) hipLaunchKernelGGL((k_solve_chain<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
-                else hipLaunchKernelGGL((k_solve_chain<P, false>), grid, block, 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
+                if (l.divides) hipLaunchKernelGGL((k_solve_chain<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, pairs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
+                else hipLaunchKernelGGL((k_solve_chain<P, false>), grid, block, 0, st, A, B, Cm, steps, bit_cols, pairs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
             } else {
                 const dim3 grid(nblk(l.hi - l.lo), (unsigned)g), block(256);
-                if (l.bits && l.divides) hipLaunchKernelGGL((k_solve_bits<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck);
+                if (l.iszero) hipLaunchKernelGGL((k_solve_iszero<P>), grid, block, 0, st, A, B, Cm, steps, pairs, l.lo, l.hi, d_xw, ncols);
+                else if (l.bits && l.divides) hipLaunchKernelGGL((k_solve_bits<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck);
                 else if (l.bits) hipLaunchKernelGGL((k_solve_bits<P, false>), grid, block, 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck);
                 else if (l.divides) hipLaunchKernelGGL((k_solve_level<P, true>), grid, block, 0, st, A, B, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck);
                 else hipLaunchKernelGGL((k_solve_level<P, false>), grid, block, 0, st, A, B, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck);

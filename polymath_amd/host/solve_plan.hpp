@@ -1,6 +1,6 @@
 // Witness solving, host side: the PLAN that completes a partial assignment by forward propagation through the rows of an R1CS
-// (DESIGN.md §4.10).  Header-only, no HIP: the library's driver (csrc/solve.hip) and two CPU programs (tests/native/
-// solve_plan_selftest.cpp, solve_bits_selftest.cpp) include the same file.
+// (DESIGN.md §4.10).  Header-only, no HIP: the library's driver (csrc/solve.hip) and three CPU programs (tests/native/
+// solve_plan_selftest.cpp, solve_bits_selftest.cpp, solve_iszero_selftest.cpp) include the same file.
 //
 // Input: the three matrices in CSR form with the first-entry rule already applied (a column occurs at most once per row and
 // matrix: the key's resident matrices are like that), m0 + mw columns and one byte per column, non-zero = unknown.  A stored entry
@@ -25,23 +25,42 @@
 //                 Booleanity rows that come AFTER the decomposition row are not looked for: that decomposition row is refused.
 // A boolean-pending column that is the single unknown of a later ordinary row is solved by it.  One still pending at the end of the
 // pass is ERR_TWO_MATRICES naming its booleanity row (the smallest such row), before ERR_UNDETERMINED is looked for.
-// Without the modulus (nullptr) both additions are off.
+//   is-zero pair  two rows with two fresh unknowns m (the multiplier) and b (the flag), the shape every equality test compiles to:
+//                 arkworks  (a - b) mult = neq ; (a - b) (1 - neq) = 0     circom IsZero  (-in) inv = out - 1 ; in out = 0
+//                 OPENER r1: exactly two distinct unknowns, each named once.  One of A_r1, B_r1 is the known side K1 (no unknown, at
+//                 least one non-zero entry), the other has (cm, m) as its only non-zero entry; C_r1 names b with coefficient cb
+//                 beside any known rest.  Both columns become PAIR-PENDING and the row is otherwise skipped; any number of openers
+//                 may be pending.  CLOSER r2: the first later row that names m or b.  It names b and not m, b is its only unknown,
+//                 in exactly one of A_r2, B_r2 (coefficient kb beside any known rest) and not in C_r2; the other of A_r2, B_r2 is
+//                 K2 = K1 or -K1 as a linear combination: the same non-zero (column, coefficient) entries in any stored order, or
+//                 every coefficient negated (a + a' = 0 by add_mod: no field multiplication here).  The pair is ONE step of kind
+//                 KIND_ISZERO at row r2 that determines both columns; with d = K1 z:
+//                     d != 0:  b = ((C_r2 z) / (K2 z) - rest_r2) / kb,  m = ((C_r1 z, with b) / d) / cm
+//                     d == 0:  b = -C_r1_rest / cb,                     m = 0      (m is free then: circom's convention, and 0^(r-2))
+//                 The step never sticks.  A caller that wants another m supplies it: only b is unknown then and r1 is an ordinary
+//                 kind-C step.  Step::pos / col name b's entry in the closer, Plan::pairs[cols_off] carries the rest (a side list, as
+//                 bit_cols is: the step record of the other kinds is what it was).  A two-unknown row that is no opener is refused at once, as before; a pair that does not close is
+//                 ERR_MANY_UNKNOWNS at r1 with the message the row has without the modulus, then what failed.  Openers pending
+//                 when the rows end are reported first, smallest r1 first.
+// Without the modulus (nullptr) all three additions are off.
 //
 // level(step) = 1 + max level of the columns the row reads (given columns: level 0); a decomposition gives all its columns that
 // level.  The steps come out sorted by level, inside a level by kind (C first: the kinds that divide share a launch; then the
-// decompositions in the same order), stable by row -- one counting sort.  O(nnz + columns), plus k log k per decomposition.
+// decompositions in the same order, then the is-zero pairs), stable by row -- one counting sort.  O(nnz + columns), plus k log k per decomposition.
 #pragma once
 #include <stdint.h>
 
 #include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace pmsolve {
 
 // z_u = (Az Bz - C_rest) / coef;  (Cz / Bz - A_rest) / coef;  (Cz / Az - B_rest) / coef;  KIND_BITS_x = KIND_BITS_C + x: a decomposition
-enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5 };
-constexpr uint32_t NUM_KINDS = 6;
+// KIND_ISZERO: an is-zero pair, both columns in one step
+enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6 };
+constexpr uint32_t NUM_KINDS = 7;
 
 constexpr uint32_t WIDE_STEPS = 32;   // a level of at least this many steps gets launches of its own; narrower ones are walked by one lane per assignment
 
@@ -55,13 +74,23 @@ struct Step {
     uint64_t pos;     // index of the unknown's entry in its matrix (col / val arrays); a decomposition: of the entry that holds c
     uint32_t row, col, kind, level;
     uint32_t bits = 0, cols_off = 0;   // a decomposition: Plan::bit_cols[cols_off .. cols_off + bits), exponent order; bits = 0 otherwise
+                                       // an is-zero pair: row = the closer, pos / col = the flag's entry in it, Plan::pairs[cols_off]
+};
+
+struct PairRows {     // what an is-zero step needs beside its Step
+    uint64_t pos_m, pos_c;   // the multiplier's entry in A_r1 or B_r1; the flag's entry in C_r1
+    uint32_t row1, col_m;    // the opener; the multiplier's column
+    uint8_t m_in_b;          // 1: the multiplier lies in B_r1 and K1 = A_r1; 0: the other way round
+    uint8_t b_in_b;          // 1: the flag lies in B_r2 and K2 = A_r2
+    uint8_t negated;         // 1: K2 = -K1
 };
 
 struct Launch {
     uint32_t lo, hi;  // steps [lo, hi) of the sorted list
     uint8_t chain;    // 1: one lane per assignment walks the steps in order; 0: one lane per (step, assignment), all of one level
-    uint8_t divides;  // 1: some step of the range is KIND_A / KIND_B / KIND_BITS_A / KIND_BITS_B
+    uint8_t divides;  // 1: some step of the range is KIND_A / KIND_B / KIND_BITS_A / KIND_BITS_B / KIND_ISZERO
     uint8_t bits = 0; // chain == 0 only.  1: every step of the range is a decomposition; 0: none is
+    uint8_t iszero = 0;  // chain == 0 only.  1: every step of the range is an is-zero pair; 0: none is
 };
 
 enum Error : int { OK = 0, ERR_MANY_UNKNOWNS = 1, ERR_TWO_MATRICES = 2, ERR_UNDETERMINED = 3, ERR_COLUMN_ZERO = 4 };
@@ -71,6 +100,7 @@ struct Plan {
     std::vector<uint32_t> level_ptr;  // level l (1-based) = steps [level_ptr[l - 1], level_ptr[l])
     std::vector<Launch> launches;
     std::vector<uint32_t> bit_cols;   // the decompositions' columns
+    std::vector<PairRows> pairs;      // the is-zero pairs' openers, in order of discovery
     int error = OK;
     uint64_t error_row = 0, error_col = 0;
     std::string message;              // empty when error == OK
@@ -168,6 +198,37 @@ inline const char *decomposition_order(const Csr m[3], const std::vector<Unknown
     return order.size() == k ? nullptr : "the coefficients are not c 2^0 ... c 2^(k-1)";
 }
 
+struct Opener {   // an is-zero opener whose closer has not come yet
+    uint64_t pos_m, pos_c;
+    uint32_t row, col_m, col_b, reads;   // reads: the largest level among the columns the row reads
+    uint8_t m_in_b;
+};
+
+// K2 (matrix k2, row r2) against K1 (matrix k1, row r1) as linear combinations: 0 equal, 1 every coefficient negated, -1 neither.
+// Neither side names an unknown; zero coefficients name nothing.  `a`, `b`: scratch.
+inline int compare_known_sides(const Csr m[3], int k1, uint64_t r1, int k2, uint64_t r2, const uint64_t *modulus, std::vector<std::pair<uint32_t, uint64_t>> &a,
+                               std::vector<std::pair<uint32_t, uint64_t>> &b) {
+    const auto gather = [&](int k, uint64_t r, std::vector<std::pair<uint32_t, uint64_t>> &out) {
+        out.clear();
+        for (uint64_t e = m[k].rowptr[r]; e < m[k].rowptr[r + 1]; ++e)
+            if (!coef_is_zero(m[k].val + 4 * e)) out.push_back({m[k].col[e], e});
+        std::sort(out.begin(), out.end());
+    };
+    gather(k1, r1, a);
+    gather(k2, r2, b);
+    if (a.size() != b.size()) return -1;
+    bool same = true, negated = true;
+    for (size_t i = 0; i < a.size(); ++i) {
+        if (a[i].first != b[i].first) return -1;
+        const uint64_t *va = m[k1].val + 4 * a[i].second, *vb = m[k2].val + 4 * b[i].second;
+        uint64_t sum[4];
+        add_mod(va, vb, modulus, sum);
+        same = same && words_equal(va, vb);
+        negated = negated && coef_is_zero(sum);
+    }
+    return same ? 0 : negated ? 1 : -1;
+}
+
 inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, const uint8_t *unknown, uint32_t wide_steps = WIDE_STEPS,
                        const uint64_t *modulus = nullptr) {
     Plan p;
@@ -183,6 +244,22 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
     std::vector<uint32_t> bool_row(modulus ? ncols : 0, NONE);   // boolean-pending: the column is UNSOLVED and this is its booleanity row
     static const char *const NAME[3] = {"A", "B", "C"};
     static const uint32_t KIND_OF[3] = {KIND_A, KIND_B, KIND_C};
+    std::vector<uint32_t> pair_of(modulus ? ncols : 0, NONE);    // pair-pending: the column is UNSOLVED and this is its entry of `openers`
+    std::vector<Opener> openers;
+    size_t open = 0;                                             // openers not closed yet
+    std::vector<std::pair<uint32_t, uint64_t>> side1, side2;
+    const auto two_unknowns = [](uint64_t r, uint32_t u, uint32_t j) {
+        return "row " + std::to_string(r) + ": two or more unknowns (columns " + std::to_string(u) + " and " + std::to_string(j) + ")";
+    };
+    const auto refuse_pair = [&](const Opener &o, const std::string &why) {
+        p.error = ERR_MANY_UNKNOWNS;
+        p.error_row = o.row;
+        p.error_col = o.col_b;
+        p.message = two_unknowns(o.row, o.col_m, o.col_b) + ", and no is-zero pair: " + why;
+        p.steps.clear();
+        p.bit_cols.clear();
+        p.pairs.clear();
+    };
     uint32_t max_level = 0;
     std::vector<Unknown> occ;
     std::vector<uint32_t> order;
@@ -203,6 +280,48 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
             }
         }
         if (occ.empty()) continue;
+        if (open) {   // the first row that names a pair-pending column closes that pair, or the pair is refused
+            const Opener *o = nullptr;
+            for (const Unknown &e : occ)
+                if (!o && pair_of[e.col] != NONE) o = &openers[pair_of[e.col]];
+            if (o) {
+                const std::string here = "row " + std::to_string(r);
+                const Unknown *flag = nullptr, *multiplier = nullptr, *other = nullptr;
+                bool in_c = false, twice = false, same_matrix = false;
+                for (const Unknown &e : occ) {
+                    if (e.col == o->col_m) multiplier = &e;
+                    else if (e.col != o->col_b) other = other ? other : &e;
+                    else if (e.matrix == 2) in_c = true;
+                    else if (flag) { twice = true; same_matrix = flag->matrix == e.matrix; }
+                    else flag = &e;
+                }
+                const std::string flag_name = " names the flag (column " + std::to_string(o->col_b) + ")";
+                std::string why;
+                if (multiplier) why = here + " names the multiplier (column " + std::to_string(o->col_m) + ")";
+                else if (other) why = here + " has a second unknown (column " + std::to_string(other->col) + ")";
+                else if (in_c) why = here + flag_name + " in C";
+                else if (twice) why = here + flag_name + (same_matrix ? std::string(" twice in ") + NAME[flag->matrix] : std::string(" in A and in B"));
+                int sign = 0;
+                if (why.empty()) {
+                    sign = compare_known_sides(m, o->m_in_b ? 0 : 1, o->row, flag->matrix == 0 ? 1 : 0, r, modulus, side1, side2);
+                    if (sign < 0) why = here + ": its known side is neither the opener's nor minus the opener's";
+                }
+                if (!why.empty()) {
+                    refuse_pair(*o, why);
+                    return p;
+                }
+                const uint32_t lv2 = (reads > o->reads ? reads : o->reads) + 1;
+                Step s{flag->pos, (uint32_t)r, o->col_b, KIND_ISZERO, lv2};
+                s.cols_off = (uint32_t)p.pairs.size();
+                p.pairs.push_back(PairRows{o->pos_m, o->pos_c, o->row, o->col_m, o->m_in_b, (uint8_t)(flag->matrix == 1), (uint8_t)sign});
+                level[o->col_m] = level[o->col_b] = lv2;
+                pair_of[o->col_m] = pair_of[o->col_b] = NONE;
+                --open;
+                if (lv2 > max_level) max_level = lv2;
+                p.steps.push_back(s);
+                continue;
+            }
+        }
         const uint32_t lv = reads + 1;
         if (occ.size() == 1) {
             const uint32_t u = occ[0].col;
@@ -239,18 +358,33 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
                 p.steps.push_back(s);
                 continue;
             }
+            // an is-zero opener: the multiplier alone on one of A, B, the other of the two known and not zero, the flag in C
+            if (!one_column && occ.size() == 2 && occ[0].matrix < 2 && occ[1].matrix == 2 && nz[occ[0].matrix] == 1 && nz[1 - occ[0].matrix] >= 1) {
+                pair_of[u] = pair_of[j] = (uint32_t)openers.size();
+                openers.push_back(Opener{occ[0].pos, occ[1].pos, (uint32_t)r, u, j, reads, (uint8_t)occ[0].matrix});
+                ++open;
+                continue;
+            }
         }
         p.error_row = r;
         p.error_col = j;
         if (j != u) {
             p.error = ERR_MANY_UNKNOWNS;
-            p.message = "row " + std::to_string(r) + ": two or more unknowns (columns " + std::to_string(u) + " and " + std::to_string(j) + ")";
+            p.message = two_unknowns(r, u, j);
             if (why) p.message += std::string(", and no bit decomposition: ") + why;
         } else {   // the same unknown again: in another matrix, or a second time in this one
             p.error = ERR_TWO_MATRICES;
             p.message = "row " + std::to_string(r) + ": unknown column " + std::to_string(j) + " occurs in " + NAME[occ[0].matrix] + " and in " + NAME[occ[1].matrix];
         }
         return p;
+    }
+    if (open) {   // openers are pushed in row order: the first one still pending has the smallest row
+        for (size_t i = 0; i < openers.size(); ++i)
+            if (pair_of[openers[i].col_m] == i) {
+                const Opener &o = openers[i];
+                refuse_pair(o, "no later row closes it");
+                return p;
+            }
     }
     if (modulus) {
         uint64_t pending = ncols;
@@ -264,6 +398,7 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
                         " occurs in A and in B (a booleanity row, and no later row determines the column)";
             p.steps.clear();
             p.bit_cols.clear();
+            p.pairs.clear();
             return p;
         }
     }
@@ -274,6 +409,7 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
             p.message = "column " + std::to_string(j) + " is marked unknown and no row determines it";
             p.steps.clear();
             p.bit_cols.clear();
+            p.pairs.clear();
             return p;
         }
     // counting sort by (level, kind); the row order inside a key is the order of discovery
@@ -289,17 +425,18 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
         for (const Step &s : p.steps) sorted[cursor[(size_t)(s.level - 1) * K + s.kind]++] = s;
         p.steps.swap(sorted);
     }
-    // launch schedule: a wide level is its own launch, split where the dividing kinds begin and again where the decompositions and
-    // their dividing kinds begin; consecutive narrow levels are one chain
+    // launch schedule: a wide level is its own launch, split where the dividing kinds begin, again where the decompositions and
+    // their dividing kinds begin, and where the is-zero pairs begin; consecutive narrow levels are one chain
     for (uint32_t l = 0; l < max_level; ++l) {
         const uint32_t *at = start.data() + (size_t)l * K;
-        const uint32_t lo = at[KIND_C], ab = at[KIND_A], bits = at[KIND_BITS_C], bits_ab = at[KIND_BITS_A], hi = at[K];
+        const uint32_t lo = at[KIND_C], ab = at[KIND_A], bits = at[KIND_BITS_C], bits_ab = at[KIND_BITS_A], pairs = at[KIND_ISZERO], hi = at[K];
         const uint8_t divides = (uint8_t)(bits > ab || hi > bits_ab);
         if (hi - lo >= wide_steps) {
             if (ab > lo) p.launches.push_back(Launch{lo, ab, 0, 0});
             if (bits > ab) p.launches.push_back(Launch{ab, bits, 0, 1});
             if (bits_ab > bits) p.launches.push_back(Launch{bits, bits_ab, 0, 0, 1});
-            if (hi > bits_ab) p.launches.push_back(Launch{bits_ab, hi, 0, 1, 1});
+            if (pairs > bits_ab) p.launches.push_back(Launch{bits_ab, pairs, 0, 1, 1});
+            if (hi > pairs) p.launches.push_back(Launch{pairs, hi, 0, 1, 0, 1});
         } else if (!p.launches.empty() && p.launches.back().chain) {
             p.launches.back().hi = hi;
             p.launches.back().divides |= divides;

@@ -801,6 +801,11 @@ impl GpuKey {
     /// completed instance (what the verifier needs; `pm_prove_tap(9)`), or the row's status: `InvalidArg` for an assignment that
     /// got stuck on a division by zero or on a value that does not fit its bits, otherwise what [`GpuKey::prove_batch`] gives it.  The outer error is the call's: an
     /// unsolvable structure is `InvalidArg` with the row or column in the message, and nothing has been computed.
+    ///
+    /// The is-zero pair -- the two rows of every equality test (`FpVar::is_neq`: `(a - b) * mult = neq`, `(a - b) * (1 - neq) = 0`;
+    /// circom's `IsZero` alike) with both the multiplier and the flag left `None` -- is completed as one step.  Where the tested
+    /// value is zero the multiplier is free and the library writes m = 0; arkworks' own witness generation writes 1 there, and a
+    /// caller that needs that value gives the multiplier as `Some(..)` and leaves only the flag open.
     #[allow(clippy::type_complexity)]
     pub fn prove_batch_from_partial<E: Pairing>(
         &self,
@@ -843,7 +848,8 @@ impl GpuKey {
 
     /// `pm_r1cs_check_batch` with `PM_ASSIGNMENT_SOLVE` and no rows asked for: complete partial assignments (`None` = to be computed)
     /// without proving.  Returns, per assignment, its stuck row (`Some(row)`: a division by zero there, or a bit decomposition of a
-    /// value of 2^k or more; the instance is then all zero) and the completed instance, leading one included.
+    /// value of 2^k or more; the instance is then all zero) and the completed instance, leading one included.  An is-zero pair never
+    /// sticks: with the tested value zero its multiplier is stored as m = 0 (see [`GpuKey::prove_batch_from_partial`]).
     #[allow(clippy::type_complexity)]
     pub fn solve<E: Pairing>(
         &self,

@@ -1,0 +1,30 @@
+"""CPU: the witness solver's plan builder on is-zero pairs (polymath_amd/host/solve_plan.hpp: opener, closer, KIND_ISZERO), compiled
+with g++ into tests/native/solve_iszero_selftest.cpp.  Accepted: arkworks' and circom's form, the known side in A or in B in either
+row, K2 = K1 and K2 = -K1 with the entries stored in another order, known rests beside the flag in both rows, a pair that stays open
+over rows that do not name it, two openers pending before either closes (closed in the order they opened and in the other order),
+a flag with an earlier booleanity row, a pair at a later level -- step, rows, entry positions, level, sort position after
+ordinary steps and decompositions, and the launch of a wide and of a narrow level against hand-written expectations; each plan
+executed serially with the host field type over marker words with d != 0 and d = 0 (one inversion per pair, 0^-1 = 0), values
+against the formulas and the rows themselves.  The multiplier given by the caller plans as an ordinary kind-C step.  Refused, each
+with row, column and a message that begins with the message of the plan without the modulus: an opener never closed, a next row
+that names m, that names the flag in C, on both sides or twice on one, K2 != +-K1, a second unknown; K1 all-zero and both unknowns on the A / B
+sides are refused at once as before.  Systems without pairs give the plan they gave.  Both curves; once more as a stand-alone
+program under AddressSanitizer and UBSan."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SOURCE = os.path.join(ROOT, "tests", "native", "solve_iszero_selftest.cpp")
+
+
+@pytest.mark.parametrize("flags", [["-O2"], ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]], ids=["plain", "sanitized"])
+def test_solve_iszero_host_selftest(tmp_path, flags):
+    exe = str(tmp_path / "solve_iszero_selftest")
+    subprocess.check_call(["g++", "-std=c++17"] + flags + ["-o", exe, SOURCE])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    # accepted 12 + 1 + 6 x (1 + 2 x 2), interleaved 2 x (5 + 4), placements 8 x (1 + 2 + 2), refused 10 x 2 + 2 + 2 + 1, equivalence 1 + 2 + 2 + 1
+    for curve in ("bls12_381", "bn254"):
+        assert "%s: 0 failures of 132" % curve in out.stdout.splitlines(), out.stdout

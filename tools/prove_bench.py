@@ -11,7 +11,10 @@ compares inputs -> proofs instead (mimcK and arx only), host limbs in both route
   (b) B partial assignments (the inputs given, everything else the unknown marker), one pm_host_prove_batch call with PM_ASSIGNMENT_SOLVE
 Every rep of (a) synthesises all B assignments again: that is the step (b) moves to the GPU.
   python tools/prove_bench.py --circuit arx --batch 256 --reps 5 --solve        ArxDemo, 32-bit words, 8 rounds; arx:W:R for others
-is the same comparison on a boolean circuit (bit decompositions, XOR rows)."""
+is the same comparison on a boolean circuit (bit decompositions, XOR rows), and
+  python tools/prove_bench.py --circuit matchcount --batch 256 --reps 5 --solve  MatchCount, 1024 values, arkworks' form;
+                                                                                 matchcount:N:FORM (FORM = ark or circom) for others
+on one that tests equality (one dependency level of N is-zero pairs; about half of the values match)."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -21,7 +24,7 @@ from polymath_amd import circuits as PC
 from polymath_amd.polymath import Polymath
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants), bench:NC (BenchCircuit, NC constraints) or arx[:WIDTH:ROUNDS] (ArxDemo)")
+ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants), bench:NC (BenchCircuit, NC constraints), arx[:WIDTH:ROUNDS] (ArxDemo) or matchcount[:N:FORM] (MatchCount)")
 ap.add_argument("--batch", type=int, default=16)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--curve", default="bls12_381")
@@ -29,8 +32,8 @@ ap.add_argument("--transcript", default="merlin")
 ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="pm_ctx_set_option before the key is made, e.g. --opt tables=0")
 ap.add_argument("--solve", action="store_true", help="host-synthesised assignments against partial assignments solved on the GPU")
 a = ap.parse_args()
-if a.solve and not a.circuit.startswith(("mimc", "arx")):
-    ap.error("--solve needs a mimcK or an arx circuit")
+if a.solve and not a.circuit.startswith(("mimc", "arx", "matchcount")):
+    ap.error("--solve needs a mimcK, an arx or a matchcount circuit")
 pm = Polymath(a.curve, a.transcript, device=0)
 for kv in a.opt:
     pm.ctx.set_option(kv.split("=", 1)[0], int(kv.split("=", 1)[1]))
@@ -45,6 +48,14 @@ elif a.circuit.startswith("arx"):
     width, rounds = (int(v) for v in a.circuit.split(":")[1:3]) if ":" in a.circuit else (32, 8)
     make = lambda: PC.ArxDemo(g.next_u64() % (1 << width), g.next_u64() % (1 << width), width, rounds, 7 % width or 1)
     again = lambda c: PC.ArxDemo(c.a, c.b, c.width, c.rounds, c.rot)
+    partial_of = lambda c: c.partial(r)
+elif a.circuit.startswith("matchcount"):
+    n_values, form = (int(a.circuit.split(":")[1]), a.circuit.split(":")[2]) if ":" in a.circuit else (1024, "ark")
+
+    def make():
+        key = g.fr(r)
+        return PC.MatchCount([key if g.next_u64() & 1 else g.fr(r) for _ in range(n_values)], key, form)
+    again = lambda c: PC.MatchCount(c.values, c.key, c.form)
     partial_of = lambda c: c.partial(r)
 else:
     nc = int(a.circuit.split(":", 1)[1])
