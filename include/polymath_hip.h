@@ -374,7 +374,9 @@ typedef enum pm_assignment_flags {
  * instance_host: the m0 public inputs (leading one included) as host Montgomery limbs -- they are hashed;
  * x, w: the assignment, host pointers or (assignment_on_device != 0) device pointers as in
  * pm_prove_phase1_device.  proof_bytes receives Proof::serialize_compressed (data_structures.rs:10-19):
- * 176 bytes on BLS12-381, 128 on BN254.  Status codes as for the phases. */
+ * 176 bytes on BLS12-381, 128 on BN254.  Status codes as for the phases.  transcript must be a pm_transcript, 0 .. 2: the
+ * pm_prove_glue flag below belongs to pm_host_prove_batch alone -- pm_host_prove, pm_host_prove_sharded and the verify entry points
+ * refuse it like any other value (PM_ERR_INVALID_ARG). */
 int pm_host_prove(pm_ctx *ctx, const pm_pk *pk, int transcript, const uint64_t *instance_host, const uint64_t *x,
                   const uint64_t *w, int assignment_on_device, const uint64_t *r_a, uint8_t *proof_bytes, size_t capacity,
                   size_t *proof_len);
@@ -397,7 +399,27 @@ int pm_host_prove(pm_ctx *ctx, const pm_pk *pk, int transcript, const uint64_t *
  * returns for it (PM_ERR_REMAINDER_NONZERO / PM_ERR_DEGREE_BOUND) and zeroed bytes, and does not disturb its neighbours.
  * PM_ERR_INVALID_ARG, nothing computed: a sharded key, a key on another device, an unknown transcript, a wrong proof_len, a NULL
  * pointer where one is required.  count == 0 is PM_OK; count == 1 is pm_host_prove.  The context stays usable as before (a proof in
- * flight between pm_prove_phase1 and phase 3 is not disturbed); pm_last_timings reports every slot summed over the batch. */
+ * flight between pm_prove_phase1 and phase 3 is not disturbed); pm_last_timings reports every slot summed over the batch.
+ *
+ * transcript = pm_transcript | pm_prove_glue.  transcript & 255 must be a pm_transcript and transcript & ~(255 | 256) zero; anything
+ * else is PM_ERR_INVALID_ARG with nothing written.
+ *   PM_PROVE_GLUE_HOST (the default): between the three device phases of a group the stream is stopped, the phase's points and
+ *     values come to the host and the glue above runs there, proof after proof: about six synchronisations a group.
+ *   PM_PROVE_GLUE_DEVICE: the same glue -- both transcript messages, x1, the powers of y1, a(x1), pi(x1), c(x1), x2, the numerator's
+ *     constants, the compressed records and the proof's bytes -- runs in three kernels with one lane per proof, and the phases read
+ *     their per-proof records from device memory those kernels wrote.  A group goes from its uploads (the assignments, r_a, and
+ *     instance_host's rows x m0 x 32 bytes, once) to its proof bytes without the host: ONE device-to-host copy (rows x proof_len
+ *     bytes and one status word per proof) and ONE stream synchronisation per group.  (A workspace that has to grow is reallocated
+ *     first, which waits for the device: the first call at a shape.)  Under PM_ASSIGNMENT_SOLVE the solver's read-back for tap 9 stays:
+ *     one more synchronisation per group, before phase 1.
+ *     CONTRACT: for every i the status and the bytes of proof i are bit for bit those of the same call without the flag, refused rows
+ *     included (same status, zeroed bytes, neighbours untouched).  The hashed public inputs are instance_host's, as in host mode --
+ *     under PM_ASSIGNMENT_SOLVE with their marker entries replaced by the solved values -- not the x row's, should a caller pass
+ *     different ones.  With the flag count == 1 runs the group path with one row (it is not forwarded to pm_host_prove).  A key whose
+ *     single proof exceeds an MSM piece keeps running as the loop of pm_host_prove, with the host's glue: the bytes are the same, and
+ *     such a call leaves no tap 11.  pm_last_timings: the glue kernels' GPU ms are part of slot 2 (poly); the stage timers are read
+ *     when pm_last_timings is called, not during the call.  pm_prove_tap(11) returns what the kernels derived. */
+typedef enum pm_prove_glue { PM_PROVE_GLUE_HOST = 0, PM_PROVE_GLUE_DEVICE = 256 } pm_prove_glue;
 int pm_host_prove_batch(pm_ctx *ctx, const pm_pk *pk, int transcript, size_t count, const uint64_t *instance_host,
                         const uint64_t *x, const uint64_t *w, int assignment_on_device, const uint64_t *r_a,
                         uint8_t *proofs, size_t proof_len, int *status);
@@ -611,7 +633,11 @@ int pm_selftest_field(pm_ctx *ctx, size_t products_per_field, uint64_t seed, uin
  *          x || w rows, assignment after assignment (a stuck one's row is undefined).  PM_ERR_STATE if the last call with the flag was a
  *          prove call (its groups reuse the prover's workspace) or there was none.  The rows stay in a device buffer of the context,
  *          count * (m0 + mw) * 32 bytes, KEPT until the next call with the flag reuses it or pm_ctx_destroy frees it: after one large
- *          batch that memory stays with the context (use a context of its own for large batches and destroy it). */
+ *          batch that memory stays with the context (use a context of its own for large batches and destroy it).
+ *       11 (no proof in flight needed) what the last pm_host_prove_batch with PM_PROVE_GLUE_DEVICE on this context derived, four
+ *          elements a proof (Montgomery), for all `count` proofs: x1, x2, a(x1), c(x1); a refused row holds zeros.  A device buffer of
+ *          the context (count * 128 bytes), kept like tap 10's.  PM_ERR_STATE when there was no such call, or the last one failed or
+ *          fell back to the per-proof loop. */
 int pm_prove_tap(pm_ctx *ctx, int which, uint64_t *out, size_t max_elems, size_t *n_elems);
 
 #ifdef __cplusplus

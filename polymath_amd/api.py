@@ -37,6 +37,8 @@ VERIFY_TIMING_SLOTS = {"decode": 0, "terms": 1, "tree": 2, "host_glue": 3, "host
 VERIFY_PAIRING = {"host": 0, "device": 1}
 # pm_verify_challenges (include/polymath_hip.h): where the per-proof Fiat-Shamir challenges run; OR-ed into pm_verify_batch2's `pairing`
 VERIFY_CHALLENGES = {"host": 0, "device": 256}
+PROVE_GLUE_HOST, PROVE_GLUE_DEVICE = 0, 256    # pm_prove_glue: OR-ed into the `transcript` argument of pm_host_prove_batch
+PROVE_GLUE = {"host": PROVE_GLUE_HOST, "device": PROVE_GLUE_DEVICE}
 # pm_assignment_flags (include/polymath_hip.h): the `assignment_on_device` argument of the check and host-prove calls is a flag word
 ASSIGNMENT_DEVICE, ASSIGNMENT_SOLVE = 1, 2
 UNKNOWN_LIMBS = (0xFFFFFFFFFFFFFFFF,) * 4     # an Fr of x / w / instance_host with these words is unknown under ASSIGNMENT_SOLVE
@@ -790,11 +792,14 @@ class ProvingKey:
             raise failure[0]
         return rc, buf.raw[:n.value]
 
-    def host_prove_batch(self, transcript, instance_limbs, x, w, r_a, on_device=False, solve=False):
+    def host_prove_batch(self, transcript, instance_limbs, x, w, r_a, on_device=False, solve=False, glue="host"):
         """pm_host_prove_batch: `count` proofs against this (unsharded) key in one native call.  instance_limbs: (count, m0, 4) host
         limbs (hashed); x, w: (count, m0, 4) / (count, mw, 4) host limbs, or device pointers (ints) to the same rows with
         on_device=True; r_a: (count, 2, 4).  solve: PM_ASSIGNMENT_SOLVE, entries equal to UNKNOWN_LIMBS (instance_limbs included) are computed
         on the device first; solve_results() then returns the completed public inputs.
+        glue: "host" (the default) or "device" -- PM_PROVE_GLUE_DEVICE: the Fiat-Shamir glue between the phases runs in kernels with
+        one lane per proof, one copy to the host and one synchronisation per group; same statuses, same bytes; glue_challenges()
+        then returns what the kernels derived.
         -> (status of the call, bytes of count * proof_len, np.int32[count] per-proof statuses)."""
         inst = _c(instance_limbs)
         count = int(inst.shape[0]) if inst.ndim == 3 else 0
@@ -808,7 +813,7 @@ class ProvingKey:
             x = _c(x)
             w = _c(w) if np.size(w) else np.zeros((max(1, count), 1, 4), dtype=np.uint64)
             px, pw = x.ctypes.data_as(ct.c_void_p), w.ctypes.data_as(ct.c_void_p)
-        rc = self.ctx.L.pm_host_prove_batch(self.ctx.h, self.h, self.TRANSCRIPT_IDS[transcript], count, _p(inst), px, pw, int(bool(on_device)) | (ASSIGNMENT_SOLVE if solve else 0), _p(r_a),
+        rc = self.ctx.L.pm_host_prove_batch(self.ctx.h, self.h, self.TRANSCRIPT_IDS[transcript] | PROVE_GLUE[glue], count, _p(inst), px, pw, int(bool(on_device)) | (ASSIGNMENT_SOLVE if solve else 0), _p(r_a),
                                             buf, proof_len, status.ctypes.data_as(ct.POINTER(ct.c_int)))
         return rc, buf.raw[:count * proof_len], status[:count]
 
@@ -873,6 +878,11 @@ class ProvingKey:
         -> (np.uint64[count] stuck row or NOT_STUCK, np.uint64[count, m0, 4] completed public inputs, Montgomery limbs, zeros where stuck)."""
         rec = self.tap(9, count * (1 + self.m0)).reshape(count, 1 + self.m0, 4)
         return rec[:, 0, 0].copy(), rec[:, 1:, :].copy()
+
+    def glue_challenges(self, count):
+        """pm_prove_tap(11) after host_prove_batch(glue="device") over `count` proofs on this key's context
+        -> np.uint64[count, 4, 4]: x1, x2, a(x1), c(x1) of every proof, Montgomery limbs, zeros for a refused row."""
+        return self.tap(11, 4 * count).reshape(count, 4, 4)
 
     def solved_assignments(self, count, mw):
         """pm_prove_tap(10) after r1cs_check[_batch](solve=True) over `count` assignments -> np.uint64[count, m0 + mw, 4], the completed

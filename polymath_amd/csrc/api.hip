@@ -176,6 +176,7 @@ extern "C" void pm_ctx_destroy(pm_ctx *ctx) {
     ctx->pw.release();
     ctx->pb.release();
     ctx->sv.release();
+    ctx->gw.release();
     for (auto &b : ctx->fb_table) b.release();
     for (auto &t : ctx->tw) { t.fwd.release(); t.inv.release(); t.fwd_int.release(); t.inv_int.release(); }
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
@@ -1085,6 +1086,14 @@ extern "C" int pm_prove_tap(pm_ctx *ctx, int which, uint64_t *out, size_t max_el
         *n_elems = ctx->sv.tap10_rows * ctx->sv.tap10_cols;
         const size_t k10 = std::min(*n_elems, max_elems);
         if (k10) PM_HIP(ctx, hipMemcpy(out, ctx->sv.xw.p, k10 * 32, hipMemcpyDeviceToHost));
+        return PM_OK;
+    }
+    if (which == 11) {  // the device glue's challenges of the last pm_host_prove_batch with PM_PROVE_GLUE_DEVICE (prove_glue.hip): device buffer
+        if (!ctx->gw.tap_rows) return PM_ERR_STATE;
+        PM_TRY(set_device(ctx));
+        *n_elems = ctx->gw.tap_rows * 4;
+        const size_t k11 = std::min(*n_elems, max_elems);
+        if (k11) PM_HIP(ctx, hipMemcpy(out, ctx->gw.tap.p, k11 * 32, hipMemcpyDeviceToHost));
         return PM_OK;
     }
     if (!ctx->pk || ctx->phase < 1) return PM_ERR_STATE;

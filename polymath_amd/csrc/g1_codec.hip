@@ -11,21 +11,10 @@
 #include <cstring>
 
 #include "internal.h"
+#include "g1_record.cuh"
 #include "../host/wire.hpp"
 
 namespace pm {
-
-// canonical a > (p - 1) / 2, i.e. a > -a in the integer order deser_g1 compares in (fq_cmp(y, -y) > 0)
-template <class P>
-__host__ __device__ __forceinline__ bool fq_canon_gt_half(const Fp<P> &a) {
-    bool gt = false, decided = false;
-#pragma unroll
-    for (int i = P::N - 1; i >= 0; --i) {
-        const uint32_t h = (P::MOD[i] >> 1) | (i + 1 < P::N ? P::MOD[i + 1] << 31 : 0u);
-        if (!decided && a.l[i] != h) { gt = a.l[i] > h; decided = true; }
-    }
-    return gt;
-}
 
 // canonical a < p
 template <class P>
@@ -126,25 +115,12 @@ __global__ __launch_bounds__(256, 2) void k_g1_decode(const uint8_t *in, size_t 
 
 template <class C>
 __global__ __launch_bounds__(256) void k_g1_encode(const Affine<C> *pts, size_t count, uint8_t *out) {
-    typedef typename C::FqP P;
-    typedef Fp<P> Fq;
-    constexpr int NW = P::N, NB = 4 * NW;
+    constexpr int NW = C::FqP::N, NB = 4 * NW;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     const Affine<C> a = pts[i];
-    const bool inf = a.is_inf();
-    const Fq x = from_mont<P>(a.x);
-    const bool larger = !inf && fq_canon_gt_half<P>(from_mont<P>(a.y));
     uint32_t w[NW];
-    if (C::ID == 0) {
-#pragma unroll
-        for (int k = 0; k < NW; ++k) w[k] = __builtin_bswap32(x.l[NW - 1 - k]);
-        w[0] |= 0x80u | (inf ? 0x40u : 0u) | (larger ? 0x20u : 0u);
-    } else {
-#pragma unroll
-        for (int k = 0; k < NW; ++k) w[k] = x.l[k];
-        w[NW - 1] |= ((inf ? 0x40u : 0u) | (larger ? 0x80u : 0u)) << 24;
-    }
+    g1_record_words<C>(a, a.is_inf(), w);
     uint4 *dst = (uint4 *)(out + i * NB);
 #pragma unroll
     for (int k = 0; k < NB / 16; ++k) dst[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);

@@ -160,18 +160,132 @@ extern "C" int pm_host_prove(pm_ctx *ctx, const pm_pk *pk, int transcript, const
 // ---- pm_host_prove_batch: `count` proofs against one unsharded key, in groups whose vectors are [rows][len] arrays (prove_batch.hip) ----
 namespace {
 
+// What runs between the phases of a group: a glue provider.  after1 / after2 come after phases 1 and 2 and leave the BatchRow records
+// of the next phase in the workspace; finish comes after phase 3 and writes the group's proofs and statuses.  begin: once per group,
+// before phase 1 (stat / out are the group's first row's).
+
+// The host: every phase's results come down (one synchronisation each), Polymath::glue_x1 / glue_x2 run per proof, the records go up.
 template <class C, class T>
-int host_prove_batch_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint64_t *instance_host, const uint64_t *x, const uint64_t *w,
-                          int on_device, bool solve, const uint64_t *r_a, uint8_t *proofs, size_t proof_len, int *status) {
+struct HostGlue {
     typedef pmhost::Polymath<C, T> PMH;
     typedef typename PMH::Fr Fr;
     typedef typename PMH::Glue Glue;
+    pm_ctx *ctx;
+    const pm_pk *pk;
+    bool solve;
+    const uint64_t *instance_host;
+    size_t proof_len;
+    pmhost::ProvingKey<C> key;          // n / m0 / sigma / omega carrier of the host glue: no device handle
+    std::vector<pm::Affine<C>> pa, pc, pd;
+    std::vector<int> ia, ic, id;
+    std::vector<unsigned> flags;
+    std::vector<Fr> x1, x2, a_at, c_at, u_at;
+    std::vector<std::vector<Fr>> inst;
+    std::vector<pmhost::Proof<C>> proof;
+    std::vector<Glue> glue;
+    size_t g0 = 0, rows = 0;
+    const uint64_t *ra = nullptr;
+    int *stat = nullptr;
+    uint8_t *out = nullptr;
+    HostGlue(pm_ctx *c, const pm_pk *k, int, size_t, size_t group, bool sv, const uint64_t *inst_host, size_t plen)
+        : ctx(c), pk(k), solve(sv), instance_host(inst_host), proof_len(plen), pa(group), pc(group), pd(group), ia(group), ic(group), id(group),
+          flags(group), x1(group), x2(group), a_at(group), c_at(group), u_at(group), inst(group, std::vector<Fr>(k->m0)), proof(group) {
+        key.n = pk->n; key.m0 = pk->m0; key.sigma = pk->sigma;
+        memcpy(key.omega.l, pk->omega, 32);
+    }
+    int start() { return PM_OK; }
+    int begin(size_t first, size_t n, const uint64_t *r_a, int *status, uint8_t *proofs) {
+        g0 = first; rows = n; ra = r_a; stat = status; out = proofs;
+        return PM_OK;
+    }
+    int after1() {
+        PM_TRY(pm::prove_batch_fetch1<C>(ctx, rows, pa.data(), ia.data(), pc.data(), ic.data(), flags.data()));
+        const size_t m0 = pk->m0;
+        glue.assign(rows, Glue());
+        for (size_t b = 0; b < rows; ++b) {
+            stat[b] = pm::phase1_flag_status(flags[b]);
+            x1[b] = x2[b] = a_at[b] = c_at[b] = Fr::zero();     // a refused proof rides along on zeros; its results are dropped
+            if (solve && pm::solve_tap9_row(ctx, pk, g0 + b)[0] != NOT_STUCK) stat[b] = PM_ERR_INVALID_ARG;   // stuck: its row holds no assignment
+            if (stat[b] != PM_OK) continue;
+            if (solve) solved_instance(ctx, pk, g0 + b, instance_host + 4 * m0 * (g0 + b), (uint64_t *)inst[b].data());
+            else memcpy((void *)inst[b].data(), instance_host + 4 * m0 * (g0 + b), m0 * sizeof(Fr));
+            proof[b].a_g1.p = pa[b]; proof[b].a_g1.inf = ia[b] != 0;
+            proof[b].c_g1.p = pc[b]; proof[b].c_g1.inf = ic[b] != 0;
+            PMH::glue_x1(glue[b], key, inst[b], proof[b]);
+            x1[b] = glue[b].x1;
+        }
+        return pm::prove_batch_rows2<C>(ctx, rows, (const uint64_t *)x1.data());
+    }
+    int after2() {
+        PM_TRY(pm::prove_batch_fetch2<C>(ctx, pk, rows, (uint64_t *)u_at.data()));
+        for (size_t b = 0; b < rows; ++b) {
+            if (stat[b] != PM_OK) continue;
+            PMH::glue_x2(glue[b], key, inst[b], (const Fr *)(ra + 8 * b), u_at[b], proof[b]);
+            x2[b] = glue[b].x2; a_at[b] = proof[b].a_at_x1; c_at[b] = glue[b].c_at_x1;
+        }
+        return pm::prove_batch_rows3<C>(ctx, pk, rows, ra, (const uint64_t *)x1.data(), (const uint64_t *)x2.data(), (const uint64_t *)a_at.data(),
+                                        (const uint64_t *)c_at.data());
+    }
+    int finish() {
+        PM_TRY(pm::prove_batch_fetch3<C>(ctx, rows, pd.data(), id.data(), flags.data()));
+        for (size_t b = 0; b < rows; ++b) {
+            uint8_t *o = out + b * proof_len;
+            if (stat[b] == PM_OK) stat[b] = pm::phase3_flag_status(flags[b]);
+            if (stat[b] == PM_OK) {
+                proof[b].d_g1.p = pd[b]; proof[b].d_g1.inf = id[b] != 0;
+                const pmhost::Bytes bytes = proof[b].to_bytes();
+                if (bytes.size() == proof_len) memcpy(o, bytes.data(), proof_len);
+                else stat[b] = PM_ERR_STATE;
+            }
+            if (stat[b] != PM_OK) memset(o, 0, proof_len);
+        }
+        return PM_OK;
+    }
+    void end(bool) {}
+};
+
+// The device (prove_glue.hip): three launches of one lane per proof; nothing comes down before finish, which makes the group's one copy
+// and one synchronisation.  The stage timers stay pending (lazy_timings, as in pm_host_prove): reading them would wait for the stream.
+template <class C, class T>
+struct DeviceGlue {
+    pm_ctx *ctx;
+    const pm_pk *pk;
+    int transcript;
+    size_t count;
+    bool solve;
+    const uint64_t *instance_host;
+    size_t proof_len;
+    size_t g0 = 0, rows = 0;
+    int *stat = nullptr;
+    uint8_t *out = nullptr;
+    DeviceGlue(pm_ctx *c, const pm_pk *k, int tr, size_t cnt, size_t, bool sv, const uint64_t *inst_host, size_t plen)
+        : ctx(c), pk(k), transcript(tr), count(cnt), solve(sv), instance_host(inst_host), proof_len(plen) {}
+    int start() {
+        ctx->lazy_timings = true;
+        return pm::glue_begin<C>(ctx, pk, count);
+    }
+    int begin(size_t first, size_t n, const uint64_t *r_a, int *status, uint8_t *proofs) {
+        g0 = first; rows = n; stat = status; out = proofs;
+        return pm::glue_upload<C>(ctx, pk, rows, instance_host + 4 * pk->m0 * g0, r_a, proof_len);
+    }
+    int after1() { return pm::glue_x1<C>(ctx, pk, transcript, rows, solve); }
+    int after2() { return pm::glue_x2<C>(ctx, pk, transcript, rows, g0); }
+    int finish() { return pm::glue_finish<C>(ctx, pk, rows, solve, out, proof_len, stat); }
+    void end(bool ok) {
+        ctx->lazy_timings = false;
+        if (ok) ctx->gw.tap_rows = count;
+    }
+};
+
+template <class C, class T, template <class, class> class GlueT>
+int host_prove_batch_impl(pm_ctx *ctx, const pm_pk *pk, int transcript, size_t count, const uint64_t *instance_host, const uint64_t *x,
+                          const uint64_t *w, int on_device, bool solve, const uint64_t *r_a, uint8_t *proofs, size_t proof_len, int *status) {
     const size_t m0 = pk->m0, mw = pk->mw;
     size_t group = 0;
     PM_TRY(pm::prove_batch_group<C>(ctx, pk, count, &group));
     if (group == 0) {
         // one proof's [d]_1 row exceeds an MSM piece (or not even one proof fits the memory share): the per-proof path, which splits
-        // its MSMs into pieces; the stage times are summed over the proofs
+        // its MSMs into pieces, with the host's glue whatever the caller chose; the stage times are summed over the proofs
         double sum[pm::T_NUM_SLOTS] = {0};
         size_t xs = m0, ws = mw;        // elements between consecutive x rows / w rows
         std::vector<uint64_t> solved_inst(solve ? 4 * m0 : 0);
@@ -218,11 +332,8 @@ int host_prove_batch_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint
         for (int s = 0; s < pm::T_NUM_SLOTS; ++s) ctx->timing_ms[s] = sum[s];
         return PM_OK;
     }
-    pmhost::ProvingKey<C> key;          // n / m0 / sigma / omega carrier of the host glue: no device handle
-    key.n = pk->n; key.m0 = pk->m0; key.sigma = pk->sigma;
-    memcpy(key.omega.l, pk->omega, 32);
     pm::timing_reset(ctx);             // the phases below add to the slots and never reset them: the sums over the batch
-    typename PMH::Fr *gxw = nullptr;   // solve: the group's x || w rows in the prover's workspace
+    pm::Fp<typename C::FrP> *gxw = nullptr;   // solve: the group's x || w rows in the prover's workspace
     const size_t n_groups = (count + group - 1) / group;
     if (solve) {
         // every assignment must mark the columns assignment 0 marks, and the structure must be solvable, before anything is computed:
@@ -233,67 +344,37 @@ int host_prove_batch_impl(pm_ctx *ctx, const pm_pk *pk, size_t count, const uint
             PM_TRY(pm::solve_load<C>(ctx, pk, gxw, count - g0 < group ? count - g0 : group, g0, x, w, on_device != 0));
         PM_TRY(pm::solve_plan<C>(ctx, pk));
     }
+    PM_TRY(pm::prove_batch_reserve<C>(ctx, pk, group));
     int rc = PM_OK;
     size_t done = 0;                   // proofs of finished groups
     try {
-        std::vector<pm::Affine<C>> pa(group), pc(group), pd(group);
-        std::vector<int> ia(group), ic(group), id(group);
-        std::vector<unsigned> flags(group);
-        std::vector<Fr> x1(group), x2(group), a_at(group), c_at(group), u_at(group);
-        std::vector<std::vector<Fr>> inst(group, std::vector<Fr>(m0));
-        std::vector<pmhost::Proof<C>> proof(group);
+        GlueT<C, T> glue(ctx, pk, transcript, count, group, solve, instance_host, proof_len);
+        rc = glue.start();
+        // ONE loop over the groups for both providers: upload, phase 1, glue, phase 2, glue, phase 3, the proofs
         for (size_t g0 = 0; g0 < count && rc == PM_OK; g0 += group) {
             const size_t rows = count - g0 < group ? count - g0 : group;
             const uint64_t *ra = r_a + 8 * g0;
-            int *stat = status + g0;
             if (solve) {
                 if (n_groups > 1) rc = pm::solve_load<C>(ctx, pk, gxw, rows, g0, x, w, on_device != 0);   // (compares the rows once more: harmless)
                 if (rc == PM_OK) rc = pm::solve_group<C>(ctx, pk, gxw, rows, g0, pm::T_WITNESS_MAP);
                 if (rc != PM_OK) break;
             }
-            rc = pm::prove_batch_phase1<C>(ctx, pk, rows, x + 4 * m0 * g0, w ? w + 4 * mw * g0 : nullptr, on_device != 0, ra, pa.data(), ia.data(),
-                                           pc.data(), ic.data(), flags.data(), solve);
-            if (rc != PM_OK) break;
-            std::vector<Glue> glue(rows);
-            for (size_t b = 0; b < rows; ++b) {
-                stat[b] = pm::phase1_flag_status(flags[b]);
-                x1[b] = x2[b] = a_at[b] = c_at[b] = Fr::zero();     // a refused proof rides along on zeros; its results are dropped
-                if (solve && pm::solve_tap9_row(ctx, pk, g0 + b)[0] != NOT_STUCK) stat[b] = PM_ERR_INVALID_ARG;   // stuck: its row holds no assignment
-                if (stat[b] != PM_OK) continue;
-                if (solve) solved_instance(ctx, pk, g0 + b, instance_host + 4 * m0 * (g0 + b), (uint64_t *)inst[b].data());
-                else memcpy((void *)inst[b].data(), instance_host + 4 * m0 * (g0 + b), m0 * sizeof(Fr));
-                proof[b].a_g1.p = pa[b]; proof[b].a_g1.inf = ia[b] != 0;
-                proof[b].c_g1.p = pc[b]; proof[b].c_g1.inf = ic[b] != 0;
-                PMH::glue_x1(glue[b], key, inst[b], proof[b]);
-                x1[b] = glue[b].x1;
-            }
-            rc = pm::prove_batch_phase2<C>(ctx, pk, rows, (const uint64_t *)x1.data(), (uint64_t *)u_at.data());
-            if (rc != PM_OK) break;
-            for (size_t b = 0; b < rows; ++b) {
-                if (stat[b] != PM_OK) continue;
-                PMH::glue_x2(glue[b], key, inst[b], (const Fr *)(ra + 8 * b), u_at[b], proof[b]);
-                x2[b] = glue[b].x2; a_at[b] = proof[b].a_at_x1; c_at[b] = glue[b].c_at_x1;
-            }
-            rc = pm::prove_batch_phase3<C>(ctx, pk, rows, ra, (const uint64_t *)x1.data(), (const uint64_t *)x2.data(), (const uint64_t *)a_at.data(),
-                                           (const uint64_t *)c_at.data(), pd.data(), id.data(), flags.data());
-            if (rc != PM_OK) break;
-            for (size_t b = 0; b < rows; ++b) {
-                uint8_t *out = proofs + (g0 + b) * proof_len;
-                if (stat[b] == PM_OK) stat[b] = pm::phase3_flag_status(flags[b]);
-                if (stat[b] == PM_OK) {
-                    proof[b].d_g1.p = pd[b]; proof[b].d_g1.inf = id[b] != 0;
-                    const pmhost::Bytes bytes = proof[b].to_bytes();
-                    if (bytes.size() == proof_len) memcpy(out, bytes.data(), proof_len);
-                    else stat[b] = PM_ERR_STATE;
-                }
-                if (stat[b] != PM_OK) memset(out, 0, proof_len);
-            }
+            if ((rc = glue.begin(g0, rows, ra, status + g0, proofs + g0 * proof_len)) != PM_OK) break;
+            if ((rc = pm::prove_batch_phase1<C>(ctx, pk, rows, x + 4 * m0 * g0, w ? w + 4 * mw * g0 : nullptr, on_device != 0, ra, solve)) != PM_OK) break;
+            if ((rc = glue.after1()) != PM_OK) break;
+            if ((rc = pm::prove_batch_phase2<C>(ctx, pk, rows)) != PM_OK) break;
+            if ((rc = glue.after2()) != PM_OK) break;
+            if ((rc = pm::prove_batch_phase3<C>(ctx, pk, rows)) != PM_OK) break;
+            if ((rc = glue.finish()) != PM_OK) break;
             done = g0 + rows;
         }
+        glue.end(rc == PM_OK);
     } catch (const std::exception &e) {
         ctx->err = e.what();
+        ctx->lazy_timings = false;
         rc = PM_ERR_STATE;
     }
+    if (rc != PM_OK) (void)hipStreamSynchronize(ctx->stream);   // nothing of a failed group stays in flight behind the call
     // the call failed inside a group: that group's rows and the ones not reached carry the call's status and zeroed bytes
     for (size_t i = done; rc != PM_OK && i < count; ++i) { status[i] = rc; memset(proofs + i * proof_len, 0, proof_len); }
     return rc;
@@ -307,13 +388,16 @@ extern "C" int pm_host_prove_batch(pm_ctx *ctx, const pm_pk *pk, int transcript,
     if (!pm::assignment_flags_ok(assignment_on_device) || !ctx || !pk) return PM_ERR_INVALID_ARG;
     const bool solve = (assignment_on_device & PM_ASSIGNMENT_SOLVE) != 0;
     const int on_device = assignment_on_device & PM_ASSIGNMENT_DEVICE;
+    if (transcript & ~(255 | PM_PROVE_GLUE_DEVICE)) return PM_ERR_INVALID_ARG;
+    const bool device_glue = (transcript & PM_PROVE_GLUE_DEVICE) != 0;
+    transcript &= 255;
     if (!pmhost::transcript_ok(transcript)) return PM_ERR_INVALID_ARG;
     if (pk->shard_count != 1 || pk->layout != PM_SHARD_PAIRS || pk->device != ctx->device) return PM_ERR_INVALID_ARG;
     const size_t fq_bytes = pk->curve == PM_BLS12_381 ? sizeof(pm::Fp<pm::BlsFqP>) : sizeof(pm::Fp<pm::BnFqP>);
     if (proof_len != 3 * fq_bytes + 32) return PM_ERR_INVALID_ARG;     // Proof::serialize_compressed: three G1 points and one Fr
     if (count == 0) return PM_OK;
     if (!instance_host || !x || !r_a || !proofs || !status || (pk->mw && !w)) return PM_ERR_INVALID_ARG;
-    if (count == 1 && solve) {   // as below; what the solver refuses is the CALL's status and leaves the outputs alone
+    if (count == 1 && solve && !device_glue) {   // as below; what the solver refuses is the CALL's status and leaves the outputs alone
         size_t len = 0;
         int stage = 0;
         const int rc = host_prove_solve_any(ctx, pk, transcript, instance_host, x, w, on_device != 0, r_a, proofs, proof_len, &len, &stage);
@@ -322,17 +406,21 @@ extern "C" int pm_host_prove_batch(pm_ctx *ctx, const pm_pk *pk, int transcript,
         if (rc != PM_OK) memset(proofs, 0, proof_len);
         return rc == PM_ERR_HIP ? (int)PM_ERR_HIP : (int)PM_OK;
     }
-    if (count == 1) {   // one proof: forwarded to the per-proof chain (permitted by the contract; the two routes have not been measured at B = 1)
+    if (count == 1 && !device_glue) {   // one proof: forwarded to the per-proof chain (permitted by the contract; the two routes have not been measured at B = 1)
         size_t len = 0;
         status[0] = pm_host_prove(ctx, pk, transcript, instance_host, x, w, assignment_on_device, r_a, proofs, proof_len, &len);
         if (status[0] != PM_OK) memset(proofs, 0, proof_len);
         return status[0] == PM_ERR_HIP ? (int)PM_ERR_HIP : (int)PM_OK;
     }
     if (hipSetDevice(ctx->device) != hipSuccess) return PM_ERR_HIP;
+    if (device_glue) ctx->gw.tap_rows = 0;   // tap 11 is the last device-glue call's; one that falls back per proof leaves none
     return pm::with_curve(pk->curve, [&](auto cv) {
         typedef pm::type_of<decltype(cv)> C;
         return pmhost::with_transcript<C>(transcript, [&](auto t) {
-            return host_prove_batch_impl<C, pm::type_of<decltype(t)>>(ctx, pk, count, instance_host, x, w, on_device, solve, r_a, proofs, proof_len, status);
+            typedef pm::type_of<decltype(t)> T;
+            if (device_glue)
+                return host_prove_batch_impl<C, T, DeviceGlue>(ctx, pk, transcript, count, instance_host, x, w, on_device, solve, r_a, proofs, proof_len, status);
+            return host_prove_batch_impl<C, T, HostGlue>(ctx, pk, transcript, count, instance_host, x, w, on_device, solve, r_a, proofs, proof_len, status);
         });
     });
 }

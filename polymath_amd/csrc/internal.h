@@ -129,8 +129,9 @@ struct MsmSet {
 struct MsmWorkspace {
     MsmSet set;
     DevBuf digits, cursor, wsum, region, sub, digits2, len_bins, block_cnt, hot;
-    DevBuf batch;   // msm_run_batch: the base range's infinity flags, then one (point, flag) record per row of a group
+    DevBuf batch;   // msm_run_batch: the base range's infinity flags, then (host form) one (point, flag) record per row of the batch
 };
+inline size_t batch_flag_bytes(size_t len) { return (len + 15) & ~(size_t)15; }
 
 // Window tables of a resident base vector (setup.hip: tables_build) or, with wide, the plan of an MSM that runs without tables: the
 // layout (msm_plan.h: WindowLayout -- planned(), widest(), the bucket sets) plus where the points are.  Point (w, i) lives at index
@@ -161,6 +162,22 @@ struct ProveWs {
         size_t held = 0;
         for_each([&](DevBuf &b) { held += b.bytes; });
         return held;
+    }
+};
+
+// pm_host_prove_batch with PM_PROVE_GLUE_DEVICE (prove_glue.hip): what the glue kernels read and write for one group of proofs, and
+// tap 11 for the whole call.  pts: the (point, flag) records of [a]_1, [c]_1, [d]_1 as three arrays of `cap` rows (the host-glue
+// prover's phases leave theirs there too); inst: the hashed public inputs, [rows][m0]; ra: r_a as [rows][2]; keep: one record per
+// proof from k_glue_x1 to the later kernels (the transcript's sponge among it); out: the group's proof bytes, then one status word
+// per proof -- what the group's one copy brings down into `host`; tap: x1, x2, a(x1), c(x1) of all proofs of the last call.
+struct GlueWs {
+    DevBuf pts, inst, ra, keep, out, tap;
+    size_t cap = 0;            // rows per array of pts
+    size_t tap_rows = 0;       // pm_prove_tap(11): proofs of the last device-glue call; 0 = none
+    std::vector<uint8_t> host, rows_host;   // rows_host: the host-glue prover's BatchRow records on their way up
+    void release() {
+        for (DevBuf *b : {&pts, &inst, &ra, &keep, &out, &tap}) b->release();
+        cap = tap_rows = 0;
     }
 };
 
@@ -340,6 +357,7 @@ struct pm_ctx {
     pm::DevBuf sh_a, sh_b, sh_c, halo, shard_roots;
     pm::ProveWs pb;      // pm_host_prove_batch: the vectors of a group of proofs
     pm::SolveWs sv;
+    pm::GlueWs gw;
     std::vector<uint64_t> verify_tap;   // pm_prove_tap(8): x1, x2, c(x1), ok of the last batch verified with device challenges, 16 words a proof
     uint64_t shard_roots_n;
     uint32_t shard_roots_N;
@@ -403,6 +421,16 @@ int msm_run(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_
 template <class C>
 int msm_run_batch(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_scalars, size_t len, size_t batch,
                   Affine<C> *h_out, int *h_inf);
+
+// the same with row b's record left in d_out[b] (device memory): enqueued on ctx->stream, no copy to the host, no synchronisation;
+// len <= msm_max_piece(ctx)
+template <class C>
+struct BatchPoint {
+    Affine<C> p;       // standard Montgomery; x = y = 0 for the identity
+    uint32_t inf;
+};
+template <class C>
+int msm_run_batch_device(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_scalars, size_t len, size_t batch, BatchPoint<C> *d_out);
 
 // the same in two halves (msm.hip): enqueue on ctx->stream without waiting / wait and convert
 template <class C>
@@ -541,20 +569,59 @@ template <class C>
 int prove_phase3_impl(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const uint64_t *a_at_x1,
                       const uint64_t *c_at_x1, uint64_t *d_xy, int *d_inf);
 
-// prove_batch.hip: the three phases over a group of `rows` proofs against one unsharded key (blockIdx.y = proof).  x / w / r_a / x1 / ...
-// are `rows` records back to back; flags_out[b] = the flag word of proof b (prove.hip: k_check_sap) as the phase left it.
+// prove_batch.hip: the three phases over a group of `rows` proofs against one unsharded key (blockIdx.y = proof).  x / w / r_a are `rows`
+// records back to back.  Every phase only ENQUEUES on the context's stream: it reads its per-proof values from device memory and leaves
+// its results there -- the (point, flag) records of [a]_1, [c]_1 (phase 1) and [d]_1 (phase 3) in pm_ctx::gw.pts, u(x1) of the rows in
+// the array prove_batch_sums names, the flag word of proof b (prove.hip: k_check_sap) in pm_ctx::pb.flags[b].  Between them a glue
+// provider writes the BatchRow records of pm_ctx::pb.rows (prove_batch_reserve sizes them): x1 before phase 2, the whole record before
+// phase 3 -- the host (prove_batch_fetch1 / _fetch2 / _fetch3 synchronise and bring a phase's results down, prove_batch_rows2 / _rows3
+// upload the records built from the host's challenges) or the kernels of prove_glue.hip (no copy, no synchronisation).
 // prove_batch_group: the largest group the context's msm_max_piece and the HBM budget allow for `count` proofs; 0 = one proof's [d]_1
 // row exceeds a piece (the caller loops over the per-proof path).
 template <class C>
 int prove_batch_group(pm_ctx *ctx, const pm_pk *pk, size_t count, size_t *group);
 template <class C>
+int prove_batch_reserve(pm_ctx *ctx, const pm_pk *pk, size_t rows);
+template <class C>
 int prove_batch_phase1(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *x, const uint64_t *w, bool assignment_on_device,
-                       const uint64_t *r_a, Affine<C> *a, int *a_inf, Affine<C> *c, int *c_inf, unsigned *flags_out, bool xw_resident = false);
+                       const uint64_t *r_a, bool xw_resident = false);
 template <class C>
-int prove_batch_phase2(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *x1, uint64_t *u_at_x1);
+int prove_batch_phase2(pm_ctx *ctx, const pm_pk *pk, size_t rows);
 template <class C>
-int prove_batch_phase3(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *r_a, const uint64_t *x1, const uint64_t *x2,
-                       const uint64_t *a_at_x1, const uint64_t *c_at_x1, Affine<C> *d, int *d_inf, unsigned *flags_out);
+int prove_batch_phase3(pm_ctx *ctx, const pm_pk *pk, size_t rows);
+template <class C>
+const Fp<typename C::FrP> *prove_batch_sums(pm_ctx *ctx, const pm_pk *pk, size_t rows);   // phase 2's u(x1), one per row (device)
+template <class C>
+int prove_batch_fetch1(pm_ctx *ctx, size_t rows, Affine<C> *a, int *a_inf, Affine<C> *c, int *c_inf, unsigned *flags_out);
+template <class C>
+int prove_batch_rows2(pm_ctx *ctx, size_t rows, const uint64_t *x1);
+template <class C>
+int prove_batch_fetch2(pm_ctx *ctx, const pm_pk *pk, size_t rows, uint64_t *u_at_x1);
+template <class C>
+int prove_batch_rows3(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *r_a, const uint64_t *x1, const uint64_t *x2, const uint64_t *a_at_x1,
+                      const uint64_t *c_at_x1);
+template <class C>
+int prove_batch_fetch3(pm_ctx *ctx, size_t rows, Affine<C> *d, int *d_inf, unsigned *flags_out);
+
+// prove_glue.hip: the device glue provider of pm_host_prove_batch (PM_PROVE_GLUE_DEVICE), one lane per proof.
+//   glue_begin     once per call: tap 11 forgotten and sized for `count` proofs
+//   glue_upload    per group, before phase 1: instance_host's rows and r_a go up (rows x m0 x 32 and rows x 64 bytes)
+//   glue_x1        after phase 1: k_glue_x1 -- the records of [a]_1, [c]_1, the transcript, x1 into pb.rows; under `solve` the marker
+//                  entries of the instance are replaced by the row's solved values and a stuck row is refused
+//   glue_x2        after phase 2: k_glue_x2 -- a(x1), c(x1), x2, the whole phase-3 record into pb.rows, tap 11 of proofs g0 ...
+//   glue_finish    after phase 3: k_proof_bytes, then the group's ONE copy to the host and ONE synchronisation; proofs / status are the
+//                  group's first row's
+// GPU ms of the three kernels go to T_POLY.
+template <class C>
+int glue_begin(pm_ctx *ctx, const pm_pk *pk, size_t count);
+template <class C>
+int glue_upload(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *instance_host, const uint64_t *r_a, size_t proof_len);
+template <class C>
+int glue_x1(pm_ctx *ctx, const pm_pk *pk, int transcript, size_t rows, bool solve);
+template <class C>
+int glue_x2(pm_ctx *ctx, const pm_pk *pk, int transcript, size_t rows, size_t g0);
+template <class C>
+int glue_finish(pm_ctx *ctx, const pm_pk *pk, size_t rows, bool solve, uint8_t *proofs, size_t proof_len, int *status);
 
 // the group's [rows][m0 + mw] assignment buffer (pm_ctx::pb.xw), reserved: what prove_batch_phase1 reads with xw_resident
 template <class C>

@@ -1127,12 +1127,6 @@ static void host_finish(const XYZZ<C> &acc, Affine<C> *out, int *inf) {
 // structured inputs (bases G, 2G, 3G ..., equal or opposite rows) coincide, cancel or are O: every addition is xyzz28_add_full, which
 // hands P = +-Q to the complete dense formulas; xyzz28_dbl is complete (no point of order 2); O is ZZ == 0 in every limb throughout.
 template <class C>
-struct BatchPoint {
-    Affine<C> p;
-    uint32_t inf;
-};
-
-template <class C>
 __global__ __launch_bounds__(64) void k_window_combine(const XYZZ<C> *sums, unsigned nwin, unsigned c, unsigned rows, BatchPoint<C> *out) {
     typedef typename C::FqRR RR;
     const unsigned row = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1360,24 +1354,34 @@ int msm_run(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_
 // pipeline handles nwin independent bucket sets, every stage indexed by set, and sorted[] holds plain base indices: a group of `rows`
 // rows is the same pipeline over rows * nwin sets -- set s = b * nwin + w owns digits [s * len, (s + 1) * len) -- planned once for
 // `len` and scaled.  New are the digits over (row, i) (k_digits_batch) and the final combine on the device (k_window_combine): one
-// copy of rows x (point, flag) ends a group; the host neither doubles nor inverts.
+// record of (point, flag) per row comes out of a group; the host neither doubles nor inverts.
 // A group is as many whole rows as keep rows * len <= msm_max_piece(), rows * nwin <= 65 535 (grid y of k_hist / k_scatter) and
 // E, NB < 2^32 (u32 positions); further groups reuse the workspace in stream order.  A row longer than one piece runs row by row
 // through msm_run.  Window tables and wide plans are NOT used here: the points are the plain resident array (pm_bases keeps it
 // beside its tables), so a precomputed pm_bases gives the same points, at the per-window pipeline's 16+ additions per pair.
 // NOT yet measured against a loop of msm_run (tools/msm_bench.py --batch does it): DESIGN.md §4.2 "Batched MSM", profiles/msm_batch.txt.
+//
+// The device form leaves row b's (point, flag) record in d_out[b], an array of the caller's in device memory, and returns with
+// everything ENQUEUED on ctx->stream: no copy to the host, no synchronisation, the batch's internal groups stream-ordered on the one
+// workspace.  It takes rows of at most one piece (a longer row needs the host between its pieces: PM_ERR_INVALID_ARG).  The host form
+// is the device form into the workspace's own array plus one copy and one synchronisation for the whole batch.
 template <class C>
-int msm_run_batch(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_scalars, size_t len, size_t batch, Affine<C> *h_out,
-                  int *h_inf) {
+__global__ void k_batch_points_identity(BatchPoint<C> *out, unsigned rows) {
+    const unsigned row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= rows) return;
+    out[row].p = Affine<C>::infinity();
+    out[row].inf = 1u;
+}
+
+template <class C>
+int msm_run_batch_device(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_scalars, size_t len, size_t batch, BatchPoint<C> *d_out) {
+    if (batch == 0) return PM_OK;
     if (len == 0) {
-        for (size_t b = 0; b < batch; ++b) { h_out[b] = Affine<C>::infinity(); h_inf[b] = 1; }
+        PM_LAUNCH(ctx, k_batch_points_identity<C>, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, ctx->stream, d_out, (unsigned)batch);
         return PM_OK;
     }
     const size_t max_piece = msm_max_piece(ctx);
-    if (len > max_piece) {
-        for (size_t b = 0; b < batch; ++b) PM_TRY(msm_run<C>(ctx, d_bases, d_scalars + b * len, len, h_out + b, h_inf + b));
-        return PM_OK;
-    }
+    if (len > max_piece || batch > 0xFFFFFFFFull) return PM_ERR_INVALID_ARG;
     BucketPlan row;
     if (!bucket_plan(WindowLayout(), len, (unsigned)C::FrP::BITS, ctx->opt.v[PM_OPT_MSM_TASK_LEN], row)) return PM_ERR_INVALID_ARG;
     const size_t u32_max = 0xFFFFFFFFull;
@@ -1389,12 +1393,9 @@ int msm_run_batch(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::Fr
     if (group < 1) return PM_ERR_INVALID_ARG;
 
     MsmWorkspace &ws = ctx->msm;
-    const size_t flag_bytes = (len + 15) & ~(size_t)15;
-    PM_HIP(ctx, ws.batch.reserve(flag_bytes + group * sizeof(BatchPoint<C>)));
+    PM_HIP(ctx, ws.batch.reserve(batch_flag_bytes(len)));      // (the host form has reserved its records behind the flags: no-op then)
     unsigned char *d_inf = ws.batch.as<unsigned char>();
-    BatchPoint<C> *d_res = (BatchPoint<C> *)(d_inf + flag_bytes);
     PM_TRY(infinity_flags<C>(ctx, d_bases, len, d_inf));
-    std::vector<BatchPoint<C>> res(group);
     for (size_t b0 = 0; b0 < batch; b0 += group) {
         StageTimer t_total(ctx, T_MSM_TOTAL);
         const size_t rows = batch - b0 < group ? batch - b0 : group;
@@ -1422,12 +1423,32 @@ int msm_run_batch(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::Fr
             XYZZ<C> *d_sums = nullptr;
             PM_TRY(reduce_single_level<C>(ctx, S, p, &d_sums));
             PM_LAUNCH(ctx, k_window_combine<C>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, ctx->stream, d_sums, p.nwin, p.c,
-                           (unsigned)rows, d_res);
+                           (unsigned)rows, d_out + b0);
         }
-        PM_HIP(ctx, hipMemcpyAsync(res.data(), d_res, rows * sizeof(BatchPoint<C>), hipMemcpyDeviceToHost, ctx->stream));
-        PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (size_t r = 0; r < rows; ++r) { h_out[b0 + r] = res[r].p; h_inf[b0 + r] = (int)res[r].inf; }
     }
+    return PM_OK;
+}
+
+template <class C>
+int msm_run_batch(pm_ctx *ctx, const Affine<C> *d_bases, const Fp<typename C::FrP> *d_scalars, size_t len, size_t batch, Affine<C> *h_out,
+                  int *h_inf) {
+    if (len == 0) {
+        for (size_t b = 0; b < batch; ++b) { h_out[b] = Affine<C>::infinity(); h_inf[b] = 1; }
+        return PM_OK;
+    }
+    if (len > msm_max_piece(ctx)) {
+        for (size_t b = 0; b < batch; ++b) PM_TRY(msm_run<C>(ctx, d_bases, d_scalars + b * len, len, h_out + b, h_inf + b));
+        return PM_OK;
+    }
+    if (batch == 0) return PM_OK;
+    const size_t flag_bytes = batch_flag_bytes(len);
+    PM_HIP(ctx, ctx->msm.batch.reserve(flag_bytes + batch * sizeof(BatchPoint<C>)));
+    BatchPoint<C> *d_res = (BatchPoint<C> *)(ctx->msm.batch.as<unsigned char>() + flag_bytes);
+    PM_TRY(msm_run_batch_device<C>(ctx, d_bases, d_scalars, len, batch, d_res));
+    std::vector<BatchPoint<C>> res(batch);
+    PM_HIP(ctx, hipMemcpyAsync(res.data(), d_res, batch * sizeof(BatchPoint<C>), hipMemcpyDeviceToHost, ctx->stream));
+    PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t r = 0; r < batch; ++r) { h_out[r] = res[r].p; h_inf[r] = (int)res[r].inf; }
     return PM_OK;
 }
 
@@ -1476,6 +1497,8 @@ template int msm_end<BlsCurve>(pm_ctx *, Affine<BlsCurve> *, int *);
 template int msm_end<BnCurve>(pm_ctx *, Affine<BnCurve> *, int *);
 template int msm_run<BlsCurve>(pm_ctx *, const Affine<BlsCurve> *, const Fp<BlsFrP> *, size_t, Affine<BlsCurve> *, int *, const MsmTables *);
 template int msm_run<BnCurve>(pm_ctx *, const Affine<BnCurve> *, const Fp<BnFrP> *, size_t, Affine<BnCurve> *, int *, const MsmTables *);
+template int msm_run_batch_device<BlsCurve>(pm_ctx *, const Affine<BlsCurve> *, const Fp<BlsFrP> *, size_t, size_t, BatchPoint<BlsCurve> *);
+template int msm_run_batch_device<BnCurve>(pm_ctx *, const Affine<BnCurve> *, const Fp<BnFrP> *, size_t, size_t, BatchPoint<BnCurve> *);
 template int msm_run_batch<BlsCurve>(pm_ctx *, const Affine<BlsCurve> *, const Fp<BlsFrP> *, size_t, size_t, Affine<BlsCurve> *, int *);
 template int msm_run_batch<BnCurve>(pm_ctx *, const Affine<BnCurve> *, const Fp<BnFrP> *, size_t, size_t, Affine<BnCurve> *, int *);
 

@@ -6,8 +6,11 @@
 // The kernels are prove_kernels.cuh's, the ones prove.hip launches for one proof, and phase 1 between the uploads and the MSMs is
 // prove.hip's phase1_enqueue_u / phase1_enqueue_rest with rows = the group.  r_a goes up as a [rows][2] array; what else differs
 // from proof to proof (x1, the numerator's constants and reduced-radix multipliers, the division's level multipliers) is one BatchRow
-// record per proof in device memory, uploaded once per phase and indexed by blockIdx.y.  Each proof has its own flag word.
-// A proof whose witness fails a check keeps running (every operation is defined on any field values); the host drops its result.
+// record per proof in device memory (batch_row.cuh), written once per phase and indexed by blockIdx.y.  Each proof has its own flag word.
+// A proof whose witness fails a check keeps running (every operation is defined on any field values); its result is dropped.
+//
+// The phases only enqueue.  Who writes the records and reads the results between them is the caller's glue provider (internal.h): the
+// host, through the fetch / rows functions at the end of this file, or the kernels of prove_glue.hip, which leave the stream alone.
 #include <cstring>
 
 #include "internal.h"
@@ -65,10 +68,16 @@ int prove_batch_group(pm_ctx *ctx, const pm_pk *pk, size_t count, size_t *group)
     return PM_OK;
 }
 
-template <class C>
-static int upload_rows(pm_ctx *ctx, const std::vector<BatchRow<typename C::FrP>> &host) {
-    PM_HIP(ctx, ctx->pb.rows.reserve(host.size() * sizeof(host[0])));
-    PM_HIP(ctx, hipMemcpyAsync(ctx->pb.rows.p, host.data(), host.size() * sizeof(host[0]), hipMemcpyHostToDevice, ctx->stream));
+// the records go up from the context's own staging: the copy is only enqueued, and the staging outlives it (its next writer comes
+// after the phase's synchronisation)
+template <class P>
+static BatchRow<P> *stage_rows(pm_ctx *ctx, size_t rows) {
+    ctx->gw.rows_host.assign(rows * sizeof(BatchRow<P>), 0);
+    return (BatchRow<P> *)ctx->gw.rows_host.data();
+}
+static int upload_rows(pm_ctx *ctx) {
+    PM_HIP(ctx, ctx->pb.rows.reserve(ctx->gw.rows_host.size()));
+    PM_HIP(ctx, hipMemcpyAsync(ctx->pb.rows.p, ctx->gw.rows_host.data(), ctx->gw.rows_host.size(), hipMemcpyHostToDevice, ctx->stream));
     return PM_OK;
 }
 
@@ -79,15 +88,35 @@ int prove_batch_xw(pm_ctx *ctx, const pm_pk *pk, size_t rows, Fp<typename C::FrP
     return PM_OK;
 }
 
+// What the glue provider touches between the phases, sized for groups of up to `rows` proofs before the first of them starts: the
+// BatchRow records (phase 1 keeps r_a at their place), the flag words, phase 2's sums, the three arrays of point records.
+template <class C>
+int prove_batch_reserve(pm_ctx *ctx, const pm_pk *pk, size_t rows) {
+    typedef typename C::FrP P;
+    typedef Fp<P> Fr;
+    const ProofShape d = proof_shape(pk);
+    if (rows == 0 || rows > 65535) return PM_ERR_INVALID_ARG;
+    ProveWs &ws = ctx->pb;
+    PM_HIP(ctx, ws.rows.reserve(rows * sizeof(BatchRow<P>)));          // > rows * 2 * sizeof(Fr)
+    PM_HIP(ctx, ws.flags.reserve(rows * sizeof(unsigned)));
+    PM_HIP(ctx, ws.part.reserve(rows * ((size_t)nblk((d.n + HORNER_L - 1) / HORNER_L) + 1) * sizeof(Fr)));
+    PM_HIP(ctx, ctx->gw.pts.reserve(3 * rows * sizeof(BatchPoint<C>)));   // (a record's size is the curve's: the stride is set per call)
+    ctx->gw.cap = rows;
+    return PM_OK;
+}
+
+template <class C>
+static BatchPoint<C> *batch_points(pm_ctx *ctx, int which) { return ctx->gw.pts.as<BatchPoint<C>>() + (size_t)which * ctx->gw.cap; }
+
 // xw_resident: the group's x || w rows are already in the workspace (prove_batch_xw: the witness solver completed them there);
 // x and w are then not read
 template <class C>
 int prove_batch_phase1(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *x, const uint64_t *w, bool assignment_on_device,
-                       const uint64_t *r_a, Affine<C> *a, int *a_inf, Affine<C> *c, int *c_inf, unsigned *flags_out, bool xw_resident) {
+                       const uint64_t *r_a, bool xw_resident) {
     typedef typename C::FrP P;
     typedef Fp<P> Fr;
     const ProofShape d = proof_shape(pk);
-    if (!layout_ok(pk, d) || rows == 0 || rows > 65535) return PM_ERR_INVALID_ARG;
+    if (!layout_ok(pk, d) || rows == 0 || rows > 65535 || rows > ctx->gw.cap) return PM_ERR_INVALID_ARG;
     if (pk->log_n + 1 > (unsigned)C::TWO_ADICITY) return PM_ERR_DOMAIN_TOO_LARGE;  // prover.rs:317
     const uint64_t n = d.n, m0 = d.m0, mw = d.mw, len_a = d.len_a, len_c = d.len_c;
     hipStream_t st = ctx->stream;
@@ -99,7 +128,6 @@ int prove_batch_phase1(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t
     PM_HIP(ctx, ws.u2.reserve(rows * 2 * n * sizeof(Fr)));
     PM_HIP(ctx, ws.sc_c.reserve(rows * len_c * sizeof(Fr)));
     PM_HIP(ctx, ws.sc_a.reserve(rows * len_a * sizeof(Fr)));
-    PM_HIP(ctx, ws.flags.reserve(rows * sizeof(unsigned)));
     Fr *xw = ws.xw.as<Fr>(), *sc_c = ws.sc_c.as<Fr>(), *sc_a = ws.sc_a.as<Fr>();
     unsigned *flags = ws.flags.as<unsigned>();
     PM_HIP(ctx, hipMemsetAsync(flags, 0, rows * sizeof(unsigned), st));
@@ -109,49 +137,46 @@ int prove_batch_phase1(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t
         PM_HIP(ctx, hipMemcpy2DAsync(xw, (m0 + mw) * sizeof(Fr), x, m0 * sizeof(Fr), m0 * sizeof(Fr), rows, kind, st));
         if (mw) PM_HIP(ctx, hipMemcpy2DAsync(xw + m0, (m0 + mw) * sizeof(Fr), w, mw * sizeof(Fr), mw * sizeof(Fr), rows, kind, st));
     }
-    PM_HIP(ctx, ws.rows.reserve(rows * 2 * sizeof(Fr)));      // this phase's per-proof values are r_a alone: [rows][2]
+    // this phase's per-proof values are r_a alone: [rows][2] where the later phases keep their records
     PM_HIP(ctx, hipMemcpyAsync(ws.rows.p, r_a, rows * 2 * sizeof(Fr), hipMemcpyHostToDevice, st));
     PM_TRY(phase1_enqueue_u<C>(ctx, pk, d, ws, rows, true));
     PM_TRY(phase1_enqueue_rest<C>(ctx, pk, d, ws, rows, (Fr *)nullptr));
     // [a]_1 and [c]_1 of every proof of the group: two batches over the key's PLAIN points (no tables, no wide plan)
     const Affine<C> *bases = (const Affine<C> *)pk->d_bases;
-    PM_TRY(msm_run_batch<C>(ctx, bases + pk->res_dev_off[0], sc_a, (size_t)len_a, rows, a, a_inf));
-    PM_TRY(msm_run_batch<C>(ctx, bases + pk->res_dev_off[1], sc_c, (size_t)len_c, rows, c, c_inf));
-    PM_HIP(ctx, hipMemcpyAsync(flags_out, flags, rows * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    PM_HIP(ctx, hipStreamSynchronize(st));
+    PM_TRY(msm_run_batch_device<C>(ctx, bases + pk->res_dev_off[0], sc_a, (size_t)len_a, rows, batch_points<C>(ctx, 0)));
+    PM_TRY(msm_run_batch_device<C>(ctx, bases + pk->res_dev_off[1], sc_c, (size_t)len_c, rows, batch_points<C>(ctx, 1)));
     return PM_OK;
 }
 
 template <class C>
-int prove_batch_phase2(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *x1, uint64_t *u_at_x1) {
+const Fp<typename C::FrP> *prove_batch_sums(pm_ctx *ctx, const pm_pk *pk, size_t rows) {
+    const ProofShape d = proof_shape(pk);
+    return ctx->pb.part.as<Fp<typename C::FrP>>() + rows * nblk((d.n + HORNER_L - 1) / HORNER_L);
+}
+
+template <class C>
+int prove_batch_phase2(pm_ctx *ctx, const pm_pk *pk, size_t rows) {
     typedef typename C::FrP P;
     typedef Fp<P> Fr;
     const ProofShape d = proof_shape(pk);
     if (rows == 0 || rows > 65535) return PM_ERR_INVALID_ARG;
     hipStream_t st = ctx->stream;
     ProveWs &ws = ctx->pb;
-    std::vector<BatchRow<P>> par(rows);
-    memset((void *)par.data(), 0, rows * sizeof(BatchRow<P>));
-    for (size_t b = 0; b < rows; ++b) par[b].x1 = load_fr<P>(x1 + 4 * b);
-    PM_TRY(upload_rows<C>(ctx, par));
     const uint64_t lanes = (d.n + HORNER_L - 1) / HORNER_L;
     const unsigned blocks = nblk(lanes);
     PM_HIP(ctx, ws.part.reserve(rows * ((size_t)blocks + 1) * sizeof(Fr)));
     Fr *part = ws.part.as<Fr>(), *sums = part + rows * blocks;
     PM_LAUNCH(ctx, k_horner_partial_rows<P>, dim3(blocks, (unsigned)rows), dim3(256), 0, st, ws.u.as<Fr>(), d.n, ws.rows.as<BatchRow<P>>(), HORNER_L, part);
     PM_LAUNCH(ctx, k_sum_small<P>, dim3((unsigned)rows), dim3(256), 0, st, part, blocks, sums);
-    PM_HIP(ctx, hipMemcpyAsync(u_at_x1, sums, rows * sizeof(Fr), hipMemcpyDeviceToHost, st));
-    PM_HIP(ctx, hipStreamSynchronize(st));
     return PM_OK;
 }
 
 template <class C>
-int prove_batch_phase3(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *r_a, const uint64_t *x1_in, const uint64_t *x2_in,
-                       const uint64_t *a_in, const uint64_t *c_in, Affine<C> *dpt, int *d_inf, unsigned *flags_out) {
+int prove_batch_phase3(pm_ctx *ctx, const pm_pk *pk, size_t rows) {
     typedef typename C::FrP P;
     typedef Fp<P> Fr;
     const ProofShape d = proof_shape(pk);
-    if (!layout_ok(pk, d) || rows == 0 || rows > 65535) return PM_ERR_INVALID_ARG;
+    if (!layout_ok(pk, d) || rows == 0 || rows > 65535 || rows > ctx->gw.cap) return PM_ERR_INVALID_ARG;
     const unsigned gy = (unsigned)rows, L = DIV_L;
     const int levels = d.levels;
     hipStream_t st = ctx->stream;
@@ -159,18 +184,6 @@ int prove_batch_phase3(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t
     StageTimer t_phase(ctx, T_PHASE);
     ProveWs &ws = ctx->pb;
     NumParams np{d.n, d.sigma, d.num_len};
-    std::vector<BatchRow<P>> par(rows);
-    memset((void *)par.data(), 0, rows * sizeof(BatchRow<P>));
-    for (size_t b = 0; b < rows; ++b) {
-        BatchRow<P> &R = par[b];
-        const Fr ra[2] = {load_fr<P>(r_a + 8 * b), load_fr<P>(r_a + 8 * b + 4)};
-        R.x1 = load_fr<P>(x1_in + 4 * b);
-        R.nc = make_num_consts<P>(load_fr<P>(x2_in + 4 * b), ra, load_fr<P>(a_in + 4 * b), load_fr<P>(c_in + 4 * b));
-        R.m28 = make_num_mul28<P>(R.x1, R.nc);
-        R.xp[0] = R.x1;
-        for (int l = 1; l <= levels; ++l) R.xp[l] = pow_u64<P>(R.xp[l - 1], L);
-    }
-    PM_TRY(upload_rows<C>(ctx, par));
     const BatchRow<P> *drows = ws.rows.as<BatchRow<P>>();
     DivLevels<Fr> lv;
     PM_HIP(ctx, div_levels_reserve(ws, d, rows, lv));
@@ -201,20 +214,79 @@ int prove_batch_phase3(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t
                            d.len_d, flags);
         }
     }
-    PM_TRY(msm_run_batch<C>(ctx, (const Affine<C> *)pk->d_bases + pk->res_dev_off[2], q, (size_t)d.len_d, rows, dpt, d_inf));   // [d]_1 = M8
-    PM_HIP(ctx, hipMemcpyAsync(flags_out, flags, rows * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    PM_HIP(ctx, hipStreamSynchronize(st));
+    return msm_run_batch_device<C>(ctx, (const Affine<C> *)pk->d_bases + pk->res_dev_off[2], q, (size_t)d.len_d, rows, batch_points<C>(ctx, 2));   // [d]_1 = M8
+}
+
+// ------------------------------------------------------------------------------- the host as glue provider
+// `n_pts` arrays of point records starting with array `first`, and the flag words: enqueued copies, then the phase's synchronisation
+template <class C>
+static int fetch_points(pm_ctx *ctx, size_t rows, int first, int n_pts, Affine<C> *const *pt, int *const *inf, unsigned *flags_out) {
+    std::vector<BatchPoint<C>> res((size_t)n_pts * rows);
+    for (int k = 0; k < n_pts; ++k)
+        PM_HIP(ctx, hipMemcpyAsync(res.data() + k * rows, batch_points<C>(ctx, first + k), rows * sizeof(BatchPoint<C>), hipMemcpyDeviceToHost, ctx->stream));
+    PM_HIP(ctx, hipMemcpyAsync(flags_out, ctx->pb.flags.p, rows * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < n_pts; ++k)
+        for (size_t r = 0; r < rows; ++r) { pt[k][r] = res[k * rows + r].p; inf[k][r] = (int)res[k * rows + r].inf; }
     return PM_OK;
+}
+
+template <class C>
+int prove_batch_fetch1(pm_ctx *ctx, size_t rows, Affine<C> *a, int *a_inf, Affine<C> *c, int *c_inf, unsigned *flags_out) {
+    Affine<C> *const pt[2] = {a, c};
+    int *const inf[2] = {a_inf, c_inf};
+    return fetch_points<C>(ctx, rows, 0, 2, pt, inf, flags_out);
+}
+
+template <class C>
+int prove_batch_fetch3(pm_ctx *ctx, size_t rows, Affine<C> *dpt, int *d_inf, unsigned *flags_out) {
+    return fetch_points<C>(ctx, rows, 2, 1, &dpt, &d_inf, flags_out);
+}
+
+template <class C>
+int prove_batch_rows2(pm_ctx *ctx, size_t rows, const uint64_t *x1) {
+    typedef typename C::FrP P;
+    BatchRow<P> *par = stage_rows<P>(ctx, rows);
+    for (size_t b = 0; b < rows; ++b) par[b].x1 = load_fr<P>(x1 + 4 * b);
+    return upload_rows(ctx);
+}
+
+template <class C>
+int prove_batch_fetch2(pm_ctx *ctx, const pm_pk *pk, size_t rows, uint64_t *u_at_x1) {
+    typedef Fp<typename C::FrP> Fr;
+    PM_HIP(ctx, hipMemcpyAsync(u_at_x1, prove_batch_sums<C>(ctx, pk, rows), rows * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PM_OK;
+}
+
+template <class C>
+int prove_batch_rows3(pm_ctx *ctx, const pm_pk *pk, size_t rows, const uint64_t *r_a, const uint64_t *x1_in, const uint64_t *x2_in,
+                      const uint64_t *a_in, const uint64_t *c_in) {
+    typedef typename C::FrP P;
+    typedef Fp<P> Fr;
+    const int levels = proof_shape(pk).levels;
+    BatchRow<P> *par = stage_rows<P>(ctx, rows);
+    for (size_t b = 0; b < rows; ++b) {
+        const Fr ra[2] = {load_fr<P>(r_a + 8 * b), load_fr<P>(r_a + 8 * b + 4)};
+        fill_batch_row<P>(par[b], load_fr<P>(x1_in + 4 * b), load_fr<P>(x2_in + 4 * b), ra, load_fr<P>(a_in + 4 * b), load_fr<P>(c_in + 4 * b), levels);
+    }
+    return upload_rows(ctx);
 }
 
 #define PM_INST(C)                                                                                                                          \
     template int prove_batch_group<C>(pm_ctx *, const pm_pk *, size_t, size_t *);                                                           \
     template int prove_batch_xw<C>(pm_ctx *, const pm_pk *, size_t, Fp<typename C::FrP> **);                                                \
-    template int prove_batch_phase1<C>(pm_ctx *, const pm_pk *, size_t, const uint64_t *, const uint64_t *, bool, const uint64_t *,         \
-                                       Affine<C> *, int *, Affine<C> *, int *, unsigned *, bool);                                          \
-    template int prove_batch_phase2<C>(pm_ctx *, const pm_pk *, size_t, const uint64_t *, uint64_t *);                                      \
-    template int prove_batch_phase3<C>(pm_ctx *, const pm_pk *, size_t, const uint64_t *, const uint64_t *, const uint64_t *,              \
-                                       const uint64_t *, const uint64_t *, Affine<C> *, int *, unsigned *);
+    template int prove_batch_reserve<C>(pm_ctx *, const pm_pk *, size_t);                                                                   \
+    template int prove_batch_phase1<C>(pm_ctx *, const pm_pk *, size_t, const uint64_t *, const uint64_t *, bool, const uint64_t *, bool);  \
+    template int prove_batch_phase2<C>(pm_ctx *, const pm_pk *, size_t);                                                                    \
+    template int prove_batch_phase3<C>(pm_ctx *, const pm_pk *, size_t);                                                                    \
+    template const Fp<typename C::FrP> *prove_batch_sums<C>(pm_ctx *, const pm_pk *, size_t);                                               \
+    template int prove_batch_fetch1<C>(pm_ctx *, size_t, Affine<C> *, int *, Affine<C> *, int *, unsigned *);                               \
+    template int prove_batch_rows2<C>(pm_ctx *, size_t, const uint64_t *);                                                                  \
+    template int prove_batch_fetch2<C>(pm_ctx *, const pm_pk *, size_t, uint64_t *);                                                        \
+    template int prove_batch_rows3<C>(pm_ctx *, const pm_pk *, size_t, const uint64_t *, const uint64_t *, const uint64_t *,               \
+                                      const uint64_t *, const uint64_t *);                                                                  \
+    template int prove_batch_fetch3<C>(pm_ctx *, size_t, Affine<C> *, int *, unsigned *);
 PM_INST(BlsCurve)
 PM_INST(BnCurve)
 

@@ -4,6 +4,7 @@
 
 #include "internal.h"
 #include "fq28.cuh"
+#include "batch_row.cuh"
 
 namespace pm {
 
@@ -44,14 +45,8 @@ struct NumParams {
     uint64_t n, sigma, len;
 };
 
-template <class P>
-struct NumConsts {
-    Fp<P> x2, r0, r1, x2r0, x2r1, b2[3], two_x2_r0, two_x2_r1, minus_const;
-};
-
 // The lengths of one proof's vectors on an unsharded key, and the level plan of the division scan (prove_kernels.cuh): level l holds
 // cnt[l] values, DIV_L of them per lane, until the top level is <= 64 values for one lane (16^6 covers every domain of both curves).
-constexpr unsigned DIV_L = 16;      // 16 puts 20 K waves on the chip at 2^20 (32: 10 K, half of its wave slots idle): 0.98 -> 0.90 ms
 constexpr unsigned HORNER_L = 16;   // coefficients per lane of the phase-2 Horner sum
 struct ProofShape {
     uint64_t n, m0, mw, nr, sigma;
@@ -100,12 +95,12 @@ static inline hipError_t div_levels_reserve(ProveWs &ws, const ProofShape &d, si
 }
 
 // The flag word of a proof (k_check_sap) as a status.  Phase 1 reads bits 0-2, phase 3 bit 3.
-static inline int phase1_flag_status(unsigned flags) {
+__host__ __device__ static inline int phase1_flag_status(unsigned flags) {
     if (flags & 1u) return PM_ERR_REMAINDER_NONZERO;                  // prover.rs:108
     if ((flags & 2u) || !(flags & 4u)) return PM_ERR_DEGREE_BOUND;    // prover.rs:107
     return PM_OK;
 }
-static inline int phase3_flag_status(unsigned flags) { return (flags & 8u) ? PM_ERR_REMAINDER_NONZERO : PM_OK; }   // prover.rs:221
+__host__ __device__ static inline int phase3_flag_status(unsigned flags) { return (flags & 8u) ? PM_ERR_REMAINDER_NONZERO : PM_OK; }   // prover.rs:221
 
 // ------------------------------------------------------------------------------- helpers
 template <class P>
@@ -171,24 +166,6 @@ static inline int stage_flags(pm_ctx *ctx, const unsigned *d_flags, volatile uns
 }
 
 
-// the constants of the numerator (prover.rs:145-197) from the challenges and r_a
-template <class P>
-static inline NumConsts<P> make_num_consts(const Fp<P> &x2, const Fp<P> rah[2], const Fp<P> &a_at, const Fp<P> &c_at) {
-    NumConsts<P> nc;
-    nc.x2 = x2;
-    nc.r0 = rah[0];
-    nc.r1 = rah[1];
-    nc.x2r0 = mul<P>(x2, rah[0]);
-    nc.x2r1 = mul<P>(x2, rah[1]);
-    nc.b2[0] = add<P>(rah[0], mul<P>(x2, sqr<P>(rah[0])));
-    nc.b2[1] = add<P>(rah[1], mul<P>(x2, dbl<P>(mul<P>(rah[0], rah[1]))));
-    nc.b2[2] = mul<P>(x2, sqr<P>(rah[1]));
-    nc.two_x2_r0 = dbl<P>(nc.x2r0);
-    nc.two_x2_r1 = dbl<P>(nc.x2r1);
-    nc.minus_const = neg<P>(add<P>(a_at, mul<P>(x2, c_at)));
-    return nc;
-}
-
 // ------------------------------------------------------------- numerator + division (phase 3)
 // Numerator of prover.rs:211-216, multiplied through by Y^-gamma = X^(5 sigma), as a function of
 // the coefficient index k (never materialised):
@@ -227,28 +204,7 @@ __device__ __forceinline__ Fp<P> numerator_at(uint64_t k, const NumParams &np, c
     return Fp<P>::zero();
 }
 
-// Round 5: the two kernels that walk the numerator -- k_div_level0 and k_div_expand0, 0.77 of the scan's 0.89 ms -- run their Horner
-// chains in REDUCED RADIX (fq28.cuh: 9 limbs of 29 bits), as the transform tiles do: the multipliers x1, x2, 2 x2 r_a are handed over
-// in the internal Montgomery form (value 2^261 mod p), so that f28_mul(standard-form value, multiplier) is again a standard-form
-// value, sums are limb-wise, and a dense canonical element is only rebuilt where one is STORED.  The dense product mul<P> unpacks both
-// operands and shifts / reduces / packs its result every time: ~370 instructions for 162 multiplier operations against ~200.
-// Values are the same residues, the stored elements the same canonical words.
-template <class RR>
-struct NumMul28 {
-    F28<RR> x1, x2, two_x2_r0, two_x2_r1;      // internal form, canonical, tight limbs
-};
-template <class P>
-static inline NumMul28<typename Radix28<P>::RR> make_num_mul28(const Fp<P> &x1, const NumConsts<P> &nc) {
-    typedef typename Radix28<P>::RR RR;
-    Fp<P> k;
-    for (int i = 0; i < P::N; ++i) k.l[i] = RR::STD2INT[i];
-    NumMul28<RR> m;
-    m.x1 = f28_unpack<RR>(mul<P>(x1, k).l);
-    m.x2 = f28_unpack<RR>(mul<P>(nc.x2, k).l);
-    m.two_x2_r0 = f28_unpack<RR>(mul<P>(nc.two_x2_r0, k).l);
-    m.two_x2_r1 = f28_unpack<RR>(mul<P>(nc.two_x2_r1, k).l);
-    return m;
-}
+// (batch_row.cuh: NumMul28 -- the Horner chains of the two kernels that walk the numerator run in reduced radix)
 // numerator_at on reduced-radix limbs: a LAZY standard-form value, limbs < 4 * 2^29, value < 7p (u + two products + a constant)
 template <class P, class RR>
 __device__ __forceinline__ F28<RR> numerator28_at(uint64_t k, const NumParams &np, const NumConsts<P> &nc, const NumMul28<RR> &m, const Fp<P> *u,

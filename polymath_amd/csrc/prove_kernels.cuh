@@ -4,22 +4,13 @@
 // Kernels whose arguments are the same for every proof take the proof as blockIdx.y and explicit row strides; prove.hip launches them
 // with grid y = 1.  Where a value differs from proof to proof (x1, the numerator's constants and reduced-radix multipliers, the
 // division's level multipliers) the body is a __device__ function on one proof's pointers and values with two entry points: `k_x`
-// takes the values as kernel arguments (prove.hip), `k_x_rows` reads them from the BatchRow record of row blockIdx.y (prove_batch.hip).
+// takes the values as kernel arguments (prove.hip), `k_x_rows` reads them from the BatchRow record (batch_row.cuh) of row blockIdx.y (prove_batch.hip).
 #pragma once
 #include "internal.h"
 #include "fq28.cuh"
 #include "prove_common.cuh"
 
 namespace pm {
-
-// what differs from proof to proof in phases 2 and 3, one record per row in device memory (uniform per workgroup: scalar loads)
-template <class P>
-struct BatchRow {
-    Fp<P> x1;
-    NumConsts<P> nc;
-    NumMul28<typename Radix28<P>::RR> m28;
-    Fp<P> xp[8];          // xp[l] = x1^(DIV_L^l): the multiplier of level l of the division scan
-};
 
 // ------------------------------------------------------------------------------- witness map
 template <class P>

@@ -1,5 +1,5 @@
-// The reference's three Fiat-Shamir transcripts (src/transcript/{merlin,keccak256,blake3}.rs) and the verifier's challenges
-// (src/verifier.rs:24-42 with src/common.rs:21-98) as PM_HD code: fixed-size, streaming restatements of host/hashes.hpp and of the
+// The reference's three Fiat-Shamir transcripts (src/transcript/{merlin,keccak256,blake3}.rs), the verifier's challenges
+// (src/verifier.rs:24-42 with src/common.rs:21-98) and the prover's (src/prover.rs:125-138, 189) as PM_HD code: fixed-size, streaming restatements of host/hashes.hpp and of the
 // transcript classes and Polymath::verifier_challenges of host/polymath.hpp -- those two files are the specification, bit for bit
 // (tests/native/transcript_selftest.cpp compares every piece on the CPU).  No allocation: each state is a POD that one lane owns,
 // and no message is ever laid out as one buffer -- the pieces (label bytes, a u64 length prefix, an Fr as its 32 canonical bytes,
@@ -464,17 +464,56 @@ PM_HD Fp<typename C::FrP> fs_lagrange_sum(const FsVk<C> &vk, const Fp<typename C
     return sum;
 }
 
+// The two halves of the transcript that the prover and the verifier share (common.rs:21-37), on a transcript the caller owns:
+// fs_absorb_x1 starts it (prover.rs:125 / verifier.rs:24), hashes the public inputs -- `first` and then inputs[0 .. n_inputs): the
+// verifier's `first` is one, the prover's is element 0 of its instance -- and the compressed records of [a]_1 and [c]_1 (4 * C::FqP::N
+// bytes each), and draws x1; fs_absorb_x2 continues the same transcript with x1, a(x1), c(x1) and draws x2.
+template <class C, class T>
+PM_HD Fp<typename C::FrP> fs_absorb_x1(T &t, const Fp<typename C::FrP> &first, const Fp<typename C::FrP> *inputs, size_t n_inputs, const uint8_t *a_rec,
+                                       const uint8_t *c_rec) {
+    constexpr size_t NB = 4 * C::FqP::N;
+    const uint8_t l_pub[13] = {'p', 'u', 'b', 'l', 'i', 'c', '_', 'i', 'n', 'p', 'u', 't', 's'};
+    const uint8_t l_com[11] = {'c', 'o', 'm', 'm', 'i', 't', 'm', 'e', 'n', 't', 's'}, l_x1[2] = {'x', '1'};
+    t.init();
+    const size_t m0 = n_inputs + 1;
+    t.begin_message(l_pub, 13, 8 + 32 * m0);                            // common.rs:21-30
+    t.put_le(m0, 8);
+    put_fr<C>(t, first);
+    for (size_t i = 0; i < n_inputs; ++i) put_fr<C>(t, inputs[i]);
+    t.begin_message(l_com, 11, 8 + 2 * NB);
+    t.put_le(2, 8);
+    put_bytes(t, a_rec, NB);
+    put_bytes(t, c_rec, NB);
+    return t.challenge(l_x1, 2);
+}
+template <class C, class T>
+PM_HD Fp<typename C::FrP> fs_absorb_x2(T &t, const Fp<typename C::FrP> &x1, const Fp<typename C::FrP> &a_at_x1, const Fp<typename C::FrP> &c_at_x1) {
+    const uint8_t l_val[6] = {'v', 'a', 'l', 'u', 'e', 's'}, l_x1[2] = {'x', '1'}, l_x2[2] = {'x', '2'};
+    t.begin_message(l_x1, 2, 32);                                       // common.rs:32-37
+    put_fr<C>(t, x1);
+    t.begin_message(l_val, 6, 8 + 64);
+    t.put_le(2, 8);
+    put_fr<C>(t, a_at_x1);
+    put_fr<C>(t, c_at_x1);
+    return t.challenge(l_x2, 2);
+}
+// c(x1) of common.rs:73-75 from a(x1), y1^gamma, pi(x1) and y1: 1 / y1^alpha is y1^3 (alpha = -3), no inversion; 0 for y1 = 0, which is
+// what the host's a^(r-2) gives for 1 / 0
+template <class P>
+PM_HD Fp<P> fs_c_at_x1(const Fp<P> &a_at, const Fp<P> &y1_gamma, const Fp<P> &pi_at_x1, const Fp<P> &y1) {
+    const Fp<P> y1_alpha_inv = mul<P>(sqr<P>(y1), y1);
+    return mul<P>(sub<P>(mul<P>(add<P>(a_at, y1_gamma), a_at), pi_at_x1), y1_alpha_inv);
+}
+
 // Polymath::verifier_challenges (host/polymath.hpp; verifier.rs:24-42) for one proof: a_rec / c_rec are the compressed records of
 // [a]_1 and [c]_1 (4 * C::FqP::N bytes each, hashed as they arrived), a_at_x1_bytes the 32 little-endian bytes of a(x1), inputs
 // the public inputs without the leading one (Montgomery).  false, nothing computed, when a_at_x1 >= r (what
-// FrOps::from_le_bytes_canonical refuses).  1 / y1^alpha is y1^3 (alpha = -3): no inversion; 1 / y1 comes out of the Lagrange
-// sum's first chunk.
+// FrOps::from_le_bytes_canonical refuses).  1 / y1 comes out of the Lagrange sum's first chunk.
 template <class C, int KIND>
 PM_HD bool fs_verifier_challenges(const FsVk<C> &vk, const Fp<typename C::FrP> *inputs, size_t n_inputs, const uint8_t *a_rec, const uint8_t *c_rec,
                                   const uint8_t *a_at_x1_bytes, FsChallenges<C> *out, Fp<typename C::FrP> *a_at_x1_out) {
     typedef typename C::FrP P;
     typedef Fp<P> Fr;
-    constexpr size_t NB = 4 * C::FqP::N;
     Fr a_at;
     for (int i = 0; i < 4; ++i) {
         const uint64_t v = load_le(a_at_x1_bytes + 8 * i, 8);
@@ -485,40 +524,59 @@ PM_HD bool fs_verifier_challenges(const FsVk<C> &vk, const Fp<typename C::FrP> *
     a_at = to_mont<P>(a_at);
     *a_at_x1_out = a_at;
 
-    const uint8_t l_pub[13] = {'p', 'u', 'b', 'l', 'i', 'c', '_', 'i', 'n', 'p', 'u', 't', 's'};
-    const uint8_t l_com[11] = {'c', 'o', 'm', 'm', 'i', 't', 'm', 'e', 'n', 't', 's'};
-    const uint8_t l_val[6] = {'v', 'a', 'l', 'u', 'e', 's'}, l_x1[2] = {'x', '1'}, l_x2[2] = {'x', '2'};
     Transcript<C, KIND> t;
-    t.init();                                                           // verifier.rs:24
-    const size_t m0 = n_inputs + 1;
-    t.begin_message(l_pub, 13, 8 + 32 * m0);                            // common.rs:21-30
-    t.put_le(m0, 8);
-    put_fr<C>(t, Fr::one());
-    for (size_t i = 0; i < n_inputs; ++i) put_fr<C>(t, inputs[i]);
-    t.begin_message(l_com, 11, 8 + 2 * NB);
-    t.put_le(2, 8);
-    put_bytes(t, a_rec, NB);
-    put_bytes(t, c_rec, NB);
-    const Fr x1 = t.challenge(l_x1, 2);
-
+    const Fr x1 = fs_absorb_x1<C>(t, Fr::one(), inputs, n_inputs, a_rec, c_rec);   // verifier.rs:24-29
     const Fr y1 = pow_u64<P>(x1, vk.sigma);                             // verifier.rs:32
     Fr y1_inv;
     const Fr lag = fs_lagrange_sum<C>(vk, inputs, n_inputs, x1, y1, &y1_inv);
     const Fr y1_gamma = pow_u64<P>(y1_inv, 5);                          // :34, MINUS_GAMMA
     const Fr pi_at_x1 = mul<P>(lag, y1_gamma);                          // :35
-    const Fr y1_alpha_inv = mul<P>(sqr<P>(y1), y1);                     // 1 / y1_inv^3 (:37, MINUS_ALPHA); 0 for y1 = 0, as a^(r-2)
-    const Fr c_at_x1 = mul<P>(sub<P>(mul<P>(add<P>(a_at, y1_gamma), a_at), pi_at_x1), y1_alpha_inv);   // :40
-
-    t.begin_message(l_x1, 2, 32);                                       // common.rs:32-37
-    put_fr<C>(t, x1);
-    t.begin_message(l_val, 6, 8 + 64);
-    t.put_le(2, 8);
-    put_fr<C>(t, a_at);
-    put_fr<C>(t, c_at_x1);
+    const Fr c_at_x1 = fs_c_at_x1<P>(a_at, y1_gamma, pi_at_x1, y1);     // :37-40
     out->x1 = x1;
     out->c_at_x1 = c_at_x1;
-    out->x2 = t.challenge(l_x2, 2);                                     // verifier.rs:42
+    out->x2 = fs_absorb_x2<C>(t, x1, a_at, c_at_x1);                    // verifier.rs:42
     return true;
+}
+
+// ------------------------------------------------------------------------------------------------ the prover's challenges
+// Polymath::glue_x1 / glue_x2 (host/polymath.hpp; prover.rs:125-138, 189) for one proof, in two halves because phase 2 runs between
+// them.  What the first half hands to the second is this record, the transcript included: the sponge is STORED (208 bytes for Merlin
+// and Keccak-256, 888 for BLAKE3), not rebuilt -- rebuilding would hash the 32 m0 + 2 * 48 bytes of the first two messages a second
+// time, which grows with m0, while the record is a fixed few hundred bytes a proof beside vectors of 23 n field elements.
+template <class C, int KIND>
+struct FsProverState {
+    Transcript<C, KIND> t;
+    Fp<typename C::FrP> x1, y1_alpha, y1_gamma;   // Montgomery; y1_alpha = y1^alpha = 1 / y1^3, y1_gamma = 1 / y1^5
+};
+template <class C>
+struct FsProverOut {
+    Fp<typename C::FrP> a_at_x1, pi_at_x1, c_at_x1, x2;
+};
+
+// instance: the m0 hashed public inputs, element 0 (the constant one of a well-formed assignment) included, as the host hashes them.
+// ONE inversion, of y1 = x1^sigma (0 for y1 = 0, as the host's); its third and fifth powers.
+template <class C, int KIND>
+PM_HD void fs_prover_x1(const FsVk<C> &vk, const Fp<typename C::FrP> *instance, size_t m0, const uint8_t *a_rec, const uint8_t *c_rec,
+                        FsProverState<C, KIND> *s) {
+    typedef typename C::FrP P;
+    typedef Fp<P> Fr;
+    s->x1 = fs_absorb_x1<C>(s->t, instance[0], instance + 1, m0 - 1, a_rec, c_rec);   // prover.rs:125-126
+    const Fr y1_inv = inverse<P>(pow_u64<P>(s->x1, vk.sigma));         // :128
+    s->y1_alpha = pow_u64<P>(y1_inv, 3);                                // :130, MINUS_ALPHA
+    s->y1_gamma = pow_u64<P>(y1_inv, 5);                                // :134, MINUS_GAMMA
+}
+// u_at_x1: phase 2's u(x1); r_a: the proof's two blinding coefficients, constant term first
+template <class C, int KIND>
+PM_HD void fs_prover_x2(const FsVk<C> &vk, const Fp<typename C::FrP> *instance, size_t m0, FsProverState<C, KIND> *s, const Fp<typename C::FrP> &u_at_x1,
+                        const Fp<typename C::FrP> r_a[2], FsProverOut<C> *out) {
+    typedef typename C::FrP P;
+    typedef Fp<P> Fr;
+    const Fr ra_at = add<P>(r_a[0], mul<P>(r_a[1], s->x1));
+    out->a_at_x1 = add<P>(u_at_x1, mul<P>(ra_at, s->y1_alpha));         // prover.rs:132
+    Fr none;
+    out->pi_at_x1 = mul<P>(fs_lagrange_sum<C>(vk, instance + 1, m0 - 1, s->x1, Fr::zero(), &none), s->y1_gamma);   // :135
+    out->c_at_x1 = fs_c_at_x1<P>(out->a_at_x1, s->y1_gamma, out->pi_at_x1, pow_u64<P>(s->x1, vk.sigma));          // :138
+    out->x2 = fs_absorb_x2<C>(s->t, s->x1, out->a_at_x1, out->c_at_x1);                                           // :189
 }
 
 }  // namespace fs

@@ -393,7 +393,7 @@ class Polymath:
             raise PolymathProverError(0, rc)
         return data
 
-    def prove_batch(self, pk, circuits_or_limbs, r_as, device_ptrs=None, solve=False):
+    def prove_batch(self, pk, circuits_or_limbs, r_as, device_ptrs=None, solve=False, glue="host"):
         """Many assignments of one circuit against one unsharded key in ONE native call (pm_host_prove_batch: every stage of the
         prover with the proof as a grid dimension, three batched MSMs per group of proofs).  circuits_or_limbs[i]: a circuit, a
         LimbCircuit or an (x_limbs, w_limbs) pair; r_as[i] = [r0, r1].  device_ptrs = (d_x, d_w): the assignments are already in HBM
@@ -402,7 +402,8 @@ class Polymath:
         assignment gets the status prove_native raises for it and leaves its neighbours alone).
         solve=True: circuits_or_limbs[i] is an (x_limbs, w_limbs) pair -- or partial_limbs(...) -- whose UNKNOWN entries the device
         computes first (PM_ASSIGNMENT_SOLVE); a stuck assignment gets status 1.  -> (proofs, statuses, instances) in that mode only:
-        instances[i] = the completed public inputs as ints, leading one included, or None where the assignment is stuck."""
+        instances[i] = the completed public inputs as ints, leading one included, or None where the assignment is stuck.
+        glue="device": the glue between the phases runs on the GPU, one lane per proof (PM_PROVE_GLUE_DEVICE); same results."""
         if self.transcript_name is None:
             raise ValueError("prove_batch needs one of the reference's transcripts: " + ", ".join(TRANSCRIPTS))
         if len(circuits_or_limbs) != len(r_as):
@@ -424,9 +425,9 @@ class Polymath:
         w_all = np.stack(ws) if count else np.zeros((0, 0, 4), dtype=np.uint64)
         ra_all = np.stack([f.fr_limbs(list(r)) for r in r_as]) if count else np.zeros((0, 2, 4), dtype=np.uint64)
         if device_ptrs is not None:
-            rc, data, status = pk.host_prove_batch(self.transcript_name, x_all, device_ptrs[0], device_ptrs[1], ra_all, on_device=True, solve=solve)
+            rc, data, status = pk.host_prove_batch(self.transcript_name, x_all, device_ptrs[0], device_ptrs[1], ra_all, on_device=True, solve=solve, glue=glue)
         else:
-            rc, data, status = pk.host_prove_batch(self.transcript_name, x_all, x_all, w_all, ra_all, solve=solve)
+            rc, data, status = pk.host_prove_batch(self.transcript_name, x_all, x_all, w_all, ra_all, solve=solve, glue=glue)
         if rc:
             raise PolymathProverError(0, rc)
         plen = len(data) // count if count else 0

@@ -82,6 +82,9 @@ pub const PM_VERIFY_PAIRING_DEVICE: i32 = 1;
 // pm_verify_challenges: where the per-proof Fiat-Shamir challenges run; OR-ed into pm_verify_batch2's `pairing`
 pub const PM_VERIFY_CHALLENGES_HOST: i32 = 0;
 pub const PM_VERIFY_CHALLENGES_DEVICE: i32 = 256;
+// pm_prove_glue: where the glue between the phases of pm_host_prove_batch runs; OR-ed into its `transcript` (that entry point alone)
+pub const PM_PROVE_GLUE_HOST: i32 = 0;
+pub const PM_PROVE_GLUE_DEVICE: i32 = 256;
 
 // pm_assignment_flags: the `assignment_on_device` argument of pm_host_prove[_batch] and pm_r1cs_check[_batch] is a flag word
 pub const PM_ASSIGNMENT_DEVICE: i32 = 1;

@@ -763,6 +763,29 @@ impl GpuKey {
         transcript: i32,
         rows: &[(&[E::ScalarField], &[E::ScalarField], [E::ScalarField; 2])],
     ) -> Result<Vec<Result<Vec<u8>, Status>>, HipError> {
+        self.prove_batch_with_glue::<E>(ctx, transcript, sys::PM_PROVE_GLUE_HOST, rows)
+    }
+
+    /// [`GpuKey::prove_batch`] with `PM_PROVE_GLUE_DEVICE`: the Fiat-Shamir glue between the phases of a group of proofs runs in
+    /// kernels with one lane per proof, and a group costs one copy to the host and one stream synchronisation.  Statuses and bytes
+    /// are those of `prove_batch`, bit for bit.
+    pub fn prove_batch_device_glue<E: Pairing>(
+        &self,
+        ctx: &mut Context,
+        transcript: i32,
+        rows: &[(&[E::ScalarField], &[E::ScalarField], [E::ScalarField; 2])],
+    ) -> Result<Vec<Result<Vec<u8>, Status>>, HipError> {
+        self.prove_batch_with_glue::<E>(ctx, transcript, sys::PM_PROVE_GLUE_DEVICE, rows)
+    }
+
+    /// `glue`: a `sys::PM_PROVE_GLUE_*` value, OR-ed into the call's `transcript` argument.
+    pub fn prove_batch_with_glue<E: Pairing>(
+        &self,
+        ctx: &mut Context,
+        transcript: i32,
+        glue: i32,
+        rows: &[(&[E::ScalarField], &[E::ScalarField], [E::ScalarField; 2])],
+    ) -> Result<Vec<Result<Vec<u8>, Status>>, HipError> {
         let curve = curve_checked::<E>()?;
         if curve != self.curve {
             return Err(err(Status::InvalidArg, "key of another curve"));
@@ -783,8 +806,8 @@ impl GpuKey {
         // SAFETY: live key and context; x / w / ra hold rows.len() records of m0 / mw / 2 elements (layout checked), `bytes` and
         // `status` have room for rows.len() records.
         let rc = unsafe {
-            sys::pm_host_prove_batch(ctx.raw, self.raw, transcript, rows.len(), fr_ptr(&x), fr_ptr(&x), w_ptr, 0, fr_ptr(&ra), bytes.as_mut_ptr(), proof_len,
-                                     status.as_mut_ptr())
+            sys::pm_host_prove_batch(ctx.raw, self.raw, transcript | glue, rows.len(), fr_ptr(&x), fr_ptr(&x), w_ptr, 0, fr_ptr(&ra), bytes.as_mut_ptr(),
+                                     proof_len, status.as_mut_ptr())
         };
         ctx.check(rc)?;
         Ok(status

@@ -14,7 +14,11 @@ Every rep of (a) synthesises all B assignments again: that is the step (b) moves
 is the same comparison on a boolean circuit (bit decompositions, XOR rows), and
   python tools/prove_bench.py --circuit matchcount --batch 256 --reps 5 --solve  MatchCount, 1024 values, arkworks' form;
                                                                                  matchcount:N:FORM (FORM = ark or circom) for others
-on one that tests equality (one dependency level of N is-zero pairs; about half of the values match)."""
+on one that tests equality (one dependency level of N is-zero pairs; about half of the values match).
+  python tools/prove_bench.py --circuit mimc322 --batch 256 --reps 5 --glue device
+compares the two glue modes of the batch call itself, alternating in this process, same key, same device-resident assignments:
+  (a) pm_host_prove_batch, host glue (about six synchronisations a group)   (b) the same call with PM_PROVE_GLUE_DEVICE (one a group)
+and prints proofs/s, the spread over the reps, the stage split of both and whether the two outputs are the same bytes."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -30,6 +34,7 @@ ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--curve", default="bls12_381")
 ap.add_argument("--transcript", default="merlin")
 ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="pm_ctx_set_option before the key is made, e.g. --opt tables=0")
+ap.add_argument("--glue", choices=("host", "device"), default="host", help="device: host glue against device glue of the batch call")
 ap.add_argument("--solve", action="store_true", help="host-synthesised assignments against partial assignments solved on the GPU")
 a = ap.parse_args()
 if a.solve and not a.circuit.startswith(("mimc", "arx", "matchcount")):
@@ -126,12 +131,37 @@ if a.solve:
     sys.exit(0)
 
 
-def run_batch():
+def run_batch(glue="host"):
     t0 = time.perf_counter()
-    rc, data, status = pk.host_prove_batch(a.transcript, xs, dx.data_ptr(), dw.data_ptr(), ras, on_device=True)
+    rc, data, status = pk.host_prove_batch(a.transcript, xs, dx.data_ptr(), dw.data_ptr(), ras, on_device=True, glue=glue)
     dt = time.perf_counter() - t0
     assert rc == 0 and not status.any(), (rc, status)
     return dt, data, pm.ctx.timings()
+
+
+def glue_comparison():
+    _, dh, _ = run_batch("host")        # warm-up of both modes and the equality check
+    _, dd, _ = run_batch("device")
+    th, td = [], []
+    for _ in range(a.reps):
+        dt, _, tm_host = run_batch("host")
+        th.append(dt)
+        dt, _, tm_dev = run_batch("device")
+        td.append(dt)
+    spread = lambda v: round((max(v) - min(v)) / med(v), 4)
+    print(json.dumps({"curve": a.curve, "circuit": a.circuit, "transcript": a.transcript, "n": pk.n, "batch": B, "bytes_equal": dh == dd,
+                      "setup_s": round(setup_s, 3),
+                      "host_glue_ms": [round(t * 1e3, 3) for t in th], "device_glue_ms": [round(t * 1e3, 3) for t in td],
+                      "host_glue_proofs_per_s": round(B / med(th), 1), "device_glue_proofs_per_s": round(B / med(td), 1),
+                      "host_glue_spread": spread(th), "device_glue_spread": spread(td),
+                      "device_over_host": round(med(th) / med(td), 3),
+                      "host_glue_stage_ms_sum_over_batch": {k: round(v, 3) for k, v in tm_host.items()},
+                      "device_glue_stage_ms_sum_over_batch": {k: round(v, 3) for k, v in tm_dev.items()}}))
+
+
+if a.glue == "device":
+    glue_comparison()
+    sys.exit(0)
 
 
 def run_loop():
