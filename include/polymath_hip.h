@@ -306,7 +306,8 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  *     same call without the flag on that assignment.  instance_host of the prove calls uses the same marker: unknown public inputs are
  *     replaced by the solved values before they are hashed.  Without the flag nothing looks for markers.  The caller's arrays are
  *     never written, on host or device: the completed assignment lives in memory of the context.
- *   The rule.  Rows are visited once, in matrix order.  At row r, among the non-zero entries of A_r, B_r, C_r:
+ *   The rule.  Rows are visited once, in matrix order; a system that this pass refuses is then looked at in ANY ROW ORDER (below).
+ *   At row r, among the non-zero entries of A_r, B_r, C_r:
  *     no unknown column                       -- a check row, skipped
  *     one unknown u, in exactly one of them   -- z_u = (Az Bz - C_rest) / coef   (u in C)
  *                                                z_u = (Cz / Bz - A_rest) / coef (u in A; u in B alike with Az), and u is known from here on
@@ -341,19 +342,32 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  *                                                entries): unsolvable
  *   A boolean-pending column that is the single unknown of a later ordinary row is solved by that row; its booleanity row is then a
  *   constraint like any other, which the check reports if the value is not 0 or 1.  One that is still pending when the rows end is
- *   unsolvable: its booleanity row (the smallest such row) and column are named.  Booleanity rows that come AFTER the decomposition row
- *   are not looked for: that decomposition row is refused.  XOR, AND, rotations and recompositions are ordinary one-unknown rows, so
- *   range checks, comparisons, modular additions and ARX hashes complete, and with the is-zero pair so do equality tests, selection on
- *   equality, table membership and data-dependent branches.  Not solved: a closer before its opener or separated from it by rows that
- *   name the pair, K2 = lambda K1 for other lambda, a known rest beside m in the opener, bits spread over two matrices, signed or
- *   non-binary digits.
+ *   unsolvable: its booleanity row (the smallest such row) and column are named.  XOR, AND, rotations and recompositions are ordinary
+ *   one-unknown rows, so range checks, comparisons, modular additions and ARX hashes complete, and with the is-zero pair so do
+ *   equality tests, selection on equality, table membership and data-dependent branches.
+ *   Rows in any order.  Where the pass in matrix order refuses, a waiting-row scheduler applies the same rules in DEPENDENCY order: it
+ *   examines the rows smallest first, and a row that cannot act yet WAITS on its unknown columns and is examined again when one of
+ *   them becomes known or boolean-pending -- a row with two or more unknowns that is no decomposition and no opener, a decomposition
+ *   row before its booleanity rows, one unknown named twice in a shape that is no booleanity row (a later row may determine it: this
+ *   one is a check row then), and a row that names a pending pair's multiplier or flag beside something else.  A row whose only
+ *   unknown is a pending flag is that pair's closer or, in any other shape, a refusal as in matrix order; a row whose only unknown
+ *   is a pending multiplier, named once, determines it as an ordinary row (the opener was none and is examined again).  An R1CS
+ *   assembled from parts, booleanity rows emitted after the recomposition, a row-sorted matrix file and a system with its assertion
+ *   first all complete this way, with the values the rows in dependency order give.  If no order solves the system the error is the
+ *   matrix-order pass's -- same row, column and text -- with "; in any row order: ..." and what stays unknown appended.  Not solved,
+ *   in any order: a closer examined before its opener (it is an ordinary dividing row then and sticks where the tested value is 0),
+ *   K2 = lambda K1 for other lambda, a known rest beside m in the opener, bits spread over two matrices, signed or non-binary digits,
+ *   per-assignment patterns, sharded keys.
  *   PM_ERR_INVALID_ARG, pm_last_error naming the row or column, nothing computed and no output written: an unsolvable row, a marked
  *   column that no row determines, a marker at column 0, a sharded key, and -- in a batch -- an assignment that does not mark the
  *   columns assignment 0 marks (the first differing (assignment, column) is named; a kernel compares them).
  *   At run time a step that would divide by zero (Bz = 0 with u in A) leaves that assignment STUCK, even where Cz = 0 too (the value
  *   is then undetermined), and so does a decomposition whose t is 2^k or more (no boolean solution; its k values are stored as
  *   zero): its other solved values are undefined, its neighbours are not affected, and its smallest stuck row is
- *   reported (a 64-bit atomic minimum: the same word on every run, since everything downstream of a stuck row has a larger index):
+ *   reported (a 64-bit atomic minimum: the same word on every run, since everything downstream of a stuck row has a larger index).
+ *   Where the rows were reordered that is not so -- a row that reads the stored zero may stick too, at a smaller index -- and the row
+ *   reported is the ROOT CAUSE: among the stuck rows the one of lowest dependency level, then smallest index, which read only valid
+ *   values:
  *     pm_r1cs_check[_batch]   n_bad[i] = UINT64_MAX, rows[i][0] = the stuck row (max_rows > 0), the other slots UINT64_MAX, abc zero
  *     pm_host_prove_batch     status[i] = PM_ERR_INVALID_ARG, zeroed bytes
  *     pm_host_prove           returns PM_ERR_INVALID_ARG

@@ -2,7 +2,8 @@
 (tests/dummy.rs:20-35, tests/mimc.rs:74-143, benches/bench.rs:38-61) and the synthetic
 "random A*B=C gates" R1CS BASELINE.json quotes the headline metric on, and two boolean circuits of this project's
 own (RangeCheck, ArxDemo) and two that branch on equality (MatchCount, EqChain: is-zero pairs in arkworks' and in circom's form) whose
-witnesses the device completes from the inputs (PM_ASSIGNMENT_SOLVE)."""
+witnesses the device completes from the inputs (PM_ASSIGNMENT_SOLVE); Reordered emits any of them with its rows in
+another order, which the solver's any-order planner accepts."""
 from .polymath import ConstraintSystem, Field, LimbCircuit, R1CS
 
 SPLITMIX_SEED = 0x706F6C796D617468  # "polymath"
@@ -323,6 +324,55 @@ def eq_chain_targets(x, hits, r, miss=5):
         targets.append(t)
         s = (s + 1 + (t if hit else 0)) % r
     return targets
+
+
+def row_order(nr, order, blocks=1):
+    """The row order Reordered replays: a permutation of range(nr).  `order` is "reverse", an int (the seed of a Fisher-Yates shuffle
+    on SplitMix64) or an explicit permutation; with blocks = k it moves whole k-row blocks (the last one may be shorter) and an
+    explicit permutation is one of the block indices -- rows keep their order inside a block."""
+    n_blocks = -(-nr // blocks)
+    if isinstance(order, str):
+        if order != "reverse":
+            raise ValueError("order is 'reverse', a seed or a permutation")
+        perm = list(range(n_blocks))[::-1]
+    elif isinstance(order, int):
+        g, perm = SplitMix64(order), list(range(n_blocks))
+        for i in range(n_blocks - 1, 0, -1):
+            j = g.next_u64() % (i + 1)
+            perm[i], perm[j] = perm[j], perm[i]
+    else:
+        perm = list(order)
+        if sorted(perm) != list(range(n_blocks)):
+            raise ValueError("order is no permutation of the %d blocks" % n_blocks)
+    return [row for blk in perm for row in range(blk * blocks, min((blk + 1) * blocks, nr))]
+
+
+class Reordered:
+    """`circuit` with its constraint rows emitted in another order (row_order): the same variables, allocated in the inner circuit's
+    order, the same rows, the same assignment -- what an R1CS assembled from parts, a row-sorted matrix file or a producer that emits
+    assertions first looks like.  The inner circuit is generated into a private ConstraintSystem and its enforce_constraint calls
+    are replayed in the new order.  partial() and native() are the inner circuit's.  With blocks = k whole k-row gadgets move, so that
+    an is-zero pair's opener stays before its closer (a closer examined first is an ordinary dividing step)."""
+
+    def __init__(self, circuit, order, blocks=1):
+        self.circuit, self.order, self.blocks = circuit, order, blocks
+
+    def generate_constraints(self, cs):
+        inner = ConstraintSystem(cs.r)
+        self.circuit.generate_constraints(inner)
+        var = {ConstraintSystem.ONE: ConstraintSystem.ONE}
+        for i, value in enumerate(inner.instance[1:], 1):
+            var[("inst", i)] = cs.new_input_variable(value)
+        for i, value in enumerate(inner.witness):
+            var[("wit", i)] = cs.new_witness_variable(value)
+        for row in row_order(len(inner.rows), self.order, self.blocks):
+            cs.enforce_constraint(*([(coef, var[v]) for coef, v in lc] for lc in inner.rows[row]))
+
+    def partial(self, *args, **kwargs):
+        return self.circuit.partial(*args, **kwargs)
+
+    def native(self, *args, **kwargs):
+        return self.circuit.native(*args, **kwargs)
 
 
 def synthetic_r1cs(r, nr, seed=SPLITMIX_SEED):

@@ -632,9 +632,11 @@ int prove_batch_xw(pm_ctx *ctx, const pm_pk *pk, size_t rows, Fp<typename C::FrP
 //   solve_load     per group: the caller's x / w rows (host or device) -> rows of d_xw ([g][m0 + mw]), and the pattern kernel over them;
 //                  g0 = index of the group's first assignment in the batch (assignment 0 sets the pattern)
 //   solve_plan     after the last group: pattern and mismatch slot come down; PM_ERR_INVALID_ARG with pm_last_error set for a marker at
-//                  column 0, a mismatching assignment or an unsolvable structure; otherwise the plan is taken from the cache or built
-//   solve_group    per group: the launch schedule over d_xw, then the stuck rows and completed instances of the group into tap 9;
-//                  GPU ms go to timing_slot.  The stream is idle on return.
+//                  column 0, a mismatching assignment or a structure that no row order solves; otherwise the plan is taken from the
+//                  cache or built (pmsolve::build_plan_any_order: matrix order first, then the waiting-row scheduler)
+//   solve_group    per group: the launch schedule over d_xw -- after a reordered plan k_solve_stuck_row, so that the stuck words hold
+//                  rows for every reader, prove_glue.hip's kernels included --, then the stuck rows and completed instances of the
+//                  group into tap 9; GPU ms go to timing_slot.  The stream is idle on return.
 // solve_all is the four over a whole batch in groups of the check's size into pm_ctx::sv.xw ([count][m0 + mw], pm_prove_tap(10)).
 template <class C>
 int solve_begin(pm_ctx *ctx, const pm_pk *pk, size_t count);

@@ -17,8 +17,13 @@
 // The solving kernels exist twice: DIV = false for ranges of kind-C steps only, DIV = true for ranges with kind-A / kind-B steps,
 // or is-zero pairs, which call inverse<P> (a Fermat chain) -- the plan sorts a level by kind, so kind-C ranges do not carry its
 // registers, and the is-zero step exists in the DIV = true chain only.
+//   k_solve_stuck_row after the launches of a REORDERED plan (build_plan_any_order found a dependency order that is not the matrix
+//                     order): one lane per assignment turns the stuck word's (level, row) into the row
 // A step that would divide by zero stores zero and lowers the assignment's stuck word to its row (64-bit atomic minimum: the same
-// word on every run); so does a decomposition whose value has no k-bit form, in all its k columns.  Every other store has one
+// word on every run); so does a decomposition whose value has no k-bit form, in all its k columns.  In matrix order everything
+// downstream of a stuck row has a larger row, so the minimum is the root cause.  Under a reordered plan that is false -- a step that
+// reads the stored zero may stick too, at a smaller row -- so the word is lowered to (level << 32) | row there: the minimum is the
+// stuck step of lowest level, then smallest row, which read only valid values, and k_solve_stuck_row leaves its row in the word.  Every other store has one
 // writer.  An is-zero pair never sticks: where the tested value is zero its multiplier is free and is stored as zero.  Plain C++ and
 // vector stores only.
 #include <cstring>
@@ -37,6 +42,7 @@ struct SolveStepDev {
     uint32_t row, col, kind, bits;   // bits != 0: a decomposition into the columns bit_cols[col .. col + bits), exponent order;
                                      // kind == KIND_ISZERO: row = the closer, pos / col = the flag's entry in it, bits = its SolvePairDev
     Fp<P> inv;                       // 1 / coefficient (k_solve_inv)
+    uint32_t level, pad;             // a stuck step lowers the stuck word to (level << 32) | row; level is 0 unless the plan is reordered
 };
 
 // what an is-zero step needs beside its SolveStepDev: the opener row r1
@@ -48,6 +54,14 @@ struct SolvePairDev {
     uint32_t negated, pad;           // K2 = -K1
     Fp<P> inv_cm, inv_cb;            // k_solve_inv
 };
+
+// What a stuck step lowers the stuck word to.  The level is read HERE, on the rare path (a volatile load the compiler cannot hoist
+// into the registers every step carries): the step bodies keep the registers they had.
+template <class P>
+__device__ __forceinline__ unsigned long long stuck_key(const SolveStepDev<P> &s) {
+    const uint32_t level = *(const volatile uint32_t *)&s.level;
+    return (unsigned long long)level << 32 | s.row;
+}
 
 template <class P>
 __device__ __forceinline__ bool is_marker(const Fp<P> &v) {
@@ -142,7 +156,7 @@ __device__ __forceinline__ void solve_step(const CsrDev &A, const CsrDev &B, con
     } else {
         const Fp<P> den = kind == pmsolve::KIND_A ? bz : az, rest = kind == pmsolve::KIND_A ? az : bz;
         if (den.is_zero()) {        // 0 / 0 included: the value is then undetermined
-            atomicMin(stuck, (unsigned long long)r);
+            atomicMin(stuck, stuck_key<P>(s));
             z[s.col] = Fp<P>::zero();
             return;
         }
@@ -181,7 +195,7 @@ __device__ __forceinline__ void solve_bits(const CsrDev &A, const CsrDev &B, con
         ok = high == 0;
     }
     if (!ok) {
-        atomicMin(stuck, (unsigned long long)r);
+        atomicMin(stuck, stuck_key<P>(s));
         t = Fp<P>::zero();
     }
     for (uint32_t i = 0; i < k; i += 32) {
@@ -261,6 +275,15 @@ __global__ __launch_bounds__(64) void k_solve_chain(CsrDev A, CsrDev B, CsrDev C
         } else if (steps[t].bits) solve_bits<P, DIV>(A, B, Cm, steps[t], bit_cols, z, stuck + b);
         else solve_step<P, DIV>(A, B, Cm, steps[t], z, stuck + b);
     }
+}
+
+// After the last launch of a REORDERED plan: the stuck word (level << 32) | row of the root cause becomes its row, which is what
+// every reader of the word expects.  One lane per assignment.
+__global__ __launch_bounds__(256) void k_solve_stuck_row(unsigned long long *stuck, uint64_t rows) {
+    const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= rows) return;
+    const unsigned long long w = stuck[b];
+    if (w != SOLVE_NONE) stuck[b] = w & 0xffffffffull;
 }
 
 namespace {
@@ -343,7 +366,7 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
     PM_HIP(ctx, hipStreamSynchronize(st));
     uint64_t modulus[4];
     for (int i = 0; i < 4; ++i) modulus[i] = (uint64_t)P::MOD[2 * i] | (uint64_t)P::MOD[2 * i + 1] << 32;
-    sv.plan = pmsolve::build_plan(m, nr, pk->m0, pk->mw, pattern.data(), pmsolve::WIDE_STEPS, modulus);
+    sv.plan = pmsolve::build_plan_any_order(m, nr, pk->m0, pk->mw, pattern.data(), pmsolve::WIDE_STEPS, modulus);
     if (sv.plan.error != pmsolve::OK) {
         ctx->err = "pm solve: " + sv.plan.message;
         return PM_ERR_INVALID_ARG;
@@ -364,6 +387,7 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
         for (size_t t = 0; t < n_steps; ++t) {
             const pmsolve::Step &s = sv.plan.steps[t];
             host[t].pos = s.pos; host[t].row = s.row; host[t].col = s.bits ? s.cols_off : s.col; host[t].kind = s.kind; host[t].bits = s.bits;
+            host[t].level = sv.plan.reordered ? s.level : 0;
             if (s.kind != pmsolve::KIND_ISZERO) continue;
             host[t].bits = (uint32_t)host_pairs.size();
             SolvePairDev<P> pr;
@@ -427,6 +451,7 @@ int solve_group(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t 
             }
             PM_HIP(ctx, hipGetLastError());
         }
+        if (sv.plan.reordered) PM_LAUNCH(ctx, k_solve_stuck_row, dim3(nblk(g)), dim3(256), 0, st, stuck, (uint64_t)g);
     }
     // the small results: per assignment the stuck word and the completed instance -> tap 9
     std::vector<unsigned long long> h_stuck(g);

@@ -1,6 +1,6 @@
 // Witness solving, host side: the PLAN that completes a partial assignment by forward propagation through the rows of an R1CS
-// (DESIGN.md §4.10).  Header-only, no HIP: the library's driver (csrc/solve.hip) and three CPU programs (tests/native/
-// solve_plan_selftest.cpp, solve_bits_selftest.cpp, solve_iszero_selftest.cpp) include the same file.
+// (DESIGN.md §4.10).  Header-only, no HIP: the library's driver (csrc/solve.hip) and four CPU programs (tests/native/
+// solve_plan_selftest.cpp, solve_bits_selftest.cpp, solve_iszero_selftest.cpp, solve_order_selftest.cpp) include the same file.
 //
 // Input: the three matrices in CSR form with the first-entry rule already applied (a column occurs at most once per row and
 // matrix: the key's resident matrices are like that), m0 + mw columns and one byte per column, non-zero = unknown.  A stored entry
@@ -44,6 +44,30 @@
 //                 when the rows end are reported first, smallest r1 first.
 // Without the modulus (nullptr) all three additions are off.
 //
+// build_plan_any_order drops the matrix order: it runs build_plan, and where that refuses, a WAITING-ROW SCHEDULER examines the rows
+// from a min-heap (at first all of them) against the same column state with the same rules, except that these refusals become waiting:
+//   no unknown                              a check row
+//   only the flag b of a registered opener  the closer (b once, in A or B, not in C, the other side +-K1): the KIND_ISZERO step, at
+//                                           1 + max of what both rows read.  Any other shape is a DEFINITE refusal, as in matrix order
+//   only the multiplier m of one, once      an ordinary step that determines m; the opener was none: it is RELEASED and examined again
+//   a pair-pending column in any other way  the row WAITS (the multiplier beside something else, a second unknown, an opener-shaped
+//                                           row over a pending column)
+//   one unknown, named once                 an ordinary step
+//   one unknown, named several times        booleanity: boolean-pending; any other shape WAITS (a later row may determine the column
+//                                           and this one is a check row then)
+//   two or more unknowns                    a decomposition: the bits step; the opener shape: registered; anything else WAITS
+// A waiting row is parked on its unknown columns and returns to the heap when one of them becomes known, boolean-pending or released.
+// With the heap empty the scheduler has failed if an opener is unclosed, a boolean-pending column unsolved or a marked column
+// undetermined; the result is then build_plan's error (code, row, column, message) with "; in any row order: ..." appended.  A plan
+// it finds has Plan::reordered = true, level(step) as below, the steps sorted by (level, kind, row) and the level_ptr and launches of
+// the same tail (finish_plan).  O(nnz log rows); a reversed chain costs one examination and one wake-up per row, not a sweep per level.
+// Unchanged by the any-order route:
+//   - a closer examined BEFORE its opener is an ordinary dividing step, and the opener an ordinary kind-C step: it sticks at d = 0
+//   - K2 = lambda K1 for another lambda than +-1 is not recognised
+//   - a known rest beside m in the opener is not handled
+//   - the bits of one decomposition over two matrices are not handled
+//   - one pattern per batch: per-assignment patterns are not supported; nor are sharded keys
+//
 // level(step) = 1 + max level of the columns the row reads (given columns: level 0); a decomposition gives all its columns that
 // level.  The steps come out sorted by level, inside a level by kind (C first: the kinds that divide share a launch; then the
 // decompositions in the same order, then the is-zero pairs), stable by row -- one counting sort.  O(nnz + columns), plus k log k per decomposition.
@@ -51,6 +75,8 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <functional>
+#include <queue>
 #include <string>
 #include <utility>
 #include <vector>
@@ -104,6 +130,7 @@ struct Plan {
     int error = OK;
     uint64_t error_row = 0, error_col = 0;
     std::string message;              // empty when error == OK
+    bool reordered = false;           // build_plan_any_order: the steps do not follow the matrix order (the stuck word needs the level then)
     uint32_t levels() const { return level_ptr.empty() ? 0 : (uint32_t)level_ptr.size() - 1; }
 };
 
@@ -227,6 +254,42 @@ inline int compare_known_sides(const Csr m[3], int k1, uint64_t r1, int k2, uint
         negated = negated && coef_is_zero(sum);
     }
     return same ? 0 : negated ? 1 : -1;
+}
+
+// The tail both builders share: p.steps (in ROW order, levels set) sorted by (level, kind), stable by row; level_ptr; the launch schedule.
+inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
+    // counting sort by (level, kind); the row order inside a key is the order the steps come in
+    constexpr size_t K = NUM_KINDS;
+    std::vector<uint32_t> start((size_t)max_level * K + 1, 0);
+    for (const Step &s : p.steps) ++start[(size_t)(s.level - 1) * K + s.kind + 1];
+    for (size_t i = 1; i < start.size(); ++i) start[i] += start[i - 1];
+    p.level_ptr.resize((size_t)max_level + 1);
+    for (uint32_t l = 0; l <= max_level; ++l) p.level_ptr[l] = start[(size_t)l * K];
+    {
+        std::vector<Step> sorted(p.steps.size());
+        std::vector<uint32_t> cursor(start.begin(), start.end() - 1);
+        for (const Step &s : p.steps) sorted[cursor[(size_t)(s.level - 1) * K + s.kind]++] = s;
+        p.steps.swap(sorted);
+    }
+    // launch schedule: a wide level is its own launch, split where the dividing kinds begin, again where the decompositions and
+    // their dividing kinds begin, and where the is-zero pairs begin; consecutive narrow levels are one chain
+    for (uint32_t l = 0; l < max_level; ++l) {
+        const uint32_t *at = start.data() + (size_t)l * K;
+        const uint32_t lo = at[KIND_C], ab = at[KIND_A], bits = at[KIND_BITS_C], bits_ab = at[KIND_BITS_A], pairs = at[KIND_ISZERO], hi = at[K];
+        const uint8_t divides = (uint8_t)(bits > ab || hi > bits_ab);
+        if (hi - lo >= wide_steps) {
+            if (ab > lo) p.launches.push_back(Launch{lo, ab, 0, 0});
+            if (bits > ab) p.launches.push_back(Launch{ab, bits, 0, 1});
+            if (bits_ab > bits) p.launches.push_back(Launch{bits, bits_ab, 0, 0, 1});
+            if (pairs > bits_ab) p.launches.push_back(Launch{bits_ab, pairs, 0, 1, 1});
+            if (hi > pairs) p.launches.push_back(Launch{pairs, hi, 0, 1, 0, 1});
+        } else if (!p.launches.empty() && p.launches.back().chain) {
+            p.launches.back().hi = hi;
+            p.launches.back().divides |= divides;
+        } else {
+            p.launches.push_back(Launch{lo, hi, 1, divides});
+        }
+    }
 }
 
 inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, const uint8_t *unknown, uint32_t wide_steps = WIDE_STEPS,
@@ -412,38 +475,173 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
             p.pairs.clear();
             return p;
         }
-    // counting sort by (level, kind); the row order inside a key is the order of discovery
-    constexpr size_t K = NUM_KINDS;
-    std::vector<uint32_t> start((size_t)max_level * K + 1, 0);
-    for (const Step &s : p.steps) ++start[(size_t)(s.level - 1) * K + s.kind + 1];
-    for (size_t i = 1; i < start.size(); ++i) start[i] += start[i - 1];
-    p.level_ptr.resize((size_t)max_level + 1);
-    for (uint32_t l = 0; l <= max_level; ++l) p.level_ptr[l] = start[(size_t)l * K];
-    {
-        std::vector<Step> sorted(p.steps.size());
-        std::vector<uint32_t> cursor(start.begin(), start.end() - 1);
-        for (const Step &s : p.steps) sorted[cursor[(size_t)(s.level - 1) * K + s.kind]++] = s;
-        p.steps.swap(sorted);
-    }
-    // launch schedule: a wide level is its own launch, split where the dividing kinds begin, again where the decompositions and
-    // their dividing kinds begin, and where the is-zero pairs begin; consecutive narrow levels are one chain
-    for (uint32_t l = 0; l < max_level; ++l) {
-        const uint32_t *at = start.data() + (size_t)l * K;
-        const uint32_t lo = at[KIND_C], ab = at[KIND_A], bits = at[KIND_BITS_C], bits_ab = at[KIND_BITS_A], pairs = at[KIND_ISZERO], hi = at[K];
-        const uint8_t divides = (uint8_t)(bits > ab || hi > bits_ab);
-        if (hi - lo >= wide_steps) {
-            if (ab > lo) p.launches.push_back(Launch{lo, ab, 0, 0});
-            if (bits > ab) p.launches.push_back(Launch{ab, bits, 0, 1});
-            if (bits_ab > bits) p.launches.push_back(Launch{bits, bits_ab, 0, 0, 1});
-            if (pairs > bits_ab) p.launches.push_back(Launch{bits_ab, pairs, 0, 1, 1});
-            if (hi > pairs) p.launches.push_back(Launch{pairs, hi, 0, 1, 0, 1});
-        } else if (!p.launches.empty() && p.launches.back().chain) {
-            p.launches.back().hi = hi;
-            p.launches.back().divides |= divides;
-        } else {
-            p.launches.push_back(Launch{lo, hi, 1, divides});
+    finish_plan(p, max_level, wide_steps);
+    return p;
+}
+
+// The waiting-row scheduler of build_plan_any_order: the rules of build_plan on the rows in DEPENDENCY order.  A min-heap of rows to
+// examine (at first every row); a row that cannot act yet is parked on its unknown columns and returns to the heap when one of them
+// becomes known, becomes boolean-pending or is released by its opener.  -> false and `why` where no order solves the system.
+// p.steps come out in order of discovery, with their levels; max_level is set.
+inline bool schedule_any_order(const Csr m[3], uint64_t nr, uint64_t ncols, const uint8_t *unknown, const uint64_t *modulus, Plan &p, uint32_t &max_level,
+                               std::string &why) {
+    constexpr uint32_t UNSOLVED = ~(uint32_t)0, NONE = ~(uint32_t)0;
+    static const uint32_t KIND_OF[3] = {KIND_A, KIND_B, KIND_C};
+    enum : uint8_t { PARKED = 0, QUEUED = 1, DONE = 2 };
+    std::vector<uint32_t> level(ncols), bool_row(ncols, NONE), pair_of(ncols, NONE), park_head(ncols, NONE);
+    for (uint64_t j = 0; j < ncols; ++j) level[j] = unknown[j] ? UNSOLVED : 0;
+    std::vector<std::pair<uint32_t, uint32_t>> parked;   // (row, next node of the same column)
+    std::vector<uint8_t> state(nr, QUEUED);
+    std::vector<uint32_t> rows(nr);
+    for (uint64_t r = 0; r < nr; ++r) rows[r] = (uint32_t)r;   // ascending: a min-heap as it stands
+    std::priority_queue<uint32_t, std::vector<uint32_t>, std::greater<uint32_t>> heap(std::greater<uint32_t>(), std::move(rows));
+    std::vector<Opener> openers;
+    size_t open = 0;
+    std::vector<std::pair<uint32_t, uint64_t>> side1, side2;
+    std::vector<Unknown> occ;
+    std::vector<uint32_t> order;
+    max_level = 0;
+    const auto push = [&](uint32_t r) {
+        if (state[r] != PARKED) return;
+        state[r] = QUEUED;
+        heap.push(r);
+    };
+    const auto wake = [&](uint32_t col) {
+        for (uint32_t i = park_head[col]; i != NONE; i = parked[i].second) push(parked[i].first);
+        park_head[col] = NONE;
+    };
+    const auto park = [&](uint32_t r) {
+        state[r] = PARKED;
+        for (const Unknown &e : occ) {
+            parked.push_back({r, park_head[e.col]});
+            park_head[e.col] = (uint32_t)parked.size() - 1;
         }
+    };
+    const auto solved = [&](uint32_t col, uint32_t lv) {
+        level[col] = lv;
+        if (lv > max_level) max_level = lv;
+        wake(col);
+    };
+    while (!heap.empty()) {
+        const uint32_t r = heap.top();
+        heap.pop();
+        uint32_t reads = 0, nz[3] = {0, 0, 0};
+        occ.clear();
+        for (int k = 0; k < 3; ++k)
+            for (uint64_t e = m[k].rowptr[r]; e < m[k].rowptr[r + 1]; ++e) {
+                if (coef_is_zero(m[k].val + 4 * e)) continue;
+                ++nz[k];
+                const uint32_t j = m[k].col[e];
+                if (level[j] != UNSOLVED) {
+                    if (level[j] > reads) reads = level[j];
+                    continue;
+                }
+                occ.push_back(Unknown{(uint32_t)k, j, e});
+            }
+        state[r] = DONE;
+        if (occ.empty()) continue;   // a check row
+        const uint32_t u = occ[0].col;
+        bool one_column = true;
+        for (const Unknown &e : occ) one_column = one_column && e.col == u;
+        const Opener *o = nullptr;
+        for (const Unknown &e : occ)
+            if (!o && pair_of[e.col] != NONE) o = &openers[pair_of[e.col]];
+        if (o && one_column && u == o->col_b) {   // the flag alone: the closer, or no order helps
+            const int sign = occ.size() == 1 && occ[0].matrix < 2 ? compare_known_sides(m, o->m_in_b ? 0 : 1, o->row, occ[0].matrix == 0 ? 1 : 0, r, modulus, side1, side2) : -1;
+            if (sign < 0) {
+                why = "row " + std::to_string(r) + " names only the flag (column " + std::to_string(u) + ") of the pair that row " + std::to_string(o->row) + " opens and does not close it";
+                return false;
+            }
+            const uint32_t lv2 = (reads > o->reads ? reads : o->reads) + 1;
+            Step s{occ[0].pos, r, u, KIND_ISZERO, lv2};
+            s.cols_off = (uint32_t)p.pairs.size();
+            p.pairs.push_back(PairRows{o->pos_m, o->pos_c, o->row, o->col_m, o->m_in_b, (uint8_t)(occ[0].matrix == 1), (uint8_t)sign});
+            p.steps.push_back(s);
+            const uint32_t col_m = o->col_m;
+            pair_of[col_m] = pair_of[u] = NONE;
+            --open;
+            solved(col_m, lv2);
+            solved(u, lv2);
+            continue;
+        }
+        if (o && one_column && occ.size() == 1 && u == o->col_m) {
+            // the multiplier alone and once: this row determines it as an ordinary step, so the opener was no opener.  It is released
+            // and examined again (its other unknown is then an ordinary kind-C step of it)
+            const uint32_t col_b = o->col_b, opener_row = o->row;
+            pair_of[u] = pair_of[col_b] = NONE;
+            --open;
+            state[opener_row] = PARKED;
+            push(opener_row);
+            wake(col_b);
+            o = nullptr;
+        }
+        if (o) {   // the multiplier beside something else, a second unknown, another opener over a pending column: after the closer
+            park(r);
+            continue;
+        }
+        const uint32_t lv = reads + 1;
+        if (one_column) {
+            if (occ.size() == 1) {
+                p.steps.push_back(Step{occ[0].pos, r, u, KIND_OF[occ[0].matrix], lv});
+                solved(u, lv);
+            } else if (is_booleanity(m, r, occ, nz, modulus)) {
+                if (bool_row[u] == NONE) {
+                    bool_row[u] = r;
+                    wake(u);
+                }
+            } else {
+                park(r);   // a later row may determine u: this one is a check row then
+            }
+            continue;
+        }
+        if (!decomposition_order(m, occ, bool_row, modulus, order)) {
+            const Unknown &c = occ[order[0]];
+            Step s{c.pos, r, c.col, KIND_BITS_C + KIND_OF[c.matrix], lv};
+            s.bits = (uint32_t)order.size();
+            s.cols_off = (uint32_t)p.bit_cols.size();
+            for (uint32_t i : order) p.bit_cols.push_back(occ[i].col);
+            p.steps.push_back(s);
+            for (uint32_t i = 0; i < s.bits; ++i) solved(p.bit_cols[s.cols_off + i], lv);
+            continue;
+        }
+        if (occ.size() == 2 && occ[0].matrix < 2 && occ[1].matrix == 2 && nz[occ[0].matrix] == 1 && nz[1 - occ[0].matrix] >= 1) {
+            pair_of[u] = pair_of[occ[1].col] = (uint32_t)openers.size();
+            openers.push_back(Opener{occ[0].pos, occ[1].pos, r, u, occ[1].col, reads, (uint8_t)occ[0].matrix});
+            ++open;
+            continue;
+        }
+        park(r);
     }
+    for (uint64_t j = 0; j < ncols; ++j)
+        if (level[j] == UNSOLVED) {
+            why = "column " + std::to_string(j) + " stays unknown";
+            if (pair_of[j] != NONE) why += " (the pair that row " + std::to_string(openers[pair_of[j]].row) + " opens is never closed)";
+            else if (bool_row[j] != NONE) why += " (boolean by row " + std::to_string(bool_row[j]) + ", and nothing determines it)";
+            return false;
+        }
+    return open == 0;
+}
+
+// build_plan for rows in ANY order.  The matrix order is tried first: a system that build_plan accepts gets build_plan's plan,
+// field for field, with reordered = false (and without the modulus, or with column 0 marked, there is nothing else).  Otherwise the
+// scheduler above looks for a dependency order; if it finds one the plan has reordered = true, the same levels per column that the
+// rows give in any solvable order, and the steps sorted by (level, kind, row) with the level_ptr and launches of finish_plan.  If it
+// finds none the result is build_plan's error -- code, row, column, message -- with what stays unknown appended to the message.
+// O(nnz log rows): a row is examined once, and once more per event on one of its unknown columns.
+inline Plan build_plan_any_order(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, const uint8_t *unknown, uint32_t wide_steps = WIDE_STEPS,
+                                 const uint64_t *modulus = nullptr) {
+    Plan first = build_plan(m, nr, m0, mw, unknown, wide_steps, modulus);
+    if (first.error == OK || first.error == ERR_COLUMN_ZERO || !modulus) return first;
+    Plan p;
+    uint32_t max_level = 0;
+    std::string why;
+    if (!schedule_any_order(m, nr, m0 + mw, unknown, modulus, p, max_level, why)) {
+        first.message += "; in any row order: " + why;
+        return first;
+    }
+    std::sort(p.steps.begin(), p.steps.end(), [](const Step &a, const Step &b) { return a.row < b.row; });   // a row gives at most one step
+    finish_plan(p, max_level, wide_steps);
+    p.reordered = true;
     return p;
 }
 

@@ -829,6 +829,12 @@ impl GpuKey {
     /// circom's `IsZero` alike) with both the multiplier and the flag left `None` -- is completed as one step.  Where the tested
     /// value is zero the multiplier is free and the library writes m = 0; arkworks' own witness generation writes 1 there, and a
     /// caller that needs that value gives the multiplier as `Some(..)` and leaves only the flag open.
+    ///
+    /// The rows need not come in dependency order: a system whose pass in matrix order is refused is planned by a waiting-row
+    /// scheduler (a row waits until the rows that compute its inputs have acted), so an R1CS assembled from parts, booleanity rows
+    /// emitted after the recomposition or a row-sorted matrix file complete as well.  An assignment that gets stuck under such a plan
+    /// reports the ROOT CAUSE: the stuck row of lowest dependency level, then smallest index.  A pair's opener must still come
+    /// before its closer; a system that no order solves keeps the matrix-order error text.
     #[allow(clippy::type_complexity)]
     pub fn prove_batch_from_partial<E: Pairing>(
         &self,

@@ -1,0 +1,408 @@
+"""GPU: PM_ASSIGNMENT_SOLVE on constraint systems whose rows do NOT come in dependency order (host/solve_plan.hpp:
+build_plan_any_order; csrc/solve.hip: the (level, row) stuck key and k_solve_stuck_row).  The bar is equality, word for word, with Python
+integers: the circuits' own assignments (polymath_amd.circuits: Reordered replays a generator's rows in another order and keeps its
+variables and values).  Every positive case here is refused in matrix order ("row 0: two or more unknowns").
+
+Shapes are the ones of the in-order tests, at the sizes where a kernel takes another path: MiMC-322 reversed and shuffled is one
+k_solve_chain launch of depth 644, at 1, 3 and 70 assignments (a partial wave, a second workgroup); RangeCheck with 32 and 257 values
+is one wide level of k_solve_bits (the threshold, a workgroup edge), with the booleanity rows after the decomposition rows; ArxDemo
+walks decompositions in A and C and ordinary rows in one chain; synthetic_r1cs at 2000 gates runs both the chain and the level
+kernels; MatchCount with 40 values is a k_solve_iszero launch, EqChain a chain of pairs, in both forms with hits and misses.  The
+stuck-root system is three rows."""
+import ctypes as ct
+
+import numpy as np
+import pytest
+import torch        # noqa: F401  before libpolymath_hip.so is loaded: torch brings its own HIP runtime (tests/ntt_device_child.py)
+
+from oracle.pyref.fields import CURVES
+
+pytestmark = pytest.mark.gpu
+
+PM_OK, PM_ERR_INVALID_ARG = 0, 1
+NONE = (1 << 64) - 1
+BOTH = ["bls12_381", "bn254"]
+PROOF_LEN = {"bls12_381": 176, "bn254": 128}
+_KEYS = {}
+
+
+def _setup(gpu_ctx, curve, circuit, seed):
+    """circuit: a generator of polymath_amd.circuits, or an (R1CS, instance, witness) triple"""
+    from polymath_amd import circuits as PC, polymath as PM
+    c = CURVES[curve]
+    g = PC.SplitMix64(seed)
+    pm = PM.Polymath(curve, "merlin", ctx=gpu_ctx)
+    x, z = g.fr(c.r), g.fr(c.r)
+    q, inst, wit = pm._synthesize(circuit)
+    pk = pm.setup((q, inst, wit), x, z)
+    return dict(pm=pm, pk=pk, q=q, inst=inst, wit=wit, x=x, z=z, f=pm.field, c=c)
+
+
+def _cached(key, make):
+    if key not in _KEYS:
+        _KEYS[key] = make()
+    return _KEYS[key]
+
+
+def _full_limbs(s, inst, wit):
+    return np.concatenate([s["f"].fr_limbs(inst), s["f"].fr_limbs(wit)]).reshape(-1, 4)
+
+
+def _rows(s, assignments, partial):
+    """assignments: [(instance, witness)] as ints; partial: (instance, witness) with None where the device solves
+    -> (want, partial rows): count x (m0 + mw) x 4 words"""
+    from polymath_amd import api
+    want = np.stack([_full_limbs(s, inst, wit) for inst, wit in assignments])
+    unknown = np.array([v is None for v in list(partial[0]) + list(partial[1])])
+    rows = want.copy()
+    rows[:, unknown] = api.UNKNOWN_LIMBS
+    return want, rows
+
+
+def _solve(s, rows, max_rows=2):
+    m0 = s["q"].m0
+    xs, ws = np.ascontiguousarray(rows[:, :m0]), np.ascontiguousarray(rows[:, m0:])
+    rc, n_bad, _, _ = s["pk"].r1cs_check_batch(xs, ws, max_rows, solve=True)
+    assert rc == PM_OK, s["pm"].ctx.last_error()
+    stuck, _ = s["pk"].solve_results(len(xs))
+    return [int(v) for v in n_bad], [int(v) for v in stuck], s["pk"].solved_assignments(len(xs), s["q"].mw)
+
+
+def _completes(s, assignments, partial, counts=(1, 3, 70)):
+    for count in counts:
+        want, rows = _rows(s, assignments[:count], partial)
+        n_bad, stuck, full = _solve(s, rows)
+        assert n_bad == [0] * count and stuck == [NONE] * count, (count, n_bad, stuck)
+        assert np.array_equal(full, want), count
+
+
+def _native(circuit, r):
+    from polymath_amd.polymath import ConstraintSystem
+    cs = ConstraintSystem(r)
+    circuit.generate_constraints(cs)
+    return list(cs.instance), list(cs.witness)
+
+
+def _out_of_order(s, partial):
+    """for systems of ORDINARY rows (no booleanity, decomposition or pair): one pass in matrix order meets a row with two unknowns,
+    which is what the planner without the scheduler refuses"""
+    q, known = s["q"], [v is not None for v in list(partial[0]) + list(partial[1])]
+    for a, b, c in zip(q.a, q.b, q.c):
+        unknown = {j for row in (a, b, c) for v, j in row if v and not known[j]}
+        if len(unknown) > 1:
+            return True
+        for j in unknown:
+            known[j] = True
+    return False
+
+
+# ---- 1. the chain kernel: MiMC-322 reversed and shuffled, inputs -> proofs in both glue modes -------------------------------------------------
+MIMC_ROUNDS = 322
+
+
+@pytest.mark.parametrize("curve,order", [("bls12_381", "reverse"), ("bls12_381", 8101), ("bn254", "reverse")])
+def test_mimc(gpu_ctx, curve, order):
+    from polymath_amd import circuits as PC
+    r = CURVES[curve].r
+    g = PC.SplitMix64(7300)
+    consts = [g.fr(r) for _ in range(MIMC_ROUNDS)]
+    s = _cached((curve, "mimc", order), lambda: _setup(gpu_ctx, curve, PC.Reordered(PC.MiMCDemo(5, 7, consts), order), 11000))
+    pm, pk, f, q = s["pm"], s["pk"], s["f"], s["q"]
+    assert q.nr == 644 and q.m0 + q.mw == 647
+    partial = ([1, None], [0, 0] + [None] * (q.mw - 2))
+    assert _out_of_order(s, partial)
+    g = PC.SplitMix64(11100)
+    assignments = []
+    for _ in range(70):
+        xl, xr = g.fr(r), g.fr(r)
+        inst, wit = _native(PC.MiMCDemo(xl, xr, consts), r)
+        assert inst[1] == PC.mimc_native(r, xl, xr, consts) and wit[:2] == [xl, xr]
+        assignments.append((inst, wit))
+    _completes(s, assignments, partial)
+    got = pm.solve_batch(pk, [pm.partial_limbs([1, None], wit[:2] + [None] * (q.mw - 2)) for _, wit in assignments[:3]])
+    assert got == [(None, inst, wit) for inst, wit in assignments[:3]]
+    # inputs -> proofs: byte for byte the proofs of the completed assignments on the same key, in both glue modes
+    count = 3
+    _, rows = _rows(s, assignments[:count], partial)
+    limbs = [(np.ascontiguousarray(rows[i, :q.m0]), np.ascontiguousarray(rows[i, q.m0:])) for i in range(count)]
+    r_as = [[51 + i, 61 + i] for i in range(count)]
+    want = [pm.prove_native(pk, f.fr_limbs(inst), f.fr_limbs(wit), r_as[i]) for i, (inst, wit) in enumerate(assignments[:count])]
+    vk = pm.make_vk(pk, s["x"], s["z"])
+    for glue in ("host", "device"):
+        proofs, statuses, instances = pm.prove_batch(pk, limbs, r_as, solve=True, glue=glue)
+        assert statuses == [0] * count and instances == [inst for inst, _ in assignments[:count]], glue
+        assert proofs == want, glue
+    assert all(pm.verify(vk, assignments[i][0][1:], want[i]) for i in range(count))
+
+
+# ---- 2. the wide-level kernels: RangeCheck, decompositions before their booleanity rows ----------------------------------------------------------
+def _range_order(n, bits, order):
+    if order != "booleans last":
+        return order
+    per = bits + 1
+    return [i for i in range(n * per) if i % per == bits] + [i for i in range(n * per) if i % per != bits]
+
+
+@pytest.mark.parametrize("curve,n,order", [("bls12_381", 32, "reverse"), ("bls12_381", 32, "booleans last"), ("bls12_381", 257, 8201),
+                                           ("bls12_381", 257, "booleans last"), ("bn254", 32, 8202), ("bn254", 257, "reverse")])
+def test_range_check(gpu_ctx, curve, n, order):
+    from polymath_amd import circuits as PC
+    r, bits = CURVES[curve].r, 8
+    s = _cached((curve, "range", n, order), lambda: _setup(gpu_ctx, curve, PC.Reordered(PC.RangeCheck([j % (1 << bits) for j in range(n)], bits), _range_order(n, bits, order)), 11200 + n))
+    q = s["q"]
+    assert (q.m0, q.mw, q.nr) == (1, n * (bits + 1), n * (bits + 1))
+    g = PC.SplitMix64(11300 + n)
+    circuits = [PC.RangeCheck([g.next_u64() % (1 << bits) for _ in range(n)], bits) for _ in range(70)]
+    partial = circuits[0].partial(r)
+    _completes(s, [([1], ci.native()) for ci in circuits], partial)
+    # a value that does not fit is stuck at ITS row of the reordered matrices; the neighbours complete
+    per = bits + 1
+    order_rows = PC.row_order(n * per, _range_order(n, bits, order))
+    bad_value = 5 if n > 5 else 0
+    values = [3] * n
+    values[bad_value] = 1 << bits
+    want, rows = _rows(s, [([1], circuits[0].native()), ([1], PC.RangeCheck(values, bits).native()), ([1], circuits[1].native())], partial)
+    n_bad, stuck, full = _solve(s, rows)
+    assert stuck == [NONE, order_rows.index(bad_value * per + bits), NONE] and n_bad == [0, NONE, 0]
+    assert np.array_equal(full[0], want[0]) and np.array_equal(full[2], want[2])
+
+
+# ---- 3. ArxDemo: decompositions in A and in C, XOR rows and recompositions in one chain -------------------------------------------------------------
+@pytest.mark.parametrize("curve,order", [("bls12_381", "reverse"), ("bls12_381", 8301), ("bn254", 8302)])
+def test_arx(gpu_ctx, curve, order):
+    from polymath_amd import circuits as PC
+    r = CURVES[curve].r
+    width, rounds, rot = 16, 3, 5
+    s = _cached((curve, "arx", order), lambda: _setup(gpu_ctx, curve, PC.Reordered(PC.ArxDemo(1, 2, width, rounds, rot), order), 11400))
+    g = PC.SplitMix64(11500)
+    circuits = [PC.ArxDemo(g.next_u64() % (1 << width), g.next_u64() % (1 << width), width, rounds, rot) for _ in range(70)]
+    partial = circuits[0].partial(r)
+    assignments = [_native(ci, r) for ci in circuits]
+    assert all(inst[1] == PC.arx_native(ci.a, ci.b, width, rounds, rot) for (inst, _), ci in zip(assignments, circuits))
+    _completes(s, assignments, partial)
+
+
+# ---- 4. synthetic_r1cs, permuted: chains of narrow levels and wide levels of kind-C steps -----------------------------------------------------------
+@pytest.mark.parametrize("curve,order", [("bls12_381", "reverse"), ("bls12_381", 8401), ("bn254", 8402)])
+def test_synthetic(gpu_ctx, curve, order):
+    from polymath_amd import circuits as PC
+    from polymath_amd.polymath import R1CS
+    r, nr = CURVES[curve].r, 2000
+
+    def make():
+        q, inst, wit = PC.synthetic_r1cs(r, nr)
+        perm = PC.row_order(nr, order)
+        return _setup(gpu_ctx, curve, (R1CS(q.m0, q.mw, [q.a[i] for i in perm], [q.b[i] for i in perm], [q.c[i] for i in perm]), inst, wit), 11600)
+    s = _cached((curve, "synth", order), make)
+    q = s["q"]
+    partial = ([1, None], [0, 0] + [None] * (q.mw - 2))
+    assert _out_of_order(s, partial)
+
+    def evaluate(w0, w1):                                       # the gates in dependency order: gate i defines column 4 + i
+        z = {0: 1, 2: w0, 3: w1}
+        gates = sorted(zip(q.a, q.b, q.c), key=lambda g: g[2][0][1] if g[2][0][1] != 1 else 1 << 62)
+        for (alpha, p), (beta, qq), (_, t) in ((a[0], b[0], c[0]) for a, b, c in gates):
+            z[t] = (alpha * z[p] % r) * (beta * z[qq] % r) % r
+        full = [z[j] for j in range(q.m0 + q.mw)]
+        return full[:2], full[2:]
+    own = (list(s["inst"]), list(s["wit"]))
+    assert evaluate(own[1][0], own[1][1]) == own
+    _completes(s, [own, evaluate(12345, r - 2), evaluate(7, 9)], partial, counts=(1, 3))
+
+
+# ---- 5. is-zero pairs: whole gadgets move, the opener stays before its closer -------------------------------------------------------------------------
+def _match_inputs(g, r, n_values, mode):
+    key = g.fr(r)
+    hit = {0: lambda j: True, 1: lambda j: False, 2: lambda j: j % 2 == 0}[mode]
+    return [key if hit(j) else (key + 1 + g.next_u64()) % r for j in range(n_values)], key
+
+
+@pytest.mark.parametrize("curve,form,order", [("bls12_381", "ark", "reverse"), ("bls12_381", "circom", 8501), ("bn254", "circom", "reverse"), ("bn254", "ark", 8502)])
+def test_match_count(gpu_ctx, curve, form, order):
+    from polymath_amd import circuits as PC
+    r, n_values = CURVES[curve].r, 40
+    blocks = 3 if form == "ark" else 2
+    s = _cached((curve, "match", form, order), lambda: _setup(gpu_ctx, curve, PC.Reordered(PC.MatchCount(list(range(n_values)), 3, form), order, blocks=blocks), 11700))
+    g = PC.SplitMix64(11800)
+    circuits = [PC.MatchCount(*_match_inputs(g, r, n_values, i % 3), form) for i in range(70)]
+    partial = circuits[0].partial(r)
+    assignments = [ci.native(r) for ci in circuits]
+    assert [inst[1] for inst, _ in assignments[:3]] == [n_values, 0, n_values // 2]
+    _completes(s, assignments, partial)
+
+
+@pytest.mark.parametrize("curve,form,bits,order", [("bls12_381", "ark", 0, "reverse"), ("bls12_381", "circom", 8, 8601), ("bn254", "circom", 0, "reverse"),
+                                                   ("bn254", "ark", 8, "reverse")])
+def test_eq_chain(gpu_ctx, curve, form, bits, order):
+    from polymath_amd import circuits as PC
+    r, depth = CURVES[curve].r, 9
+    blocks = (4 if form == "ark" else 3) + (bits + 1 if bits else 0)
+    s = _cached((curve, "chain", form, bits, order),
+                lambda: _setup(gpu_ctx, curve, PC.Reordered(PC.EqChain(3, PC.eq_chain_targets(3, [False] * depth, r), form, bits=bits), order, blocks=blocks), 11900))
+    assert s["q"].nr == blocks * depth
+    g = PC.SplitMix64(12000 + bits)
+    circuits, seen = [], set()
+    for i in range(70):
+        x = 1 + g.next_u64() % 5 if bits else g.fr(r)
+        hits = [(i + j) % 3 != 1 for j in range(depth)] if bits == 0 else [j == i % depth for j in range(depth)]     # with bits the states stay below 2^8
+        seen.update(hits)
+        circuits.append(PC.EqChain(x, PC.eq_chain_targets(x, hits, r), form, bits=bits))
+    assert seen == {True, False}
+    partial = circuits[0].partial(r)
+    _completes(s, [ci.native(r) for ci in circuits], partial)
+
+
+# ---- 6. the stuck word names the root cause ---------------------------------------------------------------------------------------------------------
+# columns: 0 one | 1 out | 2 g  3 h  4 c2 (given) | 5 x  6 y (unknown)
+#   row 0: x * y = c2      row 1: g * x = h      row 2: y * 1 = out
+# The dependency order is row 1, row 0, row 2.  With g = h = 0 row 1 sticks (0 / 0), x is stored as zero, and row 0 then divides by it
+# and sticks as well: the smaller row is the consequence, the report must be row 1.
+def root_system():
+    from polymath_amd.polymath import R1CS
+    return R1CS(2, 5, [[(1, 5)], [(1, 2)], [(1, 6)]], [[(1, 6)], [(1, 5)], [(1, 0)]], [[(1, 4)], [(1, 3)], [(1, 1)]])
+
+
+def _root_key(gpu_ctx, curve):
+    return _cached((curve, "root"), lambda: _setup(gpu_ctx, curve, (root_system(), [1, 5], [3, 12, 20, 4, 5]), 12100))
+
+
+@pytest.mark.parametrize("curve", BOTH)
+def test_stuck_root(gpu_ctx, curve):
+    from polymath_amd import api
+    s = _root_key(gpu_ctx, curve)
+    pm, pk, f, r = s["pm"], s["pk"], s["f"], s["c"].r
+    L, vp, plen = gpu_ctx.L, (lambda a: a.ctypes.data_as(ct.c_void_p)), PROOF_LEN[curve]
+    good = [([1, None], [3, 12, 20, None, None]), ([1, None], [0, 0, 20, None, None]), ([1, None], [2, 14, 21, None, None])]
+    full = [(None, [1, 5], [3, 12, 20, 4, 5]), (1, None, None), (None, [1, 3], [2, 14, 21, 7, 3])]
+    partials = [pm.partial_limbs(*p) for p in good]
+    assert pm.solve_batch(pk, partials) == full                                                        # the neighbours complete
+    stuck, inst = pk.solve_results(3)                                                                   # tap 9
+    assert [int(v) for v in stuck] == [NONE, 1, NONE] and not inst[1].any()
+    assert pm.check_batch(pk, partials, max_rows=1, solve=True) == [(0, []), (NONE, [1]), (0, [])]
+    rc, n_bad, rows, _ = pk.r1cs_check(*partials[1], 3, solve=True)                                     # pm_r1cs_check: slot 0
+    assert (rc, n_bad, [int(v) for v in rows]) == (PM_OK, NONE, [1, NONE, NONE])
+    assert int(pk.solve_results(1)[0][0]) == 1
+    x, w = partials[1]                                                                                  # pm_host_prove: the error text
+    rc, _ = pk.host_prove("merlin", x, x, w, f.fr_limbs([3, 5]), solve=True)
+    assert rc == PM_ERR_INVALID_ARG and "stuck at row 1 " in pm.ctx.last_error(), pm.ctx.last_error()
+    # the batch status in both glue modes, with zeroed bytes where the assignment is stuck
+    xs, ws = np.stack([p[0] for p in partials]), np.stack([p[1] for p in partials])
+    r_as = [[31 + i, 41 + i] for i in range(3)]
+    ra = np.stack([f.fr_limbs(v) for v in r_as])
+    want = [pm.prove_native(pk, f.fr_limbs(full[i][1]), f.fr_limbs(full[i][2]), r_as[i]) for i in (0, 2)]
+    for glue in (0, api.PROVE_GLUE_DEVICE):
+        proofs, status = ct.create_string_buffer(b"M" * (3 * plen), 3 * plen), np.full(3, 77, dtype=np.int32)
+        rc = L.pm_host_prove_batch(gpu_ctx.h, pk.h, glue, 3, api._p(xs), vp(xs), vp(ws), 2, api._p(ra), proofs, plen, status.ctypes.data_as(ct.POINTER(ct.c_int)))
+        assert rc == PM_OK and list(status) == [0, PM_ERR_INVALID_ARG, 0], (glue, rc, status)
+        assert proofs.raw[plen:2 * plen] == bytes(plen) and proofs.raw[:plen] == want[0] and proofs.raw[2 * plen:] == want[1], glue
+        assert int(pk.solve_results(3)[0][1]) == 1, glue
+    # h != 0 with g = 0 sticks at row 1 as well; g != 0 and c2 = 0 gives x != 0, y = 0: nothing sticks
+    assert pm.solve_batch(pk, [pm.partial_limbs([1, None], [0, 9, 20, None, None]), pm.partial_limbs([1, None], [2, 14, 0, None, None])]) == \
+        [(1, None, None), (None, [1, 0], [2, 14, 0, 7, 0])]
+
+
+# ---- 7. refused as before: no order separates two unknowns, a closer with another known side stays a refusal ----------------------------------------
+def kinds_system():
+    """tests/test_gpu_witness_solve.py: 0 one | 1 out | 2 a  3 c  4 inv  5 q  6 s  7 e  8 pad"""
+    from polymath_amd.polymath import R1CS
+    return R1CS(2, 7, [[(3, 4)], [(1, 2)], [(1, 4)], [(1, 6), (1, 0)], [(1, 2)]], [[(1, 2)], [(5, 5)], [(1, 5)], [(1, 0)], [(1, 2)]],
+                [[(1, 0)], [(1, 3)], [(1, 6)], [(1, 1)], [(1, 7)]])
+
+
+def other_side_system(r):
+    """tests/test_gpu_witness_solve_iszero.py: 0 one | 1 out | 2 a  3 b | 4 flag  5 m; the closer's known side is a - 2 b"""
+    from polymath_amd.polymath import R1CS
+    lc = [(1, 2), (r - 1, 3)]
+    return R1CS(2, 4, [lc, [(1, 1)], [(1, 2), (r - 2, 3)]], [[(1, 5)], [(1, 0)], [(1, 0), (r - 1, 4)]], [[(1, 4)], [(1, 2)], []])
+
+
+@pytest.mark.parametrize("which", ["two unknowns", "other side"])
+def test_refused_as_before(gpu_ctx, which):
+    from polymath_amd import api
+    curve = "bls12_381"
+    r = CURVES[curve].r
+    if which == "two unknowns":
+        a, c = 11, 13
+        inv, q = pow(3 * a, r - 2, r), c * pow(5 * a, r - 2, r) % r
+        setup = (kinds_system(), [1, (inv * q + 1) % r], [a, c, inv, q, inv * q % r, a * a % r, 9])
+        partial = ([1, None], [None, 22, None, None, None, 441, 9])
+        text, needle = "row 0: two or more unknowns (columns 4 and 2)", "in any row order"
+    else:
+        setup = (other_side_system(r), [1, 8], [8, 4, 1, pow(4, r - 2, r)])
+        partial = ([1, None], [8, 5, None, None])
+        text, needle = "row 0: two or more unknowns (columns 5 and 4)", "row 2: its known side"
+    s = _cached((curve, "refused", which), lambda: _setup(gpu_ctx, curve, setup, 12200))
+    pm, pk, f = s["pm"], s["pk"], s["f"]
+    L, vp, plen = gpu_ctx.L, (lambda arr: arr.ctypes.data_as(ct.c_void_p)), PROOF_LEN[curve]
+    pairs = [pm.partial_limbs(*partial) for _ in range(3)]
+    xs, ws = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
+    n_bad, rows, abc = np.full(3, 77, dtype=np.uint64), np.full(6, 77, dtype=np.uint64), np.full(72, 77, dtype=np.uint64)
+    ra = np.stack([f.fr_limbs([3, 5])] * 3)
+    proofs, status, n = ct.create_string_buffer(b"M" * (3 * plen), 3 * plen), np.full(3, 77, dtype=np.int32), ct.c_size_t(99)
+    sp = status.ctypes.data_as(ct.POINTER(ct.c_int))
+    calls = [lambda: L.pm_r1cs_check(gpu_ctx.h, pk.h, vp(xs), vp(ws), 2, 2, api._p(n_bad), api._p(rows), api._p(abc)),
+             lambda: L.pm_r1cs_check_batch(gpu_ctx.h, pk.h, 3, vp(xs), vp(ws), 2, 2, api._p(n_bad), api._p(rows), api._p(abc)),
+             lambda: L.pm_host_prove(gpu_ctx.h, pk.h, 0, api._p(xs), vp(xs), vp(ws), 2, api._p(ra), proofs, plen, ct.byref(n)),
+             lambda: L.pm_host_prove_batch(gpu_ctx.h, pk.h, 0, 3, api._p(xs), vp(xs), vp(ws), 2, api._p(ra), proofs, plen, sp)]
+    for call in calls:
+        assert call() == PM_ERR_INVALID_ARG
+        error = gpu_ctx.last_error()
+        assert text in error and needle in error and error.index(text) < error.index(needle), error
+        assert (n_bad == 77).all() and (rows == 77).all() and (abc == 77).all()
+        assert proofs.raw == b"M" * (3 * plen) and (status == 77).all() and n.value == 99
+
+
+# ---- 8. the plan cache: an in-order and a reordered pattern alternate on one key --------------------------------------------------------------------
+def test_plan_cache_alternates(gpu_ctx):
+    s = _root_key(gpu_ctx, "bls12_381")
+    pm, pk = s["pm"], s["pk"]
+    reordered = pm.partial_limbs([1, None], [3, 12, 20, None, None])            # x from row 1, then y from row 0: not the matrix order
+    in_order = pm.partial_limbs([1, None], [3, 12, 20, 4, None])                # x given: y from row 0, row 1 a check row, out from row 2
+    stuck_reordered = pm.partial_limbs([1, None], [0, 0, 20, None, None])       # rows 1 and 0 stick: the root is row 1
+    stuck_in_order = pm.partial_limbs([1, None], [3, 12, 20, 0, None])          # x = 0 given: row 0 sticks
+    for _ in range(3):
+        assert pm.solve_batch(pk, [reordered, stuck_reordered]) == [(None, [1, 5], [3, 12, 20, 4, 5]), (1, None, None)]
+        assert pm.solve_batch(pk, [in_order, stuck_in_order]) == [(None, [1, 5], [3, 12, 20, 4, 5]), (0, None, None)]
+    assert pm.check_batch(pk, [in_order, stuck_in_order], max_rows=1, solve=True) == [(0, []), (NONE, [0])]
+
+
+# ---- 9. grouping: one group or several, host rows or device rows: the same words and the same bytes -------------------------------------------------
+def test_groups_and_device_pointers(gpu_ctx):
+    from polymath_amd import circuits as PC
+    curve, form, n_values, count = "bls12_381", "ark", 40, 5
+    r = CURVES[curve].r
+    s = _cached((curve, "match", form, "reverse"), lambda: _setup(gpu_ctx, curve, PC.Reordered(PC.MatchCount(list(range(n_values)), 3, form), "reverse", blocks=3), 11700))
+    pm, pk, f, q = s["pm"], s["pk"], s["f"], s["q"]
+    g = PC.SplitMix64(12300)
+    circuits = [PC.MatchCount(*_match_inputs(g, r, n_values, i % 3), form) for i in range(count)]
+    full = [ci.native(r) for ci in circuits]
+    want, rows = _rows(s, full, circuits[0].partial(r))
+    xs, ws = np.ascontiguousarray(rows[:, :q.m0]), np.ascontiguousarray(rows[:, q.m0:])
+    limbs = [(xs[i], ws[i]) for i in range(count)]
+    r_as = [[71 + i, 81 + i] for i in range(count)]
+    proofs, statuses, instances = pm.prove_batch(pk, limbs, r_as, solve=True)
+    assert statuses == [0] * count and instances == [x for x, _ in full]
+    for i in range(count):
+        assert proofs[i] == pm.prove_native(pk, f.fr_limbs(full[i][0]), f.fr_limbs(full[i][1]), r_as[i])
+    dx, dw = torch.from_numpy(xs.view(np.int64)).cuda(), torch.from_numpy(ws.view(np.int64)).cuda()
+    torch.cuda.synchronize()
+    ncols = q.m0 + q.mw
+    check_log = (2 * ncols - 1).bit_length()
+    assert 2 * ncols <= 1 << check_log < 4 * ncols                         # the check solves in groups of 2 or 3
+    gpu_ctx.set_option("msm_max_piece_log", check_log)                     # (restored by conftest)
+    for device in (False, True):
+        if device:
+            rc, n_bad, _, _ = pk.r1cs_check_batch(dx.data_ptr(), dw.data_ptr(), 2, on_device=True, count=count, solve=True)
+        else:
+            rc, n_bad, _, _ = pk.r1cs_check_batch(xs, ws, 2, solve=True)
+        assert rc == PM_OK and not n_bad.any(), pm.ctx.last_error()
+        assert np.array_equal(pk.solved_assignments(count, q.mw), want), device
+    prove_log = (10 * pk.n + 22 - 1).bit_length()
+    assert 10 * pk.n + 22 <= 1 << prove_log < 2 * (10 * pk.n + 22)         # the prover in groups of 1
+    gpu_ctx.set_option("msm_max_piece_log", prove_log)
+    for glue in ("host", "device"):
+        assert pm.prove_batch(pk, limbs, r_as, solve=True, glue=glue)[0] == proofs, glue
+    got = pm.prove_batch(pk, limbs, r_as, device_ptrs=(dx.data_ptr(), dw.data_ptr()), solve=True)
+    assert got[0] == proofs and got[2] == instances
+    assert np.array_equal(dx.cpu().numpy().view(np.uint64).reshape(xs.shape), xs)           # the caller's device rows are only read
+    assert np.array_equal(dw.cpu().numpy().view(np.uint64).reshape(ws.shape), ws)

@@ -15,6 +15,10 @@ is the same comparison on a boolean circuit (bit decompositions, XOR rows), and
   python tools/prove_bench.py --circuit matchcount --batch 256 --reps 5 --solve  MatchCount, 1024 values, arkworks' form;
                                                                                  matchcount:N:FORM (FORM = ark or circom) for others
 on one that tests equality (one dependency level of N is-zero pairs; about half of the values match).
+  python tools/prove_bench.py --circuit mimc322 --batch 256 --reps 5 --solve --reorder reverse     or --reorder SEED
+runs either --solve comparison on the same circuit with its constraint rows stored in another order (circuits.Reordered: reversed, or
+shuffled by SEED; a matchcount gadget moves as a block so that every opener stays before its closer).  Route (b) then goes through the
+solver's any-order planner and the reordered plan's stuck key; route (a) is unchanged work.  UNMEASURED: no run of it is recorded.
   python tools/prove_bench.py --circuit mimc322 --batch 256 --reps 5 --glue device
 compares the two glue modes of the batch call itself, alternating in this process, same key, same device-resident assignments:
   (a) pm_host_prove_batch, host glue (about six synchronisations a group)   (b) the same call with PM_PROVE_GLUE_DEVICE (one a group)
@@ -36,9 +40,12 @@ ap.add_argument("--transcript", default="merlin")
 ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="pm_ctx_set_option before the key is made, e.g. --opt tables=0")
 ap.add_argument("--glue", choices=("host", "device"), default="host", help="device: host glue against device glue of the batch call")
 ap.add_argument("--solve", action="store_true", help="host-synthesised assignments against partial assignments solved on the GPU")
+ap.add_argument("--reorder", default=None, metavar="reverse|SEED", help="with --solve: the circuit's rows stored reversed or shuffled by SEED (unmeasured)")
 a = ap.parse_args()
 if a.solve and not a.circuit.startswith(("mimc", "arx", "matchcount")):
     ap.error("--solve needs a mimcK, an arx or a matchcount circuit")
+if a.reorder is not None and not a.solve:
+    ap.error("--reorder goes with --solve")
 pm = Polymath(a.curve, a.transcript, device=0)
 for kv in a.opt:
     pm.ctx.set_option(kv.split("=", 1)[0], int(kv.split("=", 1)[1]))
@@ -65,14 +72,20 @@ elif a.circuit.startswith("matchcount"):
 else:
     nc = int(a.circuit.split(":", 1)[1])
     make = lambda: PC.BenchCircuit(g.fr(r), g.fr(r), 10, nc)
+if a.reorder is None:
+    stored = lambda c: c
+else:       # the same variables and values, the rows in another order; `circuits` keeps the inner generators (partial_of, again)
+    order = "reverse" if a.reorder == "reverse" else int(a.reorder)
+    blocks = {"ark": 3, "circom": 2}[form] if a.circuit.startswith("matchcount") else 1
+    stored = lambda c: PC.Reordered(c, order, blocks=blocks)
 B, distinct = a.batch, min(a.batch, 32)
 circuits = [make() for _ in range(distinct)]
 t0 = time.time()
-pk = pm.setup(circuits[0], g.fr(r), g.fr(r))
+pk = pm.setup(stored(circuits[0]), g.fr(r), g.fr(r))
 setup_s = time.time() - t0
 rows = []
 for c in circuits:
-    _, inst, wit = pm._synthesize(c)
+    _, inst, wit = pm._synthesize(stored(c))
     rows.append((pm.field.fr_limbs(inst), pm.field.fr_limbs(wit), [g.fr(r), g.fr(r)]))
 pick = [i % distinct for i in range(B)]
 xs = np.ascontiguousarray(np.stack([rows[i][0] for i in pick]))
@@ -94,7 +107,7 @@ def solve_comparison():
         t_syn = 0.0
         full = []
         for c in inputs:
-            _, inst, wit = pm._synthesize(again(c))
+            _, inst, wit = pm._synthesize(stored(again(c)))
             full.append((pm.field.fr_limbs(inst), pm.field.fr_limbs(wit)))
         t_syn = time.perf_counter() - t0
         proofs, status = pm.prove_batch(pk, full, ra_all)
@@ -116,7 +129,7 @@ def solve_comparison():
         tsyn.append(syn)
         dt, _, tm_solve = run_solve()
         tsv.append(dt)
-    print(json.dumps({"curve": a.curve, "circuit": a.circuit, "n": pk.n, "batch": B, "bytes_equal": ph == ps, "setup_s": round(setup_s, 3),
+    print(json.dumps({"curve": a.curve, "circuit": a.circuit, "reorder": a.reorder, "n": pk.n, "batch": B, "bytes_equal": ph == ps, "setup_s": round(setup_s, 3),
                       "host_synthesis_ms": [round(t * 1e3, 3) for t in th], "of_which_synthesis_ms": [round(t * 1e3, 3) for t in tsyn],
                       "solve_ms": [round(t * 1e3, 3) for t in tsv],
                       "host_proofs_per_s": round(B / med(th), 1), "solve_proofs_per_s": round(B / med(tsv), 1),
