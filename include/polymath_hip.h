@@ -300,7 +300,8 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  * existing argument: the set of entry points and the option table are pinned).  0 and 1 mean what they always meant; a bit outside
  * the two below is PM_ERR_INVALID_ARG.  The other entry points with such an argument (pm_host_prove_sharded, the phases) do not solve.
  *   PM_ASSIGNMENT_SOLVE: the caller supplies only the values it chooses; every Fr of x or w whose four words are UINT64_MAX (>= r on
- *     both curves, so never a field element) is UNKNOWN and is computed on the device first, by forward propagation through the key's
+ *     both curves, so never a field element; or the quotient marker, which differs in the lowest bit: "a division row" below) is
+ *     UNKNOWN and is computed on the device first, by forward propagation through the key's
  *     resident constraint rows (first-entry rule applied, as the prover and pm_r1cs_check read them; a stored entry with a zero
  *     coefficient names no variable).  The call then runs on the completed assignment and its results are, bit for bit, those of the
  *     same call without the flag on that assignment.  instance_host of the prove calls uses the same marker: unknown public inputs are
@@ -319,6 +320,28 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  *                                                k <= bitlength(r) - 1 (254 on BLS12-381's Fr, 253 on BN254's: the solution is then unique).
  *                                                ONE step for all k columns: t = the ordinary formula of that matrix with the k entries left
  *                                                out and coef = c; z_{u_i} = bit i of the canonical integer of t, as field 0 or field 1
+ *     a division row                          -- ONE row with two fresh unknowns q (the quotient) and rem (the remainder), each named once,
+ *                                                where the caller marks q with PM_UNKNOWN_QUOTIENT_WORDS (below) instead of the plain
+ *                                                marker: circom's  q <-- a \ b; rem <-- a % b; q*b + rem === a , arkworks' DIV / REM and
+ *                                                reductions by a non-power-of-two modulus.  One of A_r, B_r has (cq, q) as its only non-zero
+ *                                                entry, the other is the known divisor side K (no unknown, not zero), C_r names rem with
+ *                                                coefficient -cq beside any known rest R.  ONE step for both columns; with d = K z and
+ *                                                a = R / cq read as canonical integers below r:
+ *                                                  d != 0:  q = floor(a / d),  rem = a mod d   (q d + rem = a in the integers, so the row
+ *                                                           holds; a 256-bit integer division per row and assignment)
+ *                                                  d == 0:  the assignment is STUCK at row r
+ *                                                The marker is explicit, as circom's <-- is: the row has the shape of an is-zero opener and
+ *                                                nothing is inferred -- with the plain marker on q it is an opener, as it always was.  The
+ *                                                quotient marker has meaning in that position only: a column that carries it and is the
+ *                                                single unknown of an ordinary row is solved by that row, and named anywhere else it is a
+ *                                                plain unknown.  Such a row is never an opener and waits for no closer.  A row with two or
+ *                                                more unknowns whose quotient-marked column is the lone entry of A_r or B_r and which misses
+ *                                                a condition is unsolvable; pm_last_error says which after ", and no division row: "
+ *                                                (cr != -cq; rem in A or B; rem named twice; the other side not known; the quotient named
+ *                                                twice; a third unknown).  The range checks that make the Euclidean pair the row's ONLY
+ *                                                solution (rem < d, and q small enough that q d + rem does not wrap) are the circuit's: they
+ *                                                are decomposition rows like any other.  Not handled: signed division, cr != -cq, a known
+ *                                                rest beside q on its side, a division without the marker
  *     an is-zero pair                         -- the two rows every equality test compiles to, with two fresh unknowns m (the multiplier)
  *                                                and b (the flag):  arkworks  (a - b) mult = neq ; (a - b) (1 - neq) = 0
  *                                                                   circom    (-in) inv = out - 1 ; in out = 0
@@ -360,10 +383,11 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  *   per-assignment patterns, sharded keys.
  *   PM_ERR_INVALID_ARG, pm_last_error naming the row or column, nothing computed and no output written: an unsolvable row, a marked
  *   column that no row determines, a marker at column 0, a sharded key, and -- in a batch -- an assignment that does not mark the
- *   columns assignment 0 marks (the first differing (assignment, column) is named; a kernel compares them).
+ *   columns assignment 0 marks, or marks one with the other marker (the first differing (assignment, column) is named; a kernel
+ *   compares them).
  *   At run time a step that would divide by zero (Bz = 0 with u in A) leaves that assignment STUCK, even where Cz = 0 too (the value
  *   is then undetermined), and so does a decomposition whose t is 2^k or more (no boolean solution; its k values are stored as
- *   zero): its other solved values are undefined, its neighbours are not affected, and its smallest stuck row is
+ *   zero) and a division row whose divisor is zero (both values are stored as zero): its other solved values are undefined, its neighbours are not affected, and its smallest stuck row is
  *   reported (a 64-bit atomic minimum: the same word on every run, since everything downstream of a stuck row has a larger index).
  *   Where the rows were reordered that is not so -- a row that reads the stored zero may stick too, at a smaller index -- and the row
  *   reported is the ROOT CAUSE: among the stuck rows the one of lowest dependency level, then smallest index, which read only valid
@@ -380,6 +404,11 @@ typedef enum pm_assignment_flags {
     PM_ASSIGNMENT_DEVICE = 1,   /* x, w are device pointers (what "non-zero" has meant) */
     PM_ASSIGNMENT_SOLVE = 2     /* entries equal to the unknown marker are solved first */
 } pm_assignment_flags;
+/* The two markers of PM_ASSIGNMENT_SOLVE, as initialisers of a uint64_t[4] (little-endian words of one Fr).  Both are >= r on both
+ * curves, so neither is ever a field element.  PM_UNKNOWN_WORDS: the value is unknown.  PM_UNKNOWN_QUOTIENT_WORDS: the value is
+ * unknown, and it is the Euclidean quotient of its division row (the rule above); everywhere else it means what PM_UNKNOWN_WORDS means. */
+#define PM_UNKNOWN_WORDS { UINT64_MAX, UINT64_MAX, UINT64_MAX, UINT64_MAX }
+#define PM_UNKNOWN_QUOTIENT_WORDS { UINT64_MAX - 1, UINT64_MAX, UINT64_MAX, UINT64_MAX }
 
 /* Whole create_proof_with_assignment (prover.rs:66-237) for an UNSHARDED key, transcript included: the three
  * phases above plus the host glue between them (compute_x1 / compute_x2, common.rs:21-71; pi and c at x1,

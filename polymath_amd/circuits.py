@@ -2,9 +2,10 @@
 (tests/dummy.rs:20-35, tests/mimc.rs:74-143, benches/bench.rs:38-61) and the synthetic
 "random A*B=C gates" R1CS BASELINE.json quotes the headline metric on, and two boolean circuits of this project's
 own (RangeCheck, ArxDemo) and two that branch on equality (MatchCount, EqChain: is-zero pairs in arkworks' and in circom's form) whose
-witnesses the device completes from the inputs (PM_ASSIGNMENT_SOLVE); Reordered emits any of them with its rows in
-another order, which the solver's any-order planner accepts."""
-from .polymath import ConstraintSystem, Field, LimbCircuit, R1CS
+witnesses the device completes from the inputs (PM_ASSIGNMENT_SOLVE), and two that divide integers (DivRem,
+ModChain: Euclidean division rows, whose quotients partial() marks QUOTIENT); Reordered emits any of them with its rows in another
+order, which the solver's any-order planner accepts."""
+from .polymath import QUOTIENT, ConstraintSystem, Field, LimbCircuit, R1CS
 
 SPLITMIX_SEED = 0x706F6C796D617468  # "polymath"
 _M64 = (1 << 64) - 1
@@ -324,6 +325,106 @@ def eq_chain_targets(x, hits, r, miss=5):
         targets.append(t)
         s = (s + 1 + (t if hit else 0)) % r
     return targets
+
+
+class _PartialDivisions(_Partial):
+    """_Partial for circuits with Euclidean division rows  q * b = a - rem  (circom's q <-- a \\ b; rem <-- a % b; q*b + rem === a):
+    partial() marks every quotient QUOTIENT -- the explicit "this unknown is a quotient" that the solver asks for, since the row has
+    the shape of an is-zero opener -- and leaves the remainders, and the bits of the range checks, None."""
+
+    def _division(self, cs, a_lc, a_v, b, b_v, bits, last_rem=None):
+        """witnesses q, rem (or the variable last_rem(rem_v) makes) and, with bits > 0, the boolean witnesses of three range checks
+        -- booleanity rows first -- then the division row and  rem * 1 = sum 2^i .. ;  (b - 1 - rem) * 1 = sum 2^i .. ;
+        q * 1 = sum 2^i ..  , which make the Euclidean pair the row's only solution.  b_v == 0 has no solution: zeros are written
+        (the device reports the row as stuck).  -> (q, rem, q_v, rem_v)"""
+        one = ConstraintSystem.ONE
+        q_v, rem_v = divmod(a_v, b_v) if b_v else (0, 0)
+        self._quotients.append(len(cs.witness))
+        q = cs.new_witness_variable(q_v)
+        rem = last_rem(rem_v) if last_rem else cs.new_witness_variable(rem_v)
+        checks = [([(1, rem)], rem_v), ([(1, b), (-1, one), (-1, rem)], (b_v - 1 - rem_v) % cs.r), ([(1, q)], q_v)] if bits else []
+        checks = [(lc, _new_bits(cs, v, bits)) for lc, v in checks]
+        cs.enforce_constraint([(1, q)], [(1, b)], a_lc + [(-1, rem)])
+        for lc, bit_vars in checks:
+            cs.enforce_constraint(lc, [(1, one)], _weighted(bit_vars))
+        return q, rem, q_v, rem_v
+
+    def partial(self, r):
+        instance, witness = super().partial(r)
+        for j in self._quotients:
+            witness[j] = QUOTIENT
+        return instance, witness
+
+    def native(self, r):
+        """-> (instance, witness) as the rows define them, on Python integers"""
+        cs = ConstraintSystem(r)
+        self.generate_constraints(cs)
+        return list(cs.instance), list(cs.witness)
+
+
+class DivRem(_PartialDivisions):
+    """N independent Euclidean divisions of `bits`-bit operands: per pair (a, b) the given witnesses a and b, the witnesses q and rem,
+    3 x bits boolean witnesses with their booleanity rows, the division row  q * b = a - rem  and the three range checks of
+    _division.  The public input is sum (q_i + rem_i).  ONE dependency level of N divisions, then one of 3 N decompositions, then
+    the sum.  The caller chooses the pairs; b = 0 has no assignment."""
+
+    def __init__(self, pairs, bits):
+        self.pairs, self.bits = [tuple(p) for p in pairs], bits
+
+    def generate_constraints(self, cs):
+        self._chosen, self._quotients = [], []
+        total, total_v = [], 0
+        for a_v, b_v in self.pairs:
+            assert 0 <= a_v < 1 << self.bits and 0 <= b_v < 1 << self.bits
+            a, b = self._given(cs, a_v), self._given(cs, b_v)
+            q, rem, q_v, rem_v = self._division(cs, [(1, a)], a_v, b, b_v, self.bits)
+            total += [(1, q), (1, rem)]
+            total_v += q_v + rem_v
+        out = cs.new_input_variable(total_v % cs.r)
+        cs.enforce_constraint(total, [(1, ConstraintSystem.ONE)], [(1, out)])
+
+    def native(self, r):
+        """-> (instance, witness) on Python integers, without generating a row: per pair a, b, q, rem, then the bits of rem, of
+        b - 1 - rem and of q, least significant first (what generate_constraints writes)"""
+        witness, total = [], 0
+        for a, b in self.pairs:
+            q, rem = divmod(a, b) if b else (0, 0)
+            witness += [a, b, q, rem]
+            for v in (rem, (b - 1 - rem) % r, q):
+                witness += [(v >> i) & 1 for i in range(self.bits)]
+            total += q + rem
+        return [1, total % r], witness
+
+
+class ModChain(_PartialDivisions):
+    """A linear congruential recurrence  s_{i+1} = (g s_i + c) mod m  over `steps` steps: the given witnesses s_0, g, c and m, per step
+    the product  g * s_i = p_i  and the division row  q_i * m = p_i + c - s_{i+1} ; s_steps is the public input.  Two narrow
+    dependency levels per step, so the whole circuit is one run of the solver's chain kernel.  g s_i + c must stay below r (the
+    operands are small integers).  With bits > 0 every step carries the three range checks of _division."""
+
+    def __init__(self, s0, g, c, m, steps, bits=0):
+        assert steps >= 1
+        self.s0, self.g, self.c, self.m, self.steps, self.bits = s0, g, c, m, steps, bits
+
+    def generate_constraints(self, cs):
+        self._chosen, self._quotients = [], []
+        one = ConstraintSystem.ONE
+        s_v = self.s0
+        s, g, c, m = (self._given(cs, v) for v in (self.s0, self.g, self.c, self.m))
+        for i in range(self.steps):
+            p_v = self.g * s_v
+            assert p_v + self.c < cs.r
+            p = cs.new_witness_variable(p_v)
+            cs.enforce_constraint([(1, g)], [(1, s)], [(1, p)])
+            last = cs.new_input_variable if i == self.steps - 1 else None
+            _, s, _, s_v = self._division(cs, [(1, p), (1, c)], p_v + self.c, m, self.m, self.bits, last_rem=last)
+
+
+def mod_chain_native(s0, g, c, m, steps):
+    """ModChain's public output on plain integers"""
+    for _ in range(steps):
+        s0 = (g * s0 + c) % m
+    return s0
 
 
 def row_order(nr, order, blocks=1):

@@ -86,7 +86,8 @@ namespace {
 
 constexpr uint64_t NOT_STUCK = ~(uint64_t)0;
 
-inline bool is_marker(const uint64_t *fr) { return (fr[0] & fr[1] & fr[2] & fr[3]) == ~(uint64_t)0; }
+// either marker of an unknown entry: the quotient's differs in the lowest bit
+inline bool is_marker(const uint64_t *fr) { return ((fr[0] | 1) & fr[1] & fr[2] & fr[3]) == ~(uint64_t)0; }
 
 // instance_host with its unknown entries replaced by the solved values of assignment i (tap 9): what gets hashed
 void solved_instance(const pm_ctx *ctx, const pm_pk *pk, size_t i, const uint64_t *instance_host, uint64_t *out) {

@@ -46,11 +46,11 @@ __device__ __forceinline__ bool glue_row_live(const GlueRows<C> &g, unsigned i) 
     return phase1_flag_status(g.flags[i]) == PM_OK && !(g.stuck && g.stuck[i] != GLUE_NOT_STUCK);
 }
 
-// the all-ones marker of an unknown entry (include/polymath_hip.h: PM_ASSIGNMENT_SOLVE)
+// either marker of an unknown entry (include/polymath_hip.h: PM_ASSIGNMENT_SOLVE): all ones, the quotient's with the lowest bit clear
 template <class P>
 __device__ __forceinline__ bool glue_is_marker(const Fp<P> &v) {
-    uint32_t all = 0xffffffffu;
-    for (int k = 0; k < 8; ++k) all &= v.l[k];
+    uint32_t all = v.l[0] | 1u;
+    for (int k = 1; k < 8; ++k) all &= v.l[k];
     return all == 0xffffffffu;
 }
 

@@ -2,25 +2,30 @@
 // (include/polymath_hip.h), so that a caller supplies only the values it chooses and the library computes the rest
 // before it checks or proves.  The PLAN -- which row determines which column, in which order -- is host work, done once per (key,
 // pattern) by host/solve_plan.hpp; the arithmetic is the kernels below, assignment = grid y (or the lane, in the chain kernel):
-//   k_solve_pattern   one lane per (column, assignment): the unknown pattern of assignment 0; every other assignment is compared
-//                     with it and the first differing (assignment, column) lowers one word
-//   k_solve_inv       one lane per step, once per plan: 1 / coefficient of the step's unknown; two more lanes per is-zero pair:
-//                     1 / cm and 1 / cb of its opener
+//   k_solve_pattern   one lane per (column, assignment): the unknown pattern of assignment 0 (a byte per column: 1 the unknown
+//                     marker, 2 the quotient marker); every other assignment is compared with it, byte for byte, and the first
+//                     differing (assignment, column) lowers one word
+//   k_solve_inv       one lane per step, once per plan: 1 / coefficient of the step's unknown (a division row: 1 / cq); two more
+//                     lanes per is-zero pair: 1 / cm and 1 / cb of its opener
 //   k_solve_level     a WIDE dependency level: one lane per (step, assignment); a level is its own launch, so stream order is
 //                     the dependency order
 //   k_solve_bits      the bit decompositions of a wide level, one lane per (step, assignment) as well: a launch of their own, so
 //                     that lanes doing one store do not sit beside lanes doing k
 //   k_solve_iszero    the is-zero pairs of a wide level, one lane per (step, assignment) as well: two stores and one inversion each
+//   k_solve_divrem    the division rows of a wide level, one lane per (step, assignment) as well: two stores and one 256-bit
+//                     integer division each (divrem.cuh: a fixed trip count, so a wave does not diverge on operand size)
 //   k_solve_chain     a run of consecutive NARROW levels: one lane per assignment walks the run's steps in plan order.  A lane
 //                     reads back only its own stores: no barriers, no fences.  The MiMC shape (depth 644, width 1) is one such run
 //                     and the batch is its parallel dimension.
 // The solving kernels exist twice: DIV = false for ranges of kind-C steps only, DIV = true for ranges with kind-A / kind-B steps,
 // or is-zero pairs, which call inverse<P> (a Fermat chain) -- the plan sorts a level by kind, so kind-C ranges do not carry its
-// registers, and the is-zero step exists in the DIV = true chain only.
+// registers, and the is-zero step and the division step (a dividing one by the plan's count, for 1 / cq) exist in the DIV = true
+// chain only.
 //   k_solve_stuck_row after the launches of a REORDERED plan (build_plan_any_order found a dependency order that is not the matrix
 //                     order): one lane per assignment turns the stuck word's (level, row) into the row
 // A step that would divide by zero stores zero and lowers the assignment's stuck word to its row (64-bit atomic minimum: the same
-// word on every run); so does a decomposition whose value has no k-bit form, in all its k columns.  In matrix order everything
+// word on every run); so does a decomposition whose value has no k-bit form, in all its k columns, and a division row whose
+// divisor is zero, in both its columns.  In matrix order everything
 // downstream of a stuck row has a larger row, so the minimum is the root cause.  Under a reordered plan that is false -- a step that
 // reads the stored zero may stick too, at a smaller row -- so the word is lowered to (level << 32) | row there: the minimum is the
 // stuck step of lowest level, then smallest row, which read only valid values, and k_solve_stuck_row leaves its row in the word.  Every other store has one
@@ -31,6 +36,7 @@
 
 #include "internal.h"
 #include "prove_common.cuh"
+#include "divrem.cuh"
 
 namespace pm {
 
@@ -41,6 +47,7 @@ struct SolveStepDev {
     uint64_t pos;                    // the unknown's entry in its matrix; a decomposition: the entry that holds c
     uint32_t row, col, kind, bits;   // bits != 0: a decomposition into the columns bit_cols[col .. col + bits), exponent order;
                                      // kind == KIND_ISZERO: row = the closer, pos / col = the flag's entry in it, bits = its SolvePairDev
+                                     // kind == KIND_DIVREM: pos / col = the quotient's entry, inv = 1 / cq, bits = its SolveDivDev
     Fp<P> inv;                       // 1 / coefficient (k_solve_inv)
     uint32_t level, pad;             // a stuck step lowers the stuck word to (level << 32) | row; level is 0 unless the plan is reordered
 };
@@ -55,6 +62,12 @@ struct SolvePairDev {
     Fp<P> inv_cm, inv_cb;            // k_solve_inv
 };
 
+// what a division step needs beside its SolveStepDev
+struct SolveDivDev {
+    uint64_t pos_r;                  // (cr, rem) in C_r
+    uint32_t col_r, q_in_b;          // the remainder's column; K = A_r (the quotient lies in B_r), 0: K = B_r
+};
+
 // What a stuck step lowers the stuck word to.  The level is read HERE, on the rare path (a volatile load the compiler cannot hoist
 // into the registers every step carries): the step bodies keep the registers they had.
 template <class P>
@@ -63,12 +76,10 @@ __device__ __forceinline__ unsigned long long stuck_key(const SolveStepDev<P> &s
     return (unsigned long long)level << 32 | s.row;
 }
 
+// either marker (divrem.cuh: marker_byte)
 template <class P>
 __device__ __forceinline__ bool is_marker(const Fp<P> &v) {
-    uint32_t a = ~0u;
-#pragma unroll
-    for (int i = 0; i < P::N; ++i) a &= v.l[i];
-    return a == ~0u;
+    return marker_byte<P>(v) != 0;
 }
 
 // xw: [g][ncols], the group's rows; g0 = the batch index of row 0.  pattern: one byte per column, written from assignment 0 of the
@@ -78,12 +89,12 @@ template <class P>
 __global__ __launch_bounds__(256) void k_solve_pattern(const Fp<P> *xw, uint64_t ncols, uint64_t g0, uint8_t *pattern, unsigned long long *mismatch) {
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (j >= ncols) return;
-    const bool unknown = is_marker<P>(xw[b * ncols + j]);
+    const uint8_t unknown = marker_byte<P>(xw[b * ncols + j]);
     if (g0 + b == 0) {
-        pattern[j] = unknown ? 1 : 0;
+        pattern[j] = unknown;
         return;
     }
-    const bool expected = g0 == 0 ? is_marker<P>(xw[j]) : pattern[j] != 0;
+    const uint8_t expected = g0 == 0 ? marker_byte<P>(xw[j]) : pattern[j];
     if (unknown != expected) atomicMin(mismatch, (unsigned long long)(((g0 + b) << 32) | j));
 }
 
@@ -95,14 +106,16 @@ __device__ __forceinline__ const CsrDev &matrix_of(uint32_t kind, const CsrDev &
 __device__ __forceinline__ uint32_t matrix_kind(uint32_t kind) { return kind >= pmsolve::KIND_BITS_C ? kind - pmsolve::KIND_BITS_C : kind; }
 
 template <class P>
-__global__ __launch_bounds__(256) void k_solve_inv(CsrDev A, CsrDev B, CsrDev Cm, SolveStepDev<P> *steps, uint64_t count, SolvePairDev<P> *pairs, uint64_t n_pairs) {
+__global__ __launch_bounds__(256) void k_solve_inv(CsrDev A, CsrDev B, CsrDev Cm, SolveStepDev<P> *steps, uint64_t count, SolvePairDev<P> *pairs, uint64_t n_pairs,
+                                                   const SolveDivDev *divs) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count + 2 * n_pairs) return;
     const Fp<P> *at;
     Fp<P> *out;
-    if (t < count) {                 // an is-zero step's own entry is the flag's, in the closer's A or B
+    if (t < count) {                 // an is-zero step's own entry is the flag's, in the closer's A or B; a division step's the quotient's
         const uint32_t kind = steps[t].kind;
-        const CsrDev &M = kind == pmsolve::KIND_ISZERO ? (pairs[steps[t].bits].b_in_b ? B : A) : matrix_of(matrix_kind(kind), A, B, Cm);
+        const CsrDev &M = kind == pmsolve::KIND_ISZERO ? (pairs[steps[t].bits].b_in_b ? B : A)
+                        : kind == pmsolve::KIND_DIVREM ? (divs[steps[t].bits].q_in_b ? B : A) : matrix_of(matrix_kind(kind), A, B, Cm);
         at = (const Fp<P> *)(M.val + 4 * steps[t].pos);
         out = &steps[t].inv;
     } else {
@@ -235,6 +248,23 @@ __device__ __forceinline__ void solve_iszero(const CsrDev &A, const CsrDev &B, c
     z[pr.col_m] = mul<P>(mul<P>(c1, inv1), pr.inv_cm);
 }
 
+// one division row on one assignment: cq q (K z) = R - cq rem, so with d = K z and a = R / cq as canonical integers
+//   d != 0:  q = floor(a / d),  rem = a mod d      (euclid_divrem: Montgomery -> canonical, 256 / 256 bits, back)
+//   d == 0:  stuck at the row, zero in both columns
+// The partial dot products as the is-zero step forms them: K's whole row and C's without rem's entry; the quotient's side has no
+// other non-zero entry, so its partial dot product is zero and is not formed.  Both columns still hold their markers.
+template <class P>
+__device__ __forceinline__ void solve_divrem(const CsrDev &A, const CsrDev &B, const CsrDev &Cm, const SolveStepDev<P> &s, const SolveDivDev &dv, Fp<P> *z,
+                                             unsigned long long *stuck) {
+    const uint64_t r = s.row;
+    const Fp<P> d = row_dot_skip<P>(dv.q_in_b ? A : B, z, r, SOLVE_NONE);
+    const Fp<P> a = mul<P>(row_dot_skip<P>(Cm, z, r, dv.pos_r), s.inv);
+    Fp<P> q = Fp<P>::zero(), rem = Fp<P>::zero();
+    if (!euclid_divrem<P>(a, d, &q, &rem)) atomicMin(stuck, stuck_key<P>(s));
+    z[s.col] = q;
+    z[dv.col_r] = rem;
+}
+
 template <class P, bool DIV>
 __global__ __launch_bounds__(256) void k_solve_level(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, uint32_t lo, uint32_t hi,
                                                      Fp<P> *xw, uint64_t ncols, unsigned long long *stuck) {
@@ -259,12 +289,21 @@ __global__ __launch_bounds__(256) void k_solve_iszero(CsrDev A, CsrDev B, CsrDev
     solve_iszero<P>(A, B, Cm, steps[t], pairs[steps[t].bits], xw + b * ncols);
 }
 
+template <class P>
+__global__ __launch_bounds__(256) void k_solve_divrem(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, const SolveDivDev *__restrict__ divs,
+                                                      uint32_t lo, uint32_t hi, Fp<P> *xw, uint64_t ncols, unsigned long long *stuck) {
+    const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (t >= hi) return;
+    solve_divrem<P>(A, B, Cm, steps[t], divs[steps[t].bits], xw + b * ncols, stuck + b);
+}
+
 // the step index is the same in every lane: the step record, the pair record, the row's CSR metadata and a decomposition's column
-// list are uniform loads.  A range with an is-zero pair is a dividing one (the plan says so): the DIV = false body has no such branch.
+// list are uniform loads.  A range with an is-zero pair or a division row is a dividing one (the plan says so): the DIV = false body
+// has no such branches.
 template <class P, bool DIV>
 __global__ __launch_bounds__(64) void k_solve_chain(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, const uint32_t *__restrict__ bit_cols,
-                                                    const SolvePairDev<P> *__restrict__ pairs, uint32_t lo, uint32_t hi, Fp<P> *xw, uint64_t ncols,
-                                                    unsigned long long *stuck, uint64_t rows) {
+                                                    const SolvePairDev<P> *__restrict__ pairs, const SolveDivDev *__restrict__ divs, uint32_t lo, uint32_t hi,
+                                                    Fp<P> *xw, uint64_t ncols, unsigned long long *stuck, uint64_t rows) {
     const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= rows) return;
     Fp<P> *z = xw + b * ncols;
@@ -272,6 +311,8 @@ __global__ __launch_bounds__(64) void k_solve_chain(CsrDev A, CsrDev B, CsrDev C
         if (steps[t].kind == pmsolve::KIND_ISZERO) {
             // DIV = false would pass over the pair and leave both markers in place: solve_plan refuses a plan that asks for that
             if constexpr (DIV) solve_iszero<P>(A, B, Cm, steps[t], pairs[steps[t].bits], z);
+        } else if (steps[t].kind == pmsolve::KIND_DIVREM) {
+            if constexpr (DIV) solve_divrem<P>(A, B, Cm, steps[t], divs[steps[t].bits], z, stuck + b);      // as above
         } else if (steps[t].bits) solve_bits<P, DIV>(A, B, Cm, steps[t], bit_cols, z, stuck + b);
         else solve_step<P, DIV>(A, B, Cm, steps[t], z, stuck + b);
     }
@@ -371,23 +412,30 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
         ctx->err = "pm solve: " + sv.plan.message;
         return PM_ERR_INVALID_ARG;
     }
-    // the DIV = false kernels have no is-zero step in them: a range with a pair must be a dividing one
+    // the DIV = false kernels have no is-zero step and no division step in them: a range with one must be a dividing one
     for (const pmsolve::Launch &l : sv.plan.launches)
         for (uint32_t t = l.lo; t < l.hi && !l.divides; ++t)
-            if (sv.plan.steps[t].kind == pmsolve::KIND_ISZERO) {
-                ctx->err = "pm solve: the plan puts the is-zero pair of row " + std::to_string(sv.plan.steps[t].row) + " into a launch that does not divide";
+            if (sv.plan.steps[t].kind == pmsolve::KIND_ISZERO || sv.plan.steps[t].kind == pmsolve::KIND_DIVREM) {
+                ctx->err = std::string("pm solve: the plan puts the ") + (sv.plan.steps[t].kind == pmsolve::KIND_ISZERO ? "is-zero pair" : "division") + " of row " +
+                           std::to_string(sv.plan.steps[t].row) + " into a launch that does not divide";
                 return PM_ERR_STATE;
             }
     const size_t n_steps = sv.plan.steps.size();
-    sv.n_pairs = 0;
+    sv.n_pairs = sv.n_divs = 0;
     if (n_steps) {
         std::vector<SolveStepDev<P>> host(n_steps);
         std::vector<SolvePairDev<P>> host_pairs;
+        std::vector<SolveDivDev> host_divs;
         memset((void *)host.data(), 0, n_steps * sizeof(SolveStepDev<P>));
         for (size_t t = 0; t < n_steps; ++t) {
             const pmsolve::Step &s = sv.plan.steps[t];
             host[t].pos = s.pos; host[t].row = s.row; host[t].col = s.bits ? s.cols_off : s.col; host[t].kind = s.kind; host[t].bits = s.bits;
             host[t].level = sv.plan.reordered ? s.level : 0;
+            if (s.kind == pmsolve::KIND_DIVREM) {
+                const pmsolve::DivRow &row = sv.plan.divs[s.cols_off];
+                host[t].bits = (uint32_t)host_divs.size();
+                host_divs.push_back(SolveDivDev{row.pos_r, row.col_r, row.q_in_b});
+            }
             if (s.kind != pmsolve::KIND_ISZERO) continue;
             host[t].bits = (uint32_t)host_pairs.size();
             SolvePairDev<P> pr;
@@ -402,6 +450,11 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
             PM_HIP(ctx, sv.pairs.reserve(sv.n_pairs * sizeof(SolvePairDev<P>)));
             PM_HIP(ctx, hipMemcpyAsync(sv.pairs.p, host_pairs.data(), sv.n_pairs * sizeof(SolvePairDev<P>), hipMemcpyHostToDevice, st));
         }
+        sv.n_divs = host_divs.size();
+        if (sv.n_divs) {
+            PM_HIP(ctx, sv.divs.reserve(sv.n_divs * sizeof(SolveDivDev)));
+            PM_HIP(ctx, hipMemcpyAsync(sv.divs.p, host_divs.data(), sv.n_divs * sizeof(SolveDivDev), hipMemcpyHostToDevice, st));
+        }
         const std::vector<uint32_t> &bit_cols = sv.plan.bit_cols;
         if (!bit_cols.empty()) {
             PM_HIP(ctx, sv.bit_cols.reserve(bit_cols.size() * sizeof(uint32_t)));
@@ -410,8 +463,9 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
         PM_HIP(ctx, sv.steps.reserve(n_steps * sizeof(SolveStepDev<P>)));
         PM_HIP(ctx, hipMemcpyAsync(sv.steps.p, host.data(), n_steps * sizeof(SolveStepDev<P>), hipMemcpyHostToDevice, st));
         PM_LAUNCH(ctx, k_solve_inv<P>, dim3(nblk(n_steps + 2 * sv.n_pairs)), dim3(256), 0, st, csr_dev(pk, 0), csr_dev(pk, 1), csr_dev(pk, 2),
-                       sv.steps.as<SolveStepDev<P>>(), (uint64_t)n_steps, sv.n_pairs ? sv.pairs.as<SolvePairDev<P>>() : nullptr, (uint64_t)sv.n_pairs);
-        PM_HIP(ctx, hipStreamSynchronize(st));   // `host` and `host_pairs` go out of scope
+                       sv.steps.as<SolveStepDev<P>>(), (uint64_t)n_steps, sv.n_pairs ? sv.pairs.as<SolvePairDev<P>>() : nullptr, (uint64_t)sv.n_pairs,
+                       sv.n_divs ? sv.divs.as<SolveDivDev>() : nullptr);
+        PM_HIP(ctx, hipStreamSynchronize(st));   // `host`, `host_pairs` and `host_divs` go out of scope
     }
     sv.plan_pattern.swap(pattern);
     sv.plan_key = pk->serial;
@@ -434,16 +488,18 @@ int solve_group(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t 
     const SolveStepDev<P> *steps = sv.steps.as<SolveStepDev<P>>();
     const uint32_t *bit_cols = sv.plan.bit_cols.empty() ? nullptr : sv.bit_cols.as<uint32_t>();
     const SolvePairDev<P> *pairs = sv.n_pairs ? sv.pairs.as<SolvePairDev<P>>() : nullptr;
+    const SolveDivDev *divs = sv.n_divs ? sv.divs.as<SolveDivDev>() : nullptr;
     {
         StageTimer t(ctx, timing_slot);
         for (const pmsolve::Launch &l : sv.plan.launches) {
             if (l.chain) {
                 const dim3 grid(nblk(g, 64)), block(64);
-                if (l.divides) hipLaunchKernelGGL((k_solve_chain<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, pairs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
-                else hipLaunchKernelGGL((k_solve_chain<P, false>), grid, block, 0, st, A, B, Cm, steps, bit_cols, pairs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
+                if (l.divides) hipLaunchKernelGGL((k_solve_chain<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, pairs, divs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
+                else hipLaunchKernelGGL((k_solve_chain<P, false>), grid, block, 0, st, A, B, Cm, steps, bit_cols, pairs, divs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
             } else {
                 const dim3 grid(nblk(l.hi - l.lo), (unsigned)g), block(256);
-                if (l.iszero) hipLaunchKernelGGL((k_solve_iszero<P>), grid, block, 0, st, A, B, Cm, steps, pairs, l.lo, l.hi, d_xw, ncols);
+                if (l.divrem) hipLaunchKernelGGL((k_solve_divrem<P>), grid, block, 0, st, A, B, Cm, steps, divs, l.lo, l.hi, d_xw, ncols, stuck);
+                else if (l.iszero) hipLaunchKernelGGL((k_solve_iszero<P>), grid, block, 0, st, A, B, Cm, steps, pairs, l.lo, l.hi, d_xw, ncols);
                 else if (l.bits && l.divides) hipLaunchKernelGGL((k_solve_bits<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck);
                 else if (l.bits) hipLaunchKernelGGL((k_solve_bits<P, false>), grid, block, 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck);
                 else if (l.divides) hipLaunchKernelGGL((k_solve_level<P, true>), grid, block, 0, st, A, B, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck);

@@ -1,9 +1,11 @@
 // Witness solving, host side: the PLAN that completes a partial assignment by forward propagation through the rows of an R1CS
-// (DESIGN.md §4.10).  Header-only, no HIP: the library's driver (csrc/solve.hip) and four CPU programs (tests/native/
-// solve_plan_selftest.cpp, solve_bits_selftest.cpp, solve_iszero_selftest.cpp, solve_order_selftest.cpp) include the same file.
+// (DESIGN.md §4.10).  Header-only, no HIP: the library's driver (csrc/solve.hip) and five CPU programs (tests/native/
+// solve_plan_selftest.cpp, solve_bits_selftest.cpp, solve_iszero_selftest.cpp, solve_order_selftest.cpp, solve_divrem_selftest.cpp)
+// include the same file.
 //
 // Input: the three matrices in CSR form with the first-entry rule already applied (a column occurs at most once per row and
-// matrix: the key's resident matrices are like that), m0 + mw columns and one byte per column, non-zero = unknown.  A stored entry
+// matrix: the key's resident matrices are like that), m0 + mw columns and one byte per column, non-zero = unknown (1: unknown;
+// 2: unknown, and a Euclidean quotient -- the caller's second marker, which has meaning in a division row only).  A stored entry
 // whose coefficient is zero names no variable.  Rows are visited ONCE, in matrix order; at row r, with the columns solved so far:
 //   no unknown column                         a check row, skipped
 //   one unknown u, in exactly one of A, B, C  a solve step (kind = the matrix that holds u); u is known from here on
@@ -42,7 +44,25 @@
 //                 bit_cols is: the step record of the other kinds is what it was).  A two-unknown row that is no opener is refused at once, as before; a pair that does not close is
 //                 ERR_MANY_UNKNOWNS at r1 with the message the row has without the modulus, then what failed.  Openers pending
 //                 when the rows end are reported first, smallest r1 first.
-// Without the modulus (nullptr) all three additions are off.
+//   division row  ONE row with two fresh unknowns q (the quotient) and rem (the remainder), each named once: circom's
+//                 q <-- a \ b; r <-- a % b; q*b + r === a, arkworks' DIV / REM and reductions by a non-power-of-two modulus.  One of
+//                 A_r, B_r has (cq, q) as its only non-zero entry and q carries pattern byte 2 (the caller says "a quotient": the
+//                 shape is the opener's, and nothing is guessed); the other is the known divisor side K (no unknown, at least one
+//                 non-zero entry); C_r names rem with coefficient cr = -cq (a + a' = 0 by add_mod) beside any known rest R.  ONE step
+//                 of kind KIND_DIVREM at row r that determines both columns, at 1 + max level of what the row reads; with d = K z and
+//                 a = R / cq as canonical integers:
+//                     d != 0:  q = floor(a / d),  rem = a mod d      (both below r; q d + rem = a in the integers, so the row holds)
+//                     d == 0:  stuck at row r, zero in both columns
+//                 Step::pos / col name q's entry, Plan::divs[cols_off] carries rem's entry in C and which side K is.  Such a row is a
+//                 division step at once: it is never registered as an opener and never waits for a closer.  Byte 2 has meaning in
+//                 that position only: a byte-2 column that is the single unknown of an ordinary row is solved by that row, and one
+//                 named anywhere else behaves as a plain unknown.  A row with two or more unknowns whose byte-2 column is the lone
+//                 entry of A or B and which misses a condition is ERR_MANY_UNKNOWNS at once, with the message the row had before and
+//                 ", and no division row: " + the condition: cr != -cq; rem in A or B; rem named twice; the other side not known
+//                 (an unknown on it, or no non-zero entry); the quotient named twice; a third unknown.  In the scheduler below such
+//                 a row WAITS instead, and is a division step as soon as q and rem are its only unknowns.
+//                 Not handled: signed division, cr != -cq, a known rest beside q on its side, a division without the marker.
+// Without the modulus (nullptr) all four additions are off.
 //
 // build_plan_any_order drops the matrix order: it runs build_plan, and where that refuses, a WAITING-ROW SCHEDULER examines the rows
 // from a min-heap (at first all of them) against the same column state with the same rules, except that these refusals become waiting:
@@ -50,12 +70,15 @@
 //   only the flag b of a registered opener  the closer (b once, in A or B, not in C, the other side +-K1): the KIND_ISZERO step, at
 //                                           1 + max of what both rows read.  Any other shape is a DEFINITE refusal, as in matrix order
 //   only the multiplier m of one, once      an ordinary step that determines m; the opener was none: it is RELEASED and examined again
+//   a division row, q and rem its only      the KIND_DIVREM step at once; an opener registered over q or rem (rem * 1 = y has that shape)
+//   unknowns                                was none: it is RELEASED and examined again
 //   a pair-pending column in any other way  the row WAITS (the multiplier beside something else, a second unknown, an opener-shaped
 //                                           row over a pending column)
 //   one unknown, named once                 an ordinary step
 //   one unknown, named several times        booleanity: boolean-pending; any other shape WAITS (a later row may determine the column
 //                                           and this one is a check row then)
-//   two or more unknowns                    a decomposition: the bits step; the opener shape: registered; anything else WAITS
+//   two or more unknowns                    a decomposition: the bits step; a division row: its step; the opener shape without the
+//                                           quotient's marker on the lone entry: registered; anything else WAITS
 // A waiting row is parked on its unknown columns and returns to the heap when one of them becomes known, boolean-pending or released.
 // With the heap empty the scheduler has failed if an opener is unclosed, a boolean-pending column unsolved or a marked column
 // undetermined; the result is then build_plan's error (code, row, column, message) with "; in any row order: ..." appended.  A plan
@@ -70,7 +93,7 @@
 //
 // level(step) = 1 + max level of the columns the row reads (given columns: level 0); a decomposition gives all its columns that
 // level.  The steps come out sorted by level, inside a level by kind (C first: the kinds that divide share a launch; then the
-// decompositions in the same order, then the is-zero pairs), stable by row -- one counting sort.  O(nnz + columns), plus k log k per decomposition.
+// decompositions in the same order, then the is-zero pairs, then the division rows), stable by row -- one counting sort.  O(nnz + columns), plus k log k per decomposition.
 #pragma once
 #include <stdint.h>
 
@@ -84,9 +107,12 @@
 namespace pmsolve {
 
 // z_u = (Az Bz - C_rest) / coef;  (Cz / Bz - A_rest) / coef;  (Cz / Az - B_rest) / coef;  KIND_BITS_x = KIND_BITS_C + x: a decomposition
-// KIND_ISZERO: an is-zero pair, both columns in one step
-enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6 };
-constexpr uint32_t NUM_KINDS = 7;
+// KIND_ISZERO: an is-zero pair, both columns in one step;  KIND_DIVREM: a division row, quotient and remainder in one step
+enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6, KIND_DIVREM = 7 };
+constexpr uint32_t NUM_KINDS = 7;        // the kinds that need no second marker: what it always counted
+constexpr uint32_t NUM_STEP_KINDS = 8;   // all of them, KIND_DIVREM included: the key width of finish_plan's counting sort
+
+constexpr uint8_t PATTERN_UNKNOWN = 1, PATTERN_QUOTIENT = 2;   // the pattern bytes (0: given)
 
 constexpr uint32_t WIDE_STEPS = 32;   // a level of at least this many steps gets launches of its own; narrower ones are walked by one lane per assignment
 
@@ -101,6 +127,7 @@ struct Step {
     uint32_t row, col, kind, level;
     uint32_t bits = 0, cols_off = 0;   // a decomposition: Plan::bit_cols[cols_off .. cols_off + bits), exponent order; bits = 0 otherwise
                                        // an is-zero pair: row = the closer, pos / col = the flag's entry in it, Plan::pairs[cols_off]
+                                       // a division row: pos / col = the quotient's entry in A_r or B_r, Plan::divs[cols_off]
 };
 
 struct PairRows {     // what an is-zero step needs beside its Step
@@ -111,12 +138,19 @@ struct PairRows {     // what an is-zero step needs beside its Step
     uint8_t negated;         // 1: K2 = -K1
 };
 
+struct DivRow {       // what a division step needs beside its Step
+    uint64_t pos_r;          // the remainder's entry in C_r
+    uint32_t col_r;          // the remainder's column
+    uint8_t q_in_b;          // 1: the quotient lies in B_r and K = A_r; 0: the other way round
+};
+
 struct Launch {
     uint32_t lo, hi;  // steps [lo, hi) of the sorted list
     uint8_t chain;    // 1: one lane per assignment walks the steps in order; 0: one lane per (step, assignment), all of one level
-    uint8_t divides;  // 1: some step of the range is KIND_A / KIND_B / KIND_BITS_A / KIND_BITS_B / KIND_ISZERO
+    uint8_t divides;  // 1: some step of the range is KIND_A / KIND_B / KIND_BITS_A / KIND_BITS_B / KIND_ISZERO / KIND_DIVREM (1 / cq)
     uint8_t bits = 0; // chain == 0 only.  1: every step of the range is a decomposition; 0: none is
     uint8_t iszero = 0;  // chain == 0 only.  1: every step of the range is an is-zero pair; 0: none is
+    uint8_t divrem = 0;  // chain == 0 only.  1: every step of the range is a division row; 0: none is
 };
 
 enum Error : int { OK = 0, ERR_MANY_UNKNOWNS = 1, ERR_TWO_MATRICES = 2, ERR_UNDETERMINED = 3, ERR_COLUMN_ZERO = 4 };
@@ -127,6 +161,7 @@ struct Plan {
     std::vector<Launch> launches;
     std::vector<uint32_t> bit_cols;   // the decompositions' columns
     std::vector<PairRows> pairs;      // the is-zero pairs' openers, in order of discovery
+    std::vector<DivRow> divs;         // the division rows' remainders, in order of discovery
     int error = OK;
     uint64_t error_row = 0, error_col = 0;
     std::string message;              // empty when error == OK
@@ -256,10 +291,44 @@ inline int compare_known_sides(const Csr m[3], int k1, uint64_t r1, int k2, uint
     return same ? 0 : negated ? 1 : -1;
 }
 
+// The division shape, for a row whose unknown entries are `occ` (two or more columns) with nz[k] non-zero entries in matrix k:
+//   0   no byte-2 column is the lone entry of A_r or B_r: the row is no candidate
+//   1   a division row: `q` = the quotient's entry, `rem` = the remainder's entry in C_r
+//  -1   a candidate that misses a condition: `why`
+inline int division_row(const Csr m[3], const std::vector<Unknown> &occ, const uint32_t nz[3], const uint8_t *unknown, const uint64_t *modulus, Unknown &q,
+                        Unknown &rem, const char *&why) {
+    const Unknown *lone = nullptr;
+    for (const Unknown &e : occ)
+        if (!lone && e.matrix < 2 && nz[e.matrix] == 1 && unknown[e.col] == PATTERN_QUOTIENT) lone = &e;
+    if (!lone) return 0;
+    q = *lone;
+    const uint32_t other_side = 1 - q.matrix;
+    const Unknown *first = nullptr;
+    uint32_t named = 0;
+    bool in_ab = false, third = false;
+    for (const Unknown &e : occ) {
+        if (&e == lone) continue;
+        if (e.col == q.col) return why = "the quotient named twice", -1;
+        if (!first) first = &e;
+        third = third || e.col != first->col;
+        ++named;
+        in_ab = in_ab || e.matrix < 2;      // the quotient's side has no other non-zero entry: this is the other side
+    }
+    if (third) return why = in_ab ? "the other side not known" : "a third unknown", -1;
+    if (in_ab) return why = "rem in A or B", -1;
+    if (named > 1) return why = "rem named twice", -1;
+    if (nz[other_side] == 0) return why = "the other side not known", -1;
+    rem = *first;
+    uint64_t sum[4];
+    add_mod(m[q.matrix].val + 4 * q.pos, m[2].val + 4 * rem.pos, modulus, sum);
+    if (!coef_is_zero(sum)) return why = "cr != -cq", -1;
+    return 1;
+}
+
 // The tail both builders share: p.steps (in ROW order, levels set) sorted by (level, kind), stable by row; level_ptr; the launch schedule.
 inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
     // counting sort by (level, kind); the row order inside a key is the order the steps come in
-    constexpr size_t K = NUM_KINDS;
+    constexpr size_t K = NUM_STEP_KINDS;
     std::vector<uint32_t> start((size_t)max_level * K + 1, 0);
     for (const Step &s : p.steps) ++start[(size_t)(s.level - 1) * K + s.kind + 1];
     for (size_t i = 1; i < start.size(); ++i) start[i] += start[i - 1];
@@ -272,17 +341,18 @@ inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
         p.steps.swap(sorted);
     }
     // launch schedule: a wide level is its own launch, split where the dividing kinds begin, again where the decompositions and
-    // their dividing kinds begin, and where the is-zero pairs begin; consecutive narrow levels are one chain
+    // their dividing kinds begin, where the is-zero pairs begin and where the division rows begin; consecutive narrow levels are one chain
     for (uint32_t l = 0; l < max_level; ++l) {
         const uint32_t *at = start.data() + (size_t)l * K;
-        const uint32_t lo = at[KIND_C], ab = at[KIND_A], bits = at[KIND_BITS_C], bits_ab = at[KIND_BITS_A], pairs = at[KIND_ISZERO], hi = at[K];
+        const uint32_t lo = at[KIND_C], ab = at[KIND_A], bits = at[KIND_BITS_C], bits_ab = at[KIND_BITS_A], pairs = at[KIND_ISZERO], divs = at[KIND_DIVREM], hi = at[K];
         const uint8_t divides = (uint8_t)(bits > ab || hi > bits_ab);
         if (hi - lo >= wide_steps) {
             if (ab > lo) p.launches.push_back(Launch{lo, ab, 0, 0});
             if (bits > ab) p.launches.push_back(Launch{ab, bits, 0, 1});
             if (bits_ab > bits) p.launches.push_back(Launch{bits, bits_ab, 0, 0, 1});
             if (pairs > bits_ab) p.launches.push_back(Launch{bits_ab, pairs, 0, 1, 1});
-            if (hi > pairs) p.launches.push_back(Launch{pairs, hi, 0, 1, 0, 1});
+            if (divs > pairs) p.launches.push_back(Launch{pairs, divs, 0, 1, 0, 1});
+            if (hi > divs) p.launches.push_back(Launch{divs, hi, 0, 1, 0, 0, 1});
         } else if (!p.launches.empty() && p.launches.back().chain) {
             p.launches.back().hi = hi;
             p.launches.back().divides |= divides;
@@ -322,6 +392,7 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
         p.steps.clear();
         p.bit_cols.clear();
         p.pairs.clear();
+        p.divs.clear();
     };
     uint32_t max_level = 0;
     std::vector<Unknown> occ;
@@ -395,7 +466,7 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
         }
         const uint32_t u = occ[0].col;
         uint32_t j = occ[1].col;
-        const char *why = nullptr;
+        const char *why = nullptr, *div_why = nullptr;
         if (modulus) {
             bool one_column = true;
             for (const Unknown &o : occ)
@@ -421,8 +492,24 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
                 p.steps.push_back(s);
                 continue;
             }
+            // a division row: the shape below with the quotient's marker on the lone entry.  It is a step at once, or refused at once
+            int div = 0;
+            if (!one_column) {
+                Unknown q, rem;
+                div = division_row(m, occ, nz, unknown, modulus, q, rem, div_why);
+                if (div > 0) {
+                    Step s{q.pos, (uint32_t)r, q.col, KIND_DIVREM, lv};
+                    s.cols_off = (uint32_t)p.divs.size();
+                    p.divs.push_back(DivRow{rem.pos, rem.col, (uint8_t)(q.matrix == 1)});
+                    level[q.col] = level[rem.col] = lv;
+                    if (lv > max_level) max_level = lv;
+                    p.steps.push_back(s);
+                    continue;
+                }
+                if (div < 0 && div_why[0] == 'c') why = nullptr;   // cr != -cq: the opener's shape, whose message had no second part
+            }
             // an is-zero opener: the multiplier alone on one of A, B, the other of the two known and not zero, the flag in C
-            if (!one_column && occ.size() == 2 && occ[0].matrix < 2 && occ[1].matrix == 2 && nz[occ[0].matrix] == 1 && nz[1 - occ[0].matrix] >= 1) {
+            if (div == 0 && !one_column && occ.size() == 2 && occ[0].matrix < 2 && occ[1].matrix == 2 && nz[occ[0].matrix] == 1 && nz[1 - occ[0].matrix] >= 1) {
                 pair_of[u] = pair_of[j] = (uint32_t)openers.size();
                 openers.push_back(Opener{occ[0].pos, occ[1].pos, (uint32_t)r, u, j, reads, (uint8_t)occ[0].matrix});
                 ++open;
@@ -435,6 +522,7 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
             p.error = ERR_MANY_UNKNOWNS;
             p.message = two_unknowns(r, u, j);
             if (why) p.message += std::string(", and no bit decomposition: ") + why;
+            if (div_why) p.message += std::string(", and no division row: ") + div_why;
         } else {   // the same unknown again: in another matrix, or a second time in this one
             p.error = ERR_TWO_MATRICES;
             p.message = "row " + std::to_string(r) + ": unknown column " + std::to_string(j) + " occurs in " + NAME[occ[0].matrix] + " and in " + NAME[occ[1].matrix];
@@ -462,6 +550,7 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
             p.steps.clear();
             p.bit_cols.clear();
             p.pairs.clear();
+            p.divs.clear();
             return p;
         }
     }
@@ -473,6 +562,7 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
             p.steps.clear();
             p.bit_cols.clear();
             p.pairs.clear();
+            p.divs.clear();
             return p;
         }
     finish_plan(p, max_level, wide_steps);
@@ -543,6 +633,33 @@ inline bool schedule_any_order(const Csr m[3], uint64_t nr, uint64_t ncols, cons
         const uint32_t u = occ[0].col;
         bool one_column = true;
         for (const Unknown &e : occ) one_column = one_column && e.col == u;
+        Unknown q, rem;
+        const char *div_why = nullptr;
+        const int div = one_column ? 0 : division_row(m, occ, nz, unknown, modulus, q, rem, div_why);
+        if (div > 0) {
+            // a division row whose only unknowns are q and rem: a step at once.  It waits for no closer, so an opener registered over
+            // one of its columns (the row rem * 1 = y has that shape) was none: it is released and examined again.  A candidate that
+            // misses a condition waits like any other row (below)
+            for (const uint32_t col : {q.col, rem.col}) {
+                if (pair_of[col] == NONE) continue;
+                const Opener &held = openers[pair_of[col]];
+                const uint32_t col_m = held.col_m, col_b = held.col_b, opener_row = held.row;
+                pair_of[col_m] = pair_of[col_b] = NONE;
+                --open;
+                state[opener_row] = PARKED;
+                push(opener_row);
+                wake(col_m);
+                wake(col_b);
+            }
+            const uint32_t lv = reads + 1;
+            Step s{q.pos, r, q.col, KIND_DIVREM, lv};
+            s.cols_off = (uint32_t)p.divs.size();
+            p.divs.push_back(DivRow{rem.pos, rem.col, (uint8_t)(q.matrix == 1)});
+            p.steps.push_back(s);
+            solved(q.col, lv);
+            solved(rem.col, lv);
+            continue;
+        }
         const Opener *o = nullptr;
         for (const Unknown &e : occ)
             if (!o && pair_of[e.col] != NONE) o = &openers[pair_of[e.col]];
@@ -604,7 +721,7 @@ inline bool schedule_any_order(const Csr m[3], uint64_t nr, uint64_t ncols, cons
             for (uint32_t i = 0; i < s.bits; ++i) solved(p.bit_cols[s.cols_off + i], lv);
             continue;
         }
-        if (occ.size() == 2 && occ[0].matrix < 2 && occ[1].matrix == 2 && nz[occ[0].matrix] == 1 && nz[1 - occ[0].matrix] >= 1) {
+        if (div == 0 && occ.size() == 2 && occ[0].matrix < 2 && occ[1].matrix == 2 && nz[occ[0].matrix] == 1 && nz[1 - occ[0].matrix] >= 1) {
             pair_of[u] = pair_of[occ[1].col] = (uint32_t)openers.size();
             openers.push_back(Opener{occ[0].pos, occ[1].pos, r, u, occ[1].col, reads, (uint8_t)occ[0].matrix});
             ++open;

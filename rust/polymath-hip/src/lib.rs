@@ -201,6 +201,13 @@ fn fr_ptr<F>(s: &[F]) -> *const u64 {
     s.as_ptr() as *const u64
 }
 
+/// The quotient marker of `PM_ASSIGNMENT_SOLVE` (`PM_UNKNOWN_QUOTIENT_WORDS`): four limbs that are no field element on either curve
+/// and say "unknown, and the Euclidean quotient of its division row" (`q * b = a - rem`: circom's `q <-- a \ b`, arkworks' DIV /
+/// REM).  The `Option` rows of [`GpuKey::prove_batch_from_partial`] and [`GpuKey::solve`] write the plain marker for `None`; a caller
+/// whose circuit has division rows passes limb rows with this constant on the quotients to the `-sys` calls.  The marker is
+/// explicit: with `None` on a quotient the row is refused, as it always was.
+pub const UNKNOWN_QUOTIENT: [u64; 4] = sys::PM_UNKNOWN_QUOTIENT_WORDS;
+
 /// Montgomery limbs of a partial assignment appended to `out`: a value's own four words, or the unknown marker (four times
 /// `u64::MAX`: not a field element on either curve) for `None`.
 fn partial_limbs<F>(vals: &[Option<F>], out: &mut Vec<u64>) {
