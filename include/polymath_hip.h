@@ -300,7 +300,8 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  * existing argument: the set of entry points and the option table are pinned).  0 and 1 mean what they always meant; a bit outside
  * the two below is PM_ERR_INVALID_ARG.  The other entry points with such an argument (pm_host_prove_sharded, the phases) do not solve.
  *   PM_ASSIGNMENT_SOLVE: the caller supplies only the values it chooses; every Fr of x or w whose four words are UINT64_MAX (>= r on
- *     both curves, so never a field element; or the quotient marker, which differs in the lowest bit: "a division row" below) is
+ *     both curves, so never a field element; or the quotient marker, which differs in the lowest bit: "a division row" below; or
+ *     the indicator marker, which differs in bit 64: "an indicator row" below) is
  *     UNKNOWN and is computed on the device first, by forward propagation through the key's
  *     resident constraint rows (first-entry rule applied, as the prover and pm_r1cs_check read them; a stored entry with a zero
  *     coefficient names no variable).  The call then runs on the completed assignment and its results are, bit for bit, those of the
@@ -342,6 +343,23 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  *                                                solution (rem < d, and q small enough that q d + rem does not wrap) are the circuit's: they
  *                                                are decomposition rows like any other.  Not handled: signed division, cr != -cq, a known
  *                                                rest beside q on its side, a division without the marker
+ *     an indicator row                        -- ONE row whose only unknown u the caller marks with PM_HINT_INDICATOR_WORDS (below) and which
+ *                                                names u exactly once, as the ONLY non-zero entry (k, u) of A_r or B_r; the other of the
+ *                                                two is the known guard side K (no unknown, not zero) and C_r has no non-zero entry:
+ *                                                circomlib's Decoder / Multiplexer,  out[i] <-- (inp == i) ? 1 : 0; out[i] * (inp - i) === 0 ,
+ *                                                which is how a circuit reads table[idx] with a signal as the index.  ONE step:
+ *                                                  z_u = 1 where K z == 0, else 0      (field one or field zero, whatever k is)
+ *                                                The step never divides and never leaves an assignment stuck.  The rows do not determine
+ *                                                the value at the hit (0 satisfies the guard too, and the sum row with success = 0), so it
+ *                                                is a hint and the marker is explicit, as circom's <-- is: nothing is inferred -- with the
+ *                                                plain marker on u the row is an ordinary dividing row, as it always was, and the
+ *                                                assignment is stuck at it where K z == 0.  The indicator marker has meaning in that
+ *                                                position only: a column that carries it and is the single unknown of a row of any other
+ *                                                shape (C_r not empty, other non-zero entries beside u on its side, an empty other side)
+ *                                                is solved by that row as an ordinary row, and named beside other unknowns it is a plain
+ *                                                unknown; no refusal is added.  Not handled: a hit value other than 1, a non-empty C_r,
+ *                                                a known rest beside u, inferring indicators without the marker, sharded keys,
+ *                                                per-assignment patterns
  *     an is-zero pair                         -- the two rows every equality test compiles to, with two fresh unknowns m (the multiplier)
  *                                                and b (the flag):  arkworks  (a - b) mult = neq ; (a - b) (1 - neq) = 0
  *                                                                   circom    (-in) inv = out - 1 ; in out = 0
@@ -367,7 +385,9 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  *   constraint like any other, which the check reports if the value is not 0 or 1.  One that is still pending when the rows end is
  *   unsolvable: its booleanity row (the smallest such row) and column are named.  XOR, AND, rotations and recompositions are ordinary
  *   one-unknown rows, so range checks, comparisons, modular additions and ARX hashes complete, and with the is-zero pair so do
- *   equality tests, selection on equality, table membership and data-dependent branches.
+ *   equality tests, selection on equality, table membership and data-dependent branches.  (Table membership in the arkworks form,
+ *   one is-zero pair per index.  circomlib's one-hot Decoder / Multiplexer completes through its indicator rows, with the indicator
+ *   marker on its outputs.)
  *   Rows in any order.  Where the pass in matrix order refuses, a waiting-row scheduler applies the same rules in DEPENDENCY order: it
  *   examines the rows smallest first, and a row that cannot act yet WAITS on its unknown columns and is examined again when one of
  *   them becomes known or boolean-pending -- a row with two or more unknowns that is no decomposition and no opener, a decomposition
@@ -383,7 +403,7 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  *   per-assignment patterns, sharded keys.
  *   PM_ERR_INVALID_ARG, pm_last_error naming the row or column, nothing computed and no output written: an unsolvable row, a marked
  *   column that no row determines, a marker at column 0, a sharded key, and -- in a batch -- an assignment that does not mark the
- *   columns assignment 0 marks, or marks one with the other marker (the first differing (assignment, column) is named; a kernel
+ *   columns assignment 0 marks, or marks one with the other marker (any two of the three markers differ; the first differing (assignment, column) is named; a kernel
  *   compares them).
  *   At run time a step that would divide by zero (Bz = 0 with u in A) leaves that assignment STUCK, even where Cz = 0 too (the value
  *   is then undetermined), and so does a decomposition whose t is 2^k or more (no boolean solution; its k values are stored as
@@ -406,9 +426,13 @@ typedef enum pm_assignment_flags {
 } pm_assignment_flags;
 /* The two markers of PM_ASSIGNMENT_SOLVE, as initialisers of a uint64_t[4] (little-endian words of one Fr).  Both are >= r on both
  * curves, so neither is ever a field element.  PM_UNKNOWN_WORDS: the value is unknown.  PM_UNKNOWN_QUOTIENT_WORDS: the value is
- * unknown, and it is the Euclidean quotient of its division row (the rule above); everywhere else it means what PM_UNKNOWN_WORDS means. */
+ * unknown, and it is the Euclidean quotient of its division row (the rule above); everywhere else it means what PM_UNKNOWN_WORDS means.
+ * A third marker, PM_HINT_INDICATOR_WORDS (2^256 - 1 - 2^64: the top word is all ones, so it is >= r on both curves as well): the
+ * value is unknown, and it is the INDICATOR of its guard row ("an indicator row" above), 1 where the guard's known side is zero,
+ * else 0; everywhere else it means what PM_UNKNOWN_WORDS means.  A value with both bit 0 and bit 64 clear is no marker. */
 #define PM_UNKNOWN_WORDS { UINT64_MAX, UINT64_MAX, UINT64_MAX, UINT64_MAX }
 #define PM_UNKNOWN_QUOTIENT_WORDS { UINT64_MAX - 1, UINT64_MAX, UINT64_MAX, UINT64_MAX }
+#define PM_HINT_INDICATOR_WORDS { UINT64_MAX, UINT64_MAX - 1, UINT64_MAX, UINT64_MAX }
 
 /* Whole create_proof_with_assignment (prover.rs:66-237) for an UNSHARDED key, transcript included: the three
  * phases above plus the host glue between them (compute_x1 / compute_x2, common.rs:21-71; pi and c at x1,

@@ -3,9 +3,10 @@
 "random A*B=C gates" R1CS BASELINE.json quotes the headline metric on, and two boolean circuits of this project's
 own (RangeCheck, ArxDemo) and two that branch on equality (MatchCount, EqChain: is-zero pairs in arkworks' and in circom's form) whose
 witnesses the device completes from the inputs (PM_ASSIGNMENT_SOLVE), and two that divide integers (DivRem,
-ModChain: Euclidean division rows, whose quotients partial() marks QUOTIENT); Reordered emits any of them with its rows in another
+ModChain: Euclidean division rows, whose quotients partial() marks QUOTIENT), and two that read a table at a signal (Decoder,
+TableWalk: circomlib's one-hot decoder, whose outputs partial() marks INDICATOR); Reordered emits any of them with its rows in another
 order, which the solver's any-order planner accepts."""
-from .polymath import QUOTIENT, ConstraintSystem, Field, LimbCircuit, R1CS
+from .polymath import INDICATOR, QUOTIENT, ConstraintSystem, Field, LimbCircuit, R1CS
 
 SPLITMIX_SEED = 0x706F6C796D617468  # "polymath"
 _M64 = (1 << 64) - 1
@@ -425,6 +426,109 @@ def mod_chain_native(s0, g, c, m, steps):
     for _ in range(steps):
         s0 = (g * s0 + c) % m
     return s0
+
+
+class _PartialIndicators(_Partial):
+    """_Partial for circuits with one-hot decoders (circomlib's Decoder:  out[i] <-- (inp == i) ? 1 : 0;  out[i] * (inp - i) === 0):
+    partial() marks every out_i INDICATOR -- the explicit "this unknown is the indicator of its guard row" that the solver asks for,
+    since the guard does not determine the value where inp == i -- and leaves the sums None."""
+
+    def _decoder(self, cs, inp, inp_v, width):
+        """`width` witnesses out_i = [inp == i], each with its guard row  out_i * (inp - i) = 0  (for i = 0 the guard's known side is
+        inp alone).  -> (outs, hit): the variables, and 1 where the index is in range, else 0"""
+        one, outs = ConstraintSystem.ONE, []
+        for i in range(width):
+            self._indicators.append(len(cs.witness))
+            out = cs.new_witness_variable(int(inp_v == i))
+            cs.enforce_constraint([(1, out)], [(1, inp)] + ([(-i, one)] if i else []), [])
+            outs.append(out)
+        return outs, int(0 <= inp_v < width)
+
+    def partial(self, r):
+        instance, witness = super().partial(r)
+        for j in self._indicators:
+            witness[j] = INDICATOR
+        return instance, witness
+
+
+class Decoder(_PartialIndicators):
+    """circomlib's Decoder(width) on the given witness inp: the witnesses out_0 .. out_{width-1} with their guard rows
+    out_i * (inp - i) = 0, the sum row  (sum out_i) * 1 = success  with success the public input, and  success * (success - 1) = 0.
+    ONE dependency level of `width` indicator rows, then one ordinary step.  Witness layout: inp, then the out_i.  An index out of
+    range (width <= inp < r) gives all zeros and success = 0."""
+
+    def __init__(self, width, index):
+        assert width >= 1
+        self.width, self.index = width, index
+
+    def generate_constraints(self, cs):
+        self._chosen, self._indicators = [], []
+        one = ConstraintSystem.ONE
+        inp_v = self.index % cs.r
+        inp = self._given(cs, inp_v)
+        outs, hit = self._decoder(cs, inp, inp_v, self.width)
+        success = cs.new_input_variable(hit)
+        cs.enforce_constraint([(1, out) for out in outs], [(1, one)], [(1, success)])
+        cs.enforce_constraint([(1, success)], [(1, success), (-1, one)], [])
+
+    def native(self, r):
+        """-> (instance, witness) on Python integers, without generating a row: inp, then out_i = [inp == i]"""
+        inp = self.index % r
+        return [1, int(inp < self.width)], [inp] + [int(inp == i) for i in range(self.width)]
+
+
+class TableWalk(_PartialIndicators):
+    """Pointer chasing through a table:  idx_{t+1} = table[idx_t],  idx_0 = start, over `steps` steps -- how a circom circuit reads
+    RAM, a selector or a jump table at a signal.  Per step one decoder on idx_t (the out_i with their guard rows, the witness
+    success_t with  (sum out_i) * 1 = success_t  and  success_t * (success_t - 1) = 0), then
+        signals=True    the table entries are given witnesses (allocated once, after idx_0): one product row  out_i * table_i = p_i
+                        per entry and the sum  (sum p_i) * 1 = idx_{t+1}
+        signals=False   the table entries are constants of the circuit: the one linear row  (sum table_i out_i) * 1 = idx_{t+1}
+    The last index is the public input.  An index out of range reads 0.  Indicator levels alternate with ordinary ones (three levels
+    per step with signals, two with constants), `len(table)` wide; the batch is the parallel dimension.  The caller chooses start and,
+    with signals, the table."""
+
+    def __init__(self, table, start, steps, signals=True):
+        assert steps >= 1 and len(table) >= 1
+        self.table, self.start, self.steps, self.signals = list(table), start, steps, signals
+
+    def generate_constraints(self, cs):
+        self._chosen, self._indicators = [], []
+        one, r, width = ConstraintSystem.ONE, cs.r, len(self.table)
+        idx_v = self.start % r
+        idx = self._given(cs, idx_v)
+        entries = [self._given(cs, v) for v in self.table] if self.signals else None
+        for t in range(self.steps):
+            outs, hit = self._decoder(cs, idx, idx_v, width)
+            success = cs.new_witness_variable(hit)
+            cs.enforce_constraint([(1, out) for out in outs], [(1, one)], [(1, success)])
+            cs.enforce_constraint([(1, success)], [(1, success), (-1, one)], [])
+            next_v = self.table[idx_v] % r if hit else 0
+            if self.signals:
+                products = []
+                for i, out in enumerate(outs):
+                    products.append(cs.new_witness_variable(self.table[i] if idx_v == i else 0))
+                    cs.enforce_constraint([(1, out)], [(1, entries[i])], [(1, products[i])])
+                total = [(1, p) for p in products]
+            else:
+                total = [(v % r, out) for v, out in zip(self.table, outs) if v % r]
+            nxt = cs.new_input_variable(next_v) if t == self.steps - 1 else cs.new_witness_variable(next_v)
+            cs.enforce_constraint(total, [(1, one)], [(1, nxt)])
+            idx, idx_v = nxt, next_v
+
+    def native(self, r):
+        """-> (instance, witness) as the rows define them, on Python integers"""
+        cs = ConstraintSystem(r)
+        self.generate_constraints(cs)
+        return list(cs.instance), list(cs.witness)
+
+
+def table_walk_native(table, start, steps, r):
+    """TableWalk's public output on plain integers"""
+    idx = start % r
+    for _ in range(steps):
+        idx = table[idx] % r if idx < len(table) else 0
+    return idx
 
 
 def row_order(nr, order, blocks=1):

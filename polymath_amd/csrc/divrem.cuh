@@ -1,6 +1,8 @@
-// The quotient marker and the Euclidean division of canonical residues, for the witness solver's division step (solve.hip:
-// k_solve_pattern, solve_divrem).  ONE routine for device and host: the kernels call it per (step, assignment), the CPU self-test
-// (tests/native/solve_divrem_selftest.cpp) executes plans with it on the host field type.
+// The markers of a partial assignment (marker_byte: THE marker test, for the solver and for both glue modes of the provers), the
+// indicator step's value (indicator_of; solve.hip: solve_indicator) and the Euclidean division of canonical residues, for the
+// witness solver's division step (solve.hip: k_solve_pattern, solve_divrem).  ONE set of routines for device and
+// host: the kernels call them per (step, assignment), the CPU self-tests (tests/native/solve_divrem_selftest.cpp,
+// solve_indicator_selftest.cpp) execute plans with them on the host field type.
 //
 // Restoring shift-subtract on four 64-bit words with a FIXED trip count of 256: the 512-bit register (hi : lo) starts as (0 : a),
 // every round shifts it left by one, subtracts d from hi on trial and keeps the difference under a mask; the quotient bit enters
@@ -14,13 +16,31 @@
 namespace pm {
 
 // The pattern byte of a value of a partial assignment (include/polymath_hip.h): 1 for the unknown marker (every word all ones), 2 for
-// the quotient marker (the same with the lowest bit clear), else 0.  Both are >= r on both curves, so never a field element.
+// the quotient marker (the same with the lowest bit clear), 3 for the indicator marker (the same with bit 64 clear), else 0 -- with
+// both bits clear as well.  All three are >= r on both curves, so never a field element.  THE marker test: the solver's kernels, the
+// host glue (host_prove.hip) and the device glue (prove_glue.hip) all ask this routine, on eight 32-bit limbs, little-endian.
+PM_HD uint8_t marker_byte_limbs(const uint32_t l[8]) {
+    uint32_t a = (l[0] | 1u) & l[1] & (l[2] | 1u);
+#pragma unroll
+    for (int i = 3; i < 8; ++i) a &= l[i];
+    const uint32_t low = l[0] & 1u, mid = l[2] & 1u;
+    return a != ~0u ? 0 : (low & mid) ? pmsolve::PATTERN_UNKNOWN : mid ? pmsolve::PATTERN_QUOTIENT : low ? pmsolve::PATTERN_INDICATOR : 0;
+}
 template <class P>
 PM_HD uint8_t marker_byte(const Fp<P> &v) {
-    uint32_t a = v.l[0] | 1u;
+    static_assert(P::N == 8, "four 64-bit words");
+    return marker_byte_limbs(v.l);
+}
+
+// The indicator step's value (solve.hip: solve_indicator): field one where the guard's known side is zero, else field zero.  One
+// & mask, as solve_bits stores its bits: no table to select from and no branch on the operand.
+template <class P>
+PM_HD Fp<P> indicator_of(const Fp<P> &kz) {
+    const uint32_t mask = 0u - (uint32_t)kz.is_zero();
+    Fp<P> v;
 #pragma unroll
-    for (int i = 1; i < P::N; ++i) a &= v.l[i];
-    return a != ~0u ? 0 : (v.l[0] & 1u) ? pmsolve::PATTERN_UNKNOWN : pmsolve::PATTERN_QUOTIENT;
+    for (int w = 0; w < P::N; ++w) v.l[w] = P::ONE[w] & mask;
+    return v;
 }
 
 // q = floor(a / d), rem = a mod d on unsigned 256-bit integers, little-endian words; any a, any d != 0 (the bit shifted out of hi

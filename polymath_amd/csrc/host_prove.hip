@@ -4,6 +4,7 @@
 // caller's context.  The three phases stay the boundary; this is their caller, compiled once.
 #include "internal.h"
 #include "prove_common.cuh"
+#include "divrem.cuh"
 #include "../host/polymath.hpp"
 #include "../host/wire.hpp"
 
@@ -86,8 +87,12 @@ namespace {
 
 constexpr uint64_t NOT_STUCK = ~(uint64_t)0;
 
-// either marker of an unknown entry: the quotient's differs in the lowest bit
-inline bool is_marker(const uint64_t *fr) { return ((fr[0] | 1) & fr[1] & fr[2] & fr[3]) == ~(uint64_t)0; }
+// any marker of an unknown entry (divrem.cuh: marker_byte_limbs, the one statement of the test)
+inline bool is_marker(const uint64_t *fr) {
+    uint32_t limbs[8];
+    memcpy(limbs, fr, sizeof limbs);
+    return pm::marker_byte_limbs(limbs) != 0;
+}
 
 // instance_host with its unknown entries replaced by the solved values of assignment i (tap 9): what gets hashed
 void solved_instance(const pm_ctx *ctx, const pm_pk *pk, size_t i, const uint64_t *instance_host, uint64_t *out) {

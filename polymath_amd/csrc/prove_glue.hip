@@ -12,6 +12,7 @@
 #include "internal.h"
 #include "g1_record.cuh"
 #include "prove_common.cuh"
+#include "divrem.cuh"
 #include "transcript.cuh"
 
 namespace pm {
@@ -46,12 +47,10 @@ __device__ __forceinline__ bool glue_row_live(const GlueRows<C> &g, unsigned i) 
     return phase1_flag_status(g.flags[i]) == PM_OK && !(g.stuck && g.stuck[i] != GLUE_NOT_STUCK);
 }
 
-// either marker of an unknown entry (include/polymath_hip.h: PM_ASSIGNMENT_SOLVE): all ones, the quotient's with the lowest bit clear
+// any marker of an unknown entry (include/polymath_hip.h: PM_ASSIGNMENT_SOLVE; divrem.cuh: marker_byte, the one statement of the test)
 template <class P>
 __device__ __forceinline__ bool glue_is_marker(const Fp<P> &v) {
-    uint32_t all = v.l[0] | 1u;
-    for (int k = 1; k < 8; ++k) all &= v.l[k];
-    return all == 0xffffffffu;
+    return marker_byte<P>(v) != 0;
 }
 
 // After phase 1.  xw: under PM_ASSIGNMENT_SOLVE the group's completed x || w rows (stride ncols), whose first m0 entries replace the

@@ -3,10 +3,10 @@
 // before it checks or proves.  The PLAN -- which row determines which column, in which order -- is host work, done once per (key,
 // pattern) by host/solve_plan.hpp; the arithmetic is the kernels below, assignment = grid y (or the lane, in the chain kernel):
 //   k_solve_pattern   one lane per (column, assignment): the unknown pattern of assignment 0 (a byte per column: 1 the unknown
-//                     marker, 2 the quotient marker); every other assignment is compared with it, byte for byte, and the first
+//                     marker, 2 the quotient marker, 3 the indicator marker); every other assignment is compared with it, byte for byte, and the first
 //                     differing (assignment, column) lowers one word
 //   k_solve_inv       one lane per step, once per plan: 1 / coefficient of the step's unknown (a division row: 1 / cq); two more
-//                     lanes per is-zero pair: 1 / cm and 1 / cb of its opener
+//                     lanes per is-zero pair: 1 / cm and 1 / cb of its opener; an indicator step needs none and its record is left alone
 //   k_solve_level     a WIDE dependency level: one lane per (step, assignment); a level is its own launch, so stream order is
 //                     the dependency order
 //   k_solve_bits      the bit decompositions of a wide level, one lane per (step, assignment) as well: a launch of their own, so
@@ -14,13 +14,15 @@
 //   k_solve_iszero    the is-zero pairs of a wide level, one lane per (step, assignment) as well: two stores and one inversion each
 //   k_solve_divrem    the division rows of a wide level, one lane per (step, assignment) as well: two stores and one 256-bit
 //                     integer division each (divrem.cuh: a fixed trip count, so a wave does not diverge on operand size)
+//   k_solve_indicator the indicator rows of a wide level, one lane per (step, assignment) as well: one dot product over the guard's
+//                     known side, a zero test and one store of field one under a mask; no division
 //   k_solve_chain     a run of consecutive NARROW levels: one lane per assignment walks the run's steps in plan order.  A lane
 //                     reads back only its own stores: no barriers, no fences.  The MiMC shape (depth 644, width 1) is one such run
 //                     and the batch is its parallel dimension.
 // The solving kernels exist twice: DIV = false for ranges of kind-C steps only, DIV = true for ranges with kind-A / kind-B steps,
 // or is-zero pairs, which call inverse<P> (a Fermat chain) -- the plan sorts a level by kind, so kind-C ranges do not carry its
 // registers, and the is-zero step and the division step (a dividing one by the plan's count, for 1 / cq) exist in the DIV = true
-// chain only.
+// chain only.  The indicator step does not divide: it is a branch of BOTH chain instantiations.
 //   k_solve_stuck_row after the launches of a REORDERED plan (build_plan_any_order found a dependency order that is not the matrix
 //                     order): one lane per assignment turns the stuck word's (level, row) into the row
 // A step that would divide by zero stores zero and lowers the assignment's stuck word to its row (64-bit atomic minimum: the same
@@ -48,6 +50,8 @@ struct SolveStepDev {
     uint32_t row, col, kind, bits;   // bits != 0: a decomposition into the columns bit_cols[col .. col + bits), exponent order;
                                      // kind == KIND_ISZERO: row = the closer, pos / col = the flag's entry in it, bits = its SolvePairDev
                                      // kind == KIND_DIVREM: pos / col = the quotient's entry, inv = 1 / cq, bits = its SolveDivDev
+                                     // kind == KIND_INDICATOR: pos / col = the indicator's entry, bits = 1: it lies in B_r and K = A_r,
+                                     //                         0: the other way round; inv is not set
     Fp<P> inv;                       // 1 / coefficient (k_solve_inv)
     uint32_t level, pad;             // a stuck step lowers the stuck word to (level << 32) | row; level is 0 unless the plan is reordered
 };
@@ -76,7 +80,7 @@ __device__ __forceinline__ unsigned long long stuck_key(const SolveStepDev<P> &s
     return (unsigned long long)level << 32 | s.row;
 }
 
-// either marker (divrem.cuh: marker_byte)
+// any of the three markers (divrem.cuh: marker_byte)
 template <class P>
 __device__ __forceinline__ bool is_marker(const Fp<P> &v) {
     return marker_byte<P>(v) != 0;
@@ -110,6 +114,7 @@ __global__ __launch_bounds__(256) void k_solve_inv(CsrDev A, CsrDev B, CsrDev Cm
                                                    const SolveDivDev *divs) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count + 2 * n_pairs) return;
+    if (t < count && steps[t].kind == pmsolve::KIND_INDICATOR) return;      // no inverse: the record stays as the host wrote it
     const Fp<P> *at;
     Fp<P> *out;
     if (t < count) {                 // an is-zero step's own entry is the flag's, in the closer's A or B; a division step's the quotient's
@@ -265,6 +270,13 @@ __device__ __forceinline__ void solve_divrem(const CsrDev &A, const CsrDev &B, c
     z[dv.col_r] = rem;
 }
 
+// one indicator row on one assignment: z_u = [K z == 0] as field one or field zero, whatever u's coefficient is.  K's whole row (the
+// indicator's side has no other non-zero entry and C_r none at all); the column still holds its marker.  No division, never stuck.
+template <class P>
+__device__ __forceinline__ void solve_indicator(const CsrDev &A, const CsrDev &B, const SolveStepDev<P> &s, Fp<P> *z) {
+    z[s.col] = indicator_of<P>(row_dot_skip<P>(s.bits ? A : B, z, s.row, SOLVE_NONE));
+}
+
 template <class P, bool DIV>
 __global__ __launch_bounds__(256) void k_solve_level(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, uint32_t lo, uint32_t hi,
                                                      Fp<P> *xw, uint64_t ncols, unsigned long long *stuck) {
@@ -297,9 +309,17 @@ __global__ __launch_bounds__(256) void k_solve_divrem(CsrDev A, CsrDev B, CsrDev
     solve_divrem<P>(A, B, Cm, steps[t], divs[steps[t].bits], xw + b * ncols, stuck + b);
 }
 
+template <class P>
+__global__ __launch_bounds__(256) void k_solve_indicator(CsrDev A, CsrDev B, const SolveStepDev<P> *__restrict__ steps, uint32_t lo, uint32_t hi, Fp<P> *xw,
+                                                         uint64_t ncols) {
+    const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (t >= hi) return;
+    solve_indicator<P>(A, B, steps[t], xw + b * ncols);
+}
+
 // the step index is the same in every lane: the step record, the pair record, the row's CSR metadata and a decomposition's column
 // list are uniform loads.  A range with an is-zero pair or a division row is a dividing one (the plan says so): the DIV = false body
-// has no such branches.
+// has no such branches.  An indicator row does not divide and is a branch of both.
 template <class P, bool DIV>
 __global__ __launch_bounds__(64) void k_solve_chain(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, const uint32_t *__restrict__ bit_cols,
                                                     const SolvePairDev<P> *__restrict__ pairs, const SolveDivDev *__restrict__ divs, uint32_t lo, uint32_t hi,
@@ -313,6 +333,8 @@ __global__ __launch_bounds__(64) void k_solve_chain(CsrDev A, CsrDev B, CsrDev C
             if constexpr (DIV) solve_iszero<P>(A, B, Cm, steps[t], pairs[steps[t].bits], z);
         } else if (steps[t].kind == pmsolve::KIND_DIVREM) {
             if constexpr (DIV) solve_divrem<P>(A, B, Cm, steps[t], divs[steps[t].bits], z, stuck + b);      // as above
+        } else if (steps[t].kind == pmsolve::KIND_INDICATOR) {
+            solve_indicator<P>(A, B, steps[t], z);
         } else if (steps[t].bits) solve_bits<P, DIV>(A, B, Cm, steps[t], bit_cols, z, stuck + b);
         else solve_step<P, DIV>(A, B, Cm, steps[t], z, stuck + b);
     }
@@ -431,6 +453,7 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
             const pmsolve::Step &s = sv.plan.steps[t];
             host[t].pos = s.pos; host[t].row = s.row; host[t].col = s.bits ? s.cols_off : s.col; host[t].kind = s.kind; host[t].bits = s.bits;
             host[t].level = sv.plan.reordered ? s.level : 0;
+            if (s.kind == pmsolve::KIND_INDICATOR) host[t].bits = s.cols_off;
             if (s.kind == pmsolve::KIND_DIVREM) {
                 const pmsolve::DivRow &row = sv.plan.divs[s.cols_off];
                 host[t].bits = (uint32_t)host_divs.size();
@@ -498,7 +521,8 @@ int solve_group(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t 
                 else hipLaunchKernelGGL((k_solve_chain<P, false>), grid, block, 0, st, A, B, Cm, steps, bit_cols, pairs, divs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
             } else {
                 const dim3 grid(nblk(l.hi - l.lo), (unsigned)g), block(256);
-                if (l.divrem) hipLaunchKernelGGL((k_solve_divrem<P>), grid, block, 0, st, A, B, Cm, steps, divs, l.lo, l.hi, d_xw, ncols, stuck);
+                if (l.indicator) hipLaunchKernelGGL((k_solve_indicator<P>), grid, block, 0, st, A, B, steps, l.lo, l.hi, d_xw, ncols);
+                else if (l.divrem) hipLaunchKernelGGL((k_solve_divrem<P>), grid, block, 0, st, A, B, Cm, steps, divs, l.lo, l.hi, d_xw, ncols, stuck);
                 else if (l.iszero) hipLaunchKernelGGL((k_solve_iszero<P>), grid, block, 0, st, A, B, Cm, steps, pairs, l.lo, l.hi, d_xw, ncols);
                 else if (l.bits && l.divides) hipLaunchKernelGGL((k_solve_bits<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck);
                 else if (l.bits) hipLaunchKernelGGL((k_solve_bits<P, false>), grid, block, 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck);

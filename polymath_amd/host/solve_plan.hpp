@@ -1,11 +1,12 @@
 // Witness solving, host side: the PLAN that completes a partial assignment by forward propagation through the rows of an R1CS
-// (DESIGN.md §4.10).  Header-only, no HIP: the library's driver (csrc/solve.hip) and five CPU programs (tests/native/
-// solve_plan_selftest.cpp, solve_bits_selftest.cpp, solve_iszero_selftest.cpp, solve_order_selftest.cpp, solve_divrem_selftest.cpp)
-// include the same file.
+// (DESIGN.md §4.10).  Header-only, no HIP: the library's driver (csrc/solve.hip) and six CPU programs (tests/native/
+// solve_plan_selftest.cpp, solve_bits_selftest.cpp, solve_iszero_selftest.cpp, solve_order_selftest.cpp, solve_divrem_selftest.cpp,
+// solve_indicator_selftest.cpp) include the same file.
 //
 // Input: the three matrices in CSR form with the first-entry rule already applied (a column occurs at most once per row and
 // matrix: the key's resident matrices are like that), m0 + mw columns and one byte per column, non-zero = unknown (1: unknown;
-// 2: unknown, and a Euclidean quotient -- the caller's second marker, which has meaning in a division row only).  A stored entry
+// 2: unknown, and a Euclidean quotient -- the caller's second marker, which has meaning in a division row only; 3: unknown, and
+// the indicator of its guard row -- the third marker, which has meaning in an indicator row only).  A stored entry
 // whose coefficient is zero names no variable.  Rows are visited ONCE, in matrix order; at row r, with the columns solved so far:
 //   no unknown column                         a check row, skipped
 //   one unknown u, in exactly one of A, B, C  a solve step (kind = the matrix that holds u); u is known from here on
@@ -62,7 +63,21 @@
 //                 (an unknown on it, or no non-zero entry); the quotient named twice; a third unknown.  In the scheduler below such
 //                 a row WAITS instead, and is a division step as soon as q and rem are its only unknowns.
 //                 Not handled: signed division, cr != -cq, a known rest beside q on its side, a division without the marker.
-// Without the modulus (nullptr) all four additions are off.
+//   indicator row ONE row whose only unknown u carries pattern byte 3 (the caller's third marker: "the indicator of its guard row")
+//                 and is named exactly once, as the ONLY non-zero entry (k, u) of A_r or B_r; the other of the two is the known guard
+//                 side K (no unknown, at least one non-zero entry) and C_r has no non-zero entry: circomlib's Decoder / Multiplexer,
+//                 out[i] <-- (inp == i) ? 1 : 0;  out[i] * (inp - i) === 0.  ONE step of kind KIND_INDICATOR at 1 + max level of what K
+//                 reads:  z_u = (K z == 0) ? 1 : 0, as field one or field zero whatever k is.  The step never divides, needs no inverse
+//                 and never leaves an assignment stuck.  The rows do not determine the value at the hit (0 satisfies them too): it is a
+//                 hint, and the marker says so; with the plain marker the row is the ordinary dividing step it always was, which is
+//                 stuck at the hit.  Step::pos / col name u's entry, Step::cols_off says which side it lies on.  The rule applies
+//                 wherever a row's single unknown, named once, makes an ordinary step (here, and in the scheduler below its one-unknown
+//                 and released-multiplier cases).  Byte 3 has meaning in that position only: a byte-3 column that is the single unknown
+//                 of a row of any other shape (C_r not empty, other non-zero entries beside u on its side, an empty other side) is solved
+//                 by that row as an ordinary step, and named beside other unknowns it is a plain unknown.  No refusal is added.
+//                 Not handled: a hit value other than 1, a non-empty C_r, a known rest beside u, inferring indicators without the
+//                 marker, sharded keys, per-assignment patterns.
+// Without the modulus (nullptr) all five additions are off.
 //
 // build_plan_any_order drops the matrix order: it runs build_plan, and where that refuses, a WAITING-ROW SCHEDULER examines the rows
 // from a min-heap (at first all of them) against the same column state with the same rules, except that these refusals become waiting:
@@ -74,7 +89,7 @@
 //   unknowns                                was none: it is RELEASED and examined again
 //   a pair-pending column in any other way  the row WAITS (the multiplier beside something else, a second unknown, an opener-shaped
 //                                           row over a pending column)
-//   one unknown, named once                 an ordinary step
+//   one unknown, named once                 an ordinary step, or -- byte 3 on it and the indicator shape -- the KIND_INDICATOR step
 //   one unknown, named several times        booleanity: boolean-pending; any other shape WAITS (a later row may determine the column
 //                                           and this one is a check row then)
 //   two or more unknowns                    a decomposition: the bits step; a division row: its step; the opener shape without the
@@ -93,7 +108,7 @@
 //
 // level(step) = 1 + max level of the columns the row reads (given columns: level 0); a decomposition gives all its columns that
 // level.  The steps come out sorted by level, inside a level by kind (C first: the kinds that divide share a launch; then the
-// decompositions in the same order, then the is-zero pairs, then the division rows), stable by row -- one counting sort.  O(nnz + columns), plus k log k per decomposition.
+// decompositions in the same order, then the is-zero pairs, then the division rows, then the indicator rows), stable by row -- one counting sort.  O(nnz + columns), plus k log k per decomposition.
 #pragma once
 #include <stdint.h>
 
@@ -108,11 +123,13 @@ namespace pmsolve {
 
 // z_u = (Az Bz - C_rest) / coef;  (Cz / Bz - A_rest) / coef;  (Cz / Az - B_rest) / coef;  KIND_BITS_x = KIND_BITS_C + x: a decomposition
 // KIND_ISZERO: an is-zero pair, both columns in one step;  KIND_DIVREM: a division row, quotient and remainder in one step
-enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6, KIND_DIVREM = 7 };
+// KIND_INDICATOR: an indicator row, z_u = [K z == 0]: no division and no inverse
+enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6, KIND_DIVREM = 7, KIND_INDICATOR = 8 };
 constexpr uint32_t NUM_KINDS = 7;        // the kinds that need no second marker: what it always counted
-constexpr uint32_t NUM_STEP_KINDS = 8;   // all of them, KIND_DIVREM included: the key width of finish_plan's counting sort
+constexpr uint32_t NUM_STEP_KINDS = 8;   // KIND_C .. KIND_DIVREM, the kinds whose value comes from field or integer arithmetic on the row: what it counted when kind 7 came
+constexpr uint32_t NUM_SORT_KINDS = 9;   // all of them, KIND_INDICATOR included: the key width of finish_plan's counting sort
 
-constexpr uint8_t PATTERN_UNKNOWN = 1, PATTERN_QUOTIENT = 2;   // the pattern bytes (0: given)
+constexpr uint8_t PATTERN_UNKNOWN = 1, PATTERN_QUOTIENT = 2, PATTERN_INDICATOR = 3;   // the pattern bytes (0: given)
 
 constexpr uint32_t WIDE_STEPS = 32;   // a level of at least this many steps gets launches of its own; narrower ones are walked by one lane per assignment
 
@@ -128,6 +145,7 @@ struct Step {
     uint32_t bits = 0, cols_off = 0;   // a decomposition: Plan::bit_cols[cols_off .. cols_off + bits), exponent order; bits = 0 otherwise
                                        // an is-zero pair: row = the closer, pos / col = the flag's entry in it, Plan::pairs[cols_off]
                                        // a division row: pos / col = the quotient's entry in A_r or B_r, Plan::divs[cols_off]
+                                       // an indicator row: pos / col = the indicator's entry, cols_off = 1: it lies in B_r and K = A_r; 0: the other way round
 };
 
 struct PairRows {     // what an is-zero step needs beside its Step
@@ -147,10 +165,11 @@ struct DivRow {       // what a division step needs beside its Step
 struct Launch {
     uint32_t lo, hi;  // steps [lo, hi) of the sorted list
     uint8_t chain;    // 1: one lane per assignment walks the steps in order; 0: one lane per (step, assignment), all of one level
-    uint8_t divides;  // 1: some step of the range is KIND_A / KIND_B / KIND_BITS_A / KIND_BITS_B / KIND_ISZERO / KIND_DIVREM (1 / cq)
+    uint8_t divides;  // 1: some step of the range is KIND_A / KIND_B / KIND_BITS_A / KIND_BITS_B / KIND_ISZERO / KIND_DIVREM (1 / cq); KIND_INDICATOR does not count
     uint8_t bits = 0; // chain == 0 only.  1: every step of the range is a decomposition; 0: none is
     uint8_t iszero = 0;  // chain == 0 only.  1: every step of the range is an is-zero pair; 0: none is
     uint8_t divrem = 0;  // chain == 0 only.  1: every step of the range is a division row; 0: none is
+    uint8_t indicator = 0;  // chain == 0 only.  1: every step of the range is an indicator row; 0: none is
 };
 
 enum Error : int { OK = 0, ERR_MANY_UNKNOWNS = 1, ERR_TWO_MATRICES = 2, ERR_UNDETERMINED = 3, ERR_COLUMN_ZERO = 4 };
@@ -325,10 +344,22 @@ inline int division_row(const Csr m[3], const std::vector<Unknown> &occ, const u
     return 1;
 }
 
+// The indicator shape, for a row whose ONLY unknown entry is `e` (named once) with nz[k] non-zero entries in matrix k: the column
+// carries byte 3, it is the lone non-zero entry of A_r or B_r, the other of the two is the known guard side K (no unknown -- there
+// is none left -- and at least one non-zero entry) and C_r has no non-zero entry.  Any other shape is an ordinary step.
+inline bool indicator_row(const Unknown &e, const uint32_t nz[3], const uint8_t *unknown) {
+    return unknown[e.col] == PATTERN_INDICATOR && e.matrix < 2 && nz[e.matrix] == 1 && nz[1 - e.matrix] >= 1 && nz[2] == 0;
+}
+inline Step indicator_step(const Unknown &e, uint32_t r, uint32_t lv) {
+    Step s{e.pos, r, e.col, KIND_INDICATOR, lv};
+    s.cols_off = e.matrix;   // 1: the indicator lies in B_r and K = A_r
+    return s;
+}
+
 // The tail both builders share: p.steps (in ROW order, levels set) sorted by (level, kind), stable by row; level_ptr; the launch schedule.
 inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
     // counting sort by (level, kind); the row order inside a key is the order the steps come in
-    constexpr size_t K = NUM_STEP_KINDS;
+    constexpr size_t K = NUM_SORT_KINDS;
     std::vector<uint32_t> start((size_t)max_level * K + 1, 0);
     for (const Step &s : p.steps) ++start[(size_t)(s.level - 1) * K + s.kind + 1];
     for (size_t i = 1; i < start.size(); ++i) start[i] += start[i - 1];
@@ -341,18 +372,21 @@ inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
         p.steps.swap(sorted);
     }
     // launch schedule: a wide level is its own launch, split where the dividing kinds begin, again where the decompositions and
-    // their dividing kinds begin, where the is-zero pairs begin and where the division rows begin; consecutive narrow levels are one chain
+    // their dividing kinds begin, where the is-zero pairs begin, where the division rows begin and where the indicator rows begin (which
+    // do not divide: a chain of C-steps and indicators is a non-dividing one); consecutive narrow levels are one chain
     for (uint32_t l = 0; l < max_level; ++l) {
         const uint32_t *at = start.data() + (size_t)l * K;
-        const uint32_t lo = at[KIND_C], ab = at[KIND_A], bits = at[KIND_BITS_C], bits_ab = at[KIND_BITS_A], pairs = at[KIND_ISZERO], divs = at[KIND_DIVREM], hi = at[K];
-        const uint8_t divides = (uint8_t)(bits > ab || hi > bits_ab);
+        const uint32_t lo = at[KIND_C], ab = at[KIND_A], bits = at[KIND_BITS_C], bits_ab = at[KIND_BITS_A], pairs = at[KIND_ISZERO], divs = at[KIND_DIVREM],
+                       inds = at[KIND_INDICATOR], hi = at[K];
+        const uint8_t divides = (uint8_t)(bits > ab || inds > bits_ab);
         if (hi - lo >= wide_steps) {
             if (ab > lo) p.launches.push_back(Launch{lo, ab, 0, 0});
             if (bits > ab) p.launches.push_back(Launch{ab, bits, 0, 1});
             if (bits_ab > bits) p.launches.push_back(Launch{bits, bits_ab, 0, 0, 1});
             if (pairs > bits_ab) p.launches.push_back(Launch{bits_ab, pairs, 0, 1, 1});
             if (divs > pairs) p.launches.push_back(Launch{pairs, divs, 0, 1, 0, 1});
-            if (hi > divs) p.launches.push_back(Launch{divs, hi, 0, 1, 0, 0, 1});
+            if (inds > divs) p.launches.push_back(Launch{divs, inds, 0, 1, 0, 0, 1});
+            if (hi > inds) p.launches.push_back(Launch{inds, hi, 0, 0, 0, 0, 0, 1});
         } else if (!p.launches.empty() && p.launches.back().chain) {
             p.launches.back().hi = hi;
             p.launches.back().divides |= divides;
@@ -461,7 +495,7 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
             const uint32_t u = occ[0].col;
             level[u] = lv;
             if (lv > max_level) max_level = lv;
-            p.steps.push_back(Step{occ[0].pos, (uint32_t)r, u, KIND_OF[occ[0].matrix], lv});
+            p.steps.push_back(modulus && indicator_row(occ[0], nz, unknown) ? indicator_step(occ[0], (uint32_t)r, lv) : Step{occ[0].pos, (uint32_t)r, u, KIND_OF[occ[0].matrix], lv});
             continue;
         }
         const uint32_t u = occ[0].col;
@@ -699,7 +733,7 @@ inline bool schedule_any_order(const Csr m[3], uint64_t nr, uint64_t ncols, cons
         const uint32_t lv = reads + 1;
         if (one_column) {
             if (occ.size() == 1) {
-                p.steps.push_back(Step{occ[0].pos, r, u, KIND_OF[occ[0].matrix], lv});
+                p.steps.push_back(indicator_row(occ[0], nz, unknown) ? indicator_step(occ[0], r, lv) : Step{occ[0].pos, r, u, KIND_OF[occ[0].matrix], lv});
                 solved(u, lv);
             } else if (is_booleanity(m, r, occ, nz, modulus)) {
                 if (bool_row[u] == NONE) {

@@ -21,6 +21,7 @@ MINUS_ALPHA, MINUS_GAMMA = 3, 5        # common.rs:11,14
 B_POLYMATH = b"polymath"               # common.rs:8
 UNKNOWN = api.UNKNOWN_LIMBS             # the marker limbs of a value the device is to solve (PM_ASSIGNMENT_SOLVE); >= r on both curves
 QUOTIENT = api.QUOTIENT_LIMBS           # the same, and the value is the Euclidean quotient of its division row (q * b = a - rem); >= r as well
+INDICATOR = api.INDICATOR_LIMBS         # the same, and the value is the indicator of its guard row (out * (inp - i) = 0: 1 where inp == i, else 0)
 
 FIELDS = {
     "bls12_381": dict(r=0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001,
@@ -441,15 +442,16 @@ class Polymath:
     # ---- partial assignments: the caller gives the values it chooses, the device computes the rest (PM_ASSIGNMENT_SOLVE)
     def partial_limbs(self, instance, witness):
         """(x_limbs, w_limbs) of an assignment given as ints, with UNKNOWN (or None) where the value is to be solved and QUOTIENT
-        where it is to be solved as the Euclidean quotient of its division row (the remainder of that row is a plain unknown)."""
+        where it is to be solved as the Euclidean quotient of its division row (the remainder of that row is a plain unknown), INDICATOR
+        where it is to be solved as the indicator of its guard row."""
         f = self.field
-        marked = lambda v: v is None or v is UNKNOWN or v is QUOTIENT
+        marked = lambda v: v is None or v is UNKNOWN or v is QUOTIENT or v is INDICATOR
         x = f.fr_limbs([0 if marked(v) else v for v in instance]).reshape(-1, 4).copy()
         w = f.fr_limbs([0 if marked(v) else v for v in witness]).reshape(-1, 4).copy() if len(witness) else np.zeros((0, 4), dtype=np.uint64)
         for arr, vals in ((x, instance), (w, witness)):
             for j, v in enumerate(vals):
                 if marked(v):
-                    arr[j] = api.QUOTIENT_LIMBS if v is QUOTIENT else api.UNKNOWN_LIMBS
+                    arr[j] = api.QUOTIENT_LIMBS if v is QUOTIENT else api.INDICATOR_LIMBS if v is INDICATOR else api.UNKNOWN_LIMBS
         return x, w
 
     def solve_batch(self, pk, partials, device_ptrs=None):

@@ -89,10 +89,11 @@ pub const PM_PROVE_GLUE_DEVICE: i32 = 256;
 // pm_assignment_flags: the `assignment_on_device` argument of pm_host_prove[_batch] and pm_r1cs_check[_batch] is a flag word
 pub const PM_ASSIGNMENT_DEVICE: i32 = 1;
 pub const PM_ASSIGNMENT_SOLVE: i32 = 2;
-// the two markers of PM_ASSIGNMENT_SOLVE (little-endian words of one Fr, both >= r on both curves): unknown; unknown, and the Euclidean
-// quotient of its division row
+// the three markers of PM_ASSIGNMENT_SOLVE (little-endian words of one Fr, all >= r on both curves): unknown; unknown, and the Euclidean
+// quotient of its division row; unknown, and the indicator of its guard row
 pub const PM_UNKNOWN_WORDS: [u64; 4] = [u64::MAX, u64::MAX, u64::MAX, u64::MAX];
 pub const PM_UNKNOWN_QUOTIENT_WORDS: [u64; 4] = [u64::MAX - 1, u64::MAX, u64::MAX, u64::MAX];
+pub const PM_HINT_INDICATOR_WORDS: [u64; 4] = [u64::MAX, u64::MAX - 1, u64::MAX, u64::MAX];
 
 // pm_transcript
 pub const PM_TRANSCRIPT_MERLIN: i32 = 0;

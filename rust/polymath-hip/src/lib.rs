@@ -208,6 +208,12 @@ fn fr_ptr<F>(s: &[F]) -> *const u64 {
 /// explicit: with `None` on a quotient the row is refused, as it always was.
 pub const UNKNOWN_QUOTIENT: [u64; 4] = sys::PM_UNKNOWN_QUOTIENT_WORDS;
 
+/// The indicator marker of `PM_ASSIGNMENT_SOLVE` (`PM_HINT_INDICATOR_WORDS`): four limbs that are no field element on either curve
+/// and say "unknown, and the indicator of its guard row" (`out * (inp - i) = 0`: circomlib's `Decoder` / `Multiplexer`,
+/// `out[i] <-- (inp == i) ? 1 : 0`).  The value is 1 where the guard's known side is zero and 0 elsewhere.  The marker is explicit:
+/// with `None` on such a column the row is an ordinary dividing row, which is stuck where `inp == i`, as it always was.
+pub const HINT_INDICATOR: [u64; 4] = sys::PM_HINT_INDICATOR_WORDS;
+
 /// Montgomery limbs of a partial assignment appended to `out`: a value's own four words, or the unknown marker (four times
 /// `u64::MAX`: not a field element on either curve) for `None`.
 fn partial_limbs<F>(vals: &[Option<F>], out: &mut Vec<u64>) {

@@ -18,7 +18,11 @@ on one that tests equality (one dependency level of N is-zero pairs; about half 
   python tools/prove_bench.py --circuit divrem --batch 256 --reps 5 --solve      DivRem, 256 divisions of 32-bit operands;
                                                                                  divrem:N:BITS for others
 on one that divides integers (one dependency level of N Euclidean division rows, then 3 N range checks; route (b) marks the
-quotients with the quotient marker).
+quotients with the quotient marker), and
+  python tools/prove_bench.py --circuit tablewalk --batch 256 --reps 5 --solve   TableWalk, a table of 64 signals walked for 32 steps;
+                                                                                 tablewalk:WIDTH:STEPS for others
+on one that reads a table at a signal (per step one level of WIDTH indicator rows, the decoder's sum and WIDTH products, the next
+index; route (b) marks the decoders' outputs with the indicator marker).
   python tools/prove_bench.py --circuit mimc322 --batch 256 --reps 5 --solve --reorder reverse     or --reorder SEED
 runs either --solve comparison on the same circuit with its constraint rows stored in another order (circuits.Reordered: reversed, or
 shuffled by SEED; a matchcount gadget moves as a block so that every opener stays before its closer).  Route (b) then goes through the
@@ -36,7 +40,7 @@ from polymath_amd import circuits as PC
 from polymath_amd.polymath import Polymath
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants), bench:NC (BenchCircuit, NC constraints), arx[:WIDTH:ROUNDS] (ArxDemo), matchcount[:N:FORM] (MatchCount) or divrem[:N:BITS] (DivRem)")
+ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants), bench:NC (BenchCircuit, NC constraints), arx[:WIDTH:ROUNDS] (ArxDemo), matchcount[:N:FORM] (MatchCount), divrem[:N:BITS] (DivRem) or tablewalk[:WIDTH:STEPS] (TableWalk)")
 ap.add_argument("--batch", type=int, default=16)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--curve", default="bls12_381")
@@ -46,8 +50,8 @@ ap.add_argument("--glue", choices=("host", "device"), default="host", help="devi
 ap.add_argument("--solve", action="store_true", help="host-synthesised assignments against partial assignments solved on the GPU")
 ap.add_argument("--reorder", default=None, metavar="reverse|SEED", help="with --solve: the circuit's rows stored reversed or shuffled by SEED (unmeasured)")
 a = ap.parse_args()
-if a.solve and not a.circuit.startswith(("mimc", "arx", "matchcount", "divrem")):
-    ap.error("--solve needs a mimcK, an arx, a matchcount or a divrem circuit")
+if a.solve and not a.circuit.startswith(("mimc", "arx", "matchcount", "divrem", "tablewalk")):
+    ap.error("--solve needs a mimcK, an arx, a matchcount, a divrem or a tablewalk circuit")
 if a.reorder is not None and not a.solve:
     ap.error("--reorder goes with --solve")
 pm = Polymath(a.curve, a.transcript, device=0)
@@ -77,6 +81,11 @@ elif a.circuit.startswith("divrem"):
     n_div, bits = (int(v) for v in a.circuit.split(":")[1:3]) if ":" in a.circuit else (256, 32)
     make = lambda: PC.DivRem([(g.next_u64() % (1 << bits), 1 + g.next_u64() % ((1 << bits) - 1)) for _ in range(n_div)], bits)
     again = lambda c: PC.DivRem(c.pairs, c.bits)
+    partial_of = lambda c: c.partial(r)
+elif a.circuit.startswith("tablewalk"):
+    width, walk_steps = (int(v) for v in a.circuit.split(":")[1:3]) if ":" in a.circuit else (64, 32)
+    make = lambda: PC.TableWalk([g.next_u64() % width for _ in range(width)], g.next_u64() % width, walk_steps)
+    again = lambda c: PC.TableWalk(c.table, c.start, c.steps, c.signals)
     partial_of = lambda c: c.partial(r)
 else:
     nc = int(a.circuit.split(":", 1)[1])
