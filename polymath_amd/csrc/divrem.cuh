@@ -1,8 +1,9 @@
 // The markers of a partial assignment (marker_byte: THE marker test, for the solver and for both glue modes of the provers), the
-// indicator step's value (indicator_of; solve.hip: solve_indicator) and the Euclidean division of canonical residues, for the
-// witness solver's division step (solve.hip: k_solve_pattern, solve_divrem).  ONE set of routines for device and
-// host: the kernels call them per (step, assignment), the CPU self-tests (tests/native/solve_divrem_selftest.cpp,
-// solve_indicator_selftest.cpp) execute plans with them on the host field type.
+// indicator step's value (indicator_of; solve_steps.cuh: solve_indicator) and the Euclidean division of canonical residues, for the
+// witness solver's division step (solve.hip: k_solve_pattern; solve_steps.cuh: solve_divrem).  ONE set of routines
+// for device and host: the kernels call them per (step, assignment) through the step bodies of solve_steps.cuh, and the CPU
+// self-tests (tests/native/solve_selftest.hpp, the rig of the six solve_*_selftest.cpp) execute plans through the same bodies on the
+// host field type.
 //
 // Restoring shift-subtract on four 64-bit words with a FIXED trip count of 256: the 512-bit register (hi : lo) starts as (0 : a),
 // every round shifts it left by one, subtracts d from hi on trial and keeps the difference under a mask; the quotient bit enters

@@ -1,7 +1,10 @@
 // PM_ASSIGNMENT_SOLVE: complete partial assignments on the device by forward propagation through the key's resident constraint rows
 // (include/polymath_hip.h), so that a caller supplies only the values it chooses and the library computes the rest
 // before it checks or proves.  The PLAN -- which row determines which column, in which order -- is host work, done once per (key,
-// pattern) by host/solve_plan.hpp; the arithmetic is the kernels below, assignment = grid y (or the lane, in the chain kernel):
+// pattern) by host/solve_plan.hpp; what ONE step does to ONE assignment (solve_step, solve_bits, solve_iszero, solve_divrem,
+// solve_indicator, the dispatch solve_any, the inverses' solve_inverse, and the records a plan becomes: solve_records) is
+// solve_steps.cuh, text that the CPU self-tests run as well; this file is the kernels that call it and the host driver,
+// assignment = grid y (or the lane, in the chain kernel):
 //   k_solve_pattern   one lane per (column, assignment): the unknown pattern of assignment 0 (a byte per column: 1 the unknown
 //                     marker, 2 the quotient marker, 3 the indicator marker); every other assignment is compared with it, byte for byte, and the first
 //                     differing (assignment, column) lowers one word
@@ -38,39 +41,11 @@
 
 #include "internal.h"
 #include "prove_common.cuh"
-#include "divrem.cuh"
+#include "solve_steps.cuh"
 
 namespace pm {
 
-constexpr uint64_t SOLVE_NONE = ~(uint64_t)0;   // no stuck row / no mismatch / no entry to skip
-
-template <class P>
-struct SolveStepDev {
-    uint64_t pos;                    // the unknown's entry in its matrix; a decomposition: the entry that holds c
-    uint32_t row, col, kind, bits;   // bits != 0: a decomposition into the columns bit_cols[col .. col + bits), exponent order;
-                                     // kind == KIND_ISZERO: row = the closer, pos / col = the flag's entry in it, bits = its SolvePairDev
-                                     // kind == KIND_DIVREM: pos / col = the quotient's entry, inv = 1 / cq, bits = its SolveDivDev
-                                     // kind == KIND_INDICATOR: pos / col = the indicator's entry, bits = 1: it lies in B_r and K = A_r,
-                                     //                         0: the other way round; inv is not set
-    Fp<P> inv;                       // 1 / coefficient (k_solve_inv)
-    uint32_t level, pad;             // a stuck step lowers the stuck word to (level << 32) | row; level is 0 unless the plan is reordered
-};
-
-// what an is-zero step needs beside its SolveStepDev: the opener row r1
-template <class P>
-struct SolvePairDev {
-    uint64_t pos_m, pos_c;           // (cm, m) in A_r1 or B_r1; (cb, b) in C_r1
-    uint32_t row1, col_m;
-    uint32_t m_in_b, b_in_b;         // K1 = A_r1 (the multiplier lies in B_r1) / K2 = A_r2 (the flag lies in B_r2); 0: the B sides
-    uint32_t negated, pad;           // K2 = -K1
-    Fp<P> inv_cm, inv_cb;            // k_solve_inv
-};
-
-// what a division step needs beside its SolveStepDev
-struct SolveDivDev {
-    uint64_t pos_r;                  // (cr, rem) in C_r
-    uint32_t col_r, q_in_b;          // the remainder's column; K = A_r (the quotient lies in B_r), 0: K = B_r
-};
+using pmsolve::Csr;   // the kernels' matrices: the three pointers of CsrDev, under the name the step bodies know
 
 // What a stuck step lowers the stuck word to.  The level is read HERE, on the rare path (a volatile load the compiler cannot hoist
 // into the registers every step carries): the step bodies keep the registers they had.
@@ -80,11 +55,14 @@ __device__ __forceinline__ unsigned long long stuck_key(const SolveStepDev<P> &s
     return (unsigned long long)level << 32 | s.row;
 }
 
-// any of the three markers (divrem.cuh: marker_byte)
-template <class P>
-__device__ __forceinline__ bool is_marker(const Fp<P> &v) {
-    return marker_byte<P>(v) != 0;
-}
+// the step bodies' sink on the device (solve_steps.cuh): the assignment's stuck word, lowered by a 64-bit atomic minimum
+struct StuckWord {
+    unsigned long long *word;
+    template <class P>
+    __device__ __forceinline__ void operator()(const SolveStepDev<P> &s) const {
+        atomicMin(word, stuck_key<P>(s));
+    }
+};
 
 // xw: [g][ncols], the group's rows; g0 = the batch index of row 0.  pattern: one byte per column, written from assignment 0 of the
 // batch (a lane per byte) and read by the groups after the first (an earlier launch wrote it); the rows that share assignment 0's
@@ -102,199 +80,32 @@ __global__ __launch_bounds__(256) void k_solve_pattern(const Fp<P> *xw, uint64_t
     if (unknown != expected) atomicMin(mismatch, (unsigned long long)(((g0 + b) << 32) | j));
 }
 
-__device__ __forceinline__ const CsrDev &matrix_of(uint32_t kind, const CsrDev &A, const CsrDev &B, const CsrDev &Cm) {
-    return kind == pmsolve::KIND_A ? A : kind == pmsolve::KIND_B ? B : Cm;
-}
-
-// KIND_BITS_x -> KIND_x
-__device__ __forceinline__ uint32_t matrix_kind(uint32_t kind) { return kind >= pmsolve::KIND_BITS_C ? kind - pmsolve::KIND_BITS_C : kind; }
-
 template <class P>
-__global__ __launch_bounds__(256) void k_solve_inv(CsrDev A, CsrDev B, CsrDev Cm, SolveStepDev<P> *steps, uint64_t count, SolvePairDev<P> *pairs, uint64_t n_pairs,
+__global__ __launch_bounds__(256) void k_solve_inv(Csr A, Csr B, Csr Cm, SolveStepDev<P> *steps, uint64_t count, SolvePairDev<P> *pairs, uint64_t n_pairs,
                                                    const SolveDivDev *divs) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count + 2 * n_pairs) return;
-    if (t < count && steps[t].kind == pmsolve::KIND_INDICATOR) return;      // no inverse: the record stays as the host wrote it
-    const Fp<P> *at;
-    Fp<P> *out;
-    if (t < count) {                 // an is-zero step's own entry is the flag's, in the closer's A or B; a division step's the quotient's
-        const uint32_t kind = steps[t].kind;
-        const CsrDev &M = kind == pmsolve::KIND_ISZERO ? (pairs[steps[t].bits].b_in_b ? B : A)
-                        : kind == pmsolve::KIND_DIVREM ? (divs[steps[t].bits].q_in_b ? B : A) : matrix_of(matrix_kind(kind), A, B, Cm);
-        at = (const Fp<P> *)(M.val + 4 * steps[t].pos);
-        out = &steps[t].inv;
-    } else {
-        SolvePairDev<P> &pr = pairs[(t - count) >> 1];
-        const bool multiplier = ((t - count) & 1) == 0;
-        at = (const Fp<P> *)(multiplier ? (pr.m_in_b ? B : A).val + 4 * pr.pos_m : Cm.val + 4 * pr.pos_c);
-        out = multiplier ? &pr.inv_cm : &pr.inv_cb;
-    }
-    const Fp<P> coef = *at;
-    *out = coef.eq(Fp<P>::one()) ? coef : inverse<P>(coef);
-}
-
-// (M z)_r without entry `skip` (SOLVE_NONE: the whole row)
-template <class P>
-__device__ __forceinline__ Fp<P> row_dot_skip(const CsrDev &M, const Fp<P> *z, uint64_t r, uint64_t skip) {
-    Fp<P> acc = Fp<P>::zero();
-    for (uint64_t k = M.rowptr[r]; k < M.rowptr[r + 1]; ++k) {
-        if (k == skip) continue;
-        acc = add<P>(acc, mul<P>(*(const Fp<P> *)(M.val + 4 * k), z[M.col[k]]));
-    }
-    return acc;
-}
-
-// (M z)_r without the entries whose value is still the marker.  In a decomposition row those are exactly its k unknowns: every other
-// column the row names was given (never a marker) or was stored by an earlier level or an earlier step of this lane (a field
-// element, zero where that step was stuck).
-template <class P>
-__device__ __forceinline__ Fp<P> row_dot_unmarked(const CsrDev &M, const Fp<P> *z, uint64_t r) {
-    Fp<P> acc = Fp<P>::zero();
-    for (uint64_t k = M.rowptr[r]; k < M.rowptr[r + 1]; ++k) {
-        const Fp<P> v = z[M.col[k]];
-        if (is_marker<P>(v)) continue;
-        acc = add<P>(acc, mul<P>(*(const Fp<P> *)(M.val + 4 * k), v));
-    }
-    return acc;
-}
-
-// one step on one assignment (z = its x || w row): the partial dot products of the row, the unknown's entry left out, then
-//   kind C: z_u = (Az Bz - C_rest) / coef      kind A: z_u = (Cz / Bz - A_rest) / coef      kind B: z_u = (Cz / Az - B_rest) / coef
-template <class P, bool DIV>
-__device__ __forceinline__ void solve_step(const CsrDev &A, const CsrDev &B, const CsrDev &Cm, const SolveStepDev<P> &s, Fp<P> *z,
-                                           unsigned long long *stuck) {
-    const uint64_t r = s.row;
-    const uint32_t kind = s.kind;
-    const Fp<P> az = row_dot_skip<P>(A, z, r, kind == pmsolve::KIND_A ? s.pos : SOLVE_NONE);
-    const Fp<P> bz = row_dot_skip<P>(B, z, r, kind == pmsolve::KIND_B ? s.pos : SOLVE_NONE);
-    const Fp<P> cz = row_dot_skip<P>(Cm, z, r, kind == pmsolve::KIND_C ? s.pos : SOLVE_NONE);
-    Fp<P> v;
-    if (!DIV || kind == pmsolve::KIND_C) {
-        v = sub<P>(mul<P>(az, bz), cz);
-    } else {
-        const Fp<P> den = kind == pmsolve::KIND_A ? bz : az, rest = kind == pmsolve::KIND_A ? az : bz;
-        if (den.is_zero()) {        // 0 / 0 included: the value is then undetermined
-            atomicMin(stuck, stuck_key<P>(s));
-            z[s.col] = Fp<P>::zero();
-            return;
-        }
-        v = sub<P>(mul<P>(cz, inverse<P>(den)), rest);
-    }
-    z[s.col] = mul<P>(v, s.inv);
-}
-
-// one decomposition on one assignment: t = (the unknown part of the row) / c with the k unknown entries left out of the dot
-// product -- their columns still hold the marker, and row_dot_unmarked passes over markers -- then z_{cols[i]} = bit i of the
-// canonical integer of t, as field 0 or field 1.  t >= 2^k has no such form: stuck, like a zero divisor, with zero in all k columns.
-template <class P, bool DIV>
-__device__ __forceinline__ void solve_bits(const CsrDev &A, const CsrDev &B, const CsrDev &Cm, const SolveStepDev<P> &s, const uint32_t *__restrict__ bit_cols,
-                                           Fp<P> *z, unsigned long long *stuck) {
-    const uint64_t r = s.row;
-    const uint32_t kind = matrix_kind(s.kind), k = s.bits;
-    const uint32_t *cols = bit_cols + s.col;
-    const Fp<P> az = kind == pmsolve::KIND_A ? row_dot_unmarked<P>(A, z, r) : row_dot_skip<P>(A, z, r, SOLVE_NONE);
-    const Fp<P> bz = kind == pmsolve::KIND_B ? row_dot_unmarked<P>(B, z, r) : row_dot_skip<P>(B, z, r, SOLVE_NONE);
-    const Fp<P> cz = kind == pmsolve::KIND_C ? row_dot_unmarked<P>(Cm, z, r) : row_dot_skip<P>(Cm, z, r, SOLVE_NONE);
-    Fp<P> v = Fp<P>::zero();
-    bool ok = true;
-    if (!DIV || kind == pmsolve::KIND_C) {
-        v = sub<P>(mul<P>(az, bz), cz);
-    } else {
-        const Fp<P> den = kind == pmsolve::KIND_A ? bz : az, rest = kind == pmsolve::KIND_A ? az : bz;
-        ok = !den.is_zero();
-        if (ok) v = sub<P>(mul<P>(cz, inverse<P>(den)), rest);
-    }
-    Fp<P> t = Fp<P>::zero();
-    if (ok) {
-        t = from_mont<P>(mul<P>(v, s.inv));
-        uint32_t high = 0;           // the bits of t from k upwards; k <= bitlength(r) - 1 < 32 N
-#pragma unroll
-        for (int i = 0; i < P::N; ++i) high |= 32u * i >= k ? t.l[i] : 32u * (i + 1) > k ? t.l[i] >> (k - 32u * i) : 0u;
-        ok = high == 0;
-    }
-    if (!ok) {
-        atomicMin(stuck, stuck_key<P>(s));
-        t = Fp<P>::zero();
-    }
-    for (uint32_t i = 0; i < k; i += 32) {
-        uint32_t word = 0;
-#pragma unroll
-        for (int w = 0; w < P::N; ++w) word = i == 32u * w ? t.l[w] : word;   // t.l[i / 32] without indexing registers
-        for (uint32_t j = i; j < k && j < i + 32; ++j) {
-            const uint32_t mask = 0u - ((word >> (j - i)) & 1u);              // one & mask: field 1 or field 0, no table to select from
-            Fp<P> bit;
-#pragma unroll
-            for (int w = 0; w < P::N; ++w) bit.l[w] = P::ONE[w] & mask;
-            z[cols[j]] = bit;
-        }
-    }
-}
-
-// one is-zero pair on one assignment.  d1 = K1 z is the tested value up to sign, d2 = K2 z = +-d1 by the plan, so ONE inversion
-// serves both rows; inverse<P>(0) is 0 (a power of zero), which is the convention for the free multiplier, so m needs no branch and
-// only b is a select:
-//   d1 != 0:  b = ((C_r2 z) / d2 - rest_r2) / kb,   m = ((C_r1 z, with b) / d1) / cm
-//   d1 == 0:  b = -C_r1_rest / cb,                  m = 0
-// Both columns still hold the marker; the dot products leave their entries out by position.
-template <class P>
-__device__ __forceinline__ void solve_iszero(const CsrDev &A, const CsrDev &B, const CsrDev &Cm, const SolveStepDev<P> &s, const SolvePairDev<P> &pr, Fp<P> *z) {
-    const uint64_t r1 = pr.row1, r2 = s.row;
-    const Fp<P> d1 = row_dot_skip<P>(pr.m_in_b ? A : B, z, r1, SOLVE_NONE);
-    const Fp<P> c1_rest = row_dot_skip<P>(Cm, z, r1, pr.pos_c);
-    const Fp<P> rest2 = row_dot_skip<P>(pr.b_in_b ? B : A, z, r2, s.pos);
-    const Fp<P> c2 = row_dot_skip<P>(Cm, z, r2, SOLVE_NONE);
-    const Fp<P> inv1 = inverse<P>(d1);
-    const Fp<P> inv2 = pr.negated ? neg<P>(inv1) : inv1;
-    const Fp<P> b_unequal = mul<P>(sub<P>(mul<P>(c2, inv2), rest2), s.inv);
-    const Fp<P> b_equal = mul<P>(neg<P>(c1_rest), pr.inv_cb);
-    const Fp<P> b = d1.is_zero() ? b_equal : b_unequal;
-    const Fp<P> c1 = add<P>(c1_rest, mul<P>(*(const Fp<P> *)(Cm.val + 4 * pr.pos_c), b));
-    z[s.col] = b;
-    z[pr.col_m] = mul<P>(mul<P>(c1, inv1), pr.inv_cm);
-}
-
-// one division row on one assignment: cq q (K z) = R - cq rem, so with d = K z and a = R / cq as canonical integers
-//   d != 0:  q = floor(a / d),  rem = a mod d      (euclid_divrem: Montgomery -> canonical, 256 / 256 bits, back)
-//   d == 0:  stuck at the row, zero in both columns
-// The partial dot products as the is-zero step forms them: K's whole row and C's without rem's entry; the quotient's side has no
-// other non-zero entry, so its partial dot product is zero and is not formed.  Both columns still hold their markers.
-template <class P>
-__device__ __forceinline__ void solve_divrem(const CsrDev &A, const CsrDev &B, const CsrDev &Cm, const SolveStepDev<P> &s, const SolveDivDev &dv, Fp<P> *z,
-                                             unsigned long long *stuck) {
-    const uint64_t r = s.row;
-    const Fp<P> d = row_dot_skip<P>(dv.q_in_b ? A : B, z, r, SOLVE_NONE);
-    const Fp<P> a = mul<P>(row_dot_skip<P>(Cm, z, r, dv.pos_r), s.inv);
-    Fp<P> q = Fp<P>::zero(), rem = Fp<P>::zero();
-    if (!euclid_divrem<P>(a, d, &q, &rem)) atomicMin(stuck, stuck_key<P>(s));
-    z[s.col] = q;
-    z[dv.col_r] = rem;
-}
-
-// one indicator row on one assignment: z_u = [K z == 0] as field one or field zero, whatever u's coefficient is.  K's whole row (the
-// indicator's side has no other non-zero entry and C_r none at all); the column still holds its marker.  No division, never stuck.
-template <class P>
-__device__ __forceinline__ void solve_indicator(const CsrDev &A, const CsrDev &B, const SolveStepDev<P> &s, Fp<P> *z) {
-    z[s.col] = indicator_of<P>(row_dot_skip<P>(s.bits ? A : B, z, s.row, SOLVE_NONE));
+    solve_inverse<P>(A, B, Cm, steps, count, pairs, divs, t);
 }
 
 template <class P, bool DIV>
-__global__ __launch_bounds__(256) void k_solve_level(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, uint32_t lo, uint32_t hi,
-                                                     Fp<P> *xw, uint64_t ncols, unsigned long long *stuck) {
+__global__ __launch_bounds__(256) void k_solve_level(Csr A, Csr B, Csr Cm, const SolveStepDev<P> *__restrict__ steps, uint32_t lo, uint32_t hi, Fp<P> *xw,
+                                                     uint64_t ncols, unsigned long long *stuck) {
     const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (t >= hi) return;
-    solve_step<P, DIV>(A, B, Cm, steps[t], xw + b * ncols, stuck + b);
+    solve_step<P, DIV>(A, B, Cm, steps[t], xw + b * ncols, StuckWord{stuck + b});
 }
 
 template <class P, bool DIV>
-__global__ __launch_bounds__(256) void k_solve_bits(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, const uint32_t *__restrict__ bit_cols,
+__global__ __launch_bounds__(256) void k_solve_bits(Csr A, Csr B, Csr Cm, const SolveStepDev<P> *__restrict__ steps, const uint32_t *__restrict__ bit_cols,
                                                     uint32_t lo, uint32_t hi, Fp<P> *xw, uint64_t ncols, unsigned long long *stuck) {
     const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (t >= hi) return;
-    solve_bits<P, DIV>(A, B, Cm, steps[t], bit_cols, xw + b * ncols, stuck + b);
+    solve_bits<P, DIV>(A, B, Cm, steps[t], bit_cols, xw + b * ncols, StuckWord{stuck + b});
 }
 
 template <class P>
-__global__ __launch_bounds__(256) void k_solve_iszero(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, const SolvePairDev<P> *__restrict__ pairs,
+__global__ __launch_bounds__(256) void k_solve_iszero(Csr A, Csr B, Csr Cm, const SolveStepDev<P> *__restrict__ steps, const SolvePairDev<P> *__restrict__ pairs,
                                                       uint32_t lo, uint32_t hi, Fp<P> *xw, uint64_t ncols) {
     const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (t >= hi) return;
@@ -302,15 +113,15 @@ __global__ __launch_bounds__(256) void k_solve_iszero(CsrDev A, CsrDev B, CsrDev
 }
 
 template <class P>
-__global__ __launch_bounds__(256) void k_solve_divrem(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, const SolveDivDev *__restrict__ divs,
+__global__ __launch_bounds__(256) void k_solve_divrem(Csr A, Csr B, Csr Cm, const SolveStepDev<P> *__restrict__ steps, const SolveDivDev *__restrict__ divs,
                                                       uint32_t lo, uint32_t hi, Fp<P> *xw, uint64_t ncols, unsigned long long *stuck) {
     const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (t >= hi) return;
-    solve_divrem<P>(A, B, Cm, steps[t], divs[steps[t].bits], xw + b * ncols, stuck + b);
+    solve_divrem<P>(A, B, Cm, steps[t], divs[steps[t].bits], xw + b * ncols, StuckWord{stuck + b});
 }
 
 template <class P>
-__global__ __launch_bounds__(256) void k_solve_indicator(CsrDev A, CsrDev B, const SolveStepDev<P> *__restrict__ steps, uint32_t lo, uint32_t hi, Fp<P> *xw,
+__global__ __launch_bounds__(256) void k_solve_indicator(Csr A, Csr B, const SolveStepDev<P> *__restrict__ steps, uint32_t lo, uint32_t hi, Fp<P> *xw,
                                                          uint64_t ncols) {
     const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (t >= hi) return;
@@ -318,26 +129,15 @@ __global__ __launch_bounds__(256) void k_solve_indicator(CsrDev A, CsrDev B, con
 }
 
 // the step index is the same in every lane: the step record, the pair record, the row's CSR metadata and a decomposition's column
-// list are uniform loads.  A range with an is-zero pair or a division row is a dividing one (the plan says so): the DIV = false body
-// has no such branches.  An indicator row does not divide and is a branch of both.
+// list are uniform loads (solve_steps.cuh: solve_any, the dispatch by kind).
 template <class P, bool DIV>
-__global__ __launch_bounds__(64) void k_solve_chain(CsrDev A, CsrDev B, CsrDev Cm, const SolveStepDev<P> *__restrict__ steps, const uint32_t *__restrict__ bit_cols,
+__global__ __launch_bounds__(64) void k_solve_chain(Csr A, Csr B, Csr Cm, const SolveStepDev<P> *__restrict__ steps, const uint32_t *__restrict__ bit_cols,
                                                     const SolvePairDev<P> *__restrict__ pairs, const SolveDivDev *__restrict__ divs, uint32_t lo, uint32_t hi,
                                                     Fp<P> *xw, uint64_t ncols, unsigned long long *stuck, uint64_t rows) {
     const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= rows) return;
     Fp<P> *z = xw + b * ncols;
-    for (uint32_t t = lo; t < hi; ++t) {
-        if (steps[t].kind == pmsolve::KIND_ISZERO) {
-            // DIV = false would pass over the pair and leave both markers in place: solve_plan refuses a plan that asks for that
-            if constexpr (DIV) solve_iszero<P>(A, B, Cm, steps[t], pairs[steps[t].bits], z);
-        } else if (steps[t].kind == pmsolve::KIND_DIVREM) {
-            if constexpr (DIV) solve_divrem<P>(A, B, Cm, steps[t], divs[steps[t].bits], z, stuck + b);      // as above
-        } else if (steps[t].kind == pmsolve::KIND_INDICATOR) {
-            solve_indicator<P>(A, B, steps[t], z);
-        } else if (steps[t].bits) solve_bits<P, DIV>(A, B, Cm, steps[t], bit_cols, z, stuck + b);
-        else solve_step<P, DIV>(A, B, Cm, steps[t], z, stuck + b);
-    }
+    for (uint32_t t = lo; t < hi; ++t) solve_any<P, DIV>(A, B, Cm, steps[t], bit_cols, pairs, divs, z, StuckWord{stuck + b});
 }
 
 // After the last launch of a REORDERED plan: the stuck word (level << 32) | row of the root cause becomes its row, which is what
@@ -351,7 +151,7 @@ __global__ __launch_bounds__(256) void k_solve_stuck_row(unsigned long long *stu
 
 namespace {
 
-inline CsrDev csr_dev(const pm_pk *pk, int i) { return CsrDev{pk->d_rowptr[i], pk->d_col[i], pk->d_val[i]}; }
+inline Csr csr_dev(const pm_pk *pk, int i) { return Csr{pk->d_rowptr[i], pk->d_col[i], pk->d_val[i]}; }
 
 }  // namespace
 
@@ -445,38 +245,16 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
     const size_t n_steps = sv.plan.steps.size();
     sv.n_pairs = sv.n_divs = 0;
     if (n_steps) {
-        std::vector<SolveStepDev<P>> host(n_steps);
-        std::vector<SolvePairDev<P>> host_pairs;
-        std::vector<SolveDivDev> host_divs;
-        memset((void *)host.data(), 0, n_steps * sizeof(SolveStepDev<P>));
-        for (size_t t = 0; t < n_steps; ++t) {
-            const pmsolve::Step &s = sv.plan.steps[t];
-            host[t].pos = s.pos; host[t].row = s.row; host[t].col = s.bits ? s.cols_off : s.col; host[t].kind = s.kind; host[t].bits = s.bits;
-            host[t].level = sv.plan.reordered ? s.level : 0;
-            if (s.kind == pmsolve::KIND_INDICATOR) host[t].bits = s.cols_off;
-            if (s.kind == pmsolve::KIND_DIVREM) {
-                const pmsolve::DivRow &row = sv.plan.divs[s.cols_off];
-                host[t].bits = (uint32_t)host_divs.size();
-                host_divs.push_back(SolveDivDev{row.pos_r, row.col_r, row.q_in_b});
-            }
-            if (s.kind != pmsolve::KIND_ISZERO) continue;
-            host[t].bits = (uint32_t)host_pairs.size();
-            SolvePairDev<P> pr;
-            memset((void *)&pr, 0, sizeof pr);
-            const pmsolve::PairRows &rows = sv.plan.pairs[s.cols_off];
-            pr.pos_m = rows.pos_m; pr.pos_c = rows.pos_c; pr.row1 = rows.row1; pr.col_m = rows.col_m; pr.m_in_b = rows.m_in_b; pr.b_in_b = rows.b_in_b;
-            pr.negated = rows.negated;
-            host_pairs.push_back(pr);
-        }
-        sv.n_pairs = host_pairs.size();
+        const SolveRecords<P> rec = solve_records<P>(sv.plan);
+        sv.n_pairs = rec.pairs.size();
         if (sv.n_pairs) {
             PM_HIP(ctx, sv.pairs.reserve(sv.n_pairs * sizeof(SolvePairDev<P>)));
-            PM_HIP(ctx, hipMemcpyAsync(sv.pairs.p, host_pairs.data(), sv.n_pairs * sizeof(SolvePairDev<P>), hipMemcpyHostToDevice, st));
+            PM_HIP(ctx, hipMemcpyAsync(sv.pairs.p, rec.pairs.data(), sv.n_pairs * sizeof(SolvePairDev<P>), hipMemcpyHostToDevice, st));
         }
-        sv.n_divs = host_divs.size();
+        sv.n_divs = rec.divs.size();
         if (sv.n_divs) {
             PM_HIP(ctx, sv.divs.reserve(sv.n_divs * sizeof(SolveDivDev)));
-            PM_HIP(ctx, hipMemcpyAsync(sv.divs.p, host_divs.data(), sv.n_divs * sizeof(SolveDivDev), hipMemcpyHostToDevice, st));
+            PM_HIP(ctx, hipMemcpyAsync(sv.divs.p, rec.divs.data(), sv.n_divs * sizeof(SolveDivDev), hipMemcpyHostToDevice, st));
         }
         const std::vector<uint32_t> &bit_cols = sv.plan.bit_cols;
         if (!bit_cols.empty()) {
@@ -484,11 +262,11 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
             PM_HIP(ctx, hipMemcpyAsync(sv.bit_cols.p, bit_cols.data(), bit_cols.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         }
         PM_HIP(ctx, sv.steps.reserve(n_steps * sizeof(SolveStepDev<P>)));
-        PM_HIP(ctx, hipMemcpyAsync(sv.steps.p, host.data(), n_steps * sizeof(SolveStepDev<P>), hipMemcpyHostToDevice, st));
+        PM_HIP(ctx, hipMemcpyAsync(sv.steps.p, rec.steps.data(), n_steps * sizeof(SolveStepDev<P>), hipMemcpyHostToDevice, st));
         PM_LAUNCH(ctx, k_solve_inv<P>, dim3(nblk(n_steps + 2 * sv.n_pairs)), dim3(256), 0, st, csr_dev(pk, 0), csr_dev(pk, 1), csr_dev(pk, 2),
                        sv.steps.as<SolveStepDev<P>>(), (uint64_t)n_steps, sv.n_pairs ? sv.pairs.as<SolvePairDev<P>>() : nullptr, (uint64_t)sv.n_pairs,
                        sv.n_divs ? sv.divs.as<SolveDivDev>() : nullptr);
-        PM_HIP(ctx, hipStreamSynchronize(st));   // `host`, `host_pairs` and `host_divs` go out of scope
+        PM_HIP(ctx, hipStreamSynchronize(st));   // `rec` goes out of scope
     }
     sv.plan_pattern.swap(pattern);
     sv.plan_key = pk->serial;
@@ -507,7 +285,7 @@ int solve_group(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t 
     PM_HIP(ctx, sv.stuck.reserve(g * sizeof(unsigned long long)));
     unsigned long long *stuck = sv.stuck.as<unsigned long long>();
     PM_HIP(ctx, hipMemsetAsync(stuck, 0xff, g * sizeof(unsigned long long), st));
-    const CsrDev A = csr_dev(pk, 0), B = csr_dev(pk, 1), Cm = csr_dev(pk, 2);
+    const Csr A = csr_dev(pk, 0), B = csr_dev(pk, 1), Cm = csr_dev(pk, 2);
     const SolveStepDev<P> *steps = sv.steps.as<SolveStepDev<P>>();
     const uint32_t *bit_cols = sv.plan.bit_cols.empty() ? nullptr : sv.bit_cols.as<uint32_t>();
     const SolvePairDev<P> *pairs = sv.n_pairs ? sv.pairs.as<SolvePairDev<P>>() : nullptr;

@@ -1,0 +1,282 @@
+// The witness solver's STEP BODIES (solve.hip: the kernels that call them): what one step of a plan does to one
+// assignment, the record a step is on the device and how those records are filled from a pmsolve::Plan.  ONE text for device and
+// host, like field.cuh and divrem.cuh: the kernels call these bodies per (step, assignment), and the CPU self-tests
+// (tests/native/solve_selftest.hpp) walk a plan's launches through the same bodies on the host field type.
+//
+// The one thing the two sides cannot share is what a stuck step does to the assignment's stuck word (a 64-bit atomic minimum on the
+// device, a plain minimum on the host), so the bodies take that action as a SINK: an object called with the step record, at the
+// place where the store used to be.  Plain C++ and vector stores only.
+#pragma once
+#include <cstring>
+#include <vector>
+
+#include "../host/solve_plan.hpp"
+#include "divrem.cuh"
+#include "field.cuh"
+
+namespace pm {
+
+constexpr uint64_t SOLVE_NONE = ~(uint64_t)0;   // no stuck row / no mismatch / no entry to skip
+
+template <class P>
+struct SolveStepDev {
+    uint64_t pos;                    // the unknown's entry in its matrix; a decomposition: the entry that holds c
+    uint32_t row, col, kind, bits;   // bits != 0: a decomposition into the columns bit_cols[col .. col + bits), exponent order;
+                                     // kind == KIND_ISZERO: row = the closer, pos / col = the flag's entry in it, bits = its SolvePairDev
+                                     // kind == KIND_DIVREM: pos / col = the quotient's entry, inv = 1 / cq, bits = its SolveDivDev
+                                     // kind == KIND_INDICATOR: pos / col = the indicator's entry, bits = 1: it lies in B_r and K = A_r,
+                                     //                         0: the other way round; inv is not set
+    Fp<P> inv;                       // 1 / coefficient (solve_inverse)
+    uint32_t level, pad;             // a stuck step lowers the stuck word to (level << 32) | row; level is 0 unless the plan is reordered
+};
+
+// what an is-zero step needs beside its SolveStepDev: the opener row r1
+template <class P>
+struct SolvePairDev {
+    uint64_t pos_m, pos_c;           // (cm, m) in A_r1 or B_r1; (cb, b) in C_r1
+    uint32_t row1, col_m;
+    uint32_t m_in_b, b_in_b;         // K1 = A_r1 (the multiplier lies in B_r1) / K2 = A_r2 (the flag lies in B_r2); 0: the B sides
+    uint32_t negated, pad;           // K2 = -K1
+    Fp<P> inv_cm, inv_cb;            // solve_inverse
+};
+
+// what a division step needs beside its SolveStepDev
+struct SolveDivDev {
+    uint64_t pos_r;                  // (cr, rem) in C_r
+    uint32_t col_r, q_in_b;          // the remainder's column; K = A_r (the quotient lies in B_r), 0: K = B_r
+};
+
+// The three record arrays of a plan, as the kernels read them; the inverses are left zero (solve_inverse fills them).
+template <class P>
+struct SolveRecords {
+    std::vector<SolveStepDev<P>> steps;
+    std::vector<SolvePairDev<P>> pairs;
+    std::vector<SolveDivDev> divs;
+};
+
+template <class P>
+inline SolveRecords<P> solve_records(const pmsolve::Plan &plan) {
+    SolveRecords<P> rec;
+    const size_t n_steps = plan.steps.size();
+    rec.steps.resize(n_steps);
+    if (n_steps) memset((void *)rec.steps.data(), 0, n_steps * sizeof(SolveStepDev<P>));
+    for (size_t t = 0; t < n_steps; ++t) {
+        const pmsolve::Step &s = plan.steps[t];
+        SolveStepDev<P> &d = rec.steps[t];
+        d.pos = s.pos; d.row = s.row; d.col = s.bits ? s.cols_off : s.col; d.kind = s.kind; d.bits = s.bits;
+        d.level = plan.reordered ? s.level : 0;
+        if (s.kind == pmsolve::KIND_INDICATOR) d.bits = s.cols_off;
+        if (s.kind == pmsolve::KIND_DIVREM) {
+            const pmsolve::DivRow &row = plan.divs[s.cols_off];
+            d.bits = (uint32_t)rec.divs.size();
+            rec.divs.push_back(SolveDivDev{row.pos_r, row.col_r, row.q_in_b});
+        }
+        if (s.kind != pmsolve::KIND_ISZERO) continue;
+        d.bits = (uint32_t)rec.pairs.size();
+        SolvePairDev<P> pr;
+        memset((void *)&pr, 0, sizeof pr);
+        const pmsolve::PairRows &rows = plan.pairs[s.cols_off];
+        pr.pos_m = rows.pos_m; pr.pos_c = rows.pos_c; pr.row1 = rows.row1; pr.col_m = rows.col_m; pr.m_in_b = rows.m_in_b; pr.b_in_b = rows.b_in_b;
+        pr.negated = rows.negated;
+        rec.pairs.push_back(pr);
+    }
+    return rec;
+}
+
+// any of the three markers (divrem.cuh: marker_byte)
+template <class P>
+PM_HD bool is_marker(const Fp<P> &v) {
+    return marker_byte<P>(v) != 0;
+}
+
+PM_HD const pmsolve::Csr &matrix_of(uint32_t kind, const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsolve::Csr &Cm) {
+    return kind == pmsolve::KIND_A ? A : kind == pmsolve::KIND_B ? B : Cm;
+}
+
+// KIND_BITS_x -> KIND_x
+PM_HD uint32_t matrix_kind(uint32_t kind) { return kind >= pmsolve::KIND_BITS_C ? kind - pmsolve::KIND_BITS_C : kind; }
+
+// Inverse t of a plan's count + 2 n_pairs: 1 / coefficient of step t's unknown (a division row: 1 / cq), and for t >= count 1 / cm
+// and 1 / cb of an is-zero pair's opener; an indicator step needs none and its record is left alone.
+template <class P>
+PM_HD void solve_inverse(const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsolve::Csr &Cm, SolveStepDev<P> *steps, uint64_t count, SolvePairDev<P> *pairs,
+                         const SolveDivDev *divs, uint64_t t) {
+    if (t < count && steps[t].kind == pmsolve::KIND_INDICATOR) return;      // no inverse: the record stays as the host wrote it
+    const Fp<P> *at;
+    Fp<P> *out;
+    if (t < count) {                 // an is-zero step's own entry is the flag's, in the closer's A or B; a division step's the quotient's
+        const uint32_t kind = steps[t].kind;
+        const pmsolve::Csr &M = kind == pmsolve::KIND_ISZERO ? (pairs[steps[t].bits].b_in_b ? B : A)
+                              : kind == pmsolve::KIND_DIVREM ? (divs[steps[t].bits].q_in_b ? B : A) : matrix_of(matrix_kind(kind), A, B, Cm);
+        at = (const Fp<P> *)(M.val + 4 * steps[t].pos);
+        out = &steps[t].inv;
+    } else {
+        SolvePairDev<P> &pr = pairs[(t - count) >> 1];
+        const bool multiplier = ((t - count) & 1) == 0;
+        at = (const Fp<P> *)(multiplier ? (pr.m_in_b ? B : A).val + 4 * pr.pos_m : Cm.val + 4 * pr.pos_c);
+        out = multiplier ? &pr.inv_cm : &pr.inv_cb;
+    }
+    const Fp<P> coef = *at;
+    *out = coef.eq(Fp<P>::one()) ? coef : inverse<P>(coef);
+}
+
+// (M z)_r without entry `skip` (SOLVE_NONE: the whole row)
+template <class P>
+PM_HD Fp<P> row_dot_skip(const pmsolve::Csr &M, const Fp<P> *z, uint64_t r, uint64_t skip) {
+    Fp<P> acc = Fp<P>::zero();
+    for (uint64_t k = M.rowptr[r]; k < M.rowptr[r + 1]; ++k) {
+        if (k == skip) continue;
+        acc = add<P>(acc, mul<P>(*(const Fp<P> *)(M.val + 4 * k), z[M.col[k]]));
+    }
+    return acc;
+}
+
+// (M z)_r without the entries whose value is still the marker.  In a decomposition row those are exactly its k unknowns: every other
+// column the row names was given (never a marker) or was stored by an earlier level or an earlier step of this lane (a field
+// element, zero where that step was stuck).
+template <class P>
+PM_HD Fp<P> row_dot_unmarked(const pmsolve::Csr &M, const Fp<P> *z, uint64_t r) {
+    Fp<P> acc = Fp<P>::zero();
+    for (uint64_t k = M.rowptr[r]; k < M.rowptr[r + 1]; ++k) {
+        const Fp<P> v = z[M.col[k]];
+        if (is_marker<P>(v)) continue;
+        acc = add<P>(acc, mul<P>(*(const Fp<P> *)(M.val + 4 * k), v));
+    }
+    return acc;
+}
+
+// one step on one assignment (z = its x || w row): the partial dot products of the row, the unknown's entry left out, then
+//   kind C: z_u = (Az Bz - C_rest) / coef      kind A: z_u = (Cz / Bz - A_rest) / coef      kind B: z_u = (Cz / Az - B_rest) / coef
+template <class P, bool DIV, class Sink>
+PM_HD void solve_step(const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsolve::Csr &Cm, const SolveStepDev<P> &s, Fp<P> *z, const Sink &stuck) {
+    const uint64_t r = s.row;
+    const uint32_t kind = s.kind;
+    const Fp<P> az = row_dot_skip<P>(A, z, r, kind == pmsolve::KIND_A ? s.pos : SOLVE_NONE);
+    const Fp<P> bz = row_dot_skip<P>(B, z, r, kind == pmsolve::KIND_B ? s.pos : SOLVE_NONE);
+    const Fp<P> cz = row_dot_skip<P>(Cm, z, r, kind == pmsolve::KIND_C ? s.pos : SOLVE_NONE);
+    Fp<P> v;
+    if (!DIV || kind == pmsolve::KIND_C) {
+        v = sub<P>(mul<P>(az, bz), cz);
+    } else {
+        const Fp<P> den = kind == pmsolve::KIND_A ? bz : az, rest = kind == pmsolve::KIND_A ? az : bz;
+        if (den.is_zero()) {        // 0 / 0 included: the value is then undetermined
+            stuck(s);
+            z[s.col] = Fp<P>::zero();
+            return;
+        }
+        v = sub<P>(mul<P>(cz, inverse<P>(den)), rest);
+    }
+    z[s.col] = mul<P>(v, s.inv);
+}
+
+// one decomposition on one assignment: t = (the unknown part of the row) / c with the k unknown entries left out of the dot
+// product -- their columns still hold the marker, and row_dot_unmarked passes over markers -- then z_{cols[i]} = bit i of the
+// canonical integer of t, as field 0 or field 1.  t >= 2^k has no such form: stuck, like a zero divisor, with zero in all k columns.
+template <class P, bool DIV, class Sink>
+PM_HD void solve_bits(const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsolve::Csr &Cm, const SolveStepDev<P> &s, const uint32_t *__restrict__ bit_cols, Fp<P> *z,
+                      const Sink &stuck) {
+    const uint64_t r = s.row;
+    const uint32_t kind = matrix_kind(s.kind), k = s.bits;
+    const uint32_t *cols = bit_cols + s.col;
+    const Fp<P> az = kind == pmsolve::KIND_A ? row_dot_unmarked<P>(A, z, r) : row_dot_skip<P>(A, z, r, SOLVE_NONE);
+    const Fp<P> bz = kind == pmsolve::KIND_B ? row_dot_unmarked<P>(B, z, r) : row_dot_skip<P>(B, z, r, SOLVE_NONE);
+    const Fp<P> cz = kind == pmsolve::KIND_C ? row_dot_unmarked<P>(Cm, z, r) : row_dot_skip<P>(Cm, z, r, SOLVE_NONE);
+    Fp<P> v = Fp<P>::zero();
+    bool ok = true;
+    if (!DIV || kind == pmsolve::KIND_C) {
+        v = sub<P>(mul<P>(az, bz), cz);
+    } else {
+        const Fp<P> den = kind == pmsolve::KIND_A ? bz : az, rest = kind == pmsolve::KIND_A ? az : bz;
+        ok = !den.is_zero();
+        if (ok) v = sub<P>(mul<P>(cz, inverse<P>(den)), rest);
+    }
+    Fp<P> t = Fp<P>::zero();
+    if (ok) {
+        t = from_mont<P>(mul<P>(v, s.inv));
+        uint32_t high = 0;           // the bits of t from k upwards; k <= bitlength(r) - 1 < 32 N
+#pragma unroll
+        for (int i = 0; i < P::N; ++i) high |= 32u * i >= k ? t.l[i] : 32u * (i + 1) > k ? t.l[i] >> (k - 32u * i) : 0u;
+        ok = high == 0;
+    }
+    if (!ok) {
+        stuck(s);
+        t = Fp<P>::zero();
+    }
+    for (uint32_t i = 0; i < k; i += 32) {
+        uint32_t word = 0;
+#pragma unroll
+        for (int w = 0; w < P::N; ++w) word = i == 32u * w ? t.l[w] : word;   // t.l[i / 32] without indexing registers
+        for (uint32_t j = i; j < k && j < i + 32; ++j) {
+            const uint32_t mask = 0u - ((word >> (j - i)) & 1u);              // one & mask: field 1 or field 0, no table to select from
+            Fp<P> bit;
+#pragma unroll
+            for (int w = 0; w < P::N; ++w) bit.l[w] = P::ONE[w] & mask;
+            z[cols[j]] = bit;
+        }
+    }
+}
+
+// one is-zero pair on one assignment.  d1 = K1 z is the tested value up to sign, d2 = K2 z = +-d1 by the plan, so ONE inversion
+// serves both rows; inverse<P>(0) is 0 (a power of zero), which is the convention for the free multiplier, so m needs no branch and
+// only b is a select:
+//   d1 != 0:  b = ((C_r2 z) / d2 - rest_r2) / kb,   m = ((C_r1 z, with b) / d1) / cm
+//   d1 == 0:  b = -C_r1_rest / cb,                  m = 0
+// Both columns still hold the marker; the dot products leave their entries out by position.
+template <class P>
+PM_HD void solve_iszero(const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsolve::Csr &Cm, const SolveStepDev<P> &s, const SolvePairDev<P> &pr, Fp<P> *z) {
+    const uint64_t r1 = pr.row1, r2 = s.row;
+    const Fp<P> d1 = row_dot_skip<P>(pr.m_in_b ? A : B, z, r1, SOLVE_NONE);
+    const Fp<P> c1_rest = row_dot_skip<P>(Cm, z, r1, pr.pos_c);
+    const Fp<P> rest2 = row_dot_skip<P>(pr.b_in_b ? B : A, z, r2, s.pos);
+    const Fp<P> c2 = row_dot_skip<P>(Cm, z, r2, SOLVE_NONE);
+    const Fp<P> inv1 = inverse<P>(d1);
+    const Fp<P> inv2 = pr.negated ? neg<P>(inv1) : inv1;
+    const Fp<P> b_unequal = mul<P>(sub<P>(mul<P>(c2, inv2), rest2), s.inv);
+    const Fp<P> b_equal = mul<P>(neg<P>(c1_rest), pr.inv_cb);
+    const Fp<P> b = d1.is_zero() ? b_equal : b_unequal;
+    const Fp<P> c1 = add<P>(c1_rest, mul<P>(*(const Fp<P> *)(Cm.val + 4 * pr.pos_c), b));
+    z[s.col] = b;
+    z[pr.col_m] = mul<P>(mul<P>(c1, inv1), pr.inv_cm);
+}
+
+// one division row on one assignment: cq q (K z) = R - cq rem, so with d = K z and a = R / cq as canonical integers
+//   d != 0:  q = floor(a / d),  rem = a mod d      (euclid_divrem: Montgomery -> canonical, 256 / 256 bits, back)
+//   d == 0:  stuck at the row, zero in both columns
+// The partial dot products as the is-zero step forms them: K's whole row and C's without rem's entry; the quotient's side has no
+// other non-zero entry, so its partial dot product is zero and is not formed.  Both columns still hold their markers.
+template <class P, class Sink>
+PM_HD void solve_divrem(const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsolve::Csr &Cm, const SolveStepDev<P> &s, const SolveDivDev &dv, Fp<P> *z,
+                        const Sink &stuck) {
+    const uint64_t r = s.row;
+    const Fp<P> d = row_dot_skip<P>(dv.q_in_b ? A : B, z, r, SOLVE_NONE);
+    const Fp<P> a = mul<P>(row_dot_skip<P>(Cm, z, r, dv.pos_r), s.inv);
+    Fp<P> q = Fp<P>::zero(), rem = Fp<P>::zero();
+    if (!euclid_divrem<P>(a, d, &q, &rem)) stuck(s);
+    z[s.col] = q;
+    z[dv.col_r] = rem;
+}
+
+// one indicator row on one assignment: z_u = [K z == 0] as field one or field zero, whatever u's coefficient is.  K's whole row (the
+// indicator's side has no other non-zero entry and C_r none at all); the column still holds its marker.  No division, never stuck.
+template <class P>
+PM_HD void solve_indicator(const pmsolve::Csr &A, const pmsolve::Csr &B, const SolveStepDev<P> &s, Fp<P> *z) {
+    z[s.col] = indicator_of<P>(row_dot_skip<P>(s.bits ? A : B, z, s.row, SOLVE_NONE));
+}
+
+// One step of a chain, whatever its kind.  A range with an is-zero pair or a division row is a dividing one (the plan says so): the
+// DIV = false body has no such branches.  An indicator row does not divide and is a branch of both.
+template <class P, bool DIV, class Sink>
+PM_HD void solve_any(const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsolve::Csr &Cm, const SolveStepDev<P> &s, const uint32_t *__restrict__ bit_cols,
+                     const SolvePairDev<P> *__restrict__ pairs, const SolveDivDev *__restrict__ divs, Fp<P> *z, const Sink &stuck) {
+    if (s.kind == pmsolve::KIND_ISZERO) {
+        // DIV = false would pass over the pair and leave both markers in place: solve_plan refuses a plan that asks for that
+        if constexpr (DIV) solve_iszero<P>(A, B, Cm, s, pairs[s.bits], z);
+    } else if (s.kind == pmsolve::KIND_DIVREM) {
+        if constexpr (DIV) solve_divrem<P>(A, B, Cm, s, divs[s.bits], z, stuck);      // as above
+    } else if (s.kind == pmsolve::KIND_INDICATOR) {
+        solve_indicator<P>(A, B, s, z);
+    } else if (s.bits) solve_bits<P, DIV>(A, B, Cm, s, bit_cols, z, stuck);
+    else solve_step<P, DIV>(A, B, Cm, s, z, stuck);
+}
+
+}  // namespace pm

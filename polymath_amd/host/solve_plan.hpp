@@ -1,7 +1,7 @@
 // Witness solving, host side: the PLAN that completes a partial assignment by forward propagation through the rows of an R1CS
-// (DESIGN.md §4.10).  Header-only, no HIP: the library's driver (csrc/solve.hip) and six CPU programs (tests/native/
-// solve_plan_selftest.cpp, solve_bits_selftest.cpp, solve_iszero_selftest.cpp, solve_order_selftest.cpp, solve_divrem_selftest.cpp,
-// solve_indicator_selftest.cpp) include the same file.
+// (DESIGN.md §4.10).  Header-only, no HIP: the library's driver (csrc/solve.hip, through csrc/solve_steps.cuh) and six CPU programs
+// (tests/native/solve_plan_selftest.cpp, solve_bits_selftest.cpp, solve_iszero_selftest.cpp, solve_order_selftest.cpp,
+// solve_divrem_selftest.cpp, solve_indicator_selftest.cpp, through their rig tests/native/solve_selftest.hpp) include the same file.
 //
 // Input: the three matrices in CSR form with the first-entry rule already applied (a column occurs at most once per row and
 // matrix: the key's resident matrices are like that), m0 + mw columns and one byte per column, non-zero = unknown (1: unknown;
@@ -396,47 +396,42 @@ inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
     }
 }
 
-inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, const uint8_t *unknown, uint32_t wide_steps = WIDE_STEPS,
-                       const uint64_t *modulus = nullptr) {
+constexpr uint32_t KIND_OF[3] = {KIND_A, KIND_B, KIND_C};   // the ordinary kind of an unknown in matrix A, B, C
+
+// What both builders keep while they walk the rows -- the column state, the openers, the plan under construction, the row under the
+// cursor -- and every rule they share, each stated once: how a row is read, which shape opens a pair, and how each kind of step is
+// made.  A step's constructor sets the levels of the columns it determines and max_level, and calls `known` (its last argument) with
+// each of those columns: in matrix order nobody listens, in the scheduler the rows parked on the column return to the heap.
+struct Planner {
+    static constexpr uint32_t UNSOLVED = ~(uint32_t)0, NONE = ~(uint32_t)0;
+    const Csr *m;
+    const uint8_t *unknown;
+    const uint64_t *modulus;
     Plan p;
-    const uint64_t ncols = m0 + mw;
-    constexpr uint32_t UNSOLVED = ~(uint32_t)0, NONE = ~(uint32_t)0;
-    if (ncols && unknown[0]) {
-        p.error = ERR_COLUMN_ZERO;
-        p.message = "column 0 (the constant one) is marked unknown";
-        return p;
-    }
-    std::vector<uint32_t> level(ncols);
-    for (uint64_t j = 0; j < ncols; ++j) level[j] = unknown[j] ? UNSOLVED : 0;
-    std::vector<uint32_t> bool_row(modulus ? ncols : 0, NONE);   // boolean-pending: the column is UNSOLVED and this is its booleanity row
-    static const char *const NAME[3] = {"A", "B", "C"};
-    static const uint32_t KIND_OF[3] = {KIND_A, KIND_B, KIND_C};
-    std::vector<uint32_t> pair_of(modulus ? ncols : 0, NONE);    // pair-pending: the column is UNSOLVED and this is its entry of `openers`
+    std::vector<uint32_t> level;      // per column: 0 given, UNSOLVED, or the level of the step that determines it
+    std::vector<uint32_t> bool_row;   // boolean-pending: the column is UNSOLVED and this is its booleanity row
+    std::vector<uint32_t> pair_of;    // pair-pending: the column is UNSOLVED and this is its entry of `openers`
     std::vector<Opener> openers;
-    size_t open = 0;                                             // openers not closed yet
-    std::vector<std::pair<uint32_t, uint64_t>> side1, side2;
-    const auto two_unknowns = [](uint64_t r, uint32_t u, uint32_t j) {
-        return "row " + std::to_string(r) + ": two or more unknowns (columns " + std::to_string(u) + " and " + std::to_string(j) + ")";
-    };
-    const auto refuse_pair = [&](const Opener &o, const std::string &why) {
-        p.error = ERR_MANY_UNKNOWNS;
-        p.error_row = o.row;
-        p.error_col = o.col_b;
-        p.message = two_unknowns(o.row, o.col_m, o.col_b) + ", and no is-zero pair: " + why;
-        p.steps.clear();
-        p.bit_cols.clear();
-        p.pairs.clear();
-        p.divs.clear();
-    };
+    size_t open = 0;                  // openers not closed yet
     uint32_t max_level = 0;
-    std::vector<Unknown> occ;
-    std::vector<uint32_t> order;
-    for (uint64_t r = 0; r < nr; ++r) {
-        uint32_t reads = 0, nz[3] = {0, 0, 0};
+    // the row under the cursor (read_row)
+    std::vector<Unknown> occ;         // its unknown entries, A then B then C, in stored order
+    uint32_t reads = 0, nz[3] = {0, 0, 0};   // the largest level among the columns it reads; its non-zero entries per matrix
+    std::vector<uint32_t> order;      // scratch: decomposition_order
+    std::vector<std::pair<uint32_t, uint64_t>> side1, side2;   // scratch: compare_known_sides
+
+    Planner(const Csr *matrices, uint64_t ncols, const uint8_t *pattern, const uint64_t *mod)
+        : m(matrices), unknown(pattern), modulus(mod), level(ncols), bool_row(mod ? ncols : 0, NONE), pair_of(mod ? ncols : 0, NONE) {
+        for (uint64_t j = 0; j < ncols; ++j) level[j] = unknown[j] ? UNSOLVED : 0;
+    }
+
+    // occ, nz and reads of row r.  whole = false stops at the second unknown entry (nz and reads are then incomplete)
+    void read_row(uint64_t r, bool whole) {
+        reads = 0;
+        nz[0] = nz[1] = nz[2] = 0;
         occ.clear();
-        // without the modulus the second unknown entry decides the error, as it always did; with it the whole row is read
-        for (int k = 0; k < 3 && (modulus || occ.size() < 2); ++k) {
-            for (uint64_t e = m[k].rowptr[r]; e < m[k].rowptr[r + 1] && (modulus || occ.size() < 2); ++e) {
+        for (int k = 0; k < 3 && (whole || occ.size() < 2); ++k) {
+            for (uint64_t e = m[k].rowptr[r]; e < m[k].rowptr[r + 1] && (whole || occ.size() < 2); ++e) {
                 if (coef_is_zero(m[k].val + 4 * e)) continue;
                 ++nz[k];
                 const uint32_t j = m[k].col[e];
@@ -447,12 +442,125 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
                 occ.push_back(Unknown{(uint32_t)k, j, e});
             }
         }
+    }
+    // the pending opener that the row's first pair-pending unknown belongs to
+    const Opener *pending_opener() const {
+        for (const Unknown &e : occ)
+            if (pair_of[e.col] != NONE) return &openers[pair_of[e.col]];
+        return nullptr;
+    }
+    // an is-zero opener: two unknowns, the multiplier alone on one of A, B, the other of the two known and not zero, the flag in C
+    bool opener_shape() const {
+        return occ.size() == 2 && occ[0].col != occ[1].col && occ[0].matrix < 2 && occ[1].matrix == 2 && nz[occ[0].matrix] == 1 && nz[1 - occ[0].matrix] >= 1;
+    }
+    void register_opener(uint32_t r) {
+        pair_of[occ[0].col] = pair_of[occ[1].col] = (uint32_t)openers.size();
+        openers.push_back(Opener{occ[0].pos, occ[1].pos, r, occ[0].col, occ[1].col, reads, (uint8_t)occ[0].matrix});
+        ++open;
+    }
+    // the opener is none after all, or its pair is closed: its columns are pair-pending no longer
+    void drop_opener(const Opener &o) {
+        pair_of[o.col_m] = pair_of[o.col_b] = NONE;
+        --open;
+    }
+    void solved(uint32_t col, uint32_t lv) {
+        level[col] = lv;
+        if (lv > max_level) max_level = lv;
+    }
+
+    // the row's single unknown e, named once: an ordinary step, or -- byte 3 on it and the indicator shape -- the indicator step
+    template <class Known>
+    void single_step(const Unknown &e, uint32_t r, const Known &known) {
+        const uint32_t lv = reads + 1;
+        p.steps.push_back(modulus && indicator_row(e, nz, unknown) ? indicator_step(e, r, lv) : Step{e.pos, r, e.col, KIND_OF[e.matrix], lv});
+        solved(e.col, lv);
+        known(e.col);
+    }
+    // a decomposition whose exponent order is `order` (decomposition_order)
+    template <class Known>
+    void bits_step(uint32_t r, const Known &known) {
+        const uint32_t lv = reads + 1;
+        const Unknown &c = occ[order[0]];
+        Step s{c.pos, r, c.col, KIND_BITS_C + KIND_OF[c.matrix], lv};
+        s.bits = (uint32_t)order.size();
+        s.cols_off = (uint32_t)p.bit_cols.size();
+        for (uint32_t i : order) {
+            p.bit_cols.push_back(occ[i].col);
+            solved(occ[i].col, lv);
+        }
+        p.steps.push_back(s);
+        for (uint32_t i : order) known(occ[i].col);
+    }
+    // a division row with quotient q and remainder rem (division_row)
+    template <class Known>
+    void division_step(const Unknown &q, const Unknown &rem, uint32_t r, const Known &known) {
+        const uint32_t lv = reads + 1;
+        Step s{q.pos, r, q.col, KIND_DIVREM, lv};
+        s.cols_off = (uint32_t)p.divs.size();
+        p.divs.push_back(DivRow{rem.pos, rem.col, (uint8_t)(q.matrix == 1)});
+        p.steps.push_back(s);
+        solved(q.col, lv);
+        solved(rem.col, lv);
+        known(q.col);
+        known(rem.col);
+    }
+    // row r closes the pair of opener o: `flag` is the flag's entry in it, sign = compare_known_sides (0: K2 = K1, 1: K2 = -K1)
+    template <class Known>
+    void iszero_step(const Opener &o, const Unknown &flag, uint32_t r, int sign, const Known &known) {
+        const uint32_t lv = (reads > o.reads ? reads : o.reads) + 1, col_m = o.col_m, col_b = o.col_b;
+        Step s{flag.pos, r, col_b, KIND_ISZERO, lv};
+        s.cols_off = (uint32_t)p.pairs.size();
+        p.pairs.push_back(PairRows{o.pos_m, o.pos_c, o.row, col_m, o.m_in_b, (uint8_t)(flag.matrix == 1), (uint8_t)sign});
+        p.steps.push_back(s);
+        drop_opener(o);
+        solved(col_m, lv);
+        solved(col_b, lv);
+        known(col_m);
+        known(col_b);
+    }
+    // a row is refused where it stands: the steps of the rows before it stay in the plan, as they always did
+    void refuse_row(int code, uint64_t row, uint64_t col, const std::string &message) {
+        p.error = code;
+        p.error_row = row;
+        p.error_col = col;
+        p.message = message;
+    }
+    // the system is refused: no part of a plan is left behind
+    void fail(int code, uint64_t row, uint64_t col, const std::string &message) {
+        refuse_row(code, row, col, message);
+        p.steps.clear();
+        p.bit_cols.clear();
+        p.pairs.clear();
+        p.divs.clear();
+    }
+};
+
+inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, const uint8_t *unknown, uint32_t wide_steps = WIDE_STEPS,
+                       const uint64_t *modulus = nullptr) {
+    const uint64_t ncols = m0 + mw;
+    constexpr uint32_t UNSOLVED = Planner::UNSOLVED, NONE = Planner::NONE;
+    if (ncols && unknown[0]) {
+        Plan p;
+        p.error = ERR_COLUMN_ZERO;
+        p.message = "column 0 (the constant one) is marked unknown";
+        return p;
+    }
+    Planner st(m, ncols, unknown, modulus);
+    const std::vector<Unknown> &occ = st.occ;
+    const auto nobody = [](uint32_t) {};   // a column became known: in matrix order nobody waits for one
+    static const char *const NAME[3] = {"A", "B", "C"};
+    const auto two_unknowns = [](uint64_t r, uint32_t u, uint32_t j) {
+        return "row " + std::to_string(r) + ": two or more unknowns (columns " + std::to_string(u) + " and " + std::to_string(j) + ")";
+    };
+    const auto refuse_pair = [&](const Opener &o, const std::string &why) {
+        st.fail(ERR_MANY_UNKNOWNS, o.row, o.col_b, two_unknowns(o.row, o.col_m, o.col_b) + ", and no is-zero pair: " + why);
+    };
+    for (uint64_t r = 0; r < nr; ++r) {
+        // without the modulus the second unknown entry decides the error, as it always did; with it the whole row is read
+        st.read_row(r, modulus != nullptr);
         if (occ.empty()) continue;
-        if (open) {   // the first row that names a pair-pending column closes that pair, or the pair is refused
-            const Opener *o = nullptr;
-            for (const Unknown &e : occ)
-                if (!o && pair_of[e.col] != NONE) o = &openers[pair_of[e.col]];
-            if (o) {
+        if (st.open) {   // the first row that names a pair-pending column closes that pair, or the pair is refused
+            if (const Opener *o = st.pending_opener()) {
                 const std::string here = "row " + std::to_string(r);
                 const Unknown *flag = nullptr, *multiplier = nullptr, *other = nullptr;
                 bool in_c = false, twice = false, same_matrix = false;
@@ -471,31 +579,19 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
                 else if (twice) why = here + flag_name + (same_matrix ? std::string(" twice in ") + NAME[flag->matrix] : std::string(" in A and in B"));
                 int sign = 0;
                 if (why.empty()) {
-                    sign = compare_known_sides(m, o->m_in_b ? 0 : 1, o->row, flag->matrix == 0 ? 1 : 0, r, modulus, side1, side2);
+                    sign = compare_known_sides(m, o->m_in_b ? 0 : 1, o->row, flag->matrix == 0 ? 1 : 0, r, modulus, st.side1, st.side2);
                     if (sign < 0) why = here + ": its known side is neither the opener's nor minus the opener's";
                 }
                 if (!why.empty()) {
                     refuse_pair(*o, why);
-                    return p;
+                    return std::move(st.p);
                 }
-                const uint32_t lv2 = (reads > o->reads ? reads : o->reads) + 1;
-                Step s{flag->pos, (uint32_t)r, o->col_b, KIND_ISZERO, lv2};
-                s.cols_off = (uint32_t)p.pairs.size();
-                p.pairs.push_back(PairRows{o->pos_m, o->pos_c, o->row, o->col_m, o->m_in_b, (uint8_t)(flag->matrix == 1), (uint8_t)sign});
-                level[o->col_m] = level[o->col_b] = lv2;
-                pair_of[o->col_m] = pair_of[o->col_b] = NONE;
-                --open;
-                if (lv2 > max_level) max_level = lv2;
-                p.steps.push_back(s);
+                st.iszero_step(*o, *flag, (uint32_t)r, sign, nobody);
                 continue;
             }
         }
-        const uint32_t lv = reads + 1;
         if (occ.size() == 1) {
-            const uint32_t u = occ[0].col;
-            level[u] = lv;
-            if (lv > max_level) max_level = lv;
-            p.steps.push_back(modulus && indicator_row(occ[0], nz, unknown) ? indicator_step(occ[0], (uint32_t)r, lv) : Step{occ[0].pos, (uint32_t)r, u, KIND_OF[occ[0].matrix], lv});
+            st.single_step(occ[0], (uint32_t)r, nobody);
             continue;
         }
         const uint32_t u = occ[0].col;
@@ -509,122 +605,85 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
                     j = o.col;
                 }
             if (one_column) {
-                if (is_booleanity(m, r, occ, nz, modulus)) {
-                    if (bool_row[u] == NONE) bool_row[u] = (uint32_t)r;
+                if (is_booleanity(m, r, occ, st.nz, modulus)) {
+                    if (st.bool_row[u] == NONE) st.bool_row[u] = (uint32_t)r;
                     continue;
                 }
-            } else if (!(why = decomposition_order(m, occ, bool_row, modulus, order))) {
-                const Unknown &c = occ[order[0]];
-                Step s{c.pos, (uint32_t)r, c.col, KIND_BITS_C + KIND_OF[c.matrix], lv};
-                s.bits = (uint32_t)order.size();
-                s.cols_off = (uint32_t)p.bit_cols.size();
-                for (uint32_t i : order) {
-                    p.bit_cols.push_back(occ[i].col);
-                    level[occ[i].col] = lv;
-                }
-                if (lv > max_level) max_level = lv;
-                p.steps.push_back(s);
+            } else if (!(why = decomposition_order(m, occ, st.bool_row, modulus, st.order))) {
+                st.bits_step((uint32_t)r, nobody);
                 continue;
             }
             // a division row: the shape below with the quotient's marker on the lone entry.  It is a step at once, or refused at once
             int div = 0;
             if (!one_column) {
                 Unknown q, rem;
-                div = division_row(m, occ, nz, unknown, modulus, q, rem, div_why);
+                div = division_row(m, occ, st.nz, unknown, modulus, q, rem, div_why);
                 if (div > 0) {
-                    Step s{q.pos, (uint32_t)r, q.col, KIND_DIVREM, lv};
-                    s.cols_off = (uint32_t)p.divs.size();
-                    p.divs.push_back(DivRow{rem.pos, rem.col, (uint8_t)(q.matrix == 1)});
-                    level[q.col] = level[rem.col] = lv;
-                    if (lv > max_level) max_level = lv;
-                    p.steps.push_back(s);
+                    st.division_step(q, rem, (uint32_t)r, nobody);
                     continue;
                 }
                 if (div < 0 && div_why[0] == 'c') why = nullptr;   // cr != -cq: the opener's shape, whose message had no second part
             }
-            // an is-zero opener: the multiplier alone on one of A, B, the other of the two known and not zero, the flag in C
-            if (div == 0 && !one_column && occ.size() == 2 && occ[0].matrix < 2 && occ[1].matrix == 2 && nz[occ[0].matrix] == 1 && nz[1 - occ[0].matrix] >= 1) {
-                pair_of[u] = pair_of[j] = (uint32_t)openers.size();
-                openers.push_back(Opener{occ[0].pos, occ[1].pos, (uint32_t)r, u, j, reads, (uint8_t)occ[0].matrix});
-                ++open;
+            if (div == 0 && st.opener_shape()) {
+                st.register_opener((uint32_t)r);
                 continue;
             }
         }
-        p.error_row = r;
-        p.error_col = j;
         if (j != u) {
-            p.error = ERR_MANY_UNKNOWNS;
-            p.message = two_unknowns(r, u, j);
-            if (why) p.message += std::string(", and no bit decomposition: ") + why;
-            if (div_why) p.message += std::string(", and no division row: ") + div_why;
+            std::string message = two_unknowns(r, u, j);
+            if (why) message += std::string(", and no bit decomposition: ") + why;
+            if (div_why) message += std::string(", and no division row: ") + div_why;
+            st.refuse_row(ERR_MANY_UNKNOWNS, r, j, message);
         } else {   // the same unknown again: in another matrix, or a second time in this one
-            p.error = ERR_TWO_MATRICES;
-            p.message = "row " + std::to_string(r) + ": unknown column " + std::to_string(j) + " occurs in " + NAME[occ[0].matrix] + " and in " + NAME[occ[1].matrix];
+            st.refuse_row(ERR_TWO_MATRICES, r, j,
+                          "row " + std::to_string(r) + ": unknown column " + std::to_string(j) + " occurs in " + NAME[occ[0].matrix] + " and in " + NAME[occ[1].matrix]);
         }
-        return p;
+        return std::move(st.p);
     }
-    if (open) {   // openers are pushed in row order: the first one still pending has the smallest row
-        for (size_t i = 0; i < openers.size(); ++i)
-            if (pair_of[openers[i].col_m] == i) {
-                const Opener &o = openers[i];
-                refuse_pair(o, "no later row closes it");
-                return p;
+    if (st.open) {   // openers are pushed in row order: the first one still pending has the smallest row
+        for (size_t i = 0; i < st.openers.size(); ++i)
+            if (st.pair_of[st.openers[i].col_m] == i) {
+                refuse_pair(st.openers[i], "no later row closes it");
+                return std::move(st.p);
             }
     }
     if (modulus) {
         uint64_t pending = ncols;
         for (uint64_t j = 0; j < ncols; ++j)
-            if (level[j] == UNSOLVED && bool_row[j] != NONE && (pending == ncols || bool_row[j] < bool_row[pending])) pending = j;
+            if (st.level[j] == UNSOLVED && st.bool_row[j] != NONE && (pending == ncols || st.bool_row[j] < st.bool_row[pending])) pending = j;
         if (pending != ncols) {
-            p.error = ERR_TWO_MATRICES;
-            p.error_row = bool_row[pending];
-            p.error_col = pending;
-            p.message = "row " + std::to_string(p.error_row) + ": unknown column " + std::to_string(pending) +
-                        " occurs in A and in B (a booleanity row, and no later row determines the column)";
-            p.steps.clear();
-            p.bit_cols.clear();
-            p.pairs.clear();
-            p.divs.clear();
-            return p;
+            const uint64_t row = st.bool_row[pending];
+            st.fail(ERR_TWO_MATRICES, row, pending,
+                    "row " + std::to_string(row) + ": unknown column " + std::to_string(pending) +
+                        " occurs in A and in B (a booleanity row, and no later row determines the column)");
+            return std::move(st.p);
         }
     }
     for (uint64_t j = 0; j < ncols; ++j)
-        if (level[j] == UNSOLVED) {
-            p.error = ERR_UNDETERMINED;
-            p.error_col = j;
-            p.message = "column " + std::to_string(j) + " is marked unknown and no row determines it";
-            p.steps.clear();
-            p.bit_cols.clear();
-            p.pairs.clear();
-            p.divs.clear();
-            return p;
+        if (st.level[j] == UNSOLVED) {
+            st.fail(ERR_UNDETERMINED, 0, j, "column " + std::to_string(j) + " is marked unknown and no row determines it");
+            return std::move(st.p);
         }
-    finish_plan(p, max_level, wide_steps);
-    return p;
+    finish_plan(st.p, st.max_level, wide_steps);
+    return std::move(st.p);
 }
 
-// The waiting-row scheduler of build_plan_any_order: the rules of build_plan on the rows in DEPENDENCY order.  A min-heap of rows to
-// examine (at first every row); a row that cannot act yet is parked on its unknown columns and returns to the heap when one of them
-// becomes known, becomes boolean-pending or is released by its opener.  -> false and `why` where no order solves the system.
-// p.steps come out in order of discovery, with their levels; max_level is set.
-inline bool schedule_any_order(const Csr m[3], uint64_t nr, uint64_t ncols, const uint8_t *unknown, const uint64_t *modulus, Plan &p, uint32_t &max_level,
-                               std::string &why) {
-    constexpr uint32_t UNSOLVED = ~(uint32_t)0, NONE = ~(uint32_t)0;
-    static const uint32_t KIND_OF[3] = {KIND_A, KIND_B, KIND_C};
+// The waiting-row scheduler of build_plan_any_order: the rules of build_plan (Planner) on the rows in DEPENDENCY order.  A min-heap of
+// rows to examine (at first every row); a row that cannot act yet is parked on its unknown columns and returns to the heap when one of
+// them becomes known, becomes boolean-pending or is released by its opener.  -> false and `why` where no order solves the system.
+// st.p.steps come out in order of discovery, with their levels; st.max_level is set.
+inline bool schedule_any_order(Planner &st, uint64_t nr, uint64_t ncols, std::string &why) {
+    constexpr uint32_t UNSOLVED = Planner::UNSOLVED, NONE = Planner::NONE;
     enum : uint8_t { PARKED = 0, QUEUED = 1, DONE = 2 };
-    std::vector<uint32_t> level(ncols), bool_row(ncols, NONE), pair_of(ncols, NONE), park_head(ncols, NONE);
-    for (uint64_t j = 0; j < ncols; ++j) level[j] = unknown[j] ? UNSOLVED : 0;
+    const Csr *m = st.m;
+    const uint64_t *modulus = st.modulus;
+    const std::vector<Unknown> &occ = st.occ;
+    std::vector<uint32_t> park_head(ncols, NONE);
     std::vector<std::pair<uint32_t, uint32_t>> parked;   // (row, next node of the same column)
     std::vector<uint8_t> state(nr, QUEUED);
     std::vector<uint32_t> rows(nr);
     for (uint64_t r = 0; r < nr; ++r) rows[r] = (uint32_t)r;   // ascending: a min-heap as it stands
     std::priority_queue<uint32_t, std::vector<uint32_t>, std::greater<uint32_t>> heap(std::greater<uint32_t>(), std::move(rows));
-    std::vector<Opener> openers;
-    size_t open = 0;
-    std::vector<std::pair<uint32_t, uint64_t>> side1, side2;
-    std::vector<Unknown> occ;
-    std::vector<uint32_t> order;
-    max_level = 0;
     const auto push = [&](uint32_t r) {
         if (state[r] != PARKED) return;
         state[r] = QUEUED;
@@ -641,27 +700,21 @@ inline bool schedule_any_order(const Csr m[3], uint64_t nr, uint64_t ncols, cons
             park_head[e.col] = (uint32_t)parked.size() - 1;
         }
     };
-    const auto solved = [&](uint32_t col, uint32_t lv) {
-        level[col] = lv;
-        if (lv > max_level) max_level = lv;
-        wake(col);
+    // the opener was none: its columns are free again, and it is examined again with the rows that wait on them.  Both columns are
+    // woken here, also the one that the releasing row goes on to solve (its step wakes that column again and finds nobody parked):
+    // every push happens before the next pop of the heap, so which of the two wakes a row makes no difference
+    const auto release = [&](const Opener &held) {
+        const uint32_t col_m = held.col_m, col_b = held.col_b, opener_row = held.row;
+        st.drop_opener(held);
+        state[opener_row] = PARKED;
+        push(opener_row);
+        wake(col_m);
+        wake(col_b);
     };
     while (!heap.empty()) {
         const uint32_t r = heap.top();
         heap.pop();
-        uint32_t reads = 0, nz[3] = {0, 0, 0};
-        occ.clear();
-        for (int k = 0; k < 3; ++k)
-            for (uint64_t e = m[k].rowptr[r]; e < m[k].rowptr[r + 1]; ++e) {
-                if (coef_is_zero(m[k].val + 4 * e)) continue;
-                ++nz[k];
-                const uint32_t j = m[k].col[e];
-                if (level[j] != UNSOLVED) {
-                    if (level[j] > reads) reads = level[j];
-                    continue;
-                }
-                occ.push_back(Unknown{(uint32_t)k, j, e});
-            }
+        st.read_row(r, true);
         state[r] = DONE;
         if (occ.empty()) continue;   // a check row
         const uint32_t u = occ[0].col;
@@ -669,75 +722,42 @@ inline bool schedule_any_order(const Csr m[3], uint64_t nr, uint64_t ncols, cons
         for (const Unknown &e : occ) one_column = one_column && e.col == u;
         Unknown q, rem;
         const char *div_why = nullptr;
-        const int div = one_column ? 0 : division_row(m, occ, nz, unknown, modulus, q, rem, div_why);
+        const int div = one_column ? 0 : division_row(m, occ, st.nz, st.unknown, modulus, q, rem, div_why);
         if (div > 0) {
             // a division row whose only unknowns are q and rem: a step at once.  It waits for no closer, so an opener registered over
             // one of its columns (the row rem * 1 = y has that shape) was none: it is released and examined again.  A candidate that
             // misses a condition waits like any other row (below)
-            for (const uint32_t col : {q.col, rem.col}) {
-                if (pair_of[col] == NONE) continue;
-                const Opener &held = openers[pair_of[col]];
-                const uint32_t col_m = held.col_m, col_b = held.col_b, opener_row = held.row;
-                pair_of[col_m] = pair_of[col_b] = NONE;
-                --open;
-                state[opener_row] = PARKED;
-                push(opener_row);
-                wake(col_m);
-                wake(col_b);
-            }
-            const uint32_t lv = reads + 1;
-            Step s{q.pos, r, q.col, KIND_DIVREM, lv};
-            s.cols_off = (uint32_t)p.divs.size();
-            p.divs.push_back(DivRow{rem.pos, rem.col, (uint8_t)(q.matrix == 1)});
-            p.steps.push_back(s);
-            solved(q.col, lv);
-            solved(rem.col, lv);
+            for (const uint32_t col : {q.col, rem.col})
+                if (st.pair_of[col] != NONE) release(st.openers[st.pair_of[col]]);
+            st.division_step(q, rem, r, wake);
             continue;
         }
-        const Opener *o = nullptr;
-        for (const Unknown &e : occ)
-            if (!o && pair_of[e.col] != NONE) o = &openers[pair_of[e.col]];
+        const Opener *o = st.pending_opener();
         if (o && one_column && u == o->col_b) {   // the flag alone: the closer, or no order helps
-            const int sign = occ.size() == 1 && occ[0].matrix < 2 ? compare_known_sides(m, o->m_in_b ? 0 : 1, o->row, occ[0].matrix == 0 ? 1 : 0, r, modulus, side1, side2) : -1;
+            const int sign = occ.size() == 1 && occ[0].matrix < 2 ? compare_known_sides(m, o->m_in_b ? 0 : 1, o->row, occ[0].matrix == 0 ? 1 : 0, r, modulus, st.side1, st.side2) : -1;
             if (sign < 0) {
                 why = "row " + std::to_string(r) + " names only the flag (column " + std::to_string(u) + ") of the pair that row " + std::to_string(o->row) + " opens and does not close it";
                 return false;
             }
-            const uint32_t lv2 = (reads > o->reads ? reads : o->reads) + 1;
-            Step s{occ[0].pos, r, u, KIND_ISZERO, lv2};
-            s.cols_off = (uint32_t)p.pairs.size();
-            p.pairs.push_back(PairRows{o->pos_m, o->pos_c, o->row, o->col_m, o->m_in_b, (uint8_t)(occ[0].matrix == 1), (uint8_t)sign});
-            p.steps.push_back(s);
-            const uint32_t col_m = o->col_m;
-            pair_of[col_m] = pair_of[u] = NONE;
-            --open;
-            solved(col_m, lv2);
-            solved(u, lv2);
+            st.iszero_step(*o, occ[0], r, sign, wake);
             continue;
         }
         if (o && one_column && occ.size() == 1 && u == o->col_m) {
             // the multiplier alone and once: this row determines it as an ordinary step, so the opener was no opener.  It is released
             // and examined again (its other unknown is then an ordinary kind-C step of it)
-            const uint32_t col_b = o->col_b, opener_row = o->row;
-            pair_of[u] = pair_of[col_b] = NONE;
-            --open;
-            state[opener_row] = PARKED;
-            push(opener_row);
-            wake(col_b);
+            release(*o);
             o = nullptr;
         }
         if (o) {   // the multiplier beside something else, a second unknown, another opener over a pending column: after the closer
             park(r);
             continue;
         }
-        const uint32_t lv = reads + 1;
         if (one_column) {
             if (occ.size() == 1) {
-                p.steps.push_back(indicator_row(occ[0], nz, unknown) ? indicator_step(occ[0], r, lv) : Step{occ[0].pos, r, u, KIND_OF[occ[0].matrix], lv});
-                solved(u, lv);
-            } else if (is_booleanity(m, r, occ, nz, modulus)) {
-                if (bool_row[u] == NONE) {
-                    bool_row[u] = r;
+                st.single_step(occ[0], r, wake);
+            } else if (is_booleanity(m, r, occ, st.nz, modulus)) {
+                if (st.bool_row[u] == NONE) {
+                    st.bool_row[u] = r;
                     wake(u);
                 }
             } else {
@@ -745,32 +765,24 @@ inline bool schedule_any_order(const Csr m[3], uint64_t nr, uint64_t ncols, cons
             }
             continue;
         }
-        if (!decomposition_order(m, occ, bool_row, modulus, order)) {
-            const Unknown &c = occ[order[0]];
-            Step s{c.pos, r, c.col, KIND_BITS_C + KIND_OF[c.matrix], lv};
-            s.bits = (uint32_t)order.size();
-            s.cols_off = (uint32_t)p.bit_cols.size();
-            for (uint32_t i : order) p.bit_cols.push_back(occ[i].col);
-            p.steps.push_back(s);
-            for (uint32_t i = 0; i < s.bits; ++i) solved(p.bit_cols[s.cols_off + i], lv);
+        if (!decomposition_order(m, occ, st.bool_row, modulus, st.order)) {
+            st.bits_step(r, wake);
             continue;
         }
-        if (div == 0 && occ.size() == 2 && occ[0].matrix < 2 && occ[1].matrix == 2 && nz[occ[0].matrix] == 1 && nz[1 - occ[0].matrix] >= 1) {
-            pair_of[u] = pair_of[occ[1].col] = (uint32_t)openers.size();
-            openers.push_back(Opener{occ[0].pos, occ[1].pos, r, u, occ[1].col, reads, (uint8_t)occ[0].matrix});
-            ++open;
+        if (div == 0 && st.opener_shape()) {
+            st.register_opener(r);
             continue;
         }
         park(r);
     }
     for (uint64_t j = 0; j < ncols; ++j)
-        if (level[j] == UNSOLVED) {
+        if (st.level[j] == UNSOLVED) {
             why = "column " + std::to_string(j) + " stays unknown";
-            if (pair_of[j] != NONE) why += " (the pair that row " + std::to_string(openers[pair_of[j]].row) + " opens is never closed)";
-            else if (bool_row[j] != NONE) why += " (boolean by row " + std::to_string(bool_row[j]) + ", and nothing determines it)";
+            if (st.pair_of[j] != NONE) why += " (the pair that row " + std::to_string(st.openers[st.pair_of[j]].row) + " opens is never closed)";
+            else if (st.bool_row[j] != NONE) why += " (boolean by row " + std::to_string(st.bool_row[j]) + ", and nothing determines it)";
             return false;
         }
-    return open == 0;
+    return st.open == 0;
 }
 
 // build_plan for rows in ANY order.  The matrix order is tried first: a system that build_plan accepts gets build_plan's plan,
@@ -783,17 +795,17 @@ inline Plan build_plan_any_order(const Csr m[3], uint64_t nr, uint64_t m0, uint6
                                  const uint64_t *modulus = nullptr) {
     Plan first = build_plan(m, nr, m0, mw, unknown, wide_steps, modulus);
     if (first.error == OK || first.error == ERR_COLUMN_ZERO || !modulus) return first;
-    Plan p;
-    uint32_t max_level = 0;
+    Planner st(m, m0 + mw, unknown, modulus);
     std::string why;
-    if (!schedule_any_order(m, nr, m0 + mw, unknown, modulus, p, max_level, why)) {
+    if (!schedule_any_order(st, nr, m0 + mw, why)) {
         first.message += "; in any row order: " + why;
         return first;
     }
+    Plan &p = st.p;
     std::sort(p.steps.begin(), p.steps.end(), [](const Step &a, const Step &b) { return a.row < b.row; });   // a row gives at most one step
-    finish_plan(p, max_level, wide_steps);
+    finish_plan(p, st.max_level, wide_steps);
     p.reordered = true;
-    return p;
+    return std::move(p);
 }
 
 }  // namespace pmsolve

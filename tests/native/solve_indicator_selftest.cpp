@@ -6,250 +6,13 @@
 // field in matrix order and which, reversed and under seeded permutations, plans with every column at its in-order level and
 // EXECUTES -- serially, with the host field type and the routine the kernels call -- to the in-order assignment; the same corpus with
 // the plain marker, which plans as it always did and sticks at the hit row; and a guard row that waits for its index.
-// Built and run by tests/test_native_solve_indicator.py.  Prints "<curve>: <failures> failures of <checks>".
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <functional>
-#include <string>
-#include <utility>
-#include <vector>
-
-#include "../../polymath_amd/host/polymath.hpp"
-#include "../../polymath_amd/host/solve_plan.hpp"
-#include "../../polymath_amd/csrc/divrem.cuh"
-
-using namespace pmsolve;
-
-static uint64_t rng_state = 0x13198A2E03707344ull;
-static uint64_t next_u64() {
-    uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// Built and run by tests/test_native_solve_indicator.py.  Prints "<curve>: <failures> failures of <checks>" and the digest of its plans (solve_selftest.hpp).
+#include "solve_selftest.hpp"
 
 template <class C>
-struct Suite {
-    typedef typename C::FrP P;
-    typedef pmhost::FrOps<C> F;
-    typedef typename F::Fr Fr;
-    typedef std::vector<std::pair<Fr, uint32_t>> Row;
-    static constexpr uint64_t NONE = ~(uint64_t)0;
-    const char *name;
-    int fails = 0, checks = 0;
-    uint64_t modulus[4];
-
-    explicit Suite(const char *n) : name(n) {
-        for (int i = 0; i < 4; ++i) modulus[i] = (uint64_t)P::MOD[2 * i] | (uint64_t)P::MOD[2 * i + 1] << 32;
-    }
-    void check(bool ok, const std::string &what) {
-        ++checks;
-        if (!ok) { ++fails; printf("%s: FAILED %s\n", name, what.c_str()); }
-    }
-    static Fr u(uint64_t v) { return F::from_u64(v); }
-    static Fr marker() { Fr m; memset(m.l, 0xff, sizeof m.l); return m; }
-    static Fr quotient_marker() { Fr m = marker(); m.l[0] = 0xfffffffeu; return m; }
-    static Fr indicator_marker() { Fr m = marker(); m.l[2] = 0xfffffffeu; return m; }      // bit 64: the lowest bit of the second 64-bit word
-    static bool is_marker(const Fr &v) { return pm::marker_byte<P>(v) != 0; }
-
-    struct System {
-        uint64_t m0 = 1, mw = 0;
-        std::vector<Row> a, b, c;
-        std::vector<uint64_t> rowptr[3], val[3];
-        std::vector<uint32_t> col[3];
-        Csr m[3];
-        uint32_t add(const Row &ra, const Row &rb, const Row &rc) { a.push_back(ra); b.push_back(rb); c.push_back(rc); return (uint32_t)a.size() - 1; }
-        uint32_t boolean(uint32_t j) { return add(Row{{F::one(), j}}, Row{{F::one(), 0}, {F::neg(F::one()), j}}, Row{}); }
-        uint64_t nr() const { return a.size(); }
-        void freeze() {
-            const std::vector<Row> *src[3] = {&a, &b, &c};
-            for (int k = 0; k < 3; ++k) {
-                rowptr[k].assign(1, 0); col[k].clear(); val[k].clear();
-                for (const Row &r : *src[k]) {
-                    for (const auto &e : r) {
-                        col[k].push_back(e.second);
-                        uint64_t w[4];
-                        memcpy(w, e.first.l, 32);
-                        val[k].insert(val[k].end(), w, w + 4);
-                    }
-                    rowptr[k].push_back(col[k].size());
-                }
-                if (col[k].empty()) { col[k].push_back(0); val[k].assign(4, 0); }
-                m[k] = Csr{rowptr[k].data(), col[k].data(), val[k].data()};
-            }
-        }
-        // pattern bytes: 1 on `cols`, 2 on `quotients`, 3 on `indicators`
-        std::vector<uint8_t> unknown(const std::vector<uint32_t> &cols, const std::vector<uint32_t> &quotients, const std::vector<uint32_t> &indicators) const {
-            std::vector<uint8_t> un(m0 + mw, 0);
-            for (uint32_t j : cols) un[j] = PATTERN_UNKNOWN;
-            for (uint32_t j : quotients) un[j] = PATTERN_QUOTIENT;
-            for (uint32_t j : indicators) un[j] = PATTERN_INDICATOR;
-            return un;
-        }
-        System permuted(const std::vector<uint32_t> &order) const {      // row i of the result is row order[i] of this system
-            System t;
-            t.m0 = m0; t.mw = mw;
-            for (uint32_t r : order) t.add(a[r], b[r], c[r]);
-            return t;
-        }
-    };
-    Plan in_order(System &s, const std::vector<uint8_t> &unknown, uint32_t wide = WIDE_STEPS, bool with_modulus = true) {
-        s.freeze();
-        return build_plan(s.m, s.nr(), s.m0, s.mw, unknown.data(), wide, with_modulus ? modulus : nullptr);
-    }
-    Plan any_order(System &s, const std::vector<uint8_t> &unknown, uint32_t wide = WIDE_STEPS) {
-        s.freeze();
-        return build_plan_any_order(s.m, s.nr(), s.m0, s.mw, unknown.data(), wide, modulus);
-    }
-
-    static Fr coef_at(const System &s, int k, uint64_t e) {
-        Fr v;
-        memcpy(v.l, s.val[k].data() + 4 * e, 32);
-        return v;
-    }
-    static Fr dot(const System &s, int k, const std::vector<Fr> &z, uint64_t r, uint64_t skip, bool unmarked) {
-        Fr acc = F::zero();
-        for (uint64_t e = s.rowptr[k][r]; e < s.rowptr[k][r + 1]; ++e) {
-            if (e == skip || (unmarked && is_marker(z[s.col[k][e]]))) continue;
-            acc = F::add(acc, F::mul(coef_at(s, k, e), z[s.col[k][e]]));
-        }
-        return acc;
-    }
-    static bool rows_hold(const System &s, const std::vector<Fr> &z) {
-        for (uint64_t r = 0; r < s.nr(); ++r)
-            if (!F::mul(dot(s, 0, z, r, NONE, false), dot(s, 1, z, r, NONE, false)).eq(dot(s, 2, z, r, NONE, false))) return false;
-        return true;
-    }
-    // The launch schedule walked serially, step by step as the kernels do (solve.hip: solve_step, solve_bits, solve_iszero,
-    // solve_divrem, solve_indicator).  -> the stuck word as the kernels leave it before k_solve_stuck_row
-    static uint64_t execute(const System &s, const Plan &p, std::vector<Fr> &z) {
-        uint64_t stuck = NONE;
-        const auto stick = [&](const Step &st) {
-            const uint64_t key = (p.reordered ? (uint64_t)st.level << 32 : 0) | st.row;
-            if (key < stuck) stuck = key;
-        };
-        for (const Launch &l : p.launches)
-            for (uint32_t t = l.lo; t < l.hi; ++t) {
-                const Step &st = p.steps[t];
-                if (st.kind == KIND_INDICATOR) {      // K's whole row, which side from the step record; pm::indicator_of is what the kernels call
-                    z[st.col] = pm::indicator_of<P>(dot(s, st.cols_off ? 0 : 1, z, st.row, NONE, false));
-                    continue;
-                }
-                if (st.kind == KIND_DIVREM) {
-                    const DivRow &dv = p.divs[st.cols_off];
-                    const int kq = dv.q_in_b ? 1 : 0;
-                    const Fr d = dot(s, 1 - kq, z, st.row, NONE, false);
-                    const Fr a = F::mul(dot(s, 2, z, st.row, dv.pos_r, false), F::inv(coef_at(s, kq, st.pos)));
-                    Fr q = F::zero(), rem = F::zero();
-                    if (!pm::euclid_divrem<P>(a, d, &q, &rem)) stick(st);
-                    z[st.col] = q;
-                    z[dv.col_r] = rem;
-                    continue;
-                }
-                if (st.kind == KIND_ISZERO) {
-                    const PairRows &pr = p.pairs[st.cols_off];
-                    const int k1 = pr.m_in_b ? 0 : 1, km = pr.m_in_b ? 1 : 0, kb = pr.b_in_b ? 1 : 0;
-                    const Fr d1 = dot(s, k1, z, pr.row1, NONE, false), c1_rest = dot(s, 2, z, pr.row1, pr.pos_c, false);
-                    const Fr rest2 = dot(s, kb, z, st.row, st.pos, false), c2 = dot(s, 2, z, st.row, NONE, false);
-                    const Fr inv1 = F::inv(d1);
-                    const Fr inv2 = pr.negated ? F::neg(inv1) : inv1;
-                    const Fr b_unequal = F::mul(F::sub(F::mul(c2, inv2), rest2), F::inv(coef_at(s, kb, st.pos)));
-                    const Fr b_equal = F::mul(F::neg(c1_rest), F::inv(coef_at(s, 2, pr.pos_c)));
-                    const Fr b = d1.is_zero() ? b_equal : b_unequal;
-                    z[st.col] = b;
-                    z[pr.col_m] = F::mul(F::mul(F::add(c1_rest, F::mul(coef_at(s, 2, pr.pos_c), b)), inv1), F::inv(coef_at(s, km, pr.pos_m)));
-                    continue;
-                }
-                const uint32_t kind = st.kind >= KIND_BITS_C ? st.kind - KIND_BITS_C : st.kind;
-                const int k = kind == KIND_A ? 0 : kind == KIND_B ? 1 : 2;
-                const bool bits = st.bits != 0;
-                const Fr az = dot(s, 0, z, st.row, !bits && k == 0 ? st.pos : NONE, bits && k == 0), bz = dot(s, 1, z, st.row, !bits && k == 1 ? st.pos : NONE, bits && k == 1),
-                         cz = dot(s, 2, z, st.row, !bits && k == 2 ? st.pos : NONE, bits && k == 2);
-                const Fr inv = F::inv(coef_at(s, k, st.pos));
-                Fr v = F::zero();
-                bool ok = true;
-                if (kind == KIND_C) {
-                    v = F::sub(F::mul(az, bz), cz);
-                } else {
-                    const Fr den = kind == KIND_A ? bz : az, rest = kind == KIND_A ? az : bz;
-                    ok = !den.is_zero();
-                    if (ok) v = F::sub(F::mul(cz, F::inv(den)), rest);
-                }
-                if (!bits) {
-                    if (!ok) stick(st);
-                    z[st.col] = ok ? F::mul(v, inv) : F::zero();
-                    continue;
-                }
-                Fr t_canon = pm::from_mont<P>(F::mul(v, inv));
-                for (uint32_t i = st.bits; ok && i < 32 * (uint32_t)P::N; ++i) ok = ((t_canon.l[i / 32] >> (i % 32)) & 1) == 0;
-                if (!ok) stick(st);
-                for (uint32_t i = 0; i < st.bits; ++i)
-                    z[p.bit_cols[st.cols_off + i]] = ok && ((t_canon.l[i / 32] >> (i % 32)) & 1) ? F::one() : F::zero();
-            }
-        return stuck;
-    }
-    static bool same_step(const Step &a, const Step &b) {
-        return a.pos == b.pos && a.row == b.row && a.col == b.col && a.kind == b.kind && a.level == b.level && a.bits == b.bits && a.cols_off == b.cols_off;
-    }
-    static bool same_launch(const Launch &a, const Launch &b) {
-        return a.lo == b.lo && a.hi == b.hi && a.chain == b.chain && a.divides == b.divides && a.bits == b.bits && a.iszero == b.iszero && a.divrem == b.divrem &&
-               a.indicator == b.indicator;
-    }
-    static bool same_plan(const Plan &a, const Plan &b) {
-        bool ok = a.error == b.error && a.error_row == b.error_row && a.error_col == b.error_col && a.message == b.message && a.steps.size() == b.steps.size() &&
-                  a.level_ptr == b.level_ptr && a.launches.size() == b.launches.size() && a.bit_cols == b.bit_cols && a.pairs.size() == b.pairs.size() &&
-                  a.divs.size() == b.divs.size() && a.reordered == b.reordered;
-        for (size_t t = 0; ok && t < a.steps.size(); ++t) ok = same_step(a.steps[t], b.steps[t]);
-        for (size_t t = 0; ok && t < a.pairs.size(); ++t)
-            ok = a.pairs[t].pos_m == b.pairs[t].pos_m && a.pairs[t].pos_c == b.pairs[t].pos_c && a.pairs[t].row1 == b.pairs[t].row1 && a.pairs[t].col_m == b.pairs[t].col_m &&
-                 a.pairs[t].m_in_b == b.pairs[t].m_in_b && a.pairs[t].b_in_b == b.pairs[t].b_in_b && a.pairs[t].negated == b.pairs[t].negated;
-        for (size_t t = 0; ok && t < a.divs.size(); ++t) ok = a.divs[t].pos_r == b.divs[t].pos_r && a.divs[t].col_r == b.divs[t].col_r && a.divs[t].q_in_b == b.divs[t].q_in_b;
-        for (size_t t = 0; ok && t < a.launches.size(); ++t) ok = same_launch(a.launches[t], b.launches[t]);
-        return ok;
-    }
-    static std::vector<uint32_t> column_levels(const System &s, const Plan &p) {      // 0: not solved by the plan
-        std::vector<uint32_t> lv(s.m0 + s.mw, 0);
-        for (const Step &st : p.steps) {
-            if (st.bits) for (uint32_t i = 0; i < st.bits; ++i) lv[p.bit_cols[st.cols_off + i]] = st.level;
-            else lv[st.col] = st.level;
-            if (st.kind == KIND_ISZERO) lv[p.pairs[st.cols_off].col_m] = st.level;
-            if (st.kind == KIND_DIVREM) lv[p.divs[st.cols_off].col_r] = st.level;
-        }
-        return lv;
-    }
-    static size_t count_kind(const Plan &p, uint32_t kind) {
-        size_t n = 0;
-        for (const Step &st : p.steps) n += st.kind == kind;
-        return n;
-    }
-    // sorted by (level, kind, row), strictly; the launches cover the steps in that order; a wide launch holds indicator rows only or
-    // none; a launch that holds nothing but kind-C steps and indicator rows does not divide
-    static bool well_sorted(const Plan &p) {
-        bool ok = p.level_ptr.size() == (size_t)p.levels() + 1 && (p.steps.empty() || (p.level_ptr.front() == 0 && p.level_ptr.back() == p.steps.size()));
-        for (size_t t = 0; ok && t < p.steps.size(); ++t) {
-            const Step &b = p.steps[t];
-            ok = b.level >= 1 && b.level <= p.levels() && p.level_ptr[b.level - 1] <= t && t < p.level_ptr[b.level];
-            if (ok && t) {
-                const Step &a = p.steps[t - 1];
-                ok = a.level < b.level || (a.level == b.level && (a.kind < b.kind || (a.kind == b.kind && a.row < b.row)));
-            }
-        }
-        uint32_t at = 0;
-        for (const Launch &l : p.launches) {
-            ok = ok && l.lo == at && l.hi > l.lo;
-            bool divides = false;
-            for (uint32_t t = l.lo; ok && t < l.hi; ++t) {
-                const uint32_t kind = p.steps[t].kind;
-                ok = l.chain || (kind == KIND_INDICATOR) == (l.indicator != 0);
-                divides = divides || (kind != KIND_C && kind != KIND_BITS_C && kind != KIND_INDICATOR);
-            }
-            ok = ok && divides == (l.divides != 0);
-            at = l.hi;
-        }
-        return ok && at == p.steps.size();
-    }
+struct Suite : SolveRig<C> {
+    SOLVE_RIG_NAMES(C)
+    explicit Suite(const char *n) : Rig(n) {}
 
     // ---- 1. the accepted shapes, against plans written by hand.  0 one | 1 inp, 2 b given | 3 u
     //   k u * guard = 0  with u in A or in B, k = 1 or 7, guard = inp - 3, 3 - inp or inp - b
@@ -499,16 +262,6 @@ struct Suite {
         };
         return c;
     }
-    static void keep_groups(std::vector<uint32_t> &order, const std::vector<std::vector<uint32_t>> &groups) {
-        std::vector<uint32_t> pos(order.size());
-        for (uint32_t i = 0; i < order.size(); ++i) pos[order[i]] = i;
-        for (const auto &g : groups) {
-            std::vector<uint32_t> at;
-            for (uint32_t r : g) at.push_back(pos[r]);
-            std::sort(at.begin(), at.end());
-            for (size_t k = 0; k < g.size(); ++k) order[at[k]] = g[k];
-        }
-    }
     void corpus() {
         std::vector<Case> cases;
         cases.push_back(decoder40());
@@ -629,12 +382,12 @@ struct Suite {
         markers();
         corpus();
         waiting_guard();
-        printf("%s: %d failures of %d\n", name, fails, checks);
-        return fails;
+        return report();
     }
 };
 
 int main() {
+    rng_state = 0x13198A2E03707344ull;
     Suite<pm::BlsCurve> bls("bls12_381");
     Suite<pm::BnCurve> bn("bn254");
     return (bls.run() | bn.run()) ? 1 : 0;

@@ -5,229 +5,14 @@
 // case must plan, give every column its in-order level, come out sorted by (level, kind, row) and EXECUTE -- serially, with the host
 // field type, the way the kernels do it -- to the in-order assignment, pairs with d != 0 and d = 0; the waiting cases by hand; the
 // refusals, which carry build_plan's code, row, column and message; the stuck word's root-cause key; and the cost of a reversed chain.
-// Built and run by tests/test_native_solve_order.py.  Prints "<curve>: <failures> failures of <checks>".
+// Built and run by tests/test_native_solve_order.py.  Prints "<curve>: <failures> failures of <checks>" and the digest of its plans (solve_selftest.hpp).
 #include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <functional>
-#include <string>
-#include <utility>
-#include <vector>
-
-#include "../../polymath_amd/host/polymath.hpp"
-#include "../../polymath_amd/host/solve_plan.hpp"
-
-using namespace pmsolve;
-
-static uint64_t rng_state = 0x243F6A8885A308D3ull;
-static uint64_t next_u64() {
-    uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+#include "solve_selftest.hpp"
 
 template <class C>
-struct Suite {
-    typedef typename C::FrP P;
-    typedef pmhost::FrOps<C> F;
-    typedef typename F::Fr Fr;
-    typedef std::vector<std::pair<Fr, uint32_t>> Row;
-    static constexpr uint64_t NONE = ~(uint64_t)0;
-    const char *name;
-    int fails = 0, checks = 0;
-    uint64_t modulus[4];
-
-    explicit Suite(const char *n) : name(n) {
-        for (int i = 0; i < 4; ++i) modulus[i] = (uint64_t)P::MOD[2 * i] | (uint64_t)P::MOD[2 * i + 1] << 32;
-    }
-    void check(bool ok, const std::string &what) {
-        ++checks;
-        if (!ok) { ++fails; printf("%s: FAILED %s\n", name, what.c_str()); }
-    }
-    static Fr rnd() { return F::mul(F::from_u64(next_u64()), F::add(F::from_u64(next_u64()), F::pow(F::from_u64(next_u64() | 1), 5))); }
-    static Fr u(uint64_t v) { return F::from_u64(v); }
-    static Fr marker() { Fr m; memset(m.l, 0xff, sizeof m.l); return m; }
-    static bool is_marker(const Fr &v) { const Fr m = marker(); return memcmp(v.l, m.l, sizeof m.l) == 0; }
-
-    struct System {
-        uint64_t m0 = 1, mw = 0;
-        std::vector<Row> a, b, c;
-        std::vector<uint64_t> rowptr[3], val[3];
-        std::vector<uint32_t> col[3];
-        Csr m[3];
-        uint32_t add(const Row &ra, const Row &rb, const Row &rc) { a.push_back(ra); b.push_back(rb); c.push_back(rc); return (uint32_t)a.size() - 1; }
-        uint32_t boolean(uint32_t j) { return add(Row{{F::one(), j}}, Row{{F::one(), 0}, {F::neg(F::one()), j}}, Row{}); }
-        uint64_t nr() const { return a.size(); }
-        void freeze() {
-            const std::vector<Row> *src[3] = {&a, &b, &c};
-            for (int k = 0; k < 3; ++k) {
-                rowptr[k].assign(1, 0); col[k].clear(); val[k].clear();
-                for (const Row &r : *src[k]) {
-                    for (const auto &e : r) {
-                        col[k].push_back(e.second);
-                        uint64_t w[4];
-                        memcpy(w, e.first.l, 32);
-                        val[k].insert(val[k].end(), w, w + 4);
-                    }
-                    rowptr[k].push_back(col[k].size());
-                }
-                if (col[k].empty()) { col[k].push_back(0); val[k].assign(4, 0); }
-                m[k] = Csr{rowptr[k].data(), col[k].data(), val[k].data()};
-            }
-        }
-        std::vector<uint8_t> unknown(const std::vector<uint32_t> &cols) const {
-            std::vector<uint8_t> un(m0 + mw, 0);
-            for (uint32_t j : cols) un[j] = 1;
-            return un;
-        }
-        // row i of the result is row order[i] of this system
-        System permuted(const std::vector<uint32_t> &order) const {
-            System t;
-            t.m0 = m0; t.mw = mw;
-            for (uint32_t r : order) t.add(a[r], b[r], c[r]);
-            return t;
-        }
-    };
-    Plan in_order(System &s, const std::vector<uint8_t> &unknown, uint32_t wide = WIDE_STEPS, bool with_modulus = true) {
-        s.freeze();
-        return build_plan(s.m, s.nr(), s.m0, s.mw, unknown.data(), wide, with_modulus ? modulus : nullptr);
-    }
-    Plan any_order(System &s, const std::vector<uint8_t> &unknown, uint32_t wide = WIDE_STEPS, bool with_modulus = true) {
-        s.freeze();
-        return build_plan_any_order(s.m, s.nr(), s.m0, s.mw, unknown.data(), wide, with_modulus ? modulus : nullptr);
-    }
-
-    static Fr coef_at(const System &s, int k, uint64_t e) {
-        Fr v;
-        memcpy(v.l, s.val[k].data() + 4 * e, 32);
-        return v;
-    }
-    static Fr dot(const System &s, int k, const std::vector<Fr> &z, uint64_t r, uint64_t skip, bool unmarked) {
-        Fr acc = F::zero();
-        for (uint64_t e = s.rowptr[k][r]; e < s.rowptr[k][r + 1]; ++e) {
-            if (e == skip || (unmarked && is_marker(z[s.col[k][e]]))) continue;
-            acc = F::add(acc, F::mul(coef_at(s, k, e), z[s.col[k][e]]));
-        }
-        return acc;
-    }
-    static bool rows_hold(const System &s, const std::vector<Fr> &z) {
-        for (uint64_t r = 0; r < s.nr(); ++r)
-            if (!F::mul(dot(s, 0, z, r, NONE, false), dot(s, 1, z, r, NONE, false)).eq(dot(s, 2, z, r, NONE, false))) return false;
-        return true;
-    }
-    // The launch schedule walked serially, step by step as the kernels do (solve.hip: solve_step, solve_bits, solve_iszero).  -> the
-    // stuck word as the kernels leave it BEFORE k_solve_stuck_row: the minimum of row, or of (level << 32) | row under a reordered
-    // plan; `stuck_rows`: every row that stuck, in the order of the walk
-    static uint64_t execute(const System &s, const Plan &p, std::vector<Fr> &z, std::vector<uint32_t> *stuck_rows = nullptr) {
-        uint64_t stuck = NONE;
-        const auto stick = [&](const Step &st) {
-            const uint64_t key = (p.reordered ? (uint64_t)st.level << 32 : 0) | st.row;
-            if (key < stuck) stuck = key;
-            if (stuck_rows) stuck_rows->push_back(st.row);
-        };
-        for (const Launch &l : p.launches)
-            for (uint32_t t = l.lo; t < l.hi; ++t) {
-                const Step &st = p.steps[t];
-                if (st.kind == KIND_ISZERO) {
-                    const PairRows &pr = p.pairs[st.cols_off];
-                    const int k1 = pr.m_in_b ? 0 : 1, km = pr.m_in_b ? 1 : 0, kb = pr.b_in_b ? 1 : 0;
-                    const Fr d1 = dot(s, k1, z, pr.row1, NONE, false), c1_rest = dot(s, 2, z, pr.row1, pr.pos_c, false);
-                    const Fr rest2 = dot(s, kb, z, st.row, st.pos, false), c2 = dot(s, 2, z, st.row, NONE, false);
-                    const Fr inv1 = F::inv(d1);           // d1^(r-2): 0 for 0, as inverse<P> on the device
-                    const Fr inv2 = pr.negated ? F::neg(inv1) : inv1;
-                    const Fr b_unequal = F::mul(F::sub(F::mul(c2, inv2), rest2), F::inv(coef_at(s, kb, st.pos)));
-                    const Fr b_equal = F::mul(F::neg(c1_rest), F::inv(coef_at(s, 2, pr.pos_c)));
-                    const Fr b = d1.is_zero() ? b_equal : b_unequal;
-                    z[st.col] = b;
-                    z[pr.col_m] = F::mul(F::mul(F::add(c1_rest, F::mul(coef_at(s, 2, pr.pos_c), b)), inv1), F::inv(coef_at(s, km, pr.pos_m)));
-                    continue;
-                }
-                const uint32_t kind = st.kind >= KIND_BITS_C ? st.kind - KIND_BITS_C : st.kind;
-                const int k = kind == KIND_A ? 0 : kind == KIND_B ? 1 : 2;
-                const bool bits = st.bits != 0;
-                const Fr az = dot(s, 0, z, st.row, !bits && k == 0 ? st.pos : NONE, bits && k == 0), bz = dot(s, 1, z, st.row, !bits && k == 1 ? st.pos : NONE, bits && k == 1),
-                         cz = dot(s, 2, z, st.row, !bits && k == 2 ? st.pos : NONE, bits && k == 2);
-                const Fr inv = F::inv(coef_at(s, k, st.pos));
-                Fr v = F::zero();
-                bool ok = true;
-                if (kind == KIND_C) {
-                    v = F::sub(F::mul(az, bz), cz);
-                } else {
-                    const Fr den = kind == KIND_A ? bz : az, rest = kind == KIND_A ? az : bz;
-                    ok = !den.is_zero();
-                    if (ok) v = F::sub(F::mul(cz, F::inv(den)), rest);
-                }
-                if (!bits) {
-                    if (!ok) stick(st);
-                    z[st.col] = ok ? F::mul(v, inv) : F::zero();
-                    continue;
-                }
-                Fr t_canon = pm::from_mont<P>(F::mul(v, inv));
-                for (uint32_t i = st.bits; ok && i < 32 * (uint32_t)P::N; ++i) ok = ((t_canon.l[i / 32] >> (i % 32)) & 1) == 0;
-                if (!ok) stick(st);
-                for (uint32_t i = 0; i < st.bits; ++i)
-                    z[p.bit_cols[st.cols_off + i]] = ok && ((t_canon.l[i / 32] >> (i % 32)) & 1) ? F::one() : F::zero();
-            }
-        return stuck;
-    }
-    static bool same_step(const Step &a, const Step &b) {
-        return a.pos == b.pos && a.row == b.row && a.col == b.col && a.kind == b.kind && a.level == b.level && a.bits == b.bits && a.cols_off == b.cols_off;
-    }
-    static bool same_pair(const PairRows &a, const PairRows &b) {
-        return a.pos_m == b.pos_m && a.pos_c == b.pos_c && a.row1 == b.row1 && a.col_m == b.col_m && a.m_in_b == b.m_in_b && a.b_in_b == b.b_in_b && a.negated == b.negated;
-    }
-    static bool same_plan(const Plan &a, const Plan &b) {
-        bool ok = a.error == b.error && a.error_row == b.error_row && a.error_col == b.error_col && a.message == b.message && a.steps.size() == b.steps.size() &&
-                  a.level_ptr == b.level_ptr && a.launches.size() == b.launches.size() && a.bit_cols == b.bit_cols && a.pairs.size() == b.pairs.size() &&
-                  a.reordered == b.reordered;
-        for (size_t t = 0; ok && t < a.steps.size(); ++t) ok = same_step(a.steps[t], b.steps[t]);
-        for (size_t t = 0; ok && t < a.pairs.size(); ++t) ok = same_pair(a.pairs[t], b.pairs[t]);
-        for (size_t t = 0; ok && t < a.launches.size(); ++t)
-            ok = a.launches[t].lo == b.launches[t].lo && a.launches[t].hi == b.launches[t].hi && a.launches[t].chain == b.launches[t].chain &&
-                 a.launches[t].divides == b.launches[t].divides && a.launches[t].bits == b.launches[t].bits && a.launches[t].iszero == b.launches[t].iszero;
-        return ok;
-    }
-    // level per column, as the plan's steps give it (0: not solved by the plan)
-    static std::vector<uint32_t> column_levels(const System &s, const Plan &p) {
-        std::vector<uint32_t> lv(s.m0 + s.mw, 0);
-        for (const Step &st : p.steps) {
-            if (st.bits) for (uint32_t i = 0; i < st.bits; ++i) lv[p.bit_cols[st.cols_off + i]] = st.level;
-            else lv[st.col] = st.level;
-            if (st.kind == KIND_ISZERO) lv[p.pairs[st.cols_off].col_m] = st.level;
-        }
-        return lv;
-    }
-    // sorted by (level, kind, row), strictly; level_ptr and the launches cover the steps in that order
-    static bool well_sorted(const Plan &p) {
-        bool ok = p.level_ptr.size() == (size_t)p.levels() + 1 && (p.steps.empty() || (p.level_ptr.front() == 0 && p.level_ptr.back() == p.steps.size()));
-        for (size_t t = 0; ok && t < p.steps.size(); ++t) {
-            const Step &b = p.steps[t];
-            ok = b.level >= 1 && b.level <= p.levels() && p.level_ptr[b.level - 1] <= t && t < p.level_ptr[b.level];
-            if (ok && t) {
-                const Step &a = p.steps[t - 1];
-                ok = a.level < b.level || (a.level == b.level && (a.kind < b.kind || (a.kind == b.kind && a.row < b.row)));
-            }
-        }
-        uint32_t at = 0;
-        for (const Launch &l : p.launches) {
-            ok = ok && l.lo == at && l.hi > l.lo;
-            at = l.hi;
-        }
-        return ok && at == p.steps.size();
-    }
-
-    static void ark(System &s, const Row &lc, uint32_t flag, uint32_t m) {
-        s.add(lc, Row{{F::one(), m}}, Row{{F::one(), flag}});
-        s.add(lc, Row{{F::one(), 0}, {F::neg(F::one()), flag}}, Row{});
-    }
-    static void circom(System &s, const Row &lc, uint32_t flag, uint32_t m) {
-        Row minus;
-        for (size_t i = lc.size(); i-- > 0;) minus.push_back({F::neg(lc[i].first), lc[i].second});
-        s.add(minus, Row{{F::one(), m}}, Row{{F::one(), flag}, {F::neg(F::one()), 0}});
-        s.add(lc, Row{{F::one(), flag}}, Row{});
-    }
+struct Suite : SolveRig<C> {
+    SOLVE_RIG_NAMES(C)
+    explicit Suite(const char *n) : Rig(n) {}
 
     // ---- the corpus.  No ordinary row has the opener's shape (one unknown alone on A or B, the other in C): the sides that hold a
     // column which a later row reads carry a constant beside it, so that a permuted order registers no opener that is none.
@@ -374,18 +159,6 @@ struct Suite {
             return z;
         };
         return c;
-    }
-
-    // the rows of each group take the group's positions in the group's order
-    static void keep_groups(std::vector<uint32_t> &order, const std::vector<std::vector<uint32_t>> &groups) {
-        std::vector<uint32_t> pos(order.size());
-        for (uint32_t i = 0; i < order.size(); ++i) pos[order[i]] = i;
-        for (const auto &g : groups) {
-            std::vector<uint32_t> at;
-            for (uint32_t r : g) at.push_back(pos[r]);
-            std::sort(at.begin(), at.end());
-            for (size_t k = 0; k < g.size(); ++k) order[at[k]] = g[k];
-        }
     }
 
     // ---- 1 + 2. the corpus in order, reversed and permuted
@@ -628,12 +401,12 @@ struct Suite {
         refused();
         root_cause();
         blow_up();
-        printf("%s: %d failures of %d\n", name, fails, checks);
-        return fails;
+        return report();
     }
 };
 
 int main() {
+    rng_state = 0x243F6A8885A308D3ull;
     Suite<pm::BlsCurve> bls("bls12_381");
     Suite<pm::BnCurve> bn("bn254");
     return (bls.run() | bn.run()) ? 1 : 0;

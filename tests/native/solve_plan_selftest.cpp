@@ -1,111 +1,16 @@
 // The witness solver's plan builder (polymath_amd/host/solve_plan.hpp: header-only, no HIP) on the CPU: step lists, kinds, levels,
 // level_ptr and the launch schedule against hand-written expectations, the structural errors with their rows and columns, and the
 // plan EXECUTED serially with the host field type (polymath_amd/host/polymath.hpp: FrOps) against direct evaluation of the circuit.
-// Built and run by tests/test_native_solve_plan.py.  Prints "<curve>: <failures> failures of <checks>".
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <utility>
-#include <vector>
-
-#include "../../polymath_amd/host/polymath.hpp"
-#include "../../polymath_amd/host/solve_plan.hpp"
-
-using namespace pmsolve;
-
-static uint64_t rng_state = 0x13198A2E03707344ull;
-static uint64_t next_u64() {
-    uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// Built and run by tests/test_native_solve_plan.py.  Prints "<curve>: <failures> failures of <checks>" and the digest of its plans (solve_selftest.hpp).
+#include "solve_selftest.hpp"
 
 template <class C>
-struct Suite {
-    typedef pmhost::FrOps<C> F;
-    typedef typename F::Fr Fr;
-    typedef std::vector<std::pair<Fr, uint32_t>> Row;
-    const char *name;
-    int fails = 0, checks = 0;
-
-    void check(bool ok, const char *what) {
-        ++checks;
-        if (!ok) { ++fails; printf("%s: FAILED %s\n", name, what); }
-    }
-    static Fr rnd() { return F::mul(F::from_u64(next_u64()), F::add(F::from_u64(next_u64()), F::pow(F::from_u64(next_u64() | 1), 5))); }
+struct Suite : SolveRig<C> {
+    SOLVE_RIG_NAMES(C)
+    explicit Suite(const char *n) : Rig(n) {}
     static Fr minus_one() { return F::neg(F::one()); }
     static bool eq(const Fr &a, const Fr &b) { return a.eq(b); }
 
-    struct System {
-        uint64_t m0 = 1, mw = 0;
-        std::vector<Row> a, b, c;
-        std::vector<uint64_t> rowptr[3], val[3];
-        std::vector<uint32_t> col[3];
-        Csr m[3];
-        void add(const Row &ra, const Row &rb, const Row &rc) { a.push_back(ra); b.push_back(rb); c.push_back(rc); }
-        uint64_t nr() const { return a.size(); }
-        void freeze() {
-            const std::vector<Row> *src[3] = {&a, &b, &c};
-            for (int k = 0; k < 3; ++k) {
-                rowptr[k].assign(1, 0); col[k].clear(); val[k].clear();
-                for (const Row &r : *src[k]) {
-                    for (const auto &e : r) {
-                        col[k].push_back(e.second);
-                        uint64_t w[4];
-                        memcpy(w, e.first.l, 32);
-                        val[k].insert(val[k].end(), w, w + 4);
-                    }
-                    rowptr[k].push_back(col[k].size());
-                }
-                if (col[k].empty()) { col[k].push_back(0); val[k].assign(4, 0); }
-                m[k] = Csr{rowptr[k].data(), col[k].data(), val[k].data()};
-            }
-        }
-        Plan plan(const std::vector<uint8_t> &unknown, uint32_t wide = WIDE_STEPS) {
-            freeze();
-            return build_plan(m, nr(), m0, mw, unknown.data(), wide);
-        }
-    };
-
-    static Fr coef_at(const System &s, int k, uint64_t e) {
-        Fr v;
-        memcpy(v.l, s.val[k].data() + 4 * e, 32);
-        return v;
-    }
-    static Fr dot_skip(const System &s, int k, const std::vector<Fr> &z, uint64_t r, uint64_t skip) {
-        Fr acc = F::zero();
-        for (uint64_t e = s.rowptr[k][r]; e < s.rowptr[k][r + 1]; ++e)
-            if (e != skip) acc = F::add(acc, F::mul(coef_at(s, k, e), z[s.col[k][e]]));
-        return acc;
-    }
-    // the launch schedule walked serially, step by step as the kernels do; -> smallest stuck row or ~0
-    static uint64_t execute(const System &s, const Plan &p, std::vector<Fr> &z) {
-        const uint64_t none = ~(uint64_t)0;
-        uint64_t stuck = none;
-        for (const Launch &l : p.launches)
-            for (uint32_t t = l.lo; t < l.hi; ++t) {
-                const Step &st = p.steps[t];
-                const int k = st.kind == KIND_A ? 0 : st.kind == KIND_B ? 1 : 2;
-                const Fr az = dot_skip(s, 0, z, st.row, k == 0 ? st.pos : none), bz = dot_skip(s, 1, z, st.row, k == 1 ? st.pos : none),
-                         cz = dot_skip(s, 2, z, st.row, k == 2 ? st.pos : none);
-                const Fr inv = F::inv(coef_at(s, k, st.pos));
-                Fr v;
-                if (st.kind == KIND_C) {
-                    v = F::sub(F::mul(az, bz), cz);
-                } else {
-                    const Fr den = st.kind == KIND_A ? bz : az, rest = st.kind == KIND_A ? az : bz;
-                    if (den.is_zero()) {
-                        if (st.row < stuck) stuck = st.row;
-                        z[st.col] = F::zero();
-                        continue;
-                    }
-                    v = F::sub(F::mul(cz, F::inv(den)), rest);
-                }
-                z[st.col] = F::mul(v, inv);
-            }
-        return stuck;
-    }
     // the invariants every plan has: sorted by (level, kind, row), level_ptr monotone and consistent, a step's inputs solved at a lower
     // level, the launches a partition of the steps in order with chains made of narrow levels and level launches of one wide level
     void check_invariants(const System &s, const Plan &p, const std::vector<uint8_t> &unknown, uint32_t wide, const char *what) {
@@ -164,7 +69,7 @@ struct Suite {
             s.add(Row{{one, tmp[i]}}, lc, Row{{one, nw[i]}, {m1, xr[i]}});
         }
         std::vector<uint8_t> unknown = {0, 1, 0, 0, 1, 1, 1, 1, 1};
-        const Plan p = s.plan(unknown);
+        const Plan p = in_order(s, unknown, WIDE_STEPS, false);
         check(p.error == OK && p.steps.size() == 6, "mimc3: six steps");
         const uint32_t want_col[6] = {4, 5, 6, 7, 8, 1};
         const uint64_t want_pos[6] = {0, 1, 3, 4, 6, 7};
@@ -194,7 +99,7 @@ struct Suite {
             for (uint32_t r = 0; r < nr; ++r) s.add(Row{{F::one(), 1 + r}}, Row{{F::one(), 0}}, Row{{F::one(), 1 + nr + r}});
             std::vector<uint8_t> unknown(1 + 2 * nr, 0);
             for (uint32_t r = 0; r < nr; ++r) unknown[1 + nr + r] = 1;
-            const Plan p = s.plan(unknown);
+            const Plan p = in_order(s, unknown, WIDE_STEPS, false);
             bool ok = p.error == OK && p.steps.size() == nr && p.level_ptr == std::vector<uint32_t>({0, nr}) && p.launches.size() == 1 &&
                       p.launches[0].chain == (nr < WIDE_STEPS ? 1 : 0) && p.launches[0].divides == 0;
             for (uint32_t r = 0; ok && r < nr; ++r) ok = p.steps[r].row == r && p.steps[r].col == 1 + nr + r && p.steps[r].level == 1 && p.steps[r].kind == KIND_C && p.steps[r].pos == r;
@@ -230,7 +135,7 @@ struct Suite {
             s.add(Row{{alpha, p}}, Row{{beta, q}}, Row{{gamma, t}});
         }
         for (uint32_t wide : {WIDE_STEPS, 4u, 1000000u}) {
-            const Plan p = s.plan(unknown, wide);
+            const Plan p = in_order(s, unknown, wide, false);
             bool ok = p.error == OK && p.steps.size() == nr;
             for (size_t t = 0; ok && t < p.steps.size(); ++t) ok = p.steps[t].level == want_level[p.steps[t].row] && p.steps[t].kind == KIND_C;
             check(ok, "random gates: levels are 1 + max of the inputs' levels");
@@ -258,14 +163,14 @@ struct Suite {
         s.add(Row{{one, 3}}, Row{{one, 4}}, Row{{one, 5}});
         s.add(Row{{one, 5}, {one, 0}}, Row{{F::from_u64(2), 6}}, Row{{one, 3}});
         std::vector<uint8_t> unknown = {0, 0, 0, 1, 1, 1, 1};
-        const Plan p = s.plan(unknown);
+        const Plan p = in_order(s, unknown, WIDE_STEPS, false);
         bool ok = p.error == OK && p.steps.size() == 4;
         const uint32_t want[4][4] = {{0, 3, KIND_A, 1}, {1, 4, KIND_B, 1}, {2, 5, KIND_C, 2}, {3, 6, KIND_B, 3}};   // row, column, kind, level
         for (int t = 0; ok && t < 4; ++t) ok = p.steps[t].row == want[t][0] && p.steps[t].col == want[t][1] && p.steps[t].kind == want[t][2] && p.steps[t].level == want[t][3];
         check(ok, "kinds: A, B, C, B at levels 1, 1, 2, 3");
         check(p.level_ptr == std::vector<uint32_t>({0, 2, 3, 4}) && p.launches.size() == 1 && p.launches[0].chain && p.launches[0].divides, "kinds: one dividing chain");
         check_invariants(s, p, unknown, WIDE_STEPS, "kinds: invariants");
-        const Plan split = s.plan(unknown, 1);        // every level wide: level 1 is a dividing launch, level 2 is not
+        const Plan split = in_order(s, unknown, 1, false);        // every level wide: level 1 is a dividing launch, level 2 is not
         check(split.launches.size() == 3 && !split.launches[0].chain && split.launches[0].divides && !split.launches[1].divides && split.launches[2].divides,
               "kinds: the dividing kinds have launches of their own");
         check_invariants(s, split, unknown, 1, "kinds: invariants, wide");
@@ -290,7 +195,7 @@ struct Suite {
             System s; s.m0 = 1; s.mw = 3;             // row 1 has two unknowns
             s.add(Row{{one, 1}}, Row{{one, 0}}, Row{{one, 1}});
             s.add(Row{{one, 2}}, Row{{one, 3}}, Row{{one, 1}});
-            const Plan p = s.plan({0, 0, 1, 1});
+            const Plan p = in_order(s, {0, 0, 1, 1}, WIDE_STEPS, false);
             check(p.error == ERR_MANY_UNKNOWNS && p.error_row == 1 && p.message.find("row 1") != std::string::npos, "error: two unknowns in row 1");
         }
         {
@@ -298,19 +203,19 @@ struct Suite {
             s.add(Row{{one, 1}}, Row{{one, 0}}, Row{{one, 1}});
             s.add(Row{{one, 1}}, Row{{one, 1}}, Row{{one, 1}});
             s.add(Row{{one, 2}}, Row{{one, 0}, {minus_one(), 2}}, Row{});
-            const Plan p = s.plan({0, 0, 1});
+            const Plan p = in_order(s, {0, 0, 1}, WIDE_STEPS, false);
             check(p.error == ERR_TWO_MATRICES && p.error_row == 2 && p.error_col == 2 && p.message.find("row 2") != std::string::npos, "error: an unknown in A and in B");
         }
         {
             System s; s.m0 = 1; s.mw = 3;             // column 3 is marked and no row touches it
             s.add(Row{{one, 1}}, Row{{one, 0}}, Row{{one, 2}});
-            const Plan p = s.plan({0, 0, 1, 1});
+            const Plan p = in_order(s, {0, 0, 1, 1}, WIDE_STEPS, false);
             check(p.error == ERR_UNDETERMINED && p.error_col == 3 && p.message.find("column 3") != std::string::npos && p.steps.empty(), "error: an undetermined column");
         }
         {
             System s; s.m0 = 1; s.mw = 1;
             s.add(Row{{one, 1}}, Row{{one, 0}}, Row{{one, 1}});
-            const Plan p = s.plan({1, 0});
+            const Plan p = in_order(s, {1, 0}, WIDE_STEPS, false);
             check(p.error == ERR_COLUMN_ZERO, "error: column 0 marked");
         }
         {
@@ -318,7 +223,7 @@ struct Suite {
             s.add(Row{{F::zero(), 3}, {one, 1}}, Row{{one, 0}}, Row{{one, 2}});
             s.add(Row{{one, 2}}, Row{{one, 1}}, Row{{one, 3}, {F::zero(), 2}});
             const std::vector<uint8_t> unknown = {0, 0, 1, 1};
-            const Plan p = s.plan(unknown);
+            const Plan p = in_order(s, unknown, WIDE_STEPS, false);
             check(p.error == OK && p.steps.size() == 2 && p.steps[0].col == 2 && p.steps[0].level == 1 && p.steps[1].col == 3 && p.steps[1].level == 2 &&
                       p.steps[0].pos == 0 && p.steps[1].pos == 1, "a zero coefficient names no variable");
             check_invariants(s, p, unknown, WIDE_STEPS, "zero coefficient: invariants");
@@ -330,7 +235,7 @@ struct Suite {
         {
             System s; s.m0 = 1; s.mw = 1;             // nothing unknown: an empty plan
             s.add(Row{{one, 1}}, Row{{one, 0}}, Row{{one, 1}});
-            const Plan p = s.plan({0, 0});
+            const Plan p = in_order(s, {0, 0}, WIDE_STEPS, false);
             check(p.error == OK && p.steps.empty() && p.launches.empty() && p.levels() == 0, "no unknowns: an empty plan");
         }
     }
@@ -341,12 +246,12 @@ struct Suite {
         random_gates();
         kinds();
         errors();
-        printf("%s: %d failures of %d\n", name, fails, checks);
-        return fails;
+        return report();
     }
 };
 
 int main() {
+    rng_state = 0x13198A2E03707344ull;
     Suite<pm::BlsCurve> bls{"bls12_381"};
     Suite<pm::BnCurve> bn{"bn254"};
     return (bls.run() | bn.run()) ? 1 : 0;

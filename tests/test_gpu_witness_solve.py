@@ -15,13 +15,12 @@ import torch        # noqa: F401  before libpolymath_hip.so is loaded: torch bri
 
 from oracle.pyref import circuits as CI
 from oracle.pyref.fields import CURVES
+from witness_solve_helpers import BOTH, NONE, PM_ERR_INVALID_ARG, PM_OK, key_cache
 
 pytestmark = pytest.mark.gpu
 
-PM_OK, PM_ERR_INVALID_ARG, PM_ERR_REMAINDER_NONZERO, PM_ERR_STATE = 0, 1, 4, 8
-NONE = (1 << 64) - 1
-BOTH = ["bls12_381", "bn254"]
-_KEYS = {}
+PM_ERR_REMAINDER_NONZERO, PM_ERR_STATE = 4, 8
+_cached = key_cache()
 
 
 def _setup(gpu_ctx, curve, q, inst, wit, seed):
@@ -32,12 +31,6 @@ def _setup(gpu_ctx, curve, q, inst, wit, seed):
     x, z = g.fr(c.r), g.fr(c.r)
     pk = pm.setup((PM.R1CS(q.m0, q.mw, q.a, q.b, q.c), inst, wit), x, z)
     return dict(pm=pm, pk=pk, q=q, inst=inst, wit=wit, x=x, z=z, f=pm.field, c=c)
-
-
-def _cached(key, make):
-    if key not in _KEYS:
-        _KEYS[key] = make()
-    return _KEYS[key]
 
 
 def _stack(s, partials):

@@ -13,70 +13,11 @@ import pytest
 import torch        # noqa: F401  before libpolymath_hip.so is loaded: torch brings its own HIP runtime (tests/ntt_device_child.py)
 
 from oracle.pyref.fields import CURVES
+from witness_solve_helpers import BOTH, NONE, PM_ERR_INVALID_ARG, PM_OK, _completes, _rows, _setup, _solve, key_cache
 
 pytestmark = pytest.mark.gpu
 
-PM_OK, PM_ERR_INVALID_ARG = 0, 1
-NONE = (1 << 64) - 1
-BOTH = ["bls12_381", "bn254"]
-_KEYS = {}
-
-
-def _setup(gpu_ctx, curve, circuit, seed):
-    """circuit: a generator of polymath_amd.circuits, or an (R1CS, instance, witness) triple"""
-    from polymath_amd import circuits as PC, polymath as PM
-    c = CURVES[curve]
-    g = PC.SplitMix64(seed)
-    pm = PM.Polymath(curve, "merlin", ctx=gpu_ctx)
-    x, z = g.fr(c.r), g.fr(c.r)
-    q, inst, wit = pm._synthesize(circuit)
-    pk = pm.setup((q, inst, wit), x, z)
-    return dict(pm=pm, pk=pk, q=q, inst=inst, wit=wit, x=x, z=z, f=pm.field, c=c)
-
-
-def _cached(key, make):
-    if key not in _KEYS:
-        _KEYS[key] = make()
-    return _KEYS[key]
-
-
-def _limbs(s, values):
-    """fr_limbs(values).reshape(-1, 4); the many zeros and ones (the bits of the range checks) come from a table"""
-    f = s["f"]
-    small = np.fromiter((v if v <= 1 else 0 for v in values), dtype=np.intp, count=len(values))
-    out = f.fr_limbs([0, 1]).reshape(2, 4)[small]
-    big = np.fromiter((v > 1 for v in values), dtype=bool, count=len(values))
-    if big.any():
-        out[big] = f.fr_limbs([v for v in values if v > 1]).reshape(-1, 4)
-    return out
-
-
-def _rows(s, assignments, partial):
-    """-> (want, rows): count x (m0 + mw) x 4 words; want = the full assignments, rows = the same with the partial's markers"""
-    from polymath_amd import api, polymath as PM
-    want = np.stack([_limbs(s, list(inst) + list(wit)) for inst, wit in assignments])
-    marks = list(partial[0]) + list(partial[1])
-    rows = want.copy()
-    rows[:, np.array([v is None for v in marks])] = api.UNKNOWN_LIMBS
-    rows[:, np.array([v is PM.QUOTIENT for v in marks])] = api.QUOTIENT_LIMBS
-    return want, rows
-
-
-def _solve(s, rows, max_rows=2):
-    m0 = s["q"].m0
-    xs, ws = np.ascontiguousarray(rows[:, :m0]), np.ascontiguousarray(rows[:, m0:])
-    rc, n_bad, bad_rows, _ = s["pk"].r1cs_check_batch(xs, ws, max_rows, solve=True)
-    assert rc == PM_OK, s["pm"].ctx.last_error()
-    stuck, _ = s["pk"].solve_results(len(xs))
-    return [int(v) for v in n_bad], bad_rows, [int(v) for v in stuck], s["pk"].solved_assignments(len(xs), s["q"].mw)
-
-
-def _completes(s, assignments, partial):
-    want, rows = _rows(s, assignments, partial)
-    n_bad, _, stuck, full = _solve(s, rows)
-    count = len(assignments)
-    assert n_bad == [0] * count and stuck == [NONE] * count, (count, n_bad, stuck)
-    assert np.array_equal(full, want), count
+_cached = key_cache()
 
 
 def _pairs(g, n, bits, i):

@@ -15,37 +15,14 @@ import pytest
 import torch        # noqa: F401  before libpolymath_hip.so is loaded: torch brings its own HIP runtime (tests/ntt_device_child.py)
 
 from oracle.pyref.fields import CURVES
+from witness_solve_helpers import BOTH, NONE, PM_ERR_INVALID_ARG, PM_OK, _full_limbs, _setup, _solve, key_cache
 
 pytestmark = pytest.mark.gpu
 
-PM_OK, PM_ERR_INVALID_ARG, PM_ERR_REMAINDER_NONZERO = 0, 1, 4
-NONE = (1 << 64) - 1
-BOTH = ["bls12_381", "bn254"]
+PM_ERR_REMAINDER_NONZERO = 4
 FORMS = ["ark", "circom"]
 PROOF_LEN = {"bls12_381": 176, "bn254": 128}
-_KEYS = {}
-
-
-def _setup(gpu_ctx, curve, circuit, seed):
-    """circuit: a generator of polymath_amd.circuits, or an (R1CS, instance, witness) triple"""
-    from polymath_amd import circuits as PC, polymath as PM
-    c = CURVES[curve]
-    g = PC.SplitMix64(seed)
-    pm = PM.Polymath(curve, "merlin", ctx=gpu_ctx)
-    x, z = g.fr(c.r), g.fr(c.r)
-    q, inst, wit = pm._synthesize(circuit)
-    pk = pm.setup((q, inst, wit), x, z)
-    return dict(pm=pm, pk=pk, q=q, inst=inst, wit=wit, x=x, z=z, f=pm.field, c=c)
-
-
-def _cached(key, make):
-    if key not in _KEYS:
-        _KEYS[key] = make()
-    return _KEYS[key]
-
-
-def _full_limbs(s, inst, wit):
-    return np.concatenate([s["f"].fr_limbs(inst), s["f"].fr_limbs(wit)]).reshape(-1, 4)
+_cached = key_cache()
 
 
 def _partial_rows(s, circuits, multipliers=False):
@@ -58,15 +35,6 @@ def _partial_rows(s, circuits, multipliers=False):
     partial = want.copy()
     partial[:, unknown] = api.UNKNOWN_LIMBS
     return want, partial
-
-
-def _solve_and_check(s, partial, max_rows=2):
-    m0 = s["q"].m0
-    xs, ws = np.ascontiguousarray(partial[:, :m0]), np.ascontiguousarray(partial[:, m0:])
-    rc, n_bad, rows, _ = s["pk"].r1cs_check_batch(xs, ws, max_rows, solve=True)
-    assert rc == PM_OK, s["pm"].ctx.last_error()
-    stuck, _ = s["pk"].solve_results(len(xs))
-    return [int(v) for v in n_bad], rows, [int(v) for v in stuck], s["pk"].solved_assignments(len(xs), s["q"].mw)
 
 
 def _match_inputs(g, r, n_values, mode):
@@ -93,7 +61,7 @@ def test_match_count(gpu_ctx, curve, form, n_values):
         want, partial = _partial_rows(s, circuits)
         counts = [s["f"].fr_int(row[1]) for row in want]
         assert counts == [{0: n_values, 1: 0, 2: (n_values + 1) // 2}[2 if count == 1 else i % 3] for i in range(count)]
-        n_bad, _, stuck, full = _solve_and_check(s, partial)
+        n_bad, _, stuck, full = _solve(s, partial)
         assert n_bad == [0] * count and stuck == [NONE] * count, (count, n_bad, stuck)
         assert np.array_equal(full, want), count
 
@@ -117,7 +85,7 @@ def test_eq_chain(gpu_ctx, curve, form, depth, bits):
             circuits.append(PC.EqChain(x, PC.eq_chain_targets(x, hits, r), form, bits=bits))
         assert seen == ({True, False} if count > 1 or depth > 1 else {True})
         want, partial = _partial_rows(s, circuits)
-        n_bad, _, stuck, full = _solve_and_check(s, partial)
+        n_bad, _, stuck, full = _solve(s, partial)
         assert n_bad == [0] * count and stuck == [NONE] * count, (count, n_bad, stuck)
         assert np.array_equal(full, want), count
 
@@ -183,7 +151,7 @@ def test_multiplier_given(gpu_ctx, curve, form):
     want, partial = _partial_rows(s, ark, multipliers=True)
     zero_want, _ = _partial_rows(s, [PC.MatchCount(values, key, form) for values, key in inputs])
     assert not np.array_equal(want[0], zero_want[0]) and np.array_equal(want[1], zero_want[1])      # the conventions differ where values match
-    n_bad, _, stuck, full = _solve_and_check(s, partial)
+    n_bad, _, stuck, full = _solve(s, partial)
     assert n_bad == [0] * count and stuck == [NONE] * count and np.array_equal(full, want)
     xs, ws = np.ascontiguousarray(partial[:, :q.m0]), np.ascontiguousarray(partial[:, q.m0:])
     r_as = [[91 + i, 101 + i] for i in range(count)]

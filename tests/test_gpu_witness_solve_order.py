@@ -16,47 +16,12 @@ import pytest
 import torch        # noqa: F401  before libpolymath_hip.so is loaded: torch brings its own HIP runtime (tests/ntt_device_child.py)
 
 from oracle.pyref.fields import CURVES
+from witness_solve_helpers import BOTH, NONE, PM_ERR_INVALID_ARG, PM_OK, _rows, _setup, key_cache
 
 pytestmark = pytest.mark.gpu
 
-PM_OK, PM_ERR_INVALID_ARG = 0, 1
-NONE = (1 << 64) - 1
-BOTH = ["bls12_381", "bn254"]
 PROOF_LEN = {"bls12_381": 176, "bn254": 128}
-_KEYS = {}
-
-
-def _setup(gpu_ctx, curve, circuit, seed):
-    """circuit: a generator of polymath_amd.circuits, or an (R1CS, instance, witness) triple"""
-    from polymath_amd import circuits as PC, polymath as PM
-    c = CURVES[curve]
-    g = PC.SplitMix64(seed)
-    pm = PM.Polymath(curve, "merlin", ctx=gpu_ctx)
-    x, z = g.fr(c.r), g.fr(c.r)
-    q, inst, wit = pm._synthesize(circuit)
-    pk = pm.setup((q, inst, wit), x, z)
-    return dict(pm=pm, pk=pk, q=q, inst=inst, wit=wit, x=x, z=z, f=pm.field, c=c)
-
-
-def _cached(key, make):
-    if key not in _KEYS:
-        _KEYS[key] = make()
-    return _KEYS[key]
-
-
-def _full_limbs(s, inst, wit):
-    return np.concatenate([s["f"].fr_limbs(inst), s["f"].fr_limbs(wit)]).reshape(-1, 4)
-
-
-def _rows(s, assignments, partial):
-    """assignments: [(instance, witness)] as ints; partial: (instance, witness) with None where the device solves
-    -> (want, partial rows): count x (m0 + mw) x 4 words"""
-    from polymath_amd import api
-    want = np.stack([_full_limbs(s, inst, wit) for inst, wit in assignments])
-    unknown = np.array([v is None for v in list(partial[0]) + list(partial[1])])
-    rows = want.copy()
-    rows[:, unknown] = api.UNKNOWN_LIMBS
-    return want, rows
+_cached = key_cache()
 
 
 def _solve(s, rows, max_rows=2):

@@ -24,3 +24,7 @@ def test_solve_bits_host_selftest(tmp_path, flags):
     # accepted 12 + 4 x 2 + 3, widest 4, refused 1 + 3 + 1 + 2 + 1 + 2 + 6 + 1, equivalence 2 + 2 + 2 + 2
     for curve in ("bls12_381", "bn254"):
         assert "%s: 0 failures of 52" % curve in out.stdout.splitlines(), out.stdout
+    # every plan the program builds, error plans with their messages included, folded field by field into one FNV-1a digest per curve
+    # (tests/native/solve_selftest.hpp); recorded from the planner as it stood before its rules were stated once
+    for curve, digest in (("bls12_381", "ccb5d308250dc75c"), ("bn254", "dfd81707c06e053c")):
+        assert "%s: 34 plans, digest %s" % (curve, digest) in out.stdout.splitlines(), out.stdout

@@ -30,3 +30,7 @@ def test_solve_divrem_host_selftest(tmp_path, flags):
     # corpus 3 x (2 x 2 + 1 or 0 + rounds + 4 x 2 x (4 + rounds)) with rounds 2, 2, 2, + 2; edges 1 + 18 + 2
     for curve in ("bls12_381", "bn254"):
         assert "%s: 0 failures of 297" % curve in out.stdout.splitlines(), out.stdout
+    # every plan the program builds, error plans with their messages included, folded field by field into one FNV-1a digest per curve
+    # (tests/native/solve_selftest.hpp); recorded from the planner as it stood before its rules were stated once
+    for curve, digest in (("bls12_381", "15edcd0305e2ab0f"), ("bn254", "2b08190d2b3575d7")):
+        assert "%s: 131 plans, digest %s" % (curve, digest) in out.stdout.splitlines(), out.stdout

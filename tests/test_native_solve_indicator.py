@@ -29,3 +29,7 @@ def test_solve_indicator_host_selftest(tmp_path, flags):
     # corpus 3 x (2 x 2 + 1 + rounds + 1 + 1 + rounds + 4 x 2 x (4 + rounds)) with rounds 3, 2, 2; waiting guard 6
     for curve in ("bls12_381", "bn254"):
         assert "%s: 0 failures of 324" % curve in out.stdout.splitlines(), out.stdout
+    # every plan the program builds, error plans with their messages included, folded field by field into one FNV-1a digest per curve
+    # (tests/native/solve_selftest.hpp); recorded from the planner as it stood before its rules were stated once
+    for curve, digest in (("bls12_381", "20a758e1ba1931e3"), ("bn254", "a5498f6e2cbf9e25")):
+        assert "%s: 136 plans, digest %s" % (curve, digest) in out.stdout.splitlines(), out.stdout

@@ -28,3 +28,7 @@ def test_solve_iszero_host_selftest(tmp_path, flags):
     # accepted 12 + 1 + 6 x (1 + 2 x 2), interleaved 2 x (5 + 4), placements 8 x (1 + 2 + 2), refused 10 x 2 + 2 + 2 + 1, equivalence 1 + 2 + 2 + 1
     for curve in ("bls12_381", "bn254"):
         assert "%s: 0 failures of 132" % curve in out.stdout.splitlines(), out.stdout
+    # every plan the program builds, error plans with their messages included, folded field by field into one FNV-1a digest per curve
+    # (tests/native/solve_selftest.hpp); recorded from the planner as it stood before its rules were stated once
+    for curve, digest in (("bls12_381", "3c43cd46e0d95347"), ("bn254", "3c43cd46e0d95347")):
+        assert "%s: 57 plans, digest %s" % (curve, digest) in out.stdout.splitlines(), out.stdout

@@ -32,3 +32,7 @@ def test_solve_order_host_selftest(tmp_path, flags):
         assert "%s: 0 failures of 608" % curve in out.stdout.splitlines(), out.stdout
         times = re.search(r"^%s: chain of 2\^18 rows: build_plan in order ([0-9.]+) ms, build_plan_any_order reversed ([0-9.]+) ms" % curve, out.stdout, flags=re.M)
         assert times and float(times.group(2)) <= 50 * float(times.group(1)), out.stdout
+    # every plan the program builds, error plans with their messages included, folded field by field into one FNV-1a digest per curve
+    # (tests/native/solve_selftest.hpp); recorded from the planner as it stood before its rules were stated once
+    for curve, digest in (("bls12_381", "4977861ae1ae1509"), ("bn254", "e410dff4f49be2be")):
+        assert "%s: 199 plans, digest %s" % (curve, digest) in out.stdout.splitlines(), out.stdout

@@ -18,3 +18,7 @@ def test_solve_plan_host_selftest(tmp_path):
     # mimc3 6, diagonal 4 x 3, random gates 3 x 4, kinds 8, errors 8
     for curve in ("bls12_381", "bn254"):
         assert "%s: 0 failures of 46" % curve in out.stdout.splitlines(), out.stdout
+    # every plan the program builds, error plans with their messages included, folded field by field into one FNV-1a digest per curve
+    # (tests/native/solve_selftest.hpp); recorded from the planner as it stood before its rules were stated once
+    for curve, digest in (("bls12_381", "52d217478e3503b8"), ("bn254", "039a04815ec996e7")):
+        assert "%s: 16 plans, digest %s" % (curve, digest) in out.stdout.splitlines(), out.stdout

@@ -52,7 +52,7 @@ def test_the_pinned_counts_still_hold():
     assert [int(v) for v in re.findall(r"=\s*(\d+)", status)] == list(range(10))
     from polymath_amd import api
     assert len(api.EXPORTS) == 70 and (api.ASSIGNMENT_DEVICE, api.ASSIGNMENT_SOLVE) == (1, 2) and len(api.OPTIONS) == 9
-    for name in ("solve.hip", "divrem.cuh"):
+    for name in ("solve.hip", "solve_steps.cuh", "divrem.cuh"):
         assert "getenv" not in open(os.path.join(ROOT, "polymath_amd", "csrc", name)).read()
     assert "getenv" not in open(os.path.join(ROOT, "polymath_amd", "host", "solve_plan.hpp")).read()
 
