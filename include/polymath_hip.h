@@ -301,7 +301,8 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  * the two below is PM_ERR_INVALID_ARG.  The other entry points with such an argument (pm_host_prove_sharded, the phases) do not solve.
  *   PM_ASSIGNMENT_SOLVE: the caller supplies only the values it chooses; every Fr of x or w whose four words are UINT64_MAX (>= r on
  *     both curves, so never a field element; or the quotient marker, which differs in the lowest bit: "a division row" below; or
- *     the indicator marker, which differs in bit 64: "an indicator row" below) is
+ *     the indicator marker, which differs in bit 64: "an indicator row" below; or the square-root marker, which differs in bit 192:
+ *     "a square-root row" below) is
  *     UNKNOWN and is computed on the device first, by forward propagation through the key's
  *     resident constraint rows (first-entry rule applied, as the prover and pm_r1cs_check read them; a stored entry with a zero
  *     coefficient names no variable).  The call then runs on the completed assignment and its results are, bit for bit, those of the
@@ -360,6 +361,27 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  *                                                unknown; no refusal is added.  Not handled: a hit value other than 1, a non-empty C_r,
  *                                                a known rest beside u, inferring indicators without the marker, sharded keys,
  *                                                per-assignment patterns
+ *     a square-root row                       -- ONE row whose only unknown u the caller marks with PM_HINT_SQRT_MARKER (below) and which names
+ *                                                u exactly twice: as the ONLY non-zero entry (ka, u) of A_r and as the ONLY non-zero entry
+ *                                                (kb, u) of B_r.  C_r names no unknown and does not name u; it may be empty.  (Stored zero
+ *                                                coefficients name nothing, as everywhere.)  circom's  x <-- sqrt(u); x*x === u  (circomlib's
+ *                                                pointbits.circom, Bits2Point_Strict) and arkworks' sqrt witness in point decompression.
+ *                                                ONE step; with c = (C z)_r / (ka kb):
+ *                                                  c a square, 0 included:  z_u = the root whose canonical integer is the smaller of the
+ *                                                                           pair, <= (r - 1) / 2: what circom's sqrt returns
+ *                                                  c a non-residue:         the assignment is STUCK at row r (zero is stored)
+ *                                                a Tonelli-Shanks of fixed trip count per row and assignment.  The rows do not determine the
+ *                                                value (-u satisfies them too), so it is a hint and the marker is explicit, as circom's <--
+ *                                                is: nothing is inferred -- with the plain marker on u the row is refused in matrix order
+ *                                                and waits, in any order, for a row that determines u, as it always did; no plan, message or
+ *                                                word changes and no refusal is added.  The square-root marker has meaning in that position
+ *                                                only: a column that carries it and is the single unknown of an ordinary row, named once,
+ *                                                is solved by that row, and named beside other unknowns it is a plain unknown.  In any row
+ *                                                order such a row waits on the unknowns of C_r like any other row and acts when u is the
+ *                                                only one left.  Not handled: a known rest beside u on either side ((u + k)(u + k) = c),
+ *                                                u in C_r (a general quadratic), the larger root or arkworks' unspecified choice of root (a
+ *                                                caller who wants either supplies u itself), inferring a square root without the marker,
+ *                                                sharded keys, per-assignment patterns
  *     an is-zero pair                         -- the two rows every equality test compiles to, with two fresh unknowns m (the multiplier)
  *                                                and b (the flag):  arkworks  (a - b) mult = neq ; (a - b) (1 - neq) = 0
  *                                                                   circom    (-in) inv = out - 1 ; in out = 0
@@ -403,11 +425,11 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  *   per-assignment patterns, sharded keys.
  *   PM_ERR_INVALID_ARG, pm_last_error naming the row or column, nothing computed and no output written: an unsolvable row, a marked
  *   column that no row determines, a marker at column 0, a sharded key, and -- in a batch -- an assignment that does not mark the
- *   columns assignment 0 marks, or marks one with the other marker (any two of the three markers differ; the first differing (assignment, column) is named; a kernel
+ *   columns assignment 0 marks, or marks one with the other marker (any two of the four markers differ; the first differing (assignment, column) is named; a kernel
  *   compares them).
  *   At run time a step that would divide by zero (Bz = 0 with u in A) leaves that assignment STUCK, even where Cz = 0 too (the value
  *   is then undetermined), and so does a decomposition whose t is 2^k or more (no boolean solution; its k values are stored as
- *   zero) and a division row whose divisor is zero (both values are stored as zero): its other solved values are undefined, its neighbours are not affected, and its smallest stuck row is
+ *   zero) and a division row whose divisor is zero (both values are stored as zero) and a square-root row whose value is a non-residue (zero is stored): its other solved values are undefined, its neighbours are not affected, and its smallest stuck row is
  *   reported (a 64-bit atomic minimum: the same word on every run, since everything downstream of a stuck row has a larger index).
  *   Where the rows were reordered that is not so -- a row that reads the stored zero may stick too, at a smaller index -- and the row
  *   reported is the ROOT CAUSE: among the stuck rows the one of lowest dependency level, then smallest index, which read only valid
@@ -429,10 +451,15 @@ typedef enum pm_assignment_flags {
  * unknown, and it is the Euclidean quotient of its division row (the rule above); everywhere else it means what PM_UNKNOWN_WORDS means.
  * A third marker, PM_HINT_INDICATOR_WORDS (2^256 - 1 - 2^64: the top word is all ones, so it is >= r on both curves as well): the
  * value is unknown, and it is the INDICATOR of its guard row ("an indicator row" above), 1 where the guard's known side is zero,
- * else 0; everywhere else it means what PM_UNKNOWN_WORDS means.  A value with both bit 0 and bit 64 clear is no marker. */
+ * else 0; everywhere else it means what PM_UNKNOWN_WORDS means.  A value with both bit 0 and bit 64 clear is no marker.
+ * A fourth marker, PM_HINT_SQRT_MARKER (2^256 - 1 - 2^192: the top word is 0xFFFF...FE, so it is >= r on both curves as well): the
+ * value is unknown, and it is the SMALLER SQUARE ROOT of its square-root row ("a square-root row" above), the root whose canonical
+ * integer is <= (r - 1) / 2; everywhere else it means what PM_UNKNOWN_WORDS means.  Exactly one of the bits 0, 64 and 192 may be
+ * clear: a value that clears bit 192 together with bit 0 or bit 64 is no marker. */
 #define PM_UNKNOWN_WORDS { UINT64_MAX, UINT64_MAX, UINT64_MAX, UINT64_MAX }
 #define PM_UNKNOWN_QUOTIENT_WORDS { UINT64_MAX - 1, UINT64_MAX, UINT64_MAX, UINT64_MAX }
 #define PM_HINT_INDICATOR_WORDS { UINT64_MAX, UINT64_MAX - 1, UINT64_MAX, UINT64_MAX }
+#define PM_HINT_SQRT_MARKER { UINT64_MAX, UINT64_MAX, UINT64_MAX, UINT64_MAX - 1 }
 
 /* Whole create_proof_with_assignment (prover.rs:66-237) for an UNSHARDED key, transcript included: the three
  * phases above plus the host glue between them (compute_x1 / compute_x2, common.rs:21-71; pi and c at x1,

@@ -44,6 +44,7 @@ ASSIGNMENT_DEVICE, ASSIGNMENT_SOLVE = 1, 2
 UNKNOWN_LIMBS = (0xFFFFFFFFFFFFFFFF,) * 4     # an Fr of x / w / instance_host with these words is unknown under ASSIGNMENT_SOLVE
 QUOTIENT_LIMBS = (0xFFFFFFFFFFFFFFFE,) + (0xFFFFFFFFFFFFFFFF,) * 3     # PM_UNKNOWN_QUOTIENT_WORDS: unknown, and the Euclidean quotient of a division row
 INDICATOR_LIMBS = (0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFE, 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFF)     # PM_HINT_INDICATOR_WORDS: unknown, and the indicator of its guard row
+SQRT_LIMBS = (0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFE)     # PM_HINT_SQRT_MARKER: unknown, and the smaller square root of its square-root row
 NOT_STUCK = 0xFFFFFFFFFFFFFFFF                # first word of a tap-9 record of an assignment that completed
 TIMING_SLOTS = ["witness_map", "ntt", "poly", "msm_sort", "msm_accumulate", "msm_reduce", "msm_total", "phase"]
 

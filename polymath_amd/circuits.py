@@ -4,9 +4,10 @@
 own (RangeCheck, ArxDemo) and two that branch on equality (MatchCount, EqChain: is-zero pairs in arkworks' and in circom's form) whose
 witnesses the device completes from the inputs (PM_ASSIGNMENT_SOLVE), and two that divide integers (DivRem,
 ModChain: Euclidean division rows, whose quotients partial() marks QUOTIENT), and two that read a table at a signal (Decoder,
-TableWalk: circomlib's one-hot decoder, whose outputs partial() marks INDICATOR); Reordered emits any of them with its rows in another
+TableWalk: circomlib's one-hot decoder, whose outputs partial() marks INDICATOR), and two that take square roots (SquareRoots,
+EdwardsDecompress: point decompression on Jubjub / Baby Jubjub, whose roots partial() marks SQRT); Reordered emits any of them with its rows in another
 order, which the solver's any-order planner accepts."""
-from .polymath import INDICATOR, QUOTIENT, ConstraintSystem, Field, LimbCircuit, R1CS
+from .polymath import INDICATOR, QUOTIENT, SQRT, ConstraintSystem, Field, LimbCircuit, R1CS, small_sqrt
 
 SPLITMIX_SEED = 0x706F6C796D617468  # "polymath"
 _M64 = (1 << 64) - 1
@@ -529,6 +530,135 @@ def table_walk_native(table, start, steps, r):
     for _ in range(steps):
         idx = table[idx] % r if idx < len(table) else 0
     return idx
+
+
+class _PartialRoots(_Partial):
+    """_Partial for circuits with square-root rows  u * u = c  (circom's  x <-- sqrt(c); x*x === c): partial() marks every root SQRT --
+    the explicit "this unknown is the smaller square root of its row" that the solver asks for, since -u satisfies the row too."""
+
+    def _root(self, cs, c, c_v):
+        """the witness u = the smaller root of c_v (0 where c_v is a non-residue: the row has no solution then and the device reports
+        it as stuck) with its row  u * u = c.  -> (u, u_v)"""
+        u_v = small_sqrt(cs.r, c_v) or 0
+        self._roots.append(len(cs.witness))
+        u = cs.new_witness_variable(u_v)
+        cs.enforce_constraint([(1, u)], [(1, u)], [(1, c)])
+        return u, u_v
+
+    def partial(self, r):
+        instance, witness = super().partial(r)
+        for j in self._roots:
+            witness[j] = SQRT
+        return instance, witness
+
+
+class SquareRoots(_PartialRoots):
+    """N independent square roots: per value the given witness c_i, the witness u_i and the row  u_i * u_i = c_i ; the public input
+    is sum u_i.  ONE dependency level of N square-root rows, then one ordinary step.  Witness layout: c_i, u_i per value.  The caller
+    chooses the c_i; a non-residue has no assignment."""
+
+    def __init__(self, values):
+        self.values = list(values)
+
+    def generate_constraints(self, cs):
+        self._chosen, self._roots = [], []
+        total, total_v = [], 0
+        for value in self.values:
+            c = self._given(cs, value % cs.r)
+            u, u_v = self._root(cs, c, value % cs.r)
+            total.append((1, u))
+            total_v += u_v
+        out = cs.new_input_variable(total_v % cs.r)
+        cs.enforce_constraint(total, [(1, ConstraintSystem.ONE)], [(1, out)])
+
+    def native(self, r):
+        """-> (instance, witness) on Python integers, without generating a row: c_i and its smaller root per value"""
+        witness, total = [], 0
+        for value in self.values:
+            u = small_sqrt(r, value % r) or 0
+            witness += [value % r, u]
+            total += u
+        return [1, total % r], witness
+
+
+# the twisted Edwards curves  a x^2 + y^2 = 1 + d x^2 y^2  over the two scalar fields: Jubjub over BLS12-381's, Baby Jubjub over BN254's
+EDWARDS = {
+    0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001: ("jubjub", -1, 0x2A9318E74BFA2B48F5FD9207E6BD7FD4292D7F6D37579D2601065FD6D6343EB1),
+    0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001: ("baby_jubjub", 168700, 168696),
+}
+
+
+class EdwardsDecompress(_PartialRoots):
+    """Point decompression on the twisted Edwards curve of the field (EDWARDS: Jubjub on BLS12-381, Baby Jubjub on BN254), the shape of
+    circomlib's Bits2Point_Strict and of arkworks' decompression gadget.  Per point, from the given witnesses y and sign:
+        y * y = y2
+        (a - d y2) * u = 1 - y2                   an ordinary dividing step: u = x^2
+        x0 * x0 = u                               the square-root row; x0 is marked SQRT
+        sign * (1 - sign) = 0                     a check row: sign is given
+        x0 * (1 - 2 sign) = x                     the root with the wanted sign
+        x0 * 1 = sum 2^i b_i                      bitlength(r) - 1 boolean witnesses, booleanity rows first: the small root always
+                                                  fits, so the row never sticks
+    and  (sum x) * 1 = out  with out the public input.  The caller chooses the y (edwards_ys draws values for which u is a residue;
+    another y has no assignment) and the signs."""
+
+    def __init__(self, ys, signs):
+        assert len(ys) == len(signs) and len(ys) >= 1 and all(sg in (0, 1) for sg in signs)
+        self.ys, self.signs = list(ys), list(signs)
+
+    def generate_constraints(self, cs):
+        self._chosen, self._roots = [], []
+        one, r = ConstraintSystem.ONE, cs.r
+        _, a, d = EDWARDS[r]
+        nbits = r.bit_length() - 1
+        total, total_v = [], 0
+        for y_v, sign_v in zip(self.ys, self.signs):
+            y_v %= r
+            y, sign = self._given(cs, y_v), self._given(cs, sign_v)
+            y2_v = y_v * y_v % r
+            y2 = cs.new_witness_variable(y2_v)
+            cs.enforce_constraint([(1, y)], [(1, y)], [(1, y2)])
+            den_v = (a - d * y2_v) % r
+            u_v = (1 - y2_v) * pow(den_v, r - 2, r) % r
+            u = cs.new_witness_variable(u_v)
+            cs.enforce_constraint([(a, one), (-d, y2)], [(1, u)], [(1, one), (-1, y2)])
+            x0, x0_v = self._root(cs, u, u_v)
+            cs.enforce_constraint([(1, sign)], [(1, one), (-1, sign)], [])
+            x_v = (r - x0_v) % r if sign_v else x0_v
+            x = cs.new_witness_variable(x_v)
+            cs.enforce_constraint([(1, x0)], [(1, one), (-2, sign)], [(1, x)])
+            cs.enforce_constraint([(1, x0)], [(1, one)], _weighted(_new_bits(cs, x0_v, nbits)))
+            total.append((1, x))
+            total_v += x_v
+        out = cs.new_input_variable(total_v % r)
+        cs.enforce_constraint(total, [(1, one)], [(1, out)])
+
+    def native(self, r):
+        """-> (instance, witness) on Python integers, without generating a row: per point y, sign, y2, u, x0, x and the bits of x0,
+        least significant first (what generate_constraints writes)"""
+        _, a, d = EDWARDS[r]
+        witness, total = [], 0
+        for y, sign in zip(self.ys, self.signs):
+            y %= r
+            y2 = y * y % r
+            u = (1 - y2) * pow((a - d * y2) % r, r - 2, r) % r
+            x0 = small_sqrt(r, u) or 0
+            x = (r - x0) % r if sign else x0
+            witness += [y, sign, y2, u, x0, x] + [(x0 >> i) & 1 for i in range(r.bit_length() - 1)]
+            total += x
+        return [1, total % r], witness
+
+
+def edwards_ys(r, count, seed=SPLITMIX_SEED):
+    """`count` values y that are the ordinate of a point of the field's Edwards curve (EDWARDS): drawn from SplitMix64(seed), kept
+    where a - d y^2 != 0 and (1 - y^2) / (a - d y^2) is a square"""
+    _, a, d = EDWARDS[r]
+    g, ys = SplitMix64(seed), []
+    while len(ys) < count:
+        y = g.fr(r)
+        den = (a - d * y * y) % r
+        if den and small_sqrt(r, (1 - y * y) * pow(den, r - 2, r) % r) is not None:
+            ys.append(y)
+    return ys
 
 
 def row_order(nr, order, blocks=1):

@@ -2,7 +2,7 @@
 // indicator step's value (indicator_of; solve_steps.cuh: solve_indicator) and the Euclidean division of canonical residues, for the
 // witness solver's division step (solve.hip: k_solve_pattern; solve_steps.cuh: solve_divrem).  ONE set of routines
 // for device and host: the kernels call them per (step, assignment) through the step bodies of solve_steps.cuh, and the CPU
-// self-tests (tests/native/solve_selftest.hpp, the rig of the six solve_*_selftest.cpp) execute plans through the same bodies on the
+// self-tests (tests/native/solve_selftest.hpp, the rig of the solve_*_selftest.cpp programs) execute plans through the same bodies on the
 // host field type.
 //
 // Restoring shift-subtract on four 64-bit words with a FIXED trip count of 256: the 512-bit register (hi : lo) starts as (0 : a),
@@ -20,12 +20,16 @@ namespace pm {
 // the quotient marker (the same with the lowest bit clear), 3 for the indicator marker (the same with bit 64 clear), else 0 -- with
 // both bits clear as well.  All three are >= r on both curves, so never a field element.  THE marker test: the solver's kernels, the
 // host glue (host_prove.hip) and the device glue (prove_glue.hip) all ask this routine, on eight 32-bit limbs, little-endian.
+// 4 for the square-root marker (every bit set except bit 192, the lowest bit of the top word; that word is 0xFFFF...FE, so the value
+// is >= r on both curves as well): exactly ONE of the bits 0, 64 and 192 may be clear, and any two of them clear is no marker.
 PM_HD uint8_t marker_byte_limbs(const uint32_t l[8]) {
-    uint32_t a = (l[0] | 1u) & l[1] & (l[2] | 1u);
-#pragma unroll
-    for (int i = 3; i < 8; ++i) a &= l[i];
-    const uint32_t low = l[0] & 1u, mid = l[2] & 1u;
-    return a != ~0u ? 0 : (low & mid) ? pmsolve::PATTERN_UNKNOWN : mid ? pmsolve::PATTERN_QUOTIENT : low ? pmsolve::PATTERN_INDICATOR : 0;
+    uint32_t a = (l[0] | 1u) & l[1] & (l[2] | 1u) & l[3] & l[4] & l[5] & (l[6] | 1u) & l[7];
+    const uint32_t low = l[0] & 1u, mid = l[2] & 1u, high = l[6] & 1u;
+    if (a != ~0u) return 0;
+    return (low & mid & high) ? pmsolve::PATTERN_UNKNOWN
+         : (mid & high)       ? pmsolve::PATTERN_QUOTIENT
+         : (low & high)       ? pmsolve::PATTERN_INDICATOR
+         : (low & mid)        ? pmsolve::PATTERN_SQRT : 0;
 }
 template <class P>
 PM_HD uint8_t marker_byte(const Fp<P> &v) {

@@ -2,11 +2,11 @@
 // (include/polymath_hip.h), so that a caller supplies only the values it chooses and the library computes the rest
 // before it checks or proves.  The PLAN -- which row determines which column, in which order -- is host work, done once per (key,
 // pattern) by host/solve_plan.hpp; what ONE step does to ONE assignment (solve_step, solve_bits, solve_iszero, solve_divrem,
-// solve_indicator, the dispatch solve_any, the inverses' solve_inverse, and the records a plan becomes: solve_records) is
+// solve_indicator, solve_sqrt, the dispatch solve_any, the inverses' solve_inverse, and the records a plan becomes: solve_records) is
 // solve_steps.cuh, text that the CPU self-tests run as well; this file is the kernels that call it and the host driver,
 // assignment = grid y (or the lane, in the chain kernel):
 //   k_solve_pattern   one lane per (column, assignment): the unknown pattern of assignment 0 (a byte per column: 1 the unknown
-//                     marker, 2 the quotient marker, 3 the indicator marker); every other assignment is compared with it, byte for byte, and the first
+//                     marker, 2 the quotient marker, 3 the indicator marker, 4 the square-root marker); every other assignment is compared with it, byte for byte, and the first
 //                     differing (assignment, column) lowers one word
 //   k_solve_inv       one lane per step, once per plan: 1 / coefficient of the step's unknown (a division row: 1 / cq); two more
 //                     lanes per is-zero pair: 1 / cm and 1 / cb of its opener; an indicator step needs none and its record is left alone
@@ -19,18 +19,22 @@
 //                     integer division each (divrem.cuh: a fixed trip count, so a wave does not diverge on operand size)
 //   k_solve_indicator the indicator rows of a wide level, one lane per (step, assignment) as well: one dot product over the guard's
 //                     known side, a zero test and one store of field one under a mask; no division
+//   k_solve_sqrt      the square-root rows of a wide level, one lane per (step, assignment) as well: one dot product over C_r, one
+//                     multiplication by 1 / (ka kb) and one constant-time Tonelli-Shanks (sqrt.cuh: a fixed trip count, so a wave does
+//                     not diverge on the operand); a non-residue is stuck at the row
 //   k_solve_chain     a run of consecutive NARROW levels: one lane per assignment walks the run's steps in plan order.  A lane
 //                     reads back only its own stores: no barriers, no fences.  The MiMC shape (depth 644, width 1) is one such run
 //                     and the batch is its parallel dimension.
 // The solving kernels exist twice: DIV = false for ranges of kind-C steps only, DIV = true for ranges with kind-A / kind-B steps,
 // or is-zero pairs, which call inverse<P> (a Fermat chain) -- the plan sorts a level by kind, so kind-C ranges do not carry its
 // registers, and the is-zero step and the division step (a dividing one by the plan's count, for 1 / cq) exist in the DIV = true
-// chain only.  The indicator step does not divide: it is a branch of BOTH chain instantiations.
+// chain only.  The indicator step does not divide: it is a branch of BOTH chain instantiations.  The square-root step (a dividing one
+// by the plan's count, for 1 / (ka kb)) exists in the DIV = true chain only.
 //   k_solve_stuck_row after the launches of a REORDERED plan (build_plan_any_order found a dependency order that is not the matrix
 //                     order): one lane per assignment turns the stuck word's (level, row) into the row
 // A step that would divide by zero stores zero and lowers the assignment's stuck word to its row (64-bit atomic minimum: the same
 // word on every run); so does a decomposition whose value has no k-bit form, in all its k columns, and a division row whose
-// divisor is zero, in both its columns.  In matrix order everything
+// divisor is zero, in both its columns, and a square-root row whose value is a non-residue.  In matrix order everything
 // downstream of a stuck row has a larger row, so the minimum is the root cause.  Under a reordered plan that is false -- a step that
 // reads the stored zero may stick too, at a smaller row -- so the word is lowered to (level << 32) | row there: the minimum is the
 // stuck step of lowest level, then smallest row, which read only valid values, and k_solve_stuck_row leaves its row in the word.  Every other store has one
@@ -126,6 +130,14 @@ __global__ __launch_bounds__(256) void k_solve_indicator(Csr A, Csr B, const Sol
     const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (t >= hi) return;
     solve_indicator<P>(A, B, steps[t], xw + b * ncols);
+}
+
+template <class P>
+__global__ __launch_bounds__(256) void k_solve_sqrt(Csr Cm, const SolveStepDev<P> *__restrict__ steps, uint32_t lo, uint32_t hi, Fp<P> *xw, uint64_t ncols,
+                                                    unsigned long long *stuck) {
+    const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (t >= hi) return;
+    solve_sqrt<P>(Cm, steps[t], xw + b * ncols, StuckWord{stuck + b});
 }
 
 // the step index is the same in every lane: the step record, the pair record, the row's CSR metadata and a decomposition's column
@@ -234,11 +246,12 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
         ctx->err = "pm solve: " + sv.plan.message;
         return PM_ERR_INVALID_ARG;
     }
-    // the DIV = false kernels have no is-zero step and no division step in them: a range with one must be a dividing one
+    // the DIV = false kernels have no is-zero step, no division step and no square-root step in them: a range with one must be a dividing one
     for (const pmsolve::Launch &l : sv.plan.launches)
         for (uint32_t t = l.lo; t < l.hi && !l.divides; ++t)
-            if (sv.plan.steps[t].kind == pmsolve::KIND_ISZERO || sv.plan.steps[t].kind == pmsolve::KIND_DIVREM) {
-                ctx->err = std::string("pm solve: the plan puts the ") + (sv.plan.steps[t].kind == pmsolve::KIND_ISZERO ? "is-zero pair" : "division") + " of row " +
+            if (sv.plan.steps[t].kind == pmsolve::KIND_ISZERO || sv.plan.steps[t].kind == pmsolve::KIND_DIVREM || sv.plan.steps[t].kind == pmsolve::KIND_SQRT) {
+                ctx->err = std::string("pm solve: the plan puts the ") +
+                           (sv.plan.steps[t].kind == pmsolve::KIND_ISZERO ? "is-zero pair" : sv.plan.steps[t].kind == pmsolve::KIND_SQRT ? "square root" : "division") + " of row " +
                            std::to_string(sv.plan.steps[t].row) + " into a launch that does not divide";
                 return PM_ERR_STATE;
             }
@@ -299,7 +312,8 @@ int solve_group(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t 
                 else hipLaunchKernelGGL((k_solve_chain<P, false>), grid, block, 0, st, A, B, Cm, steps, bit_cols, pairs, divs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
             } else {
                 const dim3 grid(nblk(l.hi - l.lo), (unsigned)g), block(256);
-                if (l.indicator) hipLaunchKernelGGL((k_solve_indicator<P>), grid, block, 0, st, A, B, steps, l.lo, l.hi, d_xw, ncols);
+                if (l.sqrt) hipLaunchKernelGGL((k_solve_sqrt<P>), grid, block, 0, st, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck);
+                else if (l.indicator) hipLaunchKernelGGL((k_solve_indicator<P>), grid, block, 0, st, A, B, steps, l.lo, l.hi, d_xw, ncols);
                 else if (l.divrem) hipLaunchKernelGGL((k_solve_divrem<P>), grid, block, 0, st, A, B, Cm, steps, divs, l.lo, l.hi, d_xw, ncols, stuck);
                 else if (l.iszero) hipLaunchKernelGGL((k_solve_iszero<P>), grid, block, 0, st, A, B, Cm, steps, pairs, l.lo, l.hi, d_xw, ncols);
                 else if (l.bits && l.divides) hipLaunchKernelGGL((k_solve_bits<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck);

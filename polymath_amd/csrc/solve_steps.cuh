@@ -13,6 +13,7 @@
 #include "../host/solve_plan.hpp"
 #include "divrem.cuh"
 #include "field.cuh"
+#include "sqrt.cuh"
 
 namespace pm {
 
@@ -26,6 +27,8 @@ struct SolveStepDev {
                                      // kind == KIND_DIVREM: pos / col = the quotient's entry, inv = 1 / cq, bits = its SolveDivDev
                                      // kind == KIND_INDICATOR: pos / col = the indicator's entry, bits = 1: it lies in B_r and K = A_r,
                                      //                         0: the other way round; inv is not set
+                                     // kind == KIND_SQRT: pos / col = the root's entry in A_r, bits = the offset of its entry in B_r from
+                                     //                    that row's start, inv = 1 / (ka kb)
     Fp<P> inv;                       // 1 / coefficient (solve_inverse)
     uint32_t level, pad;             // a stuck step lowers the stuck word to (level << 32) | row; level is 0 unless the plan is reordered
 };
@@ -65,7 +68,7 @@ inline SolveRecords<P> solve_records(const pmsolve::Plan &plan) {
         SolveStepDev<P> &d = rec.steps[t];
         d.pos = s.pos; d.row = s.row; d.col = s.bits ? s.cols_off : s.col; d.kind = s.kind; d.bits = s.bits;
         d.level = plan.reordered ? s.level : 0;
-        if (s.kind == pmsolve::KIND_INDICATOR) d.bits = s.cols_off;
+        if (s.kind == pmsolve::KIND_INDICATOR || s.kind == pmsolve::KIND_SQRT) d.bits = s.cols_off;
         if (s.kind == pmsolve::KIND_DIVREM) {
             const pmsolve::DivRow &row = plan.divs[s.cols_off];
             d.bits = (uint32_t)rec.divs.size();
@@ -83,7 +86,7 @@ inline SolveRecords<P> solve_records(const pmsolve::Plan &plan) {
     return rec;
 }
 
-// any of the three markers (divrem.cuh: marker_byte)
+// any of the four markers (divrem.cuh: marker_byte)
 template <class P>
 PM_HD bool is_marker(const Fp<P> &v) {
     return marker_byte<P>(v) != 0;
@@ -97,11 +100,18 @@ PM_HD const pmsolve::Csr &matrix_of(uint32_t kind, const pmsolve::Csr &A, const 
 PM_HD uint32_t matrix_kind(uint32_t kind) { return kind >= pmsolve::KIND_BITS_C ? kind - pmsolve::KIND_BITS_C : kind; }
 
 // Inverse t of a plan's count + 2 n_pairs: 1 / coefficient of step t's unknown (a division row: 1 / cq), and for t >= count 1 / cm
-// and 1 / cb of an is-zero pair's opener; an indicator step needs none and its record is left alone.
+// and 1 / cb of an is-zero pair's opener; an indicator step needs none and its record is left alone.  A square-root step: 1 / (ka kb),
+// the product of the root's two coefficients, both found from the step record alone.
 template <class P>
 PM_HD void solve_inverse(const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsolve::Csr &Cm, SolveStepDev<P> *steps, uint64_t count, SolvePairDev<P> *pairs,
                          const SolveDivDev *divs, uint64_t t) {
     if (t < count && steps[t].kind == pmsolve::KIND_INDICATOR) return;      // no inverse: the record stays as the host wrote it
+    if (t < count && steps[t].kind == pmsolve::KIND_SQRT) {
+        const Fp<P> ka = *(const Fp<P> *)(A.val + 4 * steps[t].pos), kb = *(const Fp<P> *)(B.val + 4 * (B.rowptr[steps[t].row] + steps[t].bits));
+        const Fp<P> coef = mul<P>(ka, kb);
+        steps[t].inv = coef.eq(Fp<P>::one()) ? coef : inverse<P>(coef);
+        return;
+    }
     const Fp<P> *at;
     Fp<P> *out;
     if (t < count) {                 // an is-zero step's own entry is the flag's, in the closer's A or B; a division step's the quotient's
@@ -263,6 +273,18 @@ PM_HD void solve_indicator(const pmsolve::Csr &A, const pmsolve::Csr &B, const S
     z[s.col] = indicator_of<P>(row_dot_skip<P>(s.bits ? A : B, z, s.row, SOLVE_NONE));
 }
 
+// one square-root row on one assignment: ka kb z_u^2 = (C z)_r, so with c = (C z)_r / (ka kb)
+//   c a square, 0 included:  z_u = the root whose canonical integer is <= (r - 1) / 2 (sqrt.cuh: fr_sqrt, a fixed trip count)
+//   c a non-residue:         stuck at the row, zero stored
+// C's whole row: it does not name u, and u's sides have no other non-zero entry.  The column still holds its marker.
+template <class P, class Sink>
+PM_HD void solve_sqrt(const pmsolve::Csr &Cm, const SolveStepDev<P> &s, Fp<P> *z, const Sink &stuck) {
+    const Fp<P> c = mul<P>(row_dot_skip<P>(Cm, z, s.row, SOLVE_NONE), s.inv);
+    Fp<P> root = Fp<P>::zero();
+    if (!fr_sqrt<P>(c, &root)) stuck(s);
+    z[s.col] = root;
+}
+
 // One step of a chain, whatever its kind.  A range with an is-zero pair or a division row is a dividing one (the plan says so): the
 // DIV = false body has no such branches.  An indicator row does not divide and is a branch of both.
 template <class P, bool DIV, class Sink>
@@ -275,6 +297,8 @@ PM_HD void solve_any(const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsolve
         if constexpr (DIV) solve_divrem<P>(A, B, Cm, s, divs[s.bits], z, stuck);      // as above
     } else if (s.kind == pmsolve::KIND_INDICATOR) {
         solve_indicator<P>(A, B, s, z);
+    } else if (s.kind == pmsolve::KIND_SQRT) {
+        if constexpr (DIV) solve_sqrt<P>(Cm, s, z, stuck);                            // as above: a dividing range only
     } else if (s.bits) solve_bits<P, DIV>(A, B, Cm, s, bit_cols, z, stuck);
     else solve_step<P, DIV>(A, B, Cm, s, z, stuck);
 }

@@ -2,11 +2,13 @@
 // (DESIGN.md §4.10).  Header-only, no HIP: the library's driver (csrc/solve.hip, through csrc/solve_steps.cuh) and six CPU programs
 // (tests/native/solve_plan_selftest.cpp, solve_bits_selftest.cpp, solve_iszero_selftest.cpp, solve_order_selftest.cpp,
 // solve_divrem_selftest.cpp, solve_indicator_selftest.cpp, through their rig tests/native/solve_selftest.hpp) include the same file.
+// (A seventh program on the same rig, solve_sqrt_selftest.cpp, pins the square-root row below.)
 //
 // Input: the three matrices in CSR form with the first-entry rule already applied (a column occurs at most once per row and
 // matrix: the key's resident matrices are like that), m0 + mw columns and one byte per column, non-zero = unknown (1: unknown;
 // 2: unknown, and a Euclidean quotient -- the caller's second marker, which has meaning in a division row only; 3: unknown, and
-// the indicator of its guard row -- the third marker, which has meaning in an indicator row only).  A stored entry
+// the indicator of its guard row -- the third marker, which has meaning in an indicator row only; 4: unknown, and the smaller square
+// root of its square-root row -- the fourth marker, which has meaning in a square-root row only).  A stored entry
 // whose coefficient is zero names no variable.  Rows are visited ONCE, in matrix order; at row r, with the columns solved so far:
 //   no unknown column                         a check row, skipped
 //   one unknown u, in exactly one of A, B, C  a solve step (kind = the matrix that holds u); u is known from here on
@@ -77,7 +79,28 @@
 //                 by that row as an ordinary step, and named beside other unknowns it is a plain unknown.  No refusal is added.
 //                 Not handled: a hit value other than 1, a non-empty C_r, a known rest beside u, inferring indicators without the
 //                 marker, sharded keys, per-assignment patterns.
-// Without the modulus (nullptr) all five additions are off.
+//   square-root row  ONE row whose only unknown u carries pattern byte 4 (the caller's fourth marker: "the square root of its row") and is
+//                 named exactly twice: as the ONLY non-zero entry (ka, u) of A_r and as the ONLY non-zero entry (kb, u) of B_r; C_r names
+//                 no unknown and does not name u, and may be empty: circom's  x <-- sqrt(u); x*x === u  (circomlib's pointbits.circom,
+//                 Bits2Point_Strict) and arkworks' sqrt witness in point decompression.  ONE step of kind KIND_SQRT at 1 + max level of
+//                 what C_r reads; with c = (C z)_r / (ka kb):
+//                     c a square, 0 included:  z_u = the root whose canonical integer is the smaller of the pair, <= (r - 1) / 2 (what
+//                                              circom's sqrt returns)
+//                     c a non-residue:         stuck at row r, zero stored (the handling of a zero divisor: the stuck word is lowered
+//                                              through the sink, and the root-cause rule applies under a reordered plan)
+//                 The rows do not determine the value (-u satisfies them too): it is a hint, and the marker says so.  Step::pos / col
+//                 name u's entry in A_r, Step::cols_off is the offset of u's entry in B_r from the start of that row; the step's
+//                 inverse is 1 / (ka kb), and a launch that holds such a step is a dividing one.  Byte 4 has meaning in that position
+//                 only: a byte-4 column that is the single unknown of an ordinary row, named once, is solved by that row, and named
+//                 beside other unknowns it is a plain unknown.  With the plain marker on u the row plans, waits and is refused exactly
+//                 as before (u u = ... : ERR_TWO_MATRICES in matrix order; in any order it waits for a row that determines u): no
+//                 plan, message or word changes and no refusal is added.  In the scheduler below such a row waits on the unknowns of
+//                 C_r like any other row and acts when u is the only one left; an opener registered over u (the row x = u * s has that
+//                 shape) was none: it is RELEASED and examined again.
+//                 Not handled: a known rest beside u on either side ((u + k)(u + k) = c), u in C_r (a general quadratic),
+//                 the larger root or arkworks' unspecified choice of root (a caller who wants either supplies u itself),
+//                 inferring a square root without the marker, sharded keys, per-assignment patterns.
+// Without the modulus (nullptr) all five additions are off.  (So is the sixth, the square-root row.)
 //
 // build_plan_any_order drops the matrix order: it runs build_plan, and where that refuses, a WAITING-ROW SCHEDULER examines the rows
 // from a min-heap (at first all of them) against the same column state with the same rules, except that these refusals become waiting:
@@ -90,6 +113,8 @@
 //   a pair-pending column in any other way  the row WAITS (the multiplier beside something else, a second unknown, an opener-shaped
 //                                           row over a pending column)
 //   one unknown, named once                 an ordinary step, or -- byte 3 on it and the indicator shape -- the KIND_INDICATOR step
+//   one unknown, byte 4, named twice, as    the KIND_SQRT step at once; an opener registered over u was none: it is RELEASED and examined
+//   the lone entries of A_r and of B_r      again
 //   one unknown, named several times        booleanity: boolean-pending; any other shape WAITS (a later row may determine the column
 //                                           and this one is a check row then)
 //   two or more unknowns                    a decomposition: the bits step; a division row: its step; the opener shape without the
@@ -108,7 +133,7 @@
 //
 // level(step) = 1 + max level of the columns the row reads (given columns: level 0); a decomposition gives all its columns that
 // level.  The steps come out sorted by level, inside a level by kind (C first: the kinds that divide share a launch; then the
-// decompositions in the same order, then the is-zero pairs, then the division rows, then the indicator rows), stable by row -- one counting sort.  O(nnz + columns), plus k log k per decomposition.
+// decompositions in the same order, then the is-zero pairs, then the division rows, then the indicator rows, then the square-root rows), stable by row -- one counting sort.  O(nnz + columns), plus k log k per decomposition.
 #pragma once
 #include <stdint.h>
 
@@ -124,12 +149,13 @@ namespace pmsolve {
 // z_u = (Az Bz - C_rest) / coef;  (Cz / Bz - A_rest) / coef;  (Cz / Az - B_rest) / coef;  KIND_BITS_x = KIND_BITS_C + x: a decomposition
 // KIND_ISZERO: an is-zero pair, both columns in one step;  KIND_DIVREM: a division row, quotient and remainder in one step
 // KIND_INDICATOR: an indicator row, z_u = [K z == 0]: no division and no inverse
-enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6, KIND_DIVREM = 7, KIND_INDICATOR = 8 };
+// KIND_SQRT: a square-root row, z_u = the smaller root of (C z)_r / (ka kb); its inverse is 1 / (ka kb), so it counts as dividing
+enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6, KIND_DIVREM = 7, KIND_INDICATOR = 8, KIND_SQRT = 9 };
 constexpr uint32_t NUM_KINDS = 7;        // the kinds that need no second marker: what it always counted
 constexpr uint32_t NUM_STEP_KINDS = 8;   // KIND_C .. KIND_DIVREM, the kinds whose value comes from field or integer arithmetic on the row: what it counted when kind 7 came
-constexpr uint32_t NUM_SORT_KINDS = 9;   // all of them, KIND_INDICATOR included: the key width of finish_plan's counting sort
+constexpr uint32_t NUM_SORT_KINDS = 10;  // all of them, KIND_INDICATOR and KIND_SQRT included: the key width of finish_plan's counting sort
 
-constexpr uint8_t PATTERN_UNKNOWN = 1, PATTERN_QUOTIENT = 2, PATTERN_INDICATOR = 3;   // the pattern bytes (0: given)
+constexpr uint8_t PATTERN_UNKNOWN = 1, PATTERN_QUOTIENT = 2, PATTERN_INDICATOR = 3, PATTERN_SQRT = 4;   // the pattern bytes (0: given)
 
 constexpr uint32_t WIDE_STEPS = 32;   // a level of at least this many steps gets launches of its own; narrower ones are walked by one lane per assignment
 
@@ -146,6 +172,7 @@ struct Step {
                                        // an is-zero pair: row = the closer, pos / col = the flag's entry in it, Plan::pairs[cols_off]
                                        // a division row: pos / col = the quotient's entry in A_r or B_r, Plan::divs[cols_off]
                                        // an indicator row: pos / col = the indicator's entry, cols_off = 1: it lies in B_r and K = A_r; 0: the other way round
+                                       // a square-root row: pos / col = the root's entry in A_r, cols_off = the offset of its entry in B_r from that row's start
 };
 
 struct PairRows {     // what an is-zero step needs beside its Step
@@ -165,11 +192,12 @@ struct DivRow {       // what a division step needs beside its Step
 struct Launch {
     uint32_t lo, hi;  // steps [lo, hi) of the sorted list
     uint8_t chain;    // 1: one lane per assignment walks the steps in order; 0: one lane per (step, assignment), all of one level
-    uint8_t divides;  // 1: some step of the range is KIND_A / KIND_B / KIND_BITS_A / KIND_BITS_B / KIND_ISZERO / KIND_DIVREM (1 / cq); KIND_INDICATOR does not count
+    uint8_t divides;  // 1: some step of the range is KIND_A / KIND_B / KIND_BITS_A / KIND_BITS_B / KIND_ISZERO / KIND_DIVREM (1 / cq) / KIND_SQRT (1 / (ka kb)); KIND_INDICATOR does not count
     uint8_t bits = 0; // chain == 0 only.  1: every step of the range is a decomposition; 0: none is
     uint8_t iszero = 0;  // chain == 0 only.  1: every step of the range is an is-zero pair; 0: none is
     uint8_t divrem = 0;  // chain == 0 only.  1: every step of the range is a division row; 0: none is
     uint8_t indicator = 0;  // chain == 0 only.  1: every step of the range is an indicator row; 0: none is
+    uint8_t sqrt = 0;       // chain == 0 only.  1: every step of the range is a square-root row; 0: none is
 };
 
 enum Error : int { OK = 0, ERR_MANY_UNKNOWNS = 1, ERR_TWO_MATRICES = 2, ERR_UNDETERMINED = 3, ERR_COLUMN_ZERO = 4 };
@@ -356,6 +384,13 @@ inline Step indicator_step(const Unknown &e, uint32_t r, uint32_t lv) {
     return s;
 }
 
+// The square-root shape, for a row whose unknown entries `occ` are all of ONE column with nz[k] non-zero entries in matrix k: the
+// column carries byte 4 and is named exactly twice, as the lone non-zero entry of A_r and the lone non-zero entry of B_r (so C_r names
+// no unknown: there is none left).  Any other shape is what it was without the marker.
+inline bool sqrt_row(const std::vector<Unknown> &occ, const uint32_t nz[3], const uint8_t *unknown) {
+    return occ.size() == 2 && occ[0].matrix == 0 && occ[1].matrix == 1 && unknown[occ[0].col] == PATTERN_SQRT && nz[0] == 1 && nz[1] == 1;
+}
+
 // The tail both builders share: p.steps (in ROW order, levels set) sorted by (level, kind), stable by row; level_ptr; the launch schedule.
 inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
     // counting sort by (level, kind); the row order inside a key is the order the steps come in
@@ -373,12 +408,13 @@ inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
     }
     // launch schedule: a wide level is its own launch, split where the dividing kinds begin, again where the decompositions and
     // their dividing kinds begin, where the is-zero pairs begin, where the division rows begin and where the indicator rows begin (which
-    // do not divide: a chain of C-steps and indicators is a non-dividing one); consecutive narrow levels are one chain
+    // do not divide: a chain of C-steps and indicators is a non-dividing one), and where the square-root rows begin (which count as
+    // dividing); consecutive narrow levels are one chain
     for (uint32_t l = 0; l < max_level; ++l) {
         const uint32_t *at = start.data() + (size_t)l * K;
         const uint32_t lo = at[KIND_C], ab = at[KIND_A], bits = at[KIND_BITS_C], bits_ab = at[KIND_BITS_A], pairs = at[KIND_ISZERO], divs = at[KIND_DIVREM],
-                       inds = at[KIND_INDICATOR], hi = at[K];
-        const uint8_t divides = (uint8_t)(bits > ab || inds > bits_ab);
+                       inds = at[KIND_INDICATOR], roots = at[KIND_SQRT], hi = at[K];
+        const uint8_t divides = (uint8_t)(bits > ab || inds > bits_ab || hi > roots);
         if (hi - lo >= wide_steps) {
             if (ab > lo) p.launches.push_back(Launch{lo, ab, 0, 0});
             if (bits > ab) p.launches.push_back(Launch{ab, bits, 0, 1});
@@ -386,7 +422,8 @@ inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
             if (pairs > bits_ab) p.launches.push_back(Launch{bits_ab, pairs, 0, 1, 1});
             if (divs > pairs) p.launches.push_back(Launch{pairs, divs, 0, 1, 0, 1});
             if (inds > divs) p.launches.push_back(Launch{divs, inds, 0, 1, 0, 0, 1});
-            if (hi > inds) p.launches.push_back(Launch{inds, hi, 0, 0, 0, 0, 0, 1});
+            if (roots > inds) p.launches.push_back(Launch{inds, roots, 0, 0, 0, 0, 0, 1});
+            if (hi > roots) p.launches.push_back(Launch{roots, hi, 0, 1, 0, 0, 0, 0, 1});
         } else if (!p.launches.empty() && p.launches.back().chain) {
             p.launches.back().hi = hi;
             p.launches.back().divides |= divides;
@@ -475,6 +512,16 @@ struct Planner {
         p.steps.push_back(modulus && indicator_row(e, nz, unknown) ? indicator_step(e, r, lv) : Step{e.pos, r, e.col, KIND_OF[e.matrix], lv});
         solved(e.col, lv);
         known(e.col);
+    }
+    // a square-root row (sqrt_row): occ = u's entry in A_r, then its entry in B_r
+    template <class Known>
+    void sqrt_step(uint32_t r, const Known &known) {
+        const uint32_t lv = reads + 1, col = occ[0].col;
+        Step s{occ[0].pos, r, col, KIND_SQRT, lv};
+        s.cols_off = (uint32_t)(occ[1].pos - m[1].rowptr[r]);
+        p.steps.push_back(s);
+        solved(col, lv);
+        known(col);
     }
     // a decomposition whose exponent order is `order` (decomposition_order)
     template <class Known>
@@ -609,6 +656,10 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
                     if (st.bool_row[u] == NONE) st.bool_row[u] = (uint32_t)r;
                     continue;
                 }
+                if (sqrt_row(occ, st.nz, unknown)) {   // u u = c with the fourth marker on u: the square-root step
+                    st.sqrt_step((uint32_t)r, nobody);
+                    continue;
+                }
             } else if (!(why = decomposition_order(m, occ, st.bool_row, modulus, st.order))) {
                 st.bits_step((uint32_t)r, nobody);
                 continue;
@@ -730,6 +781,13 @@ inline bool schedule_any_order(Planner &st, uint64_t nr, uint64_t ncols, std::st
             for (const uint32_t col : {q.col, rem.col})
                 if (st.pair_of[col] != NONE) release(st.openers[st.pair_of[col]]);
             st.division_step(q, rem, r, wake);
+            continue;
+        }
+        if (one_column && sqrt_row(occ, st.nz, st.unknown)) {
+            // a square-root row whose only unknown is its root: a step at once.  An opener registered over the root (the row
+            // x = u * s has that shape) was none: it is released and examined again, as for a division row
+            if (st.pair_of[u] != NONE) release(st.openers[st.pair_of[u]]);
+            st.sqrt_step(r, wake);
             continue;
         }
         const Opener *o = st.pending_opener();

@@ -21,6 +21,7 @@ MINUS_ALPHA, MINUS_GAMMA = 3, 5        # common.rs:11,14
 B_POLYMATH = b"polymath"               # common.rs:8
 UNKNOWN = api.UNKNOWN_LIMBS             # the marker limbs of a value the device is to solve (PM_ASSIGNMENT_SOLVE); >= r on both curves
 QUOTIENT = api.QUOTIENT_LIMBS           # the same, and the value is the Euclidean quotient of its division row (q * b = a - rem); >= r as well
+SQRT = api.SQRT_LIMBS                   # the same, and the value is the smaller square root of its square-root row (u * u = c: the root <= (r - 1) / 2)
 INDICATOR = api.INDICATOR_LIMBS         # the same, and the value is the indicator of its guard row (out * (inp - i) = 0: 1 where inp == i, else 0)
 
 FIELDS = {
@@ -195,6 +196,38 @@ def ser_g2(field, Q):
 def _fq_sqrt(p, a):
     s = pow(a, (p + 1) // 4, p)            # p = 3 mod 4 (BLS12-381 and BN254 base fields)
     return s if s * s % p == a % p else None
+
+
+def tonelli_shanks(p, a):
+    """A square root of a modulo the odd prime p, or None where a is a non-residue: Tonelli-Shanks on Python integers, for any p (the
+    scalar fields have p = 1 mod 2^32 / 2^28, where _fq_sqrt's single exponentiation does not apply).  Which of the two roots is not
+    specified; small_sqrt chooses."""
+    a %= p
+    if a == 0:
+        return 0
+    if pow(a, (p - 1) // 2, p) != 1:
+        return None
+    s, t = 0, p - 1
+    while t % 2 == 0:
+        s, t = s + 1, t // 2
+    g = 2
+    while pow(g, (p - 1) // 2, p) == 1:
+        g += 1
+    c, z, b = pow(g, t, p), pow(a, (t + 1) // 2, p), pow(a, t, p)
+    while b != 1:
+        i, b2 = 0, b
+        while b2 != 1:
+            i, b2 = i + 1, b2 * b2 % p
+        w = pow(c, 1 << (s - i - 1), p)
+        z, c, b, s = z * w % p, w * w % p, b * w * w % p, i
+    return z
+
+
+def small_sqrt(r, c):
+    """The square root of c modulo r whose canonical integer is the smaller of the pair (<= (r - 1) / 2): what circom's sqrt returns
+    and what the solver's square-root step stores.  None where c is a non-residue."""
+    z = tonelli_shanks(r, c)
+    return None if z is None else min(z, (r - z) % r)
 
 
 def _fq2_sqrt(p, a):
@@ -443,15 +476,16 @@ class Polymath:
     def partial_limbs(self, instance, witness):
         """(x_limbs, w_limbs) of an assignment given as ints, with UNKNOWN (or None) where the value is to be solved and QUOTIENT
         where it is to be solved as the Euclidean quotient of its division row (the remainder of that row is a plain unknown), INDICATOR
-        where it is to be solved as the indicator of its guard row."""
+        where it is to be solved as the indicator of its guard row, SQRT where it is to be solved as the smaller square root of its
+        square-root row."""
         f = self.field
-        marked = lambda v: v is None or v is UNKNOWN or v is QUOTIENT or v is INDICATOR
+        marked = lambda v: v is None or v is UNKNOWN or v is QUOTIENT or v is INDICATOR or v is SQRT
         x = f.fr_limbs([0 if marked(v) else v for v in instance]).reshape(-1, 4).copy()
         w = f.fr_limbs([0 if marked(v) else v for v in witness]).reshape(-1, 4).copy() if len(witness) else np.zeros((0, 4), dtype=np.uint64)
         for arr, vals in ((x, instance), (w, witness)):
             for j, v in enumerate(vals):
                 if marked(v):
-                    arr[j] = api.QUOTIENT_LIMBS if v is QUOTIENT else api.INDICATOR_LIMBS if v is INDICATOR else api.UNKNOWN_LIMBS
+                    arr[j] = api.QUOTIENT_LIMBS if v is QUOTIENT else api.INDICATOR_LIMBS if v is INDICATOR else api.SQRT_LIMBS if v is SQRT else api.UNKNOWN_LIMBS
         return x, w
 
     def solve_batch(self, pk, partials, device_ptrs=None):

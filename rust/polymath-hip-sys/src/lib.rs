@@ -94,6 +94,8 @@ pub const PM_ASSIGNMENT_SOLVE: i32 = 2;
 pub const PM_UNKNOWN_WORDS: [u64; 4] = [u64::MAX, u64::MAX, u64::MAX, u64::MAX];
 pub const PM_UNKNOWN_QUOTIENT_WORDS: [u64; 4] = [u64::MAX - 1, u64::MAX, u64::MAX, u64::MAX];
 pub const PM_HINT_INDICATOR_WORDS: [u64; 4] = [u64::MAX, u64::MAX - 1, u64::MAX, u64::MAX];
+// a fourth marker (2^256 - 1 - 2^192, >= r on both curves as well): unknown, and the smaller square root of its square-root row
+pub const PM_HINT_SQRT_MARKER: [u64; 4] = [u64::MAX, u64::MAX, u64::MAX, u64::MAX - 1];
 
 // pm_transcript
 pub const PM_TRANSCRIPT_MERLIN: i32 = 0;

@@ -214,6 +214,13 @@ pub const UNKNOWN_QUOTIENT: [u64; 4] = sys::PM_UNKNOWN_QUOTIENT_WORDS;
 /// with `None` on such a column the row is an ordinary dividing row, which is stuck where `inp == i`, as it always was.
 pub const HINT_INDICATOR: [u64; 4] = sys::PM_HINT_INDICATOR_WORDS;
 
+/// The square-root marker of `PM_ASSIGNMENT_SOLVE` (`PM_HINT_SQRT_MARKER`): four limbs that are no field element on either curve and
+/// say "unknown, and the smaller square root of its square-root row" (`u * u = c`: circom's `x <-- sqrt(c); x*x === c`, arkworks'
+/// `sqrt` witness in point decompression).  The value is the root whose canonical integer is `<= (r - 1) / 2`; a non-residue leaves
+/// that assignment stuck at the row.  The marker is explicit: with `None` on such a column the row is refused, as it always was.  A
+/// caller who wants the larger root supplies the value itself.
+pub const HINT_SQRT: [u64; 4] = sys::PM_HINT_SQRT_MARKER;
+
 /// Montgomery limbs of a partial assignment appended to `out`: a value's own four words, or the unknown marker (four times
 /// `u64::MAX`: not a field element on either curve) for `None`.
 fn partial_limbs<F>(vals: &[Option<F>], out: &mut Vec<u64>) {
