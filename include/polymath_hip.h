@@ -608,9 +608,14 @@ int pm_verify_batch(pm_ctx *ctx, int curve, int transcript, const uint8_t *vk_by
  *     and the affine points -- and a leaf's check is exact (above), so there is no bisection:
  *         *n_checks = 1 + the number of proofs that are not PM_VERIFY_MALFORMED;   with verdicts == NULL:  *n_checks <= 1
  *     (host mode: *n_checks <= 1 + 2 f ceil(log2 count)).  Malformed proofs keep PM_VERIFY_MALFORMED and are not checked.
- * Verdicts, *all_accepted, the weights, the meaning of seed32 and every PM_ERR_INVALID_ARG case are the same in both modes; another
- * `pairing` value is PM_ERR_INVALID_ARG.  pm_last_timings: slot 4 is the pairing checks' wall ms wherever they ran (device mode: line
- * tables, launches and copies), slot 5 the GPU ms of the pairing launches (device mode only).
+ *   PM_VERIFY_PAIRING_DEVICE_WAVE: PM_VERIFY_PAIRING_DEVICE with each check spread over a group of 36 lanes of one wave instead of one
+ *     lane (the same line tables, Miller loop and final exponentiation; -g G summed from a table of G's multiples built once per call).
+ *     The root is always checked this way; the leaf launch after a failing root while at most VERIFY_WAVE_LEAF_MAX = 1024 proofs are live
+ *     (a wave a leaf), and one lane a leaf above that (a starting value for the threshold, not a tuned one).  Contract: verdicts,
+ *     *all_accepted, the weights, the meaning of seed32, *n_checks and every refusal are, byte for byte, PM_VERIFY_PAIRING_DEVICE's.
+ * Verdicts, *all_accepted, the weights, the meaning of seed32 and every PM_ERR_INVALID_ARG case are the same in all modes; another
+ * `pairing` value (2, 3, 5, .., and 4 with any other low bit) is PM_ERR_INVALID_ARG with nothing written.  pm_last_timings: slot 4 is the pairing checks' wall ms wherever they ran (device mode: line
+ * tables, launches and copies), slot 5 the GPU ms of the pairing launches (the device modes only).
  * `pairing` may be OR-ed with a pm_verify_challenges value, the place of the per-proof challenges (a flag of this argument: the set of
  * entry points is pinned like the option table).  PM_VERIFY_CHALLENGES_HOST (0) changes nothing, bit for bit.
  *   PM_VERIFY_CHALLENGES_DEVICE: x1_i, x2_i, c_i(x1_i) (verifier.rs:24-42 with common.rs:21-98: the Fiat-Shamir transcript of
@@ -622,7 +627,7 @@ int pm_verify_batch(pm_ctx *ctx, int curve, int transcript, const uint8_t *vk_by
  * either pairing mode; any other bit in `pairing` is PM_ERR_INVALID_ARG.  pm_last_timings: slot 6 is the GPU ms of the challenge launch
  * (0 with host challenges); slot 3 stays the host's glue (wall ms), which with device challenges is the weights' key, the draws and
  * the uploads. */
-typedef enum pm_verify_pairing { PM_VERIFY_PAIRING_HOST = 0, PM_VERIFY_PAIRING_DEVICE = 1 } pm_verify_pairing;
+typedef enum pm_verify_pairing { PM_VERIFY_PAIRING_HOST = 0, PM_VERIFY_PAIRING_DEVICE = 1, PM_VERIFY_PAIRING_DEVICE_WAVE = 4 } pm_verify_pairing;
 typedef enum pm_verify_challenges { PM_VERIFY_CHALLENGES_HOST = 0, PM_VERIFY_CHALLENGES_DEVICE = 256 } pm_verify_challenges;
 int pm_verify_batch2(pm_ctx *ctx, int curve, int transcript, const uint8_t *vk_bytes, size_t vk_len, const uint64_t *public_inputs, size_t n_inputs,
                      const uint8_t *proofs, size_t proof_len, size_t count, const uint8_t *seed32, int pairing, uint8_t *verdicts,

@@ -34,7 +34,10 @@ VERIFY_REJECTED, VERIFY_ACCEPTED, VERIFY_MALFORMED = range(3)
 # challenge_kernel the GPU time of the challenge launch (device challenges; else 0)
 VERIFY_TIMING_SLOTS = {"decode": 0, "terms": 1, "tree": 2, "host_glue": 3, "host_pairing": 4, "pairing_kernels": 5, "challenge_kernel": 6, "device_total": 7}
 # pm_verify_pairing (include/polymath_hip.h): where pm_verify_batch2 runs its pairing checks
-VERIFY_PAIRING = {"host": 0, "device": 1}
+VERIFY_PAIRING = {"host": 0, "device": 1, "wave": 4}
+# wave mode's leaf launch after a failing root: a wave a leaf while at most this many proofs are live, a lane a leaf above (csrc/internal.h:
+# VERIFY_WAVE_LEAF_MAX; a starting value, not a tuned one)
+VERIFY_WAVE_LEAF_MAX = 1024
 # pm_verify_challenges (include/polymath_hip.h): where the per-proof Fiat-Shamir challenges run; OR-ed into pm_verify_batch2's `pairing`
 VERIFY_CHALLENGES = {"host": 0, "device": 256}
 PROVE_GLUE_HOST, PROVE_GLUE_DEVICE = 0, 256    # pm_prove_glue: OR-ed into the `transcript` argument of pm_host_prove_batch
@@ -301,7 +304,8 @@ def pairing_check_batch(ctx, curve, g2, g1):
 def verify_batch(ctx, curve, transcript, vk_bytes, public_inputs, proofs, seed=None, verdicts=True, pairing="host", challenges="host"):
     """pm_verify_batch2: many proofs against one verifying key; the per-proof curve work on the GPU, the pairing checks on the host
     (pairing="host": a handful per valid batch, a bisection otherwise; what pm_verify_batch does) or on the GPU (pairing="device":
-    the root in a launch of one lane, every live leaf in one more launch if it fails).  public_inputs: Montgomery limbs [count, n_inputs, 4], WITHOUT the leading one; proofs: a list of
+    the root in a launch of one lane, every live leaf in one more launch if it fails; pairing="wave": the same two launches with every
+    check spread over 36 lanes of a wave, the leaves while at most VERIFY_WAVE_LEAF_MAX are live -- same results).  public_inputs: Montgomery limbs [count, n_inputs, 4], WITHOUT the leading one; proofs: a list of
     Proof::serialize_compressed byte strings or one packed buffer; seed: None or 32 bytes mixed into the weights' key.
     challenges="device": the per-proof Fiat-Shamir challenges and scalar glue on the GPU too (one lane per proof; the same bits, so
     nothing in the result changes; PM_VERIFY_CHALLENGES_DEVICE OR-ed into the call's `pairing` argument).

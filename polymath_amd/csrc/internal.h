@@ -507,6 +507,18 @@ int pairing_prepare(pm_ctx *ctx, const uint32_t *g2, int k, unsigned pairs, Pair
 template <class C>
 int pairing_check_launch(pm_ctx *ctx, const PairingPrepared &prep, const Affine<C> *d_pts, const VerifyTerm<C> *d_terms, const uint32_t *d_neg_g,
                          const uint8_t *d_live, const Affine<C> &G, size_t count, uint8_t *d_is_one, int timing_slot);
+// pairing_wave.hip: the same checks, one per group of 36 lanes of a wave (pairing_wave.cuh), on the tables of pairing_prepare.  With
+// d_terms the launch also needs fixed_base_prepare's table of this call's G (the points d 2^(4 t) G), from which the lanes sum neg_g_i G.
+// PM_VERIFY_PAIRING_DEVICE_WAVE checks the root this way, and the live leaves after a failing root while there are at most
+// VERIFY_WAVE_LEAF_MAX of them (a wave a leaf; above that, a lane a leaf: pairing_check_launch).  1024 is a STARTING value, not a
+// tuned one: the measured crossover lies near 12 000 live leaves on both curves (profiles/verify_batch_wave_pairing.txt), so anything
+// up to 8192 would still gain.  polymath_amd/api.py mirrors it.
+constexpr size_t VERIFY_WAVE_LEAF_MAX = 1024;
+template <class C>
+int fixed_base_prepare(pm_ctx *ctx, const Affine<C> &G, ScopedDevBuf *out);
+template <class C>
+int pairing_check_wave_launch(pm_ctx *ctx, const PairingPrepared &prep, const ScopedDevBuf &fixed_base, const Affine<C> *d_pts, const VerifyTerm<C> *d_terms,
+                              const uint32_t *d_neg_g, const uint8_t *d_live, size_t count, uint8_t *d_is_one, int timing_slot);
 // challenges.hip: the verifier's Fiat-Shamir challenges (transcript.cuh: fs_verifier_challenges), one proof per lane, ONE launch on
 // the context's stream.  Proof i reads its [a]_1 / [c]_1 records at d_a + i a_stride / d_c + i c_stride, the 32 bytes of a(x1) at
 // d_a_at + i a_at_stride and n_inputs Montgomery public inputs at d_inputs + i n_inputs (all strides multiples of 8, the bases

@@ -3,6 +3,7 @@
 // three decompressions with a subgroup check and four scalar multiplications -- which runs here on the device.  The pairing checks,
 // a handful per valid batch, run on the host (host/pairing.hpp; pm_verify_batch, PM_VERIFY_PAIRING_HOST) or on the device
 // (pairing_batch.hip; pm_verify_batch2 with PM_VERIFY_PAIRING_DEVICE: the root in a launch of one lane, then every live leaf in ONE launch).
+// PM_VERIFY_PAIRING_DEVICE_WAVE is that mode with a check spread over 36 lanes of a wave (pairing_wave.hip): the root, and the leaves while few.
 // The call is a sequence of stages over one state struct (VerifyCall), in stream order:
 //   decode_points         host: repack the 3 point records of every proof, upload     | device: k_g1_decode (validate = 1)
 //   batch_weights         host: weights rho_i from the batch's hash
@@ -73,6 +74,7 @@ struct VerifyCall {
     unsigned depth = 0;
     ScopedDevBuf in, pts, status, scalars, tree, neg_g, live, is_one, a_at, pub, g_dev, ok, tap;
     PairingPrepared prep;
+    ScopedDevBuf fixed_base;         // wave mode: the table of G's multiples (pairing_wave.hip)
     std::vector<uint8_t> packed;     // the point records as uploaded: stay until the call is over
     std::chrono::steady_clock::time_point t_glue;   // the host's side of the challenges stage starts here
     // After the challenges stage: the scalar records are on the device (scalars), g_i = rho_i (a_at_x1 + x2 c_at_x1) (Montgomery) and
@@ -267,7 +269,9 @@ struct VerifyCall {
     // The same equation, one lane per node (pairing_batch.hip): the root alone, then -- a leaf's check being the reference's own
     // equation raised to a non-zero weight, hence exact -- every live leaf at once.  The lanes form -g G, -V and the affine points
     // themselves (verify_node_points).  Called with at least one live proof.
-    int pairing_on_device() {
+    // wave: the root by a group of lanes of one wave (pairing_wave.hip), and the leaves too while at most VERIFY_WAVE_LEAF_MAX are live;
+    // the same equation on the same tables, so the same verdicts and the same count of checks.
+    int pairing_on_device(bool wave) {
         constexpr int N = C::FqP::N;
         const typename Pairing::G2 *q[3] = {&vk.z_g2, &vk.x_g2, &vk.one_g2};
         uint32_t g2[3][4 * N] = {};
@@ -279,6 +283,7 @@ struct VerifyCall {
             memcpy(&g2[j][2 * N], q[j]->y.c0.l, 4 * N); memcpy(&g2[j][3 * N], q[j]->y.c1.l, 4 * N);
         }
         PM_TRY(pairing_prepare<C>(ctx, &g2[0][0], 3, pairs, &prep));
+        if (wave) PM_TRY(fixed_base_prepare<C>(ctx, one_g1(), &fixed_base));
         std::vector<Fr> neg_g_host(count + 1);               // canonical; the root's behind the leaves'
         std::vector<uint8_t> live_host(count), one_host(count + 1, 0);
         for (size_t i = 0; i < count; ++i) { neg_g_host[i] = from_mont<R>(neg<R>(g[i])); live_host[i] = bad[i] ? 0 : 1; }
@@ -290,13 +295,15 @@ struct VerifyCall {
         PM_HIP(ctx, hipMemcpyAsync(live.p, live_host.data(), count, hipMemcpyHostToDevice, ctx->stream));
         uint32_t *d_neg_g = neg_g.as<uint32_t>();
         uint8_t *d_is_one = is_one.as<uint8_t>();
-        PM_TRY(pairing_check_launch<C>(ctx, prep, nullptr, nodes(depth), d_neg_g + 8 * count, nullptr, one_g1(), 1, d_is_one + count, TV_PAIRING_KERNELS));
+        if (wave) PM_TRY(pairing_check_wave_launch<C>(ctx, prep, fixed_base, nullptr, nodes(depth), d_neg_g + 8 * count, nullptr, 1, d_is_one + count, TV_PAIRING_KERNELS));
+        else PM_TRY(pairing_check_launch<C>(ctx, prep, nullptr, nodes(depth), d_neg_g + 8 * count, nullptr, one_g1(), 1, d_is_one + count, TV_PAIRING_KERNELS));
         PM_HIP(ctx, hipMemcpyAsync(&one_host[count], d_is_one + count, 1, hipMemcpyDeviceToHost, ctx->stream));
         PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
         checks = 1;
         root_ok = one_host[count] != 0;
         if (root_ok || !want_verdicts) return PM_OK;
-        PM_TRY(pairing_check_launch<C>(ctx, prep, nullptr, nodes(0), d_neg_g, live.as<uint8_t>(), one_g1(), count, d_is_one, TV_PAIRING_KERNELS));
+        if (wave && live_total() <= VERIFY_WAVE_LEAF_MAX) PM_TRY(pairing_check_wave_launch<C>(ctx, prep, fixed_base, nullptr, nodes(0), d_neg_g, live.as<uint8_t>(), count, d_is_one, TV_PAIRING_KERNELS));
+        else PM_TRY(pairing_check_launch<C>(ctx, prep, nullptr, nodes(0), d_neg_g, live.as<uint8_t>(), one_g1(), count, d_is_one, TV_PAIRING_KERNELS));
         PM_HIP(ctx, hipMemcpyAsync(one_host.data(), d_is_one, count, hipMemcpyDeviceToHost, ctx->stream));
         PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
         for (size_t i = 0; i < count; ++i)
@@ -326,9 +333,9 @@ int verify_batch_impl(pm_ctx *ctx, int transcript, const uint8_t *vk_bytes, size
     PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     s.verdict.resize(count);
     for (size_t i = 0; i < count; ++i) s.verdict[i] = s.bad[i] ? PM_VERIFY_MALFORMED : PM_VERIFY_ACCEPTED;
-    if (pairing == PM_VERIFY_PAIRING_DEVICE) {
+    if (pairing != PM_VERIFY_PAIRING_HOST) {
         const auto t0 = std::chrono::steady_clock::now();
-        if (s.live_total()) PM_TRY(s.pairing_on_device());
+        if (s.live_total()) PM_TRY(s.pairing_on_device(pairing == PM_VERIFY_PAIRING_DEVICE_WAVE));
         ctx->timing_ms[TV_PAIRING_HOST] = ms_since(t0);
     } else {
         PM_TRY(s.pairing_on_host());
@@ -348,7 +355,7 @@ extern "C" int pm_verify_batch2(pm_ctx *ctx, int curve, int transcript, const ui
     // `pairing` is a pm_verify_pairing value, optionally OR-ed with PM_VERIFY_CHALLENGES_DEVICE
     const int challenges = pairing & PM_VERIFY_CHALLENGES_DEVICE;
     pairing &= ~PM_VERIFY_CHALLENGES_DEVICE;
-    if (pairing != PM_VERIFY_PAIRING_HOST && pairing != PM_VERIFY_PAIRING_DEVICE) return PM_ERR_INVALID_ARG;
+    if (pairing != PM_VERIFY_PAIRING_HOST && pairing != PM_VERIFY_PAIRING_DEVICE && pairing != PM_VERIFY_PAIRING_DEVICE_WAVE) return PM_ERR_INVALID_ARG;
     if (!ctx || !vk_bytes || !all_accepted || (count && (!proofs || (n_inputs && !public_inputs)))) return PM_ERR_INVALID_ARG;
     if (curve != PM_BLS12_381 && curve != PM_BN254) return PM_ERR_INVALID_ARG;
     if (!pmhost::transcript_ok(transcript)) return PM_ERR_INVALID_ARG;

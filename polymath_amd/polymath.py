@@ -623,7 +623,8 @@ class Polymath:
 
     def verify_batch(self, vk_bytes, list_of_inputs, list_of_proofs, seed=None, pairing="host", challenges="host"):
         """Many proofs against one key (pm_verify_batch2: the per-proof curve work on the GPU, the pairing checks on the host or,
-        pairing="device", one lane per check on the GPU: all verdicts of a failing batch from one launch; challenges="device": the
+        pairing="device", one lane per check on the GPU: all verdicts of a failing batch from one launch; pairing="wave": the same with a
+        check spread over 36 lanes of one wave (api.VERIFY_WAVE_LEAF_MAX), same results; challenges="device": the
         per-proof Fiat-Shamir challenges and scalar glue on the GPU as well, one lane per proof, same bits).
         list_of_inputs[i]: proof i's public inputs WITHOUT the leading one; list_of_proofs[i]: a Proof or its bytes.
         -> (verdicts np.uint8[count] of api.VERIFY_* codes, all_accepted, n_checks)."""

@@ -79,6 +79,7 @@ pub const PM_VERIFY_MALFORMED: u8 = 2;
 // pm_verify_pairing: where pm_verify_batch2 runs its pairing checks
 pub const PM_VERIFY_PAIRING_HOST: i32 = 0;
 pub const PM_VERIFY_PAIRING_DEVICE: i32 = 1;
+pub const PM_VERIFY_PAIRING_DEVICE_WAVE: i32 = 4;
 // pm_verify_challenges: where the per-proof Fiat-Shamir challenges run; OR-ed into pm_verify_batch2's `pairing`
 pub const PM_VERIFY_CHALLENGES_HOST: i32 = 0;
 pub const PM_VERIFY_CHALLENGES_DEVICE: i32 = 256;

@@ -396,6 +396,15 @@ impl Context {
                                sys::PM_VERIFY_CHALLENGES_HOST)
     }
 
+    /// [`Context::verify_batch_device_pairing`] with every check spread over a group of 36 lanes of one wave (`pm_verify_batch2`,
+    /// `PM_VERIFY_PAIRING_DEVICE_WAVE`): the root always, the leaves after a failing root while at most 1024 proofs are live.  Same
+    /// verdicts and the same number of checks, byte for byte.
+    pub fn verify_batch_wave_pairing(&mut self, curve: Curve, transcript: i32, vk_bytes: &[u8], public_inputs: &[u64], n_inputs: usize,
+                                     proofs: &[u8], seed: Option<&[u8; 32]>) -> Result<(Vec<Verdict>, usize), HipError> {
+        self.verify_batch_with(curve, transcript, vk_bytes, public_inputs, n_inputs, proofs, seed, sys::PM_VERIFY_PAIRING_DEVICE_WAVE,
+                               sys::PM_VERIFY_CHALLENGES_HOST)
+    }
+
     /// [`Context::verify_batch`] with both modes chosen (`pm_verify_batch2`): `pairing` a `sys::PM_VERIFY_PAIRING_*`, `challenges` a
     /// `sys::PM_VERIFY_CHALLENGES_*` value, OR-ed into the call's `pairing` argument.  With `PM_VERIFY_CHALLENGES_DEVICE` the per-proof Fiat-Shamir challenges and scalar glue
     /// run on the GPU too, one lane per proof; the challenges are the same bits, so verdicts and the number of checks do not change.
