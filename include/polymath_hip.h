@@ -246,7 +246,29 @@ typedef enum pm_g1_status {       /* one verdict per point; the text is deser_g1
     PM_G1_NONCANONICAL_INF = 5,   /* "G1: non-canonical encoding of the point at infinity" */
     PM_G1_INF_SIGN = 6            /* "G1: sign bit on the point at infinity" (BLS12-381; on BN254 that is PM_G1_BAD_FLAGS) */
 } pm_g1_status;
-/* Batch decode, host to host: `count` packed records of 48 (BLS12-381) / 32 (BN254) bytes -> out_xy (x||y Montgomery, 2*fq_limbs
+/* The second record form: ark-serialize's Compress::No (ProvingKey::serialize_uncompressed), both coordinates of every point and no
+ * square root on the way in.  PM_WIRE_UNCOMPRESSED is a FLAG, OR-ed into the `validate` argument of pm_g1_decode and
+ * pm_pk_load_bytes and into the `which` argument of pm_pk_export_bases_compressed; there is no entry point of its own.
+ *   BLS12-381 G1, 96 bytes: x || y, 48 bytes big-endian each, the three flag bits in byte 0 (x is read with them masked, y uses all
+ *     384 bits).  0x80 set: PM_G1_BAD_FLAGS, whose text in this form is "G1: not an uncompressed point".  0x20 set: PM_G1_INF_SIGN
+ *     next to 0x40, PM_G1_BAD_FLAGS on a finite point.  0x40: infinity, every other bit zero or PM_G1_NONCANONICAL_INF.
+ *   BN254 G1, 64 bytes: x || y, 32 bytes little-endian each, the two flag bits in the LAST byte (byte 63; x's top byte carries
+ *     none).  Both set: PM_G1_BAD_FLAGS.  0x40: infinity, every other bit zero.  0x80 on a finite point (ark's "y > -y") is written
+ *     as the compressed form writes it and IGNORED by the reader, as ark's reader ignores it.
+ * Then, in this order: a coordinate >= p is PM_G1_COORD_GE_P; y^2 != x^3 + b is PM_G1_NOT_ON_CURVE -- checked ALWAYS, with
+ * validation off too (stricter than ark's deserialize_uncompressed_unchecked, which trusts the pair: a resident key's points are
+ * curve points in every mode); with validation on, on BLS12-381, [r]P != O is PM_G1_NOT_IN_SUBGROUP.  pm_g1_status has no new value.
+ * A key in this form is field for field the compressed string with every point long: the vk prefix (one G1, three G2 of 192 / 128
+ * bytes, n, m0, sigma, omega) is 728 bytes on BLS12-381 and 504 on BN254.  Compressed bytes given with the flag, or uncompressed
+ * bytes without it, are a malformed key (PM_ERR_INVALID_ARG): the form is never guessed.  pm_host_verify, pm_verify_batch[2] and
+ * pm_host_make_vk keep taking and producing COMPRESSED vk and proof bytes; the host mirror (wire.hpp: read_vk_c / ser_vk_c with a
+ * form) and the Python twin convert a vk between the two.
+ * In `validate`, bit 8 selects the form and validation is on iff (validate & ~256) != 0, so 0 and 1 mean what they always meant.
+ * One thing changes in the letter: a value with bit 8 set used to read as plain "validate"; no caller in this tree passes anything
+ * but 0 or 1. */
+typedef enum pm_wire_form { PM_WIRE_COMPRESSED = 0, PM_WIRE_UNCOMPRESSED = 256 } pm_wire_form;
+/* Batch decode, host to host: `count` packed records of 48 (BLS12-381) / 32 (BN254) bytes -- 96 / 64 with PM_WIRE_UNCOMPRESSED
+ * in `validate` -- -> out_xy (x||y Montgomery, 2*fq_limbs
  * u64 per point; infinity and every refused point x = y = 0) and one pm_g1_status byte per point.  PM_OK even when points are bad:
  * the verdicts are in `status`. */
 int pm_g1_decode(pm_ctx *ctx, int curve, const uint8_t *in, size_t count, int validate, uint64_t *out_xy, uint8_t *status);
@@ -258,11 +280,14 @@ int pm_g1_decode(pm_ctx *ctx, int curve, const uint8_t *in, size_t count, int va
  * The VerifyingKey is the byte prefix (data_structures.rs:56-58: vk is the first field): 392 bytes on BLS12-381, 280 on BN254 --
  * its points are always validated (host).  PM_ERR_INVALID_ARG, no handle, nothing allocated: truncated or trailing bytes, a vector
  * length that does not fit the key's shape, vk.m0 / n / sigma / omega disagreeing with the SAP matrices, or a refused point --
- * pm_last_error then names the first one in wire order, e.g. "x_powers_g1[17]: G1: not in the prime-order subgroup". */
+ * pm_last_error then names the first one in wire order, e.g. "x_powers_g1[17]: G1: not in the prime-order subgroup".
+ * validate | PM_WIRE_UNCOMPRESSED: the bytes are ProvingKey::serialize_uncompressed (vk prefix 728 / 504 bytes); staging slots
+ * hold 2^PM_OPT_WIRE_CHUNK_LOG records of 96 / 64 bytes -- the option keeps counting points. */
 int pm_pk_load_bytes(pm_ctx *ctx, int curve, const uint8_t *bytes, size_t len, int validate, int shard_rank, int shard_count,
                      int layout, pm_pk **out);
 /* pm_pk_export_bases, compressed: `len` records of 48 / 32 bytes (ser_g1, the encoding pm_pk_load_bytes reads) into out.
- * Same ranges and restrictions as pm_pk_export_bases. */
+ * Same ranges and restrictions as pm_pk_export_bases.  which | PM_WIRE_UNCOMPRESSED: records of 96 / 64 bytes
+ * (ser_g1_uncompressed).  Any other high bit, or (which & 255) >= PM_NUM_BASE_VECS, is PM_ERR_INVALID_ARG. */
 int pm_pk_export_bases_compressed(pm_ctx *ctx, const pm_pk *pk, int which, size_t offset, size_t len, uint8_t *out);
 
 /* ---- prove: create_proof_with_assignment split at its two transcript calls ---------------- */

@@ -26,6 +26,14 @@ STATUS = {0: "PM_OK", 1: "PM_ERR_INVALID_ARG", 2: "PM_ERR_LEN_MISMATCH", 3: "PM_
 # pm_g1_status (include/polymath_hip.h): the verdict of one compressed G1 encoding
 G1_OK, G1_BAD_FLAGS, G1_COORD_GE_P, G1_NOT_ON_CURVE, G1_NOT_IN_SUBGROUP, G1_NONCANONICAL_INF, G1_INF_SIGN = range(7)
 G1_BYTES = {PM_BLS12_381: 48, PM_BN254: 32}                # compressed record of one point
+# pm_wire_form: a flag OR-ed into `validate` (pm_g1_decode, pm_pk_load_bytes) and `which` (pm_pk_export_bases_compressed)
+PM_WIRE_COMPRESSED, PM_WIRE_UNCOMPRESSED = 0, 256
+WIRE_FORMS = {"compressed": PM_WIRE_COMPRESSED, "uncompressed": PM_WIRE_UNCOMPRESSED}
+
+
+def g1_record_bytes(curve_id, form="compressed"):
+    """Bytes of one G1 record: 48 / 32 compressed, 96 / 64 uncompressed (x || y)."""
+    return G1_BYTES[curve_id] * (2 if WIRE_FORMS[form] else 1)
 PROOF_BYTES = {PM_BLS12_381: 176, PM_BN254: 128}            # Proof::serialize_compressed
 # pm_verify_verdict (include/polymath_hip.h): one per proof of pm_verify_batch
 VERIFY_REJECTED, VERIFY_ACCEPTED, VERIFY_MALFORMED = range(3)
@@ -272,17 +280,18 @@ def _byte_view(data):
     return arr, arr.ctypes.data, arr.nbytes
 
 
-def g1_decode(ctx, curve, data, validate=True):
-    """pm_g1_decode: packed compressed G1 records (48 B BLS12-381 / 32 B BN254) -> (xy np.uint64 [count, 2 fq_limbs] Montgomery,
-    infinity and refused points all-zero; status np.uint8 [count] of G1_* codes)."""
+def g1_decode(ctx, curve, data, validate=True, form="compressed"):
+    """pm_g1_decode: packed G1 records (compressed: 48 B BLS12-381 / 32 B BN254; form="uncompressed": 96 B / 64 B) -> (xy np.uint64
+    [count, 2 fq_limbs] Montgomery, infinity and refused points all-zero; status np.uint8 [count] of G1_* codes)."""
     cid = CURVE_IDS[curve]
     keep, addr, nbytes = _byte_view(data)
-    if nbytes % G1_BYTES[cid]:
-        raise ValueError("not a whole number of %d-byte records" % G1_BYTES[cid])
-    count = nbytes // G1_BYTES[cid]
+    rec = g1_record_bytes(cid, form)
+    if nbytes % rec:
+        raise ValueError("not a whole number of %d-byte records" % rec)
+    count = nbytes // rec
     xy = np.zeros((count, 2 * FQ_LIMBS64[cid]), dtype=np.uint64)
     status = np.zeros(count, dtype=np.uint8)
-    ctx.check(ctx.L.pm_g1_decode(ctx.h, cid, ct.c_void_p(addr), count, int(bool(validate)), _p(xy), status.ctypes.data_as(ct.c_void_p)))
+    ctx.check(ctx.L.pm_g1_decode(ctx.h, cid, ct.c_void_p(addr), count, int(bool(validate)) | WIRE_FORMS[form], _p(xy), status.ctypes.data_as(ct.c_void_p)))
     del keep
     return xy, status
 
@@ -679,12 +688,13 @@ class ProvingKey:
         return pk
 
     @classmethod
-    def load_bytes(cls, ctx, curve, data, validate=True, shard_rank=0, shard_count=1, layout="pairs"):
-        """pm_pk_load_bytes: ProvingKey::serialize_compressed bytes -> resident key; the points are decoded (and with `validate`
-        checked as ark's Validate::Yes does) on the device.  data: bytes, memoryview or np.memmap of a key file, not copied."""
+    def load_bytes(cls, ctx, curve, data, validate=True, shard_rank=0, shard_count=1, layout="pairs", form="compressed"):
+        """pm_pk_load_bytes: ProvingKey::serialize_compressed (form="uncompressed": serialize_uncompressed) bytes -> resident key;
+        the points are decoded (and with `validate` checked as ark's Validate::Yes does) on the device.  data: bytes, memoryview or
+        np.memmap of a key file, not copied."""
         keep, addr, nbytes = _byte_view(data)
         h = ct.c_void_p()
-        ctx.check(ctx.L.pm_pk_load_bytes(ctx.h, CURVE_IDS[curve], ct.c_void_p(addr), nbytes, int(bool(validate)), shard_rank, shard_count,
+        ctx.check(ctx.L.pm_pk_load_bytes(ctx.h, CURVE_IDS[curve], ct.c_void_p(addr), nbytes, int(bool(validate)) | WIRE_FORMS[form], shard_rank, shard_count,
                                          LAYOUTS[layout], ct.byref(h)))
         del keep
         pk = cls(ctx, curve, h, None)
@@ -723,13 +733,15 @@ class ProvingKey:
         self.ctx.check(self.ctx.L.pm_pk_export_bases(self.ctx.h, self.h, which, offset, length, _p(out)))
         return out
 
-    def export_bases_compressed(self, which, offset=0, length=None):
-        """pm_pk_export_bases_compressed: (a range of) base vector `which` as its serialize_compressed point records -> bytes."""
+    def export_bases_compressed(self, which, offset=0, length=None, form="compressed"):
+        """pm_pk_export_bases_compressed: (a range of) base vector `which` as its serialize_compressed point records -> bytes;
+        form="uncompressed": its serialize_uncompressed records (which | PM_WIRE_UNCOMPRESSED)."""
         if length is None:
             length = self.base_lens[which] - offset
-        out = ct.create_string_buffer(max(1, length * G1_BYTES[self.cid]))
-        self.ctx.check(self.ctx.L.pm_pk_export_bases_compressed(self.ctx.h, self.h, which, offset, length, out))
-        return out.raw[:length * G1_BYTES[self.cid]]
+        rec = g1_record_bytes(self.cid, form)
+        out = ct.create_string_buffer(max(1, length * rec))
+        self.ctx.check(self.ctx.L.pm_pk_export_bases_compressed(self.ctx.h, self.h, which | WIRE_FORMS[form], offset, length, out))
+        return out.raw[:length * rec]
 
     # --- the three prover phases: (status, outputs...) tuples, status codes of pm_status
     def phase1(self, x, w, r_a):

@@ -692,16 +692,18 @@ struct PinnedPair {   // two pinned staging buffers, freed with the call
 template <class C>
 static int pk_load_bytes_impl(pm_ctx *ctx, const uint8_t *bytes, size_t len, int validate, int shard_rank, int shard_count, int layout,
                               pm_pk **out) {
-    const size_t NB = 4 * C::FqP::N;
+    const int form = validate & PM_WIRE_UNCOMPRESSED;   // bit 8 selects the record form; validation is every other bit
+    validate &= ~PM_WIRE_UNCOMPRESSED;
+    const size_t NB = g1_record_bytes<C>(form);
     WireLayout w;
-    PM_TRY(pk_wire_parse<C>(bytes, len, w, ctx->err));
+    PM_TRY(pk_wire_parse<C>(bytes, len, form, w, ctx->err));
     auto fail = [&](int st, const std::string &why) { if (!why.empty()) ctx->err = "pm_pk_load_bytes: " + why; return st; };
     pm_csr m[3];
     for (int k = 0; k < 3; ++k) {
         if (w.col[k].empty()) { w.col[k].push_back(0); w.val[k].assign(4, 0); }   // non-null pointers for an empty matrix
         m[k] = pm_csr{w.nr, w.rowptr[k].data(), w.col[k].data(), w.val[k].data()};
     }
-    // The compressed points of each requested range go through two staging slots, each a pinned host buffer and a device buffer:
+    // The point records of each requested range go through two staging slots (chunk x record size bytes each), each a pinned host buffer and a device buffer:
     // the host copies chunk k + 1 out of the caller's bytes (an mmap, say) while the device decodes chunk k.  A slot is refilled
     // only after the decode that read it has finished (its event is recorded behind the kernel), whatever way the runtime moves
     // the copy.  Refused points lower a per-vector slot; nothing is read back until the whole resident set is decoded.
@@ -743,7 +745,7 @@ static int pk_load_bytes_impl(pm_ctx *ctx, const uint8_t *bytes, size_t len, int
                 if (used[slot]) PM_HIP(ctx, hipEventSynchronize(pin.ev[slot]));
                 memcpy(pin.p[slot], bytes + w.vec_off[v] + (start + s) * NB, cnt * NB);
                 PM_HIP(ctx, hipMemcpyAsync(d_in[slot].p, pin.p[slot], cnt * NB, hipMemcpyHostToDevice, ctx->stream));
-                PM_TRY(g1_decode_device<C>(ctx, d_in[slot].as<uint8_t>(), cnt, validate != 0, dst + s, nullptr, d_bad.as<unsigned long long>() + v, start + s));
+                PM_TRY(g1_decode_device<C>(ctx, d_in[slot].as<uint8_t>(), cnt, validate != 0, dst + s, nullptr, d_bad.as<unsigned long long>() + v, start + s, form));
                 PM_HIP(ctx, hipEventRecord(pin.ev[slot], ctx->stream));
                 used[slot] = true;
                 slot ^= 1;
@@ -757,7 +759,7 @@ static int pk_load_bytes_impl(pm_ctx *ctx, const uint8_t *bytes, size_t len, int
             for (int v : WIRE_VECTOR_ORDER)
                 if (h_bad[v] != ~0ull)
                     return fail(PM_ERR_INVALID_ARG, std::string(BASE_VEC_NAMES[v]) + "[" + std::to_string(h_bad[v] >> 8) + "]: " +
-                                                        g1_status_text(C::ID, (int)(h_bad[v] & 0xFF)));
+                                                        g1_status_text(C::ID, (int)(h_bad[v] & 0xFF), form));
             for (ScopedDevBuf &b : d_in) b.release();   // before the tables: they want the memory
             return PM_OK;
         },
@@ -775,7 +777,9 @@ extern "C" int pm_pk_load_bytes(pm_ctx *ctx, int curve, const uint8_t *bytes, si
 
 template <class C>
 static int g1_decode_impl(pm_ctx *ctx, const uint8_t *in, size_t count, int validate, uint64_t *out_xy, uint8_t *status) {
-    const size_t NB = 4 * C::FqP::N, CH = wire_chunk(ctx);
+    const int form = validate & PM_WIRE_UNCOMPRESSED;
+    validate &= ~PM_WIRE_UNCOMPRESSED;
+    const size_t NB = g1_record_bytes<C>(form), CH = wire_chunk(ctx);
     ScopedDevBuf d_in, d_out, d_st;
     const size_t first = std::min(count, CH);
     PM_HIP(ctx, d_in.reserve(first * NB));
@@ -784,7 +788,7 @@ static int g1_decode_impl(pm_ctx *ctx, const uint8_t *in, size_t count, int vali
     for (size_t s = 0; s < count; s += CH) {
         const size_t cnt = std::min(CH, count - s);
         PM_HIP(ctx, hipMemcpyAsync(d_in.p, in + s * NB, cnt * NB, hipMemcpyHostToDevice, ctx->stream));
-        PM_TRY(g1_decode_device<C>(ctx, d_in.as<uint8_t>(), cnt, validate != 0, d_out.as<Affine<C>>(), d_st.as<uint8_t>(), nullptr, 0));
+        PM_TRY(g1_decode_device<C>(ctx, d_in.as<uint8_t>(), cnt, validate != 0, d_out.as<Affine<C>>(), d_st.as<uint8_t>(), nullptr, 0, form));
         PM_HIP(ctx, hipMemcpyAsync((uint8_t *)out_xy + s * sizeof(Affine<C>), d_out.p, cnt * sizeof(Affine<C>), hipMemcpyDeviceToHost, ctx->stream));
         PM_HIP(ctx, hipMemcpyAsync(status + s, d_st.p, cnt, hipMemcpyDeviceToHost, ctx->stream));
         PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -954,10 +958,10 @@ extern "C" int pm_pk_export_bases(pm_ctx *ctx, const pm_pk *pk, int which, size_
     return with_curve(pk->curve, [&](auto cv) { return download_points<type_of<decltype(cv)>>(ctx, src, len, out_xy); });
 }
 
-// resident (internal-form) points -> standard form -> compressed records, in chunks through the context's scratch
+// resident (internal-form) points -> standard form -> records of `form`, in chunks through the context's scratch
 template <class C>
-static int export_compressed_impl(pm_ctx *ctx, const Affine<C> *d_src, size_t len, uint8_t *out) {
-    const size_t NB = 4 * C::FqP::N, CH = wire_chunk(ctx), first = std::min(len, CH);
+static int export_compressed_impl(pm_ctx *ctx, const Affine<C> *d_src, size_t len, int form, uint8_t *out) {
+    const size_t NB = g1_record_bytes<C>(form), CH = wire_chunk(ctx), first = std::min(len, CH);
     PM_HIP(ctx, ctx->scratch.reserve(first * (sizeof(Affine<C>) + NB)));
     Affine<C> *d_pts = ctx->scratch.as<Affine<C>>();
     uint8_t *d_rec = (uint8_t *)(d_pts + first);   // sizeof(Affine<C>) = 96 / 64 bytes: 16-byte aligned
@@ -965,7 +969,7 @@ static int export_compressed_impl(pm_ctx *ctx, const Affine<C> *d_src, size_t le
         const size_t cnt = std::min(CH, len - s);
         PM_HIP(ctx, hipMemcpyAsync(d_pts, d_src + s, cnt * sizeof(Affine<C>), hipMemcpyDeviceToDevice, ctx->stream));
         PM_TRY(bases_convert<C>(ctx, d_pts, cnt, false));
-        PM_TRY(g1_encode_device<C>(ctx, d_pts, cnt, d_rec));
+        PM_TRY(g1_encode_device<C>(ctx, d_pts, cnt, d_rec, form));
         PM_HIP(ctx, hipMemcpyAsync(out + s * NB, d_rec, cnt * NB, hipMemcpyDeviceToHost, ctx->stream));
         PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
@@ -973,14 +977,17 @@ static int export_compressed_impl(pm_ctx *ctx, const Affine<C> *d_src, size_t le
 }
 
 extern "C" int pm_pk_export_bases_compressed(pm_ctx *ctx, const pm_pk *pk, int which, size_t offset, size_t len, uint8_t *out) {
-    if (!ctx || !pk || !out || which < 0 || which >= PM_NUM_BASE_VECS) return PM_ERR_INVALID_ARG;
+    if (!ctx || !pk || !out || which < 0 || (which & ~(255 | PM_WIRE_UNCOMPRESSED))) return PM_ERR_INVALID_ARG;
+    const int form = which & PM_WIRE_UNCOMPRESSED;      // which | PM_WIRE_UNCOMPRESSED: records of 96 / 64 bytes
+    which &= 255;
+    if (which >= PM_NUM_BASE_VECS) return PM_ERR_INVALID_ARG;
     if (offset + len > pk->base_len[which]) return PM_ERR_INVALID_ARG;
     PM_TRY(set_device(ctx));
     uint64_t dev_off = 0;
     if (!pk_dev_range(pk, which, offset, len, &dev_off)) return PM_ERR_INVALID_ARG;  // not resident on this shard
     if (!len) return PM_OK;
     return with_curve(pk->curve, [&](auto cv) {
-        return export_compressed_impl<type_of<decltype(cv)>>(ctx, (const Affine<type_of<decltype(cv)>> *)pk->d_bases + dev_off, len, out);
+        return export_compressed_impl<type_of<decltype(cv)>>(ctx, (const Affine<type_of<decltype(cv)>> *)pk->d_bases + dev_off, len, form, out);
     });
 }
 

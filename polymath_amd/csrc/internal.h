@@ -480,13 +480,16 @@ int bases_convert(pm_ctx *ctx, Affine<C> *d_points, size_t len, bool to_internal
 // g1_codec.hip: compressed G1 (include/polymath_hip.h, pm_g1_status).  Decode: `count` records of 4 fq words each at d_in (16-byte
 // aligned) -> standard-Montgomery affine points (refused and infinity: x = y = 0); d_status (optional) one pm_g1_status per point;
 // d_first_bad (optional) atomically lowered to ((base_index + i) << 8 | status) for every refused point i.  Encode: the inverse,
-// standard-Montgomery points -> records (d_out 16-byte aligned).
+// standard-Montgomery points -> records (d_out 16-byte aligned).  form = PM_WIRE_UNCOMPRESSED: records of 8 fq words (x || y), the
+// same outputs and verdicts.
 template <class C>
 int g1_decode_device(pm_ctx *ctx, const uint8_t *d_in, size_t count, bool validate, Affine<C> *d_out, uint8_t *d_status,
-                     unsigned long long *d_first_bad, uint64_t base_index);
+                     unsigned long long *d_first_bad, uint64_t base_index, int form = PM_WIRE_COMPRESSED);
 template <class C>
-int g1_encode_device(pm_ctx *ctx, const Affine<C> *d_pts, size_t count, uint8_t *d_out);
-const char *g1_status_text(int curve, int status);
+int g1_encode_device(pm_ctx *ctx, const Affine<C> *d_pts, size_t count, uint8_t *d_out, int form = PM_WIRE_COMPRESSED);
+const char *g1_status_text(int curve, int status, int form = PM_WIRE_COMPRESSED);
+template <class C>
+constexpr size_t g1_record_bytes(int form) { return (size_t)4 * C::FqP::N * (form == PM_WIRE_UNCOMPRESSED ? 2 : 1); }
 
 // pairing_batch.hip: checks  prod_j e(P[i][j], Q_j) == 1  against k <= 4 fixed G2 points, one lane per check.  pairing_prepare walks the
 // Miller loop of each Q_j on the host (g2: k x 4 Fq, x.c0 || x.c1 || y.c0 || y.c1; bit j of `pairs` clear: Q_j = O, the pair is left out
@@ -539,7 +542,7 @@ template <class C>
 int verifier_challenges_launch(pm_ctx *ctx, int transcript, uint64_t n, uint64_t sigma, const Fp<typename C::FrP> &omega, const ChallengeRows &rows,
                                Fp<typename C::FrP> *d_x1, Fp<typename C::FrP> *d_x2, Fp<typename C::FrP> *d_c_at_x1, uint8_t *d_ok,
                                VerifyScalars *d_scalars, Fp<typename C::FrP> *d_g, int timing_slot);
-// ProvingKey::serialize_compressed parsed on the host without touching its base points (pk_wire_parse)
+// ProvingKey::serialize_compressed / serialize_uncompressed (form: pm_wire_form) parsed on the host without touching its base points (pk_wire_parse)
 struct WireLayout {
     size_t vk_len = 0;
     uint64_t n = 0, vk_m0 = 0, sigma = 0, omega[4] = {0, 0, 0, 0};   // the vk's header fields
@@ -549,7 +552,7 @@ struct WireLayout {
     uint64_t vec_off[PM_NUM_BASE_VECS] = {0}, vec_len[PM_NUM_BASE_VECS] = {0};   // by pm_base_vec: byte offset of point 0, points
 };
 template <class C>
-int pk_wire_parse(const uint8_t *data, size_t len, WireLayout &out, std::string &err);
+int pk_wire_parse(const uint8_t *data, size_t len, int form, WireLayout &out, std::string &err);
 
 // setup.hip: the uj_wj_lcs scalars of generator.rs:112-136 on the device (Lagrange coefficients at x + the sparse pass over the
 // key's CSR matrices); `lagrange` and `work` are the caller's scratch

@@ -8,6 +8,7 @@
 //                  x_powers_y_gamma_g1, x_powers_y_gamma_z_g1, uj_wj_lcs_by_y_alpha_g1 : Vec<G1Affine> }
 // usize / u64 = 8 B little-endian, Vec = u64 length prefix, Fr = 32 B little-endian canonical, BLS12-381
 // G1 / G2 in the zcash encoding (big-endian x, 3 flag bits; G2 = x.c1 || x.c0) [ark, from memory -- SURVEY App. C].
+// The same layout in uncompressed mode (serialize_uncompressed: x and y of every point) is the second form, pm_wire_form.
 // A WireKey is the host-side image (points decompressed, matrices with row-duplicate columns KEPT, as the
 // reference serialises what the synthesiser produced); pk_load / pk_export move it through pm_pk_load /
 // pm_pk_export_bases.  Pinned by tests/golden/pk_wire.json and the published generator encodings.
@@ -252,25 +253,166 @@ G1Point<C> deser_g1(Reader &rd, bool validate = true) {
     return g;
 }
 
-// ------------------------------------------------------------------------------------ keys
+// ------------------------------------------------------------------- the uncompressed form
+// ark-serialize's Compress::No (serialize_uncompressed): both coordinates of every point, no square root on the way in.
+//   BLS12-381 G1, 96 B: x || y, each 48 B big-endian; the three flag bits sit in byte 0 (x is read with them masked, y uses all of
+//     its 384 bits).  0x80 (compressed) and 0x20 (sort) must be clear; 0x40 is infinity and then every other bit is zero.
+//   BN254 G1, 64 B: x || y, each 32 B little-endian; the two flag bits sit in the LAST byte, y's top byte (x's top byte carries
+//     none).  0x40 is infinity (every other bit zero); 0x80 on a finite point is "y > -y": written as the compressed form writes
+//     it, ignored on the way in (ark's reader ignores it too, so a file loads whichever way its writer set the bit).
+//   G2: x.c1 || x.c0 || y.c1 || y.c0 big-endian, flags in byte 0 (BLS12-381, 192 B); x.c0 || x.c1 || y.c0 || y.c1 little-endian,
+//     flags in the last byte (BN254, 128 B).                                                           [ark, from memory]
+// The curve equation is checked ALWAYS, with validate off too -- stricter than deserialize_uncompressed_unchecked, which trusts the
+// pair: a decoded point is a curve point in every mode, as it is with the compressed form.  validate adds the subgroup check.
 template <class C>
-inline void ser_vk_c(const VerifyingKeyT<C> &vk, Bytes &out) {
-    ser_g1<C>(vk.one_g1, out);
-    ser_g2_c<C>(vk.one_g2, out);
-    ser_g2_c<C>(vk.x_g2, out);
-    ser_g2_c<C>(vk.z_g2, out);
+void ser_g1_uncompressed(const G1Point<C> &g, Bytes &out) {
+    typedef typename C::FqP Q;
+    const int NB = Q::N * 4;
+    const size_t at = out.size();
+    if (g.inf) {
+        out.insert(out.end(), 2 * NB, 0);
+        out[C::ID == 0 ? at : at + 2 * NB - 1] = 0x40;
+        return;
+    }
+    if (C::ID == 0) {
+        put_fq_be<Q>(g.p.x, out);
+        put_fq_be<Q>(g.p.y, out);
+    } else {
+        put_fq_le<Q>(g.p.x, out);
+        put_fq_le<Q>(g.p.y, out);
+        if (fq_cmp<Q>(g.p.y, pm::neg<Q>(g.p.y)) > 0) out.back() |= 0x80;
+    }
+}
+
+template <class C>
+G1Point<C> deser_g1_uncompressed(Reader &rd, bool validate = true) {
+    typedef typename C::FqP Q;
+    const int NB = Q::N * 4;
+    const uint8_t *b = rd.take(2 * NB);
+    G1Point<C> g;
+    memset(&g.p, 0, sizeof(g.p));
+    const uint8_t flags = C::ID == 0 ? b[0] : b[2 * NB - 1];
+    g.inf = (flags & 0x40) != 0;
+    if (C::ID == 0) {
+        if (flags & 0x80) throw WireError("G1: not an uncompressed point");
+        if (g.inf && (flags & 0x20)) throw WireError("G1: sign bit on the point at infinity");
+        if (flags & 0x20) throw WireError("G1: not an uncompressed point");
+    } else if (g.inf && (flags & 0x80)) throw WireError("G1: both flag bits set");                // SWFlags::from_u8 -> None
+    if (g.inf) {
+        for (int i = 0; i < 2 * NB; ++i)
+            if (i == (C::ID == 0 ? 0 : 2 * NB - 1) ? (b[i] & (C::ID == 0 ? 0x1F : 0x3F)) : b[i])
+                throw WireError("G1: non-canonical encoding of the point at infinity");
+        return g;
+    }
+    const bool ok = C::ID == 0 ? (get_fq<Q>(b, true, 0x1F, g.p.x) && get_fq<Q>(b + NB, true, 0xFF, g.p.y))
+                               : (get_fq<Q>(b, false, 0xFF, g.p.x) && get_fq<Q>(b + NB, false, 0x3F, g.p.y));
+    if (!ok) throw WireError("G1: coordinate >= p");
+    pm::Fp<Q> bb;
+    for (int i = 0; i < Q::N; ++i) bb.l[i] = C::B_MONT[i];
+    if (!pm::sqr<Q>(g.p.y).eq(pm::add<Q>(pm::mul<Q>(pm::sqr<Q>(g.p.x), g.p.x), bb))) throw WireError("G1: not on the curve");
+    if (validate && !g1_in_subgroup<C>(g)) throw WireError("G1: not in the prime-order subgroup");
+    return g;
+}
+
+template <class C>
+inline void ser_g2_uncompressed(const typename PairingOf<C>::type::G2 &g, Bytes &out) {
+    typedef typename PairingOf<C>::type B;
+    typedef typename C::FqP Q;
+    const int NB = 4 * Q::N;
+    const size_t at = out.size();
+    if (g.inf) {
+        out.insert(out.end(), 4 * NB, 0);
+        out[C::ID == 0 ? at : at + 4 * NB - 1] = 0x40;
+        return;
+    }
+    if (C::ID == 0) {
+        put_fq_be<Q>(g.x.c1, out); put_fq_be<Q>(g.x.c0, out);
+        put_fq_be<Q>(g.y.c1, out); put_fq_be<Q>(g.y.c0, out);
+    } else {
+        put_fq_le<Q>(g.x.c0, out); put_fq_le<Q>(g.x.c1, out);
+        put_fq_le<Q>(g.y.c0, out); put_fq_le<Q>(g.y.c1, out);
+        if (Fq2OpsT<C>::gt(g.y, B::neg2(g.y))) out.back() |= 0x80;
+    }
+}
+
+// always fully validated, as deser_g2_c is: on the twist and in the prime-order subgroup
+template <class C>
+inline typename PairingOf<C>::type::G2 deser_g2_uncompressed(Reader &rd) {
+    typedef typename PairingOf<C>::type B;
+    typedef typename C::FqP Q;
+    const int NB = 4 * Q::N;
+    const uint8_t *b = rd.take(4 * NB);
+    typename B::G2 g;
+    const uint8_t flags = C::ID == 0 ? b[0] : b[4 * NB - 1];
+    g.inf = (flags & 0x40) != 0;
+    if (C::ID == 0) {
+        if (flags & 0x80) throw WireError("G2: not an uncompressed point");
+        if (g.inf && (flags & 0x20)) throw WireError("G2: sign bit on the point at infinity");
+        if (flags & 0x20) throw WireError("G2: not an uncompressed point");
+    } else if (g.inf && (flags & 0x80)) throw WireError("G2: both flag bits set");
+    if (g.inf) {
+        for (int i = 0; i < 4 * NB; ++i)
+            if (i == (C::ID == 0 ? 0 : 4 * NB - 1) ? (b[i] & (C::ID == 0 ? 0x1F : 0x3F)) : b[i])
+                throw WireError("G2: non-canonical encoding of the point at infinity");
+        g.x = g.y = typename B::Fq2{B::Fq::zero(), B::Fq::zero()};
+        return g;
+    }
+    const bool ok = C::ID == 0 ? (get_fq<Q>(b, true, 0x1F, g.x.c1) && get_fq<Q>(b + NB, true, 0xFF, g.x.c0) &&
+                                  get_fq<Q>(b + 2 * NB, true, 0xFF, g.y.c1) && get_fq<Q>(b + 3 * NB, true, 0xFF, g.y.c0))
+                               : (get_fq<Q>(b, false, 0xFF, g.x.c0) && get_fq<Q>(b + NB, false, 0xFF, g.x.c1) &&
+                                  get_fq<Q>(b + 2 * NB, false, 0xFF, g.y.c0) && get_fq<Q>(b + 3 * NB, false, 0x3F, g.y.c1));
+    if (!ok) throw WireError("G2: coordinate >= p");
+    const typename B::Fq2 rhs = B::add2(B::mul2(B::mul2(g.x, g.x), g.x), B::twist_b());
+    if (!B::mul2(g.y, g.y).eq(rhs)) throw WireError("G2: not on the twist");
+    if (!B::g2_mul(g, C::FrP::MOD, C::FrP::N).inf) throw WireError("G2: not in the prime-order subgroup");
+    return g;
+}
+
+// the record of one point in either form (pm_wire_form of include/polymath_hip.h)
+inline void check_form(int form) {
+    if (form != PM_WIRE_COMPRESSED && form != PM_WIRE_UNCOMPRESSED) throw WireError("unknown wire form");
+}
+template <class C>
+inline size_t g1_record_bytes(int form) { return (size_t)C::FqP::N * 4 * (form == PM_WIRE_UNCOMPRESSED ? 2 : 1); }
+template <class C>
+inline void ser_g1_form(const G1Point<C> &g, Bytes &out, int form) {
+    if (form == PM_WIRE_UNCOMPRESSED) ser_g1_uncompressed<C>(g, out); else ser_g1<C>(g, out);
+}
+template <class C>
+inline G1Point<C> deser_g1_form(Reader &rd, bool validate, int form) {
+    return form == PM_WIRE_UNCOMPRESSED ? deser_g1_uncompressed<C>(rd, validate) : deser_g1<C>(rd, validate);
+}
+template <class C>
+inline void ser_g2_form(const typename PairingOf<C>::type::G2 &g, Bytes &out, int form) {
+    if (form == PM_WIRE_UNCOMPRESSED) ser_g2_uncompressed<C>(g, out); else ser_g2_c<C>(g, out);
+}
+template <class C>
+inline typename PairingOf<C>::type::G2 deser_g2_form(Reader &rd, int form) {
+    return form == PM_WIRE_UNCOMPRESSED ? deser_g2_uncompressed<C>(rd) : deser_g2_c<C>(rd);
+}
+
+// ------------------------------------------------------------------------------------ keys
+// form: every point of the vk in that form -- 392 / 728 bytes on BLS12-381, 280 / 504 on BN254
+template <class C>
+inline void ser_vk_c(const VerifyingKeyT<C> &vk, Bytes &out, int form = PM_WIRE_COMPRESSED) {
+    check_form(form);
+    ser_g1_form<C>(vk.one_g1, out, form);
+    ser_g2_form<C>(vk.one_g2, out, form);
+    ser_g2_form<C>(vk.x_g2, out, form);
+    ser_g2_form<C>(vk.z_g2, out, form);
     ser_u64(vk.n, out);
     ser_u64(vk.m0, out);
     ser_u64(vk.sigma, out);
     ser_fr<C>(vk.omega, out);
 }
 template <class C>
-inline VerifyingKeyT<C> read_vk_c(Reader &rd) {
+inline VerifyingKeyT<C> read_vk_c(Reader &rd, int form = PM_WIRE_COMPRESSED) {
+    check_form(form);
     VerifyingKeyT<C> vk;
-    vk.one_g1 = deser_g1<C>(rd);
-    vk.one_g2 = deser_g2_c<C>(rd);
-    vk.x_g2 = deser_g2_c<C>(rd);
-    vk.z_g2 = deser_g2_c<C>(rd);
+    vk.one_g1 = deser_g1_form<C>(rd, true, form);
+    vk.one_g2 = deser_g2_form<C>(rd, form);
+    vk.x_g2 = deser_g2_form<C>(rd, form);
+    vk.z_g2 = deser_g2_form<C>(rd, form);
     vk.n = rd.u64();
     vk.m0 = rd.u64();
     vk.sigma = rd.u64();
@@ -279,14 +421,14 @@ inline VerifyingKeyT<C> read_vk_c(Reader &rd) {
 }
 // a byte string that is one vk and nothing else: trailing bytes are refused like any other malformed key
 template <class C>
-inline VerifyingKeyT<C> read_vk_exact(const uint8_t *bytes, size_t len) {
+inline VerifyingKeyT<C> read_vk_exact(const uint8_t *bytes, size_t len, int form = PM_WIRE_COMPRESSED) {
     Reader rd(bytes, len);
-    const VerifyingKeyT<C> vk = read_vk_c<C>(rd);
+    const VerifyingKeyT<C> vk = read_vk_c<C>(rd, form);
     if (rd.off != len) throw WireError("trailing bytes after the verifying key");
     return vk;
 }
-inline void ser_vk(const VerifyingKey &vk, Bytes &out) { ser_vk_c<pm::BlsCurve>(vk, out); }
-inline VerifyingKey read_vk(Reader &rd) { return read_vk_c<pm::BlsCurve>(rd); }
+inline void ser_vk(const VerifyingKey &vk, Bytes &out, int form = PM_WIRE_COMPRESSED) { ser_vk_c<pm::BlsCurve>(vk, out, form); }
+inline VerifyingKey read_vk(Reader &rd, int form = PM_WIRE_COMPRESSED) { return read_vk_c<pm::BlsCurve>(rd, form); }
 
 // Proof::deserialize_compressed (data_structures.rs:10-19): a_g1, c_g1, a_at_x1, d_g1
 template <class C>
@@ -343,9 +485,10 @@ struct WireKey {
         return m;
     }
 
-    Bytes to_bytes() const {
+    // form: ProvingKey::serialize_compressed / serialize_uncompressed -- field for field the same string, every point in that form
+    Bytes to_bytes(int form = PM_WIRE_COMPRESSED) const {
         Bytes out;
-        ser_vk(vk, out);
+        ser_vk(vk, out, form);
         ser_u64(m0, out);
         ser_u64(mw, out);
         ser_u64(nr, out);
@@ -354,18 +497,19 @@ struct WireKey {
         put_matrix(c, out);
         for (int which : PK_WIRE_VECTORS) {
             ser_u64(vec[which].size(), out);
-            for (const auto &g : vec[which]) ser_g1<C>(g, out);
+            for (const auto &g : vec[which]) ser_g1_form<C>(g, out, form);
         }
         return out;
     }
 
     // validate: the subgroup check on every base point, as deserialize_compressed does (Validate::Yes); false =
     // deserialize_compressed_unchecked for the vectors (a 2^20-gate key holds 27 M points: 255 doublings each)
-    static WireKey parse(const uint8_t *data, size_t len, bool validate = true) {
+    // No format guessing: bytes of the other form are a malformed key.
+    static WireKey parse(const uint8_t *data, size_t len, bool validate = true, int form = PM_WIRE_COMPRESSED) {
         static_assert(C::ID == 0, "the reference instantiates Bls12_381 only (Cargo.toml:35); G2 codecs are BLS12-381");
         Reader rd(data, len);
         WireKey k;
-        k.vk = read_vk(rd);
+        k.vk = read_vk(rd, form);
         k.m0 = rd.u64();
         k.mw = rd.u64();
         k.nr = rd.u64();
@@ -374,9 +518,9 @@ struct WireKey {
         k.c = get_matrix(rd);
         for (int which : PK_WIRE_VECTORS) {
             const uint64_t cnt = rd.u64();
-            if (cnt > (len - rd.off) / (C::FqP::N * 4)) throw WireError("truncated key");
+            if (cnt > (len - rd.off) / g1_record_bytes<C>(form)) throw WireError("truncated key");
             k.vec[which].reserve(cnt);
-            for (uint64_t i = 0; i < cnt; ++i) k.vec[which].push_back(deser_g1<C>(rd, validate));
+            for (uint64_t i = 0; i < cnt; ++i) k.vec[which].push_back(deser_g1_form<C>(rd, validate, form));
         }
         if (rd.off != len) throw WireError("trailing bytes after the key");
         return k;

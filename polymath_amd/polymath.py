@@ -147,8 +147,43 @@ def ser_fr_slice(field, vs):
     return struct.pack("<Q", len(vs)) + b"".join(ser_fr(field, v) for v in vs)
 
 
-def ser_g1(field, P):
-    """ark-serialize compressed G1 (macro.rs:7-12 -> serialize_compressed)."""
+WIRE_FORMS = ("compressed", "uncompressed")
+
+
+def _check_form(form):
+    if form not in WIRE_FORMS:
+        raise ValueError("form: %r, expected 'compressed' or 'uncompressed'" % (form,))
+    return form == "uncompressed"
+
+
+def g1_bytes(field, form="compressed"):
+    """Bytes of one G1 record: 48 / 32 compressed, 96 / 64 uncompressed."""
+    return (48 if field.curve == "bls12_381" else 32) * (2 if _check_form(form) else 1)
+
+
+def g2_bytes(field, form="compressed"):
+    return 2 * g1_bytes(field, form)
+
+
+def _ser_g1_uncompressed(field, P):
+    """ark-serialize Compress::No: x || y.  BLS12-381 96 B big-endian, flags (only 0x40 infinity is ever set) in byte 0; BN254 64 B
+    little-endian, flags in the last byte (0x40 infinity, 0x80 y > -y as in the compressed form)."""
+    if field.curve == "bls12_381":
+        if P is None:
+            return bytes([0x40]) + bytes(95)
+        return P[0].to_bytes(48, "big") + P[1].to_bytes(48, "big")
+    if P is None:
+        return bytes(63) + bytes([0x40])
+    b = bytearray(P[0].to_bytes(32, "little") + P[1].to_bytes(32, "little"))
+    if P[1] > field.p - P[1]:
+        b[63] |= 0x80
+    return bytes(b)
+
+
+def ser_g1(field, P, form="compressed"):
+    """ark-serialize compressed G1 (macro.rs:7-12 -> serialize_compressed); form="uncompressed": serialize_uncompressed."""
+    if _check_form(form):
+        return _ser_g1_uncompressed(field, P)
     if field.curve == "bls12_381":      # 48 B big-endian x, flags: 0x80 compressed, 0x40 infinity, 0x20 y > -y
         if P is None:
             return bytes([0xC0]) + bytes(47)
@@ -182,12 +217,32 @@ def _fq2_gt(a, b):
     return (a[1], a[0]) > (b[1], b[0])
 
 
-def ser_g2(field, Q):
-    """BLS12-381 G2, zcash format: x.c1 || x.c0 big-endian, flags as for G1, sign = y > -y in Fq2 order."""
-    assert field.curve == "bls12_381"
+def _twist_b(field):
+    """b' of the twist y^2 = x^3 + b': 4 (1 + u) on BLS12-381, 3 / (9 + u) on BN254"""
+    if field.curve == "bls12_381":
+        return FQ2_B
+    k = 3 * pow(82, -1, field.p) % field.p
+    return (9 * k % field.p, (-k) % field.p)
+
+
+def ser_g2(field, Q, form="compressed"):
+    """G2.  BLS12-381, zcash format: x.c1 || x.c0 big-endian, flags as for G1, sign = y > -y in Fq2 order.  BN254: x.c0 || x.c1
+    little-endian, flags in the last byte.  form="uncompressed": x then y the same way, 192 / 128 bytes."""
+    p, long = field.p, _check_form(form)
+    bls = field.curve == "bls12_381"
+    n = 48 if bls else 32
     if Q is None:
-        return bytes([0xC0]) + bytes(95)
+        size = (4 if long else 2) * n
+        return (bytes([0x40 if long else 0xC0]) + bytes(size - 1)) if bls else (bytes(size - 1) + bytes([0x40]))
     (x0, x1), (y0, y1) = Q
+    larger = _fq2_gt((y0, y1), ((-y0) % p, (-y1) % p))
+    if not bls:
+        b = bytearray(x0.to_bytes(32, "little") + x1.to_bytes(32, "little") +
+                      ((y0.to_bytes(32, "little") + y1.to_bytes(32, "little")) if long else b""))
+        b[-1] |= 0x80 if larger else 0
+        return bytes(b)
+    if long:
+        return x1.to_bytes(48, "big") + x0.to_bytes(48, "big") + y1.to_bytes(48, "big") + y0.to_bytes(48, "big")
     b = bytearray(x1.to_bytes(48, "big") + x0.to_bytes(48, "big"))
     b[0] |= 0x80 | (0x20 if _fq2_gt((y0, y1), ((-y0) % field.p, (-y1) % field.p)) else 0)
     return bytes(b)
@@ -250,7 +305,37 @@ def _fq2_sqrt(p, a):
     return (x0, a1 * pow(2 * x0, -1, p) % p)
 
 
-def deser_g1(field, b):
+def _deser_g1_uncompressed(field, b):
+    """deser_g1_uncompressed of host/wire.hpp on integers (without the subgroup check, as deser_g1 here)"""
+    p = field.p
+    if field.curve == "bls12_381":
+        if len(b) != 96 or b[0] & 0x80 or (b[0] & 0x20 and not b[0] & 0x40):
+            raise ValueError("G1: not an uncompressed point")
+        if b[0] & 0x20:
+            raise ValueError("G1: sign bit on the point at infinity")
+        inf, curve_b = bool(b[0] & 0x40), 4
+        x, y = int.from_bytes(bytes([b[0] & 0x1F]) + b[1:48], "big"), int.from_bytes(b[48:], "big")
+    else:
+        if len(b) != 64:
+            raise ValueError("G1: wrong length")
+        if b[63] & 0xC0 == 0xC0:
+            raise ValueError("G1: both flag bits set")
+        inf, curve_b = bool(b[63] & 0x40), 3
+        x, y = int.from_bytes(b[:32], "little"), int.from_bytes(b[32:63] + bytes([b[63] & 0x3F]), "little")
+    if inf:
+        if x or y:
+            raise ValueError("G1: non-canonical encoding of the point at infinity")
+        return None
+    if x >= p or y >= p:
+        raise ValueError("G1: coordinate >= p")
+    if (y * y - x * x * x - curve_b) % p:
+        raise ValueError("G1: not on the curve")
+    return (x, y)
+
+
+def deser_g1(field, b, form="compressed"):
+    if _check_form(form):
+        return _deser_g1_uncompressed(field, bytes(b))
     p = field.p
     if field.curve == "bls12_381":
         if len(b) != 48 or not b[0] & 0x80:
@@ -270,20 +355,51 @@ def deser_g1(field, b):
     return (x, p - y if (y > (p - 1) // 2) != larger else y)
 
 
-def deser_g2(field, b):
-    p = field.p
-    if field.curve != "bls12_381" or len(b) != 96 or not b[0] & 0x80:
-        raise ValueError("G2: not a compressed BLS12-381 point")
-    if b[0] & 0x40:
+def deser_g2(field, b, form="compressed"):
+    """The inverse of ser_g2 on either curve and form (on the twist; no subgroup check, as deser_g1 here)."""
+    p, long, b = field.p, _check_form(form), bytes(b)
+    bls = field.curve == "bls12_381"
+    n = 48 if bls else 32
+    if len(b) != (4 if long else 2) * n:
+        raise ValueError("G2: wrong length")
+    if bls:
+        flags = b[0]
+        if bool(flags & 0x80) == long or (long and flags & 0x20):
+            raise ValueError("G2: not %s point" % ("an uncompressed" if long else "a compressed BLS12-381"))
+        larger = bool(flags & 0x20)
+        body = bytes([b[0] & 0x1F]) + b[1:]
+        co = [int.from_bytes(body[n * k:n * (k + 1)], "big") for k in range(len(b) // n)]
+        x1, x0 = co[0], co[1]
+        y_in = (co[3], co[2]) if long else None
+    else:
+        flags = b[-1]
+        if flags & 0xC0 == 0xC0:
+            raise ValueError("G2: both flag bits set")
+        larger = bool(flags & 0x80)
+        body = b[:-1] + bytes([b[-1] & 0x3F])
+        co = [int.from_bytes(body[n * k:n * (k + 1)], "little") for k in range(len(b) // n)]
+        x0, x1 = co[0], co[1]
+        y_in = (co[2], co[3]) if long else None
+    if flags & 0x40:
+        if any(co):
+            raise ValueError("G2: non-canonical encoding of the point at infinity")
         return None
-    x1, x0 = int.from_bytes(bytes([b[0] & 0x1F]) + b[1:48], "big"), int.from_bytes(b[48:], "big")
+    if any(v >= p for v in co):
+        raise ValueError("G2: coordinate >= p")
+    tb = _twist_b(field)
     xx = ((x0 * x0 - x1 * x1) % p, 2 * x0 * x1 % p)
     x3 = ((xx[0] * x0 - xx[1] * x1) % p, (xx[0] * x1 + xx[1] * x0) % p)
-    y = _fq2_sqrt(p, ((x3[0] + FQ2_B[0]) % p, (x3[1] + FQ2_B[1]) % p))
+    rhs = ((x3[0] + tb[0]) % p, (x3[1] + tb[1]) % p)
+    if long:
+        y0, y1 = y_in
+        if ((y0 * y0 - y1 * y1) % p, 2 * y0 * y1 % p) != rhs:
+            raise ValueError("G2: not on the twist")
+        return ((x0, x1), (y0, y1))
+    y = _fq2_sqrt(p, rhs)
     if y is None:
         raise ValueError("G2: not on the twist")
     neg = ((-y[0]) % p, (-y[1]) % p)
-    return ((x0, x1), neg if _fq2_gt(y, neg) != bool(b[0] & 0x20) else y)
+    return ((x0, x1), neg if _fq2_gt(y, neg) != larger else y)
 
 
 def _csr_rows(field, csr, nr):
@@ -308,15 +424,17 @@ class VerifyingKey:
         self.field, self.one_g1, self.one_g2, self.x_g2, self.z_g2 = field, one_g1, one_g2, x_g2, z_g2
         self.n, self.m0, self.sigma, self.omega = n, m0, sigma, omega
 
-    def to_bytes(self):
+    def to_bytes(self, form="compressed"):
+        """VerifyingKey::serialize_compressed (392 / 280 bytes) or, form="uncompressed", serialize_uncompressed (728 / 504)."""
         f = self.field
-        return (ser_g1(f, self.one_g1) + ser_g2(f, self.one_g2) + ser_g2(f, self.x_g2) + ser_g2(f, self.z_g2) +
+        return (ser_g1(f, self.one_g1, form) + ser_g2(f, self.one_g2, form) + ser_g2(f, self.x_g2, form) + ser_g2(f, self.z_g2, form) +
                 _u64(self.n) + _u64(self.m0) + _u64(self.sigma) + ser_fr(f, self.omega))
 
     @classmethod
-    def read(cls, field, rd):
-        g1n = 48 if field.curve == "bls12_381" else 32
-        one_g1, one_g2, x_g2, z_g2 = deser_g1(field, rd.take(g1n)), deser_g2(field, rd.take(96)), deser_g2(field, rd.take(96)), deser_g2(field, rd.take(96))
+    def read(cls, field, rd, form="compressed"):
+        g1n, g2n = g1_bytes(field, form), g2_bytes(field, form)
+        one_g1 = deser_g1(field, rd.take(g1n), form)
+        one_g2, x_g2, z_g2 = deser_g2(field, rd.take(g2n), form), deser_g2(field, rd.take(g2n), form), deser_g2(field, rd.take(g2n), form)
         n, m0, sigma = rd.u64(), rd.u64(), rd.u64()
         return cls(field, one_g1, one_g2, x_g2, z_g2, n, m0, sigma, int.from_bytes(rd.take(32), "little"))
 
@@ -684,21 +802,36 @@ class Polymath:
 
     # ---- the same wire format with the points on the device (pm_pk_load_bytes / pm_pk_export_bases_compressed): both curves
     VK_BYTES = {"bls12_381": 392, "bn254": 280}             # VerifyingKey::serialize_compressed: the key's first field
+    VK_BYTES_UNCOMPRESSED = {"bls12_381": 728, "bn254": 504}   # VerifyingKey::serialize_uncompressed
 
-    def pk_load_bytes(self, data, validate=True, shard_rank=0, shard_count=1, layout="pairs"):
+    def vk_bytes_len(self, form="compressed"):
+        return (self.VK_BYTES_UNCOMPRESSED if _check_form(form) else self.VK_BYTES)[self.curve]
+
+    def vk_transcode(self, vk_bytes, form_from, form_to):
+        """A vk's bytes from one form into the other (verify and make_vk speak the compressed form only)."""
+        rd = _Reader(vk_bytes)
+        vk = VerifyingKey.read(self.field, rd, form_from)
+        if rd.o != len(rd.b):
+            raise ValueError("trailing bytes after the verifying key")
+        return vk.to_bytes(form_to)
+
+    def pk_load_bytes(self, data, validate=True, shard_rank=0, shard_count=1, layout="pairs", form="compressed"):
         """ProvingKey::serialize_compressed bytes (bytes, memoryview or an np.memmap of the file) -> (device-resident ProvingKey,
         vk bytes).  The points are decoded on the GPU; validate = ark's Validate::Yes (subgroup check on BLS12-381), False =
-        deserialize_compressed_unchecked.  The vk is returned as its bytes (the key's prefix) on both curves: verify takes bytes."""
-        pk = api.ProvingKey.load_bytes(self.ctx, self.curve, data, validate, shard_rank, shard_count, layout)
+        deserialize_compressed_unchecked.  The vk is returned as its bytes (the key's prefix) on both curves: verify takes bytes.
+        form="uncompressed": serialize_uncompressed bytes; the prefix returned is then the 728 / 504-byte uncompressed vk (vk_transcode
+        gives the compressed bytes verify takes)."""
+        pk = api.ProvingKey.load_bytes(self.ctx, self.curve, data, validate, shard_rank, shard_count, layout, form)
         pk.omega = self.field.fr_int(pk.omega_limbs)
-        return pk, bytes(memoryview(data)[:self.VK_BYTES[self.curve]])
+        return pk, bytes(memoryview(data)[:self.vk_bytes_len(form)])
 
-    def pk_serialize(self, pk, r1cs, vk_bytes):
+    def pk_serialize(self, pk, r1cs, vk_bytes, form="compressed"):
         """ProvingKey::serialize_compressed of a resident key, the six vectors encoded on the GPU (equals pk_to_bytes on
-        BLS12-381).  vk_bytes: VerifyingKey::serialize_compressed (VerifyingKey.to_bytes, or api.make_vk on either curve)."""
+        BLS12-381).  vk_bytes: VerifyingKey::serialize_compressed (VerifyingKey.to_bytes, or api.make_vk on either curve).
+        form="uncompressed": serialize_uncompressed; vk_bytes is then the vk in that form (VerifyingKey.to_bytes(form), vk_transcode)."""
         f = self.field
-        if len(vk_bytes) != self.VK_BYTES[self.curve]:
-            raise ValueError("vk_bytes: %d bytes, expected %d" % (len(vk_bytes), self.VK_BYTES[self.curve]))
+        if len(vk_bytes) != self.vk_bytes_len(form):
+            raise ValueError("vk_bytes: %d bytes, expected %d" % (len(vk_bytes), self.vk_bytes_len(form)))
         if isinstance(r1cs, LimbCircuit):     # matrices as limb arrays (synthetic_r1cs_native): rows read back from the CSR
             mats = [_csr_rows(f, m, r1cs.nr) for m in r1cs.csrs]
         else:
@@ -706,7 +839,7 @@ class Polymath:
         out = [bytes(vk_bytes), _u64(r1cs.m0), _u64(r1cs.mw), _u64(r1cs.nr)] + [ser_matrix(f, m) for m in mats]
         for which in PK_WIRE_VECTORS:
             out.append(_u64(pk.base_lens[which]))
-            out.append(pk.export_bases_compressed(which))
+            out.append(pk.export_bases_compressed(which, form=form))
         return b"".join(out)
 
     # ---- common.rs:21-71

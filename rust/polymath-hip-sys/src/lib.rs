@@ -70,6 +70,9 @@ pub const PM_G1_NOT_ON_CURVE: u8 = 3;
 pub const PM_G1_NOT_IN_SUBGROUP: u8 = 4;
 pub const PM_G1_NONCANONICAL_INF: u8 = 5;
 pub const PM_G1_INF_SIGN: u8 = 6;
+// pm_wire_form: a flag OR-ed into `validate` (pm_g1_decode, pm_pk_load_bytes) and `which` (pm_pk_export_bases_compressed)
+pub const PM_WIRE_COMPRESSED: i32 = 0;
+pub const PM_WIRE_UNCOMPRESSED: i32 = 256;
 
 // pm_verify_verdict
 pub const PM_VERIFY_REJECTED: u8 = 0;

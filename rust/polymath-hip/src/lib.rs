@@ -721,8 +721,20 @@ impl GpuKey {
     /// `pm_pk_load_bytes`: a key file's bytes (`ProvingKey::serialize_compressed`, e.g. an mmap) straight to the device; the
     /// points are decoded there, with `validate` as ark's `Validate::Yes`.  A refused key names its first bad point in the error.
     pub fn load_bytes<E: Pairing>(ctx: &mut Context, bytes: &[u8], validate: bool) -> Result<GpuKey, HipError> {
+        Self::load_bytes_form::<E>(ctx, bytes, validate, WireForm::Compressed)
+    }
+
+    /// [`GpuKey::load_bytes`] for either record form: [`WireForm::Uncompressed`] takes `ProvingKey::serialize_uncompressed` bytes
+    /// (96 / 64-byte G1 records, vk prefix 728 / 504 bytes).  The curve equation is checked in every mode; `validate` adds the
+    /// subgroup check.  Bytes of the other form are refused as a malformed key: the form is never guessed.
+    pub fn load_bytes_form<E: Pairing>(ctx: &mut Context, bytes: &[u8], validate: bool, form: WireForm) -> Result<GpuKey, HipError> {
         let curve = curve_checked::<E>()?;
-        let vk_len = if curve.id() == sys::PM_BLS12_381 { 392 } else { 280 };
+        let vk_len = match (curve.id() == sys::PM_BLS12_381, form) {
+            (true, WireForm::Compressed) => 392,
+            (true, WireForm::Uncompressed) => 728,
+            (false, WireForm::Compressed) => 280,
+            (false, WireForm::Uncompressed) => 504,
+        };
         let header = |k: usize| bytes.get(vk_len + 8 * k..vk_len + 8 * k + 8).map(|b| u64::from_le_bytes(b.try_into().unwrap()));
         let (m0, mw) = match (header(0), header(1)) {
             (Some(m0), Some(mw)) => (m0, mw),
@@ -730,7 +742,7 @@ impl GpuKey {
         };
         let mut raw = core::ptr::null_mut();
         // SAFETY: `bytes` outlives the call and is only read; the library keeps no pointer to it.
-        let rc = unsafe { sys::pm_pk_load_bytes(ctx.raw, curve.id(), bytes.as_ptr(), bytes.len(), validate as i32, 0, 1, sys::PM_SHARD_PAIRS, &mut raw) };
+        let rc = unsafe { sys::pm_pk_load_bytes(ctx.raw, curve.id(), bytes.as_ptr(), bytes.len(), validate as i32 | form as i32, 0, 1, sys::PM_SHARD_PAIRS, &mut raw) };
         ctx.check(rc)?;
         Ok(GpuKey { raw, curve, m0, mw })
     }
@@ -1010,6 +1022,19 @@ impl GpuKey {
         Ok(KeyInfo { n, m0, sigma, omega: fr_from_raw::<E>(curve, omega), base_lens })
     }
 
+    /// `pm_pk_export_bases_compressed`: one base vector as the point records of a key file, encoded on the device -- 48 / 32 bytes
+    /// a point in [`WireForm::Compressed`], 96 / 64 in [`WireForm::Uncompressed`] (`which | PM_WIRE_UNCOMPRESSED`).
+    pub fn export_bases_bytes<E: Pairing>(&self, ctx: &mut Context, which: BaseVec, form: WireForm) -> Result<Vec<u8>, HipError> {
+        let info = self.info::<E>()?;
+        let total = info.base_lens[which as usize] as usize;
+        let record = 8 * self.curve.fq_limbs() * if form == WireForm::Uncompressed { 2 } else { 1 };
+        let mut out = vec![0u8; record * total];
+        // SAFETY: `out` holds `total` records of the form's size.
+        let rc = unsafe { sys::pm_pk_export_bases_compressed(ctx.raw, self.raw, which as i32 | form as i32, 0, total, out.as_mut_ptr()) };
+        ctx.check(rc)?;
+        Ok(out)
+    }
+
     /// `pm_pk_export_bases`: one base vector back on the host as `Vec<E::G1Affine>`, ready for a `ProvingKey<E>` field.  The
     /// device hands over `x || y` in Montgomery form (16 * fq_limbs bytes per point, the identity as all-zero x, y); records are
     /// rebuilt with `Affine::new_unchecked` / `Affine::identity()` -- no decompression, no subgroup check (the points were
@@ -1054,6 +1079,14 @@ impl GpuKey {
     pub fn raw(&self) -> *const sys::pm_pk {
         self.raw
     }
+}
+
+/// `pm_wire_form`: the record form of a key's points, a flag OR-ed into `validate` / `which`
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum WireForm {
+    Compressed = sys::PM_WIRE_COMPRESSED,
+    Uncompressed = sys::PM_WIRE_UNCOMPRESSED,
 }
 
 /// `pm_shard_layout`

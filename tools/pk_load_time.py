@@ -1,13 +1,16 @@
 """Time pm_pk_load_bytes: a ProvingKey::serialize_compressed byte string -> resident key, points decoded on the GPU.
 
-    python tools/pk_load_time.py [--log-gates 20] [--out FILE]
+    python tools/pk_load_time.py [--log-gates 20] [--form compressed|uncompressed|both] [--out FILE]
 
 BLS12-381, 2^k - 100 synthetic gates (k = 20: 27.3 M points).  The key is generated on the device and serialised with
 Polymath.pk_serialize; after one warm-up, pm_pk_load_bytes is timed three times each with validate 1 and 0 (each run ends
 with a stream synchronisation on the loading context), once more with the window tables off (tables = load - that), and
 pm_pk_load from already-decoded arrays is timed as today's path without its decoding cost.  The host baseline is
 tools/host_deser_time.cpp (the host mirror's deser_g1, one thread) on 10 000 of the key's records, scaled to the key.
-The decode kernel's own time comes from a separate `rocprofv3 --kernel-trace --stats` run of this script (--profile-only)."""
+The decode kernel's own time comes from a separate `rocprofv3 --kernel-trace --stats` run of this script (--profile-only).
+--form uncompressed times the same key as ProvingKey::serialize_uncompressed bytes (pm_pk_load_bytes with PM_WIRE_UNCOMPRESSED:
+96-byte records, no square root); --form both times the two byte strings in one process, form by form within every setting, and
+--loads-only leaves out the decoded-array and host baselines."""
 import argparse
 import os
 import struct
@@ -24,6 +27,8 @@ ap.add_argument("--log-gates", type=int, default=20)
 ap.add_argument("--out", default=None)
 ap.add_argument("--chunk-logs", default="", help="comma list of wire_chunk_log values to time once each (validate 1)")
 ap.add_argument("--profile-only", action="store_true", help="one validated load and nothing else (under rocprofv3)")
+ap.add_argument("--form", choices=("compressed", "uncompressed", "both"), default="compressed")
+ap.add_argument("--loads-only", action="store_true", help="no pm_pk_load-from-arrays and no host baseline")
 args = ap.parse_args()
 
 from polymath_amd import api, circuits as PC            # noqa: E402
@@ -47,10 +52,15 @@ x, z = g.fr(c_r), g.fr(c_r)
 t = time.perf_counter()
 pk = pm.setup(lc, x, z)
 say("key: %d gates, n = %d, %d points; generated in %.2f s" % (nr, pk.n, sum(pk.base_lens), time.perf_counter() - t))
-t = time.perf_counter()
-data = pm.pk_serialize(pk, lc, pm.make_vk(pk, x, z))
-say("pk_serialize: %d bytes in %.2f s (matrices serialised in Python)" % (len(data), time.perf_counter() - t))
-decoded = None if args.profile_only else [pk.export_bases(v) for v in range(6)]
+forms = ("compressed", "uncompressed") if args.form == "both" else (args.form,)
+vk = pm.make_vk(pk, x, z)
+blobs = {}
+for form in forms:
+    t = time.perf_counter()
+    blobs[form] = pm.pk_serialize(pk, lc, vk if form == "compressed" else pm.vk_transcode(vk, "compressed", form), form=form)
+    say("pk_serialize %s: %d bytes in %.2f s (matrices serialised in Python)" % (form, len(blobs[form]), time.perf_counter() - t))
+data = blobs.get("compressed")
+decoded = None if args.profile_only or args.loads_only else [pk.export_bases(v) for v in range(6)]
 pk.free()
 
 
@@ -58,9 +68,9 @@ def sync(k):
     k.export_bases(1, 0, 1)          # a stream synchronisation on the loading context
 
 
-def load(validate):
+def load(validate, form=forms[0]):
     t0 = time.perf_counter()
-    k = api.ProvingKey.load_bytes(pm.ctx, curve, data, validate)
+    k = api.ProvingKey.load_bytes(pm.ctx, curve, blobs[form], validate, form=form)
     sync(k)
     dt = time.perf_counter() - t0
     k.free()
@@ -68,24 +78,35 @@ def load(validate):
 
 
 if args.profile_only:
-    say("validated load: %.3f s" % load(True))
+    for form in forms:
+        say("validated load, %s: %.3f s" % (form, load(True, form)))
+        say("unvalidated load, %s: %.3f s" % (form, load(False, form)))
     sys.exit(0)
 
-load(True)                            # warm-up
+for form in forms:
+    load(True, form)                  # warm-up
 for validate in (1, 0):
-    ts = [load(bool(validate)) for _ in range(3)]
-    say("pm_pk_load_bytes validate=%d: %s s (best %.3f)" % (validate, " ".join("%.3f" % v for v in ts), min(ts)))
+    for form in forms:
+        ts = [load(bool(validate), form) for _ in range(3)]
+        say("pm_pk_load_bytes %s validate=%d: %s s (best %.3f)" % (form, validate, " ".join("%.3f" % v for v in ts), min(ts)))
 tables = pm.ctx.get_option("tables")
 pm.ctx.set_option("tables", "off")
 for validate in (1, 0):
-    ts = [load(bool(validate)) for _ in range(2)]
-    say("pm_pk_load_bytes validate=%d, tables off: %s s" % (validate, " ".join("%.3f" % v for v in ts)))
+    for form in forms:
+        ts = [load(bool(validate), form) for _ in range(3)]
+        say("pm_pk_load_bytes %s validate=%d, tables off: %s s" % (form, validate, " ".join("%.3f" % v for v in ts)))
 pm.ctx.set_option("tables", tables)
 for cl in [int(v) for v in args.chunk_logs.split(",") if v]:
     old = pm.ctx.get_option("wire_chunk_log")
     pm.ctx.set_option("wire_chunk_log", cl)
-    say("pm_pk_load_bytes validate=1, wire_chunk_log=%d: %.3f s" % (cl, load(True)))
+    for form in forms:
+        say("pm_pk_load_bytes %s validate=1, wire_chunk_log=%d: %.3f s" % (form, cl, load(True, form)))
     pm.ctx.set_option("wire_chunk_log", old)
+if args.loads_only or data is None:   # the baselines below are the compressed form's
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
 A, B, C = lc.csrs
 for _ in range(2):
     t0 = time.perf_counter()
