@@ -267,6 +267,37 @@ typedef enum pm_g1_status {       /* one verdict per point; the text is deser_g1
  * One thing changes in the letter: a value with bit 8 set used to read as plain "validate"; no caller in this tree passes anything
  * but 0 or 1. */
 typedef enum pm_wire_form { PM_WIRE_COMPRESSED = 0, PM_WIRE_UNCOMPRESSED = 256 } pm_wire_form;
+/* Point validation says that every point of a key file is a point; it does not say that the points are a proving key.  Vectors of
+ * one circuit beside the matrices of another, an [x]_2 of another ceremony, one record overwritten by another valid point: such a
+ * file loads, proves at full speed, and no verifier accepts its proofs.  PM_KEY_CHECK_RELATIONS is a FLAG, OR-ed into the `validate`
+ * argument of pm_pk_load_bytes only; there is no entry point of its own.  With it the loader decides, after the point verdicts and
+ * BEFORE the window tables are built (a refused key does not pay for tables), whether the bytes are what generate_proving_key
+ * (generator.rs:66-137) would have produced for SOME (x, z): every base vector is a fixed function of x, z and the key's own SAP
+ * matrices, and the key carries [1]_1, [1]_2, [x]_2, [z]_2 as its vk prefix.  With a = 3, g = 5, s = sigma, T = x_powers_y_gamma_z_g1,
+ * fresh 128-bit weights rho, and every check of the form e(A, [1]_2) e(B, [x]_2) e(C, [z]_2) = 1, in this order:
+ *    0     x_powers_g1[0] == vk.one_g1                                       "x_powers_g1: the first entry is not vk.one_g1"
+ *    1-5   per power vector V, in pm_base_vec order (x_powers_g1, x_powers_y_alpha_g1, x_powers_y_gamma_g1, x_powers_y_gamma_z_g1,
+ *          x_powers_zh_by_y_alpha_g1):  e(sum rho_i V[i+1], [1]_2) = e(sum rho_i V[i], [x]_2)
+ *                                                                            "<vector>: consecutive entries are not in ratio x"
+ *    6-9   anchors:  e(T[g s], [1]_2) = e(one_g1, [z]_2);  e(x_powers_y_gamma_g1[0], [z]_2) = e(T[0], [1]_2);
+ *          e(x_powers_y_alpha_g1[0], [z]_2) = e(T[(g - a) s], [1]_2);
+ *          e(x_powers_zh_by_y_alpha_g1[0], [z]_2) = e(T[n + (a + g) s] - T[(a + g) s], [1]_2)
+ *                                   "<vector>: is not anchored to vk.one_g1 and vk.z_g2"  (in the order T, y_gamma, y_alpha, zh)
+ *    10    e(sum_j rho_j uj_wj_lcs[j], [z]_2) = e(sum_k U_k T[k + a s] + sum_k W_k T[k + (a + g) s], [1]_2), U = sum_j rho_j u_j,
+ *          W = sum_j rho_j w_j over every SAP column j >= m0 (common.rs:138-207, first entry of a repeated column)
+ *                                                                            "uj_wj_lcs_by_y_alpha_g1: does not match the SAP matrices"
+ * A key that fails a relation is refused exactly as a key with a bad point is refused: PM_ERR_INVALID_ARG, no handle, nothing stays
+ * allocated, and pm_last_error is "pm_pk_load_bytes: " and the text of the FIRST failing relation in the order above.  The weights:
+ * 32 bytes from the operating system (getrandom(2)) per call, expanded on the device by ChaCha12 (block counter = weight index); the
+ * key's bytes are fixed before the draw, so a false key passes with probability about 2^-128.  A load that gets no random bytes is
+ * refused with PM_ERR_STATE.  The sums are MSMs over the plain resident points, two inverse transforms and ONE launch of the 36-lane
+ * pairing check (polymath_amd/csrc/key_check.hip; polymath_amd/host/key_check.hpp is the same decision on the CPU).
+ * The sentence above stays literally true: validation is on iff (validate & ~256) != 0, so the flag implies point validation -- the
+ * relations mean nothing on points outside the subgroup, and a caller passing 512 before the flag existed already got plain
+ * validation.  It combines with PM_WIRE_UNCOMPRESSED.  pm_g1_decode ignores it, as it always did.  With shard_count > 1 (or
+ * PM_SHARD_VECTOR) the flag is PM_ERR_INVALID_ARG: the check needs whole vectors.  Out of scope: sharded keys; checking a key that is
+ * already resident from pm_pk_load; a caller-supplied seed; a vk supplied separately from the key. */
+typedef enum pm_key_check { PM_KEY_CHECK_NONE = 0, PM_KEY_CHECK_RELATIONS = 512 } pm_key_check;
 /* Batch decode, host to host: `count` packed records of 48 (BLS12-381) / 32 (BN254) bytes -- 96 / 64 with PM_WIRE_UNCOMPRESSED
  * in `validate` -- -> out_xy (x||y Montgomery, 2*fq_limbs
  * u64 per point; infinity and every refused point x = y = 0) and one pm_g1_status byte per point.  PM_OK even when points are bad:

@@ -29,6 +29,8 @@ G1_BYTES = {PM_BLS12_381: 48, PM_BN254: 32}                # compressed record o
 # pm_wire_form: a flag OR-ed into `validate` (pm_g1_decode, pm_pk_load_bytes) and `which` (pm_pk_export_bases_compressed)
 PM_WIRE_COMPRESSED, PM_WIRE_UNCOMPRESSED = 0, 256
 WIRE_FORMS = {"compressed": PM_WIRE_COMPRESSED, "uncompressed": PM_WIRE_UNCOMPRESSED}
+# pm_key_check: a flag OR-ed into pm_pk_load_bytes' `validate` -- the key's relations against its own vk and matrices (implies validation)
+PM_KEY_CHECK_NONE, PM_KEY_CHECK_RELATIONS = 0, 512
 
 
 def g1_record_bytes(curve_id, form="compressed"):
@@ -688,13 +690,15 @@ class ProvingKey:
         return pk
 
     @classmethod
-    def load_bytes(cls, ctx, curve, data, validate=True, shard_rank=0, shard_count=1, layout="pairs", form="compressed"):
+    def load_bytes(cls, ctx, curve, data, validate=True, shard_rank=0, shard_count=1, layout="pairs", form="compressed", relations=False):
         """pm_pk_load_bytes: ProvingKey::serialize_compressed (form="uncompressed": serialize_uncompressed) bytes -> resident key;
         the points are decoded (and with `validate` checked as ark's Validate::Yes does) on the device.  data: bytes, memoryview or
-        np.memmap of a key file, not copied."""
+        np.memmap of a key file, not copied.  relations: PM_KEY_CHECK_RELATIONS -- the key is also checked against its own vk and
+        matrices (validation included) and refused, naming the first relation that fails, if it is not a proving key."""
         keep, addr, nbytes = _byte_view(data)
         h = ct.c_void_p()
-        ctx.check(ctx.L.pm_pk_load_bytes(ctx.h, CURVE_IDS[curve], ct.c_void_p(addr), nbytes, int(bool(validate)) | WIRE_FORMS[form], shard_rank, shard_count,
+        flags = int(bool(validate)) | WIRE_FORMS[form] | (PM_KEY_CHECK_RELATIONS if relations else PM_KEY_CHECK_NONE)
+        ctx.check(ctx.L.pm_pk_load_bytes(ctx.h, CURVE_IDS[curve], ct.c_void_p(addr), nbytes, flags, shard_rank, shard_count,
                                          LAYOUTS[layout], ct.byref(h)))
         del keep
         pk = cls(ctx, curve, h, None)

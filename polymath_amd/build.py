@@ -13,8 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libpolymath_hip.so")
-SOURCES = ["api.hip", "ntt.hip", "msm.hip", "msm_reduce.hip", "prove.hip", "setup.hip", "host_prove.hip", "synth.hip", "comm.hip", "prove_sharded.hip", "selftest.hip", "g1_codec.hip", "verify_batch.hip", "pairing_batch.hip", "pairing_wave.hip", "prove_batch.hip", "r1cs_check.hip", "challenges.hip", "solve.hip", "prove_glue.hip"]
-HEADERS = ["field.cuh", "divrem.cuh", "sqrt.cuh", "solve_steps.cuh", "ec.cuh", "fq28.cuh", "constants.cuh", "internal.h", "radix.cuh", "msm_plan.h", os.path.join("..", "host", "hashes.hpp"), os.path.join("..", "host", "polymath.hpp"), os.path.join("..", "host", "pairing.hpp"), os.path.join("..", "host", "wire.hpp"), os.path.join("..", "host", "layout.hpp"), os.path.join("..", "host", "key_plan.hpp"),os.path.join("..", "host", "rng.hpp"), os.path.join("..", "host", "solve_plan.hpp"), "comm.h", "prove_common.cuh", "prove_kernels.cuh", "verify_batch.cuh", "pairing.cuh", "pairing_wave.cuh", "transcript.cuh", "batch_row.cuh", "g1_record.cuh",
+SOURCES = ["api.hip", "ntt.hip", "msm.hip", "msm_reduce.hip", "prove.hip", "setup.hip", "host_prove.hip", "synth.hip", "comm.hip", "prove_sharded.hip", "selftest.hip", "g1_codec.hip", "verify_batch.hip", "pairing_batch.hip", "pairing_wave.hip", "prove_batch.hip", "r1cs_check.hip", "challenges.hip", "solve.hip", "prove_glue.hip", "key_check.hip"]
+HEADERS = ["field.cuh", "divrem.cuh", "sqrt.cuh", "solve_steps.cuh", "ec.cuh", "fq28.cuh", "constants.cuh", "internal.h", "radix.cuh", "msm_plan.h", os.path.join("..", "host", "hashes.hpp"), os.path.join("..", "host", "polymath.hpp"), os.path.join("..", "host", "pairing.hpp"), os.path.join("..", "host", "wire.hpp"), os.path.join("..", "host", "layout.hpp"), os.path.join("..", "host", "key_plan.hpp"), os.path.join("..", "host", "key_check.hpp"), os.path.join("..", "host", "rng.hpp"), os.path.join("..", "host", "solve_plan.hpp"), "comm.h", "prove_common.cuh", "prove_kernels.cuh", "verify_batch.cuh", "pairing.cuh", "pairing_wave.cuh", "transcript.cuh", "batch_row.cuh", "g1_record.cuh",
            os.path.join("..", "..", "include", "polymath_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-ffp-contract=off"]

@@ -10,11 +10,14 @@
 #include <new>
 #include <thread>
 
+#include <sys/random.h>
+
 #include "internal.h"
 #include "comm.h"
 #include "fq28.cuh"
 #include "prove_common.cuh"
 #include "../host/hashes.hpp"
+#include "../host/key_check.hpp"
 
 using namespace pm;
 
@@ -580,7 +583,8 @@ static int pk_build_tables(pm_ctx *ctx, pm_pk *pk) {
 //   planned(st, pk)   after key_plan, with its status: the caller's own checks of the shape; returns the status to go on with
 //   uploaded(st, pk)  after pk_upload_matrices, likewise: what the caller prepares once the matrices are resident
 //   fill(vec, start, count, dst)   points [start, start + count) of base vector `vec` to the device at dst, in the internal form
-//   filled()          between the fill and the tables: the byte loader reads its verdicts and frees its staging -- the tables want the memory
+//   filled(pk)        between the fill and the tables: the byte loader reads its verdicts, frees its staging -- the tables want the
+//                     memory -- and, asked to, checks the key's relations on the plain resident points (key_check.hip)
 template <class C, class Planned, class Uploaded, class Fill, class Filled>
 static int pk_build(pm_ctx *ctx, uint64_t m0, uint64_t mw, uint64_t nr, int shard_rank, int shard_count, int layout, const pm_csr *a, const pm_csr *b,
                     const pm_csr *c, Planned planned, Uploaded uploaded, Fill fill, Filled filled, pm_pk **out) {
@@ -607,13 +611,13 @@ static int pk_build(pm_ctx *ctx, uint64_t m0, uint64_t mw, uint64_t nr, int shar
         return count ? for_cat_range<C>(pk.get(), lo, lo + count, (Affine<C> *)pk->d_bases + at, fill) : (int)PM_OK;
     }));
     PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    PM_TRY(filled());
+    PM_TRY(filled(*pk));
     PM_TRY(pk_build_tables<C>(ctx, pk.get()));
     *out = pk.release();
     return PM_OK;
 }
 static int pk_pass(int st, const pm_pk &) { return st; }   // a caller of pk_build with nothing to do at a step
-static int pk_nothing() { return PM_OK; }
+static int pk_nothing(const pm_pk &) { return PM_OK; }
 
 // The way in of all three: the device, the curve, and a host exception while the key is read or built (bad_alloc in the parse of the
 // bytes, in a matrix copy, in the plan's vectors) as a status with the message in pm_last_error, never an abort.
@@ -670,9 +674,7 @@ extern "C" int pm_pk_load(pm_ctx *ctx, int curve, uint64_t n, uint64_t m0, uint6
 }
 
 // ---- keys as bytes (ProvingKey::serialize_compressed; g1_codec.hip decodes the points)
-static const char *const BASE_VEC_NAMES[PM_NUM_BASE_VECS] = {"x_powers_g1", "x_powers_y_alpha_g1", "x_powers_y_gamma_g1",
-                                                             "x_powers_y_gamma_z_g1", "x_powers_zh_by_y_alpha_g1",
-                                                             "uj_wj_lcs_by_y_alpha_g1"};
+static const char *const *const BASE_VEC_NAMES = pmhost::KEY_VEC_NAMES;   // host/key_check.hpp: the relation texts name the same vectors
 static const int WIRE_VECTOR_ORDER[PM_NUM_BASE_VECS] = {PM_X_POWERS, PM_X_POWERS_Y_ALPHA, PM_X_POWERS_ZH_BY_Y_ALPHA, PM_X_POWERS_Y_GAMMA,
                                                         PM_X_POWERS_Y_GAMMA_Z, PM_UJ_WJ_LCS_BY_Y_ALPHA};   // data_structures.rs:60-72
 
@@ -694,10 +696,13 @@ static int pk_load_bytes_impl(pm_ctx *ctx, const uint8_t *bytes, size_t len, int
                               pm_pk **out) {
     const int form = validate & PM_WIRE_UNCOMPRESSED;   // bit 8 selects the record form; validation is every other bit
     validate &= ~PM_WIRE_UNCOMPRESSED;
+    const bool relations = (validate & PM_KEY_CHECK_RELATIONS) != 0;   // one of those other bits: the relation check implies validation
     const size_t NB = g1_record_bytes<C>(form);
+    auto fail = [&](int st, const std::string &why) { if (!why.empty()) ctx->err = "pm_pk_load_bytes: " + why; return st; };
+    if (relations && (shard_count != 1 || layout != PM_SHARD_PAIRS))
+        return fail(PM_ERR_INVALID_ARG, "PM_KEY_CHECK_RELATIONS needs the whole key on one device: shard_count 1, PM_SHARD_PAIRS");
     WireLayout w;
     PM_TRY(pk_wire_parse<C>(bytes, len, form, w, ctx->err));
-    auto fail = [&](int st, const std::string &why) { if (!why.empty()) ctx->err = "pm_pk_load_bytes: " + why; return st; };
     pm_csr m[3];
     for (int k = 0; k < 3; ++k) {
         if (w.col[k].empty()) { w.col[k].push_back(0); w.val[k].assign(4, 0); }   // non-null pointers for an empty matrix
@@ -753,7 +758,7 @@ static int pk_load_bytes_impl(pm_ctx *ctx, const uint8_t *bytes, size_t len, int
             }
             return PM_OK;
         },
-        [&]() -> int {
+        [&](const pm_pk &pk) -> int {
             unsigned long long h_bad[PM_NUM_BASE_VECS];
             if (hipMemcpy(h_bad, d_bad.p, sizeof(h_bad), hipMemcpyDeviceToHost) != hipSuccess) return fail(PM_ERR_HIP, "reading the verdicts failed");
             for (int v : WIRE_VECTOR_ORDER)
@@ -761,6 +766,21 @@ static int pk_load_bytes_impl(pm_ctx *ctx, const uint8_t *bytes, size_t len, int
                     return fail(PM_ERR_INVALID_ARG, std::string(BASE_VEC_NAMES[v]) + "[" + std::to_string(h_bad[v] >> 8) + "]: " +
                                                         g1_status_text(C::ID, (int)(h_bad[v] & 0xFF), form));
             for (ScopedDevBuf &b : d_in) b.release();   // before the tables: they want the memory
+            if (!relations) return PM_OK;
+            // The loader is the verifier of this check and the key's bytes are fixed by now: the weights' seed comes from the operating
+            // system, per call, and a load that gets none is refused.
+            if (w.vk_g2_inf) return fail(PM_ERR_INVALID_ARG, "a G2 point of the vk is the point at infinity");
+            uint8_t seed[32];
+            for (size_t got = 0; got < sizeof seed;) {
+                const ssize_t r = getrandom(seed + got, sizeof seed - got, 0);
+                if (r <= 0) return fail(PM_ERR_STATE, "no random bytes from the operating system for the relation check");
+                got += (size_t)r;
+            }
+            Affine<C> one_g1;
+            memcpy((void *)&one_g1, w.vk_one_g1, sizeof one_g1);
+            int failed = pmhost::KEY_REL_NONE;
+            PM_TRY(key_check_run<C>(ctx, &pk, one_g1, w.vk_g2, seed, &failed));
+            if (failed != pmhost::KEY_REL_NONE) return fail(PM_ERR_INVALID_ARG, pmhost::key_relation_text(failed));
             return PM_OK;
         },
         out);

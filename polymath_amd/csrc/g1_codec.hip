@@ -267,6 +267,15 @@ int pk_wire_parse(const uint8_t *data, size_t len, int form, WireLayout &out, st
         out.vk_len = rd.off;
         out.n = vk.n; out.vk_m0 = vk.m0; out.sigma = vk.sigma;
         memcpy(out.omega, vk.omega.l, 32);
+        constexpr int NQ = C::FqP::N;
+        if (!vk.one_g1.inf) { memcpy(out.vk_one_g1, vk.one_g1.p.x.l, 4 * NQ); memcpy(out.vk_one_g1 + NQ, vk.one_g1.p.y.l, 4 * NQ); }
+        const typename pmhost::PairingOf<C>::type::G2 *q[3] = {&vk.one_g2, &vk.x_g2, &vk.z_g2};
+        for (int j = 0; j < 3; ++j) {
+            if (q[j]->inf) { out.vk_g2_inf = true; continue; }
+            uint32_t *g = out.vk_g2 + j * 4 * NQ;
+            memcpy(g, q[j]->x.c0.l, 4 * NQ); memcpy(g + NQ, q[j]->x.c1.l, 4 * NQ);
+            memcpy(g + 2 * NQ, q[j]->y.c0.l, 4 * NQ); memcpy(g + 3 * NQ, q[j]->y.c1.l, 4 * NQ);
+        }
         out.m0 = rd.u64(); out.mw = rd.u64(); out.nr = rd.u64();
         for (int k = 0; k < 3; ++k) {
             pmhost::CsrHost m = pmhost::WireKey<C>::get_matrix(rd);

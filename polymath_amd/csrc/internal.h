@@ -550,9 +550,20 @@ struct WireLayout {
     std::vector<uint64_t> rowptr[3], val[3];                          // a, b, c as serialised (duplicates kept), val Montgomery
     std::vector<uint32_t> col[3];
     uint64_t vec_off[PM_NUM_BASE_VECS] = {0}, vec_len[PM_NUM_BASE_VECS] = {0};   // by pm_base_vec: byte offset of point 0, points
+    // the vk's points for the relation check (key_check.hip): one_g1 as x || y (standard Montgomery; all zero = infinity) and
+    // [1]_2, [x]_2, [z]_2 packed as pairing_prepare reads them (4 Fq a point: x.c0 || x.c1 || y.c0 || y.c1); g2_inf: one of the three is the point at infinity
+    uint32_t vk_one_g1[2 * 12] = {0}, vk_g2[3 * 4 * 12] = {0};
+    bool vk_g2_inf = false;
 };
 template <class C>
 int pk_wire_parse(const uint8_t *data, size_t len, int form, WireLayout &out, std::string &err);
+
+// key_check.hip: PM_KEY_CHECK_RELATIONS.  Is the whole-resident key `pk`, its points decoded and validated but its tables not yet built,
+// what generate_proving_key would have produced for some (x, z) under the vk (one_g1; g2 = [1]_2, [x]_2, [z]_2 as pairing_prepare
+// reads them)?  *failed = the first failing relation (host/key_check.hpp: KeyRelation, key_relation_text) or KEY_REL_NONE.  seed: the 32
+// bytes the weights are expanded from.  Synchronises the stream; its device memory, the MSM workspace included, is returned.
+template <class C>
+int key_check_run(pm_ctx *ctx, const pm_pk *pk, const Affine<C> &one_g1, const uint32_t *g2, const uint8_t seed[32], int *failed);
 
 // setup.hip: the uj_wj_lcs scalars of generator.rs:112-136 on the device (Lagrange coefficients at x + the sparse pass over the
 // key's CSR matrices); `lagrange` and `work` are the caller's scratch

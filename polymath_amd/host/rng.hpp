@@ -17,26 +17,42 @@
 
 namespace pmhost {
 
-inline uint32_t chacha_rotl(uint32_t v, int c) { return (v << c) | (v >> (32 - c)); }
+// The block function is host-and-device text: the loader's relation check (csrc/key_check.hip) expands its seed with it on the GPU.
+#if defined(__HIPCC__)
+#define PM_RNG_HD __host__ __device__ inline
+#else
+#define PM_RNG_HD inline
+#endif
+
+PM_RNG_HD uint32_t chacha_rotl(uint32_t v, int c) { return (v << c) | (v >> (32 - c)); }
+PM_RNG_HD void chacha_quarter(uint32_t *x, int a, int b, int c, int d) {
+    x[a] += x[b]; x[d] = chacha_rotl(x[d] ^ x[a], 16);
+    x[c] += x[d]; x[b] = chacha_rotl(x[b] ^ x[c], 12);
+    x[a] += x[b]; x[d] = chacha_rotl(x[d] ^ x[a], 8);
+    x[c] += x[d]; x[b] = chacha_rotl(x[b] ^ x[c], 7);
+}
 
 // one ChaCha block: state = "expand 32-byte k" | key[8] | w12 w13 w14 w15 ; out = state + rounds(state)
-inline void chacha_block(const uint32_t key[8], const uint32_t tail[4], int rounds, uint32_t out[16]) {
+PM_RNG_HD void chacha_block(const uint32_t key[8], const uint32_t tail[4], int rounds, uint32_t out[16]) {
     uint32_t s[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u};
     for (int i = 0; i < 8; ++i) s[4 + i] = key[i];
     for (int i = 0; i < 4; ++i) s[12 + i] = tail[i];
     uint32_t x[16];
-    memcpy(x, s, sizeof(x));
-    auto qr = [&](int a, int b, int c, int d) {
-        x[a] += x[b]; x[d] = chacha_rotl(x[d] ^ x[a], 16);
-        x[c] += x[d]; x[b] = chacha_rotl(x[b] ^ x[c], 12);
-        x[a] += x[b]; x[d] = chacha_rotl(x[d] ^ x[a], 8);
-        x[c] += x[d]; x[b] = chacha_rotl(x[b] ^ x[c], 7);
-    };
+    for (int i = 0; i < 16; ++i) x[i] = s[i];
     for (int r = 0; r < rounds; r += 2) {
-        qr(0, 4, 8, 12); qr(1, 5, 9, 13); qr(2, 6, 10, 14); qr(3, 7, 11, 15);
-        qr(0, 5, 10, 15); qr(1, 6, 11, 12); qr(2, 7, 8, 13); qr(3, 4, 9, 14);
+        chacha_quarter(x, 0, 4, 8, 12); chacha_quarter(x, 1, 5, 9, 13); chacha_quarter(x, 2, 6, 10, 14); chacha_quarter(x, 3, 7, 11, 15);
+        chacha_quarter(x, 0, 5, 10, 15); chacha_quarter(x, 1, 6, 11, 12); chacha_quarter(x, 2, 7, 8, 13); chacha_quarter(x, 3, 4, 9, 14);
     }
     for (int i = 0; i < 16; ++i) out[i] = x[i] + s[i];
+}
+
+// Weight `index` of a 32-byte seed (key = its eight little-endian words): the first four words of ChaCha12 block `index` -- the block
+// StdRng::from_seed(seed) produces at counter = index -- read as a 128-bit integer, low word first.
+PM_RNG_HD void chacha12_weight(const uint32_t key[8], uint64_t index, uint32_t out[4]) {
+    const uint32_t tail[4] = {(uint32_t)index, (uint32_t)(index >> 32), 0u, 0u};
+    uint32_t block[16];
+    chacha_block(key, tail, 12, block);
+    for (int i = 0; i < 4; ++i) out[i] = block[i];
 }
 
 struct StdRng {   // rand::rngs::StdRng (rand 0.8) == ChaCha12Rng

@@ -815,13 +815,15 @@ class Polymath:
             raise ValueError("trailing bytes after the verifying key")
         return vk.to_bytes(form_to)
 
-    def pk_load_bytes(self, data, validate=True, shard_rank=0, shard_count=1, layout="pairs", form="compressed"):
+    def pk_load_bytes(self, data, validate=True, shard_rank=0, shard_count=1, layout="pairs", form="compressed", relations=False):
         """ProvingKey::serialize_compressed bytes (bytes, memoryview or an np.memmap of the file) -> (device-resident ProvingKey,
         vk bytes).  The points are decoded on the GPU; validate = ark's Validate::Yes (subgroup check on BLS12-381), False =
         deserialize_compressed_unchecked.  The vk is returned as its bytes (the key's prefix) on both curves: verify takes bytes.
         form="uncompressed": serialize_uncompressed bytes; the prefix returned is then the 728 / 504-byte uncompressed vk (vk_transcode
-        gives the compressed bytes verify takes)."""
-        pk = api.ProvingKey.load_bytes(self.ctx, self.curve, data, validate, shard_rank, shard_count, layout, form)
+        gives the compressed bytes verify takes).  relations=True (PM_KEY_CHECK_RELATIONS): the key is also checked against its own
+        vk and SAP matrices before its tables are built -- is it what generate_proving_key would have produced for some (x, z)? -- and
+        refused with the name of the first failing relation if not; unsharded keys only."""
+        pk = api.ProvingKey.load_bytes(self.ctx, self.curve, data, validate, shard_rank, shard_count, layout, form, relations)
         pk.omega = self.field.fr_int(pk.omega_limbs)
         return pk, bytes(memoryview(data)[:self.vk_bytes_len(form)])
 

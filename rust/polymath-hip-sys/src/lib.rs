@@ -73,6 +73,9 @@ pub const PM_G1_INF_SIGN: u8 = 6;
 // pm_wire_form: a flag OR-ed into `validate` (pm_g1_decode, pm_pk_load_bytes) and `which` (pm_pk_export_bases_compressed)
 pub const PM_WIRE_COMPRESSED: i32 = 0;
 pub const PM_WIRE_UNCOMPRESSED: i32 = 256;
+// pm_key_check: a flag OR-ed into `validate` of pm_pk_load_bytes -- the key's relations against its own vk and matrices
+pub const PM_KEY_CHECK_NONE: i32 = 0;
+pub const PM_KEY_CHECK_RELATIONS: i32 = 512;
 
 // pm_verify_verdict
 pub const PM_VERIFY_REJECTED: u8 = 0;

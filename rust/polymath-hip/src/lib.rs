@@ -728,6 +728,20 @@ impl GpuKey {
     /// (96 / 64-byte G1 records, vk prefix 728 / 504 bytes).  The curve equation is checked in every mode; `validate` adds the
     /// subgroup check.  Bytes of the other form are refused as a malformed key: the form is never guessed.
     pub fn load_bytes_form<E: Pairing>(ctx: &mut Context, bytes: &[u8], validate: bool, form: WireForm) -> Result<GpuKey, HipError> {
+        Self::load_bytes_flags::<E>(ctx, bytes, validate as i32, form)
+    }
+
+    /// [`GpuKey::load_bytes_form`] with `PM_KEY_CHECK_RELATIONS`: besides validating every point, the loader decides whether the
+    /// bytes are a proving key at all -- what `generate_proving_key` would have produced for some `(x, z)` under the key's own vk and
+    /// SAP matrices -- before it builds the window tables.  A key that is not (vectors of another circuit, an `[x]_2` of another
+    /// ceremony, one record overwritten by another valid point) is refused like a key with a bad point, the error naming the first
+    /// failing relation, e.g. `uj_wj_lcs_by_y_alpha_g1: does not match the SAP matrices`.  Unsharded keys only.
+    pub fn load_bytes_checked<E: Pairing>(ctx: &mut Context, bytes: &[u8], form: WireForm) -> Result<GpuKey, HipError> {
+        Self::load_bytes_flags::<E>(ctx, bytes, 1 | sys::PM_KEY_CHECK_RELATIONS, form)
+    }
+
+    // `validate`: the flag word without the form bit (0, 1, or 1 | PM_KEY_CHECK_RELATIONS)
+    fn load_bytes_flags<E: Pairing>(ctx: &mut Context, bytes: &[u8], validate: i32, form: WireForm) -> Result<GpuKey, HipError> {
         let curve = curve_checked::<E>()?;
         let vk_len = match (curve.id() == sys::PM_BLS12_381, form) {
             (true, WireForm::Compressed) => 392,

@@ -10,7 +10,9 @@ tools/host_deser_time.cpp (the host mirror's deser_g1, one thread) on 10 000 of 
 The decode kernel's own time comes from a separate `rocprofv3 --kernel-trace --stats` run of this script (--profile-only).
 --form uncompressed times the same key as ProvingKey::serialize_uncompressed bytes (pm_pk_load_bytes with PM_WIRE_UNCOMPRESSED:
 96-byte records, no square root); --form both times the two byte strings in one process, form by form within every setting, and
---loads-only leaves out the decoded-array and host baselines."""
+--loads-only leaves out the decoded-array and host baselines.  --relations times validate = 1 against validate = 1 | 512
+(PM_KEY_CHECK_RELATIONS), alternating, three times per form, and nothing else; PM_PROFILE_HOST=1 prints the check's stage split (each
+stage synchronised, so the flagged loads of such a run are not the ones to quote)."""
 import argparse
 import os
 import struct
@@ -29,6 +31,7 @@ ap.add_argument("--chunk-logs", default="", help="comma list of wire_chunk_log v
 ap.add_argument("--profile-only", action="store_true", help="one validated load and nothing else (under rocprofv3)")
 ap.add_argument("--form", choices=("compressed", "uncompressed", "both"), default="compressed")
 ap.add_argument("--loads-only", action="store_true", help="no pm_pk_load-from-arrays and no host baseline")
+ap.add_argument("--relations", action="store_true", help="validate 1 against 1 | 512, alternating, and nothing else")
 args = ap.parse_args()
 
 from polymath_amd import api, circuits as PC            # noqa: E402
@@ -68,9 +71,9 @@ def sync(k):
     k.export_bases(1, 0, 1)          # a stream synchronisation on the loading context
 
 
-def load(validate, form=forms[0]):
+def load(validate, form=forms[0], relations=False):
     t0 = time.perf_counter()
-    k = api.ProvingKey.load_bytes(pm.ctx, curve, blobs[form], validate, form=form)
+    k = api.ProvingKey.load_bytes(pm.ctx, curve, blobs[form], validate, form=form, **({"relations": True} if relations else {}))
     sync(k)
     dt = time.perf_counter() - t0
     k.free()
@@ -85,6 +88,19 @@ if args.profile_only:
 
 for form in forms:
     load(True, form)                  # warm-up
+if args.relations:
+    for form in forms:
+        load(True, form, True)
+        plain, flagged = [], []
+        for _ in range(3):
+            plain.append(load(True, form))
+            flagged.append(load(True, form, True))
+        say("pm_pk_load_bytes %s validate=1:       %s s (best %.3f)" % (form, " ".join("%.3f" % v for v in plain), min(plain)))
+        say("pm_pk_load_bytes %s validate=1|512:   %s s (best %.3f)" % (form, " ".join("%.3f" % v for v in flagged), min(flagged)))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
 for validate in (1, 0):
     for form in forms:
         ts = [load(bool(validate), form) for _ in range(3)]
