@@ -479,6 +479,23 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  *   in any order: a closer examined before its opener (it is an ordinary dividing row then and sticks where the tested value is 0),
  *   K2 = lambda K1 for other lambda, a known rest beside m in the opener, bits spread over two matrices, signed or non-binary digits,
  *   per-assignment patterns, sharded keys.
+ *   Linear blocks (the scheduler only).  k >= 2 rows whose unknowns are the SAME k columns, each named in C_r only (A_r and B_r name
+ *   no unknown; either may be empty, the product is then 0), none of them boolean- or pair-pending, and which no rule above claims,
+ *   are a square linear system in those columns whose matrix is part of the key: the shape of non-native multiplication
+ *   (ark-r1cs-std's mul_without_reduce, circom-bigint's BigMultNoCarry), which pins the 2l - 1 limbs of a product by evaluating
+ *   (sum a_i c^i)(sum b_i c^i) = sum p_j c^j  at 2l - 1 points c.  No row order propagates through such rows; they WAIT, and when the
+ *   k-th row over exactly the same set has been examined, with k <= 64, the k rows are ONE step for all k columns:
+ *   z_S = M^-1 (A z B z - C_known z), M[i][j] = the coefficient of column S_j in row r_i.  The rows determine the values, so there is no
+ *   marker and no hint (the quotient, indicator and square-root markers on such a column are plain unknowns there).  The library
+ *   inverts every distinct M once per plan on the host -- blocks whose k^2 coefficients are equal word for word share one inverse --
+ *   so the step never divides and never leaves an assignment stuck.  A column of the set that another row determines first shrinks
+ *   the set (a row at the point 0,  a_0 b_0 = p_0 , is an ordinary row and the others a system in 2l - 2 columns); further rows over
+ *   the set are check rows.  A singular M is PM_ERR_INVALID_ARG before any assignment is touched: "rows r_1, ..., r_k: the linear
+ *   block over columns ... is singular (no pivot in column S_j)", for the block of smallest first row.  More than 64 unknowns wait to
+ *   the end, and the refusal then ends ", and no linear block: k unknowns exceed 64"; fewer than k such rows is the refusal it always
+ *   was.  Not handled: an unknown in A_r or B_r (the matrix would depend on the assignment), rows over different sets (banded or
+ *   triangular systems), k > 64, boolean- or pair-pending columns in the set, an independent subset of dependent rows, sharded keys,
+ *   per-assignment patterns.
  *   PM_ERR_INVALID_ARG, pm_last_error naming the row or column, nothing computed and no output written: an unsolvable row, a marked
  *   column that no row determines, a marker at column 0, a sharded key, and -- in a batch -- an assignment that does not mark the
  *   columns assignment 0 marks, or marks one with the other marker (any two of the four markers differ; the first differing (assignment, column) is named; a kernel

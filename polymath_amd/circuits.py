@@ -5,7 +5,8 @@ own (RangeCheck, ArxDemo) and two that branch on equality (MatchCount, EqChain: 
 witnesses the device completes from the inputs (PM_ASSIGNMENT_SOLVE), and two that divide integers (DivRem,
 ModChain: Euclidean division rows, whose quotients partial() marks QUOTIENT), and two that read a table at a signal (Decoder,
 TableWalk: circomlib's one-hot decoder, whose outputs partial() marks INDICATOR), and two that take square roots (SquareRoots,
-EdwardsDecompress: point decompression on Jubjub / Baby Jubjub, whose roots partial() marks SQRT); Reordered emits any of them with its rows in another
+EdwardsDecompress: point decompression on Jubjub / Baby Jubjub, whose roots partial() marks SQRT), and three whose rows are square linear systems in their unknowns (LimbProduct, ProductChain: non-native
+multiplication, whose product limbs are pinned at 2l - 1 points; LinearBlocks: random systems), which the solver takes as linear blocks; Reordered emits any of them with its rows in another
 order, which the solver's any-order planner accepts."""
 from .polymath import INDICATOR, QUOTIENT, SQRT, ConstraintSystem, Field, LimbCircuit, R1CS, small_sqrt
 
@@ -659,6 +660,181 @@ def edwards_ys(r, count, seed=SPLITMIX_SEED):
         if den and small_sqrt(r, (1 - y * y) * pow(den, r - 2, r) % r) is not None:
             ys.append(y)
     return ys
+
+
+def limb_product(a, b, r):
+    """the 2l - 1 limbs of the product of two l-limb numbers without carries, mod r: p_j = sum_{i + i' = j} a_i b_i'"""
+    p = [0] * (len(a) + len(b) - 1)
+    for i, a_i in enumerate(a):
+        for k, b_k in enumerate(b):
+            p[i + k] = (p[i + k] + a_i * b_k) % r
+    return p
+
+
+def _product_rows(cs, a, b, p, first):
+    """the rows that pin the limbs p of a product: (sum a_i c^i) (sum b_i c^i) = sum p_j c^j  at c = first .. first + len(p) - 1
+    (ark-r1cs-std's mul_without_reduce, circom-bigint's BigMultNoCarry); a term whose coefficient is zero (c = 0) is not written"""
+    at = lambda limbs, c: [(pow(c, i, cs.r), v) for i, v in enumerate(limbs) if i == 0 or c]
+    for c in range(first, first + len(p)):
+        cs.enforce_constraint(at(a, c), at(b, c), at(p, c))
+
+
+class LimbProduct(_Partial):
+    """Non-native multiplication: per pair (a, b) of l-limb numbers the given witnesses a_0 .. a_{l-1}, b_0 .. b_{l-1}, the witnesses
+    p_0 .. p_{2l-2} of the product's limbs, the 2l - 1 rows of _product_rows at the points first .. first + 2l - 2, and one ordinary row
+    (sum p_j) * 1 = s ; the public input is sum s.  Every product row names all 2l - 1 unknowns, so no row order propagates through
+    them: the solver takes the rows of a product as ONE linear block, all products sharing one Vandermonde matrix.
+    With first = 0 the row at 0 is the ordinary step a_0 b_0 = p_0 and the block has 2l - 2 columns.  The caller chooses the limbs."""
+
+    def __init__(self, products, first=1):
+        assert first in (0, 1) and all(len(a) == len(b) and len(a) >= 2 for a, b in products)
+        self.products, self.first = [(list(a), list(b)) for a, b in products], first
+
+    def generate_constraints(self, cs):
+        self._chosen = []
+        one, r = ConstraintSystem.ONE, cs.r
+        total, total_v = [], 0
+        for a_v, b_v in self.products:
+            a = [self._given(cs, v) for v in a_v]
+            b = [self._given(cs, v) for v in b_v]
+            p_v = limb_product(a_v, b_v, r)
+            p = [cs.new_witness_variable(v) for v in p_v]
+            _product_rows(cs, a, b, p, self.first)
+            s = cs.new_witness_variable(sum(p_v))
+            cs.enforce_constraint([(1, v) for v in p], [(1, one)], [(1, s)])
+            total.append((1, s))
+            total_v += sum(p_v)
+        out = cs.new_input_variable(total_v)
+        cs.enforce_constraint(total, [(1, one)], [(1, out)])
+
+    def native(self, r):
+        """-> (instance, witness) on Python integers, without generating a row: per product the limbs of a, of b, of a b, and their sum"""
+        witness, total = [], 0
+        for a, b in self.products:
+            p = limb_product([v % r for v in a], [v % r for v in b], r)
+            witness += [v % r for v in a] + [v % r for v in b] + p + [sum(p) % r]
+            total += sum(p)
+        return [1, total % r], witness
+
+
+def limb_products(r, count, limbs, seed=SPLITMIX_SEED):
+    """`count` pairs of `limbs`-limb numbers for LimbProduct, every limb a field element drawn from SplitMix64(seed)"""
+    g = SplitMix64(seed)
+    return [([g.fr(r) for _ in range(limbs)], [g.fr(r) for _ in range(limbs)]) for _ in range(count)]
+
+
+class ProductChain(_Partial):
+    """`steps` non-native products in sequence: x_0 = a and b given (l limbs each); product t is p^t = x_t b (2l - 1 limbs, pinned by
+    the rows of _product_rows at the points 1 .. 2l - 1), x_{t+1} = the low l limbs of p^t, and  (sum p^t_j) * 1 = s_t ; the public
+    input is sum s_t.  One linear block per dependency level, each followed by the narrow step s_t beside the next block."""
+
+    def __init__(self, a, b, steps):
+        assert len(a) == len(b) and len(a) >= 2 and steps >= 1
+        self.a, self.b, self.steps = list(a), list(b), steps
+
+    def generate_constraints(self, cs):
+        self._chosen = []
+        one, r = ConstraintSystem.ONE, cs.r
+        x_v, b_v = [v % r for v in self.a], [v % r for v in self.b]
+        x = [self._given(cs, v) for v in x_v]
+        b = [self._given(cs, v) for v in b_v]
+        total, total_v = [], 0
+        for _ in range(self.steps):
+            p_v = limb_product(x_v, b_v, r)
+            p = [cs.new_witness_variable(v) for v in p_v]
+            _product_rows(cs, x, b, p, 1)
+            s = cs.new_witness_variable(sum(p_v))
+            cs.enforce_constraint([(1, v) for v in p], [(1, one)], [(1, s)])
+            total.append((1, s))
+            total_v += sum(p_v)
+            x, x_v = p[:len(x)], p_v[:len(x)]
+        out = cs.new_input_variable(total_v)
+        cs.enforce_constraint(total, [(1, one)], [(1, out)])
+
+    def native(self, r):
+        """-> (instance, witness) on Python integers, without generating a row: a, b, then per product its limbs and their sum"""
+        x, b = [v % r for v in self.a], [v % r for v in self.b]
+        witness, total = x + b, 0
+        for _ in range(self.steps):
+            p = limb_product(x, b, r)
+            witness += p + [sum(p) % r]
+            total += sum(p)
+            x = p[:len(x)]
+        return [1, total % r], witness
+
+
+def _invertible(rows, r):
+    """whether the square matrix `rows` is invertible mod r: elimination on Python integers"""
+    rows = [list(row) for row in rows]
+    for c in range(len(rows)):
+        pivot = next((i for i in range(c, len(rows)) if rows[i][c]), None)
+        if pivot is None:
+            return False
+        rows[c], rows[pivot] = rows[pivot], rows[c]
+        inv = pow(rows[c][c], r - 2, r)
+        for i in range(c + 1, len(rows)):
+            f = rows[i][c] * inv % r
+            if f:
+                rows[i] = [(v - f * w) % r for v, w in zip(rows[i], rows[c])]
+    return True
+
+
+class LinearBlocks(_Partial):
+    """`count` square linear systems, each with a random m x m matrix M mod r of its own (drawn from SplitMix64(seed), redrawn while
+    singular; the assignment's values come from SplitMix64(values), so that one key serves many assignments): per system the given witnesses g_i and h_i, the witnesses u_j and the rows  (g_i + h_i) * 1 = sum_j M_ij u_j , then
+    (sum u_j) * 1 = s ; the public input is sum s.  The u_j and h_i are drawn and g_i = sum_j M_ij u_j - h_i, so the assignment comes
+    from Python integers without an inversion.  One dependency level of `count` linear blocks with `count` distinct matrices."""
+
+    _matrices = {}   # (r, m, count, seed) -> the matrices: part of the key, drawn and tested once
+
+    def __init__(self, m, count, seed=SPLITMIX_SEED, values=None):
+        assert m >= 2 and count >= 1
+        self.m, self.count, self.seed, self.values = m, count, seed, seed + 1 if values is None else values
+
+    def matrices(self, r):
+        key = (r, self.m, self.count, self.seed)
+        if key not in self._matrices:
+            gen, m, mats = SplitMix64(self.seed), self.m, []
+            while len(mats) < self.count:
+                mat = [[gen.fr(r) for _ in range(m)] for _ in range(m)]
+                if _invertible(mat, r):
+                    mats.append(mat)
+            self._matrices[key] = mats
+        return self._matrices[key]
+
+    def _systems(self, r):
+        """-> per system (M, g, h, u) on Python integers; u and h are drawn from SplitMix64(values)"""
+        gen, m, out = SplitMix64(self.values), self.m, []
+        for mat in self.matrices(r):
+            u, h = [gen.fr(r) for _ in range(m)], [gen.fr(r) for _ in range(m)]
+            g = [(sum(c * v for c, v in zip(row, u)) - h_i) % r for row, h_i in zip(mat, h)]
+            out.append((mat, g, h, u))
+        return out
+
+    def generate_constraints(self, cs):
+        self._chosen = []
+        one, r = ConstraintSystem.ONE, cs.r
+        total, total_v = [], 0
+        for mat, g_v, h_v, u_v in self._systems(r):
+            g = [self._given(cs, v) for v in g_v]
+            h = [self._given(cs, v) for v in h_v]
+            u = [cs.new_witness_variable(v) for v in u_v]
+            for i, row in enumerate(mat):
+                cs.enforce_constraint([(1, g[i]), (1, h[i])], [(1, one)], [(c, v) for c, v in zip(row, u) if c])
+            s = cs.new_witness_variable(sum(u_v))
+            cs.enforce_constraint([(1, v) for v in u], [(1, one)], [(1, s)])
+            total.append((1, s))
+            total_v += sum(u_v)
+        out = cs.new_input_variable(total_v)
+        cs.enforce_constraint(total, [(1, one)], [(1, out)])
+
+    def native(self, r):
+        """-> (instance, witness) on Python integers, without generating a row: per system g, h, u and sum u"""
+        witness, total = [], 0
+        for _, g, h, u in self._systems(r):
+            witness += g + h + u + [sum(u) % r]
+            total += sum(u)
+        return [1, total % r], witness
 
 
 def row_order(nr, order, blocks=1):

@@ -185,17 +185,18 @@ struct GlueWs {
 // call with PM_ASSIGNMENT_SOLVE.  xw: the completed x || w rows of a check call (pm_prove_tap(10)); the prover completes its groups in
 // its own workspace (ProveWs::xw) and keeps only tap9.
 struct SolveWs {
-    DevBuf xw, pattern, mismatch, stuck, steps, bit_cols, pairs, divs;
+    DevBuf xw, pattern, mismatch, stuck, steps, bit_cols, pairs, divs, blocks, block_idx, block_inv;
     pmsolve::Plan plan;
     size_t n_pairs = 0;                  // is-zero pairs of the plan: records in `pairs`
     size_t n_divs = 0;                   // division rows of the plan: records in `divs`
+    size_t n_blocks = 0;                 // linear blocks of the plan: records in `blocks`, rows and columns in `block_idx`, inverses in `block_inv`
     uint64_t plan_key = 0;               // pm_pk::serial of the plan's key; 0 = no plan
     std::vector<uint8_t> plan_pattern;   // one byte per column
     std::vector<uint64_t> tap9;          // pm_prove_tap(9): per assignment 4 * (1 + m0) words; empty = no call with the flag yet
     size_t tap10_rows = 0;               // pm_prove_tap(10): rows of xw that hold a check call's completed assignments; 0 = none
     size_t tap10_cols = 0;
     void release() {
-        for (DevBuf *b : {&xw, &pattern, &mismatch, &stuck, &steps, &bit_cols, &pairs, &divs}) b->release();
+        for (DevBuf *b : {&xw, &pattern, &mismatch, &stuck, &steps, &bit_cols, &pairs, &divs, &blocks, &block_idx, &block_inv}) b->release();
     }
 };
 

@@ -2,7 +2,8 @@
 // (include/polymath_hip.h), so that a caller supplies only the values it chooses and the library computes the rest
 // before it checks or proves.  The PLAN -- which row determines which column, in which order -- is host work, done once per (key,
 // pattern) by host/solve_plan.hpp; what ONE step does to ONE assignment (solve_step, solve_bits, solve_iszero, solve_divrem,
-// solve_indicator, solve_sqrt, the dispatch solve_any, the inverses' solve_inverse, and the records a plan becomes: solve_records) is
+// solve_indicator, solve_sqrt, solve_block, the dispatch solve_any, the inverses' solve_inverse and solve_block_invert, and the records
+// a plan becomes: solve_records) is
 // solve_steps.cuh, text that the CPU self-tests run as well; this file is the kernels that call it and the host driver,
 // assignment = grid y (or the lane, in the chain kernel):
 //   k_solve_pattern   one lane per (column, assignment): the unknown pattern of assignment 0 (a byte per column: 1 the unknown
@@ -22,6 +23,10 @@
 //   k_solve_sqrt      the square-root rows of a wide level, one lane per (step, assignment) as well: one dot product over C_r, one
 //                     multiplication by 1 / (ka kb) and one constant-time Tonelli-Shanks (sqrt.cuh: a fixed trip count, so a wave does
 //                     not diverge on the operand); a non-residue is stuck at the row
+//   k_solve_block     the linear blocks of a level, whatever its width: one WAVE per (block, assignment), four to a workgroup.  Lane
+//                     i < k forms the right-hand side of row i into LDS, lane j < k accumulates column j from the LDS values and the
+//                     transposed inverse of the block's matrix, which solve_plan computed on the host once per plan (distinct matrices
+//                     only: solve_steps.cuh, solve_block_invert).  No division, no atomic, never stuck
 //   k_solve_chain     a run of consecutive NARROW levels: one lane per assignment walks the run's steps in plan order.  A lane
 //                     reads back only its own stores: no barriers, no fences.  The MiMC shape (depth 644, width 1) is one such run
 //                     and the batch is its parallel dimension.
@@ -140,6 +145,27 @@ __global__ __launch_bounds__(256) void k_solve_sqrt(Csr Cm, const SolveStepDev<P
     solve_sqrt<P>(Cm, steps[t], xw + b * ncols, StuckWord{stuck + b});
 }
 
+// One WAVE per (block, assignment), four to a workgroup.  Lane i < k forms the right-hand side of the block's row i (two dot products
+// and one sweep of C_r that passes over the markers) and leaves it in LDS, 32 B per lane; after the barrier lane j < k accumulates
+// column j from the k LDS values (the same address in every lane: a broadcast) and row i of the transposed inverse (consecutive
+// elements across the lanes), and does its one store.  Every load of the assignment precedes the barrier and every store follows it,
+// and the four blocks of a workgroup have disjoint columns at one level.  No lane leaves before the barrier; a wave past the range
+// has k = 0.
+template <class P>
+__global__ __launch_bounds__(256) void k_solve_block(Csr A, Csr B, Csr Cm, const SolveStepDev<P> *__restrict__ steps, const SolveBlockDev *__restrict__ blocks,
+                                                     const uint32_t *__restrict__ block_idx, const Fp<P> *__restrict__ block_inv, uint32_t lo, uint32_t hi, Fp<P> *xw,
+                                                     uint64_t ncols) {
+    __shared__ Fp<P> rhs[4][pmsolve::MAX_BLOCK];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * 4 + wave, b = blockIdx.y;
+    Fp<P> *z = xw + b * ncols;
+    SolveBlockDev blk{0, 0, 0, 0, 0};
+    if (t < hi) blk = blocks[steps[t].bits];
+    if (lane < blk.k) rhs[wave][lane] = solve_block_rhs<P>(A, B, Cm, block_idx[blk.rows_off + lane], z);
+    __syncthreads();
+    if (lane < blk.k) z[block_idx[blk.cols_off + lane]] = solve_block_out<P>(block_inv + blk.inv_off, blk.k, lane, rhs[wave]);
+}
+
 // the step index is the same in every lane: the step record, the pair record, the row's CSR metadata and a decomposition's column
 // list are uniform loads (solve_steps.cuh: solve_any, the dispatch by kind).
 template <class P, bool DIV>
@@ -256,9 +282,33 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
                 return PM_ERR_STATE;
             }
     const size_t n_steps = sv.plan.steps.size();
-    sv.n_pairs = sv.n_divs = 0;
+    sv.n_pairs = sv.n_divs = sv.n_blocks = 0;
     if (n_steps) {
-        const SolveRecords<P> rec = solve_records<P>(sv.plan);
+        SolveRecords<P> rec = solve_records<P>(sv.plan);
+        // the linear blocks' matrices are constants of the key: each distinct one is inverted here, once per plan, from the words the
+        // planner copied out of C; a singular one refuses the call before any assignment is touched
+        sv.n_blocks = rec.blocks.size();
+        if (sv.n_blocks) {
+            uint32_t column = 0;
+            const size_t bad = solve_block_inverses<P>(sv.plan, rec, &column);
+            if (bad != sv.plan.blocks.size()) {
+                const pmsolve::BlockRows &blk = sv.plan.blocks[bad];
+                const auto list = [](const std::vector<uint32_t> &v) {
+                    std::string out;
+                    for (size_t i = 0; i < v.size(); ++i) out += (i ? ", " : "") + std::to_string(v[i]);
+                    return out;
+                };
+                ctx->err = "pm solve: rows " + list(blk.rows) + ": the linear block over columns " + list(blk.cols) + " is singular (no pivot in column " +
+                           std::to_string(blk.cols[column]) + ")";
+                return PM_ERR_INVALID_ARG;
+            }
+            PM_HIP(ctx, sv.blocks.reserve(sv.n_blocks * sizeof(SolveBlockDev)));
+            PM_HIP(ctx, hipMemcpyAsync(sv.blocks.p, rec.blocks.data(), sv.n_blocks * sizeof(SolveBlockDev), hipMemcpyHostToDevice, st));
+            PM_HIP(ctx, sv.block_idx.reserve(rec.block_idx.size() * sizeof(uint32_t)));
+            PM_HIP(ctx, hipMemcpyAsync(sv.block_idx.p, rec.block_idx.data(), rec.block_idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            PM_HIP(ctx, sv.block_inv.reserve(rec.block_inv.size() * sizeof(Fp<P>)));
+            PM_HIP(ctx, hipMemcpyAsync(sv.block_inv.p, rec.block_inv.data(), rec.block_inv.size() * sizeof(Fp<P>), hipMemcpyHostToDevice, st));
+        }
         sv.n_pairs = rec.pairs.size();
         if (sv.n_pairs) {
             PM_HIP(ctx, sv.pairs.reserve(sv.n_pairs * sizeof(SolvePairDev<P>)));
@@ -306,7 +356,11 @@ int solve_group(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t 
     {
         StageTimer t(ctx, timing_slot);
         for (const pmsolve::Launch &l : sv.plan.launches) {
-            if (l.chain) {
+            if (l.block) {
+                if (!sv.n_blocks) return PM_ERR_STATE;
+                hipLaunchKernelGGL((k_solve_block<P>), dim3(nblk(l.hi - l.lo, 4), (unsigned)g), dim3(256), 0, st, A, B, Cm, steps, sv.blocks.as<SolveBlockDev>(),
+                                   sv.block_idx.as<uint32_t>(), sv.block_inv.as<Fp<P>>(), l.lo, l.hi, d_xw, ncols);
+            } else if (l.chain) {
                 const dim3 grid(nblk(g, 64)), block(64);
                 if (l.divides) hipLaunchKernelGGL((k_solve_chain<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, pairs, divs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
                 else hipLaunchKernelGGL((k_solve_chain<P, false>), grid, block, 0, st, A, B, Cm, steps, bit_cols, pairs, divs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);

@@ -49,17 +49,32 @@ struct SolveDivDev {
     uint32_t col_r, q_in_b;          // the remainder's column; K = A_r (the quotient lies in B_r), 0: K = B_r
 };
 
-// The three record arrays of a plan, as the kernels read them; the inverses are left zero (solve_inverse fills them).
+// what a block step needs beside its SolveStepDev (whose bits = its SolveBlockDev): k rows and k columns, both ascending, in the index
+// pool, and the inverse of its matrix in the inverse pool, k x k elements stored TRANSPOSED (InvT[i][j] = Inv[j][i]: the lanes j of a
+// wave read consecutive elements).  Blocks with the same matrix share an inverse.
+struct SolveBlockDev {
+    uint32_t k, rows_off, cols_off, pad;
+    uint64_t inv_off;                // in elements
+};
+
+// The record arrays of a plan, as the kernels read them; the inverses are left zero (solve_inverse fills them), the pool of block
+// inverses empty (solve_block_inverses fills it).
 template <class P>
 struct SolveRecords {
     std::vector<SolveStepDev<P>> steps;
     std::vector<SolvePairDev<P>> pairs;
     std::vector<SolveDivDev> divs;
+    std::vector<SolveBlockDev> blocks;
+    std::vector<uint32_t> block_idx;      // the blocks' rows and columns
+    std::vector<uint64_t> mat_off;        // per distinct matrix: where its inverse begins in block_inv; one more entry: the pool's size
+    std::vector<Fp<P>> block_inv;         // the inverse pool
 };
 
 template <class P>
 inline SolveRecords<P> solve_records(const pmsolve::Plan &plan) {
     SolveRecords<P> rec;
+    rec.mat_off.assign(1, 0);
+    for (const pmsolve::BlockMat &mat : plan.block_mats) rec.mat_off.push_back(rec.mat_off.back() + (uint64_t)mat.k * mat.k);
     const size_t n_steps = plan.steps.size();
     rec.steps.resize(n_steps);
     if (n_steps) memset((void *)rec.steps.data(), 0, n_steps * sizeof(SolveStepDev<P>));
@@ -73,6 +88,14 @@ inline SolveRecords<P> solve_records(const pmsolve::Plan &plan) {
             const pmsolve::DivRow &row = plan.divs[s.cols_off];
             d.bits = (uint32_t)rec.divs.size();
             rec.divs.push_back(SolveDivDev{row.pos_r, row.col_r, row.q_in_b});
+        }
+        if (s.kind == pmsolve::KIND_BLOCK) {
+            const pmsolve::BlockRows &blk = plan.blocks[s.cols_off];
+            const uint32_t k = (uint32_t)blk.cols.size(), rows_off = (uint32_t)rec.block_idx.size();
+            d.bits = (uint32_t)rec.blocks.size();
+            rec.block_idx.insert(rec.block_idx.end(), blk.rows.begin(), blk.rows.end());
+            rec.block_idx.insert(rec.block_idx.end(), blk.cols.begin(), blk.cols.end());
+            rec.blocks.push_back(SolveBlockDev{k, rows_off, rows_off + k, 0, rec.mat_off[blk.mat]});
         }
         if (s.kind != pmsolve::KIND_ISZERO) continue;
         d.bits = (uint32_t)rec.pairs.size();
@@ -105,7 +128,7 @@ PM_HD uint32_t matrix_kind(uint32_t kind) { return kind >= pmsolve::KIND_BITS_C 
 template <class P>
 PM_HD void solve_inverse(const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsolve::Csr &Cm, SolveStepDev<P> *steps, uint64_t count, SolvePairDev<P> *pairs,
                          const SolveDivDev *divs, uint64_t t) {
-    if (t < count && steps[t].kind == pmsolve::KIND_INDICATOR) return;      // no inverse: the record stays as the host wrote it
+    if (t < count && (steps[t].kind == pmsolve::KIND_INDICATOR || steps[t].kind == pmsolve::KIND_BLOCK)) return;   // no inverse of a coefficient: the record stays as the host wrote it
     if (t < count && steps[t].kind == pmsolve::KIND_SQRT) {
         const Fp<P> ka = *(const Fp<P> *)(A.val + 4 * steps[t].pos), kb = *(const Fp<P> *)(B.val + 4 * (B.rowptr[steps[t].row] + steps[t].bits));
         const Fp<P> coef = mul<P>(ka, kb);
@@ -283,6 +306,98 @@ PM_HD void solve_sqrt(const pmsolve::Csr &Cm, const SolveStepDev<P> &s, Fp<P> *z
     Fp<P> root = Fp<P>::zero();
     if (!fr_sqrt<P>(c, &root)) stuck(s);
     z[s.col] = root;
+}
+
+constexpr uint32_t SOLVE_NO_COLUMN = ~(uint32_t)0;   // solve_block_invert: every column has a pivot
+
+// out = M^-1 for the k x k matrix M (row-major; M is destroyed): Gauss-Jordan with a row-pivot search (the first row at or below the
+// diagonal with a non-zero entry), one inverse<P> per pivot.  The trip counts depend on k only: the search looks at every row, the
+// swap is always made (with itself where the diagonal entry serves) and every row is eliminated over its full width.
+// -> the first column without a pivot (M is singular; out is not the inverse then), or SOLVE_NO_COLUMN.
+template <class P>
+PM_HD uint32_t solve_block_invert(Fp<P> *M, uint32_t k, Fp<P> *out) {
+    for (uint32_t i = 0; i < k; ++i)
+        for (uint32_t j = 0; j < k; ++j) out[(size_t)i * k + j] = i == j ? Fp<P>::one() : Fp<P>::zero();
+    uint32_t missing = SOLVE_NO_COLUMN;
+    for (uint32_t c = 0; c < k; ++c) {
+        uint32_t p = k;
+        for (uint32_t i = c; i < k; ++i) p = (p == k && !M[(size_t)i * k + c].is_zero()) ? i : p;
+        if (p == k) {
+            missing = missing == SOLVE_NO_COLUMN ? c : missing;
+            p = c;
+        }
+        for (uint32_t j = 0; j < k; ++j) {
+            const Fp<P> m = M[(size_t)p * k + j], o = out[(size_t)p * k + j];
+            M[(size_t)p * k + j] = M[(size_t)c * k + j];
+            out[(size_t)p * k + j] = out[(size_t)c * k + j];
+            M[(size_t)c * k + j] = m;
+            out[(size_t)c * k + j] = o;
+        }
+        const Fp<P> scale = inverse<P>(M[(size_t)c * k + c]);      // inverse(0) = 0: a column without a pivot zeroes its row
+        for (uint32_t j = 0; j < k; ++j) {
+            M[(size_t)c * k + j] = mul<P>(M[(size_t)c * k + j], scale);
+            out[(size_t)c * k + j] = mul<P>(out[(size_t)c * k + j], scale);
+        }
+        for (uint32_t i = 0; i < k; ++i) {
+            const Fp<P> f = i == c ? Fp<P>::zero() : M[(size_t)i * k + c];
+            for (uint32_t j = 0; j < k; ++j) {
+                M[(size_t)i * k + j] = sub<P>(M[(size_t)i * k + j], mul<P>(f, M[(size_t)c * k + j]));
+                out[(size_t)i * k + j] = sub<P>(out[(size_t)i * k + j], mul<P>(f, out[(size_t)c * k + j]));
+            }
+        }
+    }
+    return missing;
+}
+
+// The inverse pool of a plan's records: every distinct block matrix inverted once and stored transposed at rec.mat_off[mat].
+// -> the block of smallest first row whose matrix is singular, with `column` = the index (in the block's columns) of the first column
+// without a pivot; or plan.blocks.size().
+template <class P>
+inline size_t solve_block_inverses(const pmsolve::Plan &plan, SolveRecords<P> &rec, uint32_t *column) {
+    const size_t n_mats = plan.block_mats.size();
+    std::vector<uint32_t> missing(n_mats, SOLVE_NO_COLUMN);
+    rec.block_inv.assign(rec.mat_off.back(), Fp<P>::zero());
+    std::vector<Fp<P>> M, inv;
+    for (size_t t = 0; t < n_mats; ++t) {
+        const uint32_t k = plan.block_mats[t].k;
+        M.resize((size_t)k * k);
+        inv.resize((size_t)k * k);
+        memcpy((void *)M.data(), plan.block_mats[t].words.data(), (size_t)k * k * sizeof(Fp<P>));
+        missing[t] = solve_block_invert<P>(M.data(), k, inv.data());
+        for (uint32_t i = 0; i < k; ++i)
+            for (uint32_t j = 0; j < k; ++j) rec.block_inv[rec.mat_off[t] + (size_t)i * k + j] = inv[(size_t)j * k + i];
+    }
+    size_t bad = plan.blocks.size();
+    for (size_t b = 0; b < plan.blocks.size(); ++b)
+        if (missing[plan.blocks[b].mat] != SOLVE_NO_COLUMN && (bad == plan.blocks.size() || plan.blocks[b].rows[0] < plan.blocks[bad].rows[0])) bad = b;
+    if (bad != plan.blocks.size()) *column = missing[plan.blocks[bad].mat];
+    return bad;
+}
+
+// One row of a linear block on one assignment: rhs = (A z)_r (B z)_r - the known entries of (C z)_r.  The block's columns still
+// hold their markers (they are unknown until the block's stores, which come after every rhs), and no other column a row names does.
+template <class P>
+PM_HD Fp<P> solve_block_rhs(const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsolve::Csr &Cm, uint64_t r, const Fp<P> *z) {
+    const Fp<P> az = row_dot_skip<P>(A, z, r, SOLVE_NONE), bz = row_dot_skip<P>(B, z, r, SOLVE_NONE);
+    return sub<P>(mul<P>(az, bz), row_dot_unmarked<P>(Cm, z, r));
+}
+
+// Column j of a linear block from the k right-hand sides: sum_i Inv[j][i] rhs_i, the inverse read transposed
+template <class P>
+PM_HD Fp<P> solve_block_out(const Fp<P> *__restrict__ inv_t, uint32_t k, uint32_t j, const Fp<P> *rhs) {
+    Fp<P> acc = Fp<P>::zero();
+    for (uint32_t i = 0; i < k; ++i) acc = add<P>(acc, mul<P>(inv_t[(size_t)i * k + j], rhs[i]));
+    return acc;
+}
+
+// one linear block on one assignment, serially (the kernel gives a lane to each row, then to each column): every right-hand side
+// before any store.  No division, never stuck.
+template <class P>
+PM_HD void solve_block(const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsolve::Csr &Cm, const SolveBlockDev &blk, const uint32_t *__restrict__ block_idx,
+                       const Fp<P> *__restrict__ block_inv, Fp<P> *z) {
+    Fp<P> rhs[pmsolve::MAX_BLOCK];
+    for (uint32_t i = 0; i < blk.k; ++i) rhs[i] = solve_block_rhs<P>(A, B, Cm, block_idx[blk.rows_off + i], z);
+    for (uint32_t j = 0; j < blk.k; ++j) z[block_idx[blk.cols_off + j]] = solve_block_out<P>(block_inv + blk.inv_off, blk.k, j, rhs);
 }
 
 // One step of a chain, whatever its kind.  A range with an is-zero pair or a division row is a dividing one (the plan says so): the

@@ -2,7 +2,8 @@
 // (DESIGN.md §4.10).  Header-only, no HIP: the library's driver (csrc/solve.hip, through csrc/solve_steps.cuh) and six CPU programs
 // (tests/native/solve_plan_selftest.cpp, solve_bits_selftest.cpp, solve_iszero_selftest.cpp, solve_order_selftest.cpp,
 // solve_divrem_selftest.cpp, solve_indicator_selftest.cpp, through their rig tests/native/solve_selftest.hpp) include the same file.
-// (A seventh program on the same rig, solve_sqrt_selftest.cpp, pins the square-root row below.)
+// (A seventh program on the same rig, solve_sqrt_selftest.cpp, pins the square-root row below, an eighth, solve_block_selftest.cpp,
+// the scheduler's linear blocks.)
 //
 // Input: the three matrices in CSR form with the first-entry rule already applied (a column occurs at most once per row and
 // matrix: the key's resident matrices are like that), m0 + mw columns and one byte per column, non-zero = unknown (1: unknown;
@@ -100,7 +101,7 @@
 //                 Not handled: a known rest beside u on either side ((u + k)(u + k) = c), u in C_r (a general quadratic),
 //                 the larger root or arkworks' unspecified choice of root (a caller who wants either supplies u itself),
 //                 inferring a square root without the marker, sharded keys, per-assignment patterns.
-// Without the modulus (nullptr) all five additions are off.  (So is the sixth, the square-root row.)
+// Without the modulus (nullptr) all five additions are off.  (So is the sixth, the square-root row.)  (And the linear blocks: they are the scheduler's, which runs with the modulus only.)
 //
 // build_plan_any_order drops the matrix order: it runs build_plan, and where that refuses, a WAITING-ROW SCHEDULER examines the rows
 // from a min-heap (at first all of them) against the same column state with the same rules, except that these refusals become waiting:
@@ -119,7 +120,31 @@
 //                                           and this one is a check row then)
 //   two or more unknowns                    a decomposition: the bits step; a division row: its step; the opener shape without the
 //                                           quotient's marker on the lone entry: registered; anything else WAITS
+//   two or more unknowns, all in C_r only,  a LINEAR ROW over the set S of its unknown columns: parked like any waiting row, and
+//   none boolean- or pair-pending           registered under the sorted S (below)
 // A waiting row is parked on its unknown columns and returns to the heap when one of them becomes known, boolean-pending or released.
+//   linear block  k = |S| >= 2 rows whose unknowns are the SAME k columns, each named in C_r only (A_r and B_r name no unknown; either
+//                 may be empty, the product is then 0), none of them boolean- or pair-pending, and which no rule above claims: the
+//                 shape of non-native multiplication (ark-r1cs-std's mul_without_reduce, circom-bigint's BigMultNoCarry), which pins
+//                 the 2l - 1 limbs p_j of a product by  (sum a_i c^i) (sum b_i c^i) = sum p_j c^j  at 2l - 1 points c.  No row order
+//                 propagates through such rows, but together they are a square linear system whose matrix is part of the key.  When
+//                 the k-th linear row with exactly the set S is registered and k <= 64, those k rows and k columns become ONE step of
+//                 kind KIND_BLOCK at 1 + max level of every column the k rows read; all k columns get that level, and later rows over
+//                 S are check rows.  A column of S that becomes known by another route wakes the row, which is examined again with
+//                 its smaller set (a c = 0 row a_0 b_0 = p_0 is an ordinary step, and the others a block over 2l - 2 columns).
+//                 Plan::blocks[cols_off] carries the rows and columns, both ascending, and an index into Plan::block_mats, the
+//                 DISTINCT matrices M[i][j] = the coefficient of S_j in C_{r_i} (zero where absent), compared word for word: the
+//                 planner multiplies nothing, and 10 000 products at the same points share one Vandermonde matrix.  The driver
+//                 inverts each distinct matrix once per plan (solve_steps.cuh: solve_block_invert) and refuses a singular one; the
+//                 step is then  z_S = M^-1 (A z B z - C_known z)  over the k rows: no division, never stuck.  Step::row / col name
+//                 the smallest row and column, Step::pos is not used.  A block step is a launch of its own (Launch::block), whatever
+//                 the level's width.  Pattern bytes 2, 3 and 4 on a column of S have no meaning there.  The rule is the scheduler's:
+//                 build_plan refuses the first such row as it always did.  A set of more than 64 columns keeps waiting, and the
+//                 refusal then ends ", and no linear block: k unknowns exceed 64"; fewer than k linear rows for a set is the refusal
+//                 it always was.
+//                 Not handled: an unknown in A_r or B_r (the matrix would depend on the assignment), rows over different sets
+//                 (banded or triangular systems), k > 64, boolean- or pair-pending columns in S, choosing an independent subset when
+//                 the first k rows are dependent, sharded keys, per-assignment patterns.
 // With the heap empty the scheduler has failed if an opener is unclosed, a boolean-pending column unsolved or a marked column
 // undetermined; the result is then build_plan's error (code, row, column, message) with "; in any row order: ..." appended.  A plan
 // it finds has Plan::reordered = true, level(step) as below, the steps sorted by (level, kind, row) and the level_ptr and launches of
@@ -133,12 +158,13 @@
 //
 // level(step) = 1 + max level of the columns the row reads (given columns: level 0); a decomposition gives all its columns that
 // level.  The steps come out sorted by level, inside a level by kind (C first: the kinds that divide share a launch; then the
-// decompositions in the same order, then the is-zero pairs, then the division rows, then the indicator rows, then the square-root rows), stable by row -- one counting sort.  O(nnz + columns), plus k log k per decomposition.
+// decompositions in the same order, then the is-zero pairs, then the division rows, then the indicator rows, then the square-root rows, then the linear blocks), stable by row -- one counting sort.  O(nnz + columns), plus k log k per decomposition.
 #pragma once
 #include <stdint.h>
 
 #include <algorithm>
 #include <functional>
+#include <map>
 #include <queue>
 #include <string>
 #include <utility>
@@ -150,10 +176,12 @@ namespace pmsolve {
 // KIND_ISZERO: an is-zero pair, both columns in one step;  KIND_DIVREM: a division row, quotient and remainder in one step
 // KIND_INDICATOR: an indicator row, z_u = [K z == 0]: no division and no inverse
 // KIND_SQRT: a square-root row, z_u = the smaller root of (C z)_r / (ka kb); its inverse is 1 / (ka kb), so it counts as dividing
-enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6, KIND_DIVREM = 7, KIND_INDICATOR = 8, KIND_SQRT = 9 };
+// KIND_BLOCK: a linear block, z_S = M^-1 rhs over k rows and k columns; the inverse is plan data, so it does not count as dividing
+enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6, KIND_DIVREM = 7, KIND_INDICATOR = 8, KIND_SQRT = 9, KIND_BLOCK = 10 };
 constexpr uint32_t NUM_KINDS = 7;        // the kinds that need no second marker: what it always counted
 constexpr uint32_t NUM_STEP_KINDS = 8;   // KIND_C .. KIND_DIVREM, the kinds whose value comes from field or integer arithmetic on the row: what it counted when kind 7 came
-constexpr uint32_t NUM_SORT_KINDS = 10;  // all of them, KIND_INDICATOR and KIND_SQRT included: the key width of finish_plan's counting sort
+constexpr uint32_t NUM_SORT_KINDS = 10 + 1;  // all 11 of them: the ten kinds that one lane executes, KIND_INDICATOR and KIND_SQRT included, and KIND_BLOCK; the key width of finish_plan's counting sort
+constexpr uint32_t MAX_BLOCK = 64;       // the largest linear block: one wave, a lane per row and per column
 
 constexpr uint8_t PATTERN_UNKNOWN = 1, PATTERN_QUOTIENT = 2, PATTERN_INDICATOR = 3, PATTERN_SQRT = 4;   // the pattern bytes (0: given)
 
@@ -173,6 +201,7 @@ struct Step {
                                        // a division row: pos / col = the quotient's entry in A_r or B_r, Plan::divs[cols_off]
                                        // an indicator row: pos / col = the indicator's entry, cols_off = 1: it lies in B_r and K = A_r; 0: the other way round
                                        // a square-root row: pos / col = the root's entry in A_r, cols_off = the offset of its entry in B_r from that row's start
+                                       // a linear block: row / col = its smallest row and column, pos = 0, Plan::blocks[cols_off]
 };
 
 struct PairRows {     // what an is-zero step needs beside its Step
@@ -189,6 +218,16 @@ struct DivRow {       // what a division step needs beside its Step
     uint8_t q_in_b;          // 1: the quotient lies in B_r and K = A_r; 0: the other way round
 };
 
+struct BlockRows {    // what a block step needs beside its Step
+    std::vector<uint32_t> rows, cols;   // k rows and k columns, both ascending
+    uint32_t mat;                       // Plan::block_mats[mat]
+};
+
+struct BlockMat {     // a distinct block matrix
+    uint32_t k;
+    std::vector<uint64_t> words;        // k x k coefficients of 4 words, row-major: M[i][j] = the coefficient of cols[j] in C_{rows[i]}
+};
+
 struct Launch {
     uint32_t lo, hi;  // steps [lo, hi) of the sorted list
     uint8_t chain;    // 1: one lane per assignment walks the steps in order; 0: one lane per (step, assignment), all of one level
@@ -198,6 +237,7 @@ struct Launch {
     uint8_t divrem = 0;  // chain == 0 only.  1: every step of the range is a division row; 0: none is
     uint8_t indicator = 0;  // chain == 0 only.  1: every step of the range is an indicator row; 0: none is
     uint8_t sqrt = 0;       // chain == 0 only.  1: every step of the range is a square-root row; 0: none is
+    uint8_t block = 0;      // chain == 0 only.  1: every step of the range is a linear block (one wave each); 0: none is.  Never divides
 };
 
 enum Error : int { OK = 0, ERR_MANY_UNKNOWNS = 1, ERR_TWO_MATRICES = 2, ERR_UNDETERMINED = 3, ERR_COLUMN_ZERO = 4 };
@@ -209,6 +249,8 @@ struct Plan {
     std::vector<uint32_t> bit_cols;   // the decompositions' columns
     std::vector<PairRows> pairs;      // the is-zero pairs' openers, in order of discovery
     std::vector<DivRow> divs;         // the division rows' remainders, in order of discovery
+    std::vector<BlockRows> blocks;    // the linear blocks, in order of discovery
+    std::vector<BlockMat> block_mats; // their distinct matrices, in order of discovery
     int error = OK;
     uint64_t error_row = 0, error_col = 0;
     std::string message;              // empty when error == OK
@@ -409,13 +451,16 @@ inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
     // launch schedule: a wide level is its own launch, split where the dividing kinds begin, again where the decompositions and
     // their dividing kinds begin, where the is-zero pairs begin, where the division rows begin and where the indicator rows begin (which
     // do not divide: a chain of C-steps and indicators is a non-dividing one), and where the square-root rows begin (which count as
-    // dividing); consecutive narrow levels are one chain
+    // dividing); consecutive narrow levels are one chain.  The linear blocks of a level come last and are a launch of their own
+    // whatever the level's width (a wave per block, not a lane): a chain run ends before them and a new one begins after them
     for (uint32_t l = 0; l < max_level; ++l) {
         const uint32_t *at = start.data() + (size_t)l * K;
         const uint32_t lo = at[KIND_C], ab = at[KIND_A], bits = at[KIND_BITS_C], bits_ab = at[KIND_BITS_A], pairs = at[KIND_ISZERO], divs = at[KIND_DIVREM],
-                       inds = at[KIND_INDICATOR], roots = at[KIND_SQRT], hi = at[K];
+                       inds = at[KIND_INDICATOR], roots = at[KIND_SQRT], hi = at[KIND_BLOCK], end = at[K];
         const uint8_t divides = (uint8_t)(bits > ab || inds > bits_ab || hi > roots);
-        if (hi - lo >= wide_steps) {
+        if (hi == lo) {
+            // a level of blocks only
+        } else if (hi - lo >= wide_steps) {
             if (ab > lo) p.launches.push_back(Launch{lo, ab, 0, 0});
             if (bits > ab) p.launches.push_back(Launch{ab, bits, 0, 1});
             if (bits_ab > bits) p.launches.push_back(Launch{bits, bits_ab, 0, 0, 1});
@@ -429,6 +474,11 @@ inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
             p.launches.back().divides |= divides;
         } else {
             p.launches.push_back(Launch{lo, hi, 1, divides});
+        }
+        if (end > hi) {
+            Launch blocks{hi, end, 0, 0};
+            blocks.block = 1;
+            p.launches.push_back(blocks);
         }
     }
 }
@@ -565,6 +615,42 @@ struct Planner {
         known(col_m);
         known(col_b);
     }
+    // a linear row (the scheduler only): two or more unknown entries, every one in C_r, no column boolean-pending (pair-pending
+    // columns have made the row wait before it comes here; the first-entry rule gives one entry per column)
+    bool linear_row() const {
+        if (occ.size() < 2) return false;
+        for (const Unknown &e : occ)
+            if (e.matrix != 2 || bool_row[e.col] != NONE) return false;
+        return true;
+    }
+    // a linear block: `rows` (ascending) over the columns `cols` (ascending, all still unknown), `reads` the largest level the rows read
+    template <class Known>
+    void block_step(const std::vector<uint32_t> &rows, const std::vector<uint32_t> &cols, uint32_t reads_all, const Known &known) {
+        const uint32_t lv = reads_all + 1, k = (uint32_t)cols.size();
+        std::vector<uint64_t> words((size_t)k * k * 4, 0);
+        for (uint32_t i = 0; i < k; ++i)
+            for (uint64_t e = m[2].rowptr[rows[i]]; e < m[2].rowptr[rows[i] + 1]; ++e) {
+                if (coef_is_zero(m[2].val + 4 * e) || level[m[2].col[e]] != UNSOLVED) continue;
+                const size_t j = (size_t)(std::lower_bound(cols.begin(), cols.end(), m[2].col[e]) - cols.begin());
+                std::copy(m[2].val + 4 * e, m[2].val + 4 * e + 4, words.begin() + ((size_t)i * k + j) * 4);
+            }
+        const auto found = mat_of.find(words);
+        uint32_t mat;
+        if (found != mat_of.end()) {
+            mat = found->second;
+        } else {
+            mat = (uint32_t)p.block_mats.size();
+            mat_of.emplace(words, mat);
+            p.block_mats.push_back(BlockMat{k, std::move(words)});
+        }
+        Step s{0, rows[0], cols[0], KIND_BLOCK, lv};
+        s.cols_off = (uint32_t)p.blocks.size();
+        p.blocks.push_back(BlockRows{rows, cols, mat});
+        p.steps.push_back(s);
+        for (uint32_t col : cols) solved(col, lv);
+        for (uint32_t col : cols) known(col);
+    }
+    std::map<std::vector<uint64_t>, uint32_t> mat_of;   // a block matrix' words (k follows from their number) -> its index in Plan::block_mats
     // a row is refused where it stands: the steps of the rows before it stay in the plan, as they always did
     void refuse_row(int code, uint64_t row, uint64_t col, const std::string &message) {
         p.error = code;
@@ -579,6 +665,8 @@ struct Planner {
         p.bit_cols.clear();
         p.pairs.clear();
         p.divs.clear();
+        p.blocks.clear();
+        p.block_mats.clear();
     }
 };
 
@@ -732,6 +820,11 @@ inline bool schedule_any_order(Planner &st, uint64_t nr, uint64_t ncols, std::st
     std::vector<uint32_t> park_head(ncols, NONE);
     std::vector<std::pair<uint32_t, uint32_t>> parked;   // (row, next node of the same column)
     std::vector<uint8_t> state(nr, QUEUED);
+    // the linear rows: a sorted set S of unknown columns -> its entry of set_rows, the (row, largest level it reads) registered under
+    // exactly S; registered[r] = the set row r is registered under now (a row examined again with the same set is not counted twice)
+    std::map<std::vector<uint32_t>, uint32_t> set_of;
+    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> set_rows;
+    std::vector<uint32_t> registered, set;
     std::vector<uint32_t> rows(nr);
     for (uint64_t r = 0; r < nr; ++r) rows[r] = (uint32_t)r;   // ascending: a min-heap as it stands
     std::priority_queue<uint32_t, std::vector<uint32_t>, std::greater<uint32_t>> heap(std::greater<uint32_t>(), std::move(rows));
@@ -831,6 +924,33 @@ inline bool schedule_any_order(Planner &st, uint64_t nr, uint64_t ncols, std::st
             st.register_opener(r);
             continue;
         }
+        if (st.linear_row()) {
+            // a linear row over S: registered under the sorted S, once.  The |S|-th such row makes the block; a wider set only waits
+            set.clear();
+            for (const Unknown &e : occ) set.push_back(e.col);
+            std::sort(set.begin(), set.end());
+            if (std::adjacent_find(set.begin(), set.end()) == set.end()) {
+                const auto at = set_of.emplace(set, (uint32_t)set_rows.size());
+                if (at.second) set_rows.emplace_back();
+                const uint32_t id = at.first->second;
+                if (registered.empty()) registered.assign(nr, NONE);
+                if (registered[r] != id) {
+                    registered[r] = id;
+                    set_rows[id].push_back({r, st.reads});
+                }
+                if (set.size() <= MAX_BLOCK && set_rows[id].size() == set.size()) {
+                    std::vector<uint32_t> block_rows;
+                    uint32_t reads = 0;
+                    for (const auto &row : set_rows[id]) {
+                        block_rows.push_back(row.first);
+                        if (row.second > reads) reads = row.second;
+                    }
+                    std::sort(block_rows.begin(), block_rows.end());
+                    st.block_step(block_rows, set, reads, wake);   // the other k - 1 rows wake and are check rows
+                    continue;
+                }
+            }
+        }
         park(r);
     }
     for (uint64_t j = 0; j < ncols; ++j)
@@ -838,6 +958,16 @@ inline bool schedule_any_order(Planner &st, uint64_t nr, uint64_t ncols, std::st
             why = "column " + std::to_string(j) + " stays unknown";
             if (st.pair_of[j] != NONE) why += " (the pair that row " + std::to_string(st.openers[st.pair_of[j]].row) + " opens is never closed)";
             else if (st.bool_row[j] != NONE) why += " (boolean by row " + std::to_string(st.bool_row[j]) + ", and nothing determines it)";
+            for (const auto &wide : set_of) {   // a set of linear rows too wide for a block, whose rows are linear rows over it to the end
+                bool waits = wide.first.size() > MAX_BLOCK && std::binary_search(wide.first.begin(), wide.first.end(), (uint32_t)j);
+                for (size_t i = 0; waits && i < wide.first.size(); ++i) {
+                    const uint32_t col = wide.first[i];
+                    waits = st.level[col] == UNSOLVED && st.bool_row[col] == NONE && st.pair_of[col] == NONE;
+                }
+                if (!waits) continue;
+                why += ", and no linear block: " + std::to_string(wide.first.size()) + " unknowns exceed " + std::to_string(MAX_BLOCK);
+                break;
+            }
             return false;
         }
     return st.open == 0;

@@ -26,7 +26,11 @@ index; route (b) marks the decoders' outputs with the indicator marker), and
   python tools/prove_bench.py --circuit decompress --batch 256 --reps 5 --solve  EdwardsDecompress, 32 points of Jubjub / Baby Jubjub;
                                                                                  decompress:POINTS for others
 on one that decompresses curve points (per point a division, one square-root row, a product and a decomposition of the root into
-bitlength(r) - 1 bits; route (b) marks the roots with the square-root marker).
+bitlength(r) - 1 bits; route (b) marks the roots with the square-root marker), and
+  python tools/prove_bench.py --circuit limbproduct --batch 256 --reps 5 --solve LimbProduct, 64 products of 8-limb numbers;
+                                                                                 limbproduct:COUNT:LIMBS for others
+on one that multiplies non-native numbers (one dependency level of COUNT linear blocks of 2 LIMBS - 1 unknowns through one shared
+inverse, then the sums; no marker: the rows determine the product's limbs).
   python tools/prove_bench.py --circuit mimc322 --batch 256 --reps 5 --solve --reorder reverse     or --reorder SEED
 runs either --solve comparison on the same circuit with its constraint rows stored in another order (circuits.Reordered: reversed, or
 shuffled by SEED; a matchcount gadget moves as a block so that every opener stays before its closer).  Route (b) then goes through the
@@ -44,7 +48,7 @@ from polymath_amd import circuits as PC
 from polymath_amd.polymath import Polymath
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants), bench:NC (BenchCircuit, NC constraints), arx[:WIDTH:ROUNDS] (ArxDemo), matchcount[:N:FORM] (MatchCount), divrem[:N:BITS] (DivRem), tablewalk[:WIDTH:STEPS] (TableWalk) or decompress[:POINTS] (EdwardsDecompress)")
+ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants), bench:NC (BenchCircuit, NC constraints), arx[:WIDTH:ROUNDS] (ArxDemo), matchcount[:N:FORM] (MatchCount), divrem[:N:BITS] (DivRem), tablewalk[:WIDTH:STEPS] (TableWalk), decompress[:POINTS] (EdwardsDecompress) or limbproduct[:COUNT:LIMBS] (LimbProduct)")
 ap.add_argument("--batch", type=int, default=16)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--curve", default="bls12_381")
@@ -54,8 +58,8 @@ ap.add_argument("--glue", choices=("host", "device"), default="host", help="devi
 ap.add_argument("--solve", action="store_true", help="host-synthesised assignments against partial assignments solved on the GPU")
 ap.add_argument("--reorder", default=None, metavar="reverse|SEED", help="with --solve: the circuit's rows stored reversed or shuffled by SEED (unmeasured)")
 a = ap.parse_args()
-if a.solve and not a.circuit.startswith(("mimc", "arx", "matchcount", "divrem", "tablewalk", "decompress")):
-    ap.error("--solve needs a mimcK, an arx, a matchcount, a divrem, a tablewalk or a decompress circuit")
+if a.solve and not a.circuit.startswith(("mimc", "arx", "matchcount", "divrem", "tablewalk", "decompress", "limbproduct")):
+    ap.error("--solve needs a mimcK, an arx, a matchcount, a divrem, a tablewalk, a decompress or a limbproduct circuit")
 if a.reorder is not None and not a.solve:
     ap.error("--reorder goes with --solve")
 pm = Polymath(a.curve, a.transcript, device=0)
@@ -95,6 +99,11 @@ elif a.circuit.startswith("decompress"):
     n_points = int(a.circuit.split(":")[1]) if ":" in a.circuit else 32
     make = lambda: PC.EdwardsDecompress(PC.edwards_ys(r, n_points, g.next_u64()), [g.next_u64() & 1 for _ in range(n_points)])
     again = lambda c: PC.EdwardsDecompress(c.ys, c.signs)
+    partial_of = lambda c: c.partial(r)
+elif a.circuit.startswith("limbproduct"):
+    n_products, n_limbs = (int(v) for v in a.circuit.split(":")[1:3]) if ":" in a.circuit else (64, 8)
+    make = lambda: PC.LimbProduct(PC.limb_products(r, n_products, n_limbs, g.next_u64()))
+    again = lambda c: PC.LimbProduct(c.products, c.first)
     partial_of = lambda c: c.partial(r)
 else:
     nc = int(a.circuit.split(":", 1)[1])
