@@ -228,6 +228,31 @@ int pm_pk_info(const pm_pk *pk, uint64_t *n, uint64_t *m0, uint64_t *sigma, uint
 int pm_pk_msm_plan(const pm_pk *pk, int which, uint64_t *pairs, unsigned *windows, unsigned *window_bits, int *tables);
 /* Copy (a range of) one base vector back to the host, x||y Montgomery, 16*fq_limbs bytes apart. */
 int pm_pk_export_bases(pm_ctx *ctx, const pm_pk *pk, int which, size_t offset, size_t len, uint64_t *out_xy);
+/* The witness solver's DECLARED HINTS (PM_ASSIGNMENT_SOLVE, "Declared hints" below): values that the circuit's witness generator
+ * computes and no row determines.  They belong to the key, because they are part of the circuit, like the matrices.  The call is
+ *     pm_pk_set_hints(ctx, pk, desc, n_words)  ==  pm_pk_load_bytes(ctx, curve of pk, (const uint8_t *)desc, 8 * n_words, PM_KEY_HINTS, 0, 1, 0, &pk)
+ * -- a FLAG of pm_pk_load_bytes' `validate` (below) and no entry point of its own, because the set of entry points is pinned.
+ * `pm_pk_set_hints` is ONLY SHORTHAND for that call, here and in the text of pm_last_error: the library exports no function of that
+ * name and a C caller calls pm_pk_load_bytes as written above (the Python and Rust wrappers have a set_hints that does).  With
+ * the flag no key is loaded and *out is not replaced: `bytes` is the declaration for the existing key *out.  PM_KEY_HINTS stands alone
+ * in `validate`, `curve` is the key's and `len` a multiple of 8, else PM_ERR_INVALID_ARG.  `desc` is a sequence of records of n_words
+ * 64-bit words (in memory order) in all; the one opcode is limb-wise long division:
+ *     PM_HINT_LONGDIV, n, kq, kr, kD, kE, flags,
+ *       kq quotient columns, kr remainder columns, kD dividend columns, then kE divisor columns
+ *       -- or, with PM_HINT_DIVISOR_LITERAL (flags bit 0), kE limb values of four words each (canonical integers, little-endian)
+ * Columns are CSR columns: 0 is the constant one, then the instance, then the witness.  The step stores the kq n-bit limbs of
+ * floor(D / E) and the kr n-bit limbs of D mod E for D = sum_j int(z_{D_j}) 2^(n j), E alike or the literal.
+ * PM_ERR_INVALID_ARG, pm_last_error naming the hint's index and the condition, the key unchanged: an unknown opcode, unknown flags or
+ * a truncated record; n outside 1..128; kD > 32, kE > 16, kq > 32, kr > 16, or any of them 0; n (kD - 1) >= 1024 or
+ * n (kE - 1) >= 512; a column >= m0 + mw; an output that is column 0; an output named twice, or by two hints, or also an input of
+ * its own hint; a literal limb >= r; a sharded key.  The refusals' text begins "pm_pk_set_hints: hint h: ".  A second call replaces
+ * the declaration and n_words = 0 clears it; a context's solving plan is rebuilt after either.  The caller must not race the call with
+ * calls that use the key, as with pm_pk_free.
+ * Out of scope: other opcodes (modular inverse, gcd, sorting), signed limbs, dividends beyond 1024 bits (RSA-2048), hints on sharded
+ * keys, per-assignment declarations, inferring a hint from rows. */
+typedef enum pm_hint_op { PM_HINT_LONGDIV = 1 } pm_hint_op;
+typedef enum pm_hint_flags { PM_HINT_DIVISOR_LITERAL = 1 } pm_hint_flags;
+typedef enum pm_key_hints { PM_KEY_HINTS = 1024 } pm_key_hints;
 void pm_pk_free(pm_pk *pk);
 
 /* ---- proving keys as bytes: ProvingKey::serialize_compressed (data_structures.rs:56-73), decoded on the device ---------
@@ -496,6 +521,26 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  *   was.  Not handled: an unknown in A_r or B_r (the matrix would depend on the assignment), rows over different sets (banded or
  *   triangular systems), k > 64, boolean- or pair-pending columns in the set, an independent subset of dependent rows, sharded keys,
  *   per-assignment patterns.
+ *   Declared hints (the scheduler only; pm_pk_set_hints above, beside pm_pk_free, states the declaration).  The quotient and remainder LIMBS of a
+ *   non-native reduction -- circom-bigint's BigMod / BigMultModP (div[i] <-- long_div(..)), ark-r1cs-std's non-native reduce -- are
+ *   multi-word integers that no row determines: the limb equations are underdetermined, uniqueness comes from the range checks, and
+ *   which rows name them differs per compiler, so there is no shape to recognise and no marker that could say "these 8 columns are
+ *   divmod of those 11".  The key DECLARES them instead: a hint PM_HINT_LONGDIV with limb width n names kq quotient columns, kr
+ *   remainder columns, kD dividend columns and kE divisor columns (or kE literal limbs).  In a call the hint is ACTIVE when all its
+ *   outputs carry PM_UNKNOWN_WORDS, INERT when all are given (the caller supplied q and rem; everything is as without the
+ *   declaration), and the call is refused, naming the hint, when some are marked and some given or one carries another marker.  An
+ *   output of an active hint is solved by no row: rows that name it wait, the hint waits for its inputs like a row, and when the last
+ *   is known it is ONE step: with int(v) the canonical integer of a field element, D = sum_j int(z_{D_j}) 2^(n j) and
+ *   E = sum_j int(z_{E_j}) 2^(n j) (limbs need not be normalised: the overflowing limbs of a no-carry product are the intended
+ *   dividend), it stores the kq n-bit limbs of floor(D / E) and the kr n-bit limbs of D mod E.  The assignment is STUCK, with zero in
+ *   every output, where E = 0, D >= 2^1024, E >= 2^512, q >= 2^(n kq) or rem >= 2^(n kr); the stuck word of hint h (its index in the
+ *   declaration) is nr + h, a value no row has, and the root-cause rule below applies to it with its dependency level:
+ *   pm_r1cs_check reports it in rows[i][0].  A hint that never becomes ready is refused as "hint h: input column c is never
+ *   determined", followed by what stays unknown.  With an active hint every refusal of the structure is reported from the scheduler,
+ *   as "column j stays unknown" with its reason: the row that the matrix-order pass would have named (a row with two or more
+ *   unknowns, an unknown in two matrices) is not named then, because no matrix order is tried.  Without a declaration, or with every hint inert, plans, messages and words are what
+ *   they are without this rule.  Not handled: other opcodes (modular inverse, gcd, sorting), signed limbs, dividends beyond 1024 bits
+ *   (RSA-2048), hints on sharded keys, per-assignment declarations, inferring a hint from rows.
  *   PM_ERR_INVALID_ARG, pm_last_error naming the row or column, nothing computed and no output written: an unsolvable row, a marked
  *   column that no row determines, a marker at column 0, a sharded key, and -- in a batch -- an assignment that does not mark the
  *   columns assignment 0 marks, or marks one with the other marker (any two of the four markers differ; the first differing (assignment, column) is named; a kernel

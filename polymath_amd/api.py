@@ -58,6 +58,11 @@ UNKNOWN_LIMBS = (0xFFFFFFFFFFFFFFFF,) * 4     # an Fr of x / w / instance_host w
 QUOTIENT_LIMBS = (0xFFFFFFFFFFFFFFFE,) + (0xFFFFFFFFFFFFFFFF,) * 3     # PM_UNKNOWN_QUOTIENT_WORDS: unknown, and the Euclidean quotient of a division row
 INDICATOR_LIMBS = (0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFE, 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFF)     # PM_HINT_INDICATOR_WORDS: unknown, and the indicator of its guard row
 SQRT_LIMBS = (0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFE)     # PM_HINT_SQRT_MARKER: unknown, and the smaller square root of its square-root row
+# the declared hints of the witness solver (include/polymath_hip.h): PM_KEY_HINTS, the flag of pm_pk_load_bytes' `validate` under which
+# `bytes` declares the hints of an existing key; the one opcode of a hint, its one flag and the limits of a record
+PM_KEY_HINTS = 1024
+HINT_LONGDIV, HINT_DIVISOR_LITERAL = 1, 1
+HINT_LIMITS = {"n": 128, "kq": 32, "kr": 16, "kD": 32, "kE": 16}
 NOT_STUCK = 0xFFFFFFFFFFFFFFFF                # first word of a tap-9 record of an assignment that completed
 TIMING_SLOTS = ["witness_map", "ntt", "poly", "msm_sort", "msm_accumulate", "msm_reduce", "msm_total", "phase"]
 
@@ -213,6 +218,56 @@ def _p(a):
 
 def _c(a):
     return np.ascontiguousarray(a, dtype=np.uint64)
+
+
+def encode_hints(hints):
+    """The words of pm_pk_set_hints for a list of hints.  A hint is a dict {"n", "q", "rem", "D", and "E" (divisor columns) or "literal"
+    (the divisor's limbs as Python integers)} or a tuple (n, q, rem, D, E) / (n, q, rem, D, None, literal); q, rem, D, E are lists of
+    CSR columns (0: the constant one, then the instance, then the witness).  -> np.uint64[n_words]"""
+    words = []
+    for hint in hints:
+        if isinstance(hint, dict):
+            n, q, rem, D, E, literal = hint["n"], hint["q"], hint["rem"], hint["D"], hint.get("E"), hint.get("literal")
+        else:
+            n, q, rem, D, E, literal = (tuple(hint) + (None,))[:6]
+        if (E is None) == (literal is None):
+            raise ValueError("a hint has divisor columns E or a literal divisor, not both and not neither")
+        divisor = list(E) if literal is None else list(literal)
+        words += [HINT_LONGDIV, int(n), len(q), len(rem), len(D), len(divisor), 0 if literal is None else HINT_DIVISOR_LITERAL]
+        words += [int(c) for c in list(q) + list(rem) + list(D)]
+        if literal is None:
+            words += [int(c) for c in divisor]
+        else:
+            for limb in divisor:
+                if not 0 <= int(limb) < 1 << 256:
+                    raise ValueError("a literal limb is four words")
+                words += [(int(limb) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]
+    return np.array(words, dtype=np.uint64)
+
+
+def decode_hints(words):
+    """encode_hints backwards: -> a list of dicts (the words are trusted to be well-formed: the library is what refuses)"""
+    words, out, at = [int(v) for v in words], [], 0
+    while at < len(words):
+        op, n, kq, kr, kD, kE, flags = words[at:at + 7]
+        if op != HINT_LONGDIV:
+            raise ValueError("unknown opcode %d" % op)
+        at += 7
+        take = lambda k: words[at:at + k]
+        hint = {"n": n, "q": take(kq)}
+        at += kq
+        hint["rem"] = take(kr)
+        at += kr
+        hint["D"] = take(kD)
+        at += kD
+        if flags & HINT_DIVISOR_LITERAL:
+            hint["literal"] = [sum(words[at + 4 * i + j] << (64 * j) for j in range(4)) for i in range(kE)]
+            at += 4 * kE
+        else:
+            hint["E"] = take(kE)
+            at += kE
+        out.append(hint)
+    return out
 
 
 def g1_sum(curve, pts, infs=None):
@@ -839,6 +894,18 @@ class ProvingKey:
         rc = self.ctx.L.pm_host_prove_batch(self.ctx.h, self.h, self.TRANSCRIPT_IDS[transcript] | PROVE_GLUE[glue], count, _p(inst), px, pw, int(bool(on_device)) | (ASSIGNMENT_SOLVE if solve else 0), _p(r_a),
                                             buf, proof_len, status.ctypes.data_as(ct.POINTER(ct.c_int)))
         return rc, buf.raw[:count * proof_len], status[:count]
+
+    def set_hints(self, hints):
+        """Declare the key's hints: pm_pk_load_bytes with PM_KEY_HINTS on this key (encode_hints takes the list; an empty one clears the
+        declaration) -> status"""
+        words = hints if isinstance(hints, np.ndarray) else encode_hints(hints)
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        raw = self.h.value if isinstance(self.h, ct.c_void_p) else self.h
+        key = ct.c_void_p(raw)
+        rc = self.ctx.L.pm_pk_load_bytes(self.ctx.h, self.cid, words.ctypes.data_as(ct.c_void_p) if words.size else None, int(words.size) * 8, PM_KEY_HINTS, 0, 1, 0,
+                                         ct.byref(key))
+        assert key.value == raw      # the key stays where it is
+        return rc
 
     def r1cs_check_batch(self, x, w, max_rows=16, residuals=False, on_device=False, count=None, solve=False):
         """pm_r1cs_check_batch: which constraint rows each of `count` assignments violates.  x, w: (count, m0, 4) / (count, mw, 4) host

@@ -6,7 +6,8 @@ witnesses the device completes from the inputs (PM_ASSIGNMENT_SOLVE, DESIGN.md Â
 ModChain: Euclidean division rows, whose quotients partial() marks QUOTIENT), and two that read a table at a signal (Decoder,
 TableWalk: circomlib's one-hot decoder, whose outputs partial() marks INDICATOR), and two that take square roots (SquareRoots,
 EdwardsDecompress: point decompression on Jubjub / Baby Jubjub, whose roots partial() marks SQRT), and three whose rows are square linear systems in their unknowns (LimbProduct, ProductChain: non-native
-multiplication, whose product limbs are pinned at 2l - 1 points; LinearBlocks: random systems), which the solver takes as linear blocks; Reordered emits any of them with its rows in another
+multiplication, whose product limbs are pinned at 2l - 1 points; LinearBlocks: random systems), which the solver takes as linear blocks, and two that multiply modulo a foreign prime (LimbModMul, ModMulChain: the product's block, then the
+quotient and remainder limbs of the reduction, which no row determines: hints() is the long division the key declares for them); Reordered emits any of them with its rows in another
 order, which the solver's any-order planner accepts."""
 from .polymath import INDICATOR, QUOTIENT, SQRT, ConstraintSystem, Field, LimbCircuit, R1CS, small_sqrt
 
@@ -761,6 +762,195 @@ class ProductChain(_Partial):
             total += sum(p)
             x = p[:len(x)]
         return [1, total % r], witness
+
+
+def int_limbs(value, n, count):
+    """the `count` n-bit limbs of a non-negative integer, least significant first (the value must fit)"""
+    assert 0 <= value < 1 << (n * count)
+    return [(value >> (n * i)) & ((1 << n) - 1) for i in range(count)]
+
+
+def limbs_int(limbs, n):
+    """sum limbs_j 2^(n j): the integer of limbs that need not be normalised"""
+    return sum(v << (n * j) for j, v in enumerate(limbs))
+
+
+def modmul_values(a, b, p, n, r):
+    """What one non-native modular multiplication witnesses, on Python integers: a, b, p are lists of l limbs of n bits (a and b such
+    that no limb of the no-carry product reaches r).  -> (P, q, rem, qp, carries): the 2l - 1 product limbs, the l limbs of
+    floor(a b / p) and of a b mod p (Python's divmod), the 2l - 1 limbs of the no-carry product q p mod r, and the 2l - 2 carries of
+    P_j - qp_j - rem_j + carry_{j-1} = carry_j 2^n  as field elements (a negative carry is r - |carry|)."""
+    l = len(a)
+    P = limb_product(a, b, r)
+    exact = [sum(a[i] * b[j - i] for i in range(l) if 0 <= j - i < l) for j in range(2 * l - 1)]
+    assert P == exact, "a limb of the no-carry product reaches r: D would not be a b"
+    q_int, rem_int = divmod(limbs_int(a, n) * limbs_int(b, n), limbs_int(p, n))
+    q, rem = int_limbs(q_int, n, l), int_limbs(rem_int, n, l)
+    qp_exact = [sum(q[i] * p[j - i] for i in range(l) if 0 <= j - i < l) for j in range(2 * l - 1)]
+    carries, carry = [], 0
+    for j in range(2 * l - 1):
+        total = exact[j] - qp_exact[j] - (rem[j] if j < l else 0) + carry
+        assert total % (1 << n) == 0
+        carry = total >> n                      # exact: Python's shift of a negative integer floors, and the remainder is zero
+        if j < 2 * l - 2:
+            carries.append(carry % r)
+    assert carry == 0
+    return P, q, rem, [v % r for v in qp_exact], carries
+
+
+class _PartialModMul(_Partial):
+    """What LimbModMul and ModMulChain share: one non-native modular multiplication x y mod p on l limbs of n bits, and the hints that
+    it declares.  The witnesses, in this order: the 2l - 1 limbs P of the no-carry product (the rows of _product_rows at the points
+    1 .. 2l - 1: a linear block), the l limbs of q and the l limbs of rem (HINTED: no row determines them; the hint divides P by p),
+    with `decompose` the n booleans of every limb of q and of rem with their booleanity rows and the row  limb * 1 = sum 2^i b_i, the
+    2l - 1 limbs qp of the no-carry product q p (a literal p: ordinary rows (sum_k p_k q_{j-k}) * 1 = qp_j ; p in witness columns: the rows of
+    _product_rows, a second block), the 2l - 2 carries, one unknown each in  (P_j - qp_j - rem_j + carry_{j-1}) * 1 = 2^n carry_j , and the
+    closing check row of limb 2l - 2, which has no carry to name."""
+
+    def _modmul(self, cs, x, x_v, y, y_v, p_v, p=None):
+        """-> (rem variables, rem values).  x, y: variables and values of the operands' limbs; p_v: the modulus' limbs, p: its
+        variables where it is a witness"""
+        one, r, n, l = ConstraintSystem.ONE, cs.r, self.n, self.limbs
+        P_v, q_v, rem_v, qp_v, carry_v = modmul_values(x_v, y_v, p_v, n, r)
+        P = [cs.new_witness_variable(v) for v in P_v]
+        _product_rows(cs, x, y, P, 1)
+        q = [cs.new_witness_variable(v) for v in q_v]
+        rem = [cs.new_witness_variable(v) for v in rem_v]
+        if self.decompose:
+            for var, value in zip(q + rem, q_v + rem_v):
+                cs.enforce_constraint([(1, var)], [(1, one)], _weighted(_new_bits(cs, value, n)))
+        qp = [cs.new_witness_variable(v) for v in qp_v]
+        if p is None:
+            for j in range(2 * l - 1):
+                cs.enforce_constraint([(p_v[j - i] % r, q[i]) for i in range(l) if 0 <= j - i < l and p_v[j - i]], [(1, one)], [(1, qp[j])])
+        else:
+            _product_rows(cs, q, p, qp, 1)
+        carries = [cs.new_witness_variable(v) for v in carry_v]
+        for j in range(2 * l - 1):
+            lc = [(1, P[j]), (-1, qp[j])] + ([(-1, rem[j])] if j < l else []) + ([(1, carries[j - 1])] if j else [])
+            cs.enforce_constraint(lc, [(1, one)], [(pow(2, n, r), carries[j])] if j < 2 * l - 2 else [])
+        return rem, rem_v
+
+    def _width(self):
+        """the witnesses of one multiplication: P, q, rem, the bits, qp, the carries"""
+        l = self.limbs
+        return (2 * l - 1) + 2 * l + (2 * l * self.n if self.decompose else 0) + (2 * l - 1) + (2 * l - 2)
+
+    def _hint(self, m0, at, p_cols=None):
+        """the long division of the multiplication whose witnesses begin at witness index `at`; m0: the instance's length, which a
+        witness index is offset by to give its CSR column"""
+        l, first = self.limbs, m0 + at
+        hint = {"n": self.n, "q": list(range(first + 2 * l - 1, first + 3 * l - 1)), "rem": list(range(first + 3 * l - 1, first + 4 * l - 1)),
+                "D": list(range(first, first + 2 * l - 1))}
+        if p_cols is None:
+            hint["literal"] = int_limbs(self.modulus, self.n, l)
+        else:
+            hint["E"] = list(p_cols)
+        return hint
+
+
+class LimbModMul(_PartialModMul):
+    """Non-native modular multiplication (circom-bigint's BigMultModP, ark-r1cs-std's mul + reduce): per pair (a, b) of integers the
+    given limbs of a and of b, the multiplication a b mod `modulus` of _PartialModMul with a literal modulus, and one ordinary row
+    (sum rem_i) * 1 = s ; the public input is sum s.  The caller chooses a and b; the product limbs are a linear block, q and rem are
+    the outputs of the declared hint (hints()), and everything else follows by ordinary rows and decompositions.  l max(a_i) max(b_i)
+    must stay below r (modmul_values asserts it): the hint's dividend is the integer of the product limbs."""
+
+    def __init__(self, pairs, modulus, n, limbs, decompose=True):
+        self.pairs, self.modulus, self.n, self.limbs, self.decompose = [(int(a), int(b)) for a, b in pairs], int(modulus), n, limbs, decompose
+
+    def hints(self, m0=2):
+        """the declaration for Polymath.set_hints / api.encode_hints: one long division per pair, with the modulus as a literal"""
+        per = 2 * self.limbs + self._width() + 1
+        return [self._hint(m0, i * per + 2 * self.limbs) for i in range(len(self.pairs))]
+
+    def generate_constraints(self, cs):
+        self._chosen = []
+        one, n, l = ConstraintSystem.ONE, self.n, self.limbs
+        p_v = int_limbs(self.modulus, n, l)
+        total, total_v = [], 0
+        for a_int, b_int in self.pairs:
+            a_v, b_v = int_limbs(a_int, n, l), int_limbs(b_int, n, l)
+            a = [self._given(cs, v) for v in a_v]
+            b = [self._given(cs, v) for v in b_v]
+            rem, rem_v = self._modmul(cs, a, a_v, b, b_v, p_v)
+            s = cs.new_witness_variable(sum(rem_v))
+            cs.enforce_constraint([(1, v) for v in rem], [(1, one)], [(1, s)])
+            total.append((1, s))
+            total_v += sum(rem_v)
+        out = cs.new_input_variable(total_v)
+        cs.enforce_constraint(total, [(1, one)], [(1, out)])
+
+    def native(self, r):
+        """-> (instance, witness) on Python integers, without generating a row; rem is (a b) mod modulus by Python's divmod"""
+        n, l = self.n, self.limbs
+        p_v = int_limbs(self.modulus, n, l)
+        witness, total = [], 0
+        for a_int, b_int in self.pairs:
+            a_v, b_v = int_limbs(a_int, n, l), int_limbs(b_int, n, l)
+            P, q, rem, qp, carries = modmul_values(a_v, b_v, p_v, n, r)
+            assert limbs_int(rem, n) == a_int * b_int % self.modulus
+            bits = [(v >> i) & 1 for v in q + rem for i in range(n)] if self.decompose else []
+            witness += a_v + b_v + P + q + rem + bits + qp + carries + [sum(rem) % r]
+            total += sum(rem)
+        return [1, total % r], witness
+
+
+class ModMulChain(_PartialModMul):
+    """x_{t+1} = x_t b mod p for `steps` steps on l limbs of n bits: x_0 and b given, p a literal or -- witness_modulus -- l more given
+    witnesses (the divisor of every hint is then its columns, and q p a second linear block per step); per step the multiplication of
+    _PartialModMul, whose rem is x_{t+1}, and  (sum rem_i) * 1 = s_t ; the public input is sum s_t.  Blocks, hints, decompositions and
+    carry rows alternate over 4 levels a step."""
+
+    def __init__(self, x0, b, modulus, n, limbs, steps, witness_modulus=False, decompose=True):
+        self.x0, self.b, self.modulus, self.n, self.limbs, self.steps = int(x0), int(b), int(modulus), n, limbs, steps
+        self.witness_modulus, self.decompose = witness_modulus, decompose
+
+    def hints(self, m0=2):
+        """the declaration for Polymath.set_hints / api.encode_hints: one long division per step, its divisor the literal modulus or
+        the modulus' witness columns"""
+        l = self.limbs
+        head = 3 * l if self.witness_modulus else 2 * l
+        p_cols = range(m0 + 2 * l, m0 + 3 * l) if self.witness_modulus else None
+        return [self._hint(m0, head + t * (self._width() + 1), p_cols) for t in range(self.steps)]
+
+    def generate_constraints(self, cs):
+        self._chosen = []
+        one, n, l = ConstraintSystem.ONE, self.n, self.limbs
+        x_v, b_v, p_v = int_limbs(self.x0, n, l), int_limbs(self.b, n, l), int_limbs(self.modulus, n, l)
+        x = [self._given(cs, v) for v in x_v]
+        b = [self._given(cs, v) for v in b_v]
+        p = [self._given(cs, v) for v in p_v] if self.witness_modulus else None
+        total, total_v = [], 0
+        for _ in range(self.steps):
+            x, x_v = self._modmul(cs, x, x_v, b, b_v, p_v, p)
+            s = cs.new_witness_variable(sum(x_v))
+            cs.enforce_constraint([(1, v) for v in x], [(1, one)], [(1, s)])
+            total.append((1, s))
+            total_v += sum(x_v)
+        out = cs.new_input_variable(total_v)
+        cs.enforce_constraint(total, [(1, one)], [(1, out)])
+
+    def native(self, r):
+        """-> (instance, witness) on Python integers, without generating a row; x_t = x_0 b^t mod p by Python's pow"""
+        n, l = self.n, self.limbs
+        x_v, b_v, p_v = int_limbs(self.x0, n, l), int_limbs(self.b, n, l), int_limbs(self.modulus, n, l)
+        witness, total = x_v + b_v + (p_v if self.witness_modulus else []), 0
+        for t in range(self.steps):
+            P, q, rem, qp, carries = modmul_values(x_v, b_v, p_v, n, r)
+            assert limbs_int(rem, n) == self.x0 * pow(self.b, t + 1, self.modulus) % self.modulus
+            bits = [(v >> i) & 1 for v in q + rem for i in range(n)] if self.decompose else []
+            witness += P + q + rem + bits + qp + carries + [sum(rem) % r]
+            total += sum(rem)
+            x_v = rem
+        return [1, total % r], witness
+
+
+def modmul_pairs(modulus, count, seed=SPLITMIX_SEED, bits=None):
+    """`count` pairs of integers below `modulus` (or below 2^bits) for LimbModMul, drawn from SplitMix64(seed)"""
+    g = SplitMix64(seed)
+    draw = lambda: sum(g.next_u64() << (64 * i) for i in range(-(-modulus.bit_length() // 64))) % (modulus if bits is None else 1 << bits)
+    return [(draw(), draw()) for _ in range(count)]
 
 
 def _invertible(rows, r):

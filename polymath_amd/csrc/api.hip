@@ -786,8 +786,20 @@ static int pk_load_bytes_impl(pm_ctx *ctx, const uint8_t *bytes, size_t len, int
         out);
 }
 
+static int pm_pk_set_hints(pm_ctx *ctx, pm_pk *pk, const uint64_t *desc, size_t n_words);
+
 extern "C" int pm_pk_load_bytes(pm_ctx *ctx, int curve, const uint8_t *bytes, size_t len, int validate, int shard_rank, int shard_count,
                                 int layout, pm_pk **out) {
+    if (validate & PM_KEY_HINTS) {   // no key is loaded: `bytes` declares the hints of the existing key *out, which stays where it is
+        if (!ctx || !out || !*out || (len && !bytes)) return PM_ERR_INVALID_ARG;
+        if (validate != PM_KEY_HINTS || (*out)->curve != curve || len % sizeof(uint64_t) != 0) {
+            ctx->err = "pm_pk_load_bytes: PM_KEY_HINTS stands alone in `validate`, takes the key's curve and a whole number of 64-bit words";
+            return PM_ERR_INVALID_ARG;
+        }
+        std::vector<uint64_t> desc(len / sizeof(uint64_t));   // the caller's bytes need not be aligned
+        if (len) memcpy(desc.data(), bytes, len);
+        return pm_pk_set_hints(ctx, *out, desc.data(), desc.size());
+    }
     if (!ctx || !bytes || !out) return PM_ERR_INVALID_ARG;
     *out = nullptr;
     return pk_entry(ctx, curve, [&](auto cv) {
@@ -936,6 +948,40 @@ extern "C" int pm_pk_info(const pm_pk *pk, uint64_t *n, uint64_t *m0, uint64_t *
     if (sigma) *sigma = pk->sigma;
     if (omega) memcpy(omega, pk->omega, 32);
     if (base_lens) for (int i = 0; i < PM_NUM_BASE_VECS; ++i) base_lens[i] = pk->base_len[i];
+    return PM_OK;
+}
+
+// The witness solver's declared hints: PM_KEY_HINTS of pm_pk_load_bytes (below), stated as the call it is -- pm_pk_set_hints(ctx, pk,
+// desc, n_words) -- because the set of entry points is pinned (host/solve_plan.hpp: decode_hints states the record format and every
+// refusal).  The key is changed only when the whole declaration is accepted; a new generation number keeps a context from reusing a
+// plan made under the old one (solve.hip: solve_plan).
+static int pm_pk_set_hints(pm_ctx *ctx, pm_pk *pk, const uint64_t *desc, size_t n_words) {
+    if (!ctx || !pk || (n_words && !desc)) return PM_ERR_INVALID_ARG;
+    if (pk->shard_count != 1 || pk->layout != PM_SHARD_PAIRS) {
+        ctx->err = "pm_pk_set_hints: hints on a sharded key are not supported";
+        return PM_ERR_INVALID_ARG;
+    }
+    try {
+        std::vector<pmsolve::Hint> hints;
+        std::string why;
+        const int st = pm::with_curve(pk->curve, [&](auto cv) {
+            typedef typename pm::type_of<decltype(cv)>::FrP P;
+            uint64_t modulus[4];
+            for (int i = 0; i < 4; ++i) modulus[i] = (uint64_t)P::MOD[2 * i] | (uint64_t)P::MOD[2 * i + 1] << 32;
+            why = pmsolve::decode_hints(desc, n_words, pk->m0 + pk->mw, modulus, hints);
+            return (int)PM_OK;
+        });
+        if (st != PM_OK) return st;
+        if (!why.empty()) {
+            ctx->err = "pm_pk_set_hints: " + why;
+            return PM_ERR_INVALID_ARG;
+        }
+        pk->hints.swap(hints);
+        pk->hint_gen = pm::pk_serial_next();
+    } catch (const std::bad_alloc &) {
+        ctx->err = "pm_pk_set_hints: out of host memory";
+        return PM_ERR_STATE;
+    }
     return PM_OK;
 }
 

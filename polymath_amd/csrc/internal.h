@@ -181,22 +181,24 @@ struct GlueWs {
     }
 };
 
-// Witness solving (solve.hip): the context's plan cache -- one plan, keyed by (key, unknown pattern) -- and the buffers of the last
+// Witness solving (solve.hip): the context's plan cache -- one plan, keyed by (key, the key's hint generation, unknown pattern) -- and the buffers of the last
 // call with PM_ASSIGNMENT_SOLVE.  xw: the completed x || w rows of a check call (pm_prove_tap(10)); the prover completes its groups in
 // its own workspace (ProveWs::xw) and keeps only tap9.
 struct SolveWs {
-    DevBuf xw, pattern, mismatch, stuck, steps, bit_cols, pairs, divs, blocks, block_idx, block_inv;
+    DevBuf xw, pattern, mismatch, stuck, steps, bit_cols, pairs, divs, blocks, block_idx, block_inv, hints, hint_idx;
     pmsolve::Plan plan;
     size_t n_pairs = 0;                  // is-zero pairs of the plan: records in `pairs`
     size_t n_divs = 0;                   // division rows of the plan: records in `divs`
     size_t n_blocks = 0;                 // linear blocks of the plan: records in `blocks`, rows and columns in `block_idx`, inverses in `block_inv`
+    size_t n_hints = 0;                  // long divisions of the plan: records in `hints`, columns and literal divisors in `hint_idx`
     uint64_t plan_key = 0;               // pm_pk::serial of the plan's key; 0 = no plan
+    uint64_t plan_hint_gen = 0;          // pm_pk::hint_gen of the plan's key when the plan was made
     std::vector<uint8_t> plan_pattern;   // one byte per column
     std::vector<uint64_t> tap9;          // pm_prove_tap(9): per assignment 4 * (1 + m0) words; empty = no call with the flag yet
     size_t tap10_rows = 0;               // pm_prove_tap(10): rows of xw that hold a check call's completed assignments; 0 = none
     size_t tap10_cols = 0;
     void release() {
-        for (DevBuf *b : {&xw, &pattern, &mismatch, &stuck, &steps, &bit_cols, &pairs, &divs, &blocks, &block_idx, &block_inv}) b->release();
+        for (DevBuf *b : {&xw, &pattern, &mismatch, &stuck, &steps, &bit_cols, &pairs, &divs, &blocks, &block_idx, &block_inv, &hints, &hint_idx}) b->release();
     }
 };
 
@@ -231,6 +233,10 @@ struct pm_pk : pm::KeyPlan {
     uint64_t serial = pm::pk_serial_next();
     int curve = 0, device = 0;
     uint64_t omega[4] = {0, 0, 0, 0};
+    // the declared hints of the witness solver (pm_pk_set_hints): part of the circuit, like the matrices.  hint_gen changes with
+    // every declaration (0: none was ever made), so that a plan made under another declaration is not reused
+    std::vector<pmsolve::Hint> hints;
+    uint64_t hint_gen = 0;
     // Every device allocation of the key is made by alloc() and freed by the destructor; the typed pointers below are views of them.
     std::vector<void *> owned;
     template <class T>

@@ -2,7 +2,7 @@
 // (include/polymath_hip.h), so that a caller supplies only the values it chooses and the library computes the rest
 // before it checks or proves.  The PLAN -- which row determines which column, in which order -- is host work, done once per (key,
 // pattern) by host/solve_plan.hpp; what ONE step does to ONE assignment (solve_step, solve_bits, solve_iszero, solve_divrem,
-// solve_indicator, solve_sqrt, solve_block, the dispatch solve_any, the inverses' solve_inverse and solve_block_invert, and the records
+// solve_indicator, solve_sqrt, solve_block, solve_longdiv, the dispatch solve_any, the inverses' solve_inverse and solve_block_invert, and the records
 // a plan becomes: solve_records) is
 // solve_steps.cuh, text that the CPU self-tests run as well; this file is the kernels that call it and the host driver,
 // assignment = grid y (or the lane, in the chain kernel):
@@ -27,6 +27,10 @@
 //                     i < k forms the right-hand side of row i into LDS, lane j < k accumulates column j from the LDS values and the
 //                     transposed inverse of the block's matrix, which solve_plan computed on the host once per plan (distinct matrices
 //                     only: solve_steps.cuh, solve_block_invert).  No division, no atomic, never stuck
+//   k_solve_longdiv   the declared long divisions of a level (pm_pk_set_hints), whatever its width: one lane per (hint, assignment).  The
+//                     input limbs leave Montgomery form and are accumulated at bit offset n j into a 1024-bit dividend and a 512-bit
+//                     divisor, a restoring shift-subtract divides in the launch's trip count (wave-uniform: the plan's bound, at most 1024; solve_steps.cuh: longdiv), and the n-bit limbs
+//                     of quotient and remainder are stored.  No register is indexed at run time; stuck at the word nr + h
 //   k_solve_chain     a run of consecutive NARROW levels: one lane per assignment walks the run's steps in plan order.  A lane
 //                     reads back only its own stores: no barriers, no fences.  The MiMC shape (depth 644, width 1) is one such run
 //                     and the batch is its parallel dimension.
@@ -166,6 +170,17 @@ __global__ __launch_bounds__(256) void k_solve_block(Csr A, Csr B, Csr Cm, const
     if (lane < blk.k) z[block_idx[blk.cols_off + lane]] = solve_block_out<P>(block_inv + blk.inv_off, blk.k, lane, rhs[wave]);
 }
 
+// One lane per (hint, assignment); 64 lanes to a workgroup, so that a level of a few hundred hints spreads over the device.  The lane
+// holds the dividend (32 words), the divisor (16), the remainder (17) and the trial difference (17) in registers.
+template <class P>
+__global__ __launch_bounds__(64) void k_solve_longdiv(const SolveStepDev<P> *__restrict__ steps, const SolveHintDev *__restrict__ hints,
+                                                      const uint32_t *__restrict__ hint_idx, uint32_t rounds, uint32_t lo, uint32_t hi, Fp<P> *xw,
+                                                      uint64_t ncols, unsigned long long *stuck) {
+    const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (t >= hi) return;
+    solve_longdiv<P>(steps[t], hints[steps[t].bits], hint_idx, rounds, xw + b * ncols, StuckWord{stuck + b});
+}
+
 // the step index is the same in every lane: the step record, the pair record, the row's CSR metadata and a decomposition's column
 // list are uniform loads (solve_steps.cuh: solve_any, the dispatch by kind).
 template <class P, bool DIV>
@@ -246,7 +261,7 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
                    ": every assignment of a batch must mark the same columns";
         return PM_ERR_INVALID_ARG;
     }
-    if (sv.plan_key == pk->serial && sv.plan_pattern == pattern) return PM_OK;
+    if (sv.plan_key == pk->serial && sv.plan_hint_gen == pk->hint_gen && sv.plan_pattern == pattern) return PM_OK;
     sv.plan_key = 0;
     // the key's matrices come down once per plan: the key keeps no host copy
     std::vector<uint64_t> rowptr[3], val[3];
@@ -267,7 +282,7 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
     PM_HIP(ctx, hipStreamSynchronize(st));
     uint64_t modulus[4];
     for (int i = 0; i < 4; ++i) modulus[i] = (uint64_t)P::MOD[2 * i] | (uint64_t)P::MOD[2 * i + 1] << 32;
-    sv.plan = pmsolve::build_plan_any_order(m, nr, pk->m0, pk->mw, pattern.data(), pmsolve::WIDE_STEPS, modulus);
+    sv.plan = pmsolve::build_plan_any_order(m, nr, pk->m0, pk->mw, pattern.data(), pmsolve::WIDE_STEPS, modulus, pk->hints.empty() ? nullptr : &pk->hints);
     if (sv.plan.error != pmsolve::OK) {
         ctx->err = "pm solve: " + sv.plan.message;
         return PM_ERR_INVALID_ARG;
@@ -282,7 +297,7 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
                 return PM_ERR_STATE;
             }
     const size_t n_steps = sv.plan.steps.size();
-    sv.n_pairs = sv.n_divs = sv.n_blocks = 0;
+    sv.n_pairs = sv.n_divs = sv.n_blocks = sv.n_hints = 0;
     if (n_steps) {
         SolveRecords<P> rec = solve_records<P>(sv.plan);
         // the linear blocks' matrices are constants of the key: each distinct one is inverted here, once per plan, from the words the
@@ -309,6 +324,13 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
             PM_HIP(ctx, sv.block_inv.reserve(rec.block_inv.size() * sizeof(Fp<P>)));
             PM_HIP(ctx, hipMemcpyAsync(sv.block_inv.p, rec.block_inv.data(), rec.block_inv.size() * sizeof(Fp<P>), hipMemcpyHostToDevice, st));
         }
+        sv.n_hints = rec.hints.size();
+        if (sv.n_hints) {
+            PM_HIP(ctx, sv.hints.reserve(sv.n_hints * sizeof(SolveHintDev)));
+            PM_HIP(ctx, hipMemcpyAsync(sv.hints.p, rec.hints.data(), sv.n_hints * sizeof(SolveHintDev), hipMemcpyHostToDevice, st));
+            PM_HIP(ctx, sv.hint_idx.reserve(rec.hint_idx.size() * sizeof(uint32_t)));
+            PM_HIP(ctx, hipMemcpyAsync(sv.hint_idx.p, rec.hint_idx.data(), rec.hint_idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        }
         sv.n_pairs = rec.pairs.size();
         if (sv.n_pairs) {
             PM_HIP(ctx, sv.pairs.reserve(sv.n_pairs * sizeof(SolvePairDev<P>)));
@@ -333,6 +355,7 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
     }
     sv.plan_pattern.swap(pattern);
     sv.plan_key = pk->serial;
+    sv.plan_hint_gen = pk->hint_gen;
     return PM_OK;
 }
 
@@ -342,7 +365,7 @@ int solve_group(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t 
     typedef Fp<P> Fr;
     SolveWs &sv = ctx->sv;
     const uint64_t m0 = pk->m0, ncols = m0 + pk->mw;
-    if (g == 0 || g > 65535 || sv.plan_key != pk->serial || (g0 + g) * 4 * (1 + m0) > sv.tap9.size()) return PM_ERR_STATE;
+    if (g == 0 || g > 65535 || sv.plan_key != pk->serial || sv.plan_hint_gen != pk->hint_gen || (g0 + g) * 4 * (1 + m0) > sv.tap9.size()) return PM_ERR_STATE;
     hipStream_t st = ctx->stream;
     TimingGuard timing_guard{ctx};
     PM_HIP(ctx, sv.stuck.reserve(g * sizeof(unsigned long long)));
@@ -360,6 +383,10 @@ int solve_group(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t 
                 if (!sv.n_blocks) return PM_ERR_STATE;
                 hipLaunchKernelGGL((k_solve_block<P>), dim3(nblk(l.hi - l.lo, 4), (unsigned)g), dim3(256), 0, st, A, B, Cm, steps, sv.blocks.as<SolveBlockDev>(),
                                    sv.block_idx.as<uint32_t>(), sv.block_inv.as<Fp<P>>(), l.lo, l.hi, d_xw, ncols);
+            } else if (l.longdiv) {
+                if (!sv.n_hints || l.rounds < 256 || l.rounds > 1024) return PM_ERR_STATE;
+                hipLaunchKernelGGL((k_solve_longdiv<P>), dim3(nblk(l.hi - l.lo, 64), (unsigned)g), dim3(64), 0, st, steps, sv.hints.as<SolveHintDev>(),
+                                   sv.hint_idx.as<uint32_t>(), l.rounds, l.lo, l.hi, d_xw, ncols, stuck);
             } else if (l.chain) {
                 const dim3 grid(nblk(g, 64)), block(64);
                 if (l.divides) hipLaunchKernelGGL((k_solve_chain<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, pairs, divs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);

@@ -57,6 +57,13 @@ struct SolveBlockDev {
     uint64_t inv_off;                // in elements
 };
 
+// what a long-division step needs beside its SolveStepDev (whose bits = its SolveHintDev): in the hint pool from `off` the kq quotient
+// columns, the kr remainder columns, the kD dividend columns, then the kE divisor columns -- or, literal != 0, the 16 words of the
+// divisor's literal limbs accumulated at bit offset n j and one word that is non-zero where they reach 2^512 (solve_records forms both)
+struct SolveHintDev {
+    uint32_t n, kq, kr, kD, kE, literal, off, pad;
+};
+
 // The record arrays of a plan, as the kernels read them; the inverses are left zero (solve_inverse fills them), the pool of block
 // inverses empty (solve_block_inverses fills it).
 template <class P>
@@ -68,7 +75,111 @@ struct SolveRecords {
     std::vector<uint32_t> block_idx;      // the blocks' rows and columns
     std::vector<uint64_t> mat_off;        // per distinct matrix: where its inverse begins in block_inv; one more entry: the pool's size
     std::vector<Fp<P>> block_inv;         // the inverse pool
+    std::vector<SolveHintDev> hints;
+    std::vector<uint32_t> hint_idx;       // the hint pool
 };
+
+constexpr int LONGDIV_WD = 32, LONGDIV_WE = 16;   // the long division's registers in 32-bit words: a 1024-bit dividend, a 512-bit divisor
+
+// acc += v << off for the 256-bit v (eight words) and the W-word acc, off < 32 W.  -> non-zero where bits were lost above 32 W.  No
+// register is indexed by `off`: the word of the shifted value (nine words) that falls on acc[w] is selected by comparison, W x 9 selects.
+template <int W>
+PM_HD uint32_t add_shifted(uint32_t (&acc)[W], const uint32_t v[8], uint32_t off) {
+    const uint32_t wo = off >> 5, down = 32u - (off & 31u);   // down in 1..32: a 64-bit shift
+    uint32_t s[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const uint64_t pair = (uint64_t)(k < 8 ? v[k] : 0u) << 32 | (k > 0 ? v[k - 1] : 0u);
+        s[k] = (uint32_t)(pair >> down);
+    }
+    uint32_t carry = 0, lost = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        const uint32_t k = (uint32_t)w - wo;
+        uint32_t t = 0;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) t = k == (uint32_t)i ? s[i] : t;
+        const uint64_t sum = (uint64_t)acc[w] + t + carry;
+        acc[w] = (uint32_t)sum;
+        carry = (uint32_t)(sum >> 32);
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) lost |= wo + (uint32_t)i >= (uint32_t)W ? s[i] : 0u;
+    return lost | carry;
+}
+
+// word i of the W-word src, zero where i >= W: selected by comparison, W selects, no register indexed by i
+template <int W>
+PM_HD uint32_t word_at(const uint32_t (&src)[W], uint32_t i) {
+    uint32_t g = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w) g = (uint32_t)w == i ? src[w] : g;
+    return g;
+}
+
+// the low `keep` bits of a word (keep >= 32: all of it)
+PM_HD uint32_t low_bits(uint32_t word, uint32_t keep) { return word & (keep >= 32u ? ~0u : (1u << keep) - 1u); }
+
+// The n-bit limb (n <= 128) of the W-word src at bit offset off, as a canonical element: five source words selected by comparison
+// (5 W selects, held in five scalars: no private array), a 64-bit shift per output word, a mask.  Bits at and above 32 W read as zero.
+template <class P, int W>
+PM_HD Fp<P> limb_at(const uint32_t (&src)[W], uint32_t off, uint32_t n) {
+    static_assert(P::N == 8, "four 64-bit words");
+    const uint32_t wo = off >> 5, bs = off & 31u;
+    const uint32_t g0 = word_at<W>(src, wo), g1 = word_at<W>(src, wo + 1), g2 = word_at<W>(src, wo + 2), g3 = word_at<W>(src, wo + 3), g4 = word_at<W>(src, wo + 4);
+    Fp<P> out;
+    out.l[0] = low_bits((uint32_t)(((uint64_t)g1 << 32 | g0) >> bs), n);
+    out.l[1] = low_bits((uint32_t)(((uint64_t)g2 << 32 | g1) >> bs), n > 32u ? n - 32u : 0u);
+    out.l[2] = low_bits((uint32_t)(((uint64_t)g3 << 32 | g2) >> bs), n > 64u ? n - 64u : 0u);
+    out.l[3] = low_bits((uint32_t)(((uint64_t)g4 << 32 | g3) >> bs), n > 96u ? n - 96u : 0u);
+    out.l[4] = out.l[5] = out.l[6] = out.l[7] = 0;
+    return out;
+}
+
+// the bits of the W-word a from bit `from` upwards, or-ed together: non-zero where a >= 2^from
+template <int W>
+PM_HD uint32_t bits_from(const uint32_t (&a)[W], uint32_t from) {
+    uint32_t high = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w) high |= 32u * w >= from ? a[w] : 32u * (w + 1) > from ? a[w] >> (from - 32u * w) : 0u;
+    return high;
+}
+
+// divrem.cuh's restoring shift-subtract on 32-bit words: num = floor(num / d) and rem = num mod d for a WD-word dividend and a
+// WE-word divisor d != 0; rem has WE + 1 words (twice a remainder plus a bit may reach 2^(32 WE + 1) - 1; what is left is below d).
+// The quotient is shifted into the dividend's register from the bottom, where the dividend's bits have left.  `rounds` <= 32 WD is the
+// trip count, the same in every lane of a launch (the plan's bound: Launch::rounds): the dividend is below 2^rounds and comes
+// SHIFTED LEFT by 32 WD - rounds, so that its bits leave the register's top from the first round on; after `rounds` rounds the
+// register holds the quotient and nothing else.  Every word loop unrolled, the round loop rolled; no branch and no register index
+// depends on an operand.  d == 0 gives a quotient of `rounds` ones: the caller tests for it.
+template <int WD, int WE>
+PM_HD void longdiv(uint32_t (&num)[WD], const uint32_t (&d)[WE], uint32_t (&rem)[WE + 1], uint32_t rounds) {
+#pragma unroll
+    for (int j = 0; j <= WE; ++j) rem[j] = 0;
+#pragma unroll 1
+    for (uint32_t round = 0; round < rounds; ++round) {
+#pragma unroll
+        for (int j = WE; j > 0; --j) rem[j] = rem[j] << 1 | rem[j - 1] >> 31;
+        rem[0] = rem[0] << 1 | num[WD - 1] >> 31;
+#pragma unroll
+        for (int j = WD - 1; j > 0; --j) num[j] = num[j] << 1 | num[j - 1] >> 31;
+        num[0] <<= 1;
+        uint32_t t[WE + 1], borrow = 0;
+#pragma unroll
+        for (int j = 0; j <= WE; ++j) {
+            const uint32_t dj = j < WE ? d[j < WE ? j : 0] : 0u;
+            const uint32_t x = rem[j] - borrow;
+            const uint32_t b1 = rem[j] < borrow;
+            t[j] = x - dj;
+            borrow = b1 | (uint32_t)(x < dj);
+        }
+        const uint32_t take = borrow ^ 1u;          // 2 rem + bit >= d
+        const uint32_t mask = 0u - take;
+#pragma unroll
+        for (int j = 0; j <= WE; ++j) rem[j] = (t[j] & mask) | (rem[j] & ~mask);
+        num[0] |= take;
+    }
+}
 
 template <class P>
 inline SolveRecords<P> solve_records(const pmsolve::Plan &plan) {
@@ -96,6 +207,27 @@ inline SolveRecords<P> solve_records(const pmsolve::Plan &plan) {
             rec.block_idx.insert(rec.block_idx.end(), blk.rows.begin(), blk.rows.end());
             rec.block_idx.insert(rec.block_idx.end(), blk.cols.begin(), blk.cols.end());
             rec.blocks.push_back(SolveBlockDev{k, rows_off, rows_off + k, 0, rec.mat_off[blk.mat]});
+        }
+        if (s.kind == pmsolve::KIND_LONGDIV) {
+            const pmsolve::Hint &h = plan.hints[s.cols_off];
+            const bool literal = (h.flags & pmsolve::HINT_DIVISOR_LITERAL) != 0;
+            d.bits = (uint32_t)rec.hints.size();
+            rec.hints.push_back(SolveHintDev{h.n, (uint32_t)h.q.size(), (uint32_t)h.rem.size(), (uint32_t)h.D.size(),
+                                             (uint32_t)(literal ? h.lit.size() / 4 : h.E.size()), literal ? 1u : 0u, (uint32_t)rec.hint_idx.size(), 0});
+            for (const std::vector<uint32_t> *cols : {&h.q, &h.rem, &h.D, &h.E}) rec.hint_idx.insert(rec.hint_idx.end(), cols->begin(), cols->end());
+            if (literal) {   // the divisor is a constant of the key: accumulated once, here
+                uint32_t E[LONGDIV_WE] = {0}, lost = 0;
+                for (size_t j = 0; j < h.lit.size() / 4; ++j) {
+                    uint32_t v[8];
+                    for (int i = 0; i < 4; ++i) {
+                        v[2 * i] = (uint32_t)h.lit[4 * j + i];
+                        v[2 * i + 1] = (uint32_t)(h.lit[4 * j + i] >> 32);
+                    }
+                    lost |= add_shifted<LONGDIV_WE>(E, v, h.n * (uint32_t)j);
+                }
+                rec.hint_idx.insert(rec.hint_idx.end(), E, E + LONGDIV_WE);
+                rec.hint_idx.push_back(lost);
+            }
         }
         if (s.kind != pmsolve::KIND_ISZERO) continue;
         d.bits = (uint32_t)rec.pairs.size();
@@ -128,7 +260,7 @@ PM_HD uint32_t matrix_kind(uint32_t kind) { return kind >= pmsolve::KIND_BITS_C 
 template <class P>
 PM_HD void solve_inverse(const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsolve::Csr &Cm, SolveStepDev<P> *steps, uint64_t count, SolvePairDev<P> *pairs,
                          const SolveDivDev *divs, uint64_t t) {
-    if (t < count && (steps[t].kind == pmsolve::KIND_INDICATOR || steps[t].kind == pmsolve::KIND_BLOCK)) return;   // no inverse of a coefficient: the record stays as the host wrote it
+    if (t < count && (steps[t].kind == pmsolve::KIND_INDICATOR || steps[t].kind == pmsolve::KIND_BLOCK || steps[t].kind == pmsolve::KIND_LONGDIV)) return;   // no inverse of a coefficient: the record stays as the host wrote it
     if (t < count && steps[t].kind == pmsolve::KIND_SQRT) {
         const Fp<P> ka = *(const Fp<P> *)(A.val + 4 * steps[t].pos), kb = *(const Fp<P> *)(B.val + 4 * (B.rowptr[steps[t].row] + steps[t].bits));
         const Fp<P> coef = mul<P>(ka, kb);
@@ -398,6 +530,53 @@ PM_HD void solve_block(const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsol
     Fp<P> rhs[pmsolve::MAX_BLOCK];
     for (uint32_t i = 0; i < blk.k; ++i) rhs[i] = solve_block_rhs<P>(A, B, Cm, block_idx[blk.rows_off + i], z);
     for (uint32_t j = 0; j < blk.k; ++j) z[block_idx[blk.cols_off + j]] = solve_block_out<P>(block_inv + blk.inv_off, blk.k, j, rhs);
+}
+
+// one declared long division on one assignment: every input limb from Montgomery form to its canonical integer, accumulated at bit
+// offset n j (limbs need not be normalised: they overlap and carry), D = the dividend's sum, E = the divisor's (or the literal that
+// solve_records accumulated); D is formed 1024 - rounds bits higher, where longdiv wants it (`rounds`: the launch's trip count, at
+// least n (kD - 1) + 256 or 1024, so what add_shifted loses above the register is exactly D >= 2^1024); then longdiv, and the kq n-bit limbs of floor(D / E) and the kr n-bit limbs of D mod E go back to
+// Montgomery form and into their columns.  Stuck at the hint's word (nr + h: the step's row), with zero in every output:
+//   E = 0;  D >= 2^1024;  E >= 2^512;  q >= 2^(n kq);  rem >= 2^(n kr)
+// The conditions are or-ed into one word and the outputs stored under its mask: no branch on an operand but the sink's.
+template <class P, class Sink>
+PM_HD void solve_longdiv(const SolveStepDev<P> &s, const SolveHintDev &h, const uint32_t *__restrict__ hint_idx, uint32_t rounds, Fp<P> *z, const Sink &stuck) {
+    static_assert(P::N == 8, "four 64-bit words");
+    const uint32_t *q_cols = hint_idx + h.off, *r_cols = q_cols + h.kq, *d_cols = r_cols + h.kr, *e_words = d_cols + h.kD;
+    uint32_t D[LONGDIV_WD], E[LONGDIV_WE], R[LONGDIV_WE + 1], bad = 0;
+#pragma unroll
+    for (int w = 0; w < LONGDIV_WD; ++w) D[w] = 0;
+#pragma unroll
+    for (int w = 0; w < LONGDIV_WE; ++w) E[w] = 0;
+    const uint32_t base = 32u * LONGDIV_WD - rounds;
+    for (uint32_t j = 0; j < h.kD; ++j) bad |= add_shifted<LONGDIV_WD>(D, from_mont<P>(z[d_cols[j]]).l, base + h.n * j);
+    if (h.literal) {
+#pragma unroll
+        for (int w = 0; w < LONGDIV_WE; ++w) E[w] = e_words[w];
+        bad |= e_words[LONGDIV_WE];
+    } else {
+        for (uint32_t j = 0; j < h.kE; ++j) bad |= add_shifted<LONGDIV_WE>(E, from_mont<P>(z[e_words[j]]).l, h.n * j);
+    }
+    uint32_t any = 0;
+#pragma unroll
+    for (int w = 0; w < LONGDIV_WE; ++w) any |= E[w];
+    bad |= (uint32_t)(any == 0);
+    longdiv<LONGDIV_WD, LONGDIV_WE>(D, E, R, rounds);
+    bad |= bits_from<LONGDIV_WD>(D, h.n * h.kq) | bits_from<LONGDIV_WE + 1>(R, h.n * h.kr);
+    if (bad) stuck(s);
+    const uint32_t mask = bad ? 0u : ~0u;
+    for (uint32_t i = 0; i < h.kq; ++i) {
+        Fp<P> limb = limb_at<P, LONGDIV_WD>(D, h.n * i, h.n);
+#pragma unroll
+        for (int w = 0; w < P::N; ++w) limb.l[w] &= mask;
+        z[q_cols[i]] = to_mont<P>(limb);
+    }
+    for (uint32_t i = 0; i < h.kr; ++i) {
+        Fp<P> limb = limb_at<P, LONGDIV_WE + 1>(R, h.n * i, h.n);
+#pragma unroll
+        for (int w = 0; w < P::N; ++w) limb.l[w] &= mask;
+        z[r_cols[i]] = to_mont<P>(limb);
+    }
 }
 
 // One step of a chain, whatever its kind.  A range with an is-zero pair or a division row is a dividing one (the plan says so): the

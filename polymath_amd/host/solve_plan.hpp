@@ -145,6 +145,28 @@
 //                 Not handled: an unknown in A_r or B_r (the matrix would depend on the assignment), rows over different sets
 //                 (banded or triangular systems), k > 64, boolean- or pair-pending columns in S, choosing an independent subset when
 //                 the first k rows are dependent, sharded keys, per-assignment patterns.
+//   declared hint a LONG DIVISION that the key declares (pm_pk_set_hints; decode_hints below), not a row shape: kq quotient columns, kr
+//                 remainder columns, kD dividend columns and kE divisor columns (or kE literal limbs), limbs of n bits.  Every such
+//                 gadget -- circom-bigint's BigMod / BigMultModP (div[i] <-- long_div(..)), ark-r1cs-std's non-native reduce --
+//                 witnesses q and rem as multi-word integers that no row determines: the limb equations are underdetermined and
+//                 uniqueness comes from the range checks, so there is no shape to recognise.  A hint is ACTIVE in a call when all its
+//                 outputs carry the plain unknown marker (byte 1), INERT when all are given (the caller supplied q and rem: nothing
+//                 changes), and refused when some are marked and some given or one carries byte 2, 3 or 4.  With an active hint the
+//                 system goes to the scheduler only.  An output column of an active hint is HINT-OWNED: no row solves it, and a row
+//                 that names one while it is unknown waits (it is a check row, or an ordinary row over its other unknown, once the
+//                 hint has acted).  A hint waits on its unknown input columns like a row and acts when none is left: ONE step of kind
+//                 KIND_LONGDIV at 1 + max level of its inputs; all kq + kr outputs get that level and wake their waiters.  With
+//                 D = sum_j int(z_{D_j}) 2^(n j) and E = sum_j int(z_{E_j}) 2^(n j) (int: the canonical integer; limbs need not be
+//                 normalised -- the overflowing limbs of a no-carry product are the intended dividend) the step stores the kq n-bit
+//                 limbs of floor(D / E) and the kr n-bit limbs of D mod E.  Stuck, with zero in every output: E = 0, D >= 2^1024,
+//                 E >= 2^512, q >= 2^(n kq), rem >= 2^(n kr).  Step::row is nr + h for hint h of the declaration -- a value no row
+//                 has, and the stuck word of the step; Step::col is its first quotient column, Step::cols_off its entry of
+//                 Plan::hints.  Hint steps sort last within a level, after the blocks, and are a launch of their own
+//                 (Launch::longdiv, not dividing) whatever the level's width; Launch::rounds is the division's trip count for the launch, the
+//                 largest min(1024, n (kD - 1) + 256) of its hints.  A hint that never becomes ready is refused as
+//                 "hint h: input column c is never determined", followed by the scheduler's text for the first column that stays unknown.
+//                 Not handled: other opcodes (modular inverse, gcd, sorting), signed limbs, dividends beyond 1024 bits (RSA-2048),
+//                 hints on sharded keys, per-assignment declarations, inferring a hint from rows.
 // With the heap empty the scheduler has failed if an opener is unclosed, a boolean-pending column unsolved or a marked column
 // undetermined; the result is then build_plan's error (code, row, column, message) with "; in any row order: ..." appended.  A plan
 // it finds has Plan::reordered = true, level(step) as below, the steps sorted by (level, kind, row) and the level_ptr and launches of
@@ -158,7 +180,7 @@
 //
 // level(step) = 1 + max level of the columns the row reads (given columns: level 0); a decomposition gives all its columns that
 // level.  The steps come out sorted by level, inside a level by kind (C first: the kinds that divide share a launch; then the
-// decompositions in the same order, then the is-zero pairs, then the division rows, then the indicator rows, then the square-root rows, then the linear blocks), stable by row -- one counting sort.  O(nnz + columns), plus k log k per decomposition.
+// decompositions in the same order, then the is-zero pairs, then the division rows, then the indicator rows, then the square-root rows, then the linear blocks, then the declared hints), stable by row -- one counting sort.  O(nnz + columns), plus k log k per decomposition.
 #pragma once
 #include <stdint.h>
 
@@ -177,10 +199,12 @@ namespace pmsolve {
 // KIND_INDICATOR: an indicator row, z_u = [K z == 0]: no division and no inverse
 // KIND_SQRT: a square-root row, z_u = the smaller root of (C z)_r / (ka kb); its inverse is 1 / (ka kb), so it counts as dividing
 // KIND_BLOCK: a linear block, z_S = M^-1 rhs over k rows and k columns; the inverse is plan data, so it does not count as dividing
-enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6, KIND_DIVREM = 7, KIND_INDICATOR = 8, KIND_SQRT = 9, KIND_BLOCK = 10 };
+// KIND_LONGDIV: a declared long-division hint, kq + kr columns in one step; integer arithmetic only, so it does not count as dividing
+enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6, KIND_DIVREM = 7, KIND_INDICATOR = 8, KIND_SQRT = 9, KIND_BLOCK = 10, KIND_LONGDIV = 11 };
 constexpr uint32_t NUM_KINDS = 7;        // the kinds that need no second marker: what it always counted
 constexpr uint32_t NUM_STEP_KINDS = 8;   // KIND_C .. KIND_DIVREM, the kinds whose value comes from field or integer arithmetic on the row: what it counted when kind 7 came
-constexpr uint32_t NUM_SORT_KINDS = 10 + 1;  // all 11 of them: the ten kinds that one lane executes, KIND_INDICATOR and KIND_SQRT included, and KIND_BLOCK; the key width of finish_plan's counting sort
+constexpr uint32_t NUM_SORT_KINDS = 10 + 1;  // all 11 of them: the ten kinds that one lane executes, KIND_INDICATOR and KIND_SQRT included, and KIND_BLOCK: the kinds that rows make
+constexpr uint32_t NUM_PLAN_KINDS = 12;  // with KIND_LONGDIV, which no row makes: the key width of finish_plan's counting sort (NUM_SORT_KINDS counts the kinds that rows make, as it did)
 constexpr uint32_t MAX_BLOCK = 64;       // the largest linear block: one wave, a lane per row and per column
 
 constexpr uint8_t PATTERN_UNKNOWN = 1, PATTERN_QUOTIENT = 2, PATTERN_INDICATOR = 3, PATTERN_SQRT = 4;   // the pattern bytes (0: given)
@@ -228,6 +252,17 @@ struct BlockMat {     // a distinct block matrix
     std::vector<uint64_t> words;        // k x k coefficients of 4 words, row-major: M[i][j] = the coefficient of cols[j] in C_{rows[i]}
 };
 
+// A declared hint (pm_pk_set_hints): limb-wise long division.  Columns are CSR columns (0: the constant one, then the instance, then
+// the witness).  `lit`: with HINT_DIVISOR_LITERAL the divisor's kE limbs as canonical integers of four words each, and E is empty.
+constexpr uint64_t HINT_LONGDIV = 1, HINT_DIVISOR_LITERAL = 1;
+constexpr uint32_t HINT_MAX_N = 128, HINT_MAX_KD = 32, HINT_MAX_KE = 16, HINT_MAX_KQ = 32, HINT_MAX_KR = 16, HINT_D_BITS = 1024, HINT_E_BITS = 512;
+struct Hint {
+    uint32_t n = 0, flags = 0;
+    std::vector<uint32_t> q, rem, D, E;
+    std::vector<uint64_t> lit;
+    uint32_t index = 0;                 // its place in the declaration: the stuck word is nr + index
+};
+
 struct Launch {
     uint32_t lo, hi;  // steps [lo, hi) of the sorted list
     uint8_t chain;    // 1: one lane per assignment walks the steps in order; 0: one lane per (step, assignment), all of one level
@@ -238,9 +273,12 @@ struct Launch {
     uint8_t indicator = 0;  // chain == 0 only.  1: every step of the range is an indicator row; 0: none is
     uint8_t sqrt = 0;       // chain == 0 only.  1: every step of the range is a square-root row; 0: none is
     uint8_t block = 0;      // chain == 0 only.  1: every step of the range is a linear block (one wave each); 0: none is.  Never divides
+    uint8_t longdiv = 0;    // chain == 0 only.  1: every step of the range is a declared long division; 0: none is.  Never divides
+    uint32_t rounds = 0;    // longdiv only: the division's trip count, the largest min(1024, n (kD - 1) + 256) of the range's hints -- a
+                            // dividend of kD limbs below 2^256 at bit offsets n j is below 2 to that power
 };
 
-enum Error : int { OK = 0, ERR_MANY_UNKNOWNS = 1, ERR_TWO_MATRICES = 2, ERR_UNDETERMINED = 3, ERR_COLUMN_ZERO = 4 };
+enum Error : int { OK = 0, ERR_MANY_UNKNOWNS = 1, ERR_TWO_MATRICES = 2, ERR_UNDETERMINED = 3, ERR_COLUMN_ZERO = 4, ERR_HINT = 5 };
 
 struct Plan {
     std::vector<Step> steps;          // sorted by (level, kind, row)
@@ -251,6 +289,7 @@ struct Plan {
     std::vector<DivRow> divs;         // the division rows' remainders, in order of discovery
     std::vector<BlockRows> blocks;    // the linear blocks, in order of discovery
     std::vector<BlockMat> block_mats; // their distinct matrices, in order of discovery
+    std::vector<Hint> hints;          // the declared hints that acted, in order of discovery
     int error = OK;
     uint64_t error_row = 0, error_col = 0;
     std::string message;              // empty when error == OK
@@ -436,7 +475,7 @@ inline bool sqrt_row(const std::vector<Unknown> &occ, const uint32_t nz[3], cons
 // The tail both builders share: p.steps (in ROW order, levels set) sorted by (level, kind), stable by row; level_ptr; the launch schedule.
 inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
     // counting sort by (level, kind); the row order inside a key is the order the steps come in
-    constexpr size_t K = NUM_SORT_KINDS;
+    constexpr size_t K = NUM_PLAN_KINDS;
     std::vector<uint32_t> start((size_t)max_level * K + 1, 0);
     for (const Step &s : p.steps) ++start[(size_t)(s.level - 1) * K + s.kind + 1];
     for (size_t i = 1; i < start.size(); ++i) start[i] += start[i - 1];
@@ -452,11 +491,12 @@ inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
     // their dividing kinds begin, where the is-zero pairs begin, where the division rows begin and where the indicator rows begin (which
     // do not divide: a chain of C-steps and indicators is a non-dividing one), and where the square-root rows begin (which count as
     // dividing); consecutive narrow levels are one chain.  The linear blocks of a level come last and are a launch of their own
-    // whatever the level's width (a wave per block, not a lane): a chain run ends before them and a new one begins after them
+    // whatever the level's width (a wave per block, not a lane): a chain run ends before them and a new one begins after them.  So are
+    // the declared hints of a level, after its blocks
     for (uint32_t l = 0; l < max_level; ++l) {
         const uint32_t *at = start.data() + (size_t)l * K;
         const uint32_t lo = at[KIND_C], ab = at[KIND_A], bits = at[KIND_BITS_C], bits_ab = at[KIND_BITS_A], pairs = at[KIND_ISZERO], divs = at[KIND_DIVREM],
-                       inds = at[KIND_INDICATOR], roots = at[KIND_SQRT], hi = at[KIND_BLOCK], end = at[K];
+                       inds = at[KIND_INDICATOR], roots = at[KIND_SQRT], hi = at[KIND_BLOCK], end = at[KIND_LONGDIV], hints_end = at[K];
         const uint8_t divides = (uint8_t)(bits > ab || inds > bits_ab || hi > roots);
         if (hi == lo) {
             // a level of blocks only
@@ -479,6 +519,16 @@ inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
             Launch blocks{hi, end, 0, 0};
             blocks.block = 1;
             p.launches.push_back(blocks);
+        }
+        if (hints_end > end) {   // the declared hints of the level, after its blocks: a launch of their own as well
+            Launch hints{end, hints_end, 0, 0};
+            hints.longdiv = 1;
+            for (uint32_t t = end; t < hints_end; ++t) {
+                const Hint &h = p.hints[p.steps[t].cols_off];
+                const uint32_t bits = h.n * ((uint32_t)h.D.size() - 1) + 256;
+                hints.rounds = std::max(hints.rounds, std::min(bits, HINT_D_BITS));
+            }
+            p.launches.push_back(hints);
         }
     }
 }
@@ -650,6 +700,23 @@ struct Planner {
         for (uint32_t col : cols) solved(col, lv);
         for (uint32_t col : cols) known(col);
     }
+    // a declared hint whose inputs are all known: one step at 1 + max level of its inputs (`nr`: the system's rows)
+    template <class Known>
+    void hint_step(const Hint &h, uint64_t nr, const Known &known) {
+        uint32_t lv = 0;
+        for (const std::vector<uint32_t> *in : {&h.D, &h.E})
+            for (uint32_t col : *in) lv = level[col] > lv ? level[col] : lv;
+        ++lv;
+        Step s{0, (uint32_t)(nr + h.index), h.q[0], KIND_LONGDIV, lv};
+        s.cols_off = (uint32_t)p.hints.size();
+        p.hints.push_back(h);
+        p.steps.push_back(s);
+        for (const std::vector<uint32_t> *out : {&h.q, &h.rem})
+            for (uint32_t col : *out) solved(col, lv);
+        for (const std::vector<uint32_t> *out : {&h.q, &h.rem})
+            for (uint32_t col : *out) known(col);
+    }
+    std::vector<uint8_t> owned;       // per column, with an active hint only: 1 = hint-owned (an output of an active hint)
     std::map<std::vector<uint64_t>, uint32_t> mat_of;   // a block matrix' words (k follows from their number) -> its index in Plan::block_mats
     // a row is refused where it stands: the steps of the rows before it stay in the plan, as they always did
     void refuse_row(int code, uint64_t row, uint64_t col, const std::string &message) {
@@ -667,6 +734,7 @@ struct Planner {
         p.divs.clear();
         p.blocks.clear();
         p.block_mats.clear();
+        p.hints.clear();
     }
 };
 
@@ -811,7 +879,9 @@ inline Plan build_plan(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, co
 // rows to examine (at first every row); a row that cannot act yet is parked on its unknown columns and returns to the heap when one of
 // them becomes known, becomes boolean-pending or is released by its opener.  -> false and `why` where no order solves the system.
 // st.p.steps come out in order of discovery, with their levels; st.max_level is set.
-inline bool schedule_any_order(Planner &st, uint64_t nr, uint64_t ncols, std::string &why) {
+// `active`: the declared hints that are active in this call (build_plan_any_order), or nullptr.  Their outputs are hint-owned
+// (Planner::owned), each waits on its unknown input columns and acts from the `ready` queue, before the next row is examined.
+inline bool schedule_any_order(Planner &st, uint64_t nr, uint64_t ncols, std::string &why, const std::vector<Hint> *active = nullptr) {
     constexpr uint32_t UNSOLVED = Planner::UNSOLVED, NONE = Planner::NONE;
     enum : uint8_t { PARKED = 0, QUEUED = 1, DONE = 2 };
     const Csr *m = st.m;
@@ -833,9 +903,32 @@ inline bool schedule_any_order(Planner &st, uint64_t nr, uint64_t ncols, std::st
         state[r] = QUEUED;
         heap.push(r);
     };
+    // the hints: how many unknown input columns each still waits on, and per column the hints that wait on it
+    const size_t n_hints = active ? active->size() : 0;
+    std::vector<uint32_t> hint_waits(n_hints, 0), ready;
+    std::map<uint32_t, std::vector<uint32_t>> hint_waiters;
+    for (size_t h = 0; h < n_hints; ++h) {
+        std::vector<uint32_t> inputs((*active)[h].D);
+        inputs.insert(inputs.end(), (*active)[h].E.begin(), (*active)[h].E.end());
+        std::sort(inputs.begin(), inputs.end());
+        inputs.erase(std::unique(inputs.begin(), inputs.end()), inputs.end());
+        for (uint32_t col : inputs)
+            if (st.level[col] == UNSOLVED) {
+                ++hint_waits[h];
+                hint_waiters[col].push_back((uint32_t)h);
+            }
+        if (!hint_waits[h]) ready.push_back((uint32_t)h);
+    }
     const auto wake = [&](uint32_t col) {
         for (uint32_t i = park_head[col]; i != NONE; i = parked[i].second) push(parked[i].first);
         park_head[col] = NONE;
+        if (n_hints && st.level[col] != UNSOLVED) {   // known, not merely boolean-pending or released: the hints that read it
+            const auto at = hint_waiters.find(col);
+            if (at == hint_waiters.end()) return;
+            for (uint32_t h : at->second)
+                if (--hint_waits[h] == 0) ready.push_back(h);
+            hint_waiters.erase(at);
+        }
     };
     const auto park = [&](uint32_t r) {
         state[r] = PARKED;
@@ -855,12 +948,26 @@ inline bool schedule_any_order(Planner &st, uint64_t nr, uint64_t ncols, std::st
         wake(col_m);
         wake(col_b);
     };
-    while (!heap.empty()) {
+    while (!heap.empty() || !ready.empty()) {
+        if (!ready.empty()) {        // a hint whose inputs are all known acts: its outputs wake their waiters
+            const uint32_t h = ready.back();
+            ready.pop_back();
+            st.hint_step((*active)[h], nr, wake);
+            continue;
+        }
         const uint32_t r = heap.top();
         heap.pop();
         st.read_row(r, true);
         state[r] = DONE;
         if (occ.empty()) continue;   // a check row
+        if (n_hints) {               // no row solves a hint-owned column: the row waits for the hint
+            bool waits = false;
+            for (const Unknown &e : occ) waits = waits || st.owned[e.col];
+            if (waits) {
+                park(r);
+                continue;
+            }
+        }
         const uint32_t u = occ[0].col;
         bool one_column = true;
         for (const Unknown &e : occ) one_column = one_column && e.col == u;
@@ -953,9 +1060,15 @@ inline bool schedule_any_order(Planner &st, uint64_t nr, uint64_t ncols, std::st
         }
         park(r);
     }
+    std::string unready;             // the first hint that never became ready, and its first input column (dividend, then divisor) that stays unknown
+    for (size_t h = 0; h < n_hints && unready.empty(); ++h)
+        for (const std::vector<uint32_t> *in : {&(*active)[h].D, &(*active)[h].E})
+            for (uint32_t col : *in)
+                if (unready.empty() && hint_waits[h] && st.level[col] == UNSOLVED)
+                    unready = "hint " + std::to_string((*active)[h].index) + ": input column " + std::to_string(col) + " is never determined; ";
     for (uint64_t j = 0; j < ncols; ++j)
         if (st.level[j] == UNSOLVED) {
-            why = "column " + std::to_string(j) + " stays unknown";
+            why = unready + "column " + std::to_string(j) + " stays unknown";
             if (st.pair_of[j] != NONE) why += " (the pair that row " + std::to_string(st.openers[st.pair_of[j]].row) + " opens is never closed)";
             else if (st.bool_row[j] != NONE) why += " (boolean by row " + std::to_string(st.bool_row[j]) + ", and nothing determines it)";
             for (const auto &wide : set_of) {   // a set of linear rows too wide for a block, whose rows are linear rows over it to the end
@@ -973,6 +1086,74 @@ inline bool schedule_any_order(Planner &st, uint64_t nr, uint64_t ncols, std::st
     return st.open == 0;
 }
 
+// The declaration of pm_pk_set_hints: `desc` is a sequence of records
+//   HINT_LONGDIV, n, kq, kr, kD, kE, flags, kq quotient columns, kr remainder columns, kD dividend columns, then kE divisor columns
+//   -- or, with HINT_DIVISOR_LITERAL (flags bit 0), kE limb values of four words each (canonical integers below r)
+// -> the hints in `out` and an empty string, or what is refused, "hint h: " + the condition, and `out` empty.  `modulus`: r, four words.
+inline std::string decode_hints(const uint64_t *desc, size_t n_words, uint64_t ncols, const uint64_t *modulus, std::vector<Hint> &out) {
+    out.clear();
+    std::map<uint64_t, uint32_t> output_of;   // an output column -> the hint that names it
+    size_t at = 0;
+    std::string why;
+    while (at < n_words && why.empty()) {
+        const std::string here = "hint " + std::to_string(out.size()) + ": ";
+        Hint h;
+        h.index = (uint32_t)out.size();
+        if (desc[at] != HINT_LONGDIV) { why = here + "unknown opcode " + std::to_string(desc[at]); break; }
+        if (n_words - at < 7) { why = here + "the record is truncated"; break; }
+        const uint64_t n = desc[at + 1], kq = desc[at + 2], kr = desc[at + 3], kD = desc[at + 4], kE = desc[at + 5], flags = desc[at + 6];
+        if (n < 1 || n > HINT_MAX_N) { why = here + "n = " + std::to_string(n) + " is outside 1..128"; break; }
+        if (kq < 1 || kq > HINT_MAX_KQ) { why = here + "kq = " + std::to_string(kq) + " is outside 1..32"; break; }
+        if (kr < 1 || kr > HINT_MAX_KR) { why = here + "kr = " + std::to_string(kr) + " is outside 1..16"; break; }
+        if (kD < 1 || kD > HINT_MAX_KD) { why = here + "kD = " + std::to_string(kD) + " is outside 1..32"; break; }
+        if (kE < 1 || kE > HINT_MAX_KE) { why = here + "kE = " + std::to_string(kE) + " is outside 1..16"; break; }
+        if (flags & ~HINT_DIVISOR_LITERAL) { why = here + "unknown flags " + std::to_string(flags); break; }
+        if (n * (kD - 1) >= HINT_D_BITS) { why = here + "n (kD - 1) = " + std::to_string(n * (kD - 1)) + " is 1024 or more"; break; }
+        if (n * (kE - 1) >= HINT_E_BITS) { why = here + "n (kE - 1) = " + std::to_string(n * (kE - 1)) + " is 512 or more"; break; }
+        const bool literal = (flags & HINT_DIVISOR_LITERAL) != 0;
+        const uint64_t need = 7 + kq + kr + kD + (literal ? 4 * kE : kE);
+        if (n_words - at < need) { why = here + "the record is truncated"; break; }
+        h.n = (uint32_t)n;
+        h.flags = (uint32_t)flags;
+        const uint64_t *w = desc + at + 7;
+        std::vector<uint32_t> *lists[4] = {&h.q, &h.rem, &h.D, &h.E};
+        const uint64_t counts[4] = {kq, kr, kD, literal ? 0 : kE};
+        for (int l = 0; l < 4 && why.empty(); ++l)
+            for (uint64_t i = 0; i < counts[l] && why.empty(); ++i, ++w) {
+                if (*w >= ncols) why = here + "column " + std::to_string(*w) + " is not below m0 + mw = " + std::to_string(ncols);
+                else lists[l]->push_back((uint32_t)*w);
+            }
+        if (!why.empty()) break;
+        if (literal) {
+            for (uint64_t i = 0; i < kE && why.empty(); ++i, w += 4)
+                if (!words_less(w, modulus)) why = here + "literal limb " + std::to_string(i) + " is not below r";
+                else h.lit.insert(h.lit.end(), w, w + 4);
+            if (!why.empty()) break;
+        }
+        for (const std::vector<uint32_t> *outs : {&h.q, &h.rem})
+            for (uint32_t col : *outs) {
+                if (!why.empty()) break;
+                if (col == 0) { why = here + "an output is column 0 (the constant one)"; break; }
+                const auto named = output_of.find(col);
+                if (named != output_of.end()) {
+                    why = here + "output column " + std::to_string(col) + (named->second == h.index ? " is named twice" : " is an output of hint " + std::to_string(named->second) + " as well");
+                    break;
+                }
+                output_of.emplace(col, h.index);
+            }
+        for (const std::vector<uint32_t> *in : {&h.D, &h.E})
+            for (uint32_t col : *in) {
+                const auto named = output_of.find(col);
+                if (why.empty() && named != output_of.end() && named->second == h.index) why = here + "output column " + std::to_string(col) + " is an input of the hint as well";
+            }
+        if (!why.empty()) break;
+        at += need;
+        out.push_back(std::move(h));
+    }
+    if (!why.empty()) out.clear();
+    return why;
+}
+
 // build_plan for rows in ANY order.  The matrix order is tried first: a system that build_plan accepts gets build_plan's plan,
 // field for field, with reordered = false (and without the modulus, or with column 0 marked, there is nothing else).  Otherwise the
 // scheduler above looks for a dependency order; if it finds one the plan has reordered = true, the same levels per column that the
@@ -980,7 +1161,49 @@ inline bool schedule_any_order(Planner &st, uint64_t nr, uint64_t ncols, std::st
 // finds none the result is build_plan's error -- code, row, column, message -- with what stays unknown appended to the message.
 // O(nnz log rows): a row is examined once, and once more per event on one of its unknown columns.
 inline Plan build_plan_any_order(const Csr m[3], uint64_t nr, uint64_t m0, uint64_t mw, const uint8_t *unknown, uint32_t wide_steps = WIDE_STEPS,
-                                 const uint64_t *modulus = nullptr) {
+                                 const uint64_t *modulus = nullptr, const std::vector<Hint> *hints = nullptr) {
+    // the key's declared hints (decode_hints): active where every output carries the plain marker, inert where every output is given.
+    // Without an active one everything below is what it was
+    std::vector<Hint> active;
+    const uint64_t ncols = m0 + mw;
+    for (size_t h = 0; hints && modulus && h < hints->size() && !(ncols && unknown[0]); ++h) {
+        size_t marked = 0, given = 0, special = 0;
+        for (const std::vector<uint32_t> *outs : {&(*hints)[h].q, &(*hints)[h].rem})
+            for (uint32_t col : *outs) (unknown[col] == PATTERN_UNKNOWN ? marked : unknown[col] ? special : given) += 1;
+        if (special || (marked && given)) {
+            Plan p;
+            p.error = ERR_HINT;
+            p.message = "hint " + std::to_string((*hints)[h].index) + ": " +
+                        (special ? "an output carries the quotient, indicator or square-root marker" : "some outputs are marked unknown and some are given");
+            return p;
+        }
+        if (marked) active.push_back((*hints)[h]);
+    }
+    if (!active.empty()) {   // the scheduler only: no row order solves a hint-owned column
+        if (nr + hints->size() > 0xffffffffull) {
+            Plan p;
+            p.error = ERR_HINT;
+            p.message = "rows and hints together exceed 2^32 - 1";
+            return p;
+        }
+        Planner st(m, ncols, unknown, modulus);
+        st.owned.assign(ncols, 0);
+        for (const Hint &h : active)
+            for (const std::vector<uint32_t> *outs : {&h.q, &h.rem})
+                for (uint32_t col : *outs) st.owned[col] = 1;
+        std::string why;
+        if (!schedule_any_order(st, nr, ncols, why, &active)) {
+            uint64_t col = 0;
+            while (col < ncols && st.level[col] != Planner::UNSOLVED) ++col;
+            st.fail(ERR_UNDETERMINED, 0, col < ncols ? col : 0, why);
+            return std::move(st.p);
+        }
+        Plan &p = st.p;
+        std::sort(p.steps.begin(), p.steps.end(), [](const Step &a, const Step &b) { return a.row < b.row; });   // a hint's row is nr + its index
+        finish_plan(p, st.max_level, wide_steps);
+        p.reordered = true;
+        return std::move(p);
+    }
     Plan first = build_plan(m, nr, m0, mw, unknown, wide_steps, modulus);
     if (first.error == OK || first.error == ERR_COLUMN_ZERO || !modulus) return first;
     Planner st(m, m0 + mw, unknown, modulus);

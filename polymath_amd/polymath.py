@@ -606,6 +606,12 @@ class Polymath:
                     arr[j] = api.QUOTIENT_LIMBS if v is QUOTIENT else api.INDICATOR_LIMBS if v is INDICATOR else api.SQRT_LIMBS if v is SQRT else api.UNKNOWN_LIMBS
         return x, w
 
+    def set_hints(self, pk, hints):
+        """Declare the key's hints (pm_pk_set_hints): values that the circuit's witness generator computes and no row determines.
+        hints: a list of dicts {"n", "q", "rem", "D", and "E" or "literal"} or tuples (api.encode_hints), e.g. what a generator's
+        hints(m0) returns; an empty list clears the declaration.  A refusal raises with the library's message; the key is unchanged."""
+        self.ctx.check(pk.set_hints(hints))
+
     def solve_batch(self, pk, partials, device_ptrs=None):
         """Complete partial assignments on the device: a check call with max_rows = 0 plus pm_prove_tap(10).  partials[i]: an (x_limbs,
         w_limbs) pair (partial_limbs); device_ptrs = (d_x, d_w, mw): the rows are already in HBM and `partials` is their count.

@@ -96,6 +96,11 @@ pub const PM_PROVE_GLUE_DEVICE: i32 = 256;
 // pm_assignment_flags: the `assignment_on_device` argument of pm_host_prove[_batch] and pm_r1cs_check[_batch] is a flag word
 pub const PM_ASSIGNMENT_DEVICE: i32 = 1;
 pub const PM_ASSIGNMENT_SOLVE: i32 = 2;
+// pm_key_hints: the flag of pm_pk_load_bytes' `validate` under which `bytes` declares the witness solver's hints of the existing key *out;
+// pm_hint_op / pm_hint_flags: the one opcode of a declared hint and the flag that makes its divisor a literal
+pub const PM_KEY_HINTS: i32 = 1024;
+pub const PM_HINT_LONGDIV: u64 = 1;
+pub const PM_HINT_DIVISOR_LITERAL: u64 = 1;
 // the three markers of PM_ASSIGNMENT_SOLVE (little-endian words of one Fr, all >= r on both curves): unknown; unknown, and the Euclidean
 // quotient of its division row; unknown, and the indicator of its guard row
 pub const PM_UNKNOWN_WORDS: [u64; 4] = [u64::MAX, u64::MAX, u64::MAX, u64::MAX];

@@ -755,10 +755,16 @@ impl GpuKey {
             _ => return Err(err(Status::InvalidArg, "truncated key")),
         };
         let mut raw = core::ptr::null_mut();
-        // SAFETY: `bytes` outlives the call and is only read; the library keeps no pointer to it.
-        let rc = unsafe { sys::pm_pk_load_bytes(ctx.raw, curve.id(), bytes.as_ptr(), bytes.len(), validate as i32 | form as i32, 0, 1, sys::PM_SHARD_PAIRS, &mut raw) };
+        let rc = Self::load_bytes_raw(ctx, curve, bytes.as_ptr(), bytes.len(), validate as i32 | form as i32, &mut raw);
         ctx.check(rc)?;
         Ok(GpuKey { raw, curve, m0, mw })
+    }
+
+    // THE call of pm_pk_load_bytes, for an unsharded key: the loaders above (`raw` null on entry, the new key on success) and
+    // `set_hints` (`flags` = PM_KEY_HINTS, `raw` the existing key, which stays).  `bytes` may be null where `len` is 0.
+    fn load_bytes_raw(ctx: &mut Context, curve: Curve, bytes: *const u8, len: usize, flags: i32, raw: &mut *mut sys::pm_pk) -> i32 {
+        // SAFETY: the caller's `bytes` hold `len` bytes, outlive the call and are only read; the library keeps no pointer to them.
+        unsafe { sys::pm_pk_load_bytes(ctx.raw, curve.id(), bytes, len, flags, 0, 1, sys::PM_SHARD_PAIRS, raw) }
     }
 
     /// `pm_pk_load_sharded`: this rank's share of a key for ONE proof over `shard_count` GPUs (one process per GPU).  `layout`:
@@ -1017,6 +1023,19 @@ impl GpuKey {
         ctx.check(rc)?;
         rows.truncate((n_bad as usize).min(max_rows));
         Ok((n_bad, rows))
+    }
+
+    /// Declare the witness solver's hints of this key (`pm_pk_load_bytes` with `PM_KEY_HINTS`: no key is loaded, this one keeps its
+    /// address) -- `desc` is the sequence of records the header states (`PM_HINT_LONGDIV, n, kq, kr, kD, kE, flags`, then the columns
+    /// or literal limbs); an empty slice clears the declaration.  Taking `&mut self` keeps safe code from racing the call with calls
+    /// that use the key.
+    pub fn set_hints(&mut self, ctx: &mut Context, desc: &[u64]) -> Result<(), HipError> {
+        let ptr = if desc.is_empty() { core::ptr::null() } else { desc.as_ptr() as *const u8 };
+        let mut key = self.raw;
+        // `desc` holds `8 * desc.len()` bytes, which the library only reads and copies; under PM_KEY_HINTS `key` is read and left as it is
+        let rc = Self::load_bytes_raw(ctx, self.curve, ptr, 8 * desc.len(), sys::PM_KEY_HINTS, &mut key);
+        debug_assert!(key == self.raw);
+        ctx.check(rc)
     }
 
     /// `pm_pk_info`: n, m0, sigma, omega and the six base-vector lengths of this key.

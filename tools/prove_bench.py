@@ -30,7 +30,12 @@ bitlength(r) - 1 bits; route (b) marks the roots with the square-root marker), a
   python tools/prove_bench.py --circuit limbproduct --batch 256 --reps 5 --solve LimbProduct, 64 products of 8-limb numbers;
                                                                                  limbproduct:COUNT:LIMBS for others
 on one that multiplies non-native numbers (one dependency level of COUNT linear blocks of 2 LIMBS - 1 unknowns through one shared
-inverse, then the sums; no marker: the rows determine the product's limbs).
+inverse, then the sums; no marker: the rows determine the product's limbs), and
+  python tools/prove_bench.py --circuit modmul --batch 256 --reps 5 --solve      LimbModMul, 16 multiplications modulo a 256-bit prime on
+                                                                                 4 limbs of 64 bits; modmul:COUNT:N:LIMBS for others
+on one that multiplies in a foreign field (per multiplication a linear block, one declared long division -- the key's hints are set
+from the circuit's hints() -- 2 LIMBS decompositions of N bits, the limbs of q p and a chain of carries; route (a) synthesises q and
+rem with Python's divmod).  UNMEASURED: no run of it is recorded.
   python tools/prove_bench.py --circuit mimc322 --batch 256 --reps 5 --solve --reorder reverse     or --reorder SEED
 runs either --solve comparison on the same circuit with its constraint rows stored in another order (circuits.Reordered: reversed, or
 shuffled by SEED; a matchcount gadget moves as a block so that every opener stays before its closer).  Route (b) then goes through the
@@ -48,7 +53,7 @@ from polymath_amd import circuits as PC
 from polymath_amd.polymath import Polymath
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants), bench:NC (BenchCircuit, NC constraints), arx[:WIDTH:ROUNDS] (ArxDemo), matchcount[:N:FORM] (MatchCount), divrem[:N:BITS] (DivRem), tablewalk[:WIDTH:STEPS] (TableWalk), decompress[:POINTS] (EdwardsDecompress) or limbproduct[:COUNT:LIMBS] (LimbProduct)")
+ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants), bench:NC (BenchCircuit, NC constraints), arx[:WIDTH:ROUNDS] (ArxDemo), matchcount[:N:FORM] (MatchCount), divrem[:N:BITS] (DivRem), tablewalk[:WIDTH:STEPS] (TableWalk), decompress[:POINTS] (EdwardsDecompress), limbproduct[:COUNT:LIMBS] (LimbProduct) or modmul[:COUNT:N:LIMBS] (LimbModMul)")
 ap.add_argument("--batch", type=int, default=16)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--curve", default="bls12_381")
@@ -58,8 +63,8 @@ ap.add_argument("--glue", choices=("host", "device"), default="host", help="devi
 ap.add_argument("--solve", action="store_true", help="host-synthesised assignments against partial assignments solved on the GPU")
 ap.add_argument("--reorder", default=None, metavar="reverse|SEED", help="with --solve: the circuit's rows stored reversed or shuffled by SEED (unmeasured)")
 a = ap.parse_args()
-if a.solve and not a.circuit.startswith(("mimc", "arx", "matchcount", "divrem", "tablewalk", "decompress", "limbproduct")):
-    ap.error("--solve needs a mimcK, an arx, a matchcount, a divrem, a tablewalk, a decompress or a limbproduct circuit")
+if a.solve and not a.circuit.startswith(("mimc", "arx", "matchcount", "divrem", "tablewalk", "decompress", "limbproduct", "modmul")):
+    ap.error("--solve needs a mimcK, an arx, a matchcount, a divrem, a tablewalk, a decompress, a limbproduct or a modmul circuit")
 if a.reorder is not None and not a.solve:
     ap.error("--reorder goes with --solve")
 pm = Polymath(a.curve, a.transcript, device=0)
@@ -105,6 +110,12 @@ elif a.circuit.startswith("limbproduct"):
     make = lambda: PC.LimbProduct(PC.limb_products(r, n_products, n_limbs, g.next_u64()))
     again = lambda c: PC.LimbProduct(c.products, c.first)
     partial_of = lambda c: c.partial(r)
+elif a.circuit.startswith("modmul"):
+    n_muls, limb_bits, n_limbs = (int(v) for v in a.circuit.split(":")[1:4]) if ":" in a.circuit else (16, 64, 4)
+    foreign = (1 << (limb_bits * n_limbs)) - 2 ** 32 - 977 if limb_bits * n_limbs == 256 else (1 << (limb_bits * n_limbs - 3)) - 1     # secp256k1's prime at 256 bits, else a modulus of the limbs' size
+    make = lambda: PC.LimbModMul(PC.modmul_pairs(foreign, n_muls, g.next_u64()), foreign, limb_bits, n_limbs)
+    again = lambda c: PC.LimbModMul(c.pairs, c.modulus, c.n, c.limbs, c.decompose)
+    partial_of = lambda c: c.partial(r)
 else:
     nc = int(a.circuit.split(":", 1)[1])
     make = lambda: PC.BenchCircuit(g.fr(r), g.fr(r), 10, nc)
@@ -119,6 +130,8 @@ circuits = [make() for _ in range(distinct)]
 t0 = time.time()
 pk = pm.setup(stored(circuits[0]), g.fr(r), g.fr(r))
 setup_s = time.time() - t0
+if a.circuit.startswith("modmul"):
+    pm.set_hints(pk, circuits[0].hints(2))       # the long divisions are part of the circuit: declared once, with the key
 rows = []
 for c in circuits:
     _, inst, wit = pm._synthesize(stored(c))
