@@ -236,7 +236,7 @@ int pm_pk_export_bases(pm_ctx *ctx, const pm_pk *pk, int which, size_t offset, s
  * name and a C caller calls pm_pk_load_bytes as written above (the Python and Rust wrappers have a set_hints that does).  With
  * the flag no key is loaded and *out is not replaced: `bytes` is the declaration for the existing key *out.  PM_KEY_HINTS stands alone
  * in `validate`, `curve` is the key's and `len` a multiple of 8, else PM_ERR_INVALID_ARG.  `desc` is a sequence of records of n_words
- * 64-bit words (in memory order) in all; the one opcode is limb-wise long division:
+ * 64-bit words (in memory order) in all; the first opcode is limb-wise long division (the second, modular division, follows below):
  *     PM_HINT_LONGDIV, n, kq, kr, kD, kE, flags,
  *       kq quotient columns, kr remainder columns, kD dividend columns, then kE divisor columns
  *       -- or, with PM_HINT_DIVISOR_LITERAL (flags bit 0), kE limb values of four words each (canonical integers, little-endian)
@@ -248,11 +248,26 @@ int pm_pk_export_bases(pm_ctx *ctx, const pm_pk *pk, int which, size_t offset, s
  * its own hint; a literal limb >= r; a sharded key.  The refusals' text begins "pm_pk_set_hints: hint h: ".  A second call replaces
  * the declaration and n_words = 0 clears it; a context's solving plan is rebuilt after either.  The caller must not race the call with
  * calls that use the key, as with pm_pk_free.
- * Out of scope: other opcodes (modular inverse, gcd, sorting), signed limbs, dividends beyond 1024 bits (RSA-2048), hints on sharded
- * keys, per-assignment declarations, inferring a hint from rows. */
+ * Out of scope for the long-division record: other opcodes (modular inverse, gcd, sorting), signed limbs, dividends beyond 1024 bits (RSA-2048), hints on sharded
+ * keys, per-assignment declarations, inferring a hint from rows.  Of these, modular inverse and modular division have a record of
+ * their own in the same stream (opcode 3; opcode 2 stays reserved and is refused as unknown):
+ *     PM_HINT_MODDIV, n, kz, kNp, kNm, kDp, kDm, kP, flags,
+ *       kz output columns, kNp + kNm numerator columns, kDp + kDm denominator columns, then kP modulus columns
+ *       -- or, with PM_HINT_MODULUS_LITERAL (flags bit 0), kP limb values of four words each
+ * With each column list the sum of int(z_c_j) 2^(n j) (int: the canonical integer; limbs need not be normalised), N = N+ - N-,
+ * D = D+ - D- and P the modulus, the step stores the kz n-bit limbs of the unique Z in [0, P) with Z D = N (mod P): the slope
+ * (Y2 - Y1) / (X2 - X1) of an affine point addition, ark-r1cs-std's non-native inverse, circom-ecdsa's BigModInv.  kNp = kNm = 0
+ * means N = 1, a plain inverse.  P need not be prime.  Refused like the long-division record, with the same wording for columns,
+ * outputs, literal limbs and sharded keys: unknown flags; a truncated record; n outside 1..128; kz outside 1..16 or kP outside 1..16;
+ * kDp outside 1..32; kNp, kNm or kDm above 32; n (k - 1) >= 1024 for an operand list; n (kP - 1) >= 512.  Records of both opcodes
+ * may be mixed in one declaration; they share the index h, and no output may be named by two hints of either opcode.
+ * Still out of scope: even moduli, operands beyond 1024 bits, the slope of a doubling as one hint (its numerator is a product), gcd,
+ * sorting. */
 typedef enum pm_hint_op { PM_HINT_LONGDIV = 1 } pm_hint_op;
 typedef enum pm_hint_flags { PM_HINT_DIVISOR_LITERAL = 1 } pm_hint_flags;
 typedef enum pm_key_hints { PM_KEY_HINTS = 1024 } pm_key_hints;
+typedef enum pm_hint_op_modular { PM_HINT_MODDIV = 3 } pm_hint_op_modular;
+typedef enum pm_hint_moddiv_flags { PM_HINT_MODULUS_LITERAL = 1 } pm_hint_moddiv_flags;
 void pm_pk_free(pm_pk *pk);
 
 /* ---- proving keys as bytes: ProvingKey::serialize_compressed (data_structures.rs:56-73), decoded on the device ---------
@@ -539,8 +554,18 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  *   determined", followed by what stays unknown.  With an active hint every refusal of the structure is reported from the scheduler,
  *   as "column j stays unknown" with its reason: the row that the matrix-order pass would have named (a row with two or more
  *   unknowns, an unknown in two matrices) is not named then, because no matrix order is tried.  Without a declaration, or with every hint inert, plans, messages and words are what
- *   they are without this rule.  Not handled: other opcodes (modular inverse, gcd, sorting), signed limbs, dividends beyond 1024 bits
+ *   they are without this rule.  Not handled by a long division: other opcodes (modular inverse, gcd, sorting), signed limbs, dividends beyond 1024 bits
  *   (RSA-2048), hints on sharded keys, per-assignment declarations, inferring a hint from rows.
+ *   Declared hints: modular division.  Modular inverse and division have their own record, PM_HINT_MODDIV (pm_pk_set_hints above states
+ *   it): Z = (N+ - N-) (D+ - D-)^-1 mod P is a value that every gadget on non-native arithmetic contains -- the slope of an affine
+ *   point addition, a non-native inverse -- and that no row determines: the circuit only checks Z D = N (mod P) afterwards, through
+ *   the product and the long division above.  The ACTIVE / INERT / mixed-marker rule is the long-division one, applied to the kz
+ *   outputs; the hint waits for its input columns and is ONE step at 1 + the largest level of its inputs, after the long divisions of
+ *   that level.  The assignment is STUCK at the word nr + h, with zero in every output, where P is even or P < 3, P >= 2^512, any of
+ *   N+, N-, D+, D- is >= 2^1024, gcd(D mod P, P) != 1 (D = 0 mod P included: a missing inverse is detected, not assumed away), or
+ *   Z >= 2^(n kz); the root-cause rule applies to that word as to a long division's.  Without an active modular hint every plan,
+ *   message and word is what it is without this rule.  Not handled: even moduli, operands beyond 1024 bits, the slope of a doubling
+ *   as one hint, gcd, sorting.
  *   PM_ERR_INVALID_ARG, pm_last_error naming the row or column, nothing computed and no output written: an unsolvable row, a marked
  *   column that no row determines, a marker at column 0, a sharded key, and -- in a batch -- an assignment that does not mark the
  *   columns assignment 0 marks, or marks one with the other marker (any two of the four markers differ; the first differing (assignment, column) is named; a kernel

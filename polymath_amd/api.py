@@ -63,6 +63,9 @@ SQRT_LIMBS = (0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFF, 0xFFFF
 PM_KEY_HINTS = 1024
 HINT_LONGDIV, HINT_DIVISOR_LITERAL = 1, 1
 HINT_LIMITS = {"n": 128, "kq": 32, "kr": 16, "kD": 32, "kE": 16}
+# the second opcode, modular division Z = (N+ - N-) / (D+ - D-) mod P (2 is reserved), its one flag and the limits of its record
+HINT_MODDIV, HINT_MODULUS_LITERAL = 3, 1
+MODDIV_LIMITS = {"n": 128, "kz": 16, "kNp": 32, "kNm": 32, "kDp": 32, "kDm": 32, "kP": 16}
 NOT_STUCK = 0xFFFFFFFFFFFFFFFF                # first word of a tap-9 record of an assignment that completed
 TIMING_SLOTS = ["witness_map", "ntt", "poly", "msm_sort", "msm_accumulate", "msm_reduce", "msm_total", "phase"]
 
@@ -223,9 +226,29 @@ def _c(a):
 def encode_hints(hints):
     """The words of pm_pk_set_hints for a list of hints.  A hint is a dict {"n", "q", "rem", "D", and "E" (divisor columns) or "literal"
     (the divisor's limbs as Python integers)} or a tuple (n, q, rem, D, E) / (n, q, rem, D, None, literal); q, rem, D, E are lists of
-    CSR columns (0: the constant one, then the instance, then the witness).  -> np.uint64[n_words]"""
+    CSR columns (0: the constant one, then the instance, then the witness).  A modular division is a dict with "op": "moddiv":
+    {"op", "n", "z", "Dp", "P" (modulus columns) or "literal" (the modulus' limbs), and optionally "Np", "Nm", "Dm"}; without "Np" and
+    "Nm" the numerator is 1.  -> np.uint64[n_words]"""
     words = []
     for hint in hints:
+        if isinstance(hint, dict) and hint.get("op", "longdiv") != "longdiv":
+            if hint["op"] != "moddiv":
+                raise ValueError("unknown hint op %r" % (hint["op"],))
+            P, literal = hint.get("P"), hint.get("literal")
+            if (P is None) == (literal is None):
+                raise ValueError("a modular hint has modulus columns P or a literal modulus, not both and not neither")
+            lists = [list(hint["z"])] + [list(hint.get(key, ())) for key in ("Np", "Nm")] + [list(hint["Dp"]), list(hint.get("Dm", ()))]
+            modulus = list(P) if literal is None else list(literal)
+            words += [HINT_MODDIV, int(hint["n"])] + [len(v) for v in lists] + [len(modulus), 0 if literal is None else HINT_MODULUS_LITERAL]
+            words += [int(c) for v in lists for c in v]
+            if literal is None:
+                words += [int(c) for c in modulus]
+            else:
+                for limb in modulus:
+                    if not 0 <= int(limb) < 1 << 256:
+                        raise ValueError("a literal limb is four words")
+                    words += [(int(limb) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]
+            continue
         if isinstance(hint, dict):
             n, q, rem, D, E, literal = hint["n"], hint["q"], hint["rem"], hint["D"], hint.get("E"), hint.get("literal")
         else:
@@ -246,9 +269,25 @@ def encode_hints(hints):
 
 
 def decode_hints(words):
-    """encode_hints backwards: -> a list of dicts (the words are trusted to be well-formed: the library is what refuses)"""
+    """encode_hints backwards: -> a list of dicts (the words are trusted to be well-formed: the library is what refuses).  A modular
+    division comes back with "op": "moddiv" and all of "Np", "Nm", "Dp", "Dm" (empty lists where the record has none)"""
     words, out, at = [int(v) for v in words], [], 0
     while at < len(words):
+        if words[at] == HINT_MODDIV:
+            n, kz, kNp, kNm, kDp, kDm, kP, flags = words[at + 1:at + 9]
+            at += 9
+            hint = {"op": "moddiv", "n": n}
+            for key, k in (("z", kz), ("Np", kNp), ("Nm", kNm), ("Dp", kDp), ("Dm", kDm)):
+                hint[key] = words[at:at + k]
+                at += k
+            if flags & HINT_MODULUS_LITERAL:
+                hint["literal"] = [sum(words[at + 4 * i + j] << (64 * j) for j in range(4)) for i in range(kP)]
+                at += 4 * kP
+            else:
+                hint["P"] = words[at:at + kP]
+                at += kP
+            out.append(hint)
+            continue
         op, n, kq, kr, kD, kE, flags = words[at:at + 7]
         if op != HINT_LONGDIV:
             raise ValueError("unknown opcode %d" % op)

@@ -7,7 +7,9 @@ ModChain: Euclidean division rows, whose quotients partial() marks QUOTIENT), an
 TableWalk: circomlib's one-hot decoder, whose outputs partial() marks INDICATOR), and two that take square roots (SquareRoots,
 EdwardsDecompress: point decompression on Jubjub / Baby Jubjub, whose roots partial() marks SQRT), and three whose rows are square linear systems in their unknowns (LimbProduct, ProductChain: non-native
 multiplication, whose product limbs are pinned at 2l - 1 points; LinearBlocks: random systems), which the solver takes as linear blocks, and two that multiply modulo a foreign prime (LimbModMul, ModMulChain: the product's block, then the
-quotient and remainder limbs of the reduction, which no row determines: hints() is the long division the key declares for them); Reordered emits any of them with its rows in another
+quotient and remainder limbs of the reduction, which no row determines: hints() is the long division the key declares for them), and two that divide modulo a foreign modulus (LimbModDiv: a non-native
+modular division or inverse; EcAddChain: affine point additions, whose slopes are such divisions: hints() declares a modular hint for each
+and a long division for every reduction); Reordered emits any of them with its rows in another
 order, which the solver's any-order planner accepts."""
 from .polymath import INDICATOR, QUOTIENT, SQRT, ConstraintSystem, Field, LimbCircuit, R1CS, small_sqrt
 
@@ -951,6 +953,276 @@ def modmul_pairs(modulus, count, seed=SPLITMIX_SEED, bits=None):
     g = SplitMix64(seed)
     draw = lambda: sum(g.next_u64() << (64 * i) for i in range(-(-modulus.bit_length() // 64))) % (modulus if bits is None else 1 << bits)
     return [(draw(), draw()) for _ in range(count)]
+
+
+def subtraction_pad(modulus, n, limbs, operand_bits=None):
+    """THE PADDING CONSTANT of limb-wise subtraction modulo `modulus`: `limbs` limbs whose integer  sum pad_j 2^(n j)  is a multiple of
+    the modulus and each of which is at least 2^operand_bits - 1, so that  x_j - y_j + pad_j  is a non-negative integer for every
+    subtrahend limb y_j < 2^operand_bits and the sum is x - y modulo the modulus.  With operand_bits = n (the default) it is
+    pad_j = 2^n + e_j for e the n-bit limbs of  -(sum 2^n 2^(n j)) mod modulus : every limb in [2^n, 2^(n + 1)).  With narrower
+    operands (limbs so wide that a product of two full limbs would pass r) the pad must be narrow too, and there is no such multiple
+    in general; the modulus' own limbs serve where each is at least 2^operand_bits - 1, and anything else is refused."""
+    operand_bits = n if operand_bits is None else operand_bits
+    if operand_bits == n:
+        base = sum(1 << (n * (j + 1)) for j in range(limbs))
+        pad = [(1 << n) + e for e in int_limbs(-base % modulus, n, limbs)]
+    else:
+        pad = int_limbs(modulus, n, limbs)
+        assert all(v >= (1 << operand_bits) - 1 for v in pad), "no narrow pad: a limb of the modulus is below 2^operand_bits - 1"
+    assert limbs_int(pad, n) % modulus == 0 and all(v >= (1 << operand_bits) - 1 for v in pad)
+    return pad
+
+
+class _ValuesOnly:
+    """A ConstraintSystem's variables and values without its rows: what native() runs a generator on"""
+
+    def __init__(self, r):
+        self.r, self.instance, self.witness = r, [1], []
+
+    new_input_variable = ConstraintSystem.new_input_variable
+    new_witness_variable = ConstraintSystem.new_witness_variable
+
+    def enforce_constraint(self, a, b, c):
+        pass
+
+
+_LAYOUT_R = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001   # BN254's r, the smaller one: hints() lays a circuit out on it
+
+
+class _PartialModDiv(_Partial):
+    """What LimbModDiv and EcAddChain share: arithmetic modulo a foreign `modulus` on l limbs of n bits whose divisions are declared
+    hints.  A LIMB here is (lc, value, bound): a linear combination of variables, its value as a Python integer (never negative, never
+    reduced mod r) and an upper bound of that value over all inputs; the bounds prove that no limb can reach r (asserted), so that
+    int(column) is the integer the hints are specified on.
+      _quotient   Z = (N+ - N-) / (D+ - D-) mod p from a MODULAR hint: l witnesses, with `decompose` their bits
+      _product    the 2l - 1 limbs of a no-carry product, pinned at the points 1 .. 2l - 1: a linear block
+      _reduce     T mod p for limbs T from a LONG-DIVISION hint: a column per limb of T that is not one already (an ordinary row),
+                  the limbs of q and rem (hinted; with `decompose` their bits), the limbs of the no-carry product q p (ordinary rows:
+                  p is a literal), and the carries of  T_j - qp_j - rem_j + carry_{j-1} = carry_j 2^n  with the closing check row.
+                  With `zero` the remainder must be zero -- the division is exact: asserted on the values, and l check rows
+                  rem_j * 1 = 0  pin the hint-owned remainder columns
+    Subtractions add subtraction_pad(), so every dividend limb stays a non-negative integer."""
+
+    def _setup(self, cs):
+        self._chosen, self._declared = [], []
+        self._pad = subtraction_pad(self.modulus, self.n, self.limbs, self.operand_bits)
+
+    def _given_limbs(self, cs, value, bits=None):
+        bits = self.n if bits is None else bits
+        values = int_limbs(value, self.n, self.limbs)
+        assert all(v < 1 << bits for v in values), "an operand limb is wider than operand_bits"
+        return [([(1, self._given(cs, v))], v, (1 << bits) - 1) for v in values]
+
+    def _minus(self, x, y, scale=1):
+        """x - y + scale pad, limb by limb; y may be shorter than x (its missing limbs are zero and take no pad)"""
+        out = []
+        for j, (lc, v, hi) in enumerate(x):
+            if j < len(y):
+                pad = scale * self._pad[j]
+                assert y[j][2] <= pad, "a subtrahend limb may exceed the pad"
+                lc = [term for term in _merged(lc + [(-c, var) for c, var in y[j][0]] + [(pad, ConstraintSystem.ONE)]) if term[0]]
+                v, hi = v - y[j][1] + pad, hi + pad
+            assert v >= 0
+            out.append((lc, v, hi))
+        return out
+
+    def _bits(self, cs, limbs):
+        if self.decompose:
+            for lc, v, _ in limbs:
+                cs.enforce_constraint(lc, [(1, ConstraintSystem.ONE)], _weighted(_new_bits(cs, v, self.n)))
+
+    def _fresh(self, cs, values):
+        first = len(cs.witness)
+        return [([(1, cs.new_witness_variable(v))], v, (1 << self.n) - 1) for v in values], list(range(first, first + len(values)))
+
+    def _quotient(self, cs, Np, Nm, Dp, Dm):
+        """Operands: lists of limbs that are single witness columns (or empty lists).  -> the limbs of Z"""
+        p, n = self.modulus, self.n
+        index = lambda limbs: [lc[0][1][1] for lc, _, _ in limbs]
+        assert all(len(lc) == 1 and lc[0][0] == 1 and lc[0][1][0] == "wit" for lc, _, _ in Np + Nm + Dp + Dm)
+        value = lambda limbs: limbs_int([v for _, v, _ in limbs], n)
+        N = (value(Np) - value(Nm)) % p if Np or Nm else 1
+        D = (value(Dp) - value(Dm)) % p
+        Z = N * pow(D, -1, p) % p            # raises where D has no inverse: the generator's inputs must avoid it
+        out, at = self._fresh(cs, int_limbs(Z, n, self.limbs))
+        self._declared.append({"op": "moddiv", "n": n, "z": at, "Np": index(Np), "Nm": index(Nm), "Dp": index(Dp), "Dm": index(Dm),
+                               "literal": int_limbs(p, n, self.limbs)})
+        self._bits(cs, out)
+        return out
+
+    def _product(self, cs, a, b):
+        r = cs.r
+        values = [sum(a[i][1] * b[j - i][1] for i in range(len(a)) if 0 <= j - i < len(b)) for j in range(len(a) + len(b) - 1)]
+        bounds = [sum(a[i][2] * b[j - i][2] for i in range(len(a)) if 0 <= j - i < len(b)) for j in range(len(a) + len(b) - 1)]
+        assert max(bounds) < r, "a limb of the no-carry product may reach r"
+        out = [([(1, cs.new_witness_variable(v))], v, hi) for v, hi in zip(values, bounds)]
+        at = lambda limbs, c: _merged([(coef * pow(c, i, r), var) for i, (lc, _, _) in enumerate(limbs) for coef, var in lc])
+        for c in range(1, len(out) + 1):
+            cs.enforce_constraint(at(a, c), at(b, c), at(out, c))
+        return out
+
+    def _reduce(self, cs, T, zero=False):
+        one, r, n, l, p = ConstraintSystem.ONE, cs.r, self.n, self.limbs, self.modulus
+        assert max(hi for _, _, hi in T) < r, "a dividend limb may reach r"
+        cols = []
+        for lc, v, hi in T:
+            if not (len(lc) == 1 and lc[0][0] == 1 and lc[0][1][0] == "wit"):
+                var = cs.new_witness_variable(v)
+                cs.enforce_constraint(lc, [(1, one)], [(1, var)])
+                lc = [(1, var)]
+            cols.append((lc, v, hi))
+        top = limbs_int([hi for _, _, hi in T], n)
+        assert top < 1 << 1024, "the dividend may reach 2^1024"
+        kq = max(1, -(-(top // p).bit_length() // n))
+        q_int, rem_int = divmod(limbs_int([v for _, v, _ in T], n), p)
+        assert not zero or rem_int == 0, "a hinted division that must be exact is not"
+        q, q_at = self._fresh(cs, int_limbs(q_int, n, kq))
+        rem, rem_at = self._fresh(cs, int_limbs(rem_int, n, l))
+        self._declared.append({"n": n, "q": q_at, "rem": rem_at, "D": [lc[0][1][1] for lc, _, _ in cols], "literal": int_limbs(p, n, l)})
+        self._bits(cs, q + rem)
+        p_v = int_limbs(p, n, l)
+        width = max(len(cols), kq + l - 1)
+        qp_v = [sum(q[i][1] * p_v[j - i] for i in range(kq) if 0 <= j - i < l) for j in range(width)]
+        assert max(qp_v) < r
+        qp = [cs.new_witness_variable(v) for v in qp_v]
+        for j in range(width):
+            cs.enforce_constraint([(p_v[j - i] % r, q[i][0][0][1]) for i in range(kq) if 0 <= j - i < l and p_v[j - i]], [(1, one)], [(1, qp[j])])
+        carries, carry = [], 0
+        for j in range(width):
+            total = (cols[j][1] if j < len(cols) else 0) - qp_v[j] - (rem[j][1] if j < l else 0) + carry
+            assert total % (1 << n) == 0
+            carry = total >> n
+            lc = (cols[j][0] if j < len(cols) else []) + [(-1, qp[j])] + ([(-1, rem[j][0][0][1])] if j < l else []) + ([(1, carries[-1])] if j else [])
+            if j < width - 1:
+                carries.append(cs.new_witness_variable(carry))
+            cs.enforce_constraint(lc, [(1, one)], [(pow(2, n, r), carries[-1])] if j < width - 1 else [])
+        assert carry == 0
+        if zero:
+            for lc, _, _ in rem:
+                cs.enforce_constraint(lc, [(1, one)], [])
+        return rem
+
+    def _close(self, cs, sums):
+        """one ordinary row per list of limbs,  (sum limbs) * 1 = s , and the public input  sum s"""
+        one, total, total_v = ConstraintSystem.ONE, [], 0
+        for limbs in sums:
+            v = sum(value for _, value, _ in limbs)
+            s = cs.new_witness_variable(v)
+            cs.enforce_constraint(_merged([term for lc, _, _ in limbs for term in lc]), [(1, one)], [(1, s)])
+            total.append((1, s))
+            total_v += v
+        out = cs.new_input_variable(total_v)
+        cs.enforce_constraint(total, [(1, one)], [(1, out)])
+
+    def hints(self, m0=2):
+        """the declaration for Polymath.set_hints / api.encode_hints: the modular and the long-division hints in the order the
+        generator meets them, the modulus a literal in all of them.  The witness indices are those of the generator's last pass
+        (generate_constraints, partial or native; they depend neither on r nor on the values), so a generator that was run as part of
+        a larger system declares its columns there"""
+        if not getattr(self, "_declared", None):     # no generate_constraints, partial or native yet: a pass for the layout alone
+            self.generate_constraints(_ValuesOnly(_LAYOUT_R))
+        return [{key: v if key in ("op", "n", "literal") else [m0 + j for j in v] for key, v in hint.items()} for hint in self._declared]
+
+    def native(self, r):
+        """-> (instance, witness) on Python integers, without generating a row; every value comes from Python's pow and divmod, and
+        every division that must be exact is asserted to be"""
+        cs = _ValuesOnly(r)
+        self.generate_constraints(cs)
+        return cs.instance, cs.witness
+
+
+class LimbModDiv(_PartialModDiv):
+    """Non-native modular division (the slope of a point addition, ark-r1cs-std's non-native inverse, circom-ecdsa's BigModInv): per
+    case (N+, N-, D+, D-) of integers their given limbs, Z = (N+ - N-) / (D+ - D-) mod `modulus` from a modular hint, and the check
+    Z (D+ - D- + pad) - (N+ - N-) + pad = 0 (mod modulus): the product's block, then _reduce with a remainder that must be zero.  A
+    case (None, None, D+, D-) is the inverse: N = 1, no numerator columns.  One ordinary row per case sums Z's limbs, and the public
+    input is the sum of those.  operand_bits < n keeps the given limbs and the pad narrow, for limbs so wide that full ones would
+    carry a product past r (n = 128): see subtraction_pad."""
+
+    def __init__(self, cases, modulus, n, limbs, decompose=True, operand_bits=None):
+        self.cases, self.modulus, self.n, self.limbs, self.decompose, self.operand_bits = [tuple(c) for c in cases], int(modulus), n, limbs, decompose, operand_bits
+
+    def generate_constraints(self, cs):
+        self._setup(cs)
+        sums = []
+        for Np_v, Nm_v, Dp_v, Dm_v in self.cases:
+            inverse = Np_v is None and Nm_v is None
+            Np, Nm = ([], []) if inverse else (self._given_limbs(cs, Np_v, self.operand_bits), self._given_limbs(cs, Nm_v, self.operand_bits))
+            Dp, Dm = self._given_limbs(cs, Dp_v, self.operand_bits), self._given_limbs(cs, Dm_v, self.operand_bits)
+            Z = self._quotient(cs, Np, Nm, Dp, Dm)
+            T = self._product(cs, Z, self._minus(Dp, Dm))
+            numerator = [([(1, ConstraintSystem.ONE)], 1, 1)] + [([], 0, 0)] * (self.limbs - 1) if inverse else self._minus(Np, Nm)
+            # Z D - N + pad, the whole pad: a numerator N+ - N- + pad carries one pad itself, so its subtraction takes two
+            self._reduce(cs, self._minus(T, numerator, 2 if not inverse else 1), zero=True)
+            sums.append(Z)
+        self._close(cs, sums)
+
+
+class EcAddChain(_PartialModDiv):
+    """`steps` affine additions R <- R + Q on a short Weierstrass curve y^2 = x^3 + b over `modulus` (b plays no part in an addition
+    of points with different x), on l limbs of n bits: R_0 = `point` and Q = `addend` are given, and the caller keeps the
+    x-coordinates of R_t and Q distinct (asserted).  Per step
+        lambda = (Y2 - Y1) / (X2 - X1)          a modular hint
+        lambda (X2 - X1) - (Y2 - Y1) = 0        the product's block, _reduce to zero
+        X3 = lambda^2 - X1 - X2                 the product's block, _reduce
+        Y3 = lambda (X1 - X3) - Y1              the product's block, _reduce
+    all modulo the modulus, so modular and long-division hints alternate through the dependency levels.  One ordinary row per step sums
+    the limbs of X3 and Y3; the public input is the sum of those.  The result is compared with affine addition on Python integers."""
+
+    def __init__(self, point, addend, modulus, n, limbs, steps, decompose=True):
+        self.point, self.addend, self.modulus, self.n, self.limbs, self.steps = tuple(point), tuple(addend), int(modulus), n, limbs, steps
+        self.decompose, self.operand_bits = decompose, None
+
+    def result(self):
+        """R_0 + steps Q by the affine formulas on Python integers"""
+        p, (x1, y1), (x2, y2) = self.modulus, self.point, self.addend
+        for _ in range(self.steps):
+            assert (x1 - x2) % p, "the x-coordinates meet: the chord's slope is not defined"
+            lam = (y2 - y1) * pow(x2 - x1, -1, p) % p
+            x3 = (lam * lam - x1 - x2) % p
+            x1, y1 = x3, (lam * (x1 - x3) - y1) % p
+        return x1, y1
+
+    def generate_constraints(self, cs):
+        self._setup(cs)
+        n, want = self.n, self.result()         # asserts that every chord has a slope
+        X1, Y1 = self._given_limbs(cs, self.point[0]), self._given_limbs(cs, self.point[1])
+        X2, Y2 = self._given_limbs(cs, self.addend[0]), self._given_limbs(cs, self.addend[1])
+        sums = []
+        for _ in range(self.steps):
+            lam = self._quotient(cs, Y2, Y1, X2, X1)
+            dY = self._minus(Y2, Y1)
+            self._reduce(cs, self._minus(self._product(cs, lam, self._minus(X2, X1)), dY, 2), zero=True)
+            X3 = self._reduce(cs, self._minus(self._minus(self._product(cs, lam, lam), X1), X2))
+            Y3 = self._reduce(cs, self._minus(self._product(cs, lam, self._minus(X1, X3)), Y1))
+            sums.append(X3 + Y3)
+            X1, Y1 = X3, Y3
+        assert (limbs_int([v for _, v, _ in X1], n), limbs_int([v for _, v, _ in Y1], n)) == want
+        self._close(cs, sums)
+
+
+def moddiv_cases(modulus, count, seed=SPLITMIX_SEED, inverses=0, narrow=None):
+    """`count` cases (N+, N-, D+, D-) of integers for LimbModDiv, drawn from SplitMix64(seed), the last `inverses` of them
+    (None, None, D+, D-).  The operands are below `modulus`, or -- narrow = (n, limbs, bits) -- have `limbs` limbs of n bits of which
+    only the low `bits` are drawn (LimbModDiv's operand_bits).  A denominator without an inverse modulo a composite modulus is drawn
+    again."""
+    from math import gcd
+    g = SplitMix64(seed)
+    rnd = lambda bits: sum(g.next_u64() << (64 * i) for i in range(-(-bits // 64))) & ((1 << bits) - 1)
+    draw = (lambda: rnd(modulus.bit_length() + 64) % modulus) if narrow is None else (lambda: sum(rnd(narrow[2]) << (narrow[0] * j) for j in range(narrow[1])))
+    out = []
+    while len(out) < count:
+        Np, Nm, Dp, Dm = draw(), draw(), draw(), draw()
+        if gcd((Dp - Dm) % modulus, modulus) == 1:
+            out.append((None, None, Dp, Dm) if len(out) >= count - inverses else (Np, Nm, Dp, Dm))
+    return out
+
+
+def narrow_modulus(n, limbs, bits, seed=SPLITMIX_SEED):
+    """An odd modulus (not a prime) whose `limbs` limbs of n bits each lie in [2^bits, 2^(bits + 1)): its own limbs are a narrow
+    subtraction_pad for operands of `bits`-bit limbs"""
+    g = SplitMix64(seed)
+    return sum(((1 << bits) + (g.next_u64() | (1 if j == 0 else 0))) << (n * j) for j in range(limbs))
 
 
 def _invertible(rows, r):

@@ -2,7 +2,7 @@
 // (include/polymath_hip.h), so that a caller supplies only the values it chooses and the library computes the rest
 // before it checks or proves.  The PLAN -- which row determines which column, in which order -- is host work, done once per (key,
 // pattern) by host/solve_plan.hpp; what ONE step does to ONE assignment (solve_step, solve_bits, solve_iszero, solve_divrem,
-// solve_indicator, solve_sqrt, solve_block, solve_longdiv, the dispatch solve_any, the inverses' solve_inverse and solve_block_invert, and the records
+// solve_indicator, solve_sqrt, solve_block, solve_longdiv, solve_moddiv, the dispatch solve_any, the inverses' solve_inverse and solve_block_invert, and the records
 // a plan becomes: solve_records) is
 // solve_steps.cuh, text that the CPU self-tests run as well; this file is the kernels that call it and the host driver,
 // assignment = grid y (or the lane, in the chain kernel):
@@ -31,6 +31,12 @@
 //                     input limbs leave Montgomery form and are accumulated at bit offset n j into a 1024-bit dividend and a 512-bit
 //                     divisor, a restoring shift-subtract divides in the launch's trip count (wave-uniform: the plan's bound, at most 1024; solve_steps.cuh: longdiv), and the n-bit limbs
 //                     of quotient and remainder are stored.  No register is indexed at run time; stuck at the word nr + h
+//   k_solve_moddiv    the declared modular divisions of a level, Z = (N+ - N-) / (D+ - D-) mod P, whatever its width: one lane per (hint,
+//                     assignment).  The modulus and, one after the other, the four operand lists are accumulated like a dividend;
+//                     each list is reduced modulo P by longdiv (the launch's reduction bound) and folded into N or D by masked
+//                     selects; a binary extended Euclid for odd modulus with masked updates runs the launch's 2 L rounds with the
+//                     numerator in place of 1, so that it ends in Z itself (solve_steps.cuh: modinv_odd proves the bound).  No
+//                     register is indexed at run time; stuck at the word nr + h
 //   k_solve_chain     a run of consecutive NARROW levels: one lane per assignment walks the run's steps in plan order.  A lane
 //                     reads back only its own stores: no barriers, no fences.  The MiMC shape (depth 644, width 1) is one such run
 //                     and the batch is its parallel dimension.
@@ -181,6 +187,18 @@ __global__ __launch_bounds__(64) void k_solve_longdiv(const SolveStepDev<P> *__r
     solve_longdiv<P>(steps[t], hints[steps[t].bits], hint_idx, rounds, xw + b * ncols, StuckWord{stuck + b});
 }
 
+// One lane per (hint, assignment), as k_solve_longdiv.  The phases reuse registers: a list's 32-word sum, the 17-word remainder and
+// trial difference are dead when the next list begins and when the Euclid's v and x2 come to life; the modulus, N and D (16 words
+// each) live throughout.
+template <class P>
+__global__ __launch_bounds__(64) void k_solve_moddiv(const SolveStepDev<P> *__restrict__ steps, const SolveModDev *__restrict__ mods,
+                                                     const uint32_t *__restrict__ hint_idx, uint32_t rounds, uint32_t inv_rounds, uint32_t lo, uint32_t hi,
+                                                     Fp<P> *xw, uint64_t ncols, unsigned long long *stuck) {
+    const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (t >= hi) return;
+    solve_moddiv<P>(steps[t], mods[steps[t].bits], hint_idx, rounds, inv_rounds, xw + b * ncols, StuckWord{stuck + b});
+}
+
 // the step index is the same in every lane: the step record, the pair record, the row's CSR metadata and a decomposition's column
 // list are uniform loads (solve_steps.cuh: solve_any, the dispatch by kind).
 template <class P, bool DIV>
@@ -297,7 +315,7 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
                 return PM_ERR_STATE;
             }
     const size_t n_steps = sv.plan.steps.size();
-    sv.n_pairs = sv.n_divs = sv.n_blocks = sv.n_hints = 0;
+    sv.n_pairs = sv.n_divs = sv.n_blocks = sv.n_hints = sv.n_mods = 0;
     if (n_steps) {
         SolveRecords<P> rec = solve_records<P>(sv.plan);
         // the linear blocks' matrices are constants of the key: each distinct one is inverted here, once per plan, from the words the
@@ -325,9 +343,16 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
             PM_HIP(ctx, hipMemcpyAsync(sv.block_inv.p, rec.block_inv.data(), rec.block_inv.size() * sizeof(Fp<P>), hipMemcpyHostToDevice, st));
         }
         sv.n_hints = rec.hints.size();
+        sv.n_mods = rec.mods.size();
         if (sv.n_hints) {
             PM_HIP(ctx, sv.hints.reserve(sv.n_hints * sizeof(SolveHintDev)));
             PM_HIP(ctx, hipMemcpyAsync(sv.hints.p, rec.hints.data(), sv.n_hints * sizeof(SolveHintDev), hipMemcpyHostToDevice, st));
+        }
+        if (sv.n_mods) {
+            PM_HIP(ctx, sv.mods.reserve(sv.n_mods * sizeof(SolveModDev)));
+            PM_HIP(ctx, hipMemcpyAsync(sv.mods.p, rec.mods.data(), sv.n_mods * sizeof(SolveModDev), hipMemcpyHostToDevice, st));
+        }
+        if (sv.n_hints || sv.n_mods) {
             PM_HIP(ctx, sv.hint_idx.reserve(rec.hint_idx.size() * sizeof(uint32_t)));
             PM_HIP(ctx, hipMemcpyAsync(sv.hint_idx.p, rec.hint_idx.data(), rec.hint_idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         }
@@ -387,6 +412,10 @@ int solve_group(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t 
                 if (!sv.n_hints || l.rounds < 256 || l.rounds > 1024) return PM_ERR_STATE;
                 hipLaunchKernelGGL((k_solve_longdiv<P>), dim3(nblk(l.hi - l.lo, 64), (unsigned)g), dim3(64), 0, st, steps, sv.hints.as<SolveHintDev>(),
                                    sv.hint_idx.as<uint32_t>(), l.rounds, l.lo, l.hi, d_xw, ncols, stuck);
+            } else if (l.moddiv) {
+                if (!sv.n_mods || l.rounds < 256 || l.rounds > 1024 || l.inv_rounds < 512 || l.inv_rounds > 1024) return PM_ERR_STATE;
+                hipLaunchKernelGGL((k_solve_moddiv<P>), dim3(nblk(l.hi - l.lo, 64), (unsigned)g), dim3(64), 0, st, steps, sv.mods.as<SolveModDev>(),
+                                   sv.hint_idx.as<uint32_t>(), l.rounds, l.inv_rounds, l.lo, l.hi, d_xw, ncols, stuck);
             } else if (l.chain) {
                 const dim3 grid(nblk(g, 64)), block(64);
                 if (l.divides) hipLaunchKernelGGL((k_solve_chain<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, pairs, divs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);

@@ -64,6 +64,13 @@ struct SolveHintDev {
     uint32_t n, kq, kr, kD, kE, literal, off, pad;
 };
 
+// what a modular-division step needs beside its SolveStepDev (whose bits = its SolveModDev): in the hint pool from `off` the kz output
+// columns, the kNp, kNm, kDp and kDm operand columns, then the kP modulus columns -- or, literal != 0, the 16 words of the modulus'
+// literal limbs accumulated at bit offset n j and one word that is non-zero where they reach 2^512, as for a literal divisor
+struct SolveModDev {
+    uint32_t n, kz, k[4], kP, literal, off, pad;
+};
+
 // The record arrays of a plan, as the kernels read them; the inverses are left zero (solve_inverse fills them), the pool of block
 // inverses empty (solve_block_inverses fills it).
 template <class P>
@@ -77,6 +84,7 @@ struct SolveRecords {
     std::vector<Fp<P>> block_inv;         // the inverse pool
     std::vector<SolveHintDev> hints;
     std::vector<uint32_t> hint_idx;       // the hint pool
+    std::vector<SolveModDev> mods;        // the modular divisions; their columns and literal moduli are in the hint pool too
 };
 
 constexpr int LONGDIV_WD = 32, LONGDIV_WE = 16;   // the long division's registers in 32-bit words: a 1024-bit dividend, a 512-bit divisor
@@ -208,14 +216,19 @@ inline SolveRecords<P> solve_records(const pmsolve::Plan &plan) {
             rec.block_idx.insert(rec.block_idx.end(), blk.cols.begin(), blk.cols.end());
             rec.blocks.push_back(SolveBlockDev{k, rows_off, rows_off + k, 0, rec.mat_off[blk.mat]});
         }
-        if (s.kind == pmsolve::KIND_LONGDIV) {
+        if (s.kind == pmsolve::KIND_LONGDIV || s.kind == pmsolve::KIND_MODDIV) {
             const pmsolve::Hint &h = plan.hints[s.cols_off];
-            const bool literal = (h.flags & pmsolve::HINT_DIVISOR_LITERAL) != 0;
-            d.bits = (uint32_t)rec.hints.size();
-            rec.hints.push_back(SolveHintDev{h.n, (uint32_t)h.q.size(), (uint32_t)h.rem.size(), (uint32_t)h.D.size(),
-                                             (uint32_t)(literal ? h.lit.size() / 4 : h.E.size()), literal ? 1u : 0u, (uint32_t)rec.hint_idx.size(), 0});
+            const bool literal = (h.flags & pmsolve::HINT_DIVISOR_LITERAL) != 0;   // HINT_MODULUS_LITERAL is the same bit
+            const uint32_t kE = (uint32_t)(literal ? h.lit.size() / 4 : h.E.size()), off = (uint32_t)rec.hint_idx.size();
+            if (s.kind == pmsolve::KIND_MODDIV) {
+                d.bits = (uint32_t)rec.mods.size();
+                rec.mods.push_back(SolveModDev{h.n, (uint32_t)h.q.size(), {h.k[0], h.k[1], h.k[2], h.k[3]}, kE, literal ? 1u : 0u, off, 0});
+            } else {
+                d.bits = (uint32_t)rec.hints.size();
+                rec.hints.push_back(SolveHintDev{h.n, (uint32_t)h.q.size(), (uint32_t)h.rem.size(), (uint32_t)h.D.size(), kE, literal ? 1u : 0u, off, 0});
+            }
             for (const std::vector<uint32_t> *cols : {&h.q, &h.rem, &h.D, &h.E}) rec.hint_idx.insert(rec.hint_idx.end(), cols->begin(), cols->end());
-            if (literal) {   // the divisor is a constant of the key: accumulated once, here
+            if (literal) {   // the divisor (the modulus) is a constant of the key: accumulated once, here
                 uint32_t E[LONGDIV_WE] = {0}, lost = 0;
                 for (size_t j = 0; j < h.lit.size() / 4; ++j) {
                     uint32_t v[8];
@@ -260,7 +273,7 @@ PM_HD uint32_t matrix_kind(uint32_t kind) { return kind >= pmsolve::KIND_BITS_C 
 template <class P>
 PM_HD void solve_inverse(const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsolve::Csr &Cm, SolveStepDev<P> *steps, uint64_t count, SolvePairDev<P> *pairs,
                          const SolveDivDev *divs, uint64_t t) {
-    if (t < count && (steps[t].kind == pmsolve::KIND_INDICATOR || steps[t].kind == pmsolve::KIND_BLOCK || steps[t].kind == pmsolve::KIND_LONGDIV)) return;   // no inverse of a coefficient: the record stays as the host wrote it
+    if (t < count && (steps[t].kind == pmsolve::KIND_INDICATOR || steps[t].kind == pmsolve::KIND_BLOCK || steps[t].kind == pmsolve::KIND_LONGDIV || steps[t].kind == pmsolve::KIND_MODDIV)) return;   // no inverse of a coefficient: the record stays as the host wrote it
     if (t < count && steps[t].kind == pmsolve::KIND_SQRT) {
         const Fp<P> ka = *(const Fp<P> *)(A.val + 4 * steps[t].pos), kb = *(const Fp<P> *)(B.val + 4 * (B.rowptr[steps[t].row] + steps[t].bits));
         const Fp<P> coef = mul<P>(ka, kb);
@@ -576,6 +589,156 @@ PM_HD void solve_longdiv(const SolveStepDev<P> &s, const SolveHintDev &h, const 
 #pragma unroll
         for (int w = 0; w < P::N; ++w) limb.l[w] &= mask;
         z[r_cols[i]] = to_mont<P>(limb);
+    }
+}
+
+// a -= b & mask on W words -> the borrow (0 or 1)
+template <int W>
+PM_HD uint32_t sub_masked(uint32_t (&a)[W], const uint32_t (&b)[W], uint32_t mask) {
+    uint32_t borrow = 0;
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+        const uint32_t bj = b[j] & mask, x = a[j] - borrow, b1 = a[j] < borrow;
+        a[j] = x - bj;
+        borrow = b1 | (uint32_t)(x < bj);
+    }
+    return borrow;
+}
+
+// a += b & mask on W words -> the carry (0 or 1)
+template <int W>
+PM_HD uint32_t add_masked(uint32_t (&a)[W], const uint32_t (&b)[W], uint32_t mask) {
+    uint32_t carry = 0;
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+        const uint64_t sum = (uint64_t)a[j] + (b[j] & mask) + carry;
+        a[j] = (uint32_t)sum;
+        carry = (uint32_t)(sum >> 32);
+    }
+    return carry;
+}
+
+// Binary extended Euclid for an ODD modulus p, every update masked, `rounds` rounds whatever the operands: on entry u in [0, p),
+// v = p, x1 = c in [0, p), x2 = 0; where gcd(u, p) = 1 it leaves v = 1 and x2 = c / u mod p (c = 1: the inverse; the caller passes the
+// numerator of a modular division and saves the product and the reduction that would follow).  One round:
+//     u odd and u < v:  swap (u, v) and (x1, x2)          -- v is odd on entry and stays odd: it only ever takes an odd u's value
+//     u odd:            u -= v,  x1 = x1 - x2 mod p       -- u is even now
+//     always:           u /= 2,  x1 = x1 / 2 mod p        -- p is odd: x1 or x1 + p is even
+// Invariants: x1 d = u c and x2 d = v c (mod p) for the d the caller put into u, and gcd(u, v) = gcd(d, p).
+// THE BOUND.  Let p < 2^L and s = bitlength(u) + bitlength(v) <= 2 L.  The swap leaves s alone.  A round with u > 0 lowers s by at
+// least one: an even u loses a bit by the halving; an odd u >= v becomes (u - v) / 2 < u / 2, at least one bit shorter.  v >= 1
+// always, so u > 0 means s >= 2, and u > 0 can hold for at most 2 L - 1 rounds.  With u = 0 a round changes neither v nor x2 (u is
+// even, never swapped; only x1 is halved, which nothing reads).  So after 2 L rounds u = 0 and v = gcd(d, p): the caller tests v = 1.
+// Worst cases: u = 2^(L - 1) (L - 1 halvings before the first subtraction), u = p - 1 and u = (p +- 1) / 2 (subtractions that shorten
+// by one bit only).  An even p (the caller has marked it stuck) breaks the invariants, not the trip count.  Word loops unrolled, the
+// round loop rolled; no branch and no register index depends on an operand.
+template <int W>
+PM_HD void modinv_odd(uint32_t (&u)[W], uint32_t (&v)[W], uint32_t (&x1)[W], uint32_t (&x2)[W], const uint32_t (&p)[W], uint32_t rounds) {
+#pragma unroll 1
+    for (uint32_t round = 0; round < rounds; ++round) {
+        const uint32_t odd = 0u - (u[0] & 1u);
+        uint32_t borrow = 0;         // of u - v: u < v
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const uint32_t x = u[j] - borrow, b1 = u[j] < borrow;
+            borrow = b1 | (uint32_t)(x < v[j]);
+        }
+        const uint32_t swap = odd & (0u - borrow);
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const uint32_t tu = (u[j] ^ v[j]) & swap, tx = (x1[j] ^ x2[j]) & swap;
+            u[j] ^= tu; v[j] ^= tu;
+            x1[j] ^= tx; x2[j] ^= tx;
+        }
+        sub_masked<W>(u, v, odd);
+        add_masked<W>(x1, p, 0u - sub_masked<W>(x1, x2, odd));
+        const uint32_t top = add_masked<W>(x1, p, 0u - (x1[0] & 1u));
+#pragma unroll
+        for (int j = 0; j < W - 1; ++j) {
+            u[j] = u[j] >> 1 | u[j + 1] << 31;
+            x1[j] = x1[j] >> 1 | x1[j + 1] << 31;
+        }
+        u[W - 1] >>= 1;
+        x1[W - 1] = x1[W - 1] >> 1 | top << 31;
+    }
+}
+
+// one declared modular division on one assignment: Z = (N+ - N-) / (D+ - D-) mod P.  The modulus is accumulated like a divisor (or is
+// the literal that solve_records accumulated).  Then the four operand lists in turn, in ONE rolled loop so that the kernel holds one
+// copy of longdiv: a list's limbs leave Montgomery form and are accumulated at bit offset n j, 1024 - rounds bits higher (`rounds`:
+// the launch's reduction bound, at least n (k - 1) + 256 or 1024 for every list, so what add_shifted loses is exactly a sum >= 2^1024),
+// longdiv leaves the sum mod P, and a masked select puts it into N or D (lists 0 and 2) or subtracts it modulo P (lists 1 and 3);
+// an empty list is passed over, which is a branch on the record, not on an operand.  kNp = kNm = 0: N = 1.  modinv_odd with u = D,
+// x1 = N and `inv_rounds` = 2 L rounds (P < 2^L, or P >= 2^512 and the lane is stuck already) leaves Z = N / D mod P in x2 where v = 1
+// -- the product N D^-1 and its reduction are not formed: the Euclid carries the numerator instead of 1 --, and the kz n-bit limbs of
+// Z go back to Montgomery form and into their columns.  Stuck at the hint's word (nr + h: the step's row), with zero in every output:
+//   P even or P < 3;  P >= 2^512;  N+, N-, D+ or D- >= 2^1024;  gcd(D mod P, P) != 1 (D = 0 mod P included);  Z >= 2^(n kz)
+// or-ed into one word, the outputs stored under its mask.  The dividend, remainder and trial difference of the reductions are dead
+// when the Euclid's v, x1 and x2 come to life.
+template <class P, class Sink>
+PM_HD void solve_moddiv(const SolveStepDev<P> &s, const SolveModDev &h, const uint32_t *__restrict__ hint_idx, uint32_t rounds, uint32_t inv_rounds, Fp<P> *z,
+                        const Sink &stuck) {
+    static_assert(P::N == 8, "four 64-bit words");
+    const uint32_t *z_cols = hint_idx + h.off, *cols = z_cols + h.kz, *p_words = cols + h.k[0] + h.k[1] + h.k[2] + h.k[3];
+    uint32_t M[LONGDIV_WE], Nr[LONGDIV_WE], Dr[LONGDIV_WE], bad = 0;
+#pragma unroll
+    for (int w = 0; w < LONGDIV_WE; ++w) M[w] = Nr[w] = Dr[w] = 0;
+    if (h.literal) {
+#pragma unroll
+        for (int w = 0; w < LONGDIV_WE; ++w) M[w] = p_words[w];
+        bad |= p_words[LONGDIV_WE];
+    } else {
+        for (uint32_t j = 0; j < h.kP; ++j) bad |= add_shifted<LONGDIV_WE>(M, from_mont<P>(z[p_words[j]]).l, h.n * j);
+    }
+    uint32_t high = 0;
+#pragma unroll
+    for (int w = 1; w < LONGDIV_WE; ++w) high |= M[w];
+    bad |= (uint32_t)((M[0] & 1u) == 0) | (uint32_t)(high == 0 && M[0] == 1u);   // even (0 and 2 included), or 1
+    const uint32_t base = 32u * LONGDIV_WD - rounds;
+#pragma unroll 1
+    for (uint32_t which = 0; which < 4; ++which) {
+        const uint32_t k = h.k[which];
+        if (k == 0) continue;
+        uint32_t S[LONGDIV_WD], R[LONGDIV_WE + 1], T[LONGDIV_WE];
+#pragma unroll
+        for (int w = 0; w < LONGDIV_WD; ++w) S[w] = 0;
+        for (uint32_t j = 0; j < k; ++j) bad |= add_shifted<LONGDIV_WD>(S, from_mont<P>(z[cols[j]]).l, base + h.n * j);
+        cols += k;
+        longdiv<LONGDIV_WD, LONGDIV_WE>(S, M, R, rounds);
+        const uint32_t numerator = which < 2 ? ~0u : 0u, subtract = 0u - (which & 1u);
+#pragma unroll
+        for (int w = 0; w < LONGDIV_WE; ++w) T[w] = ((Nr[w] & numerator) | (Dr[w] & ~numerator)) & subtract;   // 0, or what the list is subtracted from
+        // lists 0 and 2: T = R;  lists 1 and 3: T = T - R mod P.  R < P (R[16] = 0) wherever P != 0
+        uint32_t Rw[LONGDIV_WE];
+#pragma unroll
+        for (int w = 0; w < LONGDIV_WE; ++w) Rw[w] = R[w];
+        add_masked<LONGDIV_WE>(T, Rw, ~subtract);
+        add_masked<LONGDIV_WE>(T, M, 0u - sub_masked<LONGDIV_WE>(T, Rw, subtract));
+#pragma unroll
+        for (int w = 0; w < LONGDIV_WE; ++w) {
+            Nr[w] = (T[w] & numerator) | (Nr[w] & ~numerator);
+            Dr[w] = (T[w] & ~numerator) | (Dr[w] & numerator);
+        }
+    }
+    if ((h.k[0] | h.k[1]) == 0) Nr[0] = 1;       // a plain inverse (P = 1 is stuck)
+    uint32_t V[LONGDIV_WE], Z[LONGDIV_WE];
+#pragma unroll
+    for (int w = 0; w < LONGDIV_WE; ++w) {
+        V[w] = M[w];
+        Z[w] = 0;
+    }
+    modinv_odd<LONGDIV_WE>(Dr, V, Nr, Z, M, inv_rounds);
+    uint32_t rest = V[0] ^ 1u;       // gcd(D mod P, P) - 1
+#pragma unroll
+    for (int w = 1; w < LONGDIV_WE; ++w) rest |= V[w];
+    bad |= rest | bits_from<LONGDIV_WE>(Z, h.n * h.kz);
+    if (bad) stuck(s);
+    const uint32_t mask = bad ? 0u : ~0u;
+    for (uint32_t i = 0; i < h.kz; ++i) {
+        Fp<P> limb = limb_at<P, LONGDIV_WE>(Z, h.n * i, h.n);
+#pragma unroll
+        for (int w = 0; w < P::N; ++w) limb.l[w] &= mask;
+        z[z_cols[i]] = to_mont<P>(limb);
     }
 }
 

@@ -165,8 +165,25 @@
 //                 (Launch::longdiv, not dividing) whatever the level's width; Launch::rounds is the division's trip count for the launch, the
 //                 largest min(1024, n (kD - 1) + 256) of its hints.  A hint that never becomes ready is refused as
 //                 "hint h: input column c is never determined", followed by the scheduler's text for the first column that stays unknown.
-//                 Not handled: other opcodes (modular inverse, gcd, sorting), signed limbs, dividends beyond 1024 bits (RSA-2048),
-//                 hints on sharded keys, per-assignment declarations, inferring a hint from rows.
+//                 Not handled by the long-division record: other opcodes (modular inverse, gcd, sorting), signed limbs, dividends beyond 1024 bits (RSA-2048),
+//                 hints on sharded keys, per-assignment declarations, inferring a hint from rows.  Of these, modular inverse and
+//                 modular division now have a record of their own:
+//   modular hint  a MODULAR DIVISION that the key declares in the same stream (opcode HINT_MODDIV = 3; 2 stays reserved and refused):
+//                 kz output columns, kNp + kNm numerator columns, kDp + kDm denominator columns, kP modulus columns (or kP literal
+//                 limbs), limbs of n bits.  The slope (Y2 - Y1) / (X2 - X1) of an affine point addition, ark-r1cs-std's non-native
+//                 inverse, circom-ecdsa's BigModInv: the circuit checks Z D = N (mod P) through the product-and-reduce path, and no
+//                 row determines Z.  ACTIVE / INERT / refused, HINT-OWNED outputs, waiting on inputs and the never-ready refusal are
+//                 the long-division rules, applied to the kz outputs.  It acts as ONE step of kind KIND_MODDIV at 1 + max level of
+//                 its inputs, Step::row = nr + h, Step::col its first output, Step::cols_off its entry of Plan::hints.  With each list
+//                 the sum of int(z_{c_j}) 2^(n j) (limbs need not be normalised), N = N+ - N- (kNp = kNm = 0: N = 1, a plain
+//                 inverse), D = D+ - D- and P the modulus, the step stores the kz n-bit limbs of the unique Z in [0, P) with
+//                 Z D = N (mod P).  Stuck, with zero in every output: P even or P < 3, P >= 2^512, N+, N-, D+ or D- >= 2^1024,
+//                 gcd(D mod P, P) != 1 (D = 0 mod P included; P need not be prime), Z >= 2^(n kz).  The modular hints of a level
+//                 sort after its long divisions and are a launch of their own (Launch::moddiv; longdiv and block are 0 on it) with
+//                 two trip counts: Launch::rounds, the largest min(1024, n (k - 1) + 256) over the operand lists of its hints (the
+//                 reductions modulo P), and Launch::inv_rounds = 2 L, L the largest min(512, n (kP - 1) + 256) (the inversion).
+//                 Not handled: even moduli, operands beyond 1024 bits, the slope of a doubling as one hint (3 X^2 / 2 Y: the
+//                 numerator is a product), gcd, sorting.
 // With the heap empty the scheduler has failed if an opener is unclosed, a boolean-pending column unsolved or a marked column
 // undetermined; the result is then build_plan's error (code, row, column, message) with "; in any row order: ..." appended.  A plan
 // it finds has Plan::reordered = true, level(step) as below, the steps sorted by (level, kind, row) and the level_ptr and launches of
@@ -200,11 +217,13 @@ namespace pmsolve {
 // KIND_SQRT: a square-root row, z_u = the smaller root of (C z)_r / (ka kb); its inverse is 1 / (ka kb), so it counts as dividing
 // KIND_BLOCK: a linear block, z_S = M^-1 rhs over k rows and k columns; the inverse is plan data, so it does not count as dividing
 // KIND_LONGDIV: a declared long-division hint, kq + kr columns in one step; integer arithmetic only, so it does not count as dividing
-enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6, KIND_DIVREM = 7, KIND_INDICATOR = 8, KIND_SQRT = 9, KIND_BLOCK = 10, KIND_LONGDIV = 11 };
+// KIND_MODDIV: a declared modular-division hint, kz columns in one step; integer arithmetic only as well
+enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6, KIND_DIVREM = 7, KIND_INDICATOR = 8, KIND_SQRT = 9, KIND_BLOCK = 10, KIND_LONGDIV = 11, KIND_MODDIV = 12 };
 constexpr uint32_t NUM_KINDS = 7;        // the kinds that need no second marker: what it always counted
 constexpr uint32_t NUM_STEP_KINDS = 8;   // KIND_C .. KIND_DIVREM, the kinds whose value comes from field or integer arithmetic on the row: what it counted when kind 7 came
 constexpr uint32_t NUM_SORT_KINDS = 10 + 1;  // all 11 of them: the ten kinds that one lane executes, KIND_INDICATOR and KIND_SQRT included, and KIND_BLOCK: the kinds that rows make
 constexpr uint32_t NUM_PLAN_KINDS = 12;  // with KIND_LONGDIV, which no row makes: the key width of finish_plan's counting sort (NUM_SORT_KINDS counts the kinds that rows make, as it did)
+constexpr uint32_t NUM_HINT_KINDS = 13;  // with KIND_MODDIV: the key width of finish_plan's counting sort now (NUM_PLAN_KINDS stays what it counted when kind 11 came)
 constexpr uint32_t MAX_BLOCK = 64;       // the largest linear block: one wave, a lane per row and per column
 
 constexpr uint8_t PATTERN_UNKNOWN = 1, PATTERN_QUOTIENT = 2, PATTERN_INDICATOR = 3, PATTERN_SQRT = 4;   // the pattern bytes (0: given)
@@ -255,12 +274,21 @@ struct BlockMat {     // a distinct block matrix
 // A declared hint (pm_pk_set_hints): limb-wise long division.  Columns are CSR columns (0: the constant one, then the instance, then
 // the witness).  `lit`: with HINT_DIVISOR_LITERAL the divisor's kE limbs as canonical integers of four words each, and E is empty.
 constexpr uint64_t HINT_LONGDIV = 1, HINT_DIVISOR_LITERAL = 1;
+// the modular division's opcode (2 stays reserved and refused), its flag and the limits of its record: kz outputs, kP modulus limbs,
+// at most 32 limbs in each of N+, N-, D+, D-; every operand sum below 2^1024, the modulus below 2^512
+constexpr uint64_t HINT_MODDIV = 3, HINT_MODULUS_LITERAL = 1;
+constexpr uint32_t MODDIV_MAX_KZ = 16, MODDIV_MAX_KP = 16, MODDIV_MAX_K = 32, MODDIV_OPERAND_BITS = 1024, MODDIV_MODULUS_BITS = 512;
 constexpr uint32_t HINT_MAX_N = 128, HINT_MAX_KD = 32, HINT_MAX_KE = 16, HINT_MAX_KQ = 32, HINT_MAX_KR = 16, HINT_D_BITS = 1024, HINT_E_BITS = 512;
 struct Hint {
     uint32_t n = 0, flags = 0;
     std::vector<uint32_t> q, rem, D, E;
     std::vector<uint64_t> lit;
     uint32_t index = 0;                 // its place in the declaration: the stuck word is nr + index
+    // A MODULAR DIVISION (op == HINT_MODDIV) uses the same lists, so that the scheduler reads both opcodes alike: q = the kz output
+    // columns, rem empty, D = the kNp + kNm numerator columns followed by the kDp + kDm denominator columns, E = the kP modulus
+    // columns (lit: its literal limbs, with HINT_MODULUS_LITERAL); k[4] = kNp, kNm, kDp, kDm, the parts of D
+    uint32_t op = (uint32_t)HINT_LONGDIV;
+    uint32_t k[4] = {0, 0, 0, 0};
 };
 
 struct Launch {
@@ -274,8 +302,12 @@ struct Launch {
     uint8_t sqrt = 0;       // chain == 0 only.  1: every step of the range is a square-root row; 0: none is
     uint8_t block = 0;      // chain == 0 only.  1: every step of the range is a linear block (one wave each); 0: none is.  Never divides
     uint8_t longdiv = 0;    // chain == 0 only.  1: every step of the range is a declared long division; 0: none is.  Never divides
-    uint32_t rounds = 0;    // longdiv only: the division's trip count, the largest min(1024, n (kD - 1) + 256) of the range's hints -- a
+    uint32_t rounds = 0;    // longdiv: the division's trip count, the largest min(1024, n (kD - 1) + 256) of the range's hints -- a
                             // dividend of kD limbs below 2^256 at bit offsets n j is below 2 to that power
+                            // moddiv: the same bound over the four operand lists of the range's hints (the reductions modulo P)
+    uint8_t moddiv = 0;     // chain == 0 only.  1: every step of the range is a declared modular division; longdiv and block are 0 on it
+    uint32_t inv_rounds = 0;// moddiv only: the inversion's trip count 2 L, L the largest min(512, n (kP - 1) + 256) of the range's hints:
+                            // every modulus of the range that is not stuck is below 2^L (solve_steps.cuh: modinv_odd proves the bound)
 };
 
 enum Error : int { OK = 0, ERR_MANY_UNKNOWNS = 1, ERR_TWO_MATRICES = 2, ERR_UNDETERMINED = 3, ERR_COLUMN_ZERO = 4, ERR_HINT = 5 };
@@ -475,7 +507,7 @@ inline bool sqrt_row(const std::vector<Unknown> &occ, const uint32_t nz[3], cons
 // The tail both builders share: p.steps (in ROW order, levels set) sorted by (level, kind), stable by row; level_ptr; the launch schedule.
 inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
     // counting sort by (level, kind); the row order inside a key is the order the steps come in
-    constexpr size_t K = NUM_PLAN_KINDS;
+    constexpr size_t K = NUM_HINT_KINDS;
     std::vector<uint32_t> start((size_t)max_level * K + 1, 0);
     for (const Step &s : p.steps) ++start[(size_t)(s.level - 1) * K + s.kind + 1];
     for (size_t i = 1; i < start.size(); ++i) start[i] += start[i - 1];
@@ -492,11 +524,11 @@ inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
     // do not divide: a chain of C-steps and indicators is a non-dividing one), and where the square-root rows begin (which count as
     // dividing); consecutive narrow levels are one chain.  The linear blocks of a level come last and are a launch of their own
     // whatever the level's width (a wave per block, not a lane): a chain run ends before them and a new one begins after them.  So are
-    // the declared hints of a level, after its blocks
+    // the declared hints of a level, after its blocks: first its long divisions, then its modular divisions
     for (uint32_t l = 0; l < max_level; ++l) {
         const uint32_t *at = start.data() + (size_t)l * K;
         const uint32_t lo = at[KIND_C], ab = at[KIND_A], bits = at[KIND_BITS_C], bits_ab = at[KIND_BITS_A], pairs = at[KIND_ISZERO], divs = at[KIND_DIVREM],
-                       inds = at[KIND_INDICATOR], roots = at[KIND_SQRT], hi = at[KIND_BLOCK], end = at[KIND_LONGDIV], hints_end = at[K];
+                       inds = at[KIND_INDICATOR], roots = at[KIND_SQRT], hi = at[KIND_BLOCK], end = at[KIND_LONGDIV], hints_end = at[KIND_MODDIV], moddiv_end = at[K];
         const uint8_t divides = (uint8_t)(bits > ab || inds > bits_ab || hi > roots);
         if (hi == lo) {
             // a level of blocks only
@@ -527,6 +559,18 @@ inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
                 const Hint &h = p.hints[p.steps[t].cols_off];
                 const uint32_t bits = h.n * ((uint32_t)h.D.size() - 1) + 256;
                 hints.rounds = std::max(hints.rounds, std::min(bits, HINT_D_BITS));
+            }
+            p.launches.push_back(hints);
+        }
+        if (moddiv_end > hints_end) {   // the modular divisions of the level, after its long divisions: a launch of their own
+            Launch hints{hints_end, moddiv_end, 0, 0};
+            hints.moddiv = 1;
+            for (uint32_t t = hints_end; t < moddiv_end; ++t) {
+                const Hint &h = p.hints[p.steps[t].cols_off];
+                for (uint32_t k : h.k)
+                    if (k) hints.rounds = std::max(hints.rounds, std::min(h.n * (k - 1) + 256, MODDIV_OPERAND_BITS));
+                const uint32_t kP = (uint32_t)(h.flags & HINT_MODULUS_LITERAL ? h.lit.size() / 4 : h.E.size());
+                hints.inv_rounds = std::max(hints.inv_rounds, 2 * std::min(h.n * (kP - 1) + 256, MODDIV_MODULUS_BITS));
             }
             p.launches.push_back(hints);
         }
@@ -707,7 +751,7 @@ struct Planner {
         for (const std::vector<uint32_t> *in : {&h.D, &h.E})
             for (uint32_t col : *in) lv = level[col] > lv ? level[col] : lv;
         ++lv;
-        Step s{0, (uint32_t)(nr + h.index), h.q[0], KIND_LONGDIV, lv};
+        Step s{0, (uint32_t)(nr + h.index), h.q[0], h.op == HINT_MODDIV ? KIND_MODDIV : KIND_LONGDIV, lv};
         s.cols_off = (uint32_t)p.hints.size();
         p.hints.push_back(h);
         p.steps.push_back(s);
@@ -1089,6 +1133,9 @@ inline bool schedule_any_order(Planner &st, uint64_t nr, uint64_t ncols, std::st
 // The declaration of pm_pk_set_hints: `desc` is a sequence of records
 //   HINT_LONGDIV, n, kq, kr, kD, kE, flags, kq quotient columns, kr remainder columns, kD dividend columns, then kE divisor columns
 //   -- or, with HINT_DIVISOR_LITERAL (flags bit 0), kE limb values of four words each (canonical integers below r)
+//   HINT_MODDIV, n, kz, kNp, kNm, kDp, kDm, kP, flags, kz output columns, kNp + kNm numerator columns, kDp + kDm denominator columns,
+//   then kP modulus columns -- or, with HINT_MODULUS_LITERAL (flags bit 0), kP limb values of four words each
+// in any mixture; both opcodes share the index h and the set of output columns.  Opcode 2 is reserved and refused like any unknown one.
 // -> the hints in `out` and an empty string, or what is refused, "hint h: " + the condition, and `out` empty.  `modulus`: r, four words.
 inline std::string decode_hints(const uint64_t *desc, size_t n_words, uint64_t ncols, const uint64_t *modulus, std::vector<Hint> &out) {
     out.clear();
@@ -1099,25 +1146,49 @@ inline std::string decode_hints(const uint64_t *desc, size_t n_words, uint64_t n
         const std::string here = "hint " + std::to_string(out.size()) + ": ";
         Hint h;
         h.index = (uint32_t)out.size();
-        if (desc[at] != HINT_LONGDIV) { why = here + "unknown opcode " + std::to_string(desc[at]); break; }
-        if (n_words - at < 7) { why = here + "the record is truncated"; break; }
-        const uint64_t n = desc[at + 1], kq = desc[at + 2], kr = desc[at + 3], kD = desc[at + 4], kE = desc[at + 5], flags = desc[at + 6];
+        if (desc[at] != HINT_LONGDIV && desc[at] != HINT_MODDIV) { why = here + "unknown opcode " + std::to_string(desc[at]); break; }
+        const bool moddiv = desc[at] == HINT_MODDIV;
+        const size_t head = moddiv ? 9 : 7;
+        if (n_words - at < head) { why = here + "the record is truncated"; break; }
+        const uint64_t n = desc[at + 1], flags = desc[at + head - 1];
         if (n < 1 || n > HINT_MAX_N) { why = here + "n = " + std::to_string(n) + " is outside 1..128"; break; }
-        if (kq < 1 || kq > HINT_MAX_KQ) { why = here + "kq = " + std::to_string(kq) + " is outside 1..32"; break; }
-        if (kr < 1 || kr > HINT_MAX_KR) { why = here + "kr = " + std::to_string(kr) + " is outside 1..16"; break; }
-        if (kD < 1 || kD > HINT_MAX_KD) { why = here + "kD = " + std::to_string(kD) + " is outside 1..32"; break; }
-        if (kE < 1 || kE > HINT_MAX_KE) { why = here + "kE = " + std::to_string(kE) + " is outside 1..16"; break; }
-        if (flags & ~HINT_DIVISOR_LITERAL) { why = here + "unknown flags " + std::to_string(flags); break; }
-        if (n * (kD - 1) >= HINT_D_BITS) { why = here + "n (kD - 1) = " + std::to_string(n * (kD - 1)) + " is 1024 or more"; break; }
-        if (n * (kE - 1) >= HINT_E_BITS) { why = here + "n (kE - 1) = " + std::to_string(n * (kE - 1)) + " is 512 or more"; break; }
-        const bool literal = (flags & HINT_DIVISOR_LITERAL) != 0;
-        const uint64_t need = 7 + kq + kr + kD + (literal ? 4 * kE : kE);
+        uint64_t counts[4], kE;     // the lengths of q, rem, D, E; kE: the divisor's or the modulus' limbs, in columns or literal
+        if (moddiv) {
+            const uint64_t kz = desc[at + 2], kP = desc[at + 7], *k = desc + at + 3;   // k: kNp, kNm, kDp, kDm
+            static const char *const names[4] = {"kNp", "kNm", "kDp", "kDm"};
+            if (kz < 1 || kz > MODDIV_MAX_KZ) { why = here + "kz = " + std::to_string(kz) + " is outside 1..16"; break; }
+            for (int i = 0; i < 4 && why.empty(); ++i)
+                if (k[i] > MODDIV_MAX_K || (i == 2 && k[i] < 1)) why = here + names[i] + " = " + std::to_string(k[i]) + " is outside " + (i == 2 ? "1" : "0") + "..32";
+            if (!why.empty()) break;
+            if (kP < 1 || kP > MODDIV_MAX_KP) { why = here + "kP = " + std::to_string(kP) + " is outside 1..16"; break; }
+            if (flags & ~HINT_MODULUS_LITERAL) { why = here + "unknown flags " + std::to_string(flags); break; }
+            for (int i = 0; i < 4 && why.empty(); ++i)
+                if (k[i] && n * (k[i] - 1) >= MODDIV_OPERAND_BITS) why = here + "n (" + names[i] + " - 1) = " + std::to_string(n * (k[i] - 1)) + " is 1024 or more";
+            if (!why.empty()) break;
+            if (n * (kP - 1) >= MODDIV_MODULUS_BITS) { why = here + "n (kP - 1) = " + std::to_string(n * (kP - 1)) + " is 512 or more"; break; }
+            h.op = (uint32_t)HINT_MODDIV;
+            for (int i = 0; i < 4; ++i) h.k[i] = (uint32_t)k[i];
+            counts[0] = kz, counts[1] = 0, counts[2] = k[0] + k[1] + k[2] + k[3], kE = kP;
+        } else {
+            const uint64_t kq = desc[at + 2], kr = desc[at + 3], kD = desc[at + 4];
+            kE = desc[at + 5];
+            if (kq < 1 || kq > HINT_MAX_KQ) { why = here + "kq = " + std::to_string(kq) + " is outside 1..32"; break; }
+            if (kr < 1 || kr > HINT_MAX_KR) { why = here + "kr = " + std::to_string(kr) + " is outside 1..16"; break; }
+            if (kD < 1 || kD > HINT_MAX_KD) { why = here + "kD = " + std::to_string(kD) + " is outside 1..32"; break; }
+            if (kE < 1 || kE > HINT_MAX_KE) { why = here + "kE = " + std::to_string(kE) + " is outside 1..16"; break; }
+            if (flags & ~HINT_DIVISOR_LITERAL) { why = here + "unknown flags " + std::to_string(flags); break; }
+            if (n * (kD - 1) >= HINT_D_BITS) { why = here + "n (kD - 1) = " + std::to_string(n * (kD - 1)) + " is 1024 or more"; break; }
+            if (n * (kE - 1) >= HINT_E_BITS) { why = here + "n (kE - 1) = " + std::to_string(n * (kE - 1)) + " is 512 or more"; break; }
+            counts[0] = kq, counts[1] = kr, counts[2] = kD;
+        }
+        const bool literal = (flags & HINT_DIVISOR_LITERAL) != 0;   // HINT_MODULUS_LITERAL is the same bit
+        counts[3] = literal ? 0 : kE;
+        const uint64_t need = head + counts[0] + counts[1] + counts[2] + (literal ? 4 * kE : kE);
         if (n_words - at < need) { why = here + "the record is truncated"; break; }
         h.n = (uint32_t)n;
         h.flags = (uint32_t)flags;
-        const uint64_t *w = desc + at + 7;
+        const uint64_t *w = desc + at + head;
         std::vector<uint32_t> *lists[4] = {&h.q, &h.rem, &h.D, &h.E};
-        const uint64_t counts[4] = {kq, kr, kD, literal ? 0 : kE};
         for (int l = 0; l < 4 && why.empty(); ++l)
             for (uint64_t i = 0; i < counts[l] && why.empty(); ++i, ++w) {
                 if (*w >= ncols) why = here + "column " + std::to_string(*w) + " is not below m0 + mw = " + std::to_string(ncols);

@@ -101,6 +101,10 @@ pub const PM_ASSIGNMENT_SOLVE: i32 = 2;
 pub const PM_KEY_HINTS: i32 = 1024;
 pub const PM_HINT_LONGDIV: u64 = 1;
 pub const PM_HINT_DIVISOR_LITERAL: u64 = 1;
+// pm_hint_op_modular / pm_hint_moddiv_flags: the opcode of a declared modular division (2 is reserved) and the flag that makes its
+// modulus a literal
+pub const PM_HINT_MODDIV: u64 = 3;
+pub const PM_HINT_MODULUS_LITERAL: u64 = 1;
 // the three markers of PM_ASSIGNMENT_SOLVE (little-endian words of one Fr, all >= r on both curves): unknown; unknown, and the Euclidean
 // quotient of its division row; unknown, and the indicator of its guard row
 pub const PM_UNKNOWN_WORDS: [u64; 4] = [u64::MAX, u64::MAX, u64::MAX, u64::MAX];

@@ -680,6 +680,56 @@ impl<F> Csr<F> {
     }
 }
 
+/// The divisor of a long division or the modulus of a modular division in a [`Hint`]: CSR columns, or literal limbs of four words.
+pub enum HintLimbs<'a> {
+    Columns(&'a [u64]),
+    Literal(&'a [[u64; 4]]),
+}
+
+/// One record of the declaration that [`GpuKey::set_hints`] takes, as the header states it.  Columns are CSR columns (0: the
+/// constant one, then the instance, then the witness); limbs have `n` bits.
+pub enum Hint<'a> {
+    /// `PM_HINT_LONGDIV`: `q` and `rem` are the limbs of `floor(D / E)` and `D mod E`.
+    LongDiv { n: u64, q: &'a [u64], rem: &'a [u64], dividend: &'a [u64], divisor: HintLimbs<'a> },
+    /// `PM_HINT_MODDIV`: `z` are the limbs of the `Z` in `[0, P)` with `Z (D+ - D-) = N+ - N- (mod P)`; both numerator lists empty
+    /// mean `N = 1`, the modular inverse.
+    ModDiv { n: u64, z: &'a [u64], n_plus: &'a [u64], n_minus: &'a [u64], d_plus: &'a [u64], d_minus: &'a [u64], modulus: HintLimbs<'a> },
+}
+
+impl Hint<'_> {
+    /// The words of a declaration: the records of `hints` one after the other (what [`GpuKey::set_hints`] takes as `desc`).
+    pub fn encode(hints: &[Hint]) -> Vec<u64> {
+        let mut words = Vec::new();
+        for hint in hints {
+            let (lists, last): (Vec<&[u64]>, &HintLimbs) = match hint {
+                Hint::LongDiv { n, q, rem, dividend, divisor } => {
+                    words.extend_from_slice(&[sys::PM_HINT_LONGDIV, *n, q.len() as u64, rem.len() as u64, dividend.len() as u64]);
+                    (vec![*q, *rem, *dividend], divisor)
+                }
+                Hint::ModDiv { n, z, n_plus, n_minus, d_plus, d_minus, modulus } => {
+                    words.extend_from_slice(&[sys::PM_HINT_MODDIV, *n, z.len() as u64, n_plus.len() as u64, n_minus.len() as u64, d_plus.len() as u64,
+                                              d_minus.len() as u64]);
+                    (vec![*z, *n_plus, *n_minus, *d_plus, *d_minus], modulus)
+                }
+            };
+            // PM_HINT_DIVISOR_LITERAL and PM_HINT_MODULUS_LITERAL are the same bit of the record's last head word
+            match last {
+                HintLimbs::Columns(cols) => {
+                    words.extend_from_slice(&[cols.len() as u64, 0]);
+                    lists.iter().for_each(|l| words.extend_from_slice(l));
+                    words.extend_from_slice(cols);
+                }
+                HintLimbs::Literal(limbs) => {
+                    words.extend_from_slice(&[limbs.len() as u64, sys::PM_HINT_MODULUS_LITERAL]);
+                    lists.iter().for_each(|l| words.extend_from_slice(l));
+                    limbs.iter().for_each(|l| words.extend_from_slice(l));
+                }
+            }
+        }
+        words
+    }
+}
+
 /// A proving key resident in HBM (`pm_pk`): bases in the internal radix, window tables, CSR matrices.  Immutable after
 /// creation; contexts on the same device may share it.
 pub struct GpuKey {
@@ -1027,7 +1077,8 @@ impl GpuKey {
 
     /// Declare the witness solver's hints of this key (`pm_pk_load_bytes` with `PM_KEY_HINTS`: no key is loaded, this one keeps its
     /// address) -- `desc` is the sequence of records the header states (`PM_HINT_LONGDIV, n, kq, kr, kD, kE, flags`, then the columns
-    /// or literal limbs); an empty slice clears the declaration.  Taking `&mut self` keeps safe code from racing the call with calls
+    /// or literal limbs; `PM_HINT_MODDIV, n, kz, kNp, kNm, kDp, kDm, kP, flags` for a modular division; [`Hint::encode`] writes
+    /// both); an empty slice clears the declaration.  Taking `&mut self` keeps safe code from racing the call with calls
     /// that use the key.
     pub fn set_hints(&mut self, ctx: &mut Context, desc: &[u64]) -> Result<(), HipError> {
         let ptr = if desc.is_empty() { core::ptr::null() } else { desc.as_ptr() as *const u8 };

@@ -36,6 +36,12 @@ inverse, then the sums; no marker: the rows determine the product's limbs), and
 on one that multiplies in a foreign field (per multiplication a linear block, one declared long division -- the key's hints are set
 from the circuit's hints() -- 2 LIMBS decompositions of N bits, the limbs of q p and a chain of carries; route (a) synthesises q and
 rem with Python's divmod).  UNMEASURED: no run of it is recorded.
+  python tools/prove_bench.py --circuit moddiv --batch 256 --reps 5 --solve      LimbModDiv, 16 divisions modulo secp256k1's prime on
+                                                                                 4 limbs of 64 bits; moddiv:COUNT:N:LIMBS for others
+  python tools/prove_bench.py --circuit ecadd --batch 256 --reps 5 --solve       EcAddChain, 4 affine additions on secp256k1 from
+                                                                                 (k + 5) G and 2 G; ecadd:STEPS for others
+on circuits that divide in a foreign field (a declared modular division per quotient or slope, then the product's block and a
+declared long division per reduction, with their decompositions and carries; route (a) synthesises with Python's pow and divmod).
   python tools/prove_bench.py --circuit mimc322 --batch 256 --reps 5 --solve --reorder reverse     or --reorder SEED
 runs either --solve comparison on the same circuit with its constraint rows stored in another order (circuits.Reordered: reversed, or
 shuffled by SEED; a matchcount gadget moves as a block so that every opener stays before its closer).  Route (b) then goes through the
@@ -53,7 +59,7 @@ from polymath_amd import circuits as PC
 from polymath_amd.polymath import Polymath
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants), bench:NC (BenchCircuit, NC constraints), arx[:WIDTH:ROUNDS] (ArxDemo), matchcount[:N:FORM] (MatchCount), divrem[:N:BITS] (DivRem), tablewalk[:WIDTH:STEPS] (TableWalk), decompress[:POINTS] (EdwardsDecompress), limbproduct[:COUNT:LIMBS] (LimbProduct) or modmul[:COUNT:N:LIMBS] (LimbModMul)")
+ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants), bench:NC (BenchCircuit, NC constraints), arx[:WIDTH:ROUNDS] (ArxDemo), matchcount[:N:FORM] (MatchCount), divrem[:N:BITS] (DivRem), tablewalk[:WIDTH:STEPS] (TableWalk), decompress[:POINTS] (EdwardsDecompress), limbproduct[:COUNT:LIMBS] (LimbProduct), modmul[:COUNT:N:LIMBS] (LimbModMul), moddiv[:COUNT:N:LIMBS] (LimbModDiv) or ecadd[:STEPS] (EcAddChain)")
 ap.add_argument("--batch", type=int, default=16)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--curve", default="bls12_381")
@@ -63,8 +69,8 @@ ap.add_argument("--glue", choices=("host", "device"), default="host", help="devi
 ap.add_argument("--solve", action="store_true", help="host-synthesised assignments against partial assignments solved on the GPU")
 ap.add_argument("--reorder", default=None, metavar="reverse|SEED", help="with --solve: the circuit's rows stored reversed or shuffled by SEED (unmeasured)")
 a = ap.parse_args()
-if a.solve and not a.circuit.startswith(("mimc", "arx", "matchcount", "divrem", "tablewalk", "decompress", "limbproduct", "modmul")):
-    ap.error("--solve needs a mimcK, an arx, a matchcount, a divrem, a tablewalk, a decompress, a limbproduct or a modmul circuit")
+if a.solve and not a.circuit.startswith(("mimc", "arx", "matchcount", "divrem", "tablewalk", "decompress", "limbproduct", "modmul", "moddiv", "ecadd")):
+    ap.error("--solve needs a mimcK, an arx, a matchcount, a divrem, a tablewalk, a decompress, a limbproduct, a modmul, a moddiv or an ecadd circuit")
 if a.reorder is not None and not a.solve:
     ap.error("--reorder goes with --solve")
 pm = Polymath(a.curve, a.transcript, device=0)
@@ -116,6 +122,28 @@ elif a.circuit.startswith("modmul"):
     make = lambda: PC.LimbModMul(PC.modmul_pairs(foreign, n_muls, g.next_u64()), foreign, limb_bits, n_limbs)
     again = lambda c: PC.LimbModMul(c.pairs, c.modulus, c.n, c.limbs, c.decompose)
     partial_of = lambda c: c.partial(r)
+elif a.circuit.startswith("moddiv"):
+    n_divs, limb_bits, n_limbs = (int(v) for v in a.circuit.split(":")[1:4]) if ":" in a.circuit else (16, 64, 4)
+    foreign = (1 << (limb_bits * n_limbs)) - 2 ** 32 - 977 if limb_bits * n_limbs == 256 else (1 << (limb_bits * n_limbs - 3)) - 1     # as for modmul; need not be a prime
+    make = lambda: PC.LimbModDiv(PC.moddiv_cases(foreign, n_divs, g.next_u64()), foreign, limb_bits, n_limbs)
+    again = lambda c: PC.LimbModDiv(c.cases, c.modulus, c.n, c.limbs, c.decompose, c.operand_bits)
+    partial_of = lambda c: c.partial(r)
+elif a.circuit.startswith("ecadd"):
+    ec_steps = int(a.circuit.split(":")[1]) if ":" in a.circuit else 4
+    secp = 2 ** 256 - 2 ** 32 - 977
+    G1 = (0x79BE667EF9DCBBAC55A06295CE870B07029BFCDB2DCE28D959F2815B16F81798, 0x483ADA7726A3C4655DA4FBFC0E1108A8FD17B448A68554199C47D08FFB10D4B8)
+
+    def ec_add(p1, p2):      # affine addition or doubling on y^2 = x^3 + 7
+        (x1, y1), (x2, y2) = p1, p2
+        lam = (3 * x1 * x1) * pow(2 * y1, -1, secp) % secp if p1 == p2 else (y2 - y1) * pow(x2 - x1, -1, secp) % secp
+        x3 = (lam * lam - x1 - x2) % secp
+        return x3, (lam * (x1 - x3) - y1) % secp
+    ec_points = [G1]
+    for _ in range(40):
+        ec_points.append(ec_add(ec_points[-1], G1))
+    make = lambda: PC.EcAddChain(ec_points[4 + g.next_u64() % 32], ec_points[1], secp, 64, 4, ec_steps)      # R_t = (k + 5 + 2 t) G, k < 32, is never +-2 G: no chord without a slope
+    again = lambda c: PC.EcAddChain(c.point, c.addend, c.modulus, c.n, c.limbs, c.steps, c.decompose)
+    partial_of = lambda c: c.partial(r)
 else:
     nc = int(a.circuit.split(":", 1)[1])
     make = lambda: PC.BenchCircuit(g.fr(r), g.fr(r), 10, nc)
@@ -130,8 +158,8 @@ circuits = [make() for _ in range(distinct)]
 t0 = time.time()
 pk = pm.setup(stored(circuits[0]), g.fr(r), g.fr(r))
 setup_s = time.time() - t0
-if a.circuit.startswith("modmul"):
-    pm.set_hints(pk, circuits[0].hints(2))       # the long divisions are part of the circuit: declared once, with the key
+if a.circuit.startswith(("modmul", "moddiv", "ecadd")):
+    pm.set_hints(pk, circuits[0].hints(2))       # the long and the modular divisions are part of the circuit: declared once, with the key
 rows = []
 for c in circuits:
     _, inst, wit = pm._synthesize(stored(c))

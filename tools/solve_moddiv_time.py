@@ -1,0 +1,56 @@
+"""Times the solving call on one level of declared modular divisions (profiles/witness_solve.txt, section 7): LimbModDiv, COUNT
+divisions modulo secp256k1's prime on 4 limbs of 64 bits without the decompositions -- one level of COUNT modular hints, then one
+block launch, ordinary rows, one level of COUNT long divisions and chain launches -- BATCH assignments a call, through
+Polymath.check_batch's native call (pm_r1cs_check_batch, max_rows = 0) with PM_ASSIGNMENT_SOLVE on host limbs: one call that plans,
+then REPS timed ones in one process.  The completed assignment of one row is compared with native().
+
+    python tools/solve_moddiv_time.py [--curve bls12_381] [--count 256] [--batch 256] [--reps 7]
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/solve_moddiv_time.py      (k_solve_moddiv alone: a run of its own)
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch        # noqa: F401  before the library: torch brings its own HIP runtime
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from polymath_amd import circuits as PC  # noqa: E402
+from polymath_amd.polymath import Polymath  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--curve", default="bls12_381")
+ap.add_argument("--count", type=int, default=256)
+ap.add_argument("--batch", type=int, default=256)
+ap.add_argument("--reps", type=int, default=7)
+a = ap.parse_args()
+SECP = 2 ** 256 - 2 ** 32 - 977
+pm = Polymath(a.curve, "merlin", device=0)
+r = pm.field.r
+make = lambda seed: PC.LimbModDiv(PC.moddiv_cases(SECP, a.count, seed), SECP, 64, 4, decompose=False)
+distinct = [make(21000 + i) for i in range(min(a.batch, 8))]
+pk = pm.setup(distinct[0], 123, 456)
+pm.set_hints(pk, distinct[0].hints(2))
+partial = distinct[0].partial(r)
+marks = np.array([v is None for v in partial[0] + partial[1]], dtype=bool)
+full = [np.concatenate([pm.field.fr_limbs(inst), pm.field.fr_limbs(wit)]).reshape(-1, 4) for inst, wit in (c.native(r) for c in distinct)]
+want = np.stack([full[i % len(full)] for i in range(a.batch)])
+rows = want.copy()
+rows[:, marks] = 0xFFFFFFFFFFFFFFFF
+xs, ws = np.ascontiguousarray(rows[:, :2]), np.ascontiguousarray(rows[:, 2:])
+wall, kernels = [], []
+for rep in range(a.reps + 1):
+    t0 = time.perf_counter()
+    rc, n_bad, _, _ = pk.r1cs_check_batch(xs, ws, 0, solve=True)
+    dt = time.perf_counter() - t0
+    assert rc == 0 and not n_bad.any(), pm.ctx.last_error()
+    if rep == 0:
+        print("first call (plan): %.1f ms" % (1e3 * dt))
+        assert np.array_equal(pk.solved_assignments(a.batch, ws.shape[1])[a.batch // 2], want[a.batch // 2])
+    else:
+        wall.append(1e3 * dt)
+        kernels.append(pm.ctx.timings()["ntt"])      # slot 1: the solve kernels of the call
+spread = lambda v: "%.3f [%.3f .. %.3f]" % (sorted(v)[len(v) // 2], min(v), max(v))
+print("%s, %d hints x %d assignments, %d calls: cached call, wall ms %s; solve kernels, slot 1 ms %s" % (a.curve, a.count, a.batch, a.reps, spread(wall), spread(kernels)))
+pk.free()
