@@ -262,12 +262,27 @@ int pm_pk_export_bases(pm_ctx *ctx, const pm_pk *pk, int which, size_t offset, s
  * kDp outside 1..32; kNp, kNm or kDm above 32; n (k - 1) >= 1024 for an operand list; n (kP - 1) >= 512.  Records of both opcodes
  * may be mixed in one declaration; they share the index h, and no output may be named by two hints of either opcode.
  * Still out of scope: even moduli, operands beyond 1024 bits, the slope of a doubling as one hint (its numerator is a product), gcd,
- * sorting. */
+ * sorting.  Of the long-division record's list, dividends beyond 1024 bits (RSA-2048) now have a record of their own in the same stream
+ * (opcode 5; opcodes 2 and 4 are refused as unknown):
+ *     PM_HINT_LONGDIV_WIDE, n, kq, kr, kD, kE, flags,
+ *       kq quotient columns, kr remainder columns, kD dividend columns, then kE divisor columns
+ *       -- or, with PM_HINT_DIVISOR_LITERAL (flags bit 0, the literal flag of opcode 1), kE limb values of four words each
+ * It has the shape and the meaning of PM_HINT_LONGDIV: the step stores the kq n-bit limbs of floor(D / E) and the kr n-bit limbs of
+ * D mod E, limbs need not be normalised.  An RSA-2048 modular multiplication divides a dividend of about 4200 bits by a 2048-bit
+ * modulus: 32 limbs of 64 bits, or the 17 limbs of 121 bits of the zk-email circuits.  Refused like the long-division record, with the
+ * same wording for columns, outputs, literal limbs and sharded keys: unknown flags; a truncated record; n outside 1..128; kD > 128,
+ * kE > 64, kq > 128, kr > 64, or any of them 0; n (kD - 1) >= 8192 or n (kE - 1) >= 4096.  Records of all three opcodes may be mixed
+ * in one declaration; they share the index h, and no output may be named by two hints of any opcode.  PM_HINT_LONGDIV itself is not
+ * widened: kD = 33 under opcode 1 is refused as before.
+ * Still out of scope: modular division at these widths (PM_HINT_MODDIV keeps 1024 / 512 bits), even moduli, linear blocks beyond 64
+ * unknowns (RSA-4096 at 64-bit limbs; 3072-bit moduli at 96-bit limbs fit this record), hints on sharded keys, per-assignment
+ * declarations, gcd, sorting. */
 typedef enum pm_hint_op { PM_HINT_LONGDIV = 1 } pm_hint_op;
 typedef enum pm_hint_flags { PM_HINT_DIVISOR_LITERAL = 1 } pm_hint_flags;
 typedef enum pm_key_hints { PM_KEY_HINTS = 1024 } pm_key_hints;
 typedef enum pm_hint_op_modular { PM_HINT_MODDIV = 3 } pm_hint_op_modular;
 typedef enum pm_hint_moddiv_flags { PM_HINT_MODULUS_LITERAL = 1 } pm_hint_moddiv_flags;
+typedef enum pm_hint_op_wide { PM_HINT_LONGDIV_WIDE = 5 } pm_hint_op_wide;
 void pm_pk_free(pm_pk *pk);
 
 /* ---- proving keys as bytes: ProvingKey::serialize_compressed (data_structures.rs:56-73), decoded on the device ---------
@@ -566,6 +581,15 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  *   Z >= 2^(n kz); the root-cause rule applies to that word as to a long division's.  Without an active modular hint every plan,
  *   message and word is what it is without this rule.  Not handled: even moduli, operands beyond 1024 bits, the slope of a doubling
  *   as one hint, gcd, sorting.
+ *   Declared hints: wide long division.  Dividends beyond 1024 bits have their own record, PM_HINT_LONGDIV_WIDE (pm_pk_set_hints above
+ *   states it): the quotient and remainder limbs of a reduction modulo an RSA-2048 modulus, which range checks fix and no row
+ *   determines.  The rules are the long-division rules unchanged -- ACTIVE / INERT / mixed-marker, HINT-OWNED outputs, waiting on
+ *   inputs, the never-ready refusal -- and the hint is ONE step at 1 + the largest level of its inputs, after the modular divisions of
+ *   that level, computed by one wave.  The assignment is STUCK at the word nr + h, with zero in every output, where E = 0,
+ *   D >= 2^8192, E >= 2^4096, q >= 2^(n kq) or rem >= 2^(n kr); the root-cause rule applies to that word as to a long division's.
+ *   Without an active wide hint every plan, message and word is what it is without this rule.  Not handled: modular division at these
+ *   widths, even moduli, linear blocks beyond 64 unknowns (RSA-4096 at 64-bit limbs), hints on sharded keys, per-assignment
+ *   declarations, gcd, sorting.
  *   PM_ERR_INVALID_ARG, pm_last_error naming the row or column, nothing computed and no output written: an unsolvable row, a marked
  *   column that no row determines, a marker at column 0, a sharded key, and -- in a batch -- an assignment that does not mark the
  *   columns assignment 0 marks, or marks one with the other marker (any two of the four markers differ; the first differing (assignment, column) is named; a kernel

@@ -66,6 +66,9 @@ HINT_LIMITS = {"n": 128, "kq": 32, "kr": 16, "kD": 32, "kE": 16}
 # the second opcode, modular division Z = (N+ - N-) / (D+ - D-) mod P (2 is reserved), its one flag and the limits of its record
 HINT_MODDIV, HINT_MODULUS_LITERAL = 3, 1
 MODDIV_LIMITS = {"n": 128, "kz": 16, "kNp": 32, "kNm": 32, "kDp": 32, "kDm": 32, "kP": 16}
+# the third opcode, the wide long division (4 is refused as unknown): opcode 1's record and flag under limits of its own
+HINT_LONGDIV_WIDE = 5
+WIDE_LIMITS = {"n": 128, "kq": 128, "kr": 64, "kD": 128, "kE": 64}
 NOT_STUCK = 0xFFFFFFFFFFFFFFFF                # first word of a tap-9 record of an assignment that completed
 TIMING_SLOTS = ["witness_map", "ntt", "poly", "msm_sort", "msm_accumulate", "msm_reduce", "msm_total", "phase"]
 
@@ -228,10 +231,10 @@ def encode_hints(hints):
     (the divisor's limbs as Python integers)} or a tuple (n, q, rem, D, E) / (n, q, rem, D, None, literal); q, rem, D, E are lists of
     CSR columns (0: the constant one, then the instance, then the witness).  A modular division is a dict with "op": "moddiv":
     {"op", "n", "z", "Dp", "P" (modulus columns) or "literal" (the modulus' limbs), and optionally "Np", "Nm", "Dm"}; without "Np" and
-    "Nm" the numerator is 1.  -> np.uint64[n_words]"""
+    "Nm" the numerator is 1.  A wide long division is the long division's dict with "op": "longdiv_wide".  -> np.uint64[n_words]"""
     words = []
     for hint in hints:
-        if isinstance(hint, dict) and hint.get("op", "longdiv") != "longdiv":
+        if isinstance(hint, dict) and hint.get("op", "longdiv") not in ("longdiv", "longdiv_wide"):
             if hint["op"] != "moddiv":
                 raise ValueError("unknown hint op %r" % (hint["op"],))
             P, literal = hint.get("P"), hint.get("literal")
@@ -256,7 +259,8 @@ def encode_hints(hints):
         if (E is None) == (literal is None):
             raise ValueError("a hint has divisor columns E or a literal divisor, not both and not neither")
         divisor = list(E) if literal is None else list(literal)
-        words += [HINT_LONGDIV, int(n), len(q), len(rem), len(D), len(divisor), 0 if literal is None else HINT_DIVISOR_LITERAL]
+        wide = isinstance(hint, dict) and hint.get("op") == "longdiv_wide"
+        words += [HINT_LONGDIV_WIDE if wide else HINT_LONGDIV, int(n), len(q), len(rem), len(D), len(divisor), 0 if literal is None else HINT_DIVISOR_LITERAL]
         words += [int(c) for c in list(q) + list(rem) + list(D)]
         if literal is None:
             words += [int(c) for c in divisor]
@@ -270,7 +274,8 @@ def encode_hints(hints):
 
 def decode_hints(words):
     """encode_hints backwards: -> a list of dicts (the words are trusted to be well-formed: the library is what refuses).  A modular
-    division comes back with "op": "moddiv" and all of "Np", "Nm", "Dp", "Dm" (empty lists where the record has none)"""
+    division comes back with "op": "moddiv" and all of "Np", "Nm", "Dp", "Dm" (empty lists where the record has none), a wide long
+    division with "op": "longdiv_wide" """
     words, out, at = [int(v) for v in words], [], 0
     while at < len(words):
         if words[at] == HINT_MODDIV:
@@ -289,11 +294,11 @@ def decode_hints(words):
             out.append(hint)
             continue
         op, n, kq, kr, kD, kE, flags = words[at:at + 7]
-        if op != HINT_LONGDIV:
+        if op not in (HINT_LONGDIV, HINT_LONGDIV_WIDE):
             raise ValueError("unknown opcode %d" % op)
         at += 7
         take = lambda k: words[at:at + k]
-        hint = {"n": n, "q": take(kq)}
+        hint = {"op": "longdiv_wide", "n": n, "q": take(kq)} if op == HINT_LONGDIV_WIDE else {"n": n, "q": take(kq)}
         at += kq
         hint["rem"] = take(kr)
         at += kr

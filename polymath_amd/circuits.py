@@ -848,6 +848,8 @@ class _PartialModMul(_Partial):
             hint["literal"] = int_limbs(self.modulus, self.n, l)
         else:
             hint["E"] = list(p_cols)
+        if getattr(self, "wide", False):          # the wide long division (opcode 5): the same lists, first in the dict
+            hint = dict([("op", "longdiv_wide")] + list(hint.items()))
         return hint
 
 
@@ -858,11 +860,13 @@ class LimbModMul(_PartialModMul):
     the outputs of the declared hint (hints()), and everything else follows by ordinary rows and decompositions.  l max(a_i) max(b_i)
     must stay below r (modmul_values asserts it): the hint's dividend is the integer of the product limbs."""
 
-    def __init__(self, pairs, modulus, n, limbs, decompose=True):
+    def __init__(self, pairs, modulus, n, limbs, decompose=True, wide=False):
         self.pairs, self.modulus, self.n, self.limbs, self.decompose = [(int(a), int(b)) for a, b in pairs], int(modulus), n, limbs, decompose
+        self.wide = wide
 
     def hints(self, m0=2):
-        """the declaration for Polymath.set_hints / api.encode_hints: one long division per pair, with the modulus as a literal"""
+        """the declaration for Polymath.set_hints / api.encode_hints: one long division per pair, with the modulus as a literal;
+        wide: the wide long division (RSA-2048 sizes)"""
         per = 2 * self.limbs + self._width() + 1
         return [self._hint(m0, i * per + 2 * self.limbs) for i in range(len(self.pairs))]
 
@@ -904,9 +908,9 @@ class ModMulChain(_PartialModMul):
     _PartialModMul, whose rem is x_{t+1}, and  (sum rem_i) * 1 = s_t ; the public input is sum s_t.  Blocks, hints, decompositions and
     carry rows alternate over 4 levels a step."""
 
-    def __init__(self, x0, b, modulus, n, limbs, steps, witness_modulus=False, decompose=True):
+    def __init__(self, x0, b, modulus, n, limbs, steps, witness_modulus=False, decompose=True, wide=False):
         self.x0, self.b, self.modulus, self.n, self.limbs, self.steps = int(x0), int(b), int(modulus), n, limbs, steps
-        self.witness_modulus, self.decompose = witness_modulus, decompose
+        self.witness_modulus, self.decompose, self.wide = witness_modulus, decompose, wide
 
     def hints(self, m0=2):
         """the declaration for Polymath.set_hints / api.encode_hints: one long division per step, its divisor the literal modulus or
@@ -946,6 +950,202 @@ class ModMulChain(_PartialModMul):
             total += sum(rem)
             x_v = rem
         return [1, total % r], witness
+
+
+class RsaVerify(_PartialModMul):
+    """The arithmetic of an RSA signature check with the public exponent 2^squarings + 1 (65537 by default) on l limbs of n bits:
+    x_0 = s given, x_{t+1} = x_t^2 mod N `squarings` times, then y = x_last s mod N; every step is the multiplication of
+    _PartialModMul (a squaring passes the same limbs twice) and the public input is the sum of y's limbs.  N is a literal or --
+    witness_modulus -- l more given witnesses.  The dividends have about twice the modulus' bits, so hints() declares the WIDE long
+    division.  Both RSA-2048 shapes keep every no-carry product limb below r on both curves: 32 limbs of 64 bits (32 * 2^128) and the
+    zk-email circuits' 17 limbs of 121 bits (17 * 2^242 < 2^247)."""
+
+    wide = True
+
+    def __init__(self, signature, modulus, n, limbs, squarings=16, witness_modulus=False, decompose=False):
+        self.signature, self.modulus, self.n, self.limbs, self.squarings = int(signature), int(modulus), n, limbs, squarings
+        self.witness_modulus, self.decompose = witness_modulus, decompose
+
+    def hints(self, m0=2):
+        """one wide long division per multiplication, its divisor the literal modulus or the modulus' witness columns"""
+        l = self.limbs
+        head = 2 * l if self.witness_modulus else l
+        p_cols = range(m0 + l, m0 + 2 * l) if self.witness_modulus else None
+        return [self._hint(m0, head + t * self._width(), p_cols) for t in range(self.squarings + 1)]
+
+    def generate_constraints(self, cs):
+        self._chosen = []
+        one, n, l = ConstraintSystem.ONE, self.n, self.limbs
+        s_v, p_v = int_limbs(self.signature, n, l), int_limbs(self.modulus, n, l)
+        s = [self._given(cs, v) for v in s_v]
+        p = [self._given(cs, v) for v in p_v] if self.witness_modulus else None
+        x, x_v = s, s_v
+        for _ in range(self.squarings):
+            x, x_v = self._modmul(cs, x, x_v, x, x_v, p_v, p)
+        y, y_v = self._modmul(cs, x, x_v, s, s_v, p_v, p)
+        out = cs.new_input_variable(sum(y_v))
+        cs.enforce_constraint([(1, v) for v in y], [(1, one)], [(1, out)])
+
+    def native(self, r):
+        """-> (instance, witness) on Python integers, without generating a row; y = s^(2^squarings + 1) mod N by Python's pow"""
+        n, l = self.n, self.limbs
+        s_v, p_v = int_limbs(self.signature, n, l), int_limbs(self.modulus, n, l)
+        witness, x_v = s_v + (p_v if self.witness_modulus else []), s_v
+        for t in range(self.squarings + 1):
+            P, q, rem, qp, carries = modmul_values(x_v, x_v if t < self.squarings else s_v, p_v, n, r)
+            bits = [(v >> i) & 1 for v in q + rem for i in range(n)] if self.decompose else []
+            witness += P + q + rem + bits + qp + carries
+            x_v = rem
+        assert limbs_int(x_v, n) == pow(self.signature, 2 ** self.squarings + 1, self.modulus)
+        return [1, sum(x_v) % r], witness
+
+
+class LimbDivision(_Partial):
+    """The wide long division's test rig: per case (D limbs, E limbs) -- given as they are: a limb may be anything below r, limbs
+    need not be normalised -- kq quotient limbs and kr remainder limbs of n bits that ONLY the declared hint determines (hints():
+    opcode 5, or opcode 1 with wide=False), and one ordinary row  (sum q_i + sum rem_i) * 1 = s ; the public input is sum s.
+    divisor="literal" puts the divisor's limbs into the hint instead of into witness columns.  No row checks the division: the rig
+    is for comparing the solver with Python's divmod, which native() is.  native() refuses a case that the solver would report stuck
+    (E = 0, D >= 2^8192, E >= 2^4096, a quotient or remainder that does not fit) unless stuck=True, and then stores zeros."""
+
+    def __init__(self, cases, n, kq, kr, divisor="columns", wide=True, stuck=False):
+        assert divisor in ("columns", "literal")
+        self.cases = [([int(v) for v in D], [int(v) for v in E]) for D, E in cases]
+        self.n, self.kq, self.kr, self.divisor, self.wide, self.stuck = n, kq, kr, divisor, wide, stuck
+
+    def _outputs(self, D, E):
+        """-> (q limbs, rem limbs, stuck)"""
+        n, kq, kr = self.n, self.kq, self.kr
+        d_bits, e_bits = (8192, 4096) if self.wide else (1024, 512)
+        Dv, Ev = limbs_int(D, n), limbs_int(E, n)
+        bad = Ev == 0 or Dv >= 1 << d_bits or Ev >= 1 << e_bits
+        if not bad:
+            q, rem = divmod(Dv, Ev)
+            bad = q >= 1 << (n * kq) or rem >= 1 << (n * kr)
+        if bad:
+            assert self.stuck, "the case is stuck: D = %d bits, E = %d bits" % (Dv.bit_length(), Ev.bit_length())
+            return [0] * kq, [0] * kr, True
+        return int_limbs(q, n, kq), int_limbs(rem, n, kr), False
+
+    def stuck_cases(self):
+        """which cases the solver reports stuck"""
+        return [self._outputs(D, E)[2] for D, E in self.cases]
+
+    def _columns(self, m0=2):
+        """per case the CSR columns (D, E, q, rem); E is empty for a literal divisor"""
+        at, out = m0, []
+        for D, E in self.cases:
+            kE = len(E) if self.divisor == "columns" else 0
+            d = list(range(at, at + len(D)))
+            e = list(range(at + len(D), at + len(D) + kE))
+            q = list(range(e[-1] + 1 if e else d[-1] + 1, (e[-1] + 1 if e else d[-1] + 1) + self.kq))
+            rem = list(range(q[-1] + 1, q[-1] + 1 + self.kr))
+            out.append((d, e, q, rem))
+            at = rem[-1] + 2          # and s
+        return out
+
+    def hints(self, m0=2):
+        out = []
+        for (D, E), (d, e, q, rem) in zip(self.cases, self._columns(m0)):
+            hint = {"op": "longdiv_wide"} if self.wide else {}
+            hint.update({"n": self.n, "q": q, "rem": rem, "D": d})
+            if self.divisor == "columns":
+                hint["E"] = e
+            else:
+                hint["literal"] = list(E)
+            out.append(hint)
+        return out
+
+    def generate_constraints(self, cs):
+        self._chosen = []
+        one = ConstraintSystem.ONE
+        total, total_v = [], 0
+        for D, E in self.cases:
+            q_v, rem_v, _ = self._outputs(D, E)
+            for v in D + (E if self.divisor == "columns" else []):
+                self._given(cs, v)
+            outs = [cs.new_witness_variable(v) for v in q_v + rem_v]
+            s = cs.new_witness_variable(sum(q_v + rem_v) % cs.r)
+            cs.enforce_constraint([(1, v) for v in outs], [(1, one)], [(1, s)])
+            total.append((1, s))
+            total_v += sum(q_v + rem_v)
+        out = cs.new_input_variable(total_v % cs.r)
+        cs.enforce_constraint(total, [(1, one)], [(1, out)])
+
+    def native(self, r):
+        """-> (instance, witness) on Python integers: Python's divmod"""
+        witness, total = [], 0
+        for D, E in self.cases:
+            q_v, rem_v, _ = self._outputs(D, E)
+            witness += D + (E if self.divisor == "columns" else []) + q_v + rem_v + [sum(q_v + rem_v) % r]
+            total += sum(q_v + rem_v)
+        return [1, total % r], witness
+
+
+def rsa_modulus(bits=2048, seed=SPLITMIX_SEED):
+    """an odd integer of exactly `bits` bits drawn from SplitMix64(seed) (no prime product: the arithmetic does not ask for one) and a
+    signature below it"""
+    g = SplitMix64(seed)
+    draw = lambda: sum(g.next_u64() << (64 * i) for i in range(-(-bits // 64))) & ((1 << bits) - 1)
+    modulus = draw() | 1 | 1 << (bits - 1)
+    return modulus, draw() % modulus
+
+
+def division_cases(n, kD, kE, r, seed=SPLITMIX_SEED):
+    """The operand families of the wide long division for LimbDivision(cases, n, kD, kE), each where it fits the shape: -> a list of
+    (name, D limbs, E limbs), none of them stuck.  Values are cut into normalised limbs unless the name says otherwise.  The word
+    counts m are those of the divisor in base 2^32: lane and half-wave edges of the kernel.  The ADD-BACK family
+    E = 2^(32 m - 1) + 1, D = ((E - 1) << 32 k) | 3 makes algorithm D's estimate one too large, the SATURATING family
+    E = (0xFFFFFFFF << 32 (m - 1)) | 5, D = (E << 32) - 1 makes its first estimate reach 2^32: random operands do neither."""
+    g = SplitMix64(seed)
+    Dbits, Ebits = min(n * kD, 8192), min(n * kE, 4096)
+    rnd = lambda bits: (sum(g.next_u64() << (64 * i) for i in range(-(-bits // 64))) & ((1 << bits) - 1)) if bits > 0 else 0
+    exact = lambda bits: rnd(bits - 1) | 1 << (bits - 1)              # exactly `bits` bits
+    out = []
+
+    def add(name, D, E, d_limbs=None, e_limbs=None):
+        if E <= 0 or D < 0 or D >= 1 << Dbits or E >= 1 << Ebits:
+            return
+        out.append((name, d_limbs or int_limbs(D, n, kD), e_limbs or int_limbs(E, n, kE)))
+
+    add("random", rnd(Dbits), exact(Ebits))
+    add("random, a divisor of half the width", exact(Dbits), exact(max(1, Ebits // 2)))
+    add("a divisor of one significant word", rnd(Dbits), exact(min(32, Ebits)))
+    add("a divisor of one significant word, small", rnd(Dbits), 3)
+    for m in (2, 3, 63, 64, 65, 127, 128):
+        if 32 * m <= Ebits:
+            add("a divisor of %d significant words" % m, rnd(Dbits), exact(32 * m - (g.next_u64() % 32)))
+    top = max(1, Ebits // 32)
+    if Ebits >= 32:
+        add("normalising shift 0", rnd(Dbits), exact(32 * top))
+        add("normalising shift 31", rnd(Dbits), rnd(32 * (top - 1)) | 1 << (32 * (top - 1)))
+    for m in (3, 64, 65, 128):
+        E = (1 << (32 * m - 1)) + 1
+        for k in (1, 2, 3):
+            add("add-back m = %d k = %d" % (m, k), ((E - 1) << (32 * k)) | 3, E)
+        E = (0xFFFFFFFF << (32 * (m - 1))) | 5
+        add("saturating m = %d" % m, (E << 32) - 1, E)
+    E = exact(Ebits)
+    add("D < E", rnd(max(0, Ebits - 1)), E)
+    add("D = 0", 0, E)
+    add("D = E", E, E)
+    add("D = E - 1", E - 1, E)
+    add("E = 1", rnd(Dbits), 1)
+    if Dbits == 8192 and Ebits == 4096:
+        add("E = 2^4096 - 1 under D = 2^8192 - 1", (1 << 8192) - 1, (1 << 4096) - 1)
+    add("the largest operands of the shape", (1 << Dbits) - 1, (1 << Ebits) - 1)
+    # every limb r - 1, so that every word of the sum carries: kD limbs of the dividend where that stays below 2^8192 and the quotient
+    # fits, the divisor's limbs where the remainder still fits kE limbs of n bits
+    rbits = r.bit_length()
+    d_full = [r - 1] * kD
+    e_count = max(k for k in range(0, kE + 1) if k == 0 or n * (k - 1) + rbits <= n * kE)
+    if limbs_int(d_full, n) < 1 << 8192 and n * (kD - 1) + rbits <= n * kD + Ebits - 1:
+        add("every dividend limb r - 1", 0, E, d_limbs=d_full)
+        if e_count:
+            e_full = [r - 1] * e_count
+            if limbs_int(d_full, n) // limbs_int(e_full, n) < 1 << (n * kD):
+                out.append(("every limb r - 1", d_full, e_full))
+    return out
 
 
 def modmul_pairs(modulus, count, seed=SPLITMIX_SEED, bits=None):

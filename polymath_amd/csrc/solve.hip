@@ -2,7 +2,7 @@
 // (include/polymath_hip.h), so that a caller supplies only the values it chooses and the library computes the rest
 // before it checks or proves.  The PLAN -- which row determines which column, in which order -- is host work, done once per (key,
 // pattern) by host/solve_plan.hpp; what ONE step does to ONE assignment (solve_step, solve_bits, solve_iszero, solve_divrem,
-// solve_indicator, solve_sqrt, solve_block, solve_longdiv, solve_moddiv, the dispatch solve_any, the inverses' solve_inverse and solve_block_invert, and the records
+// solve_indicator, solve_sqrt, solve_block, solve_longdiv, solve_moddiv, solve_longdiv_wide and its longdiv_wide_words, the dispatch solve_any, the inverses' solve_inverse and solve_block_invert, and the records
 // a plan becomes: solve_records) is
 // solve_steps.cuh, text that the CPU self-tests run as well; this file is the kernels that call it and the host driver,
 // assignment = grid y (or the lane, in the chain kernel):
@@ -37,6 +37,13 @@
 //                     selects; a binary extended Euclid for odd modulus with masked updates runs the launch's 2 L rounds with the
 //                     numerator in place of 1, so that it ends in Z itself (solve_steps.cuh: modinv_odd proves the bound).  No
 //                     register is indexed at run time; stuck at the word nr + h
+//   k_solve_longdiv_wide  the declared WIDE long divisions of a level (opcode 5: up to 8192 / 4096 bits, RSA-2048), whatever its width: one
+//                     WAVE per (hint, assignment), four to a workgroup.  No lane holds an operand: the 32-bit words of dividend,
+//                     divisor and quotient live in the wave's slice of LDS, lane i working on words i, i + 64, ...  Gather: lane j
+//                     stages limb j out of Montgomery form, the words are column sums of the staged limbs, one carry resolution by
+//                     ballot.  Divide: Knuth's algorithm D in base 2^32, a word of quotient per step (solve_steps.cuh:
+//                     longdiv_wide_words states the recurrence); lane i multiplies divisor word i, carries and borrows by ballot.
+//                     Scatter: lane i cuts limb i and stores it.  Every trip count is wave-uniform; stuck at the word nr + h
 //   k_solve_chain     a run of consecutive NARROW levels: one lane per assignment walks the run's steps in plan order.  A lane
 //                     reads back only its own stores: no barriers, no fences.  The MiMC shape (depth 644, width 1) is one such run
 //                     and the batch is its parallel dimension.
@@ -197,6 +204,211 @@ __global__ __launch_bounds__(64) void k_solve_moddiv(const SolveStepDev<P> *__re
     const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (t >= hi) return;
     solve_moddiv<P>(steps[t], mods[steps[t].bits], hint_idx, rounds, inv_rounds, xw + b * ncols, StuckWord{stuck + b});
+}
+
+// ---- k_solve_longdiv_wide: one wave, one division.  The wave's slice of LDS (5888 B; four waves to a workgroup: 23 KB):
+//   stage  1024 words: the eight words of up to 128 staged limbs (dividend, then divisor); afterwards the quotient's 257 words
+//   u      WIDE_SUM_D + 6 words: the dividend's column sums, then the normalised window of algorithm D, then the remainder
+//   v      WIDE_SUM_E + 6 words: the divisor, normalised in place
+// A lane writes words that other lanes read, so every such hand-over is a wave_sync(): LDS operations of one wave complete in order,
+// the fence keeps the compiler from moving them across and waits for them.  No __syncthreads() after the kernel's head: the four
+// waves of a workgroup have trip counts of their own.
+struct WideLds {
+    uint32_t stage[1024], u[WIDE_SUM_D + 6], v[WIDE_SUM_E + 6];
+};
+
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ uint32_t wave_uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+// The carry (or borrow) INTO each of a wave's 64 consecutive words of a multi-word addition, from the words' own bits: g, this word
+// generates a carry whatever comes in; p, it passes one on (never both).  With G and P the ballots and h = G << 1 | cin, the binary
+// addition P + h runs the same recurrence c[i + 1] = g[i] | p[i] & c[i] through its own carry chain, and (P + h) ^ P has c[i] in bit
+// i.  -> this lane's carry-in; *cout: the carry out of word 63, the next 64 words' cin.
+__device__ __forceinline__ uint32_t wave_carry(bool g, bool p, uint32_t lane, uint32_t cin, uint32_t *cout) {
+    const uint64_t G = __ballot(g), Pm = __ballot(p);
+    const uint64_t c = (Pm + (G << 1 | cin)) ^ Pm;
+    *cout = (uint32_t)((G >> 63) | ((Pm >> 63) & (c >> 63)));
+    return (uint32_t)(c >> lane) & 1u;
+}
+
+// Word w of sum_j limb_j 2^(n j) over the k staged limbs, before carries: below 2^39 (k <= 128 pieces of 32 bits).  Limb j reaches
+// word w where n j < 32 w + 32 and n j + 256 > 32 w; its piece is 32 bits of the limb at the bit offset 32 w - n j in (-32, 256).
+__device__ __forceinline__ uint64_t wide_column(const uint32_t *stage, uint32_t k, uint32_t n, uint32_t w) {
+    if (k == 0) return 0;
+    const uint32_t top = 32u * w + 31u, j_hi = min(k - 1u, top / n), j_lo = 32u * w >= 256u ? (32u * w - 256u) / n + 1u : 0u;
+    uint64_t sum = 0;
+    for (uint32_t j = j_lo; j <= j_hi; ++j) {
+        const int r = (int)(32u * w) - (int)(n * j), wi = r >> 5;      // wi in -1..7
+        const uint32_t bs = (uint32_t)r & 31u;
+        const uint32_t lo = wi >= 0 ? stage[8 * j + wi] : 0u, hi = wi < 7 ? stage[8 * j + wi + 1] : 0u;
+        sum += (uint32_t)(((uint64_t)hi << 32 | lo) >> bs);
+    }
+    return sum;
+}
+
+// The operand of k limbs (columns `cols` of z) into dst[0 .. cap): staged, summed by columns, carried.  Words are taken 64 at a time, lane i word 64 c + i.  dst[w] for w < cap is written, zero where the sum does not reach.
+template <class P>
+__device__ __forceinline__ void wide_gather(const Fp<P> *z, const uint32_t *__restrict__ cols, uint32_t k, uint32_t n, uint32_t *stage, uint32_t *dst, uint32_t cap,
+                                            uint32_t lane) {
+    for (uint32_t j = lane; j < k; j += 64) {
+        const Fp<P> limb = from_mont<P>(z[cols[j]]);
+#pragma unroll
+        for (int w = 0; w < 8; ++w) stage[8 * j + w] = limb.l[w];
+    }
+    wave_sync();
+    uint32_t cin = 0, hi_in = 0;          // uniform: the carry and the column's high part that the previous 64 words hand on
+    for (uint32_t base = 0; base < cap; base += 64) {
+        const uint32_t w = base + lane;
+        const uint64_t col = w < cap ? wide_column(stage, k, n, w) : 0;
+        uint32_t hi_prev = __shfl_up((uint32_t)(col >> 32), 1);
+        if (lane == 0) hi_prev = hi_in;
+        hi_in = wave_uniform(__shfl((uint32_t)(col >> 32), 63));
+        const uint64_t sum = (uint64_t)(uint32_t)col + hi_prev;
+        const uint32_t c = wave_carry((sum >> 32) != 0, (uint32_t)sum == 0xffffffffu, lane, cin, &cin);
+        if (w < cap) dst[w] = (uint32_t)sum + c;
+    }
+    wave_sync();
+}
+
+// the significant words of a[0 .. cap): wave-uniform
+__device__ __forceinline__ uint32_t wide_significant(const uint32_t *a, uint32_t cap, uint32_t lane) {
+    uint32_t count = 0;
+    for (uint32_t base = 0; base < cap; base += 64) {
+        const uint64_t set = __ballot(base + lane < cap && a[base + lane] != 0);
+        if (set) count = base + 64u - (uint32_t)__builtin_clzll(set);
+    }
+    return wave_uniform(count);
+}
+
+// non-zero where a[0 .. cap) has a bit at or above bit `from`: wave-uniform
+__device__ __forceinline__ uint32_t wide_bits_from(const uint32_t *a, uint32_t cap, uint32_t from, uint32_t lane) {
+    uint32_t any = 0;
+    for (uint32_t base = 0; base < cap; base += 64) any |= __ballot(base + lane < cap && word_bits_from(a[base + lane], base + lane, from) != 0) != 0;
+    return any;
+}
+
+template <class P>
+__global__ __launch_bounds__(256) void k_solve_longdiv_wide(const SolveStepDev<P> *__restrict__ steps, const SolveHintDev *__restrict__ hints,
+                                                            const uint32_t *__restrict__ hint_idx, uint32_t lo, uint32_t hi, Fp<P> *xw, uint64_t ncols,
+                                                            unsigned long long *stuck) {
+    __shared__ WideLds lds[4];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * 4 + wave, b = blockIdx.y;
+    Fp<P> *z = xw + b * ncols;
+    SolveHintDev h{1, 0, 0, 0, 0, 0, 0, 0};          // a wave past the range: an empty hint, every loop of zero trips
+    if (t < hi) h = hints[steps[t].bits];
+    const uint32_t n = h.n, kq = min(h.kq, (uint32_t)pmsolve::WIDE_MAX_KQ), kr = min(h.kr, (uint32_t)pmsolve::WIDE_MAX_KR), kD = min(h.kD, (uint32_t)pmsolve::WIDE_MAX_KD),
+                   kE = min(h.kE, (uint32_t)pmsolve::WIDE_MAX_KE);
+    const uint32_t *q_cols = hint_idx + h.off, *r_cols = q_cols + h.kq, *d_cols = r_cols + h.kr, *e_words = d_cols + h.kD;
+    uint32_t *stage = lds[wave].stage, *u = lds[wave].u, *v = lds[wave].v, *q = stage;
+    constexpr uint32_t U_CAP = WIDE_SUM_D + 6, V_CAP = WIDE_SUM_E + 6;
+
+    // ---- gather
+    uint32_t bad = 0;
+    wide_gather<P>(z, d_cols, kD, n, stage, u, U_CAP, lane);
+    if (h.literal) {
+        for (uint32_t w = lane; w < V_CAP; w += 64) v[w] = w < (uint32_t)WIDE_WE ? e_words[w] : 0u;
+        bad |= e_words[WIDE_WE];
+        wave_sync();
+    } else {
+        wide_gather<P>(z, e_words, kE, n, stage, v, V_CAP, lane);
+    }
+    const uint32_t t_all = wide_significant(u, U_CAP, lane), m_all = wide_significant(v, V_CAP, lane);
+    bad |= (uint32_t)(t_all > (uint32_t)WIDE_WD) | (uint32_t)(m_all > (uint32_t)WIDE_WE) | (uint32_t)(m_all == 0);
+    bad = wave_uniform(bad);
+    // a stuck division divides nothing: zero trips below, zero in every output
+    const uint32_t m = bad ? 0u : m_all, tw = bad ? 0u : t_all;
+    for (uint32_t w = lane; w < 260; w += 64) q[w] = 0;          // the staged limbs are dead (wide_gather ends in a wave_sync)
+
+    // ---- divide.  Normalise: v <<= s over m words, u <<= s over tw + 1 words, every word read before any is written
+    const uint32_t v_top = m ? v[m - 1] : 1u, s = wave_uniform((uint32_t)__builtin_clz(v_top | (m ? 0u : 0x80000000u)));
+    {
+        uint32_t keep_v[2], keep_u[5];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const uint32_t i = 64 * c + lane;
+            keep_v[c] = i < m ? (s ? v[i] << s | (i ? v[i - 1] >> (32 - s) : 0u) : v[i]) : 0u;
+        }
+#pragma unroll
+        for (int c = 0; c < 5; ++c) {
+            const uint32_t i = 64 * c + lane;
+            keep_u[c] = i <= tw ? (s ? u[i] << s | (i ? u[i - 1] >> (32 - s) : 0u) : u[i]) : 0u;
+        }
+        wave_sync();
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+            if (64 * c + lane < m) v[64 * c + lane] = keep_v[c];
+#pragma unroll
+        for (int c = 0; c < 5; ++c)
+            if (64 * c + lane <= tw) u[64 * c + lane] = keep_u[c];
+        wave_sync();
+    }
+    const uint32_t v1 = wave_uniform(m ? v[m - 1] : 1u), v0 = wave_uniform(m >= 2 ? v[m - 2] : 0u);
+    for (uint32_t j = m && tw >= m ? tw - m + 1 : 0; j-- > 0;) {
+        uint32_t saturated;
+        uint32_t qhat = wave_uniform(wide_estimate(u[j + m], u[j + m - 1], m >= 2 ? u[j + m - 2] : 0u, v1, v0, &saturated));
+        // u[j .. j + m) -= qhat v, 64 words at a time: the product's words first (lane i: the low half of qhat v[i] plus the high half
+        // of qhat v[i - 1], carried), then the difference; a lane past the divisor passes carries and borrows on
+        uint32_t carry = 0, borrow = 0;
+        for (uint32_t base = 0; base < m; base += 64) {
+            const uint32_t i = base + lane;
+            const bool on = i < m;
+            const uint64_t sum = on ? (uint64_t)(qhat * v[i]) + (i ? __umulhi(qhat, v[i - 1]) : 0u) : 0u;
+            const uint32_t c = wave_carry(on && (sum >> 32) != 0, !on || (uint32_t)sum == 0xffffffffu, lane, carry, &carry);
+            const uint32_t prod = (uint32_t)sum + c, word = on ? u[j + i] : 0u;
+            const uint32_t bw = wave_carry(on && word < prod, !on || word == prod, lane, borrow, &borrow);
+            if (on) u[j + i] = word - prod - bw;
+        }
+        // the window's top word, in every lane alike: the product's last word is the high half of qhat v[m - 1] and the last carry
+        const uint64_t top = (uint64_t)__umulhi(qhat, v1) + carry + borrow;
+        const uint32_t u_top = u[j + m];
+        const bool back = wave_uniform(top > u_top) != 0;
+        wave_sync();
+        if (back) {          // the estimate was one too large: add the divisor back
+            uint32_t c_in = 0;
+            for (uint32_t base = 0; base < m; base += 64) {
+                const uint32_t i = base + lane;
+                const bool on = i < m;
+                const uint64_t sum = on ? (uint64_t)u[j + i] + v[i] : 0u;
+                const uint32_t c = wave_carry(on && (sum >> 32) != 0, !on || (uint32_t)sum == 0xffffffffu, lane, c_in, &c_in);
+                if (on) u[j + i] = (uint32_t)sum + c;
+            }
+            --qhat;          // the carry out cancels the borrow: the top word is zero
+        }
+        if (lane == 0) {
+            u[j + m] = back ? 0u : u_top - (uint32_t)top;
+            q[j] = qhat;
+        }
+        wave_sync();
+    }
+    // de-normalise: rem = u >> s over m words, read before written
+    {
+        uint32_t keep[2];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const uint32_t i = 64 * c + lane;
+            keep[c] = i < m ? (s ? u[i] >> s | u[i + 1] << (32 - s) : u[i]) : 0u;
+        }
+        wave_sync();
+        for (uint32_t w = lane; w < U_CAP; w += 64) u[w] = w < 64 ? keep[0] : w < 128 ? keep[1] : 0u;
+        wave_sync();
+    }
+
+    // ---- scatter
+    bad |= wide_bits_from(q, 260, n * kq, lane) | wide_bits_from(u, WIDE_WE, n * kr, lane);
+    bad = wave_uniform(bad);
+    const uint32_t mask = bad ? 0u : ~0u;
+    for (uint32_t i = lane; i < kq + kr; i += 64) {
+        Fp<P> limb = i < kq ? limb_at_words<P>(q, 260, n * i, n) : limb_at_words<P>(u, WIDE_WE, n * (i - kq), n);
+#pragma unroll
+        for (int w = 0; w < P::N; ++w) limb.l[w] &= mask;
+        z[q_cols[i]] = to_mont<P>(limb);          // the remainder's columns follow the quotient's in the pool
+    }
+    if (bad && lane == 0 && t < hi) StuckWord{stuck + b}(steps[t]);
 }
 
 // the step index is the same in every lane: the step record, the pair record, the row's CSR metadata and a decomposition's column
@@ -416,6 +628,10 @@ int solve_group(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t 
                 if (!sv.n_mods || l.rounds < 256 || l.rounds > 1024 || l.inv_rounds < 512 || l.inv_rounds > 1024) return PM_ERR_STATE;
                 hipLaunchKernelGGL((k_solve_moddiv<P>), dim3(nblk(l.hi - l.lo, 64), (unsigned)g), dim3(64), 0, st, steps, sv.mods.as<SolveModDev>(),
                                    sv.hint_idx.as<uint32_t>(), l.rounds, l.inv_rounds, l.lo, l.hi, d_xw, ncols, stuck);
+            } else if (l.longdiv_wide) {
+                if (!sv.n_hints || l.rounds < 256 || l.rounds > pmsolve::WIDE_D_BITS) return PM_ERR_STATE;
+                hipLaunchKernelGGL((k_solve_longdiv_wide<P>), dim3(nblk(l.hi - l.lo, 4), (unsigned)g), dim3(256), 0, st, steps, sv.hints.as<SolveHintDev>(),
+                                   sv.hint_idx.as<uint32_t>(), l.lo, l.hi, d_xw, ncols, stuck);
             } else if (l.chain) {
                 const dim3 grid(nblk(g, 64)), block(64);
                 if (l.divides) hipLaunchKernelGGL((k_solve_chain<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, pairs, divs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);

@@ -67,6 +67,8 @@ struct SolveHintDev {
 // what a modular-division step needs beside its SolveStepDev (whose bits = its SolveModDev): in the hint pool from `off` the kz output
 // columns, the kNp, kNm, kDp and kDm operand columns, then the kP modulus columns -- or, literal != 0, the 16 words of the modulus'
 // literal limbs accumulated at bit offset n j and one word that is non-zero where they reach 2^512, as for a literal divisor
+// A WIDE long-division step (KIND_LONGDIV_WIDE) has a SolveHintDev as well, in the same array; its literal divisor is 128 pool words
+// and the word that is non-zero where the limbs reach 2^4096.
 struct SolveModDev {
     uint32_t n, kz, k[4], kP, literal, off, pad;
 };
@@ -88,6 +90,10 @@ struct SolveRecords {
 };
 
 constexpr int LONGDIV_WD = 32, LONGDIV_WE = 16;   // the long division's registers in 32-bit words: a 1024-bit dividend, a 512-bit divisor
+// the WIDE long division's operands in 32-bit words: an 8192-bit dividend and a 4096-bit divisor, and the words their limb sums are
+// formed in -- ten more, since kD limbs below 2^256 at bit offsets up to 8191 stay below 2^(8191 + 256 + 7); a sum that reaches into
+// those ten is D >= 2^8192 (E >= 2^4096)
+constexpr int WIDE_WD = 256, WIDE_WE = 128, WIDE_SUM_D = WIDE_WD + 10, WIDE_SUM_E = WIDE_WE + 10;
 
 // acc += v << off for the 256-bit v (eight words) and the W-word acc, off < 32 W.  -> non-zero where bits were lost above 32 W.  No
 // register is indexed by `off`: the word of the shifted value (nine words) that falls on acc[w] is selected by comparison, W x 9 selects.
@@ -189,6 +195,19 @@ PM_HD void longdiv(uint32_t (&num)[WD], const uint32_t (&d)[WE], uint32_t (&rem)
     }
 }
 
+// acc += v << off for the 256-bit v (eight words) and the W words of acc in memory, off + 288 <= 32 W (nothing is lost): the wide long
+// division's accumulation, where it is serial (the host's literal divisor, the CPU rig); the kernel forms the same sum by columns
+PM_HD void add_shifted_words(uint32_t *acc, uint32_t W, const uint32_t v[8], uint32_t off) {
+    const uint32_t wo = off >> 5, bs = off & 31u;
+    uint64_t carry = 0;
+    for (uint32_t k = 0; wo + k < W && (k < 9 || carry); ++k) {
+        const uint64_t pair = (uint64_t)(k < 8 ? v[k] : 0u) << 32 | (k > 0 && k < 9 ? v[k - 1] : 0u);
+        const uint64_t sum = (uint64_t)acc[wo + k] + (k < 9 ? (uint32_t)(pair << bs >> 32) : 0u) + carry;
+        acc[wo + k] = (uint32_t)sum;
+        carry = sum >> 32;
+    }
+}
+
 template <class P>
 inline SolveRecords<P> solve_records(const pmsolve::Plan &plan) {
     SolveRecords<P> rec;
@@ -216,7 +235,7 @@ inline SolveRecords<P> solve_records(const pmsolve::Plan &plan) {
             rec.block_idx.insert(rec.block_idx.end(), blk.cols.begin(), blk.cols.end());
             rec.blocks.push_back(SolveBlockDev{k, rows_off, rows_off + k, 0, rec.mat_off[blk.mat]});
         }
-        if (s.kind == pmsolve::KIND_LONGDIV || s.kind == pmsolve::KIND_MODDIV) {
+        if (s.kind == pmsolve::KIND_LONGDIV || s.kind == pmsolve::KIND_MODDIV || s.kind == pmsolve::KIND_LONGDIV_WIDE) {
             const pmsolve::Hint &h = plan.hints[s.cols_off];
             const bool literal = (h.flags & pmsolve::HINT_DIVISOR_LITERAL) != 0;   // HINT_MODULUS_LITERAL is the same bit
             const uint32_t kE = (uint32_t)(literal ? h.lit.size() / 4 : h.E.size()), off = (uint32_t)rec.hint_idx.size();
@@ -228,7 +247,20 @@ inline SolveRecords<P> solve_records(const pmsolve::Plan &plan) {
                 rec.hints.push_back(SolveHintDev{h.n, (uint32_t)h.q.size(), (uint32_t)h.rem.size(), (uint32_t)h.D.size(), kE, literal ? 1u : 0u, off, 0});
             }
             for (const std::vector<uint32_t> *cols : {&h.q, &h.rem, &h.D, &h.E}) rec.hint_idx.insert(rec.hint_idx.end(), cols->begin(), cols->end());
-            if (literal) {   // the divisor (the modulus) is a constant of the key: accumulated once, here
+            if (literal && s.kind == pmsolve::KIND_LONGDIV_WIDE) {   // the wide divisor: 128 words and the lost word
+                uint32_t E[WIDE_SUM_E] = {0}, lost = 0;
+                for (size_t j = 0; j < h.lit.size() / 4; ++j) {
+                    uint32_t v[8];
+                    for (int i = 0; i < 4; ++i) {
+                        v[2 * i] = (uint32_t)h.lit[4 * j + i];
+                        v[2 * i + 1] = (uint32_t)(h.lit[4 * j + i] >> 32);
+                    }
+                    add_shifted_words(E, WIDE_SUM_E, v, h.n * (uint32_t)j);
+                }
+                for (int w = WIDE_WE; w < WIDE_SUM_E; ++w) lost |= E[w];
+                rec.hint_idx.insert(rec.hint_idx.end(), E, E + WIDE_WE);
+                rec.hint_idx.push_back(lost);
+            } else if (literal) {   // the divisor (the modulus) is a constant of the key: accumulated once, here
                 uint32_t E[LONGDIV_WE] = {0}, lost = 0;
                 for (size_t j = 0; j < h.lit.size() / 4; ++j) {
                     uint32_t v[8];
@@ -273,7 +305,7 @@ PM_HD uint32_t matrix_kind(uint32_t kind) { return kind >= pmsolve::KIND_BITS_C 
 template <class P>
 PM_HD void solve_inverse(const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsolve::Csr &Cm, SolveStepDev<P> *steps, uint64_t count, SolvePairDev<P> *pairs,
                          const SolveDivDev *divs, uint64_t t) {
-    if (t < count && (steps[t].kind == pmsolve::KIND_INDICATOR || steps[t].kind == pmsolve::KIND_BLOCK || steps[t].kind == pmsolve::KIND_LONGDIV || steps[t].kind == pmsolve::KIND_MODDIV)) return;   // no inverse of a coefficient: the record stays as the host wrote it
+    if (t < count && (steps[t].kind == pmsolve::KIND_INDICATOR || steps[t].kind == pmsolve::KIND_BLOCK || steps[t].kind == pmsolve::KIND_LONGDIV || steps[t].kind == pmsolve::KIND_MODDIV || steps[t].kind == pmsolve::KIND_LONGDIV_WIDE)) return;   // no inverse of a coefficient: the record stays as the host wrote it
     if (t < count && steps[t].kind == pmsolve::KIND_SQRT) {
         const Fp<P> ka = *(const Fp<P> *)(A.val + 4 * steps[t].pos), kb = *(const Fp<P> *)(B.val + 4 * (B.rowptr[steps[t].row] + steps[t].bits));
         const Fp<P> coef = mul<P>(ka, kb);
@@ -739,6 +771,145 @@ PM_HD void solve_moddiv(const SolveStepDev<P> &s, const SolveModDev &h, const ui
 #pragma unroll
         for (int w = 0; w < P::N; ++w) limb.l[w] &= mask;
         z[z_cols[i]] = to_mont<P>(limb);
+    }
+}
+
+// ---- the WIDE long division (KIND_LONGDIV_WIDE): schoolbook division in base 2^32 over word arrays in memory
+
+// what the digit recurrence did, for the tests that must know that a family of operands reaches its rare branches
+struct WideCounters {
+    uint32_t addbacks = 0, saturated = 0;
+};
+
+// the significant words of the W-word a: W less its leading zero words
+PM_HD uint32_t significant_words(const uint32_t *a, uint32_t W) {
+    while (W && a[W - 1] == 0) --W;
+    return W;
+}
+
+// One quotient digit's ESTIMATE (Knuth 4.3.1 D3): from the window's three leading words u2 u1 u0 and the normalised divisor's two
+// leading words v1 v0 (v1 >= 2^31; v0 = u0 = 0 where the divisor has one word).  floor((u2 B + u1) / v1), SATURATED at B - 1 where
+// u2 = v1 (u2 > v1 cannot be: the window's remainder is below the divisor), then lowered while qhat v0 > rhat B + u0 and rhat < B:
+// at most twice, so the refinement is two tests and no loop.  The result is the digit or one more.
+PM_HD uint32_t wide_estimate(uint32_t u2, uint32_t u1, uint32_t u0, uint32_t v1, uint32_t v0, uint32_t *saturated) {
+    const uint64_t num = (uint64_t)u2 << 32 | u1;
+    const bool sat = u2 >= v1;
+    uint64_t qhat = sat ? 0xffffffffull : num / v1;
+    uint64_t rhat = num - qhat * v1;
+    *saturated = sat ? 1u : 0u;
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+        if (rhat <= 0xffffffffull && qhat * v0 > (rhat << 32 | u0)) {
+            --qhat;
+            rhat += v1;
+        }
+    return (uint32_t)qhat;
+}
+
+// q = floor(D / E) and rem = D mod E for the nD-word D and the nE-word E (little-endian 32-bit words), Knuth's algorithm D:
+//   m = the significant words of E (m = 0: E = 0, -> 1 with q and rem zero), t = those of D; s = the leading zeros of E[m - 1]
+//   v = E << s (m words), u = D << s (t + 1 words)
+//   for j = t - m down to 0 (none where t < m):
+//       qhat = wide_estimate(u[j + m], u[j + m - 1], u[j + m - 2], v[m - 1], v[m - 2])
+//       u[j .. j + m] -= qhat v;  where that borrows: u[j .. j + m] += v and qhat -= 1      -- the ADD-BACK, about 2 / B of random digits
+//       q[j] = qhat
+//   rem = u >> s
+// A divisor of ONE significant word takes the same path: v[m - 2] and u[j + m - 2] read as zero, the refinement never fires and the
+// estimate is exact.  This is the statement of the recurrence that k_solve_longdiv_wide distributes over a wave's lanes: there lane i
+// holds word i of qhat v and of the window, and the carries and borrows are resolved by ballot.  q has nD words, rem nE; u (nD + 1
+// words) and v (nE words) are working memory.  `counters` (may be null) counts executed add-backs and saturated estimates.
+PM_HD uint32_t longdiv_wide_words(const uint32_t *D, uint32_t nD, const uint32_t *E, uint32_t nE, uint32_t *q, uint32_t *rem, uint32_t *u, uint32_t *v,
+                                  WideCounters *counters) {
+    for (uint32_t i = 0; i < nD; ++i) q[i] = 0;
+    for (uint32_t i = 0; i < nE; ++i) rem[i] = 0;
+    const uint32_t m = significant_words(E, nE), t = significant_words(D, nD);
+    if (m == 0) return 1;
+    uint32_t s = 0;
+    while (!(E[m - 1] << s & 0x80000000u)) ++s;
+    for (uint32_t i = 0; i < m; ++i) v[i] = s ? E[i] << s | (i ? E[i - 1] >> (32 - s) : 0u) : E[i];
+    for (uint32_t i = 0; i <= nD; ++i) {
+        const uint32_t lo = i && i - 1 < t ? D[i - 1] : 0u, here = i < t ? D[i] : 0u;
+        u[i] = s ? here << s | lo >> (32 - s) : here;
+    }
+    const uint32_t v1 = v[m - 1], v0 = m >= 2 ? v[m - 2] : 0u;
+    for (uint32_t j = t >= m ? t - m + 1 : 0; j-- > 0;) {
+        uint32_t saturated;
+        uint32_t qhat = wide_estimate(u[j + m], u[j + m - 1], m >= 2 ? u[j + m - 2] : 0u, v1, v0, &saturated);
+        uint64_t carry = 0, borrow = 0;
+        for (uint32_t i = 0; i < m; ++i) {
+            const uint64_t prod = (uint64_t)qhat * v[i] + carry;
+            carry = prod >> 32;
+            const uint64_t diff = (uint64_t)u[j + i] - (uint32_t)prod - borrow;
+            u[j + i] = (uint32_t)diff;
+            borrow = diff >> 63;
+        }
+        const uint64_t diff = (uint64_t)u[j + m] - carry - borrow;
+        u[j + m] = (uint32_t)diff;
+        if (diff >> 63) {
+            uint64_t c = 0;
+            for (uint32_t i = 0; i < m; ++i) {
+                const uint64_t sum = (uint64_t)u[j + i] + v[i] + c;
+                u[j + i] = (uint32_t)sum;
+                c = sum >> 32;
+            }
+            u[j + m] += (uint32_t)c;
+            --qhat;
+            if (counters) ++counters->addbacks;
+        }
+        if (counters) counters->saturated += saturated;
+        q[j] = qhat;
+    }
+    for (uint32_t i = 0; i < m; ++i) rem[i] = s ? u[i] >> s | u[i + 1] << (32 - s) : u[i];
+    return 0;
+}
+
+// limb_at for W words in memory (the kernel: in LDS): the n-bit limb (n <= 128) at bit offset off, as a canonical element; words at
+// and above W read as zero
+template <class P>
+PM_HD Fp<P> limb_at_words(const uint32_t *src, uint32_t W, uint32_t off, uint32_t n) {
+    static_assert(P::N == 8, "four 64-bit words");
+    const uint32_t wo = off >> 5, bs = off & 31u;
+    uint32_t g[5];
+#pragma unroll
+    for (uint32_t i = 0; i < 5; ++i) g[i] = wo + i < W ? src[wo + i] : 0u;
+    Fp<P> out;
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) out.l[i] = low_bits((uint32_t)(((uint64_t)g[i + 1] << 32 | g[i]) >> bs), n > 32u * i ? n - 32u * i : 0u);
+    out.l[4] = out.l[5] = out.l[6] = out.l[7] = 0;
+    return out;
+}
+
+// the bits of word w of an array from bit `from` of the array upwards: non-zero where the array has a bit at or above `from` in that word
+PM_HD uint32_t word_bits_from(uint32_t word, uint32_t w, uint32_t from) { return 32u * w >= from ? word : 32u * (w + 1) > from ? word >> (from - 32u * w) : 0u; }
+
+// one declared WIDE long division on one assignment, serially: what the CPU rig's executor runs for KIND_LONGDIV_WIDE, and the
+// statement of what k_solve_longdiv_wide computes with a wave.  Limbs leave Montgomery form and are accumulated at bit offset n j
+// into WIDE_SUM_D and WIDE_SUM_E words; longdiv_wide_words divides; the kq n-bit limbs of the quotient and the kr of the remainder go
+// back to Montgomery form.  Stuck at the hint's word (nr + h), with zero in every output:
+//   E = 0;  D >= 2^8192;  E >= 2^4096;  q >= 2^(n kq);  rem >= 2^(n kr)
+template <class P, class Sink>
+inline void solve_longdiv_wide(const SolveStepDev<P> &s, const SolveHintDev &h, const uint32_t *hint_idx, Fp<P> *z, const Sink &stuck, WideCounters *counters = nullptr) {
+    const uint32_t *q_cols = hint_idx + h.off, *r_cols = q_cols + h.kq, *d_cols = r_cols + h.kr, *e_words = d_cols + h.kD;
+    std::vector<uint32_t> D(WIDE_SUM_D, 0), E(WIDE_SUM_E, 0), Q(WIDE_WD), R(WIDE_WE), U(WIDE_WD + 1), V(WIDE_WE);
+    uint32_t bad = 0;
+    for (uint32_t j = 0; j < h.kD; ++j) add_shifted_words(D.data(), WIDE_SUM_D, from_mont<P>(z[d_cols[j]]).l, h.n * j);
+    if (h.literal) {
+        for (int w = 0; w < WIDE_WE; ++w) E[w] = e_words[w];
+        bad |= e_words[WIDE_WE];
+    } else {
+        for (uint32_t j = 0; j < h.kE; ++j) add_shifted_words(E.data(), WIDE_SUM_E, from_mont<P>(z[e_words[j]]).l, h.n * j);
+    }
+    for (int w = WIDE_WD; w < WIDE_SUM_D; ++w) bad |= D[w];
+    for (int w = WIDE_WE; w < WIDE_SUM_E; ++w) bad |= E[w];
+    bad |= longdiv_wide_words(D.data(), WIDE_WD, E.data(), WIDE_WE, Q.data(), R.data(), U.data(), V.data(), counters);
+    for (uint32_t w = 0; w < (uint32_t)WIDE_WD; ++w) bad |= word_bits_from(Q[w], w, h.n * h.kq);
+    for (uint32_t w = 0; w < (uint32_t)WIDE_WE; ++w) bad |= word_bits_from(R[w], w, h.n * h.kr);
+    if (bad) stuck(s);
+    const uint32_t mask = bad ? 0u : ~0u;
+    for (uint32_t i = 0; i < h.kq + h.kr; ++i) {
+        Fp<P> limb = i < h.kq ? limb_at_words<P>(Q.data(), WIDE_WD, h.n * i, h.n) : limb_at_words<P>(R.data(), WIDE_WE, h.n * (i - h.kq), h.n);
+        for (int w = 0; w < P::N; ++w) limb.l[w] &= mask;
+        z[q_cols[i]] = to_mont<P>(limb);          // the remainder's columns follow the quotient's in the pool
     }
 }
 

@@ -183,7 +183,23 @@
 //                 two trip counts: Launch::rounds, the largest min(1024, n (k - 1) + 256) over the operand lists of its hints (the
 //                 reductions modulo P), and Launch::inv_rounds = 2 L, L the largest min(512, n (kP - 1) + 256) (the inversion).
 //                 Not handled: even moduli, operands beyond 1024 bits, the slope of a doubling as one hint (3 X^2 / 2 Y: the
-//                 numerator is a product), gcd, sorting.
+//                 numerator is a product), gcd, sorting.  Of the long-division record's list, dividends beyond 1024 bits now
+//                 have a record of their own:
+//   wide hint     a WIDE LONG DIVISION that the key declares in the same stream (opcode HINT_LONGDIV_WIDE = 5; 2 and 4 stay refused as
+//                 unknown): the record of opcode 1 -- n, kq, kr, kD, kE, flags, the four column lists or kE literal limbs -- with
+//                 kD <= 128, kE <= 64, kq <= 128, kr <= 64, n (kD - 1) < 8192 and n (kE - 1) < 4096.  An RSA-2048 modular
+//                 multiplication divides some 4200 bits by 2048: 32 limbs of 64 bits, or zk-email's 17 of 121.  ACTIVE / INERT /
+//                 refused, HINT-OWNED outputs, waiting on inputs and the never-ready refusal are the long-division rules unchanged;
+//                 all three opcodes share the index h and the set of output columns.  It acts as ONE step of kind KIND_LONGDIV_WIDE
+//                 at 1 + max level of its inputs, Step::row = nr + h, Step::col its first quotient column, Step::cols_off its entry
+//                 of Plan::hints, and stores the kq n-bit limbs of floor(D / E) and the kr n-bit limbs of D mod E.  Stuck, with zero
+//                 in every output: E = 0, D >= 2^8192, E >= 2^4096, q >= 2^(n kq), rem >= 2^(n kr).  The wide hints of a level sort
+//                 last, after its modular ones, and are a launch of their own (Launch::longdiv_wide; longdiv, moddiv and block are 0
+//                 on it: a WAVE per hint, not a lane); Launch::rounds is the largest min(8192, n (kD - 1) + 256) of the range, a bound
+//                 that sizes things -- the division's trip counts follow the operands (solve_steps.cuh: longdiv_wide_words).
+//                 Opcode 1 is not widened: its limits, its kernel and its plans are what they were.
+//                 Not handled: modular division at these widths (HINT_MODDIV keeps 1024 / 512 bits), even moduli, linear blocks
+//                 beyond 64 unknowns (RSA-4096 at 64-bit limbs), hints on sharded keys, per-assignment declarations, gcd, sorting.
 // With the heap empty the scheduler has failed if an opener is unclosed, a boolean-pending column unsolved or a marked column
 // undetermined; the result is then build_plan's error (code, row, column, message) with "; in any row order: ..." appended.  A plan
 // it finds has Plan::reordered = true, level(step) as below, the steps sorted by (level, kind, row) and the level_ptr and launches of
@@ -218,12 +234,14 @@ namespace pmsolve {
 // KIND_BLOCK: a linear block, z_S = M^-1 rhs over k rows and k columns; the inverse is plan data, so it does not count as dividing
 // KIND_LONGDIV: a declared long-division hint, kq + kr columns in one step; integer arithmetic only, so it does not count as dividing
 // KIND_MODDIV: a declared modular-division hint, kz columns in one step; integer arithmetic only as well
-enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6, KIND_DIVREM = 7, KIND_INDICATOR = 8, KIND_SQRT = 9, KIND_BLOCK = 10, KIND_LONGDIV = 11, KIND_MODDIV = 12 };
+// KIND_LONGDIV_WIDE: a declared wide long division (opcode 5), kq + kr columns in one step of one wave; integer arithmetic only
+enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6, KIND_DIVREM = 7, KIND_INDICATOR = 8, KIND_SQRT = 9, KIND_BLOCK = 10, KIND_LONGDIV = 11, KIND_MODDIV = 12, KIND_LONGDIV_WIDE = 13 };
 constexpr uint32_t NUM_KINDS = 7;        // the kinds that need no second marker: what it always counted
 constexpr uint32_t NUM_STEP_KINDS = 8;   // KIND_C .. KIND_DIVREM, the kinds whose value comes from field or integer arithmetic on the row: what it counted when kind 7 came
 constexpr uint32_t NUM_SORT_KINDS = 10 + 1;  // all 11 of them: the ten kinds that one lane executes, KIND_INDICATOR and KIND_SQRT included, and KIND_BLOCK: the kinds that rows make
 constexpr uint32_t NUM_PLAN_KINDS = 12;  // with KIND_LONGDIV, which no row makes: the key width of finish_plan's counting sort (NUM_SORT_KINDS counts the kinds that rows make, as it did)
 constexpr uint32_t NUM_HINT_KINDS = 13;  // with KIND_MODDIV: the key width of finish_plan's counting sort now (NUM_PLAN_KINDS stays what it counted when kind 11 came)
+constexpr uint32_t NUM_WIDE_KINDS = 14;  // with KIND_LONGDIV_WIDE: the key width of finish_plan's counting sort now (NUM_HINT_KINDS stays what it counted when kind 12 came)
 constexpr uint32_t MAX_BLOCK = 64;       // the largest linear block: one wave, a lane per row and per column
 
 constexpr uint8_t PATTERN_UNKNOWN = 1, PATTERN_QUOTIENT = 2, PATTERN_INDICATOR = 3, PATTERN_SQRT = 4;   // the pattern bytes (0: given)
@@ -278,6 +296,9 @@ constexpr uint64_t HINT_LONGDIV = 1, HINT_DIVISOR_LITERAL = 1;
 // at most 32 limbs in each of N+, N-, D+, D-; every operand sum below 2^1024, the modulus below 2^512
 constexpr uint64_t HINT_MODDIV = 3, HINT_MODULUS_LITERAL = 1;
 constexpr uint32_t MODDIV_MAX_KZ = 16, MODDIV_MAX_KP = 16, MODDIV_MAX_K = 32, MODDIV_OPERAND_BITS = 1024, MODDIV_MODULUS_BITS = 512;
+// the wide long division's opcode (4 is refused as unknown, like 2) and the limits of its record; its flag is HINT_DIVISOR_LITERAL
+constexpr uint64_t HINT_LONGDIV_WIDE = 5;
+constexpr uint32_t WIDE_MAX_KD = 128, WIDE_MAX_KE = 64, WIDE_MAX_KQ = 128, WIDE_MAX_KR = 64, WIDE_D_BITS = 8192, WIDE_E_BITS = 4096;
 constexpr uint32_t HINT_MAX_N = 128, HINT_MAX_KD = 32, HINT_MAX_KE = 16, HINT_MAX_KQ = 32, HINT_MAX_KR = 16, HINT_D_BITS = 1024, HINT_E_BITS = 512;
 struct Hint {
     uint32_t n = 0, flags = 0;
@@ -287,6 +308,7 @@ struct Hint {
     // A MODULAR DIVISION (op == HINT_MODDIV) uses the same lists, so that the scheduler reads both opcodes alike: q = the kz output
     // columns, rem empty, D = the kNp + kNm numerator columns followed by the kDp + kDm denominator columns, E = the kP modulus
     // columns (lit: its literal limbs, with HINT_MODULUS_LITERAL); k[4] = kNp, kNm, kDp, kDm, the parts of D
+    // A WIDE long division (op == HINT_LONGDIV_WIDE) uses the lists exactly as a long division does
     uint32_t op = (uint32_t)HINT_LONGDIV;
     uint32_t k[4] = {0, 0, 0, 0};
 };
@@ -306,6 +328,9 @@ struct Launch {
                             // dividend of kD limbs below 2^256 at bit offsets n j is below 2 to that power
                             // moddiv: the same bound over the four operand lists of the range's hints (the reductions modulo P)
     uint8_t moddiv = 0;     // chain == 0 only.  1: every step of the range is a declared modular division; longdiv and block are 0 on it
+                            // longdiv_wide: the largest min(8192, n (kD - 1) + 256) of the range's hints: a bound that sizes the wave's
+                            // arrays, not a trip count
+    uint8_t longdiv_wide = 0;// chain == 0 only.  1: every step of the range is a declared wide long division (one wave each); longdiv, moddiv and block are 0 on it
     uint32_t inv_rounds = 0;// moddiv only: the inversion's trip count 2 L, L the largest min(512, n (kP - 1) + 256) of the range's hints:
                             // every modulus of the range that is not stuck is below 2^L (solve_steps.cuh: modinv_odd proves the bound)
 };
@@ -507,7 +532,7 @@ inline bool sqrt_row(const std::vector<Unknown> &occ, const uint32_t nz[3], cons
 // The tail both builders share: p.steps (in ROW order, levels set) sorted by (level, kind), stable by row; level_ptr; the launch schedule.
 inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
     // counting sort by (level, kind); the row order inside a key is the order the steps come in
-    constexpr size_t K = NUM_HINT_KINDS;
+    constexpr size_t K = NUM_WIDE_KINDS;
     std::vector<uint32_t> start((size_t)max_level * K + 1, 0);
     for (const Step &s : p.steps) ++start[(size_t)(s.level - 1) * K + s.kind + 1];
     for (size_t i = 1; i < start.size(); ++i) start[i] += start[i - 1];
@@ -524,11 +549,11 @@ inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
     // do not divide: a chain of C-steps and indicators is a non-dividing one), and where the square-root rows begin (which count as
     // dividing); consecutive narrow levels are one chain.  The linear blocks of a level come last and are a launch of their own
     // whatever the level's width (a wave per block, not a lane): a chain run ends before them and a new one begins after them.  So are
-    // the declared hints of a level, after its blocks: first its long divisions, then its modular divisions
+    // the declared hints of a level, after its blocks: first its long divisions, then its modular divisions, then its wide long divisions
     for (uint32_t l = 0; l < max_level; ++l) {
         const uint32_t *at = start.data() + (size_t)l * K;
         const uint32_t lo = at[KIND_C], ab = at[KIND_A], bits = at[KIND_BITS_C], bits_ab = at[KIND_BITS_A], pairs = at[KIND_ISZERO], divs = at[KIND_DIVREM],
-                       inds = at[KIND_INDICATOR], roots = at[KIND_SQRT], hi = at[KIND_BLOCK], end = at[KIND_LONGDIV], hints_end = at[KIND_MODDIV], moddiv_end = at[K];
+                       inds = at[KIND_INDICATOR], roots = at[KIND_SQRT], hi = at[KIND_BLOCK], end = at[KIND_LONGDIV], hints_end = at[KIND_MODDIV], moddiv_end = at[KIND_LONGDIV_WIDE], wide_end = at[K];
         const uint8_t divides = (uint8_t)(bits > ab || inds > bits_ab || hi > roots);
         if (hi == lo) {
             // a level of blocks only
@@ -571,6 +596,15 @@ inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
                     if (k) hints.rounds = std::max(hints.rounds, std::min(h.n * (k - 1) + 256, MODDIV_OPERAND_BITS));
                 const uint32_t kP = (uint32_t)(h.flags & HINT_MODULUS_LITERAL ? h.lit.size() / 4 : h.E.size());
                 hints.inv_rounds = std::max(hints.inv_rounds, 2 * std::min(h.n * (kP - 1) + 256, MODDIV_MODULUS_BITS));
+            }
+            p.launches.push_back(hints);
+        }
+        if (wide_end > moddiv_end) {   // the wide long divisions of the level, last: a launch of their own, a wave per hint
+            Launch hints{moddiv_end, wide_end, 0, 0};
+            hints.longdiv_wide = 1;
+            for (uint32_t t = moddiv_end; t < wide_end; ++t) {
+                const Hint &h = p.hints[p.steps[t].cols_off];
+                hints.rounds = std::max(hints.rounds, std::min(h.n * ((uint32_t)h.D.size() - 1) + 256, WIDE_D_BITS));
             }
             p.launches.push_back(hints);
         }
@@ -751,7 +785,7 @@ struct Planner {
         for (const std::vector<uint32_t> *in : {&h.D, &h.E})
             for (uint32_t col : *in) lv = level[col] > lv ? level[col] : lv;
         ++lv;
-        Step s{0, (uint32_t)(nr + h.index), h.q[0], h.op == HINT_MODDIV ? KIND_MODDIV : KIND_LONGDIV, lv};
+        Step s{0, (uint32_t)(nr + h.index), h.q[0], h.op == HINT_MODDIV ? KIND_MODDIV : h.op == HINT_LONGDIV_WIDE ? KIND_LONGDIV_WIDE : KIND_LONGDIV, lv};
         s.cols_off = (uint32_t)p.hints.size();
         p.hints.push_back(h);
         p.steps.push_back(s);
@@ -1135,7 +1169,9 @@ inline bool schedule_any_order(Planner &st, uint64_t nr, uint64_t ncols, std::st
 //   -- or, with HINT_DIVISOR_LITERAL (flags bit 0), kE limb values of four words each (canonical integers below r)
 //   HINT_MODDIV, n, kz, kNp, kNm, kDp, kDm, kP, flags, kz output columns, kNp + kNm numerator columns, kDp + kDm denominator columns,
 //   then kP modulus columns -- or, with HINT_MODULUS_LITERAL (flags bit 0), kP limb values of four words each
+//   HINT_LONGDIV_WIDE, n, kq, kr, kD, kE, flags, and what follows HINT_LONGDIV's head: the same record under the wide limits
 // in any mixture; both opcodes share the index h and the set of output columns.  Opcode 2 is reserved and refused like any unknown one.
+// So does the third opcode; 4 is refused as unknown as well.
 // -> the hints in `out` and an empty string, or what is refused, "hint h: " + the condition, and `out` empty.  `modulus`: r, four words.
 inline std::string decode_hints(const uint64_t *desc, size_t n_words, uint64_t ncols, const uint64_t *modulus, std::vector<Hint> &out) {
     out.clear();
@@ -1146,7 +1182,7 @@ inline std::string decode_hints(const uint64_t *desc, size_t n_words, uint64_t n
         const std::string here = "hint " + std::to_string(out.size()) + ": ";
         Hint h;
         h.index = (uint32_t)out.size();
-        if (desc[at] != HINT_LONGDIV && desc[at] != HINT_MODDIV) { why = here + "unknown opcode " + std::to_string(desc[at]); break; }
+        if (desc[at] != HINT_LONGDIV && desc[at] != HINT_MODDIV && desc[at] != HINT_LONGDIV_WIDE) { why = here + "unknown opcode " + std::to_string(desc[at]); break; }
         const bool moddiv = desc[at] == HINT_MODDIV;
         const size_t head = moddiv ? 9 : 7;
         if (n_words - at < head) { why = here + "the record is truncated"; break; }
@@ -1169,6 +1205,18 @@ inline std::string decode_hints(const uint64_t *desc, size_t n_words, uint64_t n
             h.op = (uint32_t)HINT_MODDIV;
             for (int i = 0; i < 4; ++i) h.k[i] = (uint32_t)k[i];
             counts[0] = kz, counts[1] = 0, counts[2] = k[0] + k[1] + k[2] + k[3], kE = kP;
+        } else if (desc[at] == HINT_LONGDIV_WIDE) {
+            const uint64_t kq = desc[at + 2], kr = desc[at + 3], kD = desc[at + 4];
+            kE = desc[at + 5];
+            if (kq < 1 || kq > WIDE_MAX_KQ) { why = here + "kq = " + std::to_string(kq) + " is outside 1..128"; break; }
+            if (kr < 1 || kr > WIDE_MAX_KR) { why = here + "kr = " + std::to_string(kr) + " is outside 1..64"; break; }
+            if (kD < 1 || kD > WIDE_MAX_KD) { why = here + "kD = " + std::to_string(kD) + " is outside 1..128"; break; }
+            if (kE < 1 || kE > WIDE_MAX_KE) { why = here + "kE = " + std::to_string(kE) + " is outside 1..64"; break; }
+            if (flags & ~HINT_DIVISOR_LITERAL) { why = here + "unknown flags " + std::to_string(flags); break; }
+            if (n * (kD - 1) >= WIDE_D_BITS) { why = here + "n (kD - 1) = " + std::to_string(n * (kD - 1)) + " is 8192 or more"; break; }
+            if (n * (kE - 1) >= WIDE_E_BITS) { why = here + "n (kE - 1) = " + std::to_string(n * (kE - 1)) + " is 4096 or more"; break; }
+            h.op = (uint32_t)HINT_LONGDIV_WIDE;
+            counts[0] = kq, counts[1] = kr, counts[2] = kD;
         } else {
             const uint64_t kq = desc[at + 2], kr = desc[at + 3], kD = desc[at + 4];
             kE = desc[at + 5];

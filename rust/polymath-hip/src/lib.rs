@@ -691,6 +691,8 @@ pub enum HintLimbs<'a> {
 pub enum Hint<'a> {
     /// `PM_HINT_LONGDIV`: `q` and `rem` are the limbs of `floor(D / E)` and `D mod E`.
     LongDiv { n: u64, q: &'a [u64], rem: &'a [u64], dividend: &'a [u64], divisor: HintLimbs<'a> },
+    /// `PM_HINT_LONGDIV_WIDE`: the same record under the wide limits (a dividend below 2^8192, a divisor below 2^4096: RSA-2048).
+    LongDivWide { n: u64, q: &'a [u64], rem: &'a [u64], dividend: &'a [u64], divisor: HintLimbs<'a> },
     /// `PM_HINT_MODDIV`: `z` are the limbs of the `Z` in `[0, P)` with `Z (D+ - D-) = N+ - N- (mod P)`; both numerator lists empty
     /// mean `N = 1`, the modular inverse.
     ModDiv { n: u64, z: &'a [u64], n_plus: &'a [u64], n_minus: &'a [u64], d_plus: &'a [u64], d_minus: &'a [u64], modulus: HintLimbs<'a> },
@@ -704,6 +706,10 @@ impl Hint<'_> {
             let (lists, last): (Vec<&[u64]>, &HintLimbs) = match hint {
                 Hint::LongDiv { n, q, rem, dividend, divisor } => {
                     words.extend_from_slice(&[sys::PM_HINT_LONGDIV, *n, q.len() as u64, rem.len() as u64, dividend.len() as u64]);
+                    (vec![*q, *rem, *dividend], divisor)
+                }
+                Hint::LongDivWide { n, q, rem, dividend, divisor } => {
+                    words.extend_from_slice(&[sys::PM_HINT_LONGDIV_WIDE, *n, q.len() as u64, rem.len() as u64, dividend.len() as u64]);
                     (vec![*q, *rem, *dividend], divisor)
                 }
                 Hint::ModDiv { n, z, n_plus, n_minus, d_plus, d_minus, modulus } => {
@@ -1078,7 +1084,7 @@ impl GpuKey {
     /// Declare the witness solver's hints of this key (`pm_pk_load_bytes` with `PM_KEY_HINTS`: no key is loaded, this one keeps its
     /// address) -- `desc` is the sequence of records the header states (`PM_HINT_LONGDIV, n, kq, kr, kD, kE, flags`, then the columns
     /// or literal limbs; `PM_HINT_MODDIV, n, kz, kNp, kNm, kDp, kDm, kP, flags` for a modular division; [`Hint::encode`] writes
-    /// both); an empty slice clears the declaration.  Taking `&mut self` keeps safe code from racing the call with calls
+    /// both, and `PM_HINT_LONGDIV_WIDE`, which has the long division's layout); an empty slice clears the declaration.  Taking `&mut self` keeps safe code from racing the call with calls
     /// that use the key.
     pub fn set_hints(&mut self, ctx: &mut Context, desc: &[u64]) -> Result<(), HipError> {
         let ptr = if desc.is_empty() { core::ptr::null() } else { desc.as_ptr() as *const u8 };

@@ -42,6 +42,12 @@ rem with Python's divmod).  UNMEASURED: no run of it is recorded.
                                                                                  (k + 5) G and 2 G; ecadd:STEPS for others
 on circuits that divide in a foreign field (a declared modular division per quotient or slope, then the product's block and a
 declared long division per reduction, with their decompositions and carries; route (a) synthesises with Python's pow and divmod).
+  python tools/prove_bench.py --circuit rsa --batch 64 --reps 5 --solve          RsaVerify, s^65537 mod a 2048-bit modulus on 32 limbs
+                                                                                 of 64 bits; rsa:BITS:N:LIMBS for others (rsa:2048:121:17)
+  python tools/prove_bench.py --circuit widediv --batch 256 --reps 5 --solve     LimbDivision, 16 wide divisions of 63 by 32 limbs of
+                                                                                 64 bits; widediv:COUNT:N:KD:KE for others
+on circuits that divide wide integers (RSA: per modular multiplication a linear block of 2 LIMBS - 1 unknowns, one declared WIDE long
+division, the limbs of q N and a chain of carries, 17 multiplications deep; route (a) synthesises with Python's divmod).
   python tools/prove_bench.py --circuit mimc322 --batch 256 --reps 5 --solve --reorder reverse     or --reorder SEED
 runs either --solve comparison on the same circuit with its constraint rows stored in another order (circuits.Reordered: reversed, or
 shuffled by SEED; a matchcount gadget moves as a block so that every opener stays before its closer).  Route (b) then goes through the
@@ -59,7 +65,7 @@ from polymath_amd import circuits as PC
 from polymath_amd.polymath import Polymath
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants), bench:NC (BenchCircuit, NC constraints), arx[:WIDTH:ROUNDS] (ArxDemo), matchcount[:N:FORM] (MatchCount), divrem[:N:BITS] (DivRem), tablewalk[:WIDTH:STEPS] (TableWalk), decompress[:POINTS] (EdwardsDecompress), limbproduct[:COUNT:LIMBS] (LimbProduct), modmul[:COUNT:N:LIMBS] (LimbModMul), moddiv[:COUNT:N:LIMBS] (LimbModDiv) or ecadd[:STEPS] (EcAddChain)")
+ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants), bench:NC (BenchCircuit, NC constraints), arx[:WIDTH:ROUNDS] (ArxDemo), matchcount[:N:FORM] (MatchCount), divrem[:N:BITS] (DivRem), tablewalk[:WIDTH:STEPS] (TableWalk), decompress[:POINTS] (EdwardsDecompress), limbproduct[:COUNT:LIMBS] (LimbProduct), modmul[:COUNT:N:LIMBS] (LimbModMul), moddiv[:COUNT:N:LIMBS] (LimbModDiv), ecadd[:STEPS] (EcAddChain), rsa[:BITS:N:LIMBS] (RsaVerify) or widediv[:COUNT:N:KD:KE] (LimbDivision)")
 ap.add_argument("--batch", type=int, default=16)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--curve", default="bls12_381")
@@ -69,8 +75,8 @@ ap.add_argument("--glue", choices=("host", "device"), default="host", help="devi
 ap.add_argument("--solve", action="store_true", help="host-synthesised assignments against partial assignments solved on the GPU")
 ap.add_argument("--reorder", default=None, metavar="reverse|SEED", help="with --solve: the circuit's rows stored reversed or shuffled by SEED (unmeasured)")
 a = ap.parse_args()
-if a.solve and not a.circuit.startswith(("mimc", "arx", "matchcount", "divrem", "tablewalk", "decompress", "limbproduct", "modmul", "moddiv", "ecadd")):
-    ap.error("--solve needs a mimcK, an arx, a matchcount, a divrem, a tablewalk, a decompress, a limbproduct, a modmul, a moddiv or an ecadd circuit")
+if a.solve and not a.circuit.startswith(("mimc", "arx", "matchcount", "divrem", "tablewalk", "decompress", "limbproduct", "modmul", "moddiv", "ecadd", "rsa", "widediv")):
+    ap.error("--solve needs a mimcK, an arx, a matchcount, a divrem, a tablewalk, a decompress, a limbproduct, a modmul, a moddiv, an ecadd, an rsa or a widediv circuit")
 if a.reorder is not None and not a.solve:
     ap.error("--reorder goes with --solve")
 pm = Polymath(a.curve, a.transcript, device=0)
@@ -144,6 +150,19 @@ elif a.circuit.startswith("ecadd"):
     make = lambda: PC.EcAddChain(ec_points[4 + g.next_u64() % 32], ec_points[1], secp, 64, 4, ec_steps)      # R_t = (k + 5 + 2 t) G, k < 32, is never +-2 G: no chord without a slope
     again = lambda c: PC.EcAddChain(c.point, c.addend, c.modulus, c.n, c.limbs, c.steps, c.decompose)
     partial_of = lambda c: c.partial(r)
+elif a.circuit.startswith("rsa"):
+    rsa_bits, limb_bits, n_limbs = (int(v) for v in a.circuit.split(":")[1:4]) if ":" in a.circuit else (2048, 64, 32)
+    rsa_n = PC.rsa_modulus(rsa_bits, g.next_u64())[0]          # one key, one literal modulus: the assignments differ in the signature
+    make = lambda: PC.RsaVerify(PC.rsa_modulus(rsa_bits, g.next_u64())[1] % rsa_n, rsa_n, limb_bits, n_limbs)
+    again = lambda c: PC.RsaVerify(c.signature, c.modulus, c.n, c.limbs, c.squarings, c.witness_modulus, c.decompose)
+    partial_of = lambda c: c.partial(r)
+elif a.circuit.startswith("widediv"):
+    n_divs, limb_bits, k_d, k_e = (int(v) for v in a.circuit.split(":")[1:5]) if ":" in a.circuit else (16, 64, 63, 32)
+    draw = lambda bits: sum(g.next_u64() << (64 * i) for i in range(-(-bits // 64))) & ((1 << bits) - 1)
+    make = lambda: PC.LimbDivision([(PC.int_limbs(draw(limb_bits * k_d), limb_bits, k_d), PC.int_limbs(draw(limb_bits * k_e) | 1 << (limb_bits * k_e - 1), limb_bits, k_e))
+                                    for _ in range(n_divs)], limb_bits, k_d, k_e)
+    again = lambda c: PC.LimbDivision(c.cases, c.n, c.kq, c.kr, c.divisor, c.wide, c.stuck)
+    partial_of = lambda c: c.partial(r)
 else:
     nc = int(a.circuit.split(":", 1)[1])
     make = lambda: PC.BenchCircuit(g.fr(r), g.fr(r), 10, nc)
@@ -158,7 +177,7 @@ circuits = [make() for _ in range(distinct)]
 t0 = time.time()
 pk = pm.setup(stored(circuits[0]), g.fr(r), g.fr(r))
 setup_s = time.time() - t0
-if a.circuit.startswith(("modmul", "moddiv", "ecadd")):
+if a.circuit.startswith(("modmul", "moddiv", "ecadd", "rsa", "widediv")):
     pm.set_hints(pk, circuits[0].hints(2))       # the long and the modular divisions are part of the circuit: declared once, with the key
 rows = []
 for c in circuits:
