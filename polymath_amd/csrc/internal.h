@@ -90,6 +90,14 @@ struct DevBuf {
     }
     template <class T>
     T *as() const { return (T *)p; }
+    // v to the buffer's start, grown to hold it, by an asynchronous copy on `stream` (v must live until it has run); an empty v
+    // touches nothing
+    template <class T>
+    hipError_t upload(const std::vector<T> &v, hipStream_t stream) {
+        if (v.empty()) return hipSuccess;
+        const hipError_t e = reserve(v.size() * sizeof(T));
+        return e != hipSuccess ? e : hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream);
+    }
 };
 
 // A DevBuf that lives for one call: released on every way out of its scope.  DevBuf itself has no destructor because the context's
@@ -187,10 +195,9 @@ struct GlueWs {
 struct SolveWs {
     DevBuf xw, pattern, mismatch, stuck, steps, bit_cols, pairs, divs, blocks, block_idx, block_inv, hints, hint_idx, mods;
     pmsolve::Plan plan;
-    size_t n_pairs = 0;                  // is-zero pairs of the plan: records in `pairs`
-    size_t n_divs = 0;                   // division rows of the plan: records in `divs`
-    size_t n_blocks = 0;                 // linear blocks of the plan: records in `blocks`, rows and columns in `block_idx`, inverses in `block_inv`
-    size_t n_hints = 0;                  // long divisions of the plan: records in `hints`, columns and literal divisors in `hint_idx`
+    // per plan.pairs / plan.divs / plan.blocks one record in `pairs` / `divs` / `blocks` (the blocks' rows and columns in `block_idx`,
+    // their inverses in `block_inv`); plan.hints divides into the two record arrays that solve_plan counts:
+    size_t n_hints = 0;                  // long divisions of the plan, wide ones included: records in `hints`, columns and literal divisors in `hint_idx`
     size_t n_mods = 0;                   // modular divisions of the plan: records in `mods`, columns and literal moduli in `hint_idx` as well
     uint64_t plan_key = 0;               // pm_pk::serial of the plan's key; 0 = no plan
     uint64_t plan_hint_gen = 0;          // pm_pk::hint_gen of the plan's key when the plan was made

@@ -2,66 +2,73 @@
 // (include/polymath_hip.h), so that a caller supplies only the values it chooses and the library computes the rest
 // before it checks or proves.  The PLAN -- which row determines which column, in which order -- is host work, done once per (key,
 // pattern) by host/solve_plan.hpp; what ONE step does to ONE assignment (solve_step, solve_bits, solve_iszero, solve_divrem,
-// solve_indicator, solve_sqrt, solve_block, solve_longdiv, solve_moddiv, solve_longdiv_wide and its longdiv_wide_words, the dispatch solve_any, the inverses' solve_inverse and solve_block_invert, and the records
-// a plan becomes: solve_records) is
-// solve_steps.cuh, text that the CPU self-tests run as well; this file is the kernels that call it and the host driver,
-// assignment = grid y (or the lane, in the chain kernel):
+// solve_indicator, solve_sqrt, solve_block, solve_longdiv, solve_moddiv, solve_longdiv_wide and its longdiv_wide_words, the dispatch
+// solve_any, the inverses' solve_inverse and solve_block_invert, and the records a plan becomes: solve_records) is solve_steps.cuh,
+// text that the CPU self-tests run as well; this file is the kernels that call it and the host driver, assignment = grid y (or the
+// lane, in the chain kernel).  Before the plan's launches:
 //   k_solve_pattern   one lane per (column, assignment): the unknown pattern of assignment 0 (a byte per column: 1 the unknown
-//                     marker, 2 the quotient marker, 3 the indicator marker, 4 the square-root marker); every other assignment is compared with it, byte for byte, and the first
-//                     differing (assignment, column) lowers one word
+//                     marker, 2 the quotient marker, 3 the indicator marker, 4 the square-root marker); every other assignment is
+//                     compared with it, byte for byte, and the first differing (assignment, column) lowers one word
 //   k_solve_inv       one lane per step, once per plan: 1 / coefficient of the step's unknown (a division row: 1 / cq); two more
 //                     lanes per is-zero pair: 1 / cm and 1 / cb of its opener; an indicator step needs none and its record is left alone
-//   k_solve_level     a WIDE dependency level: one lane per (step, assignment); a level is its own launch, so stream order is
-//                     the dependency order
-//   k_solve_bits      the bit decompositions of a wide level, one lane per (step, assignment) as well: a launch of their own, so
-//                     that lanes doing one store do not sit beside lanes doing k
-//   k_solve_iszero    the is-zero pairs of a wide level, one lane per (step, assignment) as well: two stores and one inversion each
-//   k_solve_divrem    the division rows of a wide level, one lane per (step, assignment) as well: two stores and one 256-bit
-//                     integer division each (divrem.cuh: a fixed trip count, so a wave does not diverge on operand size)
-//   k_solve_indicator the indicator rows of a wide level, one lane per (step, assignment) as well: one dot product over the guard's
-//                     known side, a zero test and one store of field one under a mask; no division
-//   k_solve_sqrt      the square-root rows of a wide level, one lane per (step, assignment) as well: one dot product over C_r, one
-//                     multiplication by 1 / (ka kb) and one constant-time Tonelli-Shanks (sqrt.cuh: a fixed trip count, so a wave does
-//                     not diverge on the operand); a non-residue is stuck at the row
-//   k_solve_block     the linear blocks of a level, whatever its width: one WAVE per (block, assignment), four to a workgroup.  Lane
-//                     i < k forms the right-hand side of row i into LDS, lane j < k accumulates column j from the LDS values and the
-//                     transposed inverse of the block's matrix, which solve_plan computed on the host once per plan (distinct matrices
-//                     only: solve_steps.cuh, solve_block_invert).  No division, no atomic, never stuck
-//   k_solve_longdiv   the declared long divisions of a level (pm_pk_set_hints), whatever its width: one lane per (hint, assignment).  The
-//                     input limbs leave Montgomery form and are accumulated at bit offset n j into a 1024-bit dividend and a 512-bit
-//                     divisor, a restoring shift-subtract divides in the launch's trip count (wave-uniform: the plan's bound, at most 1024; solve_steps.cuh: longdiv), and the n-bit limbs
-//                     of quotient and remainder are stored.  No register is indexed at run time; stuck at the word nr + h
-//   k_solve_moddiv    the declared modular divisions of a level, Z = (N+ - N-) / (D+ - D-) mod P, whatever its width: one lane per (hint,
-//                     assignment).  The modulus and, one after the other, the four operand lists are accumulated like a dividend;
-//                     each list is reduced modulo P by longdiv (the launch's reduction bound) and folded into N or D by masked
-//                     selects; a binary extended Euclid for odd modulus with masked updates runs the launch's 2 L rounds with the
-//                     numerator in place of 1, so that it ends in Z itself (solve_steps.cuh: modinv_odd proves the bound).  No
-//                     register is indexed at run time; stuck at the word nr + h
-//   k_solve_longdiv_wide  the declared WIDE long divisions of a level (opcode 5: up to 8192 / 4096 bits, RSA-2048), whatever its width: one
-//                     WAVE per (hint, assignment), four to a workgroup.  No lane holds an operand: the 32-bit words of dividend,
-//                     divisor and quotient live in the wave's slice of LDS, lane i working on words i, i + 64, ...  Gather: lane j
-//                     stages limb j out of Montgomery form, the words are column sums of the staged limbs, one carry resolution by
-//                     ballot.  Divide: Knuth's algorithm D in base 2^32, a word of quotient per step (solve_steps.cuh:
-//                     longdiv_wide_words states the recurrence); lane i multiplies divisor word i, carries and borrows by ballot.
-//                     Scatter: lane i cuts limb i and stores it.  Every trip count is wave-uniform; stuck at the word nr + h
-//   k_solve_chain     a run of consecutive NARROW levels: one lane per assignment walks the run's steps in plan order.  A lane
-//                     reads back only its own stores: no barriers, no fences.  The MiMC shape (depth 644, width 1) is one such run
-//                     and the batch is its parallel dimension.
-// The solving kernels exist twice: DIV = false for ranges of kind-C steps only, DIV = true for ranges with kind-A / kind-B steps,
+// Then the launches, one entry per pmsolve::LaunchKind (solve_group's switch): the kernel, what a lane is, whether a step can stick.
+//   LAUNCH_CHAIN      k_solve_chain<DIV>: a run of consecutive NARROW levels: one lane per assignment walks the run's steps in plan
+//                     order.  A lane reads back only its own stores: no barriers, no fences.  The MiMC shape (depth 644, width 1) is
+//                     one such run and the batch is its parallel dimension.  A step sticks as it would in the launch of its kind
+//   LAUNCH_LEVEL      k_solve_level<DIV>: the ordinary steps of a WIDE dependency level: one lane per (step, assignment); a level is
+//                     its own launch, so stream order is the dependency order.  Stuck where a kind-A / kind-B step would divide by zero
+//   LAUNCH_BITS       k_solve_bits<DIV>: the bit decompositions of a wide level, one lane per (step, assignment) as well: a launch of
+//                     their own, so that lanes doing one store do not sit beside lanes doing k.  Stuck, in all its k columns, where
+//                     the value has no k-bit form or the divisor is zero
+//   LAUNCH_ISZERO     k_solve_iszero: the is-zero pairs of a wide level, one lane per (step, assignment) as well: two stores and one
+//                     inversion each.  Never stuck
+//   LAUNCH_DIVREM     k_solve_divrem: the division rows of a wide level, one lane per (step, assignment) as well: two stores and one
+//                     256-bit integer division each (divrem.cuh: a fixed trip count, so a wave does not diverge on operand size).
+//                     Stuck, in both its columns, where the divisor is zero
+//   LAUNCH_INDICATOR  k_solve_indicator: the indicator rows of a wide level, one lane per (step, assignment) as well: one dot product
+//                     over the guard's known side, a zero test and one store of field one under a mask; no division.  Never stuck
+//   LAUNCH_SQRT       k_solve_sqrt: the square-root rows of a wide level, one lane per (step, assignment) as well: one dot product over
+//                     C_r, one multiplication by 1 / (ka kb) and one constant-time Tonelli-Shanks (sqrt.cuh: a fixed trip count, so a
+//                     wave does not diverge on the operand); a non-residue is stuck at the row
+//   LAUNCH_BLOCK      k_solve_block: the linear blocks of a level, whatever its width: one WAVE per (block, assignment), four to a
+//                     workgroup.  Lane i < k forms the right-hand side of row i into LDS, lane j < k accumulates column j from the LDS
+//                     values and the transposed inverse of the block's matrix, which solve_plan computed on the host once per plan
+//                     (distinct matrices only: solve_steps.cuh, solve_block_invert).  No division, no atomic, never stuck
+//   LAUNCH_LONGDIV    k_solve_longdiv: the declared long divisions of a level (pm_pk_set_hints), whatever its width: one lane per
+//                     (hint, assignment).  The input limbs leave Montgomery form and are accumulated at bit offset n j into a 1024-bit
+//                     dividend and a 512-bit divisor, a restoring shift-subtract divides in the launch's trip count (wave-uniform: the
+//                     plan's bound, at most 1024; solve_steps.cuh: longdiv), and the n-bit limbs of quotient and remainder are stored.
+//                     No register is indexed at run time; stuck at the word nr + h
+//   LAUNCH_MODDIV     k_solve_moddiv: the declared modular divisions of a level, Z = (N+ - N-) / (D+ - D-) mod P, whatever its width:
+//                     one lane per (hint, assignment).  The modulus and, one after the other, the four operand lists are accumulated
+//                     like a dividend; each list is reduced modulo P by longdiv (the launch's reduction bound) and folded into N or D
+//                     by masked selects; a binary extended Euclid for odd modulus with masked updates runs the launch's 2 L rounds
+//                     with the numerator in place of 1, so that it ends in Z itself (solve_steps.cuh: modinv_odd proves the bound).
+//                     No register is indexed at run time; stuck at the word nr + h
+//   LAUNCH_LONGDIV_WIDE  k_solve_longdiv_wide: the declared WIDE long divisions of a level (opcode 5: up to 8192 / 4096 bits,
+//                     RSA-2048), whatever its width: one WAVE per (hint, assignment), four to a workgroup.  No lane holds an operand:
+//                     the 32-bit words of dividend, divisor and quotient live in the wave's slice of LDS, lane i working on words i,
+//                     i + 64, ...  Gather: lane j stages limb j out of Montgomery form, the words are column sums of the staged limbs,
+//                     one carry resolution by ballot.  Divide: Knuth's algorithm D in base 2^32, a word of quotient per step
+//                     (solve_steps.cuh: longdiv_wide_words states the recurrence); lane i multiplies divisor word i, carries and
+//                     borrows by ballot.  Scatter: lane i cuts limb i and stores it.  Every trip count is wave-uniform; stuck at the
+//                     word nr + h
+// The chain, level and bits kernels exist twice: DIV = false for ranges of kind-C steps only, DIV = true for ranges with kind-A / kind-B steps,
 // or is-zero pairs, which call inverse<P> (a Fermat chain) -- the plan sorts a level by kind, so kind-C ranges do not carry its
 // registers, and the is-zero step and the division step (a dividing one by the plan's count, for 1 / cq) exist in the DIV = true
 // chain only.  The indicator step does not divide: it is a branch of BOTH chain instantiations.  The square-root step (a dividing one
-// by the plan's count, for 1 / (ka kb)) exists in the DIV = true chain only.
-//   k_solve_stuck_row after the launches of a REORDERED plan (build_plan_any_order found a dependency order that is not the matrix
-//                     order): one lane per assignment turns the stuck word's (level, row) into the row
+// by the plan's count, for 1 / (ka kb)) exists in the DIV = true chain only.  solve_plan checks every launch against the plan's table
+// (pmsolve::KIND_INFO) before any of this runs.  After the launches:
+//   k_solve_stuck_row of a REORDERED plan (build_plan_any_order found a dependency order that is not the matrix order): one lane per
+//                     assignment turns the stuck word's (level, row) into the row
 // A step that would divide by zero stores zero and lowers the assignment's stuck word to its row (64-bit atomic minimum: the same
 // word on every run); so does a decomposition whose value has no k-bit form, in all its k columns, and a division row whose
 // divisor is zero, in both its columns, and a square-root row whose value is a non-residue.  In matrix order everything
 // downstream of a stuck row has a larger row, so the minimum is the root cause.  Under a reordered plan that is false -- a step that
 // reads the stored zero may stick too, at a smaller row -- so the word is lowered to (level << 32) | row there: the minimum is the
-// stuck step of lowest level, then smallest row, which read only valid values, and k_solve_stuck_row leaves its row in the word.  Every other store has one
-// writer.  An is-zero pair never sticks: where the tested value is zero its multiplier is free and is stored as zero.  Plain C++ and
-// vector stores only.
+// stuck step of lowest level, then smallest row, which read only valid values, and k_solve_stuck_row leaves its row in the word.
+// Every other store has one writer.  An is-zero pair never sticks: where the tested value is zero its multiplier is free and is
+// stored as zero.  Plain C++ and vector stores only.
 #include <cstring>
 #include <vector>
 
@@ -517,23 +524,31 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
         ctx->err = "pm solve: " + sv.plan.message;
         return PM_ERR_INVALID_ARG;
     }
-    // the DIV = false kernels have no is-zero step, no division step and no square-root step in them: a range with one must be a dividing one
+    // every launch against KIND_INFO: a step of a chain must be one that a lane can walk, a step of any other launch must map to that
+    // launch's kind, and a dividing kind needs a dividing launch -- the DIV = false kernels have no is-zero step, no division step and
+    // no square-root step in them, and no inverse<P>
     for (const pmsolve::Launch &l : sv.plan.launches)
-        for (uint32_t t = l.lo; t < l.hi && !l.divides; ++t)
-            if (sv.plan.steps[t].kind == pmsolve::KIND_ISZERO || sv.plan.steps[t].kind == pmsolve::KIND_DIVREM || sv.plan.steps[t].kind == pmsolve::KIND_SQRT) {
+        for (uint32_t t = l.lo; t < l.hi; ++t) {
+            const pmsolve::Step &s = sv.plan.steps[t];
+            const pmsolve::KindInfo info = s.kind < pmsolve::NUM_WIDE_KINDS ? pmsolve::KIND_INFO[s.kind] : pmsolve::KindInfo{0xff, 0, 0};
+            const char *why = l.kind == pmsolve::LAUNCH_CHAIN ? (info.chained ? nullptr : "into a chain, where no lane can walk it")
+                              : info.launch != l.kind         ? "into a launch of another kind"
+                                                              : nullptr;
+            if (!why && info.divides && !l.divides) why = "into a launch that does not divide";
+            if (why) {
                 ctx->err = std::string("pm solve: the plan puts the ") +
-                           (sv.plan.steps[t].kind == pmsolve::KIND_ISZERO ? "is-zero pair" : sv.plan.steps[t].kind == pmsolve::KIND_SQRT ? "square root" : "division") + " of row " +
-                           std::to_string(sv.plan.steps[t].row) + " into a launch that does not divide";
+                           (s.kind == pmsolve::KIND_ISZERO ? "is-zero pair" : s.kind == pmsolve::KIND_SQRT ? "square root" : s.kind == pmsolve::KIND_DIVREM ? "division" : "step") +
+                           " of row " + std::to_string(s.row) + " " + why;
                 return PM_ERR_STATE;
             }
+        }
     const size_t n_steps = sv.plan.steps.size();
-    sv.n_pairs = sv.n_divs = sv.n_blocks = sv.n_hints = sv.n_mods = 0;
+    sv.n_hints = sv.n_mods = 0;
     if (n_steps) {
         SolveRecords<P> rec = solve_records<P>(sv.plan);
         // the linear blocks' matrices are constants of the key: each distinct one is inverted here, once per plan, from the words the
         // planner copied out of C; a singular one refuses the call before any assignment is touched
-        sv.n_blocks = rec.blocks.size();
-        if (sv.n_blocks) {
+        if (!rec.blocks.empty()) {
             uint32_t column = 0;
             const size_t bad = solve_block_inverses<P>(sv.plan, rec, &column);
             if (bad != sv.plan.blocks.size()) {
@@ -547,47 +562,22 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
                            std::to_string(blk.cols[column]) + ")";
                 return PM_ERR_INVALID_ARG;
             }
-            PM_HIP(ctx, sv.blocks.reserve(sv.n_blocks * sizeof(SolveBlockDev)));
-            PM_HIP(ctx, hipMemcpyAsync(sv.blocks.p, rec.blocks.data(), sv.n_blocks * sizeof(SolveBlockDev), hipMemcpyHostToDevice, st));
-            PM_HIP(ctx, sv.block_idx.reserve(rec.block_idx.size() * sizeof(uint32_t)));
-            PM_HIP(ctx, hipMemcpyAsync(sv.block_idx.p, rec.block_idx.data(), rec.block_idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            PM_HIP(ctx, sv.block_inv.reserve(rec.block_inv.size() * sizeof(Fp<P>)));
-            PM_HIP(ctx, hipMemcpyAsync(sv.block_inv.p, rec.block_inv.data(), rec.block_inv.size() * sizeof(Fp<P>), hipMemcpyHostToDevice, st));
         }
         sv.n_hints = rec.hints.size();
         sv.n_mods = rec.mods.size();
-        if (sv.n_hints) {
-            PM_HIP(ctx, sv.hints.reserve(sv.n_hints * sizeof(SolveHintDev)));
-            PM_HIP(ctx, hipMemcpyAsync(sv.hints.p, rec.hints.data(), sv.n_hints * sizeof(SolveHintDev), hipMemcpyHostToDevice, st));
-        }
-        if (sv.n_mods) {
-            PM_HIP(ctx, sv.mods.reserve(sv.n_mods * sizeof(SolveModDev)));
-            PM_HIP(ctx, hipMemcpyAsync(sv.mods.p, rec.mods.data(), sv.n_mods * sizeof(SolveModDev), hipMemcpyHostToDevice, st));
-        }
-        if (sv.n_hints || sv.n_mods) {
-            PM_HIP(ctx, sv.hint_idx.reserve(rec.hint_idx.size() * sizeof(uint32_t)));
-            PM_HIP(ctx, hipMemcpyAsync(sv.hint_idx.p, rec.hint_idx.data(), rec.hint_idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        }
-        sv.n_pairs = rec.pairs.size();
-        if (sv.n_pairs) {
-            PM_HIP(ctx, sv.pairs.reserve(sv.n_pairs * sizeof(SolvePairDev<P>)));
-            PM_HIP(ctx, hipMemcpyAsync(sv.pairs.p, rec.pairs.data(), sv.n_pairs * sizeof(SolvePairDev<P>), hipMemcpyHostToDevice, st));
-        }
-        sv.n_divs = rec.divs.size();
-        if (sv.n_divs) {
-            PM_HIP(ctx, sv.divs.reserve(sv.n_divs * sizeof(SolveDivDev)));
-            PM_HIP(ctx, hipMemcpyAsync(sv.divs.p, rec.divs.data(), sv.n_divs * sizeof(SolveDivDev), hipMemcpyHostToDevice, st));
-        }
-        const std::vector<uint32_t> &bit_cols = sv.plan.bit_cols;
-        if (!bit_cols.empty()) {
-            PM_HIP(ctx, sv.bit_cols.reserve(bit_cols.size() * sizeof(uint32_t)));
-            PM_HIP(ctx, hipMemcpyAsync(sv.bit_cols.p, bit_cols.data(), bit_cols.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        }
-        PM_HIP(ctx, sv.steps.reserve(n_steps * sizeof(SolveStepDev<P>)));
-        PM_HIP(ctx, hipMemcpyAsync(sv.steps.p, rec.steps.data(), n_steps * sizeof(SolveStepDev<P>), hipMemcpyHostToDevice, st));
-        PM_LAUNCH(ctx, k_solve_inv<P>, dim3(nblk(n_steps + 2 * sv.n_pairs)), dim3(256), 0, st, csr_dev(pk, 0), csr_dev(pk, 1), csr_dev(pk, 2),
-                       sv.steps.as<SolveStepDev<P>>(), (uint64_t)n_steps, sv.n_pairs ? sv.pairs.as<SolvePairDev<P>>() : nullptr, (uint64_t)sv.n_pairs,
-                       sv.n_divs ? sv.divs.as<SolveDivDev>() : nullptr);
+        PM_HIP(ctx, sv.blocks.upload(rec.blocks, st));
+        PM_HIP(ctx, sv.block_idx.upload(rec.block_idx, st));
+        PM_HIP(ctx, sv.block_inv.upload(rec.block_inv, st));
+        PM_HIP(ctx, sv.hints.upload(rec.hints, st));
+        PM_HIP(ctx, sv.mods.upload(rec.mods, st));
+        PM_HIP(ctx, sv.hint_idx.upload(rec.hint_idx, st));
+        PM_HIP(ctx, sv.pairs.upload(rec.pairs, st));
+        PM_HIP(ctx, sv.divs.upload(rec.divs, st));
+        PM_HIP(ctx, sv.bit_cols.upload(sv.plan.bit_cols, st));
+        PM_HIP(ctx, sv.steps.upload(rec.steps, st));
+        PM_LAUNCH(ctx, k_solve_inv<P>, dim3(nblk(n_steps + 2 * rec.pairs.size())), dim3(256), 0, st, csr_dev(pk, 0), csr_dev(pk, 1), csr_dev(pk, 2),
+                       sv.steps.as<SolveStepDev<P>>(), (uint64_t)n_steps, rec.pairs.empty() ? nullptr : sv.pairs.as<SolvePairDev<P>>(), (uint64_t)rec.pairs.size(),
+                       rec.divs.empty() ? nullptr : sv.divs.as<SolveDivDev>());
         PM_HIP(ctx, hipStreamSynchronize(st));   // `rec` goes out of scope
     }
     sv.plan_pattern.swap(pattern);
@@ -611,41 +601,60 @@ int solve_group(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t 
     const Csr A = csr_dev(pk, 0), B = csr_dev(pk, 1), Cm = csr_dev(pk, 2);
     const SolveStepDev<P> *steps = sv.steps.as<SolveStepDev<P>>();
     const uint32_t *bit_cols = sv.plan.bit_cols.empty() ? nullptr : sv.bit_cols.as<uint32_t>();
-    const SolvePairDev<P> *pairs = sv.n_pairs ? sv.pairs.as<SolvePairDev<P>>() : nullptr;
-    const SolveDivDev *divs = sv.n_divs ? sv.divs.as<SolveDivDev>() : nullptr;
+    const SolvePairDev<P> *pairs = sv.plan.pairs.empty() ? nullptr : sv.pairs.as<SolvePairDev<P>>();
+    const SolveDivDev *divs = sv.plan.divs.empty() ? nullptr : sv.divs.as<SolveDivDev>();
+    const SolveHintDev *hints = sv.hints.as<SolveHintDev>();
+    const uint32_t *hint_idx = sv.hint_idx.as<uint32_t>();
     {
         StageTimer t(ctx, timing_slot);
         for (const pmsolve::Launch &l : sv.plan.launches) {
-            if (l.block) {
-                if (!sv.n_blocks) return PM_ERR_STATE;
-                hipLaunchKernelGGL((k_solve_block<P>), dim3(nblk(l.hi - l.lo, 4), (unsigned)g), dim3(256), 0, st, A, B, Cm, steps, sv.blocks.as<SolveBlockDev>(),
-                                   sv.block_idx.as<uint32_t>(), sv.block_inv.as<Fp<P>>(), l.lo, l.hi, d_xw, ncols);
-            } else if (l.longdiv) {
+            const uint32_t count = l.hi - l.lo;
+            const dim3 lanes(nblk(count), (unsigned)g), waves(nblk(count, 4), (unsigned)g), hint_lanes(nblk(count, 64), (unsigned)g), chain(nblk(g, 64));
+            switch (l.kind) {   // the cases stand in the order the kernels have in the code object: they are instantiated here
+            case pmsolve::LAUNCH_BLOCK:
+                if (sv.plan.blocks.empty()) return PM_ERR_STATE;
+                hipLaunchKernelGGL((k_solve_block<P>), waves, dim3(256), 0, st, A, B, Cm, steps, sv.blocks.as<SolveBlockDev>(), sv.block_idx.as<uint32_t>(),
+                                   sv.block_inv.as<Fp<P>>(), l.lo, l.hi, d_xw, ncols);
+                break;
+            case pmsolve::LAUNCH_LONGDIV:
                 if (!sv.n_hints || l.rounds < 256 || l.rounds > 1024) return PM_ERR_STATE;
-                hipLaunchKernelGGL((k_solve_longdiv<P>), dim3(nblk(l.hi - l.lo, 64), (unsigned)g), dim3(64), 0, st, steps, sv.hints.as<SolveHintDev>(),
-                                   sv.hint_idx.as<uint32_t>(), l.rounds, l.lo, l.hi, d_xw, ncols, stuck);
-            } else if (l.moddiv) {
+                hipLaunchKernelGGL((k_solve_longdiv<P>), hint_lanes, dim3(64), 0, st, steps, hints, hint_idx, l.rounds, l.lo, l.hi, d_xw, ncols, stuck);
+                break;
+            case pmsolve::LAUNCH_MODDIV:
                 if (!sv.n_mods || l.rounds < 256 || l.rounds > 1024 || l.inv_rounds < 512 || l.inv_rounds > 1024) return PM_ERR_STATE;
-                hipLaunchKernelGGL((k_solve_moddiv<P>), dim3(nblk(l.hi - l.lo, 64), (unsigned)g), dim3(64), 0, st, steps, sv.mods.as<SolveModDev>(),
-                                   sv.hint_idx.as<uint32_t>(), l.rounds, l.inv_rounds, l.lo, l.hi, d_xw, ncols, stuck);
-            } else if (l.longdiv_wide) {
+                hipLaunchKernelGGL((k_solve_moddiv<P>), hint_lanes, dim3(64), 0, st, steps, sv.mods.as<SolveModDev>(), hint_idx, l.rounds, l.inv_rounds, l.lo, l.hi, d_xw,
+                                   ncols, stuck);
+                break;
+            case pmsolve::LAUNCH_LONGDIV_WIDE:
                 if (!sv.n_hints || l.rounds < 256 || l.rounds > pmsolve::WIDE_D_BITS) return PM_ERR_STATE;
-                hipLaunchKernelGGL((k_solve_longdiv_wide<P>), dim3(nblk(l.hi - l.lo, 4), (unsigned)g), dim3(256), 0, st, steps, sv.hints.as<SolveHintDev>(),
-                                   sv.hint_idx.as<uint32_t>(), l.lo, l.hi, d_xw, ncols, stuck);
-            } else if (l.chain) {
-                const dim3 grid(nblk(g, 64)), block(64);
-                if (l.divides) hipLaunchKernelGGL((k_solve_chain<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, pairs, divs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
-                else hipLaunchKernelGGL((k_solve_chain<P, false>), grid, block, 0, st, A, B, Cm, steps, bit_cols, pairs, divs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
-            } else {
-                const dim3 grid(nblk(l.hi - l.lo), (unsigned)g), block(256);
-                if (l.sqrt) hipLaunchKernelGGL((k_solve_sqrt<P>), grid, block, 0, st, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck);
-                else if (l.indicator) hipLaunchKernelGGL((k_solve_indicator<P>), grid, block, 0, st, A, B, steps, l.lo, l.hi, d_xw, ncols);
-                else if (l.divrem) hipLaunchKernelGGL((k_solve_divrem<P>), grid, block, 0, st, A, B, Cm, steps, divs, l.lo, l.hi, d_xw, ncols, stuck);
-                else if (l.iszero) hipLaunchKernelGGL((k_solve_iszero<P>), grid, block, 0, st, A, B, Cm, steps, pairs, l.lo, l.hi, d_xw, ncols);
-                else if (l.bits && l.divides) hipLaunchKernelGGL((k_solve_bits<P, true>), grid, block, 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck);
-                else if (l.bits) hipLaunchKernelGGL((k_solve_bits<P, false>), grid, block, 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck);
-                else if (l.divides) hipLaunchKernelGGL((k_solve_level<P, true>), grid, block, 0, st, A, B, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck);
-                else hipLaunchKernelGGL((k_solve_level<P, false>), grid, block, 0, st, A, B, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck);
+                hipLaunchKernelGGL((k_solve_longdiv_wide<P>), waves, dim3(256), 0, st, steps, hints, hint_idx, l.lo, l.hi, d_xw, ncols, stuck);
+                break;
+            case pmsolve::LAUNCH_CHAIN:
+                if (l.divides) hipLaunchKernelGGL((k_solve_chain<P, true>), chain, dim3(64), 0, st, A, B, Cm, steps, bit_cols, pairs, divs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
+                else hipLaunchKernelGGL((k_solve_chain<P, false>), chain, dim3(64), 0, st, A, B, Cm, steps, bit_cols, pairs, divs, l.lo, l.hi, d_xw, ncols, stuck, (uint64_t)g);
+                break;
+            case pmsolve::LAUNCH_SQRT:
+                hipLaunchKernelGGL((k_solve_sqrt<P>), lanes, dim3(256), 0, st, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck);
+                break;
+            case pmsolve::LAUNCH_INDICATOR:
+                hipLaunchKernelGGL((k_solve_indicator<P>), lanes, dim3(256), 0, st, A, B, steps, l.lo, l.hi, d_xw, ncols);
+                break;
+            case pmsolve::LAUNCH_DIVREM:
+                hipLaunchKernelGGL((k_solve_divrem<P>), lanes, dim3(256), 0, st, A, B, Cm, steps, divs, l.lo, l.hi, d_xw, ncols, stuck);
+                break;
+            case pmsolve::LAUNCH_ISZERO:
+                hipLaunchKernelGGL((k_solve_iszero<P>), lanes, dim3(256), 0, st, A, B, Cm, steps, pairs, l.lo, l.hi, d_xw, ncols);
+                break;
+            case pmsolve::LAUNCH_BITS:
+                if (l.divides) hipLaunchKernelGGL((k_solve_bits<P, true>), lanes, dim3(256), 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck);
+                else hipLaunchKernelGGL((k_solve_bits<P, false>), lanes, dim3(256), 0, st, A, B, Cm, steps, bit_cols, l.lo, l.hi, d_xw, ncols, stuck);
+                break;
+            case pmsolve::LAUNCH_LEVEL:
+                if (l.divides) hipLaunchKernelGGL((k_solve_level<P, true>), lanes, dim3(256), 0, st, A, B, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck);
+                else hipLaunchKernelGGL((k_solve_level<P, false>), lanes, dim3(256), 0, st, A, B, Cm, steps, l.lo, l.hi, d_xw, ncols, stuck);
+                break;
+            default:
+                return PM_ERR_STATE;
             }
             PM_HIP(ctx, hipGetLastError());
         }

@@ -208,6 +208,25 @@ PM_HD void add_shifted_words(uint32_t *acc, uint32_t W, const uint32_t v[8], uin
     }
 }
 
+// A literal divisor or modulus, a constant of the key, accumulated once per plan: onto `pool` the W words (16, or the wide division's
+// 128) of the sum of the literal's limbs at bit offset n j, then ONE word that is non-zero exactly where the sum reaches 2^(32 W).  The
+// sum is formed in WIDE_SUM_E words, which lose nothing at either width: n j + 288 <= 32 WIDE_SUM_E under both records' limits
+inline void literal_words(const pmsolve::Hint &h, int W, std::vector<uint32_t> &pool) {
+    static_assert(pmsolve::HINT_MAX_N * (pmsolve::HINT_MAX_KE - 1) + 288 <= 32u * WIDE_SUM_E && pmsolve::WIDE_E_BITS - 1 + 288 <= 32u * WIDE_SUM_E, "no bit is lost");
+    uint32_t E[WIDE_SUM_E] = {0}, above = 0;
+    for (size_t j = 0; j < h.lit.size() / 4; ++j) {
+        uint32_t v[8];
+        for (int i = 0; i < 4; ++i) {
+            v[2 * i] = (uint32_t)h.lit[4 * j + i];
+            v[2 * i + 1] = (uint32_t)(h.lit[4 * j + i] >> 32);
+        }
+        add_shifted_words(E, WIDE_SUM_E, v, h.n * (uint32_t)j);
+    }
+    for (int w = W; w < WIDE_SUM_E; ++w) above |= E[w];
+    pool.insert(pool.end(), E, E + W);
+    pool.push_back(above);
+}
+
 template <class P>
 inline SolveRecords<P> solve_records(const pmsolve::Plan &plan) {
     SolveRecords<P> rec;
@@ -247,32 +266,7 @@ inline SolveRecords<P> solve_records(const pmsolve::Plan &plan) {
                 rec.hints.push_back(SolveHintDev{h.n, (uint32_t)h.q.size(), (uint32_t)h.rem.size(), (uint32_t)h.D.size(), kE, literal ? 1u : 0u, off, 0});
             }
             for (const std::vector<uint32_t> *cols : {&h.q, &h.rem, &h.D, &h.E}) rec.hint_idx.insert(rec.hint_idx.end(), cols->begin(), cols->end());
-            if (literal && s.kind == pmsolve::KIND_LONGDIV_WIDE) {   // the wide divisor: 128 words and the lost word
-                uint32_t E[WIDE_SUM_E] = {0}, lost = 0;
-                for (size_t j = 0; j < h.lit.size() / 4; ++j) {
-                    uint32_t v[8];
-                    for (int i = 0; i < 4; ++i) {
-                        v[2 * i] = (uint32_t)h.lit[4 * j + i];
-                        v[2 * i + 1] = (uint32_t)(h.lit[4 * j + i] >> 32);
-                    }
-                    add_shifted_words(E, WIDE_SUM_E, v, h.n * (uint32_t)j);
-                }
-                for (int w = WIDE_WE; w < WIDE_SUM_E; ++w) lost |= E[w];
-                rec.hint_idx.insert(rec.hint_idx.end(), E, E + WIDE_WE);
-                rec.hint_idx.push_back(lost);
-            } else if (literal) {   // the divisor (the modulus) is a constant of the key: accumulated once, here
-                uint32_t E[LONGDIV_WE] = {0}, lost = 0;
-                for (size_t j = 0; j < h.lit.size() / 4; ++j) {
-                    uint32_t v[8];
-                    for (int i = 0; i < 4; ++i) {
-                        v[2 * i] = (uint32_t)h.lit[4 * j + i];
-                        v[2 * i + 1] = (uint32_t)(h.lit[4 * j + i] >> 32);
-                    }
-                    lost |= add_shifted<LONGDIV_WE>(E, v, h.n * (uint32_t)j);
-                }
-                rec.hint_idx.insert(rec.hint_idx.end(), E, E + LONGDIV_WE);
-                rec.hint_idx.push_back(lost);
-            }
+            if (literal) literal_words(h, s.kind == pmsolve::KIND_LONGDIV_WIDE ? WIDE_WE : LONGDIV_WE, rec.hint_idx);
         }
         if (s.kind != pmsolve::KIND_ISZERO) continue;
         d.bits = (uint32_t)rec.pairs.size();

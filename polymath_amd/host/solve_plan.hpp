@@ -137,7 +137,7 @@
 //                 planner multiplies nothing, and 10 000 products at the same points share one Vandermonde matrix.  The driver
 //                 inverts each distinct matrix once per plan (solve_steps.cuh: solve_block_invert) and refuses a singular one; the
 //                 step is then  z_S = M^-1 (A z B z - C_known z)  over the k rows: no division, never stuck.  Step::row / col name
-//                 the smallest row and column, Step::pos is not used.  A block step is a launch of its own (Launch::block), whatever
+//                 the smallest row and column, Step::pos is not used.  A block step is a launch of its own (LAUNCH_BLOCK), whatever
 //                 the level's width.  Pattern bytes 2, 3 and 4 on a column of S have no meaning there.  The rule is the scheduler's:
 //                 build_plan refuses the first such row as it always did.  A set of more than 64 columns keeps waiting, and the
 //                 refusal then ends ", and no linear block: k unknowns exceed 64"; fewer than k linear rows for a set is the refusal
@@ -162,7 +162,7 @@
 //                 E >= 2^512, q >= 2^(n kq), rem >= 2^(n kr).  Step::row is nr + h for hint h of the declaration -- a value no row
 //                 has, and the stuck word of the step; Step::col is its first quotient column, Step::cols_off its entry of
 //                 Plan::hints.  Hint steps sort last within a level, after the blocks, and are a launch of their own
-//                 (Launch::longdiv, not dividing) whatever the level's width; Launch::rounds is the division's trip count for the launch, the
+//                 (LAUNCH_LONGDIV, not dividing) whatever the level's width; Launch::rounds is the division's trip count for the launch, the
 //                 largest min(1024, n (kD - 1) + 256) of its hints.  A hint that never becomes ready is refused as
 //                 "hint h: input column c is never determined", followed by the scheduler's text for the first column that stays unknown.
 //                 Not handled by the long-division record: other opcodes (modular inverse, gcd, sorting), signed limbs, dividends beyond 1024 bits (RSA-2048),
@@ -179,7 +179,7 @@
 //                 inverse), D = D+ - D- and P the modulus, the step stores the kz n-bit limbs of the unique Z in [0, P) with
 //                 Z D = N (mod P).  Stuck, with zero in every output: P even or P < 3, P >= 2^512, N+, N-, D+ or D- >= 2^1024,
 //                 gcd(D mod P, P) != 1 (D = 0 mod P included; P need not be prime), Z >= 2^(n kz).  The modular hints of a level
-//                 sort after its long divisions and are a launch of their own (Launch::moddiv; longdiv and block are 0 on it) with
+//                 sort after its long divisions and are a launch of their own (LAUNCH_MODDIV) with
 //                 two trip counts: Launch::rounds, the largest min(1024, n (k - 1) + 256) over the operand lists of its hints (the
 //                 reductions modulo P), and Launch::inv_rounds = 2 L, L the largest min(512, n (kP - 1) + 256) (the inversion).
 //                 Not handled: even moduli, operands beyond 1024 bits, the slope of a doubling as one hint (3 X^2 / 2 Y: the
@@ -194,8 +194,8 @@
 //                 at 1 + max level of its inputs, Step::row = nr + h, Step::col its first quotient column, Step::cols_off its entry
 //                 of Plan::hints, and stores the kq n-bit limbs of floor(D / E) and the kr n-bit limbs of D mod E.  Stuck, with zero
 //                 in every output: E = 0, D >= 2^8192, E >= 2^4096, q >= 2^(n kq), rem >= 2^(n kr).  The wide hints of a level sort
-//                 last, after its modular ones, and are a launch of their own (Launch::longdiv_wide; longdiv, moddiv and block are 0
-//                 on it: a WAVE per hint, not a lane); Launch::rounds is the largest min(8192, n (kD - 1) + 256) of the range, a bound
+//                 last, after its modular ones, and are a launch of their own (LAUNCH_LONGDIV_WIDE: a WAVE per hint,
+//                 not a lane); Launch::rounds is the largest min(8192, n (kD - 1) + 256) of the range, a bound
 //                 that sizes things -- the division's trip counts follow the operands (solve_steps.cuh: longdiv_wide_words).
 //                 Opcode 1 is not widened: its limits, its kernel and its plans are what they were.
 //                 Not handled: modular division at these widths (HINT_MODDIV keeps 1024 / 512 bits), even moduli, linear blocks
@@ -243,6 +243,36 @@ constexpr uint32_t NUM_PLAN_KINDS = 12;  // with KIND_LONGDIV, which no row make
 constexpr uint32_t NUM_HINT_KINDS = 13;  // with KIND_MODDIV: the key width of finish_plan's counting sort now (NUM_PLAN_KINDS stays what it counted when kind 11 came)
 constexpr uint32_t NUM_WIDE_KINDS = 14;  // with KIND_LONGDIV_WIDE: the key width of finish_plan's counting sort now (NUM_HINT_KINDS stays what it counted when kind 12 came)
 constexpr uint32_t MAX_BLOCK = 64;       // the largest linear block: one wave, a lane per row and per column
+
+// What a launch does with its steps [lo, hi): LAUNCH_CHAIN, one lane per assignment walks them in order, through consecutive narrow
+// levels; every other kind, one lane (LAUNCH_BLOCK and LAUNCH_LONGDIV_WIDE: one wave) per (step, assignment), and every step has the
+// step kinds that KIND_INFO maps to that launch kind, all of one level.  LAUNCH_LEVEL: the ordinary steps.
+enum LaunchKind : uint8_t { LAUNCH_CHAIN, LAUNCH_LEVEL, LAUNCH_BITS, LAUNCH_ISZERO, LAUNCH_DIVREM, LAUNCH_INDICATOR, LAUNCH_SQRT,
+                            LAUNCH_BLOCK, LAUNCH_LONGDIV, LAUNCH_MODDIV, LAUNCH_LONGDIV_WIDE };
+
+// What "a kind of step" means to the schedule, per step kind: the launch kind it gets in a wide level; whether it counts as dividing
+// (KIND_DIVREM for 1 / cq, KIND_SQRT for 1 / (ka kb); KIND_INDICATOR, the blocks and the declared hints do not); whether one lane can
+// walk it in a chain (the blocks and the wide hints take a wave, the hints a launch's trip counts: always launches of their own).
+// finish_plan builds the launches from it, the driver and the CPU rig check a plan against it.
+struct KindInfo {
+    uint8_t launch, divides, chained;
+};
+constexpr KindInfo KIND_INFO[NUM_WIDE_KINDS] = {
+    {LAUNCH_LEVEL, 0, 1},      // KIND_C
+    {LAUNCH_LEVEL, 1, 1},      // KIND_A
+    {LAUNCH_LEVEL, 1, 1},      // KIND_B
+    {LAUNCH_BITS, 0, 1},       // KIND_BITS_C
+    {LAUNCH_BITS, 1, 1},       // KIND_BITS_A
+    {LAUNCH_BITS, 1, 1},       // KIND_BITS_B
+    {LAUNCH_ISZERO, 1, 1},     // KIND_ISZERO
+    {LAUNCH_DIVREM, 1, 1},     // KIND_DIVREM
+    {LAUNCH_INDICATOR, 0, 1},  // KIND_INDICATOR
+    {LAUNCH_SQRT, 1, 1},       // KIND_SQRT
+    {LAUNCH_BLOCK, 0, 0},      // KIND_BLOCK
+    {LAUNCH_LONGDIV, 0, 0},    // KIND_LONGDIV
+    {LAUNCH_MODDIV, 0, 0},     // KIND_MODDIV
+    {LAUNCH_LONGDIV_WIDE, 0, 0},  // KIND_LONGDIV_WIDE
+};
 
 constexpr uint8_t PATTERN_UNKNOWN = 1, PATTERN_QUOTIENT = 2, PATTERN_INDICATOR = 3, PATTERN_SQRT = 4;   // the pattern bytes (0: given)
 
@@ -315,23 +345,14 @@ struct Hint {
 
 struct Launch {
     uint32_t lo, hi;  // steps [lo, hi) of the sorted list
-    uint8_t chain;    // 1: one lane per assignment walks the steps in order; 0: one lane per (step, assignment), all of one level
-    uint8_t divides;  // 1: some step of the range is KIND_A / KIND_B / KIND_BITS_A / KIND_BITS_B / KIND_ISZERO / KIND_DIVREM (1 / cq) / KIND_SQRT (1 / (ka kb)); KIND_INDICATOR does not count
-    uint8_t bits = 0; // chain == 0 only.  1: every step of the range is a decomposition; 0: none is
-    uint8_t iszero = 0;  // chain == 0 only.  1: every step of the range is an is-zero pair; 0: none is
-    uint8_t divrem = 0;  // chain == 0 only.  1: every step of the range is a division row; 0: none is
-    uint8_t indicator = 0;  // chain == 0 only.  1: every step of the range is an indicator row; 0: none is
-    uint8_t sqrt = 0;       // chain == 0 only.  1: every step of the range is a square-root row; 0: none is
-    uint8_t block = 0;      // chain == 0 only.  1: every step of the range is a linear block (one wave each); 0: none is.  Never divides
-    uint8_t longdiv = 0;    // chain == 0 only.  1: every step of the range is a declared long division; 0: none is.  Never divides
-    uint32_t rounds = 0;    // longdiv: the division's trip count, the largest min(1024, n (kD - 1) + 256) of the range's hints -- a
-                            // dividend of kD limbs below 2^256 at bit offsets n j is below 2 to that power
-                            // moddiv: the same bound over the four operand lists of the range's hints (the reductions modulo P)
-    uint8_t moddiv = 0;     // chain == 0 only.  1: every step of the range is a declared modular division; longdiv and block are 0 on it
-                            // longdiv_wide: the largest min(8192, n (kD - 1) + 256) of the range's hints: a bound that sizes the wave's
-                            // arrays, not a trip count
-    uint8_t longdiv_wide = 0;// chain == 0 only.  1: every step of the range is a declared wide long division (one wave each); longdiv, moddiv and block are 0 on it
-    uint32_t inv_rounds = 0;// moddiv only: the inversion's trip count 2 L, L the largest min(512, n (kP - 1) + 256) of the range's hints:
+    uint8_t kind;     // a LaunchKind
+    uint8_t divides;  // 1: some step of the range has a kind that KIND_INFO counts as dividing
+    uint32_t rounds = 0;    // the three hint kinds only.  LAUNCH_LONGDIV: the division's trip count, the largest min(1024, n (kD - 1) + 256)
+                            // of the range's hints -- a dividend of kD limbs below 2^256 at bit offsets n j is below 2 to that power;
+                            // LAUNCH_MODDIV: the same bound over the four operand lists of the range's hints (the reductions modulo P);
+                            // LAUNCH_LONGDIV_WIDE: the largest min(8192, n (kD - 1) + 256) of the range's hints: a bound that sizes the
+                            // wave's arrays, not a trip count
+    uint32_t inv_rounds = 0;// LAUNCH_MODDIV only: the inversion's trip count 2 L, L the largest min(512, n (kP - 1) + 256) of the range's hints:
                             // every modulus of the range that is not stuck is below 2^L (solve_steps.cuh: modinv_odd proves the bound)
 };
 
@@ -529,6 +550,22 @@ inline bool sqrt_row(const std::vector<Unknown> &occ, const uint32_t nz[3], cons
     return occ.size() == 2 && occ[0].matrix == 0 && occ[1].matrix == 1 && unknown[occ[0].col] == PATTERN_SQRT && nz[0] == 1 && nz[1] == 1;
 }
 
+// The trip-count bounds of a hint launch over its steps (Launch::rounds, Launch::inv_rounds); a launch of any other kind keeps zero
+inline void hint_rounds(const Plan &p, Launch &l) {
+    if (l.kind != LAUNCH_LONGDIV && l.kind != LAUNCH_MODDIV && l.kind != LAUNCH_LONGDIV_WIDE) return;
+    for (uint32_t t = l.lo; t < l.hi; ++t) {
+        const Hint &h = p.hints[p.steps[t].cols_off];
+        if (l.kind == LAUNCH_MODDIV) {
+            for (uint32_t k : h.k)
+                if (k) l.rounds = std::max(l.rounds, std::min(h.n * (k - 1) + 256, MODDIV_OPERAND_BITS));
+            const uint32_t kP = (uint32_t)(h.flags & HINT_MODULUS_LITERAL ? h.lit.size() / 4 : h.E.size());
+            l.inv_rounds = std::max(l.inv_rounds, 2 * std::min(h.n * (kP - 1) + 256, MODDIV_MODULUS_BITS));
+        } else {
+            l.rounds = std::max(l.rounds, std::min(h.n * ((uint32_t)h.D.size() - 1) + 256, l.kind == LAUNCH_LONGDIV ? HINT_D_BITS : WIDE_D_BITS));
+        }
+    }
+}
+
 // The tail both builders share: p.steps (in ROW order, levels set) sorted by (level, kind), stable by row; level_ptr; the launch schedule.
 inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
     // counting sort by (level, kind); the row order inside a key is the order the steps come in
@@ -544,69 +581,36 @@ inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
         for (const Step &s : p.steps) sorted[cursor[(size_t)(s.level - 1) * K + s.kind]++] = s;
         p.steps.swap(sorted);
     }
-    // launch schedule: a wide level is its own launch, split where the dividing kinds begin, again where the decompositions and
-    // their dividing kinds begin, where the is-zero pairs begin, where the division rows begin and where the indicator rows begin (which
-    // do not divide: a chain of C-steps and indicators is a non-dividing one), and where the square-root rows begin (which count as
-    // dividing); consecutive narrow levels are one chain.  The linear blocks of a level come last and are a launch of their own
-    // whatever the level's width (a wave per block, not a lane): a chain run ends before them and a new one begins after them.  So are
-    // the declared hints of a level, after its blocks: first its long divisions, then its modular divisions, then its wide long divisions
+    // launch schedule, read from KIND_INFO.  The kinds that one lane can walk come first in a level.  Where they are a wide run, each
+    // gets the launch of its kind, adjacent kinds with the same launch kind and the same `divides` sharing one (so a level splits where
+    // the dividing kinds begin, again where the decompositions and their dividing kinds begin, then per kind; the indicator rows do not
+    // divide, the square-root rows do); where they are narrow, consecutive levels are one chain, which divides if any kind in it does (a
+    // chain of C-steps and indicators is a non-dividing one).  The other kinds come last and are launches of their own whatever the
+    // level's width (a wave per block, not a lane): a chain run ends before them and a new one begins after them.  First the linear
+    // blocks, then the declared hints: the long divisions, the modular divisions, the wide long divisions
     for (uint32_t l = 0; l < max_level; ++l) {
         const uint32_t *at = start.data() + (size_t)l * K;
-        const uint32_t lo = at[KIND_C], ab = at[KIND_A], bits = at[KIND_BITS_C], bits_ab = at[KIND_BITS_A], pairs = at[KIND_ISZERO], divs = at[KIND_DIVREM],
-                       inds = at[KIND_INDICATOR], roots = at[KIND_SQRT], hi = at[KIND_BLOCK], end = at[KIND_LONGDIV], hints_end = at[KIND_MODDIV], moddiv_end = at[KIND_LONGDIV_WIDE], wide_end = at[K];
-        const uint8_t divides = (uint8_t)(bits > ab || inds > bits_ab || hi > roots);
-        if (hi == lo) {
-            // a level of blocks only
-        } else if (hi - lo >= wide_steps) {
-            if (ab > lo) p.launches.push_back(Launch{lo, ab, 0, 0});
-            if (bits > ab) p.launches.push_back(Launch{ab, bits, 0, 1});
-            if (bits_ab > bits) p.launches.push_back(Launch{bits, bits_ab, 0, 0, 1});
-            if (pairs > bits_ab) p.launches.push_back(Launch{bits_ab, pairs, 0, 1, 1});
-            if (divs > pairs) p.launches.push_back(Launch{pairs, divs, 0, 1, 0, 1});
-            if (inds > divs) p.launches.push_back(Launch{divs, inds, 0, 1, 0, 0, 1});
-            if (roots > inds) p.launches.push_back(Launch{inds, roots, 0, 0, 0, 0, 0, 1});
-            if (hi > roots) p.launches.push_back(Launch{roots, hi, 0, 1, 0, 0, 0, 0, 1});
-        } else if (!p.launches.empty() && p.launches.back().chain) {
+        uint32_t walked = 0;   // the kinds of the chainable run
+        uint8_t divides = 0;
+        for (; walked < K && KIND_INFO[walked].chained; ++walked)
+            if (at[walked + 1] > at[walked]) divides |= KIND_INFO[walked].divides;
+        const uint32_t lo = at[0], hi = at[walked];
+        const bool wide = hi - lo >= wide_steps;
+        if (hi == lo || wide) {
+            // nothing for a chain: a level of blocks and hints only, or a wide one
+        } else if (!p.launches.empty() && p.launches.back().kind == LAUNCH_CHAIN) {
             p.launches.back().hi = hi;
             p.launches.back().divides |= divides;
         } else {
-            p.launches.push_back(Launch{lo, hi, 1, divides});
+            p.launches.push_back(Launch{lo, hi, LAUNCH_CHAIN, divides});
         }
-        if (end > hi) {
-            Launch blocks{hi, end, 0, 0};
-            blocks.block = 1;
-            p.launches.push_back(blocks);
-        }
-        if (hints_end > end) {   // the declared hints of the level, after its blocks: a launch of their own as well
-            Launch hints{end, hints_end, 0, 0};
-            hints.longdiv = 1;
-            for (uint32_t t = end; t < hints_end; ++t) {
-                const Hint &h = p.hints[p.steps[t].cols_off];
-                const uint32_t bits = h.n * ((uint32_t)h.D.size() - 1) + 256;
-                hints.rounds = std::max(hints.rounds, std::min(bits, HINT_D_BITS));
-            }
-            p.launches.push_back(hints);
-        }
-        if (moddiv_end > hints_end) {   // the modular divisions of the level, after its long divisions: a launch of their own
-            Launch hints{hints_end, moddiv_end, 0, 0};
-            hints.moddiv = 1;
-            for (uint32_t t = hints_end; t < moddiv_end; ++t) {
-                const Hint &h = p.hints[p.steps[t].cols_off];
-                for (uint32_t k : h.k)
-                    if (k) hints.rounds = std::max(hints.rounds, std::min(h.n * (k - 1) + 256, MODDIV_OPERAND_BITS));
-                const uint32_t kP = (uint32_t)(h.flags & HINT_MODULUS_LITERAL ? h.lit.size() / 4 : h.E.size());
-                hints.inv_rounds = std::max(hints.inv_rounds, 2 * std::min(h.n * (kP - 1) + 256, MODDIV_MODULUS_BITS));
-            }
-            p.launches.push_back(hints);
-        }
-        if (wide_end > moddiv_end) {   // the wide long divisions of the level, last: a launch of their own, a wave per hint
-            Launch hints{moddiv_end, wide_end, 0, 0};
-            hints.longdiv_wide = 1;
-            for (uint32_t t = moddiv_end; t < wide_end; ++t) {
-                const Hint &h = p.hints[p.steps[t].cols_off];
-                hints.rounds = std::max(hints.rounds, std::min(h.n * ((uint32_t)h.D.size() - 1) + 256, WIDE_D_BITS));
-            }
-            p.launches.push_back(hints);
+        for (uint32_t a = wide ? 0 : walked, b; a < K; a = b) {
+            const KindInfo &info = KIND_INFO[a];
+            for (b = a + 1; b < K && KIND_INFO[b].launch == info.launch && KIND_INFO[b].divides == info.divides;) ++b;
+            if (at[b] == at[a]) continue;
+            Launch own{at[a], at[b], info.launch, info.divides};
+            hint_rounds(p, own);
+            p.launches.push_back(own);
         }
     }
 }

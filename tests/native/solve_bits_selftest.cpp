@@ -17,7 +17,7 @@ struct Suite : SolveRig<C> {
         return c;
     }
     static bool launch_is(const Launch &l, uint32_t lo, uint32_t hi, int chain, int divides, int bits) {
-        return l.lo == lo && l.hi == hi && l.chain == chain && l.divides == divides && l.bits == bits;
+        return l.lo == lo && l.hi == hi && (l.kind == LAUNCH_CHAIN) == (chain != 0) && l.divides == divides && (l.kind == LAUNCH_BITS) == (bits != 0);
     }
     bool step_is(const Plan &p, uint32_t t, uint32_t row, uint32_t col, uint32_t kind, uint32_t level, uint64_t pos, const std::vector<uint32_t> &cols) {
         if (t >= p.steps.size()) return false;

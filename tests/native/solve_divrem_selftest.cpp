@@ -133,7 +133,7 @@ struct Suite : SolveRig<C> {
                             const Step want{0, 0, 3, KIND_DIVREM, 1};
                             ok = same_step(p.steps[0], want) && p.divs[0].pos_r == (uint64_t)rest && p.divs[0].col_r == 4 && p.divs[0].q_in_b == q_in_b &&
                                  p.level_ptr == std::vector<uint32_t>({0, 1}) && p.launches.size() == 1 &&
-                                 same_launch(p.launches[0], wide == 1 ? Launch{0, 1, 0, 1, 0, 0, 1} : Launch{0, 1, 1, 1});
+                                 same_launch(p.launches[0], wide == 1 ? Launch{0, 1, LAUNCH_DIVREM, 1} : Launch{0, 1, LAUNCH_CHAIN, 1});
                         }
                         check(ok, tag + ": the plan is the hand-written one");
                         check(same_plan(p, q), tag + ": the any-order builder gives the same plan");
@@ -270,8 +270,8 @@ struct Suite : SolveRig<C> {
               "beside pairs: the division is a step at row 0, no opener, and the pair still closes");
         if (p.error != OK) return;
         const Plan wide = in_order(s, unknown, 2);
-        check(wide.error == OK && wide.launches.size() == 3 && same_launch(wide.launches[0], Launch{0, 1, 0, 1, 0, 1}) && same_launch(wide.launches[1], Launch{1, 2, 0, 1, 0, 0, 1}) &&
-                  same_launch(wide.launches[2], Launch{2, 3, 1, 0}),
+        check(wide.error == OK && wide.launches.size() == 3 && same_launch(wide.launches[0], Launch{0, 1, LAUNCH_ISZERO, 1}) && same_launch(wide.launches[1], Launch{1, 2, LAUNCH_DIVREM, 1}) &&
+                  same_launch(wide.launches[2], Launch{2, 3, LAUNCH_CHAIN, 0}),
               "beside pairs: in a wide level the pairs and the divisions have launches of their own, both dividing");
         std::vector<Fr> z = {one, marker(), u(50), u(39), u(100), quotient_marker(), marker(), marker(), marker()};
         check(execute(s, p, z) == NONE && rows_hold(s, z) && z[5].eq(u(9)) && z[6].eq(u(1)) && z[7].eq(one) && z[8].eq(F::inv(u(11))) && z[1].eq(u(11)), "beside pairs: 100 = 9 * 11 + 1, a != b");
@@ -411,10 +411,10 @@ struct Suite : SolveRig<C> {
             const Plan p = in_order(s, unknown);
             if (p.error != OK) continue;
             if (c.what == "divisions")
-                check(p.launches.size() == 3 && same_launch(p.launches[0], Launch{0, 40, 0, 1, 0, 0, 1}) && same_launch(p.launches[1], Launch{40, 41, 0, 0}) &&
-                          same_launch(p.launches[2], Launch{41, 161, 0, 0, 1}) && p.levels() == 2,
+                check(p.launches.size() == 3 && same_launch(p.launches[0], Launch{0, 40, LAUNCH_DIVREM, 1}) && same_launch(p.launches[1], Launch{40, 41, LAUNCH_LEVEL, 0}) &&
+                          same_launch(p.launches[2], Launch{41, 161, LAUNCH_BITS, 0}) && p.levels() == 2,
                       "divisions: one division launch, then the sum and one decomposition launch");
-            if (c.what == "mod chain") check(p.launches.size() == 1 && same_launch(p.launches[0], Launch{0, 24, 1, 1}) && p.levels() == 24, "mod chain: one dividing chain of 24 levels");
+            if (c.what == "mod chain") check(p.launches.size() == 1 && same_launch(p.launches[0], Launch{0, 24, LAUNCH_CHAIN, 1}) && p.levels() == 24, "mod chain: one dividing chain of 24 levels");
             const std::vector<uint32_t> levels = column_levels(s, p);
             std::vector<std::vector<Fr>> want;
             for (int round = 0; round < c.rounds; ++round) {

@@ -1,5 +1,5 @@
 // CPU self-test of the witness solver's DECLARED HINTS (polymath_amd/host/solve_plan.hpp: decode_hints, Planner::hint_step, the
-// hint-owned columns of the scheduler, KIND_LONGDIV, Launch::longdiv; polymath_amd/csrc/solve_steps.cuh: add_shifted, limb_at, longdiv,
+// hint-owned columns of the scheduler, KIND_LONGDIV, LAUNCH_LONGDIV; polymath_amd/csrc/solve_steps.cuh: add_shifted, limb_at, longdiv,
 // solve_longdiv) on the rig of the other solve_*_selftest.cpp programs.  Stand-alone: g++ -std=c++17, no HIP, no GPU; the step body
 // that runs here is the text the kernel k_solve_longdiv calls.  Its literals are not committed: solve_hint_cases.hpp is what
 //     python tools/gen_solve_hint_cases.py > DIR/solve_hint_cases.hpp
@@ -27,70 +27,6 @@ struct Suite : SolveRig<C> {
     Suite(const char *n, const LongdivCase *c, size_t nc, const uint64_t (*p)[4], const ModMulCase *m, size_t nm, const uint64_t (*mp)[4])
         : Rig(n), cases(c), n_cases(nc), pool(p), muls(m), n_muls(nm), mul_pool(mp) {}
 
-    static Fr from_words(const uint64_t w[4]) {
-        Fr v;
-        memcpy(v.l, w, 32);
-        return pm::to_mont<P>(v);
-    }
-    static std::vector<uint32_t> range(uint32_t lo, uint32_t n) {
-        std::vector<uint32_t> v(n);
-        for (uint32_t i = 0; i < n; ++i) v[i] = lo + i;
-        return v;
-    }
-    // one record of pm_pk_set_hints; `lit`: the divisor's limbs as canonical words (then E is empty)
-    static std::vector<uint64_t> record(uint32_t n, const std::vector<uint32_t> &q, const std::vector<uint32_t> &rem, const std::vector<uint32_t> &D,
-                                        const std::vector<uint32_t> &E, const std::vector<uint64_t> &lit = {}) {
-        std::vector<uint64_t> w = {HINT_LONGDIV, n, q.size(), rem.size(), D.size(), lit.empty() ? E.size() : lit.size() / 4, lit.empty() ? 0 : HINT_DIVISOR_LITERAL};
-        for (const std::vector<uint32_t> *cols : {&q, &rem, &D, &E}) w.insert(w.end(), cols->begin(), cols->end());
-        w.insert(w.end(), lit.begin(), lit.end());
-        return w;
-    }
-    std::vector<Hint> declare(const System &s, const std::vector<uint64_t> &desc, std::string *why = nullptr) {
-        std::vector<Hint> hints;
-        const std::string refused = decode_hints(desc.data(), desc.size(), s.m0 + s.mw, modulus, hints);
-        if (why) *why = refused;
-        return hints;
-    }
-    Plan hinted(System &s, const std::vector<uint8_t> &unknown, const std::vector<Hint> &hints, uint32_t wide = WIDE_STEPS) {
-        s.freeze();
-        return this->folded(build_plan_any_order(s.m, s.nr(), s.m0, s.mw, unknown.data(), wide, modulus, &hints));
-    }
-    // the rig's execute with the block and the long-division launches in it
-    uint64_t run_plan(const System &s, const Plan &p, std::vector<Fr> &z) {
-        const Csr A{s.rowptr[0].data(), s.col[0].data(), s.val[0].data()}, B{s.rowptr[1].data(), s.col[1].data(), s.val[1].data()},
-            Cm{s.rowptr[2].data(), s.col[2].data(), s.val[2].data()};
-        pm::SolveRecords<P> rec = pm::solve_records<P>(p);
-        const uint64_t count = rec.steps.size();
-        for (uint64_t t = 0; t < count + 2 * rec.pairs.size(); ++t) pm::solve_inverse<P>(A, B, Cm, rec.steps.data(), count, rec.pairs.data(), rec.divs.data(), t);
-        uint32_t column = 0;
-        if (pm::solve_block_inverses<P>(p, rec, &column) != p.blocks.size()) return 0;
-        uint64_t stuck = NONE;
-        const typename Rig::StuckMin sink{&stuck, p.reordered, nullptr};
-        for (const Launch &l : p.launches)
-            for (uint32_t t = l.lo; t < l.hi; ++t) {
-                if (l.longdiv) pm::solve_longdiv<P>(rec.steps[t], rec.hints[rec.steps[t].bits], rec.hint_idx.data(), l.rounds, z.data(), sink);
-                else if (l.block) pm::solve_block<P>(A, B, Cm, rec.blocks[rec.steps[t].bits], rec.block_idx.data(), rec.block_inv.data(), z.data());
-                else if (l.divides) pm::solve_any<P, true>(A, B, Cm, rec.steps[t], p.bit_cols.data(), rec.pairs.data(), rec.divs.data(), z.data(), sink);
-                else pm::solve_any<P, false>(A, B, Cm, rec.steps[t], p.bit_cols.data(), rec.pairs.data(), rec.divs.data(), z.data(), sink);
-            }
-        return stuck;
-    }
-    // the launches cover the steps in order; a long-division launch holds hints only, is no chain and does not divide, and no other
-    // launch holds one; a hint's steps come after every other kind of its level
-    static bool launches_ok(const Plan &p) {
-        uint32_t at = 0;
-        bool ok = true;
-        for (const Launch &l : p.launches) {
-            ok = ok && l.lo == at && l.hi > l.lo && !(l.longdiv && (l.chain || l.divides || l.bits || l.iszero || l.divrem || l.indicator || l.sqrt || l.block));
-            for (uint32_t t = l.lo; ok && t < l.hi; ++t) ok = (p.steps[t].kind == KIND_LONGDIV) == (l.longdiv != 0) && (p.steps[t].kind == KIND_BLOCK) == (l.block != 0);
-            at = l.hi;
-        }
-        for (size_t t = 1; ok && t < p.steps.size(); ++t) {
-            const Step &a = p.steps[t - 1], &b = p.steps[t];
-            ok = a.level < b.level || (a.level == b.level && (a.kind < b.kind || (a.kind == b.kind && a.row < b.row)));
-        }
-        return ok && at == p.steps.size();
-    }
     static std::vector<uint32_t> levels(const System &s, const Plan &p) {
         std::vector<uint32_t> lv = column_levels(s, p);
         for (const Step &st : p.steps) {
@@ -116,22 +52,22 @@ struct Suite : SolveRig<C> {
             std::vector<uint64_t> lit;
             for (uint32_t j = 0; c.literal && j < c.kE; ++j) lit.insert(lit.end(), pool[c.at + c.kD + j], pool[c.at + c.kD + j] + 4);
             std::string why;
-            const std::vector<Hint> hints = declare(s, record(c.n, q, rem, D, E, lit), &why);
+            const std::vector<Hint> hints = declare(s, longdiv_record(c.n, q, rem, D, E, lit), &why);
             check(why.empty() && hints.size() == 1, tag + ": the declaration is accepted");
             if (hints.size() != 1) continue;
             std::vector<uint32_t> outs(q);
             outs.insert(outs.end(), rem.begin(), rem.end());
             const Plan p = hinted(s, s.unknown(outs), hints);
             Step want{0, 0, q[0], KIND_LONGDIV, 1};
-            check(p.error == OK && p.steps.size() == 1 && same_step(p.steps[0], want) && p.launches.size() == 1 && p.launches[0].longdiv == 1 && p.launches[0].lo == 0 &&
-                      p.launches[0].hi == 1 && p.launches[0].rounds == std::min(1024u, c.n * (c.kD - 1) + 256u) && launches_ok(p) && p.reordered && p.hints.size() == 1,
+            check(p.error == OK && p.steps.size() == 1 && same_step(p.steps[0], want) && p.launches.size() == 1 && p.launches[0].kind == LAUNCH_LONGDIV && p.launches[0].lo == 0 &&
+                      p.launches[0].hi == 1 && p.launches[0].rounds == std::min(1024u, c.n * (c.kD - 1) + 256u) && well_sorted(p) && p.reordered && p.hints.size() == 1,
                   tag + ": one step of kind KIND_LONGDIV at level 1, row nr + 0, a launch of its own");
             if (p.error != OK) continue;
             std::vector<Fr> z(s.m0 + s.mw, marker());
             z[0] = F::one();
             for (uint32_t j = 0; j < c.kD; ++j) z[D[j]] = from_words(pool[c.at + j]);
             for (uint32_t j = 0; j < kE_cols; ++j) z[E[j]] = from_words(pool[c.at + c.kD + j]);
-            const uint64_t stuck = run_plan(s, p, z);
+            const uint64_t stuck = execute(s, p, z);
             check(c.stuck ? stuck == ((uint64_t)1 << 32 | 0) : stuck == NONE, tag + (c.stuck ? ": stuck at the hint's word" : ": not stuck"));
             bool ok = true;
             for (uint32_t j = 0; j < c.kq; ++j) ok = ok && z[q[j]].eq(from_words(pool[c.at + c.kD + c.kE + j]));
@@ -150,7 +86,7 @@ struct Suite : SolveRig<C> {
     void refusals() {
         System s; s.mw = 40;
         const std::vector<uint32_t> q = {10, 11}, rem = {12, 13}, D = {1, 2, 3}, E = {4, 5};
-        const std::vector<uint64_t> good = record(64, q, rem, D, E);
+        const std::vector<uint64_t> good = longdiv_record(64, q, rem, D, E);
         std::string why;
         check(declare(s, good, &why).size() == 1 && why.empty(), "a good record is accepted");
         check(declare(s, {}, &why).empty() && why.empty(), "no words: no hints and no refusal");
@@ -184,27 +120,27 @@ struct Suite : SolveRig<C> {
         refuse_decl(s, bad, "hint 0: kE = 17 is outside 1..16");
         bad = good; bad[6] = 2;
         refuse_decl(s, bad, "hint 0: unknown flags 2");
-        refuse_decl(s, record(128, q, rem, range(1, 9), E), "hint 0: n (kD - 1) = 1024 is 1024 or more");
-        check(declare(s, record(93, q, rem, range(14, 12), E), &why).size() == 1, "n (kD - 1) = 1023 is accepted");
-        refuse_decl(s, record(128, q, rem, D, range(14, 5)), "hint 0: n (kE - 1) = 512 is 512 or more");
-        check(declare(s, record(73, q, rem, D, range(14, 8)), &why).size() == 1, "n (kE - 1) = 511 is accepted");
-        refuse_decl(s, record(64, q, rem, {1, 2, 41}, E), "hint 0: column 41 is not below m0 + mw = 41");
-        refuse_decl(s, record(64, {10, 41}, rem, D, E), "hint 0: column 41 is not below m0 + mw = 41");
-        refuse_decl(s, record(64, {10, 0}, rem, D, E), "hint 0: an output is column 0 (the constant one)");
-        refuse_decl(s, record(64, q, {12, 10}, D, E), "hint 0: output column 10 is named twice");
-        refuse_decl(s, record(64, q, rem, {1, 12, 3}, E), "hint 0: output column 12 is an input of the hint as well");
-        refuse_decl(s, record(64, q, rem, D, {4, 11}), "hint 0: output column 11 is an input of the hint as well");
+        refuse_decl(s, longdiv_record(128, q, rem, range(1, 9), E), "hint 0: n (kD - 1) = 1024 is 1024 or more");
+        check(declare(s, longdiv_record(93, q, rem, range(14, 12), E), &why).size() == 1, "n (kD - 1) = 1023 is accepted");
+        refuse_decl(s, longdiv_record(128, q, rem, D, range(14, 5)), "hint 0: n (kE - 1) = 512 is 512 or more");
+        check(declare(s, longdiv_record(73, q, rem, D, range(14, 8)), &why).size() == 1, "n (kE - 1) = 511 is accepted");
+        refuse_decl(s, longdiv_record(64, q, rem, {1, 2, 41}, E), "hint 0: column 41 is not below m0 + mw = 41");
+        refuse_decl(s, longdiv_record(64, {10, 41}, rem, D, E), "hint 0: column 41 is not below m0 + mw = 41");
+        refuse_decl(s, longdiv_record(64, {10, 0}, rem, D, E), "hint 0: an output is column 0 (the constant one)");
+        refuse_decl(s, longdiv_record(64, q, {12, 10}, D, E), "hint 0: output column 10 is named twice");
+        refuse_decl(s, longdiv_record(64, q, rem, {1, 12, 3}, E), "hint 0: output column 12 is an input of the hint as well");
+        refuse_decl(s, longdiv_record(64, q, rem, D, {4, 11}), "hint 0: output column 11 is an input of the hint as well");
         two = good;
-        bad = record(64, {20, 21}, {22, 13}, D, E);
+        bad = longdiv_record(64, {20, 21}, {22, 13}, D, E);
         two.insert(two.end(), bad.begin(), bad.end());
         refuse_decl(s, two, "hint 1: output column 13 is an output of hint 0 as well");
         std::vector<uint64_t> lit = {1, 0, 0, 0, modulus[0], modulus[1], modulus[2], modulus[3]};
-        refuse_decl(s, record(64, q, rem, D, {}, lit), "hint 0: literal limb 1 is not below r");
+        refuse_decl(s, longdiv_record(64, q, rem, D, {}, lit), "hint 0: literal limb 1 is not below r");
         lit[4] -= 1;
-        check(declare(s, record(64, q, rem, D, {}, lit), &why).size() == 1 && why.empty(), "a literal limb equal to r - 1 is accepted");
+        check(declare(s, longdiv_record(64, q, rem, D, {}, lit), &why).size() == 1 && why.empty(), "a literal limb equal to r - 1 is accepted");
         // a hint may read the output of another hint
         two = good;
-        bad = record(64, {20}, {22}, {10, 12}, E);
+        bad = longdiv_record(64, {20}, {22}, {10, 12}, E);
         two.insert(two.end(), bad.begin(), bad.end());
         check(declare(s, two, &why).size() == 2 && why.empty(), "the output of one hint as the input of another is accepted");
 
@@ -266,7 +202,7 @@ struct Suite : SolveRig<C> {
         const uint32_t l = g.l;
         const std::vector<uint32_t> Pc = g.take(2 * l - 1), q = g.take(l), rem = g.take(l);
         product_rows(s, x, y, Pc);
-        const std::vector<uint64_t> rec = record(g.n, q, rem, Pc, g.p_cols, g.p_cols.empty() ? g.p_words : std::vector<uint64_t>{});
+        const std::vector<uint64_t> rec = longdiv_record(g.n, q, rem, Pc, g.p_cols, g.p_cols.empty() ? g.p_words : std::vector<uint64_t>{});
         g.desc.insert(g.desc.end(), rec.begin(), rec.end());
         g.bit_cols.clear();
         for (uint32_t i = 0; g.decompose && i < 2 * l; ++i) {
@@ -366,7 +302,7 @@ struct Suite : SolveRig<C> {
                 check(why.empty() && hints.size() == rems.size(), tag + ": the declaration is accepted");
                 const std::vector<uint8_t> unknown = s.unknown(g.unknown);
                 const Plan p = hinted(s, unknown, hints);
-                check(p.error == OK && p.reordered && launches_ok(p) && count_kind(p, KIND_LONGDIV) == rems.size() && p.hints.size() == rems.size(), tag + ": plans, a step per hint");
+                check(p.error == OK && p.reordered && well_sorted(p) && count_kind(p, KIND_LONGDIV) == rems.size() && p.hints.size() == rems.size(), tag + ": plans, a step per hint");
                 if (p.error != OK) { printf("%s: %s\n", name, p.message.c_str()); continue; }
                 // without the declaration the system is refused: nothing determines q and rem
                 const Plan bare = any_order(s, unknown);
@@ -381,7 +317,7 @@ struct Suite : SolveRig<C> {
                 for (size_t j = 0; j < g.carry_cols.size(); ++j) ok = ok && lv[g.carry_cols[j]] == lv[g.q_cols[0]] + 2 + j;
                 check(ok && lv[g.P_cols[0]] >= 1, tag + ": the block, then the hint, then the decompositions beside q p, then the carries one by one");
                 std::vector<Fr> z = start(s, g, c, a, b);
-                const uint64_t stuck = run_plan(s, p, z);
+                const uint64_t stuck = execute(s, p, z);
                 check(stuck == NONE && rem_is(z, x, c) && rows_hold(s, z), tag + ": executes to Python's (a b) mod p, and every row holds");
                 // rows reversed and shuffled: the same levels and the same assignment
                 for (int round = 0; round < 3; ++round) {
@@ -393,7 +329,7 @@ struct Suite : SolveRig<C> {
                     std::vector<Fr> zt = start(t, g, c, a, b);
                     // (the levels may differ: the closing check row, examined early, determines the last carry before the carry rows reach it)
                     const std::vector<uint32_t> lt = levels(t, q);
-                    bool equal = q.error == OK && launches_ok(q) && run_plan(t, q, zt) == NONE && rows_hold(t, zt);
+                    bool equal = q.error == OK && well_sorted(q) && execute(t, q, zt) == NONE && rows_hold(t, zt);
                     for (uint32_t col : g.q_cols) equal = equal && lt[col] == lt[g.P_cols[0]] + 1;
                     for (size_t j = 0; equal && j < z.size(); ++j) equal = zt[j].eq(z[j]);
                     check(equal, tag + (round ? ": shuffled, the same assignment" : ": reversed, the same assignment"));
@@ -410,13 +346,13 @@ struct Suite : SolveRig<C> {
         const Plan with = hinted(s, given, hints), without = any_order(s, given);
         bool ok = with.error == OK && same_plan(with, without) && with.hints.empty() && without.hints.empty() && with.blocks.size() == without.blocks.size() &&
                   with.block_mats.size() == without.block_mats.size();
-        for (size_t i = 0; ok && i < with.launches.size(); ++i) ok = with.launches[i].block == without.launches[i].block && with.launches[i].sqrt == without.launches[i].sqrt && !with.launches[i].longdiv;
+        for (size_t i = 0; ok && i < with.launches.size(); ++i) ok = (with.launches[i].kind == LAUNCH_BLOCK) == (without.launches[i].kind == LAUNCH_BLOCK) && (with.launches[i].kind == LAUNCH_SQRT) == (without.launches[i].kind == LAUNCH_SQRT) && with.launches[i].kind != LAUNCH_LONGDIV;
         for (size_t i = 0; ok && i < with.blocks.size(); ++i) ok = with.blocks[i].rows == without.blocks[i].rows && with.blocks[i].cols == without.blocks[i].cols && with.blocks[i].mat == without.blocks[i].mat;
         check(ok, tag + ": inert, the plan without the declaration field by field");
         std::vector<Fr> z = solved;
         for (size_t j = 0; j < given.size(); ++j)
             if (given[j]) z[j] = marker();
-        check(with.error == OK && run_plan(s, with, z) == NONE && rows_hold(s, z), tag + ": a caller that supplies q and rem itself");
+        check(with.error == OK && execute(s, with, z) == NONE && rows_hold(s, z), tag + ": a caller that supplies q and rem itself");
     }
 
     // ---- 6. stuck under a plan with rows: the hint's word is nr + h at its level, and the root cause wins
@@ -426,33 +362,33 @@ struct Suite : SolveRig<C> {
         const Fr one = F::one();
         s.add(Row{{one, 1}}, Row{{one, 2}}, Row{{one, 3}});
         s.add(Row{{one, 7}}, Row{{one, 5}}, Row{{one, 0}});
-        const std::vector<Hint> hints = declare(s, record(64, {4}, {5}, {3}, {6}));
+        const std::vector<Hint> hints = declare(s, longdiv_record(64, {4}, {5}, {3}, {6}));
         const Plan p = hinted(s, s.unknown({3, 4, 5, 7}), hints);
         check(p.error == OK && p.steps.size() == 3 && p.steps[1].kind == KIND_LONGDIV && p.steps[1].row == 2 && p.steps[1].level == 2 && p.steps[2].level == 3,
               "stuck: the hint between two rows, at row nr + 0 = 2 and level 2");
         std::vector<Fr> z(8, marker());
         z[0] = one; z[1] = u(6); z[2] = u(7); z[6] = F::zero();
-        check(run_plan(s, p, z) == ((uint64_t)2 << 32 | 2) && z[4].is_zero() && z[5].is_zero(), "stuck: a zero divisor is reported at the hint, not at the row that then divides by the stored zero");
+        check(execute(s, p, z) == ((uint64_t)2 << 32 | 2) && z[4].is_zero() && z[5].is_zero(), "stuck: a zero divisor is reported at the hint, not at the row that then divides by the stored zero");
         std::fill(z.begin(), z.end(), marker());
         z[0] = one; z[1] = u(6); z[2] = u(7); z[6] = u(5);
-        check(run_plan(s, p, z) == NONE && z[4].eq(u(8)) && z[5].eq(u(2)) && rows_hold(s, z), "stuck: the same plan on a good divisor completes: 42 = 8 * 5 + 2");
+        check(execute(s, p, z) == NONE && z[4].eq(u(8)) && z[5].eq(u(2)) && rows_hold(s, z), "stuck: the same plan on a good divisor completes: 42 = 8 * 5 + 2");
     }
 
     // ---- 7. two hints of different sizes in one launch: the trip count is the larger bound, and the smaller dividend divides under it
     void mixed_launch() {
         // 0 one | 1, 2 D of hint 0 (n = 64) | 3 E of both | 4 .. 7 D of hint 1 (n = 128) | 8, 9 q and 10 rem of hint 0 | 11 q and 12 rem of hint 1
         System s; s.mw = 12;
-        std::vector<uint64_t> desc = record(64, {8, 9}, {10}, {1, 2}, {3}), second = record(128, {11}, {12}, {4, 5, 6, 7}, {3});
+        std::vector<uint64_t> desc = longdiv_record(64, {8, 9}, {10}, {1, 2}, {3}), second = longdiv_record(128, {11}, {12}, {4, 5, 6, 7}, {3});
         desc.insert(desc.end(), second.begin(), second.end());
         const std::vector<Hint> hints = declare(s, desc);
         const Plan p = hinted(s, s.unknown({8, 9, 10, 11, 12}), hints);
-        check(p.error == OK && p.steps.size() == 2 && p.launches.size() == 1 && p.launches[0].longdiv == 1 && p.launches[0].rounds == 128 * 3 + 256 && p.steps[0].row == 0 &&
+        check(p.error == OK && p.steps.size() == 2 && p.launches.size() == 1 && p.launches[0].kind == LAUNCH_LONGDIV && p.launches[0].rounds == 128 * 3 + 256 && p.steps[0].row == 0 &&
                   p.steps[1].row == 1,
               "mixed launch: one launch of two hints, 640 rounds (64 + 256 and 384 + 256)");
         std::vector<Fr> z(13, marker());
         z[0] = F::one(); z[1] = u(7); z[2] = u(1); z[3] = u(5); z[4] = u(9); z[5] = z[6] = z[7] = F::zero();
         const unsigned __int128 D = ((unsigned __int128)1 << 64) + 7, q = D / 5;
-        check(p.error == OK && run_plan(s, p, z) == NONE && z[8].eq(u((uint64_t)q)) && z[9].eq(u((uint64_t)(q >> 64))) && z[10].eq(u((uint64_t)(D % 5))) && z[11].eq(u(1)) &&
+        check(p.error == OK && execute(s, p, z) == NONE && z[8].eq(u((uint64_t)q)) && z[9].eq(u((uint64_t)(q >> 64))) && z[10].eq(u((uint64_t)(D % 5))) && z[11].eq(u(1)) &&
                   z[12].eq(u(4)),
               "mixed launch: (2^64 + 7) / 5 and 9 / 5 under the same trip count");
     }

@@ -35,7 +35,7 @@ struct Suite : SolveRig<C> {
                             Step want{0, 0, 3, KIND_INDICATOR, 1};
                             want.cols_off = (uint32_t)u_in_b;
                             ok = same_step(p.steps[0], want) && p.level_ptr == std::vector<uint32_t>({0, 1}) && p.launches.size() == 1 &&
-                                 same_launch(p.launches[0], wide == 1 ? Launch{0, 1, 0, 0, 0, 0, 0, 1} : Launch{0, 1, 1, 0});
+                                 same_launch(p.launches[0], wide == 1 ? Launch{0, 1, LAUNCH_INDICATOR, 0} : Launch{0, 1, LAUNCH_CHAIN, 0});
                         }
                         check(ok, tag + ": the plan is the hand-written one, and its launch does not divide");
                         check(same_plan(p, q), tag + ": the any-order builder gives the same plan");
@@ -278,13 +278,13 @@ struct Suite : SolveRig<C> {
             const Plan p = in_order(s, unknown);
             if (p.error != OK) continue;
             if (c.what == "decoder")
-                check(p.launches.size() == 2 && same_launch(p.launches[0], Launch{0, 40, 0, 0, 0, 0, 0, 1}) && same_launch(p.launches[1], Launch{40, 41, 1, 0}) && p.levels() == 2,
+                check(p.launches.size() == 2 && same_launch(p.launches[0], Launch{0, 40, LAUNCH_INDICATOR, 0}) && same_launch(p.launches[1], Launch{40, 41, LAUNCH_CHAIN, 0}) && p.levels() == 2,
                       "decoder: one indicator launch of its own, then the sum; neither divides");
             if (c.what == "table walk")
-                check(p.launches.size() == 1 && same_launch(p.launches[0], Launch{0, (uint32_t)p.steps.size(), 1, 0}) && p.levels() == 12 && p.steps.size() == 4 * 12,
+                check(p.launches.size() == 1 && same_launch(p.launches[0], Launch{0, (uint32_t)p.steps.size(), LAUNCH_CHAIN, 0}) && p.levels() == 12 && p.steps.size() == 4 * 12,
                       "table walk: one NON-dividing chain of 12 levels: only C-steps and indicators");
             if (c.what == "mixed")
-                check(p.levels() == 5 && p.launches.size() == 1 && p.launches[0].chain && p.launches[0].divides && p.pairs.size() == 1, "mixed: one dividing chain (the division and the pair)");
+                check(p.levels() == 5 && p.launches.size() == 1 && p.launches[0].kind == LAUNCH_CHAIN && p.launches[0].divides && p.pairs.size() == 1, "mixed: one dividing chain (the division and the pair)");
             const std::vector<uint32_t> levels = column_levels(s, p);
             std::vector<std::vector<Fr>> want;
             for (int round = 0; round < c.rounds; ++round) {
@@ -303,7 +303,7 @@ struct Suite : SolveRig<C> {
                 const std::vector<uint8_t> plain = s.unknown(plain_cols, c.quotients, {});
                 const Plan t = in_order(s, plain);
                 bool ok = t.error == OK && count_kind(t, KIND_INDICATOR) == 0 && t.steps.size() == p.steps.size() && column_levels(s, t) == levels;
-                for (const Launch &l : t.launches) ok = ok && l.indicator == 0;
+                for (const Launch &l : t.launches) ok = ok && l.kind != LAUNCH_INDICATOR;
                 for (size_t i = 0; ok && i < t.steps.size(); ++i)
                     if (std::find(c.indicators.begin(), c.indicators.end(), t.steps[i].col) != c.indicators.end()) ok = t.steps[i].kind == KIND_A;
                 check(ok, c.what + ": with the plain marker the guards are ordinary kind-A steps at the same levels");
@@ -355,7 +355,7 @@ struct Suite : SolveRig<C> {
         bool ok = p.error == OK && p.reordered && p.steps.size() == 2 && p.steps[0].kind == KIND_C && p.steps[0].row == 1 && p.steps[0].level == 1;
         if (ok) {
             Step want{0, 0, 4, KIND_INDICATOR, 2};
-            ok = same_step(p.steps[1], want) && p.launches.size() == 1 && same_launch(p.launches[0], Launch{0, 2, 1, 0}) && well_sorted(p);
+            ok = same_step(p.steps[1], want) && p.launches.size() == 1 && same_launch(p.launches[0], Launch{0, 2, LAUNCH_CHAIN, 0}) && well_sorted(p);
         }
         check(ok, "waiting guard: it waits for its index and is then taken as an indicator row, one level up");
         if (!ok) return;

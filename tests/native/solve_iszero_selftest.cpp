@@ -13,7 +13,7 @@ struct Suite : SolveRig<C> {
     explicit Suite(const char *n) : Rig(n) {}
 
     static bool launch_is(const Launch &l, uint32_t lo, uint32_t hi, int chain, int divides, int bits, int iszero) {
-        return l.lo == lo && l.hi == hi && l.chain == chain && l.divides == divides && l.bits == bits && l.iszero == iszero;
+        return l.lo == lo && l.hi == hi && (l.kind == LAUNCH_CHAIN) == (chain != 0) && l.divides == divides && (l.kind == LAUNCH_BITS) == (bits != 0) && (l.kind == LAUNCH_ISZERO) == (iszero != 0);
     }
     struct Pair { uint32_t row1, row, col_m, col_b; uint64_t pos_m, pos_c, pos; int m_in_b, b_in_b, negated; uint32_t level; };
     static bool pair_is(const Plan &p, uint32_t t, const Pair &w) {
@@ -293,7 +293,7 @@ struct Suite : SolveRig<C> {
                 const Plan p = in_order(s, unknown, wide);
                 bool ok = p.error == OK && p.steps.size() == 5 && p.launches.size() == (wide == 1 ? 4u : 1u) && p.pairs.empty();
                 for (const Step &st : p.steps) ok = ok && st.kind != KIND_ISZERO;
-                for (const Launch &l : p.launches) ok = ok && l.iszero == 0;
+                for (const Launch &l : p.launches) ok = ok && l.kind != LAUNCH_ISZERO;
                 // level 1: row 0 (A), row 1 (B), row 6 (BITS_C) -- sorted A, B, BITS_C; level 2: row 2 (C); level 3: row 3 (B)
                 ok = ok && p.steps[0].row == 0 && p.steps[1].row == 1 && p.steps[2].row == 6 && p.steps[3].row == 2 && p.steps[4].row == 3 &&
                      p.level_ptr == std::vector<uint32_t>({0, 3, 4, 5});

@@ -1,5 +1,5 @@
 // CPU self-test of the witness solver's declared MODULAR-DIVISION hints (polymath_amd/host/solve_plan.hpp: decode_hints' opcode 3,
-// KIND_MODDIV, Launch::moddiv and its two trip counts; polymath_amd/csrc/solve_steps.cuh: sub_masked, add_masked, modinv_odd,
+// KIND_MODDIV, LAUNCH_MODDIV and its two trip counts; polymath_amd/csrc/solve_steps.cuh: sub_masked, add_masked, modinv_odd,
 // solve_moddiv) on the rig of the other solve_*_selftest.cpp programs.  Stand-alone: g++ -std=c++17, no HIP, no GPU; the step body that
 // runs here is the text the kernel k_solve_moddiv calls.  Its literals are not committed: solve_moddiv_cases.hpp is what
 //     python tools/gen_solve_moddiv_cases.py > DIR/solve_moddiv_cases.hpp
@@ -25,17 +25,6 @@ struct Suite : SolveRig<C> {
     const uint64_t (*pool)[4];
     Suite(const char *n, const ModdivCase *c, size_t nc, const uint64_t (*p)[4]) : Rig(n), cases(c), n_cases(nc), pool(p) {}
 
-    static Fr from_words(const uint64_t w[4]) {
-        Fr v;
-        memcpy(v.l, w, 32);
-        return pm::to_mont<P>(v);
-    }
-    static std::vector<uint32_t> range(uint32_t lo, uint32_t n) {
-        std::vector<uint32_t> v(n);
-        for (uint32_t i = 0; i < n; ++i) v[i] = lo + i;
-        return v;
-    }
-    typedef std::vector<uint32_t> Cols;
     // one modular-division record of pm_pk_set_hints; `lit`: the modulus' limbs as canonical words (then Pc is empty)
     static std::vector<uint64_t> record(uint32_t n, const Cols &z, const Cols &Np, const Cols &Nm, const Cols &Dp, const Cols &Dm, const Cols &Pc,
                                         const std::vector<uint64_t> &lit = {}) {
@@ -45,57 +34,7 @@ struct Suite : SolveRig<C> {
         w.insert(w.end(), lit.begin(), lit.end());
         return w;
     }
-    static std::vector<uint64_t> longdiv_record(uint32_t n, const Cols &q, const Cols &rem, const Cols &D, const Cols &E) {
-        std::vector<uint64_t> w = {HINT_LONGDIV, n, q.size(), rem.size(), D.size(), E.size(), 0};
-        for (const Cols *cols : {&q, &rem, &D, &E}) w.insert(w.end(), cols->begin(), cols->end());
-        return w;
-    }
     static std::vector<uint64_t> literal(uint64_t v) { return {v, 0, 0, 0}; }
-    std::vector<Hint> declare(const System &s, const std::vector<uint64_t> &desc, std::string *why = nullptr) {
-        std::vector<Hint> hints;
-        const std::string refused = decode_hints(desc.data(), desc.size(), s.m0 + s.mw, modulus, hints);
-        if (why) *why = refused;
-        return hints;
-    }
-    Plan hinted(System &s, const std::vector<uint8_t> &unknown, const std::vector<Hint> &hints, uint32_t wide = WIDE_STEPS) {
-        s.freeze();
-        return this->folded(build_plan_any_order(s.m, s.nr(), s.m0, s.mw, unknown.data(), wide, modulus, &hints));
-    }
-    // the rig's execute with the hint launches in it
-    uint64_t run_plan(const System &s, const Plan &p, std::vector<Fr> &z) {
-        const Csr A{s.rowptr[0].data(), s.col[0].data(), s.val[0].data()}, B{s.rowptr[1].data(), s.col[1].data(), s.val[1].data()},
-            Cm{s.rowptr[2].data(), s.col[2].data(), s.val[2].data()};
-        pm::SolveRecords<P> rec = pm::solve_records<P>(p);
-        const uint64_t count = rec.steps.size();
-        for (uint64_t t = 0; t < count + 2 * rec.pairs.size(); ++t) pm::solve_inverse<P>(A, B, Cm, rec.steps.data(), count, rec.pairs.data(), rec.divs.data(), t);
-        uint64_t stuck = NONE;
-        const typename Rig::StuckMin sink{&stuck, p.reordered, nullptr};
-        for (const Launch &l : p.launches)
-            for (uint32_t t = l.lo; t < l.hi; ++t) {
-                if (l.moddiv) pm::solve_moddiv<P>(rec.steps[t], rec.mods[rec.steps[t].bits], rec.hint_idx.data(), l.rounds, l.inv_rounds, z.data(), sink);
-                else if (l.longdiv) pm::solve_longdiv<P>(rec.steps[t], rec.hints[rec.steps[t].bits], rec.hint_idx.data(), l.rounds, z.data(), sink);
-                else if (l.divides) pm::solve_any<P, true>(A, B, Cm, rec.steps[t], p.bit_cols.data(), rec.pairs.data(), rec.divs.data(), z.data(), sink);
-                else pm::solve_any<P, false>(A, B, Cm, rec.steps[t], p.bit_cols.data(), rec.pairs.data(), rec.divs.data(), z.data(), sink);
-            }
-        return stuck;
-    }
-    // the launches cover the steps in order; a modular launch holds modular hints only, is no chain, does not divide and is neither a
-    // long-division nor a block launch; no other launch holds one; the steps are sorted by (level, kind, row)
-    static bool launches_ok(const Plan &p) {
-        uint32_t at = 0;
-        bool ok = true;
-        for (const Launch &l : p.launches) {
-            ok = ok && l.lo == at && l.hi > l.lo && !(l.moddiv && (l.chain || l.divides || l.bits || l.iszero || l.divrem || l.indicator || l.sqrt || l.block || l.longdiv)) &&
-                 (l.moddiv ? l.rounds >= 256 && l.rounds <= 1024 && l.inv_rounds >= 512 && l.inv_rounds <= 1024 : l.inv_rounds == 0);
-            for (uint32_t t = l.lo; ok && t < l.hi; ++t) ok = (p.steps[t].kind == KIND_MODDIV) == (l.moddiv != 0) && (p.steps[t].kind == KIND_LONGDIV) == (l.longdiv != 0);
-            at = l.hi;
-        }
-        for (size_t t = 1; ok && t < p.steps.size(); ++t) {
-            const Step &a = p.steps[t - 1], &b = p.steps[t];
-            ok = a.level < b.level || (a.level == b.level && (a.kind < b.kind || (a.kind == b.kind && a.row < b.row)));
-        }
-        return ok && at == p.steps.size();
-    }
 
     // ---- 1. modular divisions against Python's pow.  A system without rows: columns 1 .. N+, N-, D+, D-, the modulus (unless it is a
     // literal), Z; the one hint is ready at once
@@ -120,15 +59,15 @@ struct Suite : SolveRig<C> {
                 if (k) rounds = std::max(rounds, std::min(1024u, c.n * (k - 1) + 256u));
             const uint32_t L = std::min(512u, c.n * (c.kP - 1) + 256u);
             Step want{0, 0, Z[0], KIND_MODDIV, 1};
-            check(p.error == OK && p.steps.size() == 1 && same_step(p.steps[0], want) && p.launches.size() == 1 && p.launches[0].moddiv == 1 && p.launches[0].longdiv == 0 &&
-                      p.launches[0].block == 0 && p.launches[0].lo == 0 && p.launches[0].hi == 1 && p.launches[0].rounds == rounds && p.launches[0].inv_rounds == 2 * L &&
-                      launches_ok(p) && p.reordered && p.hints.size() == 1,
+            check(p.error == OK && p.steps.size() == 1 && same_step(p.steps[0], want) && p.launches.size() == 1 && p.launches[0].kind == LAUNCH_MODDIV &&
+                      p.launches[0].lo == 0 && p.launches[0].hi == 1 && p.launches[0].rounds == rounds && p.launches[0].inv_rounds == 2 * L &&
+                      well_sorted(p) && p.reordered && p.hints.size() == 1,
                   tag + ": one step of kind KIND_MODDIV at level 1, row nr + 0, a launch of its own with both trip counts");
             if (p.error != OK) continue;
             std::vector<Fr> z(s.m0 + s.mw, marker());
             z[0] = F::one();
             for (uint32_t j = 0; j < k_all + kP_cols; ++j) z[1 + j] = from_words(pool[c.at + j]);
-            const uint64_t stuck = run_plan(s, p, z);
+            const uint64_t stuck = execute(s, p, z);
             check(c.stuck ? stuck == ((uint64_t)1 << 32 | 0) : stuck == NONE, tag + (c.stuck ? ": stuck at the hint's word" : ": not stuck"));
             bool ok = true;
             for (uint32_t j = 0; j < c.kz; ++j) ok = ok && z[Z[j]].eq(from_words(pool[c.at + k_all + c.kP + j]));
@@ -255,7 +194,7 @@ struct Suite : SolveRig<C> {
         {   // inert: the outputs are given, and the plan is the plan without the declaration
             const std::vector<uint8_t> un = s.unknown({30});
             const Plan with = hinted(s, un, hints), without = any_order(s, un);
-            check(with.error == OK && same_plan(with, without) && with.hints.empty() && with.launches.size() == 1 && !with.launches[0].moddiv && with.launches[0].inv_rounds == 0,
+            check(with.error == OK && same_plan(with, without) && with.hints.empty() && with.launches.size() == 1 && with.launches[0].kind != LAUNCH_MODDIV && with.launches[0].inv_rounds == 0,
                   "inert: the plan without the declaration, field by field");
         }
         check(NUM_KINDS == 7 && NUM_STEP_KINDS == 8 && NUM_SORT_KINDS == 11 && NUM_PLAN_KINDS == 12 && NUM_HINT_KINDS == 13 && KIND_LONGDIV == 11 && KIND_MODDIV == 12 &&
@@ -284,15 +223,15 @@ struct Suite : SolveRig<C> {
             const Plan p = hinted(s, s.unknown({4, 5, 6, 7, 8, 9, 10, 11}), hints);
             // level 1: row 0.  level 2: long division 1 (row 3), then modular 2 (row 4).  level 3: long division 3 (row 5), then modular 0 (row 2).  level 4: row 1
             const uint32_t kinds[6] = {KIND_C, KIND_LONGDIV, KIND_MODDIV, KIND_LONGDIV, KIND_MODDIV, KIND_C}, rows[6] = {0, 3, 4, 5, 2, 1}, lv[6] = {1, 2, 2, 3, 3, 4};
-            bool ok = p.error == OK && p.steps.size() == 6 && launches_ok(p) && p.launches.size() == 6;
+            bool ok = p.error == OK && p.steps.size() == 6 && well_sorted(p) && p.launches.size() == 6;
             for (int t = 0; ok && t < 6; ++t) ok = p.steps[t].kind == kinds[t] && p.steps[t].row == rows[t] && p.steps[t].level == lv[t];
-            for (int t = 0; ok && t < 6; ++t) ok = p.launches[t].lo == (uint32_t)t && p.launches[t].moddiv == (kinds[t] == KIND_MODDIV) && p.launches[t].longdiv == (kinds[t] == KIND_LONGDIV);
+            for (int t = 0; ok && t < 6; ++t) ok = p.launches[t].lo == (uint32_t)t && (p.launches[t].kind == LAUNCH_MODDIV) == (kinds[t] == KIND_MODDIV) && (p.launches[t].kind == LAUNCH_LONGDIV) == (kinds[t] == KIND_LONGDIV);
             check(ok, "meeting: a modular hint waits for a long division's output and the reverse; in a level the long divisions' launch, then the modular one, row = nr + h");
             if (p.error != OK) printf("%s: %s\n", name, p.message.c_str());
             std::vector<Fr> z(12, marker());
             z[0] = one; z[1] = u(6); z[2] = u(7); z[3] = u(5);
             // d = 42; q = 8, rem = 2; Z = 2 / 8 mod 101 = 2 * 38 mod 101 = 76 (8 * 38 = 304 = 3 * 101 + 1); y = 456; Z' = 1 / 42 mod 101 = 89 (42 * 89 = 3738 = 37 * 101 + 1); 89 = 17 * 5 + 4
-            check(ok && run_plan(s, p, z) == NONE && z[4].eq(u(42)) && z[5].eq(u(8)) && z[6].eq(u(2)) && z[7].eq(u(76)) && z[8].eq(u(456)) && z[9].eq(u(89)) && z[10].eq(u(17)) &&
+            check(ok && execute(s, p, z) == NONE && z[4].eq(u(42)) && z[5].eq(u(8)) && z[6].eq(u(2)) && z[7].eq(u(76)) && z[8].eq(u(456)) && z[9].eq(u(89)) && z[10].eq(u(17)) &&
                       z[11].eq(u(4)) && rows_hold(s, z),
                   "meeting: executes to 42 = 8 * 5 + 2, 2 / 8 = 76 and 1 / 42 = 89 (mod 101), 89 = 17 * 5 + 4");
         }
@@ -321,7 +260,7 @@ struct Suite : SolveRig<C> {
         const std::vector<Hint> hints = declare(s, desc);
         const std::vector<uint8_t> un = s.unknown(unknown);
         const Plan p = hinted(s, un, hints);
-        bool ok = p.error == OK && p.reordered && launches_ok(p) && count_kind(p, KIND_MODDIV) == steps && p.steps.size() == 2 * steps + 1 && p.levels() == 2 * steps + 1;
+        bool ok = p.error == OK && p.reordered && well_sorted(p) && count_kind(p, KIND_MODDIV) == steps && p.steps.size() == 2 * steps + 1 && p.levels() == 2 * steps + 1;
         for (size_t t = 0; ok && t < p.steps.size(); ++t) ok = p.steps[t].level == t + 1 && (p.steps[t].kind == KIND_MODDIV) == (t % 2 == 1 && t < 2 * steps);
         check(ok, "chain: rows and modular hints alternate over 13 levels");
         const Plan bare = any_order(s, un);
@@ -339,7 +278,7 @@ struct Suite : SolveRig<C> {
             x = N % 65521 * pw(D, 65519) % 65521;           // 65521 is prime
             sum += x;
         }
-        check(ok && run_plan(s, p, z) == NONE && rows_hold(s, z) && z[1].eq(u(sum)) && z[3 + 2 * steps].eq(u(x)), "chain: executes to the values of a 64-bit computation, and every row holds");
+        check(ok && execute(s, p, z) == NONE && rows_hold(s, z) && z[1].eq(u(sum)) && z[3 + 2 * steps].eq(u(x)), "chain: executes to the values of a 64-bit computation, and every row holds");
         for (int round = 0; round < 3; ++round) {
             std::vector<uint32_t> order(s.nr());
             for (uint32_t r = 0; r < order.size(); ++r) order[r] = round == 0 ? (uint32_t)order.size() - 1 - r : r;
@@ -347,7 +286,7 @@ struct Suite : SolveRig<C> {
             System t = s.permuted(order);
             const Plan q = hinted(t, un, hints);
             std::vector<Fr> zt = start(t);
-            bool equal = q.error == OK && launches_ok(q) && q.levels() == p.levels() && count_kind(q, KIND_MODDIV) == steps && run_plan(t, q, zt) == NONE && rows_hold(t, zt);
+            bool equal = q.error == OK && well_sorted(q) && q.levels() == p.levels() && count_kind(q, KIND_MODDIV) == steps && execute(t, q, zt) == NONE && rows_hold(t, zt);
             for (size_t j = 0; equal && j < p.steps.size(); ++j) equal = q.steps[j].level == p.steps[j].level && q.steps[j].kind == p.steps[j].kind && q.steps[j].col == p.steps[j].col;
             for (size_t j = 0; equal && j < z.size(); ++j) equal = zt[j].eq(z[j]);
             check(equal, std::string("chain: ") + (round ? "shuffled" : "reversed") + ", the same levels and the same assignment");
@@ -369,12 +308,12 @@ struct Suite : SolveRig<C> {
         for (uint64_t m : moduli) {
             std::vector<Fr> z(7, marker());
             z[0] = one; z[1] = u(6); z[2] = u(7); z[5] = u(m);
-            check(run_plan(s, p, z) == ((uint64_t)2 << 32 | 2) && z[4].is_zero(),
+            check(execute(s, p, z) == ((uint64_t)2 << 32 | 2) && z[4].is_zero(),
                   "stuck: P = " + std::to_string(m) + " (D = 0 mod P, a shared factor, or an even P) is reported at the hint, not at the row that then divides by the stored zero");
         }
         std::vector<Fr> z(7, marker());
         z[0] = one; z[1] = u(6); z[2] = u(7); z[5] = u(ok_modulus);
-        check(run_plan(s, p, z) == NONE && z[4].eq(u(38)) && rows_hold(s, z), "stuck: the same plan on P = 55 completes: 42 * 38 = 1596 = 29 * 55 + 1, though 55 is no prime");
+        check(execute(s, p, z) == NONE && z[4].eq(u(38)) && rows_hold(s, z), "stuck: the same plan on P = 55 completes: 42 * 38 = 1596 = 29 * 55 + 1, though 55 is no prime");
     }
     void mixed_launch() {
         // 0 one | 1 .. 4 D of hint 0 (n = 64, P secp256k1's) | 5 .. 8 D of hint 1 (n = 128, P = 2^384 + 5, a literal of four limbs) | 9 .. 12 Z of hint 0 | 13 .. 16 Z of hint 1
@@ -387,7 +326,7 @@ struct Suite : SolveRig<C> {
         desc.insert(desc.end(), second.begin(), second.end());
         const std::vector<Hint> hints = declare(s, desc);
         const Plan p = hinted(s, s.unknown(range(9, 8)), hints);
-        check(p.error == OK && p.steps.size() == 2 && p.launches.size() == 1 && p.launches[0].moddiv == 1 && p.launches[0].rounds == 128 * 3 + 256 && p.launches[0].inv_rounds == 1024 &&
+        check(p.error == OK && p.steps.size() == 2 && p.launches.size() == 1 && p.launches[0].kind == LAUNCH_MODDIV && p.launches[0].rounds == 128 * 3 + 256 && p.launches[0].inv_rounds == 1024 &&
                   p.steps[0].row == 0 && p.steps[1].row == 1,
               "mixed launch: one launch of two shapes, 640 reduction rounds and 2 * 512 inversion rounds (the larger of 448 and 512)");
         std::vector<Fr> z(17, marker());
@@ -395,7 +334,7 @@ struct Suite : SolveRig<C> {
         for (uint32_t j = 1; j <= 8; ++j) z[j] = F::zero();
         z[1] = u(2); z[5] = u(2);
         // 1 / 2 mod P = (P + 1) / 2
-        bool ok = p.error == OK && run_plan(s, p, z) == NONE;
+        bool ok = p.error == OK && execute(s, p, z) == NONE;
         ok = ok && z[9].eq(u(0xFFFFFFFF7FFFFE18ull)) && z[10].eq(u(~0ull)) && z[11].eq(u(~0ull)) && z[12].eq(u(0x7FFFFFFFFFFFFFFFull));
         ok = ok && z[13].eq(u(3)) && z[14].is_zero() && z[15].eq(F::pow(u(2), 127)) && z[16].is_zero();          // (2^384 + 6) / 2 = 2^383 + 3, and 383 = 2 * 128 + 127
         check(ok, "mixed launch: 1 / 2 modulo both moduli under the same trip counts");

@@ -227,7 +227,7 @@ struct Suite : SolveRig<C> {
             const Plan p = in_order(s, unknown), q = any_order(s, unknown);
             check(p.error == ERR_MANY_UNKNOWNS && p.error_row == 0, "waiting: build_plan refuses a decomposition before its booleanity rows");
             check(q.error == OK && q.reordered && q.steps.size() == 1 && q.steps[0].row == 0 && q.steps[0].kind == KIND_BITS_C && q.steps[0].bits == 2 && q.steps[0].level == 1 &&
-                      q.bit_cols == std::vector<uint32_t>({2, 3}) && q.launches.size() == 1 && q.launches[0].chain == 1,
+                      q.bit_cols == std::vector<uint32_t>({2, 3}) && q.launches.size() == 1 && q.launches[0].kind == LAUNCH_CHAIN,
                   "waiting: the decomposition row waits for its booleanity rows");
             std::vector<Fr> z = {one, u(2), marker(), marker()};
             check(q.error == OK && execute(s, q, z) == NONE && z[2].is_zero() && z[3].eq(one) && rows_hold(s, z), "waiting: ... and executes");

@@ -49,7 +49,7 @@ struct Suite : SolveRig<C> {
                 const Step &st = p.steps[t];
                 divides |= st.kind != KIND_C;
                 const uint32_t width = p.level_ptr[st.level] - p.level_ptr[st.level - 1];
-                ok = ok && (l.chain ? width < wide : (width >= wide && st.level == p.steps[l.lo].level));
+                ok = ok && (l.kind == LAUNCH_CHAIN ? width < wide : (width >= wide && st.level == p.steps[l.lo].level));
             }
             ok = ok && divides == (l.divides != 0);
         }
@@ -78,7 +78,7 @@ struct Suite : SolveRig<C> {
             ok = p.steps[t].row == t && p.steps[t].col == want_col[t] && p.steps[t].kind == KIND_C && p.steps[t].level == t + 1 && p.steps[t].pos == want_pos[t];
         check(ok, "mimc3: rows, columns, kinds, levels, entry positions");
         check(p.level_ptr == std::vector<uint32_t>({0, 1, 2, 3, 4, 5, 6}), "mimc3: level_ptr");
-        check(p.launches.size() == 1 && p.launches[0].chain == 1 && p.launches[0].divides == 0 && p.launches[0].lo == 0 && p.launches[0].hi == 6, "mimc3: one chain");
+        check(p.launches.size() == 1 && p.launches[0].kind == LAUNCH_CHAIN && p.launches[0].divides == 0 && p.launches[0].lo == 0 && p.launches[0].hi == 6, "mimc3: one chain");
         check_invariants(s, p, unknown, WIDE_STEPS, "mimc3: invariants");
         // execution against the native permutation
         Fr l = rnd(), r = rnd();
@@ -101,7 +101,7 @@ struct Suite : SolveRig<C> {
             for (uint32_t r = 0; r < nr; ++r) unknown[1 + nr + r] = 1;
             const Plan p = in_order(s, unknown, WIDE_STEPS, false);
             bool ok = p.error == OK && p.steps.size() == nr && p.level_ptr == std::vector<uint32_t>({0, nr}) && p.launches.size() == 1 &&
-                      p.launches[0].chain == (nr < WIDE_STEPS ? 1 : 0) && p.launches[0].divides == 0;
+                      (p.launches[0].kind == LAUNCH_CHAIN) == (nr < WIDE_STEPS) && p.launches[0].divides == 0;
             for (uint32_t r = 0; ok && r < nr; ++r) ok = p.steps[r].row == r && p.steps[r].col == 1 + nr + r && p.steps[r].level == 1 && p.steps[r].kind == KIND_C && p.steps[r].pos == r;
             check(ok, "diagonal: one level, wide from 32 steps on");
             check_invariants(s, p, unknown, WIDE_STEPS, "diagonal: invariants");
@@ -141,7 +141,7 @@ struct Suite : SolveRig<C> {
             check(ok, "random gates: levels are 1 + max of the inputs' levels");
             check_invariants(s, p, unknown, wide, "random gates: invariants");
             bool mixed[2] = {false, false};
-            for (const Launch &l : p.launches) mixed[l.chain] = true;
+            for (const Launch &l : p.launches) mixed[l.kind == LAUNCH_CHAIN] = true;
             check(wide == WIDE_STEPS ? (mixed[0] && mixed[1]) : wide == 4 ? mixed[0] : (mixed[1] && p.launches.size() == 1), "random gates: chains and level launches");
             std::vector<Fr> got(z.size(), F::zero());
             got[0] = z[0]; got[2] = z[2]; got[3] = z[3];
@@ -168,10 +168,10 @@ struct Suite : SolveRig<C> {
         const uint32_t want[4][4] = {{0, 3, KIND_A, 1}, {1, 4, KIND_B, 1}, {2, 5, KIND_C, 2}, {3, 6, KIND_B, 3}};   // row, column, kind, level
         for (int t = 0; ok && t < 4; ++t) ok = p.steps[t].row == want[t][0] && p.steps[t].col == want[t][1] && p.steps[t].kind == want[t][2] && p.steps[t].level == want[t][3];
         check(ok, "kinds: A, B, C, B at levels 1, 1, 2, 3");
-        check(p.level_ptr == std::vector<uint32_t>({0, 2, 3, 4}) && p.launches.size() == 1 && p.launches[0].chain && p.launches[0].divides, "kinds: one dividing chain");
+        check(p.level_ptr == std::vector<uint32_t>({0, 2, 3, 4}) && p.launches.size() == 1 && p.launches[0].kind == LAUNCH_CHAIN && p.launches[0].divides, "kinds: one dividing chain");
         check_invariants(s, p, unknown, WIDE_STEPS, "kinds: invariants");
         const Plan split = in_order(s, unknown, 1, false);        // every level wide: level 1 is a dividing launch, level 2 is not
-        check(split.launches.size() == 3 && !split.launches[0].chain && split.launches[0].divides && !split.launches[1].divides && split.launches[2].divides,
+        check(split.launches.size() == 3 && split.launches[0].kind != LAUNCH_CHAIN && split.launches[0].divides && !split.launches[1].divides && split.launches[2].divides,
               "kinds: the dividing kinds have launches of their own");
         check_invariants(s, split, unknown, 1, "kinds: invariants, wide");
         const Fr a = rnd(), c = rnd();

@@ -1,8 +1,9 @@
-// The rig of the witness solver's six CPU programs (solve_plan_selftest.cpp, solve_bits_selftest.cpp, solve_iszero_selftest.cpp,
-// solve_order_selftest.cpp, solve_divrem_selftest.cpp, solve_indicator_selftest.cpp): the systems they build, the two planners behind
-// one door each, the comparisons and invariants of plans, and ONE execute, which walks a plan's launches serially through the step
-// bodies the kernels call (polymath_amd/csrc/solve_steps.cuh) on the host field type.  A program keeps its cases, its literals, its
-// seed and its main.
+// The rig of the witness solver's eleven CPU programs (solve_plan_selftest.cpp, solve_bits_selftest.cpp, solve_iszero_selftest.cpp,
+// solve_order_selftest.cpp, solve_divrem_selftest.cpp, solve_indicator_selftest.cpp, solve_sqrt_selftest.cpp, solve_block_selftest.cpp,
+// solve_hint_selftest.cpp, solve_moddiv_selftest.cpp, solve_widediv_selftest.cpp): the systems they build, the planners behind one
+// door each (in matrix order, in any order, with declared hints), the comparisons of plans, ONE invariant of the schedule
+// (well_sorted) and ONE execute, which walks a plan's launches serially through every step body the kernels call
+// (polymath_amd/csrc/solve_steps.cuh) on the host field type.  A program keeps its cases, its literals, its seed and its main.
 //
 // Every plan that in_order / any_order return is folded, field by field, into a running 64-bit FNV-1a digest per curve; report()
 // prints it after the check count.  The drivers (tests/test_native_solve_*.py) assert the digests recorded from the planner as it
@@ -121,7 +122,11 @@ struct SolveRig {
         fold(p.level_ptr.size(), 8);
         for (uint32_t v : p.level_ptr) fold(v, 4);
         fold(p.launches.size(), 8);
-        for (const Launch &l : p.launches) { fold(l.lo, 4); fold(l.hi, 4); fold(l.chain, 1); fold(l.divides, 1); fold(l.bits, 1); fold(l.iszero, 1); fold(l.divrem, 1); fold(l.indicator, 1); }
+        // the bytes that the six flags of a launch were when the digests were recorded: chain, divides, bits, iszero, divrem, indicator
+        for (const Launch &l : p.launches) {
+            fold(l.lo, 4); fold(l.hi, 4); fold(l.kind == LAUNCH_CHAIN, 1); fold(l.divides, 1);
+            for (uint8_t kind : {LAUNCH_BITS, LAUNCH_ISZERO, LAUNCH_DIVREM, LAUNCH_INDICATOR}) fold(l.kind == kind, 1);
+        }
         fold(p.bit_cols.size(), 8);
         for (uint32_t v : p.bit_cols) fold(v, 4);
         fold(p.pairs.size(), 8);
@@ -138,6 +143,37 @@ struct SolveRig {
     Plan any_order(System &s, const std::vector<uint8_t> &unknown, uint32_t wide = WIDE_STEPS, bool with_modulus = true) {
         s.freeze();
         return folded(build_plan_any_order(s.m, s.nr(), s.m0, s.mw, unknown.data(), wide, with_modulus ? modulus : nullptr));
+    }
+    // ---- declared hints: a declaration decoded against the system (`why`: the refusal, empty where it is accepted), and the plan with it
+    std::vector<Hint> declare(const System &s, const std::vector<uint64_t> &desc, std::string *why = nullptr) {
+        std::vector<Hint> hints;
+        const std::string refused = decode_hints(desc.data(), desc.size(), s.m0 + s.mw, modulus, hints);
+        if (why) *why = refused;
+        return hints;
+    }
+    Plan hinted(System &s, const std::vector<uint8_t> &unknown, const std::vector<Hint> &hints, uint32_t wide = WIDE_STEPS) {
+        s.freeze();
+        return folded(build_plan_any_order(s.m, s.nr(), s.m0, s.mw, unknown.data(), wide, modulus, &hints));
+    }
+    typedef std::vector<uint32_t> Cols;
+    // one long-division record of pm_pk_set_hints under opcode `op` (1, or 5: the wide one); `lit`: the divisor's limbs as canonical
+    // words (then E is empty)
+    static std::vector<uint64_t> longdiv_record(uint32_t n, const Cols &q, const Cols &rem, const Cols &D, const Cols &E, const std::vector<uint64_t> &lit = {},
+                                                uint64_t op = HINT_LONGDIV) {
+        std::vector<uint64_t> w = {op, n, q.size(), rem.size(), D.size(), lit.empty() ? E.size() : lit.size() / 4, lit.empty() ? 0 : HINT_DIVISOR_LITERAL};
+        for (const Cols *cols : {&q, &rem, &D, &E}) w.insert(w.end(), cols->begin(), cols->end());
+        w.insert(w.end(), lit.begin(), lit.end());
+        return w;
+    }
+    static Cols range(uint32_t lo, uint32_t n) {
+        Cols v(n);
+        for (uint32_t i = 0; i < n; ++i) v[i] = lo + i;
+        return v;
+    }
+    static Fr from_words(const uint64_t w[4]) {      // a canonical integer of four words as an element
+        Fr v;
+        memcpy(v.l, w, 32);
+        return pm::to_mont<P>(v);
     }
 
     static Fr coef_at(const System &s, int k, uint64_t e) {
@@ -169,21 +205,38 @@ struct SolveRig {
         }
     };
     // The plan on the (frozen) system's matrices as the library runs it: the device records, their inverses, then the launch schedule
-    // walked serially through the kernels' dispatch, a launch that divides through the DIV = true bodies.  -> the stuck word as the
-    // kernels leave it BEFORE k_solve_stuck_row: the minimum of row, or of (level << 32) | row under a reordered plan; `stuck_rows`:
-    // every row that stuck, in the order of the walk
-    static uint64_t execute(const System &s, const Plan &p, std::vector<Fr> &z, std::vector<uint32_t> *stuck_rows = nullptr) {
+    // walked serially through the kernels' dispatch (solve.hip: solve_group), a launch that divides through the DIV = true bodies.  A
+    // step whose kind KIND_INFO does not map to its launch is a FAILED CHECK, and nothing runs it: solve_any would take a block or a
+    // hint for a decomposition or an ordinary step.  -> the stuck word as the kernels leave it BEFORE k_solve_stuck_row: the minimum of
+    // row, or of (level << 32) | row under a reordered plan (0 where a block is singular: "stuck at row 0" fails every caller);
+    // `stuck_rows`: every row that stuck, in the order of the walk; `counters`: what the wide divisions of the walk did
+    uint64_t execute(const System &s, const Plan &p, std::vector<Fr> &z, std::vector<uint32_t> *stuck_rows = nullptr, pm::WideCounters *counters = nullptr) {
         const Csr A{s.rowptr[0].data(), s.col[0].data(), s.val[0].data()}, B{s.rowptr[1].data(), s.col[1].data(), s.val[1].data()},
             Cm{s.rowptr[2].data(), s.col[2].data(), s.val[2].data()};
         pm::SolveRecords<P> rec = pm::solve_records<P>(p);
         const uint64_t count = rec.steps.size();
         for (uint64_t t = 0; t < count + 2 * rec.pairs.size(); ++t) pm::solve_inverse<P>(A, B, Cm, rec.steps.data(), count, rec.pairs.data(), rec.divs.data(), t);
+        uint32_t column = 0;
+        if (pm::solve_block_inverses<P>(p, rec, &column) != p.blocks.size()) return 0;
         uint64_t stuck = NONE;
         const StuckMin sink{&stuck, p.reordered, stuck_rows};
         for (const Launch &l : p.launches)
             for (uint32_t t = l.lo; t < l.hi; ++t) {
-                if (l.divides) pm::solve_any<P, true>(A, B, Cm, rec.steps[t], p.bit_cols.data(), rec.pairs.data(), rec.divs.data(), z.data(), sink);
-                else pm::solve_any<P, false>(A, B, Cm, rec.steps[t], p.bit_cols.data(), rec.pairs.data(), rec.divs.data(), z.data(), sink);
+                const pm::SolveStepDev<P> &st = rec.steps[t];
+                const bool known = st.kind < NUM_WIDE_KINDS;
+                if (!known || (l.kind == LAUNCH_CHAIN ? !KIND_INFO[st.kind].chained : KIND_INFO[st.kind].launch != l.kind)) {
+                    check(false, "execute: step " + std::to_string(t) + " of kind " + std::to_string(st.kind) + " lies in a launch of kind " + std::to_string(l.kind));
+                    continue;
+                }
+                switch (l.kind) {
+                case LAUNCH_BLOCK: pm::solve_block<P>(A, B, Cm, rec.blocks[st.bits], rec.block_idx.data(), rec.block_inv.data(), z.data()); break;
+                case LAUNCH_LONGDIV: pm::solve_longdiv<P>(st, rec.hints[st.bits], rec.hint_idx.data(), l.rounds, z.data(), sink); break;
+                case LAUNCH_MODDIV: pm::solve_moddiv<P>(st, rec.mods[st.bits], rec.hint_idx.data(), l.rounds, l.inv_rounds, z.data(), sink); break;
+                case LAUNCH_LONGDIV_WIDE: pm::solve_longdiv_wide<P>(st, rec.hints[st.bits], rec.hint_idx.data(), z.data(), sink, counters); break;
+                default:      // a chain, or the launch of a kind that one lane can walk: the same body
+                    if (l.divides) pm::solve_any<P, true>(A, B, Cm, st, p.bit_cols.data(), rec.pairs.data(), rec.divs.data(), z.data(), sink);
+                    else pm::solve_any<P, false>(A, B, Cm, st, p.bit_cols.data(), rec.pairs.data(), rec.divs.data(), z.data(), sink);
+                }
             }
         return stuck;
     }
@@ -192,8 +245,7 @@ struct SolveRig {
         return a.pos == b.pos && a.row == b.row && a.col == b.col && a.kind == b.kind && a.level == b.level && a.bits == b.bits && a.cols_off == b.cols_off;
     }
     static bool same_launch(const Launch &a, const Launch &b) {
-        return a.lo == b.lo && a.hi == b.hi && a.chain == b.chain && a.divides == b.divides && a.bits == b.bits && a.iszero == b.iszero && a.divrem == b.divrem &&
-               a.indicator == b.indicator;
+        return a.lo == b.lo && a.hi == b.hi && a.kind == b.kind && a.divides == b.divides && a.rounds == b.rounds && a.inv_rounds == b.inv_rounds;
     }
     static bool same_plan(const Plan &a, const Plan &b) {
         bool ok = a.error == b.error && a.error_row == b.error_row && a.error_col == b.error_col && a.message == b.message && a.steps.size() == b.steps.size() &&
@@ -222,13 +274,17 @@ struct SolveRig {
         for (const Step &st : p.steps) n += st.kind == kind;
         return n;
     }
-    // sorted by (level, kind, row), strictly; the launches cover the steps in that order; a wide launch holds division rows only or
-    // none, and indicator rows only or none; a launch that holds nothing but kind-C steps and indicator rows does not divide
+    // The schedule's invariant: the steps are sorted by (level, kind, row), strictly, and level_ptr says where the levels begin; the
+    // launches tile the steps in that order; launch kind and step kinds agree through KIND_INFO -- a chain holds only kinds that a lane
+    // can walk, every other launch only the kinds that map to its own, so no other launch holds such a step outside a chain --; a
+    // launch that is neither a chain nor a block or hint launch holds one level; `divides` is the OR of the table's entries (a launch
+    // that holds nothing but kind-C steps, indicator rows, blocks or hints does not divide); the trip counts are in their ranges on
+    // the three hint kinds and zero elsewhere
     static bool well_sorted(const Plan &p) {
         bool ok = p.level_ptr.size() == (size_t)p.levels() + 1 && (p.steps.empty() || (p.level_ptr.front() == 0 && p.level_ptr.back() == p.steps.size()));
         for (size_t t = 0; ok && t < p.steps.size(); ++t) {
             const Step &b = p.steps[t];
-            ok = b.level >= 1 && b.level <= p.levels() && p.level_ptr[b.level - 1] <= t && t < p.level_ptr[b.level];
+            ok = b.kind < NUM_WIDE_KINDS && b.level >= 1 && b.level <= p.levels() && p.level_ptr[b.level - 1] <= t && t < p.level_ptr[b.level];
             if (ok && t) {
                 const Step &a = p.steps[t - 1];
                 ok = a.level < b.level || (a.level == b.level && (a.kind < b.kind || (a.kind == b.kind && a.row < b.row)));
@@ -236,14 +292,17 @@ struct SolveRig {
         }
         uint32_t at = 0;
         for (const Launch &l : p.launches) {
-            ok = ok && l.lo == at && l.hi > l.lo;
-            bool divides = false;
+            const bool hint = l.kind == LAUNCH_LONGDIV || l.kind == LAUNCH_MODDIV || l.kind == LAUNCH_LONGDIV_WIDE, own = hint || l.kind == LAUNCH_BLOCK;
+            ok = ok && l.lo == at && l.hi > l.lo && l.hi <= p.steps.size() && l.kind <= LAUNCH_LONGDIV_WIDE;
+            uint8_t divides = 0;
             for (uint32_t t = l.lo; ok && t < l.hi; ++t) {
-                const uint32_t kind = p.steps[t].kind;
-                ok = l.chain || ((kind == KIND_INDICATOR) == (l.indicator != 0) && (kind == KIND_DIVREM) == (l.divrem != 0));
-                divides = divides || (kind != KIND_C && kind != KIND_BITS_C && kind != KIND_INDICATOR);
+                const KindInfo &info = KIND_INFO[p.steps[t].kind];
+                ok = (l.kind == LAUNCH_CHAIN ? info.chained != 0 : info.launch == l.kind) && (l.kind == LAUNCH_CHAIN || own || p.steps[t].level == p.steps[l.lo].level);
+                divides |= info.divides;
             }
-            ok = ok && divides == (l.divides != 0);
+            ok = ok && divides == l.divides;
+            ok = ok && (hint ? l.rounds >= 256 && l.rounds <= (l.kind == LAUNCH_LONGDIV_WIDE ? WIDE_D_BITS : HINT_D_BITS) : l.rounds == 0);
+            ok = ok && (l.kind == LAUNCH_MODDIV ? l.inv_rounds >= 512 && l.inv_rounds <= 1024 : l.inv_rounds == 0);
             at = l.hi;
         }
         return ok && at == p.steps.size();
@@ -287,4 +346,5 @@ struct SolveRig {
     using Rig::NONE; using Rig::name; using Rig::modulus; using Rig::check; using Rig::report; using Rig::rnd; using Rig::u; using Rig::marker;            \
     using Rig::quotient_marker; using Rig::indicator_marker; using Rig::is_marker; using Rig::in_order; using Rig::any_order; using Rig::coef_at;       \
     using Rig::rows_hold; using Rig::execute; using Rig::same_step; using Rig::same_launch; using Rig::same_plan; using Rig::column_levels;             \
-    using Rig::count_kind; using Rig::well_sorted; using Rig::ark; using Rig::circom; using Rig::keep_groups; using Rig::dot;
+    using Rig::count_kind; using Rig::well_sorted; using Rig::ark; using Rig::circom; using Rig::keep_groups; using Rig::dot;                           \
+    using Rig::declare; using Rig::hinted; using Rig::longdiv_record; using Rig::range; using Rig::from_words; typedef typename Rig::Cols Cols;

@@ -163,10 +163,10 @@ struct Suite : SolveRig<C> {
                                 Step want{zeros == 1 ? 1u : 0u, 0, 3, KIND_SQRT, 1};
                                 want.cols_off = zeros == 2 ? 1 : 0;
                                 ok = same_step(p.steps[0], want) && p.level_ptr == std::vector<uint32_t>({0, 1}) && p.launches.size() == 1 &&
-                                     same_launch(p.launches[0], wide == 1 ? Launch{0, 1, 0, 1} : Launch{0, 1, 1, 1}) && p.launches[0].sqrt == (wide == 1 ? 1 : 0) && well_sorted(p);
+                                     same_launch(p.launches[0], wide == 1 ? Launch{0, 1, LAUNCH_SQRT, 1} : Launch{0, 1, LAUNCH_CHAIN, 1}) && well_sorted(p);
                             }
                             check(ok, tag + ": the plan is the hand-written one, and its launch divides");
-                            check(same_plan(p, q) && q.launches.size() == p.launches.size() && (q.launches.empty() || q.launches[0].sqrt == p.launches[0].sqrt),
+                            check(same_plan(p, q) && q.launches.size() == p.launches.size() && (q.launches.empty() || (q.launches[0].kind == LAUNCH_SQRT) == (p.launches[0].kind == LAUNCH_SQRT)),
                                   tag + ": the any-order builder gives the same plan");
                             if (!ok) continue;
                             std::vector<Fr> z = {one, s_v, t_v, sqrt_marker()};
@@ -440,23 +440,23 @@ struct Suite : SolveRig<C> {
                 const Plan p = in_order(s, unknown, wide), q = any_order(s, unknown, wide);
                 bool ok = p.error == OK && count_kind(p, KIND_SQRT) == c.roots.size() && p.divs.size() == c.quotients.size() && well_sorted(p);
                 for (const Launch &l : p.launches)
-                    for (uint32_t t = l.lo; ok && t < l.hi; ++t) ok = l.chain ? l.sqrt == 0 && (p.steps[t].kind != KIND_SQRT || l.divides) : (p.steps[t].kind == KIND_SQRT) == (l.sqrt != 0);
+                    for (uint32_t t = l.lo; ok && t < l.hi; ++t) ok = l.kind == LAUNCH_CHAIN ? (p.steps[t].kind != KIND_SQRT || l.divides) : (p.steps[t].kind == KIND_SQRT) == (l.kind == LAUNCH_SQRT);
                 check(ok, c.what + ": plans in order; a wide launch holds square-root rows only or none, and a launch with one divides");
                 bool same = same_plan(p, q) && !q.reordered;
-                for (size_t t = 0; same && t < p.launches.size(); ++t) same = p.launches[t].sqrt == q.launches[t].sqrt;
+                for (size_t t = 0; same && t < p.launches.size(); ++t) same = (p.launches[t].kind == LAUNCH_SQRT) == (q.launches[t].kind == LAUNCH_SQRT);
                 check(same, c.what + ": in order the any-order builder is build_plan, field by field");
             }
             const Plan p = in_order(s, unknown);
             if (p.error != OK) continue;
             if (c.what == "square roots")
-                check(p.launches.size() == 2 && same_launch(p.launches[0], Launch{0, 40, 0, 1}) && p.launches[0].sqrt == 1 && same_launch(p.launches[1], Launch{40, 41, 1, 0}) &&
-                          p.launches[1].sqrt == 0 && p.levels() == 2,
+                check(p.launches.size() == 2 && same_launch(p.launches[0], Launch{0, 40, LAUNCH_SQRT, 1}) && same_launch(p.launches[1], Launch{40, 41, LAUNCH_CHAIN, 0}) &&
+                          p.levels() == 2,
                       "square roots: one square-root launch of its own, which divides, then the sum, which does not");
             if (c.what == "decompress")
-                check(p.levels() == 5 && p.launches.size() == 1 && p.launches[0].chain && p.launches[0].divides && count_kind(p, KIND_BITS_C) == 3 && count_kind(p, KIND_B) == 3,
+                check(p.levels() == 5 && p.launches.size() == 1 && p.launches[0].kind == LAUNCH_CHAIN && p.launches[0].divides && count_kind(p, KIND_BITS_C) == 3 && count_kind(p, KIND_B) == 3,
                       "decompress: five levels in one dividing chain: y2, u, x0, x and the bits, the sum");
             if (c.what == "mixed")
-                check(p.levels() == 4 && p.launches.size() == 1 && p.launches[0].chain && p.launches[0].divides && p.pairs.size() == 1 && p.steps[0].kind == KIND_SQRT,
+                check(p.levels() == 4 && p.launches.size() == 1 && p.launches[0].kind == LAUNCH_CHAIN && p.launches[0].divides && p.pairs.size() == 1 && p.steps[0].kind == KIND_SQRT,
                       "mixed: one dividing chain: the root, the division by it, the pair, the sum");
             const std::vector<uint32_t> levels = column_levels(s, p);
             std::vector<std::vector<Fr>> want;
@@ -525,7 +525,7 @@ struct Suite : SolveRig<C> {
         bool ok = p.error == OK && p.reordered && p.steps.size() == 2 && p.steps[0].kind == KIND_C && p.steps[0].row == 1 && p.steps[0].level == 1;
         if (ok) {
             Step want{0, 0, 4, KIND_SQRT, 2};
-            ok = same_step(p.steps[1], want) && p.launches.size() == 1 && same_launch(p.launches[0], Launch{0, 2, 1, 1}) && well_sorted(p);
+            ok = same_step(p.steps[1], want) && p.launches.size() == 1 && same_launch(p.launches[0], Launch{0, 2, LAUNCH_CHAIN, 1}) && well_sorted(p);
         }
         check(ok, "waiting root: it waits for its C side and is then taken as a square-root row, one level up");
         if (!ok) return;

@@ -1,5 +1,5 @@
 // CPU self-test of the witness solver's declared WIDE LONG-DIVISION hints (polymath_amd/host/solve_plan.hpp: decode_hints' opcode 5,
-// KIND_LONGDIV_WIDE, Launch::longdiv_wide; polymath_amd/csrc/solve_steps.cuh: wide_estimate, longdiv_wide_words, solve_longdiv_wide) on
+// KIND_LONGDIV_WIDE, LAUNCH_LONGDIV_WIDE; polymath_amd/csrc/solve_steps.cuh: wide_estimate, longdiv_wide_words, solve_longdiv_wide) on
 // the rig of the other solve_*_selftest.cpp programs.  Stand-alone: g++ -std=c++17, no HIP, no GPU; longdiv_wide_words, which runs
 // here, is the statement of the recurrence that the kernel k_solve_longdiv_wide distributes over a wave.  Its literals are not committed:
 // solve_widediv_cases.hpp is what
@@ -25,26 +25,8 @@ struct Suite : SolveRig<C> {
     const uint64_t (*pool)[4];
     Suite(const char *n, const WidedivCase *c, size_t nc, const uint64_t (*p)[4]) : Rig(n), cases(c), n_cases(nc), pool(p) {}
 
-    static Fr from_words(const uint64_t w[4]) {
-        Fr v;
-        memcpy(v.l, w, 32);
-        return pm::to_mont<P>(v);
-    }
-    static std::vector<uint32_t> range(uint32_t lo, uint32_t n) {
-        std::vector<uint32_t> v(n);
-        for (uint32_t i = 0; i < n; ++i) v[i] = lo + i;
-        return v;
-    }
-    typedef std::vector<uint32_t> Cols;
-    // one long-division record of pm_pk_set_hints under opcode `op` (1 or 5); `lit`: the divisor's limbs as canonical words (then E is empty)
-    static std::vector<uint64_t> record(uint64_t op, uint32_t n, const Cols &q, const Cols &rem, const Cols &D, const Cols &E, const std::vector<uint64_t> &lit = {}) {
-        std::vector<uint64_t> w = {op, n, q.size(), rem.size(), D.size(), lit.empty() ? E.size() : lit.size() / 4, lit.empty() ? 0 : HINT_DIVISOR_LITERAL};
-        for (const Cols *cols : {&q, &rem, &D, &E}) w.insert(w.end(), cols->begin(), cols->end());
-        w.insert(w.end(), lit.begin(), lit.end());
-        return w;
-    }
     static std::vector<uint64_t> wide(uint32_t n, const Cols &q, const Cols &rem, const Cols &D, const Cols &E, const std::vector<uint64_t> &lit = {}) {
-        return record(HINT_LONGDIV_WIDE, n, q, rem, D, E, lit);
+        return longdiv_record(n, q, rem, D, E, lit, HINT_LONGDIV_WIDE);
     }
     static std::vector<uint64_t> moddiv_record(uint32_t n, const Cols &z, const Cols &Dp, uint64_t modulus_literal) {
         std::vector<uint64_t> w = {HINT_MODDIV, n, z.size(), 0, 0, Dp.size(), 0, 1, HINT_MODULUS_LITERAL};
@@ -54,54 +36,6 @@ struct Suite : SolveRig<C> {
         return w;
     }
     static void append(std::vector<uint64_t> &to, const std::vector<uint64_t> &more) { to.insert(to.end(), more.begin(), more.end()); }
-    std::vector<Hint> declare(const System &s, const std::vector<uint64_t> &desc, std::string *why = nullptr) {
-        std::vector<Hint> hints;
-        const std::string refused = decode_hints(desc.data(), desc.size(), s.m0 + s.mw, modulus, hints);
-        if (why) *why = refused;
-        return hints;
-    }
-    Plan hinted(System &s, const std::vector<uint8_t> &unknown, const std::vector<Hint> &hints, uint32_t wide_steps = WIDE_STEPS) {
-        s.freeze();
-        return this->folded(build_plan_any_order(s.m, s.nr(), s.m0, s.mw, unknown.data(), wide_steps, modulus, &hints));
-    }
-    // the rig's execute with the hint launches in it; `counters`: what the wide divisions of the walk did
-    uint64_t run_plan(const System &s, const Plan &p, std::vector<Fr> &z, pm::WideCounters *counters = nullptr) {
-        const Csr A{s.rowptr[0].data(), s.col[0].data(), s.val[0].data()}, B{s.rowptr[1].data(), s.col[1].data(), s.val[1].data()},
-            Cm{s.rowptr[2].data(), s.col[2].data(), s.val[2].data()};
-        pm::SolveRecords<P> rec = pm::solve_records<P>(p);
-        const uint64_t count = rec.steps.size();
-        for (uint64_t t = 0; t < count + 2 * rec.pairs.size(); ++t) pm::solve_inverse<P>(A, B, Cm, rec.steps.data(), count, rec.pairs.data(), rec.divs.data(), t);
-        uint64_t stuck = NONE;
-        const typename Rig::StuckMin sink{&stuck, p.reordered, nullptr};
-        for (const Launch &l : p.launches)
-            for (uint32_t t = l.lo; t < l.hi; ++t) {
-                if (l.longdiv_wide) pm::solve_longdiv_wide<P>(rec.steps[t], rec.hints[rec.steps[t].bits], rec.hint_idx.data(), z.data(), sink, counters);
-                else if (l.moddiv) pm::solve_moddiv<P>(rec.steps[t], rec.mods[rec.steps[t].bits], rec.hint_idx.data(), l.rounds, l.inv_rounds, z.data(), sink);
-                else if (l.longdiv) pm::solve_longdiv<P>(rec.steps[t], rec.hints[rec.steps[t].bits], rec.hint_idx.data(), l.rounds, z.data(), sink);
-                else if (l.divides) pm::solve_any<P, true>(A, B, Cm, rec.steps[t], p.bit_cols.data(), rec.pairs.data(), rec.divs.data(), z.data(), sink);
-                else pm::solve_any<P, false>(A, B, Cm, rec.steps[t], p.bit_cols.data(), rec.pairs.data(), rec.divs.data(), z.data(), sink);
-            }
-        return stuck;
-    }
-    // the launches cover the steps in order; a wide launch holds wide hints only, is no chain, does not divide and is no other hint's or
-    // a block's launch; no other launch holds one; the steps are sorted by (level, kind, row)
-    static bool launches_ok(const Plan &p) {
-        uint32_t at = 0;
-        bool ok = true;
-        for (const Launch &l : p.launches) {
-            ok = ok && l.lo == at && l.hi > l.lo &&
-                 !(l.longdiv_wide && (l.chain || l.divides || l.bits || l.iszero || l.divrem || l.indicator || l.sqrt || l.block || l.longdiv || l.moddiv || l.inv_rounds)) &&
-                 (!l.longdiv_wide || (l.rounds >= 256 && l.rounds <= 8192));
-            for (uint32_t t = l.lo; ok && t < l.hi; ++t)
-                ok = (p.steps[t].kind == KIND_LONGDIV_WIDE) == (l.longdiv_wide != 0) && (p.steps[t].kind == KIND_MODDIV) == (l.moddiv != 0) && (p.steps[t].kind == KIND_LONGDIV) == (l.longdiv != 0);
-            at = l.hi;
-        }
-        for (size_t t = 1; ok && t < p.steps.size(); ++t) {
-            const Step &a = p.steps[t - 1], &b = p.steps[t];
-            ok = a.level < b.level || (a.level == b.level && (a.kind < b.kind || (a.kind == b.kind && a.row < b.row)));
-        }
-        return ok && at == p.steps.size();
-    }
 
     // ---- 1. wide divisions against Python's divmod.  A system without rows: columns 1 .. D, E (unless it is a literal), q, rem; the one
     // hint is ready at once
@@ -123,8 +57,8 @@ struct Suite : SolveRig<C> {
             outs.insert(outs.end(), R.begin(), R.end());
             const Plan p = hinted(s, s.unknown(outs), hints);
             Step want{0, 0, Q[0], KIND_LONGDIV_WIDE, 1};
-            check(p.error == OK && p.steps.size() == 1 && same_step(p.steps[0], want) && p.launches.size() == 1 && p.launches[0].longdiv_wide == 1 && p.launches[0].longdiv == 0 &&
-                      p.launches[0].lo == 0 && p.launches[0].hi == 1 && p.launches[0].rounds == std::min(8192u, c.n * (c.kD - 1) + 256u) && launches_ok(p) && p.reordered &&
+            check(p.error == OK && p.steps.size() == 1 && same_step(p.steps[0], want) && p.launches.size() == 1 && p.launches[0].kind == LAUNCH_LONGDIV_WIDE &&
+                      p.launches[0].lo == 0 && p.launches[0].hi == 1 && p.launches[0].rounds == std::min(8192u, c.n * (c.kD - 1) + 256u) && well_sorted(p) && p.reordered &&
                       p.hints.size() == 1,
                   tag + ": one step of kind KIND_LONGDIV_WIDE at level 1, row nr + 0, a launch of its own with its bound");
             if (p.error != OK) continue;
@@ -132,7 +66,7 @@ struct Suite : SolveRig<C> {
             z[0] = F::one();
             for (uint32_t j = 0; j < c.kD + kE_cols; ++j) z[1 + j] = from_words(pool[c.at + j]);
             pm::WideCounters counters;
-            const uint64_t stuck = run_plan(s, p, z, &counters);
+            const uint64_t stuck = execute(s, p, z, nullptr, &counters);
             check(c.stuck ? stuck == ((uint64_t)1 << 32 | 0) : stuck == NONE, tag + (c.stuck ? ": stuck at the hint's word" : ": not stuck"));
             bool ok = true;
             for (uint32_t j = 0; j < c.kq + c.kr; ++j) ok = ok && z[outs[j]].eq(from_words(pool[c.at + c.kD + c.kE + j]));
@@ -190,9 +124,9 @@ struct Suite : SolveRig<C> {
         refuse_decl(s, wide(128, q, rem, D, range(20, 33)), "hint 0: n (kE - 1) = 4096 is 4096 or more");
         check(declare(s, wide(65, q, rem, D, range(20, 64)), &why).size() == 1 && why.empty(), "n (kE - 1) = 4095 is accepted");
         // opcode 1 is not widened: its limits and texts are what they were
-        refuse_decl(s, record(HINT_LONGDIV, 16, q, rem, range(20, 33), E), "hint 0: kD = 33 is outside 1..32");
-        refuse_decl(s, record(HINT_LONGDIV, 16, q, rem, D, range(20, 17)), "hint 0: kE = 17 is outside 1..16");
-        refuse_decl(s, record(HINT_LONGDIV, 128, q, rem, range(20, 9), E), "hint 0: n (kD - 1) = 1024 is 1024 or more");
+        refuse_decl(s, longdiv_record(16, q, rem, range(20, 33), E), "hint 0: kD = 33 is outside 1..32");
+        refuse_decl(s, longdiv_record(16, q, rem, D, range(20, 17)), "hint 0: kE = 17 is outside 1..16");
+        refuse_decl(s, longdiv_record(128, q, rem, range(20, 9), E), "hint 0: n (kD - 1) = 1024 is 1024 or more");
         check(declare(s, wide(16, q, rem, range(20, 33), E), &why).size() == 1 && why.empty(), "kD = 33 is accepted under opcode 5");
         refuse_decl(s, wide(64, q, rem, {1, 401}, E), "hint 0: column 401 is not below m0 + mw = 401");
         refuse_decl(s, wide(64, {10, 0}, rem, D, E), "hint 0: an output is column 0 (the constant one)");
@@ -204,7 +138,7 @@ struct Suite : SolveRig<C> {
         got = declare(s, wide(64, q, rem, D, {}, lit), &why);
         check(got.size() == 1 && why.empty() && got[0].flags == HINT_DIVISOR_LITERAL && got[0].E.empty() && got[0].lit.size() == 8, "a literal limb equal to r - 1 is accepted");
         // all three opcodes in one declaration share the index h and the set of outputs
-        two = record(HINT_LONGDIV, 64, {20, 21}, {22}, {1, 2, 3}, {4});
+        two = longdiv_record(64, {20, 21}, {22}, {1, 2, 3}, {4});
         append(two, good);
         append(two, moddiv_record(64, {30}, {1}, 101));
         append(two, wide(64, {31, 32}, {33}, D, E));
@@ -212,7 +146,7 @@ struct Suite : SolveRig<C> {
         check(got.size() == 4 && why.empty() && got[0].op == HINT_LONGDIV && got[1].op == HINT_LONGDIV_WIDE && got[2].op == HINT_MODDIV && got[3].op == HINT_LONGDIV_WIDE &&
                   got[1].index == 1 && got[2].index == 2 && got[3].index == 3 && got[3].q == Cols({31, 32}),
               "all three opcodes in one declaration, in any mixture, share the index");
-        two = record(HINT_LONGDIV, 64, {20, 21}, {22}, {1, 2, 3}, {4});
+        two = longdiv_record(64, {20, 21}, {22}, {1, 2, 3}, {4});
         append(two, wide(64, {23, 22}, rem, D, E));
         refuse_decl(s, two, "hint 1: output column 22 is an output of hint 0 as well");
         two = good;
@@ -241,7 +175,7 @@ struct Suite : SolveRig<C> {
         s.add(Row{{one, 10}}, Row{{one, 1}}, Row{{one, 12}});
         std::vector<uint64_t> desc = wide(64, {8}, {9}, {4}, {3});
         append(desc, moddiv_record(64, {7}, {4}, 101));
-        append(desc, record(HINT_LONGDIV, 64, {5}, {6}, {4}, {3}));
+        append(desc, longdiv_record(64, {5}, {6}, {4}, {3}));
         append(desc, wide(128, {10}, {11}, {7, 0}, {3}));
         std::string why;
         const std::vector<Hint> hints = declare(s, desc, &why);
@@ -249,17 +183,17 @@ struct Suite : SolveRig<C> {
         const Plan p = hinted(s, s.unknown({4, 5, 6, 7, 8, 9, 10, 11, 12}), hints);
         // level 1: row 0.  level 2: the narrow division (hint 2, row 4), the modular one (hint 1, row 3), the wide one (hint 0, row 2).  level 3: wide hint 3 (row 5).  level 4: row 1
         const uint32_t kinds[6] = {KIND_C, KIND_LONGDIV, KIND_MODDIV, KIND_LONGDIV_WIDE, KIND_LONGDIV_WIDE, KIND_C}, rows[6] = {0, 4, 3, 2, 5, 1}, lv[6] = {1, 2, 2, 2, 3, 4};
-        bool ok = p.error == OK && p.steps.size() == 6 && launches_ok(p) && p.launches.size() == 6;
+        bool ok = p.error == OK && p.steps.size() == 6 && well_sorted(p) && p.launches.size() == 6;
         for (int t = 0; ok && t < 6; ++t) ok = p.steps[t].kind == kinds[t] && p.steps[t].row == rows[t] && p.steps[t].level == lv[t];
         for (int t = 0; ok && t < 6; ++t)
-            ok = p.launches[t].lo == (uint32_t)t && p.launches[t].longdiv_wide == (kinds[t] == KIND_LONGDIV_WIDE) && p.launches[t].moddiv == (kinds[t] == KIND_MODDIV) &&
-                 p.launches[t].longdiv == (kinds[t] == KIND_LONGDIV);
+            ok = p.launches[t].lo == (uint32_t)t && (p.launches[t].kind == LAUNCH_LONGDIV_WIDE) == (kinds[t] == KIND_LONGDIV_WIDE) && (p.launches[t].kind == LAUNCH_MODDIV) == (kinds[t] == KIND_MODDIV) &&
+                 (p.launches[t].kind == LAUNCH_LONGDIV) == (kinds[t] == KIND_LONGDIV);
         check(ok && p.launches[3].rounds == 256 && p.launches[4].rounds == 128 + 256, "meeting: in a level the narrow divisions' launch, the modular one, then the wide one; rounds = min(8192, n (kD - 1) + 256)");
         if (p.error != OK) printf("%s: %s\n", name, p.message.c_str());
         std::vector<Fr> z(13, marker());
         z[0] = one; z[1] = u(6); z[2] = u(7); z[3] = u(5);
         // d = 42 = 8 * 5 + 2; Z = 1 / 42 mod 101 = 89; D'' = 89 + 2^128, q'' = floor(D'' / 5), rem'' = D'' mod 5: 2^128 = 1 mod 5, so 90 mod 5 = 0
-        ok = ok && run_plan(s, p, z) == NONE && z[4].eq(u(42)) && z[5].eq(u(8)) && z[6].eq(u(2)) && z[7].eq(u(89)) && z[8].eq(u(8)) && z[9].eq(u(2)) && z[11].is_zero() &&
+        ok = ok && execute(s, p, z) == NONE && z[4].eq(u(42)) && z[5].eq(u(8)) && z[6].eq(u(2)) && z[7].eq(u(89)) && z[8].eq(u(8)) && z[9].eq(u(2)) && z[11].is_zero() &&
              F::mul(z[10], u(5)).eq(F::add(u(89), F::pow(u(2), 128))) && rows_hold(s, z);
         check(ok, "meeting: executes to 42 = 8 * 5 + 2 twice, 1 / 42 = 89 (mod 101) and (89 + 2^128) / 5 exactly");
         {   // two wide shapes in one launch: the bound is the larger one
@@ -268,7 +202,7 @@ struct Suite : SolveRig<C> {
             append(both, wide(121, {152}, {153}, range(70, 33), {141}));
             const std::vector<Hint> h2 = declare(t, both, &why);
             const Plan p2 = hinted(t, t.unknown({150, 151, 152, 153}), h2);
-            check(p2.error == OK && p2.launches.size() == 1 && p2.launches[0].longdiv_wide && p2.launches[0].rounds == 64 * 62 + 256 && p2.steps[0].row == 0 && p2.steps[1].row == 1,
+            check(p2.error == OK && p2.launches.size() == 1 && p2.launches[0].kind == LAUNCH_LONGDIV_WIDE && p2.launches[0].rounds == 64 * 62 + 256 && p2.steps[0].row == 0 && p2.steps[1].row == 1,
                   "two shapes in one launch: rounds is the larger of 4224 and 4128");
         }
     }
@@ -292,11 +226,11 @@ struct Suite : SolveRig<C> {
                   "refused: input column " + c + " (a dividend or divisor limb) that no row determines");
         }
         p = hinted(s, s.unknown({10, 11, 12, 30}), hints);
-        check(p.error == OK && count_kind(p, KIND_LONGDIV_WIDE) == 1 && p.steps.size() == 2 && launches_ok(p), "active: all outputs marked, one wide step beside the row");
+        check(p.error == OK && count_kind(p, KIND_LONGDIV_WIDE) == 1 && p.steps.size() == 2 && well_sorted(p), "active: all outputs marked, one wide step beside the row");
         {   // inert: the outputs are given, and the plan is the plan without the declaration
             const std::vector<uint8_t> un = s.unknown({30});
             const Plan with = hinted(s, un, hints), without = any_order(s, un);
-            check(with.error == OK && same_plan(with, without) && with.hints.empty() && with.launches.size() == 1 && !with.launches[0].longdiv_wide && with.launches[0].rounds == 0,
+            check(with.error == OK && same_plan(with, without) && with.hints.empty() && with.launches.size() == 1 && with.launches[0].kind != LAUNCH_LONGDIV_WIDE && with.launches[0].rounds == 0,
                   "inert: the plan without the declaration, field by field");
         }
     }
@@ -324,7 +258,7 @@ struct Suite : SolveRig<C> {
         const std::vector<Hint> hints = declare(s, desc);
         const std::vector<uint8_t> un = s.unknown(unknown);
         const Plan p = hinted(s, un, hints);
-        bool ok = p.error == OK && p.reordered && launches_ok(p) && count_kind(p, KIND_LONGDIV_WIDE) == steps && p.steps.size() == 2 * steps + 1 && p.levels() == 2 * steps + 1;
+        bool ok = p.error == OK && p.reordered && well_sorted(p) && count_kind(p, KIND_LONGDIV_WIDE) == steps && p.steps.size() == 2 * steps + 1 && p.levels() == 2 * steps + 1;
         for (size_t t = 0; ok && t < p.steps.size(); ++t) ok = p.steps[t].level == t + 1 && (p.steps[t].kind == KIND_LONGDIV_WIDE) == (t % 2 == 1 && t < 2 * steps);
         check(ok, "corpus: rows and wide hints alternate over 11 levels");
         const Plan bare = any_order(s, un);
@@ -341,7 +275,7 @@ struct Suite : SolveRig<C> {
             sum += prod / e + prod % e;
             x = prod % e;
         }
-        check(ok && run_plan(s, p, z) == NONE && rows_hold(s, z) && z[1].eq(u(sum)) && z[4 + 3 * steps].eq(u(x)), "corpus: executes to the values of a 64-bit computation, and every row holds");
+        check(ok && execute(s, p, z) == NONE && rows_hold(s, z) && z[1].eq(u(sum)) && z[4 + 3 * steps].eq(u(x)), "corpus: executes to the values of a 64-bit computation, and every row holds");
         for (int round = 0; round < 3; ++round) {
             std::vector<uint32_t> order(s.nr());
             for (uint32_t r = 0; r < order.size(); ++r) order[r] = round == 0 ? (uint32_t)order.size() - 1 - r : r;
@@ -349,7 +283,7 @@ struct Suite : SolveRig<C> {
             System t = s.permuted(order);
             const Plan q = hinted(t, un, hints);
             std::vector<Fr> zt = start(t);
-            bool equal = q.error == OK && launches_ok(q) && q.levels() == p.levels() && count_kind(q, KIND_LONGDIV_WIDE) == steps && run_plan(t, q, zt) == NONE && rows_hold(t, zt);
+            bool equal = q.error == OK && well_sorted(q) && q.levels() == p.levels() && count_kind(q, KIND_LONGDIV_WIDE) == steps && execute(t, q, zt) == NONE && rows_hold(t, zt);
             for (size_t j = 0; equal && j < p.steps.size(); ++j) equal = q.steps[j].level == p.steps[j].level && q.steps[j].kind == p.steps[j].kind && q.steps[j].col == p.steps[j].col;
             for (size_t j = 0; equal && j < z.size(); ++j) equal = zt[j].eq(z[j]);
             check(equal, std::string("corpus: ") + (round ? "shuffled" : "reversed") + ", the same levels and the same assignment");
@@ -369,13 +303,13 @@ struct Suite : SolveRig<C> {
               "stuck: the hint between two rows, at row nr + 0 = 2 and level 2");
         std::vector<Fr> z(8, marker());
         z[0] = one; z[1] = u(6); z[2] = u(7); z[6] = F::zero();
-        check(run_plan(s, p, z) == ((uint64_t)2 << 32 | 2) && z[4].is_zero() && z[5].is_zero(), "stuck: E = 0 is reported at the hint, not at the row that then divides by the stored zero");
+        check(execute(s, p, z) == ((uint64_t)2 << 32 | 2) && z[4].is_zero() && z[5].is_zero(), "stuck: E = 0 is reported at the hint, not at the row that then divides by the stored zero");
         z.assign(8, marker());
         z[0] = one; z[1] = u(6); z[2] = u(7); z[6] = u(100);
-        check(run_plan(s, p, z) == ((uint64_t)3 << 32 | 1) && z[4].is_zero() && z[5].eq(u(42)), "stuck: a quotient of zero is no stuck hint; the row that inverts it sticks, at its own row");
+        check(execute(s, p, z) == ((uint64_t)3 << 32 | 1) && z[4].is_zero() && z[5].eq(u(42)), "stuck: a quotient of zero is no stuck hint; the row that inverts it sticks, at its own row");
         z.assign(8, marker());
         z[0] = one; z[1] = u(6); z[2] = u(7); z[6] = u(42);
-        check(run_plan(s, p, z) == NONE && z[4].eq(one) && z[5].is_zero() && rows_hold(s, z), "stuck: the same plan on E = 42 completes");
+        check(execute(s, p, z) == NONE && z[4].eq(one) && z[5].is_zero() && rows_hold(s, z), "stuck: the same plan on E = 42 completes");
     }
 
     int run() {

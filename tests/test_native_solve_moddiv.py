@@ -1,5 +1,5 @@
 """CPU: the witness solver's declared modular-division hints (polymath_amd/host/solve_plan.hpp: decode_hints' opcode 3, KIND_MODDIV,
-Launch::moddiv; csrc/solve_steps.cuh: modinv_odd, solve_moddiv -- the text the kernel k_solve_moddiv calls), compiled with g++ from
+LAUNCH_MODDIV; csrc/solve_steps.cuh: modinv_odd, solve_moddiv -- the text the kernel k_solve_moddiv calls), compiled with g++ from
 tests/native/solve_moddiv_selftest.cpp.  Modular divisions against literals computed with Python's pow(D, -1, P)
 (solve_moddiv_cases.hpp, which tools/gen_solve_moddiv_cases.py writes into the test's directory before the program is built): P =
 secp256k1's prime, BLS12-381's q, 2^512 - 1, 3 and a composite; D = 1, P - 1, (P +- 1) / 2, 2^(L - 1), 0, P, a shared factor, limbs

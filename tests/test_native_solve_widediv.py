@@ -1,5 +1,5 @@
 """CPU: the witness solver's declared wide long-division hints (polymath_amd/host/solve_plan.hpp: decode_hints' opcode 5,
-KIND_LONGDIV_WIDE, Launch::longdiv_wide; csrc/solve_steps.cuh: wide_estimate, longdiv_wide_words -- the digit recurrence that the
+KIND_LONGDIV_WIDE, LAUNCH_LONGDIV_WIDE; csrc/solve_steps.cuh: wide_estimate, longdiv_wide_words -- the digit recurrence that the
 kernel k_solve_longdiv_wide distributes over a wave -- and solve_longdiv_wide), compiled with g++ from
 tests/native/solve_widediv_selftest.cpp.  Wide divisions against literals computed with Python's divmod (solve_widediv_cases.hpp,
 which tools/gen_solve_widediv_cases.py writes into the test's directory before the program is built): the six shapes and the operand

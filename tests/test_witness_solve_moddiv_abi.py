@@ -70,7 +70,7 @@ def test_header_and_plan_document_the_rule():
                    "operands beyond 1024 bits", "the slope of a doubling as one hint", "ACTIVE / INERT / mixed-marker rule"):
         assert needle in text, needle
     plan = " ".join(open(PLAN).read().replace("\n//", " ").split())
-    for needle in ("modular hint", "KIND_MODDIV", "HINT_MODDIV = 3", "Launch::moddiv", "Launch::inv_rounds = 2 L", "min(512, n (kP - 1) + 256)",
+    for needle in ("modular hint", "KIND_MODDIV", "HINT_MODDIV = 3", "LAUNCH_MODDIV", "Launch::inv_rounds = 2 L", "min(512, n (kP - 1) + 256)",
                    "P even or P < 3, P >= 2^512, N+, N-, D+ or D- >= 2^1024, gcd(D mod P, P) != 1", "Z >= 2^(n kz)", "Step::row = nr + h",
                    "other opcodes (modular inverse, gcd, sorting)", "even moduli", "gcd, sorting"):
         assert needle in plan, needle
