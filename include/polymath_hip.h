@@ -276,13 +276,31 @@ int pm_pk_export_bases(pm_ctx *ctx, const pm_pk *pk, int which, size_t offset, s
  * widened: kD = 33 under opcode 1 is refused as before.
  * Still out of scope: modular division at these widths (PM_HINT_MODDIV keeps 1024 / 512 bits), even moduli, linear blocks beyond 64
  * unknowns (RSA-4096 at 64-bit limbs; 3072-bit moduli at 96-bit limbs fit this record), hints on sharded keys, per-assignment
- * declarations, gcd, sorting. */
+ * declarations, gcd, sorting.  Of the modular record's list, the slope of a doubling now has a record of its own in the same stream
+ * (opcode 7; opcodes 2, 4 and 6 are refused as unknown, and so is 8):
+ *     PM_HINT_MODMULDIV, n, kz, kA, kB, kNp, kNm, kDp, kDm, kP, flags, cN, cD,
+ *       kz output columns, kA + kB factor columns, kNp + kNm addend columns, kDp + kDm denominator columns, then kP modulus columns
+ *       -- or, with PM_HINT_MODULUS_LITERAL (flags bit 0, the literal flag of opcode 3), kP limb values of four words each
+ * With each column list the sum of int(z_c_j) 2^(n j) (limbs need not be normalised) the step stores the kz n-bit limbs of the unique
+ * Z in [0, P) with cD (D+ - D-) Z = cN (A B + N+ - N-) (mod P).  cN and cD are one-word literals in 1 .. 2^32 - 1; because they are
+ * small literals the record works with a modulus held in columns as well.  The slope 3 X^2 / (2 Y) of a tangent (circom-ecdsa's
+ * Secp256k1Double, every "lamda <-- ..." of a doubling) is A = B = X, D+ = Y, cN = 3, cD = 2: A and B may name the same columns.
+ * kDp = kDm = 0 means D = 1, a modular multiply-add (the remainder of A B + C without its quotient); kNp = kNm = 0 means no addend.
+ * Refused like the modular record, with the same wording for columns, outputs, literal limbs and sharded keys: unknown flags; a
+ * truncated record; n outside 1..128; kz outside 1..16 or kP outside 1..16; kA or kB outside 1..32; kNp, kNm, kDp or kDm above 32;
+ * kDm > 0 with kDp = 0; n (k - 1) >= 1024 for any of the six operand lists; n (kP - 1) >= 512; cN or cD outside 1 .. 2^32 - 1.
+ * Records of all four opcodes may be mixed in one declaration; they share the index h, and no output may be named by two hints of
+ * any opcode.  PM_HINT_MODDIV itself is not touched: its record, its results and its plans are what they were.
+ * Still out of scope: curves with a != 0 as a case of their own (the numerator 3 X^2 + a is N+ = a, which this record allows);
+ * complete addition formulas; windowed or GLV scalar multiplication; operands beyond 1024 bits; even moduli; hints on sharded keys;
+ * per-assignment declarations. */
 typedef enum pm_hint_op { PM_HINT_LONGDIV = 1 } pm_hint_op;
 typedef enum pm_hint_flags { PM_HINT_DIVISOR_LITERAL = 1 } pm_hint_flags;
 typedef enum pm_key_hints { PM_KEY_HINTS = 1024 } pm_key_hints;
 typedef enum pm_hint_op_modular { PM_HINT_MODDIV = 3 } pm_hint_op_modular;
 typedef enum pm_hint_moddiv_flags { PM_HINT_MODULUS_LITERAL = 1 } pm_hint_moddiv_flags;
 typedef enum pm_hint_op_wide { PM_HINT_LONGDIV_WIDE = 5 } pm_hint_op_wide;
+typedef enum pm_hint_op_muldiv { PM_HINT_MODMULDIV = 7 } pm_hint_op_muldiv;
 void pm_pk_free(pm_pk *pk);
 
 /* ---- proving keys as bytes: ProvingKey::serialize_compressed (data_structures.rs:56-73), decoded on the device ---------
@@ -590,6 +608,18 @@ int pm_prove_phase3(pm_ctx *ctx, const uint64_t *x1, const uint64_t *x2, const u
  *   Without an active wide hint every plan, message and word is what it is without this rule.  Not handled: modular division at these
  *   widths, even moduli, linear blocks beyond 64 unknowns (RSA-4096 at 64-bit limbs), hints on sharded keys, per-assignment
  *   declarations, gcd, sorting.
+ *   Declared hints: modular multiply-divide.  The slope of a DOUBLING has its own record, PM_HINT_MODMULDIV (pm_pk_set_hints above
+ *   states it): the tangent's slope 3 X^2 / (2 Y) mod p has a product for its numerator, which PM_HINT_MODDIV's column lists cannot
+ *   express unless the circuit happens to carry 3 X^2 as columns, and a key's rows are fixed by its verifying key.  With it ECDSA
+ *   verification completes: s^-1, h / s and r / s by opcode 3, the scalars' bits by decomposition rows, the conditional additions by
+ *   ordinary rows, the reductions by opcode 1 and the linear blocks.  The rules are the modular hint's -- ACTIVE / INERT /
+ *   mixed-marker, HINT-OWNED outputs, waiting on inputs, the never-ready refusal -- applied to the kz outputs, and the hint is ONE step
+ *   at 1 + the largest level of its inputs, after the wide long divisions of that level.  The assignment is STUCK at the word nr + h,
+ *   with zero in every output, where P is even or P < 3, P >= 2^512, any of the six list sums is >= 2^1024,
+ *   gcd(cD D mod P, P) != 1 (D = 0 mod P included, and a cD that shares a factor with a composite P), or Z >= 2^(n kz) -- and in no
+ *   other case: the literals scale residues, after the reductions.  Without an active multiply-divide hint every plan, message and
+ *   word is what it is without this rule.  Not handled: complete addition formulas, windowed or GLV scalar multiplication, operands
+ *   beyond 1024 bits, even moduli, hints on sharded keys, per-assignment declarations.
  *   PM_ERR_INVALID_ARG, pm_last_error naming the row or column, nothing computed and no output written: an unsolvable row, a marked
  *   column that no row determines, a marker at column 0, a sharded key, and -- in a batch -- an assignment that does not mark the
  *   columns assignment 0 marks, or marks one with the other marker (any two of the four markers differ; the first differing (assignment, column) is named; a kernel

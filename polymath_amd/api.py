@@ -69,6 +69,10 @@ MODDIV_LIMITS = {"n": 128, "kz": 16, "kNp": 32, "kNm": 32, "kDp": 32, "kDm": 32,
 # the third opcode, the wide long division (4 is refused as unknown): opcode 1's record and flag under limits of its own
 HINT_LONGDIV_WIDE = 5
 WIDE_LIMITS = {"n": 128, "kq": 128, "kr": 64, "kD": 128, "kE": 64}
+# the fourth opcode, the modular multiply-divide cD (D+ - D-) Z = cN (A B + N+ - N-) mod P (6 is refused as unknown): opcode 3's flag,
+# the limits of its record; cN and cD are one-word literals in 1 .. 2^32 - 1
+HINT_MODMULDIV = 7
+MODMULDIV_LIMITS = {"n": 128, "kz": 16, "kA": 32, "kB": 32, "kNp": 32, "kNm": 32, "kDp": 32, "kDm": 32, "kP": 16, "c": 2 ** 32 - 1}
 NOT_STUCK = 0xFFFFFFFFFFFFFFFF                # first word of a tap-9 record of an assignment that completed
 TIMING_SLOTS = ["witness_map", "ntt", "poly", "msm_sort", "msm_accumulate", "msm_reduce", "msm_total", "phase"]
 
@@ -231,9 +235,30 @@ def encode_hints(hints):
     (the divisor's limbs as Python integers)} or a tuple (n, q, rem, D, E) / (n, q, rem, D, None, literal); q, rem, D, E are lists of
     CSR columns (0: the constant one, then the instance, then the witness).  A modular division is a dict with "op": "moddiv":
     {"op", "n", "z", "Dp", "P" (modulus columns) or "literal" (the modulus' limbs), and optionally "Np", "Nm", "Dm"}; without "Np" and
-    "Nm" the numerator is 1.  A wide long division is the long division's dict with "op": "longdiv_wide".  -> np.uint64[n_words]"""
+    "Nm" the numerator is 1.  A wide long division is the long division's dict with "op": "longdiv_wide".  A modular multiply-divide
+    is a dict with "op": "modmuldiv": {"op", "n", "z", "A", "B", "P" or "literal", and optionally "Np", "Nm", "Dp", "Dm" (no denominator
+    lists: D = 1), "cN", "cD" (1 where absent)}.  -> np.uint64[n_words]"""
     words = []
     for hint in hints:
+        if isinstance(hint, dict) and hint.get("op") == "modmuldiv":
+            P, literal = hint.get("P"), hint.get("literal")
+            if (P is None) == (literal is None):
+                raise ValueError("a modular hint has modulus columns P or a literal modulus, not both and not neither")
+            lists = [list(hint["z"]), list(hint["A"]), list(hint["B"])] + [list(hint.get(key, ())) for key in ("Np", "Nm", "Dp", "Dm")]
+            modulus = list(P) if literal is None else list(literal)
+            cN, cD = int(hint.get("cN", 1)), int(hint.get("cD", 1))
+            if not (1 <= cN < 1 << 32 and 1 <= cD < 1 << 32):
+                raise ValueError("cN and cD are one-word literals in 1 .. 2^32 - 1")
+            words += [HINT_MODMULDIV, int(hint["n"])] + [len(v) for v in lists] + [len(modulus), 0 if literal is None else HINT_MODULUS_LITERAL, cN, cD]
+            words += [int(c) for v in lists for c in v]
+            if literal is None:
+                words += [int(c) for c in modulus]
+            else:
+                for limb in modulus:
+                    if not 0 <= int(limb) < 1 << 256:
+                        raise ValueError("a literal limb is four words")
+                    words += [(int(limb) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]
+            continue
         if isinstance(hint, dict) and hint.get("op", "longdiv") not in ("longdiv", "longdiv_wide"):
             if hint["op"] != "moddiv":
                 raise ValueError("unknown hint op %r" % (hint["op"],))
@@ -275,9 +300,24 @@ def encode_hints(hints):
 def decode_hints(words):
     """encode_hints backwards: -> a list of dicts (the words are trusted to be well-formed: the library is what refuses).  A modular
     division comes back with "op": "moddiv" and all of "Np", "Nm", "Dp", "Dm" (empty lists where the record has none), a wide long
-    division with "op": "longdiv_wide" """
+    division with "op": "longdiv_wide", a modular multiply-divide with "op": "modmuldiv", all six lists, "cN" and "cD" """
     words, out, at = [int(v) for v in words], [], 0
     while at < len(words):
+        if words[at] == HINT_MODMULDIV:
+            n, kz, kA, kB, kNp, kNm, kDp, kDm, kP, flags, cN, cD = words[at + 1:at + 13]
+            at += 13
+            hint = {"op": "modmuldiv", "n": n, "cN": cN, "cD": cD}
+            for key, k in (("z", kz), ("A", kA), ("B", kB), ("Np", kNp), ("Nm", kNm), ("Dp", kDp), ("Dm", kDm)):
+                hint[key] = words[at:at + k]
+                at += k
+            if flags & HINT_MODULUS_LITERAL:
+                hint["literal"] = [sum(words[at + 4 * i + j] << (64 * j) for j in range(4)) for i in range(kP)]
+                at += 4 * kP
+            else:
+                hint["P"] = words[at:at + kP]
+                at += kP
+            out.append(hint)
+            continue
         if words[at] == HINT_MODDIV:
             n, kz, kNp, kNm, kDp, kDm, kP, flags = words[at + 1:at + 9]
             at += 9

@@ -1425,6 +1425,361 @@ def narrow_modulus(n, limbs, bits, seed=SPLITMIX_SEED):
     return sum(((1 << bits) + (g.next_u64() | (1 if j == 0 else 0))) << (n * j) for j in range(limbs))
 
 
+def product_pad(modulus, n, bounds):
+    """subtraction_pad for subtrahends whose limbs are not n-bit ones -- the 2l - 1 limbs of a no-carry product, scaled or not:
+    len(bounds) limbs whose integer  sum pad_j 2^(n j)  is a multiple of the modulus and pad_j >= bounds[j], the largest value limb j
+    of the subtrahend can take.  pad_j = 2^(b_j) + e_j with 2^(b_j) the smallest power of two above bounds[j] and e the n-bit limbs of
+    -(sum 2^(b_j) 2^(n j)) mod modulus, laid over the lowest limbs (more of them than the subtrahend has are appended)."""
+    tops = [1 << int(hi).bit_length() for hi in bounds]
+    e = -sum(t << (n * j) for j, t in enumerate(tops)) % modulus
+    count = max(len(tops), -(-max(e.bit_length(), 1) // n))
+    pad = [(tops[j] if j < len(tops) else 0) + v for j, v in enumerate(int_limbs(e, n, count))]
+    assert limbs_int(pad, n) % modulus == 0 and all(v >= hi for v, hi in zip(pad, bounds))
+    return pad
+
+
+def affine_add(p, P1, P2):
+    """P1 + P2 on y^2 = x^3 + b over the prime p (a = 0), affine on Python integers; None is the point at infinity"""
+    if P1 is None or P2 is None:
+        return P1 if P2 is None else P2
+    (x1, y1), (x2, y2) = P1, P2
+    if x1 == x2 and (y1 + y2) % p == 0:
+        return None
+    lam = 3 * x1 * x1 * pow(2 * y1, -1, p) % p if P1 == P2 else (y2 - y1) * pow(x2 - x1, -1, p) % p
+    x3 = (lam * lam - x1 - x2) % p
+    return x3, (lam * (x1 - x3) - y1) % p
+
+
+def affine_mul(p, k, P1):
+    """[k] P1 by double-and-add on Python integers"""
+    out = None
+    for bit in bin(k)[2:] if k else "":
+        out = affine_add(p, out, out)
+        if bit == "1":
+            out = affine_add(p, out, P1)
+    return out
+
+
+class _PartialModMulDiv(_PartialModDiv):
+    """What LimbModMulDiv, EcDoubleAddChain and EcdsaVerify add to _PartialModDiv: the MULTIPLY-DIVIDE hint (opcode 7), subtraction of
+    product limbs, and a second modulus.
+      _over       the helpers of _PartialModDiv read self.modulus and its pad; `with self._over(q):` runs them modulo q (ECDSA works
+                  modulo the field's prime and modulo the group order)
+      _muldiv     Z with cD (D+ - D-) Z = cN (A B + N+ - N-) mod p from a multiply-divide hint: l witnesses, with `decompose` their bits
+      _scaled     c times a list of limbs
+      _minus_wide x - y + product_pad(bounds of y): y may be the limbs of a product
+      _double, _add   a tangent and a chord on y^2 = x^3 + b, each slope a hint with its exact check"""
+
+    def _over(self, modulus):
+        circuit = self
+
+        class _Scope:
+            def __enter__(self):
+                self.saved = circuit.modulus, circuit._pad
+                circuit.modulus, circuit._pad = modulus, subtraction_pad(modulus, circuit.n, circuit.limbs, circuit.operand_bits)
+
+            def __exit__(self, *exc):
+                circuit.modulus, circuit._pad = self.saved
+
+        return _Scope()
+
+    @staticmethod
+    def _scaled(limbs, c):
+        return [([(coef * c, var) for coef, var in lc], v * c, hi * c) for lc, v, hi in limbs]
+
+    def _minus_wide(self, x, y):
+        pad = product_pad(self.modulus, self.n, [hi for _, _, hi in y])
+        zero = ([], 0, 0)
+        out = []
+        for j in range(max(len(x), len(pad))):
+            (lc, v, hi), (lc_y, v_y, _) = x[j] if j < len(x) else zero, y[j] if j < len(y) else zero
+            pad_j = pad[j] if j < len(pad) else 0
+            lc = [term for term in _merged(lc + [(-c, var) for c, var in lc_y] + [(pad_j, ConstraintSystem.ONE)]) if term[0]]
+            assert v - v_y + pad_j >= 0
+            out.append((lc, v - v_y + pad_j, hi + pad_j))
+        return out
+
+    def _muldiv(self, cs, A, B, Np, Nm, Dp, Dm, cN=1, cD=1):
+        """Operands: lists of limbs that are single witness columns (or empty lists); B may be A itself.  -> the limbs of Z"""
+        p, n = self.modulus, self.n
+        index = lambda limbs: [lc[0][1][1] for lc, _, _ in limbs]
+        assert all(len(lc) == 1 and lc[0][0] == 1 and lc[0][1][0] == "wit" for lc, _, _ in A + B + Np + Nm + Dp + Dm)
+        value = lambda limbs: limbs_int([v for _, v, _ in limbs], n)
+        N = cN * (value(A) * value(B) + value(Np) - value(Nm)) % p
+        D = cD * ((value(Dp) - value(Dm)) if Dp or Dm else 1) % p
+        Z = N * pow(D, -1, p) % p            # raises where cD D has no inverse: the generator's inputs must avoid it
+        out, at = self._fresh(cs, int_limbs(Z, n, self.limbs))
+        self._declared.append({"op": "modmuldiv", "n": n, "z": at, "A": index(A), "B": index(B), "Np": index(Np), "Nm": index(Nm), "Dp": index(Dp), "Dm": index(Dm),
+                               "cN": cN, "cD": cD, "literal": int_limbs(p, n, self.limbs)})
+        self._bits(cs, out)
+        return out
+
+    def _muldiv_check(self, cs, Z, A, B, Np, Nm, Dp, Dm, cN=1, cD=1):
+        """cD Z (D+ - D-) - cN (A B + N+ - N-) = 0 (mod p), exactly: the products' blocks, then _reduce with a remainder of zero"""
+        if Dp or Dm:
+            left = self._product(cs, Z, self._scaled(self._minus(Dp, Dm) if Dm else Dp, cD))
+        else:
+            left = self._scaled(Z, cD)
+        right = self._product(cs, A, B)
+        if Np or Nm:
+            addend = self._minus(Np or [([], 0, 0)] * len(Nm), Nm) if Nm else Np
+            right = [(_merged(lc + (addend[j][0] if j < len(addend) else [])), v + (addend[j][1] if j < len(addend) else 0), hi + (addend[j][2] if j < len(addend) else 0))
+                     for j, (lc, v, hi) in enumerate(right)]
+        self._reduce(cs, self._minus_wide(left, self._scaled(right, cN)), zero=True)
+
+    def _double(self, cs, X, Y):
+        """2 (X, Y): lambda = 3 X^2 / (2 Y) from the multiply-divide hint, the tangent check lambda 2 Y - 3 X X = 0, then
+        X' = lambda^2 - 2 X and Y' = lambda (X - X') - Y"""
+        lam = self._muldiv(cs, X, X, [], [], Y, [], 3, 2)
+        self._muldiv_check(cs, lam, X, X, [], [], Y, [], 3, 2)
+        X3 = self._reduce(cs, self._minus(self._minus(self._product(cs, lam, lam), X), X))
+        Y3 = self._reduce(cs, self._minus(self._product(cs, lam, self._minus(X, X3)), Y))
+        return X3, Y3
+
+    def _add(self, cs, X1, Y1, X2, Y2):
+        """(X1, Y1) + (X2, Y2) for X1 != X2, as EcAddChain does it: the chord's slope from a modular hint with its exact check"""
+        lam = self._quotient(cs, Y2, Y1, X2, X1)
+        self._reduce(cs, self._minus(self._product(cs, lam, self._minus(X2, X1)), self._minus(Y2, Y1), 2), zero=True)
+        X3 = self._reduce(cs, self._minus(self._minus(self._product(cs, lam, lam), X1), X2))
+        Y3 = self._reduce(cs, self._minus(self._product(cs, lam, self._minus(X1, X3)), Y1))
+        return X3, Y3
+
+    def _value(self, limbs):
+        return limbs_int([v for _, v, _ in limbs], self.n)
+
+    def hints(self, m0=2):
+        """_PartialModDiv.hints with the multiply-divide records, whose cN and cD are literals like n"""
+        if not getattr(self, "_declared", None):
+            self.generate_constraints(_ValuesOnly(_LAYOUT_R))
+        return [{key: v if key in ("op", "n", "literal", "cN", "cD") else [m0 + j for j in v] for key, v in hint.items()} for hint in self._declared]
+
+
+class LimbModMulDiv(_PartialModMulDiv):
+    """Non-native multiply-divide (the slope of a doubling, a modular multiply-add): per case (A, B, N+, N-, D+, D-) of integers their
+    given limbs -- B = None: B is A, on the same columns; (N+, N-) or (D+, D-) = (None, None): no addend, no denominator (D = 1) --,
+    Z from a multiply-divide hint with the literals cN and cD, and ONE exact check
+        cD Z (D+ - D- + pad) - cN (A B + N+ - N- + pad) + product_pad = 0  (mod modulus)
+    the products' blocks, then _reduce with a remainder that must be zero.  One ordinary row per case sums Z's limbs, and the public
+    input is the sum of those.  operand_bits as in LimbModDiv."""
+
+    def __init__(self, cases, modulus, n, limbs, cN=1, cD=1, decompose=True, operand_bits=None):
+        self.cases, self.modulus, self.n, self.limbs, self.cN, self.cD = [tuple(c) for c in cases], int(modulus), n, limbs, int(cN), int(cD)
+        self.decompose, self.operand_bits = decompose, operand_bits
+
+    def generate_constraints(self, cs):
+        self._setup(cs)
+        sums = []
+        given = lambda v: [] if v is None else self._given_limbs(cs, v, self.operand_bits)
+        for A_v, B_v, Np_v, Nm_v, Dp_v, Dm_v in self.cases:
+            assert (Np_v is None) == (Nm_v is None) and (Dp_v is None) == (Dm_v is None), "a pair of lists is absent as a pair"
+            A = given(A_v)
+            B = A if B_v is None else given(B_v)
+            Np, Nm, Dp, Dm = given(Np_v), given(Nm_v), given(Dp_v), given(Dm_v)
+            Z = self._muldiv(cs, A, B, Np, Nm, Dp, Dm, self.cN, self.cD)
+            self._muldiv_check(cs, Z, A, B, Np, Nm, Dp, Dm, self.cN, self.cD)
+            sums.append(Z)
+        self._close(cs, sums)
+
+
+def modmuldiv_cases(modulus, count, seed=SPLITMIX_SEED, cD=1, addend=True, denominator=True, square=False, narrow=None):
+    """`count` cases (A, B, N+, N-, D+, D-) of integers for LimbModMulDiv, drawn from SplitMix64(seed); without `addend` or
+    `denominator` that pair is (None, None), with `square` B is None (A's columns).  Operands as in moddiv_cases; a denominator for
+    which cD (D+ - D-) has no inverse modulo a composite modulus is drawn again."""
+    from math import gcd
+    g = SplitMix64(seed)
+    rnd = lambda bits: sum(g.next_u64() << (64 * i) for i in range(-(-bits // 64))) & ((1 << bits) - 1)
+    draw = (lambda: rnd(modulus.bit_length() + 64) % modulus) if narrow is None else (lambda: sum(rnd(narrow[2]) << (narrow[0] * j) for j in range(narrow[1])))
+    out = []
+    while len(out) < count:
+        A, B, Np, Nm, Dp, Dm = (draw() for _ in range(6))
+        if gcd(cD * ((Dp - Dm) if denominator else 1) % modulus, modulus) == 1:
+            out.append((A, None if square else B) + ((Np, Nm) if addend else (None, None)) + ((Dp, Dm) if denominator else (None, None)))
+    return out
+
+
+class EcDoubleAddChain(_PartialModMulDiv):
+    """`steps` times R <- 2 R + Q on a short Weierstrass curve y^2 = x^3 + b over `modulus` (a = 0), on l limbs of n bits: R_0 =
+    `point` and Q = `addend` are given.  Per step the tangent (_double: the slope 3 X^2 / (2 Y) is ONE multiply-divide hint, checked
+    by lambda 2 Y - 3 X X = 0) and then the chord as in EcAddChain (_add).  One ordinary row per step sums the limbs of the new R;
+    the public input is the sum of those.  The result is compared with affine arithmetic on Python integers; a vertical tangent or
+    meeting x-coordinates is asserted."""
+
+    def __init__(self, point, addend, modulus, n, limbs, steps, decompose=True):
+        self.point, self.addend, self.modulus, self.n, self.limbs, self.steps = tuple(point), tuple(addend), int(modulus), n, limbs, steps
+        self.decompose, self.operand_bits = decompose, None
+
+    def result(self):
+        """R_0 after `steps` times 2 R + Q, by the affine formulas on Python integers"""
+        p, R = self.modulus, self.point
+        for _ in range(self.steps):
+            assert R[1] % p, "a vertical tangent: the doubling's slope is not defined"
+            R = affine_add(p, R, R)
+            assert (R[0] - self.addend[0]) % p, "the x-coordinates meet: the chord's slope is not defined"
+            R = affine_add(p, R, self.addend)
+        return R
+
+    def generate_constraints(self, cs):
+        self._setup(cs)
+        want = self.result()         # asserts that every tangent and chord has a slope
+        X1, Y1 = self._given_limbs(cs, self.point[0]), self._given_limbs(cs, self.point[1])
+        X2, Y2 = self._given_limbs(cs, self.addend[0]), self._given_limbs(cs, self.addend[1])
+        sums = []
+        for _ in range(self.steps):
+            X1, Y1 = self._double(cs, X1, Y1)
+            X1, Y1 = self._add(cs, X1, Y1, X2, Y2)
+            sums.append(X1 + Y1)
+        assert (self._value(X1), self._value(Y1)) == want
+        self._close(cs, sums)
+
+
+# y^2 = x^3 + b as (p, b, order, G), and the literal point the verifier's accumulator starts from
+SECP256K1 = (2 ** 256 - 2 ** 32 - 977, 7, 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141,
+             (0x79BE667EF9DCBBAC55A06295CE870B07029BFCDB2DCE28D959F2815B16F81798, 0x483ADA7726A3C4655DA4FBFC0E1108A8FD17B448A68554199C47D08FFB10D4B8))
+SECP256K1_START = (1004, 0x6FCBC4426CE7C7F6851B83EA89CD3F118ACFA8089CE3820ED5F2DEAB371701D4)
+TOY_CURVE = (2 ** 22 - 3, 2, 4193929, (1, 2048))       # order prime, order < p < 2 order: the tests' curve, 22 scalar bits at (n, limbs) = (11, 2)
+TOY_START = (1000, 1163942)
+
+
+def ecdsa_schedule(curve, start, Q, u1, u2, bits):
+    """The verifier's schedule on Python integers: acc = S; per bit from the top acc <- 2 acc, T = acc + G, acc <- b1 ? T : acc,
+    T = acc + Q, acc <- b2 ? T : acc; then acc + (-[2^bits] S) = [u1] G + [u2] Q.  Both additions of a round are computed whatever the
+    bits are, as the circuit computes them.  -> the result, or None where a step meets an exceptional case (a vertical tangent, meeting
+    x-coordinates, the point at infinity)"""
+    p, _, _, G = curve
+    acc = start
+    for i in reversed(range(bits)):
+        if acc[1] % p == 0:
+            return None
+        acc = affine_add(p, acc, acc)
+        for point, u in ((G, u1), (Q, u2)):
+            if (acc[0] - point[0]) % p == 0:
+                return None
+            T = affine_add(p, acc, point)
+            acc = T if (u >> i) & 1 else acc
+    correction = affine_mul(p, 1 << bits, start)
+    correction = (correction[0], -correction[1] % p)
+    if (acc[0] - correction[0]) % p == 0:
+        return None
+    return affine_add(p, acc, correction)
+
+
+def ecdsa_cases(curve, count, seed=SPLITMIX_SEED, start=None, bits=None):
+    """`count` signatures (Q, h, r, s) for EcdsaVerify: key, nonce and hash from SplitMix64(seed), signing on Python integers.  A draw
+    with r = 0, s = 0 or on which the verifier's schedule meets an exceptional case is drawn again."""
+    p, _, order, G = curve
+    start = start or (TOY_START if curve == TOY_CURVE else SECP256K1_START)
+    bits = bits or order.bit_length()
+    g = SplitMix64(seed)
+    draw = lambda: sum(g.next_u64() << (64 * i) for i in range(-(-order.bit_length() // 64) + 1)) % (order - 1) + 1
+    out = []
+    while len(out) < count:
+        d, k, h = draw(), draw(), draw()
+        Q, R = affine_mul(p, d, G), affine_mul(p, k, G)
+        r = R[0] % order
+        s = pow(k, -1, order) * (h + r * d) % order
+        if r == 0 or s == 0:
+            continue
+        w = pow(s, -1, order)
+        got = ecdsa_schedule(curve, start, Q, h * w % order, r * w % order, bits)
+        if got is None:
+            continue
+        assert got[0] % order == r
+        out.append((Q, h, r, s))
+    return out
+
+
+class EcdsaVerify(_PartialModMulDiv):
+    """ECDSA verification on y^2 = x^3 + b, `curve` = (p, b, order, G), on l limbs of n bits (order < 2^(n l)).  Given: the limbs of
+    h, r, s, Qx, Qy.
+        u1 = h / s, u2 = r / s mod order      modular hints (opcode 3) with their exact checks; their limbs are decomposed, and the
+                                              bits are the selectors
+        acc = S, a literal point; G           columns pinned by ordinary rows
+        per bit from the top                  acc <- 2 acc (the slope a multiply-divide hint); T = acc + G; acc <- b1 ? T : acc by rows
+                                              (T_j - acc_j) b1 = new_j - acc_j; the same with Q and b2
+        R = acc + (-[2^bits] S)               the correction is computed here, on Python integers, and pinned like S
+        R.x = q order + rem                   a long-division hint with _reduce's rows for the order
+        rem_j - r_j = 0                       l check rows: the last rows of the system, and the only ones a wrong s fails
+    One ordinary row sums rem's limbs into the public input.  The generator asserts that no step meets an exceptional case."""
+
+    def __init__(self, curve, Q, h, r, s, n, limbs, start=None, decompose=True):
+        self.curve, self.Q, self.h, self.r_sig, self.s, self.n, self.limbs = tuple(curve), tuple(Q), int(h), int(r), int(s), n, limbs
+        self.start = tuple(start) if start else TOY_START if self.curve == TOY_CURVE else SECP256K1_START
+        self.modulus, self.decompose, self.operand_bits = self.curve[0], decompose, None
+        self.bits = n * limbs
+        assert self.curve[2] < 1 << self.bits
+
+    def _literal_point(self, cs, point):
+        one = ConstraintSystem.ONE
+        out = []
+        for coordinate in point:
+            limbs = []
+            for v in int_limbs(coordinate, self.n, self.limbs):
+                var = cs.new_witness_variable(v)
+                cs.enforce_constraint([(v, one)], [(1, one)], [(1, var)])
+                limbs.append(([(1, var)], v, (1 << self.n) - 1))
+            out.append(limbs)
+        return out
+
+    def _select(self, cs, bit, bit_v, T, acc):
+        """new_j = bit ? T_j : acc_j, by  (T_j - acc_j) bit = new_j - acc_j : one unknown, in C"""
+        out = []
+        for (lc_t, v_t, _), (lc_a, v_a, _) in zip(T, acc):
+            v = v_t if bit_v else v_a
+            var = cs.new_witness_variable(v)
+            cs.enforce_constraint(_merged(lc_t + [(-c, x) for c, x in lc_a]), [(1, bit)], _merged([(1, var)] + [(-c, x) for c, x in lc_a]))
+            out.append(([(1, var)], v, (1 << self.n) - 1))
+        return out
+
+    def generate_constraints(self, cs):
+        self._setup(cs)
+        one, n = ConstraintSystem.ONE, self.n
+        p, _, order, G = self.curve
+        h, r_sig, s = (self._given_limbs(cs, v) for v in (self.h, self.r_sig, self.s))
+        Qx, Qy = self._given_limbs(cs, self.Q[0]), self._given_limbs(cs, self.Q[1])
+        scalars = []
+        with self._over(order):
+            decompose, self.decompose = self.decompose, False
+            for numerator in (h, r_sig):
+                u = self._quotient(cs, numerator, [], s, [])          # raises where s has no inverse: s = 0
+                self._reduce(cs, self._minus(self._product(cs, u, s), numerator), zero=True)
+                scalars.append(u)
+            self.decompose = decompose
+        selectors = []
+        for u in scalars:
+            bits = []
+            for lc, v, _ in u:
+                limb_bits = _new_bits(cs, v, n)
+                cs.enforce_constraint(lc, [(1, one)], _weighted(limb_bits))
+                bits += [(b, (v >> i) & 1) for i, b in enumerate(limb_bits)]
+            selectors.append(bits)
+        u1, u2 = self._value(scalars[0]), self._value(scalars[1])
+        want = ecdsa_schedule(self.curve, self.start, self.Q, u1, u2, self.bits)
+        assert want is not None, "a step of the schedule meets an exceptional case"
+        acc = self._literal_point(cs, self.start)
+        Gl = self._literal_point(cs, G)
+        correction = affine_mul(p, 1 << self.bits, self.start)
+        for i in reversed(range(self.bits)):
+            acc = self._double(cs, *acc)
+            for point, bits in ((Gl, selectors[0]), ((Qx, Qy), selectors[1])):
+                T = self._add(cs, acc[0], acc[1], point[0], point[1])
+                bit, bit_v = bits[i]
+                acc = [self._select(cs, bit, bit_v, T[k], acc[k]) for k in range(2)]
+        Rx, Ry = self._add(cs, acc[0], acc[1], *self._literal_point(cs, (correction[0], -correction[1] % p)))
+        assert (self._value(Rx), self._value(Ry)) == want
+        with self._over(order):
+            rem = self._reduce(cs, Rx)
+        self._close(cs, [rem])
+        for (lc, _, _), (lc_r, _, _) in zip(rem, r_sig):
+            cs.enforce_constraint(lc + [(-c, x) for c, x in lc_r], [(1, one)], [])
+
+    def accepts(self):
+        """whether R.x mod order = r on Python integers (the last rows hold)"""
+        order = self.curve[2]
+        w = pow(self.s, -1, order)
+        R = ecdsa_schedule(self.curve, self.start, self.Q, self.h * w % order, self.r_sig * w % order, self.bits)
+        return R is not None and R[0] % order == self.r_sig
+
+
 def _invertible(rows, r):
     """whether the square matrix `rows` is invertible mod r: elimination on Python integers"""
     rows = [list(row) for row in rows]

@@ -193,12 +193,13 @@ struct GlueWs {
 // call with PM_ASSIGNMENT_SOLVE.  xw: the completed x || w rows of a check call (pm_prove_tap(10)); the prover completes its groups in
 // its own workspace (ProveWs::xw) and keeps only tap9.
 struct SolveWs {
-    DevBuf xw, pattern, mismatch, stuck, steps, bit_cols, pairs, divs, blocks, block_idx, block_inv, hints, hint_idx, mods;
+    DevBuf xw, pattern, mismatch, stuck, steps, bit_cols, pairs, divs, blocks, block_idx, block_inv, hints, hint_idx, mods, muls;
     pmsolve::Plan plan;
     // per plan.pairs / plan.divs / plan.blocks one record in `pairs` / `divs` / `blocks` (the blocks' rows and columns in `block_idx`,
     // their inverses in `block_inv`); plan.hints divides into the two record arrays that solve_plan counts:
     size_t n_hints = 0;                  // long divisions of the plan, wide ones included: records in `hints`, columns and literal divisors in `hint_idx`
     size_t n_mods = 0;                   // modular divisions of the plan: records in `mods`, columns and literal moduli in `hint_idx` as well
+    size_t n_muls = 0;                   // modular multiply-divides of the plan: records in `muls`, columns and literal moduli in `hint_idx` as well
     uint64_t plan_key = 0;               // pm_pk::serial of the plan's key; 0 = no plan
     uint64_t plan_hint_gen = 0;          // pm_pk::hint_gen of the plan's key when the plan was made
     std::vector<uint8_t> plan_pattern;   // one byte per column
@@ -206,7 +207,7 @@ struct SolveWs {
     size_t tap10_rows = 0;               // pm_prove_tap(10): rows of xw that hold a check call's completed assignments; 0 = none
     size_t tap10_cols = 0;
     void release() {
-        for (DevBuf *b : {&xw, &pattern, &mismatch, &stuck, &steps, &bit_cols, &pairs, &divs, &blocks, &block_idx, &block_inv, &hints, &hint_idx, &mods}) b->release();
+        for (DevBuf *b : {&xw, &pattern, &mismatch, &stuck, &steps, &bit_cols, &pairs, &divs, &blocks, &block_idx, &block_inv, &hints, &hint_idx, &mods, &muls}) b->release();
     }
 };
 

@@ -2,7 +2,7 @@
 // (include/polymath_hip.h), so that a caller supplies only the values it chooses and the library computes the rest
 // before it checks or proves.  The PLAN -- which row determines which column, in which order -- is host work, done once per (key,
 // pattern) by host/solve_plan.hpp; what ONE step does to ONE assignment (solve_step, solve_bits, solve_iszero, solve_divrem,
-// solve_indicator, solve_sqrt, solve_block, solve_longdiv, solve_moddiv, solve_longdiv_wide and its longdiv_wide_words, the dispatch
+// solve_indicator, solve_sqrt, solve_block, solve_longdiv, solve_moddiv, solve_modmuldiv, solve_longdiv_wide and its longdiv_wide_words, the dispatch
 // solve_any, the inverses' solve_inverse and solve_block_invert, and the records a plan becomes: solve_records) is solve_steps.cuh,
 // text that the CPU self-tests run as well; this file is the kernels that call it and the host driver, assignment = grid y (or the
 // lane, in the chain kernel).  Before the plan's launches:
@@ -53,6 +53,12 @@
 //                     (solve_steps.cuh: longdiv_wide_words states the recurrence); lane i multiplies divisor word i, carries and
 //                     borrows by ballot.  Scatter: lane i cuts limb i and stores it.  Every trip count is wave-uniform; stuck at the
 //                     word nr + h
+//   LAUNCH_MODMULDIV  k_solve_modmuldiv: the declared modular multiply-divides of a level (opcode 7: the slope 3 X^2 / (2 Y) of a
+//                     tangent), cD (D+ - D-) Z = cN (A B + N+ - N-) mod P, whatever its width: one lane per (hint, assignment).  Nine
+//                     phases in one rolled loop share one longdiv and one 16 x 16-word schoolbook product: the two factor lists, their
+//                     product (reduced in the launch's 2 L rounds), the addend and denominator lists folded in by masked add and
+//                     subtract modulo P, then the two one-word literals, which scale residues below P; the same Euclid ends in Z
+//                     (solve_steps.cuh: solve_modmuldiv).  No register is indexed at run time; stuck at the word nr + h
 // The chain, level and bits kernels exist twice: DIV = false for ranges of kind-C steps only, DIV = true for ranges with kind-A / kind-B steps,
 // or is-zero pairs, which call inverse<P> (a Fermat chain) -- the plan sorts a level by kind, so kind-C ranges do not carry its
 // registers, and the is-zero step and the division step (a dividing one by the plan's count, for 1 / cq) exist in the DIV = true
@@ -211,6 +217,17 @@ __global__ __launch_bounds__(64) void k_solve_moddiv(const SolveStepDev<P> *__re
     const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (t >= hi) return;
     solve_moddiv<P>(steps[t], mods[steps[t].bits], hint_idx, rounds, inv_rounds, xw + b * ncols, StuckWord{stuck + b});
+}
+
+// One lane per (hint, assignment), as k_solve_moddiv.  The modulus and the two residues (16 words each) live throughout; a phase's
+// 32-word value, its 17-word remainder and trial difference and the product's two factors are dead when the next phase begins.
+template <class P>
+__global__ __launch_bounds__(64) void k_solve_modmuldiv(const SolveStepDev<P> *__restrict__ steps, const SolveMulDev *__restrict__ muls,
+                                                        const uint32_t *__restrict__ hint_idx, uint32_t rounds, uint32_t inv_rounds, uint32_t lo, uint32_t hi,
+                                                        Fp<P> *xw, uint64_t ncols, unsigned long long *stuck) {
+    const uint64_t t = (uint64_t)lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (t >= hi) return;
+    solve_modmuldiv<P>(steps[t], muls[steps[t].bits], hint_idx, rounds, inv_rounds, xw + b * ncols, StuckWord{stuck + b});
 }
 
 // ---- k_solve_longdiv_wide: one wave, one division.  The wave's slice of LDS (5888 B; four waves to a workgroup: 23 KB):
@@ -530,7 +547,7 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
     for (const pmsolve::Launch &l : sv.plan.launches)
         for (uint32_t t = l.lo; t < l.hi; ++t) {
             const pmsolve::Step &s = sv.plan.steps[t];
-            const pmsolve::KindInfo info = s.kind < pmsolve::NUM_WIDE_KINDS ? pmsolve::KIND_INFO[s.kind] : pmsolve::KindInfo{0xff, 0, 0};
+            const pmsolve::KindInfo info = s.kind < pmsolve::NUM_MULDIV_KINDS ? pmsolve::KIND_INFO[s.kind] : pmsolve::KindInfo{0xff, 0, 0};
             const char *why = l.kind == pmsolve::LAUNCH_CHAIN ? (info.chained ? nullptr : "into a chain, where no lane can walk it")
                               : info.launch != l.kind         ? "into a launch of another kind"
                                                               : nullptr;
@@ -543,7 +560,7 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
             }
         }
     const size_t n_steps = sv.plan.steps.size();
-    sv.n_hints = sv.n_mods = 0;
+    sv.n_hints = sv.n_mods = sv.n_muls = 0;
     if (n_steps) {
         SolveRecords<P> rec = solve_records<P>(sv.plan);
         // the linear blocks' matrices are constants of the key: each distinct one is inverted here, once per plan, from the words the
@@ -565,11 +582,13 @@ int solve_plan(pm_ctx *ctx, const pm_pk *pk) {
         }
         sv.n_hints = rec.hints.size();
         sv.n_mods = rec.mods.size();
+        sv.n_muls = rec.muls.size();
         PM_HIP(ctx, sv.blocks.upload(rec.blocks, st));
         PM_HIP(ctx, sv.block_idx.upload(rec.block_idx, st));
         PM_HIP(ctx, sv.block_inv.upload(rec.block_inv, st));
         PM_HIP(ctx, sv.hints.upload(rec.hints, st));
         PM_HIP(ctx, sv.mods.upload(rec.mods, st));
+        PM_HIP(ctx, sv.muls.upload(rec.muls, st));
         PM_HIP(ctx, sv.hint_idx.upload(rec.hint_idx, st));
         PM_HIP(ctx, sv.pairs.upload(rec.pairs, st));
         PM_HIP(ctx, sv.divs.upload(rec.divs, st));
@@ -623,6 +642,11 @@ int solve_group(pm_ctx *ctx, const pm_pk *pk, Fp<typename C::FrP> *d_xw, size_t 
             case pmsolve::LAUNCH_MODDIV:
                 if (!sv.n_mods || l.rounds < 256 || l.rounds > 1024 || l.inv_rounds < 512 || l.inv_rounds > 1024) return PM_ERR_STATE;
                 hipLaunchKernelGGL((k_solve_moddiv<P>), hint_lanes, dim3(64), 0, st, steps, sv.mods.as<SolveModDev>(), hint_idx, l.rounds, l.inv_rounds, l.lo, l.hi, d_xw,
+                                   ncols, stuck);
+                break;
+            case pmsolve::LAUNCH_MODMULDIV:
+                if (!sv.n_muls || l.rounds < 256 || l.rounds > 1024 || l.inv_rounds < 512 || l.inv_rounds > 1024) return PM_ERR_STATE;
+                hipLaunchKernelGGL((k_solve_modmuldiv<P>), hint_lanes, dim3(64), 0, st, steps, sv.muls.as<SolveMulDev>(), hint_idx, l.rounds, l.inv_rounds, l.lo, l.hi, d_xw,
                                    ncols, stuck);
                 break;
             case pmsolve::LAUNCH_LONGDIV_WIDE:

@@ -73,6 +73,13 @@ struct SolveModDev {
     uint32_t n, kz, k[4], kP, literal, off, pad;
 };
 
+// what a modular multiply-divide step needs beside its SolveStepDev (whose bits = its SolveMulDev): in the hint pool from `off` the kz
+// output columns, the kA, kB, kNp, kNm, kDp and kDm operand columns, then the kP modulus columns or the 17 words of a literal modulus
+// as above; cN and cD, the two one-word literals
+struct SolveMulDev {
+    uint32_t n, kz, k[6], kP, literal, off, cN, cD, pad;
+};
+
 // The record arrays of a plan, as the kernels read them; the inverses are left zero (solve_inverse fills them), the pool of block
 // inverses empty (solve_block_inverses fills it).
 template <class P>
@@ -87,6 +94,7 @@ struct SolveRecords {
     std::vector<SolveHintDev> hints;
     std::vector<uint32_t> hint_idx;       // the hint pool
     std::vector<SolveModDev> mods;        // the modular divisions; their columns and literal moduli are in the hint pool too
+    std::vector<SolveMulDev> muls;        // the modular multiply-divides; their columns and literal moduli are in the hint pool as well
 };
 
 constexpr int LONGDIV_WD = 32, LONGDIV_WE = 16;   // the long division's registers in 32-bit words: a 1024-bit dividend, a 512-bit divisor
@@ -254,13 +262,16 @@ inline SolveRecords<P> solve_records(const pmsolve::Plan &plan) {
             rec.block_idx.insert(rec.block_idx.end(), blk.cols.begin(), blk.cols.end());
             rec.blocks.push_back(SolveBlockDev{k, rows_off, rows_off + k, 0, rec.mat_off[blk.mat]});
         }
-        if (s.kind == pmsolve::KIND_LONGDIV || s.kind == pmsolve::KIND_MODDIV || s.kind == pmsolve::KIND_LONGDIV_WIDE) {
+        if (s.kind == pmsolve::KIND_LONGDIV || s.kind == pmsolve::KIND_MODDIV || s.kind == pmsolve::KIND_LONGDIV_WIDE || s.kind == pmsolve::KIND_MODMULDIV) {
             const pmsolve::Hint &h = plan.hints[s.cols_off];
             const bool literal = (h.flags & pmsolve::HINT_DIVISOR_LITERAL) != 0;   // HINT_MODULUS_LITERAL is the same bit
             const uint32_t kE = (uint32_t)(literal ? h.lit.size() / 4 : h.E.size()), off = (uint32_t)rec.hint_idx.size();
             if (s.kind == pmsolve::KIND_MODDIV) {
                 d.bits = (uint32_t)rec.mods.size();
                 rec.mods.push_back(SolveModDev{h.n, (uint32_t)h.q.size(), {h.k[0], h.k[1], h.k[2], h.k[3]}, kE, literal ? 1u : 0u, off, 0});
+            } else if (s.kind == pmsolve::KIND_MODMULDIV) {
+                d.bits = (uint32_t)rec.muls.size();
+                rec.muls.push_back(SolveMulDev{h.n, (uint32_t)h.q.size(), {h.km[0], h.km[1], h.km[2], h.km[3], h.km[4], h.km[5]}, kE, literal ? 1u : 0u, off, h.c[0], h.c[1], 0});
             } else {
                 d.bits = (uint32_t)rec.hints.size();
                 rec.hints.push_back(SolveHintDev{h.n, (uint32_t)h.q.size(), (uint32_t)h.rem.size(), (uint32_t)h.D.size(), kE, literal ? 1u : 0u, off, 0});
@@ -299,7 +310,7 @@ PM_HD uint32_t matrix_kind(uint32_t kind) { return kind >= pmsolve::KIND_BITS_C 
 template <class P>
 PM_HD void solve_inverse(const pmsolve::Csr &A, const pmsolve::Csr &B, const pmsolve::Csr &Cm, SolveStepDev<P> *steps, uint64_t count, SolvePairDev<P> *pairs,
                          const SolveDivDev *divs, uint64_t t) {
-    if (t < count && (steps[t].kind == pmsolve::KIND_INDICATOR || steps[t].kind == pmsolve::KIND_BLOCK || steps[t].kind == pmsolve::KIND_LONGDIV || steps[t].kind == pmsolve::KIND_MODDIV || steps[t].kind == pmsolve::KIND_LONGDIV_WIDE)) return;   // no inverse of a coefficient: the record stays as the host wrote it
+    if (t < count && (steps[t].kind == pmsolve::KIND_INDICATOR || steps[t].kind == pmsolve::KIND_BLOCK || steps[t].kind == pmsolve::KIND_LONGDIV || steps[t].kind == pmsolve::KIND_MODDIV || steps[t].kind == pmsolve::KIND_LONGDIV_WIDE || steps[t].kind == pmsolve::KIND_MODMULDIV)) return;   // no inverse of a coefficient: the record stays as the host wrote it
     if (t < count && steps[t].kind == pmsolve::KIND_SQRT) {
         const Fp<P> ka = *(const Fp<P> *)(A.val + 4 * steps[t].pos), kb = *(const Fp<P> *)(B.val + 4 * (B.rowptr[steps[t].row] + steps[t].bits));
         const Fp<P> coef = mul<P>(ka, kb);
@@ -755,6 +766,145 @@ PM_HD void solve_moddiv(const SolveStepDev<P> &s, const SolveModDev &h, const ui
     }
     modinv_odd<LONGDIV_WE>(Dr, V, Nr, Z, M, inv_rounds);
     uint32_t rest = V[0] ^ 1u;       // gcd(D mod P, P) - 1
+#pragma unroll
+    for (int w = 1; w < LONGDIV_WE; ++w) rest |= V[w];
+    bad |= rest | bits_from<LONGDIV_WE>(Z, h.n * h.kz);
+    if (bad) stuck(s);
+    const uint32_t mask = bad ? 0u : ~0u;
+    for (uint32_t i = 0; i < h.kz; ++i) {
+        Fp<P> limb = limb_at<P, LONGDIV_WE>(Z, h.n * i, h.n);
+#pragma unroll
+        for (int w = 0; w < P::N; ++w) limb.l[w] &= mask;
+        z[z_cols[i]] = to_mont<P>(limb);
+    }
+}
+
+// acc <<= bits on W words, bits < 32 W: whole words by a rolled loop of `bits / 32` trips (the same in every lane of a launch), the rest
+// by one funnel shift; no register is indexed by `bits`
+template <int W>
+PM_HD void shift_up(uint32_t (&acc)[W], uint32_t bits) {
+#pragma unroll 1
+    for (uint32_t i = 0; i < (bits >> 5); ++i) {
+#pragma unroll
+        for (int w = W - 1; w > 0; --w) acc[w] = acc[w - 1];
+        acc[0] = 0;
+    }
+    const uint32_t down = 32u - (bits & 31u);    // in 1..32: a 64-bit shift
+#pragma unroll
+    for (int w = W - 1; w >= 0; --w) acc[w] = (uint32_t)(((uint64_t)acc[w] << 32 | (w > 0 ? acc[w > 0 ? w - 1 : 0] : 0u)) >> down);
+}
+
+// one declared modular multiply-divide on one assignment: Z with cD (D+ - D-) Z = cN (A B + N+ - N-) (mod P).  The modulus is
+// accumulated as solve_moddiv does.  Then NINE PHASES in one rolled loop, so that the kernel holds one copy of longdiv and one of the
+// schoolbook product; each forms a 1024-bit value in the register S where longdiv wants it (shifted left by 1024 - its trip count),
+// reduces it modulo P and folds the remainder into one of two residues, X (the numerator) and Y (the second factor, then the
+// denominator):
+//   0, 1   the lists A and B: accumulated like a dividend (`rounds`: the launch's bound, so what add_shifted loses is exactly a sum
+//          >= 2^1024);  X = A mod P,  Y = B mod P
+//   2      S = X Y, a 16 x 16-word schoolbook product, below P^2 < 2^(2 L): `inv_rounds` = 2 L rounds;  X = A B mod P
+//   3, 4   the lists N+ and N-:  X = X + N+ mod P,  X = X - N- mod P
+//   5, 6   the lists D+ and D-:  Y = D+ mod P,  Y = Y - D- mod P     (no denominator lists: Y = 1 before phase 8)
+//   7, 8   S = cN X and S = cD Y, the same product with the literal as its second factor, below 2^32 P < 2^(L + 32): L + 32 rounds
+// An empty list is passed over, which is a branch on the record, not on an operand; which phase it is, is the loop counter.  The
+// literals scale AFTER the reductions, so nothing is stuck that the five conditions below do not name.  modinv_odd with u = Y, x1 = X
+// and `inv_rounds` rounds leaves Z in x2 where v = 1, as in solve_moddiv.  Stuck at the hint's word (nr + h: the step's row), with zero
+// in every output:
+//   P even or P < 3;  P >= 2^512;  a list sum >= 2^1024;  gcd(cD D mod P, P) != 1 (D = 0 mod P included);  Z >= 2^(n kz)
+// or-ed into one word, the outputs stored under its mask.  Word loops unrolled, round loops rolled; no branch and no register index
+// depends on an operand.
+template <class P, class Sink>
+PM_HD void solve_modmuldiv(const SolveStepDev<P> &s, const SolveMulDev &h, const uint32_t *__restrict__ hint_idx, uint32_t rounds, uint32_t inv_rounds, Fp<P> *z,
+                           const Sink &stuck) {
+    static_assert(P::N == 8, "four 64-bit words");
+    const uint32_t *z_cols = hint_idx + h.off, *cols = z_cols + h.kz, *p_words = cols + h.k[0] + h.k[1] + h.k[2] + h.k[3] + h.k[4] + h.k[5];
+    uint32_t M[LONGDIV_WE], X[LONGDIV_WE], Y[LONGDIV_WE], bad = 0;
+#pragma unroll
+    for (int w = 0; w < LONGDIV_WE; ++w) M[w] = X[w] = Y[w] = 0;
+    if (h.literal) {
+#pragma unroll
+        for (int w = 0; w < LONGDIV_WE; ++w) M[w] = p_words[w];
+        bad |= p_words[LONGDIV_WE];
+    } else {
+        for (uint32_t j = 0; j < h.kP; ++j) bad |= add_shifted<LONGDIV_WE>(M, from_mont<P>(z[p_words[j]]).l, h.n * j);
+    }
+    uint32_t high = 0;
+#pragma unroll
+    for (int w = 1; w < LONGDIV_WE; ++w) high |= M[w];
+    bad |= (uint32_t)((M[0] & 1u) == 0) | (uint32_t)(high == 0 && M[0] == 1u);   // even (0 and 2 included), or 1
+    const uint32_t scale_rounds = (inv_rounds >> 1) + 32u;
+#pragma unroll 1
+    for (uint32_t phase = 0; phase < 9; ++phase) {
+        const bool product = phase == 2 || phase >= 7;
+        const uint32_t list = phase < 2 ? phase : phase - 1;      // of a list phase
+        if (!product && h.k[list < 6 ? list : 0] == 0) continue;
+        const uint32_t into_y = phase == 1 || phase == 5 || phase == 6 || phase == 8 ? ~0u : 0u;      // the residue the phase folds into
+        uint32_t S[LONGDIV_WD], R[LONGDIV_WE + 1], T[LONGDIV_WE], trips = rounds;
+#pragma unroll
+        for (int w = 0; w < LONGDIV_WD; ++w) S[w] = 0;
+        if (product) {
+            if (phase == 8 && (h.k[4] | h.k[5]) == 0) {      // no denominator lists: D = 1 (P = 1 is stuck)
+#pragma unroll
+                for (int w = 0; w < LONGDIV_WE; ++w) Y[w] = w == 0 ? 1u : 0u;
+            }
+            // the factors: X Y, X cN or Y cD
+            const uint32_t literal = phase == 2 ? 0u : ~0u, c = phase == 7 ? h.cN : h.cD;
+            uint32_t F[LONGDIV_WE], G[LONGDIV_WE];
+#pragma unroll
+            for (int w = 0; w < LONGDIV_WE; ++w) {
+                F[w] = (Y[w] & into_y) | (X[w] & ~into_y);
+                G[w] = (Y[w] & ~literal) | ((w == 0 ? c : 0u) & literal);
+            }
+#pragma unroll
+            for (int i = 0; i < LONGDIV_WE; ++i) {
+                uint32_t carry = 0;
+#pragma unroll
+                for (int j = 0; j < LONGDIV_WE; ++j) {
+                    const uint64_t t = (uint64_t)F[j] * G[i] + S[i + j] + carry;
+                    S[i + j] = (uint32_t)t;
+                    carry = (uint32_t)(t >> 32);
+                }
+                S[i + LONGDIV_WE] = carry;
+            }
+            trips = phase == 2 ? inv_rounds : scale_rounds;
+            shift_up<LONGDIV_WD>(S, 32u * LONGDIV_WD - trips);
+        } else {
+            const uint32_t k = h.k[list < 6 ? list : 0], base = 32u * LONGDIV_WD - rounds;
+            for (uint32_t j = 0; j < k; ++j) bad |= add_shifted<LONGDIV_WD>(S, from_mont<P>(z[cols[j]]).l, base + h.n * j);
+            cols += k;
+        }
+        longdiv<LONGDIV_WD, LONGDIV_WE>(S, M, R, trips);
+        // T = what the remainder R is folded into: zero (the phase sets its residue), or the residue (phases 3, 4 and 6 add to it or
+        // subtract from it).  R < P (R[16] = 0) wherever P != 0
+        const uint32_t keep = phase == 3 || phase == 4 || phase == 6 ? ~0u : 0u, subtract = phase == 4 || phase == 6 ? ~0u : 0u;
+        uint32_t Rw[LONGDIV_WE], U[LONGDIV_WE];
+#pragma unroll
+        for (int w = 0; w < LONGDIV_WE; ++w) {
+            T[w] = ((Y[w] & into_y) | (X[w] & ~into_y)) & keep;
+            Rw[w] = R[w];
+        }
+        // T + R mod P: the sum, then P taken off where the sum carried or is not below P;  T - R mod P: the difference, then P put back
+        const uint32_t carry = add_masked<LONGDIV_WE>(T, Rw, ~subtract);
+#pragma unroll
+        for (int w = 0; w < LONGDIV_WE; ++w) U[w] = T[w];
+        const uint32_t below = sub_masked<LONGDIV_WE>(U, M, ~0u);      // 1: T < P
+        const uint32_t reduce = ~subtract & (0u - (carry | (below ^ 1u)));
+#pragma unroll
+        for (int w = 0; w < LONGDIV_WE; ++w) T[w] = (U[w] & reduce) | (T[w] & ~reduce);
+        add_masked<LONGDIV_WE>(T, M, 0u - sub_masked<LONGDIV_WE>(T, Rw, subtract));
+#pragma unroll
+        for (int w = 0; w < LONGDIV_WE; ++w) {
+            X[w] = (T[w] & ~into_y) | (X[w] & into_y);
+            Y[w] = (T[w] & into_y) | (Y[w] & ~into_y);
+        }
+    }
+    uint32_t V[LONGDIV_WE], Z[LONGDIV_WE];
+#pragma unroll
+    for (int w = 0; w < LONGDIV_WE; ++w) {
+        V[w] = M[w];
+        Z[w] = 0;
+    }
+    modinv_odd<LONGDIV_WE>(Y, V, X, Z, M, inv_rounds);
+    uint32_t rest = V[0] ^ 1u;       // gcd(cD D mod P, P) - 1
 #pragma unroll
     for (int w = 1; w < LONGDIV_WE; ++w) rest |= V[w];
     bad |= rest | bits_from<LONGDIV_WE>(Z, h.n * h.kz);

@@ -200,6 +200,29 @@
 //                 Opcode 1 is not widened: its limits, its kernel and its plans are what they were.
 //                 Not handled: modular division at these widths (HINT_MODDIV keeps 1024 / 512 bits), even moduli, linear blocks
 //                 beyond 64 unknowns (RSA-4096 at 64-bit limbs), hints on sharded keys, per-assignment declarations, gcd, sorting.
+//                 Of the modular record's list, the slope of a doubling now has a record of its own:
+//   multiply-divide hint  a MODULAR MULTIPLY-DIVIDE that the key declares in the same stream (opcode HINT_MODMULDIV = 7; 2, 4 and 6 stay
+//                 refused as unknown, and so is 8): kz output columns, kA + kB factor columns, kNp + kNm addend columns, kDp + kDm
+//                 denominator columns, kP modulus columns (or kP literal limbs), limbs of n bits, and two one-word literals cN and cD
+//                 in 1 .. 2^32 - 1.  The slope 3 X^2 / (2 Y) of a tangent (circom-ecdsa's Secp256k1Double: A = B = X, D+ = Y, cN = 3,
+//                 cD = 2), and with kDp = kDm = 0 (D = 1) a modular multiply-add, the remainder of A B + C without its quotient.
+//                 ACTIVE / INERT / refused, HINT-OWNED outputs, waiting on inputs and the never-ready refusal are the long-division
+//                 rules, applied to the kz outputs; all four opcodes share the index h and the set of output columns.  It acts as
+//                 ONE step of kind KIND_MODMULDIV at 1 + max level of its inputs, Step::row = nr + h, Step::col its first output,
+//                 Step::cols_off its entry of Plan::hints.  With each list the sum of int(z_{c_j}) 2^(n j) (limbs need not be
+//                 normalised; A and B may name the same columns) the step stores the kz n-bit limbs of the unique Z in [0, P) with
+//                 cD (D+ - D-) Z = cN (A B + N+ - N-)  (mod P).  Stuck, with zero in every output: P even or P < 3, P >= 2^512, any
+//                 of the six list sums >= 2^1024, gcd(cD D mod P, P) != 1 (D = 0 mod P included, and a cD that shares a factor with a
+//                 composite P), Z >= 2^(n kz) -- and nothing else: cN and cD scale AFTER the reductions, when the value is below P.
+//                 The multiply-divide hints of a level sort last, after its wide ones, and are a launch of their own
+//                 (LAUNCH_MODMULDIV, not dividing, never chained) with two trip counts: Launch::rounds, the largest
+//                 min(1024, n (k - 1) + 256) over the six lists of its hints, and Launch::inv_rounds = 2 L, L the largest
+//                 min(512, n (kP - 1) + 256) -- the inversion's trip count and, since the product of two residues is below 2^(2 L),
+//                 the trip count of the product's reduction as well.  Opcode 3 is not touched: its record, its kernel and its plans
+//                 are what they were.
+//                 Not handled: curves with a != 0 need no more than N+ = a (the record allows it); complete addition formulas,
+//                 windowed or GLV scalar multiplication, operands beyond 1024 bits, even moduli, hints on sharded keys,
+//                 per-assignment declarations.
 // With the heap empty the scheduler has failed if an opener is unclosed, a boolean-pending column unsolved or a marked column
 // undetermined; the result is then build_plan's error (code, row, column, message) with "; in any row order: ..." appended.  A plan
 // it finds has Plan::reordered = true, level(step) as below, the steps sorted by (level, kind, row) and the level_ptr and launches of
@@ -213,7 +236,7 @@
 //
 // level(step) = 1 + max level of the columns the row reads (given columns: level 0); a decomposition gives all its columns that
 // level.  The steps come out sorted by level, inside a level by kind (C first: the kinds that divide share a launch; then the
-// decompositions in the same order, then the is-zero pairs, then the division rows, then the indicator rows, then the square-root rows, then the linear blocks, then the declared hints), stable by row -- one counting sort.  O(nnz + columns), plus k log k per decomposition.
+// decompositions in the same order, then the is-zero pairs, then the division rows, then the indicator rows, then the square-root rows, then the linear blocks, then the declared hints, the multiply-divide ones last), stable by row -- one counting sort.  O(nnz + columns), plus k log k per decomposition.
 #pragma once
 #include <stdint.h>
 
@@ -235,20 +258,22 @@ namespace pmsolve {
 // KIND_LONGDIV: a declared long-division hint, kq + kr columns in one step; integer arithmetic only, so it does not count as dividing
 // KIND_MODDIV: a declared modular-division hint, kz columns in one step; integer arithmetic only as well
 // KIND_LONGDIV_WIDE: a declared wide long division (opcode 5), kq + kr columns in one step of one wave; integer arithmetic only
-enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6, KIND_DIVREM = 7, KIND_INDICATOR = 8, KIND_SQRT = 9, KIND_BLOCK = 10, KIND_LONGDIV = 11, KIND_MODDIV = 12, KIND_LONGDIV_WIDE = 13 };
+// KIND_MODMULDIV: a declared modular multiply-divide (opcode 7), kz columns in one step; integer arithmetic only
+enum Kind : uint32_t { KIND_C = 0, KIND_A = 1, KIND_B = 2, KIND_BITS_C = 3, KIND_BITS_A = 4, KIND_BITS_B = 5, KIND_ISZERO = 6, KIND_DIVREM = 7, KIND_INDICATOR = 8, KIND_SQRT = 9, KIND_BLOCK = 10, KIND_LONGDIV = 11, KIND_MODDIV = 12, KIND_LONGDIV_WIDE = 13, KIND_MODMULDIV = 14 };
 constexpr uint32_t NUM_KINDS = 7;        // the kinds that need no second marker: what it always counted
 constexpr uint32_t NUM_STEP_KINDS = 8;   // KIND_C .. KIND_DIVREM, the kinds whose value comes from field or integer arithmetic on the row: what it counted when kind 7 came
 constexpr uint32_t NUM_SORT_KINDS = 10 + 1;  // all 11 of them: the ten kinds that one lane executes, KIND_INDICATOR and KIND_SQRT included, and KIND_BLOCK: the kinds that rows make
 constexpr uint32_t NUM_PLAN_KINDS = 12;  // with KIND_LONGDIV, which no row makes: the key width of finish_plan's counting sort (NUM_SORT_KINDS counts the kinds that rows make, as it did)
 constexpr uint32_t NUM_HINT_KINDS = 13;  // with KIND_MODDIV: the key width of finish_plan's counting sort now (NUM_PLAN_KINDS stays what it counted when kind 11 came)
 constexpr uint32_t NUM_WIDE_KINDS = 14;  // with KIND_LONGDIV_WIDE: the key width of finish_plan's counting sort now (NUM_HINT_KINDS stays what it counted when kind 12 came)
+constexpr uint32_t NUM_MULDIV_KINDS = 15;  // with KIND_MODMULDIV: the key width of finish_plan's counting sort now (NUM_WIDE_KINDS stays what it counted when kind 13 came)
 constexpr uint32_t MAX_BLOCK = 64;       // the largest linear block: one wave, a lane per row and per column
 
 // What a launch does with its steps [lo, hi): LAUNCH_CHAIN, one lane per assignment walks them in order, through consecutive narrow
 // levels; every other kind, one lane (LAUNCH_BLOCK and LAUNCH_LONGDIV_WIDE: one wave) per (step, assignment), and every step has the
 // step kinds that KIND_INFO maps to that launch kind, all of one level.  LAUNCH_LEVEL: the ordinary steps.
 enum LaunchKind : uint8_t { LAUNCH_CHAIN, LAUNCH_LEVEL, LAUNCH_BITS, LAUNCH_ISZERO, LAUNCH_DIVREM, LAUNCH_INDICATOR, LAUNCH_SQRT,
-                            LAUNCH_BLOCK, LAUNCH_LONGDIV, LAUNCH_MODDIV, LAUNCH_LONGDIV_WIDE };
+                            LAUNCH_BLOCK, LAUNCH_LONGDIV, LAUNCH_MODDIV, LAUNCH_LONGDIV_WIDE, LAUNCH_MODMULDIV };
 
 // What "a kind of step" means to the schedule, per step kind: the launch kind it gets in a wide level; whether it counts as dividing
 // (KIND_DIVREM for 1 / cq, KIND_SQRT for 1 / (ka kb); KIND_INDICATOR, the blocks and the declared hints do not); whether one lane can
@@ -257,7 +282,7 @@ enum LaunchKind : uint8_t { LAUNCH_CHAIN, LAUNCH_LEVEL, LAUNCH_BITS, LAUNCH_ISZE
 struct KindInfo {
     uint8_t launch, divides, chained;
 };
-constexpr KindInfo KIND_INFO[NUM_WIDE_KINDS] = {
+constexpr KindInfo KIND_INFO[NUM_MULDIV_KINDS] = {
     {LAUNCH_LEVEL, 0, 1},      // KIND_C
     {LAUNCH_LEVEL, 1, 1},      // KIND_A
     {LAUNCH_LEVEL, 1, 1},      // KIND_B
@@ -272,6 +297,7 @@ constexpr KindInfo KIND_INFO[NUM_WIDE_KINDS] = {
     {LAUNCH_LONGDIV, 0, 0},    // KIND_LONGDIV
     {LAUNCH_MODDIV, 0, 0},     // KIND_MODDIV
     {LAUNCH_LONGDIV_WIDE, 0, 0},  // KIND_LONGDIV_WIDE
+    {LAUNCH_MODMULDIV, 0, 0},  // KIND_MODMULDIV
 };
 
 constexpr uint8_t PATTERN_UNKNOWN = 1, PATTERN_QUOTIENT = 2, PATTERN_INDICATOR = 3, PATTERN_SQRT = 4;   // the pattern bytes (0: given)
@@ -329,6 +355,11 @@ constexpr uint32_t MODDIV_MAX_KZ = 16, MODDIV_MAX_KP = 16, MODDIV_MAX_K = 32, MO
 // the wide long division's opcode (4 is refused as unknown, like 2) and the limits of its record; its flag is HINT_DIVISOR_LITERAL
 constexpr uint64_t HINT_LONGDIV_WIDE = 5;
 constexpr uint32_t WIDE_MAX_KD = 128, WIDE_MAX_KE = 64, WIDE_MAX_KQ = 128, WIDE_MAX_KR = 64, WIDE_D_BITS = 8192, WIDE_E_BITS = 4096;
+// the modular multiply-divide's opcode (6 is refused as unknown, like 2 and 4) and the limits of its record: kz, kP and the addend and
+// denominator lists as opcode 3's, at least one and at most 32 limbs in each factor; its flag is HINT_MODULUS_LITERAL, its operand and
+// modulus bounds MODDIV_OPERAND_BITS and MODDIV_MODULUS_BITS; cN and cD are literals of one 32-bit word, not zero
+constexpr uint64_t HINT_MODMULDIV = 7, MODMULDIV_MAX_C = 0xffffffffull;
+constexpr uint32_t MODMULDIV_LISTS = 6;
 constexpr uint32_t HINT_MAX_N = 128, HINT_MAX_KD = 32, HINT_MAX_KE = 16, HINT_MAX_KQ = 32, HINT_MAX_KR = 16, HINT_D_BITS = 1024, HINT_E_BITS = 512;
 struct Hint {
     uint32_t n = 0, flags = 0;
@@ -341,18 +372,26 @@ struct Hint {
     // A WIDE long division (op == HINT_LONGDIV_WIDE) uses the lists exactly as a long division does
     uint32_t op = (uint32_t)HINT_LONGDIV;
     uint32_t k[4] = {0, 0, 0, 0};
+    // A MODULAR MULTIPLY-DIVIDE (op == HINT_MODMULDIV) uses the lists in the same way: q = the kz output columns, rem empty, D = the six
+    // operand lists one after the other -- kA, kB factor columns, kNp, kNm addend columns, kDp, kDm denominator columns --, E = the kP
+    // modulus columns (lit: its literal limbs); km[6] = kA, kB, kNp, kNm, kDp, kDm, the parts of D (k[4] stays zero: opcode 3 alone
+    // reads it); c[2] = cN, cD
+    uint32_t km[MODMULDIV_LISTS] = {0, 0, 0, 0, 0, 0};
+    uint32_t c[2] = {1, 1};
 };
 
 struct Launch {
     uint32_t lo, hi;  // steps [lo, hi) of the sorted list
     uint8_t kind;     // a LaunchKind
     uint8_t divides;  // 1: some step of the range has a kind that KIND_INFO counts as dividing
-    uint32_t rounds = 0;    // the three hint kinds only.  LAUNCH_LONGDIV: the division's trip count, the largest min(1024, n (kD - 1) + 256)
+    uint32_t rounds = 0;    // the hint kinds only.  LAUNCH_LONGDIV: the division's trip count, the largest min(1024, n (kD - 1) + 256)
                             // of the range's hints -- a dividend of kD limbs below 2^256 at bit offsets n j is below 2 to that power;
                             // LAUNCH_MODDIV: the same bound over the four operand lists of the range's hints (the reductions modulo P);
                             // LAUNCH_LONGDIV_WIDE: the largest min(8192, n (kD - 1) + 256) of the range's hints: a bound that sizes the
                             // wave's arrays, not a trip count
-    uint32_t inv_rounds = 0;// LAUNCH_MODDIV only: the inversion's trip count 2 L, L the largest min(512, n (kP - 1) + 256) of the range's hints:
+                            // LAUNCH_MODMULDIV: LAUNCH_MODDIV's bound over the six operand lists of the range's hints
+    uint32_t inv_rounds = 0;// LAUNCH_MODDIV and LAUNCH_MODMULDIV (where it is the trip count of the product's reduction as well):
+                            // the inversion's trip count 2 L, L the largest min(512, n (kP - 1) + 256) of the range's hints:
                             // every modulus of the range that is not stuck is below 2^L (solve_steps.cuh: modinv_odd proves the bound)
 };
 
@@ -552,11 +591,13 @@ inline bool sqrt_row(const std::vector<Unknown> &occ, const uint32_t nz[3], cons
 
 // The trip-count bounds of a hint launch over its steps (Launch::rounds, Launch::inv_rounds); a launch of any other kind keeps zero
 inline void hint_rounds(const Plan &p, Launch &l) {
-    if (l.kind != LAUNCH_LONGDIV && l.kind != LAUNCH_MODDIV && l.kind != LAUNCH_LONGDIV_WIDE) return;
+    if (l.kind != LAUNCH_LONGDIV && l.kind != LAUNCH_MODDIV && l.kind != LAUNCH_LONGDIV_WIDE && l.kind != LAUNCH_MODMULDIV) return;
     for (uint32_t t = l.lo; t < l.hi; ++t) {
         const Hint &h = p.hints[p.steps[t].cols_off];
-        if (l.kind == LAUNCH_MODDIV) {
+        if (l.kind == LAUNCH_MODDIV || l.kind == LAUNCH_MODMULDIV) {
             for (uint32_t k : h.k)
+                if (k) l.rounds = std::max(l.rounds, std::min(h.n * (k - 1) + 256, MODDIV_OPERAND_BITS));
+            for (uint32_t k : h.km)
                 if (k) l.rounds = std::max(l.rounds, std::min(h.n * (k - 1) + 256, MODDIV_OPERAND_BITS));
             const uint32_t kP = (uint32_t)(h.flags & HINT_MODULUS_LITERAL ? h.lit.size() / 4 : h.E.size());
             l.inv_rounds = std::max(l.inv_rounds, 2 * std::min(h.n * (kP - 1) + 256, MODDIV_MODULUS_BITS));
@@ -569,7 +610,7 @@ inline void hint_rounds(const Plan &p, Launch &l) {
 // The tail both builders share: p.steps (in ROW order, levels set) sorted by (level, kind), stable by row; level_ptr; the launch schedule.
 inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
     // counting sort by (level, kind); the row order inside a key is the order the steps come in
-    constexpr size_t K = NUM_WIDE_KINDS;
+    constexpr size_t K = NUM_MULDIV_KINDS;
     std::vector<uint32_t> start((size_t)max_level * K + 1, 0);
     for (const Step &s : p.steps) ++start[(size_t)(s.level - 1) * K + s.kind + 1];
     for (size_t i = 1; i < start.size(); ++i) start[i] += start[i - 1];
@@ -587,7 +628,7 @@ inline void finish_plan(Plan &p, uint32_t max_level, uint32_t wide_steps) {
     // divide, the square-root rows do); where they are narrow, consecutive levels are one chain, which divides if any kind in it does (a
     // chain of C-steps and indicators is a non-dividing one).  The other kinds come last and are launches of their own whatever the
     // level's width (a wave per block, not a lane): a chain run ends before them and a new one begins after them.  First the linear
-    // blocks, then the declared hints: the long divisions, the modular divisions, the wide long divisions
+    // blocks, then the declared hints: the long divisions, the modular divisions, the wide long divisions, the modular multiply-divides
     for (uint32_t l = 0; l < max_level; ++l) {
         const uint32_t *at = start.data() + (size_t)l * K;
         uint32_t walked = 0;   // the kinds of the chainable run
@@ -789,7 +830,7 @@ struct Planner {
         for (const std::vector<uint32_t> *in : {&h.D, &h.E})
             for (uint32_t col : *in) lv = level[col] > lv ? level[col] : lv;
         ++lv;
-        Step s{0, (uint32_t)(nr + h.index), h.q[0], h.op == HINT_MODDIV ? KIND_MODDIV : h.op == HINT_LONGDIV_WIDE ? KIND_LONGDIV_WIDE : KIND_LONGDIV, lv};
+        Step s{0, (uint32_t)(nr + h.index), h.q[0], h.op == HINT_MODDIV ? KIND_MODDIV : h.op == HINT_LONGDIV_WIDE ? KIND_LONGDIV_WIDE : h.op == HINT_MODMULDIV ? KIND_MODMULDIV : KIND_LONGDIV, lv};
         s.cols_off = (uint32_t)p.hints.size();
         p.hints.push_back(h);
         p.steps.push_back(s);
@@ -1174,8 +1215,10 @@ inline bool schedule_any_order(Planner &st, uint64_t nr, uint64_t ncols, std::st
 //   HINT_MODDIV, n, kz, kNp, kNm, kDp, kDm, kP, flags, kz output columns, kNp + kNm numerator columns, kDp + kDm denominator columns,
 //   then kP modulus columns -- or, with HINT_MODULUS_LITERAL (flags bit 0), kP limb values of four words each
 //   HINT_LONGDIV_WIDE, n, kq, kr, kD, kE, flags, and what follows HINT_LONGDIV's head: the same record under the wide limits
+//   HINT_MODMULDIV, n, kz, kA, kB, kNp, kNm, kDp, kDm, kP, flags, cN, cD, kz output columns, kA + kB factor columns, kNp + kNm addend
+//   columns, kDp + kDm denominator columns, then kP modulus columns -- or, with HINT_MODULUS_LITERAL, kP limb values of four words each
 // in any mixture; both opcodes share the index h and the set of output columns.  Opcode 2 is reserved and refused like any unknown one.
-// So does the third opcode; 4 is refused as unknown as well.
+// So does the third opcode; 4 is refused as unknown as well.  So does the fourth; 6 and 8 are refused as unknown as well.
 // -> the hints in `out` and an empty string, or what is refused, "hint h: " + the condition, and `out` empty.  `modulus`: r, four words.
 inline std::string decode_hints(const uint64_t *desc, size_t n_words, uint64_t ncols, const uint64_t *modulus, std::vector<Hint> &out) {
     out.clear();
@@ -1186,14 +1229,35 @@ inline std::string decode_hints(const uint64_t *desc, size_t n_words, uint64_t n
         const std::string here = "hint " + std::to_string(out.size()) + ": ";
         Hint h;
         h.index = (uint32_t)out.size();
-        if (desc[at] != HINT_LONGDIV && desc[at] != HINT_MODDIV && desc[at] != HINT_LONGDIV_WIDE) { why = here + "unknown opcode " + std::to_string(desc[at]); break; }
+        if (desc[at] != HINT_LONGDIV && desc[at] != HINT_MODDIV && desc[at] != HINT_LONGDIV_WIDE && desc[at] != HINT_MODMULDIV) { why = here + "unknown opcode " + std::to_string(desc[at]); break; }
         const bool moddiv = desc[at] == HINT_MODDIV;
-        const size_t head = moddiv ? 9 : 7;
+        const bool muldiv = desc[at] == HINT_MODMULDIV;
+        const size_t head = muldiv ? 13 : moddiv ? 9 : 7;
         if (n_words - at < head) { why = here + "the record is truncated"; break; }
-        const uint64_t n = desc[at + 1], flags = desc[at + head - 1];
+        const uint64_t n = desc[at + 1], flags = desc[at + (muldiv ? 10 : head - 1)];
         if (n < 1 || n > HINT_MAX_N) { why = here + "n = " + std::to_string(n) + " is outside 1..128"; break; }
         uint64_t counts[4], kE;     // the lengths of q, rem, D, E; kE: the divisor's or the modulus' limbs, in columns or literal
-        if (moddiv) {
+        if (muldiv) {
+            const uint64_t kz = desc[at + 2], kP = desc[at + 9], *k = desc + at + 3, cN = desc[at + 11], cD = desc[at + 12];   // k: kA, kB, kNp, kNm, kDp, kDm
+            static const char *const names[MODMULDIV_LISTS] = {"kA", "kB", "kNp", "kNm", "kDp", "kDm"};
+            if (kz < 1 || kz > MODDIV_MAX_KZ) { why = here + "kz = " + std::to_string(kz) + " is outside 1..16"; break; }
+            for (uint32_t i = 0; i < MODMULDIV_LISTS && why.empty(); ++i)
+                if (k[i] > MODDIV_MAX_K || (i < 2 && k[i] < 1)) why = here + names[i] + " = " + std::to_string(k[i]) + " is outside " + (i < 2 ? "1" : "0") + "..32";
+            if (!why.empty()) break;
+            if (k[5] > 0 && k[4] == 0) { why = here + "kDm = " + std::to_string(k[5]) + " with kDp = 0"; break; }
+            if (kP < 1 || kP > MODDIV_MAX_KP) { why = here + "kP = " + std::to_string(kP) + " is outside 1..16"; break; }
+            if (flags & ~HINT_MODULUS_LITERAL) { why = here + "unknown flags " + std::to_string(flags); break; }
+            for (uint32_t i = 0; i < MODMULDIV_LISTS && why.empty(); ++i)
+                if (k[i] && n * (k[i] - 1) >= MODDIV_OPERAND_BITS) why = here + "n (" + names[i] + " - 1) = " + std::to_string(n * (k[i] - 1)) + " is 1024 or more";
+            if (!why.empty()) break;
+            if (n * (kP - 1) >= MODDIV_MODULUS_BITS) { why = here + "n (kP - 1) = " + std::to_string(n * (kP - 1)) + " is 512 or more"; break; }
+            if (cN < 1 || cN > MODMULDIV_MAX_C) { why = here + "cN = " + std::to_string(cN) + " is outside 1..4294967295"; break; }
+            if (cD < 1 || cD > MODMULDIV_MAX_C) { why = here + "cD = " + std::to_string(cD) + " is outside 1..4294967295"; break; }
+            h.op = (uint32_t)HINT_MODMULDIV;
+            counts[0] = kz, counts[1] = 0, counts[2] = 0, kE = kP;
+            for (uint32_t i = 0; i < MODMULDIV_LISTS; ++i) h.km[i] = (uint32_t)k[i], counts[2] += k[i];
+            h.c[0] = (uint32_t)cN, h.c[1] = (uint32_t)cD;
+        } else if (moddiv) {
             const uint64_t kz = desc[at + 2], kP = desc[at + 7], *k = desc + at + 3;   // k: kNp, kNm, kDp, kDm
             static const char *const names[4] = {"kNp", "kNm", "kDp", "kDm"};
             if (kz < 1 || kz > MODDIV_MAX_KZ) { why = here + "kz = " + std::to_string(kz) + " is outside 1..16"; break; }

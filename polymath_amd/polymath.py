@@ -610,7 +610,8 @@ class Polymath:
         """Declare the key's hints (pm_pk_set_hints): values that the circuit's witness generator computes and no row determines.
         hints: a list of dicts {"n", "q", "rem", "D", and "E" or "literal"} (a long division), dicts {"op": "moddiv", "n", "z", "Dp", "P"
         or "literal", and optionally "Np", "Nm", "Dm"} (a modular division), a long division's dict with "op": "longdiv_wide" (the wide
-        long division: up to 8192 / 4096 bits) or tuples (api.encode_hints), e.g. what a generator's
+        long division: up to 8192 / 4096 bits), dicts {"op": "modmuldiv", "n", "z", "A", "B", "P" or "literal", and optionally "Np", "Nm",
+        "Dp", "Dm", "cN", "cD"} (a modular multiply-divide: the slope of a doubling) or tuples (api.encode_hints), e.g. what a generator's
         hints(m0) returns; an empty list clears the declaration.  A refusal raises with the library's message; the key is unchanged."""
         self.ctx.check(pk.set_hints(hints))
 

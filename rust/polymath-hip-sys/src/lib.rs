@@ -107,6 +107,8 @@ pub const PM_HINT_MODDIV: u64 = 3;
 pub const PM_HINT_MODULUS_LITERAL: u64 = 1;
 // pm_hint_op_wide: the opcode of a declared wide long division (4 is refused as unknown); its flag is PM_HINT_DIVISOR_LITERAL
 pub const PM_HINT_LONGDIV_WIDE: u64 = 5;
+// pm_hint_op_muldiv: the opcode of a declared modular multiply-divide (6 is refused as unknown); its flag is PM_HINT_MODULUS_LITERAL
+pub const PM_HINT_MODMULDIV: u64 = 7;
 // the three markers of PM_ASSIGNMENT_SOLVE (little-endian words of one Fr, all >= r on both curves): unknown; unknown, and the Euclidean
 // quotient of its division row; unknown, and the indicator of its guard row
 pub const PM_UNKNOWN_WORDS: [u64; 4] = [u64::MAX, u64::MAX, u64::MAX, u64::MAX];

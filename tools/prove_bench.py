@@ -42,6 +42,17 @@ rem with Python's divmod).  UNMEASURED: no run of it is recorded.
                                                                                  (k + 5) G and 2 G; ecadd:STEPS for others
 on circuits that divide in a foreign field (a declared modular division per quotient or slope, then the product's block and a
 declared long division per reduction, with their decompositions and carries; route (a) synthesises with Python's pow and divmod).
+  python tools/prove_bench.py --circuit modmuldiv --batch 256 --reps 5 --solve   LimbModMulDiv, 16 multiply-divides (all six lists, cN = 3,
+                                                                                 cD = 2) modulo secp256k1's prime on 4 limbs of 64 bits;
+                                                                                 modmuldiv:COUNT:N:LIMBS for others
+  python tools/prove_bench.py --circuit ecdouble --batch 256 --reps 5 --solve    EcDoubleAddChain, 4 times R <- 2 R + G on secp256k1 from
+                                                                                 (k + 5) G; ecdouble:STEPS for others
+  python tools/prove_bench.py --circuit ecdsa:toy --batch 16 --reps 3 --solve    EcdsaVerify on the tests' toy curve (p = 2^22 - 3, 22 scalar
+                                                                                 bits, a key of 2^15); --circuit ecdsa is secp256k1 on 4 limbs of
+                                                                                 64 bits: about 1.7 M rows, a key of 2^21, minutes of Python
+                                                                                 synthesis per assignment
+on circuits whose slopes have a product for their numerator (a declared modular multiply-divide per tangent; ECDSA verification is
+every hint opcode but the wide one, decompositions, selections and blocks in one system).  UNMEASURED: no run of them is recorded.
   python tools/prove_bench.py --circuit rsa --batch 64 --reps 5 --solve          RsaVerify, s^65537 mod a 2048-bit modulus on 32 limbs
                                                                                  of 64 bits; rsa:BITS:N:LIMBS for others (rsa:2048:121:17)
   python tools/prove_bench.py --circuit widediv --batch 256 --reps 5 --solve     LimbDivision, 16 wide divisions of 63 by 32 limbs of
@@ -65,7 +76,7 @@ from polymath_amd import circuits as PC
 from polymath_amd.polymath import Polymath
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants), bench:NC (BenchCircuit, NC constraints), arx[:WIDTH:ROUNDS] (ArxDemo), matchcount[:N:FORM] (MatchCount), divrem[:N:BITS] (DivRem), tablewalk[:WIDTH:STEPS] (TableWalk), decompress[:POINTS] (EdwardsDecompress), limbproduct[:COUNT:LIMBS] (LimbProduct), modmul[:COUNT:N:LIMBS] (LimbModMul), moddiv[:COUNT:N:LIMBS] (LimbModDiv), ecadd[:STEPS] (EcAddChain), rsa[:BITS:N:LIMBS] (RsaVerify) or widediv[:COUNT:N:KD:KE] (LimbDivision)")
+ap.add_argument("--circuit", default="mimc322", help="mimcK (K round constants), bench:NC (BenchCircuit, NC constraints), arx[:WIDTH:ROUNDS] (ArxDemo), matchcount[:N:FORM] (MatchCount), divrem[:N:BITS] (DivRem), tablewalk[:WIDTH:STEPS] (TableWalk), decompress[:POINTS] (EdwardsDecompress), limbproduct[:COUNT:LIMBS] (LimbProduct), modmul[:COUNT:N:LIMBS] (LimbModMul), moddiv[:COUNT:N:LIMBS] (LimbModDiv), ecadd[:STEPS] (EcAddChain), rsa[:BITS:N:LIMBS] (RsaVerify), widediv[:COUNT:N:KD:KE] (LimbDivision), modmuldiv[:COUNT:N:LIMBS] (LimbModMulDiv), ecdouble[:STEPS] (EcDoubleAddChain) or ecdsa[:toy] (EcdsaVerify)")
 ap.add_argument("--batch", type=int, default=16)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--curve", default="bls12_381")
@@ -75,8 +86,8 @@ ap.add_argument("--glue", choices=("host", "device"), default="host", help="devi
 ap.add_argument("--solve", action="store_true", help="host-synthesised assignments against partial assignments solved on the GPU")
 ap.add_argument("--reorder", default=None, metavar="reverse|SEED", help="with --solve: the circuit's rows stored reversed or shuffled by SEED (unmeasured)")
 a = ap.parse_args()
-if a.solve and not a.circuit.startswith(("mimc", "arx", "matchcount", "divrem", "tablewalk", "decompress", "limbproduct", "modmul", "moddiv", "ecadd", "rsa", "widediv")):
-    ap.error("--solve needs a mimcK, an arx, a matchcount, a divrem, a tablewalk, a decompress, a limbproduct, a modmul, a moddiv, an ecadd, an rsa or a widediv circuit")
+if a.solve and not a.circuit.startswith(("mimc", "arx", "matchcount", "divrem", "tablewalk", "decompress", "limbproduct", "modmul", "moddiv", "ecadd", "rsa", "widediv", "ecdouble", "ecdsa")):
+    ap.error("--solve needs a mimcK, an arx, a matchcount, a divrem, a tablewalk, a decompress, a limbproduct, a modmul, a moddiv, a modmuldiv, an ecadd, an ecdouble, an ecdsa, an rsa or a widediv circuit")
 if a.reorder is not None and not a.solve:
     ap.error("--reorder goes with --solve")
 pm = Polymath(a.curve, a.transcript, device=0)
@@ -121,6 +132,24 @@ elif a.circuit.startswith("limbproduct"):
     n_products, n_limbs = (int(v) for v in a.circuit.split(":")[1:3]) if ":" in a.circuit else (64, 8)
     make = lambda: PC.LimbProduct(PC.limb_products(r, n_products, n_limbs, g.next_u64()))
     again = lambda c: PC.LimbProduct(c.products, c.first)
+    partial_of = lambda c: c.partial(r)
+elif a.circuit.startswith("modmuldiv"):
+    n_divs, limb_bits, n_limbs = (int(v) for v in a.circuit.split(":")[1:4]) if ":" in a.circuit else (16, 64, 4)
+    foreign = (1 << (limb_bits * n_limbs)) - 2 ** 32 - 977 if limb_bits * n_limbs == 256 else (1 << (limb_bits * n_limbs - 3)) - 1     # as for modmul; need not be a prime
+    make = lambda: PC.LimbModMulDiv(PC.modmuldiv_cases(foreign, n_divs, g.next_u64(), cD=2), foreign, limb_bits, n_limbs, 3, 2)
+    again = lambda c: PC.LimbModMulDiv(c.cases, c.modulus, c.n, c.limbs, c.cN, c.cD, c.decompose, c.operand_bits)
+    partial_of = lambda c: c.partial(r)
+elif a.circuit.startswith("ecdouble"):
+    ec_steps = int(a.circuit.split(":")[1]) if ":" in a.circuit else 4
+    secp, _, _, G1 = PC.SECP256K1
+    make = lambda: PC.EcDoubleAddChain(PC.affine_mul(secp, 5 + g.next_u64() % 32, G1), G1, secp, 64, 4, ec_steps)      # the generator asserts that no step is exceptional
+    again = lambda c: PC.EcDoubleAddChain(c.point, c.addend, c.modulus, c.n, c.limbs, c.steps, c.decompose)
+    partial_of = lambda c: c.partial(r)
+elif a.circuit.startswith("ecdsa"):
+    ec_curve, (limb_bits, n_limbs) = (PC.TOY_CURVE, (11, 2)) if a.circuit.endswith(":toy") else (PC.SECP256K1, (64, 4))
+    signatures = iter(PC.ecdsa_cases(ec_curve, min(a.batch, 32), g.next_u64()))
+    make = lambda: PC.EcdsaVerify(ec_curve, *next(signatures), limb_bits, n_limbs)
+    again = lambda c: PC.EcdsaVerify(c.curve, c.Q, c.h, c.r_sig, c.s, c.n, c.limbs, c.start, c.decompose)
     partial_of = lambda c: c.partial(r)
 elif a.circuit.startswith("modmul"):
     n_muls, limb_bits, n_limbs = (int(v) for v in a.circuit.split(":")[1:4]) if ":" in a.circuit else (16, 64, 4)
@@ -177,7 +206,7 @@ circuits = [make() for _ in range(distinct)]
 t0 = time.time()
 pk = pm.setup(stored(circuits[0]), g.fr(r), g.fr(r))
 setup_s = time.time() - t0
-if a.circuit.startswith(("modmul", "moddiv", "ecadd", "rsa", "widediv")):
+if a.circuit.startswith(("modmul", "moddiv", "ecadd", "rsa", "widediv", "ecdouble", "ecdsa")):
     pm.set_hints(pk, circuits[0].hints(2))       # the long and the modular divisions are part of the circuit: declared once, with the key
 rows = []
 for c in circuits:
